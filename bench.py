@@ -140,7 +140,27 @@ def parse():
     ap.add_argument("--c5-edges", type=int, default=20000)
     ap.add_argument("--c5-chunk", type=int, default=50, help="new vertices per round")
     ap.add_argument("--c5-rounds", type=int, default=0, help="rounds to run (0 = all: vertices / chunk)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (poses, chi2 per iteration) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, suffix, poses, chi2, budget):
+    """The last timed step's results as out_dir/poses<suffix>.npy (V x 3) and chi2<suffix>.npy (one per iteration and the
+    initial one), float64.  Poses that do not fit the byte budget beside chi2 are cut to a fixed, seeded sample of rows (the
+    same rows in every run), so that two builds can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    keep = (budget - 4096 - chi2.nbytes) // poses[0].nbytes          # (4096: the two .npy headers)
+    if keep < len(poses):
+        poses = poses[np.sort(np.random.default_rng(12345).choice(len(poses), size=keep, replace=False))]
+    np.save(os.path.join(out_dir, f"poses{suffix}.npy"), poses.astype(np.float64))
+    np.save(os.path.join(out_dir, f"chi2{suffix}.npy"), chi2.astype(np.float64))
 
 
 def free_port():
@@ -682,6 +702,8 @@ def main():
         elapsed = float(t.item())
     p_cold = d_p.clone()
     chi_cold = chi.copy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, f"_rank{rank}" if world > 1 else "", p_cold.cpu().numpy(), chi_cold, DUMP_LIMIT_BYTES // world)
 
     # ---- the same step with the analysis cache on (second and later solves of a key frame on an unchanged graph)
     ctx.set_symbolic_cache(True)

@@ -1,15 +1,13 @@
 """The helper pool next to a neighbour that sits on its cores: busy processes pinned to every CPU of the pool's cache group
 (what another process of this library that started on the same CPU does to it); cold optimize(10) wall / analysis time before,
 with the neighbour, and what the pool did about it (cgmr_host_threads_info: home CPU, moves).  CGMR_HOST_MOVE=0: it stays."""
-import os, sys, time, multiprocessing as mp
+import os, subprocess, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from cg_mrslam_amd import Context, synth
 
-def spin(cpus, seconds):
-    os.sched_setaffinity(0, cpus)
-    e = time.time() + seconds
-    while time.time() < e: pass
+# the neighbours are fresh interpreters, not forks: a fork of this process would hold its open GPU device files
+SPIN = "import os, sys, time\nos.sched_setaffinity(0, {int(sys.argv[1])})\ne = time.time() + float(sys.argv[2])\nwhile time.time() < e: pass\n"
 
 def run(ctx, args, n=40):
     p, p0, g, m, i = args
@@ -40,11 +38,10 @@ if __name__ == "__main__":
     for part in grp.split(","):
         a, _, b = part.partition("-")
         cpus.update(range(int(a), int(b or a) + 1))
-    hogs = [mp.Process(target=spin, args=({c}, 25.0)) for c in sorted(cpus)]
-    [h.start() for h in hogs]
+    hogs = [subprocess.Popen([sys.executable, "-c", SPIN, str(c), "25"]) for c in sorted(cpus)]
     time.sleep(1.0)
     med, series = run(ctx, args)
     print("with %d busy processes on CPUs %s:" % (len(hogs), grp))
     print("  first 8 analyses (ms):", " ".join("%.1f" % v for v in series[:8]))
     print("  median of 40:    wall %.2f ms, analysis %.2f ms" % tuple(med), ctx.host_threads_info())
-    [h.terminate() for h in hogs]; [h.join() for h in hogs]
+    [h.terminate() for h in hogs]; [h.wait() for h in hogs]

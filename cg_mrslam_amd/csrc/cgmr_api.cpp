@@ -880,23 +880,50 @@ int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const 
   // for the condensed graph the iteration is completed first: the factor stays valid, the poses move on
   GnEdges Ed;
   Ed.meas_a = (const double*)(d + o_m); Ed.info_a = (const double*)(d + o_i); Ed.nA = nE; Ed.n_active = nE;
-  gn_pass(ctx, dp, Ed, 0, false, mode == 2, /*write_l11c=*/true);
-  launch_marginals(st, D, nq, (const int32_t*)(d + o_qc), m, (double*)(d + o_Y), (double*)(d + o_U), (double*)(d + o_part),
-                   (double*)(d + o_G), (double*)(d + o_cov), chunk, nchunk, (uint8_t*)(d + o_live));
-  if (mode == 2)
-    launch_label(st, nq, (const int32_t*)(d + o_qv), gauge, dp, (const double*)(d + o_cov), (double*)(d + o_est),
-                 (double*)(d + o_io), (int*)(d + o_fl));
   int status4[4] = {0, 0, 0, 0};
   std::vector<double> cov(9 * (size_t)nq);
-  HIP_TRY(ctx, hipMemcpyAsync(cov.data(), d + o_cov, 72 * (size_t)nq, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
-  if (mode == 2) {
-    HIP_TRY(ctx, hipMemcpyAsync(est_out, d + o_est, 24 * (size_t)nq, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(info_out, d + o_io, 48 * (size_t)nq, hipMemcpyDeviceToHost, st));
+  auto run_pass = [&]() -> int {
+    gn_pass(ctx, dp, Ed, 0, false, mode == 2, /*write_l11c=*/true);
+    launch_marginals(st, D, nq, (const int32_t*)(d + o_qc), m, (double*)(d + o_Y), (double*)(d + o_U), (double*)(d + o_part),
+                     (double*)(d + o_G), (double*)(d + o_cov), chunk, nchunk, (uint8_t*)(d + o_live));
+    if (mode == 2)
+      launch_label(st, nq, (const int32_t*)(d + o_qv), gauge, dp, (const double*)(d + o_cov), (double*)(d + o_est),
+                   (double*)(d + o_io), (int*)(d + o_fl));
+    HIP_TRY(ctx, hipMemcpyAsync(cov.data(), d + o_cov, 72 * (size_t)nq, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
+    if (mode == 2) {
+      HIP_TRY(ctx, hipMemcpyAsync(est_out, d + o_est, 24 * (size_t)nq, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, hipMemcpyAsync(info_out, d + o_io, 48 * (size_t)nq, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+  };
+  rc = run_pass();
+  if (rc) return rc;
+  if (status4[2] != 0) {
+    // A bounded wait ran out (status[2]): a hand-off between workgroups of a merged level launch (the forward pass: factor
+    // work items -> update tiles) or of the chained backward solve that never arrived -- not a numerical failure.  As gn_run
+    // does, the pass is repeated from the same poses with one launch per kernel and level (no in-kernel waits).  The cached
+    // structure keeps only the forward merges that are certainly resident from now on; the chained backward solve (mode 2)
+    // stays, as in gn_run: its waits are bounded as well, and a later time-out there falls back the same way.
+    ctx->gn_timeouts++;
+    ctx->fwd_merge_any = false;
+    choose_fwd_merge(D, ctx->side_used ? 2 : 1, false, false);
+    const std::vector<uint8_t> merge_keep = D.h_level_merge;
+    const int chain_was = D.bwd_chain_level;
+    D.h_level_merge.assign(D.nlevels, 0);
+    D.bwd_chain_level = D.nlevels;
+    const int fresh[4] = {0, 0, 0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(D.status, fresh, sizeof fresh, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dp, work.data(), 24 * (size_t)nV, hipMemcpyHostToDevice, st));
+    rc = run_pass();
+    D.h_level_merge = merge_keep;
+    D.bwd_chain_level = chain_was;
+    if (rc) return rc;
+    if (status4[2] != 0)
+      return set_err(ctx, CGMR_E_TIMEOUT, "marginals: a bounded device-side wait (forward hand-off or chained backward solve) ran out twice");
   }
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  HIP_TRY(ctx, hipGetLastError());
-  if (status4[2] != 0) { ctx->gn_timeouts++; ctx->fwd_merge_any = false; return set_err(ctx, CGMR_E_TIMEOUT, "backward solve: a bounded device-side wait ran out"); }
   if (status4[0] != 0) return set_err(ctx, CGMR_E_CHOLESKY_BASE, "Cholesky failed while computing marginals");
   if (mode == 2) {
     for (int k = 0; k < nq; k++) to_out[k] = q[k];

@@ -1,0 +1,94 @@
+"""The graphs the backward-error and marginal checks run on (tests/test_reference_cpu.py, tests/test_reference_gpu.py), one
+per branch of the supernodal factorisation they are there to reach.  TEST INFRASTRUCTURE ONLY."""
+import numpy as np
+
+from cg_mrslam_amd import synth
+
+KEYS = ("poses", "fixed", "edge_from", "edge_to", "meas", "info")
+
+
+def args(g):
+    return tuple(g[k] for k in KEYS)
+
+
+def _rotated(g, phi):
+    """The same graph turned about the origin by phi: the measurements are relative and stay, every heading moves."""
+    g = dict(g)
+    rot = np.array([[0.0, 0.0, phi]])
+    g["poses"] = synth.se2_compose(np.repeat(rot, len(g["poses"]), 0), g["poses"])
+    return g
+
+
+def wrap_graph():
+    """Headings near +-pi: C2-recipe headings are multiples of pi/2 plus odometry drift, turned so that the most common one
+    lands on pi -- many edges then join a vertex just below +pi to one just above -pi."""
+    g = synth.make_pose_graph(800, 2600, seed=6)
+    q = np.round(g["poses"][:, 2] / (np.pi / 2)).astype(int) % 4
+    mode = np.bincount(q, minlength=4).argmax()
+    return _rotated(g, np.pi - mode * np.pi / 2 + 1e-3)
+
+
+def straddling_edges(g):
+    th = g["poses"][:, 2]
+    a, b = th[g["edge_from"]], th[g["edge_to"]]
+    return int(np.sum((np.abs(a) > 3.0) & (np.abs(b) > 3.0) & (np.sign(a) != np.sign(b))))
+
+
+def ill_conditioned_graph():
+    """Anisotropic information, eigenvalues drawn log-uniformly over 1e-2 .. 1e6, axes turned at random: an ill-conditioned
+    H where the order of summation shows."""
+    g = dict(synth.make_pose_graph(600, 2000, seed=31))
+    rng = np.random.default_rng(31)
+    E = len(g["edge_from"])
+    iu = np.empty((E, 6))
+    for k in range(E):
+        Q, _ = np.linalg.qr(rng.standard_normal((3, 3)))
+        O = Q @ np.diag(10.0 ** rng.uniform(-2, 6, 3)) @ Q.T
+        iu[k] = [O[0, 0], O[0, 1], O[0, 2], O[1, 1], O[1, 2], O[2, 2]]
+    g["info"] = iu
+    return g
+
+
+def fixed_dup_isolated_graph():
+    """Three fixed vertices, 25 duplicated edges (g2o sums their quadratic forms), two vertices no edge touches."""
+    g = synth.make_pose_graph(120, 300, seed=7)
+    fixed = g["fixed"].copy()
+    fixed[[40, 119]] = 1
+    return dict(poses=np.concatenate([g["poses"], [[9.0, 9, 1], [-3, 2, 0.5]]]),
+                fixed=np.concatenate([fixed, [0, 0]]).astype(np.uint8),
+                edge_from=np.concatenate([g["edge_from"], g["edge_from"][:25]]).astype(np.int32),
+                edge_to=np.concatenate([g["edge_to"], g["edge_to"][:25]]).astype(np.int32),
+                meas=np.concatenate([g["meas"], g["meas"][:25] + 0.01]),
+                info=np.concatenate([g["info"], g["info"][:25]]))
+
+
+# name -> (builder, the branch it is there for)
+CASES = {
+    "v2e1": (lambda: synth.make_pose_graph(2, 1, seed=1), "top block only"),
+    "v5e4": (lambda: synth.make_pose_graph(5, 4, seed=2), "top block only"),
+    "chain3000": (lambda: synth.make_pose_graph(3000, 2999, seed=3), "fronts with 1-2 border poses, partial 48-column panels"),
+    "pg500": (lambda: synth.make_pose_graph(500, 1500, seed=4), "merged levels, chained backward solve"),
+    "pg2500": (lambda: synth.make_pose_graph(2500, 9000, seed=5), "merged levels, chained backward solve"),
+    "pg9000": (lambda: synth.make_pose_graph(9000, 30000, seed=11), "levels not resident at once"),
+    "c2": (lambda: synth.make_pose_graph(10000, 40000, seed=12345), "C2: levels not resident at once"),
+    "hub40": (lambda: synth.make_hub_graph(40, 30, 1), "> 8 children: streamed path"),
+    "hub100": (lambda: synth.make_hub_graph(100, 12, 2), "> 64 children"),
+    "lat40": (lambda: synth.make_lattice_graph(40), "borders in several work items"),
+    "lat80": (lambda: synth.make_lattice_graph(80), "borders in several work items"),
+    "lat74": (lambda: synth.make_lattice_graph(74), "top block within one pose of kTopMaxCols"),
+    "lat120": (lambda: synth.make_lattice_graph(120), "borders in several work items"),
+    "fixed_dup_iso": (fixed_dup_isolated_graph, "inactive vertices, summed duplicates"),
+    "wrap": (wrap_graph, "angle wrap in linearisation and update"),
+    "illcond": (ill_conditioned_graph, "ill-conditioned H"),
+}
+
+# Largest componentwise backward error (ref_numpy.step_backward_error) a Gauss-Newton step may show: ten times the largest
+# that the C oracle and SuperLU show on CASES from the initial guess, the 3rd and the 8th iterate (11.1 u, u = 2^-53: the first
+# steps of C2, pg9000 and pg2500; every other step shows 0-6 u), rounded up.  tests/test_reference_cpu.py re-measures it.
+OMEGA_MAX = 120 * np.finfo(np.float64).eps / 2
+
+# condensed edge means: est is read off the poses after one step from the spanning-tree guess, so two correct solvers differ
+# by the step's forward error, cond(H) times rounding: 3.7e-12 m between the oracle and SuperLU on a 300-vertex graph, 2.0e-9 m
+# between the GPU and SuperLU on the 1500/5000 graph (cond_1(H) 3.6e10 at the guess, by onenormest), 3.1e-8 m on the
+# 2500/9000 graph after a time-out (one launch per kernel and level); ten times the largest
+EST_ATOL = 3e-7

@@ -154,6 +154,19 @@ class Context:
         self._check(rc)
         return cov
 
+    def marginals_all(self, poses, fixed, ef, et, meas, info, cross=False):
+        """3x3 blocks of H^-1 (H linearised at ``poses``) of every vertex: ``cov[nV, 3, 3]``; with ``cross=True``
+        ``(cov, cross[nE, 3, 3])``, cross[e] = the block (from[e], to[e]).  Selected inversion (cgmr_marginals_all)."""
+        poses, ef, et, meas, info = self._graph_args(poses, ef, et, meas, info)
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        cov = np.zeros((poses.shape[0], 3, 3))
+        cr = np.zeros((len(ef), 3, 3)) if cross else None
+        rc = self.lib.cgmr_marginals_all(self.h, C.c_int(poses.shape[0]), _ptr(poses), _ptr(fixed), C.c_int(len(ef)),
+                                         _ptr(ef), _ptr(et), _ptr(meas), _ptr(info), _ptr(cov),
+                                         _ptr(cr))
+        self._check(rc)
+        return (cov, cr) if cross else cov
+
     def covariance_estimate(self, poses, ef, et, meas, info, gauge, query):
         """CovarianceEstimator::compute + getCovariance (src/slam/graph_manipulator.cpp:128-157)."""
         poses, ef, et, meas, info = self._graph_args(poses, ef, et, meas, info)

@@ -824,6 +824,40 @@ void initial_guess_host(int nV, double* poses, const uint8_t* fixed, int nE, con
   }
 }
 
+// The pass of the marginals entry points: run_pass() queues gn_pass(.., write_l11c) and what reads the factor, reads the
+// status words back into status4 and synchronises.  The poses at dp are `work` (nV of them) when it starts.
+template <typename RunPass>
+int marginal_pass(cgmr_ctx* ctx, double* dp, const double* work, int nV, int* status4, RunPass&& run_pass) {
+  GnDevice& D = ctx->gn;
+  hipStream_t st = ctx->stream;
+  int rc = run_pass();
+  if (rc) return rc;
+  if (status4[2] != 0) {
+    // A bounded wait ran out (status[2]): a hand-off between workgroups of a merged level launch (the forward pass: factor
+    // work items -> update tiles) or of the chained backward solve that never arrived -- not a numerical failure.  As gn_run
+    // does, the pass is repeated from the same poses with one launch per kernel and level (no in-kernel waits).  The cached
+    // structure keeps only the forward merges that are certainly resident from now on; the chained backward solve (mode 2)
+    // stays, as in gn_run: its waits are bounded as well, and a later time-out there falls back the same way.
+    ctx->gn_timeouts++;
+    ctx->fwd_merge_any = false;
+    choose_fwd_merge(D, ctx->side_used ? 2 : 1, false, false);
+    const std::vector<uint8_t> merge_keep = D.h_level_merge;
+    const int chain_was = D.bwd_chain_level;
+    D.h_level_merge.assign(D.nlevels, 0);
+    D.bwd_chain_level = D.nlevels;
+    const int fresh[4] = {0, 0, 0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(D.status, fresh, sizeof fresh, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dp, work, 24 * (size_t)nV, hipMemcpyHostToDevice, st));
+    rc = run_pass();
+    D.h_level_merge = merge_keep;
+    D.bwd_chain_level = chain_was;
+    if (rc) return rc;
+    if (status4[2] != 0)
+      return set_err(ctx, CGMR_E_TIMEOUT, "marginals: a bounded device-side wait (forward hand-off or chained backward solve) ran out twice");
+  }
+  return 0;
+}
+
 // Shared driver of cgmr_marginals / cgmr_covariance_estimate / cgmr_condense (host pointers).
 //   mode 0: marginals at `poses` with `fixed`;  mode 1: covariance estimate (gauge);  mode 2: condense (gauge)
 int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uint8_t* fixed_in, int nE,
@@ -899,31 +933,8 @@ int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const 
     HIP_TRY(ctx, hipGetLastError());
     return 0;
   };
-  rc = run_pass();
+  rc = marginal_pass(ctx, dp, work.data(), nV, status4, run_pass);
   if (rc) return rc;
-  if (status4[2] != 0) {
-    // A bounded wait ran out (status[2]): a hand-off between workgroups of a merged level launch (the forward pass: factor
-    // work items -> update tiles) or of the chained backward solve that never arrived -- not a numerical failure.  As gn_run
-    // does, the pass is repeated from the same poses with one launch per kernel and level (no in-kernel waits).  The cached
-    // structure keeps only the forward merges that are certainly resident from now on; the chained backward solve (mode 2)
-    // stays, as in gn_run: its waits are bounded as well, and a later time-out there falls back the same way.
-    ctx->gn_timeouts++;
-    ctx->fwd_merge_any = false;
-    choose_fwd_merge(D, ctx->side_used ? 2 : 1, false, false);
-    const std::vector<uint8_t> merge_keep = D.h_level_merge;
-    const int chain_was = D.bwd_chain_level;
-    D.h_level_merge.assign(D.nlevels, 0);
-    D.bwd_chain_level = D.nlevels;
-    const int fresh[4] = {0, 0, 0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(D.status, fresh, sizeof fresh, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(dp, work.data(), 24 * (size_t)nV, hipMemcpyHostToDevice, st));
-    rc = run_pass();
-    D.h_level_merge = merge_keep;
-    D.bwd_chain_level = chain_was;
-    if (rc) return rc;
-    if (status4[2] != 0)
-      return set_err(ctx, CGMR_E_TIMEOUT, "marginals: a bounded device-side wait (forward hand-off or chained backward solve) ran out twice");
-  }
   if (status4[0] != 0) return set_err(ctx, CGMR_E_CHOLESKY_BASE, "Cholesky failed while computing marginals");
   if (mode == 2) {
     for (int k = 0; k < nq; k++) to_out[k] = q[k];
@@ -936,13 +947,99 @@ int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const 
   return CGMR_OK;
 }
 
+// cgmr_marginals_all: Sigma of every front by selected inversion of the factor (selinv_kernels.hip), then the diagonal block
+// of every vertex and the block of every edge.  The same pass as marginal_driver's mode 0 (gn_pass at `poses` with `fixed`).
+int marginals_all_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                         const int32_t* et, const double* meas, const double* info, double* cov_out, double* cross_out) {
+  if (nV <= 0 || nE < 0 || !poses || !cov_out || (nE > 0 && (!ef || !et || !meas || !info)))
+    return set_err(ctx, CGMR_E_INVALID, "marginals: null or negative argument");
+  if (!fixed) return set_err(ctx, CGMR_E_INVALID, "fixed flags missing");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<double> work(poses, poses + 3 * (size_t)nV);             // the caller's poses stay untouched
+  memset(cov_out, 0, 72 * (size_t)nV);
+  if (cross_out) memset(cross_out, 0, 72 * (size_t)nE);
+  Symbolic& S = ctx->sym;
+  int rc = prepare_structure(ctx, nV, nE, ef, et, 1);
+  if (rc) return rc;
+  rc = prepare_pass(ctx, fixed, nE, ef, et, nE, 0, 1);
+  if (rc) return rc;
+  GnDevice& D = ctx->gn;
+  hipStream_t st = ctx->stream;
+  if (D.nf == 0) { HIP_TRY(ctx, hipStreamSynchronize(st)); return CGMR_OK; }
+  // every front's block of Sigma (own columns, then the border), and the row tiles of k_selinv_border level by level
+  const int nfr = (int)S.fronts.size();
+  std::vector<int64_t> soff(nfr + 1, 0);
+  for (int f = 0; f < nfr; f++) {
+    const int64_t n = 3 * (int64_t)(S.fronts[f].nc + S.fronts[f].ns);
+    soff[f + 1] = soff[f] + n * n;
+  }
+  SelinvPlan P;
+  std::vector<int32_t> tiles;
+  P.h_tile_ptr.assign(D.nlevels_full + 1, 0);
+  for (int l = 0; l < D.nlevels_full; l++) {
+    for (int q = D.h_flevel_ptr[l]; q < D.h_flevel_ptr[l + 1]; q++) {
+      const int f = S.level_fronts[q];
+      if (S.fronts[f].parent < 0) continue;                             // (a root has no border)
+      for (int t0 = 0; t0 < 3 * S.fronts[f].ns; t0 += kSelinvTileRows) { tiles.push_back(f); tiles.push_back(t0); }
+    }
+    P.h_tile_ptr[l + 1] = (int)tiles.size() / 2;
+  }
+  std::vector<int32_t> vcol(nV);
+  for (int v = 0; v < nV; v++) vcol[v] = ctx->vmask[v] ? -1 : S.vperm[v];     // fixed / inactive: zeros
+  // staging: poses | meas | info | vcol | col_front | soff | tiles | cov | cross;  Sigma: an arena of its own
+  struct L2 { size_t off = 0; size_t add(size_t b) { off = (off + 255) & ~size_t(255); size_t o = off; off += b; return o; } } L;
+  const size_t o_p = L.add(24 * (size_t)nV), o_m = L.add(24 * (size_t)nE), o_i = L.add(48 * (size_t)nE), o_vc = L.add(4 * (size_t)nV),
+               o_cf = L.add(4 * (size_t)D.nf), o_so = L.add(8 * soff.size()), o_t = L.add(4 * tiles.size()), o_cov = L.add(72 * (size_t)nV),
+               o_cr = L.add(72 * (size_t)nE);
+  rc = arena_reserve(ctx, ctx->io_arena, L.off + 256);
+  if (rc) return rc;
+  rc = arena_reserve(ctx, ctx->si_arena, 8 * (size_t)soff[nfr]);
+  if (rc) return rc;
+  char* d = ctx->io_arena.ptr;
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_p, work.data(), 24 * (size_t)nV, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_m, meas, 24 * (size_t)nE, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_i, info, 48 * (size_t)nE, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_vc, vcol.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_cf, S.col_front.data(), 4 * (size_t)D.nf, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_so, soff.data(), 8 * soff.size(), hipMemcpyHostToDevice, st));
+  if (!tiles.empty()) HIP_TRY(ctx, hipMemcpyAsync(d + o_t, tiles.data(), 4 * tiles.size(), hipMemcpyHostToDevice, st));
+  P.Sig = (double*)ctx->si_arena.ptr;
+  P.soff = (const int64_t*)(d + o_so);
+  P.tiles = (const int32_t*)(d + o_t);
+  double* dp = (double*)(d + o_p);
+  GnEdges Ed;
+  Ed.meas_a = (const double*)(d + o_m); Ed.info_a = (const double*)(d + o_i); Ed.nA = nE; Ed.n_active = nE;
+  int status4[4] = {0, 0, 0, 0};
+  auto run_pass = [&]() -> int {
+    gn_pass(ctx, dp, Ed, 0, false, false, /*write_l11c=*/true);
+    launch_invert_fronts(st, D, /*top_too=*/true);                     // Z = L11^-1 of every front, the top block's included
+    launch_selinv(st, D, P, nV, nE, (const int32_t*)(d + o_vc), (const int32_t*)(d + o_cf), (double*)(d + o_cov),
+                  cross_out ? (double*)(d + o_cr) : nullptr);
+    HIP_TRY(ctx, hipMemcpyAsync(cov_out, d + o_cov, 72 * (size_t)nV, hipMemcpyDeviceToHost, st));
+    if (cross_out && nE > 0) HIP_TRY(ctx, hipMemcpyAsync(cross_out, d + o_cr, 72 * (size_t)nE, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+  };
+  rc = marginal_pass(ctx, dp, work.data(), nV, status4, run_pass);
+  if (rc) return rc;
+  if (status4[0] != 0) {
+    memset(cov_out, 0, 72 * (size_t)nV);
+    if (cross_out) memset(cross_out, 0, 72 * (size_t)nE);
+    return set_err(ctx, CGMR_E_CHOLESKY_BASE, "Cholesky failed while computing marginals");
+  }
+  return CGMR_OK;
+}
+
+
 }  // namespace cgmr
 
 using namespace cgmr;
 
 extern "C" {
 
-int cgmr_version(void) { return 102; }   // 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
+int cgmr_version(void) { return 103; }   // 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
 
 int cgmr_ctx_create(int device, void* hip_stream, cgmr_ctx** out) {
   if (!out) return CGMR_E_INVALID;
@@ -984,6 +1081,7 @@ void cgmr_ctx_destroy(cgmr_ctx* ctx) {
   if (ctx->mtab_arena.ptr) (void)hipFree(ctx->mtab_arena.ptr);
   if (ctx->rep_arena.ptr) (void)hipFree(ctx->rep_arena.ptr);
   if (ctx->mg_arena.ptr) (void)hipFree(ctx->mg_arena.ptr);
+  if (ctx->si_arena.ptr) (void)hipFree(ctx->si_arena.ptr);
   if (ctx->st_arena.ptr) (void)hipFree(ctx->st_arena.ptr);
   if (ctx->pinned_st) (void)hipHostFree(ctx->pinned_st);
   if (ctx->ev_st_copied) (void)hipEventDestroy(ctx->ev_st_copied);
@@ -1101,6 +1199,12 @@ int cgmr_marginals(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fi
                    double* cov_out) {
   if (!ctx || !cov_out) return CGMR_E_INVALID;
   return marginal_driver(ctx, 0, nV, poses, fixed, nE, ef, et, meas, info, -1, nK, query, nullptr, nullptr, nullptr, cov_out);
+}
+
+int cgmr_marginals_all(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                       const int32_t* et, const double* meas, const double* info, double* cov_out, double* cross_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  return marginals_all_driver(ctx, nV, poses, fixed, nE, ef, et, meas, info, cov_out, cross_out);
 }
 
 int cgmr_covariance_estimate(cgmr_ctx* ctx, int nV, const double* poses, int nE, const int32_t* ef, const int32_t* et,

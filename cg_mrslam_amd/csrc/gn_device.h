@@ -83,7 +83,9 @@ int bwd_chain_capacity(int per_cu);
 void choose_bwd_chain(GnDevice& D, int slots_div, bool levelwise);
 void launch_update(hipStream_t st, const GnDevice& D, double* poses);
 void launch_top_block(hipStream_t st, const GnDevice& D, bool store_l, bool write_l11c, bool clear_panels, bool make_z);
-void launch_invert_fronts(hipStream_t st, const GnDevice& D);
+// Z = L11^-1 of every front below the top block; with top_too, of the top block's fronts as well (their factor must be in
+// Lbuf: launch_top_block(.., store_l))
+void launch_invert_fronts(hipStream_t st, const GnDevice& D, bool top_too = false);
 // marginals_kernels.hip
 // A batch of marginals / labelling passes, one per job of a batched GnDevice (D.njobs): job j's query list, Y, U, Gram and
 // covariance buffers are the first job's moved by j * marg_stride bytes; its query count, gauge and output slot come from
@@ -100,5 +102,20 @@ void launch_marginals(hipStream_t st, const GnDevice& D, int nK, const int32_t* 
                       bool y_is_zero = false);   // y_is_zero: the caller has cleared Y already
 void launch_label(hipStream_t st, int nK, const int32_t* d_qvert, int gauge, const double* poses, const double* cov,
                   double* est, double* info, int* flags, const GnDevice* D = nullptr, const MargBatch* batch = nullptr);
+// selinv_kernels.hip: all-pose marginals by selected inversion of the factor in D.Lbuf (gn_pass(.., write_l11c) followed by
+// launch_invert_fronts(.., top_too)).  Sig: every front's dense (w + r)^2 block of H^-1 at soff[front] doubles;
+// tiles: (front, first border row) pairs of every front with a border, level by level, kSelinvTileRows rows each, the
+// level's entries at [h_tile_ptr[l], h_tile_ptr[l + 1]) (device memory except h_tile_ptr).
+constexpr int kSelinvTileRows = 64;
+struct SelinvPlan {
+  double* Sig = nullptr;
+  const int64_t* soff = nullptr;
+  const int32_t* tiles = nullptr;
+  std::vector<int32_t> h_tile_ptr;
+};
+// vcol: per vertex its permuted column or -1 (fixed / inactive: zeros); col_front: per permuted column its front.
+// cov [nV * 9]; cross (nullable) [nE * 9] for the edges D.ef / D.et.
+void launch_selinv(hipStream_t st, const GnDevice& D, const SelinvPlan& P, int nV, int nE, const int32_t* vcol,
+                   const int32_t* col_front, double* cov, double* cross);
 
 }  // namespace cgmr

@@ -892,14 +892,16 @@ __device__ __forceinline__ void invert_l11_48(double* Lt, const double* dinv, do
   }
   __syncthreads();
 }
-// Z = L11^-1 of the fronts f0, f0 + df, .. (every front with a panel, i.e. below the top block): L11 and 1 / diag from Lbuf
-// into LDS, inverted there, stored behind the front's L21.  smem: 48 x 48 + 48 + 2 x 768 doubles.
+// Z = L11^-1 of the fronts f0, f0 + df, .. (every front with a panel, i.e. below the top block; top_too: the top block's
+// as well, whose factor the top-block launch stored with store_l): L11 and 1 / diag from Lbuf into LDS, inverted there,
+// stored behind the front's L21.  smem: 48 x 48 + 48 + 2 x 768 doubles.
 template <int NT>
-__device__ __forceinline__ void invert_fronts(const FrontDesc* __restrict__ fronts, int nfronts_all, int f0, int df, double* __restrict__ Lbuf, double* sm, int tid) {
+__device__ __forceinline__ void invert_fronts(const FrontDesc* __restrict__ fronts, int nfronts_all, int f0, int df, double* __restrict__ Lbuf, double* sm, int tid,
+                                              bool top_too = false) {
   constexpr int W = 48, kDinv = 2 * W * W, kL21 = 2 * W * W + W;
   double* Lt = sm, *dinv = sm + W * W, *sd = dinv + W, *sp = sd + 768;
   for (int f = f0; f < nfronts_all; f += df) {
-    if (fronts[f].pan_off < 0) continue;                        // (a front of the top block)
+    if (fronts[f].pan_off < 0 && !top_too) continue;            // (a front of the top block)
     double* Pn = Lbuf + fronts[f].L_off;
     const int r = 3 * fronts[f].ns;
     for (int q = tid; q < W * W; q += NT) Lt[q] = Pn[q];
@@ -1155,10 +1157,11 @@ __global__ __launch_bounds__(kTopT) void k_top_block(int c0, int ncols, int nfro
 
 // Z for a tree without a top block (no k_top_block launch to ride on)
 template <bool BATCH>
-__global__ __launch_bounds__(256) void k_invert_fronts(const FrontDesc* __restrict__ fronts, int nfronts_all, double* __restrict__ Lbuf, long long js) {
+__global__ __launch_bounds__(256) void k_invert_fronts(const FrontDesc* __restrict__ fronts, int nfronts_all, double* __restrict__ Lbuf, long long js,
+                                                       int top_too) {
   CGMR_JOB(Lbuf, js);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_z[];
-  if constexpr (kFrontW == 48) invert_fronts<256>(fronts, nfronts_all, blockIdx.x, gridDim.x, Lbuf, reinterpret_cast<double*>(smem_z), threadIdx.x);
+  if constexpr (kFrontW == 48) invert_fronts<256>(fronts, nfronts_all, blockIdx.x, gridDim.x, Lbuf, reinterpret_cast<double*>(smem_z), threadIdx.x, top_too != 0);
 }
 
 // ------------------------------------------------------------------------------ solves
@@ -1625,9 +1628,10 @@ void launch_top_block(hipStream_t st, const GnDevice& D, bool store_l, bool writ
 }
 
 // Z = L11^-1 of every front when there is no top-block launch to make it (launch_top_block(.., make_z))
-void launch_invert_fronts(hipStream_t st, const GnDevice& D) {
+void launch_invert_fronts(hipStream_t st, const GnDevice& D, bool top_too) {
   if (kFrontW != 48 || D.nfronts <= 0) return;
-  hipLaunchKernelGGL(CGMR_KERN(D, k_invert_fronts), dim3(std::min(D.nfronts, 512), 1, D.njobs), dim3(256), kInvertSmemBytes, st, D.fronts, D.nfronts, D.Lbuf, D.job_stride);
+  hipLaunchKernelGGL(CGMR_KERN(D, k_invert_fronts), dim3(std::min(D.nfronts, 512), 1, D.njobs), dim3(256), kInvertSmemBytes, st, D.fronts, D.nfronts, D.Lbuf, D.job_stride,
+                     top_too ? 1 : 0);
 }
 
 void launch_update(hipStream_t st, const GnDevice& D, double* poses) {

@@ -174,6 +174,14 @@ class GraphSLAM:
         self.last_chi2 = chi2
         self.last_status = rc
 
+    def computeMarginals(self, cross: bool = False):     # noqa: N802 (g2o spelling)
+        """SparseOptimizer::computeMarginals over every vertex, on the level-0 edges at the current estimates:
+        ``cov[nV, 3, 3]``, or ``(cov, cross[nE0, 3, 3])`` with ``cross=True`` (the block of each level-0 edge, rows the
+        from vertex, columns the to vertex).  Fixed vertices and their edges get zeros."""
+        g = self.graph
+        ef, et, meas, info = g.level0()
+        return self.ctx.marginals_all(g.poses, g.fixed, ef, et, meas, info, cross=cross)
+
     def chi2(self) -> float:
         g = self.graph
         ef, et, meas, info = g.level0()

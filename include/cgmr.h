@@ -262,6 +262,21 @@ int cgmr_match_last_kernel_seconds(const cgmr_ctx* ctx, double* seconds);
 int cgmr_marginals(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
                    const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt, const double* info_upper,
                    int nK, const int32_t* query_idx, double* cov_out);
+/* cgmr_marginals_all: the covariance of every pose, and of every edge's pair of poses, in one call -- what
+ * SparseOptimizer::computeMarginals over all vertices gives [g2o-recalled].  H is linearised at poses_xyt with the given
+ * fixed flags, as for cgmr_marginals; the caller's poses are not modified.
+ *   cov_out   [nV*9]            cov_out[v] = the 3x3 block Sigma_vv of H^-1, row-major (x, y, theta).
+ *   cross_out [nE*9] nullable   cross_out[e] = the block Sigma_{from,to}: rows index the from vertex, columns the to vertex.
+ * Fixed and inactive vertices get exact zeros, and so does every edge with such an endpoint; duplicate edges get
+ * identical blocks.  Computed by selected inversion (the Takahashi recurrence) on the supernodal factor, top-down over the
+ * elimination tree: device memory grows with the factor (every front keeps its dense block of H^-1 on its own rows,
+ * (3 (block columns + border block rows))^2 doubles each), not with the number of poses asked for.  Shares the analysis
+ * cache with the other entry points (a call right after cgmr_gn_optimize on the same edge list is a hit).  Returns
+ * CGMR_OK, CGMR_E_INVALID for a bad argument, CGMR_E_CHOLESKY_BASE when the factorisation fails, CGMR_E_TIMEOUT as
+ * cgmr_marginals does.                                                                                                   */
+int cgmr_marginals_all(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                       const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt,
+                       const double* info_upper, double* cov_out, double* cross_out);
 int cgmr_covariance_estimate(cgmr_ctx* ctx, int nV, const double* poses_xyt, int nE, const int32_t* from_idx,
                              const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int gauge_idx,
                              int nK, const int32_t* query_idx, double* cov_out);

@@ -66,6 +66,11 @@ class RobotGraph:
 
     def close(self):
         if getattr(self, "h", None):
+            if self.ctx is not None and not getattr(self.ctx, "h", None):
+                # the context was destroyed first (both in one garbage cycle, collected in any order -- after an exception, at
+                # interpreter exit): cgmr_graph_destroy would use it.  The graph's device memory is left to the process's exit
+                self.h = None
+                return
             self.lib.cgmr_graph_destroy(self.h)
             self.h = None
 

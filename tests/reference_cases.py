@@ -1,7 +1,10 @@
 """The graphs the backward-error and marginal checks run on (tests/test_reference_cpu.py, tests/test_reference_gpu.py), one
-per branch of the supernodal factorisation they are there to reach.  TEST INFRASTRUCTURE ONLY."""
+per branch of the supernodal factorisation they are there to reach, the bars of the checks that use them, and the check of a
+condensed graph against the labelling of the GPU's own step (tests/test_reference_gpu.py, tests/test_robot_graph_reference_gpu.py).
+TEST INFRASTRUCTURE ONLY."""
 import numpy as np
 
+import ref_numpy as R
 from cg_mrslam_amd import synth
 
 KEYS = ("poses", "fixed", "edge_from", "edge_to", "meas", "info")
@@ -92,3 +95,27 @@ OMEGA_MAX = 120 * np.finfo(np.float64).eps / 2
 # between the GPU and SuperLU on the 1500/5000 graph (cond_1(H) 3.6e10 at the guess, by onenormest), 3.1e-8 m on the
 # 2500/9000 graph after a time-out (one launch per kernel and level); ten times the largest
 EST_ATOL = 3e-7
+
+REF_ERR_MAX = 1e-11    # the reference blocks' own error estimate: a case above it is invalid (measured: 1.3e-12)
+INFO_RTOL = 1e-8       # condensed information, per edge by its own norm
+EST_OWN_ATOL = 1e-12   # condensed measurement against the labelling of the GPU's own step from the same guess (measured 1.4e-14)
+# ... for the batched condensed path, whose step splits the chained backward solve at another level than gn_optimize's (another
+# summation order: the two steps differ by their forward error): 1.0e-10 measured (3 robots x 2 peers), asserted at ten times that
+EST_OWN_ATOL_BATCH = 1e-9
+
+
+def check_labels_on_own_step(c, ef, et, meas, info, gauge, ref, to, est, iu, atol=EST_OWN_ATOL):
+    """The measurement and information against the labelling of the GPU's own one step from the same guess (only the gauge
+    fixed): the solvers' forward error drops out, and est must agree to rounding."""
+    fixed = np.zeros(len(ref["guess"]), np.uint8)
+    fixed[gauge] = 1
+    rc, p1, _ = c.gn_optimize(ref["guess"], fixed, ef, et, meas, info, 1)
+    assert rc == 0
+    idx = np.asarray(to, dtype=np.int64)
+    z, iu1, bad = R.label_edges_ut(p1[gauge], p1[idx], ref["cov"])
+    assert not bad.any()
+    d = np.abs(np.asarray(est) - z).max()
+    assert d <= atol, d
+    for k in range(len(idx)):
+        assert np.linalg.norm(iu[k] - iu1[k]) <= INFO_RTOL * np.linalg.norm(iu1[k]), int(idx[k])
+    return d

@@ -13,7 +13,8 @@ import pytest
 
 import ref_numpy as R
 import reference_cases as C
-from reference_cases import EST_ATOL, OMEGA_MAX
+from reference_cases import EST_ATOL, EST_OWN_ATOL_BATCH, INFO_RTOL, OMEGA_MAX, REF_ERR_MAX
+from reference_cases import check_labels_on_own_step as _check_labels_on_own_step
 from cg_mrslam_amd import synth
 from cg_mrslam_amd._lib import gn_symbolic_info
 
@@ -23,12 +24,6 @@ MARG_TAU = 1e-9        # ||Sigma_gpu - Sigma_ref||_F <= MARG_TAU ||Sigma_ref||_F
 # ... on the pass repeated with one launch per kernel and level after a time-out: 1.15e-9 measured on the 2500/9000 graph
 # (cond_1(H) 1.1e10 by onenormest), asserted at ten times that
 MARG_TAU_LEVELWISE = 1.2e-8
-REF_ERR_MAX = 1e-11    # the reference blocks' own error estimate: a case above it is invalid (measured: 1.3e-12)
-INFO_RTOL = 1e-8       # condensed information, per edge by its own norm
-EST_OWN_ATOL = 1e-12   # condensed measurement against the labelling of the GPU's own step from the same guess (measured 1.4e-14)
-# ... for the batched condensed path, whose step splits the chained backward solve at another level than gn_optimize's (another
-# summation order: the two steps differ by their forward error): 1.0e-10 measured (3 robots x 2 peers), asserted at ten times that
-EST_OWN_ATOL_BATCH = 1e-9
 TOP_MAX_COLS = 128     # kTopMaxCols (gn_symbolic.h): scalar columns of the top block
 
 
@@ -254,23 +249,6 @@ def _condense_case(oracle, g, gauge, query, p):
     ref = R.condense_ref(p, *C.args(g)[2:], gauge, query, oracle.initial_guess)
     assert np.all(ref["cov_err"] <= REF_ERR_MAX), "the reference itself is not accurate enough here"
     return ref
-
-
-def _check_labels_on_own_step(c, ef, et, meas, info, gauge, ref, to, est, iu, atol=EST_OWN_ATOL):
-    """The measurement and information against the labelling of the GPU's own one step from the same guess (only the gauge
-    fixed): the solvers' forward error drops out, and est must agree to rounding."""
-    fixed = np.zeros(len(ref["guess"]), np.uint8)
-    fixed[gauge] = 1
-    rc, p1, _ = c.gn_optimize(ref["guess"], fixed, ef, et, meas, info, 1)
-    assert rc == 0
-    idx = np.asarray(to, dtype=np.int64)
-    z, iu1, bad = R.label_edges_ut(p1[gauge], p1[idx], ref["cov"])
-    assert not bad.any()
-    d = np.abs(np.asarray(est) - z).max()
-    assert d <= atol, d
-    for k in range(len(idx)):
-        assert np.linalg.norm(iu[k] - iu1[k]) <= INFO_RTOL * np.linalg.norm(iu1[k]), int(idx[k])
-    return d
 
 
 @pytest.mark.parametrize("wrap", [False, True])

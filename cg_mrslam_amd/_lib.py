@@ -77,6 +77,25 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(0)
 
 
+class LmParams(C.Structure):
+    """cgmr_lm_params (include/cgmr.h): g2o's OptimizationAlgorithmLevenberg properties."""
+    _fields_ = [("tau", C.c_double), ("initial_lambda", C.c_double), ("max_trials", C.c_int32),
+                ("good_step_lower", C.c_double), ("good_step_upper", C.c_double)]
+
+
+LM_DEFAULTS = dict(tau=1e-5, initial_lambda=-1.0, max_trials=10, good_step_lower=1.0 / 3, good_step_upper=2.0 / 3)
+
+
+def lm_params(**kw) -> LmParams:
+    """An LmParams with g2o's defaults for whatever ``kw`` does not name."""
+    bad = set(kw) - set(LM_DEFAULTS)
+    if bad:
+        raise TypeError(f"unknown Levenberg-Marquardt parameter(s): {sorted(bad)}")
+    v = dict(LM_DEFAULTS, **kw)
+    return LmParams(float(v["tau"]), float(v["initial_lambda"]), int(v["max_trials"]), float(v["good_step_lower"]),
+                    float(v["good_step_upper"]))
+
+
 class Context:
     """One cgmr context = one HIP device + one stream (include/cgmr.h)."""
 
@@ -134,6 +153,51 @@ class Context:
                                            C.c_void_p(d_info_ptr), C.c_int(iters), _ptr(chi))
         self._check(rc, allow_cholesky=not raise_on_cholesky)
         return rc, chi
+
+    def lm_optimize(self, poses, fixed, ef, et, meas, info, iters, **params):
+        """Levenberg-Marquardt (cgmr_lm_optimize, g2o's OptimizationAlgorithmLevenberg); ``params``: tau, initial_lambda,
+        max_trials, good_step_lower, good_step_upper (g2o's defaults otherwise).  Host arrays in and out.  Returns
+        (status, poses, chi2[iters+1], lambdas[iters], trials[iters], iters_done); termination is status 0 with
+        iters_done < iters, never a Cholesky status."""
+        p = np.ascontiguousarray(poses, dtype=np.float64).copy()
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        ef = np.ascontiguousarray(ef, dtype=np.int32)
+        et = np.ascontiguousarray(et, dtype=np.int32)
+        meas = np.ascontiguousarray(meas, dtype=np.float64)
+        info = np.ascontiguousarray(info, dtype=np.float64)
+        chi = np.zeros(iters + 1)
+        lam = np.zeros(iters)
+        tri = np.zeros(iters, dtype=np.int32)
+        done = C.c_int32(0)
+        prm = lm_params(**params)
+        rc = self.lib.cgmr_lm_optimize(self.h, C.c_int(p.shape[0]), _ptr(p), _ptr(fixed), C.c_int(len(ef)), _ptr(ef), _ptr(et),
+                                       _ptr(meas), _ptr(info), C.c_int(iters), C.byref(prm), _ptr(chi), _ptr(lam), _ptr(tri),
+                                       C.byref(done))
+        self._check(rc)
+        return rc, p, chi, lam, tri, int(done.value)
+
+    def lm_optimize_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters, **params):
+        """Device pointers (ints) for poses/meas/info, host numpy for the structure.  Returns
+        (status, chi2[iters+1], lambdas[iters], trials[iters], iters_done)."""
+        chi = np.zeros(iters + 1)
+        lam = np.zeros(iters)
+        tri = np.zeros(iters, dtype=np.int32)
+        done = C.c_int32(0)
+        prm = lm_params(**params)
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        ef = np.ascontiguousarray(ef, dtype=np.int32)
+        et = np.ascontiguousarray(et, dtype=np.int32)
+        rc = self.lib.cgmr_lm_optimize_dev(self.h, C.c_int(nV), C.c_void_p(d_poses_ptr), _ptr(fixed), C.c_int(len(ef)), _ptr(ef),
+                                           _ptr(et), C.c_void_p(d_meas_ptr), C.c_void_p(d_info_ptr), C.c_int(iters),
+                                           C.byref(prm), _ptr(chi), _ptr(lam), _ptr(tri), C.byref(done))
+        self._check(rc)
+        return rc, chi, lam, tri, int(done.value)
+
+    def lm_last_stats(self):
+        """The last lm_optimize* call: dict(host_waits, trials)."""
+        out = np.zeros(2, dtype=np.int64)
+        self._check(self.lib.cgmr_lm_last_stats(self.h, _ptr(out)))
+        return dict(host_waits=int(out[0]), trials=int(out[1]))
 
     # ------------------------------------------------------------------ marginals / condensed graph
     @staticmethod

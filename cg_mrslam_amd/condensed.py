@@ -132,6 +132,27 @@ class RobotGraph:
         n = self._check(self.lib.cgmr_graph_closures(self.h, C.c_int(peer), C.c_int(0 if which == "out" else 1), C.c_int(len(out)), _p(out)))
         return out[:n].copy()
 
+    def set_algorithm(self, algorithm: str = "gn", **params):
+        """The optimiser of ``optimize``: "gn" (default, the reference's Gauss-Newton) or "levenberg" with g2o's
+        Levenberg-Marquardt parameters (tau, initial_lambda, max_trials, good_step_lower, good_step_upper)."""
+        from ._lib import lm_params
+        if algorithm not in ("gn", "levenberg"):
+            raise ValueError(f"algorithm must be 'gn' or 'levenberg', not {algorithm!r}")
+        if algorithm == "gn":
+            self._check(self.lib.cgmr_graph_set_algorithm(self.h, C.c_int(0), C.c_void_p(0)))
+        else:
+            prm = lm_params(**params)
+            self._check(self.lib.cgmr_graph_set_algorithm(self.h, C.c_int(1), C.byref(prm)))
+
+    def lm_last(self):
+        """Records of the last Levenberg-Marquardt solve: (lambdas, trials), one entry per iteration run."""
+        n = self._check(self.lib.cgmr_graph_lm_last(self.h, C.c_int(0), C.c_void_p(0), C.c_void_p(0)))
+        lam = np.zeros(n)
+        tri = np.zeros(n, dtype=np.int32)
+        if n:
+            self._check(self.lib.cgmr_graph_lm_last(self.h, C.c_int(n), _p(lam), _p(tri)))
+        return lam, tri
+
     def set_optimal_gauge(self, optimal: bool):
         """``computeCondensedGraph(robot, optimal)``: selectOptimalGauge instead of selectGaugeCentroid (reference default: off)."""
         self._check(self.lib.cgmr_graph_set_optimal_gauge(self.h, C.c_int(1 if optimal else 0)))

@@ -626,7 +626,7 @@ void gn_pass(cgmr_ctx* ctx, double* d_poses, const GnEdges& Ed, int it, bool chi
 
 // the same on an explicit device view (the context's, or a replica with its own numeric work space) and stream
 void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, const GnEdges& Ed, int it, bool chi_only,
-                bool solve_and_update, bool write_l11c) {
+                bool solve_and_update, bool write_l11c, LmState* lm, bool lm_init) {
   KTimer T{ctx, st};
   T.run(0, 1, [&] { launch_linearize(st, D, d_poses, Ed, chi_only ? 1 : 0); });
   if (chi_only || D.nf == 0) {
@@ -643,6 +643,10 @@ void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, con
   }
   D.pan_clean = false;
   T.run(1, 1, [&] { launch_assemble(st, D); });                // + the chi2 sum of this iteration (slot = iterations done)
+  if (lm) {                                                     // a Levenberg-Marquardt trial: H + lambda I (lm_kernels.hip)
+    if (lm_init) launch_lm_init(st, D, lm);
+    launch_lm_damp(st, D, lm);
+  }
   static const bool trace = getenv("CGMR_TRACE_LAUNCHES") != nullptr;
   if (trace)
     fprintf(stderr, "[cgmr] arena %p .. %p; work %p rel %p Pan %p Ablk %p bvec %p yvec %p uvec %p Lbuf %p Ubuf %p chi2 %p\n",
@@ -779,6 +783,152 @@ int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
     return set_err(ctx, CGMR_E_CHOLESKY_BASE - (status - 1),
                    "Cholesky failed (non-positive pivot) in GN iteration %d; poses left at the last good update",
                    status - 1);
+  return CGMR_OK;
+}
+
+// g2o's OptimizationAlgorithmLevenberg defaults [g2o-recalled]
+static cgmr_lm_params lm_defaults() {
+  cgmr_lm_params p;
+  p.tau = 1e-5; p.initial_lambda = -1; p.max_trials = 10; p.good_step_lower = 1.0 / 3; p.good_step_upper = 2.0 / 3;
+  return p;
+}
+
+struct LmDev {
+  LmState* S = nullptr;
+  double *rec_chi = nullptr, *rec_lambda = nullptr, *saved = nullptr;
+  int32_t* rec_trials = nullptr;
+};
+
+// One trial, the same launches whatever happens (lm_kernels.hip): linearise + assemble + damp + factor + solve + update at x,
+// chi-only linearise at x', the verdict, then restore x or keep x'.
+static void lm_trial(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, int nV, double* d_poses, const GnEdges& Ed, const LmDev& L, bool init) {
+  gn_pass_on(ctx, D, st, d_poses, Ed, 0, false, true, false, L.S, init);
+  launch_linearize(st, D, d_poses, Ed, 1);
+  launch_lm_decide(st, D, L.S, L.rec_chi, L.rec_lambda, L.rec_trials);
+  launch_lm_commit(st, nV, d_poses, L.saved, L.S);
+}
+
+int lm_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
+           const GnEdges& Ed, int iters, const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
+           int32_t* iters_done, const int32_t* hub_vertices, int n_hub_vertices) {
+  const cgmr_lm_params P = params ? *params : lm_defaults();
+  if (!(P.max_trials >= 1) || !(P.tau >= 0) || !(P.good_step_lower > 0) || !(P.good_step_upper > 0) || !std::isfinite(P.tau) ||
+      !std::isfinite(P.initial_lambda) || !std::isfinite(P.good_step_lower) || !std::isfinite(P.good_step_upper))
+    return set_err(ctx, CGMR_E_INVALID, "cgmr_lm_optimize: max_trials must be >= 1, tau >= 0, the step scales > 0, all finite");
+  const double t0 = wall_s();
+  Symbolic& S = ctx->sym;
+  // (the chi2 slots a trial uses: slot 0 only -- the cache entry of a Gauss-Newton call on the same edge list serves)
+  int rc = prepare_structure(ctx, nV, nE, ef, et, 1, hub_vertices, n_hub_vertices);
+  if (rc) return rc;
+  const double t1 = wall_s();
+  rc = prepare_pass(ctx, fixed, nE, ef, et, Ed.n_active, 0, 1);
+  if (rc) return rc;
+  const double t2 = wall_s();
+  GnDevice& D = ctx->gn;
+  hipStream_t st = ctx->stream;
+  // lm arena: state | chi2 records [iters + 1] | lambda records [iters] | trial records [iters] | saved poses [3 nV]
+  BlobLayout B;
+  const size_t o_state = B.add<LmState>(1), o_chi = B.add<double>((size_t)iters + 1), o_lam = B.add<double>((size_t)iters + 1),
+               o_tri = B.add<int32_t>((size_t)iters + 1);
+  const size_t rec_bytes = B.off;
+  const size_t o_saved = B.add<double>(3 * (size_t)std::max(nV, 1));
+  rc = arena_reserve(ctx, ctx->lm_arena, B.off + 256);
+  if (rc) return rc;
+  char* d = ctx->lm_arena.ptr;
+  LmDev L;
+  L.S = (LmState*)(d + o_state); L.rec_chi = (double*)(d + o_chi); L.rec_lambda = (double*)(d + o_lam);
+  L.rec_trials = (int32_t*)(d + o_tri); L.saved = (double*)(d + o_saved);
+  std::vector<char> h(rec_bytes, 0);
+  LmState hs;
+  hs.tau = P.tau; hs.initial_lambda = P.initial_lambda; hs.max_trials = P.max_trials;
+  hs.lower = P.good_step_lower; hs.upper = P.good_step_upper; hs.iters = iters;
+  memcpy(h.data() + o_state, &hs, sizeof hs);
+  HIP_TRY(ctx, hipMemcpyAsync(d, h.data(), rec_bytes, hipMemcpyHostToDevice, st));
+  if (nV > 0) HIP_TRY(ctx, hipMemcpyAsync(L.saved, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));
+  double* const poses_host = ctx->poses_out_host;
+  ctx->poses_out_host = nullptr;
+  int status4[4] = {0, 0, 0, 0};
+  int64_t waits = 0;
+  if (D.nf == 0 || iters == 0) {
+    // nothing to move (or nothing asked): chi2 at x.  With iterations asked, the first trial's step is zero, rho = 0: g2o
+    // terminates after it, lambda grown once by nu
+    gn_pass(ctx, d_poses, Ed, 0, true, false, false);
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
+    double chi0 = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&chi0, D.chi2, sizeof(double), hipMemcpyDeviceToHost, st));
+    if (poses_host && nV > 0) HIP_TRY(ctx, hipMemcpyAsync(poses_host, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipGetLastError());
+    waits = 1;
+    hs.iter = iters > 0 ? 1 : 0;
+    hs.lambda = 2 * (P.initial_lambda > 0 ? P.initial_lambda : 0.0);
+    hs.total_trials = hs.iter;
+    double* rc_chi = (double*)(h.data() + o_chi);
+    double* rc_lam = (double*)(h.data() + o_lam);
+    int32_t* rc_tri = (int32_t*)(h.data() + o_tri);
+    rc_chi[0] = chi0;
+    if (hs.iter) { rc_chi[1] = chi0; rc_lam[0] = hs.lambda; rc_tri[0] = 1; }
+  } else {
+    // rounds: queue one trial per iteration still to run, wait once; a rejected trial leaves its iteration to the next round
+    const int chain_was = D.bwd_chain_level;
+    const std::vector<uint8_t> merge_was = D.h_level_merge;
+    bool levelwise = false;
+    for (;;) {
+      const int n_trials = iters - hs.iter;
+      for (int t = 0; t < n_trials; t++) lm_trial(ctx, D, st, nV, d_poses, Ed, L, t == 0);   // (k_lm_init: a no-op once lambda is set)
+      HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
+      HIP_TRY(ctx, hipMemcpyAsync(h.data(), d, rec_bytes, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
+      if (poses_host && nV > 0) HIP_TRY(ctx, hipMemcpyAsync(poses_host, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, hipStreamSynchronize(st));
+      HIP_TRY(ctx, hipGetLastError());
+      waits++;
+      memcpy(&hs, h.data() + o_state, sizeof hs);
+      if (hs.halted) {
+        // A bounded wait ran out in a trial (status[2]): not a numerical verdict.  The trial restored the poses and the later
+        // ones of the round did nothing; the call goes on from the state as it stands, one launch per kernel and level (no
+        // in-kernel waits), as gn_run does.
+        if (levelwise) {
+          D.bwd_chain_level = chain_was;
+          D.h_level_merge = merge_was;
+          return set_err(ctx, CGMR_E_TIMEOUT, "Levenberg-Marquardt: a bounded device-side wait ran out twice");
+        }
+        ctx->gn_timeouts++;
+        ctx->fwd_merge_any = false;
+        levelwise = true;
+        D.bwd_chain_level = D.nlevels;
+        D.h_level_merge.assign(D.nlevels, 0);
+        hs.halted = 0;
+        hs.accept = -1;
+        const int fresh[4] = {0, 0, 0, 0};
+        HIP_TRY(ctx, hipMemcpyAsync(D.status, fresh, sizeof fresh, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(L.S, &hs, sizeof hs, hipMemcpyHostToDevice, st));
+        continue;
+      }
+      if (hs.done) break;
+    }
+    D.bwd_chain_level = chain_was;
+    D.h_level_merge = merge_was;
+  }
+  const double* rc_chi = (const double*)(h.data() + o_chi);
+  const double* rc_lam = (const double*)(h.data() + o_lam);
+  const int32_t* rc_tri = (const int32_t*)(h.data() + o_tri);
+  const int ran = std::min(hs.iter, iters);
+  if (chi2_out) for (int k = 0; k <= iters; k++) chi2_out[k] = rc_chi[std::min(k, ran)];
+  if (lambda_out) for (int k = 0; k < iters; k++) lambda_out[k] = k < ran ? rc_lam[k] : 0.0;
+  if (trials_out) for (int k = 0; k < iters; k++) trials_out[k] = k < ran ? rc_tri[k] : 0;
+  if (iters_done) *iters_done = ran;
+  ctx->lm_stats[0] = waits;
+  ctx->lm_stats[1] = hs.total_trials;
+  if (ctx->profiling) profile_collect(ctx);
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+  ctx->timing[0] = S.t_order;
+  ctx->timing[1] = S.t_struct;
+  ctx->timing[2] = (t2 - t1) + S.t_upload;
+  ctx->timing[3] = 1e-3 * ms;
+  ctx->timing[4] = wall_s() - t0;
   return CGMR_OK;
 }
 
@@ -1039,7 +1189,7 @@ using namespace cgmr;
 
 extern "C" {
 
-int cgmr_version(void) { return 103; }   // 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
+int cgmr_version(void) { return 104; }   // 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
 
 int cgmr_ctx_create(int device, void* hip_stream, cgmr_ctx** out) {
   if (!out) return CGMR_E_INVALID;
@@ -1082,6 +1232,7 @@ void cgmr_ctx_destroy(cgmr_ctx* ctx) {
   if (ctx->rep_arena.ptr) (void)hipFree(ctx->rep_arena.ptr);
   if (ctx->mg_arena.ptr) (void)hipFree(ctx->mg_arena.ptr);
   if (ctx->si_arena.ptr) (void)hipFree(ctx->si_arena.ptr);
+  if (ctx->lm_arena.ptr) (void)hipFree(ctx->lm_arena.ptr);
   if (ctx->st_arena.ptr) (void)hipFree(ctx->st_arena.ptr);
   if (ctx->pinned_st) (void)hipHostFree(ctx->pinned_st);
   if (ctx->ev_st_copied) (void)hipEventDestroy(ctx->ev_st_copied);
@@ -1148,6 +1299,53 @@ int cgmr_gn_optimize(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed,
     if (e != hipSuccess) return set_err(ctx, CGMR_E_HIP, "pose read-back: %s", hipGetErrorString(e));
   }
   return rc;
+}
+
+int cgmr_lm_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                         const int32_t* to_idx, const double* d_meas, const double* d_info, int iters, const cgmr_lm_params* params,
+                         double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (nV < 0 || nE < 0 || iters < 0 || (nV > 0 && (!d_poses || !fixed)) ||
+      (nE > 0 && (!from_idx || !to_idx || !d_meas || !d_info)))
+    return set_err(ctx, CGMR_E_INVALID, "cgmr_lm_optimize: null or negative argument");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  GnEdges Ed;
+  Ed.meas_a = d_meas; Ed.info_a = d_info; Ed.nA = nE; Ed.n_active = nE;
+  return lm_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, lambda_out, trials_out, iters_done);
+}
+
+int cgmr_lm_optimize(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                     const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_lm_params* params,
+                     double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (nV < 0 || nE < 0 || iters < 0 || (nV > 0 && (!poses || !fixed)) ||
+      (nE > 0 && (!from_idx || !to_idx || !meas || !info)))
+    return set_err(ctx, CGMR_E_INVALID, "cgmr_lm_optimize: null or negative argument");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  size_t bp = sizeof(double) * 3 * (size_t)nV, bm = sizeof(double) * 3 * (size_t)nE, bi = sizeof(double) * 6 * (size_t)nE;
+  size_t op = 0, om = (bp + 255) & ~size_t(255), oi = (om + bm + 255) & ~size_t(255);
+  int rc = arena_reserve(ctx, ctx->io_arena, oi + bi + 256);
+  if (rc) return rc;
+  char* d = ctx->io_arena.ptr;
+  HIP_TRY(ctx, hipMemcpyAsync(d + op, poses, bp, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d + om, meas, bm, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d + oi, info, bi, hipMemcpyHostToDevice, ctx->stream));
+  GnEdges Ed;
+  Ed.meas_a = (const double*)(d + om); Ed.info_a = (const double*)(d + oi); Ed.nA = nE; Ed.n_active = nE;
+  rc = lm_run(ctx, nV, (double*)(d + op), fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, lambda_out, trials_out, iters_done);
+  if (rc == CGMR_OK) {
+    hipError_t e = hipMemcpyAsync(poses, d + op, bp, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return set_err(ctx, CGMR_E_HIP, "pose read-back: %s", hipGetErrorString(e));
+  }
+  return rc;
+}
+
+int cgmr_lm_last_stats(const cgmr_ctx* ctx, int64_t out[2]) {
+  if (!ctx || !out) return CGMR_E_INVALID;
+  out[0] = ctx->lm_stats[0];
+  out[1] = ctx->lm_stats[1];
+  return CGMR_OK;
 }
 
 static void symbolic_info_out(const Symbolic& S, int nV, int64_t out[16], int32_t* perm_out) {

@@ -36,6 +36,8 @@ struct cgmr_ctx {
   cgmr::Arena rep_arena;    // replicas of the GN numeric work space (concurrent passes on one structure)
   cgmr::Arena mg_arena;     // marginals work space of the concurrent passes
   cgmr::Arena si_arena;     // cgmr_marginals_all: every front's block of H^-1 (selinv_kernels.hip)
+  cgmr::Arena lm_arena;     // cgmr_lm_optimize*: the Levenberg-Marquardt state, its records and the saved poses (lm_kernels.hip)
+  int64_t lm_stats[2] = {0, 0};   // last Levenberg-Marquardt call: host waits, trials
   // What the device needs of the analysis BEFORE the borders / maps are done (vperm, the edge list, the off-diagonal blocks'
   // rows / columns / column starts) and what it makes of it underneath the rest of the analysis: the assembly lists
   // (gn_structure.hip).  Own arena and own pinned staging block: the structure blob's are sized at the END of the analysis.

@@ -1,6 +1,7 @@
 // Host-side drivers of the Gauss-Newton path shared by the C-ABI translation units (cgmr_api.cpp, mrslam_api.cpp).
 #pragma once
 #include "cgmr_ctx.h"
+#include "lm_device.h"
 
 namespace cgmr {
 
@@ -22,12 +23,18 @@ int prepare_batch_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st);
 // streams for concurrent passes
 int gn_replicas(cgmr_ctx* ctx, int n, std::vector<GnDevice>& out, size_t* stride_out = nullptr);
 int aux_streams(cgmr_ctx* ctx, int n);
+// lm (nullable): a Levenberg-Marquardt trial -- lambda onto H's diagonal after the assembly (computed first when lm_init)
 void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, const GnEdges& Ed, int it, bool chi_only,
-                bool solve_and_update, bool write_l11c);
+                bool solve_and_update, bool write_l11c, LmState* lm = nullptr, bool lm_init = false);
 // one Gauss-Newton pass on the uploaded structure: linearise + chi2 [+ assemble + factor [+ solve + update]]
 void gn_pass(cgmr_ctx* ctx, double* d_poses, const GnEdges& Ed, int it, bool chi_only, bool solve_and_update, bool write_l11c);
 int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
            const GnEdges& Ed, int iters, double* chi2_out, const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0);
+// Levenberg-Marquardt on the same structure preparation and factorisation (g2o's OptimizationAlgorithmLevenberg): outputs
+// chi2_out [iters + 1], lambda_out / trials_out [iters] (all nullable), *iters_done; never a Cholesky status
+int lm_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
+           const GnEdges& Ed, int iters, const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
+           int32_t* iters_done, const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0);
 // SparseOptimizer::computeInitialGuess from the fixed vertices over the given edges [g2o-recalled]
 void initial_guess_host(int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
                         const double* meas);

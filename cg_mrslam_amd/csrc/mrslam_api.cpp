@@ -103,6 +103,11 @@ struct cgmr_graph {
   std::vector<uint8_t> hs_fresh;      // per peer: hs_meas / hs_info hold what the device staging holds
   double last_condense_seconds = 0, last_optimize_seconds = 0;
   bool optimal_gauge = false;         // computeCondensedGraph(robot, optimal)
+  int algorithm = CGMR_ALG_GAUSS_NEWTON;   // cgmr_graph_set_algorithm: the optimiser of cgmr_graph_optimize
+  bool lm_params_set = false;
+  cgmr_lm_params lm_params{};
+  std::vector<double> lm_lambda;      // records of the last Levenberg solve (cgmr_graph_lm_last)
+  std::vector<int32_t> lm_trials;
   bool h_poses_fresh = false;         // h_poses holds the estimates as the last optimize() left them
   double* pinned_poses = nullptr;     // landing zone of that read-back (page-locked: a copy into the pageable h_poses goes through the runtime's staging path)
   size_t pinned_poses_cap = 0;        // in poses
@@ -500,8 +505,20 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out) {
     HIP_TRY(ctx, hipHostMalloc((void**)&g->pinned_poses, 24 * g->pinned_poses_cap, hipHostMallocDefault));
   }
   ctx->poses_out_host = g->pinned_poses;
-  int rc = gn_run(ctx, nV, (double*)g->d_poses.ptr, g->fixed.data(), nE, g->all_ef.data(), g->all_et.data(), Ed, iters, chi2_out,
-                  hubs.data(), (int)hubs.size());
+  int rc;
+  g->lm_lambda.clear();
+  g->lm_trials.clear();
+  if (g->algorithm == CGMR_ALG_LEVENBERG) {
+    std::vector<double> lam(iters);
+    std::vector<int32_t> tri(iters);
+    int32_t done = 0;
+    rc = lm_run(ctx, nV, (double*)g->d_poses.ptr, g->fixed.data(), nE, g->all_ef.data(), g->all_et.data(), Ed, iters,
+                g->lm_params_set ? &g->lm_params : nullptr, chi2_out, lam.data(), tri.data(), &done, hubs.data(), (int)hubs.size());
+    if (rc == CGMR_OK) { g->lm_lambda.assign(lam.begin(), lam.begin() + done); g->lm_trials.assign(tri.begin(), tri.begin() + done); }
+  } else {
+    rc = gn_run(ctx, nV, (double*)g->d_poses.ptr, g->fixed.data(), nE, g->all_ef.data(), g->all_et.data(), Ed, iters, chi2_out,
+                hubs.data(), (int)hubs.size());
+  }
   ctx->poses_out_host = nullptr;
   g->h_poses_fresh = asked && (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE);
   if (g->h_poses_fresh) memcpy(g->h_poses.data(), g->pinned_poses, 24 * (size_t)nV);
@@ -509,6 +526,24 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out) {
   g->solved_ef = g->all_ef; g->solved_et = g->all_et;
   g->solved_nV = nV; g->solved_nA = (int)g->ef.size();
   return rc;
+}
+
+int cgmr_graph_set_algorithm(cgmr_graph* g, int algorithm, const cgmr_lm_params* params) {
+  if (!g || (algorithm != CGMR_ALG_GAUSS_NEWTON && algorithm != CGMR_ALG_LEVENBERG)) return CGMR_E_INVALID;
+  g->algorithm = algorithm;
+  g->lm_params_set = params != nullptr;
+  if (params) g->lm_params = *params;
+  return CGMR_OK;
+}
+
+int cgmr_graph_lm_last(const cgmr_graph* g, int cap, double* lambda_out, int32_t* trials_out) {
+  if (!g || cap < 0) return CGMR_E_INVALID;
+  const int n = (int)g->lm_lambda.size();
+  for (int k = 0; k < std::min(n, cap); k++) {
+    if (lambda_out) lambda_out[k] = g->lm_lambda[k];
+    if (trials_out) trials_out[k] = g->lm_trials[k];
+  }
+  return n;
 }
 
 int cgmr_graph_get_poses(cgmr_graph* g, int first, int n, double* poses_out) {

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import Context
+from ._lib import CGMR_E_CHOLESKY_BASE, Context
 
 ODOM_INFO = (100.0, 100.0, 1000.0)      # _odominf, src/slam/graph_slam.cpp:72-73
 SM_INFO = (1000.0, 1000.0, 10000.0)     # _SMinf,   src/slam/graph_slam.cpp:75-76
@@ -157,22 +157,52 @@ class PoseGraph:
 class GraphSLAM:
     """The optimiser face of the reference's ``GraphSLAM`` (src/slam/graph_slam.h:49-76)."""
 
-    def __init__(self, graph: PoseGraph, ctx: Context | None = None, device: int = 0):
+    def __init__(self, graph: PoseGraph, ctx: Context | None = None, device: int = 0, algorithm: str = "gn",
+                 lm_params: dict | None = None):
+        """``algorithm``: "gn" (the reference's Gauss-Newton) or "levenberg" (g2o's OptimizationAlgorithmLevenberg, with
+        ``lm_params``: tau, initial_lambda, max_trials, good_step_lower, good_step_upper)."""
+        if algorithm not in ("gn", "levenberg"):
+            raise ValueError(f"algorithm must be 'gn' or 'levenberg', not {algorithm!r}")
         self.graph = graph
         self.ctx = ctx or Context(device)
+        self.algorithm = algorithm
+        self.lm_params = dict(lm_params or {})
         self.last_chi2 = None
         self.last_status = 0
+        self.last_lambdas = None
+        self.last_trials = None
+        self.last_iterations = 0
 
     def optimize(self, nrunnings: int) -> None:
-        """``nrunnings`` Gauss-Newton iterations on the level-0 edges; estimates updated in place.
-        Returns nothing and never raises on a Cholesky failure, like the reference."""
+        """``nrunnings`` iterations on the level-0 edges; estimates updated in place.  Returns nothing and never raises on
+        a Cholesky failure, like the reference.  With "levenberg" the call may terminate early: ``last_iterations`` holds
+        the iterations run (g2o's SparseOptimizer::optimize return value)."""
         g = self.graph
         ef, et, meas, info = g.level0()
-        rc, poses, chi2 = self.ctx.gn_optimize(g.poses, g.fixed, ef, et, meas, info, int(nrunnings),
-                                               raise_on_cholesky=False)
+        if self.algorithm == "levenberg":
+            rc, poses, chi2, lam, tri, done = self.ctx.lm_optimize(g.poses, g.fixed, ef, et, meas, info, int(nrunnings),
+                                                                   **self.lm_params)
+            self.last_lambdas, self.last_trials, self.last_iterations = lam[:done], tri[:done], done
+        else:
+            rc, poses, chi2 = self.ctx.gn_optimize(g.poses, g.fixed, ef, et, meas, info, int(nrunnings),
+                                                   raise_on_cholesky=False)
+            self.last_iterations = int(nrunnings) if rc == 0 else CGMR_E_CHOLESKY_BASE - rc
         g.poses[:] = poses
         self.last_chi2 = chi2
         self.last_status = rc
+
+    def currentLambda(self) -> float:     # noqa: N802 (g2o spelling)
+        """OptimizationAlgorithmLevenberg::currentLambda: lambda after the last iteration of the last optimize (0 before
+        any Levenberg iteration)."""
+        if self.last_lambdas is None or len(self.last_lambdas) == 0:
+            return 0.0
+        return float(self.last_lambdas[-1])
+
+    def levenbergIterations(self) -> int:     # noqa: N802 (g2o spelling)
+        """OptimizationAlgorithmLevenberg::levenbergIteration: trials of the last iteration of the last optimize."""
+        if self.last_trials is None or len(self.last_trials) == 0:
+            return 0
+        return int(self.last_trials[-1])
 
     def computeMarginals(self, cross: bool = False):     # noqa: N802 (g2o spelling)
         """SparseOptimizer::computeMarginals over every vertex, on the level-0 edges at the current estimates:

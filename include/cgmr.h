@@ -86,6 +86,44 @@ int cgmr_gn_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8
                          const int32_t* from_idx, const int32_t* to_idx, const double* d_meas_xyt,
                          const double* d_info_upper, int iters, double* chi2_out);
 
+/* Levenberg-Marquardt optimisation (C ABI version >= 104): g2o's OptimizationAlgorithmLevenberg [g2o-recalled], the
+ * alternative the reference's map tool includes (ros_map_publisher/graph2occupancy.h:19).  Outer iteration i linearises
+ * once; its trials solve (H + lambda I) dx = b on the Gauss-Newton path's factorisation (fixed and inactive vertices stay
+ * outside the system and take no lambda), evaluate chi2 at x (+) dx and keep the step when
+ *   rho = (chi2(x) - chi2(x')) / (dx^T (lambda dx + b) + 1e-3) > 0
+ * (lambda *= max(lower, min(upper, 1 - (2 rho - 1)^3)), nu = 2); a rejected trial restores the poses bit for bit and
+ * retries with lambda *= nu, nu *= 2.  A failed factorisation is a rejected trial.  The call terminates early when an
+ * iteration runs max_trials trials, when rho == 0, or when lambda is no longer finite.  lambda starts, on the first trial of
+ * every call, at initial_lambda if > 0, else at tau * max |H_jj| over the free diagonal.
+ *   params      nullable: g2o's defaults (tau 1e-5, initial_lambda -1, max_trials 10, 1/3, 2/3)
+ *   chi2_out    [iters+1] nullable: chi2 at the start and after each iteration (after the last run: repeated)
+ *   lambda_out  [iters]   nullable: lambda at the end of each iteration (0 past iters_done)
+ *   trials_out  [iters]   nullable: trials (factorisations) of each iteration (0 past iters_done)
+ *   iters_done  nullable: iterations run, a terminating one included (g2o's optimize() return value)
+ * Returns CGMR_OK (also on termination: iters_done < iters unless it came in the last iteration), CGMR_E_INVALID,
+ * CGMR_E_HIP / _ALLOC, or CGMR_E_TIMEOUT when a bounded in-kernel wait runs out twice (after the first time the trial is
+ * repeated with one launch per kernel and level).  Never CGMR_E_CHOLESKY_*.  Shares the analysis cache with
+ * cgmr_gn_optimize*.  The device keeps the state: the host queues iters - (iterations run) trials and waits once per
+ * such round (one wait when every first trial is accepted).  CGMR_GRAPH capture does not apply to this path. */
+typedef struct cgmr_lm_params {
+  double tau;
+  double initial_lambda;
+  int32_t max_trials;
+  double good_step_lower;
+  double good_step_upper;
+} cgmr_lm_params;
+int cgmr_lm_optimize(cgmr_ctx* ctx, int nV, double* poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                     const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int iters,
+                     const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
+                     int32_t* iters_done);
+/* Device-resident variant (d_poses / d_meas / d_info on the context's device, as cgmr_gn_optimize_dev). */
+int cgmr_lm_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8_t* fixed, int nE,
+                         const int32_t* from_idx, const int32_t* to_idx, const double* d_meas_xyt,
+                         const double* d_info_upper, int iters, const cgmr_lm_params* params, double* chi2_out,
+                         double* lambda_out, int32_t* trials_out, int32_t* iters_done);
+/* The last cgmr_lm_optimize* call on this context: out[0] = host waits for the device, out[1] = trials run. */
+int cgmr_lm_last_stats(const cgmr_ctx* ctx, int64_t out[2]);
+
 /* The ordering + symbolic analysis + structure upload of the last analysed edge list stay on the context and are
  * reused by every later call (cgmr_gn_optimize*, cgmr_marginals, cgmr_covariance_estimate, cgmr_condense*) whose
  * (nV, from_idx, to_idx) are exactly the same -- the fixed flags are applied numerically and do not enter the
@@ -430,6 +468,14 @@ int cgmr_graph_debug_edges(const cgmr_graph* g, int cap, int32_t* from_out, int3
 int cgmr_graph_counts(const cgmr_graph* g, int32_t out[4]);
 /* GraphSLAM::optimize(iters); chi2_out nullable [iters+1]; returns like cgmr_gn_optimize */
 int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out);
+/* The optimiser cgmr_graph_optimize uses: CGMR_ALG_GAUSS_NEWTON (default, the reference's) or CGMR_ALG_LEVENBERG with
+ * params (nullable: g2o's defaults), run as cgmr_lm_optimize does; a Levenberg call never returns CGMR_E_CHOLESKY_*.
+ * cgmr_graph_lm_last: the records of the last Levenberg solve -- lambda_out / trials_out [cap] (nullable), returns the
+ * iterations run (0 after a Gauss-Newton solve). */
+#define CGMR_ALG_GAUSS_NEWTON 0
+#define CGMR_ALG_LEVENBERG 1
+int cgmr_graph_set_algorithm(cgmr_graph* g, int algorithm, const cgmr_lm_params* params);
+int cgmr_graph_lm_last(const cgmr_graph* g, int cap, double* lambda_out, int32_t* trials_out);
 /* estimates of vertices first .. first+n-1 in insertion order */
 int cgmr_graph_get_poses(cgmr_graph* g, int first, int n, double* poses_out);
 int cgmr_graph_set_poses(cgmr_graph* g, int first, int n, const double* poses_xyt);

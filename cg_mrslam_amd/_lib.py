@@ -96,6 +96,60 @@ def lm_params(**kw) -> LmParams:
                     float(v["good_step_upper"]))
 
 
+class Robust(C.Structure):
+    """cgmr_robust (include/cgmr.h): the robust kernels of one call."""
+    _fields_ = [("kind", C.c_void_p), ("delta", C.c_void_p), ("default_kind", C.c_int32), ("default_delta", C.c_double),
+                ("edge_chi2_out", C.c_void_p), ("weight_out", C.c_void_p)]
+
+
+# g2o's robust kernels by their C codes (include/cgmr.h: CGMR_RK_*)
+ROBUST_KINDS = {"none": 0, "huber": 1, "pseudohuber": 2, "cauchy": 3, "welsch": 4, "tukey": 5, "saturated": 6, "dcs": 7}
+
+
+def robust_code(kind) -> int:
+    """The C code of a robust kernel given by name (g2o's, any case: "Huber", "PseudoHuber", "DCS", ...) or by code."""
+    if isinstance(kind, str):
+        key = kind.lower().replace("_", "").replace("-", "")
+        if key.startswith("robustkernel"):
+            key = key[len("robustkernel"):]
+        if key not in ROBUST_KINDS:
+            raise ValueError(f"unknown robust kernel {kind!r}; one of {sorted(ROBUST_KINDS)}")
+        return ROBUST_KINDS[key]
+    if isinstance(kind, (bool, np.bool_)) or not isinstance(kind, (int, np.integer)) or not 0 <= int(kind) <= 7:
+        raise ValueError(f"robust kernel code must be 0..7, got {kind!r}")
+    return int(kind)
+
+
+def robust_arrays(kind, delta, n):
+    """(codes uint8 [n] or None, deltas float64 [n] or None, uniform code, uniform delta), checked as the library checks them:
+    a known kind, and a finite delta > 0 for every kind but "none".  Raises ValueError."""
+    if isinstance(kind, (str, int, np.integer)):
+        codes, code0 = None, robust_code(kind)
+    else:
+        arr = np.asarray(kind)
+        if arr.dtype.kind in "iu":                                 # codes: checked in one go
+            if arr.size and (arr.min() < 0 or arr.max() > 7):
+                raise ValueError("robust kernel codes must be 0..7")
+            codes = arr.astype(np.uint8).reshape(-1)
+        else:
+            codes = np.array([robust_code(k) for k in arr.tolist()], dtype=np.uint8)
+        code0 = 0
+        if codes.shape != (n,):
+            raise ValueError(f"per-edge robust kinds: {codes.shape[0]} given for {n} edges")
+    if np.ndim(delta) == 0:
+        deltas, delta0 = None, float(delta)
+    else:
+        deltas, delta0 = np.ascontiguousarray(delta, dtype=np.float64), 1.0
+        if deltas.shape != (n,):
+            raise ValueError(f"per-edge robust deltas: {deltas.shape} given for {n} edges")
+    k = codes if codes is not None else np.full(n if deltas is not None else 1, code0, dtype=np.uint8)
+    d = deltas if deltas is not None else np.full(k.shape, delta0)
+    bad = (k != 0) & ~(np.isfinite(d) & (d > 0))
+    if bad.any():
+        raise ValueError(f"robust kernel delta must be finite and > 0 (edge {int(np.flatnonzero(bad)[0])})")
+    return codes, deltas, code0, delta0
+
+
 class Context:
     """One cgmr context = one HIP device + one stream (include/cgmr.h)."""
 
@@ -192,6 +246,91 @@ class Context:
                                            C.byref(prm), _ptr(chi), _ptr(lam), _ptr(tri), C.byref(done))
         self._check(rc)
         return rc, chi, lam, tri, int(done.value)
+
+    # ------------------------------------------------------------------ robust kernels
+    @staticmethod
+    def _robust(kind, delta, n, d_kind_ptr=None, d_delta_ptr=None):
+        """cgmr_robust for host (kind / delta: name or code / scalar, or per-edge arrays) or device (d_*_ptr) inputs, with the
+        statistics arrays it fills.  Returns (struct, e2 [n], weights [n], the arrays the struct points into)."""
+        codes, deltas, code0, delta0 = robust_arrays(kind, delta, n)
+        e2, w = np.zeros(n), np.zeros(n)
+        rk = Robust(None, None, code0, delta0, e2.ctypes.data if n else None, w.ctypes.data if n else None)
+        rk.kind = d_kind_ptr if d_kind_ptr is not None else (codes.ctypes.data if codes is not None and n else None)
+        rk.delta = d_delta_ptr if d_delta_ptr is not None else (deltas.ctypes.data if deltas is not None and n else None)
+        return rk, e2, w, (codes, deltas)
+
+    def gn_optimize_robust(self, poses, fixed, ef, et, meas, info, iters, kind="none", delta=1.0, raise_on_cholesky=True):
+        """gn_optimize with robust kernels (cgmr_gn_optimize_robust): ``kind`` a name, a code or per-edge array of either,
+        ``delta`` a scalar or per-edge array.  Returns (status, poses, robust chi2[iters+1], e2 [nE], weights [nE]), the last
+        two at the returned estimate."""
+        p = np.ascontiguousarray(poses, dtype=np.float64).copy()
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        ef = np.ascontiguousarray(ef, dtype=np.int32)
+        et = np.ascontiguousarray(et, dtype=np.int32)
+        meas = np.ascontiguousarray(meas, dtype=np.float64)
+        info = np.ascontiguousarray(info, dtype=np.float64)
+        rk, e2, w, _keep = self._robust(kind, delta, len(ef))
+        chi = np.zeros(iters + 1)
+        rc = self.lib.cgmr_gn_optimize_robust(self.h, C.c_int(p.shape[0]), _ptr(p), _ptr(fixed), C.c_int(len(ef)), _ptr(ef),
+                                              _ptr(et), _ptr(meas), _ptr(info), C.c_int(iters), _ptr(chi), C.byref(rk))
+        self._check(rc, allow_cholesky=not raise_on_cholesky)
+        return rc, p, chi, e2, w
+
+    def gn_optimize_robust_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters, kind="none", delta=1.0,
+                               d_kind_ptr=None, d_delta_ptr=None, raise_on_cholesky=True):
+        """gn_optimize_dev with robust kernels: per-edge kinds (uint8) / deltas (float64) as device pointers, or a uniform
+        ``kind`` / ``delta``.  Returns (status, robust chi2[iters+1], e2 [nE], weights [nE])."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        ef = np.ascontiguousarray(ef, dtype=np.int32)
+        et = np.ascontiguousarray(et, dtype=np.int32)
+        rk, e2, w, _keep = self._robust(kind, delta, len(ef), d_kind_ptr, d_delta_ptr)
+        chi = np.zeros(iters + 1)
+        rc = self.lib.cgmr_gn_optimize_robust_dev(self.h, C.c_int(nV), C.c_void_p(d_poses_ptr), _ptr(fixed), C.c_int(len(ef)),
+                                                  _ptr(ef), _ptr(et), C.c_void_p(d_meas_ptr), C.c_void_p(d_info_ptr),
+                                                  C.c_int(iters), _ptr(chi), C.byref(rk))
+        self._check(rc, allow_cholesky=not raise_on_cholesky)
+        return rc, chi, e2, w
+
+    def lm_optimize_robust(self, poses, fixed, ef, et, meas, info, iters, kind="none", delta=1.0, **params):
+        """lm_optimize with robust kernels (``kind`` / ``delta`` as gn_optimize_robust).  Returns (status, poses, robust
+        chi2[iters+1], lambdas[iters], trials[iters], iters_done, e2 [nE], weights [nE])."""
+        p = np.ascontiguousarray(poses, dtype=np.float64).copy()
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        ef = np.ascontiguousarray(ef, dtype=np.int32)
+        et = np.ascontiguousarray(et, dtype=np.int32)
+        meas = np.ascontiguousarray(meas, dtype=np.float64)
+        info = np.ascontiguousarray(info, dtype=np.float64)
+        rk, e2, w, _keep = self._robust(kind, delta, len(ef))
+        chi = np.zeros(iters + 1)
+        lam = np.zeros(iters)
+        tri = np.zeros(iters, dtype=np.int32)
+        done = C.c_int32(0)
+        prm = lm_params(**params)
+        rc = self.lib.cgmr_lm_optimize_robust(self.h, C.c_int(p.shape[0]), _ptr(p), _ptr(fixed), C.c_int(len(ef)), _ptr(ef),
+                                              _ptr(et), _ptr(meas), _ptr(info), C.c_int(iters), C.byref(prm), _ptr(chi),
+                                              _ptr(lam), _ptr(tri), C.byref(done), C.byref(rk))
+        self._check(rc)
+        return rc, p, chi, lam, tri, int(done.value), e2, w
+
+    def lm_optimize_robust_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters, kind="none", delta=1.0,
+                               d_kind_ptr=None, d_delta_ptr=None, **params):
+        """lm_optimize_dev with robust kernels (as gn_optimize_robust_dev).  Returns (status, robust chi2[iters+1],
+        lambdas[iters], trials[iters], iters_done, e2 [nE], weights [nE])."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        ef = np.ascontiguousarray(ef, dtype=np.int32)
+        et = np.ascontiguousarray(et, dtype=np.int32)
+        rk, e2, w, _keep = self._robust(kind, delta, len(ef), d_kind_ptr, d_delta_ptr)
+        chi = np.zeros(iters + 1)
+        lam = np.zeros(iters)
+        tri = np.zeros(iters, dtype=np.int32)
+        done = C.c_int32(0)
+        prm = lm_params(**params)
+        rc = self.lib.cgmr_lm_optimize_robust_dev(self.h, C.c_int(nV), C.c_void_p(d_poses_ptr), _ptr(fixed), C.c_int(len(ef)),
+                                                  _ptr(ef), _ptr(et), C.c_void_p(d_meas_ptr), C.c_void_p(d_info_ptr),
+                                                  C.c_int(iters), C.byref(prm), _ptr(chi), _ptr(lam), _ptr(tri), C.byref(done),
+                                                  C.byref(rk))
+        self._check(rc)
+        return rc, chi, lam, tri, int(done.value), e2, w
 
     def lm_last_stats(self):
         """The last lm_optimize* call: dict(host_waits, trials)."""

@@ -144,6 +144,35 @@ class RobotGraph:
             prm = lm_params(**params)
             self._check(self.lib.cgmr_graph_set_algorithm(self.h, C.c_int(1), C.byref(prm)))
 
+    def set_edge_robust(self, kind, delta=1.0, first: int = 0, n: int | None = None):
+        """Robust kernels of own edges [first, first + n) by insertion index (n None: to the last one): ``kind`` a name or
+        code, or an array of either, one per edge; ``delta`` a scalar or array.  Edges added later take none.  Names and
+        deltas are checked here (ValueError) before the library sees them."""
+        from ._lib import robust_arrays
+        if n is None:
+            n = self.counts()["own_edges"] - first if np.ndim(kind) == 0 else len(kind)
+        codes, deltas, code0, delta0 = robust_arrays(kind, delta, n)
+        codes = np.full(n, code0, dtype=np.uint8) if codes is None else codes
+        deltas = np.full(n, delta0) if deltas is None else deltas
+        deltas = np.where(codes == 0, 1.0, deltas)
+        self._check(self.lib.cgmr_graph_set_edge_robust(self.h, C.c_int(first), C.c_int(n), _p(codes), _p(deltas)))
+
+    def set_received_robust(self, kind, delta: float = 1.0):
+        """One robust kernel for every edge received from the peers (default: none)."""
+        from ._lib import robust_arrays
+        _, _, code, d = robust_arrays(kind, delta, 1)
+        self._check(self.lib.cgmr_graph_set_received_robust(self.h, C.c_int(code), C.c_double(d if code else 1.0)))
+
+    def edge_stats(self):
+        """(e2, weights) of every level-0 edge at the estimate of the last optimize, own edges first, then the received ones
+        (debug_edges order); None when that solve ran with no kernel set."""
+        n = self._check(self.lib.cgmr_graph_edge_stats(self.h, C.c_int(0), C.c_void_p(0), C.c_void_p(0)))
+        if n == 0:
+            return None
+        e2, w = np.zeros(n), np.zeros(n)
+        self._check(self.lib.cgmr_graph_edge_stats(self.h, C.c_int(n), _p(e2), _p(w)))
+        return e2, w
+
     def lm_last(self):
         """Records of the last Levenberg-Marquardt solve: (lambdas, trials), one entry per iteration run."""
         n = self._check(self.lib.cgmr_graph_lm_last(self.h, C.c_int(0), C.c_void_p(0), C.c_void_p(0)))

@@ -703,6 +703,9 @@ int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
   double t2 = wall_s();
   GnDevice& D = ctx->gn;
   hipStream_t st = ctx->stream;
+  // (robust statistics: written by the final chi-only pass, at the estimate the call returns)
+  GnEdges Ei = Ed;
+  Ei.rk_stats = nullptr;
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));
   // Every launch of a GN iteration is the same whatever the iteration's number (status[1] on the device supplies the
   // chi2 slot and the failure tag): CGMR_GRAPH=1 captures one iteration into a hipGraph and replays it.
@@ -713,13 +716,13 @@ int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
   if (graph_mode && !ctx->profiling && !trace_launches && iters >= 2 && st != nullptr && D.nf > 0) {
     gn_init_kernels();
     HIP_TRY(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    gn_pass(ctx, d_poses, Ed, 0, false, true, false);
+    gn_pass(ctx, d_poses, Ei, 0, false, true, false);
     HIP_TRY(ctx, hipStreamEndCapture(st, &graph));
     HIP_TRY(ctx, hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0));
     for (int it = 0; it < iters; it++) HIP_TRY(ctx, hipGraphLaunch(graph_exec, st));
     gn_pass(ctx, d_poses, Ed, iters, true, true, false);
   } else {
-    for (int it = 0; it <= iters; it++) gn_pass(ctx, d_poses, Ed, it, it == iters, true, false);
+    for (int it = 0; it <= iters; it++) gn_pass(ctx, d_poses, it == iters ? Ed : Ei, it, it == iters, true, false);
   }
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
   const double t3 = wall_s();
@@ -759,7 +762,7 @@ int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
     D.h_level_merge.assign(D.nlevels, 0);
     const int fresh[4] = {0, it0, 0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(D.status, fresh, sizeof fresh, hipMemcpyHostToDevice, st));
-    for (int it = it0; it <= iters; it++) gn_pass(ctx, d_poses, Ed, it, it == iters, true, false);
+    for (int it = it0; it <= iters; it++) gn_pass(ctx, d_poses, it == iters ? Ed : Ei, it, it == iters, true, false);
     HIP_TRY(ctx, hipMemcpyAsync(chi.data(), D.chi2, sizeof(double) * (iters + 1), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
     if (poses_host && nV > 0) HIP_TRY(ctx, hipMemcpyAsync(poses_host, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToHost, st));
@@ -874,9 +877,11 @@ int lm_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
     const int chain_was = D.bwd_chain_level;
     const std::vector<uint8_t> merge_was = D.h_level_merge;
     bool levelwise = false;
+    GnEdges Ei = Ed;                                         // (robust statistics: one chi-only pass on the committed poses below)
+    Ei.rk_stats = nullptr;
     for (;;) {
       const int n_trials = iters - hs.iter;
-      for (int t = 0; t < n_trials; t++) lm_trial(ctx, D, st, nV, d_poses, Ed, L, t == 0);   // (k_lm_init: a no-op once lambda is set)
+      for (int t = 0; t < n_trials; t++) lm_trial(ctx, D, st, nV, d_poses, Ei, L, t == 0);   // (k_lm_init: a no-op once lambda is set)
       HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
       HIP_TRY(ctx, hipMemcpyAsync(h.data(), d, rec_bytes, hipMemcpyDeviceToHost, st));
       HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
@@ -908,6 +913,7 @@ int lm_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
       }
       if (hs.done) break;
     }
+    if (Ed.rk_stats) launch_linearize(st, D, d_poses, Ed, 1);   // (read back by the caller, behind the stream)
     D.bwd_chain_level = chain_was;
     D.h_level_merge = merge_was;
   }
@@ -1189,7 +1195,7 @@ using namespace cgmr;
 
 extern "C" {
 
-int cgmr_version(void) { return 104; }   // 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
+int cgmr_version(void) { return 105; }   // 105: cgmr_*_optimize_robust*, cgmr_graph_set_edge_robust / _set_received_robust / _edge_stats added; 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
 
 int cgmr_ctx_create(int device, void* hip_stream, cgmr_ctx** out) {
   if (!out) return CGMR_E_INVALID;
@@ -1233,6 +1239,7 @@ void cgmr_ctx_destroy(cgmr_ctx* ctx) {
   if (ctx->mg_arena.ptr) (void)hipFree(ctx->mg_arena.ptr);
   if (ctx->si_arena.ptr) (void)hipFree(ctx->si_arena.ptr);
   if (ctx->lm_arena.ptr) (void)hipFree(ctx->lm_arena.ptr);
+  if (ctx->rk_arena.ptr) (void)hipFree(ctx->rk_arena.ptr);
   if (ctx->st_arena.ptr) (void)hipFree(ctx->st_arena.ptr);
   if (ctx->pinned_st) (void)hipHostFree(ctx->pinned_st);
   if (ctx->ev_st_copied) (void)hipEventDestroy(ctx->ev_st_copied);
@@ -1262,9 +1269,60 @@ int cgmr_ctx_synchronize(cgmr_ctx* ctx) {
   return CGMR_OK;
 }
 
-int cgmr_gn_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
-                         const int32_t* from_idx, const int32_t* to_idx, const double* d_meas,
-                         const double* d_info, int iters, double* chi2_out) {
+// The robust description of an entry point (include/cgmr.h: cgmr_robust) into Ed, checked before anything is queued.  The host
+// entry points' kind / delta arrays are staged through rk_arena; the device ones are read back once to be checked.  The
+// statistics (2 nE doubles: e2, then rho1) land in rk_arena behind them.  rk == nullptr: nothing (the plain call).
+static int robust_setup(cgmr_ctx* ctx, const cgmr_robust* rk, int nE, bool dev, GnEdges& Ed, const char* who) {
+  if (!rk) return 0;
+  const size_t n = (size_t)std::max(nE, 0);
+  std::vector<uint8_t> hk;
+  std::vector<double> hd;
+  const uint8_t* ck = rk->kind;
+  const double* cd = rk->delta;
+  if (dev && n > 0 && (rk->kind || rk->delta)) {
+    if (rk->kind) { hk.resize(n); HIP_TRY(ctx, hipMemcpyAsync(hk.data(), rk->kind, n, hipMemcpyDeviceToHost, ctx->stream)); ck = hk.data(); }
+    if (rk->delta) { hd.resize(n); HIP_TRY(ctx, hipMemcpyAsync(hd.data(), rk->delta, 8 * n, hipMemcpyDeviceToHost, ctx->stream)); cd = hd.data(); }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  bool ok = rk->default_kind >= CGMR_RK_NONE && rk->default_kind <= CGMR_RK_DCS;
+  if (ok && !rk->kind && !rk->delta) ok = robust_valid(rk->default_kind, rk->default_delta);
+  for (size_t k = 0; ok && k < n && (ck || cd); k++)
+    ok = robust_valid(ck ? ck[k] : rk->default_kind, cd ? cd[k] : rk->default_delta);
+  if (!ok)
+    return set_err(ctx, CGMR_E_INVALID, "%s: a robust kernel kind must be 0..7, its delta finite and > 0 (kind 0 excepted)", who);
+  const bool stats = n > 0 && (rk->edge_chi2_out || rk->weight_out);
+  const size_t ok_ = 0, od = (n + 255) & ~size_t(255), os = od + ((8 * n + 255) & ~size_t(255));
+  if (stats || (!dev && (rk->kind || rk->delta))) {
+    int rc = arena_reserve(ctx, ctx->rk_arena, os + 16 * n + 256);
+    if (rc) return rc;
+  }
+  char* d = ctx->rk_arena.ptr;
+  Ed.robust = true;
+  Ed.rk_kind0 = rk->default_kind;
+  Ed.rk_delta0 = rk->default_delta;
+  if (dev) {
+    Ed.rk_kind = rk->kind;
+    Ed.rk_delta = rk->delta;
+  } else {
+    if (rk->kind && n > 0) { HIP_TRY(ctx, hipMemcpyAsync(d + ok_, rk->kind, n, hipMemcpyHostToDevice, ctx->stream)); Ed.rk_kind = (const uint8_t*)(d + ok_); }
+    if (rk->delta && n > 0) { HIP_TRY(ctx, hipMemcpyAsync(d + od, rk->delta, 8 * n, hipMemcpyHostToDevice, ctx->stream)); Ed.rk_delta = (const double*)(d + od); }
+  }
+  Ed.rk_stats = stats ? (double*)(d + os) : nullptr;
+  return 0;
+}
+
+// the statistics of the call's final pass to the caller's host arrays
+static int robust_stats_out(cgmr_ctx* ctx, const cgmr_robust* rk, int nE, const GnEdges& Ed) {
+  if (!rk || !Ed.rk_stats) return 0;
+  if (rk->edge_chi2_out) HIP_TRY(ctx, hipMemcpyAsync(rk->edge_chi2_out, Ed.rk_stats, 8 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
+  if (rk->weight_out) HIP_TRY(ctx, hipMemcpyAsync(rk->weight_out, Ed.rk_stats + nE, 8 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+static int gn_optimize_dev_impl(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                                const int32_t* to_idx, const double* d_meas, const double* d_info, int iters, double* chi2_out,
+                                const cgmr_robust* rk) {
   if (!ctx) return CGMR_E_INVALID;
   if (nV < 0 || nE < 0 || iters < 0 || (nV > 0 && (!d_poses || !fixed)) ||
       (nE > 0 && (!from_idx || !to_idx || !d_meas || !d_info)))
@@ -1272,38 +1330,51 @@ int cgmr_gn_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* 
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   GnEdges Ed;
   Ed.meas_a = d_meas; Ed.info_a = d_info; Ed.nA = nE; Ed.n_active = nE;
-  return gn_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, chi2_out);
+  int rc = robust_setup(ctx, rk, nE, true, Ed, "cgmr_gn_optimize_robust_dev");
+  if (rc) return rc;
+  rc = gn_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, chi2_out);
+  if (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE) {
+    const int rs = robust_stats_out(ctx, rk, nE, Ed);
+    if (rs) return rs;
+  }
+  return rc;
 }
 
-int cgmr_gn_optimize(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
-                     const int32_t* to_idx, const double* meas, const double* info, int iters, double* chi2_out) {
+static int gn_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                            const int32_t* to_idx, const double* meas, const double* info, int iters, double* chi2_out,
+                            const cgmr_robust* rk) {
   if (!ctx) return CGMR_E_INVALID;
   if (nV < 0 || nE < 0 || iters < 0 || (nV > 0 && (!poses || !fixed)) ||
       (nE > 0 && (!from_idx || !to_idx || !meas || !info)))
     return set_err(ctx, CGMR_E_INVALID, "cgmr_gn_optimize: null or negative argument");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  GnEdges Ed;
+  int rc = robust_setup(ctx, rk, nE, false, Ed, "cgmr_gn_optimize_robust");
+  if (rc) return rc;
   size_t bp = sizeof(double) * 3 * (size_t)nV, bm = sizeof(double) * 3 * (size_t)nE, bi = sizeof(double) * 6 * (size_t)nE;
   size_t op = 0, om = (bp + 255) & ~size_t(255), oi = (om + bm + 255) & ~size_t(255);
-  int rc = arena_reserve(ctx, ctx->io_arena, oi + bi + 256);
+  rc = arena_reserve(ctx, ctx->io_arena, oi + bi + 256);
   if (rc) return rc;
   char* d = ctx->io_arena.ptr;
   HIP_TRY(ctx, hipMemcpyAsync(d + op, poses, bp, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d + om, meas, bm, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d + oi, info, bi, hipMemcpyHostToDevice, ctx->stream));
-  GnEdges Ed;
   Ed.meas_a = (const double*)(d + om); Ed.info_a = (const double*)(d + oi); Ed.nA = nE; Ed.n_active = nE;
   rc = gn_run(ctx, nV, (double*)(d + op), fixed, nE, from_idx, to_idx, Ed, iters, chi2_out);
   if (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE) {
     hipError_t e = hipMemcpyAsync(poses, d + op, bp, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return set_err(ctx, CGMR_E_HIP, "pose read-back: %s", hipGetErrorString(e));
+    const int rs = robust_stats_out(ctx, rk, nE, Ed);
+    if (rs) return rs;
   }
   return rc;
 }
 
-int cgmr_lm_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
-                         const int32_t* to_idx, const double* d_meas, const double* d_info, int iters, const cgmr_lm_params* params,
-                         double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done) {
+static int lm_optimize_dev_impl(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                                const int32_t* to_idx, const double* d_meas, const double* d_info, int iters,
+                                const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
+                                int32_t* iters_done, const cgmr_robust* rk) {
   if (!ctx) return CGMR_E_INVALID;
   if (nV < 0 || nE < 0 || iters < 0 || (nV > 0 && (!d_poses || !fixed)) ||
       (nE > 0 && (!from_idx || !to_idx || !d_meas || !d_info)))
@@ -1311,34 +1382,93 @@ int cgmr_lm_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* 
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   GnEdges Ed;
   Ed.meas_a = d_meas; Ed.info_a = d_info; Ed.nA = nE; Ed.n_active = nE;
-  return lm_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, lambda_out, trials_out, iters_done);
+  int rc = robust_setup(ctx, rk, nE, true, Ed, "cgmr_lm_optimize_robust_dev");
+  if (rc) return rc;
+  rc = lm_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, lambda_out, trials_out, iters_done);
+  if (rc == CGMR_OK) rc = robust_stats_out(ctx, rk, nE, Ed);
+  return rc;
 }
 
-int cgmr_lm_optimize(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
-                     const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_lm_params* params,
-                     double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done) {
+static int lm_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                            const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_lm_params* params,
+                            double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done, const cgmr_robust* rk) {
   if (!ctx) return CGMR_E_INVALID;
   if (nV < 0 || nE < 0 || iters < 0 || (nV > 0 && (!poses || !fixed)) ||
       (nE > 0 && (!from_idx || !to_idx || !meas || !info)))
     return set_err(ctx, CGMR_E_INVALID, "cgmr_lm_optimize: null or negative argument");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  GnEdges Ed;
+  int rc = robust_setup(ctx, rk, nE, false, Ed, "cgmr_lm_optimize_robust");
+  if (rc) return rc;
   size_t bp = sizeof(double) * 3 * (size_t)nV, bm = sizeof(double) * 3 * (size_t)nE, bi = sizeof(double) * 6 * (size_t)nE;
   size_t op = 0, om = (bp + 255) & ~size_t(255), oi = (om + bm + 255) & ~size_t(255);
-  int rc = arena_reserve(ctx, ctx->io_arena, oi + bi + 256);
+  rc = arena_reserve(ctx, ctx->io_arena, oi + bi + 256);
   if (rc) return rc;
   char* d = ctx->io_arena.ptr;
   HIP_TRY(ctx, hipMemcpyAsync(d + op, poses, bp, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d + om, meas, bm, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d + oi, info, bi, hipMemcpyHostToDevice, ctx->stream));
-  GnEdges Ed;
   Ed.meas_a = (const double*)(d + om); Ed.info_a = (const double*)(d + oi); Ed.nA = nE; Ed.n_active = nE;
   rc = lm_run(ctx, nV, (double*)(d + op), fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, lambda_out, trials_out, iters_done);
   if (rc == CGMR_OK) {
     hipError_t e = hipMemcpyAsync(poses, d + op, bp, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return set_err(ctx, CGMR_E_HIP, "pose read-back: %s", hipGetErrorString(e));
+    rc = robust_stats_out(ctx, rk, nE, Ed);
   }
   return rc;
+}
+
+int cgmr_gn_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
+                         const int32_t* from_idx, const int32_t* to_idx, const double* d_meas,
+                         const double* d_info, int iters, double* chi2_out) {
+  return gn_optimize_dev_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, chi2_out, nullptr);
+}
+
+int cgmr_gn_optimize(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                     const int32_t* to_idx, const double* meas, const double* info, int iters, double* chi2_out) {
+  return gn_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, chi2_out, nullptr);
+}
+
+int cgmr_lm_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                         const int32_t* to_idx, const double* d_meas, const double* d_info, int iters, const cgmr_lm_params* params,
+                         double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done) {
+  return lm_optimize_dev_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, params, chi2_out, lambda_out,
+                              trials_out, iters_done, nullptr);
+}
+
+int cgmr_lm_optimize(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                     const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_lm_params* params,
+                     double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done) {
+  return lm_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, params, chi2_out, lambda_out, trials_out,
+                          iters_done, nullptr);
+}
+
+int cgmr_gn_optimize_robust(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                            const int32_t* to_idx, const double* meas, const double* info, int iters, double* chi2_out,
+                            const cgmr_robust* rk) {
+  return gn_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, chi2_out, rk);
+}
+
+int cgmr_gn_optimize_robust_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                                const int32_t* to_idx, const double* d_meas, const double* d_info, int iters, double* chi2_out,
+                                const cgmr_robust* rk) {
+  return gn_optimize_dev_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, chi2_out, rk);
+}
+
+int cgmr_lm_optimize_robust(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                            const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_lm_params* params,
+                            double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done, const cgmr_robust* rk) {
+  return lm_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, params, chi2_out, lambda_out, trials_out,
+                          iters_done, rk);
+}
+
+int cgmr_lm_optimize_robust_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                                const int32_t* to_idx, const double* d_meas, const double* d_info, int iters,
+                                const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
+                                int32_t* iters_done, const cgmr_robust* rk) {
+  return lm_optimize_dev_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, params, chi2_out, lambda_out,
+                              trials_out, iters_done, rk);
 }
 
 int cgmr_lm_last_stats(const cgmr_ctx* ctx, int64_t out[2]) {

@@ -37,6 +37,7 @@ struct cgmr_ctx {
   cgmr::Arena mg_arena;     // marginals work space of the concurrent passes
   cgmr::Arena si_arena;     // cgmr_marginals_all: every front's block of H^-1 (selinv_kernels.hip)
   cgmr::Arena lm_arena;     // cgmr_lm_optimize*: the Levenberg-Marquardt state, its records and the saved poses (lm_kernels.hip)
+  cgmr::Arena rk_arena;     // robust entry points: staged per-edge kinds / deltas, the per-edge statistics (cgmr_robust)
   int64_t lm_stats[2] = {0, 0};   // last Levenberg-Marquardt call: host waits, trials
   // What the device needs of the analysis BEFORE the borders / maps are done (vperm, the edge list, the off-diagonal blocks'
   // rows / columns / column starts) and what it makes of it underneath the rest of the analysis: the assembly lists

@@ -53,9 +53,19 @@ struct GnDevice {
 
 // Numeric edge data of one pass: edges [0, nA) from (meas_a, info_a), [nA, nE) from (meas_b, info_b); edges
 // [n_active, nE) are switched off.
+// robust: every edge's information is scaled by rho1 of its robust kernel (gn_kernels.hip: robustify; include/cgmr.h:
+// cgmr_robust): edge k < nA takes kind rk_kind[k] (or rk_kind0 with rk_kind null) and delta rk_delta[k] (or rk_delta0), device
+// memory; edges [nA, nE) take rk_kind0 / rk_delta0.  rk_stats (device, nullable) receives e2 of every edge, then rho1 of
+// every edge.  Not robust: the plain launch, exactly as before.
 struct GnEdges {
   const double *meas_a = nullptr, *info_a = nullptr, *meas_b = nullptr, *info_b = nullptr;
   int nA = 0, n_active = 0;
+  bool robust = false;
+  const uint8_t* rk_kind = nullptr;
+  const double* rk_delta = nullptr;
+  int rk_kind0 = 0;
+  double rk_delta0 = 1.0;
+  double* rk_stats = nullptr;
 };
 // gn_structure.hip: the assembly lists (asm_ptr: nf + nb + 1, asm_src: one entry per (edge, key)) from the permutation, the
 // edge list and the off-diagonal blocks (offbase: nf + 1 column starts into off_row); work space: ekey nE, cnt nf + nb + 3,

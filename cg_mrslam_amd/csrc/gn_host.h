@@ -1,9 +1,17 @@
 // Host-side drivers of the Gauss-Newton path shared by the C-ABI translation units (cgmr_api.cpp, mrslam_api.cpp).
 #pragma once
+#include <cmath>
+
 #include "cgmr_ctx.h"
 #include "lm_device.h"
 
 namespace cgmr {
+
+// a robust kernel kind (include/cgmr.h: CGMR_RK_*) with its delta as the entry points accept them: a known kind, and a finite
+// delta > 0 unless the kind is CGMR_RK_NONE
+inline bool robust_valid(int kind, double delta) {
+  return kind == CGMR_RK_NONE || (kind > CGMR_RK_NONE && kind <= CGMR_RK_DCS && std::isfinite(delta) && delta > 0);
+}
 
 int pinned_mask_reserve(cgmr_ctx* ctx, size_t bytes);
 // ordering + symbolic analysis + structure upload for the edge list, or nothing when the context still holds them

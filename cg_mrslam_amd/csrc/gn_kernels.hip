@@ -90,12 +90,75 @@ __device__ __forceinline__ double d_normalize_theta(double t) {
 // device-resident robot graph keeps the edges received from other robots in a buffer of their own.  Edges
 // [n_active, nE) are switched off for this pass (the condensed graph is built on the robot's own edges only,
 // condensed_graph_buffer.cpp:347-366): they contribute exact zeros to H, b and chi2.
-template <bool BATCH>
+//
+// ROBUST (g2o's robust kernels, include/cgmr.h: cgmr_robust): the edge's e2 = e^T O e maps to (rho0, rho1) = robustify(kind,
+// delta, e2); rho0 goes into the chi2 partial sum instead of e2 and the finished 33 terms are scaled by rho1 (g2o's
+// robustInformation, without the second-order term).  Scaling the terms rather than O differs from g2o's order by rounding
+// only and is exact for rho1 = 1.  A plain solve runs the instance without it, whose code is what it always was: the robust
+// description is a trailing parameter pack, empty in the plain instances (an argument of an empty type would still take
+// 8 bytes of the argument segment and move the implicit arguments behind it).
+struct RobustArgs {
+  const uint8_t* kind;   // [nA] or null: edges [0, nA) take kind[k]; every other edge takes kind0
+  const double* delta;   // [nA] or null: edges [0, nA) take delta[k]; every other edge takes delta0
+  double* stats;         // [2 nE] or null: e2 of every edge, then rho1 of every edge
+  double delta0;
+  int kind0;
+};
+
+// rho0 (returned) and rho1 of g2o's robust kernels (robust_kernel_impl.cpp [g2o-recalled]; the table in include/cgmr.h),
+// in double; kind 0 (or a code the host has not let through): the plain e2, weight 1
+__device__ __forceinline__ double robustify(int kind, double delta, double e2, double& rho1) {
+  const double dsqr = delta * delta;
+  rho1 = 1.0;
+  switch (kind) {
+    case 1:                                                     // Huber
+      if (e2 <= dsqr) return e2;
+      { const double se = sqrt(e2); rho1 = delta / se; return 2 * se * delta - dsqr; }
+    case 2: {                                                   // PseudoHuber
+      const double a = sqrt(e2 / dsqr + 1.0);
+      rho1 = 1.0 / a;
+      return 2 * dsqr * (a - 1.0);
+    }
+    case 3: {                                                   // Cauchy
+      const double a = e2 / dsqr + 1.0;
+      rho1 = 1.0 / a;
+      return dsqr * log(a);
+    }
+    case 4: {                                                   // Welsch
+      const double a = exp(-(e2 / dsqr));
+      rho1 = a;
+      return dsqr * (1.0 - a);
+    }
+    case 5:                                                     // Tukey
+      if (sqrt(e2) <= delta) {
+        const double a = 1.0 - e2 / dsqr;
+        rho1 = a * a;
+        return dsqr * (1.0 - a * a * a) / 3.0;
+      }
+      rho1 = 0.0;
+      return dsqr / 3.0;
+    case 6:                                                     // Saturated
+      if (e2 <= dsqr) return e2;
+      rho1 = 0.0;
+      return dsqr;
+    case 7: {                                                   // DCS (delta = phi)
+      const double sc = 2 * delta / (delta + e2);
+      if (sc >= 1.0) return e2;
+      rho1 = sc * sc;
+      return rho1 * e2;
+    }
+    default: return e2;
+  }
+}
+
+template <bool BATCH, bool ROBUST, typename... Rk>
 __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active, const double* __restrict__ poses,
                                                    const int32_t* __restrict__ ef, const int32_t* __restrict__ et,
                                                    const double* __restrict__ meas, const double* __restrict__ info,
                                                    const double* __restrict__ meas_b, const double* __restrict__ info_b,
-                                                   double* __restrict__ term, int chi_only, long long js, long long ps) {
+                                                   double* __restrict__ term, int chi_only, long long js, long long ps,
+                                                   Rk... rk_pack) {
+  static_assert(sizeof...(Rk) == (ROBUST ? 1 : 0), "k_linearize: one RobustArgs in the robust instance, none otherwise");
   CGMR_JOB(poses, ps); CGMR_JOB(term, js);
   __shared__ double s_chi[4];
   const int k0 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -119,8 +182,18 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
 #pragma unroll
   for (int r = 0; r < 3; r++) Oe[r] = O[3 * r] * e[0] + O[3 * r + 1] * e[1] + O[3 * r + 2] * e[2];
   size_t E = (size_t)nE;
+  [[maybe_unused]] double rho1 = 1.0;
   {
     double ch = live ? e[0] * Oe[0] + e[1] * Oe[1] + e[2] * Oe[2] : 0.0;
+    if constexpr (ROBUST) {
+      const RobustArgs rk(rk_pack...);
+      const double e2 = e[0] * Oe[0] + e[1] * Oe[1] + e[2] * Oe[2];
+      const int kind = rk.kind && k < nA ? (int)rk.kind[k] : rk.kind0;     // (the robot graph's received edges: one class)
+      const double delta = rk.delta && k < nA ? rk.delta[k] : rk.delta0;
+      const double rho0 = robustify(kind, delta, e2, rho1);
+      ch = live ? rho0 : 0.0;
+      if (rk.stats && k0 < nE) { rk.stats[k] = e2; rk.stats[E + k] = rho1; }
+    }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) ch += __shfl_xor(ch, m, 64);
     if ((threadIdx.x & 63) == 0) s_chi[threadIdx.x >> 6] = ch;
@@ -171,6 +244,10 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
     }
     mine[27 + r] = -(JiO[3 * r] * e[0] + JiO[3 * r + 1] * e[1] + JiO[3 * r + 2] * e[2]);
     mine[30 + r] = -(JjO[3 * r] * e[0] + JjO[3 * r + 1] * e[1] + JjO[3 * r + 2] * e[2]);
+  }
+  if constexpr (ROBUST) {
+#pragma unroll
+    for (int q = 0; q < 33; q++) mine[q] *= rho1;
   }
   }
   __syncthreads();
@@ -1454,8 +1531,18 @@ __global__ __launch_bounds__(256) void k_update_poses(int nV, const int32_t* __r
 void launch_linearize(hipStream_t st, const GnDevice& D, const double* poses, const GnEdges& Ed, int chi_only) {
   if (D.nE == 0) return;
   gn_init_kernels();
-  hipLaunchKernelGGL(CGMR_KERN(D, k_linearize), dim3((D.nE + 255) / 256, 1, D.njobs), dim3(256), chi_only ? 0 : 256 * 33 * sizeof(double), st, D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et,
-                     Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride, D.pose_stride);
+  const dim3 grid((D.nE + 255) / 256, 1, D.njobs);
+  const size_t lds = chi_only ? 0 : 256 * 33 * sizeof(double);
+  if (Ed.robust) {                    // (the batched condensed passes are plain: the host never hands them a robust description)
+    RobustArgs rk;
+    rk.kind = Ed.rk_kind; rk.delta = Ed.rk_delta; rk.stats = Ed.rk_stats; rk.delta0 = Ed.rk_delta0; rk.kind0 = Ed.rk_kind0;
+    hipLaunchKernelGGL((k_linearize<false, true, RobustArgs>), grid, dim3(256), lds, st, D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et,
+                       Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride, D.pose_stride, rk);
+    return;
+  }
+  hipLaunchKernelGGL((D.njobs > 1 ? k_linearize<true, false> : k_linearize<false, false>), grid, dim3(256), lds, st, D.nE, Ed.nA,
+                     Ed.n_active, poses, D.ef, D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride,
+                     D.pose_stride);
 }
 
 void launch_chi2(hipStream_t st, const GnDevice& D, double* out) {
@@ -1479,7 +1566,8 @@ void gn_init_kernels() {
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, factor_smem_bytes(kChunkRows + 1));
     for (const void* f : {reinterpret_cast<const void*>(k_front_level<false>), reinterpret_cast<const void*>(k_front_level<true>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(factor_smem_bytes(kChunkRows + 1), 2 * (int)sizeof(UpdTileLds<kFrontW>)));
-    for (const void* f : {reinterpret_cast<const void*>(k_linearize<false>), reinterpret_cast<const void*>(k_linearize<true>)})
+    for (const void* f : {reinterpret_cast<const void*>(k_linearize<false, false>), reinterpret_cast<const void*>(k_linearize<true, false>),
+                          reinterpret_cast<const void*>(k_linearize<false, true, RobustArgs>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 33 * (int)sizeof(double));
     for (const void* f : {reinterpret_cast<const void*>(k_top_block<false>), reinterpret_cast<const void*>(k_top_block<true>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, top_smem_bytes(kTopMaxCols));

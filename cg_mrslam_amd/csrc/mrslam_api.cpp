@@ -106,6 +106,16 @@ struct cgmr_graph {
   int algorithm = CGMR_ALG_GAUSS_NEWTON;   // cgmr_graph_set_algorithm: the optimiser of cgmr_graph_optimize
   bool lm_params_set = false;
   cgmr_lm_params lm_params{};
+  // robust kernels (cgmr_graph_set_edge_robust): kind / delta of every own edge on the host and, from the first setting on, on
+  // the device (rk_dev; grown with d_meas_a); the received edges' class; the per-edge statistics of the last optimize (e2 of
+  // every level-0 edge, then rho1; empty when it ran plain)
+  std::vector<uint8_t> rk_kind;
+  std::vector<double> rk_delta;
+  DevBuf d_rk_kind, d_rk_delta;
+  bool rk_dev = false;
+  int rk_recv_kind = CGMR_RK_NONE;
+  double rk_recv_delta = 1.0;
+  std::vector<double> rk_stats;
   std::vector<double> lm_lambda;      // records of the last Levenberg solve (cgmr_graph_lm_last)
   std::vector<int32_t> lm_trials;
   bool h_poses_fresh = false;         // h_poses holds the estimates as the last optimize() left them
@@ -158,6 +168,25 @@ int dev_grow(cgmr_graph* g, DevBuf& B, size_t used_bytes, size_t need_bytes) {
 }
 
 size_t round256(size_t v) { return (v + 255) & ~size_t(255); }
+
+// the robust kinds / deltas of own edges [first, first + n) to the device arrays (grown to every own edge)
+int rk_upload(cgmr_graph* g, int first, int n) {
+  cgmr_ctx* ctx = g->ctx;
+  if (!ctx) return 0;
+  const size_t nA = g->ef.size(), used = g->rk_dev ? std::min(nA, (size_t)first) : 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = dev_grow(g, g->d_rk_kind, used, nA);
+  if (!rc) rc = dev_grow(g, g->d_rk_delta, 8 * used, 8 * nA);
+  if (rc) return rc;
+  if (!g->rk_dev) { first = 0; n = (int)nA; }
+  if (n > 0) {
+    HIP_TRY(ctx, hipMemcpyAsync(g->d_rk_kind.ptr + first, g->rk_kind.data() + first, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(g->d_rk_delta.ptr + 8 * (size_t)first, g->rk_delta.data() + first, 8 * (size_t)n, hipMemcpyHostToDevice,
+                                ctx->stream));
+  }
+  g->rk_dev = true;
+  return 0;
+}
 
 int alloc_fixed(cgmr_graph* g) {
   cgmr_ctx* ctx = g->ctx;
@@ -375,7 +404,7 @@ void cgmr_graph_destroy(cgmr_graph* g) {
     (void)hipSetDevice(g->ctx->device);
     (void)hipStreamSynchronize(g->ctx->stream);
     (void)side_join_host(g->ctx);
-    for (DevBuf* b : {&g->d_poses, &g->d_meas_a, &g->d_info_a, &g->d_vids, &g->d_work})
+    for (DevBuf* b : {&g->d_poses, &g->d_meas_a, &g->d_info_a, &g->d_vids, &g->d_work, &g->d_rk_kind, &g->d_rk_delta})
       if (b->ptr) (void)hipFree(b->ptr);
     // the blocks this graph's arrays have outgrown (nothing of it is in flight any more: both streams were waited for above)
     auto& gy = g->ctx->graveyard;
@@ -456,6 +485,12 @@ int cgmr_graph_add_edges(cgmr_graph* g, int n, const int32_t* from_ids, const in
     HIP_TRY(ctx, hipMemcpyAsync(g->d_meas_a.ptr + 24 * e0, meas_xyt, 24 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(g->d_info_a.ptr + 48 * e0, info_upper, 48 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   }
+  g->rk_kind.resize(g->ef.size(), CGMR_RK_NONE);
+  g->rk_delta.resize(g->ef.size(), 1.0);
+  if (g->rk_dev && n > 0) {
+    int rc = rk_upload(g, (int)e0, n);
+    if (rc) return rc;
+  }
   rebuild_all_edges(g);
   return CGMR_OK;
 }
@@ -490,6 +525,17 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out) {
   Ed.meas_a = (const double*)g->d_meas_a.ptr; Ed.info_a = (const double*)g->d_info_a.ptr;
   Ed.meas_b = g->d_meas_b; Ed.info_b = g->d_info_b;
   Ed.nA = (int)g->ef.size(); Ed.n_active = nE;
+  g->rk_stats.clear();
+  if (g->rk_dev) {                    // (set once any kernel is: own edges from the device arrays, received ones from the class)
+    Ed.robust = true;
+    Ed.rk_kind = (const uint8_t*)g->d_rk_kind.ptr; Ed.rk_delta = (const double*)g->d_rk_delta.ptr;
+    Ed.rk_kind0 = g->rk_recv_kind; Ed.rk_delta0 = g->rk_recv_delta;
+    if (nE > 0) {
+      int rc = arena_reserve(ctx, ctx->rk_arena, 16 * (size_t)nE + 256);
+      if (rc) return rc;
+      Ed.rk_stats = (double*)ctx->rk_arena.ptr;
+    }
+  }
   const double t0 = wall_s();
   // the gauge vertices of the stars received from the peers (every received edge starts at one): hubs of the ordering
   std::vector<int32_t> hubs;
@@ -521,6 +567,11 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out) {
   }
   ctx->poses_out_host = nullptr;
   g->h_poses_fresh = asked && (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE);
+  if (Ed.rk_stats && (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE)) {
+    g->rk_stats.resize(2 * (size_t)nE);
+    HIP_TRY(ctx, hipMemcpyAsync(g->rk_stats.data(), Ed.rk_stats, 16 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
   if (g->h_poses_fresh) memcpy(g->h_poses.data(), g->pinned_poses, 24 * (size_t)nV);
   g->last_optimize_seconds = wall_s() - t0;
   g->solved_ef = g->all_ef; g->solved_et = g->all_et;
@@ -534,6 +585,34 @@ int cgmr_graph_set_algorithm(cgmr_graph* g, int algorithm, const cgmr_lm_params*
   g->lm_params_set = params != nullptr;
   if (params) g->lm_params = *params;
   return CGMR_OK;
+}
+
+int cgmr_graph_set_edge_robust(cgmr_graph* g, int first, int n, const uint8_t* kind, const double* delta) {
+  if (!g || first < 0 || n < 0 || first + n > (int)g->ef.size() || (n > 0 && !kind)) return CGMR_E_INVALID;
+  for (int k = 0; k < n; k++)
+    if (!robust_valid(kind[k], delta ? delta[k] : 1.0))
+      return gerr(g, CGMR_E_INVALID, "cgmr_graph_set_edge_robust: a kind must be 0..7, its delta finite and > 0 (kind 0 excepted)");
+  for (int k = 0; k < n; k++) { g->rk_kind[first + k] = kind[k]; g->rk_delta[first + k] = delta ? delta[k] : 1.0; }
+  return rk_upload(g, first, n);
+}
+
+int cgmr_graph_set_received_robust(cgmr_graph* g, int kind, double delta) {
+  if (!g) return CGMR_E_INVALID;
+  if (!robust_valid(kind, delta))
+    return gerr(g, CGMR_E_INVALID, "cgmr_graph_set_received_robust: the kind must be 0..7, its delta finite and > 0 (kind 0 excepted)");
+  g->rk_recv_kind = kind;
+  g->rk_recv_delta = kind == CGMR_RK_NONE ? 1.0 : delta;
+  return g->rk_dev ? 0 : rk_upload(g, 0, (int)g->ef.size());
+}
+
+int cgmr_graph_edge_stats(const cgmr_graph* g, int cap, double* edge_chi2_out, double* weight_out) {
+  if (!g || cap < 0) return CGMR_E_INVALID;
+  const int n = (int)(g->rk_stats.size() / 2);
+  for (int k = 0; k < std::min(n, cap); k++) {
+    if (edge_chi2_out) edge_chi2_out[k] = g->rk_stats[k];
+    if (weight_out) weight_out[k] = g->rk_stats[n + k];
+  }
+  return n;
 }
 
 int cgmr_graph_lm_last(const cgmr_graph* g, int cap, double* lambda_out, int32_t* trials_out) {

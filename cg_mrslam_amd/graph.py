@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import CGMR_E_CHOLESKY_BASE, Context
+from ._lib import CGMR_E_CHOLESKY_BASE, Context, robust_arrays, robust_code
 
 ODOM_INFO = (100.0, 100.0, 1000.0)      # _odominf, src/slam/graph_slam.cpp:72-73
 SM_INFO = (1000.0, 1000.0, 10000.0)     # _SMinf,   src/slam/graph_slam.cpp:75-76
@@ -172,6 +172,11 @@ class GraphSLAM:
         self.last_lambdas = None
         self.last_trials = None
         self.last_iterations = 0
+        # robust kernels per edge of the graph (setRobustKernel): C codes and deltas, None while none is set
+        self._rk_kind = None
+        self._rk_delta = None
+        self.last_edge_chi2 = None
+        self.last_weights = None
 
     def optimize(self, nrunnings: int) -> None:
         """``nrunnings`` iterations on the level-0 edges; estimates updated in place.  Returns nothing and never raises on
@@ -179,17 +184,79 @@ class GraphSLAM:
         the iterations run (g2o's SparseOptimizer::optimize return value)."""
         g = self.graph
         ef, et, meas, info = g.level0()
+        rk = self._robust_level0()
+        self.last_edge_chi2 = self.last_weights = None
         if self.algorithm == "levenberg":
-            rc, poses, chi2, lam, tri, done = self.ctx.lm_optimize(g.poses, g.fixed, ef, et, meas, info, int(nrunnings),
-                                                                   **self.lm_params)
+            if rk is None:
+                rc, poses, chi2, lam, tri, done = self.ctx.lm_optimize(g.poses, g.fixed, ef, et, meas, info, int(nrunnings),
+                                                                       **self.lm_params)
+            else:
+                rc, poses, chi2, lam, tri, done, self.last_edge_chi2, self.last_weights = self.ctx.lm_optimize_robust(
+                    g.poses, g.fixed, ef, et, meas, info, int(nrunnings), *rk, **self.lm_params)
             self.last_lambdas, self.last_trials, self.last_iterations = lam[:done], tri[:done], done
         else:
-            rc, poses, chi2 = self.ctx.gn_optimize(g.poses, g.fixed, ef, et, meas, info, int(nrunnings),
-                                                   raise_on_cholesky=False)
+            if rk is None:
+                rc, poses, chi2 = self.ctx.gn_optimize(g.poses, g.fixed, ef, et, meas, info, int(nrunnings),
+                                                       raise_on_cholesky=False)
+            else:
+                rc, poses, chi2, self.last_edge_chi2, self.last_weights = self.ctx.gn_optimize_robust(
+                    g.poses, g.fixed, ef, et, meas, info, int(nrunnings), *rk, raise_on_cholesky=False)
             self.last_iterations = int(nrunnings) if rc == 0 else CGMR_E_CHOLESKY_BASE - rc
         g.poses[:] = poses
         self.last_chi2 = chi2
         self.last_status = rc
+
+    # ---------------------------------------------------------------- robust kernels (g2o's edge->setRobustKernel)
+    def setRobustKernel(self, name, delta: float = 1.0, edges=None) -> None:     # noqa: N802 (g2o spelling)
+        """``edge->setRobustKernel(new RobustKernel<name>); kernel->setDelta(delta)`` for the graph's edges ``edges`` (indices
+        into its edge list; None: every level-0 edge).  ``name``: "Huber", "PseudoHuber", "Cauchy", "Welsch", "Tukey",
+        "Saturated", "DCS" (delta = phi) or "none"; anything else, or a delta that is not finite and > 0, raises
+        ValueError.  optimize() then minimises the robust chi2; chi2() stays the plain one (g2o's activeChi2)."""
+        code = robust_code(name)
+        n = self.graph.n_edges
+        idx = np.flatnonzero(self.graph.edge_level == 0) if edges is None else np.asarray(edges, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= n):
+            raise ValueError(f"edge index out of range 0..{n - 1}")
+        robust_arrays(code, delta, idx.size)                       # (the delta's check)
+        self._grow_robust()
+        self._rk_kind[idx] = code
+        self._rk_delta[idx] = float(delta) if code else 1.0
+
+    def clearRobustKernels(self) -> None:     # noqa: N802
+        """Every edge back to no robust kernel."""
+        self._rk_kind = self._rk_delta = None
+
+    def edgeWeights(self):     # noqa: N802
+        """rho1 of every level-0 edge (level0() order) at the estimate the last optimize() returned; None when that ran with
+        no robust kernel set."""
+        return self.last_weights
+
+    def robustChi2(self) -> float:     # noqa: N802
+        """g2o's activeRobustChi2 at the current estimates: the sum of rho0 over the level-0 edges (chi2() with no kernel)."""
+        g = self.graph
+        ef, et, meas, info = g.level0()
+        rk = self._robust_level0()
+        if rk is None:
+            return self.chi2()
+        _, _, chi2, _, _ = self.ctx.gn_optimize_robust(g.poses, g.fixed, ef, et, meas, info, 0, *rk)
+        return float(chi2[0])
+
+    def _grow_robust(self):
+        n = self.graph.n_edges
+        if self._rk_kind is None:
+            self._rk_kind, self._rk_delta = np.zeros(n, dtype=np.uint8), np.ones(n)
+        elif len(self._rk_kind) != n:                              # (edges added since: no kernel; a graph loaded since: its own)
+            m = min(len(self._rk_kind), n)
+            self._rk_kind = np.concatenate([self._rk_kind[:m], np.zeros(n - m, dtype=np.uint8)])
+            self._rk_delta = np.concatenate([self._rk_delta[:m], np.ones(n - m)])
+
+    def _robust_level0(self):
+        """(kinds, deltas) of the level-0 edges, or None when no edge has a kernel (the plain path)."""
+        if self._rk_kind is None or not self._rk_kind.any():
+            return None
+        self._grow_robust()
+        m = self.graph.edge_level == 0
+        return self._rk_kind[m], self._rk_delta[m]
 
     def currentLambda(self) -> float:     # noqa: N802 (g2o spelling)
         """OptimizationAlgorithmLevenberg::currentLambda: lambda after the last iteration of the last optimize (0 before

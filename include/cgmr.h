@@ -124,6 +124,61 @@ int cgmr_lm_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8
 /* The last cgmr_lm_optimize* call on this context: out[0] = host waits for the device, out[1] = trials run. */
 int cgmr_lm_last_stats(const cgmr_ctx* ctx, int64_t out[2]);
 
+/* Robust kernels (C ABI version >= 105; g2o's edge->setRobustKernel(new RobustKernelX) with setDelta(delta)) [g2o-recalled].  An edge with error e
+ * and information O at the linearisation point has e2 = e^T O e; its kernel maps e2 to (rho0, rho1).  The edge then adds
+ * J^T (rho1 O) J to H and -rho1 J^T O e to b (g2o's robustInformation; the second-order term is left out, as in g2o), and
+ * rho0 to the objective.  The chi2 of the robust entry points is the robust chi2, the sum of rho0 over the edges (g2o's
+ * activeRobustChi2); it equals the plain chi2 when every edge is CGMR_RK_NONE.  With d2 = delta * delta:
+ *   CGMR_RK_NONE          rho0 = e2, rho1 = 1
+ *   CGMR_RK_HUBER         e2 <= d2: (e2, 1); else (2 delta sqrt(e2) - d2, delta / sqrt(e2))
+ *   CGMR_RK_PSEUDO_HUBER  a = sqrt(1 + e2 / d2): (2 d2 (a - 1), 1 / a)
+ *   CGMR_RK_CAUCHY        a = 1 + e2 / d2: (d2 log(a), 1 / a)
+ *   CGMR_RK_WELSCH        a = exp(-e2 / d2): (d2 (1 - a), a)
+ *   CGMR_RK_TUKEY         sqrt(e2) <= delta, a = 1 - e2 / d2: (d2 (1 - a^3) / 3, a^2); else (d2 / 3, 0)
+ *   CGMR_RK_SATURATED     e2 <= d2: (e2, 1); else (d2, 0)
+ *   CGMR_RK_DCS           delta = phi, s = 2 phi / (phi + e2): s >= 1: (e2, 1); else (s^2 e2, s^2)
+ * delta must be finite and > 0 for every kind but CGMR_RK_NONE; anything else (an unknown kind included) is CGMR_E_INVALID,
+ * returned before anything is queued.  g2o's Fair and GemanMcClure kernels are not offered: their formulas are not recalled
+ * reliably enough to pin them down.
+ * A zero weight (Tukey, Saturated, Welsch underflowing) can leave a free vertex whose edges all weigh 0: its block of H is
+ * singular, as in g2o.  Gauss-Newton then returns CGMR_E_CHOLESKY_BASE - it with the poses at the last good update;
+ * Levenberg-Marquardt rejects the trial.
+ * Out of scope: the marginals, cgmr_covariance_estimate, cgmr_condense* and the robot graph's condensed graphs use the plain
+ * information whatever kernels are set (g2o would use the robust H there). */
+#define CGMR_RK_NONE 0
+#define CGMR_RK_HUBER 1
+#define CGMR_RK_PSEUDO_HUBER 2
+#define CGMR_RK_CAUCHY 3
+#define CGMR_RK_WELSCH 4
+#define CGMR_RK_TUKEY 5
+#define CGMR_RK_SATURATED 6
+#define CGMR_RK_DCS 7
+typedef struct cgmr_robust {
+  const uint8_t* kind;      /* [nE] nullable: every edge takes default_kind (host memory, device memory for the _dev entry points) */
+  const double* delta;      /* [nE] nullable: every edge takes default_delta (the same memory as kind) */
+  int32_t default_kind;
+  double default_delta;
+  double* edge_chi2_out;    /* [nE] host, nullable: e^T O e of every edge at the returned estimate */
+  double* weight_out;       /* [nE] host, nullable: rho1 there */
+} cgmr_robust;
+/* cgmr_gn_optimize / cgmr_lm_optimize and their _dev variants with robust kernels.  rk == NULL: the plain call, bit for bit.
+ * The statistics are those of the estimate the call returns (Gauss-Newton: also after a failed Cholesky, at the poses as
+ * left).  The _dev variants read kind / delta back once to check them. */
+int cgmr_gn_optimize_robust(cgmr_ctx* ctx, int nV, double* poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                            const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int iters,
+                            double* chi2_out, const cgmr_robust* rk);
+int cgmr_gn_optimize_robust_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8_t* fixed, int nE,
+                                const int32_t* from_idx, const int32_t* to_idx, const double* d_meas_xyt,
+                                const double* d_info_upper, int iters, double* chi2_out, const cgmr_robust* rk);
+int cgmr_lm_optimize_robust(cgmr_ctx* ctx, int nV, double* poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                            const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int iters,
+                            const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
+                            int32_t* iters_done, const cgmr_robust* rk);
+int cgmr_lm_optimize_robust_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8_t* fixed, int nE,
+                                const int32_t* from_idx, const int32_t* to_idx, const double* d_meas_xyt,
+                                const double* d_info_upper, int iters, const cgmr_lm_params* params, double* chi2_out,
+                                double* lambda_out, int32_t* trials_out, int32_t* iters_done, const cgmr_robust* rk);
+
 /* The ordering + symbolic analysis + structure upload of the last analysed edge list stay on the context and are
  * reused by every later call (cgmr_gn_optimize*, cgmr_marginals, cgmr_covariance_estimate, cgmr_condense*) whose
  * (nV, from_idx, to_idx) are exactly the same -- the fixed flags are applied numerically and do not enter the
@@ -475,6 +530,15 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out);
 #define CGMR_ALG_GAUSS_NEWTON 0
 #define CGMR_ALG_LEVENBERG 1
 int cgmr_graph_set_algorithm(cgmr_graph* g, int algorithm, const cgmr_lm_params* params);
+/* Robust kernels of the robot graph (cgmr_robust above), applied by cgmr_graph_optimize under either algorithm: own edges
+ * [first, first + n) by insertion index take kind[k] / delta[k] (host arrays; delta nullable: 1.0, which only kind 0 may
+ * keep); own edges added later take CGMR_RK_NONE.  The received edges take one class, set by cgmr_graph_set_received_robust
+ * (default CGMR_RK_NONE).  The condensed graphs stay plain.  cgmr_graph_edge_stats: e^T O e and rho1 of every level-0 edge at
+ * the estimate of the last cgmr_graph_optimize, own edges first, then the received ones (the order of cgmr_graph_debug_edges);
+ * returns that edge count, 0 when that solve ran with no kernel set. */
+int cgmr_graph_set_edge_robust(cgmr_graph* g, int first, int n, const uint8_t* kind, const double* delta);
+int cgmr_graph_set_received_robust(cgmr_graph* g, int kind, double delta);
+int cgmr_graph_edge_stats(const cgmr_graph* g, int cap, double* edge_chi2_out, double* weight_out);
 int cgmr_graph_lm_last(const cgmr_graph* g, int cap, double* lambda_out, int32_t* trials_out);
 /* estimates of vertices first .. first+n-1 in insertion order */
 int cgmr_graph_get_poses(cgmr_graph* g, int first, int n, double* poses_out);

@@ -397,6 +397,64 @@ class Context:
             self._check(rc)
         return to[:rc].copy(), est[:rc].copy(), iu[:rc].copy(), cov[:rc].copy()
 
+    # robust kernels in the marginals and the condensed graph (include/cgmr.h: cgmr_marginals_robust ...): ``kind`` / ``delta`` as
+    # for gn_optimize_robust; rho1 at the linearisation point of the H that is inverted (the poses given for the marginals, the
+    # spanning-tree guess for covariance_estimate / condense).  Each returns what the plain call does, then (e2 [nE], weights
+    # [nE]) at that point.
+    def marginals_robust(self, poses, fixed, ef, et, meas, info, query, kind="none", delta=1.0):
+        """marginals with robust kernels: (cov, e2, weights)."""
+        poses, ef, et, meas, info = self._graph_args(poses, ef, et, meas, info)
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        query = np.ascontiguousarray(query, dtype=np.int32)
+        rk, e2, w, _keep = self._robust(kind, delta, len(ef))
+        cov = np.zeros((len(query), 3, 3))
+        rc = self.lib.cgmr_marginals_robust(self.h, C.c_int(poses.shape[0]), _ptr(poses), _ptr(fixed), C.c_int(len(ef)),
+                                            _ptr(ef), _ptr(et), _ptr(meas), _ptr(info), C.c_int(len(query)), _ptr(query),
+                                            _ptr(cov), C.byref(rk))
+        self._check(rc)
+        return cov, e2, w
+
+    def marginals_all_robust(self, poses, fixed, ef, et, meas, info, cross=False, kind="none", delta=1.0):
+        """marginals_all with robust kernels: (cov, e2, weights), or (cov, cross, e2, weights) with ``cross=True``."""
+        poses, ef, et, meas, info = self._graph_args(poses, ef, et, meas, info)
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        rk, e2, w, _keep = self._robust(kind, delta, len(ef))
+        cov = np.zeros((poses.shape[0], 3, 3))
+        cr = np.zeros((len(ef), 3, 3)) if cross else None
+        rc = self.lib.cgmr_marginals_all_robust(self.h, C.c_int(poses.shape[0]), _ptr(poses), _ptr(fixed), C.c_int(len(ef)),
+                                                _ptr(ef), _ptr(et), _ptr(meas), _ptr(info), _ptr(cov), _ptr(cr), C.byref(rk))
+        self._check(rc)
+        return (cov, cr, e2, w) if cross else (cov, e2, w)
+
+    def covariance_estimate_robust(self, poses, ef, et, meas, info, gauge, query, kind="none", delta=1.0):
+        """covariance_estimate with robust kernels: (cov, e2, weights)."""
+        poses, ef, et, meas, info = self._graph_args(poses, ef, et, meas, info)
+        query = np.ascontiguousarray(query, dtype=np.int32)
+        rk, e2, w, _keep = self._robust(kind, delta, len(ef))
+        cov = np.zeros((len(query), 3, 3))
+        rc = self.lib.cgmr_covariance_estimate_robust(self.h, C.c_int(poses.shape[0]), _ptr(poses), C.c_int(len(ef)), _ptr(ef),
+                                                      _ptr(et), _ptr(meas), _ptr(info), C.c_int(int(gauge)),
+                                                      C.c_int(len(query)), _ptr(query), _ptr(cov), C.byref(rk))
+        self._check(rc)
+        return cov, e2, w
+
+    def condense_robust(self, poses, ef, et, meas, info, gauge, query, kind="none", delta=1.0):
+        """condense with robust kernels: (to, est, info_upper, cov, e2, weights)."""
+        poses, ef, et, meas, info = self._graph_args(poses, ef, et, meas, info)
+        query = np.ascontiguousarray(query, dtype=np.int32)
+        rk, e2, w, _keep = self._robust(kind, delta, len(ef))
+        n = max(len(query), 1)
+        to = np.zeros(n, dtype=np.int32)
+        est = np.zeros((n, 3))
+        iu = np.zeros((n, 6))
+        cov = np.zeros((n, 3, 3))
+        rc = self.lib.cgmr_condense_robust(self.h, C.c_int(poses.shape[0]), _ptr(poses), C.c_int(len(ef)), _ptr(ef), _ptr(et),
+                                           _ptr(meas), _ptr(info), C.c_int(int(gauge)), C.c_int(len(query)), _ptr(query),
+                                           _ptr(to), _ptr(est), _ptr(iu), _ptr(cov), C.byref(rk))
+        if rc < 0:
+            self._check(rc)
+        return to[:rc].copy(), est[:rc].copy(), iu[:rc].copy(), cov[:rc].copy(), e2, w
+
     def set_symbolic_cache(self, on: bool):
         """Reuse of the ordering / symbolic analysis / structure upload across calls on the same edge list (default on)."""
         self._check(self.lib.cgmr_set_symbolic_cache(self.h, C.c_int(1 if on else 0)))

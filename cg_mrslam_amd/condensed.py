@@ -163,6 +163,11 @@ class RobotGraph:
         _, _, code, d = robust_arrays(kind, delta, 1)
         self._check(self.lib.cgmr_graph_set_received_robust(self.h, C.c_int(code), C.c_double(d if code else 1.0)))
 
+    def set_condensed_robust(self, on: bool):
+        """Build every condensed graph with the own edges' robust kernels (set_edge_robust), rho1 taken at each graph's
+        spanning-tree guess (cgmr_graph_set_condensed_robust; default off: the plain condensed graphs, byte for byte)."""
+        self._check(self.lib.cgmr_graph_set_condensed_robust(self.h, C.c_int(1 if on else 0)))
+
     def edge_stats(self):
         """(e2, weights) of every level-0 edge at the estimate of the last optimize, own edges first, then the received ones
         (debug_edges order); None when that solve ran with no kernel set."""

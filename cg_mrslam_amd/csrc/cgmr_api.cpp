@@ -980,6 +980,57 @@ void initial_guess_host(int nV, double* poses, const uint8_t* fixed, int nE, con
   }
 }
 
+// The robust description of an entry point (include/cgmr.h: cgmr_robust) into Ed, checked before anything is queued.  The host
+// entry points' kind / delta arrays are staged through rk_arena; the device ones are read back once to be checked.  The
+// statistics (2 nE doubles: e2, then rho1) land in rk_arena behind them.  rk == nullptr: nothing (the plain call).
+static int robust_setup(cgmr_ctx* ctx, const cgmr_robust* rk, int nE, bool dev, GnEdges& Ed, const char* who) {
+  if (!rk) return 0;
+  const size_t n = (size_t)std::max(nE, 0);
+  std::vector<uint8_t> hk;
+  std::vector<double> hd;
+  const uint8_t* ck = rk->kind;
+  const double* cd = rk->delta;
+  if (dev && n > 0 && (rk->kind || rk->delta)) {
+    if (rk->kind) { hk.resize(n); HIP_TRY(ctx, hipMemcpyAsync(hk.data(), rk->kind, n, hipMemcpyDeviceToHost, ctx->stream)); ck = hk.data(); }
+    if (rk->delta) { hd.resize(n); HIP_TRY(ctx, hipMemcpyAsync(hd.data(), rk->delta, 8 * n, hipMemcpyDeviceToHost, ctx->stream)); cd = hd.data(); }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  bool ok = rk->default_kind >= CGMR_RK_NONE && rk->default_kind <= CGMR_RK_DCS;
+  if (ok && !rk->kind && !rk->delta) ok = robust_valid(rk->default_kind, rk->default_delta);
+  for (size_t k = 0; ok && k < n && (ck || cd); k++)
+    ok = robust_valid(ck ? ck[k] : rk->default_kind, cd ? cd[k] : rk->default_delta);
+  if (!ok)
+    return set_err(ctx, CGMR_E_INVALID, "%s: a robust kernel kind must be 0..7, its delta finite and > 0 (kind 0 excepted)", who);
+  const bool stats = n > 0 && (rk->edge_chi2_out || rk->weight_out);
+  const size_t ok_ = 0, od = (n + 255) & ~size_t(255), os = od + ((8 * n + 255) & ~size_t(255));
+  if (stats || (!dev && (rk->kind || rk->delta))) {
+    int rc = arena_reserve(ctx, ctx->rk_arena, os + 16 * n + 256);
+    if (rc) return rc;
+  }
+  char* d = ctx->rk_arena.ptr;
+  Ed.robust = true;
+  Ed.rk_kind0 = rk->default_kind;
+  Ed.rk_delta0 = rk->default_delta;
+  if (dev) {
+    Ed.rk_kind = rk->kind;
+    Ed.rk_delta = rk->delta;
+  } else {
+    if (rk->kind && n > 0) { HIP_TRY(ctx, hipMemcpyAsync(d + ok_, rk->kind, n, hipMemcpyHostToDevice, ctx->stream)); Ed.rk_kind = (const uint8_t*)(d + ok_); }
+    if (rk->delta && n > 0) { HIP_TRY(ctx, hipMemcpyAsync(d + od, rk->delta, 8 * n, hipMemcpyHostToDevice, ctx->stream)); Ed.rk_delta = (const double*)(d + od); }
+  }
+  Ed.rk_stats = stats ? (double*)(d + os) : nullptr;
+  return 0;
+}
+
+// the statistics of the call's final pass to the caller's host arrays
+static int robust_stats_out(cgmr_ctx* ctx, const cgmr_robust* rk, int nE, const GnEdges& Ed) {
+  if (!rk || !Ed.rk_stats) return 0;
+  if (rk->edge_chi2_out) HIP_TRY(ctx, hipMemcpyAsync(rk->edge_chi2_out, Ed.rk_stats, 8 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
+  if (rk->weight_out) HIP_TRY(ctx, hipMemcpyAsync(rk->weight_out, Ed.rk_stats + nE, 8 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 // The pass of the marginals entry points: run_pass() queues gn_pass(.., write_l11c) and what reads the factor, reads the
 // status words back into status4 and synchronises.  The poses at dp are `work` (nV of them) when it starts.
 template <typename RunPass>
@@ -1018,13 +1069,19 @@ int marginal_pass(cgmr_ctx* ctx, double* dp, const double* work, int nV, int* st
 //   mode 0: marginals at `poses` with `fixed`;  mode 1: covariance estimate (gauge);  mode 2: condense (gauge)
 int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uint8_t* fixed_in, int nE,
                     const int32_t* ef, const int32_t* et, const double* meas, const double* info, int gauge, int nK,
-                    const int32_t* query, int32_t* to_out, double* est_out, double* info_out, double* cov_out) {
+                    const int32_t* query, int32_t* to_out, double* est_out, double* info_out, double* cov_out,
+                    const cgmr_robust* rk) {
   if (nV <= 0 || nE < 0 || nK < 0 || !poses || (nE > 0 && (!ef || !et || !meas || !info)) || (nK > 0 && !query))
     return set_err(ctx, CGMR_E_INVALID, "marginals: null or negative argument");
   if (mode != 0 && (gauge < 0 || gauge >= nV)) return set_err(ctx, CGMR_E_INVALID, "gauge index out of range");
   for (int k = 0; k < nK; k++)
     if (query[k] < 0 || query[k] >= nV) return set_err(ctx, CGMR_E_INVALID, "query index out of range");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // robust kernels: rho1 at the pass's linearisation point (the poses given, or the spanning-tree guess of modes 1 and 2)
+  GnEdges Ed;
+  int rc = robust_setup(ctx, rk, nE, false, Ed, mode == 0 ? "cgmr_marginals_robust" : mode == 1 ? "cgmr_covariance_estimate_robust"
+                                                                                                  : "cgmr_condense_robust");
+  if (rc) return rc;
   std::vector<uint8_t> fixed(nV, 0);
   std::vector<double> work(poses, poses + 3 * (size_t)nV);             // pushState: the caller's poses stay untouched
   if (mode == 0) { if (!fixed_in) return set_err(ctx, CGMR_E_INVALID, "fixed flags missing"); fixed.assign(fixed_in, fixed_in + nV); }
@@ -1038,7 +1095,7 @@ int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const 
   const int nq = (int)q.size();
   if (cov_out && mode != 2) memset(cov_out, 0, sizeof(double) * 9 * (size_t)nK);
   Symbolic& S = ctx->sym;
-  int rc = prepare_structure(ctx, nV, nE, ef, et, 1);
+  rc = prepare_structure(ctx, nV, nE, ef, et, 1);
   if (rc) return rc;
   rc = prepare_pass(ctx, fixed.data(), nE, ef, et, nE, 0, 1);
   if (rc) return rc;
@@ -1068,7 +1125,6 @@ int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const 
   double* dp = (double*)(d + o_p);
   // the Hessian of this iteration (linearised at the initial guess) is what computeMarginals sees [g2o-recalled];
   // for the condensed graph the iteration is completed first: the factor stays valid, the poses move on
-  GnEdges Ed;
   Ed.meas_a = (const double*)(d + o_m); Ed.info_a = (const double*)(d + o_i); Ed.nA = nE; Ed.n_active = nE;
   int status4[4] = {0, 0, 0, 0};
   std::vector<double> cov(9 * (size_t)nq);
@@ -1091,6 +1147,8 @@ int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const 
   };
   rc = marginal_pass(ctx, dp, work.data(), nV, status4, run_pass);
   if (rc) return rc;
+  rc = robust_stats_out(ctx, rk, nE, Ed);                            // (also after a failed Cholesky: e2 / rho1 of that H)
+  if (rc) return rc;
   if (status4[0] != 0) return set_err(ctx, CGMR_E_CHOLESKY_BASE, "Cholesky failed while computing marginals");
   if (mode == 2) {
     for (int k = 0; k < nq; k++) to_out[k] = q[k];
@@ -1106,16 +1164,20 @@ int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const 
 // cgmr_marginals_all: Sigma of every front by selected inversion of the factor (selinv_kernels.hip), then the diagonal block
 // of every vertex and the block of every edge.  The same pass as marginal_driver's mode 0 (gn_pass at `poses` with `fixed`).
 int marginals_all_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
-                         const int32_t* et, const double* meas, const double* info, double* cov_out, double* cross_out) {
+                         const int32_t* et, const double* meas, const double* info, double* cov_out, double* cross_out,
+                         const cgmr_robust* rk) {
   if (nV <= 0 || nE < 0 || !poses || !cov_out || (nE > 0 && (!ef || !et || !meas || !info)))
     return set_err(ctx, CGMR_E_INVALID, "marginals: null or negative argument");
   if (!fixed) return set_err(ctx, CGMR_E_INVALID, "fixed flags missing");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  GnEdges Ed;                                                           // (robust kernels: rho1 at `poses`)
+  int rc = robust_setup(ctx, rk, nE, false, Ed, "cgmr_marginals_all_robust");
+  if (rc) return rc;
   std::vector<double> work(poses, poses + 3 * (size_t)nV);             // the caller's poses stay untouched
   memset(cov_out, 0, 72 * (size_t)nV);
   if (cross_out) memset(cross_out, 0, 72 * (size_t)nE);
   Symbolic& S = ctx->sym;
-  int rc = prepare_structure(ctx, nV, nE, ef, et, 1);
+  rc = prepare_structure(ctx, nV, nE, ef, et, 1);
   if (rc) return rc;
   rc = prepare_pass(ctx, fixed, nE, ef, et, nE, 0, 1);
   if (rc) return rc;
@@ -1163,7 +1225,6 @@ int marginals_all_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8
   P.soff = (const int64_t*)(d + o_so);
   P.tiles = (const int32_t*)(d + o_t);
   double* dp = (double*)(d + o_p);
-  GnEdges Ed;
   Ed.meas_a = (const double*)(d + o_m); Ed.info_a = (const double*)(d + o_i); Ed.nA = nE; Ed.n_active = nE;
   int status4[4] = {0, 0, 0, 0};
   auto run_pass = [&]() -> int {
@@ -1180,6 +1241,8 @@ int marginals_all_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8
   };
   rc = marginal_pass(ctx, dp, work.data(), nV, status4, run_pass);
   if (rc) return rc;
+  rc = robust_stats_out(ctx, rk, nE, Ed);
+  if (rc) return rc;
   if (status4[0] != 0) {
     memset(cov_out, 0, 72 * (size_t)nV);
     if (cross_out) memset(cross_out, 0, 72 * (size_t)nE);
@@ -1195,7 +1258,7 @@ using namespace cgmr;
 
 extern "C" {
 
-int cgmr_version(void) { return 105; }   // 105: cgmr_*_optimize_robust*, cgmr_graph_set_edge_robust / _set_received_robust / _edge_stats added; 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
+int cgmr_version(void) { return 105; }   // 105: cgmr_*_optimize_robust*, cgmr_graph_set_edge_robust / _set_received_robust / _edge_stats added, later (same number: callers find them by their symbols) cgmr_marginals_robust, cgmr_marginals_all_robust, cgmr_covariance_estimate_robust, cgmr_condense_robust, cgmr_graph_set_condensed_robust; 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
 
 int cgmr_ctx_create(int device, void* hip_stream, cgmr_ctx** out) {
   if (!out) return CGMR_E_INVALID;
@@ -1267,57 +1330,6 @@ int cgmr_ctx_synchronize(cgmr_ctx* ctx) {
   if (!ctx) return CGMR_E_INVALID;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return CGMR_OK;
-}
-
-// The robust description of an entry point (include/cgmr.h: cgmr_robust) into Ed, checked before anything is queued.  The host
-// entry points' kind / delta arrays are staged through rk_arena; the device ones are read back once to be checked.  The
-// statistics (2 nE doubles: e2, then rho1) land in rk_arena behind them.  rk == nullptr: nothing (the plain call).
-static int robust_setup(cgmr_ctx* ctx, const cgmr_robust* rk, int nE, bool dev, GnEdges& Ed, const char* who) {
-  if (!rk) return 0;
-  const size_t n = (size_t)std::max(nE, 0);
-  std::vector<uint8_t> hk;
-  std::vector<double> hd;
-  const uint8_t* ck = rk->kind;
-  const double* cd = rk->delta;
-  if (dev && n > 0 && (rk->kind || rk->delta)) {
-    if (rk->kind) { hk.resize(n); HIP_TRY(ctx, hipMemcpyAsync(hk.data(), rk->kind, n, hipMemcpyDeviceToHost, ctx->stream)); ck = hk.data(); }
-    if (rk->delta) { hd.resize(n); HIP_TRY(ctx, hipMemcpyAsync(hd.data(), rk->delta, 8 * n, hipMemcpyDeviceToHost, ctx->stream)); cd = hd.data(); }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  bool ok = rk->default_kind >= CGMR_RK_NONE && rk->default_kind <= CGMR_RK_DCS;
-  if (ok && !rk->kind && !rk->delta) ok = robust_valid(rk->default_kind, rk->default_delta);
-  for (size_t k = 0; ok && k < n && (ck || cd); k++)
-    ok = robust_valid(ck ? ck[k] : rk->default_kind, cd ? cd[k] : rk->default_delta);
-  if (!ok)
-    return set_err(ctx, CGMR_E_INVALID, "%s: a robust kernel kind must be 0..7, its delta finite and > 0 (kind 0 excepted)", who);
-  const bool stats = n > 0 && (rk->edge_chi2_out || rk->weight_out);
-  const size_t ok_ = 0, od = (n + 255) & ~size_t(255), os = od + ((8 * n + 255) & ~size_t(255));
-  if (stats || (!dev && (rk->kind || rk->delta))) {
-    int rc = arena_reserve(ctx, ctx->rk_arena, os + 16 * n + 256);
-    if (rc) return rc;
-  }
-  char* d = ctx->rk_arena.ptr;
-  Ed.robust = true;
-  Ed.rk_kind0 = rk->default_kind;
-  Ed.rk_delta0 = rk->default_delta;
-  if (dev) {
-    Ed.rk_kind = rk->kind;
-    Ed.rk_delta = rk->delta;
-  } else {
-    if (rk->kind && n > 0) { HIP_TRY(ctx, hipMemcpyAsync(d + ok_, rk->kind, n, hipMemcpyHostToDevice, ctx->stream)); Ed.rk_kind = (const uint8_t*)(d + ok_); }
-    if (rk->delta && n > 0) { HIP_TRY(ctx, hipMemcpyAsync(d + od, rk->delta, 8 * n, hipMemcpyHostToDevice, ctx->stream)); Ed.rk_delta = (const double*)(d + od); }
-  }
-  Ed.rk_stats = stats ? (double*)(d + os) : nullptr;
-  return 0;
-}
-
-// the statistics of the call's final pass to the caller's host arrays
-static int robust_stats_out(cgmr_ctx* ctx, const cgmr_robust* rk, int nE, const GnEdges& Ed) {
-  if (!rk || !Ed.rk_stats) return 0;
-  if (rk->edge_chi2_out) HIP_TRY(ctx, hipMemcpyAsync(rk->edge_chi2_out, Ed.rk_stats, 8 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
-  if (rk->weight_out) HIP_TRY(ctx, hipMemcpyAsync(rk->weight_out, Ed.rk_stats + nE, 8 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return 0;
 }
 
 static int gn_optimize_dev_impl(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
@@ -1526,27 +1538,57 @@ int cgmr_marginals(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fi
                    const int32_t* et, const double* meas, const double* info, int nK, const int32_t* query,
                    double* cov_out) {
   if (!ctx || !cov_out) return CGMR_E_INVALID;
-  return marginal_driver(ctx, 0, nV, poses, fixed, nE, ef, et, meas, info, -1, nK, query, nullptr, nullptr, nullptr, cov_out);
+  return marginal_driver(ctx, 0, nV, poses, fixed, nE, ef, et, meas, info, -1, nK, query, nullptr, nullptr, nullptr, cov_out, nullptr);
 }
 
 int cgmr_marginals_all(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
                        const int32_t* et, const double* meas, const double* info, double* cov_out, double* cross_out) {
   if (!ctx) return CGMR_E_INVALID;
-  return marginals_all_driver(ctx, nV, poses, fixed, nE, ef, et, meas, info, cov_out, cross_out);
+  return marginals_all_driver(ctx, nV, poses, fixed, nE, ef, et, meas, info, cov_out, cross_out, nullptr);
 }
 
 int cgmr_covariance_estimate(cgmr_ctx* ctx, int nV, const double* poses, int nE, const int32_t* ef, const int32_t* et,
                              const double* meas, const double* info, int gauge, int nK, const int32_t* query,
                              double* cov_out) {
   if (!ctx || !cov_out) return CGMR_E_INVALID;
-  return marginal_driver(ctx, 1, nV, poses, nullptr, nE, ef, et, meas, info, gauge, nK, query, nullptr, nullptr, nullptr, cov_out);
+  return marginal_driver(ctx, 1, nV, poses, nullptr, nE, ef, et, meas, info, gauge, nK, query, nullptr, nullptr, nullptr, cov_out,
+                         nullptr);
 }
 
 int cgmr_condense(cgmr_ctx* ctx, int nV, const double* poses, int nE, const int32_t* ef, const int32_t* et,
                   const double* meas, const double* info, int gauge, int nK, const int32_t* query, int32_t* to_out,
                   double* est_out, double* info_out, double* cov_out) {
   if (!ctx || !to_out || !est_out || !info_out) return CGMR_E_INVALID;
-  return marginal_driver(ctx, 2, nV, poses, nullptr, nE, ef, et, meas, info, gauge, nK, query, to_out, est_out, info_out, cov_out);
+  return marginal_driver(ctx, 2, nV, poses, nullptr, nE, ef, et, meas, info, gauge, nK, query, to_out, est_out, info_out, cov_out,
+                         nullptr);
+}
+
+int cgmr_marginals_robust(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                          const int32_t* et, const double* meas, const double* info, int nK, const int32_t* query,
+                          double* cov_out, const cgmr_robust* rk) {
+  if (!ctx || !cov_out) return CGMR_E_INVALID;
+  return marginal_driver(ctx, 0, nV, poses, fixed, nE, ef, et, meas, info, -1, nK, query, nullptr, nullptr, nullptr, cov_out, rk);
+}
+
+int cgmr_marginals_all_robust(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                              const int32_t* et, const double* meas, const double* info, double* cov_out, double* cross_out,
+                              const cgmr_robust* rk) {
+  if (!ctx) return CGMR_E_INVALID;
+  return marginals_all_driver(ctx, nV, poses, fixed, nE, ef, et, meas, info, cov_out, cross_out, rk);
+}
+
+int cgmr_covariance_estimate_robust(cgmr_ctx* ctx, int nV, const double* poses, int nE, const int32_t* ef, const int32_t* et,
+                                    const double* meas, const double* info, int gauge, int nK, const int32_t* query,
+                                    double* cov_out, const cgmr_robust* rk) {
+  if (!ctx || !cov_out) return CGMR_E_INVALID;
+  return marginal_driver(ctx, 1, nV, poses, nullptr, nE, ef, et, meas, info, gauge, nK, query, nullptr, nullptr, nullptr, cov_out, rk);
+}
+
+int cgmr_condense_robust(cgmr_ctx* ctx, int nV, const double* poses, int nE, const int32_t* ef, const int32_t* et,
+                         const double* meas, const double* info, int gauge, int nK, const int32_t* query, int32_t* to_out,
+                         double* est_out, double* info_out, double* cov_out, const cgmr_robust* rk) {
+  if (!ctx || !to_out || !est_out || !info_out) return CGMR_E_INVALID;
+  return marginal_driver(ctx, 2, nV, poses, nullptr, nE, ef, et, meas, info, gauge, nK, query, to_out, est_out, info_out, cov_out, rk);
 }
 
 int cgmr_set_symbolic_cache(cgmr_ctx* ctx, int on) {

@@ -97,6 +97,9 @@ __device__ __forceinline__ double d_normalize_theta(double t) {
 // only and is exact for rho1 = 1.  A plain solve runs the instance without it, whose code is what it always was: the robust
 // description is a trailing parameter pack, empty in the plain instances (an argument of an empty type would still take
 // 8 bytes of the argument segment and move the implicit arguments behind it).
+// BATCH and ROBUST together (the robot graph's robust condensed graphs, cgmr_graph_set_condensed_robust): every job takes its
+// rho1 from its own poses (moved by the pose stride); kind / delta are the jobs' shared edge list's and are not moved; the
+// statistics are never written (the host rejects a batch with stats).
 struct RobustArgs {
   const uint8_t* kind;   // [nA] or null: edges [0, nA) take kind[k]; every other edge takes kind0
   const double* delta;   // [nA] or null: edges [0, nA) take delta[k]; every other edge takes delta0
@@ -192,7 +195,8 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
       const double delta = rk.delta && k < nA ? rk.delta[k] : rk.delta0;
       const double rho0 = robustify(kind, delta, e2, rho1);
       ch = live ? rho0 : 0.0;
-      if (rk.stats && k0 < nE) { rk.stats[k] = e2; rk.stats[E + k] = rho1; }
+      if constexpr (!BATCH)                                              // (a batch: no statistics, the host passes none)
+        if (rk.stats && k0 < nE) { rk.stats[k] = e2; rk.stats[E + k] = rho1; }
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) ch += __shfl_xor(ch, m, 64);
@@ -1533,11 +1537,13 @@ void launch_linearize(hipStream_t st, const GnDevice& D, const double* poses, co
   gn_init_kernels();
   const dim3 grid((D.nE + 255) / 256, 1, D.njobs);
   const size_t lds = chi_only ? 0 : 256 * 33 * sizeof(double);
-  if (Ed.robust) {                    // (the batched condensed passes are plain: the host never hands them a robust description)
+  if (Ed.robust) {                    // (a batch takes no statistics: run_cond_jobs never asks for them, the batched instance writes none)
     RobustArgs rk;
-    rk.kind = Ed.rk_kind; rk.delta = Ed.rk_delta; rk.stats = Ed.rk_stats; rk.delta0 = Ed.rk_delta0; rk.kind0 = Ed.rk_kind0;
-    hipLaunchKernelGGL((k_linearize<false, true, RobustArgs>), grid, dim3(256), lds, st, D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et,
-                       Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride, D.pose_stride, rk);
+    rk.kind = Ed.rk_kind; rk.delta = Ed.rk_delta; rk.stats = D.njobs > 1 ? nullptr : Ed.rk_stats; rk.delta0 = Ed.rk_delta0;
+    rk.kind0 = Ed.rk_kind0;
+    hipLaunchKernelGGL((D.njobs > 1 ? k_linearize<true, true, RobustArgs> : k_linearize<false, true, RobustArgs>), grid, dim3(256), lds,
+                       st, D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only,
+                       D.job_stride, D.pose_stride, rk);
     return;
   }
   hipLaunchKernelGGL((D.njobs > 1 ? k_linearize<true, false> : k_linearize<false, false>), grid, dim3(256), lds, st, D.nE, Ed.nA,
@@ -1567,7 +1573,8 @@ void gn_init_kernels() {
     for (const void* f : {reinterpret_cast<const void*>(k_front_level<false>), reinterpret_cast<const void*>(k_front_level<true>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(factor_smem_bytes(kChunkRows + 1), 2 * (int)sizeof(UpdTileLds<kFrontW>)));
     for (const void* f : {reinterpret_cast<const void*>(k_linearize<false, false>), reinterpret_cast<const void*>(k_linearize<true, false>),
-                          reinterpret_cast<const void*>(k_linearize<false, true, RobustArgs>)})
+                          reinterpret_cast<const void*>(k_linearize<false, true, RobustArgs>),
+                          reinterpret_cast<const void*>(k_linearize<true, true, RobustArgs>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 33 * (int)sizeof(double));
     for (const void* f : {reinterpret_cast<const void*>(k_top_block<false>), reinterpret_cast<const void*>(k_top_block<true>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, top_smem_bytes(kTopMaxCols));

@@ -116,6 +116,7 @@ struct cgmr_graph {
   int rk_recv_kind = CGMR_RK_NONE;
   double rk_recv_delta = 1.0;
   std::vector<double> rk_stats;
+  bool cond_robust = false;           // cgmr_graph_set_condensed_robust: the condensed graphs take the own edges' kernels
   std::vector<double> lm_lambda;      // records of the last Levenberg solve (cgmr_graph_lm_last)
   std::vector<int32_t> lm_trials;
   bool h_poses_fresh = false;         // h_poses holds the estimates as the last optimize() left them
@@ -179,6 +180,10 @@ int rk_upload(cgmr_graph* g, int first, int n) {
   if (!rc) rc = dev_grow(g, g->d_rk_delta, 8 * used, 8 * nA);
   if (rc) return rc;
   if (!g->rk_dev) { first = 0; n = (int)nA; }
+  if (n > 0 && g->cond_pending) {     // (a condensed batch not waited for may still read the entries rewritten in place)
+    int rj = side_join_stream(ctx, ctx->stream);
+    if (rj) return rj;
+  }
   if (n > 0) {
     HIP_TRY(ctx, hipMemcpyAsync(g->d_rk_kind.ptr + first, g->rk_kind.data() + first, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(g->d_rk_delta.ptr + 8 * (size_t)first, g->rk_delta.data() + first, 8 * (size_t)n, hipMemcpyHostToDevice,
@@ -605,6 +610,12 @@ int cgmr_graph_set_received_robust(cgmr_graph* g, int kind, double delta) {
   return g->rk_dev ? 0 : rk_upload(g, 0, (int)g->ef.size());
 }
 
+int cgmr_graph_set_condensed_robust(cgmr_graph* g, int on) {
+  if (!g) return CGMR_E_INVALID;
+  g->cond_robust = on != 0;
+  return CGMR_OK;
+}
+
 int cgmr_graph_edge_stats(const cgmr_graph* g, int cap, double* edge_chi2_out, double* weight_out) {
   if (!g || cap < 0) return CGMR_E_INVALID;
   const int n = (int)(g->rk_stats.size() / 2);
@@ -747,6 +758,12 @@ int run_cond_jobs(cgmr_graph* g, std::vector<CondJob>& jobs, bool to_wire, std::
   Ed.meas_a = (const double*)g->d_meas_a.ptr; Ed.info_a = (const double*)g->d_info_a.ptr;
   Ed.meas_b = g->d_meas_b; Ed.info_b = g->d_info_b;
   Ed.nA = nA; Ed.n_active = nA;                                  // getMyEdges: the received edges are switched off
+  if (g->cond_robust && g->rk_dev) {  // the own edges' kernels (the received ones are switched off: their class never enters)
+    Ed.robust = true;
+    Ed.rk_kind = (const uint8_t*)g->d_rk_kind.ptr; Ed.rk_delta = (const double*)g->d_rk_delta.ptr;
+    Ed.rk_kind0 = CGMR_RK_NONE; Ed.rk_delta0 = 1.0;
+  }
+  if (Ed.rk_stats && nj > 1) return gerr(g, CGMR_E_INVALID, "a batch of condensed graphs takes no robust statistics");
   std::vector<uint8_t> fixed(nV);
   std::vector<int32_t> qcol;
   // the spanning-tree initial guess of every job (its own gauge as the root: 0.15-0.3 ms of host work each) on the helper

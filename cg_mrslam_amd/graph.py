@@ -271,13 +271,19 @@ class GraphSLAM:
             return 0
         return int(self.last_trials[-1])
 
-    def computeMarginals(self, cross: bool = False):     # noqa: N802 (g2o spelling)
+    def computeMarginals(self, cross: bool = False, robust: bool = False):     # noqa: N802 (g2o spelling)
         """SparseOptimizer::computeMarginals over every vertex, on the level-0 edges at the current estimates:
         ``cov[nV, 3, 3]``, or ``(cov, cross[nE0, 3, 3])`` with ``cross=True`` (the block of each level-0 edge, rows the
-        from vertex, columns the to vertex).  Fixed vertices and their edges get zeros."""
+        from vertex, columns the to vertex).  Fixed vertices and their edges get zeros.  ``robust=True``: H with the kernels of
+        setRobustKernel, every edge's information scaled by rho1 at the current estimates (g2o inverts the H of the last
+        buildSystem, robust weights included); with no kernel set, the plain result."""
         g = self.graph
         ef, et, meas, info = g.level0()
-        return self.ctx.marginals_all(g.poses, g.fixed, ef, et, meas, info, cross=cross)
+        rk = self._robust_level0() if robust else None
+        if rk is None:
+            return self.ctx.marginals_all(g.poses, g.fixed, ef, et, meas, info, cross=cross)
+        out = self.ctx.marginals_all_robust(g.poses, g.fixed, ef, et, meas, info, cross, *rk)
+        return out[:2] if cross else out[0]
 
     def chi2(self) -> float:
         g = self.graph

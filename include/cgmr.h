@@ -143,8 +143,15 @@ int cgmr_lm_last_stats(const cgmr_ctx* ctx, int64_t out[2]);
  * A zero weight (Tukey, Saturated, Welsch underflowing) can leave a free vertex whose edges all weigh 0: its block of H is
  * singular, as in g2o.  Gauss-Newton then returns CGMR_E_CHOLESKY_BASE - it with the poses at the last good update;
  * Levenberg-Marquardt rejects the trial.
- * Out of scope: the marginals, cgmr_covariance_estimate, cgmr_condense* and the robot graph's condensed graphs use the plain
- * information whatever kernels are set (g2o would use the robust H there). */
+ * The marginals and the condensed graphs take the robust H through their own entry points (cgmr_marginals_robust,
+ * cgmr_marginals_all_robust, cgmr_covariance_estimate_robust, cgmr_condense_robust; the robot graph: cgmr_graph_set_condensed_robust),
+ * as g2o's computeMarginals inverts the H of the last buildSystem, robust weights included [g2o-recalled].  rho1 is taken at
+ * the linearisation point of the H that is inverted: the poses passed in for the marginals; for cgmr_covariance_estimate_robust
+ * and cgmr_condense_robust, the spanning-tree initial guess their one Gauss-Newton iteration starts from.  There the robust H
+ * drives the iteration's step as well as the marginals, so a condensed edge's measurement can change, not its information
+ * alone.  At that guess every spanning-tree edge has a zero residual (to rounding) and weight 1 under every kind: an outlier
+ * is down-weighted only when it is off the tree, and how much depends on the residual it shows at the guess, not at the
+ * optimum. */
 #define CGMR_RK_NONE 0
 #define CGMR_RK_HUBER 1
 #define CGMR_RK_PSEUDO_HUBER 2
@@ -376,6 +383,26 @@ int cgmr_covariance_estimate(cgmr_ctx* ctx, int nV, const double* poses_xyt, int
 int cgmr_condense(cgmr_ctx* ctx, int nV, const double* poses_xyt, int nE, const int32_t* from_idx,
                   const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int gauge_idx, int nK,
                   const int32_t* query_idx, int32_t* to_out, double* est_out, double* info_upper_out, double* cov_out);
+/* The four calls above with robust kernels (cgmr_robust; present in C ABI version 105 libraries that export these symbols):
+ * every edge's information is scaled by rho1 at the linearisation point of the H that is inverted (see cgmr_robust above: the
+ * poses given for the marginals, the spanning-tree guess for covariance_estimate / condense).  edge_chi2_out / weight_out
+ * receive e2 and rho1 there (not written when no pass runs: no free vertex, or no query left).  rk == NULL: the plain call,
+ * bit for bit; so is a description whose kinds are all CGMR_RK_NONE.  A bad kind or delta is CGMR_E_INVALID before anything
+ * is queued.  A zero weight that leaves a free vertex's block singular (Tukey, Saturated) gives CGMR_E_CHOLESKY_BASE, as a
+ * singular H does in the plain calls; the bounded-wait time-out is handled as there. */
+int cgmr_marginals_robust(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                          const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt, const double* info_upper,
+                          int nK, const int32_t* query_idx, double* cov_out, const cgmr_robust* rk);
+int cgmr_marginals_all_robust(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                              const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt,
+                              const double* info_upper, double* cov_out, double* cross_out, const cgmr_robust* rk);
+int cgmr_covariance_estimate_robust(cgmr_ctx* ctx, int nV, const double* poses_xyt, int nE, const int32_t* from_idx,
+                                    const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int gauge_idx,
+                                    int nK, const int32_t* query_idx, double* cov_out, const cgmr_robust* rk);
+int cgmr_condense_robust(cgmr_ctx* ctx, int nV, const double* poses_xyt, int nE, const int32_t* from_idx,
+                         const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int gauge_idx, int nK,
+                         const int32_t* query_idx, int32_t* to_out, double* est_out, double* info_upper_out, double* cov_out,
+                         const cgmr_robust* rk);
 
 /* ------------------------------------------------------------------------------------------
  * Generic correlative search (loop-closure / hierarchical / global matching).
@@ -533,12 +560,17 @@ int cgmr_graph_set_algorithm(cgmr_graph* g, int algorithm, const cgmr_lm_params*
 /* Robust kernels of the robot graph (cgmr_robust above), applied by cgmr_graph_optimize under either algorithm: own edges
  * [first, first + n) by insertion index take kind[k] / delta[k] (host arrays; delta nullable: 1.0, which only kind 0 may
  * keep); own edges added later take CGMR_RK_NONE.  The received edges take one class, set by cgmr_graph_set_received_robust
- * (default CGMR_RK_NONE).  The condensed graphs stay plain.  cgmr_graph_edge_stats: e^T O e and rho1 of every level-0 edge at
+ * (default CGMR_RK_NONE).  The condensed graphs stay plain unless cgmr_graph_set_condensed_robust(g, 1) is called (default
+ * off): then every condensed graph the robot builds (cgmr_graph_compute_condensed, _async, the optimal gauge's candidates)
+ * scales its own edges' information by rho1 at its spanning-tree guess, as cgmr_condense_robust does; the received edges are
+ * switched off in those passes, so their class never enters.  Switched off, the condensed graphs are the plain ones byte for
+ * byte.  cgmr_graph_edge_stats: e^T O e and rho1 of every level-0 edge at
  * the estimate of the last cgmr_graph_optimize, own edges first, then the received ones (the order of cgmr_graph_debug_edges);
  * returns that edge count, 0 when that solve ran with no kernel set. */
 int cgmr_graph_set_edge_robust(cgmr_graph* g, int first, int n, const uint8_t* kind, const double* delta);
 int cgmr_graph_set_received_robust(cgmr_graph* g, int kind, double delta);
 int cgmr_graph_edge_stats(const cgmr_graph* g, int cap, double* edge_chi2_out, double* weight_out);
+int cgmr_graph_set_condensed_robust(cgmr_graph* g, int on);
 int cgmr_graph_lm_last(const cgmr_graph* g, int cap, double* lambda_out, int32_t* trials_out);
 /* estimates of vertices first .. first+n-1 in insertion order */
 int cgmr_graph_get_poses(cgmr_graph* g, int first, int n, double* poses_out);

@@ -6,20 +6,26 @@ Workload (BASELINE.json configs[1], "C2"): the synthetic 10k-vertex / 40k-edge S
 guess: host ordering + symbolic analysis (g2o redoes both on every optimize() call, so in the headline they are inside
 the timed region here as well: the analysis cache is switched OFF for it), upload of the structure, 10 Gauss-Newton
 iterations on the GPU, chi2 read-back.  Numeric inputs (poses, measurements, information matrices) are resident in HBM
-before the timed region starts.  value = GN iterations / second over all ranks.  ``warm`` reports the same step with the
-analysis cache on (what a key frame's second and third solve on an unchanged graph cost).
+before the timed region starts.  value = GN iterations / second over all ranks.
+
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes ``--dump-outputs`` and
+prints the JSON line with ``value``, ``ms_per_step`` and what the timed steps measured themselves (host analysis and
+device time per step, chi2, the host helper pool that ran them).  ``--full`` adds every other leg, after the timed region
+and in this order: ``warm`` (the same step with the analysis cache on: what a key frame's second and third solve on an
+unchanged graph cost), ``keyframe``, ``exchange``, then on rank 0 ``roofline``, ``cpu_baseline``, ``matcher``,
+``exchange_loopback`` and ``team``.
 
 Multi-GPU (``--gpus N``: N ranks, one process per GPU; spawned here when the driver has not already done so): every rank
 owns one robot's sub-graph (a C2 graph with its own seed) -- the path shards by robot with no data-path collective
-inside optimize(); weak scaling.  For N > 1 the ``exchange`` leg then runs BASELINE.json's C5 protocol: N robots x 5000
-vertices grown 50 at a time, every round optimize(5) -> condensed graphs for every peer that asked -> ONE RCCL
-all-gather of the 44-byte/edge wire buffers on a side stream (overlapping the next round's solve) -> newest edge set per
-peer replaces the old one (cg_mrslam_amd/mrslam.py).
+inside optimize(); weak scaling.  With ``--full`` and N > 1 the ``exchange`` leg then runs BASELINE.json's C5 protocol:
+N robots x 5000 vertices grown 50 at a time, every round optimize(5) -> condensed graphs for every peer that asked -> ONE
+RCCL all-gather of the 44-byte/edge wire buffers on a side stream (overlapping the next round's solve) -> newest edge set
+per peer replaces the old one (cg_mrslam_amd/mrslam.py).
 The second half of BASELINE.json's metric, scan-match pairs/s (config C3: 10^6 distinct pairs resident in HBM), is
-measured on rank 0 after the timed region and reported under ``matcher``.
+measured with ``--full`` on rank 0 after the timed region and reported under ``matcher``.
 
-Extra objects on the JSON line: ``roofline`` for the dominant kernel (timed with HIP events on the context's stream) and
-``cpu_baseline`` (the CPU oracle on rank 0, N=1 only: one thread, and all host cores with the count stated).
+Further objects of the ``--full`` line: ``roofline`` for the dominant kernel (timed with HIP events on the context's
+stream) and ``cpu_baseline`` (the CPU oracle on rank 0, N=1 only: one thread, and all host cores with the count stated).
 """
 from __future__ import annotations
 
@@ -133,6 +139,9 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--vertices", type=int, default=10000)
     ap.add_argument("--edges", type=int, default=40000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg: warm, keyframe, exchange, roofline, cpu_baseline, matcher, "
+                         "exchange_loopback, team (off: the headline alone); the options below shape those legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-team", action="store_true", help="skip the C4 leg (four robots of the cg_mrslam node on this GPU) and the 8-robot C5 loopback leg")
     ap.add_argument("--match-pairs", type=int, default=1000000, help="distinct scan pairs of the matcher leg (0 = skip)")
@@ -610,16 +619,19 @@ def exchange_leg(ctx, rank, world, args, dry=False, solo=False):
 
 
 def dry_main(args, rank, world):
-    """No GPU (CPU test of the launcher): rendezvous over gloo, the exchange leg on graphs without a device."""
+    """No GPU (CPU test of the launcher): rendezvous over gloo and, with ``--full``, the exchange leg on graphs without a
+    device."""
     import torch.distributed as dist
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     dist.init_process_group(backend="gloo", rank=rank, world_size=world)
     args.c5_vertices, args.c5_edges = min(args.c5_vertices, 600), min(args.c5_edges, 2000)
-    exchange = exchange_leg(None, rank, world, args, dry=True)
+    out = {"metric": "GN iterations/sec on 10k-vertex SE2 graph (final chi2 reported)", "value": None,
+           "unit": "GN iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+           "dry_run": True, "scaling": "weak", "full": args.full}
+    if args.full:
+        out["exchange"] = exchange_leg(None, rank, world, args, dry=True)
     if rank == 0:
-        print(json.dumps({"metric": "GN iterations/sec on 10k-vertex SE2 graph (final chi2 reported)", "value": None,
-                          "unit": "GN iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                          "dry_run": True, "scaling": "weak", "exchange": exchange}))
+        print(json.dumps(out))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -704,6 +716,31 @@ def main():
     chi_cold = chi.copy()
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, f"_rank{rank}" if world > 1 else "", p_cold.cpu().numpy(), chi_cold, DUMP_LIMIT_BYTES // world)
+
+    # ---- the headline line: what the timed steps measured, and the host they ran on (read here, before any other leg)
+    total_iters = GN_ITERS * args.steps * world
+    out = {
+        "metric": "GN iterations/sec on 10k-vertex SE2 graph (final chi2 reported)",
+        "value": round(total_iters / elapsed, 3), "unit": "GN iterations/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
+        "config": {"workload": f"C2: synthetic {V}-vertex/{E}-edge SE2 pose graph per GPU, one step = "
+                               f"GraphSLAM::optimize({GN_ITERS}) incl. host ordering+symbolic analysis (analysis cache off)",
+                   "gn_iterations_per_step": GN_ITERS, "graphs": world, "parallelism": f"1 robot sub-graph per GPU x{world}"},
+        "chi2_final": float(chi_cold[-1]), "chi2_initial": float(chi_cold[0]),
+        "host_symbolic_ms_per_step": round(1e3 * host_sym / args.steps, 3),
+        "device_ms_per_step": round(1e3 * dev_time / args.steps, 3),
+        "host_threads": host_threads(),
+        "host_loadavg_1min": round(os.getloadavg()[0], 1),   # runnable threads on the (shared) host, this process's included: a busy neighbour shows here
+        "host_pool": dict(ctx.host_threads_info(), opt_in={k: os.environ.get(k) for k in HOST_OPT_IN}),          # as the library runs them: pinned around a last-level cache or not, where
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- the same step with the analysis cache on (second and later solves of a key frame on an unchanged graph)
     ctx.set_symbolic_cache(True)
@@ -906,22 +943,8 @@ def main():
                if args.match_pairs > 0 else None)
 
     loopback = guarded("exchange_loopback", lambda: loopback_leg(args)) if world == 1 and not args.no_team else None
-    total_iters = GN_ITERS * args.steps * world
-    out = {
-        "metric": "GN iterations/sec on 10k-vertex SE2 graph (final chi2 reported)",
-        "value": round(total_iters / elapsed, 3), "unit": "GN iterations/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"C2: synthetic {V}-vertex/{E}-edge SE2 pose graph per GPU, one step = "
-                               f"GraphSLAM::optimize({GN_ITERS}) incl. host ordering+symbolic analysis (analysis cache off)",
-                   "gn_iterations_per_step": GN_ITERS, "graphs": world, "parallelism": f"1 robot sub-graph per GPU x{world}"},
-        "chi2_final": float(chi_cold[-1]), "chi2_initial": float(chi_cold[0]),
-        "host_symbolic_ms_per_step": round(1e3 * host_sym / args.steps, 3),
-        "host_threads": host_threads(),
-        "host_loadavg_1min": round(os.getloadavg()[0], 1),   # runnable threads on the (shared) host, this process's included: a busy neighbour shows here
-        "host_pool": dict(ctx.host_threads_info(), opt_in={k: os.environ.get(k) for k in HOST_OPT_IN}),          # as the library runs them: pinned around a last-level cache or not, where
+    out.update({
         "host_symbolic_ms_one_thread": (host_symbolic_ms_one_thread(V, E, 12345 + 17 * rank) if world == 1 else None),
-        "device_ms_per_step": round(1e3 * dev_time / args.steps, 3),
         "warm": warm, "keyframe": keyframe,
         "symbolic": {k: info[k] for k in ("fronts", "levels", "L_doubles", "U_doubles", "max_border", "factor_flops")},
         "kernel_seconds_profiled": {k: round(v[0] / nprof, 6) for k, v in kt.items()},
@@ -938,7 +961,7 @@ def main():
                                                     "_vs_robot0_alone divides the N = 1 exchange leg's round instead (robot 0's graph, the easiest of "
                                                     "the eight: 8 tree levels against 10-14)",
         "host_pool_of_every_rank": host_pools,
-    }
+    })
     if cpu:
         out["speedup_vs_cpu_1thread"] = round(out["value"] / cpu["value"], 2)
     print(json.dumps(out))

@@ -234,18 +234,23 @@ def test_gloo_two_rank_exchange():
 
 def test_bench_gpus_2_spawns_two_ranks_dry_run():
     """``bench.py --gpus 2`` without RANK in the environment must start two ranks itself.  Without a GPU the ranks run the
-    protocol dry (CGMR_BENCH_DRY=1: rendezvous over gloo, the C5 round protocol on graphs without a device with fake
-    condensed edges) -- the launcher, the rank plumbing and the exchange leg are what is tested here."""
+    protocol dry (CGMR_BENCH_DRY=1: rendezvous over gloo, with --full the C5 round protocol on graphs without a device with
+    fake condensed edges) -- the launcher, the rank plumbing and the exchange leg are what is tested here.  A plain run
+    rendezvouses and leaves the exchange leg out."""
+    import json
     env = dict(os.environ, CGMR_BENCH_DRY="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
-                       env=env, capture_output=True, text=True, timeout=300)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"]
+    p0 = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+    assert p0.returncode == 0, p0.stderr[-2000:]
+    out0 = json.loads([ln for ln in p0.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out0["n_gpus"] == 2 and out0["dry_run"] is True and out0["full"] is False and "exchange" not in out0
+    p = subprocess.run(cmd + ["--full"], env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
-    import json
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
     out = json.loads(line)
-    assert out["n_gpus"] == 2 and out["dry_run"] is True
+    assert out["n_gpus"] == 2 and out["dry_run"] is True and out["full"] is True
     ex = out["exchange"]
     assert ex is not None and ex["robots"] == 2 and ex["rounds"] >= 2 and ex["condensed_edges_received_total"] > 0
     # a rank count that disagrees with the environment is refused, not ignored

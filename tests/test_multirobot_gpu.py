@@ -333,6 +333,34 @@ def test_native_rccl_allgather_single_rank(ctx):
     lib.cgmr_comm_destroy(comm)
 
 
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_plain_run_is_the_headline_alone(tmp_path, gpus):
+    """``bench.py`` without ``--full``: the timed steps, the dumped outputs and the headline line, none of the other legs.
+    Two ranks share cuda:0 over gloo, as above.  Reduced sizes."""
+    env = dict(os.environ, CGMR_BENCH_SINGLE_DEVICE="1", CGMR_BENCH_BACKEND="gloo")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_PORT"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--vertices", "2000",
+           "--edges", "7000", "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["n_gpus"] == gpus and out["steps"] == 2 and out["warmup"] == 1 and out["full"] is False
+    assert out["value"] > 0 and out["unit"] == "GN iterations/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert abs(out["ms_per_step"] - 1e3 * 10 * gpus / out["value"]) <= 1e-3 * out["ms_per_step"]
+    assert 0 < out["chi2_final"] < out["chi2_initial"] and out["device_ms_per_step"] > 0
+    for leg in ("warm", "keyframe", "exchange", "roofline", "cpu_baseline", "matcher", "team", "exchange_loopback",
+                "host_symbolic_ms_one_thread", "host_pool_of_every_rank"):
+        assert leg not in out, leg
+    for r in range(gpus):
+        suffix = f"_rank{r}" if gpus > 1 else ""
+        poses, chi2 = np.load(tmp_path / f"poses{suffix}.npy"), np.load(tmp_path / f"chi2{suffix}.npy")
+        assert poses.shape == (2000, 3) and chi2.shape == (11,)
+    assert np.load(tmp_path / f"chi2{'_rank0' if gpus > 1 else ''}.npy")[-1] == out["chi2_final"]
+
+
 def test_bench_two_ranks_on_one_gpu():
     """``bench.py --gpus 2`` spawns its two ranks itself; on this one-GPU box they share cuda:0 and the collectives run
     over gloo (CGMR_BENCH_SINGLE_DEVICE / CGMR_BENCH_BACKEND).  The C5 exchange leg must really exchange."""
@@ -340,7 +368,7 @@ def test_bench_two_ranks_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--vertices", "2000",
-           "--edges", "7000", "--match-pairs", "0", "--c5-vertices", "800", "--c5-edges", "2800", "--c5-chunk", "100"]
+           "--edges", "7000", "--match-pairs", "0", "--c5-vertices", "800", "--c5-edges", "2800", "--c5-chunk", "100", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -360,7 +388,8 @@ def test_bench_five_ranks_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(R), "--steps", "2", "--warmup", "1", "--vertices", "2000",
-           "--edges", "7000", "--match-pairs", "0", "--c5-vertices", "600", "--c5-edges", "2100", "--c5-chunk", "50", "--no-cpu-baseline"]
+           "--edges", "7000", "--match-pairs", "0", "--c5-vertices", "600", "--c5-edges", "2100", "--c5-chunk", "50", "--no-cpu-baseline",
+           "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])

@@ -39,7 +39,7 @@ cd /tmp
 # profiles/r06_profiler_crash.md, tools/stress/team_stress.sh)
 for try in 1 2; do
   rm -rf $O/bench
-  timeout 900 rocprofv3 --kernel-trace --stats -d $O/bench --output-format csv -- python $R/bench.py > $O/bench.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats -d $O/bench --output-format csv -- python $R/bench.py --full > $O/bench.log 2>&1
   grep -q "^{\"metric\"" $O/bench.log && break
   cp $O/bench.log $O/bench_failed_try$try.log
 done

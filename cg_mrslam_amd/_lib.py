@@ -3,6 +3,7 @@ missing -- there is deliberately no CPU path behind these calls."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -94,6 +95,35 @@ def lm_params(**kw) -> LmParams:
     v = dict(LM_DEFAULTS, **kw)
     return LmParams(float(v["tau"]), float(v["initial_lambda"]), int(v["max_trials"]), float(v["good_step_lower"]),
                     float(v["good_step_upper"]))
+
+
+class DlParams(C.Structure):
+    """cgmr_dl_params (include/cgmr.h): g2o's OptimizationAlgorithmDogleg properties."""
+    _fields_ = [("initial_delta", C.c_double), ("max_trials", C.c_int32), ("initial_lambda", C.c_double),
+                ("lambda_factor", C.c_double)]
+
+
+DL_DEFAULTS = dict(initial_delta=1e4, max_trials=100, initial_lambda=1e-7, lambda_factor=10.0)
+DL_STEP_SD, DL_STEP_GN, DL_STEP_DL = 1, 2, 3      # include/cgmr.h: CGMR_DL_STEP_*
+
+
+def dl_params(**kw) -> DlParams:
+    """A DlParams with g2o's defaults for whatever ``kw`` does not name."""
+    bad = set(kw) - set(DL_DEFAULTS)
+    if bad:
+        raise TypeError(f"unknown dogleg parameter(s): {sorted(bad)}")
+    v = dict(DL_DEFAULTS, **kw)
+    return DlParams(float(v["initial_delta"]), int(v["max_trials"]), float(v["initial_lambda"]), float(v["lambda_factor"]))
+
+
+def dl_params_checked(kw) -> DlParams:
+    """dl_params(**kw), with the values the library accepts (ValueError otherwise): max_trials >= 1; initial_delta,
+    initial_lambda finite and > 0; lambda_factor finite and > 1."""
+    p = dl_params(**kw)
+    fin = all(math.isfinite(v) for v in (p.initial_delta, p.initial_lambda, p.lambda_factor))
+    if not (fin and p.max_trials >= 1 and p.initial_delta > 0 and p.initial_lambda > 0 and p.lambda_factor > 1):
+        raise ValueError("dogleg parameters: max_trials >= 1, initial_delta / initial_lambda > 0, lambda_factor > 1, all finite")
+    return p
 
 
 class Robust(C.Structure):
@@ -337,6 +367,59 @@ class Context:
         out = np.zeros(2, dtype=np.int64)
         self._check(self.lib.cgmr_lm_last_stats(self.h, _ptr(out)))
         return dict(host_waits=int(out[0]), trials=int(out[1]))
+
+    # ------------------------------------------------------------------ dogleg
+    def dl_optimize(self, poses, fixed, ef, et, meas, info, iters, kind=None, delta=1.0, raise_on_fail=True, **params):
+        """Dogleg (cgmr_dl_optimize, g2o's OptimizationAlgorithmDogleg); ``params``: initial_delta, max_trials,
+        initial_lambda, lambda_factor (g2o's defaults otherwise); ``kind`` / ``delta``: robust kernels as gn_optimize_robust
+        takes them (None: the plain call).  Host arrays in and out.  Returns (status, poses, chi2[iters+1], deltas[iters],
+        trials[iters], steps[iters], iters_done), with e2 [nE] and weights [nE] appended when ``kind`` is given.
+        Termination is status 0 with iters_done < iters; g2o's Fail in iteration i is CGMR_E_CHOLESKY_BASE - i (raised
+        unless ``raise_on_fail`` is False)."""
+        p = np.ascontiguousarray(poses, dtype=np.float64).copy()
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        ef = np.ascontiguousarray(ef, dtype=np.int32)
+        et = np.ascontiguousarray(et, dtype=np.int32)
+        meas = np.ascontiguousarray(meas, dtype=np.float64)
+        info = np.ascontiguousarray(info, dtype=np.float64)
+        prm = dl_params(**params)
+        rk, e2, w, _keep = self._robust(kind, delta, len(ef)) if kind is not None else (None, None, None, None)
+        chi, dlt, tri, stp = np.zeros(iters + 1), np.zeros(iters), np.zeros(iters, dtype=np.int32), np.zeros(iters, dtype=np.int32)
+        done = C.c_int32(0)
+        rc = self.lib.cgmr_dl_optimize(self.h, C.c_int(p.shape[0]), _ptr(p), _ptr(fixed), C.c_int(len(ef)), _ptr(ef), _ptr(et),
+                                       _ptr(meas), _ptr(info), C.c_int(iters), C.byref(prm), _ptr(chi), _ptr(dlt), _ptr(tri),
+                                       _ptr(stp), C.byref(done), C.byref(rk) if rk is not None else C.c_void_p(0))
+        self._check(rc, allow_cholesky=not raise_on_fail)
+        out = (rc, p, chi, dlt, tri, stp, int(done.value))
+        return out + (e2, w) if kind is not None else out
+
+    def dl_optimize_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters, kind=None, delta=1.0,
+                        d_kind_ptr=None, d_delta_ptr=None, raise_on_fail=True, **params):
+        """Device pointers (ints) for poses/meas/info, host numpy for the structure; robust kernels as
+        gn_optimize_robust_dev takes them (``kind`` None and no device arrays: the plain call).  Returns (status,
+        chi2[iters+1], deltas[iters], trials[iters], steps[iters], iters_done), with e2 and weights appended when robust."""
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        ef = np.ascontiguousarray(ef, dtype=np.int32)
+        et = np.ascontiguousarray(et, dtype=np.int32)
+        prm = dl_params(**params)
+        robust = kind is not None or d_kind_ptr is not None or d_delta_ptr is not None
+        rk, e2, w, _keep = self._robust("none" if kind is None else kind, delta, len(ef), d_kind_ptr, d_delta_ptr) if robust \
+            else (None, None, None, None)
+        chi, dlt, tri, stp = np.zeros(iters + 1), np.zeros(iters), np.zeros(iters, dtype=np.int32), np.zeros(iters, dtype=np.int32)
+        done = C.c_int32(0)
+        rc = self.lib.cgmr_dl_optimize_dev(self.h, C.c_int(nV), C.c_void_p(d_poses_ptr), _ptr(fixed), C.c_int(len(ef)), _ptr(ef),
+                                           _ptr(et), C.c_void_p(d_meas_ptr), C.c_void_p(d_info_ptr), C.c_int(iters),
+                                           C.byref(prm), _ptr(chi), _ptr(dlt), _ptr(tri), _ptr(stp), C.byref(done),
+                                           C.byref(rk) if rk is not None else C.c_void_p(0))
+        self._check(rc, allow_cholesky=not raise_on_fail)
+        out = (rc, chi, dlt, tri, stp, int(done.value))
+        return out + (e2, w) if robust else out
+
+    def dl_last_stats(self):
+        """The last dl_optimize* call: dict(host_waits, trials, factorisations)."""
+        out = np.zeros(3, dtype=np.int64)
+        self._check(self.lib.cgmr_dl_last_stats(self.h, _ptr(out)))
+        return dict(host_waits=int(out[0]), trials=int(out[1]), factorisations=int(out[2]))
 
     # ------------------------------------------------------------------ marginals / condensed graph
     @staticmethod

@@ -133,13 +133,18 @@ class RobotGraph:
         return out[:n].copy()
 
     def set_algorithm(self, algorithm: str = "gn", **params):
-        """The optimiser of ``optimize``: "gn" (default, the reference's Gauss-Newton) or "levenberg" with g2o's
-        Levenberg-Marquardt parameters (tau, initial_lambda, max_trials, good_step_lower, good_step_upper)."""
-        from ._lib import lm_params
-        if algorithm not in ("gn", "levenberg"):
-            raise ValueError(f"algorithm must be 'gn' or 'levenberg', not {algorithm!r}")
+        """The optimiser of ``optimize``: "gn" (default, the reference's Gauss-Newton), "levenberg" with g2o's
+        Levenberg-Marquardt parameters (tau, initial_lambda, max_trials, good_step_lower, good_step_upper) or "dl" (g2o's
+        dogleg) with its parameters (initial_delta, max_trials, initial_lambda, lambda_factor; checked here, ValueError)."""
+        from ._lib import dl_params_checked, lm_params
+        if algorithm not in ("gn", "levenberg", "dl"):
+            raise ValueError(f"algorithm must be 'gn', 'levenberg' or 'dl', not {algorithm!r}")
         if algorithm == "gn":
             self._check(self.lib.cgmr_graph_set_algorithm(self.h, C.c_int(0), C.c_void_p(0)))
+        elif algorithm == "dl":
+            prm = dl_params_checked(params)
+            self._check(self.lib.cgmr_graph_set_dogleg_params(self.h, C.byref(prm)))
+            self._check(self.lib.cgmr_graph_set_algorithm(self.h, C.c_int(2), C.c_void_p(0)))
         else:
             prm = lm_params(**params)
             self._check(self.lib.cgmr_graph_set_algorithm(self.h, C.c_int(1), C.byref(prm)))
@@ -186,6 +191,16 @@ class RobotGraph:
         if n:
             self._check(self.lib.cgmr_graph_lm_last(self.h, C.c_int(n), _p(lam), _p(tri)))
         return lam, tri
+
+    def dl_last(self):
+        """Records of the last dogleg solve: (deltas, trials, steps), one entry per iteration run."""
+        n = self._check(self.lib.cgmr_graph_dl_last(self.h, C.c_int(0), C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)))
+        dlt = np.zeros(n)
+        tri = np.zeros(n, dtype=np.int32)
+        stp = np.zeros(n, dtype=np.int32)
+        if n:
+            self._check(self.lib.cgmr_graph_dl_last(self.h, C.c_int(n), _p(dlt), _p(tri), _p(stp)))
+        return dlt, tri, stp
 
     def set_optimal_gauge(self, optimal: bool):
         """``computeCondensedGraph(robot, optimal)``: selectOptimalGauge instead of selectGaugeCentroid (reference default: off)."""

@@ -626,7 +626,7 @@ void gn_pass(cgmr_ctx* ctx, double* d_poses, const GnEdges& Ed, int it, bool chi
 
 // the same on an explicit device view (the context's, or a replica with its own numeric work space) and stream
 void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, const GnEdges& Ed, int it, bool chi_only,
-                bool solve_and_update, bool write_l11c, LmState* lm, bool lm_init) {
+                bool solve_and_update, bool write_l11c, LmState* lm, bool lm_init, const DlState* dl) {
   KTimer T{ctx, st};
   T.run(0, 1, [&] { launch_linearize(st, D, d_poses, Ed, chi_only ? 1 : 0); });
   if (chi_only || D.nf == 0) {
@@ -647,6 +647,7 @@ void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, con
     if (lm_init) launch_lm_init(st, D, lm);
     launch_lm_damp(st, D, lm);
   }
+  if (dl) launch_dl_damp(st, D, dl);                            // a dogleg head: H + currentLambda I once H was not PD (dl_kernels.hip)
   static const bool trace = getenv("CGMR_TRACE_LAUNCHES") != nullptr;
   if (trace)
     fprintf(stderr, "[cgmr] arena %p .. %p; work %p rel %p Pan %p Ablk %p bvec %p yvec %p uvec %p Lbuf %p Ubuf %p chi2 %p\n",
@@ -688,7 +689,7 @@ void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, con
   // (the forward solve L y = b rides through k_front_factor as an extra row of every front)
   if (D.bwd_chain_level < D.nlevels) T.run(6, 1, [&] { launch_bwd_chain(st, D); });
   for (int l = D.bwd_chain_level - 1; l >= 0; l--) T.run(6, 1, [&] { launch_bwd_level(st, D, l); });
-  T.run(7, 1, [&] { launch_update(st, D, d_poses); });
+  if (!dl) T.run(7, 1, [&] { launch_update(st, D, d_poses); });   // (a dogleg head leaves the step to its tails)
 }
 
 int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef,
@@ -935,6 +936,186 @@ int lm_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
   ctx->timing[2] = (t2 - t1) + S.t_upload;
   ctx->timing[3] = 1e-3 * ms;
   ctx->timing[4] = wall_s() - t0;
+  return CGMR_OK;
+}
+
+// g2o's OptimizationAlgorithmDogleg defaults [g2o-recalled]
+static cgmr_dl_params dl_defaults() {
+  cgmr_dl_params p;
+  p.initial_delta = 1e4; p.max_trials = 100; p.initial_lambda = 1e-7; p.lambda_factor = 10;
+  return p;
+}
+
+static bool dl_params_valid(const cgmr_dl_params& P) {
+  return P.max_trials >= 1 && std::isfinite(P.initial_delta) && P.initial_delta > 0 && std::isfinite(P.initial_lambda) &&
+         P.initial_lambda > 0 && std::isfinite(P.lambda_factor) && P.lambda_factor > 1;
+}
+
+bool dl_params_ok(const cgmr_dl_params* p) { return !p || dl_params_valid(*p); }
+
+// A head (dl_kernels.hip): linearise + assemble + [damp] + factor + solve at x (no update), b^T H b, k_dl_begin.
+static void dl_head(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, const GnEdges& Ed, const DlDev& L) {
+  gn_pass_on(ctx, D, st, d_poses, Ed, 0, false, true, false, nullptr, false, L.S);
+  launch_dl_quad(st, D, D.bvec, L.qpart);
+  launch_dl_begin(st, D, L);
+}
+
+// A tail: the step for the current delta, h^T H h, update, chi-only linearise at x (+) h, the verdict, keep or restore x.
+static void dl_tail(GnDevice& D, hipStream_t st, int nV, double* d_poses, const GnEdges& Ed, const DlDev& L) {
+  launch_dl_step(st, D, L);
+  launch_dl_quad(st, D, D.xvec, L.qpart);
+  launch_update(st, D, d_poses);
+  launch_linearize(st, D, d_poses, Ed, 1);
+  launch_dl_decide(st, D, L);
+  launch_dl_commit(st, nV, d_poses, L);
+}
+
+int dl_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
+           const GnEdges& Ed, int iters, const cgmr_dl_params* params, double* chi2_out, double* delta_out, int32_t* trials_out,
+           int32_t* step_out, int32_t* iters_done, const int32_t* hub_vertices, int n_hub_vertices) {
+  const cgmr_dl_params P = params ? *params : dl_defaults();
+  if (!dl_params_valid(P))
+    return set_err(ctx, CGMR_E_INVALID,
+                   "cgmr_dl_optimize: max_trials must be >= 1, initial_delta / initial_lambda > 0, lambda_factor > 1, all finite");
+  const double t0 = wall_s();
+  Symbolic& S = ctx->sym;
+  // (the chi2 slots a head uses: slot 0 only -- the cache entry of a Gauss-Newton call on the same edge list serves)
+  int rc = prepare_structure(ctx, nV, nE, ef, et, 1, hub_vertices, n_hub_vertices);
+  if (rc) return rc;
+  const double t1 = wall_s();
+  rc = prepare_pass(ctx, fixed, nE, ef, et, Ed.n_active, 0, 1);
+  if (rc) return rc;
+  const double t2 = wall_s();
+  GnDevice& D = ctx->gn;
+  hipStream_t st = ctx->stream;
+  // dl arena: state | chi2 [iters + 1] | delta, trials, steps [iters] | saved poses [3 nV] | hgn, hsd [3 nf] | quad partials
+  BlobLayout B;
+  const size_t o_state = B.add<DlState>(1), o_chi = B.add<double>((size_t)iters + 1), o_del = B.add<double>((size_t)iters + 1),
+               o_tri = B.add<int32_t>((size_t)iters + 1), o_stp = B.add<int32_t>((size_t)iters + 1);
+  const size_t rec_bytes = B.off;
+  const size_t nf3 = 3 * (size_t)std::max(D.nf, 1);
+  const size_t o_saved = B.add<double>(3 * (size_t)std::max(nV, 1)), o_hgn = B.add<double>(nf3), o_hsd = B.add<double>(nf3),
+               o_q = B.add<double>((size_t)std::max((nE + 255) / 256, 1));
+  rc = arena_reserve(ctx, ctx->dl_arena, B.off + 256);
+  if (rc) return rc;
+  char* d = ctx->dl_arena.ptr;
+  DlDev L;
+  L.S = (DlState*)(d + o_state); L.rec_chi = (double*)(d + o_chi); L.rec_delta = (double*)(d + o_del);
+  L.rec_trials = (int32_t*)(d + o_tri); L.rec_step = (int32_t*)(d + o_stp); L.saved = (double*)(d + o_saved);
+  L.hgn = (double*)(d + o_hgn); L.hsd = (double*)(d + o_hsd); L.qpart = (double*)(d + o_q);
+  std::vector<char> h(rec_bytes, 0);
+  DlState hs;
+  hs.delta = P.initial_delta; hs.lambda = P.initial_lambda; hs.lambda_factor = P.lambda_factor; hs.max_trials = P.max_trials;
+  hs.iters = iters;
+  memcpy(h.data() + o_state, &hs, sizeof hs);
+  HIP_TRY(ctx, hipMemcpyAsync(d, h.data(), rec_bytes, hipMemcpyHostToDevice, st));
+  if (nV > 0) HIP_TRY(ctx, hipMemcpyAsync(L.saved, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));
+  double* const poses_host = ctx->poses_out_host;
+  ctx->poses_out_host = nullptr;
+  int64_t waits = 0;
+  if (D.nf == 0 || iters == 0) {
+    // nothing to move (or nothing asked): chi2 at x.  With iterations asked, g2o's empty system gives h = 0 and rho = 0
+    // on every trial: one iteration of max_trials GN trials, delta halved on each, Terminate
+    gn_pass(ctx, d_poses, Ed, 0, true, false, false);
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
+    double chi0 = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&chi0, D.chi2, sizeof(double), hipMemcpyDeviceToHost, st));
+    if (poses_host && nV > 0) HIP_TRY(ctx, hipMemcpyAsync(poses_host, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipGetLastError());
+    waits = 1;
+    double* rc_chi = (double*)(h.data() + o_chi);
+    rc_chi[0] = chi0;
+    if (iters > 0) {
+      for (int q = 0; q < P.max_trials; q++) hs.delta *= 0.5;
+      hs.iter = 1;
+      hs.total_trials = P.max_trials;
+      hs.terminated = 1;
+      rc_chi[1] = chi0;
+      ((double*)(h.data() + o_del))[0] = hs.delta;
+      ((int32_t*)(h.data() + o_tri))[0] = P.max_trials;
+      ((int32_t*)(h.data() + o_stp))[0] = CGMR_DL_STEP_GN;
+    }
+  } else {
+    // rounds: an open iteration (its GN step solved, no good step yet) gets tails only, doubling in number from round to
+    // round; every iteration not started yet gets a head and a tail.  One wait per round.
+    const int chain_was = D.bwd_chain_level;
+    const std::vector<uint8_t> merge_was = D.h_level_merge;
+    bool levelwise = false;
+    GnEdges Ei = Ed;                                         // (robust statistics: one chi-only pass on the final poses below)
+    Ei.rk_stats = nullptr;
+    int n_cont = 1;
+    for (;;) {
+      const bool open = hs.solved != 0;
+      if (open) {
+        n_cont = std::min(2 * n_cont, P.max_trials - hs.trial);
+        for (int t = 0; t < n_cont; t++) dl_tail(D, st, nV, d_poses, Ei, L);
+      }
+      const int n_new = iters - hs.iter - (open ? 1 : 0);
+      for (int t = 0; t < n_new; t++) {
+        dl_head(ctx, D, st, d_poses, Ei, L);
+        dl_tail(D, st, nV, d_poses, Ei, L);
+      }
+      HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
+      HIP_TRY(ctx, hipMemcpyAsync(h.data(), d, rec_bytes, hipMemcpyDeviceToHost, st));
+      if (poses_host && nV > 0) HIP_TRY(ctx, hipMemcpyAsync(poses_host, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, hipStreamSynchronize(st));
+      HIP_TRY(ctx, hipGetLastError());
+      waits++;
+      memcpy(&hs, h.data() + o_state, sizeof hs);
+      if (hs.halted) {
+        // A bounded wait ran out in a head (status[2]): not a numerical verdict.  The poses are those the iteration started
+        // from and nothing after the head changed anything; the call goes on from the state as it stands, one launch per
+        // kernel and level (no in-kernel waits), as lm_run does.
+        if (levelwise) {
+          D.bwd_chain_level = chain_was;
+          D.h_level_merge = merge_was;
+          return set_err(ctx, CGMR_E_TIMEOUT, "dogleg: a bounded device-side wait ran out twice");
+        }
+        ctx->gn_timeouts++;
+        ctx->fwd_merge_any = false;
+        levelwise = true;
+        D.bwd_chain_level = D.nlevels;
+        D.h_level_merge.assign(D.nlevels, 0);
+        hs.halted = 0;
+        hs.accept = -1;
+        const int fresh[4] = {0, 0, 0, 0};
+        HIP_TRY(ctx, hipMemcpyAsync(D.status, fresh, sizeof fresh, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(L.S, &hs, sizeof hs, hipMemcpyHostToDevice, st));
+        continue;
+      }
+      if (hs.done) break;
+    }
+    if (Ed.rk_stats) launch_linearize(st, D, d_poses, Ed, 1);   // (read back by the caller, behind the stream)
+    D.bwd_chain_level = chain_was;
+    D.h_level_merge = merge_was;
+  }
+  const double* rc_chi = (const double*)(h.data() + o_chi);
+  const double* rc_del = (const double*)(h.data() + o_del);
+  const int32_t* rc_tri = (const int32_t*)(h.data() + o_tri);
+  const int32_t* rc_stp = (const int32_t*)(h.data() + o_stp);
+  const int ran = std::min(hs.iter, iters);
+  if (chi2_out) for (int k = 0; k <= iters; k++) chi2_out[k] = rc_chi[std::min(k, ran)];
+  if (delta_out) for (int k = 0; k < iters; k++) delta_out[k] = k < ran ? rc_del[k] : 0.0;
+  if (trials_out) for (int k = 0; k < iters; k++) trials_out[k] = k < ran ? rc_tri[k] : 0;
+  if (step_out) for (int k = 0; k < iters; k++) step_out[k] = k < ran ? rc_stp[k] : 0;
+  if (iters_done) *iters_done = ran;
+  ctx->dl_stats[0] = waits;
+  ctx->dl_stats[1] = hs.total_trials;
+  ctx->dl_stats[2] = hs.factorisations;
+  if (ctx->profiling) profile_collect(ctx);
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+  ctx->timing[0] = S.t_order;
+  ctx->timing[1] = S.t_struct;
+  ctx->timing[2] = (t2 - t1) + S.t_upload;
+  ctx->timing[3] = 1e-3 * ms;
+  ctx->timing[4] = wall_s() - t0;
+  if (hs.failed)
+    return set_err(ctx, CGMR_E_CHOLESKY_BASE - ran,
+                   "dogleg: H + currentLambda I not positive definite with currentLambda at 1e3 in iteration %d (g2o's Fail); "
+                   "poses left at the last accepted step", ran);
   return CGMR_OK;
 }
 
@@ -1258,7 +1439,7 @@ using namespace cgmr;
 
 extern "C" {
 
-int cgmr_version(void) { return 105; }   // 105: cgmr_*_optimize_robust*, cgmr_graph_set_edge_robust / _set_received_robust / _edge_stats added, later (same number: callers find them by their symbols) cgmr_marginals_robust, cgmr_marginals_all_robust, cgmr_covariance_estimate_robust, cgmr_condense_robust, cgmr_graph_set_condensed_robust; 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
+int cgmr_version(void) { return 105; }   // 105: cgmr_*_optimize_robust*, cgmr_graph_set_edge_robust / _set_received_robust / _edge_stats added, later (same number: callers find them by their symbols) cgmr_marginals_robust, cgmr_marginals_all_robust, cgmr_covariance_estimate_robust, cgmr_condense_robust, cgmr_graph_set_condensed_robust, cgmr_dl_optimize*, cgmr_dl_last_stats, cgmr_graph_set_dogleg_params, cgmr_graph_dl_last (CGMR_ALG_DOGLEG); 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
 
 int cgmr_ctx_create(int device, void* hip_stream, cgmr_ctx** out) {
   if (!out) return CGMR_E_INVALID;
@@ -1302,6 +1483,7 @@ void cgmr_ctx_destroy(cgmr_ctx* ctx) {
   if (ctx->mg_arena.ptr) (void)hipFree(ctx->mg_arena.ptr);
   if (ctx->si_arena.ptr) (void)hipFree(ctx->si_arena.ptr);
   if (ctx->lm_arena.ptr) (void)hipFree(ctx->lm_arena.ptr);
+  if (ctx->dl_arena.ptr) (void)hipFree(ctx->dl_arena.ptr);
   if (ctx->rk_arena.ptr) (void)hipFree(ctx->rk_arena.ptr);
   if (ctx->st_arena.ptr) (void)hipFree(ctx->st_arena.ptr);
   if (ctx->pinned_st) (void)hipHostFree(ctx->pinned_st);
@@ -1487,6 +1669,74 @@ int cgmr_lm_last_stats(const cgmr_ctx* ctx, int64_t out[2]) {
   if (!ctx || !out) return CGMR_E_INVALID;
   out[0] = ctx->lm_stats[0];
   out[1] = ctx->lm_stats[1];
+  return CGMR_OK;
+}
+
+static int dl_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                            const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_dl_params* params,
+                            double* chi2_out, double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
+                            const cgmr_robust* rk, bool dev) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (nV < 0 || nE < 0 || iters < 0 || (nV > 0 && (!poses || !fixed)) ||
+      (nE > 0 && (!from_idx || !to_idx || !meas || !info)))
+    return set_err(ctx, CGMR_E_INVALID, "cgmr_dl_optimize: null or negative argument");
+  if (!dl_params_ok(params))
+    return set_err(ctx, CGMR_E_INVALID,
+                   "cgmr_dl_optimize: max_trials must be >= 1, initial_delta / initial_lambda > 0, lambda_factor > 1, all finite");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  GnEdges Ed;
+  int rc = robust_setup(ctx, rk, nE, dev, Ed, dev ? "cgmr_dl_optimize_dev" : "cgmr_dl_optimize");
+  if (rc) return rc;
+  double* d_poses = poses;
+  const size_t bp = sizeof(double) * 3 * (size_t)nV;
+  char* d = nullptr;
+  if (dev) {
+    Ed.meas_a = meas; Ed.info_a = info;
+  } else {
+    size_t bm = sizeof(double) * 3 * (size_t)nE, bi = sizeof(double) * 6 * (size_t)nE;
+    size_t om = (bp + 255) & ~size_t(255), oi = (om + bm + 255) & ~size_t(255);
+    rc = arena_reserve(ctx, ctx->io_arena, oi + bi + 256);
+    if (rc) return rc;
+    d = ctx->io_arena.ptr;
+    HIP_TRY(ctx, hipMemcpyAsync(d, poses, bp, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d + om, meas, bm, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d + oi, info, bi, hipMemcpyHostToDevice, ctx->stream));
+    Ed.meas_a = (const double*)(d + om); Ed.info_a = (const double*)(d + oi);
+    d_poses = (double*)d;
+  }
+  Ed.nA = nE; Ed.n_active = nE;
+  rc = dl_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, delta_out, trials_out, step_out, iters_done);
+  if (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE) {
+    if (!dev) {
+      hipError_t e = hipMemcpyAsync(poses, d, bp, hipMemcpyDeviceToHost, ctx->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+      if (e != hipSuccess) return set_err(ctx, CGMR_E_HIP, "pose read-back: %s", hipGetErrorString(e));
+    }
+    const int rs = robust_stats_out(ctx, rk, nE, Ed);
+    if (rs) return rs;
+  }
+  return rc;
+}
+
+int cgmr_dl_optimize(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                     const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_dl_params* params,
+                     double* chi2_out, double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
+                     const cgmr_robust* rk) {
+  return dl_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, params, chi2_out, delta_out, trials_out,
+                          step_out, iters_done, rk, false);
+}
+
+int cgmr_dl_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                         const int32_t* to_idx, const double* d_meas, const double* d_info, int iters, const cgmr_dl_params* params,
+                         double* chi2_out, double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
+                         const cgmr_robust* rk) {
+  return dl_optimize_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, params, chi2_out, delta_out,
+                          trials_out, step_out, iters_done, rk, true);
+}
+
+int cgmr_dl_last_stats(const cgmr_ctx* ctx, int64_t out[3]) {
+  if (!ctx || !out) return CGMR_E_INVALID;
+  for (int k = 0; k < 3; k++) out[k] = ctx->dl_stats[k];
   return CGMR_OK;
 }
 

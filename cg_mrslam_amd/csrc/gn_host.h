@@ -3,6 +3,7 @@
 #include <cmath>
 
 #include "cgmr_ctx.h"
+#include "dl_device.h"
 #include "lm_device.h"
 
 namespace cgmr {
@@ -32,8 +33,9 @@ int prepare_batch_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st);
 int gn_replicas(cgmr_ctx* ctx, int n, std::vector<GnDevice>& out, size_t* stride_out = nullptr);
 int aux_streams(cgmr_ctx* ctx, int n);
 // lm (nullable): a Levenberg-Marquardt trial -- lambda onto H's diagonal after the assembly (computed first when lm_init)
+// dl (nullable): a dogleg head -- currentLambda onto H's diagonal while H has not been PD; solved, the poses are not updated
 void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, const GnEdges& Ed, int it, bool chi_only,
-                bool solve_and_update, bool write_l11c, LmState* lm = nullptr, bool lm_init = false);
+                bool solve_and_update, bool write_l11c, LmState* lm = nullptr, bool lm_init = false, const DlState* dl = nullptr);
 // one Gauss-Newton pass on the uploaded structure: linearise + chi2 [+ assemble + factor [+ solve + update]]
 void gn_pass(cgmr_ctx* ctx, double* d_poses, const GnEdges& Ed, int it, bool chi_only, bool solve_and_update, bool write_l11c);
 int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
@@ -43,6 +45,13 @@ int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
 int lm_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
            const GnEdges& Ed, int iters, const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
            int32_t* iters_done, const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0);
+// Dogleg on the same structure preparation and factorisation (g2o's OptimizationAlgorithmDogleg): outputs chi2_out
+// [iters + 1], delta_out / trials_out / step_out [iters] (all nullable), *iters_done; CGMR_E_CHOLESKY_BASE - i on g2o's Fail
+int dl_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
+           const GnEdges& Ed, int iters, const cgmr_dl_params* params, double* chi2_out, double* delta_out, int32_t* trials_out,
+           int32_t* step_out, int32_t* iters_done, const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0);
+// null, or parameters dl_run accepts
+bool dl_params_ok(const cgmr_dl_params* params);
 // SparseOptimizer::computeInitialGuess from the fixed vertices over the given edges [g2o-recalled]
 void initial_guess_host(int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
                         const double* meas);

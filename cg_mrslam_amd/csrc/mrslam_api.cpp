@@ -106,6 +106,8 @@ struct cgmr_graph {
   int algorithm = CGMR_ALG_GAUSS_NEWTON;   // cgmr_graph_set_algorithm: the optimiser of cgmr_graph_optimize
   bool lm_params_set = false;
   cgmr_lm_params lm_params{};
+  bool dl_params_set = false;          // cgmr_graph_set_dogleg_params (else g2o's defaults)
+  cgmr_dl_params dl_params{};
   // robust kernels (cgmr_graph_set_edge_robust): kind / delta of every own edge on the host and, from the first setting on, on
   // the device (rk_dev; grown with d_meas_a); the received edges' class; the per-edge statistics of the last optimize (e2 of
   // every level-0 edge, then rho1; empty when it ran plain)
@@ -119,6 +121,8 @@ struct cgmr_graph {
   bool cond_robust = false;           // cgmr_graph_set_condensed_robust: the condensed graphs take the own edges' kernels
   std::vector<double> lm_lambda;      // records of the last Levenberg solve (cgmr_graph_lm_last)
   std::vector<int32_t> lm_trials;
+  std::vector<double> dl_delta;       // records of the last dogleg solve (cgmr_graph_dl_last)
+  std::vector<int32_t> dl_trials, dl_step;
   bool h_poses_fresh = false;         // h_poses holds the estimates as the last optimize() left them
   double* pinned_poses = nullptr;     // landing zone of that read-back (page-locked: a copy into the pageable h_poses goes through the runtime's staging path)
   size_t pinned_poses_cap = 0;        // in poses
@@ -559,6 +563,9 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out) {
   int rc;
   g->lm_lambda.clear();
   g->lm_trials.clear();
+  g->dl_delta.clear();
+  g->dl_trials.clear();
+  g->dl_step.clear();
   if (g->algorithm == CGMR_ALG_LEVENBERG) {
     std::vector<double> lam(iters);
     std::vector<int32_t> tri(iters);
@@ -566,6 +573,18 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out) {
     rc = lm_run(ctx, nV, (double*)g->d_poses.ptr, g->fixed.data(), nE, g->all_ef.data(), g->all_et.data(), Ed, iters,
                 g->lm_params_set ? &g->lm_params : nullptr, chi2_out, lam.data(), tri.data(), &done, hubs.data(), (int)hubs.size());
     if (rc == CGMR_OK) { g->lm_lambda.assign(lam.begin(), lam.begin() + done); g->lm_trials.assign(tri.begin(), tri.begin() + done); }
+  } else if (g->algorithm == CGMR_ALG_DOGLEG) {
+    std::vector<double> del(iters);
+    std::vector<int32_t> tri(iters), stp(iters);
+    int32_t done = 0;
+    rc = dl_run(ctx, nV, (double*)g->d_poses.ptr, g->fixed.data(), nE, g->all_ef.data(), g->all_et.data(), Ed, iters,
+                g->dl_params_set ? &g->dl_params : nullptr, chi2_out, del.data(), tri.data(), stp.data(), &done, hubs.data(),
+                (int)hubs.size());
+    if (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE) {
+      g->dl_delta.assign(del.begin(), del.begin() + done);
+      g->dl_trials.assign(tri.begin(), tri.begin() + done);
+      g->dl_step.assign(stp.begin(), stp.begin() + done);
+    }
   } else {
     rc = gn_run(ctx, nV, (double*)g->d_poses.ptr, g->fixed.data(), nE, g->all_ef.data(), g->all_et.data(), Ed, iters, chi2_out,
                 hubs.data(), (int)hubs.size());
@@ -585,10 +604,26 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out) {
 }
 
 int cgmr_graph_set_algorithm(cgmr_graph* g, int algorithm, const cgmr_lm_params* params) {
-  if (!g || (algorithm != CGMR_ALG_GAUSS_NEWTON && algorithm != CGMR_ALG_LEVENBERG)) return CGMR_E_INVALID;
+  if (!g || (algorithm != CGMR_ALG_GAUSS_NEWTON && algorithm != CGMR_ALG_LEVENBERG && algorithm != CGMR_ALG_DOGLEG))
+    return CGMR_E_INVALID;
+  if (algorithm == CGMR_ALG_DOGLEG) {
+    if (params) return gerr(g, CGMR_E_INVALID, "cgmr_graph_set_algorithm: dogleg takes its parameters from cgmr_graph_set_dogleg_params");
+    g->algorithm = algorithm;
+    return CGMR_OK;
+  }
   g->algorithm = algorithm;
   g->lm_params_set = params != nullptr;
   if (params) g->lm_params = *params;
+  return CGMR_OK;
+}
+
+int cgmr_graph_set_dogleg_params(cgmr_graph* g, const cgmr_dl_params* params) {
+  if (!g) return CGMR_E_INVALID;
+  if (!dl_params_ok(params))
+    return gerr(g, CGMR_E_INVALID,
+                "cgmr_graph_set_dogleg_params: max_trials must be >= 1, initial_delta / initial_lambda > 0, lambda_factor > 1, all finite");
+  g->dl_params_set = params != nullptr;
+  if (params) g->dl_params = *params;
   return CGMR_OK;
 }
 
@@ -632,6 +667,17 @@ int cgmr_graph_lm_last(const cgmr_graph* g, int cap, double* lambda_out, int32_t
   for (int k = 0; k < std::min(n, cap); k++) {
     if (lambda_out) lambda_out[k] = g->lm_lambda[k];
     if (trials_out) trials_out[k] = g->lm_trials[k];
+  }
+  return n;
+}
+
+int cgmr_graph_dl_last(const cgmr_graph* g, int cap, double* delta_out, int32_t* trials_out, int32_t* step_out) {
+  if (!g || cap < 0) return CGMR_E_INVALID;
+  const int n = (int)g->dl_delta.size();
+  for (int k = 0; k < std::min(n, cap); k++) {
+    if (delta_out) delta_out[k] = g->dl_delta[k];
+    if (trials_out) trials_out[k] = g->dl_trials[k];
+    if (step_out) step_out[k] = g->dl_step[k];
   }
   return n;
 }

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import CGMR_E_CHOLESKY_BASE, Context, robust_arrays, robust_code
+from ._lib import CGMR_E_CHOLESKY_BASE, DL_DEFAULTS, Context, dl_params_checked, robust_arrays, robust_code
 
 ODOM_INFO = (100.0, 100.0, 1000.0)      # _odominf, src/slam/graph_slam.cpp:72-73
 SM_INFO = (1000.0, 1000.0, 10000.0)     # _SMinf,   src/slam/graph_slam.cpp:75-76
@@ -158,15 +158,24 @@ class GraphSLAM:
     """The optimiser face of the reference's ``GraphSLAM`` (src/slam/graph_slam.h:49-76)."""
 
     def __init__(self, graph: PoseGraph, ctx: Context | None = None, device: int = 0, algorithm: str = "gn",
-                 lm_params: dict | None = None):
-        """``algorithm``: "gn" (the reference's Gauss-Newton) or "levenberg" (g2o's OptimizationAlgorithmLevenberg, with
-        ``lm_params``: tau, initial_lambda, max_trials, good_step_lower, good_step_upper)."""
-        if algorithm not in ("gn", "levenberg"):
-            raise ValueError(f"algorithm must be 'gn' or 'levenberg', not {algorithm!r}")
+                 lm_params: dict | None = None, dl_params: dict | None = None):
+        """``algorithm``: "gn" (the reference's Gauss-Newton), "levenberg" (g2o's OptimizationAlgorithmLevenberg, with
+        ``lm_params``: tau, initial_lambda, max_trials, good_step_lower, good_step_upper) or "dl" (g2o's
+        OptimizationAlgorithmDogleg, the factory's "dl_var", with ``dl_params``: initial_delta, max_trials, initial_lambda,
+        lambda_factor)."""
+        if algorithm == "levenberg":
+            pass
+        elif algorithm == "dl":
+            dl_params_checked(dl_params or {})
+        elif algorithm != "gn":
+            raise ValueError(f"algorithm must be 'gn', 'levenberg' or 'dl', not {algorithm!r}")
         self.graph = graph
         self.ctx = ctx or Context(device)
         self.algorithm = algorithm
         self.lm_params = dict(lm_params or {})
+        self.dl_params = dict(dl_params or {})
+        self.last_deltas = None
+        self.last_steps = None
         self.last_chi2 = None
         self.last_status = 0
         self.last_lambdas = None
@@ -194,6 +203,14 @@ class GraphSLAM:
                 rc, poses, chi2, lam, tri, done, self.last_edge_chi2, self.last_weights = self.ctx.lm_optimize_robust(
                     g.poses, g.fixed, ef, et, meas, info, int(nrunnings), *rk, **self.lm_params)
             self.last_lambdas, self.last_trials, self.last_iterations = lam[:done], tri[:done], done
+        elif self.algorithm == "dl":
+            out = self.ctx.dl_optimize(g.poses, g.fixed, ef, et, meas, info, int(nrunnings), *(rk or (None,)),
+                                       raise_on_fail=False, **self.dl_params)
+            rc, poses, chi2, dlt, tri, stp, done = out[:7]
+            if rk is not None:
+                self.last_edge_chi2, self.last_weights = out[7:]
+            self.last_deltas, self.last_trials, self.last_steps = dlt[:done], tri[:done], stp[:done]
+            self.last_iterations = done if rc == 0 else 0          # (g2o's optimize() returns 0 after Fail)
         else:
             if rk is None:
                 rc, poses, chi2 = self.ctx.gn_optimize(g.poses, g.fixed, ef, et, meas, info, int(nrunnings),
@@ -257,6 +274,20 @@ class GraphSLAM:
         self._grow_robust()
         m = self.graph.edge_level == 0
         return self._rk_kind[m], self._rk_delta[m]
+
+    def trustRegion(self) -> float:     # noqa: N802 (g2o spelling)
+        """OptimizationAlgorithmDogleg::trustRegion: delta after the last iteration of the last optimize (the initial delta
+        before any dogleg iteration)."""
+        if self.last_deltas is None or len(self.last_deltas) == 0:
+            return float(self.dl_params.get("initial_delta", DL_DEFAULTS["initial_delta"]))
+        return float(self.last_deltas[-1])
+
+    def lastStep(self) -> int:     # noqa: N802 (g2o spelling)
+        """OptimizationAlgorithmDogleg::lastStep: the kind of the last trial's step, 1 SD, 2 GN, 3 DL (DL_STEP_*; 0 before
+        any dogleg iteration)."""
+        if self.last_steps is None or len(self.last_steps) == 0:
+            return 0
+        return int(self.last_steps[-1])
 
     def currentLambda(self) -> float:     # noqa: N802 (g2o spelling)
         """OptimizationAlgorithmLevenberg::currentLambda: lambda after the last iteration of the last optimize (0 before

@@ -186,6 +186,58 @@ int cgmr_lm_optimize_robust_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, cons
                                 const double* d_info_upper, int iters, const cgmr_lm_params* params, double* chi2_out,
                                 double* lambda_out, int32_t* trials_out, int32_t* iters_done, const cgmr_robust* rk);
 
+/* Dogleg optimisation (C ABI version 105, added later under the same number: callers find it by its symbols): g2o's
+ * OptimizationAlgorithmDogleg [g2o-recalled: recalled from g2o, not read from its source; the contract is
+ * tests/ref_dogleg.py], the third algorithm of the optimisation-algorithm factory the reference includes (graph_slam.h:36,
+ * "dl_var").  At the start of a call delta = initial_delta, currentLambda = initial_lambda, wasPD = true.  Outer iteration i
+ * linearises once (currentChi = the (robust) chi2 at x, H and b = -J^T Omega e; fixed and inactive vertices stay out) and:
+ *   alpha = |b|^2 / (b^T H b), hsd = alpha b;
+ *   hgn solves H hgn = b -- H + currentLambda I on the free diagonal once any factorisation of the call has failed (wasPD
+ *   false); then an ok solve sets currentLambda = max(1e-12, currentLambda / (0.5 lambda_factor)), a failed one multiplies it
+ *   by lambda_factor and repeats, and above 1e3 the call fails (g2o's Fail);
+ *   trials: |hgn| < delta: h = hgn (CGMR_DL_STEP_GN); |hsd| > delta: h = delta / |hsd| hsd (_SD); else h = hsd + beta (hgn -
+ *   hsd) with |h| = delta (_DL); rho = (currentChi - chi2(x (+) h)) / (-h^T H h + 2 b^T h) (a gain below 1e-12 in magnitude
+ *   counts as 1e-12); rho > 0 keeps the step, otherwise x is restored bit for bit; rho > 0.75: delta = max(delta, 3 |h|),
+ *   rho < 0.25: delta *= 0.5; repeat while no step was good and the trials are fewer than max_trials.
+ * The call terminates (g2o's Terminate) after an iteration that ran max_trials trials -- even when its last one was good --
+ * or had no good step; that iteration counts as run.  H is never damped for alpha or the gain.  A rejected trial needs no
+ * new factorisation: its retry mixes the same hgn and hsd for the smaller delta.
+ *   params      nullable: g2o's defaults (initial_delta 1e4, max_trials 100, initial_lambda 1e-7, lambda_factor 10);
+ *               max_trials >= 1, the rest finite and > 0, lambda_factor > 1, or CGMR_E_INVALID before anything is queued
+ *   chi2_out    [iters+1] nullable: chi2 at the start and after each iteration (after the last one run: repeated)
+ *   delta_out   [iters]   nullable: delta at the end of each iteration (0 past iters_done)
+ *   trials_out  [iters]   nullable: trials of each iteration (0 past iters_done)
+ *   step_out    [iters]   nullable: CGMR_DL_STEP_* of each iteration's last trial (0 past iters_done)
+ *   iters_done  nullable: iterations run, a terminating one included
+ *   rk          nullable: the plain call; otherwise the robust rules of cgmr_robust above (robust chi2 and H)
+ * Returns CGMR_OK (also on termination), CGMR_E_CHOLESKY_BASE - i on g2o's Fail in iteration i (the poses at the last
+ * accepted step, the records of iterations 0 .. i-1, *iters_done = i), CGMR_E_INVALID, CGMR_E_HIP / _ALLOC, or
+ * CGMR_E_TIMEOUT when a bounded in-kernel wait runs out twice.  Shares the analysis cache with cgmr_gn_optimize*.  The device
+ * keeps the state; the host queues rounds and waits once per round: one wait when every first trial is accepted and H stays
+ * positive definite. */
+typedef struct cgmr_dl_params {
+  double initial_delta;
+  int32_t max_trials;
+  double initial_lambda;
+  double lambda_factor;
+} cgmr_dl_params;
+#define CGMR_DL_STEP_SD 1
+#define CGMR_DL_STEP_GN 2
+#define CGMR_DL_STEP_DL 3
+int cgmr_dl_optimize(cgmr_ctx* ctx, int nV, double* poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                     const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int iters,
+                     const cgmr_dl_params* params, double* chi2_out, double* delta_out, int32_t* trials_out,
+                     int32_t* step_out, int32_t* iters_done, const cgmr_robust* rk);
+/* Device-resident variant (d_poses / d_meas / d_info, and rk's kind / delta, on the context's device). */
+int cgmr_dl_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8_t* fixed, int nE,
+                         const int32_t* from_idx, const int32_t* to_idx, const double* d_meas_xyt,
+                         const double* d_info_upper, int iters, const cgmr_dl_params* params, double* chi2_out,
+                         double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
+                         const cgmr_robust* rk);
+/* The last cgmr_dl_optimize* call on this context: out[0] = host waits for the device, out[1] = trials run, out[2] =
+ * factorisations that served an iteration (failed damped ones included). */
+int cgmr_dl_last_stats(const cgmr_ctx* ctx, int64_t out[3]);
+
 /* The ordering + symbolic analysis + structure upload of the last analysed edge list stay on the context and are
  * reused by every later call (cgmr_gn_optimize*, cgmr_marginals, cgmr_covariance_estimate, cgmr_condense*) whose
  * (nV, from_idx, to_idx) are exactly the same -- the fixed flags are applied numerically and do not enter the
@@ -553,10 +605,17 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out);
 /* The optimiser cgmr_graph_optimize uses: CGMR_ALG_GAUSS_NEWTON (default, the reference's) or CGMR_ALG_LEVENBERG with
  * params (nullable: g2o's defaults), run as cgmr_lm_optimize does; a Levenberg call never returns CGMR_E_CHOLESKY_*.
  * cgmr_graph_lm_last: the records of the last Levenberg solve -- lambda_out / trials_out [cap] (nullable), returns the
- * iterations run (0 after a Gauss-Newton solve). */
+ * iterations run (0 after a Gauss-Newton solve).
+ * CGMR_ALG_DOGLEG (params must be NULL, else CGMR_E_INVALID) runs as cgmr_dl_optimize does, with the parameters of
+ * cgmr_graph_set_dogleg_params (checked there; default g2o's); it returns CGMR_E_CHOLESKY_BASE - i on g2o's Fail.
+ * cgmr_graph_dl_last: the records of the last dogleg solve -- delta_out / trials_out / step_out [cap] (nullable), returns
+ * the iterations run (0 after another algorithm's solve). */
 #define CGMR_ALG_GAUSS_NEWTON 0
 #define CGMR_ALG_LEVENBERG 1
+#define CGMR_ALG_DOGLEG 2
 int cgmr_graph_set_algorithm(cgmr_graph* g, int algorithm, const cgmr_lm_params* params);
+int cgmr_graph_set_dogleg_params(cgmr_graph* g, const cgmr_dl_params* params);
+int cgmr_graph_dl_last(const cgmr_graph* g, int cap, double* delta_out, int32_t* trials_out, int32_t* step_out);
 /* Robust kernels of the robot graph (cgmr_robust above), applied by cgmr_graph_optimize under either algorithm: own edges
  * [first, first + n) by insertion index take kind[k] / delta[k] (host arrays; delta nullable: 1.0, which only kind 0 may
  * keep); own edges added later take CGMR_RK_NONE.  The received edges take one class, set by cgmr_graph_set_received_robust

@@ -213,69 +213,72 @@ class Context:
     def synchronize(self):
         self._check(self.lib.cgmr_ctx_synchronize(self.h))
 
-    # ------------------------------------------------------------------ GN
+    # ------------------------------------------------------------------ GN / Levenberg-Marquardt / dogleg
+    @staticmethod
+    def _problem(poses, fixed, ef, et, meas, info):
+        """The six arrays of a problem as the library reads them.  ``poses`` a host array: everything is host memory, and the
+        call writes to a copy of the poses; ``poses`` a (device pointer, nV) pair: meas / info are device pointers too.
+        Returns (nV, the poses' copy or None, the six ctypes arguments, the arrays they point into)."""
+        keep = [np.ascontiguousarray(fixed, dtype=np.uint8), np.ascontiguousarray(ef, dtype=np.int32),
+                np.ascontiguousarray(et, dtype=np.int32)]
+        if isinstance(poses, tuple):
+            (d_poses, nV), p = poses, None
+            dev = [C.c_void_p(d_poses), C.c_void_p(meas), C.c_void_p(info)]
+        else:
+            p = np.ascontiguousarray(poses, dtype=np.float64).copy()
+            keep += [p, np.ascontiguousarray(meas, dtype=np.float64), np.ascontiguousarray(info, dtype=np.float64)]
+            nV, dev = p.shape[0], [_ptr(a) for a in keep[3:]]
+        fx, f, t = (_ptr(a) for a in keep[:3])
+        return nV, p, (dev[0], fx, C.c_int(len(keep[1])), f, t, dev[1], dev[2]), keep
+
+    @staticmethod
+    def _records(iters, n_int):
+        """The outputs of a call: chi2 [iters + 1]; for a trust-region algorithm (``n_int`` not None) one float64 record
+        [iters] (lambdas / deltas) and ``n_int`` int32 ones (trials, steps)."""
+        if n_int is None:
+            return [np.zeros(iters + 1)]
+        return [np.zeros(iters + 1), np.zeros(iters)] + [np.zeros(iters, dtype=np.int32) for _ in range(n_int)]
+
+    def _optimize(self, entry, problem, iters, prm=None, n_int=None, rk=False, allow_fail=False):
+        """One cgmr_*_optimize* call on ``problem`` (the arguments of _problem).  ``prm``: the parameters of a trust-region
+        algorithm, which also returns its iterations done; ``rk``: a cgmr_robust, None for a null one, False for an entry
+        point that takes none.  Returns (status, [the poses,] chi2, [records, iterations done])."""
+        nV, p, (poses, fixed, nE, ef, et, meas, info), _keep = self._problem(*problem)
+        rec, done = self._records(iters, n_int), C.c_int32(0)
+        args = [self.h, C.c_int(nV), poses, fixed, nE, ef, et, meas, info, C.c_int(iters)]
+        if prm is not None:
+            args.append(C.byref(prm))
+        args += [_ptr(a) for a in rec]
+        if prm is not None:
+            args.append(C.byref(done))
+        if rk is not False:
+            args.append(C.byref(rk) if rk is not None else C.c_void_p(0))
+        rc = getattr(self.lib, entry)(*args)
+        self._check(rc, allow_cholesky=allow_fail)
+        return (rc,) + (() if p is None else (p,)) + tuple(rec) + (() if prm is None else (int(done.value),))
+
     def gn_optimize(self, poses, fixed, ef, et, meas, info, iters, raise_on_cholesky=True):
         """Host arrays in, host arrays out.  Returns (status, poses, chi2[iters+1])."""
-        p = np.ascontiguousarray(poses, dtype=np.float64).copy()
-        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
-        ef = np.ascontiguousarray(ef, dtype=np.int32)
-        et = np.ascontiguousarray(et, dtype=np.int32)
-        meas = np.ascontiguousarray(meas, dtype=np.float64)
-        info = np.ascontiguousarray(info, dtype=np.float64)
-        chi = np.zeros(iters + 1)
-        rc = self.lib.cgmr_gn_optimize(self.h, C.c_int(p.shape[0]), _ptr(p), _ptr(fixed), C.c_int(len(ef)),
-                                       _ptr(ef), _ptr(et), _ptr(meas), _ptr(info), C.c_int(iters), _ptr(chi))
-        self._check(rc, allow_cholesky=not raise_on_cholesky)
-        return rc, p, chi
+        return self._optimize("cgmr_gn_optimize", (poses, fixed, ef, et, meas, info), iters, allow_fail=not raise_on_cholesky)
 
     def gn_optimize_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters,
                         raise_on_cholesky=True):
         """Device pointers (ints) for poses/meas/info, host numpy for the structure."""
-        chi = np.zeros(iters + 1)
-        rc = self.lib.cgmr_gn_optimize_dev(self.h, C.c_int(nV), C.c_void_p(d_poses_ptr), _ptr(fixed),
-                                           C.c_int(len(ef)), _ptr(ef), _ptr(et), C.c_void_p(d_meas_ptr),
-                                           C.c_void_p(d_info_ptr), C.c_int(iters), _ptr(chi))
-        self._check(rc, allow_cholesky=not raise_on_cholesky)
-        return rc, chi
+        return self._optimize("cgmr_gn_optimize_dev", ((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), iters,
+                              allow_fail=not raise_on_cholesky)
 
     def lm_optimize(self, poses, fixed, ef, et, meas, info, iters, **params):
         """Levenberg-Marquardt (cgmr_lm_optimize, g2o's OptimizationAlgorithmLevenberg); ``params``: tau, initial_lambda,
         max_trials, good_step_lower, good_step_upper (g2o's defaults otherwise).  Host arrays in and out.  Returns
         (status, poses, chi2[iters+1], lambdas[iters], trials[iters], iters_done); termination is status 0 with
         iters_done < iters, never a Cholesky status."""
-        p = np.ascontiguousarray(poses, dtype=np.float64).copy()
-        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
-        ef = np.ascontiguousarray(ef, dtype=np.int32)
-        et = np.ascontiguousarray(et, dtype=np.int32)
-        meas = np.ascontiguousarray(meas, dtype=np.float64)
-        info = np.ascontiguousarray(info, dtype=np.float64)
-        chi = np.zeros(iters + 1)
-        lam = np.zeros(iters)
-        tri = np.zeros(iters, dtype=np.int32)
-        done = C.c_int32(0)
-        prm = lm_params(**params)
-        rc = self.lib.cgmr_lm_optimize(self.h, C.c_int(p.shape[0]), _ptr(p), _ptr(fixed), C.c_int(len(ef)), _ptr(ef), _ptr(et),
-                                       _ptr(meas), _ptr(info), C.c_int(iters), C.byref(prm), _ptr(chi), _ptr(lam), _ptr(tri),
-                                       C.byref(done))
-        self._check(rc)
-        return rc, p, chi, lam, tri, int(done.value)
+        return self._optimize("cgmr_lm_optimize", (poses, fixed, ef, et, meas, info), iters, lm_params(**params), 1)
 
     def lm_optimize_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters, **params):
         """Device pointers (ints) for poses/meas/info, host numpy for the structure.  Returns
         (status, chi2[iters+1], lambdas[iters], trials[iters], iters_done)."""
-        chi = np.zeros(iters + 1)
-        lam = np.zeros(iters)
-        tri = np.zeros(iters, dtype=np.int32)
-        done = C.c_int32(0)
-        prm = lm_params(**params)
-        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
-        ef = np.ascontiguousarray(ef, dtype=np.int32)
-        et = np.ascontiguousarray(et, dtype=np.int32)
-        rc = self.lib.cgmr_lm_optimize_dev(self.h, C.c_int(nV), C.c_void_p(d_poses_ptr), _ptr(fixed), C.c_int(len(ef)), _ptr(ef),
-                                           _ptr(et), C.c_void_p(d_meas_ptr), C.c_void_p(d_info_ptr), C.c_int(iters),
-                                           C.byref(prm), _ptr(chi), _ptr(lam), _ptr(tri), C.byref(done))
-        self._check(rc)
-        return rc, chi, lam, tri, int(done.value)
+        return self._optimize("cgmr_lm_optimize_dev", ((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), iters,
+                              lm_params(**params), 1)
 
     # ------------------------------------------------------------------ robust kernels
     @staticmethod
@@ -293,74 +296,32 @@ class Context:
         """gn_optimize with robust kernels (cgmr_gn_optimize_robust): ``kind`` a name, a code or per-edge array of either,
         ``delta`` a scalar or per-edge array.  Returns (status, poses, robust chi2[iters+1], e2 [nE], weights [nE]), the last
         two at the returned estimate."""
-        p = np.ascontiguousarray(poses, dtype=np.float64).copy()
-        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
-        ef = np.ascontiguousarray(ef, dtype=np.int32)
-        et = np.ascontiguousarray(et, dtype=np.int32)
-        meas = np.ascontiguousarray(meas, dtype=np.float64)
-        info = np.ascontiguousarray(info, dtype=np.float64)
         rk, e2, w, _keep = self._robust(kind, delta, len(ef))
-        chi = np.zeros(iters + 1)
-        rc = self.lib.cgmr_gn_optimize_robust(self.h, C.c_int(p.shape[0]), _ptr(p), _ptr(fixed), C.c_int(len(ef)), _ptr(ef),
-                                              _ptr(et), _ptr(meas), _ptr(info), C.c_int(iters), _ptr(chi), C.byref(rk))
-        self._check(rc, allow_cholesky=not raise_on_cholesky)
-        return rc, p, chi, e2, w
+        return self._optimize("cgmr_gn_optimize_robust", (poses, fixed, ef, et, meas, info), iters, rk=rk,
+                              allow_fail=not raise_on_cholesky) + (e2, w)
 
     def gn_optimize_robust_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters, kind="none", delta=1.0,
                                d_kind_ptr=None, d_delta_ptr=None, raise_on_cholesky=True):
         """gn_optimize_dev with robust kernels: per-edge kinds (uint8) / deltas (float64) as device pointers, or a uniform
         ``kind`` / ``delta``.  Returns (status, robust chi2[iters+1], e2 [nE], weights [nE])."""
-        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
-        ef = np.ascontiguousarray(ef, dtype=np.int32)
-        et = np.ascontiguousarray(et, dtype=np.int32)
         rk, e2, w, _keep = self._robust(kind, delta, len(ef), d_kind_ptr, d_delta_ptr)
-        chi = np.zeros(iters + 1)
-        rc = self.lib.cgmr_gn_optimize_robust_dev(self.h, C.c_int(nV), C.c_void_p(d_poses_ptr), _ptr(fixed), C.c_int(len(ef)),
-                                                  _ptr(ef), _ptr(et), C.c_void_p(d_meas_ptr), C.c_void_p(d_info_ptr),
-                                                  C.c_int(iters), _ptr(chi), C.byref(rk))
-        self._check(rc, allow_cholesky=not raise_on_cholesky)
-        return rc, chi, e2, w
+        return self._optimize("cgmr_gn_optimize_robust_dev", ((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), iters,
+                              rk=rk, allow_fail=not raise_on_cholesky) + (e2, w)
 
     def lm_optimize_robust(self, poses, fixed, ef, et, meas, info, iters, kind="none", delta=1.0, **params):
         """lm_optimize with robust kernels (``kind`` / ``delta`` as gn_optimize_robust).  Returns (status, poses, robust
         chi2[iters+1], lambdas[iters], trials[iters], iters_done, e2 [nE], weights [nE])."""
-        p = np.ascontiguousarray(poses, dtype=np.float64).copy()
-        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
-        ef = np.ascontiguousarray(ef, dtype=np.int32)
-        et = np.ascontiguousarray(et, dtype=np.int32)
-        meas = np.ascontiguousarray(meas, dtype=np.float64)
-        info = np.ascontiguousarray(info, dtype=np.float64)
         rk, e2, w, _keep = self._robust(kind, delta, len(ef))
-        chi = np.zeros(iters + 1)
-        lam = np.zeros(iters)
-        tri = np.zeros(iters, dtype=np.int32)
-        done = C.c_int32(0)
-        prm = lm_params(**params)
-        rc = self.lib.cgmr_lm_optimize_robust(self.h, C.c_int(p.shape[0]), _ptr(p), _ptr(fixed), C.c_int(len(ef)), _ptr(ef),
-                                              _ptr(et), _ptr(meas), _ptr(info), C.c_int(iters), C.byref(prm), _ptr(chi),
-                                              _ptr(lam), _ptr(tri), C.byref(done), C.byref(rk))
-        self._check(rc)
-        return rc, p, chi, lam, tri, int(done.value), e2, w
+        return self._optimize("cgmr_lm_optimize_robust", (poses, fixed, ef, et, meas, info), iters, lm_params(**params), 1,
+                              rk=rk) + (e2, w)
 
     def lm_optimize_robust_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters, kind="none", delta=1.0,
                                d_kind_ptr=None, d_delta_ptr=None, **params):
         """lm_optimize_dev with robust kernels (as gn_optimize_robust_dev).  Returns (status, robust chi2[iters+1],
         lambdas[iters], trials[iters], iters_done, e2 [nE], weights [nE])."""
-        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
-        ef = np.ascontiguousarray(ef, dtype=np.int32)
-        et = np.ascontiguousarray(et, dtype=np.int32)
         rk, e2, w, _keep = self._robust(kind, delta, len(ef), d_kind_ptr, d_delta_ptr)
-        chi = np.zeros(iters + 1)
-        lam = np.zeros(iters)
-        tri = np.zeros(iters, dtype=np.int32)
-        done = C.c_int32(0)
-        prm = lm_params(**params)
-        rc = self.lib.cgmr_lm_optimize_robust_dev(self.h, C.c_int(nV), C.c_void_p(d_poses_ptr), _ptr(fixed), C.c_int(len(ef)),
-                                                  _ptr(ef), _ptr(et), C.c_void_p(d_meas_ptr), C.c_void_p(d_info_ptr),
-                                                  C.c_int(iters), C.byref(prm), _ptr(chi), _ptr(lam), _ptr(tri), C.byref(done),
-                                                  C.byref(rk))
-        self._check(rc)
-        return rc, chi, lam, tri, int(done.value), e2, w
+        return self._optimize("cgmr_lm_optimize_robust_dev", ((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), iters,
+                              lm_params(**params), 1, rk=rk) + (e2, w)
 
     def lm_last_stats(self):
         """The last lm_optimize* call: dict(host_waits, trials)."""
@@ -376,21 +337,10 @@ class Context:
         trials[iters], steps[iters], iters_done), with e2 [nE] and weights [nE] appended when ``kind`` is given.
         Termination is status 0 with iters_done < iters; g2o's Fail in iteration i is CGMR_E_CHOLESKY_BASE - i (raised
         unless ``raise_on_fail`` is False)."""
-        p = np.ascontiguousarray(poses, dtype=np.float64).copy()
-        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
-        ef = np.ascontiguousarray(ef, dtype=np.int32)
-        et = np.ascontiguousarray(et, dtype=np.int32)
-        meas = np.ascontiguousarray(meas, dtype=np.float64)
-        info = np.ascontiguousarray(info, dtype=np.float64)
         prm = dl_params(**params)
         rk, e2, w, _keep = self._robust(kind, delta, len(ef)) if kind is not None else (None, None, None, None)
-        chi, dlt, tri, stp = np.zeros(iters + 1), np.zeros(iters), np.zeros(iters, dtype=np.int32), np.zeros(iters, dtype=np.int32)
-        done = C.c_int32(0)
-        rc = self.lib.cgmr_dl_optimize(self.h, C.c_int(p.shape[0]), _ptr(p), _ptr(fixed), C.c_int(len(ef)), _ptr(ef), _ptr(et),
-                                       _ptr(meas), _ptr(info), C.c_int(iters), C.byref(prm), _ptr(chi), _ptr(dlt), _ptr(tri),
-                                       _ptr(stp), C.byref(done), C.byref(rk) if rk is not None else C.c_void_p(0))
-        self._check(rc, allow_cholesky=not raise_on_fail)
-        out = (rc, p, chi, dlt, tri, stp, int(done.value))
+        out = self._optimize("cgmr_dl_optimize", (poses, fixed, ef, et, meas, info), iters, prm, 2, rk=rk,
+                             allow_fail=not raise_on_fail)
         return out + (e2, w) if kind is not None else out
 
     def dl_optimize_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters, kind=None, delta=1.0,
@@ -398,21 +348,12 @@ class Context:
         """Device pointers (ints) for poses/meas/info, host numpy for the structure; robust kernels as
         gn_optimize_robust_dev takes them (``kind`` None and no device arrays: the plain call).  Returns (status,
         chi2[iters+1], deltas[iters], trials[iters], steps[iters], iters_done), with e2 and weights appended when robust."""
-        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
-        ef = np.ascontiguousarray(ef, dtype=np.int32)
-        et = np.ascontiguousarray(et, dtype=np.int32)
         prm = dl_params(**params)
         robust = kind is not None or d_kind_ptr is not None or d_delta_ptr is not None
         rk, e2, w, _keep = self._robust("none" if kind is None else kind, delta, len(ef), d_kind_ptr, d_delta_ptr) if robust \
             else (None, None, None, None)
-        chi, dlt, tri, stp = np.zeros(iters + 1), np.zeros(iters), np.zeros(iters, dtype=np.int32), np.zeros(iters, dtype=np.int32)
-        done = C.c_int32(0)
-        rc = self.lib.cgmr_dl_optimize_dev(self.h, C.c_int(nV), C.c_void_p(d_poses_ptr), _ptr(fixed), C.c_int(len(ef)), _ptr(ef),
-                                           _ptr(et), C.c_void_p(d_meas_ptr), C.c_void_p(d_info_ptr), C.c_int(iters),
-                                           C.byref(prm), _ptr(chi), _ptr(dlt), _ptr(tri), _ptr(stp), C.byref(done),
-                                           C.byref(rk) if rk is not None else C.c_void_p(0))
-        self._check(rc, allow_cholesky=not raise_on_fail)
-        out = (rc, chi, dlt, tri, stp, int(done.value))
+        out = self._optimize("cgmr_dl_optimize_dev", ((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), iters, prm, 2,
+                             rk=rk, allow_fail=not raise_on_fail)
         return out + (e2, w) if robust else out
 
     def dl_last_stats(self):

@@ -1,7 +1,10 @@
 // C ABI of libcgmr.so (include/cgmr.h): context management and the Gauss-Newton driver.
 // Compiled with hipcc; contains no kernels (those live in gn_kernels.hip / matcher_kernels.hip).
 #include "cgmr_ctx.h"
+#include "dl_device.h"
 #include "gn_host.h"
+#include "lm_device.h"
+#include "tr_device.h"
 
 #include <algorithm>
 #include <chrono>
@@ -10,6 +13,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 namespace cgmr {
@@ -618,19 +622,16 @@ struct KTimer {   // optional per-launch-class timing (profiling mode only)
   }
 };
 
-// one Gauss-Newton pass on the uploaded structure: linearise + chi2 [+ assemble + factor [+ solve + update]]
-void gn_pass(cgmr_ctx* ctx, double* d_poses, const GnEdges& Ed, int it, bool chi_only,
-             bool solve_and_update, bool write_l11c) {
-  gn_pass_on(ctx, ctx->gn, ctx->stream, d_poses, Ed, it, chi_only, solve_and_update, write_l11c);
+void gn_pass(cgmr_ctx* ctx, double* d_poses, const GnEdges& Ed, const GnPassOpts& o) {
+  gn_pass_on(ctx, ctx->gn, ctx->stream, d_poses, Ed, o);
 }
 
-// the same on an explicit device view (the context's, or a replica with its own numeric work space) and stream
-void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, const GnEdges& Ed, int it, bool chi_only,
-                bool solve_and_update, bool write_l11c, LmState* lm, bool lm_init, const DlState* dl) {
+void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, const GnEdges& Ed, const GnPassOpts& o) {
+  const bool write_l11c = o.write_l11c;
   KTimer T{ctx, st};
-  T.run(0, 1, [&] { launch_linearize(st, D, d_poses, Ed, chi_only ? 1 : 0); });
-  if (chi_only || D.nf == 0) {
-    T.run(2, 1, [&] { launch_chi2(st, D, D.chi2 + it); });
+  T.run(0, 1, [&] { launch_linearize(st, D, d_poses, Ed, o.chi_only ? 1 : 0); });
+  if (o.chi_only || D.nf == 0) {
+    T.run(2, 1, [&] { launch_chi2(st, D, D.chi2 + o.chi_slot); });
     return;
   }
   // the assembled panels start from zero: H blocks and b (k_assemble), then the children's contributions level by level
@@ -643,11 +644,7 @@ void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, con
   }
   D.pan_clean = false;
   T.run(1, 1, [&] { launch_assemble(st, D); });                // + the chi2 sum of this iteration (slot = iterations done)
-  if (lm) {                                                     // a Levenberg-Marquardt trial: H + lambda I (lm_kernels.hip)
-    if (lm_init) launch_lm_init(st, D, lm);
-    launch_lm_damp(st, D, lm);
-  }
-  if (dl) launch_dl_damp(st, D, dl);                            // a dogleg head: H + currentLambda I once H was not PD (dl_kernels.hip)
+  if (o.after_assemble) o.after_assemble(st, D, o.after_assemble_arg);
   static const bool trace = getenv("CGMR_TRACE_LAUNCHES") != nullptr;
   if (trace)
     fprintf(stderr, "[cgmr] arena %p .. %p; work %p rel %p Pan %p Ablk %p bvec %p yvec %p uvec %p Lbuf %p Ubuf %p chi2 %p\n",
@@ -678,36 +675,103 @@ void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, con
   // the top of the tree in one launch: assembly, factorisation, forward and backward solve of the block's columns
   static const bool clear_in_top = !(getenv("CGMR_CLEAR_IN_TOP") && atoi(getenv("CGMR_CLEAR_IN_TOP")) == 0);
   // (the chained backward solve works with L11^-1 of every front: made by the idle workgroups of the top-block launch)
-  const bool chain = solve_and_update && D.bwd_chain_level < D.nlevels;
+  const bool chain = o.solve && D.bwd_chain_level < D.nlevels;
   if (D.top_nfronts > 0) {
     T.run(5, 1, [&] { launch_top_block(st, D, /*store_l=*/write_l11c, write_l11c, clear_in_top, chain); });
     D.pan_clean = clear_in_top && D.pan_doubles > 0;
   } else if (chain) {
     T.run(5, 1, [&] { launch_invert_fronts(st, D); });
   }
-  if (!solve_and_update) return;
+  if (!o.solve) return;
   // (the forward solve L y = b rides through k_front_factor as an extra row of every front)
   if (D.bwd_chain_level < D.nlevels) T.run(6, 1, [&] { launch_bwd_chain(st, D); });
   for (int l = D.bwd_chain_level - 1; l >= 0; l--) T.run(6, 1, [&] { launch_bwd_level(st, D, l); });
-  if (!dl) T.run(7, 1, [&] { launch_update(st, D, d_poses); });   // (a dogleg head leaves the step to its tails)
+  if (o.update_poses) T.run(7, 1, [&] { launch_update(st, D, d_poses); });
 }
+
+int LevelwiseScope::arm(hipStream_t st, int it0) {
+  count_timeout(ctx);
+  armed = true;
+  chain_was = D.bwd_chain_level;
+  merge_was = D.h_level_merge;
+  D.bwd_chain_level = D.nlevels;
+  D.h_level_merge.assign(D.nlevels, 0);
+  const int fresh[4] = {0, it0, 0, 0};
+  HIP_TRY(ctx, hipMemcpyAsync(D.status, fresh, sizeof fresh, hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+// What an optimisation call does around its device work, whatever the algorithm: the structure and the masks with their
+// wall-clock marks, the timing events, the caller's host copy of the estimates, the wait, cgmr_gn_timing's five entries.
+struct GnCall {
+  cgmr_ctx* ctx;
+  int nV;
+  double* d_poses;
+  double t0, t1 = 0, t2 = 0;
+  double* poses_host = nullptr;
+  struct Readback { void* dst; const void* src; size_t bytes; };
+
+  GnCall(cgmr_ctx* c, int nv, double* dp) : ctx(c), nV(nv), d_poses(dp), t0(wall_s()) {}
+  // chi_slots: iterations whose chi2 slot the structure's work space must hold
+  int prepare(const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et, int n_active, int chi_slots,
+              const int32_t* hub_vertices, int n_hub_vertices) {
+    int rc = prepare_structure(ctx, nV, nE, ef, et, chi_slots, hub_vertices, n_hub_vertices);
+    if (rc) return rc;
+    t1 = wall_s();
+    rc = prepare_pass(ctx, fixed, nE, ef, et, n_active, 0, 1);
+    t2 = wall_s();
+    return rc;
+  }
+  // the device work starts here (ev0; its end: the last hipEventRecord of ev1 before a wait)
+  int begin() {
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    // the caller's host copy of the estimates rides in every wait (a robot graph whose peers have asked for condensed graphs
+    // picks their gauges from it right after the solve)
+    poses_host = ctx->poses_out_host;
+    ctx->poses_out_host = nullptr;
+    return 0;
+  }
+  int wait(std::initializer_list<Readback> what) {
+    hipStream_t st = ctx->stream;
+    for (const Readback& r : what)
+      if (r.bytes) HIP_TRY(ctx, hipMemcpyAsync(r.dst, r.src, r.bytes, hipMemcpyDeviceToHost, st));
+    if (poses_host && nV > 0) HIP_TRY(ctx, hipMemcpyAsync(poses_host, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+  }
+  void finish() {
+    const Symbolic& S = ctx->sym;
+    if (ctx->profiling) profile_collect(ctx);
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+    ctx->timing[0] = S.t_order;
+    ctx->timing[1] = S.t_struct;
+    ctx->timing[2] = (t2 - t1) + S.t_upload;     // structure blob (host staging + H2D enqueue) + per-pass masks
+    ctx->timing[3] = 1e-3 * ms;
+    ctx->timing[4] = wall_s() - t0;
+  }
+};
 
 int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef,
            const int32_t* et, const GnEdges& Ed, int iters, double* chi2_out, const int32_t* hub_vertices, int n_hub_vertices) {
-  double t0 = wall_s();
-  Symbolic& S = ctx->sym;
-  int rc = prepare_structure(ctx, nV, nE, ef, et, iters, hub_vertices, n_hub_vertices);
+  GnCall call(ctx, nV, d_poses);
+  int rc = call.prepare(fixed, nE, ef, et, Ed.n_active, iters, hub_vertices, n_hub_vertices);
   if (rc) return rc;
-  double t1 = wall_s();
-  rc = prepare_pass(ctx, fixed, nE, ef, et, Ed.n_active, 0, 1);
-  if (rc) return rc;
-  double t2 = wall_s();
   GnDevice& D = ctx->gn;
   hipStream_t st = ctx->stream;
   // (robust statistics: written by the final chi-only pass, at the estimate the call returns)
   GnEdges Ei = Ed;
   Ei.rk_stats = nullptr;
-  HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));
+  // iterations it0 .. iters - 1, then the chi-only pass at the estimate they leave
+  auto queue_from = [&](int it0) {
+    GnPassOpts o;
+    for (o.chi_slot = it0; o.chi_slot < iters; o.chi_slot++) gn_pass(ctx, d_poses, Ei, o);
+    o.chi_only = true;
+    gn_pass(ctx, d_poses, Ed, o);
+  };
+  rc = call.begin();
+  if (rc) return rc;
   // Every launch of a GN iteration is the same whatever the iteration's number (status[1] on the device supplies the
   // chi2 slot and the failure tag): CGMR_GRAPH=1 captures one iteration into a hipGraph and replays it.
   static const bool graph_mode = getenv("CGMR_GRAPH") && atoi(getenv("CGMR_GRAPH")) != 0;
@@ -717,77 +781,133 @@ int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
   if (graph_mode && !ctx->profiling && !trace_launches && iters >= 2 && st != nullptr && D.nf > 0) {
     gn_init_kernels();
     HIP_TRY(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    gn_pass(ctx, d_poses, Ei, 0, false, true, false);
+    gn_pass(ctx, d_poses, Ei, GnPassOpts());
     HIP_TRY(ctx, hipStreamEndCapture(st, &graph));
     HIP_TRY(ctx, hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0));
     for (int it = 0; it < iters; it++) HIP_TRY(ctx, hipGraphLaunch(graph_exec, st));
-    gn_pass(ctx, d_poses, Ed, iters, true, true, false);
+    queue_from(iters);
   } else {
-    for (int it = 0; it <= iters; it++) gn_pass(ctx, d_poses, it == iters ? Ed : Ei, it, it == iters, true, false);
+    queue_from(0);
   }
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
   const double t3 = wall_s();
-  // read back chi2 + status
   std::vector<double> chi(iters + 1);
   int status4[4] = {0, 0, 0, 0};
-  HIP_TRY(ctx, hipMemcpyAsync(chi.data(), D.chi2, sizeof(double) * (iters + 1), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
-  // the caller's host copy of the estimates, in the same wait (a robot graph whose peers have asked for condensed graphs
-  // picks their gauges from it right after the solve)
-  double* const poses_host = ctx->poses_out_host;
-  ctx->poses_out_host = nullptr;
-  if (poses_host && nV > 0) HIP_TRY(ctx, hipMemcpyAsync(poses_host, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  HIP_TRY(ctx, hipGetLastError());
+  const std::initializer_list<GnCall::Readback> results = {{chi.data(), D.chi2, sizeof(double) * (iters + 1)}, {status4, D.status, sizeof status4}};
+  rc = call.wait(results);
+  if (rc) return rc;
   {
     // CGMR_GN_TRACE: where a solve's wall time goes beside the analysis -- queueing the launches, waiting for the stream
     static const bool gn_trace = getenv("CGMR_GN_TRACE") != nullptr;
     if (gn_trace) {
       const double t4 = wall_s();
-      ctx->trace_n++; ctx->trace_sum[0] += t1 - t0; ctx->trace_sum[1] += t2 - t1; ctx->trace_sum[2] += t3 - t2; ctx->trace_sum[3] += t4 - t3;
+      ctx->trace_n++; ctx->trace_sum[0] += call.t1 - call.t0; ctx->trace_sum[1] += call.t2 - call.t1; ctx->trace_sum[2] += t3 - call.t2; ctx->trace_sum[3] += t4 - t3;
     }
   }
   if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
   if (graph) (void)hipGraphDestroy(graph);
   if (status4[2] != 0 && status4[0] > 0) {
-    // A bounded wait of the chained backward solve ran out (status[2]): a hand-off between workgroups that never arrived,
-    // not a numerical failure.  The iteration it happened in (status[0] - 1) and the later ones were not applied
-    // (k_update_poses leaves the poses alone once status[0] is set), so they are repeated from the poses as they stand with
-    // one backward launch per tree level -- no in-kernel waits -- and the call goes on as if nothing had happened.
-    ctx->gn_timeouts++;
-    ctx->fwd_merge_any = false;                                  // (the next structures merge only what is certainly resident)
+    // A bounded wait of the chained backward solve ran out.  The iteration it happened in (status[0] - 1) and the later ones
+    // were not applied (k_update_poses leaves the poses alone once status[0] is set), so they are repeated from the poses as
+    // they stand, level-wise, and the call goes on as if nothing had happened.
     const int it0 = status4[0] - 1;
-    const int chain_was = D.bwd_chain_level;
-    D.bwd_chain_level = D.nlevels;
-    const std::vector<uint8_t> merge_was = D.h_level_merge;
-    D.h_level_merge.assign(D.nlevels, 0);
-    const int fresh[4] = {0, it0, 0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(D.status, fresh, sizeof fresh, hipMemcpyHostToDevice, st));
-    for (int it = it0; it <= iters; it++) gn_pass(ctx, d_poses, it == iters ? Ed : Ei, it, it == iters, true, false);
-    HIP_TRY(ctx, hipMemcpyAsync(chi.data(), D.chi2, sizeof(double) * (iters + 1), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
-    if (poses_host && nV > 0) HIP_TRY(ctx, hipMemcpyAsync(poses_host, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    HIP_TRY(ctx, hipGetLastError());
-    D.bwd_chain_level = chain_was;
-    D.h_level_merge = merge_was;
+    LevelwiseScope levelwise(ctx, D);
+    rc = levelwise.arm(st, it0);
+    if (rc) return rc;
+    queue_from(it0);
+    rc = call.wait(results);
+    if (rc) return rc;
     if (status4[2] != 0) return set_err(ctx, CGMR_E_TIMEOUT, "backward solve: a bounded device-side wait ran out twice");
   }
   const int status = status4[0];
-  if (ctx->profiling) profile_collect(ctx);
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+  call.finish();
   if (chi2_out) memcpy(chi2_out, chi.data(), sizeof(double) * (iters + 1));
-  ctx->timing[0] = S.t_order;
-  ctx->timing[1] = S.t_struct;
-  ctx->timing[2] = (t2 - t1) + S.t_upload;     // structure blob (host staging + H2D enqueue) + per-pass masks
-  ctx->timing[3] = 1e-3 * ms;
-  ctx->timing[4] = wall_s() - t0;
   if (status != 0)
     return set_err(ctx, CGMR_E_CHOLESKY_BASE - (status - 1),
                    "Cholesky failed (non-positive pivot) in GN iteration %d; poses left at the last good update",
                    status - 1);
   return CGMR_OK;
+}
+
+// Levenberg-Marquardt and dogleg are two policies of one driver.  A policy P supplies
+//   State, L (its device buffers; L.S the state, L.saved the saved poses), kName;
+//   reserve():      its arena laid out as state | records | work space, L bound to it; the bytes of state + records
+//   start():        the state a call begins with;
+//   queue_round():  the launches of one round, from the host's copy of the state;
+//   also_read():    what a round's wait reads back beside state + records;
+//   empty_system(): the closed-form answer when nothing can move, into the host's copy of state + records;
+//   finish():       records and statistics out, the call's return code.
+// The driver owns the rest: upload, the saved poses, the rounds with their one wait each, a timed-out round's repeat
+// (LevelwiseScope), the final pass of the robust statistics.
+template <typename P>
+static int tr_run(cgmr_ctx* ctx, P& pol, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
+                  const GnEdges& Ed, int iters, const int32_t* hub_vertices, int n_hub_vertices) {
+  GnCall call(ctx, nV, d_poses);
+  // (the chi2 slots a trial uses: slot 0 only -- the cache entry of a Gauss-Newton call on the same edge list serves)
+  int rc = call.prepare(fixed, nE, ef, et, Ed.n_active, 1, hub_vertices, n_hub_vertices);
+  if (rc) return rc;
+  GnDevice& D = ctx->gn;
+  hipStream_t st = ctx->stream;
+  size_t rec_bytes = 0;
+  rc = pol.reserve(ctx, iters, nV, D.nf, nE, &rec_bytes);
+  if (rc) return rc;
+  char* const d = (char*)pol.L.S;
+  std::vector<char> h(rec_bytes, 0);                          // the host's copy of state + records
+  typename P::State hs = pol.start(iters);
+  memcpy(h.data(), &hs, sizeof hs);
+  HIP_TRY(ctx, hipMemcpyAsync(d, h.data(), rec_bytes, hipMemcpyHostToDevice, st));
+  if (nV > 0) HIP_TRY(ctx, hipMemcpyAsync(pol.L.saved, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToDevice, st));
+  rc = call.begin();
+  if (rc) return rc;
+  int64_t waits = 0;
+  if (D.nf == 0 || iters == 0) {
+    // nothing to move (or nothing asked): chi2 at x, and what g2o makes of an empty system
+    GnPassOpts chi_pass;
+    chi_pass.chi_only = true;
+    gn_pass(ctx, d_poses, Ed, chi_pass);
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
+    double chi0 = 0;
+    rc = call.wait({{&chi0, D.chi2, sizeof(double)}});
+    if (rc) return rc;
+    waits = 1;
+    pol.empty_system(hs, h.data(), chi0, iters);
+  } else {
+    LevelwiseScope levelwise(ctx, D);
+    GnEdges Ei = Ed;                                         // (robust statistics: one chi-only pass on the final poses below)
+    Ei.rk_stats = nullptr;
+    for (;;) {
+      pol.queue_round(ctx, D, st, nV, d_poses, Ei, hs, iters);
+      HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
+      rc = call.wait({{h.data(), d, rec_bytes}, pol.also_read(D)});
+      if (rc) return rc;
+      waits++;
+      memcpy(&hs, h.data(), sizeof hs);
+      if (hs.halted) {
+        // A bounded wait ran out in a pass (status[2]): not a numerical verdict.  The poses are those the trial started from
+        // and nothing queued behind it changed anything; the call goes on from the state as it stands, level-wise.
+        if (levelwise.armed) return set_err(ctx, CGMR_E_TIMEOUT, "%s: a bounded device-side wait ran out twice", P::kName);
+        rc = levelwise.arm(st);
+        if (rc) return rc;
+        hs.halted = 0;
+        hs.accept = -1;
+        HIP_TRY(ctx, hipMemcpyAsync(pol.L.S, &hs, sizeof hs, hipMemcpyHostToDevice, st));
+        continue;
+      }
+      if (hs.done) break;
+    }
+    if (Ed.rk_stats) launch_linearize(st, D, d_poses, Ed, 1);   // (read back by the caller, behind the stream)
+  }
+  call.finish();
+  return pol.finish(ctx, hs, h.data(), std::min(hs.iter, iters), iters, waits);
+}
+
+// records [0, ran) of an iteration's array to the caller's (nullable), zeros behind them
+template <typename T>
+static void records_out(T* out, const T* rec, int ran, int iters) {
+  if (out) for (int k = 0; k < iters; k++) out[k] = k < ran ? rec[k] : T(0);
+}
+static void chi2_records_out(double* out, const double* rec, int ran, int iters) {
+  if (out) for (int k = 0; k <= iters; k++) out[k] = rec[std::min(k, ran)];
 }
 
 // g2o's OptimizationAlgorithmLevenberg defaults [g2o-recalled]
@@ -797,20 +917,77 @@ static cgmr_lm_params lm_defaults() {
   return p;
 }
 
-struct LmDev {
-  LmState* S = nullptr;
-  double *rec_chi = nullptr, *rec_lambda = nullptr, *saved = nullptr;
-  int32_t* rec_trials = nullptr;
-};
+struct LmPolicy {
+  using State = LmState;
+  static constexpr const char* kName = "Levenberg-Marquardt";
+  cgmr_lm_params P;
+  double *chi2_out, *lambda_out;
+  int32_t *trials_out, *iters_done;
+  LmDev L;
+  size_t o_chi = 0, o_lam = 0, o_tri = 0;
+  int status4[4] = {0, 0, 0, 0};
 
-// One trial, the same launches whatever happens (lm_kernels.hip): linearise + assemble + damp + factor + solve + update at x,
-// chi-only linearise at x', the verdict, then restore x or keep x'.
-static void lm_trial(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, int nV, double* d_poses, const GnEdges& Ed, const LmDev& L, bool init) {
-  gn_pass_on(ctx, D, st, d_poses, Ed, 0, false, true, false, L.S, init);
-  launch_linearize(st, D, d_poses, Ed, 1);
-  launch_lm_decide(st, D, L.S, L.rec_chi, L.rec_lambda, L.rec_trials);
-  launch_lm_commit(st, nV, d_poses, L.saved, L.S);
-}
+  // lm arena: state | chi2 records [iters + 1] | lambda records [iters] | trial records [iters] | saved poses [3 nV]
+  int reserve(cgmr_ctx* ctx, int iters, int nV, int, int, size_t* rec_bytes) {
+    BlobLayout B;
+    B.add<LmState>(1);
+    o_chi = B.add<double>((size_t)iters + 1); o_lam = B.add<double>((size_t)iters + 1); o_tri = B.add<int32_t>((size_t)iters + 1);
+    *rec_bytes = B.off;
+    const size_t o_saved = B.add<double>(3 * (size_t)std::max(nV, 1));
+    int rc = arena_reserve(ctx, ctx->lm_arena, B.off + 256);
+    if (rc) return rc;
+    char* d = ctx->lm_arena.ptr;
+    L.S = (LmState*)d; L.rec_chi = (double*)(d + o_chi); L.rec_lambda = (double*)(d + o_lam);
+    L.rec_trials = (int32_t*)(d + o_tri); L.saved = (double*)(d + o_saved);
+    return 0;
+  }
+  LmState start(int iters) const {
+    LmState hs;
+    hs.tau = P.tau; hs.initial_lambda = P.initial_lambda; hs.max_trials = P.max_trials;
+    hs.lower = P.good_step_lower; hs.upper = P.good_step_upper; hs.iters = iters;
+    return hs;
+  }
+  static void damp(hipStream_t st, const GnDevice& D, void* self) { launch_lm_damp(st, D, ((LmPolicy*)self)->L.S); }
+  static void init_and_damp(hipStream_t st, const GnDevice& D, void* self) {
+    launch_lm_init(st, D, ((LmPolicy*)self)->L.S);
+    damp(st, D, self);
+  }
+  // One trial, the same launches whatever happens (lm_kernels.hip): linearise + assemble + damp + factor + solve + update at x,
+  // chi-only linearise at x', the verdict, then restore x or keep x'.
+  void trial(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, int nV, double* d_poses, const GnEdges& Ed, bool init) {
+    GnPassOpts o;
+    o.after_assemble = init ? init_and_damp : damp;
+    o.after_assemble_arg = this;
+    gn_pass_on(ctx, D, st, d_poses, Ed, o);
+    launch_linearize(st, D, d_poses, Ed, 1);
+    launch_lm_decide(st, D, L);
+    launch_tr_commit(st, nV, d_poses, L.saved, &L.S->accept);
+  }
+  // one trial per iteration still to run; a rejected trial leaves its iteration to the next round
+  void queue_round(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, int nV, double* d_poses, const GnEdges& Ed, const LmState& hs, int iters) {
+    const int n_trials = iters - hs.iter;
+    for (int t = 0; t < n_trials; t++) trial(ctx, D, st, nV, d_poses, Ed, t == 0);   // (k_lm_init: a no-op once lambda is set)
+  }
+  GnCall::Readback also_read(const GnDevice& D) { return {status4, D.status, sizeof status4}; }
+  // with iterations asked, the first trial's step is zero, rho = 0: g2o terminates after it, lambda grown once by nu
+  void empty_system(LmState& hs, char* h, double chi0, int iters) const {
+    hs.iter = iters > 0 ? 1 : 0;
+    hs.lambda = 2 * (P.initial_lambda > 0 ? P.initial_lambda : 0.0);
+    hs.total_trials = hs.iter;
+    double* rc_chi = (double*)(h + o_chi);
+    rc_chi[0] = chi0;
+    if (hs.iter) { rc_chi[1] = chi0; ((double*)(h + o_lam))[0] = hs.lambda; ((int32_t*)(h + o_tri))[0] = 1; }
+  }
+  int finish(cgmr_ctx* ctx, const LmState& hs, const char* h, int ran, int iters, int64_t waits) const {
+    chi2_records_out(chi2_out, (const double*)(h + o_chi), ran, iters);
+    records_out(lambda_out, (const double*)(h + o_lam), ran, iters);
+    records_out(trials_out, (const int32_t*)(h + o_tri), ran, iters);
+    if (iters_done) *iters_done = ran;
+    ctx->lm_stats[0] = waits;
+    ctx->lm_stats[1] = hs.total_trials;
+    return CGMR_OK;
+  }
+};
 
 int lm_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
            const GnEdges& Ed, int iters, const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
@@ -819,124 +996,8 @@ int lm_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
   if (!(P.max_trials >= 1) || !(P.tau >= 0) || !(P.good_step_lower > 0) || !(P.good_step_upper > 0) || !std::isfinite(P.tau) ||
       !std::isfinite(P.initial_lambda) || !std::isfinite(P.good_step_lower) || !std::isfinite(P.good_step_upper))
     return set_err(ctx, CGMR_E_INVALID, "cgmr_lm_optimize: max_trials must be >= 1, tau >= 0, the step scales > 0, all finite");
-  const double t0 = wall_s();
-  Symbolic& S = ctx->sym;
-  // (the chi2 slots a trial uses: slot 0 only -- the cache entry of a Gauss-Newton call on the same edge list serves)
-  int rc = prepare_structure(ctx, nV, nE, ef, et, 1, hub_vertices, n_hub_vertices);
-  if (rc) return rc;
-  const double t1 = wall_s();
-  rc = prepare_pass(ctx, fixed, nE, ef, et, Ed.n_active, 0, 1);
-  if (rc) return rc;
-  const double t2 = wall_s();
-  GnDevice& D = ctx->gn;
-  hipStream_t st = ctx->stream;
-  // lm arena: state | chi2 records [iters + 1] | lambda records [iters] | trial records [iters] | saved poses [3 nV]
-  BlobLayout B;
-  const size_t o_state = B.add<LmState>(1), o_chi = B.add<double>((size_t)iters + 1), o_lam = B.add<double>((size_t)iters + 1),
-               o_tri = B.add<int32_t>((size_t)iters + 1);
-  const size_t rec_bytes = B.off;
-  const size_t o_saved = B.add<double>(3 * (size_t)std::max(nV, 1));
-  rc = arena_reserve(ctx, ctx->lm_arena, B.off + 256);
-  if (rc) return rc;
-  char* d = ctx->lm_arena.ptr;
-  LmDev L;
-  L.S = (LmState*)(d + o_state); L.rec_chi = (double*)(d + o_chi); L.rec_lambda = (double*)(d + o_lam);
-  L.rec_trials = (int32_t*)(d + o_tri); L.saved = (double*)(d + o_saved);
-  std::vector<char> h(rec_bytes, 0);
-  LmState hs;
-  hs.tau = P.tau; hs.initial_lambda = P.initial_lambda; hs.max_trials = P.max_trials;
-  hs.lower = P.good_step_lower; hs.upper = P.good_step_upper; hs.iters = iters;
-  memcpy(h.data() + o_state, &hs, sizeof hs);
-  HIP_TRY(ctx, hipMemcpyAsync(d, h.data(), rec_bytes, hipMemcpyHostToDevice, st));
-  if (nV > 0) HIP_TRY(ctx, hipMemcpyAsync(L.saved, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));
-  double* const poses_host = ctx->poses_out_host;
-  ctx->poses_out_host = nullptr;
-  int status4[4] = {0, 0, 0, 0};
-  int64_t waits = 0;
-  if (D.nf == 0 || iters == 0) {
-    // nothing to move (or nothing asked): chi2 at x.  With iterations asked, the first trial's step is zero, rho = 0: g2o
-    // terminates after it, lambda grown once by nu
-    gn_pass(ctx, d_poses, Ed, 0, true, false, false);
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
-    double chi0 = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&chi0, D.chi2, sizeof(double), hipMemcpyDeviceToHost, st));
-    if (poses_host && nV > 0) HIP_TRY(ctx, hipMemcpyAsync(poses_host, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    HIP_TRY(ctx, hipGetLastError());
-    waits = 1;
-    hs.iter = iters > 0 ? 1 : 0;
-    hs.lambda = 2 * (P.initial_lambda > 0 ? P.initial_lambda : 0.0);
-    hs.total_trials = hs.iter;
-    double* rc_chi = (double*)(h.data() + o_chi);
-    double* rc_lam = (double*)(h.data() + o_lam);
-    int32_t* rc_tri = (int32_t*)(h.data() + o_tri);
-    rc_chi[0] = chi0;
-    if (hs.iter) { rc_chi[1] = chi0; rc_lam[0] = hs.lambda; rc_tri[0] = 1; }
-  } else {
-    // rounds: queue one trial per iteration still to run, wait once; a rejected trial leaves its iteration to the next round
-    const int chain_was = D.bwd_chain_level;
-    const std::vector<uint8_t> merge_was = D.h_level_merge;
-    bool levelwise = false;
-    GnEdges Ei = Ed;                                         // (robust statistics: one chi-only pass on the committed poses below)
-    Ei.rk_stats = nullptr;
-    for (;;) {
-      const int n_trials = iters - hs.iter;
-      for (int t = 0; t < n_trials; t++) lm_trial(ctx, D, st, nV, d_poses, Ei, L, t == 0);   // (k_lm_init: a no-op once lambda is set)
-      HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
-      HIP_TRY(ctx, hipMemcpyAsync(h.data(), d, rec_bytes, hipMemcpyDeviceToHost, st));
-      HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
-      if (poses_host && nV > 0) HIP_TRY(ctx, hipMemcpyAsync(poses_host, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToHost, st));
-      HIP_TRY(ctx, hipStreamSynchronize(st));
-      HIP_TRY(ctx, hipGetLastError());
-      waits++;
-      memcpy(&hs, h.data() + o_state, sizeof hs);
-      if (hs.halted) {
-        // A bounded wait ran out in a trial (status[2]): not a numerical verdict.  The trial restored the poses and the later
-        // ones of the round did nothing; the call goes on from the state as it stands, one launch per kernel and level (no
-        // in-kernel waits), as gn_run does.
-        if (levelwise) {
-          D.bwd_chain_level = chain_was;
-          D.h_level_merge = merge_was;
-          return set_err(ctx, CGMR_E_TIMEOUT, "Levenberg-Marquardt: a bounded device-side wait ran out twice");
-        }
-        ctx->gn_timeouts++;
-        ctx->fwd_merge_any = false;
-        levelwise = true;
-        D.bwd_chain_level = D.nlevels;
-        D.h_level_merge.assign(D.nlevels, 0);
-        hs.halted = 0;
-        hs.accept = -1;
-        const int fresh[4] = {0, 0, 0, 0};
-        HIP_TRY(ctx, hipMemcpyAsync(D.status, fresh, sizeof fresh, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(L.S, &hs, sizeof hs, hipMemcpyHostToDevice, st));
-        continue;
-      }
-      if (hs.done) break;
-    }
-    if (Ed.rk_stats) launch_linearize(st, D, d_poses, Ed, 1);   // (read back by the caller, behind the stream)
-    D.bwd_chain_level = chain_was;
-    D.h_level_merge = merge_was;
-  }
-  const double* rc_chi = (const double*)(h.data() + o_chi);
-  const double* rc_lam = (const double*)(h.data() + o_lam);
-  const int32_t* rc_tri = (const int32_t*)(h.data() + o_tri);
-  const int ran = std::min(hs.iter, iters);
-  if (chi2_out) for (int k = 0; k <= iters; k++) chi2_out[k] = rc_chi[std::min(k, ran)];
-  if (lambda_out) for (int k = 0; k < iters; k++) lambda_out[k] = k < ran ? rc_lam[k] : 0.0;
-  if (trials_out) for (int k = 0; k < iters; k++) trials_out[k] = k < ran ? rc_tri[k] : 0;
-  if (iters_done) *iters_done = ran;
-  ctx->lm_stats[0] = waits;
-  ctx->lm_stats[1] = hs.total_trials;
-  if (ctx->profiling) profile_collect(ctx);
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-  ctx->timing[0] = S.t_order;
-  ctx->timing[1] = S.t_struct;
-  ctx->timing[2] = (t2 - t1) + S.t_upload;
-  ctx->timing[3] = 1e-3 * ms;
-  ctx->timing[4] = wall_s() - t0;
-  return CGMR_OK;
+  LmPolicy pol{P, chi2_out, lambda_out, trials_out, iters_done};
+  return tr_run(ctx, pol, nV, d_poses, fixed, nE, ef, et, Ed, iters, hub_vertices, n_hub_vertices);
 }
 
 // g2o's OptimizationAlgorithmDogleg defaults [g2o-recalled]
@@ -953,22 +1014,107 @@ static bool dl_params_valid(const cgmr_dl_params& P) {
 
 bool dl_params_ok(const cgmr_dl_params* p) { return !p || dl_params_valid(*p); }
 
-// A head (dl_kernels.hip): linearise + assemble + [damp] + factor + solve at x (no update), b^T H b, k_dl_begin.
-static void dl_head(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, const GnEdges& Ed, const DlDev& L) {
-  gn_pass_on(ctx, D, st, d_poses, Ed, 0, false, true, false, nullptr, false, L.S);
-  launch_dl_quad(st, D, D.bvec, L.qpart);
-  launch_dl_begin(st, D, L);
-}
+struct DlPolicy {
+  using State = DlState;
+  static constexpr const char* kName = "dogleg";
+  cgmr_dl_params P;
+  double *chi2_out, *delta_out;
+  int32_t *trials_out, *step_out, *iters_done;
+  DlDev L;
+  size_t o_chi = 0, o_del = 0, o_tri = 0, o_stp = 0;
+  int n_cont = 1;                                            // tails the last round gave an open iteration
 
-// A tail: the step for the current delta, h^T H h, update, chi-only linearise at x (+) h, the verdict, keep or restore x.
-static void dl_tail(GnDevice& D, hipStream_t st, int nV, double* d_poses, const GnEdges& Ed, const DlDev& L) {
-  launch_dl_step(st, D, L);
-  launch_dl_quad(st, D, D.xvec, L.qpart);
-  launch_update(st, D, d_poses);
-  launch_linearize(st, D, d_poses, Ed, 1);
-  launch_dl_decide(st, D, L);
-  launch_dl_commit(st, nV, d_poses, L);
-}
+  // dl arena: state | chi2 [iters + 1] | delta, trials, steps [iters] | saved poses [3 nV] | hgn, hsd [3 nf] | quad partials
+  int reserve(cgmr_ctx* ctx, int iters, int nV, int nf, int nE, size_t* rec_bytes) {
+    BlobLayout B;
+    B.add<DlState>(1);
+    o_chi = B.add<double>((size_t)iters + 1); o_del = B.add<double>((size_t)iters + 1);
+    o_tri = B.add<int32_t>((size_t)iters + 1); o_stp = B.add<int32_t>((size_t)iters + 1);
+    *rec_bytes = B.off;
+    const size_t nf3 = 3 * (size_t)std::max(nf, 1);
+    const size_t o_saved = B.add<double>(3 * (size_t)std::max(nV, 1)), o_hgn = B.add<double>(nf3), o_hsd = B.add<double>(nf3),
+                 o_q = B.add<double>((size_t)std::max((nE + 255) / 256, 1));
+    int rc = arena_reserve(ctx, ctx->dl_arena, B.off + 256);
+    if (rc) return rc;
+    char* d = ctx->dl_arena.ptr;
+    L.S = (DlState*)d; L.rec_chi = (double*)(d + o_chi); L.rec_delta = (double*)(d + o_del);
+    L.rec_trials = (int32_t*)(d + o_tri); L.rec_step = (int32_t*)(d + o_stp); L.saved = (double*)(d + o_saved);
+    L.hgn = (double*)(d + o_hgn); L.hsd = (double*)(d + o_hsd); L.qpart = (double*)(d + o_q);
+    return 0;
+  }
+  DlState start(int iters) const {
+    DlState hs;
+    hs.delta = P.initial_delta; hs.lambda = P.initial_lambda; hs.lambda_factor = P.lambda_factor; hs.max_trials = P.max_trials;
+    hs.iters = iters;
+    return hs;
+  }
+  static void damp(hipStream_t st, const GnDevice& D, void* self) { launch_dl_damp(st, D, ((DlPolicy*)self)->L.S); }
+  // A head (dl_kernels.hip): linearise + assemble + [damp] + factor + solve at x (the step is left to the tails), b^T H b,
+  // k_dl_begin.
+  void head(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, const GnEdges& Ed) {
+    GnPassOpts o;
+    o.update_poses = false;
+    o.after_assemble = damp;
+    o.after_assemble_arg = this;
+    gn_pass_on(ctx, D, st, d_poses, Ed, o);
+    launch_dl_quad(st, D, D.bvec, L.qpart);
+    launch_dl_begin(st, D, L);
+  }
+  // A tail: the step for the current delta, h^T H h, update, chi-only linearise at x (+) h, the verdict, keep or restore x.
+  void tail(GnDevice& D, hipStream_t st, int nV, double* d_poses, const GnEdges& Ed) {
+    launch_dl_step(st, D, L);
+    launch_dl_quad(st, D, D.xvec, L.qpart);
+    launch_update(st, D, d_poses);
+    launch_linearize(st, D, d_poses, Ed, 1);
+    launch_dl_decide(st, D, L);
+    launch_tr_commit(st, nV, d_poses, L.saved, &L.S->accept);
+  }
+  // an open iteration (its GN step solved, no good step yet) gets tails only, doubling in number from round to round; every
+  // iteration not started yet gets a head and a tail
+  void queue_round(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, int nV, double* d_poses, const GnEdges& Ed, const DlState& hs, int iters) {
+    const bool open = hs.solved != 0;
+    if (open) {
+      n_cont = std::min(2 * n_cont, P.max_trials - hs.trial);
+      for (int t = 0; t < n_cont; t++) tail(D, st, nV, d_poses, Ed);
+    }
+    const int n_new = iters - hs.iter - (open ? 1 : 0);
+    for (int t = 0; t < n_new; t++) {
+      head(ctx, D, st, d_poses, Ed);
+      tail(D, st, nV, d_poses, Ed);
+    }
+  }
+  GnCall::Readback also_read(const GnDevice&) { return {nullptr, nullptr, 0}; }
+  // with iterations asked, g2o's empty system gives h = 0 and rho = 0 on every trial: one iteration of max_trials GN trials,
+  // delta halved on each, Terminate
+  void empty_system(DlState& hs, char* h, double chi0, int iters) const {
+    double* rc_chi = (double*)(h + o_chi);
+    rc_chi[0] = chi0;
+    if (iters == 0) return;
+    for (int q = 0; q < P.max_trials; q++) hs.delta *= 0.5;
+    hs.iter = 1;
+    hs.total_trials = P.max_trials;
+    hs.terminated = 1;
+    rc_chi[1] = chi0;
+    ((double*)(h + o_del))[0] = hs.delta;
+    ((int32_t*)(h + o_tri))[0] = P.max_trials;
+    ((int32_t*)(h + o_stp))[0] = CGMR_DL_STEP_GN;
+  }
+  int finish(cgmr_ctx* ctx, const DlState& hs, const char* h, int ran, int iters, int64_t waits) const {
+    chi2_records_out(chi2_out, (const double*)(h + o_chi), ran, iters);
+    records_out(delta_out, (const double*)(h + o_del), ran, iters);
+    records_out(trials_out, (const int32_t*)(h + o_tri), ran, iters);
+    records_out(step_out, (const int32_t*)(h + o_stp), ran, iters);
+    if (iters_done) *iters_done = ran;
+    ctx->dl_stats[0] = waits;
+    ctx->dl_stats[1] = hs.total_trials;
+    ctx->dl_stats[2] = hs.factorisations;
+    if (hs.failed)
+      return set_err(ctx, CGMR_E_CHOLESKY_BASE - ran,
+                     "dogleg: H + currentLambda I not positive definite with currentLambda at 1e3 in iteration %d (g2o's Fail); "
+                     "poses left at the last accepted step", ran);
+    return CGMR_OK;
+  }
+};
 
 int dl_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
            const GnEdges& Ed, int iters, const cgmr_dl_params* params, double* chi2_out, double* delta_out, int32_t* trials_out,
@@ -977,146 +1123,8 @@ int dl_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
   if (!dl_params_valid(P))
     return set_err(ctx, CGMR_E_INVALID,
                    "cgmr_dl_optimize: max_trials must be >= 1, initial_delta / initial_lambda > 0, lambda_factor > 1, all finite");
-  const double t0 = wall_s();
-  Symbolic& S = ctx->sym;
-  // (the chi2 slots a head uses: slot 0 only -- the cache entry of a Gauss-Newton call on the same edge list serves)
-  int rc = prepare_structure(ctx, nV, nE, ef, et, 1, hub_vertices, n_hub_vertices);
-  if (rc) return rc;
-  const double t1 = wall_s();
-  rc = prepare_pass(ctx, fixed, nE, ef, et, Ed.n_active, 0, 1);
-  if (rc) return rc;
-  const double t2 = wall_s();
-  GnDevice& D = ctx->gn;
-  hipStream_t st = ctx->stream;
-  // dl arena: state | chi2 [iters + 1] | delta, trials, steps [iters] | saved poses [3 nV] | hgn, hsd [3 nf] | quad partials
-  BlobLayout B;
-  const size_t o_state = B.add<DlState>(1), o_chi = B.add<double>((size_t)iters + 1), o_del = B.add<double>((size_t)iters + 1),
-               o_tri = B.add<int32_t>((size_t)iters + 1), o_stp = B.add<int32_t>((size_t)iters + 1);
-  const size_t rec_bytes = B.off;
-  const size_t nf3 = 3 * (size_t)std::max(D.nf, 1);
-  const size_t o_saved = B.add<double>(3 * (size_t)std::max(nV, 1)), o_hgn = B.add<double>(nf3), o_hsd = B.add<double>(nf3),
-               o_q = B.add<double>((size_t)std::max((nE + 255) / 256, 1));
-  rc = arena_reserve(ctx, ctx->dl_arena, B.off + 256);
-  if (rc) return rc;
-  char* d = ctx->dl_arena.ptr;
-  DlDev L;
-  L.S = (DlState*)(d + o_state); L.rec_chi = (double*)(d + o_chi); L.rec_delta = (double*)(d + o_del);
-  L.rec_trials = (int32_t*)(d + o_tri); L.rec_step = (int32_t*)(d + o_stp); L.saved = (double*)(d + o_saved);
-  L.hgn = (double*)(d + o_hgn); L.hsd = (double*)(d + o_hsd); L.qpart = (double*)(d + o_q);
-  std::vector<char> h(rec_bytes, 0);
-  DlState hs;
-  hs.delta = P.initial_delta; hs.lambda = P.initial_lambda; hs.lambda_factor = P.lambda_factor; hs.max_trials = P.max_trials;
-  hs.iters = iters;
-  memcpy(h.data() + o_state, &hs, sizeof hs);
-  HIP_TRY(ctx, hipMemcpyAsync(d, h.data(), rec_bytes, hipMemcpyHostToDevice, st));
-  if (nV > 0) HIP_TRY(ctx, hipMemcpyAsync(L.saved, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));
-  double* const poses_host = ctx->poses_out_host;
-  ctx->poses_out_host = nullptr;
-  int64_t waits = 0;
-  if (D.nf == 0 || iters == 0) {
-    // nothing to move (or nothing asked): chi2 at x.  With iterations asked, g2o's empty system gives h = 0 and rho = 0
-    // on every trial: one iteration of max_trials GN trials, delta halved on each, Terminate
-    gn_pass(ctx, d_poses, Ed, 0, true, false, false);
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
-    double chi0 = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&chi0, D.chi2, sizeof(double), hipMemcpyDeviceToHost, st));
-    if (poses_host && nV > 0) HIP_TRY(ctx, hipMemcpyAsync(poses_host, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    HIP_TRY(ctx, hipGetLastError());
-    waits = 1;
-    double* rc_chi = (double*)(h.data() + o_chi);
-    rc_chi[0] = chi0;
-    if (iters > 0) {
-      for (int q = 0; q < P.max_trials; q++) hs.delta *= 0.5;
-      hs.iter = 1;
-      hs.total_trials = P.max_trials;
-      hs.terminated = 1;
-      rc_chi[1] = chi0;
-      ((double*)(h.data() + o_del))[0] = hs.delta;
-      ((int32_t*)(h.data() + o_tri))[0] = P.max_trials;
-      ((int32_t*)(h.data() + o_stp))[0] = CGMR_DL_STEP_GN;
-    }
-  } else {
-    // rounds: an open iteration (its GN step solved, no good step yet) gets tails only, doubling in number from round to
-    // round; every iteration not started yet gets a head and a tail.  One wait per round.
-    const int chain_was = D.bwd_chain_level;
-    const std::vector<uint8_t> merge_was = D.h_level_merge;
-    bool levelwise = false;
-    GnEdges Ei = Ed;                                         // (robust statistics: one chi-only pass on the final poses below)
-    Ei.rk_stats = nullptr;
-    int n_cont = 1;
-    for (;;) {
-      const bool open = hs.solved != 0;
-      if (open) {
-        n_cont = std::min(2 * n_cont, P.max_trials - hs.trial);
-        for (int t = 0; t < n_cont; t++) dl_tail(D, st, nV, d_poses, Ei, L);
-      }
-      const int n_new = iters - hs.iter - (open ? 1 : 0);
-      for (int t = 0; t < n_new; t++) {
-        dl_head(ctx, D, st, d_poses, Ei, L);
-        dl_tail(D, st, nV, d_poses, Ei, L);
-      }
-      HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
-      HIP_TRY(ctx, hipMemcpyAsync(h.data(), d, rec_bytes, hipMemcpyDeviceToHost, st));
-      if (poses_host && nV > 0) HIP_TRY(ctx, hipMemcpyAsync(poses_host, d_poses, 24 * (size_t)nV, hipMemcpyDeviceToHost, st));
-      HIP_TRY(ctx, hipStreamSynchronize(st));
-      HIP_TRY(ctx, hipGetLastError());
-      waits++;
-      memcpy(&hs, h.data() + o_state, sizeof hs);
-      if (hs.halted) {
-        // A bounded wait ran out in a head (status[2]): not a numerical verdict.  The poses are those the iteration started
-        // from and nothing after the head changed anything; the call goes on from the state as it stands, one launch per
-        // kernel and level (no in-kernel waits), as lm_run does.
-        if (levelwise) {
-          D.bwd_chain_level = chain_was;
-          D.h_level_merge = merge_was;
-          return set_err(ctx, CGMR_E_TIMEOUT, "dogleg: a bounded device-side wait ran out twice");
-        }
-        ctx->gn_timeouts++;
-        ctx->fwd_merge_any = false;
-        levelwise = true;
-        D.bwd_chain_level = D.nlevels;
-        D.h_level_merge.assign(D.nlevels, 0);
-        hs.halted = 0;
-        hs.accept = -1;
-        const int fresh[4] = {0, 0, 0, 0};
-        HIP_TRY(ctx, hipMemcpyAsync(D.status, fresh, sizeof fresh, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(L.S, &hs, sizeof hs, hipMemcpyHostToDevice, st));
-        continue;
-      }
-      if (hs.done) break;
-    }
-    if (Ed.rk_stats) launch_linearize(st, D, d_poses, Ed, 1);   // (read back by the caller, behind the stream)
-    D.bwd_chain_level = chain_was;
-    D.h_level_merge = merge_was;
-  }
-  const double* rc_chi = (const double*)(h.data() + o_chi);
-  const double* rc_del = (const double*)(h.data() + o_del);
-  const int32_t* rc_tri = (const int32_t*)(h.data() + o_tri);
-  const int32_t* rc_stp = (const int32_t*)(h.data() + o_stp);
-  const int ran = std::min(hs.iter, iters);
-  if (chi2_out) for (int k = 0; k <= iters; k++) chi2_out[k] = rc_chi[std::min(k, ran)];
-  if (delta_out) for (int k = 0; k < iters; k++) delta_out[k] = k < ran ? rc_del[k] : 0.0;
-  if (trials_out) for (int k = 0; k < iters; k++) trials_out[k] = k < ran ? rc_tri[k] : 0;
-  if (step_out) for (int k = 0; k < iters; k++) step_out[k] = k < ran ? rc_stp[k] : 0;
-  if (iters_done) *iters_done = ran;
-  ctx->dl_stats[0] = waits;
-  ctx->dl_stats[1] = hs.total_trials;
-  ctx->dl_stats[2] = hs.factorisations;
-  if (ctx->profiling) profile_collect(ctx);
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-  ctx->timing[0] = S.t_order;
-  ctx->timing[1] = S.t_struct;
-  ctx->timing[2] = (t2 - t1) + S.t_upload;
-  ctx->timing[3] = 1e-3 * ms;
-  ctx->timing[4] = wall_s() - t0;
-  if (hs.failed)
-    return set_err(ctx, CGMR_E_CHOLESKY_BASE - ran,
-                   "dogleg: H + currentLambda I not positive definite with currentLambda at 1e3 in iteration %d (g2o's Fail); "
-                   "poses left at the last accepted step", ran);
-  return CGMR_OK;
+  DlPolicy pol{P, chi2_out, delta_out, trials_out, step_out, iters_done};
+  return tr_run(ctx, pol, nV, d_poses, fixed, nE, ef, et, Ed, iters, hub_vertices, n_hub_vertices);
 }
 
 // SparseOptimizer::computeInitialGuess with unit edge cost [g2o-recalled]: breadth-first from the fixed
@@ -1226,19 +1234,12 @@ int marginal_pass(cgmr_ctx* ctx, double* dp, const double* work, int nV, int* st
     // does, the pass is repeated from the same poses with one launch per kernel and level (no in-kernel waits).  The cached
     // structure keeps only the forward merges that are certainly resident from now on; the chained backward solve (mode 2)
     // stays, as in gn_run: its waits are bounded as well, and a later time-out there falls back the same way.
-    ctx->gn_timeouts++;
-    ctx->fwd_merge_any = false;
     choose_fwd_merge(D, ctx->side_used ? 2 : 1, false, false);
-    const std::vector<uint8_t> merge_keep = D.h_level_merge;
-    const int chain_was = D.bwd_chain_level;
-    D.h_level_merge.assign(D.nlevels, 0);
-    D.bwd_chain_level = D.nlevels;
-    const int fresh[4] = {0, 0, 0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(D.status, fresh, sizeof fresh, hipMemcpyHostToDevice, st));
+    LevelwiseScope levelwise(ctx, D);                             // (ends with those merges and the chained solve back)
+    rc = levelwise.arm(st);
+    if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(dp, work, 24 * (size_t)nV, hipMemcpyHostToDevice, st));
     rc = run_pass();
-    D.h_level_merge = merge_keep;
-    D.bwd_chain_level = chain_was;
     if (rc) return rc;
     if (status4[2] != 0)
       return set_err(ctx, CGMR_E_TIMEOUT, "marginals: a bounded device-side wait (forward hand-off or chained backward solve) ran out twice");
@@ -1309,8 +1310,11 @@ int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const 
   Ed.meas_a = (const double*)(d + o_m); Ed.info_a = (const double*)(d + o_i); Ed.nA = nE; Ed.n_active = nE;
   int status4[4] = {0, 0, 0, 0};
   std::vector<double> cov(9 * (size_t)nq);
+  GnPassOpts pass;
+  pass.write_l11c = true;
+  pass.solve = pass.update_poses = mode == 2;
   auto run_pass = [&]() -> int {
-    gn_pass(ctx, dp, Ed, 0, false, mode == 2, /*write_l11c=*/true);
+    gn_pass(ctx, dp, Ed, pass);
     launch_marginals(st, D, nq, (const int32_t*)(d + o_qc), m, (double*)(d + o_Y), (double*)(d + o_U), (double*)(d + o_part),
                      (double*)(d + o_G), (double*)(d + o_cov), chunk, nchunk, (uint8_t*)(d + o_live));
     if (mode == 2)
@@ -1408,8 +1412,11 @@ int marginals_all_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8
   double* dp = (double*)(d + o_p);
   Ed.meas_a = (const double*)(d + o_m); Ed.info_a = (const double*)(d + o_i); Ed.nA = nE; Ed.n_active = nE;
   int status4[4] = {0, 0, 0, 0};
+  GnPassOpts pass;
+  pass.write_l11c = true;
+  pass.solve = false;
   auto run_pass = [&]() -> int {
-    gn_pass(ctx, dp, Ed, 0, false, false, /*write_l11c=*/true);
+    gn_pass(ctx, dp, Ed, pass);
     launch_invert_fronts(st, D, /*top_too=*/true);                     // Z = L11^-1 of every front, the top block's included
     launch_selinv(st, D, P, nV, nE, (const int32_t*)(d + o_vc), (const int32_t*)(d + o_cf), (double*)(d + o_cov),
                   cross_out ? (double*)(d + o_cr) : nullptr);
@@ -1432,6 +1439,90 @@ int marginals_all_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8
   return CGMR_OK;
 }
 
+// The arguments every *_optimize* entry point takes, checked alike; `name`: the entry point family in the error text
+static int optimize_args_check(cgmr_ctx* ctx, const char* name, int nV, const double* poses, const uint8_t* fixed, int nE,
+                               const int32_t* from_idx, const int32_t* to_idx, const double* meas, const double* info, int iters) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (nV < 0 || nE < 0 || iters < 0 || (nV > 0 && (!poses || !fixed)) || (nE > 0 && (!from_idx || !to_idx || !meas || !info)))
+    return set_err(ctx, CGMR_E_INVALID, "%s: null or negative argument", name);
+  return 0;
+}
+
+// Around run(d_poses, Ed) -- gn_run, lm_run or dl_run on device arrays --: the robust description, and unless `dev` (poses,
+// meas and info are the device's already) the host arrays staged through io_arena and the poses read back.  The poses and
+// the robust statistics are returned when the call ended well, and with cholesky_too also on a Cholesky status.
+template <typename Run>
+static int optimize_staged(cgmr_ctx* ctx, const char* who, bool dev, bool cholesky_too, int nV, double* poses, int nE,
+                           const double* meas, const double* info, const cgmr_robust* rk, Run&& run) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  GnEdges Ed;
+  int rc = robust_setup(ctx, rk, nE, dev, Ed, who);
+  if (rc) return rc;
+  double* d_poses = poses;
+  const size_t bp = sizeof(double) * 3 * (size_t)nV;
+  if (dev) {
+    Ed.meas_a = meas; Ed.info_a = info;
+  } else {
+    const size_t bm = sizeof(double) * 3 * (size_t)nE, bi = sizeof(double) * 6 * (size_t)nE;
+    const size_t om = (bp + 255) & ~size_t(255), oi = (om + bm + 255) & ~size_t(255);
+    rc = arena_reserve(ctx, ctx->io_arena, oi + bi + 256);
+    if (rc) return rc;
+    char* d = ctx->io_arena.ptr;
+    HIP_TRY(ctx, hipMemcpyAsync(d, poses, bp, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d + om, meas, bm, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d + oi, info, bi, hipMemcpyHostToDevice, ctx->stream));
+    Ed.meas_a = (const double*)(d + om); Ed.info_a = (const double*)(d + oi);
+    d_poses = (double*)d;
+  }
+  Ed.nA = nE; Ed.n_active = nE;
+  rc = run(d_poses, Ed);
+  if (rc == CGMR_OK || (cholesky_too && rc <= CGMR_E_CHOLESKY_BASE)) {
+    if (!dev) {
+      hipError_t e = hipMemcpyAsync(poses, d_poses, bp, hipMemcpyDeviceToHost, ctx->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+      if (e != hipSuccess) return set_err(ctx, CGMR_E_HIP, "pose read-back: %s", hipGetErrorString(e));
+    }
+    const int rs = robust_stats_out(ctx, rk, nE, Ed);
+    if (rs) return rs;
+  }
+  return rc;
+}
+
+static int gn_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                            const int32_t* to_idx, const double* meas, const double* info, int iters, double* chi2_out,
+                            const cgmr_robust* rk, bool dev) {
+  const int rc = optimize_args_check(ctx, "cgmr_gn_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
+  if (rc) return rc;
+  return optimize_staged(ctx, dev ? "cgmr_gn_optimize_robust_dev" : "cgmr_gn_optimize_robust", dev, true, nV, poses, nE, meas, info, rk,
+                         [&](double* d_poses, const GnEdges& Ed) { return gn_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, chi2_out); });
+}
+
+static int lm_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                            const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_lm_params* params,
+                            double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done, const cgmr_robust* rk,
+                            bool dev) {
+  const int rc = optimize_args_check(ctx, "cgmr_lm_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
+  if (rc) return rc;
+  return optimize_staged(ctx, dev ? "cgmr_lm_optimize_robust_dev" : "cgmr_lm_optimize_robust", dev, false, nV, poses, nE, meas, info, rk,
+                         [&](double* d_poses, const GnEdges& Ed) {
+                           return lm_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, lambda_out, trials_out, iters_done);
+                         });
+}
+
+static int dl_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                            const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_dl_params* params,
+                            double* chi2_out, double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
+                            const cgmr_robust* rk, bool dev) {
+  const int rc = optimize_args_check(ctx, "cgmr_dl_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
+  if (rc) return rc;
+  if (!dl_params_ok(params))
+    return set_err(ctx, CGMR_E_INVALID,
+                   "cgmr_dl_optimize: max_trials must be >= 1, initial_delta / initial_lambda > 0, lambda_factor > 1, all finite");
+  return optimize_staged(ctx, dev ? "cgmr_dl_optimize_dev" : "cgmr_dl_optimize", dev, true, nV, poses, nE, meas, info, rk,
+                         [&](double* d_poses, const GnEdges& Ed) {
+                           return dl_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, delta_out, trials_out, step_out, iters_done);
+                         });
+}
 
 }  // namespace cgmr
 
@@ -1514,155 +1605,56 @@ int cgmr_ctx_synchronize(cgmr_ctx* ctx) {
   return CGMR_OK;
 }
 
-static int gn_optimize_dev_impl(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
-                                const int32_t* to_idx, const double* d_meas, const double* d_info, int iters, double* chi2_out,
-                                const cgmr_robust* rk) {
-  if (!ctx) return CGMR_E_INVALID;
-  if (nV < 0 || nE < 0 || iters < 0 || (nV > 0 && (!d_poses || !fixed)) ||
-      (nE > 0 && (!from_idx || !to_idx || !d_meas || !d_info)))
-    return set_err(ctx, CGMR_E_INVALID, "cgmr_gn_optimize: null or negative argument");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  GnEdges Ed;
-  Ed.meas_a = d_meas; Ed.info_a = d_info; Ed.nA = nE; Ed.n_active = nE;
-  int rc = robust_setup(ctx, rk, nE, true, Ed, "cgmr_gn_optimize_robust_dev");
-  if (rc) return rc;
-  rc = gn_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, chi2_out);
-  if (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE) {
-    const int rs = robust_stats_out(ctx, rk, nE, Ed);
-    if (rs) return rs;
-  }
-  return rc;
-}
-
-static int gn_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
-                            const int32_t* to_idx, const double* meas, const double* info, int iters, double* chi2_out,
-                            const cgmr_robust* rk) {
-  if (!ctx) return CGMR_E_INVALID;
-  if (nV < 0 || nE < 0 || iters < 0 || (nV > 0 && (!poses || !fixed)) ||
-      (nE > 0 && (!from_idx || !to_idx || !meas || !info)))
-    return set_err(ctx, CGMR_E_INVALID, "cgmr_gn_optimize: null or negative argument");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  GnEdges Ed;
-  int rc = robust_setup(ctx, rk, nE, false, Ed, "cgmr_gn_optimize_robust");
-  if (rc) return rc;
-  size_t bp = sizeof(double) * 3 * (size_t)nV, bm = sizeof(double) * 3 * (size_t)nE, bi = sizeof(double) * 6 * (size_t)nE;
-  size_t op = 0, om = (bp + 255) & ~size_t(255), oi = (om + bm + 255) & ~size_t(255);
-  rc = arena_reserve(ctx, ctx->io_arena, oi + bi + 256);
-  if (rc) return rc;
-  char* d = ctx->io_arena.ptr;
-  HIP_TRY(ctx, hipMemcpyAsync(d + op, poses, bp, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d + om, meas, bm, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d + oi, info, bi, hipMemcpyHostToDevice, ctx->stream));
-  Ed.meas_a = (const double*)(d + om); Ed.info_a = (const double*)(d + oi); Ed.nA = nE; Ed.n_active = nE;
-  rc = gn_run(ctx, nV, (double*)(d + op), fixed, nE, from_idx, to_idx, Ed, iters, chi2_out);
-  if (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE) {
-    hipError_t e = hipMemcpyAsync(poses, d + op, bp, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return set_err(ctx, CGMR_E_HIP, "pose read-back: %s", hipGetErrorString(e));
-    const int rs = robust_stats_out(ctx, rk, nE, Ed);
-    if (rs) return rs;
-  }
-  return rc;
-}
-
-static int lm_optimize_dev_impl(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
-                                const int32_t* to_idx, const double* d_meas, const double* d_info, int iters,
-                                const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
-                                int32_t* iters_done, const cgmr_robust* rk) {
-  if (!ctx) return CGMR_E_INVALID;
-  if (nV < 0 || nE < 0 || iters < 0 || (nV > 0 && (!d_poses || !fixed)) ||
-      (nE > 0 && (!from_idx || !to_idx || !d_meas || !d_info)))
-    return set_err(ctx, CGMR_E_INVALID, "cgmr_lm_optimize: null or negative argument");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  GnEdges Ed;
-  Ed.meas_a = d_meas; Ed.info_a = d_info; Ed.nA = nE; Ed.n_active = nE;
-  int rc = robust_setup(ctx, rk, nE, true, Ed, "cgmr_lm_optimize_robust_dev");
-  if (rc) return rc;
-  rc = lm_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, lambda_out, trials_out, iters_done);
-  if (rc == CGMR_OK) rc = robust_stats_out(ctx, rk, nE, Ed);
-  return rc;
-}
-
-static int lm_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
-                            const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_lm_params* params,
-                            double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done, const cgmr_robust* rk) {
-  if (!ctx) return CGMR_E_INVALID;
-  if (nV < 0 || nE < 0 || iters < 0 || (nV > 0 && (!poses || !fixed)) ||
-      (nE > 0 && (!from_idx || !to_idx || !meas || !info)))
-    return set_err(ctx, CGMR_E_INVALID, "cgmr_lm_optimize: null or negative argument");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  GnEdges Ed;
-  int rc = robust_setup(ctx, rk, nE, false, Ed, "cgmr_lm_optimize_robust");
-  if (rc) return rc;
-  size_t bp = sizeof(double) * 3 * (size_t)nV, bm = sizeof(double) * 3 * (size_t)nE, bi = sizeof(double) * 6 * (size_t)nE;
-  size_t op = 0, om = (bp + 255) & ~size_t(255), oi = (om + bm + 255) & ~size_t(255);
-  rc = arena_reserve(ctx, ctx->io_arena, oi + bi + 256);
-  if (rc) return rc;
-  char* d = ctx->io_arena.ptr;
-  HIP_TRY(ctx, hipMemcpyAsync(d + op, poses, bp, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d + om, meas, bm, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d + oi, info, bi, hipMemcpyHostToDevice, ctx->stream));
-  Ed.meas_a = (const double*)(d + om); Ed.info_a = (const double*)(d + oi); Ed.nA = nE; Ed.n_active = nE;
-  rc = lm_run(ctx, nV, (double*)(d + op), fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, lambda_out, trials_out, iters_done);
-  if (rc == CGMR_OK) {
-    hipError_t e = hipMemcpyAsync(poses, d + op, bp, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return set_err(ctx, CGMR_E_HIP, "pose read-back: %s", hipGetErrorString(e));
-    rc = robust_stats_out(ctx, rk, nE, Ed);
-  }
-  return rc;
-}
-
 int cgmr_gn_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
                          const int32_t* from_idx, const int32_t* to_idx, const double* d_meas,
                          const double* d_info, int iters, double* chi2_out) {
-  return gn_optimize_dev_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, chi2_out, nullptr);
+  return gn_optimize_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, chi2_out, nullptr, true);
 }
 
 int cgmr_gn_optimize(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                      const int32_t* to_idx, const double* meas, const double* info, int iters, double* chi2_out) {
-  return gn_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, chi2_out, nullptr);
+  return gn_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, chi2_out, nullptr, false);
 }
 
 int cgmr_lm_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                          const int32_t* to_idx, const double* d_meas, const double* d_info, int iters, const cgmr_lm_params* params,
                          double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done) {
-  return lm_optimize_dev_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, params, chi2_out, lambda_out,
-                              trials_out, iters_done, nullptr);
+  return lm_optimize_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, params, chi2_out, lambda_out,
+                          trials_out, iters_done, nullptr, true);
 }
 
 int cgmr_lm_optimize(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                      const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_lm_params* params,
                      double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done) {
   return lm_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, params, chi2_out, lambda_out, trials_out,
-                          iters_done, nullptr);
+                          iters_done, nullptr, false);
 }
 
 int cgmr_gn_optimize_robust(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                             const int32_t* to_idx, const double* meas, const double* info, int iters, double* chi2_out,
                             const cgmr_robust* rk) {
-  return gn_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, chi2_out, rk);
+  return gn_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, chi2_out, rk, false);
 }
 
 int cgmr_gn_optimize_robust_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                                 const int32_t* to_idx, const double* d_meas, const double* d_info, int iters, double* chi2_out,
                                 const cgmr_robust* rk) {
-  return gn_optimize_dev_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, chi2_out, rk);
+  return gn_optimize_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, chi2_out, rk, true);
 }
 
 int cgmr_lm_optimize_robust(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                             const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_lm_params* params,
                             double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done, const cgmr_robust* rk) {
   return lm_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, params, chi2_out, lambda_out, trials_out,
-                          iters_done, rk);
+                          iters_done, rk, false);
 }
 
 int cgmr_lm_optimize_robust_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                                 const int32_t* to_idx, const double* d_meas, const double* d_info, int iters,
                                 const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
                                 int32_t* iters_done, const cgmr_robust* rk) {
-  return lm_optimize_dev_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, params, chi2_out, lambda_out,
-                              trials_out, iters_done, rk);
+  return lm_optimize_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, params, chi2_out, lambda_out,
+                          trials_out, iters_done, rk, true);
 }
 
 int cgmr_lm_last_stats(const cgmr_ctx* ctx, int64_t out[2]) {
@@ -1670,52 +1662,6 @@ int cgmr_lm_last_stats(const cgmr_ctx* ctx, int64_t out[2]) {
   out[0] = ctx->lm_stats[0];
   out[1] = ctx->lm_stats[1];
   return CGMR_OK;
-}
-
-static int dl_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
-                            const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_dl_params* params,
-                            double* chi2_out, double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
-                            const cgmr_robust* rk, bool dev) {
-  if (!ctx) return CGMR_E_INVALID;
-  if (nV < 0 || nE < 0 || iters < 0 || (nV > 0 && (!poses || !fixed)) ||
-      (nE > 0 && (!from_idx || !to_idx || !meas || !info)))
-    return set_err(ctx, CGMR_E_INVALID, "cgmr_dl_optimize: null or negative argument");
-  if (!dl_params_ok(params))
-    return set_err(ctx, CGMR_E_INVALID,
-                   "cgmr_dl_optimize: max_trials must be >= 1, initial_delta / initial_lambda > 0, lambda_factor > 1, all finite");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  GnEdges Ed;
-  int rc = robust_setup(ctx, rk, nE, dev, Ed, dev ? "cgmr_dl_optimize_dev" : "cgmr_dl_optimize");
-  if (rc) return rc;
-  double* d_poses = poses;
-  const size_t bp = sizeof(double) * 3 * (size_t)nV;
-  char* d = nullptr;
-  if (dev) {
-    Ed.meas_a = meas; Ed.info_a = info;
-  } else {
-    size_t bm = sizeof(double) * 3 * (size_t)nE, bi = sizeof(double) * 6 * (size_t)nE;
-    size_t om = (bp + 255) & ~size_t(255), oi = (om + bm + 255) & ~size_t(255);
-    rc = arena_reserve(ctx, ctx->io_arena, oi + bi + 256);
-    if (rc) return rc;
-    d = ctx->io_arena.ptr;
-    HIP_TRY(ctx, hipMemcpyAsync(d, poses, bp, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d + om, meas, bm, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d + oi, info, bi, hipMemcpyHostToDevice, ctx->stream));
-    Ed.meas_a = (const double*)(d + om); Ed.info_a = (const double*)(d + oi);
-    d_poses = (double*)d;
-  }
-  Ed.nA = nE; Ed.n_active = nE;
-  rc = dl_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, delta_out, trials_out, step_out, iters_done);
-  if (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE) {
-    if (!dev) {
-      hipError_t e = hipMemcpyAsync(poses, d, bp, hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      if (e != hipSuccess) return set_err(ctx, CGMR_E_HIP, "pose read-back: %s", hipGetErrorString(e));
-    }
-    const int rs = robust_stats_out(ctx, rk, nE, Ed);
-    if (rs) return rs;
-  }
-  return rc;
 }
 
 int cgmr_dl_optimize(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,

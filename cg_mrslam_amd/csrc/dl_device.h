@@ -8,7 +8,7 @@
 
 namespace cgmr {
 
-// One per call, in device memory, set up by the host before the first head (dl_run) and read back once per round.
+// One per call, in device memory, set up by the host before the first head (cgmr_api.cpp: tr_run) and read back once per round.
 struct DlState {
   double delta = 1e4;                        // trust-region radius
   double lambda = 1e-7;                      // currentLambda: the damping once H has not been positive definite
@@ -27,7 +27,7 @@ struct DlState {
   int32_t failed = 0;                        // 1: g2o's Fail (currentLambda above 1e3 with H + lambda I still not PD)
   int32_t halted = 0;                        // 1: a bounded wait ran out in a head: the host repeats it
   int32_t step = 0;                          // CGMR_DL_STEP_* of the current trial
-  int32_t accept = -1;                       // verdict of the last tail for k_dl_commit: 1 keep, 0 restore, -1 nothing
+  int32_t accept = -1;                       // verdict of the last tail for k_tr_commit: 1 keep, 0 restore, -1 nothing
   int32_t total_trials = 0;                  // trials decided in this call
   int32_t factorisations = 0;                // heads that served an iteration (a failed damped factorisation included)
 };
@@ -50,7 +50,5 @@ void launch_dl_begin(hipStream_t st, const GnDevice& D, const DlDev& L);
 void launch_dl_step(hipStream_t st, const GnDevice& D, const DlDev& L);
 // per tail: rho, the verdict, delta, termination, the records
 void launch_dl_decide(hipStream_t st, const GnDevice& D, const DlDev& L);
-// n = nV poses: accepted -> saved = poses; rejected -> poses = saved
-void launch_dl_commit(hipStream_t st, int nV, double* poses, const DlDev& L);
 
 }  // namespace cgmr

@@ -5,16 +5,16 @@
 //   multiplyHessian (b^T H b, h^T H h)                    -> k_dl_quad, from the edges' term records
 //   alpha, hsd, the damping loop's bookkeeping            -> k_dl_begin
 //   the GN / SD / DL choice                               -> k_dl_step
-//   rho, the trust region, push / pop                     -> k_dl_decide, k_dl_commit
+//   rho, the trust region, push / pop                     -> k_dl_decide, k_tr_commit (tr_kernels.hip)
 //
-// An iteration is a head and one or more tails (cgmr_api.cpp: dl_run).  Head: linearise, assemble, [damp,] factor, solve
+// An iteration is a head and one or more tails (cgmr_api.cpp: DlPolicy).  Head: linearise, assemble, [damp,] factor, solve
 // (no pose update), k_dl_quad(b), k_dl_begin.  Tail: k_dl_step, k_dl_quad(h), update, chi-only linearise, k_dl_decide,
-// k_dl_commit.  A rejected trial changes delta only, so the next tail mixes the same saved hgn and hsd again: no
+// k_tr_commit.  A rejected trial changes delta only, so the next tail mixes the same saved hgn and hsd again: no
 // factorisation.  The term records k_linearize left at x stay valid through the tails (the chi-only linearisation returns
 // before it writes them), and b stays in bvec through the solve.  The state lives on the device, so the host queues heads
 // and tails without reading anything back in between:
 //   - a tail does nothing unless an iteration is open (S->solved): k_dl_step keeps status[0] set, so k_update_poses skips;
-//     k_dl_decide and k_dl_commit leave the state, the records and the poses alone;
+//     k_dl_decide and k_tr_commit leave the state, the records and the poses alone;
 //   - a head behind an open iteration is stale: x is bit-identical to what the open iteration started from (its rejected
 //     trials restored it), so its terms and b are the same; k_dl_begin leaves hgn, hsd and the state alone;
 //   - a head whose damped factorisation failed leaves the iteration unsolved: the next head retries with the grown lambda.
@@ -27,28 +27,14 @@
 #include "dl_device.h"
 #include "gn_device.h"
 #include "gn_symbolic.h"
+#include "tr_device.h"
 
 namespace cgmr {
 
 namespace {
 
-constexpr int kDecideT = 1024;                  // threads of the one-workgroup kernels
-constexpr int kDoneTag = 1 << 30;               // status[0] once the call is over: no update applies any more
 constexpr int kIdleTag = (1 << 30) + 1;         // status[0] in a tail with no open iteration: its update does nothing
 constexpr int kStepGN = 2, kStepSD = 1, kStepDL = 3;   // include/cgmr.h: CGMR_DL_STEP_*
-
-// fixed-order sum over one workgroup of kDecideT threads
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = kDecideT / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
-}
 
 }  // namespace
 
@@ -57,12 +43,7 @@ __global__ __launch_bounds__(256) void k_dl_damp(int nf, const int32_t* __restri
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 3 * nf) return;
   if (S->was_pd || S->solved || S->done || S->halted) return;
-  const int c = t / 3, r = t - 3 * c;
-  if (cmask[c]) return;
-  const double lam = S->lambda;
-  const int dst = blk_dst[c];
-  if (dst >= 0) Pan[(size_t)dst + r * kPanStride + r] += lam;
-  else Ablk[(size_t)(-dst - 1) * 9 + 4 * r] += lam;
+  damp_diagonal(t, blk_dst, cmask, Pan, Ablk, S->lambda);
 }
 
 // v^T H v = sum over the edges of vi^T Hii vi + 2 vi^T Hij vj + vj^T Hjj vj, from the 33-double term records (k_linearize:
@@ -139,9 +120,9 @@ __global__ __launch_bounds__(kDecideT) void k_dl_begin(int nf, int nP, const dou
     hgn[j] = xj;
   }
   for (int k = threadIdx.x; k < nP; k += kDecideT) bhb += qpart[k];
-  bb = block_sum(bb, sh);
-  hh = block_sum(hh, sh);
-  bhb = block_sum(bhb, sh);
+  bb = block_reduce<false>(bb, sh);
+  hh = block_reduce<false>(hh, sh);
+  bhb = block_reduce<false>(bhb, sh);
   const double alpha = bb / bhb;                        // (b = 0: 0 / 0, as in g2o)
   double ss = 0;
   for (int j = threadIdx.x; j < 3 * nf; j += kDecideT) {
@@ -149,7 +130,7 @@ __global__ __launch_bounds__(kDecideT) void k_dl_begin(int nf, int nP, const dou
     hsd[j] = s;
     ss += s * s;
   }
-  ss = block_sum(ss, sh);
+  ss = block_reduce<false>(ss, sh);
   if (threadIdx.x == 0) {
     S->hgn_norm = sqrt(hh);
     S->hsd_norm = sqrt(ss);
@@ -181,9 +162,9 @@ __global__ __launch_bounds__(kDecideT) void k_dl_step(int nf, const double* __re
       bma += a * a;
       s2 += hsd[j] * hsd[j];
     }
-    c = block_sum(c, sh);
-    bma = block_sum(bma, sh);
-    s2 = block_sum(s2, sh);
+    c = block_reduce<false>(c, sh);
+    bma = block_reduce<false>(bma, sh);
+    s2 = block_reduce<false>(s2, sh);
     if (c <= 0) beta = (-c + sqrt(c * c + bma * (delta * delta - s2))) / bma;
     else beta = (delta * delta - s2) / (c + sqrt(c * c + bma * (delta * delta - s2)));
   }
@@ -195,8 +176,8 @@ __global__ __launch_bounds__(kDecideT) void k_dl_step(int nf, const double* __re
     bh += bvec[j] * h;
     hh += h * h;
   }
-  bh = block_sum(bh, sh);
-  hh = block_sum(hh, sh);
+  bh = block_reduce<false>(bh, sh);
+  hh = block_reduce<false>(hh, sh);
   if (threadIdx.x == 0) {
     S->bh = bh;
     S->h_norm = sqrt(hh);
@@ -224,8 +205,8 @@ __global__ __launch_bounds__(kDecideT) void k_dl_decide(int nP, const double* __
   if (!s_go) return;
   double tc = 0, hq = 0;
   for (int k = threadIdx.x; k < nP; k += kDecideT) { tc += part[k]; hq += qpart[k]; }
-  tc = block_sum(tc, sh);
-  hq = block_sum(hq, sh);
+  tc = block_reduce<false>(tc, sh);
+  hq = block_reduce<false>(hq, sh);
   if (threadIdx.x != 0) return;
   const double cur = S->cur_chi;
   double lin = -1 * hq + 2 * S->bh;
@@ -259,15 +240,6 @@ __global__ __launch_bounds__(kDecideT) void k_dl_decide(int nP, const double* __
   status[1] = 0;                                         // k_assemble's chi2 slot, k_update_poses' counter: per trial
 }
 
-__global__ __launch_bounds__(256) void k_dl_commit(int n, double* __restrict__ poses, double* __restrict__ saved,
-                                                   const DlState* __restrict__ S) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const int a = S->accept;
-  if (a == 1) saved[t] = poses[t];
-  else if (a == 0) poses[t] = saved[t];
-}
-
 void launch_dl_damp(hipStream_t st, const GnDevice& D, const DlState* S) {
   if (D.nf <= 0) return;
   hipLaunchKernelGGL(k_dl_damp, dim3((3 * D.nf + 255) / 256), dim3(256), 0, st, D.nf, D.blk_dst, D.cmask, D.Pan, D.Ablk, S);
@@ -290,11 +262,6 @@ void launch_dl_step(hipStream_t st, const GnDevice& D, const DlDev& L) {
 void launch_dl_decide(hipStream_t st, const GnDevice& D, const DlDev& L) {
   hipLaunchKernelGGL(k_dl_decide, dim3(1), dim3(kDecideT), 0, st, (D.nE + 255) / 256, D.term + (size_t)33 * D.nE, L.qpart, D.status,
                      L.S, L.rec_chi, L.rec_delta, L.rec_trials, L.rec_step);
-}
-
-void launch_dl_commit(hipStream_t st, int nV, double* poses, const DlDev& L) {
-  if (nV <= 0) return;
-  hipLaunchKernelGGL(k_dl_commit, dim3((3 * nV + 255) / 256), dim3(256), 0, st, 3 * nV, poses, L.saved, L.S);
 }
 
 }  // namespace cgmr

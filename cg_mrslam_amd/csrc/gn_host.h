@@ -3,8 +3,6 @@
 #include <cmath>
 
 #include "cgmr_ctx.h"
-#include "dl_device.h"
-#include "lm_device.h"
 
 namespace cgmr {
 
@@ -32,12 +30,47 @@ int prepare_batch_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st);
 // streams for concurrent passes
 int gn_replicas(cgmr_ctx* ctx, int n, std::vector<GnDevice>& out, size_t* stride_out = nullptr);
 int aux_streams(cgmr_ctx* ctx, int n);
-// lm (nullable): a Levenberg-Marquardt trial -- lambda onto H's diagonal after the assembly (computed first when lm_init)
-// dl (nullable): a dogleg head -- currentLambda onto H's diagonal while H has not been PD; solved, the poses are not updated
-void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, const GnEdges& Ed, int it, bool chi_only,
-                bool solve_and_update, bool write_l11c, LmState* lm = nullptr, bool lm_init = false, const DlState* dl = nullptr);
-// one Gauss-Newton pass on the uploaded structure: linearise + chi2 [+ assemble + factor [+ solve + update]]
-void gn_pass(cgmr_ctx* ctx, double* d_poses, const GnEdges& Ed, int it, bool chi_only, bool solve_and_update, bool write_l11c);
+// What a pass does behind its linearisation.  The order of its launches: [panel memset] -> assemble -> after_assemble ->
+// the levels -> top block / inversion -> backward solve -> pose update.
+struct GnPassOpts {
+  int chi_slot = 0;            // slot of D.chi2 that the chi2 launch of a chi-only pass (or of an empty system) writes
+  bool chi_only = false;       // linearise + chi2, nothing else
+  bool solve = true;           // forward and backward solve behind the factorisation
+  bool update_poses = true;    // apply the solved step (false: the caller makes its own step of it first)
+  bool write_l11c = false;     // keep what the marginals read of the factor
+  // queued between the assembly and the first level (a damping of H's diagonal)
+  void (*after_assemble)(hipStream_t st, const GnDevice& D, void* arg) = nullptr;
+  void* after_assemble_arg = nullptr;
+};
+// one pass on a device view (the context's, or a replica with its own numeric work space) and stream: linearise + chi2
+// [+ assemble + factor [+ solve [+ update]]]
+void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, const GnEdges& Ed, const GnPassOpts& o);
+// the same on the context's own view and stream
+void gn_pass(cgmr_ctx* ctx, double* d_poses, const GnEdges& Ed, const GnPassOpts& o);
+// A bounded device-side wait ran out (status[2]): a hand-off between workgroups that never arrived, not a numerical failure.
+inline void count_timeout(cgmr_ctx* ctx) {
+  ctx->gn_timeouts++;
+  ctx->fwd_merge_any = false;                                  // (the next structures merge only what is certainly resident)
+}
+// What was not applied is repeated with one launch per kernel and level -- no in-kernel waits.  arm() counts the event,
+// switches the view to "no chained backward solve, no merged level" and queues fresh status words (status[1] = it0); the
+// view gets back what arm() found when the scope ends, on whichever way the function is left.
+struct LevelwiseScope {
+  cgmr_ctx* ctx;
+  GnDevice& D;
+  bool armed = false;
+  int chain_was = 0;
+  std::vector<uint8_t> merge_was;
+  LevelwiseScope(cgmr_ctx* c, GnDevice& d) : ctx(c), D(d) {}
+  LevelwiseScope(const LevelwiseScope&) = delete;
+  LevelwiseScope& operator=(const LevelwiseScope&) = delete;
+  int arm(hipStream_t st, int it0 = 0);
+  ~LevelwiseScope() {
+    if (!armed) return;
+    D.bwd_chain_level = chain_was;
+    D.h_level_merge.swap(merge_was);
+  }
+};
 int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
            const GnEdges& Ed, int iters, double* chi2_out, const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0);
 // Levenberg-Marquardt on the same structure preparation and factorisation (g2o's OptimizationAlgorithmLevenberg): outputs

@@ -8,7 +8,7 @@
 
 namespace cgmr {
 
-// One per call, in device memory, set up by the host before the first trial (lm_run) and read back once per round.
+// One per call, in device memory, set up by the host before the first trial (cgmr_api.cpp: tr_run) and read back once per round.
 struct LmState {
   double lambda = 0, nu = 2;                 // current damping and its growth factor on a reject
   double tau = 1e-5, initial_lambda = -1;    // g2o's properties (initial_lambda <= 0: tau * max |H_jj|)
@@ -21,15 +21,19 @@ struct LmState {
   int32_t terminated = 0;                    // 1: g2o's Terminate (trial limit, rho == 0, lambda not finite)
   int32_t halted = 0;                        // 1: a bounded wait ran out in a trial: the host repeats it
   int32_t need_init = 1;                     // lambda still to be computed (first trial of the call)
-  int32_t accept = -1;                       // verdict of the last trial for k_lm_commit: 1 accept, 0 restore, -1 nothing
+  int32_t accept = -1;                       // verdict of the last trial for k_tr_commit: 1 accept, 0 restore, -1 nothing
   int32_t total_trials = 0;                  // trials decided in this call
+};
+
+// The device buffers of a call: records rec_chi [iters + 1], rec_lambda / rec_trials [iters]; saved poses [3 nV].
+struct LmDev {
+  LmState* S = nullptr;
+  double *rec_chi = nullptr, *rec_lambda = nullptr, *saved = nullptr;
+  int32_t* rec_trials = nullptr;
 };
 
 void launch_lm_init(hipStream_t st, const GnDevice& D, LmState* S);
 void launch_lm_damp(hipStream_t st, const GnDevice& D, const LmState* S);
-// rec_chi [iters + 1], rec_lambda / rec_trials [iters]
-void launch_lm_decide(hipStream_t st, const GnDevice& D, LmState* S, double* rec_chi, double* rec_lambda, int32_t* rec_trials);
-// n = nV poses: accepted -> saved = poses; rejected -> poses = saved
-void launch_lm_commit(hipStream_t st, int nV, double* poses, double* saved, const LmState* S);
+void launch_lm_decide(hipStream_t st, const GnDevice& D, const LmDev& L);
 
 }  // namespace cgmr

@@ -3,14 +3,14 @@
 // Reference behaviour: g2o's OptimizationAlgorithmLevenberg::solve [g2o-recalled; the contract is tests/ref_lm.py]:
 //   computeLambdaInit                                   -> k_lm_init
 //   BlockSolver::setLambda (H + lambda I)               -> k_lm_damp
-//   computeScale, the rho test, lambda / nu, push / pop -> k_lm_decide, k_lm_commit
+//   computeScale, the rho test, lambda / nu, push / pop -> k_lm_decide, k_tr_commit (tr_kernels.hip)
 //
-// One trial is a fixed launch sequence whatever its outcome (cgmr_api.cpp: lm_trial): linearise, assemble, [init,] damp,
+// One trial is a fixed launch sequence whatever its outcome (cgmr_api.cpp: LmPolicy::trial): linearise, assemble, [init,] damp,
 // factor, solve, update, chi-only linearise, decide, commit.  Re-linearising at unchanged poses yields the same terms bit for
 // bit, so a rejected trial needs nothing but the restored poses.  The state (lambda, nu, counters, records) lives on the
 // device: the host queues trials without reading anything back in between.  Once the call has terminated, every later
 // launch of a queued trial leaves the poses, the state and the records alone (k_lm_decide keeps status[0] set, so
-// k_update_poses skips; k_lm_commit does nothing).  All reductions have a fixed order: results are bit-reproducible.
+// k_update_poses skips; k_tr_commit does nothing).  All reductions have a fixed order: results are bit-reproducible.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -19,29 +19,9 @@
 #include "gn_device.h"
 #include "gn_symbolic.h"
 #include "lm_device.h"
+#include "tr_device.h"
 
 namespace cgmr {
-
-namespace {
-
-constexpr int kDecideT = 1024;                  // threads of the one-workgroup kernels
-constexpr int kDoneTag = 1 << 30;               // status[0] after termination: no update applies any more
-
-// fixed-order sum / max over one workgroup of kDecideT threads
-template <bool MAX>
-__device__ __forceinline__ double block_reduce(double v, double* sh) {
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = kDecideT / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] = MAX ? fmax(sh[threadIdx.x], sh[threadIdx.x + s]) : sh[threadIdx.x] + sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
-}
-
-}  // namespace
 
 // lambda = initialLambda if > 0, else tau * max |H_jj| over the unmasked diagonal (H as k_assemble left it: undamped, before
 // the children's contributions, which only the factorisation adds).  Only while S->need_init is set: the first trial of a call.
@@ -65,18 +45,12 @@ __global__ __launch_bounds__(kDecideT) void k_lm_init(int nf, const int32_t* __r
   }
 }
 
-// H + lambda I: lambda onto the three diagonal entries of every unmasked diagonal block, where k_assemble put the block
-// (blk_dst: the owning front's panel, or the Ablk slot of a top-block front).  Masked columns keep their identity rows.
+// H + lambda I on the unmasked diagonal (tr_device.h: damp_diagonal)
 __global__ __launch_bounds__(256) void k_lm_damp(int nf, const int32_t* __restrict__ blk_dst, const uint8_t* __restrict__ cmask,
                                                  double* __restrict__ Pan, double* __restrict__ Ablk, const LmState* __restrict__ S) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 3 * nf) return;
-  const int c = t / 3, r = t - 3 * c;
-  if (cmask[c]) return;
-  const double lam = S->lambda;
-  const int dst = blk_dst[c];
-  if (dst >= 0) Pan[(size_t)dst + r * kPanStride + r] += lam;
-  else Ablk[(size_t)(-dst - 1) * 9 + 4 * r] += lam;
+  damp_diagonal(t, blk_dst, cmask, Pan, Ablk, S->lambda);
 }
 
 // The trial's verdict.  currentChi: chi2 at x (k_assemble's slot 0); tempChi: the chi-only linearisation's partial sums at
@@ -148,16 +122,6 @@ __global__ __launch_bounds__(kDecideT) void k_lm_decide(int nf, int nP, const do
   status[1] = 0;                                       // k_assemble's chi2 slot, k_update_poses' counter: per trial
 }
 
-// accepted: the saved copy follows x; rejected: x is restored from it, bit for bit
-__global__ __launch_bounds__(256) void k_lm_commit(int n, double* __restrict__ poses, double* __restrict__ saved,
-                                                   const LmState* __restrict__ S) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const int a = S->accept;
-  if (a == 1) saved[t] = poses[t];
-  else if (a == 0) poses[t] = saved[t];
-}
-
 void launch_lm_init(hipStream_t st, const GnDevice& D, LmState* S) {
   hipLaunchKernelGGL(k_lm_init, dim3(1), dim3(kDecideT), 0, st, D.nf, D.blk_dst, D.cmask, D.Pan, D.Ablk, S);
 }
@@ -167,14 +131,9 @@ void launch_lm_damp(hipStream_t st, const GnDevice& D, const LmState* S) {
   hipLaunchKernelGGL(k_lm_damp, dim3((3 * D.nf + 255) / 256), dim3(256), 0, st, D.nf, D.blk_dst, D.cmask, D.Pan, D.Ablk, S);
 }
 
-void launch_lm_decide(hipStream_t st, const GnDevice& D, LmState* S, double* rec_chi, double* rec_lambda, int32_t* rec_trials) {
+void launch_lm_decide(hipStream_t st, const GnDevice& D, const LmDev& L) {
   hipLaunchKernelGGL(k_lm_decide, dim3(1), dim3(kDecideT), 0, st, D.nf, (D.nE + 255) / 256, D.term + (size_t)33 * D.nE, D.xvec, D.bvec,
-                     D.chi2, D.status, S, rec_chi, rec_lambda, rec_trials);
-}
-
-void launch_lm_commit(hipStream_t st, int nV, double* poses, double* saved, const LmState* S) {
-  if (nV <= 0) return;
-  hipLaunchKernelGGL(k_lm_commit, dim3((3 * nV + 255) / 256), dim3(256), 0, st, 3 * nV, poses, saved, S);
+                     D.chi2, D.status, L.S, L.rec_chi, L.rec_lambda, L.rec_trials);
 }
 
 }  // namespace cgmr

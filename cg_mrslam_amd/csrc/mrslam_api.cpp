@@ -296,7 +296,7 @@ int cond_finish(cgmr_graph* g) {
   if (!failed) return 0;
   for (int32_t p : g->cond_peers) { g->out[p].n = 0; g->out[p].host_valid = false; }
   g->cond_failed_batches++;
-  if (timed_out) { g->cond_levelwise = true; ctx->gn_timeouts++; ctx->fwd_merge_any = false; return g->cond_last_rc = gerr(g, CGMR_E_TIMEOUT, "a bounded device-side wait ran out while building a condensed graph"); }
+  if (timed_out) { g->cond_levelwise = true; count_timeout(ctx); return g->cond_last_rc = gerr(g, CGMR_E_TIMEOUT, "a bounded device-side wait ran out while building a condensed graph"); }
   return g->cond_last_rc = gerr(g, CGMR_E_CHOLESKY_BASE, "Cholesky failed while building a condensed graph");
 }
 
@@ -942,7 +942,9 @@ int run_cond_jobs(cgmr_graph* g, std::vector<CondJob>& jobs, bool to_wire, std::
     if (trace) for (auto& e : evs) (void)hipEventCreate(&e);
     if (trace) (void)hipEventRecord(evs[0], st);
     const double tp0 = wall_s();
-    gn_pass_on(ctx, DB, st, d_work0, Ed, 0, false, true, /*write_l11c=*/true);
+    GnPassOpts pass;
+    pass.write_l11c = true;
+    gn_pass_on(ctx, DB, st, d_work0, Ed, pass);
     const double tp1 = wall_s();
     t_gn = tp1 - tp0;
     if (trace) (void)hipEventRecord(evs[1], st);
@@ -1003,7 +1005,7 @@ int run_cond_jobs(cgmr_graph* g, std::vector<CondJob>& jobs, bool to_wire, std::
     if (trace)
       fprintf(stderr, "[cond] %d jobs in one batch, nV %d nE %d: structure %.0f us, queueing %.0f us (initial guesses %.0f, masks %.0f, uploads %.0f, GN pass %.0f, marginals + labels %.0f), waiting %.0f us\n",
               nj, nV, nE, 1e6 * (tt1 - tt0), 1e6 * (tt2 - tt1), 1e6 * t_guess, 1e6 * t_mask, 1e6 * t_up, 1e6 * t_gn, 1e6 * t_marg, 1e6 * (wall_s() - tt2));
-    if (timed_out) { ctx->gn_timeouts++; ctx->fwd_merge_any = false; return gerr(g, CGMR_E_TIMEOUT, "a bounded device-side wait ran out while building a condensed graph"); }
+    if (timed_out) { count_timeout(ctx); return gerr(g, CGMR_E_TIMEOUT, "a bounded device-side wait ran out while building a condensed graph"); }
     for (int i = 0; i < nj; i++)
       if (status[i] != 0) return gerr(g, CGMR_E_CHOLESKY_BASE, "Cholesky failed while building a condensed graph");
     return 0;
@@ -1041,7 +1043,9 @@ int run_cond_jobs(cgmr_graph* g, std::vector<CondJob>& jobs, bool to_wire, std::
     HIP_TRY(ctx, hipMemcpyAsync(d_qc, qcol.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, sj));
     HIP_TRY(ctx, hipMemcpyAsync(d_qv, J.q.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, sj));
     const double tp0 = wall_s();
-    gn_pass_on(ctx, D, sj, d_work, Ed, 0, false, true, /*write_l11c=*/true);
+    GnPassOpts pass;
+    pass.write_l11c = true;
+    gn_pass_on(ctx, D, sj, d_work, Ed, pass);
     const double tp1 = wall_s();
     t_gn += tp1 - tp0;
     const int m = ((4 * nq + 15) / 16) * 16;

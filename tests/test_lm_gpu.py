@@ -234,6 +234,40 @@ def test_one_launch_per_level_gives_the_same_trace(ctx, tmp_path):
         assert np.allclose(z[name + "_lam"], lam, rtol=RTOL, atol=0) and np.allclose(z[name + "_chi"], chi, rtol=RTOL, atol=0), name
 
 
+def test_a_timed_out_trial_is_repeated_one_launch_per_level():
+    """A bounded device-side wait that runs out in a trial (forced: CGMR_BWD_SPIN_LIMIT=1, one poll per wait) is no verdict:
+    the call goes on with one launch per kernel and level and gives the plain call's trace; the context counts the event
+    and the next call runs the merged and chained launches again.  bad_start: trials are rejected and the plain call takes
+    several rounds, so the repeated call passes through every part of the round loop."""
+    from cg_mrslam_amd import Context
+    name = "bad_start"
+    g, iters = graph(name), CASES[name][1]
+    ref = ref_lm.lm_optimize(*C.args(g), iters)
+    c = Context(0)
+    try:
+        first = c.lm_optimize(*C.args(g), iters)
+        plain = c.lm_last_stats()
+        assert first[0] == 0 and c.gn_timeouts() == 0
+        assert plain["host_waits"] > 1 and any(t > 1 for t in first[4]), (name, plain, "the case rejects nothing")
+        os.environ["CGMR_BWD_SPIN_LIMIT"] = "1"
+        try:
+            rc, _, chi, lam, tri, done = c.lm_optimize(*C.args(g), iters)
+        finally:
+            del os.environ["CGMR_BWD_SPIN_LIMIT"]
+        print(name, "plain", plain, "forced", c.lm_last_stats(), "timeouts", c.gn_timeouts(), "trials", tri, first[4])
+        print(name, "chi", np.abs(chi - first[2]) / np.abs(first[2]), "lambda", np.abs(lam - first[3]) / np.maximum(first[3], 1e-300))
+        assert rc == 0
+        assert c.gn_timeouts() >= 1, "the forced time-out did not happen: the test checks nothing"
+        assert done == first[5] and np.array_equal(tri, first[4]), (tri, first[4])
+        assert np.allclose(lam, first[3], rtol=RTOL, atol=0) and np.allclose(chi, first[2], rtol=RTOL, atol=0)
+        assert check_trace(name, ref, chi, lam, tri, done, rounding_floor(g)) >= 1
+        again = c.lm_optimize(*C.args(g), iters)
+        for u, v in zip(first, again):
+            assert np.array_equal(np.asarray(u), np.asarray(v))
+    finally:
+        c.close()
+
+
 def test_robot_graph_levenberg_matches_reference():
     from cg_mrslam_amd import Context
     from robot_sequences import make_robot_rounds, solved_system

@@ -86,6 +86,7 @@ struct cgmr_ctx {
   int64_t match_pairs = 0, match_slow_pairs = 0;   // last batched close-matching launch: pairs, pairs off the LDS fast path
   int64_t match_ext_pairs = 0;                     // ... pairs whose reference tiles borrowed half the point lists (NT_EXT)
   int64_t match_redo_why[3] = {0, 0, 0};           // ... by cause: grid, window / point count, an angle's lists
+  int64_t match_shape[4] = {0, 0, 0, 0};           // ... what the host chose for it: distance transform, 32-bit sort keys, lean instance, split
   int64_t match_redo_pairs = 0;                    // ... pairs the lean kernel instance handed to the general one
   bool profiling = false;
   double ksec[12] = {0};        // classes 0..7 as cgmr_gn_kernel_times, 8 = front_level (a level's factorisation + update tiles in one launch)

@@ -25,6 +25,7 @@ namespace {
 
 // ScanMatcher::initializeKernel (src/matcher/scan_matcher.cpp:38-61); element (row i, col j) at j*dim+i
 int make_kernel(double resolution, double kernel_range, int kscale, std::vector<uint8_t>& k) {
+  if (!(kernel_range / resolution < 16.0) || !(kernel_range * kscale < 128.0)) return -1;   // (the limits below, before the casts)
   int size = (int)(kernel_range / resolution);
   int center = size, dim = 2 * size + 1;
   int K1 = (int)(resolution * kscale), K2 = (int)(kernel_range * kscale);
@@ -33,7 +34,7 @@ int make_kernel(double resolution, double kernel_range, int kscale, std::vector<
   for (int j = 0; j <= size; j++)
     for (int i = 0; i <= size; i++) {
       double dv = K1 * std::sqrt((double)(j * j + i * i));
-      if (dv >= 128.0) continue;
+      if (dv >= 128.0) return -1;               // (`char distance = K1 * sqrt(..)` is undefined there; the reference's kernels stay below)
       char distance = (char)dv;
       if (distance > K2) continue;
       uint8_t d = (uint8_t)distance;
@@ -53,11 +54,23 @@ struct Layout {
 // grid geometry + kernel of a ScanMatcher (initializeGrid / initializeKernel)
 int setup_geometry(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, MatchParams& P, std::vector<uint8_t>& kern) {
   memset(&P, 0, sizeof P);
+  // (a zero, negative or non-finite value would reach the casts below, and the kernels, as an infinite or NaN cell count)
+  if (!cfg || !std::isfinite(cfg->resolution) || !((float)cfg->resolution > 0.f) || !std::isfinite((float)(1. / (float)cfg->resolution)))
+    return set_err(ctx, CGMR_E_INVALID, "grid resolution must be positive and finite");
+  if (!std::isfinite(cfg->grid_ll_x) || !std::isfinite(cfg->grid_ll_y) || !std::isfinite(cfg->grid_ur_x) || !std::isfinite(cfg->grid_ur_y) ||
+      !(cfg->grid_ur_x > cfg->grid_ll_x) || !(cfg->grid_ur_y > cfg->grid_ll_y))
+    return set_err(ctx, CGMR_E_INVALID, "grid corners must be finite, the upper right one beyond the lower left one");
+  if (cfg->kscale <= 0 || !std::isfinite(cfg->kernel_range) || cfg->kernel_range < 0)
+    return set_err(ctx, CGMR_E_INVALID, "kscale must be positive, the kernel range finite and not negative");
   P.ll_x = cfg->grid_ll_x; P.ll_y = cfg->grid_ll_y;
   P.res = (float)cfg->resolution;
   P.inv_res = (float)(1. / P.res);
-  P.nx = (int)((cfg->grid_ur_x - cfg->grid_ll_x) * P.inv_res);
-  P.ny = (int)((cfg->grid_ur_y - cfg->grid_ll_y) * P.inv_res);
+  {
+    const float fx = (cfg->grid_ur_x - cfg->grid_ll_x) * P.inv_res, fy = (cfg->grid_ur_y - cfg->grid_ll_y) * P.inv_res;
+    if (!(fx < 1e6f) || !(fy < 1e6f)) return set_err(ctx, CGMR_E_INVALID, "grid exceeds the %d-tile directory", kMatchMaxDir);
+    P.nx = (int)fx;
+    P.ny = (int)fy;
+  }
   int ntx = (P.nx + 7) / 8, nty = (P.ny + 7) / 8;
   if (P.nx <= 0 || P.ny <= 0 || (ntx + 2) * (nty + kMatchDirGuardY) > kMatchMaxDir)
     return set_err(ctx, CGMR_E_INVALID, "grid %dx%d cells exceeds the %d-tile directory", P.nx, P.ny, kMatchMaxDir);
@@ -123,7 +136,18 @@ int match_run(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_pairs, int n_
   P.theta_res = cfg->theta_res; P.max_score = max_score;
   P.dx = cfg->bin_x; P.dy = cfg->bin_y; P.dth = cfg->bin_theta;
   P.sub_res = cfg->subsample_res;
-  if ((2 * cfg->win_theta) / cfg->theta_res + 2 > kMatchMaxTheta)
+  {
+    const double pos[5] = {cfg->theta_res, cfg->bin_x, cfg->bin_y, cfg->bin_theta, cfg->subsample_res};
+    for (double v : pos)
+      if (!std::isfinite(v) || !(v > 0))
+        return set_err(ctx, CGMR_E_INVALID, "theta_res, the result bins and subsample_res must be positive and finite");
+    const double fin[7] = {cfg->win_x, cfg->win_y, cfg->win_theta, cfg->max_range, cfg->min_range, cfg->angle_min, cfg->angle_inc};
+    for (double v : fin)
+      if (!std::isfinite(v)) return set_err(ctx, CGMR_E_INVALID, "search window and laser description must be finite");
+    if (!std::isfinite(cfg->laser_pose[0]) || !std::isfinite(cfg->laser_pose[1]) || !std::isfinite(cfg->laser_pose[2]) || !std::isfinite(max_score))
+      return set_err(ctx, CGMR_E_INVALID, "laser pose and maxScore must be finite");
+  }
+  if (!((2 * cfg->win_theta) / cfg->theta_res + 2 <= kMatchMaxTheta))
     return set_err(ctx, CGMR_E_INVALID, "more than %d search angles", kMatchMaxTheta);
   P.scratch_stride = ((size_t)4 * kMatchMaxPoints * sizeof(double) + (size_t)4 * kMatchMaxRefScans * kMatchMaxPoints +
                       (size_t)P.overflow_tiles * 64 + 255) & ~size_t(255);
@@ -249,6 +273,7 @@ int match_run(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_pairs, int n_
   (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
   ctx->match_seconds = 1e-3 * ms;
   ctx->match_pairs = n_pairs;
+  ctx->match_shape[0] = P.edt; ctx->match_shape[1] = P.sort32; ctx->match_shape[2] = lean ? 1 : 0; ctx->match_shape[3] = P.split;
   ctx->match_slow_pairs = errv[2] + (int64_t)errv[16 + 2];         // (second block: the slow pairs' own launch; zero when it had nothing to do)
   ctx->match_ext_pairs = errv[7] + (int64_t)errv[16 + 7];
   if (errv[0] == 0) errv[0] = errv[16];
@@ -409,6 +434,12 @@ int cgmr_match_last_stats(const cgmr_ctx* ctx, int64_t out[2]) {
 int cgmr_match_last_redo_pairs(const cgmr_ctx* ctx, int64_t* out) {
   if (!ctx || !out) return CGMR_E_INVALID;
   *out = ctx->match_redo_pairs;
+  return CGMR_OK;
+}
+
+int cgmr_match_last_launch_shape(const cgmr_ctx* ctx, int64_t out[4]) {
+  if (!ctx || !out) return CGMR_E_INVALID;
+  for (int i = 0; i < 4; i++) out[i] = ctx->match_shape[i];
   return CGMR_OK;
 }
 

@@ -339,8 +339,14 @@ class ScanMatcher(_GenericSearch, _BatchedSearch):
         self.ctx._check(self.ctx.lib.cgmr_match_last_stats(self.ctx.h, C.c_void_p(out.ctypes.data)))
         pc = np.zeros(4, dtype=np.int64)
         self.ctx._check(self.ctx.lib.cgmr_match_last_path_counts(self.ctx.h, C.c_void_p(pc.ctypes.data)))
+        rd = C.c_int64(0)
+        self.ctx._check(self.ctx.lib.cgmr_match_last_redo_pairs(self.ctx.h, C.byref(rd)))
+        sh = np.zeros(4, dtype=np.int64)
+        self.ctx._check(self.ctx.lib.cgmr_match_last_launch_shape(self.ctx.h, C.c_void_p(sh.ctypes.data)))
         return {"pairs": int(out[0]), "slow_pairs": int(out[1]), "borrowed_pool_pairs": int(pc[0]),
-                "redo_by_cause": {"grid": int(pc[1]), "window_or_points": int(pc[2]), "lists": int(pc[3])}}
+                "redo_by_cause": {"grid": int(pc[1]), "window_or_points": int(pc[2]), "lists": int(pc[3])},
+                "redo_pairs": int(rd.value),
+                "launch": {"edt": int(sh[0]), "sort32": int(sh[1]), "lean": int(sh[2]), "split": int(sh[3])}}
 
     def closeScanMatching_dev(self, d_ranges_ref, d_ranges_cur, d_guess, n_pairs, d_xyt, d_score, d_found,   # noqa: N802
                               maxScore=0.15, d_nres=0):   # noqa: N803

@@ -320,7 +320,24 @@ int cgmr_gn_kernel_times_ex(const cgmr_ctx* ctx, double seconds_out[12], int64_t
  * (src/slam/graph_slam.cpp:58-62) plus the laser description of RobotLaser / LaserParameters.
  * cgmr_matcher_config_close() fills in the reference's close-matcher defaults:
  * grid [-15,15]^2 at 0.025 m, kernel range 0.2 m, kscale 128, window +/-(0.3 m, 0.3 m, 0.2 rad),
- * theta step 0.00625, result bins (0.5, 0.5, 0.2), query subsampling 0.1 m.                */
+ * theta step 0.00625, result bins (0.5, 0.5, 0.2), query subsampling 0.1 m.
+ *
+ * Limits (every one refused with CGMR_E_INVALID and a message before or by the launch; tests/test_matcher_config_gpu.py
+ * holds each of them with a configuration beyond it and, where the limit is a size -- bins, angles, directory, table values,
+ * table radius, beams --, one inside it that must match the oracle):
+ *   - resolution, theta_res, bin_x / bin_y / bin_theta and subsample_res positive and finite; kscale > 0; the window, the
+ *     corners, max_range, min_range and the maxScore of a call finite (to accept every candidate pass a large finite
+ *     maxScore); grid_ur beyond grid_ll in both coordinates;
+ *   - the grid fits the tile directory: (ceil(nx / 8) + 2) * (ceil(ny / 8) + 7) <= 152 * 157, i.e. 1200 x 1200 cells or a
+ *     non-square grid of the same directory size (1400 x 1000);
+ *   - the kernel table: radius int(kernel_range / resolution) <= 15 cells, and every value of it fits a signed char as in
+ *     the reference (`char distance = K1 * sqrt(..)`): int(resolution * kscale) * sqrt(2) * radius < 128 (which implies
+ *     int(kernel_range * kscale) <= 127);
+ *   - at most 80 search angles: (2 win_theta) / theta_res + 2 <= 80; at most 128 result bins inside a window;
+ *   - n_beams <= 1088.
+ * Inside these limits every configuration is bit-identical to the reference's arithmetic; which device code serves it
+ * (cgmr_match_last_launch_shape, cgmr_match_last_path_counts) depends on the configuration: the fast search needs cell counts
+ * that are multiples of 8 and a fill value int(kernel_range * kscale) <= 63.                */
 typedef struct cgmr_matcher_config {
   float grid_ll_x, grid_ll_y, grid_ur_x, grid_ur_y;   /* initializeGrid(lowerLeft, upperRight, res) */
   double resolution;                                  /* grid resolution and kernel resolution      */
@@ -389,6 +406,11 @@ int cgmr_match_last_redo_pairs(const cgmr_ctx* ctx, int64_t* out);
  * [1] the reference grid (tiles beyond LDS, or a cell off the grid whose stamp reaches in), [2] the search window or the point
  * count (more than 32 offsets along an axis, more points than one list holds), [3] an angle whose point lists did not fit. */
 int cgmr_match_last_path_counts(const cgmr_ctx* ctx, int64_t out[4]);
+/* What the host chose for the last batched close-matching launch from the configuration and the batch size (read-only):
+ * out[0] = 1 the distance-transform rasteriser / 0 the compare-and-swap stamping one (kernel radius above 8 cells, or a table
+ * that is not a non-decreasing function of the squared distance); out[1] = 1 32-bit / 0 64-bit subsample sort keys;
+ * out[2] = 1 when the lean kernel instance ran in front of the general one; out[3] = workgroups per pair (split). */
+int cgmr_match_last_launch_shape(const cgmr_ctx* ctx, int64_t out[4]);
 /* Device time (HIP events on the context's stream) of the last matcher launch, seconds. */
 int cgmr_match_last_kernel_seconds(const cgmr_ctx* ctx, double* seconds);
 

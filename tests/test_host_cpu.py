@@ -613,3 +613,10 @@ def test_dead_reckoning_chain_equals_se2_compose_bit_for_bit():
         prev = synth.se2_compose(prev[None], inc[k][None])[0]
         want.append(prev)
     assert np.array_equal(got, np.array(want))
+
+
+def test_launch_shape_query_rejects_a_missing_context_without_a_gpu():
+    import ctypes as C
+    lib = _lib.load_library()
+    out = (C.c_int64 * 4)()
+    assert lib.cgmr_match_last_launch_shape(None, out) == lib.cgmr_match_last_stats(None, out) < 0

@@ -581,15 +581,6 @@ int prepare_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, const uint8_t* f
   return 0;
 }
 
-// the passes of a batch (GnDevice::njobs) start from the masks staged in slots 0 .. njobs-1 and from clean status words
-int prepare_batch_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st) {
-  const Symbolic& S = ctx->sym;
-  HIP_TRY(ctx, hipMemset2DAsync(D.status, (size_t)D.job_stride, 0, 16, (size_t)D.njobs, st));
-  if (S.nf == 0) return 0;
-  HIP_TRY(ctx, hipMemcpy2DAsync(D.cmask, (size_t)D.job_stride, ctx->pinned_mask, (size_t)S.nf, (size_t)S.nf, (size_t)D.njobs, hipMemcpyHostToDevice, st));
-  return 0;
-}
-
 // profiling mode: add up the event pairs of the launches since the last collection (call after a stream sync)
 void profile_collect(cgmr_ctx* ctx) {
   for (size_t k = 0; k < ctx->ev_cls.size(); k++) {
@@ -1284,17 +1275,11 @@ int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const 
   GnDevice& D = ctx->gn;
   hipStream_t st = ctx->stream;
   if (D.nf == 0 || nq == 0) { HIP_TRY(ctx, hipStreamSynchronize(st)); return mode == 2 ? 0 : CGMR_OK; }
-  const int m = ((4 * nq + 15) / 16) * 16;          // 4 columns of Y per query (3 + 1 padding): a query never straddles a 16-column tile
-  const int n = 3 * D.nf;
-  const int chunk = 2048, nchunk = (n + chunk - 1) / chunk;
-  // staging: poses | meas | info | qcol | qvert | Y | Uv | part | G | cov | est | info_out | flags
-  struct L2 { size_t off = 0; size_t add(size_t b) { off = (off + 255) & ~size_t(255); size_t o = off; off += b; return o; } } L;
-  size_t o_p = L.add(24 * (size_t)nV), o_m = L.add(24 * (size_t)nE), o_i = L.add(48 * (size_t)nE), o_qc = L.add(4 * (size_t)nq),
-         o_qv = L.add(4 * (size_t)nq), o_Y = L.add(8 * (size_t)n * m), o_U = L.add(8 * ((size_t)3 * S.rows.size() + 3) * m),
-         o_part = L.add(8 * (size_t)nchunk * 16 * m), o_G = L.add(8 * (size_t)16 * m), o_cov = L.add(72 * (size_t)nq),
-         o_est = L.add(24 * (size_t)nq), o_io = L.add(48 * (size_t)nq), o_fl = L.add(4 * (size_t)nq),
-         o_live = L.add((size_t)std::max(ctx->gn.nfronts, 1) * (m / 16));
-  rc = arena_reserve(ctx, ctx->io_arena, L.off + 256);
+  // staging: poses | meas | info | the marginals' and labels' work space
+  Layout256 L;
+  const size_t o_p = L.add(24 * (size_t)nV), o_m = L.add(24 * (size_t)nE), o_i = L.add(48 * (size_t)nE);
+  const MargLayout M(nq, D.nf, S.rows.size(), D.nfronts, L.off);
+  rc = arena_reserve(ctx, ctx->io_arena, M.end + 256);
   if (rc) return rc;
   char* d = ctx->io_arena.ptr;
   std::vector<int32_t> qcol(nq);
@@ -1302,8 +1287,8 @@ int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const 
   HIP_TRY(ctx, hipMemcpyAsync(d + o_p, work.data(), 24 * (size_t)nV, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d + o_m, meas, 24 * (size_t)nE, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d + o_i, info, 48 * (size_t)nE, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d + o_qc, qcol.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d + o_qv, q.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + M.o_qc, qcol.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + M.o_qv, q.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, st));
   double* dp = (double*)(d + o_p);
   // the Hessian of this iteration (linearised at the initial guess) is what computeMarginals sees [g2o-recalled];
   // for the condensed graph the iteration is completed first: the factor stays valid, the poses move on
@@ -1315,16 +1300,16 @@ int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const 
   pass.solve = pass.update_poses = mode == 2;
   auto run_pass = [&]() -> int {
     gn_pass(ctx, dp, Ed, pass);
-    launch_marginals(st, D, nq, (const int32_t*)(d + o_qc), m, (double*)(d + o_Y), (double*)(d + o_U), (double*)(d + o_part),
-                     (double*)(d + o_G), (double*)(d + o_cov), chunk, nchunk, (uint8_t*)(d + o_live));
+    launch_marginals(st, D, nq, (const int32_t*)(d + M.o_qc), M.m, (double*)(d + M.o_Y), (double*)(d + M.o_U), (double*)(d + M.o_part),
+                     (double*)(d + M.o_G), (double*)(d + M.o_cov), M.chunk, M.nchunk, (uint8_t*)(d + M.o_live));
     if (mode == 2)
-      launch_label(st, nq, (const int32_t*)(d + o_qv), gauge, dp, (const double*)(d + o_cov), (double*)(d + o_est),
-                   (double*)(d + o_io), (int*)(d + o_fl));
-    HIP_TRY(ctx, hipMemcpyAsync(cov.data(), d + o_cov, 72 * (size_t)nq, hipMemcpyDeviceToHost, st));
+      launch_label(st, nq, (const int32_t*)(d + M.o_qv), gauge, dp, (const double*)(d + M.o_cov), (double*)(d + M.o_est),
+                   (double*)(d + M.o_info), (int*)(d + M.o_fl));
+    HIP_TRY(ctx, hipMemcpyAsync(cov.data(), d + M.o_cov, 72 * (size_t)nq, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
     if (mode == 2) {
-      HIP_TRY(ctx, hipMemcpyAsync(est_out, d + o_est, 24 * (size_t)nq, hipMemcpyDeviceToHost, st));
-      HIP_TRY(ctx, hipMemcpyAsync(info_out, d + o_io, 48 * (size_t)nq, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, hipMemcpyAsync(est_out, d + M.o_est, 24 * (size_t)nq, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, hipMemcpyAsync(info_out, d + M.o_info, 48 * (size_t)nq, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(ctx, hipStreamSynchronize(st));
     HIP_TRY(ctx, hipGetLastError());
@@ -1390,7 +1375,7 @@ int marginals_all_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8
   std::vector<int32_t> vcol(nV);
   for (int v = 0; v < nV; v++) vcol[v] = ctx->vmask[v] ? -1 : S.vperm[v];     // fixed / inactive: zeros
   // staging: poses | meas | info | vcol | col_front | soff | tiles | cov | cross;  Sigma: an arena of its own
-  struct L2 { size_t off = 0; size_t add(size_t b) { off = (off + 255) & ~size_t(255); size_t o = off; off += b; return o; } } L;
+  Layout256 L;
   const size_t o_p = L.add(24 * (size_t)nV), o_m = L.add(24 * (size_t)nE), o_i = L.add(48 * (size_t)nE), o_vc = L.add(4 * (size_t)nV),
                o_cf = L.add(4 * (size_t)D.nf), o_so = L.add(8 * soff.size()), o_t = L.add(4 * tiles.size()), o_cov = L.add(72 * (size_t)nV),
                o_cr = L.add(72 * (size_t)nE);

@@ -741,324 +741,345 @@ struct CondJob {
   std::vector<int32_t> q;             // the other requested vertices (vertex indices, id order)
 };
 
-// CondensedGraphCreator::compute (condensed_graph_creator.cpp:33-66) for a batch of (gauge, vertex set) jobs on the
-// robot's own edges.  One symbolic analysis (shared with cgmr_graph_optimize: same edge list) serves all jobs -- the
-// gauge and the switched-off received edges are numeric masks.  Every job gets a copy of the numeric work space and
-// a side stream: one pass keeps a handful of workgroups busy per tree level, so the passes overlap almost perfectly.
-// to_wire: the labelled edges go to the peer's slots (double-precision copy + 44-byte wire records in the send
-// buffer); otherwise only the information matrices come back (info_out[i], 6 doubles per edge: gauge search).
-// async_out (nullable): on entry true = queue the batch on the context's side stream and return without waiting (the
-// caller finishes it later: cond_finish); set to false when the batch could not be queued that way and was waited for.
-int run_cond_jobs(cgmr_graph* g, std::vector<CondJob>& jobs, bool to_wire, std::vector<std::vector<double>>* info_out,
-                  bool* async_out = nullptr) {
-  cgmr_ctx* ctx = g->ctx;
-  hipStream_t st = ctx->stream;
-  bool go_async = async_out && *async_out;
-  if (async_out) *async_out = false;
-  const int nV = (int)g->ids.size(), nA = (int)g->ef.size(), cap = g->cap;
-  const int nj = (int)jobs.size();
-  if (nj == 0) return 0;
-  static const bool trace = getenv("CGMR_COND_TRACE") != nullptr;
-  const double tt0 = wall_s();
-  double t_guess = 0, t_mask = 0, t_up = 0, t_gn = 0, t_marg = 0;
+// The staging block of a batch of nj jobs: masks | initial guesses | query columns | query vertices | job descriptors go up in
+// one copy from pinned memory (the first s_st bytes); the status words (4 per job) come back behind them.
+struct CondStage {
+  size_t s_work = 0, s_qc = 0, s_qv = 0, s_jd = 0, s_st = 0, s_end = 0;
+  CondStage() = default;
+  CondStage(int nj, int nf, int nV, int maxq) {
+    Layout256 L;
+    L.add((size_t)nf * nj);                                      // (the masks: offset 0)
+    s_work = L.add((size_t)24 * nV * nj); s_qc = L.add((size_t)4 * maxq * nj); s_qv = L.add((size_t)4 * maxq * nj);
+    s_jd = L.add(sizeof(CondJobDev) * (size_t)nj); s_st = L.add(16 * (size_t)nj);
+    s_end = L.off;
+  }
+};
+
+// One batch of condensed-graph passes on its way through run_cond_jobs' phases.
+struct CondBatch {
+  cgmr_graph* g;
+  cgmr_ctx* ctx;
+  std::vector<CondJob>& jobs;
+  bool to_wire;
+  int nV, nA, nE = 0, nj, nf = 0, maxq = 1;
+  const int32_t *s_ef = nullptr, *s_et = nullptr;   // the edge list the structure was analysed for (own edges first)
+  hipStream_t st = nullptr;           // the context's stream, or its side stream for a batch that is not waited for
+  std::vector<GnDevice> reps;         // a view of every job's copy of the numeric work space (the passes on streams)
+  GnDevice DB;                        // the batch's view: job 0's, job j moved by j * DB.job_stride
+  GnEdges Ed;
+  MargLayout M;                       // one job's marginals work space; job j: moved by j * per_job
+  size_t per_job = 0;
+  CondStage S;
+  char *hstage = nullptr, *d0 = nullptr, *ds = nullptr;   // the staging block in pinned memory; on the device: job 0's marginals work space, the staging block's copy behind the jobs'
+  // CGMR_COND_TRACE: host seconds of the phases, device events around the pass / the marginals / the labels
+  bool trace = false;
+  double t0 = 0, t_structure = 0, t_space = 0, t_guess = 0, t_mask = 0, t_up = 0, t_gn = 0, t_marg = 0;
+  hipEvent_t evs[4] = {nullptr, nullptr, nullptr, nullptr};
+
+  CondBatch(cgmr_graph* g_, std::vector<CondJob>& j, bool w)
+      : g(g_), ctx(g_->ctx), jobs(j), to_wire(w), nV((int)g_->ids.size()), nA((int)g_->ef.size()), nj((int)j.size()) {}
+  CondBatch(const CondBatch&) = delete;
+  ~CondBatch() { for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e); }
+  void mark(int k) { if (trace) (void)hipEventRecord(evs[k], st); }
+};
+
+// Structure, work space and edge description of the batch: one symbolic analysis (shared with cgmr_graph_optimize: same edge
+// list) serves all jobs -- the gauge and the switched-off received edges are numeric masks --, every job gets a copy of the
+// numeric work space and a marginals work space sized for the largest query set; the staging block lies behind them.
+int cond_setup(CondBatch& B) {
+  cgmr_graph* g = B.g;
+  cgmr_ctx* ctx = B.ctx;
   // the edge list the structure is analysed for: the last solve's if nothing of mine has changed since (a hit in the
   // analysis cache; own edges are only ever appended, so equal counts mean equal lists), else the current one
-  const bool reuse = g->solved_nV == nV && g->solved_nA == nA && (int)g->solved_ef.size() >= nA;
+  const bool reuse = g->solved_nV == B.nV && g->solved_nA == B.nA && (int)g->solved_ef.size() >= B.nA;
   const std::vector<int32_t>& s_ef = reuse ? g->solved_ef : g->all_ef;
   const std::vector<int32_t>& s_et = reuse ? g->solved_et : g->all_et;
-  const int nE = (int)s_ef.size();
-  int rc = prepare_structure(ctx, nV, nE, s_ef.data(), s_et.data(), 1);
+  B.nE = (int)s_ef.size();
+  B.s_ef = s_ef.data(); B.s_et = s_et.data();
+  int rc = prepare_structure(ctx, B.nV, B.nE, s_ef.data(), s_et.data(), 1);
   if (rc) return rc;
-  const double tt1 = wall_s();
-  const Symbolic& S = ctx->sym;
-  const int nstreams = std::min(nj, 8);
-  std::vector<GnDevice> reps;
-  size_t rep_stride = 0;
+  const double t1 = wall_s();
+  B.t_structure = t1 - B.t0;
+  B.nf = ctx->gn.nf;
   const size_t rep_cap0 = ctx->rep_arena.cap, mg_cap0 = ctx->mg_arena.cap;
-  rc = gn_replicas(ctx, nj, reps, &rep_stride);
+  size_t rep_stride = 0;
+  rc = gn_replicas(ctx, B.nj, B.reps, &rep_stride);
   if (rc) return rc;
-  const double tt1a = wall_s();
-  // marginals work space per pass, sized for the largest query set
-  int maxq = 1;
-  for (CondJob& J : jobs) maxq = std::max(maxq, (int)J.q.size());
-  const int nf = ctx->gn.nf;
-  const int m_max = ((4 * maxq + 15) / 16) * 16, n = 3 * nf, chunk = 2048, nchunk = (n + chunk - 1) / chunk;
-  struct L2 { size_t off = 0; size_t add(size_t b) { off = (off + 255) & ~size_t(255); size_t o = off; off += b; return o; } } L;
-  const size_t o_qc = L.add(4 * (size_t)maxq), o_qv = L.add(4 * (size_t)maxq), o_Y = L.add(8 * (size_t)n * m_max),
-               o_U = L.add(8 * ((size_t)3 * S.rows.size() + 3) * m_max), o_part = L.add(8 * (size_t)nchunk * 16 * m_max),
-               o_G = L.add(8 * (size_t)16 * m_max), o_cov = L.add(72 * (size_t)maxq), o_fl = L.add(4 * (size_t)maxq),
-               o_e64 = L.add(24 * (size_t)maxq), o_i64 = L.add(48 * (size_t)maxq), o_st = L.add(16),
-               o_live = L.add((size_t)std::max(ctx->gn.nfronts, 1) * (m_max / 16));
-  const size_t per_job = (L.off + 255) & ~size_t(255);
-  // behind the jobs' blocks: the staging block of a batched run (masks | initial guesses | query columns | query vertices |
-  // job descriptors), one copy from the pinned block
-  const size_t o_stage = per_job * (size_t)nj;
-  const size_t stage_cap = (size_t)nf * nj + (size_t)24 * nV * nj + 2 * (size_t)4 * maxq * nj + sizeof(CondJobDev) * (size_t)nj + 5 * 256;
-  rc = arena_reserve(ctx, ctx->mg_arena, o_stage + stage_cap + 256);
+  B.DB = B.reps[0];
+  B.DB.njobs = B.nj; B.DB.job_stride = (long long)rep_stride; B.DB.pose_stride = 24LL * B.nV;
+  const double t1a = wall_s();
+  for (CondJob& J : B.jobs) B.maxq = std::max(B.maxq, (int)J.q.size());
+  B.M = MargLayout(B.maxq, B.nf, ctx->sym.rows.size(), ctx->gn.nfronts, 0, /*flags_first=*/true);
+  B.per_job = round256(B.M.end);
+  B.S = CondStage(B.nj, B.nf, B.nV, B.maxq);
+  rc = arena_reserve(ctx, ctx->mg_arena, B.per_job * (size_t)B.nj + B.S.s_end + 256);
   if (rc) return rc;
-  const double tt1b = wall_s();                                  // (replicas, work space: allocations when something grew)
-  if (trace && tt1b - tt1 > 300e-6)
-    fprintf(stderr, "[cond]   work space: replicas %.0f us (%zu -> %zu MB), marginals arena %.0f us (%zu -> %zu MB)\n", 1e6 * (tt1a - tt1), rep_cap0 >> 20,
-            ctx->rep_arena.cap >> 20, 1e6 * (tt1b - tt1a), mg_cap0 >> 20, ctx->mg_arena.cap >> 20);
-  GnEdges Ed;
+  B.d0 = ctx->mg_arena.ptr;
+  B.ds = B.d0 + B.per_job * (size_t)B.nj;
+  const double t1b = wall_s();                                   // (work space: allocations when something grew)
+  B.t_space = t1b - t1;
+  if (B.trace && t1b - t1 > 300e-6)
+    fprintf(stderr, "[cond]   work space: replicas %.0f us (%zu -> %zu MB), marginals arena %.0f us (%zu -> %zu MB)\n", 1e6 * (t1a - t1), rep_cap0 >> 20,
+            ctx->rep_arena.cap >> 20, 1e6 * (t1b - t1a), mg_cap0 >> 20, ctx->mg_arena.cap >> 20);
+  GnEdges& Ed = B.Ed;
   Ed.meas_a = (const double*)g->d_meas_a.ptr; Ed.info_a = (const double*)g->d_info_a.ptr;
   Ed.meas_b = g->d_meas_b; Ed.info_b = g->d_info_b;
-  Ed.nA = nA; Ed.n_active = nA;                                  // getMyEdges: the received edges are switched off
+  Ed.nA = B.nA; Ed.n_active = B.nA;                              // getMyEdges: the received edges are switched off
   if (g->cond_robust && g->rk_dev) {  // the own edges' kernels (the received ones are switched off: their class never enters)
     Ed.robust = true;
     Ed.rk_kind = (const uint8_t*)g->d_rk_kind.ptr; Ed.rk_delta = (const double*)g->d_rk_delta.ptr;
     Ed.rk_kind0 = CGMR_RK_NONE; Ed.rk_delta0 = 1.0;
   }
-  if (Ed.rk_stats && nj > 1) return gerr(g, CGMR_E_INVALID, "a batch of condensed graphs takes no robust statistics");
-  std::vector<uint8_t> fixed(nV);
-  std::vector<int32_t> qcol;
-  // the spanning-tree initial guess of every job (its own gauge as the root: 0.15-0.3 ms of host work each) on the helper
-  // threads; dst(i): where job i's guess goes (a batch: straight into its slot of the staging block)
-  std::vector<std::vector<double>> works(nj);
-  auto run_guesses = [&](const std::function<double*(int)>& dst) {
-    const double tg0 = wall_s();
-    static const bool cached_walk = !(getenv("CGMR_GUESS_CACHED") && atoi(getenv("CGMR_GUESS_CACHED")) == 0);
-    host_run_tasks(nj, [&](int i) {
-      double* w = dst(i);
-      memcpy(w, g->h_poses.data(), (size_t)24 * nV);
-      if (cached_walk) {
-        thread_local std::vector<int32_t> queue;
-        thread_local std::vector<double> cs;
-        thread_local std::vector<uint8_t> seen;
-        initial_guess_own_edges(g, jobs[i].gauge, w, queue, cs, seen);
-      } else {
-        std::vector<uint8_t> fx(nV, 0);
-        fx[jobs[i].gauge] = 1;
-        initial_guess_host(nV, w, fx.data(), nA, g->ef.data(), g->et.data(), g->h_meas.data());
-      }
-    });
-    t_guess = wall_s() - tg0;
-  };
-  WireEdge* send_edges = reinterpret_cast<WireEdge*>(g->d_send + wire_edges_off(g->n_robots));
-  // Several passes: ONE sequence of launches with a job dimension (gn_kernels.hip CGMR_JOB) instead of a stream of ~65
-  // launches per job side by side -- next to each other the device dispatched the small kernels of 7 jobs at ~7 us apiece
-  // (3.9 ms for the condensed graphs of a round with 8 robots); CGMR_COND_BATCH=0: the streams
-  static const bool batch_on = !(getenv("CGMR_COND_BATCH") && atoi(getenv("CGMR_COND_BATCH")) == 0);
-  const bool batched = batch_on && nf > 0;            // (a single pass as a batch of one: no side stream to fork and join, staging from pinned memory)
-  std::vector<int32_t> status(nj, 0);
-  go_async = go_async && batched && to_wire && !info_out;
-  // whatever ran on the side stream before (another graph of this context, this graph's previous batch) used the replicas
-  // and the marginals work space this batch is about to fill
-  // (work queued on the side stream behind the fork is marked -- side_busy, side_tail -- even when this function leaves on an error:
-  // the next join then waits for it instead of skipping it)
-  struct SideGuard {
-    cgmr_ctx* c; bool armed;
-    ~SideGuard() { if (armed) (void)side_mark(c); }
-  } side_guard{ctx, false};
-  if (go_async) {
-    rc = side_fork(ctx);
+  return 0;
+}
+
+// The pinned staging block: the context's (the solver's mask staging -- nothing of it is in flight now) or, for a batch that is
+// not waited for, the graph's own: the next solve stages its mask while this batch's copy may still be queued.
+int cond_stage_block(CondBatch& B, bool go_async) {
+  cgmr_graph* g = B.g;
+  cgmr_ctx* ctx = B.ctx;
+  if (!go_async) {
+    int rc = pinned_mask_reserve(ctx, B.S.s_end);
     if (rc) return rc;
-    side_guard.armed = true;
-    st = ctx->side;
-    rc = wait_consumers(g, st);
-    if (rc) return rc;
-  } else {
-    rc = side_join_stream(ctx, st);
-    if (rc) return rc;
-    rc = wait_consumers(g, st);
-    if (rc) return rc;
-  }
-  if (batched) {
-    // staging (the context's mask block: nothing else is in flight from it): masks | initial guesses | query columns |
-    // query vertices | job descriptors
-    auto up256 = [](size_t v) { return (v + 255) & ~size_t(255); };
-    const size_t s_work = up256((size_t)nf * nj), s_qc = s_work + up256((size_t)24 * nV * nj), s_qv = s_qc + up256((size_t)4 * maxq * nj),
-                 s_jd = s_qv + up256((size_t)4 * maxq * nj), s_st = s_jd + up256(sizeof(CondJobDev) * (size_t)nj), s_end = s_st + 16 * (size_t)nj;
-    // staging block: the context's (the solver's mask staging -- nothing of it is in flight now) or, for a batch that is
-    // not waited for, the graph's own: the next solve stages its mask while this batch's copy may still be queued
-    char* hstage = nullptr;
-    if (go_async) {
-      if (s_end > g->cond_pinned_cap) {
-        if (g->cond_pinned) {
-          rc = side_join_host(ctx);
-          if (rc) return rc;
-          (void)hipHostFree(g->cond_pinned);
-          g->cond_pinned = nullptr; g->cond_pinned_cap = 0;
-        }
-        const size_t want = 2 * s_end + (64 << 10);           // (page-locking is slow: rarely)
-        HIP_TRY(ctx, hipHostMalloc((void**)&g->cond_pinned, want, hipHostMallocDefault));
-        g->cond_pinned_cap = want;
-      }
-      hstage = g->cond_pinned;
-    } else {
-      rc = pinned_mask_reserve(ctx, s_end);
-      if (rc) return rc;
-      hstage = ctx->pinned_mask;
-    }
-    GnDevice DB = reps[0];
-    DB.njobs = nj; DB.job_stride = (long long)rep_stride; DB.pose_stride = 24LL * nV;
-    // the chained backward solve needs its workgroups resident together: the chain of the batch takes nj times the slots
-    {
-      // (after a time-out -- two chained solves per context on eight contexts of one device make them likelier -- the batches of
-      // this graph solve level by level: no in-kernel waits, like gn_run's retry)
-      choose_bwd_chain(DB, (ctx->side_used ? 2 : 1) * nj, g->cond_levelwise);
-      choose_fwd_merge(DB, (ctx->side_used ? 2 : 1) * nj, g->cond_levelwise, ctx->fwd_merge_any);
-    }
-    run_guesses([&](int i) { return (double*)(hstage + s_work + (size_t)24 * nV * i); });
-    const double tm0 = wall_s();
-    // the column masks: a vertex without an own edge is out of every job's system (the received edges are switched off);
-    // the jobs differ in their gauge only
-    std::vector<uint8_t> live(nV, 0);
-    for (int k = 0; k < nA; k++) { live[s_ef[k]] = 1; live[s_et[k]] = 1; }
-    std::vector<char> base(nf);
-    for (int c = 0; c < nf; c++) base[c] = live[S.perm[c]] ? 0 : 1;
-    for (int i = 0; i < nj; i++) {
-      char* h = hstage;
-      char* pm = h + (size_t)nf * i;
-      memcpy(pm, base.data(), (size_t)nf);
-      const int gauge = jobs[i].gauge;
-      if (S.vperm[gauge] >= 0) pm[S.vperm[gauge]] = 1;
-      const int nq = (int)jobs[i].q.size();
-      int32_t* qc = (int32_t*)(h + s_qc) + (size_t)maxq * i;
-      int32_t* qv = (int32_t*)(h + s_qv) + (size_t)maxq * i;
-      for (int k = 0; k < nq; k++) { const int q = jobs[i].q[k]; qc[k] = (q == gauge || !live[q]) ? -1 : S.vperm[q]; qv[k] = q; }
-      CondJobDev& jd = ((CondJobDev*)(h + s_jd))[i];
-      jd.nq = nq; jd.gauge = gauge; jd.gauge_id = g->ids[gauge]; jd.out_slot = to_wire ? jobs[i].peer : i;
-    }
-    t_mask = wall_s() - tm0;
-    const double tu0 = wall_s();
-    char* h = hstage;
-    char* d0 = ctx->mg_arena.ptr;
-    char* ds = d0 + o_stage;                                     // device copy of the staging block
-    double* d_work0 = (double*)(ds + s_work);                    // the passes work on the poses where they landed
-    HIP_TRY(ctx, hipMemcpyAsync(ds, h, s_st, hipMemcpyHostToDevice, st));
-    {
-      CondPrepare P;
-      P.njobs = nj; P.nf = nf; P.maxq = maxq;
-      P.stage_mask = (const uint8_t*)ds; P.stage_qc = (const int32_t*)(ds + s_qc); P.stage_qv = (const int32_t*)(ds + s_qv);
-      P.cmask = DB.cmask; P.qc = (int32_t*)(d0 + o_qc); P.qv = (int32_t*)(d0 + o_qv); P.status = DB.status;
-      P.pan = DB.Pan; P.pan_doubles = DB.pan_doubles; P.Y = (double*)(d0 + o_Y); P.y_doubles = (long long)n * m_max;
-      P.rep_stride = DB.job_stride; P.marg_stride = (long long)per_job;
-      launch_cond_prepare(st, P);
-      DB.pan_clean = DB.pan_doubles > 0;                         // (gn_pass_on: no memset in front of the assembly)
-    }
-    t_up = wall_s() - tu0;
-    hipEvent_t evs[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (trace) for (auto& e : evs) (void)hipEventCreate(&e);
-    if (trace) (void)hipEventRecord(evs[0], st);
-    const double tp0 = wall_s();
-    GnPassOpts pass;
-    pass.write_l11c = true;
-    gn_pass_on(ctx, DB, st, d_work0, Ed, pass);
-    const double tp1 = wall_s();
-    t_gn = tp1 - tp0;
-    if (trace) (void)hipEventRecord(evs[1], st);
-    MargBatch MBt;
-    MBt.jobs = (const CondJobDev*)(ds + s_jd);
-    MBt.marg_stride = (long long)per_job;
-    double *est0, *info0;
-    if (to_wire) { est0 = g->d_est64; info0 = g->d_info64; MBt.est_stride = 24LL * cap; MBt.info_stride = 48LL * cap; MBt.wire_stride = (long long)sizeof(WireEdge) * cap; }
-    else { est0 = (double*)(d0 + o_e64); info0 = (double*)(d0 + o_i64); MBt.est_stride = MBt.info_stride = (long long)per_job; }
-    launch_marginals(st, DB, maxq, (const int32_t*)(d0 + o_qc), m_max, (double*)(d0 + o_Y), (double*)(d0 + o_U), (double*)(d0 + o_part),
-                     (double*)(d0 + o_G), (double*)(d0 + o_cov), chunk, nchunk, (uint8_t*)(d0 + o_live), &MBt, /*y_is_zero=*/true);
-    if (trace) (void)hipEventRecord(evs[2], st);
-    launch_label(st, maxq, (const int32_t*)(d0 + o_qv), 0, d_work0, (const double*)(d0 + o_cov), est0, info0, (int*)(d0 + o_fl), &DB, &MBt);
-    if (to_wire)
-      launch_wire_write_edges(st, maxq, 0, (const int32_t*)(d0 + o_qv), (const int32_t*)g->d_vids.ptr, est0, info0, send_edges, nj, &MBt);
-    if (trace) (void)hipEventRecord(evs[3], st);
-    HIP_TRY(ctx, hipMemcpy2DAsync(h + s_st, 16, DB.status, (size_t)DB.job_stride, 16, (size_t)nj, hipMemcpyDeviceToHost, st));
-    t_marg = wall_s() - tp1;
-    if (go_async) {
-      // not waited for: the status words are looked at by cond_finish(); a message packed before that gets its counts
-      // corrected on the device (cgmr_graph_pack)
-      HIP_TRY(ctx, hipEventRecord(g->ev_cond_done, st));
-      side_guard.armed = false;
-      rc = side_mark(ctx);
-      if (rc) return rc;
-      g->cond_pending = true;
-      g->cond_last_rc = 0;
-      g->cond_peers.clear();
-      for (CondJob& J : jobs) g->cond_peers.push_back(J.peer);
-      g->cond_status = (const int32_t*)(h + s_st);
-      g->cond_jobs_dev = (const CondJobDev*)(ds + s_jd);
-      g->cond_status_dev = DB.status;
-      g->cond_status_stride = DB.job_stride;
-      if (trace) {
-        for (auto& e : evs) if (e) (void)hipEventDestroy(e);
-        fprintf(stderr, "[cond] %d jobs queued on the side stream, nV %d nE %d: structure %.0f us, queueing %.0f us (work space %.0f, initial guesses %.0f, masks %.0f, uploads %.0f, GN pass %.0f, marginals + labels %.0f)\n",
-                nj, nV, nE, 1e6 * (tt1 - tt0), 1e6 * (wall_s() - tt1), 1e6 * (tt1b - tt1), 1e6 * t_guess, 1e6 * t_mask, 1e6 * t_up, 1e6 * t_gn, 1e6 * t_marg);
-      }
-      *async_out = true;
-      return 0;
-    }
-    if (info_out) info_out->assign(nj, {});
-    for (int i = 0; i < nj && info_out && !to_wire; i++) {
-      (*info_out)[i].resize(6 * jobs[i].q.size());
-      HIP_TRY(ctx, hipMemcpyAsync((*info_out)[i].data(), d0 + per_job * (size_t)i + o_i64, 48 * jobs[i].q.size(), hipMemcpyDeviceToHost, st));
-    }
-    const double tt2 = wall_s();
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    HIP_TRY(ctx, hipGetLastError());
-    bool timed_out = false;
-    for (int i = 0; i < nj; i++) { status[i] = ((const int32_t*)(h + s_st))[4 * i]; timed_out = timed_out || ((const int32_t*)(h + s_st))[4 * i + 2] != 0; }
-    if (trace) {
-      float a = 0, b = 0, c = 0;
-      (void)hipEventElapsedTime(&a, evs[0], evs[1]); (void)hipEventElapsedTime(&b, evs[1], evs[2]); (void)hipEventElapsedTime(&c, evs[2], evs[3]);
-      fprintf(stderr, "[cond]   device: GN pass %.0f us, marginals %.0f us (m %d, %d levels), labels + wire %.0f us\n", 1e3 * a, 1e3 * b, m_max, DB.nlevels_full, 1e3 * c);
-      for (auto& e : evs) (void)hipEventDestroy(e);
-    }
-    if (trace)
-      fprintf(stderr, "[cond] %d jobs in one batch, nV %d nE %d: structure %.0f us, queueing %.0f us (initial guesses %.0f, masks %.0f, uploads %.0f, GN pass %.0f, marginals + labels %.0f), waiting %.0f us\n",
-              nj, nV, nE, 1e6 * (tt1 - tt0), 1e6 * (tt2 - tt1), 1e6 * t_guess, 1e6 * t_mask, 1e6 * t_up, 1e6 * t_gn, 1e6 * t_marg, 1e6 * (wall_s() - tt2));
-    if (timed_out) { count_timeout(ctx); return gerr(g, CGMR_E_TIMEOUT, "a bounded device-side wait ran out while building a condensed graph"); }
-    for (int i = 0; i < nj; i++)
-      if (status[i] != 0) return gerr(g, CGMR_E_CHOLESKY_BASE, "Cholesky failed while building a condensed graph");
+    B.hstage = ctx->pinned_mask;
     return 0;
   }
-  rc = aux_streams(ctx, nstreams);
+  if (B.S.s_end > g->cond_pinned_cap) {
+    if (g->cond_pinned) {
+      int rc = side_join_host(ctx);
+      if (rc) return rc;
+      (void)hipHostFree(g->cond_pinned);
+      g->cond_pinned = nullptr; g->cond_pinned_cap = 0;
+    }
+    const size_t want = 2 * B.S.s_end + (64 << 10);              // (page-locking is slow: rarely)
+    HIP_TRY(ctx, hipHostMalloc((void**)&g->cond_pinned, want, hipHostMallocDefault));
+    g->cond_pinned_cap = want;
+  }
+  B.hstage = g->cond_pinned;
+  return 0;
+}
+
+// GraphManipulator::fixGauge + optimize(1) (graph_manipulator.cpp:62-124): only the gauge is fixed, spanning-tree initial
+// guess over my own edges with the gauge as the root (0.15-0.3 ms of host work each: on the helper threads); dst(i): where job
+// i's guess goes
+template <typename Dst>
+void cond_guesses(CondBatch& B, Dst&& dst) {
+  const cgmr_graph* g = B.g;
+  const int nV = B.nV, nA = B.nA;
+  const double tg0 = wall_s();
+  static const bool cached_walk = !(getenv("CGMR_GUESS_CACHED") && atoi(getenv("CGMR_GUESS_CACHED")) == 0);
+  host_run_tasks(B.nj, [&](int i) {
+    double* w = dst(i);
+    memcpy(w, g->h_poses.data(), (size_t)24 * nV);
+    if (cached_walk) {
+      thread_local std::vector<int32_t> queue;
+      thread_local std::vector<double> cs;
+      thread_local std::vector<uint8_t> seen;
+      initial_guess_own_edges(g, B.jobs[i].gauge, w, queue, cs, seen);
+    } else {
+      std::vector<uint8_t> fx(nV, 0);
+      fx[B.jobs[i].gauge] = 1;
+      initial_guess_host(nV, w, fx.data(), nA, g->ef.data(), g->et.data(), g->h_meas.data());
+    }
+  });
+  B.t_guess = wall_s() - tg0;
+}
+
+// The host's part of the batch, written straight into the staging block: every job's initial guess, column mask, query lists
+// and descriptor.
+void cond_fill_stage(CondBatch& B) {
+  const cgmr_graph* g = B.g;
+  const Symbolic& S = B.ctx->sym;
+  const int nV = B.nV, nA = B.nA, nf = B.nf, maxq = B.maxq;
+  char* h = B.hstage;
+  cond_guesses(B, [&](int i) { return (double*)(h + B.S.s_work + (size_t)24 * nV * i); });
+  const double tm0 = wall_s();
+  // the column masks: a vertex without an own edge is out of every job's system (the received edges are switched off);
+  // the jobs differ in their gauge only
+  std::vector<uint8_t> live(nV, 0);
+  for (int k = 0; k < nA; k++) { live[B.s_ef[k]] = 1; live[B.s_et[k]] = 1; }
+  std::vector<char> base(nf);
+  for (int c = 0; c < nf; c++) base[c] = live[S.perm[c]] ? 0 : 1;
+  for (int i = 0; i < B.nj; i++) {
+    const CondJob& J = B.jobs[i];
+    char* pm = h + (size_t)nf * i;
+    memcpy(pm, base.data(), (size_t)nf);
+    if (S.vperm[J.gauge] >= 0) pm[S.vperm[J.gauge]] = 1;
+    const int nq = (int)J.q.size();
+    int32_t* qc = (int32_t*)(h + B.S.s_qc) + (size_t)maxq * i;
+    int32_t* qv = (int32_t*)(h + B.S.s_qv) + (size_t)maxq * i;
+    for (int k = 0; k < nq; k++) { const int q = J.q[k]; qc[k] = (q == J.gauge || !live[q]) ? -1 : S.vperm[q]; qv[k] = q; }
+    CondJobDev& jd = ((CondJobDev*)(h + B.S.s_jd))[i];
+    jd.nq = nq; jd.gauge = J.gauge; jd.gauge_id = g->ids[J.gauge]; jd.out_slot = B.to_wire ? J.peer : i;
+  }
+  B.t_mask = wall_s() - tm0;
+}
+
+// The device's part, ONE sequence of launches with a job dimension (gn_kernels.hip CGMR_JOB) -- a stream of ~65 launches per
+// job side by side had the device dispatch the small kernels of 7 jobs at ~7 us apiece (3.9 ms for the condensed graphs of a
+// round with 8 robots): the staging block goes up, one Gauss-Newton pass, the marginals of that pass's Hessian, the labelled
+// edges (to_wire: double-precision copy in the peers' slots + 44-byte wire records in the send buffer; else in the jobs' work
+// spaces), the status words back into the staging block.
+int cond_queue(CondBatch& B) {
+  cgmr_graph* g = B.g;
+  cgmr_ctx* ctx = B.ctx;
+  hipStream_t st = B.st;
+  GnDevice& DB = B.DB;
+  const MargLayout& M = B.M;
+  const CondStage& S = B.S;
+  const int nj = B.nj, maxq = B.maxq, cap = g->cap;
+  char *d0 = B.d0, *ds = B.ds;
+  // the chained backward solve and the merged levels need their workgroups resident together: the batch takes nj times the slots
+  // (after a time-out -- two chained solves per context on eight contexts of one device make them likelier -- the batches of
+  // this graph solve level by level: no in-kernel waits, like gn_run's retry)
+  choose_bwd_chain(DB, (ctx->side_used ? 2 : 1) * nj, g->cond_levelwise);
+  choose_fwd_merge(DB, (ctx->side_used ? 2 : 1) * nj, g->cond_levelwise, ctx->fwd_merge_any);
+  const double tu0 = wall_s();
+  double* d_work0 = (double*)(ds + S.s_work);                    // the passes work on the poses where they landed
+  HIP_TRY(ctx, hipMemcpyAsync(ds, B.hstage, S.s_st, hipMemcpyHostToDevice, st));
+  CondPrepare P;
+  P.njobs = nj; P.nf = B.nf; P.maxq = maxq;
+  P.stage_mask = (const uint8_t*)ds; P.stage_qc = (const int32_t*)(ds + S.s_qc); P.stage_qv = (const int32_t*)(ds + S.s_qv);
+  P.cmask = DB.cmask; P.qc = (int32_t*)(d0 + M.o_qc); P.qv = (int32_t*)(d0 + M.o_qv); P.status = DB.status;
+  P.pan = DB.Pan; P.pan_doubles = DB.pan_doubles; P.Y = (double*)(d0 + M.o_Y); P.y_doubles = (long long)M.n * M.m;
+  P.rep_stride = DB.job_stride; P.marg_stride = (long long)B.per_job;
+  launch_cond_prepare(st, P);
+  DB.pan_clean = DB.pan_doubles > 0;                             // (gn_pass_on: no memset in front of the assembly)
+  B.t_up = wall_s() - tu0;
+  if (B.trace) for (auto& e : B.evs) (void)hipEventCreate(&e);
+  B.mark(0);
+  const double tp0 = wall_s();
+  GnPassOpts pass;
+  pass.write_l11c = true;
+  gn_pass_on(ctx, DB, st, d_work0, B.Ed, pass);
+  const double tp1 = wall_s();
+  B.t_gn = tp1 - tp0;
+  B.mark(1);
+  MargBatch MBt;
+  MBt.jobs = (const CondJobDev*)(ds + S.s_jd);
+  MBt.marg_stride = (long long)B.per_job;
+  double *est0, *info0;
+  if (B.to_wire) { est0 = g->d_est64; info0 = g->d_info64; MBt.est_stride = 24LL * cap; MBt.info_stride = 48LL * cap; MBt.wire_stride = (long long)sizeof(WireEdge) * cap; }
+  else { est0 = (double*)(d0 + M.o_est); info0 = (double*)(d0 + M.o_info); MBt.est_stride = MBt.info_stride = (long long)B.per_job; }
+  launch_marginals(st, DB, maxq, (const int32_t*)(d0 + M.o_qc), M.m, (double*)(d0 + M.o_Y), (double*)(d0 + M.o_U), (double*)(d0 + M.o_part),
+                   (double*)(d0 + M.o_G), (double*)(d0 + M.o_cov), M.chunk, M.nchunk, (uint8_t*)(d0 + M.o_live), &MBt, /*y_is_zero=*/true);
+  B.mark(2);
+  launch_label(st, maxq, (const int32_t*)(d0 + M.o_qv), 0, d_work0, (const double*)(d0 + M.o_cov), est0, info0, (int*)(d0 + M.o_fl), &DB, &MBt);
+  if (B.to_wire) {
+    WireEdge* send_edges = reinterpret_cast<WireEdge*>(g->d_send + wire_edges_off(g->n_robots));
+    launch_wire_write_edges(st, maxq, 0, (const int32_t*)(d0 + M.o_qv), (const int32_t*)g->d_vids.ptr, est0, info0, send_edges, nj, &MBt);
+  }
+  B.mark(3);
+  HIP_TRY(ctx, hipMemcpy2DAsync(B.hstage + S.s_st, 16, DB.status, (size_t)DB.job_stride, 16, (size_t)nj, hipMemcpyDeviceToHost, st));
+  B.t_marg = wall_s() - tp1;
+  return 0;
+}
+
+// Ending of a batch that is not waited for (ev_cond_done is recorded behind it): the status words are looked at by
+// cond_finish(); a message packed before that gets its counts corrected on the device (cgmr_graph_pack).
+void cond_hand_over(CondBatch& B) {
+  cgmr_graph* g = B.g;
+  g->cond_pending = true;
+  g->cond_last_rc = 0;
+  g->cond_peers.clear();
+  for (CondJob& J : B.jobs) g->cond_peers.push_back(J.peer);
+  g->cond_status = (const int32_t*)(B.hstage + B.S.s_st);
+  g->cond_jobs_dev = (const CondJobDev*)(B.ds + B.S.s_jd);
+  g->cond_status_dev = B.DB.status;
+  g->cond_status_stride = B.DB.job_stride;
+  if (B.trace)
+    fprintf(stderr, "[cond] %d jobs queued on the side stream, nV %d nE %d: structure %.0f us, queueing %.0f us (work space %.0f, initial guesses %.0f, masks %.0f, uploads %.0f, GN pass %.0f, marginals + labels %.0f)\n",
+            B.nj, B.nV, B.nE, 1e6 * B.t_structure, 1e6 * (wall_s() - B.t0 - B.t_structure), 1e6 * B.t_space, 1e6 * B.t_guess, 1e6 * B.t_mask, 1e6 * B.t_up, 1e6 * B.t_gn, 1e6 * B.t_marg);
+}
+
+// Ending of a waited batch: the information matrices of a gauge search (info_out[i], 6 doubles per edge) come back with the
+// status words.
+int cond_wait(CondBatch& B, std::vector<std::vector<double>>* info_out) {
+  cgmr_graph* g = B.g;
+  cgmr_ctx* ctx = B.ctx;
+  const int nj = B.nj;
+  if (info_out) info_out->assign(nj, {});
+  for (int i = 0; i < nj && info_out && !B.to_wire; i++) {
+    (*info_out)[i].resize(6 * B.jobs[i].q.size());
+    HIP_TRY(ctx, hipMemcpyAsync((*info_out)[i].data(), B.d0 + B.per_job * (size_t)i + B.M.o_info, 48 * B.jobs[i].q.size(), hipMemcpyDeviceToHost, B.st));
+  }
+  const double t2 = wall_s();
+  HIP_TRY(ctx, hipStreamSynchronize(B.st));
+  HIP_TRY(ctx, hipGetLastError());
+  const int32_t* status = (const int32_t*)(B.hstage + B.S.s_st);
+  bool failed = false, timed_out = false;
+  for (int i = 0; i < nj; i++) { failed = failed || status[4 * i] != 0; timed_out = timed_out || status[4 * i + 2] != 0; }
+  if (B.trace) {
+    float a = 0, b = 0, c = 0;
+    (void)hipEventElapsedTime(&a, B.evs[0], B.evs[1]); (void)hipEventElapsedTime(&b, B.evs[1], B.evs[2]); (void)hipEventElapsedTime(&c, B.evs[2], B.evs[3]);
+    fprintf(stderr, "[cond]   device: GN pass %.0f us, marginals %.0f us (m %d, %d levels), labels + wire %.0f us\n", 1e3 * a, 1e3 * b, B.M.m, B.DB.nlevels_full, 1e3 * c);
+    fprintf(stderr, "[cond] %d jobs in one batch, nV %d nE %d: structure %.0f us, queueing %.0f us (initial guesses %.0f, masks %.0f, uploads %.0f, GN pass %.0f, marginals + labels %.0f), waiting %.0f us\n",
+            nj, B.nV, B.nE, 1e6 * B.t_structure, 1e6 * (t2 - B.t0 - B.t_structure), 1e6 * B.t_guess, 1e6 * B.t_mask, 1e6 * B.t_up, 1e6 * B.t_gn, 1e6 * B.t_marg, 1e6 * (wall_s() - t2));
+  }
+  if (timed_out) { count_timeout(ctx); return gerr(g, CGMR_E_TIMEOUT, "a bounded device-side wait ran out while building a condensed graph"); }
+  if (failed) return gerr(g, CGMR_E_CHOLESKY_BASE, "Cholesky failed while building a condensed graph");
+  return 0;
+}
+
+// CGMR_COND_BATCH=0 (and the formal case of a structure without a free column): every job as its own stream of ~65 launches on
+// its replica of the numeric work space, side by side on the context's aux streams, as before the batch.  Always waited for.
+int cond_streams(CondBatch& B, std::vector<std::vector<double>>* info_out) {
+  cgmr_graph* g = B.g;
+  cgmr_ctx* ctx = B.ctx;
+  hipStream_t st = B.st;
+  const MargLayout& M = B.M;
+  const Symbolic& S = ctx->sym;
+  const int nV = B.nV, nj = B.nj, cap = g->cap, nstreams = std::min(nj, 8);
+  int rc = aux_streams(ctx, nstreams);
   if (rc) return rc;
   rc = dev_grow(g, g->d_work, 0, 24 * (size_t)nV * nj);       // (the passes on streams work on uploaded copies of the poses)
   if (rc) return rc;
-  run_guesses([&](int i) { works[i].resize(3 * (size_t)nV); return works[i].data(); });
+  std::vector<std::vector<double>> works(nj);
+  cond_guesses(B, [&](int i) { works[i].resize(3 * (size_t)nV); return works[i].data(); });
+  std::vector<uint8_t> fixed(nV);
+  std::vector<int32_t> qcol, status(nj, 0);
+  WireEdge* send_edges = reinterpret_cast<WireEdge*>(g->d_send + wire_edges_off(g->n_robots));
   HIP_TRY(ctx, hipEventRecord(ctx->aux_fork, st));
   for (int k = 0; k < nstreams; k++) HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux[k], ctx->aux_fork, 0));
   for (int i = 0; i < nj; i++) {
-    CondJob& J = jobs[i];
+    CondJob& J = B.jobs[i];
     hipStream_t sj = ctx->aux[i % nstreams];
-    GnDevice& D = reps[i];
-    char* d = ctx->mg_arena.ptr + per_job * (size_t)i;
+    GnDevice& D = B.reps[i];
+    char* d = B.d0 + B.per_job * (size_t)i;
     const int nq = (int)J.q.size();
-    // GraphManipulator::fixGauge + optimize(1) (graph_manipulator.cpp:62-124): only the gauge is fixed, spanning-tree
-    // initial guess over my own edges, one Gauss-Newton iteration; the marginals are those of that iteration's Hessian
     std::fill(fixed.begin(), fixed.end(), 0);
     fixed[J.gauge] = 1;
-    const std::vector<double>& work = works[i];
     double* d_work = (double*)(g->d_work.ptr + 24 * (size_t)nV * i);
     const double tu0 = wall_s();
-    HIP_TRY(ctx, hipMemcpyAsync(d_work, work.data(), 24 * (size_t)nV, hipMemcpyHostToDevice, sj));
-    t_up += wall_s() - tu0;
+    HIP_TRY(ctx, hipMemcpyAsync(d_work, works[i].data(), 24 * (size_t)nV, hipMemcpyHostToDevice, sj));
+    B.t_up += wall_s() - tu0;
     const double tm0 = wall_s();
-    rc = prepare_pass_on(ctx, D, sj, fixed.data(), nE, s_ef.data(), s_et.data(), nA, i, nj);
+    rc = prepare_pass_on(ctx, D, sj, fixed.data(), B.nE, B.s_ef, B.s_et, B.nA, i, nj);
     if (rc) return rc;
-    t_mask += wall_s() - tm0;
+    B.t_mask += wall_s() - tm0;
     qcol.resize(nq);
     for (int k = 0; k < nq; k++) qcol[k] = ctx->vmask[J.q[k]] ? -1 : S.vperm[J.q[k]];
-    int32_t* d_qc = (int32_t*)(d + o_qc);
-    int32_t* d_qv = (int32_t*)(d + o_qv);
+    int32_t* d_qc = (int32_t*)(d + M.o_qc);
+    int32_t* d_qv = (int32_t*)(d + M.o_qv);
     HIP_TRY(ctx, hipMemcpyAsync(d_qc, qcol.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, sj));
     HIP_TRY(ctx, hipMemcpyAsync(d_qv, J.q.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, sj));
     const double tp0 = wall_s();
     GnPassOpts pass;
     pass.write_l11c = true;
-    gn_pass_on(ctx, D, sj, d_work, Ed, pass);
+    gn_pass_on(ctx, D, sj, d_work, B.Ed, pass);
     const double tp1 = wall_s();
-    t_gn += tp1 - tp0;
+    B.t_gn += tp1 - tp0;
     const int m = ((4 * nq + 15) / 16) * 16;
-    launch_marginals(sj, D, nq, d_qc, m, (double*)(d + o_Y), (double*)(d + o_U), (double*)(d + o_part), (double*)(d + o_G),
-                     (double*)(d + o_cov), chunk, nchunk, (uint8_t*)(d + o_live));
-    double* est64 = to_wire ? g->d_est64 + 3 * (size_t)cap * J.peer : (double*)(d + o_e64);
-    double* info64 = to_wire ? g->d_info64 + 6 * (size_t)cap * J.peer : (double*)(d + o_i64);
-    launch_label(sj, nq, d_qv, J.gauge, d_work, (const double*)(d + o_cov), est64, info64, (int*)(d + o_fl));
-    if (to_wire)
+    launch_marginals(sj, D, nq, d_qc, m, (double*)(d + M.o_Y), (double*)(d + M.o_U), (double*)(d + M.o_part), (double*)(d + M.o_G),
+                     (double*)(d + M.o_cov), M.chunk, M.nchunk, (uint8_t*)(d + M.o_live));
+    double* est64 = B.to_wire ? g->d_est64 + 3 * (size_t)cap * J.peer : (double*)(d + M.o_est);
+    double* info64 = B.to_wire ? g->d_info64 + 6 * (size_t)cap * J.peer : (double*)(d + M.o_info);
+    launch_label(sj, nq, d_qv, J.gauge, d_work, (const double*)(d + M.o_cov), est64, info64, (int*)(d + M.o_fl));
+    if (B.to_wire)
       launch_wire_write_edges(sj, nq, g->ids[J.gauge], d_qv, (const int32_t*)g->d_vids.ptr, est64, info64,
                               send_edges + (size_t)cap * J.peer);
-    HIP_TRY(ctx, hipMemcpyAsync(d + o_st, D.status, 4, hipMemcpyDeviceToDevice, sj));
-    t_marg += wall_s() - tp1;
+    HIP_TRY(ctx, hipMemcpyAsync(d + M.o_st, D.status, 4, hipMemcpyDeviceToDevice, sj));
+    B.t_marg += wall_s() - tp1;
   }
   for (int k = 0; k < nstreams; k++) {
     HIP_TRY(ctx, hipEventRecord(ctx->aux_done[k], ctx->aux[k]));
@@ -1066,21 +1087,81 @@ int run_cond_jobs(cgmr_graph* g, std::vector<CondJob>& jobs, bool to_wire, std::
   }
   if (info_out) info_out->assign(nj, {});
   for (int i = 0; i < nj; i++) {
-    char* d = ctx->mg_arena.ptr + per_job * (size_t)i;
-    HIP_TRY(ctx, hipMemcpyAsync(&status[i], d + o_st, 4, hipMemcpyDeviceToHost, st));
-    if (info_out && !to_wire) {
-      (*info_out)[i].resize(6 * jobs[i].q.size());
-      HIP_TRY(ctx, hipMemcpyAsync((*info_out)[i].data(), d + o_i64, 48 * jobs[i].q.size(), hipMemcpyDeviceToHost, st));
+    char* d = B.d0 + B.per_job * (size_t)i;
+    HIP_TRY(ctx, hipMemcpyAsync(&status[i], d + M.o_st, 4, hipMemcpyDeviceToHost, st));
+    if (info_out && !B.to_wire) {
+      (*info_out)[i].resize(6 * B.jobs[i].q.size());
+      HIP_TRY(ctx, hipMemcpyAsync((*info_out)[i].data(), d + M.o_info, 48 * B.jobs[i].q.size(), hipMemcpyDeviceToHost, st));
     }
   }
-  const double tt2 = wall_s();
+  const double t2 = wall_s();
   HIP_TRY(ctx, hipStreamSynchronize(st));
   HIP_TRY(ctx, hipGetLastError());
-  if (trace)
+  if (B.trace)
     fprintf(stderr, "[cond] %d jobs, nV %d nE %d: structure %.0f us, queueing %.0f us (initial guesses %.0f, masks %.0f, pose upload %.0f, GN pass %.0f, marginals + labels %.0f), waiting %.0f us\n", nj, nV,
-            nE, 1e6 * (tt1 - tt0), 1e6 * (tt2 - tt1), 1e6 * t_guess, 1e6 * t_mask, 1e6 * t_up, 1e6 * t_gn, 1e6 * t_marg, 1e6 * (wall_s() - tt2));
+            B.nE, 1e6 * B.t_structure, 1e6 * (t2 - B.t0 - B.t_structure), 1e6 * B.t_guess, 1e6 * B.t_mask, 1e6 * B.t_up, 1e6 * B.t_gn, 1e6 * B.t_marg, 1e6 * (wall_s() - t2));
   for (int i = 0; i < nj; i++)
     if (status[i] != 0) return gerr(g, CGMR_E_CHOLESKY_BASE, "Cholesky failed while building a condensed graph");
+  return 0;
+}
+
+// CondensedGraphCreator::compute (condensed_graph_creator.cpp:33-66) for a batch of (gauge, vertex set) jobs on the
+// robot's own edges: ONE sequence of launches with a job dimension (a single job is a batch of one); CGMR_COND_BATCH=0: a
+// stream of launches per job.
+// to_wire: the labelled edges go to the peer's slots (double-precision copy + 44-byte wire records in the send
+// buffer); otherwise only the information matrices come back (info_out[i], 6 doubles per edge: gauge search).
+// async_out (nullable): on entry true = queue the batch on the context's side stream and return without waiting (the
+// caller finishes it later: cond_finish); set to false when the batch could not be queued that way and was waited for.
+int run_cond_jobs(cgmr_graph* g, std::vector<CondJob>& jobs, bool to_wire, std::vector<std::vector<double>>* info_out,
+                  bool* async_out = nullptr) {
+  cgmr_ctx* ctx = g->ctx;
+  bool go_async = async_out && *async_out && to_wire && !info_out;
+  if (async_out) *async_out = false;
+  if (jobs.empty()) return 0;
+  CondBatch B(g, jobs, to_wire);
+  static const bool trace = getenv("CGMR_COND_TRACE") != nullptr;
+  B.trace = trace;
+  B.t0 = wall_s();
+  int rc = cond_setup(B);
+  if (rc) return rc;
+  static const bool batch_on = !(getenv("CGMR_COND_BATCH") && atoi(getenv("CGMR_COND_BATCH")) == 0);
+  const bool batched = batch_on && B.nf > 0;
+  go_async = go_async && batched;     // (only the batch runs on the side stream)
+  // whatever ran on the side stream before (another graph of this context, this graph's previous batch) used the work spaces
+  // this batch is about to fill
+  // (work queued on the side stream behind the fork is marked -- side_busy, side_tail -- even when this function leaves on an error:
+  // the next join then waits for it instead of skipping it)
+  struct SideGuard {
+    cgmr_ctx* c; bool armed;
+    ~SideGuard() { if (armed) (void)side_mark(c); }
+  } side_guard{ctx, false};
+  B.st = ctx->stream;
+  if (go_async) {
+    rc = side_fork(ctx);
+    if (rc) return rc;
+    side_guard.armed = true;
+    B.st = ctx->side;
+    rc = wait_consumers(g, B.st);
+    if (rc) return rc;
+  } else {
+    rc = side_join_stream(ctx, B.st);
+    if (rc) return rc;
+    rc = wait_consumers(g, B.st);
+    if (rc) return rc;
+  }
+  if (!batched) return cond_streams(B, info_out);
+  rc = cond_stage_block(B, go_async);
+  if (rc) return rc;
+  cond_fill_stage(B);
+  rc = cond_queue(B);
+  if (rc) return rc;
+  if (!go_async) return cond_wait(B, info_out);
+  HIP_TRY(ctx, hipEventRecord(g->ev_cond_done, B.st));
+  side_guard.armed = false;
+  rc = side_mark(ctx);
+  if (rc) return rc;
+  cond_hand_over(B);
+  *async_out = true;
   return 0;
 }
 
@@ -1104,8 +1185,8 @@ extern "C" {
 // peer < 0, for every peer that has asked for vertices: gauge = selectGaugeCentroid (:318-345) -- or, after
 // cgmr_graph_set_optimal_gauge(g, 1), selectOptimalGauge (:252-288: the candidate whose star has the smallest overall
 // uncertainty, every candidate's condensed graph being built for that) --, edges = getMyEdges (own edges only),
-// CondensedGraphCreator::compute per peer.  The passes of all peers (and of the gauge candidates) are queued on side
-// streams back to back; the labelled edges land in the send buffer as wire records.  Returns the number of peers built.
+// CondensedGraphCreator::compute per peer.  The passes of all peers (and of eight gauge candidates at a time) run as
+// one batch; the labelled edges land in the send buffer as wire records.  Returns the number of peers built.
 }  // extern "C"
 
 namespace {

@@ -38,7 +38,9 @@ def _p(a):
 class RobotGraph:
     """``cgmr_graph``: the g2o optimiser of one robot plus its ``CondensedGraphBuffer``."""
 
-    #: edges (and closure ids) per peer a reference message holds: MAX_LENGTH_MSG = 100000 bytes of 44-byte edges (msg_factory.h:115)
+    #: edges per peer a reference message can hold: MAX_LENGTH_MSG = 100000 bytes of 44-byte edges (msg_factory.h:115).  It is
+    #: the capacity of a slice (of edges, and of closure ids), not a promise that a full slice of both fits one message:
+    #: 2270 edges leave room for 24 closure ids.  ``message_for`` applies the byte limit itself.
     REFERENCE_CAP_EDGES = 2270
 
     def __init__(self, ctx: Context | None, robot: int, n_robots: int, base_id: int = 10000, cap_edges: int = 128,
@@ -282,7 +284,9 @@ class RobotGraph:
         return n
 
     def message_for(self, peer):
-        """``constructCondensedGraphMessage(peer)``: a ``messages.CondensedGraphMessage`` or None (nothing to send)."""
+        """``constructCondensedGraphMessage(peer)``: a ``messages.CondensedGraphMessage`` or None (nothing to send).  A message
+        beyond the slice capacity or beyond ``MAX_LENGTH_MSG`` bytes is not sent: None, and one more ``skipped_messages()`` --
+        what comes back always has a ``to_bytes()``."""
         from .messages import EDGE_DTYPE, CondensedGraphMessage
         cap = self.cap
         edges, clos = np.empty(cap, dtype=EDGE_DTYPE), np.empty(cap, dtype=np.int32)
@@ -308,6 +312,14 @@ class RobotGraph:
         n = self._check(self.lib.cgmr_graph_received_edges(self.h, C.c_int(peer), C.c_int(n), _p(f), _p(t), _p(m), _p(i)))
         return f[:n].astype(np.int64), t[:n].astype(np.int64), m[:n], i[:n]
 
+    def debug_received_segment(self):
+        """Test support: (meas[n,3], info[n,6]) of the received edges as the solver reads them (the compact second edge segment),
+        peer order; ``received_edges`` reads the staging."""
+        n = self._check(self.lib.cgmr_graph_debug_received_segment(self.h, C.c_int(0), None, None))
+        m, i = np.zeros((n, 3)), np.zeros((n, 6))
+        self._check(self.lib.cgmr_graph_debug_received_segment(self.h, C.c_int(n), _p(m), _p(i)))
+        return m, i
+
     def counts_received(self, peer):
         """Edges currently held from ``peer`` (no data moved)."""
         return int(self._check(self.lib.cgmr_graph_received_edges(self.h, C.c_int(peer), C.c_int(0), None, None, None, None)))
@@ -316,6 +328,31 @@ class RobotGraph:
         out = np.zeros(2)
         self._check(self.lib.cgmr_graph_last_seconds(self.h, _p(out)))
         return {"optimize": float(out[0]), "condense": float(out[1])}
+
+
+def wire_narrow_edges(ctx: Context, from_id, to_vertex, vertex_ids, est, info):
+    """Test support (``cgmr_wire_narrow_edges``): the device's double -> float32 wire records of host data, [n] WIRE_EDGE_DTYPE."""
+    to, ids, e, i = _i32(to_vertex), _i32(vertex_ids), _f64(est).reshape(-1, 3), _f64(info).reshape(-1, 6)
+    out = np.zeros(len(to), dtype=WIRE_EDGE_DTYPE)
+    ctx._check(ctx.lib.cgmr_wire_narrow_edges(ctx.h, C.c_int(len(to)), C.c_int32(int(from_id)), _p(to), C.c_int(len(ids)), _p(ids), _p(e),
+                                              _p(i), _p(out)))
+    return out
+
+
+def wire_narrow_edges_batched(ctx: Context, nq, gauge_id, out_slot, strides, to_vertex, vertex_ids, est, info, wire):
+    """Test support (``cgmr_wire_narrow_edges_batched``): one batched launch.  ``strides`` = (marg, est, info, wire) in bytes;
+    ``to_vertex`` / ``est`` / ``info`` / ``wire`` are uint8 buffers laid out by those strides (include/cgmr.h); returns the wire
+    buffer as the device left it."""
+    nq, gid, slot, ids = _i32(nq), _i32(gauge_id), _i32(out_slot), _i32(vertex_ids)
+    bufs = [np.ascontiguousarray(b, dtype=np.uint8).reshape(-1) for b in (to_vertex, est, info, wire)]
+    n_slots = len(bufs[3]) // int(strides[3])
+    if len(bufs[0]) != len(nq) * strides[0] or any(len(b) != n_slots * s for b, s in zip(bufs[1:], strides[1:])):
+        raise ValueError("buffers must hold njobs * marg_stride and n_slots * stride bytes")
+    out = bufs[3].copy()
+    ctx._check(ctx.lib.cgmr_wire_narrow_edges_batched(ctx.h, C.c_int(len(nq)), _p(nq), _p(gid), _p(slot), C.c_int(n_slots),
+                                                      *(C.c_longlong(int(s)) for s in strides), _p(bufs[0]), C.c_int(len(ids)), _p(ids),
+                                                      _p(bufs[1]), _p(bufs[2]), _p(out)))
+    return out
 
 
 def unpack_wire(buf: np.ndarray, n_robots: int, cap: int):

@@ -17,6 +17,13 @@ struct WireEdge {
 };
 static_assert(sizeof(WireEdge) == 44, "wire edge must be 44 bytes");
 
+// One CondensedGraphMessage as the reference serialises it (msg_factory.cpp:256-262): int32 type and robot, a size_t counter
+// and 44 bytes per edge, a size_t counter and 4 bytes per closure id; one datagram holds MAX_LENGTH_MSG bytes (msg_factory.h:115)
+constexpr size_t kMaxLengthMsg = 100000;
+inline size_t condensed_message_bytes(int n_edges, int n_closures) {
+  return 8 + 8 + sizeof(WireEdge) * (size_t)n_edges + 8 + 4 * (size_t)n_closures;
+}
+
 // One rank's buffer: int32 header {robot, n_robots, n_edges[R], n_closures[R]}, WireEdge edges[R][cap] (slice p = the
 // edges for peer p), int32 closures[R][cap] (slice p = the ids this robot requests from p).
 inline size_t wire_bytes(int n_robots, int cap) {

@@ -17,6 +17,20 @@ a robot running this package can therefore talk to a robot running the reference
 
 Only the two messages ``GraphComm::sendToThrd`` actually sends are implemented (graph_comm.cpp:126-155): ComboMessage
 and CondensedGraphMessage.  Host bookkeeping only -- no numerics.
+
+The layout and the narrowing are pinned to the reference's own compiled serialiser: tests/golden/msg_ref.npz holds what
+``toCharArray`` wrote and ``MessageFactory::fromCharArray`` read back for every type, with the values where a double ->
+float conversion can go wrong (oracle/ref_msg_main.cpp, tools/make_ref_msg_golden.py, tests/test_reference_messages_cpu.py).
+
+The size limit -- one deliberate deviation.  ``to_bytes()`` returns None (nothing is sent) when the WHOLE message exceeds
+``MAX_LENGTH_MSG``.  The reference checks less: the two combined messages hand the full ``bsize`` to each of their parts
+instead of what is left (msg_factory.cpp:146-152, 256-262), so ``toCharArray(buf, MAX_LENGTH_MSG)`` returns null only when
+the header with the first part, or the second part on its own, exceeds the limit -- and otherwise writes up to 199 984
+bytes (2272 edges + 24 998 closure ids) into ``GraphComm``'s ``char bufferc[MAX_LENGTH_MSG]`` (graph_comm.cpp:112), past
+its end.  That is a bug not to be copied.  Hence: up to ``MAX_LENGTH_MSG`` bytes this package writes what the reference
+writes; where the reference returns null so does this package; in between, where the reference overruns its buffer, this
+package sends nothing.  ``serialize()`` is the byte string without the limit (the tests compare it with the reference's
+over-long output).
 """
 from __future__ import annotations
 
@@ -62,11 +76,14 @@ class ComboMessage:
         self.minangle, self.angleincrement = np.float32(minangle), np.float32(angleincrement)
         self.maxrange, self.accuracy = np.float32(maxrange), np.float32(accuracy)
 
-    def to_bytes(self) -> bytes | None:
+    def serialize(self) -> bytes:
         b = struct.pack("<ii", self.type, self.robotId) + _counted(self.vertices)
         b += struct.pack("<i", self.nodeId) + _counted(self.readings)
-        b += struct.pack("<ffff", self.minangle, self.angleincrement, self.maxrange, self.accuracy)
-        return b if len(b) <= MAX_LENGTH_MSG else None          # toCharArray returns 0: nothing is sent
+        return b + struct.pack("<ffff", self.minangle, self.angleincrement, self.maxrange, self.accuracy)
+
+    def to_bytes(self) -> bytes | None:
+        b = self.serialize()
+        return b if len(b) <= MAX_LENGTH_MSG else None          # nothing is sent (the size limit, module docstring)
 
     @classmethod
     def from_bytes(cls, buf: bytes) -> "ComboMessage":
@@ -103,9 +120,12 @@ class CondensedGraphMessage:
             e["info"] = np.asarray(info, dtype=np.float64).reshape(-1, 6)
         return cls(robotId, e, closures)
 
+    def serialize(self) -> bytes:
+        return struct.pack("<ii", self.type, self.robotId) + _counted(self.edges) + _counted(self.closures)
+
     def to_bytes(self) -> bytes | None:
-        b = struct.pack("<ii", self.type, self.robotId) + _counted(self.edges) + _counted(self.closures)
-        return b if len(b) <= MAX_LENGTH_MSG else None
+        b = self.serialize()
+        return b if len(b) <= MAX_LENGTH_MSG else None          # nothing is sent (the size limit, module docstring)
 
     @classmethod
     def from_bytes(cls, buf: bytes) -> "CondensedGraphMessage":

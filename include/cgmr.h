@@ -712,7 +712,9 @@ int cgmr_graph_pack_host(cgmr_graph* g, void* send_out);
 int cgmr_graph_ingest_host(cgmr_graph* g, const void* recv, int32_t* n_edges_out);
 /* One peer's share of the round message as the reference's CondensedGraphMessage carries it
  * (MRGraphSLAM::constructCondensedGraphMessage, src/mrslam/mr_graph_slam.cpp:607-670): edges44_out receives
- * {int32 from, to; float est[3]; float info[6]} records.  Returns 1 = there is a message, 0 = nothing to send, < 0 error. */
+ * {int32 from, to; float est[3]; float info[6]} records.  Returns 1 = there is a message, 0 = nothing to send, < 0 error.
+ * A message beyond cap_edges_per_peer, or whose byte string (24 + 44 * edges + 4 * closure ids) would exceed the
+ * reference's MAX_LENGTH_MSG = 100000, is not sent: 0 with both counts 0, and one more cgmr_graph_skipped_messages. */
 int cgmr_graph_message_for(cgmr_graph* g, int peer, int cap_edges, void* edges44_out, int32_t* n_edges_out, int cap_closures,
                            int32_t* closure_ids_out, int32_t* n_closures_out);
 /* MRGraphSLAM::addInterRobotData(CondensedGraphMessage*) (src/mrslam/mr_graph_slam.cpp:331-395) for one message from
@@ -722,6 +724,27 @@ int cgmr_graph_message_from(cgmr_graph* g, int sender, int n_edges, const void* 
 /* the edges currently held from `peer`: returns their count; outputs nullable */
 int cgmr_graph_received_edges(cgmr_graph* g, int peer, int cap, int32_t* from_ids_out, int32_t* to_ids_out, double* meas_out,
                               double* info_upper_out);
+/* Test support, in the manner of cgmr_graph_debug_edges.
+ * cgmr_graph_debug_received_segment: the numbers of the received edges as the SOLVER reads them -- the compact second edge
+ * segment the ingest kernels fill, peer order (the order of cgmr_graph_debug_edges behind the own edges); meas_out [cap * 3],
+ * info_upper_out [cap * 6], both nullable; returns the number of received edges.  (cgmr_graph_received_edges reads the staging.)
+ * cgmr_wire_narrow_edges: the kernel that writes a condensed graph's 44-byte wire records (double -> float32, the ids
+ * vertex_ids[to_vertex[k]]), run on host arrays: to_vertex [n] indices into vertex_ids [n_vertices], est [n * 3],
+ * info_upper [n * 6]; edges44_out receives n records.  The solver never hands that kernel a float32 subnormal, a tie or an
+ * overflow; this is the way in for them.
+ * cgmr_wire_narrow_edges_batched: the same kernel as a batch of condensed-graph passes launches it, once for njobs jobs: job j
+ * has nq[j] edges and the gauge id gauge_id[j], reads its vertex indices at to_vertex + j * marg_stride bytes and -- by its
+ * output slot -- est / info_upper at out_slot[j] * est_stride / info_stride bytes, and writes its records at
+ * wire_inout + out_slot[j] * wire_stride bytes.  to_vertex holds njobs * marg_stride bytes; est, info_upper and wire_inout
+ * hold n_slots strides each.  wire_inout goes to the device as it is and comes back whole, so bytes the kernel must not
+ * touch keep the caller's value.  Every index and stride is checked on the host (CGMR_E_INVALID). */
+int cgmr_graph_debug_received_segment(cgmr_graph* g, int cap, double* meas_out, double* info_upper_out);
+int cgmr_wire_narrow_edges(cgmr_ctx* ctx, int n, int32_t from_id, const int32_t* to_vertex, int n_vertices, const int32_t* vertex_ids,
+                           const double* est, const double* info_upper, void* edges44_out);
+int cgmr_wire_narrow_edges_batched(cgmr_ctx* ctx, int njobs, const int32_t* nq, const int32_t* gauge_id, const int32_t* out_slot,
+                                   int n_slots, long long marg_stride, long long est_stride, long long info_stride,
+                                   long long wire_stride, const void* to_vertex, int n_vertices, const int32_t* vertex_ids,
+                                   const void* est, const void* info_upper, void* wire_inout);
 /* wall seconds of the last cgmr_graph_optimize / cgmr_graph_compute_condensed */
 int cgmr_graph_last_seconds(const cgmr_graph* g, double out[2]);
 

@@ -120,6 +120,21 @@ def test_three_robot_rounds_match_oracle_backend(ctx, oracle):
     assert pairs >= 4                                       # most ordered pairs exchanged condensed graphs
 
 
+def _world_sha256(R):
+    """Digest of what a multi-robot world feeds the rounds, in a fixed order: per robot its ids, initial poses, edge end
+    points, measurements and information (own edges, then the inter-robot closures), then the closure lists by peer."""
+    import hashlib
+    h = hashlib.sha256()
+    for g in R:
+        for key, dt in (("ids", "<i4"), ("poses_all", "<f8"), ("ef_all", "<i4"), ("et_all", "<i4"), ("meas_all", "<f8"),
+                        ("info_all", "<f8")):
+            h.update(np.ascontiguousarray(g[key], dtype=dt).tobytes())
+        for key in ("in_closures", "out_closures"):
+            for q in sorted(g[key]):
+                h.update(np.int32(q).tobytes() + np.ascontiguousarray(g[key][q], dtype="<i4").tobytes())
+    return h.hexdigest()
+
+
 _BATCH_CHILD = r"""
 import sys, numpy as np
 sys.path.insert(0, 'tests')
@@ -141,9 +156,12 @@ for r in range(nr):
             gid, to, est, iu = rounds[r].g.condensed(q)
             out['to%d_%d' % (r, q)] = np.asarray(to); out['est%d_%d' % (r, q)] = np.asarray(est); out['iu%d_%d' % (r, q)] = np.asarray(iu)
 out['built'] = np.array([b for (_, b, _) in log], dtype=np.int64)
+out['world_sha256'] = np.array(T._world_sha256(R))
 np.savez(sys.argv[1], **out)
 print('rounds ok')
 """
+
+COND_STREAMS_GOLDEN = os.path.join(ROOT, "tests", "golden", "cond_streams_r4x6.npz")   # (tools/make_cond_streams_golden.py writes it)
 
 
 def test_condensed_graphs_as_one_batch_equal_the_passes_on_streams(tmp_path):
@@ -160,6 +178,7 @@ def test_condensed_graphs_as_one_batch_equal_the_passes_on_streams(tmp_path):
         assert r.returncode == 0 and "rounds ok" in r.stdout, r.stderr[-2000:]
         res[mode] = dict(np.load(path))
     a, b = res["1"], res["0"]
+    assert str(a.pop("world_sha256")) == str(b.pop("world_sha256"))     # (both children made the same world)
     assert sorted(a) == sorted(b) and np.array_equal(a["built"], b["built"]) and a["built"].sum() > 10
     n_edges = 0
     for k in a:

@@ -27,9 +27,9 @@ namespace cgmr {
 // (the kernels carry their names into the profiles: rocprofv3 prints an empty name for a kernel of an anonymous namespace)
 constexpr int kLongList = 16;
 
-// the three keys of edge k: a = diagonal block of `from`, b = of `to` (-1: a self edge counts once), e = nf + index of the
-// lower off-diagonal block (max(a, b), min(a, b)) (-1: an end point has no column, or a self edge); code of e: 2 = Hij as
-// it is (row a, column b), 3 = transposed -- gn_symbolic.cpp, "assembly lists"
+// the three keys of edge k: a = diagonal block of `from`, b = of `to`, e = nf + index of the lower off-diagonal block
+// (max(a, b), min(a, b)) (-1: an end point has no column); code of e: 2 = Hij as it is (row a, column b), 3 = transposed.
+// A self edge has no key at all: its term (Ji + Jj)^T Omega (Ji + Jj) is exactly zero -- gn_symbolic.cpp, "assembly lists"
 __device__ __forceinline__ void edge_keys(int k, int nf, const int32_t* __restrict__ vperm, const int32_t* __restrict__ ef,
                                           const int32_t* __restrict__ et, int& a, int& b) {
   a = vperm[ef[k]];
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void k_asm_count(int nE, int nf, const int32_t
     e = nf + q;
   }
   ekey[k] = e;
-  if (a >= 0) atomicAdd(&cnt[a], 1);
+  if (a >= 0 && a != b) atomicAdd(&cnt[a], 1);
   if (b >= 0 && b != a) atomicAdd(&cnt[b], 1);
   if (e >= 0) atomicAdd(&cnt[e], 1);
 }
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void k_asm_file(int nE, int nf, const int32_t*
   int a, b;
   edge_keys(k, nf, vperm, ef, et, a, b);
   const int e = ekey[k];
-  if (a >= 0) src[atomicAdd(&cur[a], 1)] = 4 * k + 0;
+  if (a >= 0 && a != b) src[atomicAdd(&cur[a], 1)] = 4 * k + 0;
   if (b >= 0 && b != a) src[atomicAdd(&cur[b], 1)] = 4 * k + 1;
   if (e >= 0) src[atomicAdd(&cur[e], 1)] = 4 * k + (a > b ? 2 : 3);
 }

@@ -1349,8 +1349,10 @@ int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32
   parallel_for(nE, NT, [&](int lo, int hi) {
     for (int k = lo; k < hi; k++) {
       int a = S.vperm[ef[k]], b = S.vperm[et[k]];
-      e_a[k] = a;
-      e_b[k] = (b >= 0 && a == b) ? -1 : b;              // self edge: one diagonal contribution only
+      // self edge: the chain rule's term, (Ji + Jj)^T Omega (Ji + Jj) on the one block -- Ji + Jj is exactly zero (the error
+      // z^-1 (xi^-1 xi) does not depend on xi), so the edge adds to chi2 and to no list (include/cgmr.h, cgmr_gn_optimize)
+      e_a[k] = (a >= 0 && a == b) ? -1 : a;
+      e_b[k] = (b >= 0 && a == b) ? -1 : b;
       if (a >= 0 && b >= 0 && a != b) e_off[k] = nf + (a > b ? off_id(a, b) : off_id(b, a));
     }
   });

@@ -73,7 +73,12 @@ int cgmr_ctx_synchronize(cgmr_ctx* ctx);
  * Host-pointer variant: copies in, runs on the GPU, copies poses and chi2 back.
  * Limit: a front of the elimination tree may have at most 10 890 border poses (16-bit row maps in LDS); a graph
  * whose nested-dissection separators are wider is rejected with CGMR_E_INVALID (none of the BASELINE.json
- * configurations comes near: C2 has 74, a 100k-vertex / 300k-edge graph about 800).              */
+ * configurations comes near: C2 has 74, a 100k-vertex / 300k-edge graph about 800).
+ * An edge from a vertex to itself (from_idx[k] == to_idx[k]) is accepted and is the chain rule's term: its error is
+ * z^-1 (xi^-1 xi), its one Jacobian Ji + Jj, so H_ii += (Ji + Jj)^T Omega (Ji + Jj) and b_i likewise.  That error does not
+ * depend on xi and Ji + Jj is exactly zero: the edge adds its constant to chi2 and nothing to H or b (a vertex with no
+ * other edge is left without a pivot, as in any system that does not determine it).  The same holds on every path that
+ * linearises (Levenberg-Marquardt, dogleg, marginals, condensed graphs).                          */
 int cgmr_gn_optimize(cgmr_ctx* ctx, int nV, double* poses_xyt, const uint8_t* fixed, int nE,
                      const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt,
                      const double* info_upper, int iters, double* chi2_out);

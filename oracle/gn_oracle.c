@@ -440,6 +440,19 @@ static void gn_sys_linearize(gn_sys_t *S, const double *poses, const int32_t *ef
     mat_atb(Ji, O, JiO);       /* Ji^T Omega */
     mat_atb(Jj, O, JjO);
     int a = S->hidx[ef[k]], b = S->hidx[et[k]];
+    if (a >= 0 && a == b) {
+      /* an edge from a vertex to itself: the chain rule's term, J = Ji + Jj on the one block (its error z^-1 (xi^-1 xi)
+         does not depend on xi, so J is zero: the edge adds to chi2 and to no row of H or b) */
+      int c = S->iperm[a];
+      double J[9], JO[9];
+      for (int q = 0; q < 9; q++) J[q] = Ji[q] + Jj[q];
+      mat_atb(J, O, JO);
+      mat_ab(JO, J, H);
+      for (int cc = 0; cc < 3; cc++)
+        for (int rr = 0; rr <= cc; rr++) S->C.x[blk_scalar_pos(S, c, S->pos_ii[k], rr, cc)] += H[3 * rr + cc];
+      for (int rr = 0; rr < 3; rr++) S->b[3 * c + rr] -= JO[3 * rr] * e[0] + JO[3 * rr + 1] * e[1] + JO[3 * rr + 2] * e[2];
+      continue;
+    }
     if (a >= 0) {
       int c = S->iperm[a];
       mat_ab(JiO, Ji, H);

@@ -64,7 +64,14 @@ def jacobians(poses, ef, et, meas):
     Z[:, 0, 0] = cz; Z[:, 0, 1] = sz
     Z[:, 1, 0] = -sz; Z[:, 1, 1] = cz
     Z[:, 2, 2] = 1
-    return Z @ A, Z @ B
+    Ji, Jj = Z @ A, Z @ B
+    # an edge from a vertex to itself is the chain rule's term: e = z^-1 (xi^-1 xi) with the one Jacobian Ji + Jj on the one
+    # block, H_ii += (Ji + Jj)^T Omega (Ji + Jj) and b_i likewise.  (e does not depend on xi: the sum is zero, the edge adds
+    # to chi2 only.)  Carried by Ji; Jj is cleared so that build_system's four blocks add up to exactly that term
+    self_edge = np.asarray(ef) == np.asarray(et)
+    Ji[self_edge] += Jj[self_edge]
+    Jj[self_edge] = 0
+    return Ji, Jj
 
 
 def chi2(poses, ef, et, meas, info_upper):

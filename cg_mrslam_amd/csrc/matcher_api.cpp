@@ -7,6 +7,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <chrono>
+#include <cstdarg>
+#include <cstdio>
 #include <vector>
 
 #include "cgmr_ctx.h"
@@ -559,6 +561,36 @@ int cgmr_subsample(int n, const double* pts, double res, double* out) {
   return m;
 }
 
+}  // extern "C"
+
+namespace {
+
+// CGMR_MATCH_TRACE: the generic searches print one line per stage on stderr (tools/README.md)
+bool match_trace() {
+  static const bool on = getenv("CGMR_MATCH_TRACE") != nullptr;
+  return on;
+}
+
+using Clock = std::chrono::steady_clock;
+double us_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); }
+double us_since(Clock::time_point a) { return us_between(a, Clock::now()); }
+
+// The host's view of one search: tables made and staged, launches up to the call's one synchronisation, results decoded.
+struct StageTrace {
+  Clock::time_point begin = Clock::now(), staged, back;
+  // "<head>: stage .. us, device+sync .. us (<kernels> ..), decode .. us" -- kernels: the device time between the call's events
+  void print(const cgmr_ctx* ctx, const char* kernels, const char* head_fmt, ...) const {
+    if (!match_trace()) return;
+    char head[256];
+    va_list ap;
+    va_start(ap, head_fmt);
+    vsnprintf(head, sizeof head, head_fmt, ap);
+    va_end(ap);
+    fprintf(stderr, "%s: stage %.0f us, device+sync %.0f us (%s %.0f), decode %.0f us\n", head, us_between(begin, staged),
+            us_between(staged, back), kernels, 1e6 * ctx->match_seconds, us_since(back));
+  }
+};
+
 // One search of a batch: CharGrid::greedySearch(mresvec, points, regions, params) on a grid rasterised from its own
 // reference points.
 struct SearchJob {
@@ -566,6 +598,47 @@ struct SearchJob {
   const double* qry = nullptr; int n_qry = 0;
   const float* regions = nullptr; int n_regions = 0;
 };
+
+std::vector<SearchJob> one_job(int n_ref, const double* ref, int n_qry, const double* qry, int n_regions, const float* regions) {
+  std::vector<SearchJob> jobs(1);
+  jobs[0].ref = ref; jobs[0].n_ref = n_ref; jobs[0].qry = qry; jobs[0].n_qry = n_qry;
+  jobs[0].regions = regions; jobs[0].n_regions = n_regions;
+  return jobs;
+}
+
+int check_jobs(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::vector<SearchJob>& jobs, double theta_res, double dx,
+               double dy, double dth) {
+  if (!cfg || !(theta_res > 0) || !(dx > 0) || !(dy > 0) || !(dth > 0)) return set_err(ctx, CGMR_E_INVALID, "greedy search: bad argument");
+  for (const SearchJob& J : jobs) {
+    if (J.n_ref < 0 || J.n_qry < 0 || J.n_regions < 0 || (J.n_ref > 0 && !J.ref) || (J.n_qry > 0 && !J.qry) || (J.n_regions > 0 && !J.regions))
+      return set_err(ctx, CGMR_E_INVALID, "greedy search: bad argument");
+    if (J.n_ref > kMatchMaxRef) return set_err(ctx, CGMR_E_INVALID, "more than %d reference points", kMatchMaxRef);
+  }
+  return CGMR_OK;
+}
+
+// What a greedy search adds to the grid geometry: the steps in metres, the angle step, the score bound, the result bins.
+struct SearchSpec { double step_x, step_y, theta_res, max_score, dx, dy, dth; };
+
+void apply_search(MatchParams& P, const SearchSpec& S) {
+  P.max_score = S.max_score; P.dx = S.dx; P.dy = S.dy; P.dth = S.dth; P.theta_res = S.theta_res;
+  // chargrid.cpp:214-221
+  int xs = (int)(S.step_x / P.res), ys = (int)(S.step_y / P.res);
+  if (xs <= 0) xs = 1;
+  if (ys <= 0) ys = 1;
+  P.x_steps = xs; P.y_steps = ys;
+}
+
+// Level lv of CharGrid::hierarchicalSearch's n_levels (chargrid.cpp:310-344): step 2^i cells, theta step max(2^i / 2, 1) * thetaRes,
+// bins 2^i * (dx, dy, dth) with i = n_levels - 1 - lv; a result seeds a region of half a bin around it for the next level.
+struct Level { int m, mtheta; SearchSpec S; double half[3]; };
+
+Level level_of(int lv, int n_levels, const cgmr_matcher_config* cfg, double theta_res, double max_score, double dx, double dy, double dth) {
+  const int m = 1 << (n_levels - 1 - lv);
+  const int mtheta = (m / 2 < 1) ? m : m / 2;
+  const float stepf = (float)m * (float)cfg->resolution;
+  return {m, mtheta, {(double)stepf, (double)stepf, mtheta * theta_res, max_score, dx * m, dy * m, dth * m}, {dx * m * .5, dy * m * .5, dth * m * .5}};
+}
 
 // The tables of one k_match_greedy launch: regions -> descriptors, search angles, (region, angle) work items, result-bin boxes,
 // workgroups per job -- exactly like the reference walks its regions (chargrid.cpp:214-239).  P carries the level's steps.
@@ -579,40 +652,30 @@ struct GreedyTables {
   int max_ref = 1, nblocks = 0;
   int cand_per_pass = kMatchCandPerPass;     // MatchParams::cand_per_pass of the launch these tables are for
 };
-static int greedy_tables(cgmr_ctx* ctx, const MatchParams& P, const std::vector<SearchJob>& jobs, double theta_res, double dx, double dy,
-                         double dth, GreedyTables& T) {
+int greedy_tables(cgmr_ctx* ctx, const MatchParams& P, const std::vector<SearchJob>& jobs, GreedyTables& T) {
   // regions -> descriptors, exactly like the reference walks them (chargrid.cpp:223-239), job by job
   const int nj = (int)jobs.size();
   const int xs = P.x_steps, ys = P.y_steps;
-  std::vector<RegionDesc>& R = T.R;
-  std::vector<double>& theta = T.theta;
-  std::vector<int32_t>&items = T.items, &block_job = T.block_job;
-  std::vector<GreedyJob>& G = T.G;
-  std::vector<int>&first_region = T.first_region, &nthreads = T.nthreads;
-  size_t &n_refs = T.n_refs, &n_qrys = T.n_qrys, &total_bins = T.total_bins;
-  int &max_ref = T.max_ref, &nblocks = T.nblocks;
   int live = 0;
-  R.clear(); theta.clear(); items.clear(); block_job.clear();
-  G.assign(nj, GreedyJob());
-  first_region.assign(nj, 0); nthreads.assign(nj, 0);
-  n_refs = n_qrys = total_bins = 0; max_ref = 1; nblocks = 0;
+  T = GreedyTables();
+  T.G.assign(nj, GreedyJob()); T.first_region.assign(nj, 0); T.nthreads.assign(nj, 0);
   auto w2g = [&](float w, float ll) { return (int)std::lrint((w - ll) * P.inv_res); };
   for (const SearchJob& J : jobs) live += J.n_regions > 0 ? 1 : 0;
   const int blocks_cap = std::max(1, std::min(256, 2048 / std::max(live, 1)));     // few jobs: several workgroups each
   for (int j = 0; j < nj; j++) {
     const SearchJob& J = jobs[j];
-    GreedyJob& D0 = G[j];
+    GreedyJob& D0 = T.G[j];
     memset(&D0, 0, sizeof D0);
-    D0.ref_off = (int32_t)n_refs; D0.n_ref = J.n_ref; n_refs += (size_t)J.n_ref;
-    D0.qry_off = (int32_t)n_qrys; D0.n_qry = J.n_qry; n_qrys += (size_t)J.n_qry;
-    D0.item_off = (int32_t)(items.size() / 2);
-    first_region[j] = (int)R.size();
-    D0.region_off = (int32_t)R.size(); D0.n_regions = J.n_regions;
-    max_ref = std::max(max_ref, J.n_ref);
+    D0.ref_off = (int32_t)T.n_refs; D0.n_ref = J.n_ref; T.n_refs += (size_t)J.n_ref;
+    D0.qry_off = (int32_t)T.n_qrys; D0.n_qry = J.n_qry; T.n_qrys += (size_t)J.n_qry;
+    D0.item_off = (int32_t)(T.items.size() / 2);
+    T.first_region[j] = (int)T.R.size();
+    D0.region_off = (int32_t)T.R.size(); D0.n_regions = J.n_regions;
+    T.max_ref = std::max(T.max_ref, J.n_ref);
     if (J.n_regions == 0) continue;
     const int num_threads = std::min(J.n_regions, 4);
     const int chunk = J.n_regions / num_threads;
-    nthreads[j] = num_threads;
+    T.nthreads[j] = num_threads;
     D0.n_threads = num_threads;
     std::vector<uint32_t> next_order(num_threads, 0);
     bool any = false;
@@ -625,37 +688,37 @@ static int greedy_tables(cgmr_ctx* ctx, const MatchParams& P, const std::vector<
       int hi_x = w2g(g[3], P.ll_x), hi_y = w2g(g[4], P.ll_y);
       D.ni = hi_x > D.lo_x ? (hi_x - D.lo_x + xs - 1) / xs : 0;
       D.nj = hi_y > D.lo_y ? (hi_y - D.lo_y + ys - 1) / ys : 0;
-      D.th_off = (int)theta.size();
-      for (double t = g[2]; t < g[5]; t += theta_res) {
-        theta.push_back(t);
-        if (theta.size() - D.th_off > 100000) return set_err(ctx, CGMR_E_INVALID, "too many search angles in a region");
+      D.th_off = (int)T.theta.size();
+      for (double t = g[2]; t < g[5]; t += P.theta_res) {
+        T.theta.push_back(t);
+        if (T.theta.size() - D.th_off > 100000) return set_err(ctx, CGMR_E_INVALID, "too many search angles in a region");
       }
-      D.nth = (int)theta.size() - D.th_off;
+      D.nth = (int)T.theta.size() - D.th_off;
       D.thread = std::min(r / chunk, num_threads - 1);
       D.order_base = next_order[D.thread];
       unsigned long long cnt = (unsigned long long)D.nth * D.ni * D.nj;
       if (next_order[D.thread] + cnt > 0xffffffffULL) return set_err(ctx, CGMR_E_INVALID, "search space exceeds 2^32 candidates per result map");
       next_order[D.thread] += (uint32_t)cnt;
-      const int rid = (int)R.size();
-      R.push_back(D);
+      const int rid = (int)T.R.size();
+      T.R.push_back(D);
       if (cnt == 0) continue;
-      for (int ti = 0; ti < D.nth; ti++) { items.push_back(rid); items.push_back(ti); }
+      for (int ti = 0; ti < D.nth; ti++) { T.items.push_back(rid); T.items.push_back(ti); }
       max_cand = std::max(max_cand, D.ni * D.nj);
       float xa = P.ll_x + (P.res * (float)D.lo_x), xb = P.ll_x + (P.res * (float)(D.lo_x + (D.ni - 1) * xs));
       float ya = P.ll_y + (P.res * (float)D.lo_y), yb = P.ll_y + (P.res * (float)(D.lo_y + (D.nj - 1) * ys));
-      int a0 = (int)((double)xa / dx), a1 = (int)((double)xb / dx), c0 = (int)((double)ya / dy), c1 = (int)((double)yb / dy);
-      int e0 = (int)(theta[D.th_off] / dth), e1 = (int)(theta[D.th_off + D.nth - 1] / dth);
+      int a0 = (int)((double)xa / P.dx), a1 = (int)((double)xb / P.dx), c0 = (int)((double)ya / P.dy), c1 = (int)((double)yb / P.dy);
+      int e0 = (int)(T.theta[D.th_off] / P.dth), e1 = (int)(T.theta[D.th_off + D.nth - 1] / P.dth);
       if (!any) { bx0 = a0; bx1 = a1; by0 = c0; by1 = c1; bt0 = e0; bt1 = e1; any = true; }
       else { bx0 = std::min(bx0, a0); bx1 = std::max(bx1, a1); by0 = std::min(by0, c0); by1 = std::max(by1, c1);
              bt0 = std::min(bt0, e0); bt1 = std::max(bt1, e1); }
     }
-    D0.n_items = (int32_t)(items.size() / 2) - D0.item_off;
+    D0.n_items = (int32_t)(T.items.size() / 2) - D0.item_off;
     if (!any || D0.n_items == 0) { D0.n_items = 0; continue; }
     D0.bx0 = bx0; D0.by0 = by0; D0.bt0 = bt0; D0.nbx = bx1 - bx0 + 1; D0.nby = by1 - by0 + 1; D0.nbt = bt1 - bt0 + 1;
     const size_t nbins = (size_t)D0.nbx * D0.nby * D0.nbt;
     if (nbins * num_threads > (size_t)1 << 26) return set_err(ctx, CGMR_E_INVALID, "result discretisation too fine for the search volume");
-    D0.bins_off = (int64_t)total_bins;
-    total_bins += nbins * num_threads;
+    D0.bins_off = (int64_t)T.total_bins;
+    T.total_bins += nbins * num_threads;
     D0.n_passes = max_cand;                                    // (the candidates of its largest region: passes below)
   }
   // Work units are (region, angle, candidate pass).  A pass is 576 candidates when that makes enough units to fill the chip
@@ -666,183 +729,163 @@ static int greedy_tables(cgmr_ctx* ctx, const MatchParams& P, const std::vector<
     cpp = 128;
     for (int c : {kMatchCandPerPass, 256}) {
       long long units = 0;
-      for (int j = 0; j < nj; j++) units += (long long)G[j].n_items * ((G[j].n_passes + c - 1) / c);
+      for (int j = 0; j < nj; j++) units += (long long)T.G[j].n_items * ((T.G[j].n_passes + c - 1) / c);
       if (units >= 256) { cpp = c; break; }
     }
   }
   T.cand_per_pass = cpp;
   for (int j = 0; j < nj; j++) {
-    GreedyJob& D0 = G[j];
-    D0.block0 = nblocks;
+    GreedyJob& D0 = T.G[j];
+    D0.block0 = T.nblocks;
     if (D0.n_items == 0) { D0.n_passes = 1; continue; }
     D0.n_passes = (D0.n_passes + cpp - 1) / cpp;
     D0.n_blocks = (int)std::max<long long>(1, std::min<long long>(blocks_cap, (long long)D0.n_items * D0.n_passes));   // one unit per workgroup and round
-    for (int b = 0; b < D0.n_blocks; b++) block_job.push_back(j);
-    nblocks += D0.n_blocks;
+    for (int b = 0; b < D0.n_blocks; b++) T.block_job.push_back(j);
+    T.nblocks += D0.n_blocks;
   }
+  if (T.total_bins > (size_t)1 << 28) return set_err(ctx, CGMR_E_INVALID, "result maps of the batch exceed 2 GB");
   return CGMR_OK;
 }
 
-// CharGrid::greedySearch for every job of the batch in ONE launch; per job every result of its <= 4 thread maps,
-// ascending score (ties: result-map order).  All jobs share the grid geometry, the steps and the discretisation.
-static int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::vector<SearchJob>& jobs, double step_x,
-                             double step_y, double theta_res, double max_score, double dx, double dy, double dth,
-                             std::vector<std::vector<cgmr_match_result>>& out) {
-  const int nj = (int)jobs.size();
-  out.assign(nj, {});
-  static const bool trace = getenv("CGMR_MATCH_TRACE") != nullptr;
-  const auto t_begin = std::chrono::steady_clock::now();
-  if (!cfg || !(theta_res > 0) || !(dx > 0) || !(dy > 0) || !(dth > 0)) return set_err(ctx, CGMR_E_INVALID, "greedy search: bad argument");
-  for (const SearchJob& J : jobs) {
-    if (J.n_ref < 0 || J.n_qry < 0 || J.n_regions < 0 || (J.n_ref > 0 && !J.ref) || (J.n_qry > 0 && !J.qry) || (J.n_regions > 0 && !J.regions))
-      return set_err(ctx, CGMR_E_INVALID, "greedy search: bad argument");
-    if (J.n_ref > kMatchMaxRef) return set_err(ctx, CGMR_E_INVALID, "more than %d reference points", kMatchMaxRef);
-  }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  MatchParams P;
-  std::vector<uint8_t> kern;
-  int rc = setup_geometry(ctx, cfg, P, kern);
-  if (rc) return rc;
-  P.max_score = max_score; P.dx = dx; P.dy = dy; P.dth = dth; P.theta_res = theta_res;
-  // chargrid.cpp:214-221
-  int xs = (int)(step_x / P.res), ys = (int)(step_y / P.res);
-  if (xs <= 0) xs = 1;
-  if (ys <= 0) ys = 1;
-  P.x_steps = xs; P.y_steps = ys;
-  GreedyTables T;
-  rc = greedy_tables(ctx, P, jobs, theta_res, dx, dy, dth, T);
-  if (rc) return rc;
-  std::vector<RegionDesc>& R = T.R;
-  std::vector<double>& theta = T.theta;
-  std::vector<int32_t>&items = T.items, &block_job = T.block_job;
-  std::vector<GreedyJob>& G = T.G;
-  std::vector<int>&first_region = T.first_region, &nthreads = T.nthreads;
-  const size_t n_refs = T.n_refs, n_qrys = T.n_qrys, total_bins = T.total_bins;
-  const int max_ref = T.max_ref, nblocks = T.nblocks;
-  P.cand_per_pass = T.cand_per_pass;
-  if (nblocks == 0) return CGMR_OK;
-  if (total_bins > (size_t)1 << 28) return set_err(ctx, CGMR_E_INVALID, "result maps of the batch exceed 2 GB");
+// The per-workgroup scratch of k_match_greedy: the packed cells of the largest reference set + the overflow tiles
+void set_greedy_scratch(MatchParams& P, int max_ref) {
   P.ref_cap = (max_ref + 63) & ~63;
   P.scratch_stride = ((size_t)4 * P.ref_cap + (size_t)P.overflow_tiles * 64 + 255) & ~size_t(255);
-  Layout L;
-  size_t o_ref = L.add(16 * std::max<size_t>(n_refs, 1)), o_q = L.add(16 * std::max<size_t>(n_qrys, 1)),
-         o_reg = L.add(sizeof(RegionDesc) * std::max<size_t>(R.size(), 1)), o_th = L.add(8 * std::max<size_t>(theta.size(), 1)),
-         o_it = L.add(4 * std::max<size_t>(items.size(), 1)), o_job = L.add(sizeof(GreedyJob) * (size_t)nj),
-         o_bj = L.add(4 * block_job.size()), o_kern = L.add(kern.size());
-  size_t hbytes = L.off;
-  // the error word sits right in front of the result maps: one copy brings both back, into a part of the pinned block the
-  // upload does not use (no synchronisation between the two directions)
-  size_t o_err = L.add(256 + 8 * total_bins), o_bins = o_err + 256, o_scratch = L.add(P.scratch_stride * (size_t)nblocks);
-  rc = arena_reserve(ctx, ctx->mt_arena, L.off + 256);
-  if (rc) return rc;
-  const size_t h_back = (hbytes + 255) & ~size_t(255);
-  rc = pinned_reserve(ctx, h_back + 256 + 8 * total_bins);
-  if (rc) return rc;
-  char* h = ctx->pinned;
-  for (int j = 0; j < nj; j++) {
-    if (jobs[j].n_ref) memcpy(h + o_ref + 16 * (size_t)G[j].ref_off, jobs[j].ref, 16 * (size_t)jobs[j].n_ref);
-    if (jobs[j].n_qry) memcpy(h + o_q + 16 * (size_t)G[j].qry_off, jobs[j].qry, 16 * (size_t)jobs[j].n_qry);
+}
+
+// The upload of a launch made from host tables: reference and query points of every job, the GreedyTables, the kernel.  Laid out
+// first -- the caller appends what else it uploads and reserves both blocks --, copied into the pinned block then.
+struct TableStage {
+  size_t o_ref, o_q, o_reg, o_th, o_it, o_job, o_bj, o_kern;
+  TableStage(Layout& L, const GreedyTables& T, const std::vector<uint8_t>& kern) {
+    o_ref = L.add(16 * std::max<size_t>(T.n_refs, 1)); o_q = L.add(16 * std::max<size_t>(T.n_qrys, 1));
+    o_reg = L.add(sizeof(RegionDesc) * std::max<size_t>(T.R.size(), 1)); o_th = L.add(8 * std::max<size_t>(T.theta.size(), 1));
+    o_it = L.add(4 * std::max<size_t>(T.items.size(), 1)); o_job = L.add(sizeof(GreedyJob) * T.G.size());
+    o_bj = L.add(4 * T.block_job.size()); o_kern = L.add(kern.size());
   }
-  if (!R.empty()) memcpy(h + o_reg, R.data(), sizeof(RegionDesc) * R.size());
-  if (!theta.empty()) memcpy(h + o_th, theta.data(), 8 * theta.size());
-  if (!items.empty()) memcpy(h + o_it, items.data(), 4 * items.size());
-  memcpy(h + o_job, G.data(), sizeof(GreedyJob) * (size_t)nj);
-  memcpy(h + o_bj, block_job.data(), 4 * block_job.size());
-  memcpy(h + o_kern, kern.data(), kern.size());
-  char* d = ctx->mt_arena.ptr;
-  const auto t_staged = std::chrono::steady_clock::now();
-  HIP_TRY(ctx, hipMemcpyAsync(d, h, hbytes, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(d + o_err, 0, 256, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(d + o_bins, 0xff, 8 * total_bins, ctx->stream));
+  void copy(char* h, const std::vector<SearchJob>& jobs, const GreedyTables& T, const std::vector<uint8_t>& kern) const {
+    for (size_t j = 0; j < jobs.size(); j++) {
+      if (jobs[j].n_ref) memcpy(h + o_ref + 16 * (size_t)T.G[j].ref_off, jobs[j].ref, 16 * (size_t)jobs[j].n_ref);
+      if (jobs[j].n_qry) memcpy(h + o_q + 16 * (size_t)T.G[j].qry_off, jobs[j].qry, 16 * (size_t)jobs[j].n_qry);
+    }
+    if (!T.R.empty()) memcpy(h + o_reg, T.R.data(), sizeof(RegionDesc) * T.R.size());
+    if (!T.theta.empty()) memcpy(h + o_th, T.theta.data(), 8 * T.theta.size());
+    if (!T.items.empty()) memcpy(h + o_it, T.items.data(), 4 * T.items.size());
+    memcpy(h + o_job, T.G.data(), sizeof(GreedyJob) * T.G.size());
+    memcpy(h + o_bj, T.block_job.data(), 4 * T.block_job.size());
+    memcpy(h + o_kern, kern.data(), kern.size());
+  }
+};
+
+// The bracket around a search's launches: ev0 in front; behind them ev1, ONE copy that brings the error word and the results behind
+// it back (into a part of the pinned block the upload does not use), the call's only synchronisation, the device time, the error word.
+int launches_begin(cgmr_ctx* ctx) {
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  launch_match_greedy(ctx->stream, nblocks, P, (const GreedyJob*)(d + o_job), (const int32_t*)(d + o_bj), (const double*)(d + o_ref),
-                      (const double*)(d + o_q), (const RegionDesc*)(d + o_reg), (const double*)(d + o_th),
-                      (const int32_t*)(d + o_it), (const uint8_t*)(d + o_kern), (unsigned char*)(d + o_scratch),
-                      (unsigned long long*)(d + o_bins), (int*)(d + o_err));
+  return CGMR_OK;
+}
+int launches_end(cgmr_ctx* ctx, char* h_back, const char* d_err, size_t back_bytes) {
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(h + h_back, d + o_err, 256 + 8 * total_bins, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(h_back, d_err, back_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const int err = *reinterpret_cast<const int*>(h + h_back);
   HIP_TRY(ctx, hipGetLastError());
   float ms = 0;
   (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
   ctx->match_seconds = 1e-3 * ms;
-  const auto t_back = std::chrono::steady_clock::now();
+  int err = 0;
+  memcpy(&err, h_back, sizeof err);
   if (err != 0) return set_err(ctx, CGMR_E_INVALID, "matcher kernel error %d", err);
-  struct TraceAtExit {
-    bool on; std::chrono::steady_clock::time_point a, b, c; float ms; int nj, nblocks; size_t bins, items, hbytes;
-    ~TraceAtExit() {
-      if (!on) return;
-      auto us = [](auto x, auto y) { return std::chrono::duration<double, std::micro>(y - x).count(); };
-      fprintf(stderr, "[greedy] jobs %d blocks %d items %zu bins %zu upload %zu B: stage %.0f us, device+sync %.0f us (kernel %.0f), decode %.0f us\n",
-              nj, nblocks, items, bins, hbytes, us(a, b), us(b, c), 1e3 * ms, us(c, std::chrono::steady_clock::now()));
-    }
-  } trace_at_exit{trace, t_begin, t_staged, t_back, ms, nj, nblocks, total_bins, items.size() / 2, hbytes};
-  // decode: thread maps in thread order, each in (ix, iy, ith) order; then a stable sort on the score
-  for (int j = 0; j < nj; j++) {
-    const GreedyJob& D0 = G[j];
+  return CGMR_OK;
+}
+
+// the result maps of a launch -> per job every result of its <= 4 thread maps: thread maps in thread order, each in (ix, iy, ith)
+// order; then a stable sort on the score
+int greedy_decode(cgmr_ctx* ctx, const MatchParams& P, const GreedyTables& T, const std::vector<SearchJob>& jobs,
+                  const unsigned long long* all_bins, std::vector<std::vector<cgmr_match_result>>& out) {
+  for (size_t j = 0; j < jobs.size(); j++) {
+    const GreedyJob& D0 = T.G[j];
     if (D0.n_items == 0) continue;
     const size_t nbins = (size_t)D0.nbx * D0.nby * D0.nbt;
-    const unsigned long long* bins = (const unsigned long long*)(h + h_back + 256) + D0.bins_off;
+    const unsigned long long* bins = all_bins + D0.bins_off;
     std::vector<cgmr_match_result>& res = out[j];
-    for (int th = 0; th < nthreads[j]; th++)
+    for (int th = 0; th < T.nthreads[j]; th++)
       for (size_t q = 0; q < nbins; q++) {
         unsigned long long key = bins[(size_t)th * nbins + q];
         if (key == ~0ULL) continue;
         uint32_t ord = (uint32_t)(key & 0xffffffffu);
         int reg = -1;
-        for (int r = first_region[j]; r < first_region[j] + jobs[j].n_regions; r++) {
-          const unsigned long long cnt = (unsigned long long)R[r].nth * R[r].ni * R[r].nj;
-          if (R[r].thread == th && cnt > 0 && ord >= R[r].order_base && ord - R[r].order_base < cnt) { reg = r; break; }
+        for (int r = T.first_region[j]; r < T.first_region[j] + jobs[j].n_regions; r++) {
+          const unsigned long long cnt = (unsigned long long)T.R[r].nth * T.R[r].ni * T.R[r].nj;
+          if (T.R[r].thread == th && cnt > 0 && ord >= T.R[r].order_base && ord - T.R[r].order_base < cnt) { reg = r; break; }
         }
         if (reg < 0) return set_err(ctx, CGMR_E_INVALID, "corrupt result key");
-        const RegionDesc& D = R[reg];
+        const RegionDesc& D = T.R[reg];
         uint32_t local = ord - D.order_base;
         int ncand = D.ni * D.nj;
         int ti = (int)(local / ncand), cidx = (int)(local % ncand);
         int a = cidx / D.nj, b = cidx % D.nj;
-        float wx = P.ll_x + (P.res * (float)(D.lo_x + a * xs));
-        float wy = P.ll_y + (P.res * (float)(D.lo_y + b * ys));
+        float wx = P.ll_x + (P.res * (float)(D.lo_x + a * P.x_steps));
+        float wy = P.ll_y + (P.res * (float)(D.lo_y + b * P.y_steps));
         uint32_t sb = (uint32_t)(key >> 32);
         float sc;
         memcpy(&sc, &sb, 4);
-        res.push_back({(double)wx, (double)wy, theta[D.th_off + ti], (double)sc});
+        res.push_back({(double)wx, (double)wy, T.theta[D.th_off + ti], (double)sc});
       }
     std::stable_sort(res.begin(), res.end(), [](const cgmr_match_result& a, const cgmr_match_result& b) { return a.score < b.score; });
   }
   return CGMR_OK;
 }
 
-// single search
-static int greedy_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_ref, const double* ref_pts, int n_qry,
-                       const double* qry_pts, int n_regions, const float* regions, double step_x, double step_y,
-                       double theta_res, double max_score, double dx, double dy, double dth,
-                       std::vector<cgmr_match_result>& res) {
-  res.clear();
-  std::vector<SearchJob> jobs(1);
-  jobs[0].ref = ref_pts; jobs[0].n_ref = n_ref; jobs[0].qry = qry_pts; jobs[0].n_qry = n_qry;
-  jobs[0].regions = regions; jobs[0].n_regions = n_regions;
-  std::vector<std::vector<cgmr_match_result>> out;
-  int rc = greedy_batch_core(ctx, cfg, jobs, step_x, step_y, theta_res, max_score, dx, dy, dth, out);
+// CharGrid::greedySearch for every job of the batch in ONE launch; per job every result of its <= 4 thread maps,
+// ascending score (ties: result-map order).  All jobs share the grid geometry, the steps and the discretisation.
+int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::vector<SearchJob>& jobs, const SearchSpec& S,
+                      std::vector<std::vector<cgmr_match_result>>& out) {
+  const int nj = (int)jobs.size();
+  out.assign(nj, {});
+  StageTrace trace;
+  int rc = check_jobs(ctx, cfg, jobs, S.theta_res, S.dx, S.dy, S.dth);
   if (rc) return rc;
-  res.swap(out[0]);
-  return CGMR_OK;
-}
-
-int cgmr_match_greedy(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_ref, const double* ref_pts, int n_qry,
-                      const double* qry_pts, int n_regions, const float* regions, double step_x, double step_y,
-                      double theta_res, double max_score, double dx, double dy, double dth,
-                      cgmr_match_result* results_out, int cap, int* n_out) {
-  if (!ctx) return CGMR_E_INVALID;
-  if (cap < 0 || !n_out || (cap > 0 && !results_out)) return set_err(ctx, CGMR_E_INVALID, "cgmr_match_greedy: bad argument");
-  *n_out = 0;
-  std::vector<cgmr_match_result> res;
-  int rc = greedy_core(ctx, cfg, n_ref, ref_pts, n_qry, qry_pts, n_regions, regions, step_x, step_y, theta_res, max_score,
-                       dx, dy, dth, res);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  MatchParams P;
+  std::vector<uint8_t> kern;
+  rc = setup_geometry(ctx, cfg, P, kern);
   if (rc) return rc;
-  *n_out = (int)res.size();
-  for (int k = 0; k < (int)res.size() && k < cap; k++) results_out[k] = res[k];
-  return CGMR_OK;
+  apply_search(P, S);
+  GreedyTables T;
+  rc = greedy_tables(ctx, P, jobs, T);
+  if (rc) return rc;
+  P.cand_per_pass = T.cand_per_pass;
+  if (T.nblocks == 0) return CGMR_OK;
+  set_greedy_scratch(P, T.max_ref);
+  Layout L;
+  const TableStage U(L, T, kern);
+  const size_t hbytes = L.off;
+  // the error word sits right in front of the result maps: one copy brings both back
+  const size_t back_bytes = 256 + 8 * T.total_bins;
+  const size_t o_err = L.add(back_bytes), o_bins = o_err + 256, o_scratch = L.add(P.scratch_stride * (size_t)T.nblocks);
+  rc = arena_reserve(ctx, ctx->mt_arena, L.off + 256);
+  if (rc) return rc;
+  const size_t h_back = (hbytes + 255) & ~size_t(255);
+  rc = pinned_reserve(ctx, h_back + back_bytes);
+  if (rc) return rc;
+  char* h = ctx->pinned;
+  U.copy(h, jobs, T, kern);
+  char* d = ctx->mt_arena.ptr;
+  trace.staged = Clock::now();
+  HIP_TRY(ctx, hipMemcpyAsync(d, h, hbytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(d + o_err, 0, 256, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(d + o_bins, 0xff, 8 * T.total_bins, ctx->stream));
+  rc = launches_begin(ctx);
+  if (rc) return rc;
+  launch_match_greedy(ctx->stream, T.nblocks, P, (const GreedyJob*)(d + U.o_job), (const int32_t*)(d + U.o_bj), (const double*)(d + U.o_ref),
+                      (const double*)(d + U.o_q), (const RegionDesc*)(d + U.o_reg), (const double*)(d + U.o_th),
+                      (const int32_t*)(d + U.o_it), (const uint8_t*)(d + U.o_kern), (unsigned char*)(d + o_scratch),
+                      (unsigned long long*)(d + o_bins), (int*)(d + o_err));
+  rc = launches_end(ctx, h + h_back, d + o_err, back_bytes);
+  trace.back = Clock::now();
+  if (rc) return rc;
+  rc = greedy_decode(ctx, P, T, jobs, (const unsigned long long*)(h + h_back + 256), out);
+  trace.print(ctx, "kernel", "[greedy] jobs %d blocks %d items %zu bins %zu upload %zu B", nj, T.nblocks, T.items.size() / 2, T.total_bins, hbytes);
+  return rc;
 }
 
 struct VerifyIn {
@@ -852,8 +895,8 @@ struct VerifyIn {
 };
 
 // numeric core of verifyMatching for a batch of candidate transforms, one workgroup each, one launch
-static int verify_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::vector<VerifyIn>& in, double nonmatched_score,
-                             std::vector<double>& score, std::vector<int>& nnm) {
+int verify_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::vector<VerifyIn>& in, double nonmatched_score,
+                      std::vector<double>& score, std::vector<int>& nnm) {
   const int nj = (int)in.size();
   score.assign(nj, 0.0);
   nnm.assign(nj, 0);
@@ -900,40 +943,15 @@ static int verify_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, cons
   memset(h + o_err, 0, 16);
   char* d = ctx->mt_arena.ptr;
   HIP_TRY(ctx, hipMemcpyAsync(d, h, hbytes, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  rc = launches_begin(ctx);
+  if (rc) return rc;
   launch_match_verify(ctx->stream, nj, P, (const VerifyJob*)(d + o_job), (const double*)(d + o2), (const double*)(d + o1),
                       nonmatched_score, (const uint8_t*)(d + o_kern), (unsigned char*)(d + o_scratch), (double*)(d + o_sc),
                       (int*)(d + o_nn), (int*)(d + o_err));
-  HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(h + h_back, d + o_err, back_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_TRY(ctx, hipGetLastError());
-  int err = 0;
-  memcpy(&err, h + h_back, sizeof(int));
+  rc = launches_end(ctx, h + h_back, d + o_err, back_bytes);
+  if (rc) return rc;
   memcpy(score.data(), h + h_back + (o_sc - o_err), 8 * (size_t)nj);
   memcpy(nnm.data(), h + h_back + (o_nn - o_err), 4 * (size_t)nj);
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-  ctx->match_seconds = 1e-3 * ms;
-  if (err != 0) return set_err(ctx, CGMR_E_INVALID, "matcher kernel error %d", err);
-  return CGMR_OK;
-}
-
-int cgmr_match_verify(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n2, const double* pts2, int n1, const double* pts1,
-                      double nonmatched_score, const float lower_xy[2], const float upper_xy[2], double* score_out,
-                      int* n_nonmatched_out) {
-  if (!ctx) return CGMR_E_INVALID;
-  if (!cfg || n1 < 0 || n2 < 0 || (n1 > 0 && !pts1) || (n2 > 0 && !pts2) || !lower_xy || !upper_xy || !score_out)
-    return set_err(ctx, CGMR_E_INVALID, "cgmr_match_verify: bad argument");
-  std::vector<VerifyIn> in(1);
-  in[0].pts2 = pts2; in[0].n2 = n2; in[0].pts1 = pts1; in[0].n1 = n1;
-  in[0].lower[0] = lower_xy[0]; in[0].lower[1] = lower_xy[1]; in[0].upper[0] = upper_xy[0]; in[0].upper[1] = upper_xy[1];
-  std::vector<double> score;
-  std::vector<int> nnm;
-  int rc = verify_batch_core(ctx, cfg, in, nonmatched_score, score, nnm);
-  if (rc) return rc;
-  *score_out = score[0];
-  if (n_nonmatched_out) *n_nonmatched_out = nnm[0];
   return CGMR_OK;
 }
 
@@ -942,10 +960,6 @@ int cgmr_match_verify(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n2, con
 // and CharGrid::hierarchicalSearch (src/matcher/chargrid.cpp:310-413): vertex sets arrive as flat scan sets, the
 // region / transform bookkeeping is host code with the reference's arithmetic (Vector3f regions: float; SE2
 // products: double with libm sin / cos), every search runs on the GPU.
-}  // extern "C"
-
-namespace {
-
 struct Se2 { double x, y, t; };
 inline double norm_theta(double t) {
   const double pi = 3.14159265358979323846;
@@ -1069,28 +1083,40 @@ std::vector<double> subsample_of(const std::vector<double>& pts, double res) {
   return out;
 }
 
+// The points of a batch of searches over scan sets (prepare_scan_sets): job j searches ref[ref_alias[j]] for qry[j]
+struct SetPoints {
+  std::vector<std::vector<double>> ref, qry;
+  std::vector<int> ref_alias;
+  SearchJob job(int j, const float* regions, int n_regions) const {
+    const std::vector<double>& rj = ref[ref_alias[j]];
+    SearchJob J;
+    J.ref = rj.data(); J.n_ref = (int)(rj.size() / 2);
+    J.qry = qry[j].data(); J.n_qry = (int)(qry[j].size() / 2);
+    J.regions = regions; J.n_regions = n_regions;
+    return J;
+  }
+};
+
 // Host preparation of a batch of searches over scan sets: the reference points of every distinct reference set (jobs that
 // pass the very same set share them: ref_alias), points and 0.1 m subsample of every current set (scan_matcher.cpp:216-217,
 // 376-381).  Tasks for the helper threads: the scans of a reference set in runs of a few scans (a 21-scan set is 150 us of
 // host work in one piece), every current set with its subsample; then the runs of a set are joined in scan order and
 // thinned out (a robot that stays in the same rooms hits the same cells again and again: 13k points -> 600).
 void prepare_scan_sets(const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets, const cgmr_scan_set* cur_sets,
-                       std::vector<std::vector<double>>& ref, std::vector<std::vector<double>>& qry, std::vector<int>& ref_alias,
-                       bool trace) {
-  auto us_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count(); };
-  ref.assign(n_jobs, {}); qry.assign(n_jobs, {}); ref_alias.assign(n_jobs, 0);
+                       SetPoints& pts) {
+  pts.ref.assign(n_jobs, {}); pts.qry.assign(n_jobs, {}); pts.ref_alias.assign(n_jobs, 0);
   for (int j = 0; j < n_jobs; j++) {
-    ref_alias[j] = j;
+    pts.ref_alias[j] = j;
     for (int k = 0; k < j; k++)
       if (ref_sets[k].ranges == ref_sets[j].ranges && ref_sets[k].poses_xyt == ref_sets[j].poses_xyt &&
-          ref_sets[k].n_scans == ref_sets[j].n_scans && ref_sets[k].ref_index == ref_sets[j].ref_index) { ref_alias[j] = ref_alias[k]; break; }
+          ref_sets[k].n_scans == ref_sets[j].n_scans && ref_sets[k].ref_index == ref_sets[j].ref_index) { pts.ref_alias[j] = pts.ref_alias[k]; break; }
   }
-  const auto ta = std::chrono::steady_clock::now();
+  const auto ta = Clock::now();
   struct Run { int job, k0, k1; std::vector<double> pts; };
   std::vector<Run> runs;
   const int kRun = 3;
   for (int j = 0; j < n_jobs; j++)
-    if (ref_alias[j] == j)
+    if (pts.ref_alias[j] == j)
       for (int k0 = 0; k0 < ref_sets[j].n_scans; k0 += kRun) runs.push_back({j, k0, std::min(ref_sets[j].n_scans, k0 + kRun), {}});
   const int n_runs = (int)runs.size();
   host_run_tasks(n_runs + n_jobs, [&](int t) {
@@ -1103,20 +1129,20 @@ void prepare_scan_sets(const cgmr_matcher_config* cfg, int n_jobs, const cgmr_sc
     const int j = t - n_runs;
     std::vector<double> cur;
     points_from_vset(cfg, cur_sets + j, nullptr, cur);
-    qry[j] = subsample_of(cur, 0.1);
+    pts.qry[j] = subsample_of(cur, 0.1);
   });
   const double us_runs = us_since(ta);
   std::vector<int> owners;
-  for (int j = 0; j < n_jobs; j++) if (ref_alias[j] == j) owners.push_back(j);
+  for (int j = 0; j < n_jobs; j++) if (pts.ref_alias[j] == j) owners.push_back(j);
   host_run_tasks((int)owners.size(), [&](int q) {
     const int j = owners[q];
     size_t total = 0;
     for (const Run& r : runs) if (r.job == j) total += r.pts.size();
-    ref[j].reserve(total);
-    for (const Run& r : runs) if (r.job == j) ref[j].insert(ref[j].end(), r.pts.begin(), r.pts.end());
-    keep_first_point_per_cell(cfg, ref[j], ref_sets[j].n_scans > kRun ? 0 : 2048);
+    pts.ref[j].reserve(total);
+    for (const Run& r : runs) if (r.job == j) pts.ref[j].insert(pts.ref[j].end(), r.pts.begin(), r.pts.end());
+    keep_first_point_per_cell(cfg, pts.ref[j], ref_sets[j].n_scans > kRun ? 0 : 2048);
   });
-  if (trace)
+  if (match_trace())
     fprintf(stderr, "[sets] %d runs + %d current sets %.0f us, join + thin out %.0f us\n", n_runs, n_jobs, us_runs, us_since(ta) - us_runs);
 }
 
@@ -1132,50 +1158,33 @@ int hierarchical_batch_dev(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const 
   done = false;
   const int nj = (int)jobs0.size();
   if (nj == 0 || n_levels < 2 || n_levels > 8) return CGMR_OK;      // (one level: the loop below -- the reference's single level never runs, chargrid.cpp:336)
-  static const bool trace = getenv("CGMR_MATCH_TRACE") != nullptr;
-  const auto t_begin = std::chrono::steady_clock::now();
-  if (!cfg || !(theta_res > 0) || !(dx > 0) || !(dy > 0) || !(dth > 0)) return set_err(ctx, CGMR_E_INVALID, "greedy search: bad argument");
-  for (const SearchJob& J : jobs0) {
-    if (J.n_ref < 0 || J.n_qry < 0 || J.n_regions < 0 || (J.n_ref > 0 && !J.ref) || (J.n_qry > 0 && !J.qry) || (J.n_regions > 0 && !J.regions))
-      return set_err(ctx, CGMR_E_INVALID, "greedy search: bad argument");
-    if (J.n_ref > kMatchMaxRef) return set_err(ctx, CGMR_E_INVALID, "more than %d reference points", kMatchMaxRef);
-  }
+  StageTrace trace;
+  int rc = check_jobs(ctx, cfg, jobs0, theta_res, dx, dy, dth);
+  if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   MatchParams P0;
   std::vector<uint8_t> kern;
-  int rc = setup_geometry(ctx, cfg, P0, kern);
+  rc = setup_geometry(ctx, cfg, P0, kern);
   if (rc) return rc;
-  // the levels' parameters, as hierarchical_batch_core / greedy_batch_core derive them
   std::vector<MatchParams> PL(n_levels, P0);
-  std::vector<double> half_x(n_levels), half_y(n_levels), half_t(n_levels);
-  const float res_f = (float)cfg->resolution;
+  std::vector<Level> V(n_levels);
   int tmax = 1;
   for (int lv = 0; lv < n_levels; lv++) {
-    const int i = n_levels - 1 - lv;
-    const int m = 1 << i;
-    const int mtheta = (m / 2 < 1) ? m : m / 2;
-    const float stepf = (float)m * res_f;
-    MatchParams& P = PL[lv];
-    P.max_score = max_score; P.dx = dx * m; P.dy = dy * m; P.dth = dth * m; P.theta_res = mtheta * theta_res;
-    int xs = (int)((double)stepf / P.res), ys = (int)((double)stepf / P.res);
-    if (xs <= 0) xs = 1;
-    if (ys <= 0) ys = 1;
-    P.x_steps = xs; P.y_steps = ys;
-    half_x[lv] = dx * m * .5; half_y[lv] = dy * m * .5; half_t[lv] = dth * m * .5;
+    V[lv] = level_of(lv, n_levels, cfg, theta_res, max_score, dx, dy, dth);
+    apply_search(PL[lv], V[lv].S);
     if (lv > 0) {
-      const double cnt = 2 * half_t[lv - 1] / P.theta_res;
+      const double cnt = 2 * V[lv - 1].half[2] / PL[lv].theta_res;
       if (!(cnt < 250)) return CGMR_OK;                        // (not served here)
       tmax = std::max(tmax, (int)cnt + 3);
     }
   }
   GreedyTables T;
-  rc = greedy_tables(ctx, PL[0], jobs0, PL[0].theta_res, PL[0].dx, PL[0].dy, PL[0].dth, T);
+  rc = greedy_tables(ctx, PL[0], jobs0, T);
   if (rc) return rc;
   PL[0].cand_per_pass = T.cand_per_pass;
   for (int lv = 1; lv < n_levels; lv++) PL[lv].cand_per_pass = 128;      // (regions of half a bin: ~100 candidates, one pass of two slots per lane)
   out.assign(nj, {});
   if (T.nblocks == 0) { done = true; return CGMR_OK; }
-  if (T.total_bins > (size_t)1 << 28) return set_err(ctx, CGMR_E_INVALID, "result maps of the batch exceed 2 GB");
   const int capR = 256, capT = capR * tmax, capI = capT;
   const int bpj = std::max(1, std::min(256, 2048 / nj));       // workgroups per job on the later levels (the ones without an item return at once)
   std::vector<long long> capB(n_levels, 0);
@@ -1190,16 +1199,11 @@ int hierarchical_batch_dev(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const 
     if (worst > (1ll << 21) || worst * nj > (1ll << 25)) return CGMR_OK;      // (not served here)
     capB[lv] = (worst + 31) & ~31ll;
   }
-  for (int lv = 0; lv < n_levels; lv++) {
-    PL[lv].ref_cap = (T.max_ref + 63) & ~63;
-    PL[lv].scratch_stride = ((size_t)4 * PL[lv].ref_cap + (size_t)PL[lv].overflow_tiles * 64 + 255) & ~size_t(255);
-  }
+  for (int lv = 0; lv < n_levels; lv++) set_greedy_scratch(PL[lv], T.max_ref);
   const size_t img = match_grid_image_bytes(P0);
   Layout L;
-  const size_t o_ref = L.add(16 * std::max<size_t>(T.n_refs, 1)), o_q = L.add(16 * std::max<size_t>(T.n_qrys, 1)),
-               o_reg0 = L.add(sizeof(RegionDesc) * std::max<size_t>(T.R.size(), 1)), o_th0 = L.add(8 * std::max<size_t>(T.theta.size(), 1)),
-               o_it0 = L.add(4 * std::max<size_t>(T.items.size(), 1)), o_job0 = L.add(sizeof(GreedyJob) * (size_t)nj),
-               o_bj0 = L.add(4 * T.block_job.size()), o_bjn = L.add(4 * (size_t)nj * bpj), o_kern = L.add(kern.size());
+  const TableStage U(L, T, kern);
+  const size_t o_bjn = L.add(4 * (size_t)nj * bpj);
   // The first level's result maps (all ones), the error words and the result counts (zero) ride with the upload when the maps are
   // small -- a global matching's are 360 bytes --: two fill launches less per search.
   const bool fills_ride = 8 * T.total_bins <= (size_t)64 << 10;
@@ -1208,7 +1212,8 @@ int hierarchical_batch_dev(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const 
   const size_t o_err = L.add(256 + cnt_bytes + res_bytes), o_cnt = o_err + 256, o_res = o_cnt + cnt_bytes;
   const size_t hbytes = fills_ride ? o_cnt + cnt_bytes : o_err;
   if (!fills_ride) o_bins0 = L.add(8 * T.total_bins);
-  std::vector<size_t> o_reg(n_levels, 0), o_th(n_levels, 0), o_it(n_levels, 0), o_job(n_levels, 0), o_bins(n_levels, 0);
+  // level 0 reads the uploaded tables, the later levels the slices k_hier_next fills
+  std::vector<size_t> o_reg(n_levels, U.o_reg), o_th(n_levels, U.o_th), o_it(n_levels, U.o_it), o_job(n_levels, U.o_job), o_bins(n_levels, o_bins0);
   for (int lv = 1; lv < n_levels; lv++) {
     o_reg[lv] = L.add(sizeof(RegionDesc) * (size_t)capR * nj);
     o_th[lv] = L.add(8 * (size_t)capT * nj);
@@ -1224,22 +1229,13 @@ int hierarchical_batch_dev(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const 
   rc = pinned_reserve(ctx, h_back + back_bytes);
   if (rc) return rc;
   char* h = ctx->pinned;
-  for (int j = 0; j < nj; j++) {
-    if (jobs0[j].n_ref) memcpy(h + o_ref + 16 * (size_t)T.G[j].ref_off, jobs0[j].ref, 16 * (size_t)jobs0[j].n_ref);
-    if (jobs0[j].n_qry) memcpy(h + o_q + 16 * (size_t)T.G[j].qry_off, jobs0[j].qry, 16 * (size_t)jobs0[j].n_qry);
-  }
-  if (!T.R.empty()) memcpy(h + o_reg0, T.R.data(), sizeof(RegionDesc) * T.R.size());
-  if (!T.theta.empty()) memcpy(h + o_th0, T.theta.data(), 8 * T.theta.size());
-  if (!T.items.empty()) memcpy(h + o_it0, T.items.data(), 4 * T.items.size());
-  memcpy(h + o_job0, T.G.data(), sizeof(GreedyJob) * (size_t)nj);
-  memcpy(h + o_bj0, T.block_job.data(), 4 * T.block_job.size());
+  U.copy(h, jobs0, T, kern);
   {
     int32_t* bjn = reinterpret_cast<int32_t*>(h + o_bjn);
     for (int j = 0; j < nj; j++) for (int b = 0; b < bpj; b++) bjn[(size_t)j * bpj + b] = j;
   }
-  memcpy(h + o_kern, kern.data(), kern.size());
   char* d = ctx->mt_arena.ptr;
-  const auto t_staged = std::chrono::steady_clock::now();
+  trace.staged = Clock::now();
   if (fills_ride) {
     memset(h + o_bins0, 0xff, 8 * T.total_bins);
     memset(h + o_err, 0, 256 + cnt_bytes);
@@ -1249,20 +1245,21 @@ int hierarchical_batch_dev(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const 
     HIP_TRY(ctx, hipMemsetAsync(d + o_err, 0, 256 + cnt_bytes, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(d + o_bins0, 0xff, 8 * T.total_bins, ctx->stream));
   }
-  HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  rc = launches_begin(ctx);
+  if (rc) return rc;
   int* d_err = (int*)(d + o_err);
-  launch_match_greedy(ctx->stream, T.nblocks, PL[0], (const GreedyJob*)(d + o_job0), (const int32_t*)(d + o_bj0), (const double*)(d + o_ref),
-                      (const double*)(d + o_q), (const RegionDesc*)(d + o_reg0), (const double*)(d + o_th0), (const int32_t*)(d + o_it0),
-                      (const uint8_t*)(d + o_kern), (unsigned char*)(d + o_scratch), (unsigned long long*)(d + o_bins0), d_err,
+  launch_match_greedy(ctx->stream, T.nblocks, PL[0], (const GreedyJob*)(d + U.o_job), (const int32_t*)(d + U.o_bj), (const double*)(d + U.o_ref),
+                      (const double*)(d + U.o_q), (const RegionDesc*)(d + U.o_reg), (const double*)(d + U.o_th), (const int32_t*)(d + U.o_it),
+                      (const uint8_t*)(d + U.o_kern), (unsigned char*)(d + o_scratch), (unsigned long long*)(d + o_bins0), d_err,
                       (unsigned char*)(d + o_cache), img, n_levels > 1 ? 1 : 0);
   for (int lv = 0; lv < n_levels; lv++) {
     const bool last = lv == n_levels - 1;
     HierStep H;
     memset(&H, 0, sizeof H);
-    H.jobs = (const GreedyJob*)(d + (lv == 0 ? o_job0 : o_job[lv]));
-    H.regions = (const RegionDesc*)(d + (lv == 0 ? o_reg0 : o_reg[lv]));
-    H.theta = (const double*)(d + (lv == 0 ? o_th0 : o_th[lv]));
-    H.bins = (const unsigned long long*)(d + (lv == 0 ? o_bins0 : o_bins[lv]));
+    H.jobs = (const GreedyJob*)(d + o_job[lv]);
+    H.regions = (const RegionDesc*)(d + o_reg[lv]);
+    H.theta = (const double*)(d + o_th[lv]);
+    H.bins = (const unsigned long long*)(d + o_bins[lv]);
     H.x_steps = PL[lv].x_steps; H.y_steps = PL[lv].y_steps;
     H.final_level = last ? 1 : 0;
     H.cap_regions = capR; H.cap_theta = capT; H.cap_items = capI;
@@ -1276,7 +1273,7 @@ int hierarchical_batch_dev(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const 
       H.items_next = (int32_t*)(d + o_it[lv + 1]);
       H.bins_next = (unsigned long long*)(d + o_bins[lv + 1]);
       H.x_steps_next = PL[lv + 1].x_steps; H.y_steps_next = PL[lv + 1].y_steps;
-      H.half_x = half_x[lv]; H.half_y = half_y[lv]; H.half_t = half_t[lv];
+      H.half_x = V[lv].half[0]; H.half_y = V[lv].half[1]; H.half_t = V[lv].half[2];
       H.theta_res_next = PL[lv + 1].theta_res; H.dx_next = PL[lv + 1].dx; H.dy_next = PL[lv + 1].dy; H.dth_next = PL[lv + 1].dth;
       H.cap_bins_next = capB[lv + 1];
       H.cand_per_pass_next = PL[lv + 1].cand_per_pass;
@@ -1284,23 +1281,16 @@ int hierarchical_batch_dev(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const 
     launch_hier_next(ctx->stream, nj, PL[lv], H, d_err);
     if (!last)
       launch_match_greedy(ctx->stream, nj * bpj, PL[lv + 1], (const GreedyJob*)(d + o_job[lv + 1]), (const int32_t*)(d + o_bjn),
-                          (const double*)(d + o_ref), (const double*)(d + o_q), (const RegionDesc*)(d + o_reg[lv + 1]),
-                          (const double*)(d + o_th[lv + 1]), (const int32_t*)(d + o_it[lv + 1]), (const uint8_t*)(d + o_kern),
+                          (const double*)(d + U.o_ref), (const double*)(d + U.o_q), (const RegionDesc*)(d + o_reg[lv + 1]),
+                          (const double*)(d + o_th[lv + 1]), (const int32_t*)(d + o_it[lv + 1]), (const uint8_t*)(d + U.o_kern),
                           (unsigned char*)(d + o_scratch), (unsigned long long*)(d + o_bins[lv + 1]), d_err,
                           (unsigned char*)(d + o_cache), img, 2);
   }
-  HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(h + h_back, d + o_err, back_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_TRY(ctx, hipGetLastError());
-  const int* errv = reinterpret_cast<const int*>(h + h_back);
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-  ctx->match_seconds = 1e-3 * ms;
-  const auto t_back = std::chrono::steady_clock::now();
-  if (errv[0] != 0) return set_err(ctx, CGMR_E_INVALID, "matcher kernel error %d", errv[0]);
-  if (errv[8] != 0) {                                         // a job outgrew its slices: level by level instead
-    if (trace) fprintf(stderr, "[hier] %d jobs, %d levels: table slices too small, level by level\n", nj, n_levels);
+  rc = launches_end(ctx, h + h_back, d + o_err, back_bytes);
+  trace.back = Clock::now();
+  if (rc) return rc;
+  if (reinterpret_cast<const int*>(h + h_back)[8] != 0) {     // a job outgrew its slices: level by level instead
+    if (match_trace()) fprintf(stderr, "[hier] %d jobs, %d levels: table slices too small, level by level\n", nj, n_levels);
     return CGMR_OK;
   }
   const int* counts = reinterpret_cast<const int*>(h + h_back + 256);
@@ -1314,19 +1304,12 @@ int hierarchical_batch_dev(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const 
     }
   }
   done = true;
-  if (trace) {
-    auto us = [](auto x, auto y) { return std::chrono::duration<double, std::micro>(y - x).count(); };
-    fprintf(stderr, "[hier] jobs %d levels %d blocks %d + %d x %d upload %zu B: stage %.0f us, device+sync %.0f us (kernels %.0f), decode %.0f us\n",
-            nj, n_levels, T.nblocks, n_levels - 1, nj * bpj, hbytes, us(t_begin, t_staged), us(t_staged, t_back), 1e3 * ms,
-            us(t_back, std::chrono::steady_clock::now()));
-  }
+  trace.print(ctx, "kernels", "[hier] jobs %d levels %d blocks %d + %d x %d upload %zu B", nj, n_levels, T.nblocks, n_levels - 1, nj * bpj, hbytes);
   return CGMR_OK;
 }
 
-// CharGrid::hierarchicalSearch (chargrid.cpp:310-344, 376-400) for a batch of searches: levels n-1 .. 0, step 2^i
-// cells, theta step max(2^i / 2, 1) * thetaRes, bins 2^i * (dx, dy, dth); every result of a level seeds a region of
-// half a bin around it for the next one; the last level only runs if the one before found something.  One launch per
-// level serves every search that is still alive.
+// CharGrid::hierarchicalSearch (chargrid.cpp:310-344, 376-400) for a batch of searches, level by level (level_of); the last
+// level only runs if the one before found something.  One launch per level serves every search that is still alive.
 int hierarchical_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::vector<SearchJob>& jobs0, double theta_res,
                             double max_score, double dx, double dy, double dth, int n_levels,
                             std::vector<std::vector<cgmr_match_result>>& out) {
@@ -1341,11 +1324,7 @@ int hierarchical_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const
   std::vector<std::vector<float>> cur(nj);
   std::vector<uint8_t> alive(nj, 1);
   for (int j = 0; j < nj; j++) cur[j].assign(jobs0[j].regions, jobs0[j].regions + 6 * (size_t)jobs0[j].n_regions);
-  const float res_f = (float)cfg->resolution;
   for (int lv = 0; lv < n_levels; lv++) {
-    const int i = n_levels - 1 - lv;
-    const int m = 1 << i;
-    const int mtheta = (m / 2 < 1) ? m : m / 2;
     const bool last = lv == n_levels - 1;
     std::vector<SearchJob> jobs;
     std::vector<int> who;
@@ -1359,11 +1338,10 @@ int hierarchical_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const
       who.push_back(j);
     }
     if (jobs.empty()) break;
-    const float stepf = (float)m * res_f;
+    const Level V = level_of(lv, n_levels, cfg, theta_res, max_score, dx, dy, dth);
     std::vector<std::vector<cgmr_match_result>> res;
-    int rc = greedy_batch_core(ctx, cfg, jobs, (double)stepf, (double)stepf, mtheta * theta_res, max_score, dx * m, dy * m, dth * m, res);
+    int rc = greedy_batch_core(ctx, cfg, jobs, V.S, res);
     if (rc) return rc;
-    const double half[3] = {dx * m * .5, dy * m * .5, dth * m * .5};
     for (size_t q = 0; q < who.size(); q++) {
       const int j = who[q];
       out[j].swap(res[q]);
@@ -1372,8 +1350,8 @@ int hierarchical_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const
       for (size_t k = 0; k < out[j].size(); k++) {
         const double c[3] = {out[j][k].x, out[j][k].y, out[j][k].theta};
         for (int a = 0; a < 3; a++) {
-          cur[j][6 * k + a] = (float)(-half[a] + c[a]);
-          cur[j][6 * k + 3 + a] = (float)(half[a] + c[a]);
+          cur[j][6 * k + a] = (float)(-V.half[a] + c[a]);
+          cur[j][6 * k + 3 + a] = (float)(V.half[a] + c[a]);
         }
       }
     }
@@ -1381,21 +1359,67 @@ int hierarchical_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const
   return CGMR_OK;
 }
 
-int hierarchical_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_ref, const double* ref, int n_qry, const double* qry,
-                      int n_regions, const float* regions, double theta_res, double max_score, double dx, double dy,
-                      double dth, int n_levels, std::vector<cgmr_match_result>& out) {
-  std::vector<SearchJob> jobs(1);
-  jobs[0].ref = ref; jobs[0].n_ref = n_ref; jobs[0].qry = qry; jobs[0].n_qry = n_qry; jobs[0].regions = regions; jobs[0].n_regions = n_regions;
-  std::vector<std::vector<cgmr_match_result>> res;
-  int rc = hierarchical_batch_core(ctx, cfg, jobs, theta_res, max_score, dx, dy, dth, n_levels, res);
-  if (rc) return rc;
-  out.swap(res[0]);
+// what every batch entry point over scan sets checks first; `name` for the error text
+int check_set_batch(cgmr_ctx* ctx, const char* name, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* a,
+                    const cgmr_scan_set* b, const void* p0, const void* p1) {
+  if (!cfg || n_jobs < 0 || (n_jobs > 0 && (!a || !b || !p0 || !p1))) return set_err(ctx, CGMR_E_INVALID, "%s: bad argument", name);
+  for (int j = 0; j < n_jobs; j++)
+    if (!scan_set_ok(a + j) || !scan_set_ok(b + j)) return set_err(ctx, CGMR_E_INVALID, "%s: bad scan set", name);
   return CGMR_OK;
+}
+
+// per job the best result of a hierarchy, or zeros, and whether there was one
+void write_best(const std::vector<std::vector<cgmr_match_result>>& res, double* trel_out, int* found_out) {
+  for (size_t j = 0; j < res.size(); j++) {
+    double* t = trel_out + 3 * j;
+    t[0] = t[1] = t[2] = 0;
+    found_out[j] = res[j].empty() ? 0 : 1;
+    if (!res[j].empty()) { t[0] = res[j][0].x; t[1] = res[j][0].y; t[2] = res[j][0].theta; }
+  }
+}
+
+// a single search's results into the caller's array: all are counted, the first `cap` written
+void write_results(const std::vector<cgmr_match_result>& res, cgmr_match_result* results_out, int cap, int* n_out) {
+  *n_out = (int)res.size();
+  for (int k = 0; k < (int)res.size() && k < cap; k++) results_out[k] = res[k];
 }
 
 }  // namespace
 
 extern "C" {
+
+int cgmr_match_greedy(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_ref, const double* ref_pts, int n_qry,
+                      const double* qry_pts, int n_regions, const float* regions, double step_x, double step_y,
+                      double theta_res, double max_score, double dx, double dy, double dth,
+                      cgmr_match_result* results_out, int cap, int* n_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (cap < 0 || !n_out || (cap > 0 && !results_out)) return set_err(ctx, CGMR_E_INVALID, "cgmr_match_greedy: bad argument");
+  *n_out = 0;
+  std::vector<std::vector<cgmr_match_result>> res;
+  int rc = greedy_batch_core(ctx, cfg, one_job(n_ref, ref_pts, n_qry, qry_pts, n_regions, regions),
+                             {step_x, step_y, theta_res, max_score, dx, dy, dth}, res);
+  if (rc) return rc;
+  write_results(res[0], results_out, cap, n_out);
+  return CGMR_OK;
+}
+
+int cgmr_match_verify(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n2, const double* pts2, int n1, const double* pts1,
+                      double nonmatched_score, const float lower_xy[2], const float upper_xy[2], double* score_out,
+                      int* n_nonmatched_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (!cfg || n1 < 0 || n2 < 0 || (n1 > 0 && !pts1) || (n2 > 0 && !pts2) || !lower_xy || !upper_xy || !score_out)
+    return set_err(ctx, CGMR_E_INVALID, "cgmr_match_verify: bad argument");
+  std::vector<VerifyIn> in(1);
+  in[0].pts2 = pts2; in[0].n2 = n2; in[0].pts1 = pts1; in[0].n1 = n1;
+  in[0].lower[0] = lower_xy[0]; in[0].lower[1] = lower_xy[1]; in[0].upper[0] = upper_xy[0]; in[0].upper[1] = upper_xy[1];
+  std::vector<double> score;
+  std::vector<int> nnm;
+  int rc = verify_batch_core(ctx, cfg, in, nonmatched_score, score, nnm);
+  if (rc) return rc;
+  *score_out = score[0];
+  if (n_nonmatched_out) *n_nonmatched_out = nnm[0];
+  return CGMR_OK;
+}
 
 int cgmr_transform_points_from_vset(const cgmr_matcher_config* cfg, const cgmr_scan_set* vset, double* pts_out, int cap) {
   if (!cfg || !scan_set_ok(vset) || cap < 0 || (cap > 0 && !pts_out)) return CGMR_E_INVALID;
@@ -1415,12 +1439,11 @@ int cgmr_match_hierarchical(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n
   if (n_levels < 1 || n_levels > 16 || cap < 0 || !n_out || (cap > 0 && !results_out) || n_regions < 0 || (n_regions > 0 && !regions))
     return set_err(ctx, CGMR_E_INVALID, "cgmr_match_hierarchical: bad argument");
   *n_out = 0;
-  std::vector<cgmr_match_result> res;
-  int rc = hierarchical_core(ctx, cfg, n_ref, ref_pts, n_qry, qry_pts, n_regions, regions, theta_res, max_score, dx, dy, dth,
-                             n_levels, res);
+  std::vector<std::vector<cgmr_match_result>> res;
+  int rc = hierarchical_batch_core(ctx, cfg, one_job(n_ref, ref_pts, n_qry, qry_pts, n_regions, regions), theta_res, max_score, dx, dy,
+                                   dth, n_levels, res);
   if (rc) return rc;
-  *n_out = (int)res.size();
-  for (int k = 0; k < (int)res.size() && k < cap; k++) results_out[k] = res[k];
+  write_results(res[0], results_out, cap, n_out);
   return CGMR_OK;
 }
 
@@ -1459,27 +1482,23 @@ int cgmr_close_scan_matching(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, cons
   const float region[6] = {(float)(-cfg->win_x + g.x), (float)(-cfg->win_y + g.y), (float)(-cfg->win_theta + g.t),
                            (float)(cfg->win_x + g.x),  (float)(cfg->win_y + g.y),  (float)(cfg->win_theta + g.t)};
   const double step = (double)(float)cfg->resolution;
-  std::vector<cgmr_match_result> res;
-  int rc = greedy_core(ctx, cfg, (int)(ref.size() / 2), ref.data(), (int)(qry.size() / 2), qry.data(), 1, region, step, step,
-                       cfg->theta_res, max_score, cfg->bin_x, cfg->bin_y, cfg->bin_theta, res);
+  std::vector<std::vector<cgmr_match_result>> res;
+  int rc = greedy_batch_core(ctx, cfg, one_job((int)(ref.size() / 2), ref.data(), (int)(qry.size() / 2), qry.data(), 1, region),
+                             {step, step, cfg->theta_res, max_score, cfg->bin_x, cfg->bin_y, cfg->bin_theta}, res);
   if (rc) return rc;
-  if (!res.empty()) { *found_out = 1; trel_out[0] = res[0].x; trel_out[1] = res[0].y; trel_out[2] = res[0].theta; }
+  write_best(res, trel_out, found_out);
   return CGMR_OK;
 }
 
 int cgmr_scan_matching_lc_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
                                 const cgmr_scan_set* cur_sets, double max_score, double* trel_out, int* n_out) {
   if (!ctx) return CGMR_E_INVALID;
-  if (!cfg || n_jobs < 0 || (n_jobs > 0 && (!ref_sets || !cur_sets || !trel_out || !n_out)))
-    return set_err(ctx, CGMR_E_INVALID, "cgmr_scan_matching_lc: bad argument");
-  for (int j = 0; j < n_jobs; j++)
-    if (!scan_set_ok(ref_sets + j) || !scan_set_ok(cur_sets + j)) return set_err(ctx, CGMR_E_INVALID, "cgmr_scan_matching_lc: bad scan set");
+  int rc = check_set_batch(ctx, "cgmr_scan_matching_lc", cfg, n_jobs, ref_sets, cur_sets, trel_out, n_out);
+  if (rc) return rc;
   struct Key { int a, b, c; bool operator<(const Key& o) const { return a != o.a ? a < o.a : (b != o.b ? b < o.b : c < o.c); } };
-  std::vector<std::vector<double>> ref, qry;
+  SetPoints pts;
   std::vector<std::vector<float>> regions(n_jobs), regionspi(n_jobs);
-  std::vector<int> ref_alias;
-  static const bool lc_trace = getenv("CGMR_MATCH_TRACE") != nullptr;
-  prepare_scan_sets(cfg, n_jobs, ref_sets, cur_sets, ref, qry, ref_alias, lc_trace);
+  prepare_scan_sets(cfg, n_jobs, ref_sets, cur_sets, pts);
   for (int j = 0; j < n_jobs; j++) {
     const cgmr_scan_set* S = ref_sets + j;
     const Se2 refp = se2_of(S->poses_xyt + 3 * (size_t)S->ref_index);
@@ -1505,14 +1524,10 @@ int cgmr_scan_matching_lc_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, i
   for (int pass = 0; pass < 2; pass++)
     for (int j = 0; j < n_jobs; j++) {
       const std::vector<float>& rg = pass ? regionspi[j] : regions[j];
-      const std::vector<double>& rj = ref[ref_alias[j]];
-      SearchJob& J = jobs[(size_t)pass * n_jobs + j];
-      J.ref = rj.data(); J.n_ref = (int)(rj.size() / 2);
-      J.qry = qry[j].data(); J.n_qry = (int)(qry[j].size() / 2);
-      J.regions = rg.data(); J.n_regions = (int)(rg.size() / 6);
+      jobs[(size_t)pass * n_jobs + j] = pts.job(j, rg.data(), (int)(rg.size() / 6));
     }
   std::vector<std::vector<cgmr_match_result>> res;
-  int rc = greedy_batch_core(ctx, cfg, jobs, step, step, theta_res, max_score, dx, dy, dth, res);
+  rc = greedy_batch_core(ctx, cfg, jobs, {step, step, theta_res, max_score, dx, dy, dth}, res);
   if (rc) return rc;
   for (int pass = 0; pass < 2; pass++)
     for (int j = 0; j < n_jobs; j++) {
@@ -1549,41 +1564,24 @@ int cgmr_scan_matching_lc(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const c
 int cgmr_global_matching_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
                                const cgmr_scan_set* cur_sets, double max_score, double* trel_out, int* found_out) {
   if (!ctx) return CGMR_E_INVALID;
-  if (!cfg || n_jobs < 0 || (n_jobs > 0 && (!ref_sets || !cur_sets || !trel_out || !found_out)))
-    return set_err(ctx, CGMR_E_INVALID, "cgmr_global_matching: bad argument");
-  for (int j = 0; j < n_jobs; j++)
-    if (!scan_set_ok(ref_sets + j) || !scan_set_ok(cur_sets + j)) return set_err(ctx, CGMR_E_INVALID, "cgmr_global_matching: bad scan set");
-  std::vector<std::vector<double>> ref(n_jobs), qry(n_jobs);
+  int rc = check_set_batch(ctx, "cgmr_global_matching", cfg, n_jobs, ref_sets, cur_sets, trel_out, found_out);
+  if (rc) return rc;
   const float pi_f = (float)3.14159265358979323846;
   const float region[6] = {-10.f, -5.f, -pi_f, 10.f, 5.f, pi_f};                   // scan_matcher.cpp:383-391
+  const auto t_begin = Clock::now();
+  SetPoints pts;
+  prepare_scan_sets(cfg, n_jobs, ref_sets, cur_sets, pts);
+  const double us_sets = us_since(t_begin);
   std::vector<SearchJob> jobs(n_jobs);
-  std::vector<int> ref_alias(n_jobs, 0);
-  static const bool gm_trace = getenv("CGMR_MATCH_TRACE") != nullptr;
-  const auto tg0 = std::chrono::steady_clock::now();
-  double us_ref = 0;
-  auto us_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count(); };
-  const auto ta = std::chrono::steady_clock::now();
-  prepare_scan_sets(cfg, n_jobs, ref_sets, cur_sets, ref, qry, ref_alias, gm_trace);
-  us_ref = us_since(ta);
-  for (int j = 0; j < n_jobs; j++) {
-    const std::vector<double>& rj = ref[ref_alias[j]];
-    jobs[j].ref = rj.data(); jobs[j].n_ref = (int)(rj.size() / 2);
-    jobs[j].qry = qry[j].data(); jobs[j].n_qry = (int)(qry[j].size() / 2);
-    jobs[j].regions = region; jobs[j].n_regions = 1;
-  }
+  for (int j = 0; j < n_jobs; j++) jobs[j] = pts.job(j, region, 1);
   std::vector<std::vector<cgmr_match_result>> res;
-  const auto th0 = std::chrono::steady_clock::now();
-  int rc = hierarchical_batch_core(ctx, cfg, jobs, 0.025, max_score, 0.5, 0.5, 0.2, 4, res);
+  const auto t_hier = Clock::now();
+  rc = hierarchical_batch_core(ctx, cfg, jobs, 0.025, max_score, 0.5, 0.5, 0.2, 4, res);
   if (rc) return rc;
-  if (gm_trace)
-    fprintf(stderr, "[global] %d jobs: points + subsample (helper threads) %.0f us, hierarchy %.0f us, total %.0f us\n", n_jobs, us_ref, us_since(th0),
-            us_since(tg0));
-  for (int j = 0; j < n_jobs; j++) {
-    double* t = trel_out + 3 * (size_t)j;
-    t[0] = t[1] = t[2] = 0;
-    found_out[j] = res[j].empty() ? 0 : 1;
-    if (!res[j].empty()) { t[0] = res[j][0].x; t[1] = res[j][0].y; t[2] = res[j][0].theta; }
-  }
+  if (match_trace())
+    fprintf(stderr, "[global] %d jobs: points + subsample (helper threads) %.0f us, hierarchy %.0f us, total %.0f us\n", n_jobs, us_sets,
+            us_since(t_hier), us_since(t_begin));
+  write_best(res, trel_out, found_out);
   return CGMR_OK;
 }
 
@@ -1601,14 +1599,10 @@ int cgmr_global_matching(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const cg
 int cgmr_scan_matching_lc_hierarchical_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
                                              const cgmr_scan_set* cur_sets, double max_score, double* trel_out, int* found_out) {
   if (!ctx) return CGMR_E_INVALID;
-  if (!cfg || n_jobs < 0 || (n_jobs > 0 && (!ref_sets || !cur_sets || !trel_out || !found_out)))
-    return set_err(ctx, CGMR_E_INVALID, "cgmr_scan_matching_lc_hierarchical: bad argument");
-  for (int j = 0; j < n_jobs; j++)
-    if (!scan_set_ok(ref_sets + j) || !scan_set_ok(cur_sets + j)) return set_err(ctx, CGMR_E_INVALID, "cgmr_scan_matching_lc_hierarchical: bad scan set");
-  std::vector<std::vector<double>> ref(n_jobs), qry(n_jobs);
-  std::vector<int> ref_alias(n_jobs, 0);
-  static const bool trace = getenv("CGMR_MATCH_TRACE") != nullptr;
-  prepare_scan_sets(cfg, n_jobs, ref_sets, cur_sets, ref, qry, ref_alias, trace);
+  int rc = check_set_batch(ctx, "cgmr_scan_matching_lc_hierarchical", cfg, n_jobs, ref_sets, cur_sets, trel_out, found_out);
+  if (rc) return rc;
+  SetPoints pts;
+  prepare_scan_sets(cfg, n_jobs, ref_sets, cur_sets, pts);
   std::vector<std::vector<float>> regions(n_jobs);
   std::vector<SearchJob> jobs(n_jobs);
   for (int j = 0; j < n_jobs; j++) {
@@ -1616,20 +1610,12 @@ int cgmr_scan_matching_lc_hierarchical_batch(cgmr_ctx* ctx, const cgmr_matcher_c
     const Se2 d = se2_mul(se2_inv(se2_of(R->poses_xyt + 3 * (size_t)R->ref_index)), se2_of(Cs->poses_xyt + 3 * (size_t)Cs->ref_index));   // :318
     // Eigen::Vector3f lower(-2. + initGuess.x(), ...): every double sum narrowed to float (:322-323)
     regions[j] = {(float)(-2. + d.x), (float)(-2. + d.y), (float)(-1. + d.t), (float)(2. + d.x), (float)(2. + d.y), (float)(1. + d.t)};
-    const std::vector<double>& rj = ref[ref_alias[j]];
-    jobs[j].ref = rj.data(); jobs[j].n_ref = (int)(rj.size() / 2);
-    jobs[j].qry = qry[j].data(); jobs[j].n_qry = (int)(qry[j].size() / 2);
-    jobs[j].regions = regions[j].data(); jobs[j].n_regions = 1;
+    jobs[j] = pts.job(j, regions[j].data(), 1);
   }
   std::vector<std::vector<cgmr_match_result>> res;
-  int rc = hierarchical_batch_core(ctx, cfg, jobs, 0.025, max_score, 0.5, 0.5, 0.2, 3, res);    // :332-339
+  rc = hierarchical_batch_core(ctx, cfg, jobs, 0.025, max_score, 0.5, 0.5, 0.2, 3, res);    // :332-339
   if (rc) return rc;
-  for (int j = 0; j < n_jobs; j++) {
-    double* t = trel_out + 3 * (size_t)j;
-    t[0] = t[1] = t[2] = 0;
-    found_out[j] = res[j].empty() ? 0 : 1;
-    if (!res[j].empty()) { t[0] = res[j][0].x; t[1] = res[j][0].y; t[2] = res[j][0].theta; }
-  }
+  write_best(res, trel_out, found_out);
   return CGMR_OK;
 }
 
@@ -1644,10 +1630,8 @@ int cgmr_scan_matching_lc_hierarchical(cgmr_ctx* ctx, const cgmr_matcher_config*
 int cgmr_verify_matching_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* sets1,
                                const cgmr_scan_set* sets2, const double* trel12, double* score_out, int* accepted_out) {
   if (!ctx) return CGMR_E_INVALID;
-  if (!cfg || n_jobs < 0 || (n_jobs > 0 && (!sets1 || !sets2 || !trel12 || !score_out)))
-    return set_err(ctx, CGMR_E_INVALID, "cgmr_verify_matching: bad argument");
-  for (int j = 0; j < n_jobs; j++)
-    if (!scan_set_ok(sets1 + j) || !scan_set_ok(sets2 + j)) return set_err(ctx, CGMR_E_INVALID, "cgmr_verify_matching: bad scan set");
+  int rc = check_set_batch(ctx, "cgmr_verify_matching", cfg, n_jobs, sets1, sets2, trel12, score_out);
+  if (rc) return rc;
   std::vector<std::vector<double>> p2(n_jobs), p1(n_jobs);
   std::vector<VerifyIn> in(n_jobs);
   // the points of both sets of every job, in runs of a few scans on the helper threads, joined in scan order
@@ -1680,7 +1664,7 @@ int cgmr_verify_matching_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, in
   }
   std::vector<double> score;
   std::vector<int> nnm;
-  int rc = verify_batch_core(ctx, cfg, in, 0.3, score, nnm);
+  rc = verify_batch_core(ctx, cfg, in, 0.3, score, nnm);
   if (rc) return rc;
   for (int j = 0; j < n_jobs; j++) {
     score_out[j] = score[j];

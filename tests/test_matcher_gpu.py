@@ -347,6 +347,61 @@ def test_level_loop_on_the_device_and_level_by_level(ctx, oracle):
     assert host.shape == dev.shape and np.array_equal(host.reshape(dev.shape), dev)
 
 
+def _global_batch_jobs(sp):
+    """Three single-scan global matchings of make_scan_pairs(3, ..): the third job's current scan has every beam at max range."""
+    rq = sp["ranges_qry"].copy()
+    rq[2] = sp["max_range"]
+    return [([(sp["ranges_ref"][p], np.zeros(3))], 0, [(rq[p], sp["guess"][p])], 0) for p in range(3)]
+
+
+def test_level_by_level_batch_with_a_job_that_dies(ctx, oracle):
+    """globalMatchingBatch with three jobs (seed 77, maxScore 0.4) chosen with the oracle so that
+      * at least one job has more than 256 and at most 4096 results on the global region (+-10, +-5, +-pi; 4 levels;
+        0.025 / 0.5 / 0.5 / 0.2): the whole batch leaves the device tables and runs level by level (the oracle counts
+        1075 and 336 for jobs 0 and 1);
+      * at least one job has none: job 2's current scan is all at max range, so it dies at the first level while the others
+        go on -- the level-by-level loop's alive / who[q] -> j bookkeeping with a batch.
+    Both conditions are asserted from the oracle's counts.  Per job the batch equals the single globalMatching call and the
+    first row of the oracle's hierarchical_search bit for bit, and the same batch in a process with CGMR_HIER_HOST=1."""
+    import subprocess, sys, os, json
+    seed, max_score = 77, 0.4
+    sp = synth.make_scan_pairs(3, seed=seed)
+    m = _lc(ctx, sp)
+    jobs = _global_batch_jobs(sp)
+    region = np.array([[-10, -5, np.float32(-np.pi), 10, 5, np.float32(np.pi)]], dtype=np.float32)
+    counts, first = [], []
+    for ref_scans, ri, cur_scans, ci in jobs:
+        ref = m.transformPointsFromVSet(ref_scans, ri)
+        q = m.subsample(m.transformPointsFromVSet(cur_scans, ci), 0.1)
+        n, want = oracle.hierarchical_search((-35, -35), (35, 35), 0.1, 0.1, 0.5, ref, q, region, 0.025, max_score, 0.5, 0.5, 0.2, 4)
+        counts.append(n)
+        first.append(want[0][:3].copy() if n else None)
+    print("oracle counts", counts)
+    assert any(256 < n <= 4096 for n in counts)                   # (the oracle wrapper holds 4096 rows)
+    assert any(n == 0 for n in counts)
+    batch = m.globalMatchingBatch(jobs, max_score)
+    assert len(batch) == 3
+    for j, (found, trel) in enumerate(batch):
+        ok1, trel1 = m.globalMatching(*jobs[j], max_score)
+        assert found == ok1 == (counts[j] > 0), (j, found, ok1, counts[j])
+        if found:
+            assert np.array_equal(trel, trel1) and np.array_equal(trel, first[j]), (j, trel, trel1, first[j])
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import json\nfrom cg_mrslam_amd import Context, synth\nfrom tests.test_matcher_gpu import _lc, _global_batch_jobs\n"
+            f"ctx = Context(0)\nsp = synth.make_scan_pairs(3, seed={seed})\nm = _lc(ctx, sp)\n"
+            f"res = m.globalMatchingBatch(_global_batch_jobs(sp), {max_score})\n"
+            "print(json.dumps([[bool(f), None if t is None else [float(v).hex() for v in t]] for f, t in res]))\n")
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, env=dict(os.environ, PYTHONPATH=root, CGMR_HIER_HOST="1"),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-1500:]
+    host = json.loads(r.stdout.strip().splitlines()[-1])
+    assert len(host) == 3
+    for (found, trel), (hf, ht) in zip(batch, host):
+        assert found == hf
+        if found:
+            assert np.array_equal(trel, np.array([float.fromhex(v) for v in ht]))
+
+
 def test_scan_matching_lc_multi_scan_reference_set(ctx, oracle):
     """scanMatchingLC (scan_matcher.cpp:201-294) with a 3-scan reference set: the host-side region/merge logic
     around the GPU search is checked against the same flow driven by the oracle's greedy search."""

@@ -837,10 +837,26 @@ int greedy_decode(cgmr_ctx* ctx, const MatchParams& P, const GreedyTables& T, co
 
 // CharGrid::greedySearch for every job of the batch in ONE launch; per job every result of its <= 4 thread maps,
 // ascending score (ties: result-map order).  All jobs share the grid geometry, the steps and the discretisation.
+// With `resp` the same tables, staging and launch bracket serve the response surface instead (k_match_response: one region per
+// job, S.max_score and the bins unused): resp->out receives a result per job, `out` stays empty.
+struct ResponseSpec {
+  double T;
+  const double* winners;                     // [n_jobs * 4] (x, y, theta, score) of the search before
+  const int* found;                          // [n_jobs], nullable = all found: 0 -> status 2
+  struct cgmr_match_response* out;           // [n_jobs]
+};
+static_assert(sizeof(struct cgmr_match_response) == sizeof(MatchResponse) && offsetof(struct cgmr_match_response, status) == offsetof(MatchResponse, status) &&
+              offsetof(struct cgmr_match_response, mass) == offsetof(MatchResponse, mass), "cgmr_match_response is the kernels' MatchResponse");
+
 int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::vector<SearchJob>& jobs, const SearchSpec& S,
-                      std::vector<std::vector<cgmr_match_result>>& out) {
+                      std::vector<std::vector<cgmr_match_result>>& out, const ResponseSpec* resp = nullptr) {
   const int nj = (int)jobs.size();
   out.assign(nj, {});
+  if (resp)
+    for (int j = 0; j < nj; j++) {
+      memset(&resp->out[j], 0, sizeof resp->out[j]);
+      resp->out[j].status = (resp->found && !resp->found[j]) ? 2 : 1;     // (what a launch without workgroups leaves: nothing counted)
+    }
   StageTrace trace;
   int rc = check_jobs(ctx, cfg, jobs, S.theta_res, S.dx, S.dy, S.dth);
   if (rc) return rc;
@@ -858,10 +874,12 @@ int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::
   set_greedy_scratch(P, T.max_ref);
   Layout L;
   const TableStage U(L, T, kern);
+  const size_t o_win = resp ? L.add(32 * (size_t)nj) : 0, o_found = resp ? L.add(4 * (size_t)nj) : 0;
   const size_t hbytes = L.off;
-  // the error word sits right in front of the result maps: one copy brings both back
-  const size_t back_bytes = 256 + 8 * T.total_bins;
+  // the error word sits right in front of the result maps (the responses): one copy brings both back
+  const size_t back_bytes = 256 + (resp ? sizeof(MatchResponse) * (size_t)nj : 8 * T.total_bins);
   const size_t o_err = L.add(back_bytes), o_bins = o_err + 256, o_scratch = L.add(P.scratch_stride * (size_t)T.nblocks);
+  const size_t o_part = resp ? L.add(8 * (size_t)kRespSums * (size_t)T.nblocks) : 0;
   rc = arena_reserve(ctx, ctx->mt_arena, L.off + 256);
   if (rc) return rc;
   const size_t h_back = (hbytes + 255) & ~size_t(255);
@@ -869,20 +887,36 @@ int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::
   if (rc) return rc;
   char* h = ctx->pinned;
   U.copy(h, jobs, T, kern);
+  if (resp) {
+    memcpy(h + o_win, resp->winners, 32 * (size_t)nj);
+    for (int j = 0; j < nj; j++) reinterpret_cast<int32_t*>(h + o_found)[j] = (resp->found && !resp->found[j]) ? 0 : 1;
+  }
   char* d = ctx->mt_arena.ptr;
   trace.staged = Clock::now();
   HIP_TRY(ctx, hipMemcpyAsync(d, h, hbytes, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(d + o_err, 0, 256, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(d + o_bins, 0xff, 8 * T.total_bins, ctx->stream));
+  if (!resp) HIP_TRY(ctx, hipMemsetAsync(d + o_bins, 0xff, 8 * T.total_bins, ctx->stream));
   rc = launches_begin(ctx);
   if (rc) return rc;
-  launch_match_greedy(ctx->stream, T.nblocks, P, (const GreedyJob*)(d + U.o_job), (const int32_t*)(d + U.o_bj), (const double*)(d + U.o_ref),
-                      (const double*)(d + U.o_q), (const RegionDesc*)(d + U.o_reg), (const double*)(d + U.o_th),
-                      (const int32_t*)(d + U.o_it), (const uint8_t*)(d + U.o_kern), (unsigned char*)(d + o_scratch),
-                      (unsigned long long*)(d + o_bins), (int*)(d + o_err));
+  if (resp)
+    launch_match_response(ctx->stream, T.nblocks, nj, P, (const GreedyJob*)(d + U.o_job), (const int32_t*)(d + U.o_bj),
+                          (const double*)(d + U.o_ref), (const double*)(d + U.o_q), (const RegionDesc*)(d + U.o_reg),
+                          (const double*)(d + U.o_th), (const int32_t*)(d + U.o_it), (const uint8_t*)(d + U.o_kern),
+                          (unsigned char*)(d + o_scratch), (int*)(d + o_err), (const double*)(d + o_win), (const int32_t*)(d + o_found),
+                          resp->T, (double*)(d + o_part), (MatchResponse*)(d + o_bins));
+  else
+    launch_match_greedy(ctx->stream, T.nblocks, P, (const GreedyJob*)(d + U.o_job), (const int32_t*)(d + U.o_bj), (const double*)(d + U.o_ref),
+                        (const double*)(d + U.o_q), (const RegionDesc*)(d + U.o_reg), (const double*)(d + U.o_th),
+                        (const int32_t*)(d + U.o_it), (const uint8_t*)(d + U.o_kern), (unsigned char*)(d + o_scratch),
+                        (unsigned long long*)(d + o_bins), (int*)(d + o_err));
   rc = launches_end(ctx, h + h_back, d + o_err, back_bytes);
   trace.back = Clock::now();
   if (rc) return rc;
+  if (resp) {
+    memcpy(resp->out, h + h_back + 256, sizeof(MatchResponse) * (size_t)nj);
+    trace.print(ctx, "kernels", "[response] jobs %d blocks %d items %zu upload %zu B", nj, T.nblocks, T.items.size() / 2, hbytes);
+    return CGMR_OK;
+  }
   rc = greedy_decode(ctx, P, T, jobs, (const unsigned long long*)(h + h_back + 256), out);
   trace.print(ctx, "kernel", "[greedy] jobs %d blocks %d items %zu bins %zu upload %zu B", nj, T.nblocks, T.items.size() / 2, T.total_bins, hbytes);
   return rc;
@@ -1447,10 +1481,11 @@ int cgmr_match_hierarchical(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n
   return CGMR_OK;
 }
 
-int cgmr_close_scan_matching(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const cgmr_scan_set* vset,
-                             const float* cur_ranges, const double cur_pose_xyt[3], double max_score, double trel_out[3],
-                             int* found_out) {
-  if (!ctx) return CGMR_E_INVALID;
+// cgmr_close_scan_matching; *score_out (nullable): the winner's score, for the response surface behind it
+static int close_scan_matching_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const cgmr_scan_set* vset, const float* cur_ranges,
+                                    const double cur_pose_xyt[3], double max_score, double trel_out[3], int* found_out,
+                                    double* score_out) {
+  if (score_out) *score_out = 0;
   if (!cfg || !scan_set_ok(vset) || !cur_ranges || !cur_pose_xyt || !trel_out || !found_out)
     return set_err(ctx, CGMR_E_INVALID, "cgmr_close_scan_matching: bad argument");
   *found_out = 0;
@@ -1472,6 +1507,7 @@ int cgmr_close_scan_matching(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, cons
                                          trel_out, &score, &found, nullptr);
     if (rc) return rc;
     *found_out = found;
+    if (score_out && found) *score_out = score;
     return CGMR_OK;
   }
   std::vector<double> ref;
@@ -1487,8 +1523,101 @@ int cgmr_close_scan_matching(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, cons
                              {step, step, cfg->theta_res, max_score, cfg->bin_x, cfg->bin_y, cfg->bin_theta}, res);
   if (rc) return rc;
   write_best(res, trel_out, found_out);
+  if (score_out && !res[0].empty()) *score_out = res[0][0].score;
   return CGMR_OK;
 }
+
+int cgmr_close_scan_matching(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const cgmr_scan_set* vset,
+                             const float* cur_ranges, const double cur_pose_xyt[3], double max_score, double trel_out[3],
+                             int* found_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  return close_scan_matching_core(ctx, cfg, vset, cur_ranges, cur_pose_xyt, max_score, trel_out, found_out, nullptr);
+}
+
+// ---- the response surface of a search (include/cgmr.h, "Scan-match covariance") ----------------------------------------------
+static int response_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::vector<SearchJob>& jobs, double step_x, double step_y,
+                          double theta_res, double T, const double* winners, const int* found, struct cgmr_match_response* out) {
+  std::vector<std::vector<cgmr_match_result>> none;
+  const ResponseSpec R = {T, winners, found, out};
+  // (no score bound and no result maps behind a response: the bins the tables lay out are one metre / radian wide and stay unused)
+  return greedy_batch_core(ctx, cfg, jobs, {step_x, step_y, theta_res, 0., 1., 1., 1.}, none, &R);
+}
+
+static bool temperature_ok(double T) { return std::isfinite(T) && T > 0; }
+
+int cgmr_match_response(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_ref, const double* ref_pts, int n_qry,
+                        const double* qry_pts, const float region[6], double step_x, double step_y, double theta_res, double T,
+                        const double winner[4], struct cgmr_match_response* out) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (!temperature_ok(T)) return set_err(ctx, CGMR_E_INVALID, "cgmr_match_response: the temperature must be positive and finite");
+  if (!cfg || !region || !winner || !out) return set_err(ctx, CGMR_E_INVALID, "cgmr_match_response: bad argument");
+  return response_batch(ctx, cfg, one_job(n_ref, ref_pts, n_qry, qry_pts, 1, region), step_x, step_y, theta_res, T, winner, nullptr, out);
+}
+
+int cgmr_match_response_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_response_job* jobs_in, double step_x,
+                              double step_y, double theta_res, double T, struct cgmr_match_response* out) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (!temperature_ok(T)) return set_err(ctx, CGMR_E_INVALID, "cgmr_match_response_batch: the temperature must be positive and finite");
+  if (!cfg || n_jobs < 0 || (n_jobs > 0 && (!jobs_in || !out))) return set_err(ctx, CGMR_E_INVALID, "cgmr_match_response_batch: bad argument");
+  if (n_jobs == 0) return CGMR_OK;
+  std::vector<SearchJob> jobs((size_t)n_jobs);
+  std::vector<double> winners(4 * (size_t)n_jobs);
+  std::vector<int> found((size_t)n_jobs);
+  for (int j = 0; j < n_jobs; j++) {
+    const cgmr_response_job& I = jobs_in[j];
+    if (I.n_regions != 1) return set_err(ctx, CGMR_E_INVALID, "cgmr_match_response_batch: job %d has %d regions, a response has exactly one", j, I.n_regions);
+    if (!I.regions) return set_err(ctx, CGMR_E_INVALID, "cgmr_match_response_batch: bad argument");
+    jobs[j].ref = I.ref_pts_xy; jobs[j].n_ref = I.n_ref; jobs[j].qry = I.qry_pts_xy; jobs[j].n_qry = I.n_qry;
+    jobs[j].regions = I.regions; jobs[j].n_regions = 1;
+    for (int q = 0; q < 4; q++) winners[4 * (size_t)j + q] = I.winner[q];
+    found[j] = I.found;
+  }
+  return response_batch(ctx, cfg, jobs, step_x, step_y, theta_res, T, winners.data(), found.data(), out);
+}
+
+int cgmr_close_scan_matching_cov(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const cgmr_scan_set* vset, const float* cur_ranges,
+                                 const double cur_pose_xyt[3], double max_score, double T, double trel_out[3], int* found_out,
+                                 double info_out[9], struct cgmr_match_response* resp_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (!temperature_ok(T)) return set_err(ctx, CGMR_E_INVALID, "cgmr_close_scan_matching_cov: the temperature must be positive and finite");
+  if (!info_out) return set_err(ctx, CGMR_E_INVALID, "cgmr_close_scan_matching_cov: bad argument");
+  struct cgmr_match_response resp;
+  memset(&resp, 0, sizeof resp);
+  resp.status = 2;
+  for (int q = 0; q < 9; q++) info_out[q] = 0;
+  if (resp_out) *resp_out = resp;
+  double score = 0;
+  int rc = close_scan_matching_core(ctx, cfg, vset, cur_ranges, cur_pose_xyt, max_score, trel_out, found_out, &score);
+  if (rc || !*found_out) return rc;
+  // the search's own window and points (the generic form of the call above: scan_matcher.cpp:119-151)
+  std::vector<double> ref;
+  points_from_vset(cfg, vset, nullptr, ref);
+  std::vector<double> qry;
+  apply_transf(se2_of(cfg->laser_pose), subsample_of(cartesian_of(cfg, cur_ranges), cfg->subsample_res), qry);
+  const Se2 g = se2_mul(se2_inv(se2_of(vset->poses_xyt + 3 * (size_t)vset->ref_index)), se2_of(cur_pose_xyt));
+  const float region[6] = {(float)(-cfg->win_x + g.x), (float)(-cfg->win_y + g.y), (float)(-cfg->win_theta + g.t),
+                           (float)(cfg->win_x + g.x),  (float)(cfg->win_y + g.y),  (float)(cfg->win_theta + g.t)};
+  const double step = (double)(float)cfg->resolution;
+  const double winner[4] = {trel_out[0], trel_out[1], trel_out[2], score};
+  rc = response_batch(ctx, cfg, one_job((int)(ref.size() / 2), ref.data(), (int)(qry.size() / 2), qry.data(), 1, region), step, step,
+                      cfg->theta_res, T, winner, nullptr, &resp);
+  if (rc) return rc;
+  memcpy(info_out, resp.info, sizeof resp.info);
+  if (resp_out) *resp_out = resp;
+  return CGMR_OK;
+}
+
+int cgmr_match_response_information(const double cov[9], double theta_star, double step_x_m, double step_y_m, double theta_res,
+                                    double info_out[9]) {
+  if (!cov || !info_out) return CGMR_E_INVALID;
+  for (int q = 0; q < 9; q++) info_out[q] = 0;
+  bool ok = std::isfinite(theta_star) && std::isfinite(step_x_m) && std::isfinite(step_y_m) && std::isfinite(theta_res);
+  for (int q = 0; q < 9; q++) ok = ok && std::isfinite(cov[q]);
+  if (!ok) return CGMR_E_INVALID;
+  return match_response_information(cov, std::cos(theta_star), std::sin(theta_star), step_x_m, step_y_m, theta_res, info_out) ? CGMR_OK
+                                                                                                                         : CGMR_E_INVALID;
+}
+
 
 int cgmr_scan_matching_lc_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
                                 const cgmr_scan_set* cur_sets, double max_score, double* trel_out, int* n_out) {

@@ -105,6 +105,50 @@ struct VerifyJob {
   int32_t lo_x, lo_y, hi_x, hi_y;            // countPoints window in cells
 };
 
+// The response surface of a correlative search (k_match_response / k_match_response_finish; the definition is in include/cgmr.h,
+// "Scan-match covariance"): what a workgroup leaves per launch, and the result of a job -- the layout of struct cgmr_match_response.
+constexpr int kRespSums = 12;                // mass, 3 first moments, 6 second moments (xx xy xt yy yt tt), border mass, candidate count
+struct MatchResponse {
+  double mean[3], cov[9], info[9];
+  double mass, border_mass;
+  int64_t n_candidates;
+  int32_t status, reserved;
+};
+
+// info = (J (cov + floor) J^T)^-1 with floor = diag(step_x^2, step_y^2, theta_res^2) / 12 and J = blockdiag(R(theta*)^T, 1), the inverse
+// by cofactors; cs / sn = cos / sin of theta*.  False (info left zero) when the matrix is not invertible in double.
+__host__ __device__ inline bool match_response_information(const double* cov, double cs, double sn, double step_x, double step_y,
+                                                           double theta_res, double* info) {
+  double C[3][3], M[3][3];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) C[i][j] = cov[3 * i + j];
+  C[0][0] += step_x * step_x / 12.;
+  C[1][1] += step_y * step_y / 12.;
+  C[2][2] += theta_res * theta_res / 12.;
+  const double J[3][3] = {{cs, sn, 0.}, {-sn, cs, 0.}, {0., 0., 1.}};
+  double JC[3][3];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) JC[i][j] = J[i][0] * C[0][j] + J[i][1] * C[1][j] + J[i][2] * C[2][j];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) M[i][j] = JC[i][0] * J[j][0] + JC[i][1] * J[j][1] + JC[i][2] * J[j][2];
+  const double c00 = M[1][1] * M[2][2] - M[1][2] * M[2][1], c01 = M[1][2] * M[2][0] - M[1][0] * M[2][2],
+               c02 = M[1][0] * M[2][1] - M[1][1] * M[2][0];
+  const double det = M[0][0] * c00 + M[0][1] * c01 + M[0][2] * c02;
+  for (int q = 0; q < 9; q++) info[q] = 0.;
+  if (!(det > 0.) || !(1. / det < 1.7976931348623157e308)) return false;
+  const double id = 1. / det;
+  info[0] = c00 * id;
+  info[1] = (M[0][2] * M[2][1] - M[0][1] * M[2][2]) * id;
+  info[2] = (M[0][1] * M[1][2] - M[0][2] * M[1][1]) * id;
+  info[3] = c01 * id;
+  info[4] = (M[0][0] * M[2][2] - M[0][2] * M[2][0]) * id;
+  info[5] = (M[0][2] * M[1][0] - M[0][0] * M[1][2]) * id;
+  info[6] = c02 * id;
+  info[7] = (M[0][1] * M[2][0] - M[0][0] * M[2][1]) * id;
+  info[8] = (M[0][0] * M[1][1] - M[0][1] * M[1][0]) * id;
+  return true;
+}
+
 size_t match_smem_bytes();
 void launch_match_verify(hipStream_t st, int n_jobs, const MatchParams& P, const VerifyJob* jobs, const double* pts2, const double* pts1,
                          double nonmatched_score, const uint8_t* kernel_lut, unsigned char* scratch, double* score_out,
@@ -113,6 +157,12 @@ void launch_match_greedy(hipStream_t st, int nblocks, const MatchParams& P, cons
                          const double* ref_pts, const double* qry_pts, const RegionDesc* regions, const double* theta,
                          const int32_t* items, const uint8_t* kernel_lut, unsigned char* scratch, unsigned long long* bins,
                          int* err, unsigned char* grid_cache = nullptr, size_t grid_cache_stride = 0, int grid_cache_mode = 0);
+// The response surface of every job of a k_match_greedy job table (one region per job): `partials` holds kRespSums doubles per
+// workgroup of the launch, winners 4 doubles (x, y, theta, score) and found one flag per job -- all device memory.
+void launch_match_response(hipStream_t st, int nblocks, int n_jobs, const MatchParams& P, const GreedyJob* jobs, const int32_t* block_job,
+                           const double* ref_pts, const double* qry_pts, const RegionDesc* regions, const double* theta,
+                           const int32_t* items, const uint8_t* kernel_lut, unsigned char* scratch, int* err, const double* winners,
+                           const int32_t* found, double temperature, double* partials, MatchResponse* out);
 size_t match_grid_image_bytes(const MatchParams& P);     // one job's slot in the grid cache (mode 1: the job's first workgroup stores
                                                          // the rasterised grid there, mode 2: every workgroup loads it instead of rasterising)
 void launch_hier_next(hipStream_t st, int n_jobs, const MatchParams& P, const HierStep& H, int* err);

@@ -2067,6 +2067,207 @@ __global__ __launch_bounds__(GR_THREADS) void k_match_greedy(MatchParams P, cons
 }
 
 
+// The response surface of a search (include/cgmr.h, "Scan-match covariance"): k_match_greedy's job table and front half -- the
+// job's workgroups rasterise its grid, build a work unit's kept-point list together and sum the cells of up to
+// kMatchCandPerPass candidates --, but every candidate counts: with the float score s_c of the reference read as double,
+// w_c = exp(-(s_c - s*) / T) and d_c = candidate - winner, a thread adds w_c, w_c d_c, w_c d_c d_c^T and the weight of the
+// candidates on the border of the search ranges to private double sums.  They meet across the wavefront by shuffles, across the
+// eight wavefronts in LDS in wavefront order, and leave the workgroup as ONE vector of kRespSums doubles: no floating-point
+// atomics, the same launch gives the same bits.  Every workgroup of the launch writes its vector (zeros when it had no unit,
+// or the search before found nothing: found[job] == 0).  One region per job; no result maps, no score bound.
+__global__ __launch_bounds__(GR_THREADS) void k_match_response(MatchParams P, const GreedyJob* __restrict__ jobs,
+                                                        const int32_t* __restrict__ block_job,
+                                                        const double* __restrict__ ref_pts_all,
+                                                        const double* __restrict__ qry_pts_all,
+                                                        const RegionDesc* __restrict__ regions,
+                                                        const double* __restrict__ theta,
+                                                        const int32_t* __restrict__ items,
+                                                        const uint8_t* __restrict__ kernel_lut,
+                                                        unsigned char* __restrict__ scratch, int* __restrict__ err,
+                                                        const double* __restrict__ winners, const int32_t* __restrict__ found,
+                                                        double temperature, double* __restrict__ partials) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  Smem& S = *reinterpret_cast<Smem*>(smem_raw);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int job = block_job[blockIdx.x];
+  const GreedyJob J = jobs[job];
+  const int jb = blockIdx.x - J.block0;                      // my index among the job's workgroups
+  const int npass = max(J.n_passes, 1);
+  double acc[kRespSums];
+#pragma unroll
+  for (int q = 0; q < kRespSums; q++) acc[q] = 0.;
+  if (J.n_items > 0 && (long long)jb < (long long)J.n_items * npass && found[job] != 0) {
+    const double wx0 = winners[4 * (size_t)job], wy0 = winners[4 * (size_t)job + 1], wt0 = winners[4 * (size_t)job + 2],
+                 ws0 = winners[4 * (size_t)job + 3];
+    const double* ref_pts = ref_pts_all + 2 * (size_t)J.ref_off;
+    const double* qry_pts = qry_pts_all + 2 * (size_t)J.qry_off;
+    unsigned char* my = scratch + (size_t)blockIdx.x * P.scratch_stride;
+    uint32_t* rcell = reinterpret_cast<uint32_t*>(my);                               // P.ref_cap packed cells
+    const uint32_t* gtiles = rcell + P.ref_cap;
+    const int nty = (P.ny + 7) >> 3;
+    const int DW = nty + kMatchDirGuardY;
+    for (int q = tid; q < P.kdim * P.kdim; q += GR_THREADS) S.kernel[q] = kernel_lut[q];
+    for (int i = tid; i < J.n_ref; i += GR_THREADS) rcell[i] = world_to_packed_cell(P, ref_pts[2 * i], ref_pts[2 * i + 1]);
+    __syncthreads();
+    build_grid<false>(S, P, rcell, J.n_ref, rcell + P.ref_cap, /*allow_fast=*/false, err);
+    const float ikscale = (float)(1. / (float)P.kscale);
+    uint32_t* const pl = &S.plist[0][0];
+    int* const totals = reinterpret_cast<int*>(&S.totals[0][0]);
+    const int cpp = P.cand_per_pass > 0 ? min(P.cand_per_pass, 64 * CAND_U) : 64 * CAND_U;
+    for (long long unit = jb; unit < (long long)J.n_items * npass; unit += J.n_blocks) {
+      const int it = (int)(unit / npass), pass = (int)(unit - (long long)it * npass);
+      const RegionDesc R = regions[items[2 * (size_t)(J.item_off + it)]];
+      const int ti = items[2 * (size_t)(J.item_off + it) + 1];
+      const int ncand = R.ni * R.nj;
+      if ((long long)pass * cpp >= ncand) continue;
+      const double t = theta[R.th_off + ti];
+      double sn, cs;
+      portable_sincos(t, &sn, &cs);
+      const int cb = pass * cpp;
+      const int nu = (min(ncand - cb, cpp) + 63) / 64;
+      int ci[CAND_U], cj[CAND_U], sum[CAND_U];
+#pragma unroll
+      for (int u = 0; u < CAND_U; u++) {
+        int cidx = cb + u * 64 + lane;
+        int a = cidx / R.nj, b = cidx - a * R.nj;
+        ci[u] = R.lo_x + a * P.x_steps;
+        cj[u] = R.lo_y + b * P.y_steps;
+        sum[u] = 0;
+      }
+      __syncthreads();                                            // (the previous unit's sums have been read)
+      for (int q = tid; q < 64 * CAND_U; q += GR_THREADS) totals[q] = 0;
+      // the unit's kept-point list and the cell sums over it: as k_match_greedy
+      int k = 0;
+      for (int c0 = 0; c0 < J.n_qry; c0 += kGrListCap) {
+        const int c1 = min(J.n_qry, c0 + kGrListCap);
+        __syncthreads();
+        if (tid == 0) S.misc[14] = 0;
+        __syncthreads();
+        for (int base = c0 + wave * 64; base < c1; base += GR_THREADS) {
+          const int q = base + lane;
+          const bool valid = q < c1;
+          uint32_t packed = 0;
+          if (valid) packed = turn_and_pack(P, qry_pts[2 * q], qry_pts[2 * q + 1], cs, sn);
+          uint32_t left = __shfl_up(packed, 1, 64);
+          if (lane == 0 && q > 0) left = turn_and_pack(P, qry_pts[2 * (q - 1)], qry_pts[2 * (q - 1) + 1], cs, sn);
+          const bool keep = valid && (q == 0 || packed != left);
+          const unsigned long long mask = __ballot(keep);
+          int wbase = 0;
+          if (lane == 0 && mask) wbase = atomicAdd(&S.misc[14], __popcll(mask));
+          wbase = __shfl(wbase, 0, 64);
+          if (keep) pl[wbase + __popcll(mask & ((1ULL << lane) - 1ULL))] = packed;
+        }
+        __syncthreads();
+        const int kc = S.misc[14];
+        const int q0 = (int)(((long long)kc * wave) / GR_WAVES), q1 = (int)(((long long)kc * (wave + 1)) / GR_WAVES);
+        if (nu <= 2)
+          for (int q = q0; q < q1; q += 4) gather_cells<2, 4>(S, P, gtiles, DW, pl, q, q1, ci, cj, sum);
+        else if (nu <= 4)
+          for (int q = q0; q < q1; q += 2) gather_cells<4, 2>(S, P, gtiles, DW, pl, q, q1, ci, cj, sum);
+        else
+          for (int q = q0; q < q1; q++) gather_cells<CAND_U, 1>(S, P, gtiles, DW, pl, q, q1, ci, cj, sum);
+        k += kc;
+      }
+      __syncthreads();                                            // (totals are zero)
+#pragma unroll
+      for (int u = 0; u < CAND_U; u++)
+        if (sum[u]) atomicAdd(&totals[u * 64 + lane], sum[u]);      // (integers: the order does not show)
+      __syncthreads();
+      if (k == 0) continue;                                       // no query point: the candidates of the unit are left out
+      const bool t_border = ti == 0 || ti == R.nth - 1;
+      const double dt = t - wt0;
+      for (int c = tid; c < min(cpp, ncand - cb); c += GR_THREADS) {
+        const int cidx = cb + c;
+        const int a = cidx / R.nj, b = cidx - a * R.nj;
+        const int cix = R.lo_x + a * P.x_steps, cjy = R.lo_y + b * P.y_steps;
+        float dsum = (float)totals[c] * ikscale;
+        dsum = (float)((double)dsum / (double)k);
+        const float wx = P.ll_x + (P.res * (float)cix);
+        const float wyy = P.ll_y + (P.res * (float)cjy);
+        const double w = exp(-((double)dsum - ws0) / temperature);
+        const double dx = (double)wx - wx0, dy = (double)wyy - wy0;
+        const double wdx = w * dx, wdy = w * dy, wdt = w * dt;
+        acc[0] += w;
+        acc[1] += wdx; acc[2] += wdy; acc[3] += wdt;
+        acc[4] += wdx * dx; acc[5] += wdx * dy; acc[6] += wdx * dt;
+        acc[7] += wdy * dy; acc[8] += wdy * dt; acc[9] += wdt * dt;
+        if (t_border || a == 0 || a == R.ni - 1 || b == 0 || b == R.nj - 1) acc[10] += w;
+        acc[11] += 1.;
+      }
+    }
+  }
+  // across the wavefront, then across the wavefronts in their order
+#pragma unroll
+  for (int q = 0; q < kRespSums; q++)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc[q] += __shfl_down(acc[q], off, 64);
+  double* const red = &S.theta_cs[0][0];                           // GR_WAVES x kRespSums doubles (the angle tables are the close matcher's)
+  static_assert(GR_WAVES * kRespSums <= MAXTHETA * 2, "wavefront sums of k_match_response");
+  __syncthreads();
+  if (lane == 0)
+#pragma unroll
+    for (int q = 0; q < kRespSums; q++) red[wave * kRespSums + q] = acc[q];
+  __syncthreads();
+  if (tid < kRespSums) {
+    double v = 0.;
+    for (int w = 0; w < GR_WAVES; w++) v += red[w * kRespSums + tid];
+    partials[(size_t)blockIdx.x * kRespSums + tid] = v;
+  }
+}
+
+// One thread per job: the job's workgroup vectors summed in workgroup order, then the moments, the quantisation floor, the
+// rotation into the measurement's frame and the inverse.  status 0 ok, 1 nothing counted (or a mass that is zero or not finite:
+// a winner far from every candidate's score), 2 skipped (found[job] == 0); a job with status != 0 is all zeros.
+__global__ __launch_bounds__(64) void k_match_response_finish(MatchParams P, int n_jobs, const GreedyJob* __restrict__ jobs,
+                                                               const double* __restrict__ winners,
+                                                               const int32_t* __restrict__ found,
+                                                               const double* __restrict__ partials,
+                                                               MatchResponse* __restrict__ out) {
+  const int job = blockIdx.x * 64 + threadIdx.x;
+  if (job >= n_jobs) return;
+  const GreedyJob J = jobs[job];
+  MatchResponse r;
+  for (int q = 0; q < 3; q++) r.mean[q] = 0.;
+  for (int q = 0; q < 9; q++) { r.cov[q] = 0.; r.info[q] = 0.; }
+  r.mass = 0.; r.border_mass = 0.; r.n_candidates = 0; r.status = 0; r.reserved = 0;
+  if (found[job] == 0) {
+    r.status = 2;
+    out[job] = r;
+    return;
+  }
+  double s[kRespSums];
+  for (int q = 0; q < kRespSums; q++) s[q] = 0.;
+  if (J.n_items > 0)
+    for (int b = 0; b < J.n_blocks; b++)
+      for (int q = 0; q < kRespSums; q++) s[q] += partials[(size_t)(J.block0 + b) * kRespSums + q];
+  const double mass = s[0];
+  if (!(s[11] > 0.) || !(mass > 0.) || !(mass <= 1.7976931348623157e308)) {
+    r.status = 1;
+    out[job] = r;
+    return;
+  }
+  const double u[3] = {s[1] / mass, s[2] / mass, s[3] / mass};
+  const double m2[3][3] = {{s[4], s[5], s[6]}, {s[5], s[7], s[8]}, {s[6], s[8], s[9]}};
+  for (int i = 0; i < 3; i++) {
+    r.mean[i] = winners[4 * (size_t)job + i] + u[i];
+    for (int j = 0; j < 3; j++) r.cov[3 * i + j] = m2[i][j] / mass - u[i] * u[j];
+  }
+  r.mass = mass;
+  r.border_mass = s[10] / mass;
+  r.n_candidates = (int64_t)s[11];
+  double sn, cs;
+  portable_sincos(winners[4 * (size_t)job + 2], &sn, &cs);
+  if (!match_response_information(r.cov, cs, sn, (double)P.x_steps * (double)P.res, (double)P.y_steps * (double)P.res, P.theta_res, r.info)) {
+    for (int q = 0; q < 3; q++) r.mean[q] = 0.;
+    for (int q = 0; q < 9; q++) r.cov[q] = 0.;
+    r.mass = 0.; r.border_mass = 0.; r.n_candidates = 0;
+    r.status = 1;
+  }
+  out[job] = r;
+}
+
+
 // Numeric core of ScanMatcher::verifyMatching (scan_matcher.cpp:430-505), one workgroup per job: grid from pts2, the
 // points of pts1 the grid does not explain, a second grid from those, mean cell value over a window.
 constexpr int VF_THREADS = 512;               // threads of k_match_verify (two rasterisations per job: they scale with the wavefronts)
@@ -2345,6 +2546,17 @@ void launch_match_greedy(hipStream_t st, int nblocks, const MatchParams& P, cons
   set_lds_attr_once<1>(reinterpret_cast<const void*>(k_match_greedy));
   hipLaunchKernelGGL(k_match_greedy, dim3(nblocks), dim3(GR_THREADS), sizeof(Smem), st, P, jobs, block_job, ref_pts, qry_pts, regions,
                      theta, items, kernel_lut, scratch, bins, err, grid_cache, grid_cache_stride, grid_cache_mode);
+}
+
+void launch_match_response(hipStream_t st, int nblocks, int n_jobs, const MatchParams& P, const GreedyJob* jobs, const int32_t* block_job,
+                           const double* ref_pts, const double* qry_pts, const RegionDesc* regions, const double* theta,
+                           const int32_t* items, const uint8_t* kernel_lut, unsigned char* scratch, int* err, const double* winners,
+                           const int32_t* found, double temperature, double* partials, MatchResponse* out) {
+  set_lds_attr_once<2>(reinterpret_cast<const void*>(k_match_response));
+  if (nblocks > 0)
+    hipLaunchKernelGGL(k_match_response, dim3(nblocks), dim3(GR_THREADS), sizeof(Smem), st, P, jobs, block_job, ref_pts, qry_pts, regions,
+                       theta, items, kernel_lut, scratch, err, winners, found, temperature, partials);
+  hipLaunchKernelGGL(k_match_response_finish, dim3((n_jobs + 63) / 64), dim3(64), 0, st, P, n_jobs, jobs, winners, found, partials, out);
 }
 
 size_t match_grid_image_bytes(const MatchParams& P) {

@@ -28,6 +28,25 @@ class MatchResult(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("theta", C.c_double), ("score", C.c_double)]
 
 
+class MatchResponse(C.Structure):
+    """``struct cgmr_match_response`` (include/cgmr.h): the response surface of a search, cov / info 3x3 row-major."""
+    _fields_ = [("mean", C.c_double * 3), ("cov", C.c_double * 9), ("info", C.c_double * 9), ("mass", C.c_double),
+                ("border_mass", C.c_double), ("n_candidates", C.c_int64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ResponseJob(C.Structure):
+    """``cgmr_response_job`` (include/cgmr.h)."""
+    _fields_ = [("n_ref", C.c_int), ("ref_pts_xy", C.c_void_p), ("n_qry", C.c_int), ("qry_pts_xy", C.c_void_p),
+                ("n_regions", C.c_int), ("regions", C.c_void_p), ("winner", C.c_double * 4), ("found", C.c_int)]
+
+
+def _response_dict(r):
+    """A MatchResponse as plain numpy values."""
+    return {"mean": np.array(r.mean[:]), "cov": np.array(r.cov[:]).reshape(3, 3), "info": np.array(r.info[:]).reshape(3, 3),
+            "mass": float(r.mass), "border_mass": float(r.border_mass), "n_candidates": int(r.n_candidates),
+            "status": int(r.status)}
+
+
 def _se2_mul(a, b):
     """g2o SE2 product: translation a.t + R(a.theta) b.t, angle normalised [g2o-recalled]."""
     import math
@@ -148,6 +167,51 @@ class _GenericSearch:
         m = min(n.value, cap)
         return np.array([[buf[k].x, buf[k].y, buf[k].theta, buf[k].score] for k in range(m)]).reshape(-1, 4)
 
+    # ---- the response surface of a search: the information matrix of the match itself (include/cgmr.h) -------
+    def matchResponse(self, ref_pts, qry_pts, region, thetaRes, T, winner, step=None):   # noqa: N802,N803
+        """The weighted second moments of the candidates of ``greedySearch`` over ONE region around ``winner`` =
+        (x*, y*, theta*, s*), at temperature ``T`` (metres of score; no default -- DESIGN.md).  Returns a dict: mean, cov,
+        info (3x3, info in the frame g2o's EdgeSE2 error lives in), mass, border_mass, n_candidates, status."""
+        ref = np.ascontiguousarray(ref_pts, dtype=np.float64).reshape(-1, 2)
+        qry = np.ascontiguousarray(qry_pts, dtype=np.float64).reshape(-1, 2)
+        reg = np.ascontiguousarray(region, dtype=np.float32).reshape(-1, 6)
+        if len(reg) != 1:
+            raise ValueError("a response has exactly one region")
+        win = np.ascontiguousarray(winner, dtype=np.float64).reshape(4)
+        step = float(np.float32(self.cfg.resolution)) if step is None else float(step)
+        out = MatchResponse()
+        rc = self.ctx.lib.cgmr_match_response(self.ctx.h, C.byref(self.cfg), C.c_int(len(ref)), C.c_void_p(ref.ctypes.data),
+                                              C.c_int(len(qry)), C.c_void_p(qry.ctypes.data), C.c_void_p(reg.ctypes.data),
+                                              C.c_double(step), C.c_double(step), C.c_double(thetaRes), C.c_double(T),
+                                              C.c_void_p(win.ctypes.data), C.byref(out))
+        self.ctx._check(rc)
+        return _response_dict(out)
+
+    def matchResponseBatch(self, jobs, thetaRes, T, step=None, raw=False):   # noqa: N802,N803
+        """``matchResponse`` for many searches in one launch.  ``jobs``: list of (ref_pts, qry_pts, region, winner) with
+        ``winner`` None for a search that found nothing (status 2).  ``raw``: the result structs' bytes instead of dicts."""
+        step = float(np.float32(self.cfg.resolution)) if step is None else float(step)
+        arr = (ResponseJob * max(len(jobs), 1))()
+        keep = []
+        for k, (ref_pts, qry_pts, region, winner) in enumerate(jobs):
+            ref = np.ascontiguousarray(ref_pts, dtype=np.float64).reshape(-1, 2)
+            qry = np.ascontiguousarray(qry_pts, dtype=np.float64).reshape(-1, 2)
+            reg = np.ascontiguousarray(region, dtype=np.float32).reshape(-1, 6)
+            keep.append((ref, qry, reg))
+            arr[k].n_ref, arr[k].ref_pts_xy = len(ref), ref.ctypes.data
+            arr[k].n_qry, arr[k].qry_pts_xy = len(qry), qry.ctypes.data
+            arr[k].n_regions, arr[k].regions = len(reg), reg.ctypes.data
+            arr[k].found = 0 if winner is None else 1
+            for q in range(4):
+                arr[k].winner[q] = 0.0 if winner is None else float(winner[q])
+        out = (MatchResponse * max(len(jobs), 1))()
+        rc = self.ctx.lib.cgmr_match_response_batch(self.ctx.h, C.byref(self.cfg), C.c_int(len(jobs)), arr, C.c_double(step),
+                                                    C.c_double(step), C.c_double(thetaRes), C.c_double(T), out)
+        self.ctx._check(rc)
+        if raw:
+            return bytes(out)[:C.sizeof(MatchResponse) * len(jobs)]
+        return [_response_dict(out[k]) for k in range(len(jobs))]
+
     # ---- ScanMatcher::scanMatchingLC (scan_matcher.cpp:201-294) ---------------------------------------------
     def scanMatchingLC(self, ref_scans, ref_index, cur_scans, cur_index, maxScore):   # noqa: N802,N803
         """Returns the list of SE2 (x, y, theta) the reference pushes into ``trel`` (0-2 entries)."""
@@ -184,14 +248,24 @@ class _GenericSearch:
         return (True, [out.copy()]) if found.value else (False, [])
 
     # ---- ScanMatcher::closeScanMatching with a multi-scan reference set (scan_matcher.cpp:112-189) ---------------
-    def closeScanMatchingVSet(self, ref_scans, origin_index, cur_ranges, cur_pose, maxScore=0.15):   # noqa: N802,N803
+    def closeScanMatchingVSet(self, ref_scans, origin_index, cur_ranges, cur_pose, maxScore=0.15, covariance_T=None):   # noqa: N802,N803
         """The reference's call shape: up to 6 reference scans (graph_slam.cpp:230-241) rasterised in the frame of the
-        origin vertex, the current scan subsampled, window around origin^-1 * current.  Returns (found, trel)."""
+        origin vertex, the current scan subsampled, window around origin^-1 * current.  Returns (found, trel).
+        With ``covariance_T`` (a temperature, see ``matchResponse``) the response surface of the same window is taken
+        behind the search: returns (found, trel, info, response) -- info 3x3, zeros unless response["status"] == 0."""
         a, ka = _scan_set(ref_scans, origin_index)
         cur = np.ascontiguousarray(cur_ranges, dtype=np.float32)
         pose = np.ascontiguousarray(cur_pose, dtype=np.float64)
         out = np.zeros(3)
         found = C.c_int(0)
+        if covariance_T is not None:
+            info, resp = np.zeros(9), MatchResponse()
+            rc = self.ctx.lib.cgmr_close_scan_matching_cov(self.ctx.h, C.byref(self.cfg), C.byref(a), C.c_void_p(cur.ctypes.data),
+                                                           C.c_void_p(pose.ctypes.data), C.c_double(maxScore),
+                                                           C.c_double(covariance_T), C.c_void_p(out.ctypes.data), C.byref(found),
+                                                           C.c_void_p(info.ctypes.data), C.byref(resp))
+            self.ctx._check(rc)
+            return (bool(found.value), out.copy() if found.value else None, info.reshape(3, 3), _response_dict(resp))
         rc = self.ctx.lib.cgmr_close_scan_matching(self.ctx.h, C.byref(self.cfg), C.byref(a), C.c_void_p(cur.ctypes.data),
                                                    C.c_void_p(pose.ctypes.data), C.c_double(maxScore),
                                                    C.c_void_p(out.ctypes.data), C.byref(found))

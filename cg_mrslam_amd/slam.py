@@ -213,7 +213,7 @@ class GraphSLAMDriver(GraphSLAM):
     ``covariance_estimate``."""
 
     def __init__(self, ctx, close_matcher, lc_matcher, idRobot=0, baseId=10000, windowLoopClosure=10, maxScore=0.15,   # noqa: N803
-                 inlierThreshold=2.0, minInliers=7):   # noqa: N803
+                 inlierThreshold=2.0, minInliers=7, sm_information="fixed"):   # noqa: N803
         g = PoseGraph(np.zeros(0, dtype=np.int32), np.zeros((0, 3)), np.zeros(0, dtype=np.uint8),
                       np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros((0, 3)), np.zeros((0, 6)))
         super().__init__(g, ctx=ctx)
@@ -234,6 +234,12 @@ class GraphSLAMDriver(GraphSLAM):
         self._last_vertex = None
         self._last_odom = None
         self.log = []
+        # information of a scan-match edge: "fixed" = the reference's constant _SMinf (graph_slam.cpp:246-249), ("response", T) = the
+        # information matrix of the match itself (matcher.matchResponse; T: its temperature, no default)
+        if sm_information != "fixed" and not (isinstance(sm_information, tuple) and len(sm_information) == 2 and
+                                              sm_information[0] == "response" and float(sm_information[1]) > 0):
+            raise ValueError('sm_information is "fixed" or ("response", T) with T > 0')
+        self.sm_information = sm_information
 
     # ------------------------------------------------------------------ graph bookkeeping
     def _index_of_id(self, vid):
@@ -302,9 +308,18 @@ class GraphSLAMDriver(GraphSLAM):
                 break
             vset.add(vj)
         order, scans = self._scans(vset)
-        found, transf = self.close_matcher.closeScanMatchingVSet(scans, order.index(last), ranges, curr_est, self.maxScore)
+        info = SM_INFO
+        if self.sm_information == "fixed":
+            found, transf = self.close_matcher.closeScanMatchingVSet(scans, order.index(last), ranges, curr_est, self.maxScore)
+        else:
+            found, transf, rinfo, resp = self.close_matcher.closeScanMatchingVSet(scans, order.index(last), ranges, curr_est, self.maxScore,
+                                                                                  covariance_T=float(self.sm_information[1]))
+            if found and resp["status"] == 0:
+                info = np.array([rinfo[0, 0], rinfo[0, 1], rinfo[0, 2], rinfo[1, 1], rinfo[1, 2], rinfo[2, 2]])
+            elif found:                                         # no usable response: the reference's constant
+                self.log.append(("sm_information_fallback", int(self.g.ids[v]), int(resp["status"])))
         if found:
-            self._add_edge(last, v, transf, SM_INFO, "sm", eid)
+            self._add_edge(last, v, transf, info, "sm", eid)
         else:                                                   # trust the odometry
             self._add_edge(last, v, displacement, ODOM_INFO, "odom", eid)
         self.log.append(("addDataSM", int(self.g.ids[v]), bool(found)))

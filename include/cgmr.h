@@ -570,6 +570,72 @@ int cgmr_scan_matching_lc_hierarchical_batch(cgmr_ctx* ctx, const cgmr_matcher_c
 int cgmr_verify_matching_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* sets1,
                                const cgmr_scan_set* sets2, const double* trel12, double* score_out, int* accepted_out);
 
+/* ------------------------------------------------------------------------------------------
+ * Scan-match covariance from the correlative search's response surface (C ABI version 105, added later under the same
+ * number: callers find it by its symbols).  The reference declares MatcherResult::informationMatrix
+ * (src/matcher/chargrid.h:50-60) and leaves it at identity; GraphSLAM::addDataSM writes the constant _SMinf onto every
+ * scan-match edge (src/slam/graph_slam.cpp:246-249).  These calls deliver the information matrix of the match itself.
+ *
+ * Definition.
+ * The inputs are the same as for `cgmr_match_greedy`, with exactly one region per job: reference points, query points, the region, `step_x`, `step_y` and `theta_res`. Two more inputs are added: a temperature `T > 0` in metres of score, and the winner `(x*, y*, θ*, s*)` that the preceding search returned.
+ *
+ * The candidates are exactly those of `CharGrid::greedySearch` (`chargrid.cpp:237-287`):
+ *
+ * - the angles `t = lower.θ; t < upper.θ; t += theta_res`, accumulated in double (the host's existing angle table);
+ * - the cells `i, j` from `world2grid(lower)` to `world2grid(upper)` in steps `xSteps`, `ySteps`;
+ * - the kept-point rule of `:246-256`.
+ *
+ * A candidate's score `s_c` is the reference's float32 `dsum`, read as double. Candidates with `k == 0` are left out. No `maxScore` cut is applied.
+ *
+ * With `w_c = exp(-(s_c - s*) / T)` and `d_c = (x_c - x*, y_c - y*, t_c - θ*)`, where `x_c`, `y_c` are the reference's float `grid2world` values read as double:
+ *
+ * - `mass = Σ w_c`
+ * - `u = Σ w_c d_c / mass`
+ * - `cov = Σ w_c d_c d_cᵀ / mass − u uᵀ`; centring the moments at the winner keeps this subtraction harmless
+ * - `mean = (x*, y*, θ*) + u`
+ * - `border_mass` is the share of `mass` on candidates whose `i`, `j` or angle index is the first or last of its range.
+ * - `floor = diag((xSteps·res)²/12, (ySteps·res)²/12, theta_res²/12)`, the variance of the search's own quantisation.
+ * - `info = (J (cov + floor) Jᵀ)⁻¹` with `J = blockdiag(R(θ*)ᵀ, 1)`. g2o's `EdgeSE2` error lives in the frame of the measurement's end, so the translation block is rotated into it.
+ *
+ * The output also carries `n_candidates` and a status: 0 means ok, 1 means no candidate was counted, and 2 means the job was skipped because the search found nothing. A job with status ≠ 0 returns zeros and never NaN.
+ *
+ * (`res` is the grid's float32 resolution read as double, as in grid2world.  Status 1 also covers a mass that is zero or not
+ * finite -- a winner whose score lies far from every candidate's -- and a matrix that cannot be inverted in double.)  `T` has no
+ * default: it is a modelling parameter to be calibrated on real scans.  cov and info are 3x3, row-major.  The same
+ * call made twice returns identical bits (no floating-point atomics; fixed summation order).
+ *
+ *   cgmr_match_response             one job: region [6] float32 as in cgmr_match_greedy, winner [4] = (x*, y*, theta*, s*)
+ *   cgmr_match_response_batch       n_jobs in one launch of each kernel; a job with found == 0 is skipped (status 2); n_regions
+ *                                   must be 1 (the field exists so that a caller's region list can be passed as it is)
+ *   cgmr_close_scan_matching_cov    cgmr_close_scan_matching, then the response over the window that search used (same host
+ *                                   arithmetic for the region and the points); info_out = the response's info, zeros when nothing
+ *                                   was found or the status is not 0; resp_out nullable
+ *   cgmr_match_response_information host only: info_out = (J (cov + floor) J^T)^-1 from cov, theta*, the steps in metres and
+ *                                   theta_res -- the finishing arithmetic of the calls above (CGMR_E_INVALID: not invertible)   */
+struct cgmr_match_response {
+  double mean[3], cov[9], info[9];
+  double mass, border_mass;
+  int64_t n_candidates;
+  int32_t status, reserved;
+};
+typedef struct cgmr_response_job {
+  int n_ref; const double* ref_pts_xy;
+  int n_qry; const double* qry_pts_xy;
+  int n_regions; const float* regions;       /* exactly one region */
+  double winner[4];
+  int found;
+} cgmr_response_job;
+int cgmr_match_response(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_ref, const double* ref_pts_xy, int n_qry,
+                        const double* qry_pts_xy, const float region[6], double step_x, double step_y, double theta_res, double T,
+                        const double winner[4], struct cgmr_match_response* out);
+int cgmr_match_response_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_response_job* jobs,
+                              double step_x, double step_y, double theta_res, double T, struct cgmr_match_response* out);
+int cgmr_close_scan_matching_cov(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const cgmr_scan_set* vset,
+                                 const float* cur_ranges, const double cur_pose_xyt[3], double max_score, double T,
+                                 double trel_out[3], int* found_out, double info_out[9], struct cgmr_match_response* resp_out);
+int cgmr_match_response_information(const double cov[9], double theta_star, double step_x_m, double step_y_m, double theta_res,
+                                    double info_out[9]);
+
 /* Host helpers with the reference's exact arithmetic (no GPU): RawLaser::cartesian [g2o-recalled] and
  * CharGrid::subsample (src/matcher/chargrid.cpp:61-122).  Both return the number of points written. */
 int cgmr_scan_cartesian(int n_beams, const float* ranges, double angle_min, double angle_inc, double max_range,

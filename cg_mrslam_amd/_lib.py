@@ -41,6 +41,7 @@ _SYMBOLS = [
     "cgmr_gn_optimize", "cgmr_gn_optimize_dev", "cgmr_gn_symbolic_info", "cgmr_gn_last_timing",
     "cgmr_set_profiling", "cgmr_gn_kernel_times", "cgmr_gn_kernel_times_ex",
     "cgmr_match_response", "cgmr_match_response_batch", "cgmr_close_scan_matching_cov", "cgmr_match_response_information",
+    "cgmr_refine_params_default", "cgmr_match_refine", "cgmr_match_refine_batch", "cgmr_close_scan_matching_refined",
 ]
 
 

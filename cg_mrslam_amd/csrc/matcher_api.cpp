@@ -848,10 +848,30 @@ struct ResponseSpec {
 static_assert(sizeof(struct cgmr_match_response) == sizeof(MatchResponse) && offsetof(struct cgmr_match_response, status) == offsetof(MatchResponse, status) &&
               offsetof(struct cgmr_match_response, mass) == offsetof(MatchResponse, mass), "cgmr_match_response is the kernels' MatchResponse");
 
+// With `refine` they serve the refinement of a match (k_match_refine: no regions, ONE workgroup per job whatever the tables say,
+// S's bound and bins unused): refine->out receives a result per job.  At most one of resp / refine.
+struct RefineSpec {
+  RefineParams params;
+  const double* winners;                     // [n_jobs * 4] (x, y, theta, score) of the search before
+  const int* found;                          // [n_jobs]: 0 -> status 2
+  struct cgmr_match_refined* out;            // [n_jobs]
+};
+static_assert(sizeof(struct cgmr_match_refined) == sizeof(MatchRefined) && offsetof(struct cgmr_match_refined, status) == offsetof(MatchRefined, status) &&
+              offsetof(struct cgmr_match_refined, hessian) == offsetof(MatchRefined, hessian) && sizeof(MatchRefined) % 8 == 0,
+              "cgmr_match_refined is the kernels' MatchRefined");
+static_assert(sizeof(cgmr_refine_params) == sizeof(RefineParams) && offsetof(cgmr_refine_params, bound_steps) == offsetof(RefineParams, bound_steps),
+              "cgmr_refine_params is the kernels' RefineParams");
+
 int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::vector<SearchJob>& jobs, const SearchSpec& S,
-                      std::vector<std::vector<cgmr_match_result>>& out, const ResponseSpec* resp = nullptr) {
+                      std::vector<std::vector<cgmr_match_result>>& out, const ResponseSpec* resp = nullptr, const RefineSpec* refine = nullptr) {
   const int nj = (int)jobs.size();
   out.assign(nj, {});
+  if (refine)
+    for (int j = 0; j < nj; j++) {
+      memset(&refine->out[j], 0, sizeof refine->out[j]);
+      for (int q = 0; q < 3; q++) refine->out[j].pose[q] = refine->winners[4 * (size_t)j + q];
+      refine->out[j].status = refine->found[j] ? 1 : 2;
+    }
   if (resp)
     for (int j = 0; j < nj; j++) {
       memset(&resp->out[j], 0, sizeof resp->out[j]);
@@ -870,14 +890,20 @@ int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::
   rc = greedy_tables(ctx, P, jobs, T);
   if (rc) return rc;
   P.cand_per_pass = T.cand_per_pass;
+  if (refine) {                                                    // one workgroup per job: workgroup j is job j
+    T.block_job.resize(nj);
+    for (int j = 0; j < nj; j++) { T.G[j].block0 = j; T.G[j].n_blocks = 1; T.block_job[j] = j; }
+    T.nblocks = nj;
+  }
   if (T.nblocks == 0) return CGMR_OK;
   set_greedy_scratch(P, T.max_ref);
   Layout L;
   const TableStage U(L, T, kern);
-  const size_t o_win = resp ? L.add(32 * (size_t)nj) : 0, o_found = resp ? L.add(4 * (size_t)nj) : 0;
+  const bool winners = resp || refine;
+  const size_t o_win = winners ? L.add(32 * (size_t)nj) : 0, o_found = winners ? L.add(4 * (size_t)nj) : 0;
   const size_t hbytes = L.off;
-  // the error word sits right in front of the result maps (the responses): one copy brings both back
-  const size_t back_bytes = 256 + (resp ? sizeof(MatchResponse) * (size_t)nj : 8 * T.total_bins);
+  // the error word sits right in front of the result maps (the responses, the refined matches): one copy brings both back
+  const size_t back_bytes = 256 + (resp ? sizeof(MatchResponse) * (size_t)nj : refine ? sizeof(MatchRefined) * (size_t)nj : 8 * T.total_bins);
   const size_t o_err = L.add(back_bytes), o_bins = o_err + 256, o_scratch = L.add(P.scratch_stride * (size_t)T.nblocks);
   const size_t o_part = resp ? L.add(8 * (size_t)kRespSums * (size_t)T.nblocks) : 0;
   rc = arena_reserve(ctx, ctx->mt_arena, L.off + 256);
@@ -891,11 +917,15 @@ int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::
     memcpy(h + o_win, resp->winners, 32 * (size_t)nj);
     for (int j = 0; j < nj; j++) reinterpret_cast<int32_t*>(h + o_found)[j] = (resp->found && !resp->found[j]) ? 0 : 1;
   }
+  if (refine) {
+    memcpy(h + o_win, refine->winners, 32 * (size_t)nj);
+    for (int j = 0; j < nj; j++) reinterpret_cast<int32_t*>(h + o_found)[j] = refine->found[j] ? 1 : 0;
+  }
   char* d = ctx->mt_arena.ptr;
   trace.staged = Clock::now();
   HIP_TRY(ctx, hipMemcpyAsync(d, h, hbytes, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(d + o_err, 0, 256, ctx->stream));
-  if (!resp) HIP_TRY(ctx, hipMemsetAsync(d + o_bins, 0xff, 8 * T.total_bins, ctx->stream));
+  if (!resp && !refine) HIP_TRY(ctx, hipMemsetAsync(d + o_bins, 0xff, 8 * T.total_bins, ctx->stream));
   rc = launches_begin(ctx);
   if (rc) return rc;
   if (resp)
@@ -904,6 +934,10 @@ int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::
                           (const double*)(d + U.o_th), (const int32_t*)(d + U.o_it), (const uint8_t*)(d + U.o_kern),
                           (unsigned char*)(d + o_scratch), (int*)(d + o_err), (const double*)(d + o_win), (const int32_t*)(d + o_found),
                           resp->T, (double*)(d + o_part), (MatchResponse*)(d + o_bins));
+  else if (refine)
+    launch_match_refine(ctx->stream, nj, P, (const GreedyJob*)(d + U.o_job), (const double*)(d + U.o_ref), (const double*)(d + U.o_q),
+                        (const uint8_t*)(d + U.o_kern), (unsigned char*)(d + o_scratch), (int*)(d + o_err), (const double*)(d + o_win),
+                        (const int32_t*)(d + o_found), refine->params, (MatchRefined*)(d + o_bins));
   else
     launch_match_greedy(ctx->stream, T.nblocks, P, (const GreedyJob*)(d + U.o_job), (const int32_t*)(d + U.o_bj), (const double*)(d + U.o_ref),
                         (const double*)(d + U.o_q), (const RegionDesc*)(d + U.o_reg), (const double*)(d + U.o_th),
@@ -915,6 +949,11 @@ int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::
   if (resp) {
     memcpy(resp->out, h + h_back + 256, sizeof(MatchResponse) * (size_t)nj);
     trace.print(ctx, "kernels", "[response] jobs %d blocks %d items %zu upload %zu B", nj, T.nblocks, T.items.size() / 2, hbytes);
+    return CGMR_OK;
+  }
+  if (refine) {
+    memcpy(refine->out, h + h_back + 256, sizeof(MatchRefined) * (size_t)nj);
+    trace.print(ctx, "kernel", "[refine] jobs %d blocks %d upload %zu B", nj, T.nblocks, hbytes);
     return CGMR_OK;
   }
   rc = greedy_decode(ctx, P, T, jobs, (const unsigned long long*)(h + h_back + 256), out);
@@ -1618,6 +1657,98 @@ int cgmr_match_response_information(const double cov[9], double theta_star, doub
                                                                                                                          : CGMR_E_INVALID;
 }
 
+
+// ---- refining a match below the grid's resolution (include/cgmr.h, "Refining a match") ---------------------------------------
+cgmr_refine_params cgmr_refine_params_default(void) {
+  cgmr_refine_params p;
+  p.max_iters = 10; p.max_halvings = 4; p.ridge = 1e-6; p.step_tol = 1e-6; p.bound_steps = 1.0;
+  return p;
+}
+
+// the parameter and winner checks of the three calls (no device touched); `name` heads the message
+static int refine_args_ok(cgmr_ctx* ctx, const char* name, const cgmr_refine_params* p, int n_winners, const double* winners, size_t stride) {
+  if (!p) return set_err(ctx, CGMR_E_INVALID, "%s: bad argument", name);
+  if (p->max_iters < 1 || p->max_iters > 64) return set_err(ctx, CGMR_E_INVALID, "%s: max_iters %d is outside 1..64", name, p->max_iters);
+  if (p->max_halvings < 0 || p->max_halvings > 16) return set_err(ctx, CGMR_E_INVALID, "%s: max_halvings %d is outside 0..16", name, p->max_halvings);
+  if (!std::isfinite(p->ridge) || p->ridge < 0) return set_err(ctx, CGMR_E_INVALID, "%s: the ridge must be finite and not negative", name);
+  if (!std::isfinite(p->step_tol) || !(p->step_tol > 0)) return set_err(ctx, CGMR_E_INVALID, "%s: step_tol must be positive and finite", name);
+  if (!std::isfinite(p->bound_steps) || !(p->bound_steps > 0)) return set_err(ctx, CGMR_E_INVALID, "%s: bound_steps must be positive and finite", name);
+  for (int j = 0; j < n_winners; j++)
+    for (int q = 0; q < 4; q++)
+      if (!std::isfinite(winners[stride * (size_t)j + q])) return set_err(ctx, CGMR_E_INVALID, "%s: the winner of job %d is not finite", name, j);
+  return CGMR_OK;
+}
+
+static int refine_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::vector<SearchJob>& jobs, double step_x, double step_y,
+                        double theta_res, const cgmr_refine_params& p, const double* winners, const int* found, struct cgmr_match_refined* out) {
+  std::vector<std::vector<cgmr_match_result>> none;
+  const RefineSpec R = {{p.max_iters, p.max_halvings, p.ridge, p.step_tol, p.bound_steps}, winners, found, out};
+  // (no regions, no score bound and no result maps behind a refinement: the bins are one metre / radian wide and stay unused)
+  return greedy_batch_core(ctx, cfg, jobs, {step_x, step_y, theta_res, 0., 1., 1., 1.}, none, nullptr, &R);
+}
+
+int cgmr_match_refine(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_ref, const double* ref_pts, int n_qry, const double* qry_pts,
+                      double step_x, double step_y, double theta_res, const double winner[4], int found, const cgmr_refine_params* params,
+                      struct cgmr_match_refined* out) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (!cfg || !winner || !out) return set_err(ctx, CGMR_E_INVALID, "cgmr_match_refine: bad argument");
+  int rc = refine_args_ok(ctx, "cgmr_match_refine", params, 1, winner, 4);
+  if (rc) return rc;
+  return refine_batch(ctx, cfg, one_job(n_ref, ref_pts, n_qry, qry_pts, 0, nullptr), step_x, step_y, theta_res, *params, winner, &found, out);
+}
+
+int cgmr_match_refine_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_refine_job* jobs_in, double step_x,
+                            double step_y, double theta_res, const cgmr_refine_params* params, struct cgmr_match_refined* out) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (!cfg || n_jobs < 0 || (n_jobs > 0 && (!jobs_in || !out))) return set_err(ctx, CGMR_E_INVALID, "cgmr_match_refine_batch: bad argument");
+  std::vector<SearchJob> jobs((size_t)n_jobs);
+  std::vector<double> winners(4 * (size_t)n_jobs);
+  std::vector<int> found((size_t)n_jobs);
+  for (int j = 0; j < n_jobs; j++) {
+    const cgmr_refine_job& I = jobs_in[j];
+    jobs[j].ref = I.ref_pts_xy; jobs[j].n_ref = I.n_ref; jobs[j].qry = I.qry_pts_xy; jobs[j].n_qry = I.n_qry;
+    for (int q = 0; q < 4; q++) winners[4 * (size_t)j + q] = I.winner[q];
+    found[j] = I.found;
+  }
+  int rc = refine_args_ok(ctx, "cgmr_match_refine_batch", params, n_jobs, winners.data(), 4);
+  if (rc) return rc;
+  if (n_jobs == 0) return CGMR_OK;
+  return refine_batch(ctx, cfg, jobs, step_x, step_y, theta_res, *params, winners.data(), found.data(), out);
+}
+
+int cgmr_close_scan_matching_refined(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const cgmr_scan_set* vset, const float* cur_ranges,
+                                     const double cur_pose_xyt[3], double max_score, const cgmr_refine_params* params, double trel_out[3],
+                                     double trel_search_out[3], int* found_out, struct cgmr_match_refined* refined_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  int rc = refine_args_ok(ctx, "cgmr_close_scan_matching_refined", params, 0, nullptr, 4);
+  if (rc) return rc;
+  double score = 0;
+  rc = close_scan_matching_core(ctx, cfg, vset, cur_ranges, cur_pose_xyt, max_score, trel_out, found_out, &score);
+  if (rc) return rc;
+  struct cgmr_match_refined ref;
+  memset(&ref, 0, sizeof ref);
+  for (int q = 0; q < 3; q++) ref.pose[q] = trel_out[q];
+  ref.status = 2;
+  if (trel_search_out) for (int q = 0; q < 3; q++) trel_search_out[q] = trel_out[q];
+  if (refined_out) *refined_out = ref;
+  if (!*found_out) return CGMR_OK;
+  // the points and the steps of cgmr_close_scan_matching_cov (the generic form of the search: scan_matcher.cpp:119-151)
+  std::vector<double> refp;
+  points_from_vset(cfg, vset, nullptr, refp);
+  std::vector<double> qry;
+  apply_transf(se2_of(cfg->laser_pose), subsample_of(cartesian_of(cfg, cur_ranges), cfg->subsample_res), qry);
+  const double step = (double)(float)cfg->resolution;
+  const double winner[4] = {trel_out[0], trel_out[1], trel_out[2], score};
+  const int found = 1;
+  rc = refine_args_ok(ctx, "cgmr_close_scan_matching_refined", params, 1, winner, 4);
+  if (rc) return rc;
+  rc = refine_batch(ctx, cfg, one_job((int)(refp.size() / 2), refp.data(), (int)(qry.size() / 2), qry.data(), 0, nullptr), step, step,
+                    cfg->theta_res, *params, winner, &found, &ref);
+  if (rc) return rc;
+  if (ref.status == 0) for (int q = 0; q < 3; q++) trel_out[q] = ref.pose[q];
+  if (refined_out) *refined_out = ref;
+  return CGMR_OK;
+}
 
 int cgmr_scan_matching_lc_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
                                 const cgmr_scan_set* cur_sets, double max_score, double* trel_out, int* n_out) {

@@ -149,6 +149,20 @@ __host__ __device__ inline bool match_response_information(const double* cov, do
   return true;
 }
 
+// Refining a match below the grid's resolution (k_match_refine; the definition is in include/cgmr.h, "Refining a match"): the
+// numerical settings of a launch and the result of a job -- the layouts of cgmr_refine_params and struct cgmr_match_refined.
+constexpr int kRefineSums = 12;              // cost, sum of r, b (3), H (xx xy xt yy yt tt), n_active
+struct RefineParams {
+  int32_t max_iters, max_halvings;
+  double ridge, step_tol, bound_steps;
+};
+struct MatchRefined {
+  double pose[3];
+  double cost0, cost, score0, score;
+  double hessian[9];
+  int32_t n_active, n_iters, n_halvings, stop, at_bound, status;
+};
+
 size_t match_smem_bytes();
 void launch_match_verify(hipStream_t st, int n_jobs, const MatchParams& P, const VerifyJob* jobs, const double* pts2, const double* pts1,
                          double nonmatched_score, const uint8_t* kernel_lut, unsigned char* scratch, double* score_out,
@@ -163,6 +177,11 @@ void launch_match_response(hipStream_t st, int nblocks, int n_jobs, const MatchP
                            const double* ref_pts, const double* qry_pts, const RegionDesc* regions, const double* theta,
                            const int32_t* items, const uint8_t* kernel_lut, unsigned char* scratch, int* err, const double* winners,
                            const int32_t* found, double temperature, double* partials, MatchResponse* out);
+// The refinement of every job of a k_match_greedy job table, ONE workgroup per job (n_jobs workgroups; the regions, angles and work
+// items of the table are not read): winners 4 doubles (x, y, theta, score) and found one flag per job -- all device memory.
+void launch_match_refine(hipStream_t st, int n_jobs, const MatchParams& P, const GreedyJob* jobs, const double* ref_pts,
+                         const double* qry_pts, const uint8_t* kernel_lut, unsigned char* scratch, int* err, const double* winners,
+                         const int32_t* found, const RefineParams& RP, MatchRefined* out);
 size_t match_grid_image_bytes(const MatchParams& P);     // one job's slot in the grid cache (mode 1: the job's first workgroup stores
                                                          // the rasterised grid there, mode 2: every workgroup loads it instead of rasterising)
 void launch_hier_next(hipStream_t st, int n_jobs, const MatchParams& P, const HierStep& H, int* err);

@@ -2268,6 +2268,165 @@ __global__ __launch_bounds__(64) void k_match_response_finish(MatchParams P, int
 }
 
 
+// Refining a match below the grid's resolution (include/cgmr.h, "Refining a match"): one evaluation of the sums at a pose.  A thread
+// takes every GR_THREADS-th query point: the point under the pose in grid coordinates, the four nodes around it through the tile
+// directory (grid_cell: LDS pool or overflow tiles), the bilinear value r and its exact gradient; a point whose four nodes are not
+// all on the grid counts the fill value and no gradient -- the test comes before any cell is read.  Twelve private double sums
+// (cost, sum of r, b, the upper triangle of H, n_active) meet across the wavefront by shuffles and across the eight wavefronts in
+// LDS in wavefront order; EVERY thread then adds the eight vectors in that order, so all of them hold the same bits and take the
+// same branches behind it.  No floating-point atomics.  Call by all threads of the workgroup (two barriers inside).
+__device__ __forceinline__ void refine_eval(Smem& S, const MatchParams& P, const uint32_t* gtiles, int DW, const double* __restrict__ qry_pts,
+                                            int n_qry, double x, double y, double th, double* tot) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double sn, cs;
+  portable_sincos(th, &sn, &cs);
+  const double llx = (double)P.ll_x, lly = (double)P.ll_y, res = (double)P.res, ks = (double)P.kscale;
+  const double fill = (double)P.fill / ks;
+  const double umax = (double)(P.nx - 1), vmax = (double)(P.ny - 1);
+  double acc[kRefineSums];
+#pragma unroll
+  for (int q = 0; q < kRefineSums; q++) acc[q] = 0.;
+  for (int q = tid; q < n_qry; q += GR_THREADS) {
+    const double qx = qry_pts[2 * q], qy = qry_pts[2 * q + 1];
+    const double rx = cs * qx - sn * qy, ry = sn * qx + cs * qy;
+    const double u = ((rx + x) - llx) / res, v = ((ry + y) - lly) / res;
+    double r = fill, gx = 0., gy = 0.;
+    if (u >= 0. && u < umax && v >= 0. && v < vmax) {             // 0 <= i0, i0 + 1 <= nx - 1 (false for a NaN)
+      const double fu = floor(u), fv = floor(v);
+      const int i0 = (int)fu, j0 = (int)fv;
+      const double a = u - fu, b = v - fv;
+      const double f00 = (double)grid_cell(S, P, gtiles, DW, i0, j0) / ks, f10 = (double)grid_cell(S, P, gtiles, DW, i0 + 1, j0) / ks;
+      const double f01 = (double)grid_cell(S, P, gtiles, DW, i0, j0 + 1) / ks, f11 = (double)grid_cell(S, P, gtiles, DW, i0 + 1, j0 + 1) / ks;
+      r = (1. - a) * (1. - b) * f00 + a * (1. - b) * f10 + (1. - a) * b * f01 + a * b * f11;
+      gx = ((1. - b) * (f10 - f00) + b * (f11 - f01)) / res;
+      gy = ((1. - a) * (f01 - f00) + a * (f11 - f10)) / res;
+    }
+    const double gt = gx * (-ry) + gy * rx;                        // J_q = (gx, gy, gt)
+    acc[0] += r * r; acc[1] += r;
+    acc[2] += gx * r; acc[3] += gy * r; acc[4] += gt * r;
+    acc[5] += gx * gx; acc[6] += gx * gy; acc[7] += gx * gt;
+    acc[8] += gy * gy; acc[9] += gy * gt; acc[10] += gt * gt;
+    if (gx != 0. || gy != 0.) acc[11] += 1.;
+  }
+#pragma unroll
+  for (int q = 0; q < kRefineSums; q++)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc[q] += __shfl_down(acc[q], off, 64);
+  double* const red = &S.theta_cs[0][0];                           // GR_WAVES x kRefineSums doubles (the angle tables are the close matcher's)
+  static_assert(GR_WAVES * kRefineSums <= MAXTHETA * 2, "wavefront sums of k_match_refine");
+  __syncthreads();                                                 // (the previous evaluation's vectors have been read)
+  if (lane == 0)
+#pragma unroll
+    for (int q = 0; q < kRefineSums; q++) red[wave * kRefineSums + q] = acc[q];
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < kRefineSums; q++) {
+    double v = 0.;
+    for (int w = 0; w < GR_WAVES; w++) v += red[w * kRefineSums + q];
+    tot[q] = v;
+  }
+}
+
+// One workgroup per job: k_match_response's front half (kernel table, reference points -> packed cells, build_grid into the LDS tiles
+// and the overflow tiles of the workgroup's scratch), then the damped Gauss-Newton loop of the definition on the field that sits there.
+// Every thread runs the loop's scalar part (a 3x3 solve by cofactors, the clipping, the comparisons) on the same totals; thread 0
+// writes the result.  At most 1 + max_iters * (max_halvings + 1) evaluations.  The pose is kept as winner + offset: clipping the
+// offset to +-bound makes the at_bound test exact.
+__global__ __launch_bounds__(GR_THREADS) void k_match_refine(MatchParams P, const GreedyJob* __restrict__ jobs,
+                                                      const double* __restrict__ ref_pts_all, const double* __restrict__ qry_pts_all,
+                                                      const uint8_t* __restrict__ kernel_lut, unsigned char* __restrict__ scratch,
+                                                      int* __restrict__ err, const double* __restrict__ winners,
+                                                      const int32_t* __restrict__ found, RefineParams RP, MatchRefined* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  Smem& S = *reinterpret_cast<Smem*>(smem_raw);
+  const int tid = threadIdx.x;
+  const int job = blockIdx.x;
+  const GreedyJob J = jobs[job];
+  const double win[3] = {winners[4 * (size_t)job], winners[4 * (size_t)job + 1], winners[4 * (size_t)job + 2]};
+  MatchRefined r;
+  for (int q = 0; q < 3; q++) r.pose[q] = win[q];
+  r.cost0 = 0.; r.cost = 0.; r.score0 = 0.; r.score = 0.;
+  for (int q = 0; q < 9; q++) r.hessian[q] = 0.;
+  r.n_active = 0; r.n_iters = 0; r.n_halvings = 0; r.stop = 0; r.at_bound = 0; r.status = 0;
+  if (found[job] == 0 || J.n_qry == 0) {                           // (the same for every thread of the workgroup)
+    r.status = found[job] == 0 ? 2 : 1;
+    if (tid == 0) out[job] = r;
+    return;
+  }
+  const double* ref_pts = ref_pts_all + 2 * (size_t)J.ref_off;
+  const double* qry_pts = qry_pts_all + 2 * (size_t)J.qry_off;
+  unsigned char* my = scratch + (size_t)blockIdx.x * P.scratch_stride;
+  uint32_t* rcell = reinterpret_cast<uint32_t*>(my);               // P.ref_cap packed cells
+  const uint32_t* gtiles = rcell + P.ref_cap;
+  const int DW = ((P.ny + 7) >> 3) + kMatchDirGuardY;
+  for (int q = tid; q < P.kdim * P.kdim; q += GR_THREADS) S.kernel[q] = kernel_lut[q];
+  for (int i = tid; i < J.n_ref; i += GR_THREADS) rcell[i] = world_to_packed_cell(P, ref_pts[2 * i], ref_pts[2 * i + 1]);
+  __syncthreads();
+  build_grid<false>(S, P, rcell, J.n_ref, rcell + P.ref_cap, /*allow_fast=*/false, err);
+
+  double cur[kRefineSums], cand[kRefineSums];
+  refine_eval(S, P, gtiles, DW, qry_pts, J.n_qry, win[0], win[1], win[2], cur);
+  if (!(cur[5] + cur[8] + cur[10] != 0.)) {                        // trace(H) == 0: no point has a gradient
+    r.status = 1;
+    if (tid == 0) out[job] = r;
+    return;
+  }
+  const double inv_n = 1. / (double)J.n_qry;
+  r.cost0 = cur[0];
+  r.score0 = cur[1] * inv_n;
+  const double bound[3] = {RP.bound_steps * ((double)P.x_steps * (double)P.res), RP.bound_steps * ((double)P.y_steps * (double)P.res),
+                           RP.bound_steps * P.theta_res};
+  double delta[3] = {0., 0., 0.}, pose[3] = {win[0], win[1], win[2]};
+  int n_iters = 0, n_halvings = 0, stop = 0;
+  for (int it = 0; it < RP.max_iters; it++) {
+    const double mu = RP.ridge * (cur[5] + cur[8] + cur[10]) / 3.;
+    const double a00 = cur[5] + mu, a01 = cur[6], a02 = cur[7], a11 = cur[8] + mu, a12 = cur[9], a22 = cur[10] + mu;
+    const double c00 = a11 * a22 - a12 * a12, c01 = a12 * a02 - a01 * a22, c02 = a01 * a12 - a11 * a02;
+    const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
+    const double det = a00 * c00 + a01 * c01 + a02 * c02;
+    double d[3] = {-(c00 * cur[2] + c01 * cur[3] + c02 * cur[4]) / det, -(c01 * cur[2] + c11 * cur[3] + c12 * cur[4]) / det,
+                   -(c02 * cur[2] + c12 * cur[3] + c22 * cur[4]) / det};
+    const double big = 1.7976931348623157e308;
+    if (!(fabs(d[0]) <= big) || !(fabs(d[1]) <= big) || !(fabs(d[2]) <= big)) { stop = 2; break; }   // a system that cannot be solved in double
+    const double size = fmax(fmax(fabs(d[0]) / bound[0], fabs(d[1]) / bound[1]), fabs(d[2]) / bound[2]);
+    if (size < RP.step_tol) { stop = 1; break; }
+    bool moved = false;
+    for (int h = 0; h <= RP.max_halvings; h++) {
+      double cd[3], c[3];
+      for (int k = 0; k < 3; k++) {
+        cd[k] = fmin(fmax(delta[k] + d[k], -bound[k]), bound[k]);
+        c[k] = win[k] + cd[k];
+      }
+      if (c[0] == pose[0] && c[1] == pose[1] && c[2] == pose[2]) { stop = 3; break; }
+      refine_eval(S, P, gtiles, DW, qry_pts, J.n_qry, c[0], c[1], c[2], cand);
+      if (cand[0] < cur[0]) {
+        for (int k = 0; k < 3; k++) { delta[k] = cd[k]; pose[k] = c[k]; }
+        for (int q = 0; q < kRefineSums; q++) cur[q] = cand[q];
+        moved = true;
+        n_iters++;
+        break;
+      }
+      for (int k = 0; k < 3; k++) d[k] *= 0.5;
+      n_halvings++;
+    }
+    if (stop == 3) break;
+    if (!moved) { stop = 2; break; }
+  }
+  for (int k = 0; k < 3; k++) {
+    r.pose[k] = pose[k];
+    if (fabs(delta[k]) == bound[k]) r.at_bound |= 1 << k;
+  }
+  r.cost = cur[0];
+  r.score = cur[1] * inv_n;
+  r.hessian[0] = cur[5]; r.hessian[1] = cur[6]; r.hessian[2] = cur[7];
+  r.hessian[3] = cur[6]; r.hessian[4] = cur[8]; r.hessian[5] = cur[9];
+  r.hessian[6] = cur[7]; r.hessian[7] = cur[9]; r.hessian[8] = cur[10];
+  r.n_active = (int32_t)cur[11];
+  r.n_iters = n_iters; r.n_halvings = n_halvings; r.stop = stop;
+  if (tid == 0) out[job] = r;
+}
+
+
 // Numeric core of ScanMatcher::verifyMatching (scan_matcher.cpp:430-505), one workgroup per job: grid from pts2, the
 // points of pts1 the grid does not explain, a second grid from those, mean cell value over a window.
 constexpr int VF_THREADS = 512;               // threads of k_match_verify (two rasterisations per job: they scale with the wavefronts)
@@ -2557,6 +2716,15 @@ void launch_match_response(hipStream_t st, int nblocks, int n_jobs, const MatchP
     hipLaunchKernelGGL(k_match_response, dim3(nblocks), dim3(GR_THREADS), sizeof(Smem), st, P, jobs, block_job, ref_pts, qry_pts, regions,
                        theta, items, kernel_lut, scratch, err, winners, found, temperature, partials);
   hipLaunchKernelGGL(k_match_response_finish, dim3((n_jobs + 63) / 64), dim3(64), 0, st, P, n_jobs, jobs, winners, found, partials, out);
+}
+
+void launch_match_refine(hipStream_t st, int n_jobs, const MatchParams& P, const GreedyJob* jobs, const double* ref_pts,
+                         const double* qry_pts, const uint8_t* kernel_lut, unsigned char* scratch, int* err, const double* winners,
+                         const int32_t* found, const RefineParams& RP, MatchRefined* out) {
+  set_lds_attr_once<3>(reinterpret_cast<const void*>(k_match_refine));
+  if (n_jobs > 0)
+    hipLaunchKernelGGL(k_match_refine, dim3(n_jobs), dim3(GR_THREADS), sizeof(Smem), st, P, jobs, ref_pts, qry_pts, kernel_lut, scratch, err,
+                       winners, found, RP, out);
 }
 
 size_t match_grid_image_bytes(const MatchParams& P) {

@@ -47,6 +47,50 @@ def _response_dict(r):
             "status": int(r.status)}
 
 
+class RefineParams(C.Structure):
+    """``cgmr_refine_params`` (include/cgmr.h): the numerical settings of a refinement.  ``RefineParams()`` holds the
+    defaults of ``cgmr_refine_params_default`` -- 10, 4, 1e-6, 1e-6, 1.0; keyword arguments replace single ones."""
+    _fields_ = [("max_iters", C.c_int32), ("max_halvings", C.c_int32), ("ridge", C.c_double), ("step_tol", C.c_double),
+                ("bound_steps", C.c_double)]
+
+    def __init__(self, **kw):
+        from ._lib import load_library
+        fn = load_library().cgmr_refine_params_default
+        fn.restype = _RefineParamsPod
+        d = fn()
+        super().__init__(d.max_iters, d.max_halvings, d.ridge, d.step_tol, d.bound_steps)
+        for k, v in kw.items():
+            if k not in ("max_iters", "max_halvings", "ridge", "step_tol", "bound_steps"):
+                raise TypeError(f"RefineParams has no field {k!r}")
+            setattr(self, k, v)
+
+
+class _RefineParamsPod(C.Structure):
+    """(the return type of ``cgmr_refine_params_default``: the fields without the constructor above)"""
+    _fields_ = RefineParams._fields_
+
+
+class MatchRefined(C.Structure):
+    """``struct cgmr_match_refined`` (include/cgmr.h): a match moved below the grid's resolution, hessian 3x3 row-major."""
+    _fields_ = [("pose", C.c_double * 3), ("cost0", C.c_double), ("cost", C.c_double), ("score0", C.c_double),
+                ("score", C.c_double), ("hessian", C.c_double * 9), ("n_active", C.c_int32), ("n_iters", C.c_int32),
+                ("n_halvings", C.c_int32), ("stop", C.c_int32), ("at_bound", C.c_int32), ("status", C.c_int32)]
+
+
+class RefineJob(C.Structure):
+    """``cgmr_refine_job`` (include/cgmr.h)."""
+    _fields_ = [("n_ref", C.c_int), ("ref_pts_xy", C.c_void_p), ("n_qry", C.c_int), ("qry_pts_xy", C.c_void_p),
+                ("winner", C.c_double * 4), ("found", C.c_int)]
+
+
+def _refined_dict(r):
+    """A MatchRefined as plain numpy values."""
+    return {"pose": np.array(r.pose[:]), "cost0": float(r.cost0), "cost": float(r.cost), "score0": float(r.score0),
+            "score": float(r.score), "hessian": np.array(r.hessian[:]).reshape(3, 3), "n_active": int(r.n_active),
+            "n_iters": int(r.n_iters), "n_halvings": int(r.n_halvings), "stop": int(r.stop), "at_bound": int(r.at_bound),
+            "status": int(r.status)}
+
+
 def _se2_mul(a, b):
     """g2o SE2 product: translation a.t + R(a.theta) b.t, angle normalised [g2o-recalled]."""
     import math
@@ -212,6 +256,50 @@ class _GenericSearch:
             return bytes(out)[:C.sizeof(MatchResponse) * len(jobs)]
         return [_response_dict(out[k]) for k in range(len(jobs))]
 
+    # ---- refining a match below the grid's resolution (include/cgmr.h, "Refining a match") -------------------
+    def matchRefine(self, ref_pts, qry_pts, thetaRes, winner, params=None, step=None, raw=False):   # noqa: N802,N803
+        """Damped Gauss-Newton on the bilinear distance field of ``ref_pts``, started at ``winner`` = (x*, y*, theta*, s*)
+        of the search before and kept within ``params.bound_steps`` search steps of it; ``winner`` None = the search
+        found nothing (status 2).  Returns a dict: pose, cost0, cost, score0, score, hessian (3x3), n_active, n_iters,
+        n_halvings, stop, at_bound, status (``raw``: the result struct's bytes instead).  The pose's cost is not higher
+        than the winner's; nothing more is promised."""
+        ref = np.ascontiguousarray(ref_pts, dtype=np.float64).reshape(-1, 2)
+        qry = np.ascontiguousarray(qry_pts, dtype=np.float64).reshape(-1, 2)
+        win = np.zeros(4) if winner is None else np.ascontiguousarray(winner, dtype=np.float64).reshape(4)
+        par = RefineParams() if params is None else params
+        step = float(np.float32(self.cfg.resolution)) if step is None else float(step)
+        out = MatchRefined()
+        rc = self.ctx.lib.cgmr_match_refine(self.ctx.h, C.byref(self.cfg), C.c_int(len(ref)), C.c_void_p(ref.ctypes.data),
+                                            C.c_int(len(qry)), C.c_void_p(qry.ctypes.data), C.c_double(step), C.c_double(step),
+                                            C.c_double(thetaRes), C.c_void_p(win.ctypes.data), C.c_int(0 if winner is None else 1),
+                                            C.byref(par), C.byref(out))
+        self.ctx._check(rc)
+        return bytes(out) if raw else _refined_dict(out)
+
+    def matchRefineBatch(self, jobs, thetaRes, params=None, step=None, raw=False):   # noqa: N802,N803
+        """``matchRefine`` for many matches in one launch, one workgroup each.  ``jobs``: list of (ref_pts, qry_pts, winner)
+        with ``winner`` None for a search that found nothing.  ``raw``: the result structs' bytes instead of dicts."""
+        par = RefineParams() if params is None else params
+        step = float(np.float32(self.cfg.resolution)) if step is None else float(step)
+        arr = (RefineJob * max(len(jobs), 1))()
+        keep = []
+        for k, (ref_pts, qry_pts, winner) in enumerate(jobs):
+            ref = np.ascontiguousarray(ref_pts, dtype=np.float64).reshape(-1, 2)
+            qry = np.ascontiguousarray(qry_pts, dtype=np.float64).reshape(-1, 2)
+            keep.append((ref, qry))
+            arr[k].n_ref, arr[k].ref_pts_xy = len(ref), ref.ctypes.data
+            arr[k].n_qry, arr[k].qry_pts_xy = len(qry), qry.ctypes.data
+            arr[k].found = 0 if winner is None else 1
+            for q in range(4):
+                arr[k].winner[q] = 0.0 if winner is None else float(winner[q])
+        out = (MatchRefined * max(len(jobs), 1))()
+        rc = self.ctx.lib.cgmr_match_refine_batch(self.ctx.h, C.byref(self.cfg), C.c_int(len(jobs)), arr, C.c_double(step),
+                                                  C.c_double(step), C.c_double(thetaRes), C.byref(par), out)
+        self.ctx._check(rc)
+        if raw:
+            return bytes(out)[:C.sizeof(MatchRefined) * len(jobs)]
+        return [_refined_dict(out[k]) for k in range(len(jobs))]
+
     # ---- ScanMatcher::scanMatchingLC (scan_matcher.cpp:201-294) ---------------------------------------------
     def scanMatchingLC(self, ref_scans, ref_index, cur_scans, cur_index, maxScore):   # noqa: N802,N803
         """Returns the list of SE2 (x, y, theta) the reference pushes into ``trel`` (0-2 entries)."""
@@ -248,16 +336,33 @@ class _GenericSearch:
         return (True, [out.copy()]) if found.value else (False, [])
 
     # ---- ScanMatcher::closeScanMatching with a multi-scan reference set (scan_matcher.cpp:112-189) ---------------
-    def closeScanMatchingVSet(self, ref_scans, origin_index, cur_ranges, cur_pose, maxScore=0.15, covariance_T=None):   # noqa: N802,N803
+    def closeScanMatchingVSet(self, ref_scans, origin_index, cur_ranges, cur_pose, maxScore=0.15, covariance_T=None, refine=None):   # noqa: N802,N803
         """The reference's call shape: up to 6 reference scans (graph_slam.cpp:230-241) rasterised in the frame of the
         origin vertex, the current scan subsampled, window around origin^-1 * current.  Returns (found, trel).
         With ``covariance_T`` (a temperature, see ``matchResponse``) the response surface of the same window is taken
-        behind the search: returns (found, trel, info, response) -- info 3x3, zeros unless response["status"] == 0."""
+        behind the search: returns (found, trel, info, response) -- info 3x3, zeros unless response["status"] == 0.
+        With ``refine`` (a ``RefineParams``, see ``matchRefine``) the winner is refined on the same points: ``trel`` is the
+        refined pose and the refinement's result dict comes last -- (found, trel, refined), or with ``covariance_T`` as
+        well (found, trel, info, response, refined), the response still taken around the search's winner.  The dict
+        carries the search's own winner as ``search``."""
         a, ka = _scan_set(ref_scans, origin_index)
         cur = np.ascontiguousarray(cur_ranges, dtype=np.float32)
         pose = np.ascontiguousarray(cur_pose, dtype=np.float64)
         out = np.zeros(3)
         found = C.c_int(0)
+        if refine is not None:
+            ref, search = MatchRefined(), np.zeros(3)
+            rc = self.ctx.lib.cgmr_close_scan_matching_refined(self.ctx.h, C.byref(self.cfg), C.byref(a), C.c_void_p(cur.ctypes.data),
+                                                               C.c_void_p(pose.ctypes.data), C.c_double(maxScore), C.byref(refine),
+                                                               C.c_void_p(out.ctypes.data), C.c_void_p(search.ctypes.data),
+                                                               C.byref(found), C.byref(ref))
+            self.ctx._check(rc)
+            refined = dict(_refined_dict(ref), search=search.copy() if found.value else None)
+            trel = out.copy() if found.value else None
+            if covariance_T is None:
+                return (bool(found.value), trel, refined)
+            _, _, info, resp = self.closeScanMatchingVSet(ref_scans, origin_index, cur_ranges, cur_pose, maxScore, covariance_T=covariance_T)
+            return (bool(found.value), trel, info, resp, refined)
         if covariance_T is not None:
             info, resp = np.zeros(9), MatchResponse()
             rc = self.ctx.lib.cgmr_close_scan_matching_cov(self.ctx.h, C.byref(self.cfg), C.byref(a), C.c_void_p(cur.ctypes.data),

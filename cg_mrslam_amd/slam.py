@@ -213,7 +213,7 @@ class GraphSLAMDriver(GraphSLAM):
     ``covariance_estimate``."""
 
     def __init__(self, ctx, close_matcher, lc_matcher, idRobot=0, baseId=10000, windowLoopClosure=10, maxScore=0.15,   # noqa: N803
-                 inlierThreshold=2.0, minInliers=7, sm_information="fixed"):   # noqa: N803
+                 inlierThreshold=2.0, minInliers=7, sm_information="fixed", sm_refine=None):   # noqa: N803
         g = PoseGraph(np.zeros(0, dtype=np.int32), np.zeros((0, 3)), np.zeros(0, dtype=np.uint8),
                       np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros((0, 3)), np.zeros((0, 6)))
         super().__init__(g, ctx=ctx)
@@ -240,6 +240,11 @@ class GraphSLAMDriver(GraphSLAM):
                                               sm_information[0] == "response" and float(sm_information[1]) > 0):
             raise ValueError('sm_information is "fixed" or ("response", T) with T > 0')
         self.sm_information = sm_information
+        # measurement of a scan-match edge: None = the search's winner, a cell of its grid (the reference); a matcher.RefineParams =
+        # the winner refined below the grid's resolution (matcher.matchRefine).  Loop-closure and inter-robot edges stay as they are.
+        if sm_refine is not None and not hasattr(sm_refine, "bound_steps"):
+            raise ValueError("sm_refine is None or a matcher.RefineParams")
+        self.sm_refine = sm_refine
 
     # ------------------------------------------------------------------ graph bookkeeping
     def _index_of_id(self, vid):
@@ -309,15 +314,24 @@ class GraphSLAMDriver(GraphSLAM):
             vset.add(vj)
         order, scans = self._scans(vset)
         info = SM_INFO
-        if self.sm_information == "fixed":
+        refined = None
+        if self.sm_information == "fixed" and self.sm_refine is None:
             found, transf = self.close_matcher.closeScanMatchingVSet(scans, order.index(last), ranges, curr_est, self.maxScore)
+        elif self.sm_information == "fixed":
+            found, transf, refined = self.close_matcher.closeScanMatchingVSet(scans, order.index(last), ranges, curr_est, self.maxScore,
+                                                                              refine=self.sm_refine)
         else:
-            found, transf, rinfo, resp = self.close_matcher.closeScanMatchingVSet(scans, order.index(last), ranges, curr_est, self.maxScore,
-                                                                                  covariance_T=float(self.sm_information[1]))
+            kw = {} if self.sm_refine is None else {"refine": self.sm_refine}
+            found, transf, rinfo, resp, *rest = self.close_matcher.closeScanMatchingVSet(scans, order.index(last), ranges, curr_est,
+                                                                                         self.maxScore,
+                                                                                         covariance_T=float(self.sm_information[1]), **kw)
+            refined = rest[0] if rest else None
             if found and resp["status"] == 0:
                 info = np.array([rinfo[0, 0], rinfo[0, 1], rinfo[0, 2], rinfo[1, 1], rinfo[1, 2], rinfo[2, 2]])
             elif found:                                         # no usable response: the reference's constant
                 self.log.append(("sm_information_fallback", int(self.g.ids[v]), int(resp["status"])))
+        if found and refined is not None:                       # (transf is the refined pose; the search's winner when the status is not 0)
+            self.log.append(("sm_refine", int(self.g.ids[v]), refined["status"], refined["stop"], refined["n_iters"], refined))
         if found:
             self._add_edge(last, v, transf, info, "sm", eid)
         else:                                                   # trust the odometry

@@ -636,6 +636,103 @@ int cgmr_close_scan_matching_cov(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, 
 int cgmr_match_response_information(const double cov[9], double theta_star, double step_x_m, double step_y_m, double theta_res,
                                     double info_out[9]);
 
+/* ------------------------------------------------------------------------------------------
+ * Refining a match below the grid's resolution (C ABI version 105, added later under the same number: callers find it by
+ * its symbols).  closeScanMatching returns the best cell of CharGrid::greedySearch (src/matcher/chargrid.cpp:237-287): a
+ * multiple of the grid's resolution and of theta_res, and GraphSLAM::addDataSM (src/slam/graph_slam.cpp:230-249) puts that
+ * rounding onto every scan-match edge.  These calls move the winner to where the distance field says the minimum is.  They
+ * promise a pose whose cost is not higher than the winner's, inside a stated bound; they do not promise accuracy (a field
+ * with gaps has a local minimum at every reference point: DESIGN.md 3.2).  Nothing else changes: the searches return the
+ * bits they returned before.
+ *
+ * Definition.
+ * Inputs: as for `cgmr_match_response` without the region -- config, reference points, query points, `step_x`, `step_y`,
+ * `theta_res` --, the winner `(x*, y*, θ*, s*)` with its `found` flag, and a parameter struct.
+ *
+ * Field.
+ * - `res`, `ll_x`, `ll_y` are the grid's float32 values read as double.
+ * - Node `(i, j)` lies at the world position `(ll_x + res·i, ll_y + res·j)`. This is `grid2world`, and the search's `world2grid` rounds to the nearest node.
+ * - The node carries `F[i][j] = cell(i, j) / kscale` metres.
+ * - `cell` is the rasterised grid of the reference points, exactly as the searches build it.
+ *
+ * Residual of a query point.
+ * - For query point `q` under pose `(x, y, θ)`: `w = R(θ) q + (x, y)`, `u = (w_x − ll_x) / res`, `v` likewise.
+ * - `i0 = floor(u)`, `a = u − i0`, `j0 = floor(v)`, `b = v − j0`.
+ * - The point is *inside* iff `0 ≤ i0`, `i0 + 1 ≤ nx − 1`, `0 ≤ j0`, `j0 + 1 ≤ ny − 1`.
+ * - Inside: `r` is the bilinear interpolation of the four nodes, and `∇r` is its exact gradient, `(∂r/∂u, ∂r/∂v) / res`.
+ * - Outside: `r = int(kernel_range·kscale) / kscale` and the gradient is zero.
+ * - This differs from the reference's `isInside`. `grid_cell` returns 0 off the grid, so the inside test comes before any cell is read.
+ * - Every query point counts. There is no kept-point rule and no `maxScore`.
+ * - `J_q = ∇rᵀ · [1 0 −(s q_x + c q_y); 0 1 (c q_x − s q_y)]`.
+ *
+ * Sums at a pose.
+ * - `cost = Σ r²`
+ * - `b = Σ J_qᵀ r`
+ * - `H = Σ J_qᵀ J_q`
+ * - `score = Σ r / n_qry`. This is comparable with the search's score but not equal to it.
+ * - `n_active` = the number of points with a non-zero gradient.
+ *
+ * Iteration.
+ * - Start at the winner, with `bound = bound_steps · (step_x_m, step_y_m, theta_res)`; `step_x_m = xSteps·res` as for the response.
+ * - Repeat up to `max_iters` times.
+ * - Form `μ = ridge · trace(H) / 3`.
+ * - Solve `d = −(H + μ I)⁻¹ b` directly in double.  A `d` that is not finite (a singular system) stops with code 2.
+ * - If `max_k |d_k| / bound_k < step_tol`, stop with code 1.
+ * - Otherwise try up to `max_halvings + 1` candidates `c = clip(pose + d, winner − bound, winner + bound)`, halving `d` after each failure.
+ * - If a `c` equals the current pose in all three coordinates exactly, stop with code 3.
+ * - If `cost(c) < cost`, move to `c`. Its sums are already known.
+ * - If no candidate is taken, stop with code 2.
+ * - If the iterations run out, stop with code 0.
+ * - The pose is kept as winner + offset and the offset is what is clipped, so that the `at_bound` test below is exact.
+ *
+ * Output (`struct cgmr_match_refined`).
+ * - `pose[3]`, `cost0` (at the winner), `cost`, `score0`, `score`.
+ * - `hessian[9]` = `H` at the final pose, row-major, without the ridge.
+ * - `n_active` at the final pose, `n_iters` (moves taken), `n_halvings` (candidates turned down), `stop`.
+ * - `at_bound`: bit k is set when `|pose_k − winner_k| == bound_k`.
+ * - `status`: 0 ok; 1 nothing to refine (`n_qry == 0` or `trace(H) == 0` at the winner); 2 skipped (`found == 0`).
+ * - With status ≠ 0, `pose` is the winner as given and everything else is zero. Never NaN.
+ * - The same call twice returns identical bits.
+ *
+ * Parameters.
+ * - `cgmr_refine_params { int32 max_iters; int32 max_halvings; double ridge, step_tol, bound_steps; }`.
+ * - `cgmr_refine_params_default()` fills in 10, 4, 1e-6, 1e-6, 1.0. These are numerical settings, not calibration.
+ * - Refused with `CGMR_E_INVALID` and a message: `max_iters` outside 1..64, `max_halvings` outside 0..16, a `ridge` that is
+ *   negative or not finite, a `step_tol` or `bound_steps` that is not positive and finite, a winner that is not finite.
+ *
+ *   cgmr_match_refine                 one job: winner [4] = (x*, y*, theta*, s*), found = the search's flag
+ *   cgmr_match_refine_batch           n_jobs in one launch, one workgroup each; a job with found == 0 is skipped (status 2)
+ *   cgmr_close_scan_matching_refined  cgmr_close_scan_matching, then the refinement with the points and steps
+ *                                     cgmr_close_scan_matching_cov uses: trel_out = the refined pose (the search's winner when
+ *                                     the status is not 0), trel_search_out (nullable) = the search's winner, found_out = the
+ *                                     search's flag, refined_out nullable                                                     */
+typedef struct cgmr_refine_params {
+  int32_t max_iters, max_halvings;
+  double ridge, step_tol, bound_steps;
+} cgmr_refine_params;
+struct cgmr_match_refined {
+  double pose[3];
+  double cost0, cost, score0, score;
+  double hessian[9];
+  int32_t n_active, n_iters, n_halvings, stop, at_bound, status;
+};
+typedef struct cgmr_refine_job {
+  int n_ref; const double* ref_pts_xy;
+  int n_qry; const double* qry_pts_xy;
+  double winner[4];
+  int found;
+} cgmr_refine_job;
+cgmr_refine_params cgmr_refine_params_default(void);
+int cgmr_match_refine(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_ref, const double* ref_pts_xy, int n_qry,
+                      const double* qry_pts_xy, double step_x, double step_y, double theta_res, const double winner[4], int found,
+                      const cgmr_refine_params* params, struct cgmr_match_refined* out);
+int cgmr_match_refine_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_refine_job* jobs, double step_x,
+                            double step_y, double theta_res, const cgmr_refine_params* params, struct cgmr_match_refined* out);
+int cgmr_close_scan_matching_refined(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const cgmr_scan_set* vset,
+                                     const float* cur_ranges, const double cur_pose_xyt[3], double max_score,
+                                     const cgmr_refine_params* params, double trel_out[3], double trel_search_out[3],
+                                     int* found_out, struct cgmr_match_refined* refined_out);
+
 /* Host helpers with the reference's exact arithmetic (no GPU): RawLaser::cartesian [g2o-recalled] and
  * CharGrid::subsample (src/matcher/chargrid.cpp:61-122).  Both return the number of points written. */
 int cgmr_scan_cartesian(int n_beams, const float* ranges, double angle_min, double angle_inc, double max_range,

@@ -42,6 +42,8 @@ _SYMBOLS = [
     "cgmr_set_profiling", "cgmr_gn_kernel_times", "cgmr_gn_kernel_times_ex",
     "cgmr_match_response", "cgmr_match_response_batch", "cgmr_close_scan_matching_cov", "cgmr_match_response_information",
     "cgmr_refine_params_default", "cgmr_match_refine", "cgmr_match_refine_batch", "cgmr_close_scan_matching_refined",
+    "cgmr_match_polish_batch", "cgmr_scan_matching_lc_polished_batch", "cgmr_scan_matching_lc_polished",
+    "cgmr_global_matching_polished_batch", "cgmr_global_matching_polished",
 ]
 
 

@@ -862,10 +862,40 @@ static_assert(sizeof(struct cgmr_match_refined) == sizeof(MatchRefined) && offse
 static_assert(sizeof(cgmr_refine_params) == sizeof(RefineParams) && offsetof(cgmr_refine_params, bound_steps) == offsetof(RefineParams, bound_steps),
               "cgmr_refine_params is the kernels' RefineParams");
 
+// With `polish` they serve both behind one rasterisation (k_match_polish: a job's regions are the windows around its winners, ONE
+// workgroup per job as for the refinement): polish->out receives kPolishMaxWinners results per job.  At most one of the three.
+struct PolishSpec {
+  double T;                                  // > 0: take the response; 0: not asked for
+  int do_refine;
+  RefineParams params;
+  const double* winners;                     // [n_jobs * kPolishMaxWinners * 4] (x, y, theta, score) of the search before
+  const int* n_winners;                      // [n_jobs]: 0..kPolishMaxWinners = the regions of the job
+  struct cgmr_match_polished* out;           // [n_jobs * kPolishMaxWinners]
+};
+static_assert(sizeof(struct cgmr_match_polished) == sizeof(MatchPolished) && offsetof(struct cgmr_match_polished, refined) == offsetof(MatchPolished, refined) &&
+              sizeof(MatchPolished) == sizeof(MatchResponse) + sizeof(MatchRefined) && CGMR_POLISH_MAX_WINNERS == kPolishMaxWinners,
+              "cgmr_match_polished is the kernels' MatchPolished");
+
+// what the polished calls leave for a winner before (or without) a launch: `asked` parts with nothing counted / nothing to refine
+// (status 1), the others "not asked for" (3), an entry without a winner skipped (2); refined.pose holds the winner
+void polish_prefill(struct cgmr_match_polished& e, const double* winner, bool want_response, bool want_refine) {
+  memset(&e, 0, sizeof e);
+  e.response.status = !winner ? 2 : (want_response ? 1 : 3);
+  e.refined.status = !winner ? 2 : (want_refine ? 1 : 3);
+  if (winner) for (int q = 0; q < 3; q++) e.refined.pose[q] = winner[q];
+}
+
 int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::vector<SearchJob>& jobs, const SearchSpec& S,
-                      std::vector<std::vector<cgmr_match_result>>& out, const ResponseSpec* resp = nullptr, const RefineSpec* refine = nullptr) {
+                      std::vector<std::vector<cgmr_match_result>>& out, const ResponseSpec* resp = nullptr, const RefineSpec* refine = nullptr,
+                      const PolishSpec* polish = nullptr) {
   const int nj = (int)jobs.size();
   out.assign(nj, {});
+  if (polish)
+    for (int j = 0; j < nj; j++)
+      for (int k = 0; k < kPolishMaxWinners; k++)
+        polish_prefill(polish->out[(size_t)kPolishMaxWinners * j + k],
+                       k < polish->n_winners[j] ? polish->winners + 4 * ((size_t)kPolishMaxWinners * j + k) : nullptr, polish->T > 0,
+                       polish->do_refine != 0);
   if (refine)
     for (int j = 0; j < nj; j++) {
       memset(&refine->out[j], 0, sizeof refine->out[j]);
@@ -886,11 +916,18 @@ int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::
   rc = setup_geometry(ctx, cfg, P, kern);
   if (rc) return rc;
   apply_search(P, S);
+  if (polish) P.cand_per_pass = kMatchCandPerPass;                 // (the one workgroup of a job walks every pass: the largest there is)
   GreedyTables T;
   rc = greedy_tables(ctx, P, jobs, T);
   if (rc) return rc;
   P.cand_per_pass = T.cand_per_pass;
-  if (refine) {                                                    // one workgroup per job: workgroup j is job j
+  if (polish)
+    for (int j = 0; j < nj; j++)
+      for (int r = T.first_region[j]; r < T.first_region[j] + jobs[j].n_regions; r++)
+        if ((long long)T.R[r].nth * T.R[r].ni * T.R[r].nj > kPolishMaxCandidates)
+          return set_err(ctx, CGMR_E_INVALID, "polish: the window of winner %d of job %d holds %lld candidates, more than %d", r - T.first_region[j],
+                         j, (long long)T.R[r].nth * T.R[r].ni * T.R[r].nj, kPolishMaxCandidates);
+  if (refine || polish) {                                          // one workgroup per job: workgroup j is job j
     T.block_job.resize(nj);
     for (int j = 0; j < nj; j++) { T.G[j].block0 = j; T.G[j].n_blocks = 1; T.block_job[j] = j; }
     T.nblocks = nj;
@@ -899,11 +936,13 @@ int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::
   set_greedy_scratch(P, T.max_ref);
   Layout L;
   const TableStage U(L, T, kern);
-  const bool winners = resp || refine;
-  const size_t o_win = winners ? L.add(32 * (size_t)nj) : 0, o_found = winners ? L.add(4 * (size_t)nj) : 0;
+  const bool winners = resp || refine || polish;
+  const size_t win_bytes = 32 * (size_t)nj * (polish ? kPolishMaxWinners : 1);
+  const size_t o_win = winners ? L.add(win_bytes) : 0, o_found = winners ? L.add(4 * (size_t)nj) : 0;
   const size_t hbytes = L.off;
   // the error word sits right in front of the result maps (the responses, the refined matches): one copy brings both back
-  const size_t back_bytes = 256 + (resp ? sizeof(MatchResponse) * (size_t)nj : refine ? sizeof(MatchRefined) * (size_t)nj : 8 * T.total_bins);
+  const size_t back_bytes = 256 + (resp ? sizeof(MatchResponse) * (size_t)nj : refine ? sizeof(MatchRefined) * (size_t)nj
+                                   : polish ? sizeof(MatchPolished) * (size_t)kPolishMaxWinners * (size_t)nj : 8 * T.total_bins);
   const size_t o_err = L.add(back_bytes), o_bins = o_err + 256, o_scratch = L.add(P.scratch_stride * (size_t)T.nblocks);
   const size_t o_part = resp ? L.add(8 * (size_t)kRespSums * (size_t)T.nblocks) : 0;
   rc = arena_reserve(ctx, ctx->mt_arena, L.off + 256);
@@ -921,11 +960,15 @@ int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::
     memcpy(h + o_win, refine->winners, 32 * (size_t)nj);
     for (int j = 0; j < nj; j++) reinterpret_cast<int32_t*>(h + o_found)[j] = refine->found[j] ? 1 : 0;
   }
+  if (polish) {
+    memcpy(h + o_win, polish->winners, win_bytes);
+    for (int j = 0; j < nj; j++) reinterpret_cast<int32_t*>(h + o_found)[j] = polish->n_winners[j];
+  }
   char* d = ctx->mt_arena.ptr;
   trace.staged = Clock::now();
   HIP_TRY(ctx, hipMemcpyAsync(d, h, hbytes, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(d + o_err, 0, 256, ctx->stream));
-  if (!resp && !refine) HIP_TRY(ctx, hipMemsetAsync(d + o_bins, 0xff, 8 * T.total_bins, ctx->stream));
+  if (!resp && !refine && !polish) HIP_TRY(ctx, hipMemsetAsync(d + o_bins, 0xff, 8 * T.total_bins, ctx->stream));
   rc = launches_begin(ctx);
   if (rc) return rc;
   if (resp)
@@ -938,6 +981,11 @@ int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::
     launch_match_refine(ctx->stream, nj, P, (const GreedyJob*)(d + U.o_job), (const double*)(d + U.o_ref), (const double*)(d + U.o_q),
                         (const uint8_t*)(d + U.o_kern), (unsigned char*)(d + o_scratch), (int*)(d + o_err), (const double*)(d + o_win),
                         (const int32_t*)(d + o_found), refine->params, (MatchRefined*)(d + o_bins));
+  else if (polish)
+    launch_match_polish(ctx->stream, nj, P, (const GreedyJob*)(d + U.o_job), (const double*)(d + U.o_ref), (const double*)(d + U.o_q),
+                        (const RegionDesc*)(d + U.o_reg), (const double*)(d + U.o_th), (const uint8_t*)(d + U.o_kern),
+                        (unsigned char*)(d + o_scratch), (int*)(d + o_err), (const double*)(d + o_win), (const int32_t*)(d + o_found),
+                        polish->T, polish->do_refine, polish->params, (MatchPolished*)(d + o_bins));
   else
     launch_match_greedy(ctx->stream, T.nblocks, P, (const GreedyJob*)(d + U.o_job), (const int32_t*)(d + U.o_bj), (const double*)(d + U.o_ref),
                         (const double*)(d + U.o_q), (const RegionDesc*)(d + U.o_reg), (const double*)(d + U.o_th),
@@ -954,6 +1002,11 @@ int greedy_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const std::
   if (refine) {
     memcpy(refine->out, h + h_back + 256, sizeof(MatchRefined) * (size_t)nj);
     trace.print(ctx, "kernel", "[refine] jobs %d blocks %d upload %zu B", nj, T.nblocks, hbytes);
+    return CGMR_OK;
+  }
+  if (polish) {
+    memcpy(polish->out, h + h_back + 256, sizeof(MatchPolished) * (size_t)kPolishMaxWinners * (size_t)nj);
+    trace.print(ctx, "kernel", "[polish] jobs %d regions %zu upload %zu B", nj, T.R.size(), hbytes);
     return CGMR_OK;
   }
   rc = greedy_decode(ctx, P, T, jobs, (const unsigned long long*)(h + h_back + 256), out);
@@ -1750,9 +1803,96 @@ int cgmr_close_scan_matching_refined(cgmr_ctx* ctx, const cgmr_matcher_config* c
   return CGMR_OK;
 }
 
-int cgmr_scan_matching_lc_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
-                                const cgmr_scan_set* cur_sets, double max_score, double* trel_out, int* n_out) {
+// ---- refinement and response of a search's results behind one rasterisation (include/cgmr.h, "Polishing a search's results") --
+// the parameter checks of the polished calls (no device touched); `name` heads the message
+static int polish_params_ok(cgmr_ctx* ctx, const char* name, const cgmr_polish_params* p) {
+  if (!p) return set_err(ctx, CGMR_E_INVALID, "%s: bad argument", name);
+  if (p->T != 0 && !temperature_ok(p->T)) return set_err(ctx, CGMR_E_INVALID, "%s: the temperature must be positive and finite, or 0 for no response", name);
+  for (int q = 0; q < 3; q++)
+    if (!std::isfinite(p->window[q]) || !(p->window[q] > 0))
+      return set_err(ctx, CGMR_E_INVALID, "%s: the half-widths of the window must be positive and finite", name);
+  if (p->refine != 0 && p->refine != 1) return set_err(ctx, CGMR_E_INVALID, "%s: refine must be 0 or 1", name);
+  if (p->refine) return refine_args_ok(ctx, name, &p->refine_params, 0, nullptr, 4);
+  return CGMR_OK;
+}
+
+// One polish job as the callers hold it: points, the winners as the search produced them
+struct PolishIn {
+  const double* ref = nullptr; int n_ref = 0;
+  const double* qry = nullptr; int n_qry = 0;
+  int n_winners = 0;
+  double winners[kPolishMaxWinners][4];
+};
+
+// `out`: kPolishMaxWinners entries per job
+static int polish_batch(cgmr_ctx* ctx, const char* name, const cgmr_matcher_config* cfg, const std::vector<PolishIn>& in, double step_x,
+                        double step_y, double theta_res, const cgmr_polish_params& p, struct cgmr_match_polished* out) {
+  const int nj = (int)in.size();
+  if (nj == 0) return CGMR_OK;
+  std::vector<SearchJob> jobs((size_t)nj);
+  std::vector<float> regions(6 * (size_t)kPolishMaxWinners * (size_t)nj, 0.f);
+  std::vector<double> winners(4 * (size_t)kPolishMaxWinners * (size_t)nj, 0.);
+  std::vector<int> n_winners((size_t)nj);
+  for (int j = 0; j < nj; j++) {
+    const PolishIn& I = in[j];
+    if (I.n_winners < 0 || I.n_winners > kPolishMaxWinners)
+      return set_err(ctx, CGMR_E_INVALID, "%s: job %d has %d winners, outside 0..%d", name, j, I.n_winners, kPolishMaxWinners);
+    float* rg = regions.data() + 6 * (size_t)kPolishMaxWinners * j;
+    for (int k = 0; k < I.n_winners; k++) {
+      for (int q = 0; q < 4; q++) {
+        if (!std::isfinite(I.winners[k][q])) return set_err(ctx, CGMR_E_INVALID, "%s: winner %d of job %d is not finite", name, k, j);
+        winners[4 * ((size_t)kPolishMaxWinners * j + k) + q] = I.winners[k][q];
+      }
+      // the window around the winner as the search produced it: the sums in double, narrowed to the regions' float once
+      for (int q = 0; q < 3; q++) {
+        rg[6 * k + q] = (float)(I.winners[k][q] - p.window[q]);
+        rg[6 * k + 3 + q] = (float)(I.winners[k][q] + p.window[q]);
+      }
+    }
+    jobs[j].ref = I.ref; jobs[j].n_ref = I.n_ref; jobs[j].qry = I.qry; jobs[j].n_qry = I.n_qry;
+    jobs[j].regions = rg; jobs[j].n_regions = p.T > 0 ? I.n_winners : 0;      // (no response: no window, no tables for it)
+    n_winners[j] = I.n_winners;
+  }
+  std::vector<std::vector<cgmr_match_result>> none;
+  const cgmr_refine_params& rp = p.refine_params;
+  const PolishSpec R = {p.T, p.refine, {rp.max_iters, rp.max_halvings, rp.ridge, rp.step_tol, rp.bound_steps}, winners.data(), n_winners.data(), out};
+  // (no score bound and no result maps: the bins the tables lay out are one metre / radian wide and stay unused)
+  return greedy_batch_core(ctx, cfg, jobs, {step_x, step_y, theta_res, 0., 1., 1., 1.}, none, nullptr, nullptr, &R);
+}
+
+int cgmr_match_polish_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_polish_job* jobs_in, double step_x,
+                            double step_y, double theta_res, const cgmr_polish_params* params, struct cgmr_match_polished* out) {
   if (!ctx) return CGMR_E_INVALID;
+  if (!cfg || n_jobs < 0 || (n_jobs > 0 && (!jobs_in || !out))) return set_err(ctx, CGMR_E_INVALID, "cgmr_match_polish_batch: bad argument");
+  int rc = polish_params_ok(ctx, "cgmr_match_polish_batch", params);
+  if (rc) return rc;
+  std::vector<PolishIn> in((size_t)n_jobs);
+  for (int j = 0; j < n_jobs; j++) {
+    const cgmr_polish_job& I = jobs_in[j];
+    in[j].ref = I.ref_pts_xy; in[j].n_ref = I.n_ref; in[j].qry = I.qry_pts_xy; in[j].n_qry = I.n_qry;
+    in[j].n_winners = I.n_winners;
+    memcpy(in[j].winners, I.winners, sizeof in[j].winners);
+  }
+  return polish_batch(ctx, "cgmr_match_polish_batch", cfg, in, step_x, step_y, theta_res, *params, out);
+}
+
+// the scan-set forms' way out: the first `per_job` of a job's kPolishMaxWinners entries, the angles normalised as the search's own
+static void polish_copy_out(const std::vector<struct cgmr_match_polished>& all, int n_jobs, int per_job, struct cgmr_match_polished* out) {
+  for (int j = 0; j < n_jobs; j++)
+    for (int k = 0; k < per_job; k++) {
+      struct cgmr_match_polished e = all[(size_t)kPolishMaxWinners * j + k];
+      e.response.mean[2] = norm_theta(e.response.mean[2]);
+      e.refined.pose[2] = norm_theta(e.refined.pose[2]);
+      out[(size_t)per_job * j + k] = e;
+    }
+}
+
+// cgmr_scan_matching_lc_batch; with `polish` every returned result is then polished in ONE launch on the same prepared points, with
+// the search's own score and the winner as the search produced it (before norm_theta): polished_out[j * 2 + k] belongs to
+// trel_out[j * 6 + 3 k]
+static int scan_matching_lc_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
+                                 const cgmr_scan_set* cur_sets, double max_score, double* trel_out, int* n_out,
+                                 const cgmr_polish_params* polish, struct cgmr_match_polished* polished_out) {
   int rc = check_set_batch(ctx, "cgmr_scan_matching_lc", cfg, n_jobs, ref_sets, cur_sets, trel_out, n_out);
   if (rc) return rc;
   struct Key { int a, b, c; bool operator<(const Key& o) const { return a != o.a ? a < o.a : (b != o.b ? b < o.b : c < o.c); } };
@@ -1810,7 +1950,53 @@ int cgmr_scan_matching_lc_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, i
     }
     n_out[j] = (int)mj.size();
   }
+  if (!polish) return CGMR_OK;
+  std::vector<PolishIn> in((size_t)n_jobs);
+  for (int j = 0; j < n_jobs; j++) {
+    const SearchJob J = pts.job(j, nullptr, 0);
+    in[j].ref = J.ref; in[j].n_ref = J.n_ref; in[j].qry = J.qry; in[j].n_qry = J.n_qry;
+    in[j].n_winners = (int)merged[j].size();
+    for (int k = 0; k < in[j].n_winners; k++) {
+      // the merged result is the best of one of the job's two searches: that search's own angle, before norm_theta
+      const cgmr_match_result& b = merged[j][k].second;
+      double raw_theta = b.theta;
+      for (int pass = 0; pass < 2; pass++) {
+        const std::vector<cgmr_match_result>& rj = res[(size_t)pass * n_jobs + j];
+        if (!rj.empty() && rj[0].x == b.x && rj[0].y == b.y && rj[0].score == b.score && norm_theta(rj[0].theta) == b.theta) { raw_theta = rj[0].theta; break; }
+      }
+      in[j].winners[k][0] = b.x; in[j].winners[k][1] = b.y; in[j].winners[k][2] = raw_theta; in[j].winners[k][3] = b.score;
+    }
+  }
+  std::vector<struct cgmr_match_polished> all((size_t)kPolishMaxWinners * (size_t)n_jobs);
+  rc = polish_batch(ctx, "cgmr_scan_matching_lc_polished", cfg, in, step, step, theta_res, *polish, all.data());
+  if (rc) return rc;
+  polish_copy_out(all, n_jobs, 2, polished_out);
   return CGMR_OK;
+}
+
+int cgmr_scan_matching_lc_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
+                                const cgmr_scan_set* cur_sets, double max_score, double* trel_out, int* n_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  return scan_matching_lc_core(ctx, cfg, n_jobs, ref_sets, cur_sets, max_score, trel_out, n_out, nullptr, nullptr);
+}
+
+int cgmr_scan_matching_lc_polished_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
+                                         const cgmr_scan_set* cur_sets, double max_score, const cgmr_polish_params* params, double* trel_out,
+                                         int* n_out, struct cgmr_match_polished* polished_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (n_jobs > 0 && !polished_out) return set_err(ctx, CGMR_E_INVALID, "cgmr_scan_matching_lc_polished: bad argument");
+  int rc = polish_params_ok(ctx, "cgmr_scan_matching_lc_polished", params);
+  if (rc) return rc;
+  return scan_matching_lc_core(ctx, cfg, n_jobs, ref_sets, cur_sets, max_score, trel_out, n_out, params, polished_out);
+}
+
+int cgmr_scan_matching_lc_polished(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const cgmr_scan_set* ref_set, const cgmr_scan_set* cur_set,
+                                   double max_score, const cgmr_polish_params* params, double* trel_out, int* n_out,
+                                   struct cgmr_match_polished* polished_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (!ref_set || !cur_set || !trel_out || !n_out || !polished_out) return set_err(ctx, CGMR_E_INVALID, "cgmr_scan_matching_lc_polished: bad argument");
+  *n_out = 0;
+  return cgmr_scan_matching_lc_polished_batch(ctx, cfg, 1, ref_set, cur_set, max_score, params, trel_out, n_out, polished_out);
 }
 
 int cgmr_scan_matching_lc(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const cgmr_scan_set* ref_set,
@@ -1821,9 +2007,10 @@ int cgmr_scan_matching_lc(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const c
   return cgmr_scan_matching_lc_batch(ctx, cfg, 1, ref_set, cur_set, max_score, trel_out, n_out);
 }
 
-int cgmr_global_matching_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
-                               const cgmr_scan_set* cur_sets, double max_score, double* trel_out, int* found_out) {
-  if (!ctx) return CGMR_E_INVALID;
+// cgmr_global_matching_batch; with `polish` the best result of every job is then polished in ONE launch on the same prepared points
+static int global_matching_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
+                                const cgmr_scan_set* cur_sets, double max_score, double* trel_out, int* found_out,
+                                const cgmr_polish_params* polish, struct cgmr_match_polished* polished_out) {
   int rc = check_set_batch(ctx, "cgmr_global_matching", cfg, n_jobs, ref_sets, cur_sets, trel_out, found_out);
   if (rc) return rc;
   const float pi_f = (float)3.14159265358979323846;
@@ -1842,7 +2029,44 @@ int cgmr_global_matching_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, in
     fprintf(stderr, "[global] %d jobs: points + subsample (helper threads) %.0f us, hierarchy %.0f us, total %.0f us\n", n_jobs, us_sets,
             us_since(t_hier), us_since(t_begin));
   write_best(res, trel_out, found_out);
+  if (!polish) return CGMR_OK;
+  std::vector<PolishIn> in((size_t)n_jobs);
+  for (int j = 0; j < n_jobs; j++) {
+    in[j].ref = jobs[j].ref; in[j].n_ref = jobs[j].n_ref; in[j].qry = jobs[j].qry; in[j].n_qry = jobs[j].n_qry;
+    in[j].n_winners = res[j].empty() ? 0 : 1;
+    if (!res[j].empty()) { in[j].winners[0][0] = res[j][0].x; in[j].winners[0][1] = res[j][0].y; in[j].winners[0][2] = res[j][0].theta; in[j].winners[0][3] = res[j][0].score; }
+  }
+  std::vector<struct cgmr_match_polished> all((size_t)kPolishMaxWinners * (size_t)n_jobs);
+  const double step = (double)(float)cfg->resolution;
+  rc = polish_batch(ctx, "cgmr_global_matching_polished", cfg, in, step, step, 0.025, *polish, all.data());
+  if (rc) return rc;
+  polish_copy_out(all, n_jobs, 1, polished_out);
   return CGMR_OK;
+}
+
+int cgmr_global_matching_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
+                               const cgmr_scan_set* cur_sets, double max_score, double* trel_out, int* found_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  return global_matching_core(ctx, cfg, n_jobs, ref_sets, cur_sets, max_score, trel_out, found_out, nullptr, nullptr);
+}
+
+int cgmr_global_matching_polished_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
+                                        const cgmr_scan_set* cur_sets, double max_score, const cgmr_polish_params* params, double* trel_out,
+                                        int* found_out, struct cgmr_match_polished* polished_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (n_jobs > 0 && !polished_out) return set_err(ctx, CGMR_E_INVALID, "cgmr_global_matching_polished: bad argument");
+  int rc = polish_params_ok(ctx, "cgmr_global_matching_polished", params);
+  if (rc) return rc;
+  return global_matching_core(ctx, cfg, n_jobs, ref_sets, cur_sets, max_score, trel_out, found_out, params, polished_out);
+}
+
+int cgmr_global_matching_polished(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const cgmr_scan_set* ref_set, const cgmr_scan_set* cur_set,
+                                  double max_score, const cgmr_polish_params* params, double trel_out[3], int* found_out,
+                                  struct cgmr_match_polished* polished_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (!ref_set || !cur_set || !trel_out || !found_out || !polished_out) return set_err(ctx, CGMR_E_INVALID, "cgmr_global_matching_polished: bad argument");
+  *found_out = 0;
+  return cgmr_global_matching_polished_batch(ctx, cfg, 1, ref_set, cur_set, max_score, params, trel_out, found_out, polished_out);
 }
 
 int cgmr_global_matching(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const cgmr_scan_set* ref_set,

@@ -163,6 +163,15 @@ struct MatchRefined {
   int32_t n_active, n_iters, n_halvings, stop, at_bound, status;
 };
 
+// Refinement and response of up to kPolishMaxWinners winners of a job behind one rasterisation (k_match_polish): the result of a
+// winner -- the layout of struct cgmr_match_polished.
+constexpr int kPolishMaxWinners = 4;
+constexpr int kPolishMaxCandidates = 65536;  // angles x cells of a winner's window: one workgroup sums them all
+struct MatchPolished {
+  MatchResponse response;
+  MatchRefined refined;
+};
+
 size_t match_smem_bytes();
 void launch_match_verify(hipStream_t st, int n_jobs, const MatchParams& P, const VerifyJob* jobs, const double* pts2, const double* pts1,
                          double nonmatched_score, const uint8_t* kernel_lut, unsigned char* scratch, double* score_out,
@@ -182,6 +191,13 @@ void launch_match_response(hipStream_t st, int nblocks, int n_jobs, const MatchP
 void launch_match_refine(hipStream_t st, int n_jobs, const MatchParams& P, const GreedyJob* jobs, const double* ref_pts,
                          const double* qry_pts, const uint8_t* kernel_lut, unsigned char* scratch, int* err, const double* winners,
                          const int32_t* found, const RefineParams& RP, MatchRefined* out);
+// Refinement and response of every job's winners, ONE workgroup per job (n_jobs workgroups): the job's regions are its winners'
+// windows, winners kPolishMaxWinners x 4 doubles and n_winners one count per job, out kPolishMaxWinners results per job -- all
+// device memory.  temperature > 0: take the response; do_refine: refine with RP.
+void launch_match_polish(hipStream_t st, int n_jobs, const MatchParams& P, const GreedyJob* jobs, const double* ref_pts,
+                         const double* qry_pts, const RegionDesc* regions, const double* theta, const uint8_t* kernel_lut,
+                         unsigned char* scratch, int* err, const double* winners, const int32_t* n_winners, double temperature,
+                         int do_refine, const RefineParams& RP, MatchPolished* out);
 size_t match_grid_image_bytes(const MatchParams& P);     // one job's slot in the grid cache (mode 1: the job's first workgroup stores
                                                          // the rasterised grid there, mode 2: every workgroup loads it instead of rasterising)
 void launch_hier_next(hipStream_t st, int n_jobs, const MatchParams& P, const HierStep& H, int* err);

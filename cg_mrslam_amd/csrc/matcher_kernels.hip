@@ -2067,6 +2067,147 @@ __global__ __launch_bounds__(GR_THREADS) void k_match_greedy(MatchParams P, cons
 }
 
 
+// One work unit of the response surface, by all threads of the workgroup: angle ti of region R, candidate pass `pass` of cpp
+// candidates (barriers inside).  The unit's kept-point list and the cell sums over it as k_match_greedy forms them, then every
+// candidate's weight into the thread's private sums acc.  A pass beyond the region's candidates, or an angle without a query point,
+// adds nothing.
+__device__ __forceinline__ void response_unit(Smem& S, const MatchParams& P, const uint32_t* gtiles, int DW, const double* __restrict__ qry_pts,
+                                              int n_qry, const RegionDesc& R, int ti, int pass, int cpp, double t, double wx0, double wy0,
+                                              double wt0, double ws0, double temperature, double (&acc)[kRespSums]) {
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const float ikscale = (float)(1. / (float)P.kscale);
+  uint32_t* const pl = &S.plist[0][0];
+  int* const totals = reinterpret_cast<int*>(&S.totals[0][0]);
+  const int ncand = R.ni * R.nj;
+  if ((long long)pass * cpp >= ncand) return;
+  double sn, cs;
+  portable_sincos(t, &sn, &cs);
+  const int cb = pass * cpp;
+  const int nu = (min(ncand - cb, cpp) + 63) / 64;
+  int ci[CAND_U], cj[CAND_U], sum[CAND_U];
+#pragma unroll
+  for (int u = 0; u < CAND_U; u++) {
+    int cidx = cb + u * 64 + lane;
+    int a = cidx / R.nj, b = cidx - a * R.nj;
+    ci[u] = R.lo_x + a * P.x_steps;
+    cj[u] = R.lo_y + b * P.y_steps;
+    sum[u] = 0;
+  }
+  __syncthreads();                                            // (the previous unit's sums have been read)
+  for (int q = tid; q < 64 * CAND_U; q += GR_THREADS) totals[q] = 0;
+  // the unit's kept-point list and the cell sums over it: as k_match_greedy
+  int k = 0;
+  for (int c0 = 0; c0 < n_qry; c0 += kGrListCap) {
+    const int c1 = min(n_qry, c0 + kGrListCap);
+    __syncthreads();
+    if (tid == 0) S.misc[14] = 0;
+    __syncthreads();
+    for (int base = c0 + wave * 64; base < c1; base += GR_THREADS) {
+      const int q = base + lane;
+      const bool valid = q < c1;
+      uint32_t packed = 0;
+      if (valid) packed = turn_and_pack(P, qry_pts[2 * q], qry_pts[2 * q + 1], cs, sn);
+      uint32_t left = __shfl_up(packed, 1, 64);
+      if (lane == 0 && q > 0) left = turn_and_pack(P, qry_pts[2 * (q - 1)], qry_pts[2 * (q - 1) + 1], cs, sn);
+      const bool keep = valid && (q == 0 || packed != left);
+      const unsigned long long mask = __ballot(keep);
+      int wbase = 0;
+      if (lane == 0 && mask) wbase = atomicAdd(&S.misc[14], __popcll(mask));
+      wbase = __shfl(wbase, 0, 64);
+      if (keep) pl[wbase + __popcll(mask & ((1ULL << lane) - 1ULL))] = packed;
+    }
+    __syncthreads();
+    const int kc = S.misc[14];
+    const int q0 = (int)(((long long)kc * wave) / GR_WAVES), q1 = (int)(((long long)kc * (wave + 1)) / GR_WAVES);
+    if (nu <= 2)
+      for (int q = q0; q < q1; q += 4) gather_cells<2, 4>(S, P, gtiles, DW, pl, q, q1, ci, cj, sum);
+    else if (nu <= 4)
+      for (int q = q0; q < q1; q += 2) gather_cells<4, 2>(S, P, gtiles, DW, pl, q, q1, ci, cj, sum);
+    else
+      for (int q = q0; q < q1; q++) gather_cells<CAND_U, 1>(S, P, gtiles, DW, pl, q, q1, ci, cj, sum);
+    k += kc;
+  }
+  __syncthreads();                                            // (totals are zero)
+#pragma unroll
+  for (int u = 0; u < CAND_U; u++)
+    if (sum[u]) atomicAdd(&totals[u * 64 + lane], sum[u]);      // (integers: the order does not show)
+  __syncthreads();
+  if (k == 0) return;                                         // no query point: the candidates of the unit are left out
+  const bool t_border = ti == 0 || ti == R.nth - 1;
+  const double dt = t - wt0;
+  for (int c = tid; c < min(cpp, ncand - cb); c += GR_THREADS) {
+    const int cidx = cb + c;
+    const int a = cidx / R.nj, b = cidx - a * R.nj;
+    const int cix = R.lo_x + a * P.x_steps, cjy = R.lo_y + b * P.y_steps;
+    float dsum = (float)totals[c] * ikscale;
+    dsum = (float)((double)dsum / (double)k);
+    const float wx = P.ll_x + (P.res * (float)cix);
+    const float wyy = P.ll_y + (P.res * (float)cjy);
+    const double w = exp(-((double)dsum - ws0) / temperature);
+    const double dx = (double)wx - wx0, dy = (double)wyy - wy0;
+    const double wdx = w * dx, wdy = w * dy, wdt = w * dt;
+    acc[0] += w;
+    acc[1] += wdx; acc[2] += wdy; acc[3] += wdt;
+    acc[4] += wdx * dx; acc[5] += wdx * dy; acc[6] += wdx * dt;
+    acc[7] += wdy * dy; acc[8] += wdy * dt; acc[9] += wdt * dt;
+    if (t_border || a == 0 || a == R.ni - 1 || b == 0 || b == R.nj - 1) acc[10] += w;
+    acc[11] += 1.;
+  }
+}
+
+// The threads' private sums across the wavefront by shuffles, then one vector per wavefront in LDS: on return (two barriers inside)
+// red[w * kRespSums + q] holds sum q of wavefront w; whoever adds them takes them in wavefront order.
+__device__ __forceinline__ const double* response_wave_sums(Smem& S, double (&acc)[kRespSums]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < kRespSums; q++)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc[q] += __shfl_down(acc[q], off, 64);
+  double* const red = &S.theta_cs[0][0];                           // GR_WAVES x kRespSums doubles (the angle tables are the close matcher's)
+  static_assert(GR_WAVES * kRespSums <= MAXTHETA * 2, "wavefront sums of the response surface");
+  __syncthreads();
+  if (lane == 0)
+#pragma unroll
+    for (int q = 0; q < kRespSums; q++) red[wave * kRespSums + q] = acc[q];
+  __syncthreads();
+  return red;
+}
+
+// The sums of a job -> its result: the moments, the quantisation floor, the rotation into the measurement's frame and the inverse.
+// r arrives all zero; status 1 (everything left zero) when nothing was counted, the mass is zero or not finite, or the matrix cannot
+// be inverted in double.  win = (x*, y*, theta*) of the search.
+__device__ __forceinline__ void response_finish_sums(const MatchParams& P, const double (&s)[kRespSums], const double* win, MatchResponse& r) {
+  const double mass = s[0];
+  if (!(s[11] > 0.) || !(mass > 0.) || !(mass <= 1.7976931348623157e308)) {
+    r.status = 1;
+    return;
+  }
+  const double u[3] = {s[1] / mass, s[2] / mass, s[3] / mass};
+  const double m2[3][3] = {{s[4], s[5], s[6]}, {s[5], s[7], s[8]}, {s[6], s[8], s[9]}};
+  for (int i = 0; i < 3; i++) {
+    r.mean[i] = win[i] + u[i];
+    for (int j = 0; j < 3; j++) r.cov[3 * i + j] = m2[i][j] / mass - u[i] * u[j];
+  }
+  r.mass = mass;
+  r.border_mass = s[10] / mass;
+  r.n_candidates = (int64_t)s[11];
+  double sn, cs;
+  portable_sincos(win[2], &sn, &cs);
+  if (!match_response_information(r.cov, cs, sn, (double)P.x_steps * (double)P.res, (double)P.y_steps * (double)P.res, P.theta_res, r.info)) {
+    for (int q = 0; q < 3; q++) r.mean[q] = 0.;
+    for (int q = 0; q < 9; q++) r.cov[q] = 0.;
+    r.mass = 0.; r.border_mass = 0.; r.n_candidates = 0;
+    r.status = 1;
+  }
+}
+
+__device__ __forceinline__ void response_clear(MatchResponse& r, int status) {
+  for (int q = 0; q < 3; q++) r.mean[q] = 0.;
+  for (int q = 0; q < 9; q++) { r.cov[q] = 0.; r.info[q] = 0.; }
+  r.mass = 0.; r.border_mass = 0.; r.n_candidates = 0; r.status = status; r.reserved = 0;
+}
+
 // The response surface of a search (include/cgmr.h, "Scan-match covariance"): k_match_greedy's job table and front half -- the
 // job's workgroups rasterise its grid, build a work unit's kept-point list together and sum the cells of up to
 // kMatchCandPerPass candidates --, but every candidate counts: with the float score s_c of the reference read as double,
@@ -2089,7 +2230,6 @@ __global__ __launch_bounds__(GR_THREADS) void k_match_response(MatchParams P, co
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   Smem& S = *reinterpret_cast<Smem*>(smem_raw);
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
   const int job = block_job[blockIdx.x];
   const GreedyJob J = jobs[job];
   const int jb = blockIdx.x - J.block0;                      // my index among the job's workgroups
@@ -2111,104 +2251,16 @@ __global__ __launch_bounds__(GR_THREADS) void k_match_response(MatchParams P, co
     for (int i = tid; i < J.n_ref; i += GR_THREADS) rcell[i] = world_to_packed_cell(P, ref_pts[2 * i], ref_pts[2 * i + 1]);
     __syncthreads();
     build_grid<false>(S, P, rcell, J.n_ref, rcell + P.ref_cap, /*allow_fast=*/false, err);
-    const float ikscale = (float)(1. / (float)P.kscale);
-    uint32_t* const pl = &S.plist[0][0];
-    int* const totals = reinterpret_cast<int*>(&S.totals[0][0]);
     const int cpp = P.cand_per_pass > 0 ? min(P.cand_per_pass, 64 * CAND_U) : 64 * CAND_U;
     for (long long unit = jb; unit < (long long)J.n_items * npass; unit += J.n_blocks) {
       const int it = (int)(unit / npass), pass = (int)(unit - (long long)it * npass);
       const RegionDesc R = regions[items[2 * (size_t)(J.item_off + it)]];
       const int ti = items[2 * (size_t)(J.item_off + it) + 1];
-      const int ncand = R.ni * R.nj;
-      if ((long long)pass * cpp >= ncand) continue;
-      const double t = theta[R.th_off + ti];
-      double sn, cs;
-      portable_sincos(t, &sn, &cs);
-      const int cb = pass * cpp;
-      const int nu = (min(ncand - cb, cpp) + 63) / 64;
-      int ci[CAND_U], cj[CAND_U], sum[CAND_U];
-#pragma unroll
-      for (int u = 0; u < CAND_U; u++) {
-        int cidx = cb + u * 64 + lane;
-        int a = cidx / R.nj, b = cidx - a * R.nj;
-        ci[u] = R.lo_x + a * P.x_steps;
-        cj[u] = R.lo_y + b * P.y_steps;
-        sum[u] = 0;
-      }
-      __syncthreads();                                            // (the previous unit's sums have been read)
-      for (int q = tid; q < 64 * CAND_U; q += GR_THREADS) totals[q] = 0;
-      // the unit's kept-point list and the cell sums over it: as k_match_greedy
-      int k = 0;
-      for (int c0 = 0; c0 < J.n_qry; c0 += kGrListCap) {
-        const int c1 = min(J.n_qry, c0 + kGrListCap);
-        __syncthreads();
-        if (tid == 0) S.misc[14] = 0;
-        __syncthreads();
-        for (int base = c0 + wave * 64; base < c1; base += GR_THREADS) {
-          const int q = base + lane;
-          const bool valid = q < c1;
-          uint32_t packed = 0;
-          if (valid) packed = turn_and_pack(P, qry_pts[2 * q], qry_pts[2 * q + 1], cs, sn);
-          uint32_t left = __shfl_up(packed, 1, 64);
-          if (lane == 0 && q > 0) left = turn_and_pack(P, qry_pts[2 * (q - 1)], qry_pts[2 * (q - 1) + 1], cs, sn);
-          const bool keep = valid && (q == 0 || packed != left);
-          const unsigned long long mask = __ballot(keep);
-          int wbase = 0;
-          if (lane == 0 && mask) wbase = atomicAdd(&S.misc[14], __popcll(mask));
-          wbase = __shfl(wbase, 0, 64);
-          if (keep) pl[wbase + __popcll(mask & ((1ULL << lane) - 1ULL))] = packed;
-        }
-        __syncthreads();
-        const int kc = S.misc[14];
-        const int q0 = (int)(((long long)kc * wave) / GR_WAVES), q1 = (int)(((long long)kc * (wave + 1)) / GR_WAVES);
-        if (nu <= 2)
-          for (int q = q0; q < q1; q += 4) gather_cells<2, 4>(S, P, gtiles, DW, pl, q, q1, ci, cj, sum);
-        else if (nu <= 4)
-          for (int q = q0; q < q1; q += 2) gather_cells<4, 2>(S, P, gtiles, DW, pl, q, q1, ci, cj, sum);
-        else
-          for (int q = q0; q < q1; q++) gather_cells<CAND_U, 1>(S, P, gtiles, DW, pl, q, q1, ci, cj, sum);
-        k += kc;
-      }
-      __syncthreads();                                            // (totals are zero)
-#pragma unroll
-      for (int u = 0; u < CAND_U; u++)
-        if (sum[u]) atomicAdd(&totals[u * 64 + lane], sum[u]);      // (integers: the order does not show)
-      __syncthreads();
-      if (k == 0) continue;                                       // no query point: the candidates of the unit are left out
-      const bool t_border = ti == 0 || ti == R.nth - 1;
-      const double dt = t - wt0;
-      for (int c = tid; c < min(cpp, ncand - cb); c += GR_THREADS) {
-        const int cidx = cb + c;
-        const int a = cidx / R.nj, b = cidx - a * R.nj;
-        const int cix = R.lo_x + a * P.x_steps, cjy = R.lo_y + b * P.y_steps;
-        float dsum = (float)totals[c] * ikscale;
-        dsum = (float)((double)dsum / (double)k);
-        const float wx = P.ll_x + (P.res * (float)cix);
-        const float wyy = P.ll_y + (P.res * (float)cjy);
-        const double w = exp(-((double)dsum - ws0) / temperature);
-        const double dx = (double)wx - wx0, dy = (double)wyy - wy0;
-        const double wdx = w * dx, wdy = w * dy, wdt = w * dt;
-        acc[0] += w;
-        acc[1] += wdx; acc[2] += wdy; acc[3] += wdt;
-        acc[4] += wdx * dx; acc[5] += wdx * dy; acc[6] += wdx * dt;
-        acc[7] += wdy * dy; acc[8] += wdy * dt; acc[9] += wdt * dt;
-        if (t_border || a == 0 || a == R.ni - 1 || b == 0 || b == R.nj - 1) acc[10] += w;
-        acc[11] += 1.;
-      }
+      response_unit(S, P, gtiles, DW, qry_pts, J.n_qry, R, ti, pass, cpp, theta[R.th_off + ti], wx0, wy0, wt0, ws0, temperature, acc);
     }
   }
   // across the wavefront, then across the wavefronts in their order
-#pragma unroll
-  for (int q = 0; q < kRespSums; q++)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc[q] += __shfl_down(acc[q], off, 64);
-  double* const red = &S.theta_cs[0][0];                           // GR_WAVES x kRespSums doubles (the angle tables are the close matcher's)
-  static_assert(GR_WAVES * kRespSums <= MAXTHETA * 2, "wavefront sums of k_match_response");
-  __syncthreads();
-  if (lane == 0)
-#pragma unroll
-    for (int q = 0; q < kRespSums; q++) red[wave * kRespSums + q] = acc[q];
-  __syncthreads();
+  const double* const red = response_wave_sums(S, acc);
   if (tid < kRespSums) {
     double v = 0.;
     for (int w = 0; w < GR_WAVES; w++) v += red[w * kRespSums + tid];
@@ -2228,9 +2280,7 @@ __global__ __launch_bounds__(64) void k_match_response_finish(MatchParams P, int
   if (job >= n_jobs) return;
   const GreedyJob J = jobs[job];
   MatchResponse r;
-  for (int q = 0; q < 3; q++) r.mean[q] = 0.;
-  for (int q = 0; q < 9; q++) { r.cov[q] = 0.; r.info[q] = 0.; }
-  r.mass = 0.; r.border_mass = 0.; r.n_candidates = 0; r.status = 0; r.reserved = 0;
+  response_clear(r, 0);
   if (found[job] == 0) {
     r.status = 2;
     out[job] = r;
@@ -2241,29 +2291,7 @@ __global__ __launch_bounds__(64) void k_match_response_finish(MatchParams P, int
   if (J.n_items > 0)
     for (int b = 0; b < J.n_blocks; b++)
       for (int q = 0; q < kRespSums; q++) s[q] += partials[(size_t)(J.block0 + b) * kRespSums + q];
-  const double mass = s[0];
-  if (!(s[11] > 0.) || !(mass > 0.) || !(mass <= 1.7976931348623157e308)) {
-    r.status = 1;
-    out[job] = r;
-    return;
-  }
-  const double u[3] = {s[1] / mass, s[2] / mass, s[3] / mass};
-  const double m2[3][3] = {{s[4], s[5], s[6]}, {s[5], s[7], s[8]}, {s[6], s[8], s[9]}};
-  for (int i = 0; i < 3; i++) {
-    r.mean[i] = winners[4 * (size_t)job + i] + u[i];
-    for (int j = 0; j < 3; j++) r.cov[3 * i + j] = m2[i][j] / mass - u[i] * u[j];
-  }
-  r.mass = mass;
-  r.border_mass = s[10] / mass;
-  r.n_candidates = (int64_t)s[11];
-  double sn, cs;
-  portable_sincos(winners[4 * (size_t)job + 2], &sn, &cs);
-  if (!match_response_information(r.cov, cs, sn, (double)P.x_steps * (double)P.res, (double)P.y_steps * (double)P.res, P.theta_res, r.info)) {
-    for (int q = 0; q < 3; q++) r.mean[q] = 0.;
-    for (int q = 0; q < 9; q++) r.cov[q] = 0.;
-    r.mass = 0.; r.border_mass = 0.; r.n_candidates = 0;
-    r.status = 1;
-  }
+  response_finish_sums(P, s, winners + 4 * (size_t)job, r);
   out[job] = r;
 }
 
@@ -2327,51 +2355,28 @@ __device__ __forceinline__ void refine_eval(Smem& S, const MatchParams& P, const
   }
 }
 
-// One workgroup per job: k_match_response's front half (kernel table, reference points -> packed cells, build_grid into the LDS tiles
-// and the overflow tiles of the workgroup's scratch), then the damped Gauss-Newton loop of the definition on the field that sits there.
-// Every thread runs the loop's scalar part (a 3x3 solve by cofactors, the clipping, the comparisons) on the same totals; thread 0
-// writes the result.  At most 1 + max_iters * (max_halvings + 1) evaluations.  The pose is kept as winner + offset: clipping the
-// offset to +-bound makes the at_bound test exact.
-__global__ __launch_bounds__(GR_THREADS) void k_match_refine(MatchParams P, const GreedyJob* __restrict__ jobs,
-                                                      const double* __restrict__ ref_pts_all, const double* __restrict__ qry_pts_all,
-                                                      const uint8_t* __restrict__ kernel_lut, unsigned char* __restrict__ scratch,
-                                                      int* __restrict__ err, const double* __restrict__ winners,
-                                                      const int32_t* __restrict__ found, RefineParams RP, MatchRefined* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  Smem& S = *reinterpret_cast<Smem*>(smem_raw);
-  const int tid = threadIdx.x;
-  const int job = blockIdx.x;
-  const GreedyJob J = jobs[job];
-  const double win[3] = {winners[4 * (size_t)job], winners[4 * (size_t)job + 1], winners[4 * (size_t)job + 2]};
-  MatchRefined r;
+__device__ __forceinline__ void refined_clear(MatchRefined& r, const double (&win)[3], int status) {
   for (int q = 0; q < 3; q++) r.pose[q] = win[q];
   r.cost0 = 0.; r.cost = 0.; r.score0 = 0.; r.score = 0.;
   for (int q = 0; q < 9; q++) r.hessian[q] = 0.;
-  r.n_active = 0; r.n_iters = 0; r.n_halvings = 0; r.stop = 0; r.at_bound = 0; r.status = 0;
-  if (found[job] == 0 || J.n_qry == 0) {                           // (the same for every thread of the workgroup)
-    r.status = found[job] == 0 ? 2 : 1;
-    if (tid == 0) out[job] = r;
-    return;
-  }
-  const double* ref_pts = ref_pts_all + 2 * (size_t)J.ref_off;
-  const double* qry_pts = qry_pts_all + 2 * (size_t)J.qry_off;
-  unsigned char* my = scratch + (size_t)blockIdx.x * P.scratch_stride;
-  uint32_t* rcell = reinterpret_cast<uint32_t*>(my);               // P.ref_cap packed cells
-  const uint32_t* gtiles = rcell + P.ref_cap;
-  const int DW = ((P.ny + 7) >> 3) + kMatchDirGuardY;
-  for (int q = tid; q < P.kdim * P.kdim; q += GR_THREADS) S.kernel[q] = kernel_lut[q];
-  for (int i = tid; i < J.n_ref; i += GR_THREADS) rcell[i] = world_to_packed_cell(P, ref_pts[2 * i], ref_pts[2 * i + 1]);
-  __syncthreads();
-  build_grid<false>(S, P, rcell, J.n_ref, rcell + P.ref_cap, /*allow_fast=*/false, err);
+  r.n_active = 0; r.n_iters = 0; r.n_halvings = 0; r.stop = 0; r.at_bound = 0; r.status = status;
+}
 
+// The damped Gauss-Newton loop of the definition on the field that sits in the workgroup's tiles, by all threads of the workgroup:
+// every thread runs the loop's scalar part (a 3x3 solve by cofactors, the clipping, the comparisons) on the same totals.  At most
+// 1 + max_iters * (max_halvings + 1) evaluations.  The pose is kept as winner + offset: clipping the offset to +-bound makes the
+// at_bound test exact.  Returns the result: status 1 (pose = the winner, everything else zero) when no point has a gradient.
+__device__ __forceinline__ MatchRefined refine_run(Smem& S, const MatchParams& P, const uint32_t* gtiles, int DW, const double* __restrict__ qry_pts,
+                                                   int n_qry, const double (&win)[3], const RefineParams& RP) {
+  MatchRefined r;
+  refined_clear(r, win, 0);
   double cur[kRefineSums], cand[kRefineSums];
-  refine_eval(S, P, gtiles, DW, qry_pts, J.n_qry, win[0], win[1], win[2], cur);
+  refine_eval(S, P, gtiles, DW, qry_pts, n_qry, win[0], win[1], win[2], cur);
   if (!(cur[5] + cur[8] + cur[10] != 0.)) {                        // trace(H) == 0: no point has a gradient
     r.status = 1;
-    if (tid == 0) out[job] = r;
-    return;
+    return r;
   }
-  const double inv_n = 1. / (double)J.n_qry;
+  const double inv_n = 1. / (double)n_qry;
   r.cost0 = cur[0];
   r.score0 = cur[1] * inv_n;
   const double bound[3] = {RP.bound_steps * ((double)P.x_steps * (double)P.res), RP.bound_steps * ((double)P.y_steps * (double)P.res),
@@ -2398,7 +2403,7 @@ __global__ __launch_bounds__(GR_THREADS) void k_match_refine(MatchParams P, cons
         c[k] = win[k] + cd[k];
       }
       if (c[0] == pose[0] && c[1] == pose[1] && c[2] == pose[2]) { stop = 3; break; }
-      refine_eval(S, P, gtiles, DW, qry_pts, J.n_qry, c[0], c[1], c[2], cand);
+      refine_eval(S, P, gtiles, DW, qry_pts, n_qry, c[0], c[1], c[2], cand);
       if (cand[0] < cur[0]) {
         for (int k = 0; k < 3; k++) { delta[k] = cd[k]; pose[k] = c[k]; }
         for (int q = 0; q < kRefineSums; q++) cur[q] = cand[q];
@@ -2423,7 +2428,130 @@ __global__ __launch_bounds__(GR_THREADS) void k_match_refine(MatchParams P, cons
   r.hessian[6] = cur[7]; r.hessian[7] = cur[9]; r.hessian[8] = cur[10];
   r.n_active = (int32_t)cur[11];
   r.n_iters = n_iters; r.n_halvings = n_halvings; r.stop = stop;
+  return r;
+}
+
+// One workgroup per job: k_match_response's front half (kernel table, reference points -> packed cells, build_grid into the LDS tiles
+// and the overflow tiles of the workgroup's scratch), then refine_run on the field that sits there.  Thread 0 writes the result.
+__global__ __launch_bounds__(GR_THREADS) void k_match_refine(MatchParams P, const GreedyJob* __restrict__ jobs,
+                                                      const double* __restrict__ ref_pts_all, const double* __restrict__ qry_pts_all,
+                                                      const uint8_t* __restrict__ kernel_lut, unsigned char* __restrict__ scratch,
+                                                      int* __restrict__ err, const double* __restrict__ winners,
+                                                      const int32_t* __restrict__ found, RefineParams RP, MatchRefined* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  Smem& S = *reinterpret_cast<Smem*>(smem_raw);
+  const int tid = threadIdx.x;
+  const int job = blockIdx.x;
+  const GreedyJob J = jobs[job];
+  const double win[3] = {winners[4 * (size_t)job], winners[4 * (size_t)job + 1], winners[4 * (size_t)job + 2]};
+  MatchRefined r;
+  refined_clear(r, win, 0);
+  if (found[job] == 0 || J.n_qry == 0) {                           // (the same for every thread of the workgroup)
+    r.status = found[job] == 0 ? 2 : 1;
+    if (tid == 0) out[job] = r;
+    return;
+  }
+  const double* ref_pts = ref_pts_all + 2 * (size_t)J.ref_off;
+  const double* qry_pts = qry_pts_all + 2 * (size_t)J.qry_off;
+  unsigned char* my = scratch + (size_t)blockIdx.x * P.scratch_stride;
+  uint32_t* rcell = reinterpret_cast<uint32_t*>(my);               // P.ref_cap packed cells
+  const uint32_t* gtiles = rcell + P.ref_cap;
+  const int DW = ((P.ny + 7) >> 3) + kMatchDirGuardY;
+  for (int q = tid; q < P.kdim * P.kdim; q += GR_THREADS) S.kernel[q] = kernel_lut[q];
+  for (int i = tid; i < J.n_ref; i += GR_THREADS) rcell[i] = world_to_packed_cell(P, ref_pts[2 * i], ref_pts[2 * i + 1]);
+  __syncthreads();
+  build_grid<false>(S, P, rcell, J.n_ref, rcell + P.ref_cap, /*allow_fast=*/false, err);
+  r = refine_run(S, P, gtiles, DW, qry_pts, J.n_qry, win, RP);
   if (tid == 0) out[job] = r;
+}
+
+// Refinement and response of a job's winners behind ONE rasterisation (include/cgmr.h, "Polishing a search's results"): one
+// workgroup per job -- k_match_refine's front half once, then refine_run for every winner in order (if asked), then the response
+// surface over every winner's own region in order (if asked: regions[J.region_off + k], the window around the winner as the search
+// produced it).  Two loops, not one with both parts in its body: the results are the same and the one loop needed scratch memory.  The
+// workgroup walks all (angle, candidate pass) units of the region itself; the threads' private sums meet as in k_match_response
+// (shuffles, then the eight wavefronts in LDS in wavefront order) and thread 0 finishes and writes the result.  Neither part disturbs
+// the grid: the refinement reads it, the response uses the point lists and the totals beside it.  out holds kPolishMaxWinners
+// entries per job: a part that was not asked for has status 3 (zeros, refined.pose = the winner), an entry without a winner status 2.
+// Every loop is bounded by its inputs: max_iters x max_halvings, the region's angles x passes (the host bounds the candidates).
+__global__ __launch_bounds__(GR_THREADS) void k_match_polish(MatchParams P, const GreedyJob* __restrict__ jobs,
+                                                      const double* __restrict__ ref_pts_all, const double* __restrict__ qry_pts_all,
+                                                      const RegionDesc* __restrict__ regions, const double* __restrict__ theta,
+                                                      const uint8_t* __restrict__ kernel_lut, unsigned char* __restrict__ scratch,
+                                                      int* __restrict__ err, const double* __restrict__ winners,
+                                                      const int32_t* __restrict__ n_winners, double temperature, int do_refine,
+                                                      RefineParams RP, MatchPolished* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  Smem& S = *reinterpret_cast<Smem*>(smem_raw);
+  const int tid = threadIdx.x;
+  const int job = blockIdx.x;
+  const GreedyJob J = jobs[job];
+  const int nw = min(max(n_winners[job], 0), kPolishMaxWinners);
+  const bool do_response = temperature > 0.;
+  const double* const wj = winners + 4 * (size_t)kPolishMaxWinners * (size_t)job;
+  MatchPolished* const oj = out + (size_t)kPolishMaxWinners * (size_t)job;
+  if (tid == 0)
+    for (int k = nw; k < kPolishMaxWinners; k++) {
+      const double zero[3] = {0., 0., 0.};
+      MatchPolished e;
+      response_clear(e.response, 2);
+      refined_clear(e.refined, zero, 2);
+      oj[k] = e;
+    }
+  if (nw == 0) return;                                             // (the same for every thread of the workgroup)
+  const double* ref_pts = ref_pts_all + 2 * (size_t)J.ref_off;
+  const double* qry_pts = qry_pts_all + 2 * (size_t)J.qry_off;
+  unsigned char* my = scratch + (size_t)blockIdx.x * P.scratch_stride;
+  uint32_t* rcell = reinterpret_cast<uint32_t*>(my);               // P.ref_cap packed cells
+  const uint32_t* gtiles = rcell + P.ref_cap;
+  const int DW = ((P.ny + 7) >> 3) + kMatchDirGuardY;
+  for (int q = tid; q < P.kdim * P.kdim; q += GR_THREADS) S.kernel[q] = kernel_lut[q];
+  for (int i = tid; i < J.n_ref; i += GR_THREADS) rcell[i] = world_to_packed_cell(P, ref_pts[2 * i], ref_pts[2 * i + 1]);
+  __syncthreads();
+  build_grid<false>(S, P, rcell, J.n_ref, rcell + P.ref_cap, /*allow_fast=*/false, err);
+  const int cpp = P.cand_per_pass > 0 ? min(P.cand_per_pass, 64 * CAND_U) : 64 * CAND_U;
+#pragma unroll 1
+  for (int k = 0; k < nw; k++) {
+    const double win[3] = {wj[4 * k], wj[4 * k + 1], wj[4 * k + 2]};
+    MatchRefined rf;
+    if (do_refine && J.n_qry != 0) rf = refine_run(S, P, gtiles, DW, qry_pts, J.n_qry, win, RP);
+    else refined_clear(rf, win, do_refine ? 1 : 3);
+    if (tid == 0) oj[k].refined = rf;
+  }
+#pragma unroll 1
+  for (int k = 0; k < nw; k++) {
+    const double win[3] = {wj[4 * k], wj[4 * k + 1], wj[4 * k + 2]};
+    const double ws0 = wj[4 * k + 3];
+    if (do_response) {
+      const RegionDesc R = regions[J.region_off + k];
+      const int npass = (R.ni * R.nj + cpp - 1) / cpp;
+      double acc[kRespSums];
+#pragma unroll
+      for (int q = 0; q < kRespSums; q++) acc[q] = 0.;
+#pragma unroll 1
+      for (int ti = 0; ti < R.nth; ti++)
+#pragma unroll 1
+        for (int pass = 0; pass < npass; pass++)
+          response_unit(S, P, gtiles, DW, qry_pts, J.n_qry, R, ti, pass, cpp, theta[R.th_off + ti], win[0], win[1], win[2], ws0, temperature, acc);
+      const double* const red = response_wave_sums(S, acc);
+      if (tid == 0) {
+        double s[kRespSums];
+        for (int q = 0; q < kRespSums; q++) {
+          double v = 0.;
+          for (int w = 0; w < GR_WAVES; w++) v += red[w * kRespSums + q];
+          s[q] = v;
+        }
+        MatchResponse rs;
+        response_clear(rs, 0);
+        response_finish_sums(P, s, win, rs);
+        oj[k].response = rs;
+      }
+    } else if (tid == 0) {
+      MatchResponse rs;
+      response_clear(rs, 3);
+      oj[k].response = rs;
+    }
+  }
 }
 
 
@@ -2725,6 +2853,16 @@ void launch_match_refine(hipStream_t st, int n_jobs, const MatchParams& P, const
   if (n_jobs > 0)
     hipLaunchKernelGGL(k_match_refine, dim3(n_jobs), dim3(GR_THREADS), sizeof(Smem), st, P, jobs, ref_pts, qry_pts, kernel_lut, scratch, err,
                        winners, found, RP, out);
+}
+
+void launch_match_polish(hipStream_t st, int n_jobs, const MatchParams& P, const GreedyJob* jobs, const double* ref_pts,
+                         const double* qry_pts, const RegionDesc* regions, const double* theta, const uint8_t* kernel_lut,
+                         unsigned char* scratch, int* err, const double* winners, const int32_t* n_winners, double temperature,
+                         int do_refine, const RefineParams& RP, MatchPolished* out) {
+  set_lds_attr_once<4>(reinterpret_cast<const void*>(k_match_polish));
+  if (n_jobs > 0)
+    hipLaunchKernelGGL(k_match_polish, dim3(n_jobs), dim3(GR_THREADS), sizeof(Smem), st, P, jobs, ref_pts, qry_pts, regions, theta, kernel_lut,
+                       scratch, err, winners, n_winners, temperature, do_refine, RP, out);
 }
 
 size_t match_grid_image_bytes(const MatchParams& P) {

@@ -91,6 +91,58 @@ def _refined_dict(r):
             "status": int(r.status)}
 
 
+POLISH_MAX_WINNERS = 4        # CGMR_POLISH_MAX_WINNERS (include/cgmr.h)
+
+
+class _PolishParamsPod(C.Structure):
+    """``cgmr_polish_params`` (include/cgmr.h)."""
+    _fields_ = [("T", C.c_double), ("window", C.c_double * 3), ("refine", C.c_int32), ("reserved", C.c_int32),
+                ("refine_params", _RefineParamsPod)]
+
+
+class PolishParams:
+    """What the polished searches take behind a result (include/cgmr.h, "Polishing a search's results").  ``T``: the
+    temperature of the response (see ``matchResponse``; no default -- None: no response).  ``window``: the half-widths
+    (x, y, theta) of the response's window around a winner; the default is the searches' own results discretisation
+    (dx, dy, dth), the distance below which the search itself counts two results as one match.  ``refine``: a
+    ``RefineParams`` (see ``matchRefine``), None: no refinement."""
+
+    def __init__(self, T=None, window=(0.5, 0.5, 0.2), refine=None):   # noqa: N803
+        if refine is not None and not isinstance(refine, RefineParams):
+            raise ValueError("PolishParams: refine must be a RefineParams or None")
+        self.T = None if T is None else float(T)
+        self.window = tuple(float(w) for w in window)
+        if len(self.window) != 3:
+            raise ValueError("PolishParams: window holds three half-widths (x, y, theta)")
+        self.refine = refine
+
+    def pod(self):
+        p = _PolishParamsPod()
+        p.T = 0.0 if self.T is None else self.T
+        for q in range(3):
+            p.window[q] = self.window[q]
+        p.refine = 0 if self.refine is None else 1
+        r = RefineParams() if self.refine is None else self.refine
+        for k, _ in RefineParams._fields_:
+            setattr(p.refine_params, k, getattr(r, k))
+        return p
+
+
+class MatchPolished(C.Structure):
+    """``struct cgmr_match_polished`` (include/cgmr.h): the response and the refinement of one winner."""
+    _fields_ = [("response", MatchResponse), ("refined", MatchRefined)]
+
+
+class PolishJob(C.Structure):
+    """``cgmr_polish_job`` (include/cgmr.h)."""
+    _fields_ = [("n_ref", C.c_int), ("ref_pts_xy", C.c_void_p), ("n_qry", C.c_int), ("qry_pts_xy", C.c_void_p),
+                ("n_winners", C.c_int), ("winners", (C.c_double * 4) * POLISH_MAX_WINNERS)]
+
+
+def _polished_dict(e):
+    return {"response": _response_dict(e.response), "refined": _refined_dict(e.refined)}
+
+
 def _se2_mul(a, b):
     """g2o SE2 product: translation a.t + R(a.theta) b.t, angle normalised [g2o-recalled]."""
     import math
@@ -300,24 +352,68 @@ class _GenericSearch:
             return bytes(out)[:C.sizeof(MatchRefined) * len(jobs)]
         return [_refined_dict(out[k]) for k in range(len(jobs))]
 
+    # ---- refinement and response of a search's results behind one rasterisation (include/cgmr.h) -------------
+    def matchPolishBatch(self, jobs, thetaRes, params, step=None, raw=False):   # noqa: N802,N803
+        """``matchRefine`` and ``matchResponse`` for up to four winners per job, one workgroup and ONE rasterisation of the
+        job's grid each, all jobs in one launch.  ``jobs``: list of (ref_pts, qry_pts, winners) with ``winners`` a list of
+        (x*, y*, theta*, s*); ``params``: a ``PolishParams``.  Returns per job a list of {"response", "refined"} dicts, one
+        per winner; a part that was not asked for has status 3.  ``raw``: the bytes of all 4 result structs of every job."""
+        step = float(np.float32(self.cfg.resolution)) if step is None else float(step)
+        arr = (PolishJob * max(len(jobs), 1))()
+        keep = []
+        for k, (ref_pts, qry_pts, winners) in enumerate(jobs):
+            ref = np.ascontiguousarray(ref_pts, dtype=np.float64).reshape(-1, 2)
+            qry = np.ascontiguousarray(qry_pts, dtype=np.float64).reshape(-1, 2)
+            keep.append((ref, qry))
+            arr[k].n_ref, arr[k].ref_pts_xy = len(ref), ref.ctypes.data
+            arr[k].n_qry, arr[k].qry_pts_xy = len(qry), qry.ctypes.data
+            arr[k].n_winners = len(winners)                       # (more than four: the call refuses it by name)
+            for w, win in enumerate(winners[:POLISH_MAX_WINNERS]):
+                for q in range(4):
+                    arr[k].winners[w][q] = float(win[q])
+        out = (MatchPolished * max(POLISH_MAX_WINNERS * len(jobs), 1))()
+        par = params.pod()
+        rc = self.ctx.lib.cgmr_match_polish_batch(self.ctx.h, C.byref(self.cfg), C.c_int(len(jobs)), arr, C.c_double(step),
+                                                  C.c_double(step), C.c_double(thetaRes), C.byref(par), out)
+        self.ctx._check(rc)
+        if raw:
+            return bytes(out)[:C.sizeof(MatchPolished) * POLISH_MAX_WINNERS * len(jobs)]
+        return [[_polished_dict(out[POLISH_MAX_WINNERS * k + w]) for w in range(len(jobs[k][2]))] for k in range(len(jobs))]
+
     # ---- ScanMatcher::scanMatchingLC (scan_matcher.cpp:201-294) ---------------------------------------------
-    def scanMatchingLC(self, ref_scans, ref_index, cur_scans, cur_index, maxScore):   # noqa: N802,N803
-        """Returns the list of SE2 (x, y, theta) the reference pushes into ``trel`` (0-2 entries)."""
+    def scanMatchingLC(self, ref_scans, ref_index, cur_scans, cur_index, maxScore, polish=None):   # noqa: N802,N803
+        """Returns the list of SE2 (x, y, theta) the reference pushes into ``trel`` (0-2 entries).  With ``polish`` (a
+        ``PolishParams``) every result is polished behind the search: returns (that list, a list of {"response", "refined"}
+        dicts, one per result)."""
         a, ka = _scan_set(ref_scans, ref_index)
         b, kb = _scan_set(cur_scans, cur_index)
         out = np.zeros((2, 3))
         n = C.c_int(0)
+        if polish is not None:
+            par, pol = polish.pod(), (MatchPolished * 2)()
+            rc = self.ctx.lib.cgmr_scan_matching_lc_polished(self.ctx.h, C.byref(self.cfg), C.byref(a), C.byref(b), C.c_double(maxScore),
+                                                             C.byref(par), C.c_void_p(out.ctypes.data), C.byref(n), pol)
+            self.ctx._check(rc)
+            return [out[k].copy() for k in range(n.value)], [_polished_dict(pol[k]) for k in range(n.value)]
         rc = self.ctx.lib.cgmr_scan_matching_lc(self.ctx.h, C.byref(self.cfg), C.byref(a), C.byref(b), C.c_double(maxScore),
                                                 C.c_void_p(out.ctypes.data), C.byref(n))
         self.ctx._check(rc)
         return [out[k].copy() for k in range(n.value)]
 
     # ---- ScanMatcher::globalMatching (scan_matcher.cpp:366-428) ---------------------------------------------
-    def globalMatching(self, ref_scans, ref_index, cur_scans, cur_index, maxScore):   # noqa: N802,N803
+    def globalMatching(self, ref_scans, ref_index, cur_scans, cur_index, maxScore, polish=None):   # noqa: N802,N803
+        """Returns (found, trel).  With ``polish`` (a ``PolishParams``): ((found, trel), a list of one {"response", "refined"}
+        dict when something was found, else an empty one)."""
         a, ka = _scan_set(ref_scans, ref_index)
         b, kb = _scan_set(cur_scans, cur_index)
         out = np.zeros(3)
         found = C.c_int(0)
+        if polish is not None:
+            par, pol = polish.pod(), MatchPolished()
+            rc = self.ctx.lib.cgmr_global_matching_polished(self.ctx.h, C.byref(self.cfg), C.byref(a), C.byref(b), C.c_double(maxScore),
+                                                            C.byref(par), C.c_void_p(out.ctypes.data), C.byref(found), C.byref(pol))
+            self.ctx._check(rc)
+            return ((True, out.copy()), [_polished_dict(pol)]) if found.value else ((False, None), [])
         rc = self.ctx.lib.cgmr_global_matching(self.ctx.h, C.byref(self.cfg), C.byref(a), C.byref(b), C.c_double(maxScore),
                                                C.c_void_p(out.ctypes.data), C.byref(found))
         self.ctx._check(rc)
@@ -406,19 +502,37 @@ class _BatchedSearch:
     """Batched forms of the ScanMatcher member functions: many independent calls, one kernel launch
     per search level.  ``jobs``: list of (ref_scans, ref_index, cur_scans, cur_index)."""
 
-    def scanMatchingLCBatch(self, jobs, maxScore):   # noqa: N802,N803
+    def scanMatchingLCBatch(self, jobs, maxScore, polish=None):   # noqa: N802,N803
+        """Returns per job the list of ``scanMatchingLC``.  With ``polish`` (a ``PolishParams``): (those lists, per job a
+        list of {"response", "refined"} dicts, one per result), every result of the batch polished in one launch."""
         a, ka = _scan_set_array([(j[0], j[1]) for j in jobs])
         b, kb = _scan_set_array([(j[2], j[3]) for j in jobs])
         out, n = np.zeros((len(jobs), 2, 3)), np.zeros(len(jobs), dtype=np.int32)
+        if polish is not None:
+            par, pol = polish.pod(), (MatchPolished * max(2 * len(jobs), 1))()
+            self.ctx._check(self.ctx.lib.cgmr_scan_matching_lc_polished_batch(self.ctx.h, C.byref(self.cfg), C.c_int(len(jobs)), a, b,
+                                                                              C.c_double(maxScore), C.byref(par),
+                                                                              C.c_void_p(out.ctypes.data), C.c_void_p(n.ctypes.data), pol))
+            return ([[out[j, k].copy() for k in range(n[j])] for j in range(len(jobs))],
+                    [[_polished_dict(pol[2 * j + k]) for k in range(n[j])] for j in range(len(jobs))])
         self.ctx._check(self.ctx.lib.cgmr_scan_matching_lc_batch(self.ctx.h, C.byref(self.cfg), C.c_int(len(jobs)), a, b,
                                                                  C.c_double(maxScore), C.c_void_p(out.ctypes.data),
                                                                  C.c_void_p(n.ctypes.data)))
         return [[out[j, k].copy() for k in range(n[j])] for j in range(len(jobs))]
 
-    def globalMatchingBatch(self, jobs, maxScore):   # noqa: N802,N803
+    def globalMatchingBatch(self, jobs, maxScore, polish=None):   # noqa: N802,N803
+        """Returns per job (found, trel).  With ``polish`` (a ``PolishParams``): (that list, per job a list of one
+        {"response", "refined"} dict when something was found, else an empty one)."""
         a, ka = _scan_set_array([(j[0], j[1]) for j in jobs])
         b, kb = _scan_set_array([(j[2], j[3]) for j in jobs])
         out, f = np.zeros((len(jobs), 3)), np.zeros(len(jobs), dtype=np.int32)
+        if polish is not None:
+            par, pol = polish.pod(), (MatchPolished * max(len(jobs), 1))()
+            self.ctx._check(self.ctx.lib.cgmr_global_matching_polished_batch(self.ctx.h, C.byref(self.cfg), C.c_int(len(jobs)), a, b,
+                                                                             C.c_double(maxScore), C.byref(par),
+                                                                             C.c_void_p(out.ctypes.data), C.c_void_p(f.ctypes.data), pol))
+            return ([(True, out[j].copy()) if f[j] else (False, None) for j in range(len(jobs))],
+                    [[_polished_dict(pol[j])] if f[j] else [] for j in range(len(jobs))])
         self.ctx._check(self.ctx.lib.cgmr_global_matching_batch(self.ctx.h, C.byref(self.cfg), C.c_int(len(jobs)), a, b,
                                                                 C.c_double(maxScore), C.c_void_p(out.ctypes.data),
                                                                 C.c_void_p(f.ctypes.data)))

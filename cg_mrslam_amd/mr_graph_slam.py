@@ -89,7 +89,12 @@ class MRGraphSLAMDriver(GraphSLAMDriver):
     ``robot_graph``: a ``condensed.RobotGraph`` (or an object with its interface) created for (idRobot, nRobots); it holds
     the optimiser's copy of the graph, so ``optimize`` runs there and the estimates are read back."""
 
-    def __init__(self, ctx, close_matcher, lc_matcher, robot_graph, idRobot, nRobots, **kw):   # noqa: N803
+    def __init__(self, ctx, close_matcher, lc_matcher, robot_graph, idRobot, nRobots, mr_polish=None, **kw):   # noqa: N803
+        # inter-robot edges: None = globalMatching's result with the constant information (the reference); a matcher.PolishParams =
+        # the result polished behind the search, as GraphSLAMDriver's lc_polish does for loop closures
+        if mr_polish is not None and not (hasattr(mr_polish, "pod") and hasattr(mr_polish, "window")):
+            raise ValueError("mr_polish is None or a matcher.PolishParams")
+        self.mr_polish = mr_polish
         self.rg = robot_graph
         self.nRobots = nRobots   # noqa: N815
         self._n_recv = 0                       # received condensed edges at the tail of the host edge arrays
@@ -188,10 +193,20 @@ class MRGraphSLAMDriver(GraphSLAMDriver):
         return vset
 
     def _global_matching(self, jobs):
+        """-> ([(found, trel)], [the polished result of a found one, else None]); without mr_polish all None."""
         m = self.lc_matcher
+        if self.mr_polish is not None:
+            if len(jobs) > 1 and hasattr(m, "globalMatchingBatch"):
+                res, pol = m.globalMatchingBatch(jobs, self.maxScoreMR, polish=self.mr_polish)
+            else:
+                both = [m.globalMatching(*j, self.maxScoreMR, polish=self.mr_polish) for j in jobs]
+                res, pol = [b[0] for b in both], [b[1] for b in both]
+            return res, [p[0] if p else None for p in pol]
         if len(jobs) > 1 and hasattr(m, "globalMatchingBatch"):
-            return m.globalMatchingBatch(jobs, self.maxScoreMR)
-        return [m.globalMatching(*j, self.maxScoreMR) for j in jobs]
+            res = m.globalMatchingBatch(jobs, self.maxScoreMR)
+        else:
+            res = [m.globalMatching(*j, self.maxScoreMR) for j in jobs]
+        return res, [None] * len(res)
 
     def _verify_matching(self, jobs, trel):
         m = self.lc_matcher
@@ -199,12 +214,14 @@ class MRGraphSLAMDriver(GraphSLAMDriver):
             return m.verifyMatchingBatch(jobs, trel)
         return [m.verifyMatching(*j, t) for j, t in zip(jobs, trel)]
 
-    @staticmethod
-    def _closure(ref_id, vid, transf):
+    def _closure(self, ref_id, vid, transf, pol=None):
         c = ClosureBuffer()
         c.addVertex(vid)
-        c.addEdge({"from": ref_id, "to": vid, "meas": np.asarray(transf, dtype=np.float64).copy(), "info": INTER_ROBOT_INFO,
-                   "added": False})
+        edge = {"from": ref_id, "to": vid, "meas": np.asarray(transf, dtype=np.float64).copy(), "info": INTER_ROBOT_INFO,
+                "added": False}
+        if pol is not None:                                      # (LoopClosureChecker weighs with "info"; edge_info is for the graph)
+            edge["meas"], edge["edge_info"] = self._polished_closure("mr_polish", ref_id, vid, transf, pol, self.mr_polish, INTER_ROBOT_INFO)
+        c.addEdge(edge)
         return c
 
     # ------------------------------------------------------------------ mr_graph_slam.cpp:60-116
@@ -236,7 +253,7 @@ class MRGraphSLAMDriver(GraphSLAMDriver):
                     self.lasers[idx] = self.peer[vto]["ranges"]
                 if not e["added"]:                               # HyperGraph::addEdge refuses an edge twice
                     e["added"] = True
-                    self._add_edge(self._index_of_id(e["from"]), idx, e["meas"], INTER_ROBOT_INFO, "mr",
+                    self._add_edge(self._index_of_id(e["from"]), idx, e["meas"], e.get("edge_info", INTER_ROBOT_INFO), "mr",
                                    self._running_edge_id + self.baseId)
                 in_closures.append(vto)
             if in_closures:
@@ -279,7 +296,8 @@ class MRGraphSLAMDriver(GraphSLAMDriver):
         cur_order = sorted(vset)
         cur_scans = [(self.peer[q]["ranges"], self._peer_pose(q)) for q in cur_order]
         job = (ref_scans, order.index(ref_vertex), cur_scans, cur_order.index(v))
-        found, transf = self._global_matching([job])[0]
+        res, pol = self._global_matching([job])
+        found, transf = res[0]
         ref_id = int(self.g.ids[ref_vertex])
         self.log.append(("combo", robot, v, ref_id, bool(found)))
         if found:
@@ -288,7 +306,7 @@ class MRGraphSLAMDriver(GraphSLAMDriver):
                 self.log.append(("verify", robot, v, bool(ok), float(score)))
                 if not ok:
                     return
-            self.interRobotClosures.insert(self._closure(ref_id, v, transf), robot)
+            self.interRobotClosures.insert(self._closure(ref_id, v, transf, pol[0]), robot)
         else:
             c = ClosureBuffer()
             c.addVertex(v)
@@ -319,7 +337,7 @@ class MRGraphSLAMDriver(GraphSLAMDriver):
             for vid in sorted(set(self.interRobotVertices.mrClosures[robot_id].vertex_ids())):
                 todo.append((robot_id, vid))
         jobs = [(ref_scans, ri, [(self.peer[vid]["ranges"], self._peer_pose(vid))], 0) for _, vid in todo]
-        results = self._global_matching(jobs) if jobs else []
+        results, polished = self._global_matching(jobs) if jobs else ([], [])
         hit = [k for k, (found, _) in enumerate(results) if found]
         verified = {}
         if self.detectRobotInRange and hit:
@@ -331,7 +349,7 @@ class MRGraphSLAMDriver(GraphSLAMDriver):
             self.log.append(("mr_match", robot_id, vid, last_id, bool(found)))
             if not found or (self.detectRobotInRange and not verified[k]):
                 continue
-            closure = self._closure(last_id, vid, transf)
+            closure = self._closure(last_id, vid, transf, polished[k])
             self.interRobotClosures.insert(closure, robot_id)
             self.interRobotVertices.remove(closure, robot_id)
         self.checkInterRobotClosures()

@@ -213,7 +213,7 @@ class GraphSLAMDriver(GraphSLAM):
     ``covariance_estimate``."""
 
     def __init__(self, ctx, close_matcher, lc_matcher, idRobot=0, baseId=10000, windowLoopClosure=10, maxScore=0.15,   # noqa: N803
-                 inlierThreshold=2.0, minInliers=7, sm_information="fixed", sm_refine=None):   # noqa: N803
+                 inlierThreshold=2.0, minInliers=7, sm_information="fixed", sm_refine=None, lc_polish=None):   # noqa: N803
         g = PoseGraph(np.zeros(0, dtype=np.int32), np.zeros((0, 3)), np.zeros(0, dtype=np.uint8),
                       np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros((0, 3)), np.zeros((0, 6)))
         super().__init__(g, ctx=ctx)
@@ -245,6 +245,12 @@ class GraphSLAMDriver(GraphSLAM):
         if sm_refine is not None and not hasattr(sm_refine, "bound_steps"):
             raise ValueError("sm_refine is None or a matcher.RefineParams")
         self.sm_refine = sm_refine
+        # loop-closure edges: None = the search's winner with the constant information (the reference); a matcher.PolishParams = every
+        # result of scanMatchingLC polished behind the search (matcher.matchPolishBatch): the refined pose as the measurement and
+        # the response's information on the edge that enters the graph, each where it was asked for and its status is 0
+        if lc_polish is not None and not (hasattr(lc_polish, "pod") and hasattr(lc_polish, "window")):
+            raise ValueError("lc_polish is None or a matcher.PolishParams")
+        self.lc_polish = lc_polish
 
     # ------------------------------------------------------------------ graph bookkeeping
     def _index_of_id(self, vid):
@@ -271,6 +277,23 @@ class GraphSLAMDriver(GraphSLAM):
         g.edge_level = np.append(g.edge_level, np.int32(0))
         self.edge_ids.append(eid)
         self.edge_kind.append(kind)
+
+    def _polished_closure(self, kind, from_id, to_id, transf, pol, params, constant):
+        """(meas, edge_info) of a closure whose search result ``transf`` was polished into ``pol``: the refined pose / the
+        response's information where they were asked for and their status is 0, else the search's pose / ``constant``.
+        Logs one ``kind`` entry, and a ``kind + "_fallback"`` entry when a response was asked for and there is none."""
+        resp, refined = pol["response"], pol["refined"]
+        search = np.asarray(transf, dtype=np.float64).copy()
+        meas = refined["pose"].copy() if params.refine is not None and refined["status"] == 0 else search
+        info = constant
+        if params.T is not None and resp["status"] == 0:
+            m = resp["info"]
+            info = np.array([m[0, 0], m[0, 1], m[0, 2], m[1, 1], m[1, 2], m[2, 2]])
+        elif params.T is not None:
+            self.log.append((kind + "_fallback", (from_id, to_id), int(resp["status"])))
+        self.log.append((kind, from_id, to_id, resp["status"], refined["status"], refined["stop"], refined["n_iters"],
+                         dict(pol, search=search)))
+        return meas, info
 
     def lastVertex(self):   # noqa: N802
         return self._last_vertex
@@ -401,12 +424,21 @@ class GraphSLAMDriver(GraphSLAM):
             order, scans = self._scans(myvset)
             ref_index = order.index(closest)
             if (not self.isMyVertex(closest)) or abs(int(g.ids[last]) - int(g.ids[closest])) > 10:
-                results = self.lc_matcher.scanMatchingLC(scans, ref_index, [(self.lasers[last], g.poses[last].copy())], 0,
-                                                         self.maxScore)
-                for r in results:
+                if self.lc_polish is None:
+                    results = self.lc_matcher.scanMatchingLC(scans, ref_index, [(self.lasers[last], g.poses[last].copy())], 0,
+                                                             self.maxScore)
+                    polished = [None] * len(results)
+                else:
+                    results, polished = self.lc_matcher.scanMatchingLC(scans, ref_index, [(self.lasers[last], g.poses[last].copy())], 0,
+                                                                       self.maxScore, polish=self.lc_polish)
+                for r, pol in zip(results, polished):
                     self._running_edge_id += 1
-                    loop_closing.append({"from": closest, "to": last, "meas": np.asarray(r, dtype=np.float64).copy(),
-                                         "id": self._running_edge_id + self.baseId, "added": False})
+                    edge = {"from": closest, "to": last, "meas": np.asarray(r, dtype=np.float64).copy(),
+                            "id": self._running_edge_id + self.baseId, "added": False}
+                    if pol is not None:                          # (LoopClosureChecker weighs with the constant; edge_info is for the graph)
+                        edge["meas"], edge["edge_info"] = self._polished_closure("lc_polish", int(g.ids[closest]), int(g.ids[last]), r, pol,
+                                                                                 self.lc_polish, SM_INFO)
+                    loop_closing.append(edge)
                 self.log.append(("lc", int(g.ids[closest]), int(g.ids[last]), len(results)))
             else:
                 found, transf = self.close_matcher.closeScanMatchingVSet(scans, ref_index, self.lasers[last], g.poses[last],
@@ -434,7 +466,7 @@ class GraphSLAMDriver(GraphSLAM):
             for e, chi in self.lcc.closures():
                 if chi < self.inlierThreshold and not e["added"]:      # HyperGraph::addEdge refuses an edge twice
                     e["added"] = True
-                    self._add_edge(e["from"], e["to"], e["meas"], SM_INFO, "lc", e["id"])
+                    self._add_edge(e["from"], e["to"], e["meas"], e.get("edge_info", SM_INFO), "lc", e["id"])
 
     def updateClosures(self):   # noqa: N802  (graph_slam.cpp:536-560)
         self._closures.updateList(self.windowLoopClosure)

@@ -733,6 +733,74 @@ int cgmr_close_scan_matching_refined(cgmr_ctx* ctx, const cgmr_matcher_config* c
                                      const cgmr_refine_params* params, double trel_out[3], double trel_search_out[3],
                                      int* found_out, struct cgmr_match_refined* refined_out);
 
+/* ------------------------------------------------------------------------------------------
+ * Polishing a search's results: refinement and response behind one rasterisation (C ABI version 105, added later under the
+ * same number: callers find it by its symbols).  The loop-closure and global matchers return the best cell of a 0.1 m grid with
+ * 0.025 rad steps; the two sections above can be pointed at such a match with the generic calls, at the price of one
+ * rasterisation of the job's grid per call and per result.  These calls rasterise a job's grid once, then run the refinement
+ * ("Refining a match") for each of the job's winners in order, then take the response ("Scan-match covariance") over a window
+ * around each winner in order.  Neither part reads what the other writes.  No new arithmetic: both parts are the definitions above.
+ *
+ * - A job has reference points, query points and `n_winners` in 0..CGMR_POLISH_MAX_WINNERS winners `(x, y, θ, s)`.
+ * - Refinement (`refine == 1`): `refined` holds the bits `cgmr_match_refine_batch` returns for the same points, winner, steps and
+ *   `refine_params`.
+ * - Response (`T > 0`): one region per winner, `lower = (float)(w − h)`, `upper = (float)(w + h)` with `w` the winner as the search
+ *   produced it (before any angle normalisation) and `h = window`; the sums are formed in double and narrowed once.  It is taken
+ *   around the search's winner, not the refined pose.  One workgroup sums all candidates of a window, in a partition of its own:
+ *   the result agrees with `cgmr_match_response_batch` on the same region to rounding, not to the bit.
+ * - Status codes are those of the two parts, and 3: not asked for.  A part with status 3 is all zeros, except `refined.pose`,
+ *   which holds the winner.  Entries beyond `n_winners` have status 2 in both parts (`refined.pose` zero).  Never NaN.
+ * - Refused with `CGMR_E_INVALID` and a message: what `cgmr_match_refine_batch` and `cgmr_match_response_batch` refuse; a `T`
+ *   that is negative or not finite; a half-width that is not positive and finite; `refine` other than 0 or 1; `n_winners` outside
+ *   0..4; a winner that is not finite; with `T > 0`, a window with more than 65 536 candidates (angles × cells).  Without a
+ *   response (`T == 0`) the window is checked for being positive and finite and is otherwise not used: no region is built for it.
+ * - The same call twice returns identical bits.
+ *
+ *   cgmr_match_polish_batch               n_jobs in ONE launch, one workgroup each; out holds CGMR_POLISH_MAX_WINNERS entries per job
+ *   cgmr_scan_matching_lc_polished_batch  cgmr_scan_matching_lc_batch (trel_out, n_out: the same bits), then every returned result
+ *                                         polished in one launch on the same prepared points with the search's own score,
+ *                                         step = (float)resolution and theta_res = 0.025: polished_out[j * 2 + k] belongs to
+ *                                         trel_out[j * 6 + 3 k].  The kernel works on the raw winner; response.mean[2] and
+ *                                         refined.pose[2] are normalised on the way out, as the search's own angle is.
+ *   cgmr_global_matching_polished_batch   cgmr_global_matching_batch (trel_out, found_out: the same bits), then the same for every
+ *                                         job's result: polished_out[j]
+ *   cgmr_scan_matching_lc_polished, cgmr_global_matching_polished: a batch of one                                               */
+#define CGMR_POLISH_MAX_WINNERS 4
+typedef struct cgmr_polish_params {
+  double T;              /* > 0: take the response at this temperature (no default); 0: no response */
+  double window[3];      /* half-widths (x, y, theta) of the response window around a winner */
+  int32_t refine;        /* 1: refine with refine_params; 0: no refinement */
+  int32_t reserved;
+  cgmr_refine_params refine_params;
+} cgmr_polish_params;
+struct cgmr_match_polished {
+  struct cgmr_match_response response;
+  struct cgmr_match_refined refined;
+};
+typedef struct cgmr_polish_job {
+  int n_ref; const double* ref_pts_xy;
+  int n_qry; const double* qry_pts_xy;
+  int n_winners;
+  double winners[CGMR_POLISH_MAX_WINNERS][4];
+} cgmr_polish_job;
+int cgmr_match_polish_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_polish_job* jobs, double step_x,
+                            double step_y, double theta_res, const cgmr_polish_params* params,
+                            struct cgmr_match_polished* out /* [n_jobs * CGMR_POLISH_MAX_WINNERS] */);
+int cgmr_scan_matching_lc_polished_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
+                                         const cgmr_scan_set* cur_sets, double max_score, const cgmr_polish_params* params,
+                                         double* trel_out /* [n_jobs * 6] */, int* n_out,
+                                         struct cgmr_match_polished* polished_out /* [n_jobs * 2] */);
+int cgmr_scan_matching_lc_polished(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const cgmr_scan_set* ref_set,
+                                   const cgmr_scan_set* cur_set, double max_score, const cgmr_polish_params* params,
+                                   double* trel_out /* [6] */, int* n_out, struct cgmr_match_polished* polished_out /* [2] */);
+int cgmr_global_matching_polished_batch(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets,
+                                        const cgmr_scan_set* cur_sets, double max_score, const cgmr_polish_params* params,
+                                        double* trel_out /* [n_jobs * 3] */, int* found_out,
+                                        struct cgmr_match_polished* polished_out /* [n_jobs] */);
+int cgmr_global_matching_polished(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const cgmr_scan_set* ref_set,
+                                  const cgmr_scan_set* cur_set, double max_score, const cgmr_polish_params* params,
+                                  double trel_out[3], int* found_out, struct cgmr_match_polished* polished_out);
+
 /* Host helpers with the reference's exact arithmetic (no GPU): RawLaser::cartesian [g2o-recalled] and
  * CharGrid::subsample (src/matcher/chargrid.cpp:61-122).  Both return the number of points written. */
 int cgmr_scan_cartesian(int n_beams, const float* ranges, double angle_min, double angle_inc, double max_range,

@@ -139,14 +139,19 @@ def expected_close(oracle, cfg, ranges_ref, ranges_qry, guess, max_score):
     return _search(oracle, cfg, oracle.apply_transf(cfg["laser_pose"], ref), ranges_qry, guess, max_score)
 
 
-def expected_close_vset(oracle, cfg, ranges_ref_set, ref_rel, ranges_qry, guess, max_score):
-    """The same with a reference set of several scans (transformPointsFromVSet, scan_matcher.cpp:89-110): ``ref_rel[k]``
+def vset_points(oracle, cfg, ranges_ref_set, ref_rel):
+    """The reference points of a set of several scans (transformPointsFromVSet, scan_matcher.cpp:89-110): ``ref_rel[k]``
     = origin^-1 * v_k, zeros for the origin vertex; every scan goes through (origin^-1 * v_k) * laserPose."""
     parts = []
     for k in range(len(ranges_ref_set)):
         v = oracle.cartesian(ranges_ref_set[k], cfg["angle_min"], cfg["angle_inc"], cfg["max_range"], cfg["min_range"])
         parts.append(oracle.apply_transf(_se2_mul(np.asarray(ref_rel[k], dtype=np.float64), np.asarray(cfg["laser_pose"], dtype=np.float64)), v))
-    return _search(oracle, cfg, np.concatenate(parts), ranges_qry, guess, max_score)
+    return np.concatenate(parts)
+
+
+def expected_close_vset(oracle, cfg, ranges_ref_set, ref_rel, ranges_qry, guess, max_score):
+    """The same with a reference set of several scans: the search over ``vset_points``."""
+    return _search(oracle, cfg, vset_points(oracle, cfg, ranges_ref_set, ref_rel), ranges_qry, guess, max_score)
 
 
 def expected_close_batch(oracle, cfg, ranges_ref, ranges_qry, guess, max_score):

@@ -2,9 +2,10 @@
 match below the grid's resolution"), numpy over ``oracle.rasterize``, the definition taken literally.  Never the code
 under test: not imported by anything under ``cg_mrslam_amd/`` and importing nothing from it.
 
-``refine`` returns the dict the device call returns plus three diagnostics of the run (``diag``): how close any of its
-decisions came to going the other way, how close any point came to a cell boundary, and how badly conditioned any of
-its 3x3 systems was.  The GPU tests compare with the device only where these say the comparison is meaningful.
+``refine`` returns the dict the device call returns plus four diagnostics of the run (``diag``): how close any of its
+decisions came to going the other way, how close any inside point came to a cell boundary, how badly conditioned any of
+its 3x3 systems was, and how close any point, inside or outside, came to the border test itself.  The GPU tests compare
+with the device only where these say the comparison is meaningful.
 """
 import math
 
@@ -36,9 +37,10 @@ def field(oracle, grid, ref_pts):
             int(kr * ks) / ks)
 
 
-def sums_at(fld, qry, pose, kink=None):
+def sums_at(fld, qry, pose, kink=None, border=None):
     """cost, b, H, score, n_active at a pose.  ``kink``: a one-element list that keeps the smallest distance of any u, v
-    of an inside point from an integer."""
+    of an inside point from an integer.  ``border``: a one-element list that keeps the smallest distance, in cells, of any
+    point's u from 0 and nx - 1 and of its v from 0 and ny - 1: the four comparisons of the border test."""
     F, llx, lly, res, fill = fld
     nx, ny = F.shape
     q = np.asarray(qry, dtype=np.float64).reshape(-1, 2)
@@ -48,6 +50,10 @@ def sums_at(fld, qry, pose, kink=None):
     v = ((s * q[:, 0] + c * q[:, 1] + y) - lly) / res
     with np.errstate(invalid="ignore"):
         inside = (u >= 0) & (u < nx - 1) & (v >= 0) & (v < ny - 1)       # 0 <= i0 and i0 + 1 <= nx - 1
+    if border is not None and len(q):
+        with np.errstate(invalid="ignore"):
+            border[0] = min(border[0], float(np.nanmin(np.minimum(np.minimum(np.abs(u), np.abs(u - (nx - 1))),
+                                                                  np.minimum(np.abs(v), np.abs(v - (ny - 1)))))))
     r = np.full(len(q), fill)
     g = np.zeros((len(q), 2))
     if inside.any():
@@ -72,7 +78,7 @@ def refine(oracle, grid, ref_pts, qry_pts, theta_res, winner, params=None, step=
     win = np.asarray(winner, dtype=np.float64)[:3].copy()
     zero = dict(pose=win.copy(), cost0=0.0, cost=0.0, score0=0.0, score=0.0, hessian=np.zeros((3, 3)), n_active=0, n_iters=0,
                 n_halvings=0, stop=0, at_bound=0)
-    diag = dict(decision=math.inf, kink=math.inf, cond=0.0)
+    diag = dict(decision=math.inf, kink=math.inf, cond=0.0, border=math.inf)
     if not found:
         return dict(zero, status=2, diag=diag)
     qry = np.asarray(qry_pts, dtype=np.float64).reshape(-1, 2)
@@ -81,8 +87,8 @@ def refine(oracle, grid, ref_pts, qry_pts, theta_res, winner, params=None, step=
     fld = field(oracle, grid, ref_pts)
     xs, res32 = R.steps_of(grid, step)
     bound = P["bound_steps"] * np.array([xs * res32, xs * res32, theta_res])
-    kink = [math.inf]
-    cur = sums_at(fld, qry, win, kink)
+    kink, border = [math.inf], [math.inf]
+    cur = sums_at(fld, qry, win, kink, border)
     if np.trace(cur["H"]) == 0:
         return dict(zero, status=1, diag=diag)
     cost0, score0 = cur["cost"], cur["score"]
@@ -112,7 +118,7 @@ def refine(oracle, grid, ref_pts, qry_pts, theta_res, winner, params=None, step=
             if np.array_equal(c, pose):
                 stop = 3
                 break
-            cand = sums_at(fld, qry, c, kink)
+            cand = sums_at(fld, qry, c, kink, border)
             diag["decision"] = min(diag["decision"], abs(cand["cost"] - cur["cost"]) / cost0)
             if cand["cost"] < cur["cost"]:
                 delta, pose, cur, moved = cd, c, cand, True
@@ -126,7 +132,7 @@ def refine(oracle, grid, ref_pts, qry_pts, theta_res, winner, params=None, step=
             stop = 2
             break
     at_bound = sum(1 << k for k in range(3) if abs(delta[k]) == bound[k])
-    diag["kink"] = kink[0]
+    diag["kink"], diag["border"] = kink[0], border[0]
     return dict(pose=pose, cost0=cost0, cost=cur["cost"], score0=score0, score=cur["score"], hessian=cur["H"],
                 n_active=cur["n_active"], n_iters=n_iters, n_halvings=n_halvings, stop=stop, at_bound=at_bound, status=0,
                 diag=diag, bound=bound, fill=fld[4])

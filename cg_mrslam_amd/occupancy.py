@@ -54,8 +54,9 @@ class Graph2occupancy:
 
     def geometry(self):
         """graph2occupancy.cpp:44-118: transformed poses, bounding box, size, offset.  Note the reference seeds the
-        maxima with ``numeric_limits<double>::min()`` (the smallest positive double), kept here."""
-        base = np.array([0.0, 0.0, self.angle])
+        maxima with ``numeric_limits<double>::min()`` (the smallest positive double), kept here, and holds the base angle as a
+        ``float`` (graph2occupancy.h:75, srslam.cpp:107): baseTransform turns by float(pi / 2) = 1.5707963705062866."""
+        base = np.array([0.0, 0.0, float(np.float32(self.angle))])
         tposes = np.array([_se2_mul(base, p) for p in self.poses]).reshape(-1, 3)
         ur = float(self.usable_range)
         xmin = ymin = np.finfo(np.float64).max
@@ -101,15 +102,21 @@ class Graph2occupancy:
         self.ctx._check(rc)
         self.hits, self.misses, self.image, self.offset, self.kernel_seconds = hits, misses, image, offset, ks.value
         self.cfg = cfg
-        # map centre (graph2occupancy.cpp:149-158): from the first fixed vertex, if any
-        self.map_center = np.zeros(2, dtype=np.float32)
+        self.map_center = self.mapCenterOf(tposes, size, offset)
+        return True
+
+    def mapCenterOf(self, tposes, size, offset):   # noqa: N802
+        """Map centre (graph2occupancy.cpp:149-158) for the result of ``geometry()``: from the first fixed vertex, if any.
+        Host arithmetic only: float products, double sums, narrowed to float."""
+        center = np.zeros(2, dtype=np.float32)
         if self.fixed is not None and self.fixed.any():
             ip = tposes[int(np.flatnonzero(self.fixed)[0])]
             res = self.resolution
             ox = int(np.rint((np.float32(ip[0]) - offset[0]) / res))
             oy = int(np.rint((np.float32(ip[1]) - offset[1]) / res))
-            self.map_center = np.array([np.float32((-res * oy) + ip[1]), np.float32(-(res * (size[0] - ox) + ip[0]))], dtype=np.float32)
-        return True
+            center[0] = np.float32(float(-res * np.float32(oy)) + ip[1])
+            center[1] = np.float32(-(float(res * np.float32(size[0] - ox)) + ip[0]))
+        return center
 
     def getMapCenter(self):   # noqa: N802
         return self.map_center

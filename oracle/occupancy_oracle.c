@@ -1,9 +1,13 @@
 /* TEST INFRASTRUCTURE ONLY -- CPU restatement of the occupancy-map ray casting of cg_mrslam.
  * Nothing under cg_mrslam_amd/ may import, link or execute this file; it is the checker for the HIP kernels.
  *
- * PARITY UNPINNED: the reference's map publisher needs Eigen, g2o and OpenCV, none of which exist in this image,
- * so it cannot be built or run here and it ships no test vectors.  Every function cites the reference lines it
- * restates; tests/test_oracle_occupancy.py checks this file against an independent plain-Python restatement.
+ * What pins it: the reference's map publisher needs Eigen, g2o and OpenCV, so it is not compiled here and ships no test
+ * vectors.  Instead tests/ref_occupancy.py restates the same reference lines independently in plain Python (float32
+ * scalars, the C library's cosf / sinf), tests/occupancy_cases.py holds small cases with answers worked out by hand
+ * from those lines (rounding ties, the strict comparisons, clipping, every octant, the footprint's cells), and
+ * tests/test_occupancy_cases_cpu.py requires this file to equal both, cell for cell, on every case;
+ * tests/test_oracle_occupancy.py adds a second plain-Python restatement on synthetic scans.  Every function cites the
+ * reference lines it restates.
  *
  *   cfo_grid_line        GridLineTraversal::gridLineCore / gridLine   src/ros_map_publisher/grid_line_traversal.cpp:31-154
  *   cfo_integrate_scan   FrequencyMap::integrateScan + fillRobotPose  src/ros_map_publisher/frequency_map.cpp:27-103

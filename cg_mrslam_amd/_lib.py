@@ -44,7 +44,10 @@ _SYMBOLS = [
     "cgmr_refine_params_default", "cgmr_match_refine", "cgmr_match_refine_batch", "cgmr_close_scan_matching_refined",
     "cgmr_match_polish_batch", "cgmr_scan_matching_lc_polished_batch", "cgmr_scan_matching_lc_polished",
     "cgmr_global_matching_polished_batch", "cgmr_global_matching_polished",
+    "cgmr_marginals_joint", "cgmr_marginals_pairs", "cgmr_relative_covariance",
 ]
+
+JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)
 
 
 def declared_symbols():
@@ -482,6 +485,63 @@ class Context:
         if rc < 0:
             self._check(rc)
         return to[:rc].copy(), est[:rc].copy(), iu[:rc].copy(), cov[:rc].copy(), e2, w
+
+    # joint and pairwise blocks of H^-1, relative-pose uncertainty (include/cgmr.h: cgmr_marginals_joint ...).  ``kind`` None: the
+    # plain call; otherwise robust kernels as marginals_robust takes them, and (e2 [nE], weights [nE]) are appended.
+    def _joint_call(self, entry, poses, fixed, ef, et, meas, info, tail, kind, delta):
+        poses, ef, et, meas, info = self._graph_args(poses, ef, et, meas, info)
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        rk, e2, w, _keep = self._robust(kind, delta, len(ef)) if kind is not None else (None, None, None, None)
+        rc = getattr(self.lib, entry)(self.h, C.c_int(poses.shape[0]), _ptr(poses), _ptr(fixed), C.c_int(len(ef)), _ptr(ef), _ptr(et),
+                                      _ptr(meas), _ptr(info), *tail, C.byref(rk) if rk is not None else C.c_void_p(0))
+        self._check(rc)
+        return () if kind is None else (e2, w)
+
+    @staticmethod
+    def _pair_arrays(pair_a, pair_b):
+        a = np.ascontiguousarray(pair_a, dtype=np.int32).reshape(-1)
+        b = np.ascontiguousarray(pair_b, dtype=np.int32).reshape(-1)
+        if a.shape != b.shape:
+            raise ValueError(f"pairs: {a.shape[0]} first vertices, {b.shape[0]} second vertices")
+        return a, b
+
+    def marginals_joint(self, poses, fixed, ef, et, meas, info, query, kind=None, delta=1.0):
+        """The joint covariance of the query vertices, ``[3 nK, 3 nK]`` in query order (block (k, l) = Sigma of query[k],
+        query[l]); exactly symmetric, zeros for fixed / inactive vertices.  At most JOINT_MAX_QUERIES unique vertices."""
+        query = np.ascontiguousarray(query, dtype=np.int32).reshape(-1)
+        cov = np.zeros((3 * len(query), 3 * len(query)))
+        st = self._joint_call("cgmr_marginals_joint", poses, fixed, ef, et, meas, info,
+                              (C.c_int(len(query)), _ptr(query), _ptr(cov)), kind, delta)
+        return (cov,) + st if st else cov
+
+    def marginals_pairs(self, poses, fixed, ef, et, meas, info, pair_a, pair_b, kind=None, delta=1.0):
+        """(Sigma_aa, Sigma_ab, Sigma_bb), each ``[nP, 3, 3]``, for the vertex pairs (pair_a[p], pair_b[p]) -- any two vertices,
+        not only a graph edge's; rows of Sigma_ab index a."""
+        a, b = self._pair_arrays(pair_a, pair_b)
+        aa, ab, bb = (np.zeros((len(a), 3, 3)) for _ in range(3))
+        st = self._joint_call("cgmr_marginals_pairs", poses, fixed, ef, et, meas, info,
+                              (C.c_int(len(a)), _ptr(a), _ptr(b), _ptr(aa), _ptr(ab), _ptr(bb)), kind, delta)
+        return (aa, ab, bb) + st
+
+    def relative_covariance(self, poses, fixed, ef, et, meas, info, pair_a, pair_b, hyp_meas=None, hyp_info=None, kind=None,
+                            delta=1.0):
+        """(z [nP, 3], Sigma_z [nP, 3, 3], d2 [nP] or None): z = x_a^-1 x_b and its first-order covariance from the joint
+        covariance of (x_a, x_b).  ``hyp_meas`` [nP, 3] (and ``hyp_info`` [nP, 6], upper triangle, optional): d2 is the squared
+        Mahalanobis distance of that hypothesis from z under Sigma_z (+ hyp_info^-1); NaN where not positive definite."""
+        a, b = self._pair_arrays(pair_a, pair_b)
+        n = len(a)
+        hm = hi = d2 = None
+        if hyp_meas is not None:
+            hm = np.ascontiguousarray(hyp_meas, dtype=np.float64).reshape(n, 3)
+            d2 = np.zeros(n)
+        if hyp_info is not None:
+            if hm is None:
+                raise ValueError("hyp_info needs hyp_meas")
+            hi = np.ascontiguousarray(hyp_info, dtype=np.float64).reshape(n, 6)
+        z, cz = np.zeros((n, 3)), np.zeros((n, 3, 3))
+        st = self._joint_call("cgmr_relative_covariance", poses, fixed, ef, et, meas, info,
+                              (C.c_int(n), _ptr(a), _ptr(b), _ptr(z), _ptr(cz), _ptr(hm), _ptr(hi), _ptr(d2)), kind, delta)
+        return (z, cz, d2) + st
 
     def set_symbolic_cache(self, on: bool):
         """Reuse of the ordering / symbolic analysis / structure upload across calls on the same edge list (default on)."""

@@ -1424,6 +1424,171 @@ int marginals_all_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8
   return CGMR_OK;
 }
 
+// Shared driver of cgmr_marginals_joint / cgmr_marginals_pairs / cgmr_relative_covariance: the pass of marginal_driver's mode 0
+// (gn_pass at `poses` with `fixed`), the solve half of launch_marginals for the unique vertices asked for, then the tiles of
+// Y^T Y that hold a requested block (joint_marginals_kernels.hip).
+//   mode 0: joint -- va = the nK queries, out_a = cov [(3 nK)^2]
+//   mode 1: pairs -- (va, vb) the nP pairs, out_a / out_b / out_c = aa / ab / bb (nullable)
+//   mode 2: relative covariance -- the pairs' blocks stay on the device; out_a / out_b / out_c = rel_xyt / rel_cov / d2 (nullable)
+int joint_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                 const int32_t* et, const double* meas, const double* info, int nQ, const int32_t* va, const int32_t* vb,
+                 double* out_a, double* out_b, double* out_c, const double* hyp_meas, const double* hyp_info,
+                 const cgmr_robust* rk) {
+  const char* who = mode == 0 ? "cgmr_marginals_joint" : mode == 1 ? "cgmr_marginals_pairs" : "cgmr_relative_covariance";
+  if (nV <= 0 || nE < 0 || nQ < 0 || !poses || !fixed || (nE > 0 && (!ef || !et || !meas || !info)) ||
+      (nQ > 0 && (!va || (mode != 0 && !vb))) || (mode == 0 && nQ > 0 && !out_a) || (mode == 2 && ((out_c && !hyp_meas) || (hyp_info && !hyp_meas))))
+    return set_err(ctx, CGMR_E_INVALID, "%s: null or negative argument", who);
+  for (int k = 0; k < nQ; k++)
+    if (va[k] < 0 || va[k] >= nV || (mode != 0 && (vb[k] < 0 || vb[k] >= nV)))
+      return set_err(ctx, CGMR_E_INVALID, "%s: vertex index out of range", who);
+  if (nQ == 0) return CGMR_OK;
+  // the unique vertices, in order of first appearance: 4 columns of Y each
+  std::vector<int32_t> slot_of(nV, -1), uq;
+  auto slot = [&](int v) { if (slot_of[v] < 0) { slot_of[v] = (int32_t)uq.size(); uq.push_back(v); } return slot_of[v]; };
+  for (int k = 0; k < nQ; k++) { slot(va[k]); if (mode != 0) slot(vb[k]); }
+  const int nU = (int)uq.size();
+  if (nU > CGMR_JOINT_MAX_QUERIES)
+    return set_err(ctx, CGMR_E_INVALID, "%s: %d unique query vertices, at most CGMR_JOINT_MAX_QUERIES = %d", who, nU, CGMR_JOINT_MAX_QUERIES);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  GnEdges Ed;                                                           // (robust kernels: rho1 at `poses`)
+  int rc = robust_setup(ctx, rk, nE, false, Ed, who);
+  if (rc) return rc;
+  std::vector<double> work(poses, poses + 3 * (size_t)nV);             // the caller's poses stay untouched
+  Symbolic& S = ctx->sym;
+  rc = prepare_structure(ctx, nV, nE, ef, et, 1);
+  if (rc) return rc;
+  rc = prepare_pass(ctx, fixed, nE, ef, et, nE, 0, 1);
+  if (rc) return rc;
+  GnDevice& D = ctx->gn;
+  hipStream_t st = ctx->stream;
+  const size_t nq = (size_t)nQ;
+  const size_t b_a = mode == 0 ? 72 * nq * nq : mode == 1 ? 72 * nq : 24 * nq, b_b = 72 * nq, b_c = mode == 1 ? 72 * nq : 8 * nq;
+  auto zero_outputs = [&]() {
+    if (out_a) memset(out_a, 0, b_a);
+    if (mode != 0 && out_b) memset(out_b, 0, b_b);
+    if (mode != 0 && out_c) memset(out_c, 0, b_c);
+  };
+  if (D.nf == 0 && mode != 2) { HIP_TRY(ctx, hipStreamSynchronize(st)); zero_outputs(); return CGMR_OK; }   // no free vertex: zeros
+  const bool factor = D.nf > 0;
+  // the tiles: every lower one (joint), or those of the pairs' blocks, sorted, each once
+  const MargLayout M(nU, D.nf, S.rows.size(), D.nfronts, 0);
+  const int T = M.m / 16;
+  std::vector<int32_t> qcol(nU), tl, pr;
+  for (int k = 0; k < nU; k++) qcol[k] = ctx->vmask[uq[k]] ? -1 : S.vperm[uq[k]];      // fixed / inactive: zero columns
+  JointGram JG;
+  if (mode == 0) {
+    JG.ntile = (long long)T * (T + 1) / 2;
+    pr.resize(nQ);
+    for (int k = 0; k < nQ; k++) pr[k] = qcol[slot_of[va[k]]] < 0 ? -1 : slot_of[va[k]];
+  } else {
+    std::vector<int64_t> keys;
+    keys.reserve(3 * nq);
+    auto key = [&](int sa, int sb) { const int I = std::max(sa, sb) / 4, J = std::min(sa, sb) / 4; return (int64_t)I * T + J; };
+    for (int k = 0; k < nQ; k++) {
+      const int sa = slot_of[va[k]], sb = slot_of[vb[k]];
+      keys.push_back(key(sa, sa)); keys.push_back(key(sa, sb)); keys.push_back(key(sb, sb));
+    }
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    JG.ntile = (long long)keys.size();
+    tl.resize(2 * keys.size());
+    for (size_t t = 0; t < keys.size(); t++) { tl[2 * t] = (int32_t)(keys[t] / T); tl[2 * t + 1] = (int32_t)(keys[t] % T); }
+    auto pos = [&](int sa, int sb) { return (int32_t)(std::lower_bound(keys.begin(), keys.end(), key(sa, sb)) - keys.begin()); };
+    pr.resize(5 * nq);
+    for (int k = 0; k < nQ; k++) {
+      const int sa = slot_of[va[k]], sb = slot_of[vb[k]];
+      int32_t* P = &pr[5 * (size_t)k];
+      P[0] = qcol[sa] < 0 ? -1 : sa; P[1] = qcol[sb] < 0 ? -1 : sb;
+      P[2] = pos(sa, sa); P[3] = pos(sa, sb); P[4] = pos(sb, sb);
+    }
+  }
+  const long long nwg = mode == 0 ? (long long)((T + 3) / 4) * ((T + 3) / 4 + 1) / 2 : JG.ntile;
+  joint_gram_split(M.n, nwg, &JG.rows, &JG.nsplit);
+  // staging: poses | meas | info | query columns, Y, border vectors, live flags (MargLayout) | tile list | pairs / slots |
+  // partial tiles | tiles | outputs | the pair vertices and the hypotheses
+  Layout256 L;
+  const size_t o_p = L.add(24 * (size_t)nV), o_m = L.add(24 * (size_t)nE), o_i = L.add(48 * (size_t)nE);
+  const MargLayout ML(nU, D.nf, S.rows.size(), D.nfronts, L.off);
+  L.off = ML.end;
+  const size_t o_tl = L.add(4 * tl.size()), o_pr = L.add(4 * pr.size()),
+               o_part = L.add(JG.nsplit > 1 ? 2048 * (size_t)JG.nsplit * (size_t)JG.ntile : 0), o_G = L.add(2048 * (size_t)JG.ntile),
+               o_a = L.add(mode == 0 ? 72 * nq * nq : 72 * nq), o_b = L.add(mode == 0 ? 0 : 72 * nq), o_c = L.add(mode == 0 ? 0 : 72 * nq),
+               o_va = L.add(mode == 2 ? 4 * nq : 0), o_vb = L.add(mode == 2 ? 4 * nq : 0), o_hm = L.add(mode == 2 && hyp_meas ? 24 * nq : 0),
+               o_hi = L.add(mode == 2 && hyp_info ? 48 * nq : 0), o_rz = L.add(mode == 2 ? 24 * nq : 0), o_rc = L.add(mode == 2 ? 72 * nq : 0),
+               o_d2 = L.add(mode == 2 ? 8 * nq : 0);
+  rc = arena_reserve(ctx, ctx->io_arena, L.off + 256);
+  if (rc) return rc;
+  char* d = ctx->io_arena.ptr;
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_p, work.data(), 24 * (size_t)nV, hipMemcpyHostToDevice, st));
+  if (nE > 0) {
+    HIP_TRY(ctx, hipMemcpyAsync(d + o_m, meas, 24 * (size_t)nE, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d + o_i, info, 48 * (size_t)nE, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(d + ML.o_qc, qcol.data(), 4 * (size_t)nU, hipMemcpyHostToDevice, st));
+  if (!tl.empty()) HIP_TRY(ctx, hipMemcpyAsync(d + o_tl, tl.data(), 4 * tl.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_pr, pr.data(), 4 * pr.size(), hipMemcpyHostToDevice, st));
+  if (mode == 2) {
+    HIP_TRY(ctx, hipMemcpyAsync(d + o_va, va, 4 * nq, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d + o_vb, vb, 4 * nq, hipMemcpyHostToDevice, st));
+    if (hyp_meas) HIP_TRY(ctx, hipMemcpyAsync(d + o_hm, hyp_meas, 24 * nq, hipMemcpyHostToDevice, st));
+    if (hyp_info) HIP_TRY(ctx, hipMemcpyAsync(d + o_hi, hyp_info, 48 * nq, hipMemcpyHostToDevice, st));
+  }
+  JG.tiles = mode == 0 ? nullptr : (const int32_t*)(d + o_tl);
+  JG.part = (double*)(d + o_part);
+  JG.G = (double*)(d + o_G);
+  double* dp = (double*)(d + o_p);
+  Ed.meas_a = (const double*)(d + o_m); Ed.info_a = (const double*)(d + o_i); Ed.nA = nE; Ed.n_active = nE;
+  int status4[4] = {0, 0, 0, 0};
+  GnPassOpts pass;
+  pass.write_l11c = true;
+  pass.solve = pass.update_poses = false;
+  const bool want_d2 = mode == 2 && out_c;
+  auto run_pass = [&]() -> int {
+    if (factor) {
+      gn_pass(ctx, dp, Ed, pass);
+      launch_marginals_solve(st, D, nU, (const int32_t*)(d + ML.o_qc), ML.m, (double*)(d + ML.o_Y), (double*)(d + ML.o_U),
+                             (uint8_t*)(d + ML.o_live));
+      launch_joint_gram(st, ML.n, ML.m, (const double*)(d + ML.o_Y), JG);
+      if (mode == 0) launch_joint_extract(st, nQ, (const int32_t*)(d + o_pr), JG.G, (double*)(d + o_a));
+      else launch_pairs_extract(st, nQ, (const int32_t*)(d + o_pr), JG.G, (double*)(d + o_a), (double*)(d + o_b), (double*)(d + o_c));
+      HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
+    } else {                                                           // (mode 2 without a free vertex: zero blocks)
+      HIP_TRY(ctx, hipMemsetAsync(d + o_a, 0, 72 * nq, st));
+      HIP_TRY(ctx, hipMemsetAsync(d + o_b, 0, 72 * nq, st));
+      HIP_TRY(ctx, hipMemsetAsync(d + o_c, 0, 72 * nq, st));
+    }
+    if (mode == 0) HIP_TRY(ctx, hipMemcpyAsync(out_a, d + o_a, b_a, hipMemcpyDeviceToHost, st));
+    if (mode == 1) {
+      if (out_a) HIP_TRY(ctx, hipMemcpyAsync(out_a, d + o_a, b_a, hipMemcpyDeviceToHost, st));
+      if (out_b) HIP_TRY(ctx, hipMemcpyAsync(out_b, d + o_b, b_b, hipMemcpyDeviceToHost, st));
+      if (out_c) HIP_TRY(ctx, hipMemcpyAsync(out_c, d + o_c, b_c, hipMemcpyDeviceToHost, st));
+    }
+    if (mode == 2) {
+      launch_relative_cov(st, nQ, (const int32_t*)(d + o_va), (const int32_t*)(d + o_vb), dp, (const double*)(d + o_a),
+                          (const double*)(d + o_b), (const double*)(d + o_c), hyp_meas ? (const double*)(d + o_hm) : nullptr,
+                          hyp_info ? (const double*)(d + o_hi) : nullptr, (double*)(d + o_rz), (double*)(d + o_rc),
+                          want_d2 ? (double*)(d + o_d2) : nullptr);
+      if (out_a) HIP_TRY(ctx, hipMemcpyAsync(out_a, d + o_rz, b_a, hipMemcpyDeviceToHost, st));
+      if (out_b) HIP_TRY(ctx, hipMemcpyAsync(out_b, d + o_rc, b_b, hipMemcpyDeviceToHost, st));
+      if (want_d2) HIP_TRY(ctx, hipMemcpyAsync(out_c, d + o_d2, b_c, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+  };
+  rc = marginal_pass(ctx, dp, work.data(), nV, status4, run_pass);
+  if (rc) return rc;
+  if (factor) {
+    rc = robust_stats_out(ctx, rk, nE, Ed);
+    if (rc) return rc;
+  }
+  if (status4[0] != 0) {
+    zero_outputs();
+    return set_err(ctx, CGMR_E_CHOLESKY_BASE, "Cholesky failed while computing marginals");
+  }
+  return CGMR_OK;
+}
+
 // The arguments every *_optimize* entry point takes, checked alike; `name`: the entry point family in the error text
 static int optimize_args_check(cgmr_ctx* ctx, const char* name, int nV, const double* poses, const uint8_t* fixed, int nE,
                                const int32_t* from_idx, const int32_t* to_idx, const double* meas, const double* info, int iters) {
@@ -1515,7 +1680,7 @@ using namespace cgmr;
 
 extern "C" {
 
-int cgmr_version(void) { return 105; }   // 105: cgmr_*_optimize_robust*, cgmr_graph_set_edge_robust / _set_received_robust / _edge_stats added, later (same number: callers find them by their symbols) cgmr_marginals_robust, cgmr_marginals_all_robust, cgmr_covariance_estimate_robust, cgmr_condense_robust, cgmr_graph_set_condensed_robust, cgmr_dl_optimize*, cgmr_dl_last_stats, cgmr_graph_set_dogleg_params, cgmr_graph_dl_last (CGMR_ALG_DOGLEG); 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
+int cgmr_version(void) { return 105; }   // 105: cgmr_*_optimize_robust*, cgmr_graph_set_edge_robust / _set_received_robust / _edge_stats added, later (same number: callers find them by their symbols) cgmr_marginals_robust, cgmr_marginals_all_robust, cgmr_covariance_estimate_robust, cgmr_condense_robust, cgmr_graph_set_condensed_robust, cgmr_dl_optimize*, cgmr_dl_last_stats, cgmr_graph_set_dogleg_params, cgmr_graph_dl_last (CGMR_ALG_DOGLEG), cgmr_marginals_joint, cgmr_marginals_pairs, cgmr_relative_covariance; 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
 
 int cgmr_ctx_create(int device, void* hip_stream, cgmr_ctx** out) {
   if (!out) return CGMR_E_INVALID;
@@ -1770,6 +1935,30 @@ int cgmr_condense_robust(cgmr_ctx* ctx, int nV, const double* poses, int nE, con
                          double* est_out, double* info_out, double* cov_out, const cgmr_robust* rk) {
   if (!ctx || !to_out || !est_out || !info_out) return CGMR_E_INVALID;
   return marginal_driver(ctx, 2, nV, poses, nullptr, nE, ef, et, meas, info, gauge, nK, query, to_out, est_out, info_out, cov_out, rk);
+}
+
+int cgmr_marginals_joint(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                         const int32_t* et, const double* meas, const double* info, int nK, const int32_t* query, double* cov_out,
+                         const cgmr_robust* rk) {
+  if (!ctx) return CGMR_E_INVALID;
+  return joint_driver(ctx, 0, nV, poses, fixed, nE, ef, et, meas, info, nK, query, nullptr, cov_out, nullptr, nullptr, nullptr, nullptr, rk);
+}
+
+int cgmr_marginals_pairs(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                         const int32_t* et, const double* meas, const double* info, int nP, const int32_t* pair_a,
+                         const int32_t* pair_b, double* cov_aa_out, double* cov_ab_out, double* cov_bb_out, const cgmr_robust* rk) {
+  if (!ctx) return CGMR_E_INVALID;
+  return joint_driver(ctx, 1, nV, poses, fixed, nE, ef, et, meas, info, nP, pair_a, pair_b, cov_aa_out, cov_ab_out, cov_bb_out, nullptr,
+                      nullptr, rk);
+}
+
+int cgmr_relative_covariance(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                             const int32_t* et, const double* meas, const double* info, int nP, const int32_t* pair_a,
+                             const int32_t* pair_b, double* rel_xyt_out, double* rel_cov_out, const double* hyp_meas,
+                             const double* hyp_info, double* d2_out, const cgmr_robust* rk) {
+  if (!ctx) return CGMR_E_INVALID;
+  return joint_driver(ctx, 2, nV, poses, fixed, nE, ef, et, meas, info, nP, pair_a, pair_b, rel_xyt_out, rel_cov_out, d2_out, hyp_meas,
+                      hyp_info, rk);
 }
 
 int cgmr_set_symbolic_cache(cgmr_ctx* ctx, int on) {

@@ -112,6 +112,32 @@ void launch_marginals(hipStream_t st, const GnDevice& D, int nK, const int32_t* 
                       bool y_is_zero = false);   // y_is_zero: the caller has cleared Y already
 void launch_label(hipStream_t st, int nK, const int32_t* d_qvert, int gauge, const double* poses, const double* cov,
                   double* est, double* info, int* flags, const GnDevice* D = nullptr, const MargBatch* batch = nullptr);
+// The first half of launch_marginals alone: Y = L^-1 E for the query columns (clear Y, unit columns, forward solve level by level)
+void launch_marginals_solve(hipStream_t st, const GnDevice& D, int nK, const int32_t* d_qcol, int m, double* Y, double* Uv,
+                            uint8_t* live, const MargBatch* batch = nullptr, bool y_is_zero = false);
+// joint_marginals_kernels.hip: 16x16 tiles of Y^T Y beyond the diagonal ones.  A tile is 256 doubles, (row, col) at row * 16 + col.
+//   tiles != nullptr: the ntile listed tiles (I, J), J <= I (device memory, 2 ints each), tile t at position t of G
+//   tiles == nullptr: every lower tile of the T = m / 16 tile rows, ntile = T (T + 1) / 2, tile (I, J) at I (I + 1) / 2 + J
+// The n rows of Y are contracted in nsplit ranges of `rows` rows (joint_gram_split); part: nsplit * ntile tiles of scratch
+// (not used with nsplit == 1).
+struct JointGram {
+  const int32_t* tiles = nullptr;
+  long long ntile = 0;
+  int rows = 0, nsplit = 1;
+  double *part = nullptr, *G = nullptr;
+};
+// rows per range and number of ranges for nwg workgroups per range: many workgroups walk more rows each
+void joint_gram_split(int n, long long nwg, int* rows_out, int* nsplit_out);
+void launch_joint_gram(hipStream_t st, int n, int m, const double* Y, const JointGram& J);
+// cov [3 nK x 3 nK] from the dense tile set; slot[k]: the query's 4-column group of Y or -1 (zeros)
+void launch_joint_extract(hipStream_t st, int nK, const int32_t* slot, const double* G, double* cov);
+// aa / ab / bb [nP * 9] from a tile list; pr: per pair the slots of a and b (or -1) and the positions of the tiles of (a, a), (a, b), (b, b)
+void launch_pairs_extract(hipStream_t st, int nP, const int32_t* pr, const double* G, double* aa, double* ab, double* bb);
+// z = x_a^-1 x_b [nP * 3], its covariance [nP * 9], and with a hypothesis (hyp_meas, hyp_info nullable) its squared Mahalanobis
+// distance d2 [nP]; rel / rel_cov / d2 nullable (d2 needs hyp_meas)
+void launch_relative_cov(hipStream_t st, int nP, const int32_t* pa, const int32_t* pb, const double* poses, const double* aa,
+                         const double* ab, const double* bb, const double* hyp_meas, const double* hyp_info, double* rel,
+                         double* rel_cov, double* d2);
 // selinv_kernels.hip: all-pose marginals by selected inversion of the factor in D.Lbuf (gn_pass(.., write_l11c) followed by
 // launch_invert_fronts(.., top_too)).  Sig: every front's dense (w + r)^2 block of H^-1 at soff[front] doubles;
 // tiles: (front, first border row) pairs of every front with a border, level by level, kSelinvTileRows rows each, the

@@ -318,8 +318,9 @@ __global__ void k_label_edges(int nK, const int32_t* __restrict__ qvert, int gau
 }
 
 // ----------------------------------------------------------------------------------- launchers
-void launch_marginals(hipStream_t st, const GnDevice& D, int nK, const int32_t* d_qcol, int m, double* Y, double* Uv,
-                      double* part, double* G, double* cov, int chunk, int nchunk, uint8_t* live, const MargBatch* batch, bool y_is_zero) {
+// the solve half: Y = L^-1 E (also the first half of the joint / pairwise marginals, joint_marginals_kernels.hip)
+void launch_marginals_solve(hipStream_t st, const GnDevice& D, int nK, const int32_t* d_qcol, int m, double* Y, double* Uv,
+                            uint8_t* live, const MargBatch* batch, bool y_is_zero) {
   const int nj = batch ? D.njobs : 1;
   const long long ms = batch ? batch->marg_stride : 0, js = batch ? D.job_stride : 0;
   const CondJobDev* jd = batch ? batch->jobs : nullptr;
@@ -334,6 +335,15 @@ void launch_marginals(hipStream_t st, const GnDevice& D, int nK, const int32_t* 
     hipLaunchKernelGGL(kern, dim3(nfr, m / MB, nj), dim3(256), 0, st, D.fronts, D.level_fronts, D.h_flevel_ptr[l], D.children,
                        D.rel, D.inv, D.Lbuf, m, Y, Uv, live, js, ms);
   }
+}
+
+// the solve half, then the Gram half: the diagonal tiles of Y^T Y and the query blocks out of them
+void launch_marginals(hipStream_t st, const GnDevice& D, int nK, const int32_t* d_qcol, int m, double* Y, double* Uv,
+                      double* part, double* G, double* cov, int chunk, int nchunk, uint8_t* live, const MargBatch* batch, bool y_is_zero) {
+  launch_marginals_solve(st, D, nK, d_qcol, m, Y, Uv, live, batch, y_is_zero);
+  const int nj = batch ? D.njobs : 1;
+  const long long ms = batch ? batch->marg_stride : 0;
+  const CondJobDev* jd = batch ? batch->jobs : nullptr;
   const int T = m / 16;
   hipLaunchKernelGGL(k_gram_diag_partial, dim3(T, nchunk, nj), dim3(256), 0, st, 3 * D.nf, m, chunk, Y, part, ms);
   hipLaunchKernelGGL(k_gram_diag_reduce, dim3((T * 256 + 255) / 256, 1, nj), dim3(256), 0, st, T, nchunk, part, G, ms);

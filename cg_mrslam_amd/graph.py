@@ -316,6 +316,41 @@ class GraphSLAM:
         out = self.ctx.marginals_all_robust(g.poses, g.fixed, ef, et, meas, info, cross, *rk)
         return out[:2] if cross else out[0]
 
+    def _joint_args(self, robust):
+        """The level-0 problem at the current estimates and the robust arguments of the joint / pairwise marginals calls."""
+        g = self.graph
+        rk = self._robust_level0() if robust else None
+        kw = {} if rk is None else dict(kind=rk[0], delta=rk[1])
+        return (g.poses, g.fixed, *g.level0()), kw
+
+    def computeMarginalBlocks(self, blockIndices, robust: bool = False):     # noqa: N802, N803 (g2o spelling)
+        """SparseOptimizer::computeMarginals(spinv, blockIndices): the 3x3 blocks Sigma_ij of H^-1 for arbitrary vertex index
+        pairs ``(i, j)`` -- adjacent or not --, on the level-0 edges at the current estimates as computeMarginals.  Returns
+        ``{(i, j): 3x3}``, rows indexing i.  ``robust`` as for computeMarginals."""
+        pairs = [(int(i), int(j)) for i, j in blockIndices]
+        if not pairs:
+            return {}
+        a, kw = self._joint_args(robust)
+        ab = self.ctx.marginals_pairs(*a, [p[0] for p in pairs], [p[1] for p in pairs], **kw)[1]
+        return {p: ab[k].copy() for k, p in enumerate(pairs)}
+
+    def jointMarginal(self, vertices, robust: bool = False):     # noqa: N802 (g2o spelling)
+        """The joint covariance ``[3 n, 3 n]`` of the given vertex indices, in their order (the input of a Mahalanobis test on
+        several poses at once, or of a condensed graph denser than a star)."""
+        a, kw = self._joint_args(robust)
+        out = self.ctx.marginals_joint(*a, vertices, **kw)
+        return out[0] if kw else out
+
+    def relativeCovariance(self, pairs, hypotheses=None, robust: bool = False):     # noqa: N802 (g2o spelling)
+        """For the vertex index pairs ``(a, b)``: ``(z [n, 3], Sigma_z [n, 3, 3])``, z = x_a^-1 x_b and its covariance, without
+        re-gauging the graph per pair.  ``hypotheses`` = ``(meas [n, 3], info_upper [n, 6] or None)``: a candidate measurement
+        per pair; then ``(z, Sigma_z, d2 [n])`` with the squared Mahalanobis distance a closure is gated on."""
+        pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        a, kw = self._joint_args(robust)
+        hm, hi = (None, None) if hypotheses is None else hypotheses
+        z, cz, d2 = self.ctx.relative_covariance(*a, pairs[:, 0], pairs[:, 1], hm, hi, **kw)[:3]
+        return (z, cz) if hypotheses is None else (z, cz, d2)
+
     def chi2(self) -> float:
         g = self.graph
         ef, et, meas, info = g.level0()

@@ -483,6 +483,47 @@ int cgmr_condense_robust(cgmr_ctx* ctx, int nV, const double* poses_xyt, int nE,
                          const int32_t* query_idx, int32_t* to_out, double* est_out, double* info_upper_out, double* cov_out,
                          const cgmr_robust* rk);
 
+/* Joint and pairwise marginal covariances, and the uncertainty of a relative pose (present in C ABI version 105 libraries that
+ * export these symbols).  cgmr_marginals gives Sigma_vv, cgmr_marginals_all Sigma_ij for the graph's edges; these give
+ * Sigma_ij for ANY two poses -- SparseOptimizer::computeMarginals(spinv, blockIndices) with arbitrary (i, j) [g2o-recalled].
+ * H is linearised at poses_xyt with the given fixed flags, exactly as for cgmr_marginals; the caller's poses are not
+ * modified.  rk (nullable, last): robust kernels as for cgmr_marginals_robust; NULL is the plain call.  All three share the
+ * analysis cache and the bounded-wait fall-back of cgmr_marginals, and return CGMR_OK, CGMR_E_INVALID (null context, null
+ * or negative argument, an index outside [0, nV), too many query vertices -- all before anything is queued),
+ * CGMR_E_CHOLESKY_BASE (outputs zeroed), CGMR_E_TIMEOUT, CGMR_E_HIP / _ALLOC.  Two calls give identical bytes.
+ *
+ * The work is Y = L^-1 E for 4 columns per UNIQUE query vertex (the forward solve of cgmr_marginals), then the 16x16 tiles of
+ * Y^T Y that hold a requested block.  Device memory: Y takes 32 bytes x 3 x free poses per unique query vertex; the Gram
+ * tiles of the dense joint call take (u / 4)(u / 4 + 1) KiB for u unique vertices.  CGMR_JOINT_MAX_QUERIES bounds u in all
+ * three calls: at the limit Y is 64 KiB per row of H (1.8 GiB for 10 000 poses) and the dense tiles are 257 MiB.
+ *
+ * cgmr_marginals_joint: cov_out [(3 nK)^2], row-major, the joint covariance of the query vertices in query order: block
+ *   (k, l) = Sigma_{query[k], query[l]}.  Exactly symmetric.  Fixed / inactive queries give exact zero rows and columns, a
+ *   vertex listed twice gives identical rows and columns.  nK == 0: CGMR_OK, nothing written.
+ * cgmr_marginals_pairs: for pair p the blocks Sigma_aa, Sigma_ab (rows index pair_a[p], columns pair_b[p]) and Sigma_bb,
+ *   each output [nP * 9] and nullable.  The unique vertices of the pairs form the query set; only the tiles that hold a
+ *   requested block are contracted.  A pair with a fixed / inactive end gives a zero Sigma_ab; pair (a, a) gives
+ *   aa == ab == bb.  nP == 0: CGMR_OK, nothing written.
+ * cgmr_relative_covariance: for pair p, rel_xyt_out [nP * 3] = z = x_a^-1 x_b at poses_xyt and rel_cov_out [nP * 9] =
+ *   Sigma_z = J_a Sigma_aa J_a^T + J_a Sigma_ab J_b^T + J_b Sigma_ab^T J_a^T + J_b Sigma_bb J_b^T, J_a / J_b the Jacobians of
+ *   z for the additive (x, y, theta) update (EdgeSE2's, zero measurement).  With a hypothesis per pair -- hyp_meas_xyt
+ *   [nP * 3] and hyp_info_upper [nP * 6] (nullable: no measurement noise) -- d2_out [nP] = e^T (J_e Sigma_z J_e^T +
+ *   Omega^-1)^-1 e, e the EdgeSE2 error of the hypothesis at z: the squared Mahalanobis distance a closure candidate is
+ *   gated on; NaN where that 3x3 matrix is not positive definite.  rel_xyt_out, rel_cov_out, d2_out are nullable; d2_out
+ *   needs hyp_meas_xyt.                                                                                                 */
+#define CGMR_JOINT_MAX_QUERIES 2048
+int cgmr_marginals_joint(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                         const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt, const double* info_upper,
+                         int nK, const int32_t* query_idx, double* cov_out, const cgmr_robust* rk);
+int cgmr_marginals_pairs(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                         const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt, const double* info_upper,
+                         int nP, const int32_t* pair_a, const int32_t* pair_b, double* cov_aa_out, double* cov_ab_out,
+                         double* cov_bb_out, const cgmr_robust* rk);
+int cgmr_relative_covariance(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                             const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt, const double* info_upper,
+                             int nP, const int32_t* pair_a, const int32_t* pair_b, double* rel_xyt_out, double* rel_cov_out,
+                             const double* hyp_meas_xyt, const double* hyp_info_upper, double* d2_out, const cgmr_robust* rk);
+
 /* ------------------------------------------------------------------------------------------
  * Generic correlative search (loop-closure / hierarchical / global matching).
  *

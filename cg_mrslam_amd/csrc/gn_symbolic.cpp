@@ -493,7 +493,7 @@ NDRange nd(NDCtx& C, int begin, int end, int depth, int start = -1, int* node_ou
       for (int k = 1; k < K; k++) if (cand[k].nlev > cand[best].nlev) best = k;
       const Cand& X = cand[best];
       for (int q = 0; q < n; q++) { const int v = X.q[q]; C.vs[v] = X.vs[v]; Q[q] = v; }
-      std::copy(X.lv.begin(), X.lv.begin() + X.nlev + 1, LV);
+      std::copy(X.lv.begin(), X.lv.begin() + X.nlev, LV);   // (nlev <= n entries: LV holds n, and the reader adds the trailing zero itself)
       reached = n;
       multi_done = true;
     }

@@ -442,10 +442,10 @@ int gn_upload(cgmr_ctx* ctx, const Symbolic& S, const int32_t* ef, const int32_t
 }
 
 // `n` extra copies of the numeric work space of the uploaded structure (the structure arrays are shared): independent
-// numeric passes on the same graph -- one condensed graph per peer -- run concurrently on streams of their own.
-int gn_replicas(cgmr_ctx* ctx, int n, std::vector<GnDevice>& out, size_t* stride_out) {
+// numeric passes on the same graph -- one condensed graph per peer -- run as the jobs of one batch.  D: the first copy's view,
+// copy j lies j * *stride_out bytes behind it.
+int gn_replicas(cgmr_ctx* ctx, int n, GnDevice& D, size_t* stride_out) {
   const Symbolic& S = ctx->sym;
-  const GnDevice& D0 = ctx->gn;
   BlobLayout N;
   size_t o_term = N.add<double>((size_t)34 * S.nE), o_A = N.add<double>((size_t)9 * (S.nf + S.nb)), o_b = N.add<double>((size_t)3 * S.nf),
          o_y = N.add<double>((size_t)3 * S.nf), o_x = N.add<double>((size_t)3 * S.nf), o_u = N.add<double>((size_t)3 * S.rows.size() + 3),
@@ -455,29 +455,12 @@ int gn_replicas(cgmr_ctx* ctx, int n, std::vector<GnDevice>& out, size_t* stride
   const size_t per = (N.off + 255) & ~size_t(255);
   int rc = arena_reserve(ctx, ctx->rep_arena, per * (size_t)std::max(n, 1) + 256);
   if (rc) return rc;
-  out.assign(n, D0);
-  if (stride_out) *stride_out = per;
-  for (int i = 0; i < n; i++) {
-    char* d = ctx->rep_arena.ptr + per * (size_t)i;
-    GnDevice& D = out[i];
-    D.term = (double*)(d + o_term); D.Ablk = (double*)(d + o_A); D.bvec = (double*)(d + o_b); D.yvec = (double*)(d + o_y);
-    D.xvec = (double*)(d + o_x); D.uvec = (double*)(d + o_u); D.Lbuf = (double*)(d + o_L); D.Ubuf = (double*)(d + o_U); D.Pan = (double*)(d + o_pan); D.pan_clean = false;
-    D.chi2 = (double*)(d + o_chi); D.status = (int*)(d + o_status); D.ready = (int*)(d + o_ready); D.cmask = (uint8_t*)(d + o_cmask);
-  }
-  return 0;
-}
-
-// side streams for concurrent passes, created on first use
-int aux_streams(cgmr_ctx* ctx, int n) {
-  while ((int)ctx->aux.size() < n) {
-    hipStream_t s = nullptr;
-    hipEvent_t e = nullptr;
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    ctx->aux.push_back(s);
-    ctx->aux_done.push_back(e);
-  }
-  if (!ctx->aux_fork) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->aux_fork, hipEventDisableTiming));
+  *stride_out = per;
+  char* d = ctx->rep_arena.ptr;
+  D = ctx->gn;
+  D.term = (double*)(d + o_term); D.Ablk = (double*)(d + o_A); D.bvec = (double*)(d + o_b); D.yvec = (double*)(d + o_y);
+  D.xvec = (double*)(d + o_x); D.uvec = (double*)(d + o_u); D.Lbuf = (double*)(d + o_L); D.Ubuf = (double*)(d + o_U); D.Pan = (double*)(d + o_pan); D.pan_clean = false;
+  D.chi2 = (double*)(d + o_chi); D.status = (int*)(d + o_status); D.ready = (int*)(d + o_ready); D.cmask = (uint8_t*)(d + o_cmask);
   return 0;
 }
 
@@ -551,14 +534,10 @@ int prepare_structure(cgmr_ctx* ctx, int nV, int nE, const int32_t* ef, const in
 
 // Per numeric pass: the column mask (fixed vertices; vertices whose edges are all switched off when only the
 // first n_active edges take part), the status words.  ctx->vmask keeps the per-vertex flags for the caller.
-int prepare_pass(cgmr_ctx* ctx, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et, int n_active, int slot,
-                 int nslots) {
-  return prepare_pass_on(ctx, ctx->gn, ctx->stream, fixed, nE, ef, et, n_active, slot, nslots);
-}
-
-int prepare_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
-                    int n_active, int slot, int nslots, bool upload, char* stage) {
+int prepare_pass(cgmr_ctx* ctx, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et, int n_active) {
   const Symbolic& S = ctx->sym;
+  GnDevice& D = ctx->gn;
+  hipStream_t st = ctx->stream;
   ctx->vmask.assign(S.nV, 0);
   if (fixed) for (int v = 0; v < S.nV; v++) ctx->vmask[v] = fixed[v] ? 1 : 0;
   if (n_active < nE) {
@@ -566,18 +545,13 @@ int prepare_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, const uint8_t* f
     for (int k = 0; k < n_active; k++) { live[ef[k]] = 1; live[et[k]] = 1; }
     for (int v = 0; v < S.nV; v++) if (!live[v]) ctx->vmask[v] = 1;
   }
-  if (upload) HIP_TRY(ctx, hipMemsetAsync(D.status, 0, 16, st));
+  HIP_TRY(ctx, hipMemsetAsync(D.status, 0, 16, st));
   if (S.nf == 0) return 0;
-  // several passes may be queued without a host synchronisation in between (one condensed graph per peer): each
-  // stages its mask in a slot of its own
-  if (!stage) {
-    int rc = pinned_mask_reserve(ctx, (size_t)S.nf * std::max(nslots, 1));
-    if (rc) return rc;
-    stage = ctx->pinned_mask;
-  }
-  char* pm = stage + (size_t)S.nf * slot;
+  int rc = pinned_mask_reserve(ctx, (size_t)S.nf);
+  if (rc) return rc;
+  char* pm = ctx->pinned_mask;
   for (int c = 0; c < S.nf; c++) pm[c] = (char)ctx->vmask[S.perm[c]];
-  if (upload) HIP_TRY(ctx, hipMemcpyAsync(D.cmask, pm, (size_t)S.nf, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(D.cmask, pm, (size_t)S.nf, hipMemcpyHostToDevice, st));
   return 0;
 }
 
@@ -709,7 +683,7 @@ struct GnCall {
     int rc = prepare_structure(ctx, nV, nE, ef, et, chi_slots, hub_vertices, n_hub_vertices);
     if (rc) return rc;
     t1 = wall_s();
-    rc = prepare_pass(ctx, fixed, nE, ef, et, n_active, 0, 1);
+    rc = prepare_pass(ctx, fixed, nE, ef, et, n_active);
     t2 = wall_s();
     return rc;
   }
@@ -1211,15 +1185,67 @@ static int robust_stats_out(cgmr_ctx* ctx, const cgmr_robust* rk, int nE, const 
   return 0;
 }
 
-// The pass of the marginals entry points: run_pass() queues gn_pass(.., write_l11c) and what reads the factor, reads the
-// status words back into status4 and synchronises.  The poses at dp are `work` (nV of them) when it starts.
-template <typename RunPass>
-int marginal_pass(cgmr_ctx* ctx, double* dp, const double* work, int nV, int* status4, RunPass&& run_pass) {
-  GnDevice& D = ctx->gn;
-  hipStream_t st = ctx->stream;
-  int rc = run_pass();
-  if (rc) return rc;
-  if (status4[2] != 0) {
+// What a marginals entry point does around its own launches, whichever blocks of H^-1 it is after: the robust description, a
+// private copy of the poses, the structure and the masks, the head of the staging block (poses | meas | info; the driver
+// adds its own fields to L behind it), one pass that keeps the factor with what reads it, the statistics and the ending.
+struct MargCall {
+  cgmr_ctx* ctx;
+  int nV, nE;
+  const cgmr_robust* rk;
+  GnEdges Ed;
+  std::vector<double> work;          // pushState: the caller's poses stay untouched
+  Layout256 L;
+  size_t o_p, o_m, o_i;
+  char* d = nullptr;                 // the staging block on the device and the poses in it, from stage() on
+  double* dp = nullptr;
+  bool factor = true;                // false: no free vertex, nothing to factor -- run() queues no pass, close() reads no statistics
+  int status4[4] = {0, 0, 0, 0};
+
+  MargCall(cgmr_ctx* c, int nv, const double* poses, int ne, const cgmr_robust* r)
+      : ctx(c), nV(nv), nE(ne), rk(r), work(poses, poses + 3 * (size_t)nv), o_p(L.add(24 * (size_t)nv)), o_m(L.add(24 * (size_t)ne)),
+        o_i(L.add(48 * (size_t)ne)) {}
+  // robust kernels: rho1 at the pass's linearisation point
+  int open(const char* who) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return robust_setup(ctx, rk, nE, false, Ed, who);
+  }
+  int structure(const uint8_t* fixed, const int32_t* ef, const int32_t* et) {
+    const int rc = prepare_structure(ctx, nV, nE, ef, et, 1);
+    return rc ? rc : prepare_pass(ctx, fixed, nE, ef, et, nE);
+  }
+  // the staging block as L describes it by now; the head goes up
+  int stage(const double* meas, const double* info) {
+    const int rc = arena_reserve(ctx, ctx->io_arena, L.off + 256);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    d = ctx->io_arena.ptr;
+    dp = (double*)(d + o_p);
+    HIP_TRY(ctx, hipMemcpyAsync(dp, work.data(), 24 * (size_t)nV, hipMemcpyHostToDevice, st));
+    if (nE > 0) {
+      HIP_TRY(ctx, hipMemcpyAsync(d + o_m, meas, 24 * (size_t)nE, hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, hipMemcpyAsync(d + o_i, info, 48 * (size_t)nE, hipMemcpyHostToDevice, st));
+    }
+    Ed.meas_a = (const double*)(d + o_m); Ed.info_a = (const double*)(d + o_i); Ed.nA = nE; Ed.n_active = nE;
+    return 0;
+  }
+  // gn_pass(.., write_l11c) at dp, then queue(): the driver's launches that read the factor and its result copies; the status
+  // words come back with them.
+  template <typename Queue>
+  int run(GnPassOpts pass, Queue&& queue) {
+    GnDevice& D = ctx->gn;
+    hipStream_t st = ctx->stream;
+    pass.write_l11c = true;
+    auto once = [&]() -> int {
+      if (factor) gn_pass(ctx, dp, Ed, pass);
+      const int rc = queue();
+      if (rc) return rc;
+      if (factor) HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, hipStreamSynchronize(st));
+      HIP_TRY(ctx, hipGetLastError());
+      return 0;
+    };
+    int rc = once();
+    if (rc || status4[2] == 0) return rc;
     // A bounded wait ran out (status[2]): a hand-off between workgroups of a merged level launch (the forward pass: factor
     // work items -> update tiles) or of the chained backward solve that never arrived -- not a numerical failure.  As gn_run
     // does, the pass is repeated from the same poses with one launch per kernel and level (no in-kernel waits).  The cached
@@ -1229,14 +1255,21 @@ int marginal_pass(cgmr_ctx* ctx, double* dp, const double* work, int nV, int* st
     LevelwiseScope levelwise(ctx, D);                             // (ends with those merges and the chained solve back)
     rc = levelwise.arm(st);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(dp, work, 24 * (size_t)nV, hipMemcpyHostToDevice, st));
-    rc = run_pass();
+    HIP_TRY(ctx, hipMemcpyAsync(dp, work.data(), 24 * (size_t)nV, hipMemcpyHostToDevice, st));
+    rc = once();
     if (rc) return rc;
     if (status4[2] != 0)
       return set_err(ctx, CGMR_E_TIMEOUT, "marginals: a bounded device-side wait (forward hand-off or chained backward solve) ran out twice");
+    return 0;
   }
-  return 0;
-}
+  // the statistics (also after a failed Cholesky: e2 / rho1 of that H), then the factorisation's verdict
+  int close() {
+    const int rc = factor ? robust_stats_out(ctx, rk, nE, Ed) : 0;
+    if (rc) return rc;
+    if (status4[0] != 0) return set_err(ctx, CGMR_E_CHOLESKY_BASE, "Cholesky failed while computing marginals");
+    return 0;
+  }
+};
 
 // Shared driver of cgmr_marginals / cgmr_covariance_estimate / cgmr_condense (host pointers).
 //   mode 0: marginals at `poses` with `fixed`;  mode 1: covariance estimate (gauge);  mode 2: condense (gauge)
@@ -1249,77 +1282,58 @@ int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const 
   if (mode != 0 && (gauge < 0 || gauge >= nV)) return set_err(ctx, CGMR_E_INVALID, "gauge index out of range");
   for (int k = 0; k < nK; k++)
     if (query[k] < 0 || query[k] >= nV) return set_err(ctx, CGMR_E_INVALID, "query index out of range");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // robust kernels: rho1 at the pass's linearisation point (the poses given, or the spanning-tree guess of modes 1 and 2)
-  GnEdges Ed;
-  int rc = robust_setup(ctx, rk, nE, false, Ed, mode == 0 ? "cgmr_marginals_robust" : mode == 1 ? "cgmr_covariance_estimate_robust"
-                                                                                                  : "cgmr_condense_robust");
+  // (the linearisation point: the poses given, or the spanning-tree guess of modes 1 and 2)
+  MargCall call(ctx, nV, poses, nE, rk);
+  int rc = call.open(mode == 0 ? "cgmr_marginals_robust" : mode == 1 ? "cgmr_covariance_estimate_robust" : "cgmr_condense_robust");
   if (rc) return rc;
   std::vector<uint8_t> fixed(nV, 0);
-  std::vector<double> work(poses, poses + 3 * (size_t)nV);             // pushState: the caller's poses stay untouched
   if (mode == 0) { if (!fixed_in) return set_err(ctx, CGMR_E_INVALID, "fixed flags missing"); fixed.assign(fixed_in, fixed_in + nV); }
   else {
     fixed[gauge] = 1;                                                   // fixGauge: every other vertex is freed
-    initial_guess_host(nV, work.data(), fixed.data(), nE, ef, et, meas);
+    initial_guess_host(nV, call.work.data(), fixed.data(), nE, ef, et, meas);
   }
   // query list (condense: everything but the gauge)
   std::vector<int32_t> q;
   for (int k = 0; k < nK; k++) if (mode != 2 || query[k] != gauge) q.push_back(query[k]);
   const int nq = (int)q.size();
   if (cov_out && mode != 2) memset(cov_out, 0, sizeof(double) * 9 * (size_t)nK);
+  rc = call.structure(fixed.data(), ef, et);
+  if (rc) return rc;
   Symbolic& S = ctx->sym;
-  rc = prepare_structure(ctx, nV, nE, ef, et, 1);
-  if (rc) return rc;
-  rc = prepare_pass(ctx, fixed.data(), nE, ef, et, nE, 0, 1);
-  if (rc) return rc;
   GnDevice& D = ctx->gn;
   hipStream_t st = ctx->stream;
   if (D.nf == 0 || nq == 0) { HIP_TRY(ctx, hipStreamSynchronize(st)); return mode == 2 ? 0 : CGMR_OK; }
   // staging: poses | meas | info | the marginals' and labels' work space
-  Layout256 L;
-  const size_t o_p = L.add(24 * (size_t)nV), o_m = L.add(24 * (size_t)nE), o_i = L.add(48 * (size_t)nE);
-  const MargLayout M(nq, D.nf, S.rows.size(), D.nfronts, L.off);
-  rc = arena_reserve(ctx, ctx->io_arena, M.end + 256);
+  const MargLayout M(nq, D.nf, S.rows.size(), D.nfronts, call.L.off);
+  call.L.off = M.end;
+  rc = call.stage(meas, info);
   if (rc) return rc;
-  char* d = ctx->io_arena.ptr;
+  char* d = call.d;
   std::vector<int32_t> qcol(nq);
   for (int k = 0; k < nq; k++) qcol[k] = ctx->vmask[q[k]] ? -1 : S.vperm[q[k]];     // fixed / inactive: zeros
-  HIP_TRY(ctx, hipMemcpyAsync(d + o_p, work.data(), 24 * (size_t)nV, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d + o_m, meas, 24 * (size_t)nE, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d + o_i, info, 48 * (size_t)nE, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d + M.o_qc, qcol.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d + M.o_qv, q.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, st));
-  double* dp = (double*)(d + o_p);
   // the Hessian of this iteration (linearised at the initial guess) is what computeMarginals sees [g2o-recalled];
   // for the condensed graph the iteration is completed first: the factor stays valid, the poses move on
-  Ed.meas_a = (const double*)(d + o_m); Ed.info_a = (const double*)(d + o_i); Ed.nA = nE; Ed.n_active = nE;
-  int status4[4] = {0, 0, 0, 0};
   std::vector<double> cov(9 * (size_t)nq);
   GnPassOpts pass;
-  pass.write_l11c = true;
   pass.solve = pass.update_poses = mode == 2;
-  auto run_pass = [&]() -> int {
-    gn_pass(ctx, dp, Ed, pass);
+  rc = call.run(pass, [&]() -> int {
     launch_marginals(st, D, nq, (const int32_t*)(d + M.o_qc), M.m, (double*)(d + M.o_Y), (double*)(d + M.o_U), (double*)(d + M.o_part),
                      (double*)(d + M.o_G), (double*)(d + M.o_cov), M.chunk, M.nchunk, (uint8_t*)(d + M.o_live));
     if (mode == 2)
-      launch_label(st, nq, (const int32_t*)(d + M.o_qv), gauge, dp, (const double*)(d + M.o_cov), (double*)(d + M.o_est),
+      launch_label(st, nq, (const int32_t*)(d + M.o_qv), gauge, call.dp, (const double*)(d + M.o_cov), (double*)(d + M.o_est),
                    (double*)(d + M.o_info), (int*)(d + M.o_fl));
     HIP_TRY(ctx, hipMemcpyAsync(cov.data(), d + M.o_cov, 72 * (size_t)nq, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
     if (mode == 2) {
       HIP_TRY(ctx, hipMemcpyAsync(est_out, d + M.o_est, 24 * (size_t)nq, hipMemcpyDeviceToHost, st));
       HIP_TRY(ctx, hipMemcpyAsync(info_out, d + M.o_info, 48 * (size_t)nq, hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    HIP_TRY(ctx, hipGetLastError());
     return 0;
-  };
-  rc = marginal_pass(ctx, dp, work.data(), nV, status4, run_pass);
+  });
   if (rc) return rc;
-  rc = robust_stats_out(ctx, rk, nE, Ed);                            // (also after a failed Cholesky: e2 / rho1 of that H)
+  rc = call.close();
   if (rc) return rc;
-  if (status4[0] != 0) return set_err(ctx, CGMR_E_CHOLESKY_BASE, "Cholesky failed while computing marginals");
   if (mode == 2) {
     for (int k = 0; k < nq; k++) to_out[k] = q[k];
     if (cov_out) memcpy(cov_out, cov.data(), 72 * (size_t)nq);
@@ -1339,18 +1353,17 @@ int marginals_all_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8
   if (nV <= 0 || nE < 0 || !poses || !cov_out || (nE > 0 && (!ef || !et || !meas || !info)))
     return set_err(ctx, CGMR_E_INVALID, "marginals: null or negative argument");
   if (!fixed) return set_err(ctx, CGMR_E_INVALID, "fixed flags missing");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  GnEdges Ed;                                                           // (robust kernels: rho1 at `poses`)
-  int rc = robust_setup(ctx, rk, nE, false, Ed, "cgmr_marginals_all_robust");
+  MargCall call(ctx, nV, poses, nE, rk);
+  int rc = call.open("cgmr_marginals_all_robust");
   if (rc) return rc;
-  std::vector<double> work(poses, poses + 3 * (size_t)nV);             // the caller's poses stay untouched
-  memset(cov_out, 0, 72 * (size_t)nV);
-  if (cross_out) memset(cross_out, 0, 72 * (size_t)nE);
+  auto zero_outputs = [&]() {
+    memset(cov_out, 0, 72 * (size_t)nV);
+    if (cross_out) memset(cross_out, 0, 72 * (size_t)nE);
+  };
+  zero_outputs();
+  rc = call.structure(fixed, ef, et);
+  if (rc) return rc;
   Symbolic& S = ctx->sym;
-  rc = prepare_structure(ctx, nV, nE, ef, et, 1);
-  if (rc) return rc;
-  rc = prepare_pass(ctx, fixed, nE, ef, et, nE, 0, 1);
-  if (rc) return rc;
   GnDevice& D = ctx->gn;
   hipStream_t st = ctx->stream;
   if (D.nf == 0) { HIP_TRY(ctx, hipStreamSynchronize(st)); return CGMR_OK; }
@@ -1375,18 +1388,14 @@ int marginals_all_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8
   std::vector<int32_t> vcol(nV);
   for (int v = 0; v < nV; v++) vcol[v] = ctx->vmask[v] ? -1 : S.vperm[v];     // fixed / inactive: zeros
   // staging: poses | meas | info | vcol | col_front | soff | tiles | cov | cross;  Sigma: an arena of its own
-  Layout256 L;
-  const size_t o_p = L.add(24 * (size_t)nV), o_m = L.add(24 * (size_t)nE), o_i = L.add(48 * (size_t)nE), o_vc = L.add(4 * (size_t)nV),
-               o_cf = L.add(4 * (size_t)D.nf), o_so = L.add(8 * soff.size()), o_t = L.add(4 * tiles.size()), o_cov = L.add(72 * (size_t)nV),
-               o_cr = L.add(72 * (size_t)nE);
-  rc = arena_reserve(ctx, ctx->io_arena, L.off + 256);
-  if (rc) return rc;
+  Layout256& L = call.L;
+  const size_t o_vc = L.add(4 * (size_t)nV), o_cf = L.add(4 * (size_t)D.nf), o_so = L.add(8 * soff.size()), o_t = L.add(4 * tiles.size()),
+               o_cov = L.add(72 * (size_t)nV), o_cr = L.add(72 * (size_t)nE);
   rc = arena_reserve(ctx, ctx->si_arena, 8 * (size_t)soff[nfr]);
   if (rc) return rc;
-  char* d = ctx->io_arena.ptr;
-  HIP_TRY(ctx, hipMemcpyAsync(d + o_p, work.data(), 24 * (size_t)nV, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d + o_m, meas, 24 * (size_t)nE, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d + o_i, info, 48 * (size_t)nE, hipMemcpyHostToDevice, st));
+  rc = call.stage(meas, info);
+  if (rc) return rc;
+  char* d = call.d;
   HIP_TRY(ctx, hipMemcpyAsync(d + o_vc, vcol.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d + o_cf, S.col_front.data(), 4 * (size_t)D.nf, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d + o_so, soff.data(), 8 * soff.size(), hipMemcpyHostToDevice, st));
@@ -1394,34 +1403,20 @@ int marginals_all_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8
   P.Sig = (double*)ctx->si_arena.ptr;
   P.soff = (const int64_t*)(d + o_so);
   P.tiles = (const int32_t*)(d + o_t);
-  double* dp = (double*)(d + o_p);
-  Ed.meas_a = (const double*)(d + o_m); Ed.info_a = (const double*)(d + o_i); Ed.nA = nE; Ed.n_active = nE;
-  int status4[4] = {0, 0, 0, 0};
   GnPassOpts pass;
-  pass.write_l11c = true;
   pass.solve = false;
-  auto run_pass = [&]() -> int {
-    gn_pass(ctx, dp, Ed, pass);
+  rc = call.run(pass, [&]() -> int {
     launch_invert_fronts(st, D, /*top_too=*/true);                     // Z = L11^-1 of every front, the top block's included
     launch_selinv(st, D, P, nV, nE, (const int32_t*)(d + o_vc), (const int32_t*)(d + o_cf), (double*)(d + o_cov),
                   cross_out ? (double*)(d + o_cr) : nullptr);
     HIP_TRY(ctx, hipMemcpyAsync(cov_out, d + o_cov, 72 * (size_t)nV, hipMemcpyDeviceToHost, st));
     if (cross_out && nE > 0) HIP_TRY(ctx, hipMemcpyAsync(cross_out, d + o_cr, 72 * (size_t)nE, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    HIP_TRY(ctx, hipGetLastError());
     return 0;
-  };
-  rc = marginal_pass(ctx, dp, work.data(), nV, status4, run_pass);
+  });
   if (rc) return rc;
-  rc = robust_stats_out(ctx, rk, nE, Ed);
-  if (rc) return rc;
-  if (status4[0] != 0) {
-    memset(cov_out, 0, 72 * (size_t)nV);
-    if (cross_out) memset(cross_out, 0, 72 * (size_t)nE);
-    return set_err(ctx, CGMR_E_CHOLESKY_BASE, "Cholesky failed while computing marginals");
-  }
-  return CGMR_OK;
+  rc = call.close();
+  if (rc == CGMR_E_CHOLESKY_BASE) zero_outputs();
+  return rc;
 }
 
 // Shared driver of cgmr_marginals_joint / cgmr_marginals_pairs / cgmr_relative_covariance: the pass of marginal_driver's mode 0
@@ -1449,16 +1444,12 @@ int joint_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uin
   const int nU = (int)uq.size();
   if (nU > CGMR_JOINT_MAX_QUERIES)
     return set_err(ctx, CGMR_E_INVALID, "%s: %d unique query vertices, at most CGMR_JOINT_MAX_QUERIES = %d", who, nU, CGMR_JOINT_MAX_QUERIES);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  GnEdges Ed;                                                           // (robust kernels: rho1 at `poses`)
-  int rc = robust_setup(ctx, rk, nE, false, Ed, who);
+  MargCall call(ctx, nV, poses, nE, rk);
+  int rc = call.open(who);
   if (rc) return rc;
-  std::vector<double> work(poses, poses + 3 * (size_t)nV);             // the caller's poses stay untouched
+  rc = call.structure(fixed, ef, et);
+  if (rc) return rc;
   Symbolic& S = ctx->sym;
-  rc = prepare_structure(ctx, nV, nE, ef, et, 1);
-  if (rc) return rc;
-  rc = prepare_pass(ctx, fixed, nE, ef, et, nE, 0, 1);
-  if (rc) return rc;
   GnDevice& D = ctx->gn;
   hipStream_t st = ctx->stream;
   const size_t nq = (size_t)nQ;
@@ -1469,7 +1460,7 @@ int joint_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uin
     if (mode != 0 && out_c) memset(out_c, 0, b_c);
   };
   if (D.nf == 0 && mode != 2) { HIP_TRY(ctx, hipStreamSynchronize(st)); zero_outputs(); return CGMR_OK; }   // no free vertex: zeros
-  const bool factor = D.nf > 0;
+  call.factor = D.nf > 0;
   // the tiles: every lower one (joint), or those of the pairs' blocks, sorted, each once
   const MargLayout M(nU, D.nf, S.rows.size(), D.nfronts, 0);
   const int T = M.m / 16;
@@ -1506,8 +1497,7 @@ int joint_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uin
   joint_gram_split(M.n, nwg, &JG.rows, &JG.nsplit);
   // staging: poses | meas | info | query columns, Y, border vectors, live flags (MargLayout) | tile list | pairs / slots |
   // partial tiles | tiles | outputs | the pair vertices and the hypotheses
-  Layout256 L;
-  const size_t o_p = L.add(24 * (size_t)nV), o_m = L.add(24 * (size_t)nE), o_i = L.add(48 * (size_t)nE);
+  Layout256& L = call.L;
   const MargLayout ML(nU, D.nf, S.rows.size(), D.nfronts, L.off);
   L.off = ML.end;
   const size_t o_tl = L.add(4 * tl.size()), o_pr = L.add(4 * pr.size()),
@@ -1516,14 +1506,9 @@ int joint_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uin
                o_va = L.add(mode == 2 ? 4 * nq : 0), o_vb = L.add(mode == 2 ? 4 * nq : 0), o_hm = L.add(mode == 2 && hyp_meas ? 24 * nq : 0),
                o_hi = L.add(mode == 2 && hyp_info ? 48 * nq : 0), o_rz = L.add(mode == 2 ? 24 * nq : 0), o_rc = L.add(mode == 2 ? 72 * nq : 0),
                o_d2 = L.add(mode == 2 ? 8 * nq : 0);
-  rc = arena_reserve(ctx, ctx->io_arena, L.off + 256);
+  rc = call.stage(meas, info);
   if (rc) return rc;
-  char* d = ctx->io_arena.ptr;
-  HIP_TRY(ctx, hipMemcpyAsync(d + o_p, work.data(), 24 * (size_t)nV, hipMemcpyHostToDevice, st));
-  if (nE > 0) {
-    HIP_TRY(ctx, hipMemcpyAsync(d + o_m, meas, 24 * (size_t)nE, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d + o_i, info, 48 * (size_t)nE, hipMemcpyHostToDevice, st));
-  }
+  char* d = call.d;
   HIP_TRY(ctx, hipMemcpyAsync(d + ML.o_qc, qcol.data(), 4 * (size_t)nU, hipMemcpyHostToDevice, st));
   if (!tl.empty()) HIP_TRY(ctx, hipMemcpyAsync(d + o_tl, tl.data(), 4 * tl.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d + o_pr, pr.data(), 4 * pr.size(), hipMemcpyHostToDevice, st));
@@ -1536,22 +1521,16 @@ int joint_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uin
   JG.tiles = mode == 0 ? nullptr : (const int32_t*)(d + o_tl);
   JG.part = (double*)(d + o_part);
   JG.G = (double*)(d + o_G);
-  double* dp = (double*)(d + o_p);
-  Ed.meas_a = (const double*)(d + o_m); Ed.info_a = (const double*)(d + o_i); Ed.nA = nE; Ed.n_active = nE;
-  int status4[4] = {0, 0, 0, 0};
   GnPassOpts pass;
-  pass.write_l11c = true;
   pass.solve = pass.update_poses = false;
   const bool want_d2 = mode == 2 && out_c;
-  auto run_pass = [&]() -> int {
-    if (factor) {
-      gn_pass(ctx, dp, Ed, pass);
+  rc = call.run(pass, [&]() -> int {
+    if (call.factor) {
       launch_marginals_solve(st, D, nU, (const int32_t*)(d + ML.o_qc), ML.m, (double*)(d + ML.o_Y), (double*)(d + ML.o_U),
                              (uint8_t*)(d + ML.o_live));
       launch_joint_gram(st, ML.n, ML.m, (const double*)(d + ML.o_Y), JG);
       if (mode == 0) launch_joint_extract(st, nQ, (const int32_t*)(d + o_pr), JG.G, (double*)(d + o_a));
       else launch_pairs_extract(st, nQ, (const int32_t*)(d + o_pr), JG.G, (double*)(d + o_a), (double*)(d + o_b), (double*)(d + o_c));
-      HIP_TRY(ctx, hipMemcpyAsync(status4, D.status, sizeof status4, hipMemcpyDeviceToHost, st));
     } else {                                                           // (mode 2 without a free vertex: zero blocks)
       HIP_TRY(ctx, hipMemsetAsync(d + o_a, 0, 72 * nq, st));
       HIP_TRY(ctx, hipMemsetAsync(d + o_b, 0, 72 * nq, st));
@@ -1564,7 +1543,7 @@ int joint_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uin
       if (out_c) HIP_TRY(ctx, hipMemcpyAsync(out_c, d + o_c, b_c, hipMemcpyDeviceToHost, st));
     }
     if (mode == 2) {
-      launch_relative_cov(st, nQ, (const int32_t*)(d + o_va), (const int32_t*)(d + o_vb), dp, (const double*)(d + o_a),
+      launch_relative_cov(st, nQ, (const int32_t*)(d + o_va), (const int32_t*)(d + o_vb), call.dp, (const double*)(d + o_a),
                           (const double*)(d + o_b), (const double*)(d + o_c), hyp_meas ? (const double*)(d + o_hm) : nullptr,
                           hyp_info ? (const double*)(d + o_hi) : nullptr, (double*)(d + o_rz), (double*)(d + o_rc),
                           want_d2 ? (double*)(d + o_d2) : nullptr);
@@ -1572,21 +1551,12 @@ int joint_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uin
       if (out_b) HIP_TRY(ctx, hipMemcpyAsync(out_b, d + o_rc, b_b, hipMemcpyDeviceToHost, st));
       if (want_d2) HIP_TRY(ctx, hipMemcpyAsync(out_c, d + o_d2, b_c, hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    HIP_TRY(ctx, hipGetLastError());
     return 0;
-  };
-  rc = marginal_pass(ctx, dp, work.data(), nV, status4, run_pass);
+  });
   if (rc) return rc;
-  if (factor) {
-    rc = robust_stats_out(ctx, rk, nE, Ed);
-    if (rc) return rc;
-  }
-  if (status4[0] != 0) {
-    zero_outputs();
-    return set_err(ctx, CGMR_E_CHOLESKY_BASE, "Cholesky failed while computing marginals");
-  }
-  return CGMR_OK;
+  rc = call.close();
+  if (rc == CGMR_E_CHOLESKY_BASE) zero_outputs();
+  return rc;
 }
 
 // The arguments every *_optimize* entry point takes, checked alike; `name`: the entry point family in the error text
@@ -1729,11 +1699,8 @@ void cgmr_ctx_destroy(cgmr_ctx* ctx) {
   if (ctx->st_arena.ptr) (void)hipFree(ctx->st_arena.ptr);
   if (ctx->pinned_st) (void)hipHostFree(ctx->pinned_st);
   if (ctx->ev_st_copied) (void)hipEventDestroy(ctx->ev_st_copied);
-  for (hipStream_t a : ctx->aux) { (void)hipStreamSynchronize(a); (void)hipStreamDestroy(a); }
   if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); }
   for (hipEvent_t e : {ctx->side_fork, ctx->side_tail}) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : ctx->aux_done) (void)hipEventDestroy(e);
-  if (ctx->aux_fork) (void)hipEventDestroy(ctx->aux_fork);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   if (ctx->pinned_mask) (void)hipHostFree(ctx->pinned_mask);
   for (hipEvent_t e : {ctx->ev0, ctx->ev1, ctx->ev_a, ctx->ev_b})

@@ -49,9 +49,6 @@ struct cgmr_ctx {
   size_t pinned_st_cap = 0;
   hipEvent_t ev_st_copied = nullptr;   // behind the last copy out of pinned_st
   struct StView { int32_t *vperm = nullptr, *ef = nullptr, *et = nullptr, *off_row = nullptr, *off_col = nullptr, *offbase = nullptr, *asm_ptr = nullptr, *asm_src = nullptr; } st_view;
-  std::vector<hipStream_t> aux;          // side streams of the concurrent passes
-  std::vector<hipEvent_t> aux_done;
-  hipEvent_t aux_fork = nullptr;
   // Side stream: batches of condensed-graph passes queued without waiting for them (cgmr_graph_compute_condensed_async) run
   // beside whatever the context's stream does next -- the next round's structure analysis on the host, its solve on the
   // device.  They work in replicas of the numeric buffers and READ the uploaded structure: a new structure upload, a

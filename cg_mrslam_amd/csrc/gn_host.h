@@ -17,17 +17,12 @@ int pinned_mask_reserve(cgmr_ctx* ctx, size_t bytes);
 // hub_vertices (nullable): vertices the ordering keeps out of the dissection and eliminates last (gn_symbolic.h: analyze)
 int prepare_structure(cgmr_ctx* ctx, int nV, int nE, const int32_t* ef, const int32_t* et, int iters,
                       const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0);
-// per numeric pass: column mask (fixed vertices; vertices without an edge among the first n_active), status words;
-// ctx->vmask keeps the per-vertex flags.  slot / nslots: staging slot of the mask when passes are queued back to back
-int prepare_pass(cgmr_ctx* ctx, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et, int n_active, int slot,
-                 int nslots);
-int prepare_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
-                    int n_active, int slot, int nslots, bool upload = true, char* stage = nullptr);   // stage: the masks' staging block (default: the context's)
-// (upload = false: the mask is only staged, in slot `slot` of `stage`, for a caller that uploads the slots of a batch itself)
-// n extra copies of the numeric work space of the uploaded structure (stride_out: bytes from one copy to the next); side
-// streams for concurrent passes
-int gn_replicas(cgmr_ctx* ctx, int n, std::vector<GnDevice>& out, size_t* stride_out = nullptr);
-int aux_streams(cgmr_ctx* ctx, int n);
+// per numeric pass on the context's own view and stream: column mask (fixed vertices; vertices without an edge among the first
+// n_active), status words; ctx->vmask keeps the per-vertex flags
+int prepare_pass(cgmr_ctx* ctx, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et, int n_active);
+// n extra copies of the numeric work space of the uploaded structure: D = the first copy's view, *stride_out = bytes from one
+// copy to the next
+int gn_replicas(cgmr_ctx* ctx, int n, GnDevice& D, size_t* stride_out);
 // A block of device or pinned memory laid out field by field, every field on a 256-byte boundary.
 struct Layout256 {
   size_t off = 0;
@@ -37,12 +32,12 @@ struct Layout256 {
 // The work space of launch_marginals and launch_label for nq query vertices, from `base` on: query columns | query vertices |
 // Y (3 nf x m) | border vectors (rows: Symbolic::rows.size()) | partial Gram sums | G | covariances | the labelled edges'
 // estimates, information matrices and flags | live tiles per front; `end`: the first byte behind it.  The two users keep the
-// order they always had behind the covariances (flags_first: flags | estimates | information | 16 bytes of status words,
-// else estimates | information | flags), so no offset that reaches the device has moved.
+// order they always had behind the covariances (flags_first: flags | estimates | information, else estimates | information |
+// flags).
 struct MargLayout {
   static constexpr int chunk = 2048;
   int m = 0, n = 0, nchunk = 0;
-  size_t o_qc = 0, o_qv = 0, o_Y = 0, o_U = 0, o_part = 0, o_G = 0, o_cov = 0, o_est = 0, o_info = 0, o_fl = 0, o_st = 0, o_live = 0, end = 0;
+  size_t o_qc = 0, o_qv = 0, o_Y = 0, o_U = 0, o_part = 0, o_G = 0, o_cov = 0, o_est = 0, o_info = 0, o_fl = 0, o_live = 0, end = 0;
   MargLayout() = default;
   MargLayout(int nq, int nf, size_t rows, int nfronts, size_t base = 0, bool flags_first = false)
       : m(((4 * nq + 15) / 16) * 16),   // 4 columns of Y per query (3 + 1 padding): a query never straddles a 16-column tile
@@ -53,7 +48,7 @@ struct MargLayout {
     o_cov = L.add(72 * (size_t)nq);
     if (flags_first) o_fl = L.add(4 * (size_t)nq);
     o_est = L.add(24 * (size_t)nq); o_info = L.add(48 * (size_t)nq);
-    if (flags_first) o_st = L.add(16); else o_fl = L.add(4 * (size_t)nq);
+    if (!flags_first) o_fl = L.add(4 * (size_t)nq);
     o_live = L.add((size_t)(nfronts > 1 ? nfronts : 1) * (m / 16));
     end = L.off;
   }

@@ -84,7 +84,7 @@ struct cgmr_graph {
   // host staging of received numeric data (host-only mode and getters): slot-indexed like the device staging
   std::vector<double> hs_meas, hs_info;
   // device
-  DevBuf d_poses, d_meas_a, d_info_a, d_vids, d_work;
+  DevBuf d_poses, d_meas_a, d_info_a, d_vids;
   char* d_fixed_block = nullptr;      // one allocation for the fixed-size buffers below
   double *d_stage_meas = nullptr, *d_stage_info = nullptr, *d_tmp_meas = nullptr, *d_tmp_info = nullptr;
   double *d_meas_b = nullptr, *d_info_b = nullptr, *d_est64 = nullptr, *d_info64 = nullptr, *d_qposes = nullptr;
@@ -413,7 +413,7 @@ void cgmr_graph_destroy(cgmr_graph* g) {
     (void)hipSetDevice(g->ctx->device);
     (void)hipStreamSynchronize(g->ctx->stream);
     (void)side_join_host(g->ctx);
-    for (DevBuf* b : {&g->d_poses, &g->d_meas_a, &g->d_info_a, &g->d_vids, &g->d_work, &g->d_rk_kind, &g->d_rk_delta})
+    for (DevBuf* b : {&g->d_poses, &g->d_meas_a, &g->d_info_a, &g->d_vids, &g->d_rk_kind, &g->d_rk_delta})
       if (b->ptr) (void)hipFree(b->ptr);
     // the blocks this graph's arrays have outgrown (nothing of it is in flight any more: both streams were waited for above)
     auto& gy = g->ctx->graveyard;
@@ -764,7 +764,6 @@ struct CondBatch {
   int nV, nA, nE = 0, nj, nf = 0, maxq = 1;
   const int32_t *s_ef = nullptr, *s_et = nullptr;   // the edge list the structure was analysed for (own edges first)
   hipStream_t st = nullptr;           // the context's stream, or its side stream for a batch that is not waited for
-  std::vector<GnDevice> reps;         // a view of every job's copy of the numeric work space (the passes on streams)
   GnDevice DB;                        // the batch's view: job 0's, job j moved by j * DB.job_stride
   GnEdges Ed;
   MargLayout M;                       // one job's marginals work space; job j: moved by j * per_job
@@ -803,9 +802,8 @@ int cond_setup(CondBatch& B) {
   B.nf = ctx->gn.nf;
   const size_t rep_cap0 = ctx->rep_arena.cap, mg_cap0 = ctx->mg_arena.cap;
   size_t rep_stride = 0;
-  rc = gn_replicas(ctx, B.nj, B.reps, &rep_stride);
+  rc = gn_replicas(ctx, B.nj, B.DB, &rep_stride);
   if (rc) return rc;
-  B.DB = B.reps[0];
   B.DB.njobs = B.nj; B.DB.job_stride = (long long)rep_stride; B.DB.pose_stride = 24LL * B.nV;
   const double t1a = wall_s();
   for (CondJob& J : B.jobs) B.maxq = std::max(B.maxq, (int)J.q.size());
@@ -859,17 +857,18 @@ int cond_stage_block(CondBatch& B, bool go_async) {
   return 0;
 }
 
-// GraphManipulator::fixGauge + optimize(1) (graph_manipulator.cpp:62-124): only the gauge is fixed, spanning-tree initial
-// guess over my own edges with the gauge as the root (0.15-0.3 ms of host work each: on the helper threads); dst(i): where job
-// i's guess goes
-template <typename Dst>
-void cond_guesses(CondBatch& B, Dst&& dst) {
+// The host's part of the batch, written straight into the staging block: every job's initial guess, column mask, query lists
+// and descriptor.  The guess is GraphManipulator::fixGauge + optimize(1) (graph_manipulator.cpp:62-124): only the gauge is fixed,
+// spanning-tree initial guess over my own edges with the gauge as the root (0.15-0.3 ms of host work each: on the helper threads).
+void cond_fill_stage(CondBatch& B) {
   const cgmr_graph* g = B.g;
-  const int nV = B.nV, nA = B.nA;
+  const Symbolic& S = B.ctx->sym;
+  const int nV = B.nV, nA = B.nA, nf = B.nf, maxq = B.maxq;
+  char* h = B.hstage;
   const double tg0 = wall_s();
   static const bool cached_walk = !(getenv("CGMR_GUESS_CACHED") && atoi(getenv("CGMR_GUESS_CACHED")) == 0);
   host_run_tasks(B.nj, [&](int i) {
-    double* w = dst(i);
+    double* w = (double*)(h + B.S.s_work + (size_t)24 * nV * i);
     memcpy(w, g->h_poses.data(), (size_t)24 * nV);
     if (cached_walk) {
       thread_local std::vector<int32_t> queue;
@@ -882,18 +881,8 @@ void cond_guesses(CondBatch& B, Dst&& dst) {
       initial_guess_host(nV, w, fx.data(), nA, g->ef.data(), g->et.data(), g->h_meas.data());
     }
   });
-  B.t_guess = wall_s() - tg0;
-}
-
-// The host's part of the batch, written straight into the staging block: every job's initial guess, column mask, query lists
-// and descriptor.
-void cond_fill_stage(CondBatch& B) {
-  const cgmr_graph* g = B.g;
-  const Symbolic& S = B.ctx->sym;
-  const int nV = B.nV, nA = B.nA, nf = B.nf, maxq = B.maxq;
-  char* h = B.hstage;
-  cond_guesses(B, [&](int i) { return (double*)(h + B.S.s_work + (size_t)24 * nV * i); });
   const double tm0 = wall_s();
+  B.t_guess = tm0 - tg0;
   // the column masks: a vertex without an own edge is out of every job's system (the received edges are switched off);
   // the jobs differ in their gauge only
   std::vector<uint8_t> live(nV, 0);
@@ -1021,93 +1010,8 @@ int cond_wait(CondBatch& B, std::vector<std::vector<double>>* info_out) {
   return 0;
 }
 
-// CGMR_COND_BATCH=0 (and the formal case of a structure without a free column): every job as its own stream of ~65 launches on
-// its replica of the numeric work space, side by side on the context's aux streams, as before the batch.  Always waited for.
-int cond_streams(CondBatch& B, std::vector<std::vector<double>>* info_out) {
-  cgmr_graph* g = B.g;
-  cgmr_ctx* ctx = B.ctx;
-  hipStream_t st = B.st;
-  const MargLayout& M = B.M;
-  const Symbolic& S = ctx->sym;
-  const int nV = B.nV, nj = B.nj, cap = g->cap, nstreams = std::min(nj, 8);
-  int rc = aux_streams(ctx, nstreams);
-  if (rc) return rc;
-  rc = dev_grow(g, g->d_work, 0, 24 * (size_t)nV * nj);       // (the passes on streams work on uploaded copies of the poses)
-  if (rc) return rc;
-  std::vector<std::vector<double>> works(nj);
-  cond_guesses(B, [&](int i) { works[i].resize(3 * (size_t)nV); return works[i].data(); });
-  std::vector<uint8_t> fixed(nV);
-  std::vector<int32_t> qcol, status(nj, 0);
-  WireEdge* send_edges = reinterpret_cast<WireEdge*>(g->d_send + wire_edges_off(g->n_robots));
-  HIP_TRY(ctx, hipEventRecord(ctx->aux_fork, st));
-  for (int k = 0; k < nstreams; k++) HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux[k], ctx->aux_fork, 0));
-  for (int i = 0; i < nj; i++) {
-    CondJob& J = B.jobs[i];
-    hipStream_t sj = ctx->aux[i % nstreams];
-    GnDevice& D = B.reps[i];
-    char* d = B.d0 + B.per_job * (size_t)i;
-    const int nq = (int)J.q.size();
-    std::fill(fixed.begin(), fixed.end(), 0);
-    fixed[J.gauge] = 1;
-    double* d_work = (double*)(g->d_work.ptr + 24 * (size_t)nV * i);
-    const double tu0 = wall_s();
-    HIP_TRY(ctx, hipMemcpyAsync(d_work, works[i].data(), 24 * (size_t)nV, hipMemcpyHostToDevice, sj));
-    B.t_up += wall_s() - tu0;
-    const double tm0 = wall_s();
-    rc = prepare_pass_on(ctx, D, sj, fixed.data(), B.nE, B.s_ef, B.s_et, B.nA, i, nj);
-    if (rc) return rc;
-    B.t_mask += wall_s() - tm0;
-    qcol.resize(nq);
-    for (int k = 0; k < nq; k++) qcol[k] = ctx->vmask[J.q[k]] ? -1 : S.vperm[J.q[k]];
-    int32_t* d_qc = (int32_t*)(d + M.o_qc);
-    int32_t* d_qv = (int32_t*)(d + M.o_qv);
-    HIP_TRY(ctx, hipMemcpyAsync(d_qc, qcol.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, sj));
-    HIP_TRY(ctx, hipMemcpyAsync(d_qv, J.q.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, sj));
-    const double tp0 = wall_s();
-    GnPassOpts pass;
-    pass.write_l11c = true;
-    gn_pass_on(ctx, D, sj, d_work, B.Ed, pass);
-    const double tp1 = wall_s();
-    B.t_gn += tp1 - tp0;
-    const int m = ((4 * nq + 15) / 16) * 16;
-    launch_marginals(sj, D, nq, d_qc, m, (double*)(d + M.o_Y), (double*)(d + M.o_U), (double*)(d + M.o_part), (double*)(d + M.o_G),
-                     (double*)(d + M.o_cov), M.chunk, M.nchunk, (uint8_t*)(d + M.o_live));
-    double* est64 = B.to_wire ? g->d_est64 + 3 * (size_t)cap * J.peer : (double*)(d + M.o_est);
-    double* info64 = B.to_wire ? g->d_info64 + 6 * (size_t)cap * J.peer : (double*)(d + M.o_info);
-    launch_label(sj, nq, d_qv, J.gauge, d_work, (const double*)(d + M.o_cov), est64, info64, (int*)(d + M.o_fl));
-    if (B.to_wire)
-      launch_wire_write_edges(sj, nq, g->ids[J.gauge], d_qv, (const int32_t*)g->d_vids.ptr, est64, info64,
-                              send_edges + (size_t)cap * J.peer);
-    HIP_TRY(ctx, hipMemcpyAsync(d + M.o_st, D.status, 4, hipMemcpyDeviceToDevice, sj));
-    B.t_marg += wall_s() - tp1;
-  }
-  for (int k = 0; k < nstreams; k++) {
-    HIP_TRY(ctx, hipEventRecord(ctx->aux_done[k], ctx->aux[k]));
-    HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->aux_done[k], 0));
-  }
-  if (info_out) info_out->assign(nj, {});
-  for (int i = 0; i < nj; i++) {
-    char* d = B.d0 + B.per_job * (size_t)i;
-    HIP_TRY(ctx, hipMemcpyAsync(&status[i], d + M.o_st, 4, hipMemcpyDeviceToHost, st));
-    if (info_out && !B.to_wire) {
-      (*info_out)[i].resize(6 * B.jobs[i].q.size());
-      HIP_TRY(ctx, hipMemcpyAsync((*info_out)[i].data(), d + M.o_info, 48 * B.jobs[i].q.size(), hipMemcpyDeviceToHost, st));
-    }
-  }
-  const double t2 = wall_s();
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  HIP_TRY(ctx, hipGetLastError());
-  if (B.trace)
-    fprintf(stderr, "[cond] %d jobs, nV %d nE %d: structure %.0f us, queueing %.0f us (initial guesses %.0f, masks %.0f, pose upload %.0f, GN pass %.0f, marginals + labels %.0f), waiting %.0f us\n", nj, nV,
-            B.nE, 1e6 * B.t_structure, 1e6 * (t2 - B.t0 - B.t_structure), 1e6 * B.t_guess, 1e6 * B.t_mask, 1e6 * B.t_up, 1e6 * B.t_gn, 1e6 * B.t_marg, 1e6 * (wall_s() - t2));
-  for (int i = 0; i < nj; i++)
-    if (status[i] != 0) return gerr(g, CGMR_E_CHOLESKY_BASE, "Cholesky failed while building a condensed graph");
-  return 0;
-}
-
 // CondensedGraphCreator::compute (condensed_graph_creator.cpp:33-66) for a batch of (gauge, vertex set) jobs on the
-// robot's own edges: ONE sequence of launches with a job dimension (a single job is a batch of one); CGMR_COND_BATCH=0: a
-// stream of launches per job.
+// robot's own edges: ONE sequence of launches with a job dimension (a single job is a batch of one).
 // to_wire: the labelled edges go to the peer's slots (double-precision copy + 44-byte wire records in the send
 // buffer); otherwise only the information matrices come back (info_out[i], 6 doubles per edge: gauge search).
 // async_out (nullable): on entry true = queue the batch on the context's side stream and return without waiting (the
@@ -1124,9 +1028,8 @@ int run_cond_jobs(cgmr_graph* g, std::vector<CondJob>& jobs, bool to_wire, std::
   B.t0 = wall_s();
   int rc = cond_setup(B);
   if (rc) return rc;
-  static const bool batch_on = !(getenv("CGMR_COND_BATCH") && atoi(getenv("CGMR_COND_BATCH")) == 0);
-  const bool batched = batch_on && B.nf > 0;
-  go_async = go_async && batched;     // (only the batch runs on the side stream)
+  // (the callers come with own edges only, and analyze() gives every vertex with an edge a column: never without a free one)
+  if (B.nf == 0) return gerr(g, CGMR_E_INVALID, "condensed graphs: the structure has no free column");
   // whatever ran on the side stream before (another graph of this context, this graph's previous batch) used the work spaces
   // this batch is about to fill
   // (work queued on the side stream behind the fork is marked -- side_busy, side_tail -- even when this function leaves on an error:
@@ -1149,7 +1052,6 @@ int run_cond_jobs(cgmr_graph* g, std::vector<CondJob>& jobs, bool to_wire, std::
     rc = wait_consumers(g, B.st);
     if (rc) return rc;
   }
-  if (!batched) return cond_streams(B, info_out);
   rc = cond_stage_block(B, go_async);
   if (rc) return rc;
   cond_fill_stage(B);

@@ -164,21 +164,19 @@ print('rounds ok')
 COND_STREAMS_GOLDEN = os.path.join(ROOT, "tests", "golden", "cond_streams_r4x6.npz")   # (tools/make_cond_streams_golden.py writes it)
 
 
-def test_condensed_graphs_as_one_batch_equal_the_passes_on_streams(tmp_path):
-    """The condensed graphs of a round run as ONE batch of launches with a job dimension (mrslam_api.cpp run_cond_jobs); with
-    CGMR_COND_BATCH=0 every pass gets its stream of launches as in round 2.  Four robots x 6 rounds each way (the switch is
-    read once per process: two children): same graphs built, same requested vertices, condensed edges and poses equal to
-    rounding (the batch splits the backward solve's chained launch at another level: other summation order in the border
-    reductions), the float32 wire records equal to a float32 ulp."""
-    res = {}
-    for mode in ("1", "0"):
-        path = str(tmp_path / ("batch%s.npz" % mode))
-        env = dict(os.environ, CGMR_COND_BATCH=mode, PYTHONPATH=ROOT)
-        r = subprocess.run([sys.executable, "-c", _BATCH_CHILD, path], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0 and "rounds ok" in r.stdout, r.stderr[-2000:]
-        res[mode] = dict(np.load(path))
-    a, b = res["1"], res["0"]
-    assert str(a.pop("world_sha256")) == str(b.pop("world_sha256"))     # (both children made the same world)
+def test_condensed_graphs_as_one_batch_equal_the_recorded_passes_on_streams(tmp_path):
+    """The condensed graphs of a round run as ONE batch of launches with a job dimension (mrslam_api.cpp run_cond_jobs).  Until
+    they were retired every pass could also get its own stream of launches, as in round 2; what those passes computed for four
+    robots x 6 rounds is on record (COND_STREAMS_GOLDEN, written from the last library that had them).  The batch, in a child process as the record was made: same world, same graphs built, same requested vertices,
+    condensed edges and poses equal to rounding (the batch splits the backward solve's chained launch at another level: other
+    summation order in the border reductions), the float32 wire records equal to a float32 ulp."""
+    assert os.path.isfile(COND_STREAMS_GOLDEN), COND_STREAMS_GOLDEN + " is missing"
+    path = str(tmp_path / "batch.npz")
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, "-c", _BATCH_CHILD, path], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "rounds ok" in r.stdout, r.stderr[-2000:]
+    a, b = dict(np.load(path)), dict(np.load(COND_STREAMS_GOLDEN))
+    assert str(a.pop("world_sha256")) == str(b.pop("world_sha256"))     # (the child made the world of the record)
     assert sorted(a) == sorted(b) and np.array_equal(a["built"], b["built"]) and a["built"].sum() > 10
     n_edges = 0
     for k in a:

@@ -3,12 +3,13 @@
 
     CGMR_LIB=/abs/path/to/parent/libcgmr.so python tools/make_cond_streams_golden.py [--out tests/golden/cond_streams_r4x6.npz]
 
-The passes on streams (every condensed graph as its own stream of launches, CGMR_COND_BATCH=0) are due to be retired; only a
-library that still has the switch can make this record, so CGMR_LIB must name one (when the path goes: a build of the commit
-before).  The run is the child process of tests/test_multirobot_gpu.py's
-test_condensed_graphs_as_one_batch_equal_the_passes_on_streams, script and all, with the switch set: 4 robots, 6 rounds of 150
-vertices on one context.  The fixture holds data only: every robot's wire message, poses and condensed graphs, the graphs
-built per round, and a SHA-256 of the world's input arrays.
+The passes on streams (every condensed graph as its own stream of launches, CGMR_COND_BATCH=0) are retired; this tool made the
+committed record from the last library that had them and stays as its provenance.  Only a library that still has the switch
+can make the record again, so CGMR_LIB must name one (a build of the commit before the retirement); any other is refused.  The
+run is the child process of tests/test_multirobot_gpu.py's
+test_condensed_graphs_as_one_batch_equal_the_recorded_passes_on_streams, script and all, with the switch set: 4 robots, 6 rounds
+of 150 vertices on one context.  The fixture holds data only: every robot's wire message, poses and condensed graphs, the
+graphs built per round, and a SHA-256 of the world's input arrays.
 """
 import argparse
 import os

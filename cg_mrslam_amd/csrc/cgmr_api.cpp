@@ -126,8 +126,7 @@ struct BlobLayout {
 
 // AnalyzeHooks::blocks_ready of a context's analysis: what the assembly lists depend on goes to the device as soon as it is
 // final (vperm, the edge list, the off-diagonal blocks' rows / columns / column starts: one copy from a pinned block of its own)
-// and the device builds the lists (gn_structure.hip) underneath the rest of the host's analysis.  CGMR_ASM_DEVICE=0: the host
-// builds them as before and they travel with the structure blob.
+// and the device builds the lists (gn_structure.hip) underneath the rest of the host's analysis.
 int gn_upload_early(cgmr_ctx* ctx, const Symbolic& S, const int32_t* ef, const int32_t* et, const int32_t* offbase) {
   const size_t nV = (size_t)S.nV, nE = (size_t)S.nE, nb = (size_t)S.nb, nf = (size_t)S.nf, nkeys = nf + nb;
   BlobLayout B;
@@ -168,6 +167,7 @@ int gn_upload_early(cgmr_ctx* ctx, const Symbolic& S, const int32_t* ef, const i
   V.vperm = (int32_t*)(d + o_vperm); V.ef = (int32_t*)(d + o_ef); V.et = (int32_t*)(d + o_et);
   V.off_row = (int32_t*)(d + o_orow); V.off_col = (int32_t*)(d + o_ocol); V.offbase = (int32_t*)(d + o_obase);
   V.asm_ptr = (int32_t*)(d + o_asmp); V.asm_src = (int32_t*)(d + o_asms);
+  V.fresh = true;
   AsmBuild A;
   A.nE = S.nE; A.nf = S.nf; A.nb = S.nb;
   A.vperm = V.vperm; A.ef = V.ef; A.et = V.et; A.off_row = V.off_row; A.offbase = (const int32_t*)(d + o_obase);
@@ -178,8 +178,14 @@ int gn_upload_early(cgmr_ctx* ctx, const Symbolic& S, const int32_t* ef, const i
   return 0;
 }
 
-// Lay out and upload the structure arrays; point GnDevice into the arena.
-int gn_upload(cgmr_ctx* ctx, const Symbolic& S, const int32_t* ef, const int32_t* et, int iters) {
+// Lay out and upload the structure arrays the host made; point GnDevice into the arena.  vperm, the edge list, the off-diagonal
+// blocks and the assembly lists are on the device already (gn_upload_early, which S's analysis called: ctx->st_view); the row
+// maps, the destinations and the work records are made there from what goes up here (k_build_maps).
+int gn_upload(cgmr_ctx* ctx, const Symbolic& S, int iters) {
+  cgmr_ctx::StView& V = ctx->st_view;
+  if (S.nf == 0) V = cgmr_ctx::StView();                    // (no column: the analysis ends before its hook, and no pass reads these)
+  else if (!V.fresh) return set_err(ctx, CGMR_E_INVALID, "structure upload of an analysis without its device pass (AnalyzeHooks::blocks_ready)");
+  V.fresh = false;
   // the factor kernels keep row positions (own columns + border rows) in 16-bit LDS maps
   if (3 * (int64_t)S.max_ns + kFrontW > 32767)
     return set_err(ctx, CGMR_E_INVALID, "a front has %d border poses; at most %d are supported", S.max_ns, (32767 - kFrontW) / 3);
@@ -193,8 +199,7 @@ int gn_upload(cgmr_ctx* ctx, const Symbolic& S, const int32_t* ef, const int32_t
   const std::vector<int32_t>& LF = S.gn_level_fronts;
   static const int mid_chunk = getenv("CGMR_CHUNK") ? std::min(kChunkRows, std::max(16, atoi(getenv("CGMR_CHUNK")))) : kMidChunkRows;
   static const int leaf_chunk = getenv("CGMR_LEAF_CHUNK") ? atoi(getenv("CGMR_LEAF_CHUNK")) : kLeafChunkRows;
-  // sizing pass: work records (one per front and row chunk) and update tiles per level fix the blob layout; the records
-  // themselves are written straight into the pinned staging blob further down, by several host threads
+  // sizing pass: work records (one per front and row chunk) and update tiles per level fix the blob layout
   D.h_tile_ptr.assign(D.nlevels + 1, 0);
   D.h_work_ptr.assign(D.nlevels + 1, 0);
   D.h_level_chrows.assign(D.nlevels, 1);
@@ -208,7 +213,9 @@ int gn_upload(cgmr_ctx* ctx, const Symbolic& S, const int32_t* ef, const int32_t
     if (F.ns > 0) sched[std::min(F.sched_t, D.nlevels - 1)].push_back(LF[q]);
   }
   for (auto& v : sched) std::sort(v.begin(), v.end());
-  std::vector<int32_t> rec0_of(S.fronts.size(), -1);        // a front's first work record: the update tiles address the front through it
+  // a front's first work record (the update tiles address the front through it) and its record count (0: top block), for k_build_maps
+  std::vector<int32_t> rec0_of(2 * S.fronts.size(), 0);
+  for (size_t f = 0; f < S.fronts.size(); f++) rec0_of[2 * f] = -1;
   for (int l = 0; l < D.nlevels; l++) {
     for (int q = S.gn_level_ptr[l]; q < S.gn_level_ptr[l + 1]; q++)
       if (S.fronts[LF[q]].nchild > 0) D.h_level_leaf[l] = 0;
@@ -223,8 +230,10 @@ int gn_upload(cgmr_ctx* ctx, const Symbolic& S, const int32_t* ef, const int32_t
     int nwork = 0;
     for (int q = S.gn_level_ptr[l]; q < S.gn_level_ptr[l + 1]; q++) {
       const int r = 3 * S.fronts[LF[q]].ns;
-      rec0_of[LF[q]] = D.h_work_ptr[l] + nwork;
-      nwork += std::max(1, (r + chunk_rows - 1) / chunk_rows);
+      const int nchunk = std::max(1, (r + chunk_rows - 1) / chunk_rows);
+      rec0_of[2 * LF[q]] = D.h_work_ptr[l] + nwork;
+      rec0_of[2 * LF[q] + 1] = nchunk;
+      nwork += nchunk;
       D.h_level_chrows[l] = std::max(D.h_level_chrows[l], std::min(r, chunk_rows) + 1);
     }
     int xload[8] = {0, 0, 0, 0, 0, 0, 0, 0};                     // update tiles per XCD (see the tile list below)
@@ -242,24 +251,9 @@ int gn_upload(cgmr_ctx* ctx, const Symbolic& S, const int32_t* ef, const int32_t
   size_t o_fronts_lv = B.add<FrontDesc>(S.fronts.size());   // the same descriptors in level order: the solves index them by workgroup
   size_t o_rows = B.add<int32_t>(S.rows.size());
   size_t o_children = B.add<int32_t>(S.children.size());
-  const bool dev_maps = S.maps_on_device;                   // rel / inv / blk_dst / b_dst are made on the device (below): no staging, no upload
-  size_t o_rel = B.add<int32_t>(dev_maps ? 0 : S.rel.size());
-  size_t o_inv = B.add<int32_t>(dev_maps ? 0 : S.inv.size());
-  size_t o_bdst = B.add<int32_t>(dev_maps ? 0 : S.blk_dst.size());
-  size_t o_rdst = B.add<int32_t>(dev_maps ? 0 : S.b_dst.size());
   size_t o_lf = B.add<int32_t>(S.level_fronts.size());
   size_t o_tiles = B.add<int32_t>(3 * n_tiles);
-  size_t o_work = B.add<WorkRec>(dev_maps ? 0 : n_work);     // (device-made with the maps: k_build_maps)
-  size_t o_rec0 = B.add<int32_t>(dev_maps ? 2 * S.fronts.size() : 0);
-  // (S.asm_on_device: these seven are on the device already, gn_upload_early)
-  const bool early = S.asm_on_device;
-  size_t o_asmp = B.add<int32_t>(early ? 0 : S.asm_ptr.size());
-  size_t o_asms = B.add<int32_t>(early ? 0 : S.asm_src.size());
-  size_t o_vperm = B.add<int32_t>(early ? 0 : S.vperm.size());
-  size_t o_ef = B.add<int32_t>(early ? 0 : S.nE);
-  size_t o_et = B.add<int32_t>(early ? 0 : S.nE);
-  size_t o_orow = B.add<int32_t>(early ? 0 : S.off_row.size());
-  size_t o_ocol = B.add<int32_t>(early ? 0 : S.off_col.size());
+  size_t o_rec0 = B.add<int32_t>(rec0_of.size());
   size_t o_tf = B.add<int32_t>(S.top_fronts.size()), o_tc = B.add<int32_t>(S.top_children.size()), o_tb = B.add<int32_t>(S.top_blocks.size());
   size_t blob_bytes = (B.off + 255) & ~size_t(255);
   // numeric work space
@@ -278,11 +272,10 @@ int gn_upload(cgmr_ctx* ctx, const Symbolic& S, const int32_t* ef, const int32_t
   size_t o_status = N.add<int>(4);
   size_t o_ready = N.add<int>(S.fronts.size() + 4);
   size_t o_cmask = N.add<uint8_t>((size_t)S.nf + 16);
-  if (dev_maps) {
-    o_rel = N.add<int32_t>((size_t)S.n_rel + 4); o_inv = N.add<int32_t>((size_t)S.n_inv + 4);
-    o_bdst = N.add<int32_t>((size_t)S.nf + S.nb + 4); o_rdst = N.add<int32_t>((size_t)S.nf + 4);
-    o_work = N.add<WorkRec>(n_work + 1);
-  }
+  // (device-made: k_build_maps)
+  size_t o_rel = N.add<int32_t>((size_t)S.n_rel + 4), o_inv = N.add<int32_t>((size_t)S.n_inv + 4);
+  size_t o_bdst = N.add<int32_t>((size_t)S.nf + S.nb + 4), o_rdst = N.add<int32_t>((size_t)S.nf + 4);
+  size_t o_work = N.add<WorkRec>(n_work + 1);
   size_t total = N.off + 256;
   int rc = arena_reserve(ctx, ctx->gn_arena, total);
   if (rc) return rc;
@@ -293,43 +286,12 @@ int gn_upload(cgmr_ctx* ctx, const Symbolic& S, const int32_t* ef, const int32_t
   // staging: independent pieces on the analysis' helper threads
   host_run_tasks(6, [&](int task) {
     switch (task) {
-      case 0: {                                                  // work records + update tiles, level by level
-        WorkRec* work = dev_maps ? nullptr : reinterpret_cast<WorkRec*>(h + o_work);
+      case 0: {                                                  // update tiles, level by level
         int32_t* tiles = reinterpret_cast<int32_t*>(h + o_tiles);
-        if (dev_maps) {                                          // the device writes the records: where each front's begin, how many
-          int32_t* r0 = reinterpret_cast<int32_t*>(h + o_rec0);
-          for (size_t f = 0; f < S.fronts.size(); f++) { r0[2 * f] = -1; r0[2 * f + 1] = 0; }
-        }
         // Update tiles of one front sit 8 apart in the launch: workgroup b runs on XCD b % 8 (observed; speed only), so
         // the tiles that share the front's L21 rows share one L2 instead of fetching them into up to eight.  A front goes
         // to the XCD with the fewest tiles so far; the shorter queues are padded with empty entries (rec = -1).
         for (int l = 0; l < D.nlevels; l++) {
-          const int chunk_rows = D.h_level_chunk[l];
-          int w = D.h_work_ptr[l];
-          for (int q = S.gn_level_ptr[l]; q < S.gn_level_ptr[l + 1]; q++) {
-            const int f = LF[q];
-            const int r = 3 * S.fronts[f].ns;
-            const int nchunk = std::max(1, (r + chunk_rows - 1) / chunk_rows);
-            if (dev_maps) {
-              int32_t* r0 = reinterpret_cast<int32_t*>(h + o_rec0);
-              r0[2 * f] = w; r0[2 * f + 1] = nchunk;
-              w += nchunk;
-              continue;
-            }
-            for (int c = 0; c < nchunk; c++) {
-              WorkRec& wr = work[w++];
-              memset(&wr, 0, sizeof wr);
-              wr.F = S.fronts[f];
-              wr.front = f;
-              wr.chunk = c;
-              for (int k = 0; k < std::min<int>(wr.F.nchild, kWorkChildren); k++) {
-                const FrontDesc& G = S.fronts[S.children[wr.F.child_off + k]];
-                WorkChild& wc = wr.ch[k];
-                wc.U_off = G.U_off; wc.ns = G.ns; wc.na = G.na;
-                wc.rel_off = G.rel_off; wc.inv_off = G.inv_off; wc.rows_off = G.rows_off;
-              }
-            }
-          }
           int32_t* tl = tiles + 3 * (size_t)D.h_tile_ptr[l];
           const int slots = D.h_tile_ptr[l + 1] - D.h_tile_ptr[l];
           for (int k = 0; k < slots; k++) { tl[3 * k] = -1; tl[3 * k + 1] = 0; tl[3 * k + 2] = 0; }
@@ -340,48 +302,35 @@ int gn_upload(cgmr_ctx* ctx, const Symbolic& S, const int32_t* ef, const int32_t
             for (int ti = 0; ti < T; ti++)
               for (int tj = 0; tj <= ti; tj++) {
                 int32_t* e = tl + 3 * (size_t)(8 * xload[x]++ + x);
-                e[0] = rec0_of[f]; e[1] = ti; e[2] = tj;
+                e[0] = rec0_of[2 * f]; e[1] = ti; e[2] = tj;
               }
           }
         }
         break;
       }
       case 1:
-        if (dev_maps) break;
-        put(o_bdst, S.blk_dst.data(), S.blk_dst.size() * 4);
-        put(o_rdst, S.b_dst.data(), S.b_dst.size() * 4);
+        put(o_rec0, rec0_of.data(), rec0_of.size() * 4);
+        put(o_children, S.children.data(), S.children.size() * 4);
         break;
-      case 2: {
+      case 2:
         put(o_fronts, S.fronts.data(), S.fronts.size() * sizeof(FrontDesc));
+        break;
+      case 3: {
         FrontDesc* lv = reinterpret_cast<FrontDesc*>(h + o_fronts_lv);       // Gauss-Newton level order (the backward solve's index)
         for (size_t q = 0; q < S.fronts.size(); q++) {
           if (q < LF.size()) lv[q] = S.fronts[LF[q]];
           else memset(&lv[q], 0, sizeof(FrontDesc));             // fronts of the top block: not addressed through this table
         }
-        put(o_children, S.children.data(), S.children.size() * 4);
+        break;
+      }
+      case 4:
         put(o_lf, S.level_fronts.data(), S.level_fronts.size() * 4);
         put(o_tf, S.top_fronts.data(), S.top_fronts.size() * 4);
         put(o_tc, S.top_children.data(), S.top_children.size() * 4);
         put(o_tb, S.top_blocks.data(), S.top_blocks.size() * 4);
         break;
-      }
-      case 3:
-        put(o_rows, S.rows.data(), S.rows.size() * 4);
-        if (!dev_maps) put(o_rel, S.rel.data(), S.rel.size() * 4);
-        break;
-      case 4:
-        if (!dev_maps) put(o_inv, S.inv.data(), S.inv.size() * 4);
-        if (early) break;
-        put(o_asmp, S.asm_ptr.data(), S.asm_ptr.size() * 4);
-        put(o_asms, S.asm_src.data(), S.asm_src.size() * 4);
-        break;
       default:
-        if (early) break;
-        put(o_vperm, S.vperm.data(), S.vperm.size() * 4);
-        put(o_ef, ef, (size_t)S.nE * 4);
-        put(o_et, et, (size_t)S.nE * 4);
-        put(o_orow, S.off_row.data(), S.off_row.size() * 4);
-        put(o_ocol, S.off_col.data(), S.off_col.size() * 4);
+        put(o_rows, S.rows.data(), S.rows.size() * 4);
         break;
     }
   });
@@ -401,17 +350,7 @@ int gn_upload(cgmr_ctx* ctx, const Symbolic& S, const int32_t* ef, const int32_t
   D.level_fronts = (int32_t*)(d + o_lf);
   D.tiles = (int32_t*)(d + o_tiles);
   D.work = (WorkRec*)(d + o_work);
-  D.asm_ptr = (int32_t*)(d + o_asmp);
-  D.asm_src = (int32_t*)(d + o_asms);
-  D.vperm = (int32_t*)(d + o_vperm);
-  D.ef = (int32_t*)(d + o_ef);
-  D.et = (int32_t*)(d + o_et);
-  D.off_row = (int32_t*)(d + o_orow);
-  D.off_col = (int32_t*)(d + o_ocol);
-  if (early) {
-    const cgmr_ctx::StView& V = ctx->st_view;
-    D.asm_ptr = V.asm_ptr; D.asm_src = V.asm_src; D.vperm = V.vperm; D.ef = V.ef; D.et = V.et; D.off_row = V.off_row; D.off_col = V.off_col;
-  }
+  D.asm_ptr = V.asm_ptr; D.asm_src = V.asm_src; D.vperm = V.vperm; D.ef = V.ef; D.et = V.et; D.off_row = V.off_row; D.off_col = V.off_col;
   D.cmask = (uint8_t*)(d + o_cmask);
   D.top_fronts = (int32_t*)(d + o_tf); D.top_children = (int32_t*)(d + o_tc); D.top_blocks = (int32_t*)(d + o_tb);
   D.top_nfronts = (int)S.top_fronts.size(); D.top_c0 = S.top_c0; D.top_ncols = 3 * S.top_nposes;
@@ -424,10 +363,8 @@ int gn_upload(cgmr_ctx* ctx, const Symbolic& S, const int32_t* ef, const int32_t
   D.uvec = (double*)(d + o_u);
   D.Lbuf = (double*)(d + o_L);
   D.Ubuf = (double*)(d + o_U);
-  if (dev_maps) {
-    launch_build_maps(ctx->stream, D, ctx->st_view.offbase, (const int32_t*)(d + o_rec0));
-    HIP_TRY(ctx, hipGetLastError());
-  }
+  launch_build_maps(ctx->stream, D, V.offbase, (const int32_t*)(d + o_rec0));
+  HIP_TRY(ctx, hipGetLastError());
   D.Pan = (double*)(d + o_pan);
   D.pan_clean = false;
   D.pan_doubles = S.pan_doubles;
@@ -506,20 +443,16 @@ int prepare_structure(cgmr_ctx* ctx, int nV, int nE, const int32_t* ef, const in
   // the tree edge by edge (an edge to a hub -- the gauge of a received star -- always passes).
   const bool have_prev = ctx->sym_cache_on && ctx->sym_valid;
   ctx->sym_valid = false;
-  static const bool asm_device = !(getenv("CGMR_ASM_DEVICE") && atoi(getenv("CGMR_ASM_DEVICE")) == 0);
   AnalyzeHooks hooks;
   int hook_rc = 0;
-  static const bool maps_device = !(getenv("CGMR_MAPS_DEVICE") && atoi(getenv("CGMR_MAPS_DEVICE")) == 0);
-  hooks.maps_on_device = asm_device && maps_device;
-  if (asm_device)
-    hooks.blocks_ready = [&](const Symbolic& S, const int32_t* offbase) { hook_rc = gn_upload_early(ctx, S, ef, et, offbase); return hook_rc ? -100 : 0; };
+  hooks.blocks_ready = [&](const Symbolic& S, const int32_t* offbase) { hook_rc = gn_upload_early(ctx, S, ef, et, offbase); return hook_rc ? -100 : 0; };
   int rc = analyze_next(ctx->sym, have_prev, ctx->sym_nV, ctx->sym_ef, ctx->sym_et, nV, nE, ef, et, hub_vertices, n_hub_vertices, &hooks);
   if (rc == -100) return hook_rc;                                   // (the device pass of the analysis failed: its error is set)
   if (rc == 0 && ctx->sym.extended) ctx->sym_extended++; else ctx->sym_misses++;
   if (rc) return set_err(ctx, CGMR_E_INVALID, "graph structure rejected (edge index out of range)");
   const int chi_cap = std::max(iters, 30);
   const double tu0 = wall_s();
-  rc = gn_upload(ctx, ctx->sym, ef, et, chi_cap);
+  rc = gn_upload(ctx, ctx->sym, chi_cap);
   if (rc) return rc;
   ctx->sym.t_upload = wall_s() - tu0;
   if (ctx->sym_cache_on) {
@@ -2084,21 +2017,22 @@ extern "C" int cgmr_debug_symbolic_steps(int n_steps, const int32_t* nV, const i
   return n;
 }
 
-// Tests: the assembly lists (gn_symbolic.h: asm_ptr / asm_src) as the host builds them for an edge list (ctx == nullptr), or
-// as they stand on the device for the graph the context analysed last (ef / et ignored).  Returns nf + nb (the number of
+// Tests: the assembly lists (gn_symbolic.h: asm_ptr / asm_src) as the host's reference builds them for an edge list (ctx ==
+// nullptr: structure_reference), or as they stand on the device for the graph the context analysed last (ef / et ignored).  Returns nf + nb (the number of
 // keys; -1: error), the number of list entries in *n_src_out.
 extern "C" int cgmr_debug_asm_lists(cgmr_ctx* ctx, int nV, int nE, const int32_t* ef, const int32_t* et, int cap_ptr, int32_t* ptr_out,
                                     int cap_src, int32_t* src_out, int32_t* n_src_out) {
   if (!ptr_out || !src_out || !n_src_out) return -1;
   if (!ctx) {
     Symbolic S;
-    if (analyze(nV, nullptr, nE, ef, et, S)) return -1;
+    StructureRef R;
+    if (analyze(nV, nullptr, nE, ef, et, S) || structure_reference(S, nE, ef, et, R)) return -1;
     const int nk = S.nf + S.nb;
-    if (nk + 1 > cap_ptr || (int)S.asm_src.size() > cap_src) return -1;
-    if (S.asm_ptr.empty()) { *n_src_out = 0; return nk; }
-    memcpy(ptr_out, S.asm_ptr.data(), 4 * (size_t)(nk + 1));
-    memcpy(src_out, S.asm_src.data(), 4 * S.asm_src.size());
-    *n_src_out = (int)S.asm_src.size();
+    if (nk + 1 > cap_ptr || (int)R.asm_src.size() > cap_src) return -1;
+    if (R.asm_ptr.empty()) { *n_src_out = 0; return nk; }
+    memcpy(ptr_out, R.asm_ptr.data(), 4 * (size_t)(nk + 1));
+    memcpy(src_out, R.asm_src.data(), 4 * R.asm_src.size());
+    *n_src_out = (int)R.asm_src.size();
     return nk;
   }
   const GnDevice& D = ctx->gn;
@@ -2113,23 +2047,23 @@ extern "C" int cgmr_debug_asm_lists(cgmr_ctx* ctx, int nV, int nE, const int32_t
   return nk;
 }
 
-// Tests: rel | inv | blk_dst | b_dst (gn_symbolic.h) one behind the other, as the host builds them for an edge list (ctx ==
-// nullptr) or as they stand on the device for the graph the context analysed last.  Returns the number of ints, -1: error.
+// Tests: rel | inv | blk_dst | b_dst (gn_symbolic.h) one behind the other, as the host's reference builds them for an edge list
+// (ctx == nullptr: structure_reference) or as they stand on the device for the graph the context analysed last.  Returns the number of ints, -1: error.
 extern "C" int cgmr_debug_maps(cgmr_ctx* ctx, int nV, int nE, const int32_t* ef, const int32_t* et, int cap, int32_t* out) {
   if (!out) return -1;
   if (!ctx) {
     Symbolic S;
-    if (analyze(nV, nullptr, nE, ef, et, S)) return -1;
-    const size_t n = S.rel.size() + S.inv.size() + S.blk_dst.size() + S.b_dst.size();
+    StructureRef R;
+    if (analyze(nV, nullptr, nE, ef, et, S) || structure_reference(S, nE, ef, et, R)) return -1;
+    const size_t n = R.rel.size() + R.inv.size() + R.blk_dst.size() + R.b_dst.size();
     if (n > (size_t)cap) return -1;
     int32_t* o = out;
-    for (const std::vector<int32_t>* v : {&S.rel, &S.inv, &S.blk_dst, &S.b_dst}) { memcpy(o, v->data(), 4 * v->size()); o += v->size(); }
+    for (const std::vector<int32_t>* v : {&R.rel, &R.inv, &R.blk_dst, &R.b_dst}) { memcpy(o, v->data(), 4 * v->size()); o += v->size(); }
     return (int)n;
   }
   const GnDevice& D = ctx->gn;
   const Symbolic& S = ctx->sym;
-  const size_t sizes[4] = {(size_t)(S.maps_on_device ? S.n_rel : (int64_t)S.rel.size()), (size_t)(S.maps_on_device ? S.n_inv : (int64_t)S.inv.size()),
-                           (size_t)S.nf + S.nb, (size_t)S.nf};
+  const size_t sizes[4] = {(size_t)S.n_rel, (size_t)S.n_inv, (size_t)S.nf + S.nb, (size_t)S.nf};
   const int32_t* srcs[4] = {D.rel, D.inv, D.blk_dst, D.b_dst};
   if (sizes[0] + sizes[1] + sizes[2] + sizes[3] > (size_t)cap) return -1;
   if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return -1;
@@ -2139,4 +2073,43 @@ extern "C" int cgmr_debug_maps(cgmr_ctx* ctx, int nV, int nE, const int32_t* ef,
     o += sizes[k];
   }
   return (int)(o - out);
+}
+
+// Tests: the factor kernel's work records (gn_symbolic.h: WorkRec) of the graph the context analysed last, as they stand on the
+// device (dev_out) and as a host loop over the context's analysis and chunk lengths writes them (ref_out); cap records each.
+// Returns the number of records (more than cap: nothing was written), -1: error.
+extern "C" int cgmr_debug_work_records(cgmr_ctx* ctx, int cap, void* dev_out, void* ref_out) {
+  if (!ctx) return -1;
+  const GnDevice& D = ctx->gn;
+  const Symbolic& S = ctx->sym;
+  const int n_work = D.h_work_ptr.empty() ? 0 : D.h_work_ptr.back();
+  if (n_work > cap || n_work == 0) return n_work;
+  if (!dev_out || !ref_out) return -1;
+  if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return -1;
+  if (n_work && hipMemcpy(dev_out, D.work, sizeof(WorkRec) * (size_t)n_work, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  WorkRec* work = static_cast<WorkRec*>(ref_out);
+  for (int l = 0; l < D.nlevels; l++) {
+    const int chunk_rows = D.h_level_chunk[l];
+    int w = D.h_work_ptr[l];
+    for (int q = S.gn_level_ptr[l]; q < S.gn_level_ptr[l + 1]; q++) {
+      const int f = S.gn_level_fronts[q];
+      const int r = 3 * S.fronts[f].ns;
+      const int nchunk = std::max(1, (r + chunk_rows - 1) / chunk_rows);
+      for (int c = 0; c < nchunk; c++) {
+        WorkRec& wr = work[w++];
+        memset(&wr, 0, sizeof wr);
+        wr.F = S.fronts[f];
+        wr.front = f;
+        wr.chunk = c;
+        for (int k = 0; k < std::min<int>(wr.F.nchild, kWorkChildren); k++) {
+          const FrontDesc& G = S.fronts[S.children[wr.F.child_off + k]];
+          WorkChild& wc = wr.ch[k];
+          wc.U_off = G.U_off; wc.ns = G.ns; wc.na = G.na;
+          wc.rel_off = G.rel_off; wc.inv_off = G.inv_off; wc.rows_off = G.rows_off;
+        }
+      }
+    }
+    if (w != D.h_work_ptr[l + 1]) return -1;
+  }
+  return n_work;
 }

@@ -48,7 +48,7 @@ struct cgmr_ctx {
   char* pinned_st = nullptr;
   size_t pinned_st_cap = 0;
   hipEvent_t ev_st_copied = nullptr;   // behind the last copy out of pinned_st
-  struct StView { int32_t *vperm = nullptr, *ef = nullptr, *et = nullptr, *off_row = nullptr, *off_col = nullptr, *offbase = nullptr, *asm_ptr = nullptr, *asm_src = nullptr; } st_view;
+  struct StView { int32_t *vperm = nullptr, *ef = nullptr, *et = nullptr, *off_row = nullptr, *off_col = nullptr, *offbase = nullptr, *asm_ptr = nullptr, *asm_src = nullptr; bool fresh = false; } st_view;   // fresh: made by the analysis whose structure goes up next
   // Side stream: batches of condensed-graph passes queued without waiting for them (cgmr_graph_compute_condensed_async) run
   // beside whatever the context's stream does next -- the next round's structure analysis on the host, its solve on the
   // device.  They work in replicas of the numeric buffers and READ the uploaded structure: a new structure upload, a

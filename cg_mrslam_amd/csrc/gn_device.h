@@ -69,7 +69,8 @@ struct GnEdges {
 };
 // gn_structure.hip: the assembly lists (asm_ptr: nf + nb + 1, asm_src: one entry per (edge, key)) from the permutation, the
 // edge list and the off-diagonal blocks (offbase: nf + 1 column starts into off_row); work space: ekey nE, cnt nf + nb + 3,
-// longlist 3 nE / 16 + 1, tmp 3 nE (all int32, device memory)
+// longlist 3 nE / 16 + 1, tmp 3 nE (all int32, device memory).  The tests hold the result of this and of launch_build_maps to
+// the host's serial reference, entry for entry (gn_symbolic.h: structure_reference)
 struct AsmBuild {
   int nE = 0, nf = 0, nb = 0;
   const int32_t *vperm = nullptr, *ef = nullptr, *et = nullptr, *off_row = nullptr, *offbase = nullptr;

@@ -5,7 +5,8 @@
 // What it replaces: g2o's BlockSolver::buildStructure allocates the block pattern of Hpp and hands every edge the address of
 // its Hessian blocks ([g2o-recalled]; redone on every optimize() call, reference call sites
 // src/slam/graph_slam.cpp:564-565, src/slam/graph_manipulator.cpp:117-123).  Until round 6 the host did the same here
-// (gn_symbolic.cpp: "assembly lists", 0.25-0.35 ms of eight threads and 0.6 MB of upload per cold optimize()).  The lists
+// (0.25-0.35 ms of eight threads and 0.6 MB of upload per cold optimize(); what is left of it is the serial reference the
+// tests hold these kernels to, gn_symbolic.cpp: structure_reference).  The lists
 // depend on the permutation and on the off-diagonal blocks only, which are final long before the analysis is (borders,
 // amalgamation, maps come after them): the device builds the lists underneath the rest of the host's analysis.
 //
@@ -29,7 +30,7 @@ constexpr int kLongList = 16;
 
 // the three keys of edge k: a = diagonal block of `from`, b = of `to`, e = nf + index of the lower off-diagonal block
 // (max(a, b), min(a, b)) (-1: an end point has no column); code of e: 2 = Hij as it is (row a, column b), 3 = transposed.
-// A self edge has no key at all: its term (Ji + Jj)^T Omega (Ji + Jj) is exactly zero -- gn_symbolic.cpp, "assembly lists"
+// A self edge has no key at all: its term (Ji + Jj)^T Omega (Ji + Jj) is exactly zero -- gn_symbolic.cpp, structure_reference
 __device__ __forceinline__ void edge_keys(int k, int nf, const int32_t* __restrict__ vperm, const int32_t* __restrict__ ef,
                                           const int32_t* __restrict__ et, int& a, int& b) {
   a = vperm[ef[k]];
@@ -228,7 +229,7 @@ __global__ __launch_bounds__(256) void k_asm_sort_long(const int32_t* __restrict
 }
 
 // The child -> parent row maps and the H blocks' destinations of one front per workgroup, from the uploaded front table
-// (gn_symbolic.cpp, "maps + A lists" and "where every front's contribution and every H block goes" are the host's version):
+// (gn_symbolic.cpp: structure_reference is the host's serial version, which the tests compare with):
 //   rel[G.rel_off + q]  position of child G's border row q in this front: < nc an own column, nc + p the p-th border row
 //   inv[G.inv_off + p]  the child's row that lands on this front's border row p, or -1
 //   blk_dst[blk]        offset in Pan of element (0, 0) of H block blk (diagonal blocks 0 .. nf - 1, then the off-diagonal
@@ -271,7 +272,7 @@ __global__ __launch_bounds__(256) void k_build_maps(int nf, const FrontDesc* __r
   bool in_top = false;
   for (int k = 0; k < n_top; k++) in_top = in_top || top_fronts[k] == f;
   const int ob0 = offbase[F.c0];
-  for (int t = threadIdx.x; t < F.a_cnt; t += 256) {    // the front's A blocks in alist order: per column the diagonal block, then its blocks below
+  for (int t = threadIdx.x; t < F.a_cnt; t += 256) {    // the front's A blocks (slots a_off ..): per column the diagonal block, then its blocks below
     int c = F.c0;
     while (c + 1 < cend && (c + 1 - F.c0) + (offbase[c + 1] - ob0) <= t) c++;
     const int j = t - ((c - F.c0) + (offbase[c] - ob0));  // 0: the diagonal block, j >= 1: the column's (j - 1)-th off-diagonal block

@@ -1325,75 +1325,13 @@ int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32
       for (int p = cp[c]; p < cp[c + 1]; p++) if (ci[p] > c) { S.off_row[k] = ci[p]; S.off_col[k] = c; k++; }
     }
   });
-  auto off_id = [&](int r, int c) {   // r > c: the blocks of column c are listed by ascending row, a handful of them
-    int k = offbase[c];
-    while (S.off_row[k] != r) k++;
-    return k;
-  };
   CK("off-diagonal blocks");
-  // assembly CSR: block -> contributing edge terms
-  // A caller with a device takes over here (round 6): everything the lists depend on is final, the device builds them
-  // underneath the borders / maps below (AnalyzeHooks::blocks_ready; 0.25-0.35 ms of the eight threads otherwise)
+  // A caller with a device takes over the assembly lists here (round 6): everything they depend on is final, the device
+  // builds them underneath the borders / maps below (AnalyzeHooks::blocks_ready)
   if (hooks && hooks->blocks_ready) {
     const int hrc = hooks->blocks_ready(S, offbase.data());
     if (hrc) return hrc;
-    S.asm_on_device = true;
-    S.maps_on_device = hooks->maps_on_device;
     CK("assembly lists: handed to the device");
-  }
-  if (!S.asm_on_device) {
-  // (every thread walks all edges in order and keeps the blocks of its own key range: lists stay in edge order)
-  const int nkeys = nf + S.nb;
-  S.asm_ptr.assign(nkeys + 1, 0);
-  std::vector<int32_t> e_a(nE), e_b(nE), e_off(nE, -1);
-  parallel_for(nE, NT, [&](int lo, int hi) {
-    for (int k = lo; k < hi; k++) {
-      int a = S.vperm[ef[k]], b = S.vperm[et[k]];
-      // self edge: the chain rule's term, (Ji + Jj)^T Omega (Ji + Jj) on the one block -- Ji + Jj is exactly zero (the error
-      // z^-1 (xi^-1 xi) does not depend on xi), so the edge adds to chi2 and to no list (include/cgmr.h, cgmr_gn_optimize)
-      e_a[k] = (a >= 0 && a == b) ? -1 : a;
-      e_b[k] = (b >= 0 && a == b) ? -1 : b;
-      if (a >= 0 && b >= 0 && a != b) e_off[k] = nf + (a > b ? off_id(a, b) : off_id(b, a));
-    }
-  });
-  CK("  asm: edge keys");
-  const int nkt = (nE >= 4096) ? NT : 1;
-  auto key_range = [&](int t, int& klo, int& khi) { klo = (int)((int64_t)nkeys * t / nkt); khi = (int)((int64_t)nkeys * (t + 1) / nkt); };
-  auto run_keyed = [&](auto&& body) {
-    std::vector<HelperPool::Job> jobs(nkt > 1 ? nkt - 1 : 0);
-    for (int t = 1; t < nkt; t++) { jobs[t - 1].fn = [&body, t] { body(t); }; pool().run(jobs[t - 1]); }
-    body(0);
-    for (auto& j : jobs) HelperPool::wait(j);
-  };
-  run_keyed([&](int t) {
-    int klo, khi;
-    key_range(t, klo, khi);
-    for (int k = 0; k < nE; k++) {
-      const int a = e_a[k], b = e_b[k], e = e_off[k];
-      if (a >= klo && a < khi) S.asm_ptr[a + 1]++;
-      if (b >= klo && b < khi) S.asm_ptr[b + 1]++;
-      if (e >= klo && e < khi) S.asm_ptr[e + 1]++;
-    }
-  });
-  CK("  asm: count");
-  for (int q = 0; q < nkeys; q++) S.asm_ptr[q + 1] += S.asm_ptr[q];
-  S.asm_src.resize(S.asm_ptr[nkeys]);
-  CK("  asm: prefix + resize");
-  {
-    std::vector<int32_t> pos(S.asm_ptr.begin(), S.asm_ptr.end() - 1);
-    run_keyed([&](int t) {
-      int klo, khi;
-      key_range(t, klo, khi);
-      for (int k = 0; k < nE; k++) {
-        const int a = e_a[k], b = e_b[k], e = e_off[k];
-        if (a >= klo && a < khi) S.asm_src[pos[a]++] = 4 * k + 0;
-        if (b >= klo && b < khi) S.asm_src[pos[b]++] = 4 * k + 1;
-        // a > b: lower block (row a = i, col b = j) is Hij as is; else (row b = j, col a = i) = Hij^T
-        if (e >= klo && e < khi) S.asm_src[pos[e]++] = 4 * k + (a > b ? 2 : 3);
-      }
-    });
-  }
-  CK("assembly lists");
   }
   // fronts
   int nfr = (int)panel_start.size();
@@ -1592,7 +1530,7 @@ int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32
     }
   }
   CK("borders + amalgamation");
-  // children lists, rel / inv maps, A lists, offsets: the sizes first (serial, cheap), then the contents in parallel
+  // children lists and the offsets of everything a front owns: the sizes first (serial, cheap), then the contents in parallel
   int64_t Loff = 0, Uoff = 0, Panoff = 0;
   double flops = 0;
   {
@@ -1629,63 +1567,21 @@ int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32
     }
     S.children.resize(n_child);
     S.n_rel = n_rel; S.n_inv = n_inv;
-    if (!S.maps_on_device) {
-      S.rel.resize(n_rel);
-      S.inv.assign(n_inv, -1);
-      S.alist.resize(3 * n_a);
-    }
   }
-  if (S.maps_on_device) {
-    // the device fills rel / inv / blk_dst / b_dst from the uploaded front table (gn_structure.hip: k_build_maps); the host
-    // keeps what it reads itself: the children lists and every child's count of border rows inside its parent's own columns
-    parallel_for(nfr, NT, [&](int flo, int fhi) {
-      for (int f = flo; f < fhi; f++) {
-        const FrontDesc& F = S.fronts[f];
-        std::copy(kids[f].begin(), kids[f].end(), S.children.begin() + F.child_off);
-        for (int ch : kids[f]) {
-          FrontDesc& G = S.fronts[ch];
-          const int32_t* gr = S.rows.data() + G.rows_off;
-          G.na = (int)(std::lower_bound(gr, gr + G.ns, F.c0 + F.nc) - gr);
-        }
-      }
-    }, 256);
-  } else
+  // the device fills rel / inv / blk_dst / b_dst from the uploaded front table (gn_structure.hip: k_build_maps); the host
+  // keeps what it reads itself: the children lists and every child's count of border rows inside its parent's own columns
   parallel_for(nfr, NT, [&](int flo, int fhi) {
-    std::vector<int32_t> posmap(nf, -1);                 // border row -> position in the current front's row list
     for (int f = flo; f < fhi; f++) {
       const FrontDesc& F = S.fronts[f];
       std::copy(kids[f].begin(), kids[f].end(), S.children.begin() + F.child_off);
-      for (int q = 0; q < F.ns; q++) posmap[S.rows[F.rows_off + q]] = q;
-      // maps of each child into this front
       for (int ch : kids[f]) {
         FrontDesc& G = S.fronts[ch];
-        int32_t* rel = S.rel.data() + G.rel_off;
-        int32_t* inv = S.inv.data() + G.inv_off;
-        int na = 0;
-        for (int q = 0; q < G.ns; q++) {
-          int r = S.rows[G.rows_off + q];
-          if (r < F.c0 + F.nc) { rel[q] = r - F.c0; na++; }
-          else { int p = posmap[r]; rel[q] = F.nc + p; inv[p] = q; }
-        }
-        G.na = na;
-      }
-      // A blocks of this front's columns
-      int32_t* al = S.alist.data() + 3 * (size_t)F.a_off;
-      for (int c = F.c0; c < F.c0 + F.nc; c++) {
-        int lc = c - F.c0;
-        *al++ = c; *al++ = lc; *al++ = lc;
-        int k = offbase[c];
-        for (int p = cp[c]; p < cp[c + 1]; p++) {
-          int r = ci[p];
-          if (r <= c) continue;
-          int lr = (r < F.c0 + F.nc) ? r - F.c0 : F.nc + posmap[r];
-          *al++ = nf + k; *al++ = lr; *al++ = lc;
-          k++;
-        }
+        const int32_t* gr = S.rows.data() + G.rows_off;
+        G.na = (int)(std::lower_bound(gr, gr + G.ns, F.c0 + F.nc) - gr);
       }
     }
   }, 256);
-  CK("maps + A lists");
+  CK("children lists");
   S.L_doubles = Loff;
   S.U_doubles = Uoff;
   S.pan_doubles = Panoff;
@@ -1735,7 +1631,7 @@ int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32
       for (int f = 0; f < nfr; f++)
         if (!in_top[f] && S.fronts[f].parent >= 0 && in_top[S.fronts[f].parent]) S.top_children.push_back(f);
       for (int f : chain) {
-        // the front's A blocks in the order of its alist: per own column the diagonal block, then the column's blocks below
+        // the front's A blocks in the order a_off counts them: per own column the diagonal block, then the column's blocks below
         // the diagonal by ascending row (the global row of a block is all the dense top block needs)
         const FrontDesc& F = S.fronts[f];
         int k = 0;
@@ -1782,29 +1678,86 @@ int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32
         F.sched_slot = 0;
       }
     }
-    if (S.maps_on_device) {
-      if (Panoff + kFrontW > 0x7fffffff) return -2;          // (the destinations are 32-bit offsets into the panels)
-    } else {
-    S.blk_dst.assign((size_t)nf + S.nb, 0);
-    S.b_dst.assign(nf, -1);
-    for (int f = 0; f < nfr; f++) {
-      const FrontDesc& F = S.fronts[f];
-      for (int k = 0; k < F.a_cnt; k++) {
-        const int32_t* al = S.alist.data() + 3 * (size_t)(F.a_off + k);
-        const int blk = al[0], lr = al[1], lc = al[2];
-        if (in_top[f]) { S.blk_dst[blk] = -(F.a_off + k + 1); continue; }
-        const int64_t row = lr < F.nc ? 3 * lr : kFrontW + 3 * (lr - F.nc);
-        const int64_t off = F.pan_off + row * kPanStride + 3 * lc;
-        if (off > 0x7fffffff) return -2;                     // (a graph two orders of magnitude beyond the benchmark configurations)
-        S.blk_dst[blk] = (int32_t)off;
-      }
-      if (!in_top[f])
-        for (int c = 0; c < F.nc; c++) S.b_dst[F.c0 + c] = (int32_t)(F.pan_off + (int64_t)(kFrontW + 3 * F.ns) * kPanStride + 3 * c);
-    }
-    }
+    if (Panoff + kFrontW > 0x7fffffff) return -2;            // (the H blocks' destinations are 32-bit offsets into the panels)
   }
   CK("destinations");
   S.t_struct = now_s() - t1;
+  return 0;
+}
+
+int structure_reference(const Symbolic& S, int nE, const int32_t* ef, const int32_t* et, StructureRef& R) {
+  R = StructureRef();
+  const int nf = S.nf, nfr = (int)S.fronts.size();
+  if (nf == 0) return 0;
+  std::vector<int32_t> offbase(nf + 1, 0);               // column c's first off-diagonal block
+  for (int32_t c : S.off_col) offbase[c + 1]++;
+  for (int c = 0; c < nf; c++) offbase[c + 1] += offbase[c];
+  // ---- assembly lists: a counting sort of every edge's keys (its end points' diagonal blocks, their off-diagonal block)
+  // that keeps the edge order
+  auto keys = [&](int k, int& a, int& b, int& e) {
+    a = S.vperm[ef[k]]; b = S.vperm[et[k]]; e = -1;
+    // self edge: the chain rule's term, (Ji + Jj)^T Omega (Ji + Jj) on the one block -- Ji + Jj is exactly zero (the error
+    // z^-1 (xi^-1 xi) does not depend on xi), so the edge adds to chi2 and to no list (include/cgmr.h, cgmr_gn_optimize)
+    if (a == b) { a = b = -1; return; }
+    if (a < 0 || b < 0) return;
+    e = offbase[std::min(a, b)];                         // the blocks of a column are listed by ascending row, a handful of them
+    while (S.off_row[e] != std::max(a, b)) e++;
+    e += nf;
+  };
+  const int nkeys = nf + S.nb;
+  R.asm_ptr.assign(nkeys + 1, 0);
+  for (int k = 0; k < nE; k++) {
+    int a, b, e;
+    keys(k, a, b, e);
+    for (int key : {a, b, e}) if (key >= 0) R.asm_ptr[key + 1]++;
+  }
+  for (int q = 0; q < nkeys; q++) R.asm_ptr[q + 1] += R.asm_ptr[q];
+  R.asm_src.resize(R.asm_ptr[nkeys]);
+  std::vector<int32_t> cur(R.asm_ptr.begin(), R.asm_ptr.end() - 1);
+  for (int k = 0; k < nE; k++) {
+    int a, b, e;
+    keys(k, a, b, e);
+    if (a >= 0) R.asm_src[cur[a]++] = 4 * k + 0;
+    if (b >= 0) R.asm_src[cur[b]++] = 4 * k + 1;
+    // a > b: lower block (row a = i, col b = j) is Hij as is; else (row b = j, col a = i) = Hij^T
+    if (e >= 0) R.asm_src[cur[e]++] = 4 * k + (S.vperm[ef[k]] > S.vperm[et[k]] ? 2 : 3);
+  }
+  // ---- the children's rows in their parent, and where every H block and right-hand-side entry goes (the order of
+  // k_build_maps: per own column the diagonal block, then the column's blocks below it)
+  R.rel.resize(S.n_rel);
+  R.inv.assign(S.n_inv, -1);
+  R.blk_dst.assign((size_t)nkeys, 0);
+  R.b_dst.assign(nf, -1);
+  std::vector<uint8_t> in_top(nfr, 0);
+  for (int f : S.top_fronts) in_top[f] = 1;
+  std::vector<int32_t> posmap(nf, -1);                   // border row -> position in the current front's row list
+  for (int f = 0; f < nfr; f++) {
+    const FrontDesc& F = S.fronts[f];
+    const int cend = F.c0 + F.nc;
+    for (int q = 0; q < F.ns; q++) posmap[S.rows[F.rows_off + q]] = q;
+    auto local = [&](int r) { return r < cend ? r - F.c0 : F.nc + posmap[r]; };
+    for (int k = 0; k < F.nchild; k++) {
+      const FrontDesc& G = S.fronts[S.children[F.child_off + k]];
+      for (int q = 0; q < G.ns; q++) {
+        const int lr = local(S.rows[G.rows_off + q]);
+        R.rel[G.rel_off + q] = lr;
+        if (lr >= F.nc) R.inv[G.inv_off + lr - F.nc] = q;
+      }
+    }
+    int slot = F.a_off;
+    auto place = [&](int blk, int lr, int lc) {
+      const int64_t row = lr < F.nc ? 3 * lr : kFrontW + 3 * (lr - F.nc);
+      const int64_t off = F.pan_off + row * kPanStride + 3 * lc;
+      R.blk_dst[blk] = in_top[f] ? -(slot + 1) : (int32_t)off;
+      slot++;
+      return in_top[f] || off <= 0x7fffffff;
+    };
+    for (int c = F.c0; c < cend; c++) {
+      if (!place(c, c - F.c0, c - F.c0)) return -2;
+      for (int k = offbase[c]; k < offbase[c + 1]; k++) if (!place(nf + k, local(S.off_row[k]), c - F.c0)) return -2;
+      if (!in_top[f]) R.b_dst[c] = (int32_t)(F.pan_off + (int64_t)(kFrontW + 3 * F.ns) * kPanStride + 3 * (c - F.c0));
+    }
+  }
   return 0;
 }
 

@@ -58,8 +58,8 @@ struct FrontDesc {                   // one per front, uploaded verbatim (all in
                       //   (0..nc_p-1 = parent's own columns, nc_p.. = parent's border), block units
   int32_t na;         // number of leading border rows that fall into the parent's own columns
   int32_t inv_off;    // offset into inv[]: ns_parent entries, inv[p] = k such that rel[k]-nc_p == p, or -1
-  int32_t a_off;      // offset into alist[] (triples) of the A blocks assembled by this front
-  int32_t a_cnt;
+  int32_t a_off;      // first of the a_cnt H blocks this front assembles, counted over all fronts: per own column the
+  int32_t a_cnt;      //   diagonal block, then the column's blocks below the diagonal by ascending row
   int32_t pan_slots;  // copies of this front's assembled panel (see pan_off): children scheduled into the same update launch
                       //   add into different copies, the factor kernel sums the copies in order
   int64_t L_off;      // offset (doubles) of this front's factor panel: header (factor_header(W)) then L21 (r x W)
@@ -105,20 +105,11 @@ struct Symbolic {
   std::vector<int32_t> hidx;           // vertex -> block index before permutation, -1 fixed/inactive
   std::vector<int32_t> vperm;          // vertex -> permuted block column, -1 fixed/inactive
   std::vector<int32_t> perm;           // permuted block column -> vertex index
-  // assembly of H blocks from edge terms (CSR over nf diagonal blocks then nb off-diagonal blocks)
-  std::vector<int32_t> asm_ptr;        // nf+nb+1
-  std::vector<int32_t> asm_src;        // edge*4 + code (0: Hii, 1: Hjj, 2: Hij, 3: Hij^T)
-  bool maps_on_device = false;         // rel / inv / blk_dst / b_dst / alist likewise (AnalyzeHooks::maps_on_device): sizes in n_rel / n_inv
-  int64_t n_rel = 0, n_inv = 0;
-  bool asm_on_device = false;          // the two lists above were left to the caller's device pass (AnalyzeHooks::blocks_ready) and are empty here
+  int64_t n_rel = 0, n_inv = 0;        // entries of the child -> parent row maps rel / inv (FrontDesc::rel_off / inv_off index them)
   std::vector<int32_t> off_row, off_col;  // per off-diagonal block: permuted row > col
-  std::vector<int32_t> blk_dst;        // per H block (nf diagonal, then nb off-diagonal): offset (doubles) in Pan of its element
-                                       //   (0, 0) (rows kPanStride apart), or -(slot + 1): slot in Ablk (fronts of the top block)
-  std::vector<int32_t> b_dst;          // per permuted block column: offset in Pan of its first right-hand-side entry, -1: top block
   // fronts
   std::vector<FrontDesc> fronts;
-  std::vector<int32_t> rows, children, rel, inv;
-  std::vector<int32_t> alist;          // triples (block id [0..nf) diag / nf+k offdiag, local row block, local col block)
+  std::vector<int32_t> rows, children;
   std::vector<int32_t> level_ptr;      // nlevels+1, fronts sorted by level in level_fronts
   std::vector<int32_t> level_fronts;
   std::vector<int32_t> col_front;      // permuted block column -> owning front
@@ -177,14 +168,27 @@ struct AnalyzeHooks {
   // Called on the analysing thread once the permutation and the off-diagonal block lists are final -- S.vperm, S.off_row,
   // S.off_col, S.nf, S.nb; offbase[c] = index of column c's first block, nf + 1 entries -- i.e. before the borders, the
   // amalgamation and the maps: a caller with a device builds the assembly lists there (gn_structure.hip: every edge's three
-  // keys, a counting sort by key that keeps the edge order) underneath the rest of the analysis.  When the hook is set
-  // analyze() does not build S.asm_ptr / S.asm_src (S.asm_on_device).  A non-zero return aborts the analysis with that value.
+  // keys, a counting sort by key that keeps the edge order) underneath the rest of the analysis.  A non-zero return aborts the
+  // analysis with that value.
   std::function<int(const Symbolic&, const int32_t* offbase)> blocks_ready;
-  // with blocks_ready: the caller's device also fills the child -> parent row maps (rel, inv) and the H blocks' destinations
-  // (blk_dst, b_dst) from the front table once that is uploaded (gn_structure.hip: k_build_maps); analyze() leaves them empty
-  bool maps_on_device = false;
 };
 int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et, Symbolic& S, Symbolic* prev = nullptr,
             int n_common = -1, const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0, const AnalyzeHooks* hooks = nullptr);
+
+// The structure arrays that only the device reads, which the device builds for itself (gn_structure.hip: k_asm_*, k_build_maps),
+// as one plain serial pass over a finished analysis and its edge list builds them: what the tests hold the kernels to, entry
+// for entry.  Nothing on the solver's path calls this.
+struct StructureRef {
+  // assembly of H blocks from edge terms (CSR over nf diagonal blocks then nb off-diagonal blocks), lists in edge order; an
+  // edge from a vertex to itself is in no list
+  std::vector<int32_t> asm_ptr;        // nf+nb+1
+  std::vector<int32_t> asm_src;        // edge*4 + code (0: Hii, 1: Hjj, 2: Hij, 3: Hij^T)
+  std::vector<int32_t> rel, inv;       // child -> parent row maps (FrontDesc::rel_off / inv_off)
+  std::vector<int32_t> blk_dst;        // per H block (nf diagonal, then nb off-diagonal): offset (doubles) in Pan of its element
+                                       //   (0, 0) (rows kPanStride apart), or -(slot + 1): slot in Ablk (fronts of the top block)
+  std::vector<int32_t> b_dst;          // per permuted block column: offset in Pan of its first right-hand-side entry, -1: top block
+};
+// Returns 0, or -2 when a destination does not fit 31 bits.
+int structure_reference(const Symbolic& S, int nE, const int32_t* ef, const int32_t* et, StructureRef& R);
 
 }  // namespace cgmr

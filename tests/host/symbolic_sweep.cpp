@@ -4,7 +4,9 @@
 // root's multi-start sweep, on graphs that grow 50 vertices at a time across that threshold (the key-frame pattern, with the
 // previous analysis handed over as cgmr_gn_symbolic_info_grown does) and with named hub vertices, and checks every result:
 // the permutation is a bijection, the fronts partition the columns, every front's parent, level, children and border rows
-// are consistent.  The helper pool reads CGMR_HOST_THREADS once per process: run it once with 1 and once with 4 (make check).
+// are consistent; and structure_reference() -- the serial builder of the arrays the device makes for itself, which the GPU tests
+// hold the kernels to -- runs on every analysis: its lists are complete and every row map entry lies inside the parent.  The
+// helper pool reads CGMR_HOST_THREADS once per process: run it once with 1 and once with 4 (make check).
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -103,6 +105,19 @@ void check(const std::string& name, const Symbolic& S, int nV, int nE, const int
     if (b < F.c0 + F.nc) continue;
     const int32_t* r = S.rows.data() + F.rows_off;
     EXPECT(std::binary_search(r, r + F.ns, b), "edge %d: column %d is not in the border of front %d", k, b, S.col_front[a]);
+  }
+  cgmr::StructureRef R;
+  EXPECT(cgmr::structure_reference(S, nE, ef, et, R) == 0, "structure_reference failed");
+  EXPECT((int)R.asm_ptr.size() == nf + S.nb + 1 && R.asm_ptr[nf + S.nb] == (int)R.asm_src.size(), "assembly lists: %zu keys, %zu entries", R.asm_ptr.size(), R.asm_src.size());
+  EXPECT((int64_t)R.rel.size() == S.n_rel && (int64_t)R.inv.size() == S.n_inv, "row maps: %zu and %zu entries", R.rel.size(), R.inv.size());
+  for (int f = 0; f < nfr; f++) {
+    const FrontDesc& F = S.fronts[f];
+    if (F.parent < 0) continue;
+    const FrontDesc& P = S.fronts[F.parent];
+    for (int k = 0; k < F.ns; k++) {
+      const int p = R.rel[F.rel_off + k];
+      EXPECT(p >= 0 && p < P.nc + P.ns, "front %d: border row %d at position %d of parent %d (%d + %d)", f, k, p, F.parent, P.nc, P.ns);
+    }
   }
 }
 

@@ -19,7 +19,7 @@ import test_dogleg_gpu as DL
 import test_lm_gpu as LM
 import test_topology_gpu as TG
 from reference_cases import OMEGA_MAX
-from test_gn_gpu import _asm_lists
+from test_gn_gpu import _asm_lists, _work_records
 from test_joint_marginals_gpu import MARG_TAU as JOINT_TAU
 from test_reference_gpu import MARG_TAU
 from test_reference_gpu import ctx_resident_only  # noqa: F401  (a fixture)
@@ -154,6 +154,8 @@ def test_structure_built_on_the_device_equals_the_hosts(ctx, family):
         assert len(src_h) > 0 and np.array_equal(ptr_d, ptr_h) and np.array_equal(src_d, src_h), name
         assert len(ptr_h) - 1 == s["keys"] and np.diff(ptr_h).max() == s["longest_list"], name
         assert np.array_equal(TG._maps(lib, ctx.h, nV, ef, et), TG._maps(lib, None, nV, ef, et)), name
+        w_d, w_h = _work_records(lib, ctx.h)
+        assert np.array_equal(w_d, w_h), name
         t = s["table"]
         front, chunk, parent, level, ns = _worklist(lib, ctx, len(t))
         assert np.array_equal(parent, t[:, 3]) and np.array_equal(level, t[:, 4]) and np.array_equal(ns, t[:, 2]), name

@@ -294,11 +294,9 @@ def test_launch_variants_of_round_6_agree(oracle):
             "    out[str(V)] = {'rc': int(rc), 'chi': [float(x) for x in chi], 'p': p.tolist(), 'timeouts': int(c.gn_timeouts())}\n"
             "print('RESULT' + json.dumps(out))\n" % root)
     res = {}
-    # (last session of round 6: the structure arrays the device builds -- assembly lists, row maps, destinations -- against the
-    # host's, and the levels that are not resident at once as two launches each)
+    # (last session of round 6: the levels that are not resident at once as two launches each)
     for name, env in (("default", {}), ("separate_launches", {"CGMR_FWD_MERGE": "0"}), ("chain_wgs_2", {"CGMR_BWD_CHAIN_WGS": "2"}),
-                      ("chain_wgs_4", {"CGMR_BWD_CHAIN_WGS": "4"}), ("merge_resident_only", {"CGMR_FWD_MERGE_ANY": "0"}),
-                      ("structure_by_host", {"CGMR_ASM_DEVICE": "0"}), ("maps_by_host", {"CGMR_MAPS_DEVICE": "0"})):
+                      ("chain_wgs_4", {"CGMR_BWD_CHAIN_WGS": "4"}), ("merge_resident_only", {"CGMR_FWD_MERGE_ANY": "0"})):
         r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
         line = [l for l in r.stdout.splitlines() if l.startswith("RESULT")]
         assert r.returncode == 0 and line, (name, r.stderr[-2000:])
@@ -323,8 +321,6 @@ def test_launch_variants_of_round_6_agree(oracle):
             assert np.abs(p[:, :2] - p2[:, :2]).max() <= POS_ATOL
             assert np.abs(synth.normalize_theta(p[:, 2] - p2[:, 2])).max() <= ANG_ATOL
             np.testing.assert_allclose(d["chi"][-1], res["default"][str(V)]["chi"][-1], rtol=1e-10)
-            if name in ("structure_by_host", "maps_by_host"):     # the same lists, maps and destinations: the same sums in the same order, the same bits
-                assert d["chi"] == res["default"][str(V)]["chi"] and d["p"] == res["default"][str(V)]["p"], name
 
 
 def _asm_lists(lib, ctx_h, nV, ef, et):
@@ -339,11 +335,26 @@ def _asm_lists(lib, ctx_h, nV, ef, et):
     return ptr[:nk + 1].copy(), src[:ns.value].copy()
 
 
+WORK_REC_BYTES = 384      # sizeof(WorkRec), gn_symbolic.h: FrontDesc 112, front / chunk / pad 16, kWorkChildren x WorkChild 8 x 32
+
+
+def _work_records(lib, ctx_h):
+    """The work records of the graph the context analysed last: (the device's, the host loop's), one row of bytes each (none
+    when every front lies in the top block)."""
+    import ctypes as C
+    lib.cgmr_debug_work_records.restype = C.c_int
+    n = lib.cgmr_debug_work_records(ctx_h, C.c_int(0), None, None)
+    assert n >= 0
+    dev, ref = (np.full((n, WORK_REC_BYTES), 0xA5, dtype=np.uint8) for _ in range(2))
+    assert lib.cgmr_debug_work_records(ctx_h, C.c_int(n), C.c_void_p(dev.ctypes.data), C.c_void_p(ref.ctypes.data)) == n
+    return dev, ref
+
+
 def test_assembly_lists_built_on_the_device_equal_the_hosts(ctx, oracle):
     """Round 6: the assembly lists of k_assemble (per block of H the edge terms that add up to it, in edge order) are built on
-    the device underneath the host's analysis (gn_structure.hip) instead of by the host (gn_symbolic.cpp).  Same lists, entry
-    for entry -- C2, and a graph with duplicate edges and two hubs whose lists (hundreds of entries)
-    take the long-list path --, and a solve on them meets the oracle."""
+    the device underneath the host's analysis (gn_structure.hip); the host's serial reference (gn_symbolic.cpp:
+    structure_reference) is what they are held to.  Same lists, entry for entry -- C2, and a graph with duplicate edges and
+    two hubs whose lists (hundreds of entries) take the long-list path --, and a solve on them meets the oracle."""
     import ctypes as C
     from cg_mrslam_amd import load_library
     lib = load_library()
@@ -376,7 +387,7 @@ def test_assembly_lists_built_on_the_device_equal_the_hosts(ctx, oracle):
         ptr_d, src_d = _asm_lists(lib, ctx.h, nV, g["edge_from"], g["edge_to"])
         ptr_h, src_h = _asm_lists(lib, None, nV, g["edge_from"], g["edge_to"])
         assert len(src_h) > 0 and np.array_equal(ptr_d, ptr_h) and np.array_equal(src_d, src_h)
-        # ... and the child -> parent row maps and the H blocks' destinations (k_build_maps against the host's loops)
+        # ... and the child -> parent row maps and the H blocks' destinations (k_build_maps against the reference's loops)
         cap = 40 * (nV + len(g["edge_from"])) + 1024
         m_d, m_h = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
         lib.cgmr_debug_maps.restype = C.c_int
@@ -384,6 +395,9 @@ def test_assembly_lists_built_on_the_device_equal_the_hosts(ctx, oracle):
         n_d = lib.cgmr_debug_maps(ctx.h, C.c_int(nV), C.c_int(len(ea)), C.c_void_p(ea.ctypes.data), C.c_void_p(eb.ctypes.data), C.c_int(cap), C.c_void_p(m_d.ctypes.data))
         n_h = lib.cgmr_debug_maps(None, C.c_int(nV), C.c_int(len(ea)), C.c_void_p(ea.ctypes.data), C.c_void_p(eb.ctypes.data), C.c_int(cap), C.c_void_p(m_h.ctypes.data))
         assert n_d == n_h > 0 and np.array_equal(m_d[:n_d], m_h[:n_h])
+        # ... and the factor kernel's work records, byte for byte
+        w_d, w_h = _work_records(lib, ctx.h)
+        assert len(w_h) > 0 and np.array_equal(w_d, w_h)
         if g is cases[1][0]:                     # (C2 against the oracle: test_gpu_full_size_c2)
             assert np.diff(ptr_h).max() > 300
             st, p2, chi2, _ = oracle.gn_optimize(*a, iters)

@@ -137,7 +137,6 @@ def test_gn_step_backward_error_device_entry_and_extended_ordering(ctx):
 
 VARIANTS = (("default", {}), ("separate_launches", {"CGMR_FWD_MERGE": "0"}), ("chain_wgs_2", {"CGMR_BWD_CHAIN_WGS": "2"}),
             ("chain_wgs_4", {"CGMR_BWD_CHAIN_WGS": "4"}), ("merge_resident_only", {"CGMR_FWD_MERGE_ANY": "0"}),
-            ("structure_by_host", {"CGMR_ASM_DEVICE": "0"}), ("maps_by_host", {"CGMR_MAPS_DEVICE": "0"}),
             ("no_top_block", {"CGMR_TOP_BLOCK": "0"}), ("panels_cleared_apart", {"CGMR_CLEAR_IN_TOP": "0"}),
             # (chunk lengths below the defaults 79 / 95 / 31: the panel loads of the factor kernel are sized for the defaults)
             ("short_chunks", {"CGMR_CHUNK": "47", "CGMR_LEAF_CHUNK": "63", "CGMR_TOP_CHUNK": "47"}),

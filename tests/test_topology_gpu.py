@@ -19,7 +19,7 @@ import test_dogleg_gpu as DL
 import test_lm_gpu as LM
 import topology_cases as T
 from reference_cases import EST_ATOL, INFO_RTOL, OMEGA_MAX
-from test_gn_gpu import ANG_ATOL, CHI_RTOL, POS_ATOL, _asm_lists, _check
+from test_gn_gpu import ANG_ATOL, CHI_RTOL, POS_ATOL, _asm_lists, _check, _work_records
 from test_marginals_all_gpu import _check_against_reference
 from test_reference_gpu import MARG_TAU, _check_marginals, _condense_case, _top_vertices
 from test_reference_gpu import ctx_resident_only  # noqa: F401  (a fixture)
@@ -332,3 +332,5 @@ def test_structure_built_on_the_device_equals_the_hosts(ctx, name):
     if name == "self_edge":
         assert not np.any(src_d >> 2 == len(g["edge_from"]) - 1)
     assert np.array_equal(_maps(lib, ctx.h, nV, g["edge_from"], g["edge_to"]), _maps(lib, None, nV, g["edge_from"], g["edge_to"]))
+    w_d, w_h = _work_records(lib, ctx.h)
+    assert np.array_equal(w_d, w_h)

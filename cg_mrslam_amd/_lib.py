@@ -139,6 +139,28 @@ class Robust(C.Structure):
                 ("edge_chi2_out", C.c_void_p), ("weight_out", C.c_void_p)]
 
 
+class FactorTypes(C.Structure):
+    """cgmr_factor_types (include/cgmr.h): the vertex and edge kinds of one typed call."""
+    _fields_ = [("vertex_kind", C.c_void_p), ("edge_kind", C.c_void_p)]
+
+
+# include/cgmr.h: CGMR_VERTEX_* / CGMR_EDGE_* (kind 2 is reserved)
+VERTEX_SE2, VERTEX_XY = 0, 1
+EDGE_SE2, EDGE_SE2_XY, EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY = 0, 1, 3, 4
+
+
+def factor_types(vertex_kind, edge_kind, nV, nE):
+    """(FactorTypes, the arrays it points into) for per-vertex / per-edge kinds (None: all zero)."""
+    vk = None if vertex_kind is None else np.ascontiguousarray(vertex_kind, dtype=np.uint8).reshape(-1)
+    ek = None if edge_kind is None else np.ascontiguousarray(edge_kind, dtype=np.uint8).reshape(-1)
+    if vk is not None and vk.shape != (nV,):
+        raise ValueError(f"vertex kinds: {vk.shape[0]} given for {nV} vertices")
+    if ek is not None and ek.shape != (nE,):
+        raise ValueError(f"edge kinds: {ek.shape[0]} given for {nE} edges")
+    ft = FactorTypes(vk.ctypes.data if vk is not None and nV else None, ek.ctypes.data if ek is not None and nE else None)
+    return ft, (vk, ek)
+
+
 # g2o's robust kernels by their C codes (include/cgmr.h: CGMR_RK_*)
 ROBUST_KINDS = {"none": 0, "huber": 1, "pseudohuber": 2, "cauchy": 3, "welsch": 4, "tukey": 5, "saturated": 6, "dcs": 7}
 
@@ -246,7 +268,7 @@ class Context:
             return [np.zeros(iters + 1)]
         return [np.zeros(iters + 1), np.zeros(iters)] + [np.zeros(iters, dtype=np.int32) for _ in range(n_int)]
 
-    def _optimize(self, entry, problem, iters, prm=None, n_int=None, rk=False, allow_fail=False):
+    def _optimize(self, entry, problem, iters, prm=None, n_int=None, rk=False, allow_fail=False, ft=None):
         """One cgmr_*_optimize* call on ``problem`` (the arguments of _problem).  ``prm``: the parameters of a trust-region
         algorithm, which also returns its iterations done; ``rk``: a cgmr_robust, None for a null one, False for an entry
         point that takes none.  Returns (status, [the poses,] chi2, [records, iterations done])."""
@@ -258,6 +280,8 @@ class Context:
         args += [_ptr(a) for a in rec]
         if prm is not None:
             args.append(C.byref(done))
+        if ft is not None:                                        # (the typed entry points: cgmr_factor_types in front of rk)
+            args.append(C.byref(ft))
         if rk is not False:
             args.append(C.byref(rk) if rk is not None else C.c_void_p(0))
         rc = getattr(self.lib, entry)(*args)
@@ -368,6 +392,88 @@ class Context:
         out = np.zeros(3, dtype=np.int64)
         self._check(self.lib.cgmr_dl_last_stats(self.h, _ptr(out)))
         return dict(host_waits=int(out[0]), trials=int(out[1]), factorisations=int(out[2]))
+
+    # ------------------------------------------------------------------ typed factors (landmarks, priors)
+    # include/cgmr.h: cgmr_factor_types.  ``vertex_kind`` [nV] (0 pose, 1 point) and ``edge_kind`` [nE] (0 EDGE_SE2, 1 EDGE_SE2_XY,
+    # 3 EDGE_PRIOR_SE2, 4 EDGE_PRIOR_SE2_XY; a prior has from == to), None = all zero; ``kind`` / ``delta``: robust kernels as
+    # gn_optimize_robust takes them, None = the plain call.  Each returns what its untyped call does, with (e2, weights) appended
+    # when ``kind`` is given.
+    def _typed(self, entry, problem, iters, vertex_kind, edge_kind, kind, delta, prm=None, n_int=None, allow_fail=False):
+        nE = len(problem[2])
+        nV = problem[0][1] if isinstance(problem[0], tuple) else len(problem[0])
+        ft, _keep_ft = factor_types(vertex_kind, edge_kind, nV, nE)
+        rk, e2, w, _keep = self._robust(kind, delta, nE) if kind is not None else (None, None, None, None)
+        out = self._optimize(entry, problem, iters, prm, n_int, rk=rk, allow_fail=allow_fail, ft=ft)
+        return out + (e2, w) if kind is not None else out
+
+    def gn_optimize_typed(self, poses, fixed, ef, et, meas, info, iters, vertex_kind=None, edge_kind=None, kind=None, delta=1.0,
+                          raise_on_cholesky=True):
+        """Gauss-Newton with typed factors: (status, poses, chi2[iters+1])."""
+        return self._typed("cgmr_gn_optimize_typed", (poses, fixed, ef, et, meas, info), iters, vertex_kind, edge_kind, kind, delta,
+                           allow_fail=not raise_on_cholesky)
+
+    def gn_optimize_typed_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters, vertex_kind=None, edge_kind=None,
+                              kind=None, delta=1.0, raise_on_cholesky=True):
+        """gn_optimize_typed on device pointers (the kinds stay host arrays): (status, chi2[iters+1])."""
+        return self._typed("cgmr_gn_optimize_typed_dev", ((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), iters,
+                           vertex_kind, edge_kind, kind, delta, allow_fail=not raise_on_cholesky)
+
+    def lm_optimize_typed(self, poses, fixed, ef, et, meas, info, iters, vertex_kind=None, edge_kind=None, kind=None, delta=1.0,
+                          **params):
+        """Levenberg-Marquardt with typed factors: (status, poses, chi2, lambdas, trials, iters_done)."""
+        return self._typed("cgmr_lm_optimize_typed", (poses, fixed, ef, et, meas, info), iters, vertex_kind, edge_kind, kind, delta,
+                           lm_params(**params), 1)
+
+    def lm_optimize_typed_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters, vertex_kind=None, edge_kind=None,
+                              kind=None, delta=1.0, **params):
+        """lm_optimize_typed on device pointers: (status, chi2, lambdas, trials, iters_done)."""
+        return self._typed("cgmr_lm_optimize_typed_dev", ((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), iters,
+                           vertex_kind, edge_kind, kind, delta, lm_params(**params), 1)
+
+    def dl_optimize_typed(self, poses, fixed, ef, et, meas, info, iters, vertex_kind=None, edge_kind=None, kind=None, delta=1.0,
+                          raise_on_fail=True, **params):
+        """Dogleg with typed factors: (status, poses, chi2, deltas, trials, steps, iters_done)."""
+        return self._typed("cgmr_dl_optimize_typed", (poses, fixed, ef, et, meas, info), iters, vertex_kind, edge_kind, kind, delta,
+                           dl_params(**params), 2, allow_fail=not raise_on_fail)
+
+    def dl_optimize_typed_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters, vertex_kind=None, edge_kind=None,
+                              kind=None, delta=1.0, raise_on_fail=True, **params):
+        """dl_optimize_typed on device pointers: (status, chi2, deltas, trials, steps, iters_done)."""
+        return self._typed("cgmr_dl_optimize_typed_dev", ((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), iters,
+                           vertex_kind, edge_kind, kind, delta, dl_params(**params), 2, allow_fail=not raise_on_fail)
+
+    def marginals_typed(self, poses, fixed, ef, et, meas, info, query, vertex_kind=None, edge_kind=None, kind=None, delta=1.0):
+        """marginals on the typed H: cov [nK, 3, 3] (a point's third row and column are zero); (cov, e2, weights) with ``kind``."""
+        poses, ef, et, meas, info = self._graph_args(poses, ef, et, meas, info)
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        query = np.ascontiguousarray(query, dtype=np.int32)
+        ft, _keep_ft = factor_types(vertex_kind, edge_kind, poses.shape[0], len(ef))
+        rk, e2, w, _keep = self._robust(kind, delta, len(ef)) if kind is not None else (None, None, None, None)
+        cov = np.zeros((len(query), 3, 3))
+        rc = self.lib.cgmr_marginals_typed(self.h, C.c_int(poses.shape[0]), _ptr(poses), _ptr(fixed), C.c_int(len(ef)), _ptr(ef),
+                                           _ptr(et), _ptr(meas), _ptr(info), C.c_int(len(query)), _ptr(query), _ptr(cov),
+                                           C.byref(ft), C.byref(rk) if rk is not None else C.c_void_p(0))
+        self._check(rc)
+        return (cov, e2, w) if kind is not None else cov
+
+    def marginals_all_typed(self, poses, fixed, ef, et, meas, info, cross=False, vertex_kind=None, edge_kind=None, kind=None,
+                            delta=1.0):
+        """marginals_all on the typed H: cov [nV, 3, 3], with ``cross=True`` (cov, cross [nE, 3, 3]); (e2, weights) appended
+        with ``kind``."""
+        poses, ef, et, meas, info = self._graph_args(poses, ef, et, meas, info)
+        fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
+        ft, _keep_ft = factor_types(vertex_kind, edge_kind, poses.shape[0], len(ef))
+        rk, e2, w, _keep = self._robust(kind, delta, len(ef)) if kind is not None else (None, None, None, None)
+        cov = np.zeros((poses.shape[0], 3, 3))
+        cr = np.zeros((len(ef), 3, 3)) if cross else None
+        rc = self.lib.cgmr_marginals_all_typed(self.h, C.c_int(poses.shape[0]), _ptr(poses), _ptr(fixed), C.c_int(len(ef)),
+                                               _ptr(ef), _ptr(et), _ptr(meas), _ptr(info), _ptr(cov), _ptr(cr), C.byref(ft),
+                                               C.byref(rk) if rk is not None else C.c_void_p(0))
+        self._check(rc)
+        out = (cov, cr) if cross else (cov,)
+        if kind is not None:
+            out += (e2, w)
+        return out if len(out) > 1 else out[0]
 
     # ------------------------------------------------------------------ marginals / condensed graph
     @staticmethod

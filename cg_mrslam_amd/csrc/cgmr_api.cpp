@@ -542,6 +542,7 @@ void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, con
   }
   D.pan_clean = false;
   T.run(1, 1, [&] { launch_assemble(st, D); });                // + the chi2 sum of this iteration (slot = iterations done)
+  if (Ed.typed && Ed.n_unary > 0) T.run(1, 1, [&] { launch_add_unary(st, D, Ed); });   // the priors: self edges, no assembly key
   if (o.after_assemble) o.after_assemble(st, D, o.after_assemble_arg);
   static const bool trace = getenv("CGMR_TRACE_LAUNCHES") != nullptr;
   if (trace)
@@ -1118,6 +1119,87 @@ static int robust_stats_out(cgmr_ctx* ctx, const cgmr_robust* rk, int nE, const 
   return 0;
 }
 
+// The factor types of a typed entry point (include/cgmr.h: cgmr_factor_types), checked on the host before the device is
+// touched: every vertex kind 0 or 1, every edge kind with the vertex kinds and the arity its factor needs.  `any`: some kind
+// is not zero (all zero: the call is the plain one, bit for bit -- the plain launches).  The priors grouped by vertex, in edge
+// order, for k_add_unary.
+struct TypedHost {
+  bool any = false;
+  std::vector<uint8_t> vk, ek;
+  std::vector<int32_t> uv_vertex, uv_ptr, uv_edge;
+};
+static int typed_check(cgmr_ctx* ctx, const char* who, const cgmr_factor_types* ft, int nV, int nE, const int32_t* ef, const int32_t* et,
+                       TypedHost& T) {
+  if (!ft) return 0;                                          // (the plain call: nothing is built)
+  T.vk.assign((size_t)std::max(nV, 0), 0);
+  T.ek.assign((size_t)std::max(nE, 0), 0);
+  if (ft->vertex_kind) T.vk.assign(ft->vertex_kind, ft->vertex_kind + nV);
+  if (ft->edge_kind) T.ek.assign(ft->edge_kind, ft->edge_kind + nE);
+  for (int v = 0; v < nV; v++)
+    if (T.vk[v] > 1) return set_err(ctx, CGMR_E_INVALID, "%s: vertex %d has kind %d (0 = SE2 pose, 1 = point)", who, v, (int)T.vk[v]);
+  std::vector<int32_t> cnt((size_t)std::max(nV, 0) + 1, 0);
+  int n_prior = 0;
+  for (int k = 0; k < nE; k++) {
+    const int kind = T.ek[k], a = ef[k], b = et[k];
+    if (a < 0 || a >= nV || b < 0 || b >= nV) return set_err(ctx, CGMR_E_INVALID, "%s: edge %d has a vertex index out of range", who, k);
+    if (kind == 2) return set_err(ctx, CGMR_E_INVALID, "%s: edge %d has kind 2 (bearing-only observations are reserved, not implemented)", who, k);
+    if (kind > 4) return set_err(ctx, CGMR_E_INVALID, "%s: edge %d has unknown kind %d", who, k, kind);
+    if (kind == 1) {
+      if (T.vk[a] != 0 || T.vk[b] != 1)
+        return set_err(ctx, CGMR_E_INVALID, "%s: edge %d (EDGE_SE2_XY) must go from a pose to a point", who, k);
+    } else {
+      if (T.vk[a] != 0 || T.vk[b] != 0)
+        return set_err(ctx, CGMR_E_INVALID, "%s: edge %d (kind %d) touches a point; only EDGE_SE2_XY may", who, k, kind);
+      if (kind >= 3) {
+        if (a != b) return set_err(ctx, CGMR_E_INVALID, "%s: edge %d is a prior (kind %d) and must have from == to", who, k, kind);
+        cnt[a + 1]++;
+        n_prior++;
+      }
+    }
+    if (kind) T.any = true;
+  }
+  if (!T.any) return 0;
+  // CSR of the priors by vertex: vertices ascending, a vertex's edges ascending
+  std::vector<int32_t> slot((size_t)nV, -1);
+  for (int v = 0; v < nV; v++)
+    if (cnt[v + 1]) { slot[v] = (int32_t)T.uv_vertex.size(); T.uv_vertex.push_back(v); T.uv_ptr.push_back(0); }
+  T.uv_ptr.push_back(0);
+  for (size_t u = 0; u < T.uv_vertex.size(); u++) T.uv_ptr[u + 1] = T.uv_ptr[u] + cnt[T.uv_vertex[u] + 1];
+  T.uv_edge.assign((size_t)n_prior, 0);
+  std::vector<int32_t> cur(T.uv_ptr.begin(), T.uv_ptr.end());
+  for (int k = 0; k < nE; k++) if (T.ek[k] >= 3) T.uv_edge[cur[slot[ef[k]]]++] = k;
+  return 0;
+}
+// ... staged through ty_arena into Ed (nothing when every kind is zero)
+static int typed_upload(cgmr_ctx* ctx, const TypedHost* T, GnEdges& Ed) {
+  if (!T || !T->any) return 0;
+  Layout256 L;
+  const size_t nU = T->uv_vertex.size();
+  const size_t o_ek = L.add(T->ek.size()), o_uv = L.add(4 * std::max<size_t>(nU, 1)), o_up = L.add(4 * (nU + 1)),
+               o_ue = L.add(4 * std::max<size_t>(T->uv_edge.size(), 1));
+  int rc = arena_reserve(ctx, ctx->ty_arena, L.off + 256);
+  if (rc) return rc;
+  char* d = ctx->ty_arena.ptr;
+  hipStream_t st = ctx->stream;
+  // (pageable host memory: the copies have left the vectors when they return)
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_ek, T->ek.data(), T->ek.size(), hipMemcpyHostToDevice, st));
+  if (nU > 0) {
+    HIP_TRY(ctx, hipMemcpyAsync(d + o_uv, T->uv_vertex.data(), 4 * nU, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d + o_up, T->uv_ptr.data(), 4 * (nU + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d + o_ue, T->uv_edge.data(), 4 * T->uv_edge.size(), hipMemcpyHostToDevice, st));
+  }
+  Ed.typed = true;
+  Ed.edge_kind = (const uint8_t*)(d + o_ek);
+  Ed.n_unary = (int)nU;
+  Ed.uv_vertex = (const int32_t*)(d + o_uv); Ed.uv_ptr = (const int32_t*)(d + o_up); Ed.uv_edge = (const int32_t*)(d + o_ue);
+  return 0;
+}
+// a point's dummy unknown out of a 3x3 block of H^-1: third row (the block's row vertex is a point) / third column (its column vertex is)
+static void zero_point_dims(double* blk, bool row_point, bool col_point) {
+  if (row_point) blk[6] = blk[7] = blk[8] = 0.0;
+  if (col_point) blk[2] = blk[5] = blk[8] = 0.0;
+}
+
 // What a marginals entry point does around its own launches, whichever blocks of H^-1 it is after: the robust description, a
 // private copy of the poses, the structure and the masks, the head of the staging block (poses | meas | info; the driver
 // adds its own fields to L behind it), one pass that keeps the factor with what reads it, the statistics and the ending.
@@ -1138,9 +1220,10 @@ struct MargCall {
       : ctx(c), nV(nv), nE(ne), rk(r), work(poses, poses + 3 * (size_t)nv), o_p(L.add(24 * (size_t)nv)), o_m(L.add(24 * (size_t)ne)),
         o_i(L.add(48 * (size_t)ne)) {}
   // robust kernels: rho1 at the pass's linearisation point
-  int open(const char* who) {
+  int open(const char* who, const TypedHost* typed = nullptr) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return robust_setup(ctx, rk, nE, false, Ed, who);
+    const int rc = robust_setup(ctx, rk, nE, false, Ed, who);
+    return rc ? rc : typed_upload(ctx, typed, Ed);
   }
   int structure(const uint8_t* fixed, const int32_t* ef, const int32_t* et) {
     const int rc = prepare_structure(ctx, nV, nE, ef, et, 1);
@@ -1209,15 +1292,18 @@ struct MargCall {
 int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uint8_t* fixed_in, int nE,
                     const int32_t* ef, const int32_t* et, const double* meas, const double* info, int gauge, int nK,
                     const int32_t* query, int32_t* to_out, double* est_out, double* info_out, double* cov_out,
-                    const cgmr_robust* rk) {
+                    const cgmr_robust* rk, const cgmr_factor_types* ft = nullptr) {
   if (nV <= 0 || nE < 0 || nK < 0 || !poses || (nE > 0 && (!ef || !et || !meas || !info)) || (nK > 0 && !query))
     return set_err(ctx, CGMR_E_INVALID, "marginals: null or negative argument");
   if (mode != 0 && (gauge < 0 || gauge >= nV)) return set_err(ctx, CGMR_E_INVALID, "gauge index out of range");
   for (int k = 0; k < nK; k++)
     if (query[k] < 0 || query[k] >= nV) return set_err(ctx, CGMR_E_INVALID, "query index out of range");
   // (the linearisation point: the poses given, or the spanning-tree guess of modes 1 and 2)
+  TypedHost typed;                                                      // (mode 0 only: cgmr_marginals_typed)
+  int rc = typed_check(ctx, "cgmr_marginals_typed", ft, nV, nE, ef, et, typed);
+  if (rc) return rc;
   MargCall call(ctx, nV, poses, nE, rk);
-  int rc = call.open(mode == 0 ? "cgmr_marginals_robust" : mode == 1 ? "cgmr_covariance_estimate_robust" : "cgmr_condense_robust");
+  rc = call.open(ft ? "cgmr_marginals_typed" : mode == 0 ? "cgmr_marginals_robust" : mode == 1 ? "cgmr_covariance_estimate_robust" : "cgmr_condense_robust", &typed);
   if (rc) return rc;
   std::vector<uint8_t> fixed(nV, 0);
   if (mode == 0) { if (!fixed_in) return set_err(ctx, CGMR_E_INVALID, "fixed flags missing"); fixed.assign(fixed_in, fixed_in + nV); }
@@ -1274,7 +1360,10 @@ int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const 
   }
   // scatter back in query order; fixed / inactive queries keep zeros
   for (int k = 0; k < nq; k++)
-    if (qcol[k] >= 0) memcpy(cov_out + 9 * (size_t)k, cov.data() + 9 * (size_t)k, 72);
+    if (qcol[k] >= 0) {
+      memcpy(cov_out + 9 * (size_t)k, cov.data() + 9 * (size_t)k, 72);
+      if (typed.any && typed.vk[q[k]]) zero_point_dims(cov_out + 9 * (size_t)k, true, true);
+    }
   return CGMR_OK;
 }
 
@@ -1282,12 +1371,15 @@ int marginal_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const 
 // of every vertex and the block of every edge.  The same pass as marginal_driver's mode 0 (gn_pass at `poses` with `fixed`).
 int marginals_all_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
                          const int32_t* et, const double* meas, const double* info, double* cov_out, double* cross_out,
-                         const cgmr_robust* rk) {
+                         const cgmr_robust* rk, const cgmr_factor_types* ft = nullptr) {
   if (nV <= 0 || nE < 0 || !poses || !cov_out || (nE > 0 && (!ef || !et || !meas || !info)))
     return set_err(ctx, CGMR_E_INVALID, "marginals: null or negative argument");
   if (!fixed) return set_err(ctx, CGMR_E_INVALID, "fixed flags missing");
+  TypedHost typed;
+  int rc = typed_check(ctx, "cgmr_marginals_all_typed", ft, nV, nE, ef, et, typed);
+  if (rc) return rc;
   MargCall call(ctx, nV, poses, nE, rk);
-  int rc = call.open("cgmr_marginals_all_robust");
+  rc = call.open(ft ? "cgmr_marginals_all_typed" : "cgmr_marginals_all_robust", &typed);
   if (rc) return rc;
   auto zero_outputs = [&]() {
     memset(cov_out, 0, 72 * (size_t)nV);
@@ -1349,6 +1441,10 @@ int marginals_all_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8
   if (rc) return rc;
   rc = call.close();
   if (rc == CGMR_E_CHOLESKY_BASE) zero_outputs();
+  if (rc == CGMR_OK && typed.any) {
+    for (int v = 0; v < nV; v++) if (typed.vk[v]) zero_point_dims(cov_out + 9 * (size_t)v, true, true);
+    if (cross_out) for (int k = 0; k < nE; k++) zero_point_dims(cross_out + 9 * (size_t)k, typed.vk[ef[k]] != 0, typed.vk[et[k]] != 0);
+  }
   return rc;
 }
 
@@ -1506,10 +1602,12 @@ static int optimize_args_check(cgmr_ctx* ctx, const char* name, int nV, const do
 // the robust statistics are returned when the call ended well, and with cholesky_too also on a Cholesky status.
 template <typename Run>
 static int optimize_staged(cgmr_ctx* ctx, const char* who, bool dev, bool cholesky_too, int nV, double* poses, int nE,
-                           const double* meas, const double* info, const cgmr_robust* rk, Run&& run) {
+                           const double* meas, const double* info, const cgmr_robust* rk, const TypedHost* typed, Run&& run) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   GnEdges Ed;
   int rc = robust_setup(ctx, rk, nE, dev, Ed, who);
+  if (rc) return rc;
+  rc = typed_upload(ctx, typed, Ed);
   if (rc) return rc;
   double* d_poses = poses;
   const size_t bp = sizeof(double) * 3 * (size_t)nV;
@@ -1543,20 +1641,26 @@ static int optimize_staged(cgmr_ctx* ctx, const char* who, bool dev, bool choles
 
 static int gn_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                             const int32_t* to_idx, const double* meas, const double* info, int iters, double* chi2_out,
-                            const cgmr_robust* rk, bool dev) {
-  const int rc = optimize_args_check(ctx, "cgmr_gn_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
+                            const cgmr_robust* rk, bool dev, const cgmr_factor_types* ft = nullptr) {
+  int rc = optimize_args_check(ctx, "cgmr_gn_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
   if (rc) return rc;
-  return optimize_staged(ctx, dev ? "cgmr_gn_optimize_robust_dev" : "cgmr_gn_optimize_robust", dev, true, nV, poses, nE, meas, info, rk,
+  TypedHost typed;
+  rc = typed_check(ctx, dev ? "cgmr_gn_optimize_typed_dev" : "cgmr_gn_optimize_typed", ft, nV, nE, from_idx, to_idx, typed);
+  if (rc) return rc;
+  return optimize_staged(ctx, ft ? "cgmr_gn_optimize_typed" : dev ? "cgmr_gn_optimize_robust_dev" : "cgmr_gn_optimize_robust", dev, true, nV, poses, nE, meas, info, rk, &typed,
                          [&](double* d_poses, const GnEdges& Ed) { return gn_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, chi2_out); });
 }
 
 static int lm_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                             const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_lm_params* params,
                             double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done, const cgmr_robust* rk,
-                            bool dev) {
-  const int rc = optimize_args_check(ctx, "cgmr_lm_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
+                            bool dev, const cgmr_factor_types* ft = nullptr) {
+  int rc = optimize_args_check(ctx, "cgmr_lm_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
   if (rc) return rc;
-  return optimize_staged(ctx, dev ? "cgmr_lm_optimize_robust_dev" : "cgmr_lm_optimize_robust", dev, false, nV, poses, nE, meas, info, rk,
+  TypedHost typed;
+  rc = typed_check(ctx, dev ? "cgmr_lm_optimize_typed_dev" : "cgmr_lm_optimize_typed", ft, nV, nE, from_idx, to_idx, typed);
+  if (rc) return rc;
+  return optimize_staged(ctx, ft ? "cgmr_lm_optimize_typed" : dev ? "cgmr_lm_optimize_robust_dev" : "cgmr_lm_optimize_robust", dev, false, nV, poses, nE, meas, info, rk, &typed,
                          [&](double* d_poses, const GnEdges& Ed) {
                            return lm_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, lambda_out, trials_out, iters_done);
                          });
@@ -1565,13 +1669,16 @@ static int lm_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t*
 static int dl_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                             const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_dl_params* params,
                             double* chi2_out, double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
-                            const cgmr_robust* rk, bool dev) {
-  const int rc = optimize_args_check(ctx, "cgmr_dl_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
+                            const cgmr_robust* rk, bool dev, const cgmr_factor_types* ft = nullptr) {
+  int rc = optimize_args_check(ctx, "cgmr_dl_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
+  if (rc) return rc;
+  TypedHost typed;
+  rc = typed_check(ctx, dev ? "cgmr_dl_optimize_typed_dev" : "cgmr_dl_optimize_typed", ft, nV, nE, from_idx, to_idx, typed);
   if (rc) return rc;
   if (!dl_params_ok(params))
     return set_err(ctx, CGMR_E_INVALID,
                    "cgmr_dl_optimize: max_trials must be >= 1, initial_delta / initial_lambda > 0, lambda_factor > 1, all finite");
-  return optimize_staged(ctx, dev ? "cgmr_dl_optimize_dev" : "cgmr_dl_optimize", dev, true, nV, poses, nE, meas, info, rk,
+  return optimize_staged(ctx, ft ? "cgmr_dl_optimize_typed" : dev ? "cgmr_dl_optimize_dev" : "cgmr_dl_optimize", dev, true, nV, poses, nE, meas, info, rk, &typed,
                          [&](double* d_poses, const GnEdges& Ed) {
                            return dl_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, delta_out, trials_out, step_out, iters_done);
                          });
@@ -1583,7 +1690,7 @@ using namespace cgmr;
 
 extern "C" {
 
-int cgmr_version(void) { return 105; }   // 105: cgmr_*_optimize_robust*, cgmr_graph_set_edge_robust / _set_received_robust / _edge_stats added, later (same number: callers find them by their symbols) cgmr_marginals_robust, cgmr_marginals_all_robust, cgmr_covariance_estimate_robust, cgmr_condense_robust, cgmr_graph_set_condensed_robust, cgmr_dl_optimize*, cgmr_dl_last_stats, cgmr_graph_set_dogleg_params, cgmr_graph_dl_last (CGMR_ALG_DOGLEG), cgmr_marginals_joint, cgmr_marginals_pairs, cgmr_relative_covariance; 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
+int cgmr_version(void) { return 105; }   // 105: cgmr_*_optimize_robust*, cgmr_graph_set_edge_robust / _set_received_robust / _edge_stats added, later (same number: callers find them by their symbols) cgmr_marginals_robust, cgmr_marginals_all_robust, cgmr_covariance_estimate_robust, cgmr_condense_robust, cgmr_graph_set_condensed_robust, cgmr_dl_optimize*, cgmr_dl_last_stats, cgmr_graph_set_dogleg_params, cgmr_graph_dl_last (CGMR_ALG_DOGLEG), cgmr_marginals_joint, cgmr_marginals_pairs, cgmr_relative_covariance, cgmr_*_optimize_typed*, cgmr_marginals_typed, cgmr_marginals_all_typed; 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
 
 int cgmr_ctx_create(int device, void* hip_stream, cgmr_ctx** out) {
   if (!out) return CGMR_E_INVALID;
@@ -1629,6 +1736,7 @@ void cgmr_ctx_destroy(cgmr_ctx* ctx) {
   if (ctx->lm_arena.ptr) (void)hipFree(ctx->lm_arena.ptr);
   if (ctx->dl_arena.ptr) (void)hipFree(ctx->dl_arena.ptr);
   if (ctx->rk_arena.ptr) (void)hipFree(ctx->rk_arena.ptr);
+  if (ctx->ty_arena.ptr) (void)hipFree(ctx->ty_arena.ptr);
   if (ctx->st_arena.ptr) (void)hipFree(ctx->st_arena.ptr);
   if (ctx->pinned_st) (void)hipHostFree(ctx->pinned_st);
   if (ctx->ev_st_copied) (void)hipEventDestroy(ctx->ev_st_copied);
@@ -1728,6 +1836,64 @@ int cgmr_dl_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* 
                          const cgmr_robust* rk) {
   return dl_optimize_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, params, chi2_out, delta_out,
                           trials_out, step_out, iters_done, rk, true);
+}
+
+int cgmr_gn_optimize_typed(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                           const int32_t* to_idx, const double* meas, const double* info, int iters, double* chi2_out,
+                           const cgmr_factor_types* types, const cgmr_robust* rk) {
+  return gn_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, chi2_out, rk, false, types);
+}
+
+int cgmr_gn_optimize_typed_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                               const int32_t* to_idx, const double* d_meas, const double* d_info, int iters, double* chi2_out,
+                               const cgmr_factor_types* types, const cgmr_robust* rk) {
+  return gn_optimize_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, chi2_out, rk, true, types);
+}
+
+int cgmr_lm_optimize_typed(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                           const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_lm_params* params,
+                           double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done,
+                           const cgmr_factor_types* types, const cgmr_robust* rk) {
+  return lm_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, params, chi2_out, lambda_out, trials_out,
+                          iters_done, rk, false, types);
+}
+
+int cgmr_lm_optimize_typed_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                               const int32_t* to_idx, const double* d_meas, const double* d_info, int iters,
+                               const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
+                               int32_t* iters_done, const cgmr_factor_types* types, const cgmr_robust* rk) {
+  return lm_optimize_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, params, chi2_out, lambda_out,
+                          trials_out, iters_done, rk, true, types);
+}
+
+int cgmr_dl_optimize_typed(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                           const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_dl_params* params,
+                           double* chi2_out, double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
+                           const cgmr_factor_types* types, const cgmr_robust* rk) {
+  return dl_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, params, chi2_out, delta_out, trials_out,
+                          step_out, iters_done, rk, false, types);
+}
+
+int cgmr_dl_optimize_typed_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                               const int32_t* to_idx, const double* d_meas, const double* d_info, int iters,
+                               const cgmr_dl_params* params, double* chi2_out, double* delta_out, int32_t* trials_out,
+                               int32_t* step_out, int32_t* iters_done, const cgmr_factor_types* types, const cgmr_robust* rk) {
+  return dl_optimize_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, params, chi2_out, delta_out,
+                          trials_out, step_out, iters_done, rk, true, types);
+}
+
+int cgmr_marginals_typed(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                         const int32_t* et, const double* meas, const double* info, int nK, const int32_t* query,
+                         double* cov_out, const cgmr_factor_types* types, const cgmr_robust* rk) {
+  if (!ctx) return CGMR_E_INVALID;
+  return marginal_driver(ctx, 0, nV, poses, fixed, nE, ef, et, meas, info, -1, nK, query, nullptr, nullptr, nullptr, cov_out, rk, types);
+}
+
+int cgmr_marginals_all_typed(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                             const int32_t* et, const double* meas, const double* info, double* cov_out, double* cross_out,
+                             const cgmr_factor_types* types, const cgmr_robust* rk) {
+  if (!ctx) return CGMR_E_INVALID;
+  return marginals_all_driver(ctx, nV, poses, fixed, nE, ef, et, meas, info, cov_out, cross_out, rk, types);
 }
 
 int cgmr_dl_last_stats(const cgmr_ctx* ctx, int64_t out[3]) {

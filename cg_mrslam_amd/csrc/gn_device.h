@@ -66,6 +66,13 @@ struct GnEdges {
   int rk_kind0 = 0;
   double rk_delta0 = 1.0;
   double* rk_stats = nullptr;
+  // typed (include/cgmr.h: cgmr_factor_types; gn_kernels.hip: TypedArgs): edge k < nA is of kind edge_kind[k] (device memory).
+  // The priors among them, grouped by vertex for k_add_unary: vertex uv_vertex[u] owns the edges uv_edge[uv_ptr[u] ..
+  // uv_ptr[u + 1]), ascending (device memory).  One job only.  Not typed: the launches as before.
+  bool typed = false;
+  const uint8_t* edge_kind = nullptr;
+  int n_unary = 0;
+  const int32_t *uv_vertex = nullptr, *uv_ptr = nullptr, *uv_edge = nullptr;
 };
 // gn_structure.hip: the assembly lists (asm_ptr: nf + nb + 1, asm_src: one entry per (edge, key)) from the permutation, the
 // edge list and the off-diagonal blocks (offbase: nf + 1 column starts into off_row); work space: ekey nE, cnt nf + nb + 3,
@@ -83,6 +90,7 @@ void launch_build_maps(hipStream_t st, const GnDevice& D, const int32_t* offbase
 void launch_linearize(hipStream_t st, const GnDevice& D, const double* poses, const GnEdges& Ed, int chi_only);
 void launch_chi2(hipStream_t st, const GnDevice& D, double* out);
 void launch_assemble(hipStream_t st, const GnDevice& D);
+void launch_add_unary(hipStream_t st, const GnDevice& D, const GnEdges& Ed);   // the priors' records, behind launch_assemble (typed passes)
 void gn_init_kernels();
 void launch_factor_level(hipStream_t st, const GnDevice& D, int level, bool write_l11c);
 void launch_update_level(hipStream_t st, const GnDevice& D, int level);

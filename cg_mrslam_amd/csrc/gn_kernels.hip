@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <type_traits>
 
 #include "gn_symbolic.h"
 #include "gn_device.h"
@@ -154,6 +155,27 @@ __device__ __forceinline__ double robustify(int kind, double delta, double e2, d
   }
 }
 
+// TYPED (g2o's slam2d factor types, include/cgmr.h: cgmr_factor_types): edge k < nA is of kind edge_kind[k] --
+//   0  EDGE_SE2           as above
+//   1  EDGE_SE2_XY        pose i sees point l:  e = R(th_i)^T (l - t_i) - z (2)
+//   3  EDGE_PRIOR_SE2     unary (i == j):       e = (R(z_th)^T (t_i - z_t), normalize(th_i - z_th))
+//   4  EDGE_PRIOR_SE2_XY  unary (i == j):       e = t_i - z (2)
+// A 2-dimensional factor takes z0, z1 and the entries (0,0) (0,1) (1,1) of its information; its third error component and the
+// third row / column of O are zero, so e^T O e -- and with it the robust weight -- is that of the factor's own dimension.  The
+// record keeps its layout.  A point owns a 3x3 block column like a pose: a kind-1 edge leaves the third row / column of Hjj
+// and the third column of Hij zero except for Hjj(2,2), a copy of Hjj(0,0) (1.0 when that is not positive): the dummy unknown
+// decouples with a positive pivot and a zero right-hand side, its dx is exactly zero, and its diagonal never exceeds a real one
+// of the same block (k_lm_init's max |H_jj| is the true-dimension system's).  A prior's record holds Hii and bi; the structure
+// gives a self edge no assembly key, k_add_unary adds the record behind k_assemble.  The kinds are a third kind of trailing
+// argument: the plain and the robust instances keep their names and their code.
+struct TypedArgs {
+  const uint8_t* edge_kind;   // [nA]; edges [nA, nE) are kind 0
+};
+template <typename T> __device__ __forceinline__ T pick_arg(T a) { return a; }
+template <typename T, typename U> __device__ __forceinline__ T pick_arg(T a, U) { return a; }
+template <typename T, typename U> __device__ __forceinline__ T pick_arg(U, T b) { return b; }
+template <typename T, typename... P> struct pack_has { static constexpr bool value = (std::is_same<T, P>::value || ...); };
+
 template <bool BATCH, bool ROBUST, typename... Rk>
 __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active, const double* __restrict__ poses,
                                                    const int32_t* __restrict__ ef, const int32_t* __restrict__ et,
@@ -161,7 +183,8 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
                                                    const double* __restrict__ meas_b, const double* __restrict__ info_b,
                                                    double* __restrict__ term, int chi_only, long long js, long long ps,
                                                    Rk... rk_pack) {
-  static_assert(sizeof...(Rk) == (ROBUST ? 1 : 0), "k_linearize: one RobustArgs in the robust instance, none otherwise");
+  constexpr bool TYPED = pack_has<TypedArgs, Rk...>::value;
+  static_assert(sizeof...(Rk) == (ROBUST ? 1 : 0) + (TYPED ? 1 : 0), "k_linearize: one RobustArgs in the robust instances, one TypedArgs in the typed ones");
   CGMR_JOB(poses, ps); CGMR_JOB(term, js);
   __shared__ double s_chi[4];
   const int k0 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -181,6 +204,16 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
   double e[3] = {cz * tx + sz * ty, -sz * tx + cz * ty, d_normalize_theta(rth - z2)};
   const double* u = k < nA ? info + 6 * (size_t)k : info_b + 6 * (size_t)(k - nA);
   double O[9] = {u[0], u[1], u[2], u[1], u[3], u[4], u[2], u[4], u[5]};
+  [[maybe_unused]] int fk = 0;
+  if constexpr (TYPED) {
+    fk = k < nA ? (int)pick_arg<TypedArgs>(rk_pack...).edge_kind[k] : 0;
+    if (fk == 1) { e[0] = tx; e[1] = ty; e[2] = 0.0; }
+    else if (fk == 3) {
+      const double px = xi0 - z0, py = xi1 - z1;
+      e[0] = cz * px + sz * py; e[1] = -sz * px + cz * py; e[2] = d_normalize_theta(xi2 - z2);
+    } else if (fk == 4) { e[0] = xi0 - z0; e[1] = xi1 - z1; e[2] = 0.0; }
+    if (fk == 1 || fk == 4) { O[2] = O[5] = O[6] = O[7] = O[8] = 0.0; }
+  }
   double Oe[3];
 #pragma unroll
   for (int r = 0; r < 3; r++) Oe[r] = O[3 * r] * e[0] + O[3 * r + 1] * e[1] + O[3 * r + 2] * e[2];
@@ -189,7 +222,7 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
   {
     double ch = live ? e[0] * Oe[0] + e[1] * Oe[1] + e[2] * Oe[2] : 0.0;
     if constexpr (ROBUST) {
-      const RobustArgs rk(rk_pack...);
+      const RobustArgs rk = pick_arg<RobustArgs>(rk_pack...);
       const double e2 = e[0] * Oe[0] + e[1] * Oe[1] + e[2] * Oe[2];
       const int kind = rk.kind && k < nA ? (int)rk.kind[k] : rk.kind0;     // (the robot graph's received edges: one class)
       const double delta = rk.delta && k < nA ? rk.delta[k] : rk.delta0;
@@ -227,6 +260,20 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
     Jj[3 + q] = -sz * B[q] + cz * B[3 + q];
     Jj[6 + q] = B[6 + q];
   }
+  if constexpr (TYPED) {
+    if (fk != 0) {
+#pragma unroll
+      for (int q = 0; q < 9; q++) { Ji[q] = 0.0; Jj[q] = 0.0; }
+      if (fk == 1) {
+#pragma unroll
+        for (int q = 0; q < 6; q++) { Ji[q] = A[q]; Jj[q] = B[q]; }
+      } else if (fk == 3) {
+        Ji[0] = cz; Ji[1] = sz; Ji[3] = -sz; Ji[4] = cz; Ji[8] = 1.0;
+      } else {
+        Ji[0] = 1.0; Ji[4] = 1.0;
+      }
+    }
+  }
   double JiO[9], JjO[9];   // J^T O
 #pragma unroll
   for (int r = 0; r < 3; r++)
@@ -248,6 +295,9 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
     }
     mine[27 + r] = -(JiO[3 * r] * e[0] + JiO[3 * r + 1] * e[1] + JiO[3 * r + 2] * e[2]);
     mine[30 + r] = -(JjO[3 * r] * e[0] + JjO[3 * r + 1] * e[1] + JjO[3 * r + 2] * e[2]);
+  }
+  if constexpr (TYPED) {
+    if (fk == 1) mine[26] = mine[18] > 0.0 ? mine[18] : 1.0;   // the point's dummy pivot
   }
   if constexpr (ROBUST) {
 #pragma unroll
@@ -357,6 +407,37 @@ template <bool BATCH>
 __global__ __launch_bounds__(256) void k_chi2_reduce(int nP, const double* __restrict__ part, double* __restrict__ out, long long js) {
   CGMR_JOB(part, js); CGMR_JOB(out, js);
   block_chi2_sum(nP, part, out);
+}
+
+// ------------------------------------------------------------------------------ unary terms
+// Priors (edge kinds 3 and 4) are edges from a vertex to itself, which the structure gives no assembly key: their records are
+// added here, behind k_assemble and in front of whatever reads the assembled system (the damping, the factorisation).  One
+// thread per (vertex with priors, scalar of its diagonal block or of its right-hand side): it walks the vertex's priors in edge
+// order (uv_ptr / uv_edge: a CSR the host builds from the edge kinds) and adds the sum of term[edge * 33 + 0..8] to the block
+// where blk_dst points, of term[edge * 33 + 27..29] to bvec and where b_dst points.  Masked columns keep their identity.
+__global__ __launch_bounds__(256) void k_add_unary(int nU, const int32_t* __restrict__ uv_vertex, const int32_t* __restrict__ uv_ptr,
+                                                   const int32_t* __restrict__ uv_edge, const int32_t* __restrict__ vperm,
+                                                   const uint8_t* __restrict__ cmask, const int32_t* __restrict__ blk_dst,
+                                                   const int32_t* __restrict__ b_dst, const double* __restrict__ term,
+                                                   double* __restrict__ Ablk, double* __restrict__ Pan, double* __restrict__ bvec) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nU * 12) return;
+  const int u = t / 12, s = t - 12 * u;
+  const int c = vperm[uv_vertex[u]];
+  if (c < 0 || cmask[c]) return;
+  const int comp = s < 9 ? s : 27 + (s - 9);
+  double acc = 0.0;
+  for (int p = uv_ptr[u]; p < uv_ptr[u + 1]; p++) acc += term[(size_t)uv_edge[p] * 33 + comp];
+  if (s < 9) {
+    const int dst = blk_dst[c];
+    if (dst >= 0) Pan[(size_t)dst + (s / 3) * kPanStride + s % 3] += acc;
+    else Ablk[(size_t)(-dst - 1) * 9 + s] += acc;
+  } else {
+    const int r = s - 9;
+    bvec[3 * (size_t)c + r] += acc;
+    const int dst = b_dst[c];
+    if (dst >= 0) Pan[(size_t)dst + r] += acc;
+  }
 }
 
 // ------------------------------------------------------------------------- front factorise
@@ -1537,6 +1618,23 @@ void launch_linearize(hipStream_t st, const GnDevice& D, const double* poses, co
   gn_init_kernels();
   const dim3 grid((D.nE + 255) / 256, 1, D.njobs);
   const size_t lds = chi_only ? 0 : 256 * 33 * sizeof(double);
+  if (Ed.typed) {                     // (never a batch: the typed entry points run one job)
+    TypedArgs ty;
+    ty.edge_kind = Ed.edge_kind;
+    if (Ed.robust) {
+      RobustArgs rk;
+      rk.kind = Ed.rk_kind; rk.delta = Ed.rk_delta; rk.stats = D.njobs > 1 ? nullptr : Ed.rk_stats; rk.delta0 = Ed.rk_delta0;
+      rk.kind0 = Ed.rk_kind0;
+      hipLaunchKernelGGL((D.njobs > 1 ? k_linearize<true, true, RobustArgs, TypedArgs> : k_linearize<false, true, RobustArgs, TypedArgs>), grid,
+                         dim3(256), lds, st, D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term,
+                         chi_only, D.job_stride, D.pose_stride, rk, ty);
+      return;
+    }
+    hipLaunchKernelGGL((D.njobs > 1 ? k_linearize<true, false, TypedArgs> : k_linearize<false, false, TypedArgs>), grid, dim3(256), lds, st,
+                       D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only,
+                       D.job_stride, D.pose_stride, ty);
+    return;
+  }
   if (Ed.robust) {                    // (a batch takes no statistics: run_cond_jobs never asks for them, the batched instance writes none)
     RobustArgs rk;
     rk.kind = Ed.rk_kind; rk.delta = Ed.rk_delta; rk.stats = D.njobs > 1 ? nullptr : Ed.rk_stats; rk.delta0 = Ed.rk_delta0;
@@ -1561,6 +1659,12 @@ void launch_assemble(hipStream_t st, const GnDevice& D) {
                      D.asm_src, D.blk_dst, D.b_dst, D.cmask, D.off_row, D.off_col, D.term, D.Ablk, D.Pan, D.bvec, D.chi2, D.status, D.nfronts, D.xvec, D.ready, D.job_stride);
 }
 
+void launch_add_unary(hipStream_t st, const GnDevice& D, const GnEdges& Ed) {
+  if (!Ed.typed || Ed.n_unary <= 0 || D.nf == 0) return;
+  hipLaunchKernelGGL(k_add_unary, dim3((Ed.n_unary * 12 + 255) / 256), dim3(256), 0, st, Ed.n_unary, Ed.uv_vertex, Ed.uv_ptr, Ed.uv_edge,
+                     D.vperm, D.cmask, D.blk_dst, D.b_dst, D.term, D.Ablk, D.Pan, D.bvec);
+}
+
 // one-time kernel attributes (dynamic LDS above 64 KB): once per HIP device of the process (the attribute belongs to
 // the device's copy of the function), thread-safe, never inside a stream capture
 void gn_init_kernels() {
@@ -1574,7 +1678,10 @@ void gn_init_kernels() {
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(factor_smem_bytes(kChunkRows + 1), 2 * (int)sizeof(UpdTileLds<kFrontW>)));
     for (const void* f : {reinterpret_cast<const void*>(k_linearize<false, false>), reinterpret_cast<const void*>(k_linearize<true, false>),
                           reinterpret_cast<const void*>(k_linearize<false, true, RobustArgs>),
-                          reinterpret_cast<const void*>(k_linearize<true, true, RobustArgs>)})
+                          reinterpret_cast<const void*>(k_linearize<true, true, RobustArgs>),
+                          reinterpret_cast<const void*>(k_linearize<false, false, TypedArgs>), reinterpret_cast<const void*>(k_linearize<true, false, TypedArgs>),
+                          reinterpret_cast<const void*>(k_linearize<false, true, RobustArgs, TypedArgs>),
+                          reinterpret_cast<const void*>(k_linearize<true, true, RobustArgs, TypedArgs>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 33 * (int)sizeof(double));
     for (const void* f : {reinterpret_cast<const void*>(k_top_block<false>), reinterpret_cast<const void*>(k_top_block<true>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, top_smem_bytes(kTopMaxCols));

@@ -68,7 +68,7 @@ class RobotLaser:
 
 
 class PoseGraph:
-    def __init__(self, ids, poses, fixed, edge_from, edge_to, meas, info, edge_level=None):
+    def __init__(self, ids, poses, fixed, edge_from, edge_to, meas, info, edge_level=None, vertex_kind=None, edge_kind=None):
         self.ids = np.ascontiguousarray(ids, dtype=np.int64)
         self.poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3).copy()
         self.fixed = np.ascontiguousarray(fixed, dtype=np.uint8).copy()
@@ -81,6 +81,55 @@ class PoseGraph:
         self.edge_level = (np.zeros(len(self.edge_from), dtype=np.int32) if edge_level is None
                            else np.ascontiguousarray(edge_level, dtype=np.int32))
         self.lasers = {}          # vertex index -> RobotLaser (user data; written/read as ROBOTLASER1 lines)
+        # typed factors (include/cgmr.h: cgmr_factor_types): per vertex 0 = SE2 pose, 1 = point (VERTEX_XY; its third pose
+        # component stays 0); per edge 0 = EDGE_SE2, 1 = EDGE_SE2_XY, 3 = EDGE_PRIOR_SE2, 4 = EDGE_PRIOR_SE2_XY (priors: from ==
+        # to).  A 2-dimensional factor keeps (zx, zy, 0) and (I11, I12, 0, I22, 0, 0).  None: a pure pose graph, as ever.
+        self.vertex_kind = None if vertex_kind is None else np.ascontiguousarray(vertex_kind, dtype=np.uint8).copy()
+        self.edge_kind = None if edge_kind is None else np.ascontiguousarray(edge_kind, dtype=np.uint8).copy()
+
+    @property
+    def typed(self):
+        """True when some vertex or edge is not of kind 0 (the solver then takes the typed entry points)."""
+        return bool((self.vertex_kind is not None and self.vertex_kind.any()) or
+                    (self.edge_kind is not None and self.edge_kind.any()))
+
+    def kinds(self):
+        """(vertex kinds [nV], edge kinds [nE]) with zeros where none were given."""
+        vk = self.vertex_kind if self.vertex_kind is not None else np.zeros(self.n_vertices, dtype=np.uint8)
+        ek = self.edge_kind if self.edge_kind is not None else np.zeros(self.n_edges, dtype=np.uint8)
+        return vk, ek
+
+    def add_vertex(self, vid, estimate, kind=0, fixed=False):
+        """Append a vertex (``estimate``: (x, y, theta), or (x, y) for a point); returns its index."""
+        est = np.zeros(3)
+        est[:2 if kind == 1 else 3] = np.asarray(estimate, dtype=np.float64).reshape(-1)[:2 if kind == 1 else 3]
+        vk, _ = self.kinds()
+        self.ids = np.append(self.ids, np.int64(vid))
+        self.poses = np.vstack([self.poses, est[None, :]])
+        self.fixed = np.append(self.fixed, np.uint8(1 if fixed else 0))
+        if kind or self.vertex_kind is not None:
+            self.vertex_kind = np.append(vk, np.uint8(kind))
+        return self.n_vertices - 1
+
+    def add_edge(self, i, j, meas, info, kind=0, level=0):
+        """Append an edge between the vertex indices ``i`` and ``j`` (a prior: i == j).  ``meas`` / ``info``: 3 and 6 values, or
+        2 and 3 (I11, I12, I22) for a 2-dimensional factor; returns the edge's index."""
+        m, u = np.zeros(3), np.zeros(6)
+        mv, uv = np.asarray(meas, dtype=np.float64).reshape(-1), np.asarray(info, dtype=np.float64).reshape(-1)
+        if kind in (1, 4):
+            m[:2] = mv[:2]
+            u[[0, 1, 3]] = uv[:3] if uv.size == 3 else uv[[0, 1, 3]]
+        else:
+            m[:], u[:] = mv[:3], uv[:6]
+        _, ek = self.kinds()
+        self.edge_from = np.append(self.edge_from, np.int32(i))
+        self.edge_to = np.append(self.edge_to, np.int32(j))
+        self.meas = np.vstack([self.meas, m[None, :]])
+        self.info = np.vstack([self.info, u[None, :]])
+        self.edge_level = np.append(self.edge_level, np.int32(level))
+        if kind or self.edge_kind is not None:
+            self.edge_kind = np.append(ek, np.uint8(kind))
+        return self.n_edges - 1
 
     @property
     def n_vertices(self):
@@ -101,13 +150,18 @@ class PoseGraph:
 
     # ---------------------------------------------------------------- .g2o text format
     def save_g2o(self, path, precision=None):
-        """VERTEX_SE2 (+ ROBOTLASER1 data) / FIX / EDGE_SE2 lines.  ``precision=None`` reproduces g2o's default
-        ostream precision (6 significant digits, lossy -- SURVEY.md section 5); pass 17 for round trips."""
+        """VERTEX_SE2 (+ ROBOTLASER1 data) / FIX / EDGE_SE2 lines, and for a typed graph VERTEX_XY, EDGE_SE2_XY,
+        EDGE_PRIOR_SE2 and EDGE_PRIOR_SE2_XY.  ``precision=None`` reproduces g2o's default ostream precision (6 significant
+        digits, lossy -- SURVEY.md section 5); pass 17 for round trips."""
         fmt = "%g" if precision is None else f"%.{precision}g"
+        vk, ek = self.kinds()
         with open(path, "w") as f:
             for k in range(self.n_vertices):
                 x, y, t = self.poses[k]
-                f.write(f"VERTEX_SE2 {int(self.ids[k])} {fmt % x} {fmt % y} {fmt % t}\n")
+                if vk[k] == 1:
+                    f.write(f"VERTEX_XY {int(self.ids[k])} {fmt % x} {fmt % y}\n")
+                else:
+                    f.write(f"VERTEX_SE2 {int(self.ids[k])} {fmt % x} {fmt % y} {fmt % t}\n")
                 if k in self.lasers:
                     f.write(self.lasers[k].write(fmt) + "\n")      # saveUserData: the data lines follow their vertex
                 if self.fixed[k]:
@@ -117,13 +171,29 @@ class PoseGraph:
                     continue                      # only level-0 edges are saved by default
                 m = self.meas[k]
                 i = self.info[k]
+                if ek[k] == 1:
+                    f.write("EDGE_SE2_XY %d %d " % (self.ids[self.edge_from[k]], self.ids[self.edge_to[k]])
+                            + " ".join(fmt % v for v in (*m[:2], i[0], i[1], i[3])) + "\n")
+                    continue
+                if ek[k] == 3:
+                    f.write("EDGE_PRIOR_SE2 %d " % self.ids[self.edge_from[k]] + " ".join(fmt % v for v in (*m, *i)) + "\n")
+                    continue
+                if ek[k] == 4:
+                    f.write("EDGE_PRIOR_SE2_XY %d " % self.ids[self.edge_from[k]]
+                            + " ".join(fmt % v for v in (*m[:2], i[0], i[1], i[3])) + "\n")
+                    continue
                 f.write("EDGE_SE2 %d %d " % (self.ids[self.edge_from[k]], self.ids[self.edge_to[k]])
                         + " ".join(fmt % v for v in (*m, *i)) + "\n")
 
     @classmethod
     def load_g2o(cls, path):
         ids, poses, fixed_ids, ef, et, meas, info = [], [], set(), [], [], [], []
+        vkind, ekind = [], []     # typed graphs: VERTEX_XY, EDGE_SE2_XY, EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY
         lasers = {}               # vertex id -> RobotLaser
+
+        def info2(t):             # I11 I12 I22 in the 3x3 upper-triangle layout
+            a, b, c = (float(v) for v in t)
+            return [a, b, 0.0, c, 0.0, 0.0]
         with open(path) as f:
             for line in f:
                 tok = line.split()
@@ -132,6 +202,11 @@ class PoseGraph:
                 if tok[0] == "VERTEX_SE2":
                     ids.append(int(tok[1]))
                     poses.append([float(v) for v in tok[2:5]])
+                    vkind.append(0)
+                elif tok[0] == "VERTEX_XY":
+                    ids.append(int(tok[1]))
+                    poses.append([float(tok[2]), float(tok[3]), 0.0])
+                    vkind.append(1)
                 elif tok[0] == "FIX":
                     fixed_ids.update(int(v) for v in tok[1:])
                 elif tok[0] == "EDGE_SE2":
@@ -139,6 +214,25 @@ class PoseGraph:
                     et.append(int(tok[2]))
                     meas.append([float(v) for v in tok[3:6]])
                     info.append([float(v) for v in tok[6:12]])
+                    ekind.append(0)
+                elif tok[0] == "EDGE_SE2_XY":
+                    ef.append(int(tok[1]))
+                    et.append(int(tok[2]))
+                    meas.append([float(tok[3]), float(tok[4]), 0.0])
+                    info.append(info2(tok[5:8]))
+                    ekind.append(1)
+                elif tok[0] == "EDGE_PRIOR_SE2":
+                    ef.append(int(tok[1]))
+                    et.append(int(tok[1]))
+                    meas.append([float(v) for v in tok[2:5]])
+                    info.append([float(v) for v in tok[5:11]])
+                    ekind.append(3)
+                elif tok[0] == "EDGE_PRIOR_SE2_XY":
+                    ef.append(int(tok[1]))
+                    et.append(int(tok[1]))
+                    meas.append([float(tok[2]), float(tok[3]), 0.0])
+                    info.append(info2(tok[4:7]))
+                    ekind.append(4)
                 elif tok[0] == "ROBOTLASER1" and ids:
                     lasers[ids[-1]] = RobotLaser.read(tok)     # data lines belong to the preceding vertex
         ids = np.asarray(ids, dtype=np.int64)
@@ -150,6 +244,9 @@ class PoseGraph:
         efi = np.array([index[v] for v in ef], dtype=np.int32)
         eti = np.array([index[v] for v in et], dtype=np.int32)
         g = cls(ids, poses, fixed, efi, eti, np.asarray(meas).reshape(-1, 3), np.asarray(info).reshape(-1, 6))
+        if any(vkind) or any(ekind):
+            g.vertex_kind = np.asarray(vkind, dtype=np.uint8)[order]
+            g.edge_kind = np.asarray(ekind, dtype=np.uint8)
         g.lasers = {index[v]: l for v, l in lasers.items()}
         return g
 
@@ -195,7 +292,27 @@ class GraphSLAM:
         ef, et, meas, info = g.level0()
         rk = self._robust_level0()
         self.last_edge_chi2 = self.last_weights = None
-        if self.algorithm == "levenberg":
+        ty = self._typed_level0()
+        if ty is not None:
+            # landmarks / priors: the typed entry points (the same records; e2 and weights behind them with a kernel set)
+            a = (g.poses, g.fixed, ef, et, meas, info, int(nrunnings))
+            kw = dict(vertex_kind=ty[0], edge_kind=ty[1], **({} if rk is None else dict(kind=rk[0], delta=rk[1])))
+            if self.algorithm == "levenberg":
+                out = self.ctx.lm_optimize_typed(*a, **kw, **self.lm_params)
+                rc, poses, chi2, lam, tri, done = out[:6]
+                self.last_lambdas, self.last_trials, self.last_iterations = lam[:done], tri[:done], done
+            elif self.algorithm == "dl":
+                out = self.ctx.dl_optimize_typed(*a, **kw, raise_on_fail=False, **self.dl_params)
+                rc, poses, chi2, dlt, tri, stp, done = out[:7]
+                self.last_deltas, self.last_trials, self.last_steps = dlt[:done], tri[:done], stp[:done]
+                self.last_iterations = done if rc == 0 else 0
+            else:
+                out = self.ctx.gn_optimize_typed(*a, **kw, raise_on_cholesky=False)
+                rc, poses, chi2 = out[:3]
+                self.last_iterations = int(nrunnings) if rc == 0 else CGMR_E_CHOLESKY_BASE - rc
+            if rk is not None:
+                self.last_edge_chi2, self.last_weights = out[-2:]
+        elif self.algorithm == "levenberg":
             if rk is None:
                 rc, poses, chi2, lam, tri, done = self.ctx.lm_optimize(g.poses, g.fixed, ef, et, meas, info, int(nrunnings),
                                                                        **self.lm_params)
@@ -222,6 +339,31 @@ class GraphSLAM:
         g.poses[:] = poses
         self.last_chi2 = chi2
         self.last_status = rc
+
+    # ---------------------------------------------------------------- landmarks and priors (g2o's slam2d types)
+    def _typed_level0(self):
+        """(vertex kinds, kinds of the level-0 edges), or None for a pure pose graph (the plain path)."""
+        g = self.graph
+        if not g.typed:
+            return None
+        vk, ek = g.kinds()
+        return vk, ek[g.edge_level == 0]
+
+    def addLandmark(self, vid, xy, fixed: bool = False) -> int:     # noqa: N802
+        """A VertexPointXY with id ``vid`` at ``xy``; returns its vertex index."""
+        return self.graph.add_vertex(vid, xy, kind=1, fixed=fixed)
+
+    def addObservation(self, pose_idx, landmark_idx, z_xy, info) -> int:     # noqa: N802
+        """An EdgeSE2PointXY: the point seen at ``z_xy`` in the pose's frame; ``info`` = (I11, I12, I22).  Returns the edge index."""
+        return self.graph.add_edge(pose_idx, landmark_idx, z_xy, info, kind=1)
+
+    def addPrior(self, pose_idx, z_xyt, info) -> int:     # noqa: N802
+        """An EdgeSE2Prior on a pose; ``info`` = the 6 upper-triangle values.  Returns the edge index."""
+        return self.graph.add_edge(pose_idx, pose_idx, z_xyt, info, kind=3)
+
+    def addPositionPrior(self, pose_idx, z_xy, info) -> int:     # noqa: N802
+        """An EdgeSE2XYPrior (a GPS / UWB fix) on a pose; ``info`` = (I11, I12, I22).  Returns the edge index."""
+        return self.graph.add_edge(pose_idx, pose_idx, z_xy, info, kind=4)
 
     # ---------------------------------------------------------------- robust kernels (g2o's edge->setRobustKernel)
     def setRobustKernel(self, name, delta: float = 1.0, edges=None) -> None:     # noqa: N802 (g2o spelling)
@@ -255,6 +397,9 @@ class GraphSLAM:
         rk = self._robust_level0()
         if rk is None:
             return self.chi2()
+        ty = self._typed_level0()
+        if ty is not None:
+            return float(self.ctx.gn_optimize_typed(g.poses, g.fixed, ef, et, meas, info, 0, ty[0], ty[1], rk[0], rk[1])[2][0])
         _, _, chi2, _, _ = self.ctx.gn_optimize_robust(g.poses, g.fixed, ef, et, meas, info, 0, *rk)
         return float(chi2[0])
 
@@ -311,6 +456,11 @@ class GraphSLAM:
         g = self.graph
         ef, et, meas, info = g.level0()
         rk = self._robust_level0() if robust else None
+        ty = self._typed_level0()
+        if ty is not None:
+            kw = {} if rk is None else dict(kind=rk[0], delta=rk[1])
+            out = self.ctx.marginals_all_typed(g.poses, g.fixed, ef, et, meas, info, cross, ty[0], ty[1], **kw)
+            return out[:2] if cross else (out if rk is None else out[0])
         if rk is None:
             return self.ctx.marginals_all(g.poses, g.fixed, ef, et, meas, info, cross=cross)
         out = self.ctx.marginals_all_robust(g.poses, g.fixed, ef, et, meas, info, cross, *rk)
@@ -354,6 +504,9 @@ class GraphSLAM:
     def chi2(self) -> float:
         g = self.graph
         ef, et, meas, info = g.level0()
+        ty = self._typed_level0()
+        if ty is not None:
+            return float(self.ctx.gn_optimize_typed(g.poses, g.fixed, ef, et, meas, info, 0, ty[0], ty[1])[2][0])
         _, _, chi2 = self.ctx.gn_optimize(g.poses, g.fixed, ef, et, meas, info, 0)
         return float(chi2[0])
 

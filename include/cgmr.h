@@ -243,6 +243,76 @@ int cgmr_dl_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8
  * factorisations that served an iteration (failed damped ones included). */
 int cgmr_dl_last_stats(const cgmr_ctx* ctx, int64_t out[3]);
 
+/* Typed factors: point landmarks and priors, g2o's slam2d types (present in C ABI version 105 libraries that export these
+ * symbols) [g2o-recalled].  Every vertex still owns three doubles of the pose array and a 3x3 block column of H; every edge
+ * still has meas_xyt [3] and info_upper [6].
+ *   vertex kinds  CGMR_VERTEX_SE2 (0)  a pose (x, y, theta)
+ *                 CGMR_VERTEX_XY  (1)  a point (x, y): its third double is 0.0 on input and exactly 0.0 on output
+ *   edge kinds    CGMR_EDGE_SE2 (0)           EDGE_SE2            pose i -> pose j, as everywhere above
+ *                 CGMR_EDGE_SE2_XY (1)        EDGE_SE2_XY         pose i -> point l: e = R(theta_i)^T (l - t_i) - z           (2)
+ *                 2                           reserved (bearing-only observations): rejected
+ *                 CGMR_EDGE_PRIOR_SE2 (3)     EDGE_PRIOR_SE2      from == to == i: e = (R(z_theta)^T (t_i - z_t),
+ *                                                                 normalize(theta_i - z_theta))                              (3)
+ *                 CGMR_EDGE_PRIOR_SE2_XY (4)  EDGE_PRIOR_SE2_XY   from == to == i: e = t_i - z                               (2)
+ * A 2-dimensional factor reads its first two measurements and the entries I11 I12 I22 (positions 0, 1, 3) of info_upper;
+ * the rest is ignored.  A robust kernel sees e^T Omega e of the factor's own dimension.  CGMR_E_INVALID, with a message that
+ * names the edge and before the device is touched, for: a kind-1 edge whose from is not a pose or whose to is not a point;
+ * a kind-0, 3 or 4 edge that touches a point; a prior with from != to; kind 2 or any kind above 4; a vertex kind above 1.
+ * A prior makes its vertex a live column: a graph with no fixed vertex and one CGMR_EDGE_PRIOR_SE2 is a regular system.
+ * A point's third unknown is carried as a decoupled dummy (pivot = a copy of the block's H_xx, right-hand side 0): its step
+ * is exactly zero, the Levenberg-Marquardt start tau * max |H_jj| and every chi2 are those of the true-dimension system.
+ * types == NULL, a null member, or kinds that are all zero: the plain / robust call, bit for bit (the same launches).  rk is
+ * nullable as in the robust entry points.  vertex_kind / edge_kind are host memory in the _dev variants too (they are
+ * structure, like fixed / from_idx / to_idx).  The typed path adds one small launch per linearisation that has priors;
+ * CGMR_GRAPH capture is not supported on it (as for Levenberg-Marquardt).  Not offered for joint / pairwise marginals,
+ * relative covariances, condensed graphs and the robot graph (cgmr_graph_*).
+ * cgmr_marginals_typed / cgmr_marginals_all_typed: cgmr_marginals_robust / cgmr_marginals_all_robust on the typed H.  A
+ * point's 3x3 block comes back with its third row and column zero; so does the third column of the cross block of a
+ * kind-1 edge (rows: the pose, columns: the point). */
+#define CGMR_VERTEX_SE2 0
+#define CGMR_VERTEX_XY 1
+#define CGMR_EDGE_SE2 0
+#define CGMR_EDGE_SE2_XY 1
+#define CGMR_EDGE_PRIOR_SE2 3
+#define CGMR_EDGE_PRIOR_SE2_XY 4
+typedef struct cgmr_factor_types {
+  const uint8_t* vertex_kind;   /* [nV] host, nullable: every vertex is a pose */
+  const uint8_t* edge_kind;     /* [nE] host, nullable: every edge is an EDGE_SE2 */
+} cgmr_factor_types;
+int cgmr_gn_optimize_typed(cgmr_ctx* ctx, int nV, double* poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                           const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int iters,
+                           double* chi2_out, const cgmr_factor_types* types, const cgmr_robust* rk);
+int cgmr_gn_optimize_typed_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8_t* fixed, int nE,
+                               const int32_t* from_idx, const int32_t* to_idx, const double* d_meas_xyt,
+                               const double* d_info_upper, int iters, double* chi2_out, const cgmr_factor_types* types,
+                               const cgmr_robust* rk);
+int cgmr_lm_optimize_typed(cgmr_ctx* ctx, int nV, double* poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                           const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int iters,
+                           const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
+                           int32_t* iters_done, const cgmr_factor_types* types, const cgmr_robust* rk);
+int cgmr_lm_optimize_typed_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8_t* fixed, int nE,
+                               const int32_t* from_idx, const int32_t* to_idx, const double* d_meas_xyt,
+                               const double* d_info_upper, int iters, const cgmr_lm_params* params, double* chi2_out,
+                               double* lambda_out, int32_t* trials_out, int32_t* iters_done,
+                               const cgmr_factor_types* types, const cgmr_robust* rk);
+int cgmr_dl_optimize_typed(cgmr_ctx* ctx, int nV, double* poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                           const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int iters,
+                           const cgmr_dl_params* params, double* chi2_out, double* delta_out, int32_t* trials_out,
+                           int32_t* step_out, int32_t* iters_done, const cgmr_factor_types* types, const cgmr_robust* rk);
+int cgmr_dl_optimize_typed_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8_t* fixed, int nE,
+                               const int32_t* from_idx, const int32_t* to_idx, const double* d_meas_xyt,
+                               const double* d_info_upper, int iters, const cgmr_dl_params* params, double* chi2_out,
+                               double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
+                               const cgmr_factor_types* types, const cgmr_robust* rk);
+int cgmr_marginals_typed(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                         const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt, const double* info_upper,
+                         int nK, const int32_t* query_idx, double* cov_out, const cgmr_factor_types* types,
+                         const cgmr_robust* rk);
+int cgmr_marginals_all_typed(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                             const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt,
+                             const double* info_upper, double* cov_out, double* cross_out,
+                             const cgmr_factor_types* types, const cgmr_robust* rk);
+
 /* The ordering + symbolic analysis + structure upload of the last analysed edge list stay on the context and are
  * reused by every later call (cgmr_gn_optimize*, cgmr_marginals, cgmr_covariance_estimate, cgmr_condense*) whose
  * (nV, from_idx, to_idx) are exactly the same -- the fixed flags are applied numerically and do not enter the

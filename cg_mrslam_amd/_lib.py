@@ -45,6 +45,7 @@ _SYMBOLS = [
     "cgmr_match_polish_batch", "cgmr_scan_matching_lc_polished_batch", "cgmr_scan_matching_lc_polished",
     "cgmr_global_matching_polished_batch", "cgmr_global_matching_polished",
     "cgmr_marginals_joint", "cgmr_marginals_pairs", "cgmr_relative_covariance",
+    "cgmr_marginals_joint_typed", "cgmr_marginals_pairs_typed", "cgmr_observation_covariance",
 ]
 
 JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)
@@ -144,9 +145,9 @@ class FactorTypes(C.Structure):
     _fields_ = [("vertex_kind", C.c_void_p), ("edge_kind", C.c_void_p)]
 
 
-# include/cgmr.h: CGMR_VERTEX_* / CGMR_EDGE_* (kind 2 is reserved)
+# include/cgmr.h: CGMR_VERTEX_* / CGMR_EDGE_*
 VERTEX_SE2, VERTEX_XY = 0, 1
-EDGE_SE2, EDGE_SE2_XY, EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY = 0, 1, 3, 4
+EDGE_SE2, EDGE_SE2_XY, EDGE_BEARING_SE2_XY, EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY = 0, 1, 2, 3, 4
 
 
 def factor_types(vertex_kind, edge_kind, nV, nE):
@@ -395,7 +396,7 @@ class Context:
 
     # ------------------------------------------------------------------ typed factors (landmarks, priors)
     # include/cgmr.h: cgmr_factor_types.  ``vertex_kind`` [nV] (0 pose, 1 point) and ``edge_kind`` [nE] (0 EDGE_SE2, 1 EDGE_SE2_XY,
-    # 3 EDGE_PRIOR_SE2, 4 EDGE_PRIOR_SE2_XY; a prior has from == to), None = all zero; ``kind`` / ``delta``: robust kernels as
+    # 2 EDGE_BEARING_SE2_XY, 3 EDGE_PRIOR_SE2, 4 EDGE_PRIOR_SE2_XY; a prior has from == to), None = all zero; ``kind`` / ``delta``: robust kernels as
     # gn_optimize_robust takes them, None = the plain call.  Each returns what its untyped call does, with (e2, weights) appended
     # when ``kind`` is given.
     def _typed(self, entry, problem, iters, vertex_kind, edge_kind, kind, delta, prm=None, n_int=None, allow_fail=False):
@@ -594,12 +595,20 @@ class Context:
 
     # joint and pairwise blocks of H^-1, relative-pose uncertainty (include/cgmr.h: cgmr_marginals_joint ...).  ``kind`` None: the
     # plain call; otherwise robust kernels as marginals_robust takes them, and (e2 [nE], weights [nE]) are appended.
-    def _joint_call(self, entry, poses, fixed, ef, et, meas, info, tail, kind, delta):
+    # ``vertex_kind`` / ``edge_kind`` (either given): the typed entry point (cgmr_marginals_joint_typed ...), kinds as for
+    # gn_optimize_typed; a point's third row and column come back exactly zero.
+    def _joint_call(self, entry, poses, fixed, ef, et, meas, info, tail, kind, delta, vertex_kind=None, edge_kind=None, typed=False):
         poses, ef, et, meas, info = self._graph_args(poses, ef, et, meas, info)
         fixed = np.ascontiguousarray(fixed, dtype=np.uint8)
         rk, e2, w, _keep = self._robust(kind, delta, len(ef)) if kind is not None else (None, None, None, None)
+        types = ()
+        if typed or vertex_kind is not None or edge_kind is not None:
+            ft, _keep_ft = factor_types(vertex_kind, edge_kind, poses.shape[0], len(ef))
+            types = (C.byref(ft),)
+            if not typed:
+                entry += "_typed"
         rc = getattr(self.lib, entry)(self.h, C.c_int(poses.shape[0]), _ptr(poses), _ptr(fixed), C.c_int(len(ef)), _ptr(ef), _ptr(et),
-                                      _ptr(meas), _ptr(info), *tail, C.byref(rk) if rk is not None else C.c_void_p(0))
+                                      _ptr(meas), _ptr(info), *tail, *types, C.byref(rk) if rk is not None else C.c_void_p(0))
         self._check(rc)
         return () if kind is None else (e2, w)
 
@@ -611,22 +620,23 @@ class Context:
             raise ValueError(f"pairs: {a.shape[0]} first vertices, {b.shape[0]} second vertices")
         return a, b
 
-    def marginals_joint(self, poses, fixed, ef, et, meas, info, query, kind=None, delta=1.0):
+    def marginals_joint(self, poses, fixed, ef, et, meas, info, query, kind=None, delta=1.0, vertex_kind=None, edge_kind=None):
         """The joint covariance of the query vertices, ``[3 nK, 3 nK]`` in query order (block (k, l) = Sigma of query[k],
         query[l]); exactly symmetric, zeros for fixed / inactive vertices.  At most JOINT_MAX_QUERIES unique vertices."""
         query = np.ascontiguousarray(query, dtype=np.int32).reshape(-1)
         cov = np.zeros((3 * len(query), 3 * len(query)))
         st = self._joint_call("cgmr_marginals_joint", poses, fixed, ef, et, meas, info,
-                              (C.c_int(len(query)), _ptr(query), _ptr(cov)), kind, delta)
+                              (C.c_int(len(query)), _ptr(query), _ptr(cov)), kind, delta, vertex_kind, edge_kind)
         return (cov,) + st if st else cov
 
-    def marginals_pairs(self, poses, fixed, ef, et, meas, info, pair_a, pair_b, kind=None, delta=1.0):
+    def marginals_pairs(self, poses, fixed, ef, et, meas, info, pair_a, pair_b, kind=None, delta=1.0, vertex_kind=None,
+                        edge_kind=None):
         """(Sigma_aa, Sigma_ab, Sigma_bb), each ``[nP, 3, 3]``, for the vertex pairs (pair_a[p], pair_b[p]) -- any two vertices,
         not only a graph edge's; rows of Sigma_ab index a."""
         a, b = self._pair_arrays(pair_a, pair_b)
         aa, ab, bb = (np.zeros((len(a), 3, 3)) for _ in range(3))
         st = self._joint_call("cgmr_marginals_pairs", poses, fixed, ef, et, meas, info,
-                              (C.c_int(len(a)), _ptr(a), _ptr(b), _ptr(aa), _ptr(ab), _ptr(bb)), kind, delta)
+                              (C.c_int(len(a)), _ptr(a), _ptr(b), _ptr(aa), _ptr(ab), _ptr(bb)), kind, delta, vertex_kind, edge_kind)
         return (aa, ab, bb) + st
 
     def relative_covariance(self, poses, fixed, ef, et, meas, info, pair_a, pair_b, hyp_meas=None, hyp_info=None, kind=None,
@@ -647,6 +657,32 @@ class Context:
         z, cz = np.zeros((n, 3)), np.zeros((n, 3, 3))
         st = self._joint_call("cgmr_relative_covariance", poses, fixed, ef, et, meas, info,
                               (C.c_int(n), _ptr(a), _ptr(b), _ptr(z), _ptr(cz), _ptr(hm), _ptr(hi), _ptr(d2)), kind, delta)
+        return (z, cz, d2) + st
+
+    def observation_covariance(self, poses, fixed, ef, et, meas, info, pair_a, pair_b, obs_kind=None, hyp_meas=None, hyp_info=None,
+                               vertex_kind=None, edge_kind=None, kind=None, delta=1.0):
+        """Data association (cgmr_observation_covariance): pair p predicted as a factor of kind ``obs_kind[p]`` -- 0 pose-pose
+        (relative_covariance), 1 EDGE_SE2_XY, 2 EDGE_BEARING_SE2_XY, from pose pair_a[p] to pair_b[p]; None: all 0.  Returns
+        (z [nP, 3], S [nP, 3, 3], d2 [nP] or None), padded with zeros outside the factor's dimension; ``hyp_meas`` [nP, 3] /
+        ``hyp_info`` [nP, 6] as for relative_covariance, read in the factor's dimension (a bearing: hyp_meas[:, 0] and
+        hyp_info[:, 0]).  ``kind`` / ``delta``: robust kernels, (e2, weights) appended."""
+        a, b = self._pair_arrays(pair_a, pair_b)
+        n = len(a)
+        ok = None if obs_kind is None else np.ascontiguousarray(obs_kind, dtype=np.uint8).reshape(-1)
+        if ok is not None and ok.shape != (n,):
+            raise ValueError(f"observation kinds: {ok.shape[0]} given for {n} pairs")
+        hm = hi = d2 = None
+        if hyp_meas is not None:
+            hm = np.ascontiguousarray(hyp_meas, dtype=np.float64).reshape(n, 3)
+            d2 = np.zeros(n)
+        if hyp_info is not None:
+            if hm is None:
+                raise ValueError("hyp_info needs hyp_meas")
+            hi = np.ascontiguousarray(hyp_info, dtype=np.float64).reshape(n, 6)
+        z, cz = np.zeros((n, 3)), np.zeros((n, 3, 3))
+        st = self._joint_call("cgmr_observation_covariance", poses, fixed, ef, et, meas, info,
+                              (C.c_int(n), _ptr(a), _ptr(b), _ptr(ok), _ptr(z), _ptr(cz), _ptr(hm), _ptr(hi), _ptr(d2)), kind, delta,
+                              vertex_kind, edge_kind, typed=True)
         return (z, cz, d2) + st
 
     def set_symbolic_cache(self, on: bool):

@@ -1142,14 +1142,13 @@ static int typed_check(cgmr_ctx* ctx, const char* who, const cgmr_factor_types* 
   for (int k = 0; k < nE; k++) {
     const int kind = T.ek[k], a = ef[k], b = et[k];
     if (a < 0 || a >= nV || b < 0 || b >= nV) return set_err(ctx, CGMR_E_INVALID, "%s: edge %d has a vertex index out of range", who, k);
-    if (kind == 2) return set_err(ctx, CGMR_E_INVALID, "%s: edge %d has kind 2 (bearing-only observations are reserved, not implemented)", who, k);
     if (kind > 4) return set_err(ctx, CGMR_E_INVALID, "%s: edge %d has unknown kind %d", who, k, kind);
-    if (kind == 1) {
+    if (kind == 1 || kind == 2) {
       if (T.vk[a] != 0 || T.vk[b] != 1)
-        return set_err(ctx, CGMR_E_INVALID, "%s: edge %d (EDGE_SE2_XY) must go from a pose to a point", who, k);
+        return set_err(ctx, CGMR_E_INVALID, "%s: edge %d (%s) must go from a pose to a point", who, k, kind == 1 ? "EDGE_SE2_XY" : "EDGE_BEARING_SE2_XY");
     } else {
       if (T.vk[a] != 0 || T.vk[b] != 0)
-        return set_err(ctx, CGMR_E_INVALID, "%s: edge %d (kind %d) touches a point; only EDGE_SE2_XY may", who, k, kind);
+        return set_err(ctx, CGMR_E_INVALID, "%s: edge %d (kind %d) touches a point; only EDGE_SE2_XY and EDGE_BEARING_SE2_XY may", who, k, kind);
       if (kind >= 3) {
         if (a != b) return set_err(ctx, CGMR_E_INVALID, "%s: edge %d is a prior (kind %d) and must have from == to", who, k, kind);
         cnt[a + 1]++;
@@ -1448,23 +1447,40 @@ int marginals_all_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8
   return rc;
 }
 
-// Shared driver of cgmr_marginals_joint / cgmr_marginals_pairs / cgmr_relative_covariance: the pass of marginal_driver's mode 0
+// Shared driver of cgmr_marginals_joint / cgmr_marginals_pairs / cgmr_relative_covariance, their typed forms and
+// cgmr_observation_covariance (`who`): the pass of marginal_driver's mode 0
 // (gn_pass at `poses` with `fixed`), the solve half of launch_marginals for the unique vertices asked for, then the tiles of
 // Y^T Y that hold a requested block (joint_marginals_kernels.hip).
 //   mode 0: joint -- va = the nK queries, out_a = cov [(3 nK)^2]
 //   mode 1: pairs -- (va, vb) the nP pairs, out_a / out_b / out_c = aa / ab / bb (nullable)
-//   mode 2: relative covariance -- the pairs' blocks stay on the device; out_a / out_b / out_c = rel_xyt / rel_cov / d2 (nullable)
-int joint_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+//   mode 2: relative covariance -- the pairs' blocks stay on the device; out_a / out_b / out_c = rel_xyt / rel_cov / d2 (nullable);
+//           obs: cgmr_observation_covariance, pair p predicted as a factor of kind obs_kind[p] (null: all 0).  The pairs of
+//           kind 0 are k_relative_cov's (it runs over the whole list when there is one), the others k_observation_cov's behind it.
+// ft: the factor types (typed_check before the device is touched; a point's dummy third row / column comes back zero).
+int joint_driver(cgmr_ctx* ctx, const char* who, int mode, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
                  const int32_t* et, const double* meas, const double* info, int nQ, const int32_t* va, const int32_t* vb,
                  double* out_a, double* out_b, double* out_c, const double* hyp_meas, const double* hyp_info,
-                 const cgmr_robust* rk) {
-  const char* who = mode == 0 ? "cgmr_marginals_joint" : mode == 1 ? "cgmr_marginals_pairs" : "cgmr_relative_covariance";
+                 const cgmr_robust* rk, const cgmr_factor_types* ft = nullptr, bool obs = false, const uint8_t* obs_kind = nullptr) {
   if (nV <= 0 || nE < 0 || nQ < 0 || !poses || !fixed || (nE > 0 && (!ef || !et || !meas || !info)) ||
       (nQ > 0 && (!va || (mode != 0 && !vb))) || (mode == 0 && nQ > 0 && !out_a) || (mode == 2 && ((out_c && !hyp_meas) || (hyp_info && !hyp_meas))))
     return set_err(ctx, CGMR_E_INVALID, "%s: null or negative argument", who);
   for (int k = 0; k < nQ; k++)
     if (va[k] < 0 || va[k] >= nV || (mode != 0 && (vb[k] < 0 || vb[k] >= nV)))
       return set_err(ctx, CGMR_E_INVALID, "%s: vertex index out of range", who);
+  TypedHost typed;
+  int rc = typed_check(ctx, who, ft, nV, nE, ef, et, typed);
+  if (rc) return rc;
+  bool obs_typed = false, obs_pose = !obs;                        // some pair is a landmark observation / a relative pose
+  if (obs)
+    for (int k = 0; k < nQ; k++) {
+      const int kind = obs_kind ? obs_kind[k] : 0;
+      const bool a_pt = ft && !typed.vk.empty() && typed.vk[va[k]], b_pt = ft && !typed.vk.empty() && typed.vk[vb[k]];
+      if (kind > 2) return set_err(ctx, CGMR_E_INVALID, "%s: pair %d has observation kind %d (0, 1 or 2)", who, k, kind);
+      if (a_pt) return set_err(ctx, CGMR_E_INVALID, "%s: pair %d is observed from vertex %d, a point", who, k, va[k]);
+      if (kind == 0 && b_pt) return set_err(ctx, CGMR_E_INVALID, "%s: pair %d of kind 0 (EDGE_SE2) ends at vertex %d, a point", who, k, vb[k]);
+      if (kind != 0 && !b_pt) return set_err(ctx, CGMR_E_INVALID, "%s: pair %d of kind %d ends at vertex %d, a pose", who, k, kind, vb[k]);
+      if (kind) obs_typed = true; else obs_pose = true;
+    }
   if (nQ == 0) return CGMR_OK;
   // the unique vertices, in order of first appearance: 4 columns of Y each
   std::vector<int32_t> slot_of(nV, -1), uq;
@@ -1474,7 +1490,7 @@ int joint_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uin
   if (nU > CGMR_JOINT_MAX_QUERIES)
     return set_err(ctx, CGMR_E_INVALID, "%s: %d unique query vertices, at most CGMR_JOINT_MAX_QUERIES = %d", who, nU, CGMR_JOINT_MAX_QUERIES);
   MargCall call(ctx, nV, poses, nE, rk);
-  int rc = call.open(who);
+  rc = call.open(who, &typed);
   if (rc) return rc;
   rc = call.structure(fixed, ef, et);
   if (rc) return rc;
@@ -1534,7 +1550,7 @@ int joint_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uin
                o_a = L.add(mode == 0 ? 72 * nq * nq : 72 * nq), o_b = L.add(mode == 0 ? 0 : 72 * nq), o_c = L.add(mode == 0 ? 0 : 72 * nq),
                o_va = L.add(mode == 2 ? 4 * nq : 0), o_vb = L.add(mode == 2 ? 4 * nq : 0), o_hm = L.add(mode == 2 && hyp_meas ? 24 * nq : 0),
                o_hi = L.add(mode == 2 && hyp_info ? 48 * nq : 0), o_rz = L.add(mode == 2 ? 24 * nq : 0), o_rc = L.add(mode == 2 ? 72 * nq : 0),
-               o_d2 = L.add(mode == 2 ? 8 * nq : 0);
+               o_d2 = L.add(mode == 2 ? 8 * nq : 0), o_ok = L.add(obs_typed ? nq : 0);
   rc = call.stage(meas, info);
   if (rc) return rc;
   char* d = call.d;
@@ -1546,6 +1562,7 @@ int joint_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uin
     HIP_TRY(ctx, hipMemcpyAsync(d + o_vb, vb, 4 * nq, hipMemcpyHostToDevice, st));
     if (hyp_meas) HIP_TRY(ctx, hipMemcpyAsync(d + o_hm, hyp_meas, 24 * nq, hipMemcpyHostToDevice, st));
     if (hyp_info) HIP_TRY(ctx, hipMemcpyAsync(d + o_hi, hyp_info, 48 * nq, hipMemcpyHostToDevice, st));
+    if (obs_typed) HIP_TRY(ctx, hipMemcpyAsync(d + o_ok, obs_kind, nq, hipMemcpyHostToDevice, st));
   }
   JG.tiles = mode == 0 ? nullptr : (const int32_t*)(d + o_tl);
   JG.part = (double*)(d + o_part);
@@ -1571,11 +1588,17 @@ int joint_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uin
       if (out_b) HIP_TRY(ctx, hipMemcpyAsync(out_b, d + o_b, b_b, hipMemcpyDeviceToHost, st));
       if (out_c) HIP_TRY(ctx, hipMemcpyAsync(out_c, d + o_c, b_c, hipMemcpyDeviceToHost, st));
     }
-    if (mode == 2) {
+    if (mode == 2 && obs_pose)
       launch_relative_cov(st, nQ, (const int32_t*)(d + o_va), (const int32_t*)(d + o_vb), call.dp, (const double*)(d + o_a),
                           (const double*)(d + o_b), (const double*)(d + o_c), hyp_meas ? (const double*)(d + o_hm) : nullptr,
                           hyp_info ? (const double*)(d + o_hi) : nullptr, (double*)(d + o_rz), (double*)(d + o_rc),
                           want_d2 ? (double*)(d + o_d2) : nullptr);
+    if (mode == 2 && obs_typed)
+      launch_observation_cov(st, nQ, (const int32_t*)(d + o_va), (const int32_t*)(d + o_vb), (const uint8_t*)(d + o_ok), call.dp,
+                             (const double*)(d + o_a), (const double*)(d + o_b), (const double*)(d + o_c),
+                             hyp_meas ? (const double*)(d + o_hm) : nullptr, hyp_info ? (const double*)(d + o_hi) : nullptr,
+                             (double*)(d + o_rz), (double*)(d + o_rc), want_d2 ? (double*)(d + o_d2) : nullptr);
+    if (mode == 2) {
       if (out_a) HIP_TRY(ctx, hipMemcpyAsync(out_a, d + o_rz, b_a, hipMemcpyDeviceToHost, st));
       if (out_b) HIP_TRY(ctx, hipMemcpyAsync(out_b, d + o_rc, b_b, hipMemcpyDeviceToHost, st));
       if (want_d2) HIP_TRY(ctx, hipMemcpyAsync(out_c, d + o_d2, b_c, hipMemcpyDeviceToHost, st));
@@ -1585,6 +1608,19 @@ int joint_driver(cgmr_ctx* ctx, int mode, int nV, const double* poses, const uin
   if (rc) return rc;
   rc = call.close();
   if (rc == CGMR_E_CHOLESKY_BASE) zero_outputs();
+  if (rc == CGMR_OK && typed.any && mode == 0) {                  // the points' dummy unknowns: rows and columns 3 k + 2
+    const size_t N = 3 * nq;
+    for (int k = 0; k < nQ; k++)
+      if (typed.vk[va[k]])
+        for (size_t q = 0; q < N; q++) out_a[(3 * (size_t)k + 2) * N + q] = out_a[q * N + 3 * (size_t)k + 2] = 0.0;
+  }
+  if (rc == CGMR_OK && typed.any && mode == 1)
+    for (int k = 0; k < nQ; k++) {
+      const bool pa = typed.vk[va[k]] != 0, pb = typed.vk[vb[k]] != 0;
+      if (out_a) zero_point_dims(out_a + 9 * (size_t)k, pa, pa);
+      if (out_b) zero_point_dims(out_b + 9 * (size_t)k, pa, pb);
+      if (out_c) zero_point_dims(out_c + 9 * (size_t)k, pb, pb);
+    }
   return rc;
 }
 
@@ -1690,7 +1726,7 @@ using namespace cgmr;
 
 extern "C" {
 
-int cgmr_version(void) { return 105; }   // 105: cgmr_*_optimize_robust*, cgmr_graph_set_edge_robust / _set_received_robust / _edge_stats added, later (same number: callers find them by their symbols) cgmr_marginals_robust, cgmr_marginals_all_robust, cgmr_covariance_estimate_robust, cgmr_condense_robust, cgmr_graph_set_condensed_robust, cgmr_dl_optimize*, cgmr_dl_last_stats, cgmr_graph_set_dogleg_params, cgmr_graph_dl_last (CGMR_ALG_DOGLEG), cgmr_marginals_joint, cgmr_marginals_pairs, cgmr_relative_covariance, cgmr_*_optimize_typed*, cgmr_marginals_typed, cgmr_marginals_all_typed; 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
+int cgmr_version(void) { return 105; }   // 105: cgmr_*_optimize_robust*, cgmr_graph_set_edge_robust / _set_received_robust / _edge_stats added, later (same number: callers find them by their symbols) cgmr_marginals_robust, cgmr_marginals_all_robust, cgmr_covariance_estimate_robust, cgmr_condense_robust, cgmr_graph_set_condensed_robust, cgmr_dl_optimize*, cgmr_dl_last_stats, cgmr_graph_set_dogleg_params, cgmr_graph_dl_last (CGMR_ALG_DOGLEG), cgmr_marginals_joint, cgmr_marginals_pairs, cgmr_relative_covariance, cgmr_*_optimize_typed*, cgmr_marginals_typed, cgmr_marginals_all_typed, cgmr_marginals_joint_typed, cgmr_marginals_pairs_typed, cgmr_observation_covariance (and edge kind 2, CGMR_EDGE_BEARING_SE2_XY); 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
 
 int cgmr_ctx_create(int device, void* hip_stream, cgmr_ctx** out) {
   if (!out) return CGMR_E_INVALID;
@@ -2007,14 +2043,14 @@ int cgmr_marginals_joint(cgmr_ctx* ctx, int nV, const double* poses, const uint8
                          const int32_t* et, const double* meas, const double* info, int nK, const int32_t* query, double* cov_out,
                          const cgmr_robust* rk) {
   if (!ctx) return CGMR_E_INVALID;
-  return joint_driver(ctx, 0, nV, poses, fixed, nE, ef, et, meas, info, nK, query, nullptr, cov_out, nullptr, nullptr, nullptr, nullptr, rk);
+  return joint_driver(ctx, "cgmr_marginals_joint", 0, nV, poses, fixed, nE, ef, et, meas, info, nK, query, nullptr, cov_out, nullptr, nullptr, nullptr, nullptr, rk);
 }
 
 int cgmr_marginals_pairs(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
                          const int32_t* et, const double* meas, const double* info, int nP, const int32_t* pair_a,
                          const int32_t* pair_b, double* cov_aa_out, double* cov_ab_out, double* cov_bb_out, const cgmr_robust* rk) {
   if (!ctx) return CGMR_E_INVALID;
-  return joint_driver(ctx, 1, nV, poses, fixed, nE, ef, et, meas, info, nP, pair_a, pair_b, cov_aa_out, cov_ab_out, cov_bb_out, nullptr,
+  return joint_driver(ctx, "cgmr_marginals_pairs", 1, nV, poses, fixed, nE, ef, et, meas, info, nP, pair_a, pair_b, cov_aa_out, cov_ab_out, cov_bb_out, nullptr,
                       nullptr, rk);
 }
 
@@ -2023,8 +2059,35 @@ int cgmr_relative_covariance(cgmr_ctx* ctx, int nV, const double* poses, const u
                              const int32_t* pair_b, double* rel_xyt_out, double* rel_cov_out, const double* hyp_meas,
                              const double* hyp_info, double* d2_out, const cgmr_robust* rk) {
   if (!ctx) return CGMR_E_INVALID;
-  return joint_driver(ctx, 2, nV, poses, fixed, nE, ef, et, meas, info, nP, pair_a, pair_b, rel_xyt_out, rel_cov_out, d2_out, hyp_meas,
+  return joint_driver(ctx, "cgmr_relative_covariance", 2, nV, poses, fixed, nE, ef, et, meas, info, nP, pair_a, pair_b, rel_xyt_out, rel_cov_out, d2_out, hyp_meas,
                       hyp_info, rk);
+}
+
+int cgmr_marginals_joint_typed(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                               const int32_t* et, const double* meas, const double* info, int nK, const int32_t* query,
+                               double* cov_out, const cgmr_factor_types* types, const cgmr_robust* rk) {
+  if (!ctx) return CGMR_E_INVALID;
+  return joint_driver(ctx, "cgmr_marginals_joint_typed", 0, nV, poses, fixed, nE, ef, et, meas, info, nK, query, nullptr, cov_out, nullptr,
+                      nullptr, nullptr, nullptr, rk, types);
+}
+
+int cgmr_marginals_pairs_typed(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                               const int32_t* et, const double* meas, const double* info, int nP, const int32_t* pair_a,
+                               const int32_t* pair_b, double* cov_aa_out, double* cov_ab_out, double* cov_bb_out,
+                               const cgmr_factor_types* types, const cgmr_robust* rk) {
+  if (!ctx) return CGMR_E_INVALID;
+  return joint_driver(ctx, "cgmr_marginals_pairs_typed", 1, nV, poses, fixed, nE, ef, et, meas, info, nP, pair_a, pair_b, cov_aa_out,
+                      cov_ab_out, cov_bb_out, nullptr, nullptr, rk, types);
+}
+
+int cgmr_observation_covariance(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                                const int32_t* et, const double* meas, const double* info, int nP, const int32_t* pair_a,
+                                const int32_t* pair_b, const uint8_t* obs_kind, double* z_out, double* cov_out,
+                                const double* hyp_meas, const double* hyp_info, double* d2_out, const cgmr_factor_types* types,
+                                const cgmr_robust* rk) {
+  if (!ctx) return CGMR_E_INVALID;
+  return joint_driver(ctx, "cgmr_observation_covariance", 2, nV, poses, fixed, nE, ef, et, meas, info, nP, pair_a, pair_b, z_out, cov_out,
+                      d2_out, hyp_meas, hyp_info, rk, types, true, obs_kind);
 }
 
 int cgmr_set_symbolic_cache(cgmr_ctx* ctx, int on) {

@@ -147,6 +147,11 @@ void launch_pairs_extract(hipStream_t st, int nP, const int32_t* pr, const doubl
 void launch_relative_cov(hipStream_t st, int nP, const int32_t* pa, const int32_t* pb, const double* poses, const double* aa,
                          const double* ab, const double* bb, const double* hyp_meas, const double* hyp_info, double* rel,
                          double* rel_cov, double* d2);
+// the same per pair of kind[p] = 0; kind 1 / 2: the predicted EDGE_SE2_XY / EDGE_BEARING_SE2_XY observation of point b from pose
+// a, its covariance and d2 in the factor's own dimension, padded with zeros (cgmr_observation_covariance)
+void launch_observation_cov(hipStream_t st, int nP, const int32_t* pa, const int32_t* pb, const uint8_t* kind, const double* poses,
+                            const double* aa, const double* ab, const double* bb, const double* hyp_meas, const double* hyp_info,
+                            double* z, double* cov, double* d2);
 // selinv_kernels.hip: all-pose marginals by selected inversion of the factor in D.Lbuf (gn_pass(.., write_l11c) followed by
 // launch_invert_fronts(.., top_too)).  Sig: every front's dense (w + r)^2 block of H^-1 at soff[front] doubles;
 // tiles: (front, first border row) pairs of every front with a border, level by level, kSelinvTileRows rows each, the

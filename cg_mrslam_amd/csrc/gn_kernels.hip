@@ -158,6 +158,7 @@ __device__ __forceinline__ double robustify(int kind, double delta, double e2, d
 // TYPED (g2o's slam2d factor types, include/cgmr.h: cgmr_factor_types): edge k < nA is of kind edge_kind[k] --
 //   0  EDGE_SE2           as above
 //   1  EDGE_SE2_XY        pose i sees point l:  e = R(th_i)^T (l - t_i) - z (2)
+//   2  EDGE_BEARING_SE2_XY  pose i sees point l: e = normalize(atan2(ry, rx) - z0) (1), (rx, ry) = R(th_i)^T (l - t_i)
 //   3  EDGE_PRIOR_SE2     unary (i == j):       e = (R(z_th)^T (t_i - z_t), normalize(th_i - z_th))
 //   4  EDGE_PRIOR_SE2_XY  unary (i == j):       e = t_i - z (2)
 // A 2-dimensional factor takes z0, z1 and the entries (0,0) (0,1) (1,1) of its information; its third error component and the
@@ -165,7 +166,12 @@ __device__ __forceinline__ double robustify(int kind, double delta, double e2, d
 // record keeps its layout.  A point owns a 3x3 block column like a pose: a kind-1 edge leaves the third row / column of Hjj
 // and the third column of Hij zero except for Hjj(2,2), a copy of Hjj(0,0) (1.0 when that is not positive): the dummy unknown
 // decouples with a positive pivot and a zero right-hand side, its dx is exactly zero, and its diagonal never exceeds a real one
-// of the same block (k_lm_init's max |H_jj| is the true-dimension system's).  A prior's record holds Hii and bi; the structure
+// of the same block (k_lm_init's max |H_jj| is the true-dimension system's).  A bearing reads z0 and the entry (0,0) of its
+// information; its Jacobians are the row (-ry / q) J1[0] + (rx / q) J1[1] of the kind-1 Jacobians J1, q = rx^2 + ry^2 (the heading's
+// entry is -1), zero with the point on the pose.  Its Hjj(2,2) is the copy of Hjj(0,0) with no fall-back to 1.0: a bearing along
+// the world's x axis has Hjj(0,0) = 0 exactly, and a 1.0 there would exceed the point's real diagonal entries and raise
+// Levenberg's tau * max |H_jj|; summed over the point's edges the dummy is the block's H_xx, positive whenever the point's 2x2
+// block is positive definite.  A prior's record holds Hii and bi; the structure
 // gives a self edge no assembly key, k_add_unary adds the record behind k_assemble.  The kinds are a third kind of trailing
 // argument: the plain and the robust instances keep their names and their code.
 struct TypedArgs {
@@ -208,11 +214,14 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
   if constexpr (TYPED) {
     fk = k < nA ? (int)pick_arg<TypedArgs>(rk_pack...).edge_kind[k] : 0;
     if (fk == 1) { e[0] = tx; e[1] = ty; e[2] = 0.0; }
-    else if (fk == 3) {
+    else if (fk == 2) {
+      e[0] = d_normalize_theta((rx * rx + ry * ry > 0.0 ? atan2(ry, rx) : 0.0) - z0); e[1] = 0.0; e[2] = 0.0;
+    } else if (fk == 3) {
       const double px = xi0 - z0, py = xi1 - z1;
       e[0] = cz * px + sz * py; e[1] = -sz * px + cz * py; e[2] = d_normalize_theta(xi2 - z2);
     } else if (fk == 4) { e[0] = xi0 - z0; e[1] = xi1 - z1; e[2] = 0.0; }
     if (fk == 1 || fk == 4) { O[2] = O[5] = O[6] = O[7] = O[8] = 0.0; }
+    if (fk == 2) { O[1] = O[2] = O[3] = O[4] = O[5] = O[6] = O[7] = O[8] = 0.0; }
   }
   double Oe[3];
 #pragma unroll
@@ -267,6 +276,14 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
       if (fk == 1) {
 #pragma unroll
         for (int q = 0; q < 6; q++) { Ji[q] = A[q]; Jj[q] = B[q]; }
+      } else if (fk == 2) {
+        const double qq = rx * rx + ry * ry;
+        if (qq > 0.0) {
+          const double ua = -ry / qq, ub = rx / qq;
+#pragma unroll
+          for (int q = 0; q < 3; q++) { Ji[q] = ua * A[q] + ub * A[3 + q]; Jj[q] = ua * B[q] + ub * B[3 + q]; }
+          Ji[2] = -1.0;                                    // (ua ry - ub rx = -1)
+        }
       } else if (fk == 3) {
         Ji[0] = cz; Ji[1] = sz; Ji[3] = -sz; Ji[4] = cz; Ji[8] = 1.0;
       } else {
@@ -298,6 +315,7 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
   }
   if constexpr (TYPED) {
     if (fk == 1) mine[26] = mine[18] > 0.0 ? mine[18] : 1.0;   // the point's dummy pivot
+    if (fk == 2) mine[26] = mine[18];                          // ... a bearing's: the copy alone (see above)
   }
   if constexpr (ROBUST) {
 #pragma unroll

@@ -252,6 +252,105 @@ __global__ void k_relative_cov(int nP, const int32_t* __restrict__ pa, const int
   d2[p] = r;
 }
 
+// The predicted observation of vertex b from pose a, its covariance and the gate of a candidate measurement; one thread per
+// pair, kind[p] the factor the pair would be (include/cgmr.h: cgmr_observation_covariance):
+//   0  pose - pose   nothing here: k_relative_cov, launched in front over the same list, has written the pair (EDGE_SE2)
+//   1  pose - point  z = R_a^T (l - t_a) (2),  J = [A rows 0-1 | R_a^T] (2x5)            (EDGE_SE2_XY)
+//   2  pose - point  z = atan2(ry, rx) (1),    J = (-ry / q) J1 row 0 + (rx / q) J1 row 1  (EDGE_BEARING_SE2_XY), q = rx^2 + ry^2
+// S = J Sigma J^T with Sigma the 5x5 joint covariance of (x_a, l): the pose's block, the first two columns of Sigma_ab, the
+// point's leading 2x2 (the point's dummy third unknown is never read).  With a hypothesis: e = z - zh (the bearing's
+// normalised), d2 = e^T (S + Omega^-1)^-1 e in the factor's own dimension, Omega from info_upper[0, 1, 3] / info_upper[0];
+// NaN when that matrix is not positive definite.  Outputs padded to 3 and 3x3 with exact zeros.  A bearing of a point on
+// the pose (q == 0): z = 0, S and d2 NaN.
+__global__ void k_observation_cov(int nP, const int32_t* __restrict__ pa, const int32_t* __restrict__ pb,
+                                  const uint8_t* __restrict__ kind, const double* __restrict__ poses,
+                                  const double* __restrict__ aa, const double* __restrict__ ab, const double* __restrict__ bb,
+                                  const double* __restrict__ hyp_meas, const double* __restrict__ hyp_info,
+                                  double* __restrict__ zo, double* __restrict__ cov, double* __restrict__ d2) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nP) return;
+  const int fk = kind[p];
+  if (fk == 0) return;
+  const double* xa = poses + 3 * (size_t)pa[p];
+  const double* xl = poses + 3 * (size_t)pb[p];
+  const double c = cos(xa[2]), s = sin(xa[2]);
+  const double dx = xl[0] - xa[0], dy = xl[1] - xa[1];
+  const double rx = c * dx + s * dy, ry = -s * dx + c * dy;
+  const double* Saa = aa + 9 * (size_t)p;
+  const double* Sab = ab + 9 * (size_t)p;
+  const double* Sbb = bb + 9 * (size_t)p;
+  double Sg[25];                                                  // the joint covariance of (x_a, l)
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 3; j++) Sg[5 * i + j] = Saa[3 * i + j];
+    for (int j = 0; j < 2; j++) { Sg[5 * i + 3 + j] = Sab[3 * i + j]; Sg[5 * (3 + j) + i] = Sab[3 * i + j]; }
+  }
+  for (int i = 0; i < 2; i++)
+    for (int j = 0; j < 2; j++) Sg[5 * (3 + i) + 3 + j] = Sbb[3 * i + j];
+  double J[10] = {-c, -s, ry, c, s, s, -c, -rx, -s, c};
+  const int dim = fk == 1 ? 2 : 1;
+  double z[3] = {rx, ry, 0.0};
+  bool on_pose = false;
+  if (fk == 2) {
+    const double q = rx * rx + ry * ry;
+    on_pose = !(q > 0.0);
+    z[0] = on_pose ? 0.0 : atan2(ry, rx);
+    z[1] = 0.0;
+    const double u = -ry / q, v = rx / q;
+    for (int k = 0; k < 5; k++) J[k] = u * J[k] + v * J[5 + k];
+    J[2] = -1.0;
+  }
+  // M = J Sigma (2 x 5), S = M J^T (2 x 2); a bearing uses S(0, 0) alone (its second row of J is left over from kind 1)
+  double M[10], S[4];
+  for (int i = 0; i < 2; i++)
+    for (int j = 0; j < 5; j++) {
+      double u = 0;
+      for (int k = 0; k < 5; k++) u += J[5 * i + k] * Sg[5 * k + j];
+      M[5 * i + j] = u;
+    }
+  for (int i = 0; i < 2; i++)
+    for (int j = 0; j < 2; j++) {
+      double u = 0;
+      for (int k = 0; k < 5; k++) u += M[5 * i + k] * J[5 * j + k];
+      S[2 * i + j] = u;
+    }
+  if (dim == 2) { const double u = 0.5 * (S[1] + S[2]); S[1] = u; S[2] = u; }
+  if (on_pose) S[0] = NAN;
+  if (zo) for (int i = 0; i < 3; i++) zo[3 * (size_t)p + i] = z[i];
+  if (cov) {
+    double* o = cov + 9 * (size_t)p;
+    for (int i = 0; i < 9; i++) o[i] = 0.0;
+    o[0] = S[0];
+    if (dim == 2) { o[1] = S[1]; o[3] = S[2]; o[4] = S[3]; }
+  }
+  if (!d2) return;
+  const double* zh = hyp_meas + 3 * (size_t)p;
+  double r = NAN;
+  if (dim == 2) {
+    const double e0 = z[0] - zh[0], e1 = z[1] - zh[1];
+    double m00 = S[0], m01 = S[1], m11 = S[3];
+    if (hyp_info) {
+      const double* iu = hyp_info + 6 * (size_t)p;
+      const double a = iu[0], b = iu[1], d = iu[3];
+      const double id = 1.0 / (a * d - b * b);
+      m00 += d * id; m01 -= b * id; m11 += a * id;
+    }
+    // M = L L^T; d2 = |L^-1 e|^2
+    if (m00 > 0 && m00 < INFINITY) {
+      const double l00 = sqrt(m00), l10 = m01 / l00, dd = m11 - l10 * l10;
+      if (dd > 0 && dd < INFINITY) {
+        const double y0 = e0 / l00, y1 = (e1 - l10 * y0) / sqrt(dd);
+        r = y0 * y0 + y1 * y1;
+      }
+    }
+  } else if (!on_pose) {
+    const double e0 = j_norm_theta(z[0] - zh[0]);
+    double m = S[0];
+    if (hyp_info) m += 1.0 / hyp_info[6 * (size_t)p];
+    if (m > 0 && m < INFINITY) r = e0 * e0 / m;
+  }
+  d2[p] = r;
+}
+
 // ----------------------------------------------------------------------------------- launchers
 void joint_gram_split(int n, long long nwg, int* rows_out, int* nsplit_out) {
   // about kTargetWgs workgroups in all; a range is at least kMinRows rows (a multiple of 16: 4 wavefronts x 4 rows a step)
@@ -297,6 +396,13 @@ void launch_relative_cov(hipStream_t st, int nP, const int32_t* pa, const int32_
                          double* rel_cov, double* d2) {
   hipLaunchKernelGGL(k_relative_cov, dim3((nP + 63) / 64), dim3(64), 0, st, nP, pa, pb, poses, aa, ab, bb, hyp_meas, hyp_info, rel,
                      rel_cov, d2);
+}
+
+void launch_observation_cov(hipStream_t st, int nP, const int32_t* pa, const int32_t* pb, const uint8_t* kind, const double* poses,
+                            const double* aa, const double* ab, const double* bb, const double* hyp_meas, const double* hyp_info,
+                            double* z, double* cov, double* d2) {
+  hipLaunchKernelGGL(k_observation_cov, dim3((nP + 63) / 64), dim3(64), 0, st, nP, pa, pb, kind, poses, aa, ab, bb, hyp_meas, hyp_info,
+                     z, cov, d2);
 }
 
 }  // namespace cgmr

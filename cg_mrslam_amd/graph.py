@@ -82,8 +82,9 @@ class PoseGraph:
                            else np.ascontiguousarray(edge_level, dtype=np.int32))
         self.lasers = {}          # vertex index -> RobotLaser (user data; written/read as ROBOTLASER1 lines)
         # typed factors (include/cgmr.h: cgmr_factor_types): per vertex 0 = SE2 pose, 1 = point (VERTEX_XY; its third pose
-        # component stays 0); per edge 0 = EDGE_SE2, 1 = EDGE_SE2_XY, 3 = EDGE_PRIOR_SE2, 4 = EDGE_PRIOR_SE2_XY (priors: from ==
-        # to).  A 2-dimensional factor keeps (zx, zy, 0) and (I11, I12, 0, I22, 0, 0).  None: a pure pose graph, as ever.
+        # component stays 0); per edge 0 = EDGE_SE2, 1 = EDGE_SE2_XY, 2 = EDGE_BEARING_SE2_XY, 3 = EDGE_PRIOR_SE2, 4 =
+        # EDGE_PRIOR_SE2_XY (priors: from == to).  A 2-dimensional factor keeps (zx, zy, 0) and (I11, I12, 0, I22, 0, 0), a bearing
+        # (z, 0, 0) and (I, 0, 0, 0, 0, 0).  None: a pure pose graph, as ever.
         self.vertex_kind = None if vertex_kind is None else np.ascontiguousarray(vertex_kind, dtype=np.uint8).copy()
         self.edge_kind = None if edge_kind is None else np.ascontiguousarray(edge_kind, dtype=np.uint8).copy()
 
@@ -113,12 +114,14 @@ class PoseGraph:
 
     def add_edge(self, i, j, meas, info, kind=0, level=0):
         """Append an edge between the vertex indices ``i`` and ``j`` (a prior: i == j).  ``meas`` / ``info``: 3 and 6 values, or
-        2 and 3 (I11, I12, I22) for a 2-dimensional factor; returns the edge's index."""
+        2 and 3 (I11, I12, I22) for a 2-dimensional factor, or one of each for a bearing (kind 2); returns the edge's index."""
         m, u = np.zeros(3), np.zeros(6)
         mv, uv = np.asarray(meas, dtype=np.float64).reshape(-1), np.asarray(info, dtype=np.float64).reshape(-1)
         if kind in (1, 4):
             m[:2] = mv[:2]
             u[[0, 1, 3]] = uv[:3] if uv.size == 3 else uv[[0, 1, 3]]
+        elif kind == 2:
+            m[0], u[0] = mv[0], uv[0]
         else:
             m[:], u[:] = mv[:3], uv[:6]
         _, ek = self.kinds()
@@ -151,7 +154,7 @@ class PoseGraph:
     # ---------------------------------------------------------------- .g2o text format
     def save_g2o(self, path, precision=None):
         """VERTEX_SE2 (+ ROBOTLASER1 data) / FIX / EDGE_SE2 lines, and for a typed graph VERTEX_XY, EDGE_SE2_XY,
-        EDGE_PRIOR_SE2 and EDGE_PRIOR_SE2_XY.  ``precision=None`` reproduces g2o's default ostream precision (6 significant
+        EDGE_BEARING_SE2_XY, EDGE_PRIOR_SE2 and EDGE_PRIOR_SE2_XY.  ``precision=None`` reproduces g2o's default ostream precision (6 significant
         digits, lossy -- SURVEY.md section 5); pass 17 for round trips."""
         fmt = "%g" if precision is None else f"%.{precision}g"
         vk, ek = self.kinds()
@@ -175,6 +178,10 @@ class PoseGraph:
                     f.write("EDGE_SE2_XY %d %d " % (self.ids[self.edge_from[k]], self.ids[self.edge_to[k]])
                             + " ".join(fmt % v for v in (*m[:2], i[0], i[1], i[3])) + "\n")
                     continue
+                if ek[k] == 2:
+                    f.write("EDGE_BEARING_SE2_XY %d %d " % (self.ids[self.edge_from[k]], self.ids[self.edge_to[k]])
+                            + " ".join(fmt % v for v in (m[0], i[0])) + "\n")
+                    continue
                 if ek[k] == 3:
                     f.write("EDGE_PRIOR_SE2 %d " % self.ids[self.edge_from[k]] + " ".join(fmt % v for v in (*m, *i)) + "\n")
                     continue
@@ -188,7 +195,7 @@ class PoseGraph:
     @classmethod
     def load_g2o(cls, path):
         ids, poses, fixed_ids, ef, et, meas, info = [], [], set(), [], [], [], []
-        vkind, ekind = [], []     # typed graphs: VERTEX_XY, EDGE_SE2_XY, EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY
+        vkind, ekind = [], []     # typed graphs: VERTEX_XY, EDGE_SE2_XY, EDGE_BEARING_SE2_XY, EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY
         lasers = {}               # vertex id -> RobotLaser
 
         def info2(t):             # I11 I12 I22 in the 3x3 upper-triangle layout
@@ -221,6 +228,12 @@ class PoseGraph:
                     meas.append([float(tok[3]), float(tok[4]), 0.0])
                     info.append(info2(tok[5:8]))
                     ekind.append(1)
+                elif tok[0] == "EDGE_BEARING_SE2_XY":
+                    ef.append(int(tok[1]))
+                    et.append(int(tok[2]))
+                    meas.append([float(tok[3]), 0.0, 0.0])
+                    info.append([float(tok[4]), 0.0, 0.0, 0.0, 0.0, 0.0])
+                    ekind.append(2)
                 elif tok[0] == "EDGE_PRIOR_SE2":
                     ef.append(int(tok[1]))
                     et.append(int(tok[1]))
@@ -357,6 +370,11 @@ class GraphSLAM:
         """An EdgeSE2PointXY: the point seen at ``z_xy`` in the pose's frame; ``info`` = (I11, I12, I22).  Returns the edge index."""
         return self.graph.add_edge(pose_idx, landmark_idx, z_xy, info, kind=1)
 
+    def addBearing(self, pose_idx, landmark_idx, z, info) -> int:     # noqa: N802
+        """An EdgeSE2PointXYBearing: the point seen under the angle ``z`` in the pose's frame, with the scalar information
+        ``info``.  Returns the edge index."""
+        return self.graph.add_edge(pose_idx, landmark_idx, [float(z)], [float(info)], kind=2)
+
     def addPrior(self, pose_idx, z_xyt, info) -> int:     # noqa: N802
         """An EdgeSE2Prior on a pose; ``info`` = the 6 upper-triangle values.  Returns the edge index."""
         return self.graph.add_edge(pose_idx, pose_idx, z_xyt, info, kind=3)
@@ -467,11 +485,15 @@ class GraphSLAM:
         return out[:2] if cross else out[0]
 
     def _joint_args(self, robust):
-        """The level-0 problem at the current estimates and the robust arguments of the joint / pairwise marginals calls."""
+        """The level-0 problem at the current estimates, the robust and the typed arguments of the joint / pairwise marginals
+        calls (a typed graph: the kinds, and with them the typed entry points), and whether the call returns statistics."""
         g = self.graph
         rk = self._robust_level0() if robust else None
         kw = {} if rk is None else dict(kind=rk[0], delta=rk[1])
-        return (g.poses, g.fixed, *g.level0()), kw
+        ty = self._typed_level0()
+        if ty is not None:
+            kw.update(vertex_kind=ty[0], edge_kind=ty[1])
+        return (g.poses, g.fixed, *g.level0()), kw, rk is not None
 
     def computeMarginalBlocks(self, blockIndices, robust: bool = False):     # noqa: N802, N803 (g2o spelling)
         """SparseOptimizer::computeMarginals(spinv, blockIndices): the 3x3 blocks Sigma_ij of H^-1 for arbitrary vertex index
@@ -480,26 +502,62 @@ class GraphSLAM:
         pairs = [(int(i), int(j)) for i, j in blockIndices]
         if not pairs:
             return {}
-        a, kw = self._joint_args(robust)
+        a, kw, _ = self._joint_args(robust)
         ab = self.ctx.marginals_pairs(*a, [p[0] for p in pairs], [p[1] for p in pairs], **kw)[1]
         return {p: ab[k].copy() for k, p in enumerate(pairs)}
 
     def jointMarginal(self, vertices, robust: bool = False):     # noqa: N802 (g2o spelling)
         """The joint covariance ``[3 n, 3 n]`` of the given vertex indices, in their order (the input of a Mahalanobis test on
         several poses at once, or of a condensed graph denser than a star)."""
-        a, kw = self._joint_args(robust)
+        a, kw, stats = self._joint_args(robust)
         out = self.ctx.marginals_joint(*a, vertices, **kw)
-        return out[0] if kw else out
+        return out[0] if stats else out
 
     def relativeCovariance(self, pairs, hypotheses=None, robust: bool = False):     # noqa: N802 (g2o spelling)
         """For the vertex index pairs ``(a, b)``: ``(z [n, 3], Sigma_z [n, 3, 3])``, z = x_a^-1 x_b and its covariance, without
         re-gauging the graph per pair.  ``hypotheses`` = ``(meas [n, 3], info_upper [n, 6] or None)``: a candidate measurement
         per pair; then ``(z, Sigma_z, d2 [n])`` with the squared Mahalanobis distance a closure is gated on."""
         pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
-        a, kw = self._joint_args(robust)
+        a, kw, _ = self._joint_args(robust)
         hm, hi = (None, None) if hypotheses is None else hypotheses
-        z, cz, d2 = self.ctx.relative_covariance(*a, pairs[:, 0], pairs[:, 1], hm, hi, **kw)[:3]
+        if "vertex_kind" in kw:                                    # a typed graph: the same launch behind the typed check
+            z, cz, d2 = self.ctx.observation_covariance(*a, pairs[:, 0], pairs[:, 1], None, hm, hi, **kw)[:3]
+        else:
+            z, cz, d2 = self.ctx.relative_covariance(*a, pairs[:, 0], pairs[:, 1], hm, hi, **kw)[:3]
         return (z, cz) if hypotheses is None else (z, cz, d2)
+
+    def observationCovariance(self, pairs, kinds, hypotheses=None, robust: bool = False):     # noqa: N802
+        """Data association: for the vertex index pairs ``(pose, b)`` predicted as factors of ``kinds`` (per pair 0 EDGE_SE2,
+        1 EDGE_SE2_XY, 2 EDGE_BEARING_SE2_XY): ``(z [n, 3], S [n, 3, 3])``, the predicted observation and its covariance
+        J Sigma J^T, padded with zeros outside the factor's dimension.  ``hypotheses`` = ``(meas [n, 3], info_upper [n, 6] or
+        None)``: then ``(z, S, d2 [n])``, d2 the squared Mahalanobis distance of the candidate measurement under S + Omega^-1."""
+        pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        a, kw, _ = self._joint_args(robust)
+        hm, hi = (None, None) if hypotheses is None else hypotheses
+        z, cz, d2 = self.ctx.observation_covariance(*a, pairs[:, 0], pairs[:, 1], kinds, hm, hi, **kw)[:3]
+        return (z, cz) if hypotheses is None else (z, cz, d2)
+
+    def gateObservations(self, pose_idx, landmark_idxs, z, info, kind: int = 1, robust: bool = False):     # noqa: N802
+        """The individual-compatibility gate of M measurements taken from pose ``pose_idx`` against L known landmarks:
+        ``d2 [M, L]``, the squared Mahalanobis distance of measurement m as an observation of landmark l.  ``z`` [M, 2] and
+        ``info`` [M, 3] (I11, I12, I22) for ``kind`` 1, ``z`` [M] and ``info`` [M] for ``kind`` 2 (bearings).  One call over the
+        M L pairs (L + 1 unique vertices); the assignment is the caller's."""
+        lm = np.asarray(landmark_idxs, dtype=np.int32).reshape(-1)
+        zz = np.asarray(z, dtype=np.float64).reshape(-1, 2 if kind == 1 else 1)
+        uu = np.asarray(info, dtype=np.float64).reshape(len(zz), -1)
+        M, L = len(zz), len(lm)
+        hm, hi = np.zeros((M, 3)), np.zeros((M, 6))
+        if kind == 1:
+            hm[:, :2] = zz
+            hi[:, [0, 1, 3]] = uu if uu.shape[1] == 3 else uu[:, [0, 1, 3]]
+        elif kind == 2:
+            hm[:, 0], hi[:, 0] = zz[:, 0], uu[:, 0]
+        else:
+            raise ValueError("gateObservations: kind must be 1 (EDGE_SE2_XY) or 2 (EDGE_BEARING_SE2_XY)")
+        pairs = np.stack([np.full(M * L, int(pose_idx), dtype=np.int32), np.tile(lm, M)], axis=1)
+        d2 = self.observationCovariance(pairs, np.full(M * L, kind, dtype=np.uint8), (np.repeat(hm, L, axis=0), np.repeat(hi, L, axis=0)),
+                                        robust)[2]
+        return d2.reshape(M, L)
 
     def chi2(self) -> float:
         g = self.graph

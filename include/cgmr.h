@@ -250,22 +250,26 @@ int cgmr_dl_last_stats(const cgmr_ctx* ctx, int64_t out[3]);
  *                 CGMR_VERTEX_XY  (1)  a point (x, y): its third double is 0.0 on input and exactly 0.0 on output
  *   edge kinds    CGMR_EDGE_SE2 (0)           EDGE_SE2            pose i -> pose j, as everywhere above
  *                 CGMR_EDGE_SE2_XY (1)        EDGE_SE2_XY         pose i -> point l: e = R(theta_i)^T (l - t_i) - z           (2)
- *                 2                           reserved (bearing-only observations): rejected
+ *                 CGMR_EDGE_BEARING_SE2_XY (2) EDGE_BEARING_SE2_XY pose i -> point l: e = normalize(atan2(ry, rx) - z0),
+ *                                                                 (rx, ry) = R(theta_i)^T (l - t_i)                          (1)
  *                 CGMR_EDGE_PRIOR_SE2 (3)     EDGE_PRIOR_SE2      from == to == i: e = (R(z_theta)^T (t_i - z_t),
  *                                                                 normalize(theta_i - z_theta))                              (3)
  *                 CGMR_EDGE_PRIOR_SE2_XY (4)  EDGE_PRIOR_SE2_XY   from == to == i: e = t_i - z                               (2)
  * A 2-dimensional factor reads its first two measurements and the entries I11 I12 I22 (positions 0, 1, 3) of info_upper;
- * the rest is ignored.  A robust kernel sees e^T Omega e of the factor's own dimension.  CGMR_E_INVALID, with a message that
+ * the rest is ignored; the 1-dimensional bearing reads meas_xyt[0] and info_upper[0] alone.  With the point on the pose
+ * (rx = ry = 0) a bearing's error is normalize(-z0) and its Jacobians are zero.  A robust kernel sees e^T Omega e of the factor's own dimension.  CGMR_E_INVALID, with a message that
  * names the edge and before the device is touched, for: a kind-1 edge whose from is not a pose or whose to is not a point;
- * a kind-0, 3 or 4 edge that touches a point; a prior with from != to; kind 2 or any kind above 4; a vertex kind above 1.
+ * a kind-0, 3 or 4 edge that touches a point; a prior with from != to; any kind above 4; a vertex kind above 1 (kind 2 has kind 1's rule).
  * A prior makes its vertex a live column: a graph with no fixed vertex and one CGMR_EDGE_PRIOR_SE2 is a regular system.
- * A point's third unknown is carried as a decoupled dummy (pivot = a copy of the block's H_xx, right-hand side 0): its step
- * is exactly zero, the Levenberg-Marquardt start tau * max |H_jj| and every chi2 are those of the true-dimension system.
+ * A point's third unknown is carried as a decoupled dummy (pivot = a copy of the block's H_xx, right-hand side 0; a kind-1
+ * edge whose H_xx is not positive contributes 1.0 instead, a bearing always its own H_xx, which is 0 along the world's x
+ * axis: a point needs two bearings, or one kind-1 observation, to be determined at all): its step is exactly zero, the Levenberg-Marquardt start tau * max |H_jj| and every chi2 are those of the true-dimension system.
  * types == NULL, a null member, or kinds that are all zero: the plain / robust call, bit for bit (the same launches).  rk is
  * nullable as in the robust entry points.  vertex_kind / edge_kind are host memory in the _dev variants too (they are
  * structure, like fixed / from_idx / to_idx).  The typed path adds one small launch per linearisation that has priors;
- * CGMR_GRAPH capture is not supported on it (as for Levenberg-Marquardt).  Not offered for joint / pairwise marginals,
- * relative covariances, condensed graphs and the robot graph (cgmr_graph_*).
+ * CGMR_GRAPH capture is not supported on it (as for Levenberg-Marquardt).  Joint / pairwise marginals and the
+ * gate of a landmark observation: cgmr_marginals_joint_typed, cgmr_marginals_pairs_typed, cgmr_observation_covariance below.
+ * Not offered for condensed graphs and the robot graph (cgmr_graph_*): the multi-robot protocol has no landmarks.
  * cgmr_marginals_typed / cgmr_marginals_all_typed: cgmr_marginals_robust / cgmr_marginals_all_robust on the typed H.  A
  * point's 3x3 block comes back with its third row and column zero; so does the third column of the cross block of a
  * kind-1 edge (rows: the pose, columns: the point). */
@@ -273,6 +277,7 @@ int cgmr_dl_last_stats(const cgmr_ctx* ctx, int64_t out[3]);
 #define CGMR_VERTEX_XY 1
 #define CGMR_EDGE_SE2 0
 #define CGMR_EDGE_SE2_XY 1
+#define CGMR_EDGE_BEARING_SE2_XY 2
 #define CGMR_EDGE_PRIOR_SE2 3
 #define CGMR_EDGE_PRIOR_SE2_XY 4
 typedef struct cgmr_factor_types {
@@ -593,6 +598,41 @@ int cgmr_relative_covariance(cgmr_ctx* ctx, int nV, const double* poses_xyt, con
                              const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt, const double* info_upper,
                              int nP, const int32_t* pair_a, const int32_t* pair_b, double* rel_xyt_out, double* rel_cov_out,
                              const double* hyp_meas_xyt, const double* hyp_info_upper, double* d2_out, const cgmr_robust* rk);
+
+/* The same on typed factors (cgmr_factor_types above; present in C ABI version 105 libraries that export these symbols).
+ * cgmr_marginals_joint_typed / cgmr_marginals_pairs_typed: the plain calls' arguments, then types and rk as the other typed
+ * entry points take them; the kinds are checked as there (CGMR_E_INVALID names the edge) before the device is touched.  A
+ * point's third row and column are exactly zero in every block (the joint matrix's rows and columns 3 k + 2; aa, ab, bb);
+ * the joint matrix stays exactly symmetric; two calls give identical bytes.  types == NULL, a null member or all-zero kinds:
+ * the plain call bit for bit.  Limits, errors and zero rules are those of the plain calls.
+ *
+ * cgmr_observation_covariance: data association.  Pair p is predicted as a factor of kind obs_kind[p] (host, [nP]; NULL: all 0)
+ * from pose pair_a[p] to vertex pair_b[p], at poses_xyt, with the covariance S = J Sigma J^T of that prediction:
+ *   0  b a pose: exactly cgmr_relative_covariance (with types == NULL on a pose graph, bit for bit)
+ *   1  b a point: z = R_a^T (l - t_a); J = [A rows 0-1 | R_a^T] (2x5), A as in EdgeSE2PointXY; Sigma the 5x5 joint covariance
+ *      of (x_a, l).  Hypothesis: e = z - zh (hyp_meas_xyt[0, 1]), Omega from hyp_info_upper[0, 1, 3]
+ *   2  b a point: z = atan2(ry, rx); J the 1x5 bearing row; e = normalize(z - zh[0]); Omega = hyp_info_upper[0].  With the
+ *      point on the pose (rx = ry = 0): z = 0, S and d2 are NaN
+ * d2_out [nP] = e^T (S + Omega^-1)^-1 e in the factor's own dimension (hyp_info_upper NULL: no Omega term); NaN where that
+ * matrix is not positive definite (a pair with both ends fixed and no Omega, for one).  z_out [nP * 3] and cov_out [nP * 9] are
+ * padded with exact zeros outside the factor's dimension.  Nullability as in cgmr_relative_covariance.  CGMR_E_INVALID, naming
+ * the pair and before anything is queued: an obs_kind above 2, pair_a[p] a point, kind 0 with b a point, kind 1 / 2 with b a
+ * pose.  One thread per pair after the pairs' blocks of cgmr_marginals_pairs_typed, which stay on the device. */
+int cgmr_marginals_joint_typed(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                               const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt,
+                               const double* info_upper, int nK, const int32_t* query_idx, double* cov_out,
+                               const cgmr_factor_types* types, const cgmr_robust* rk);
+int cgmr_marginals_pairs_typed(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                               const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt,
+                               const double* info_upper, int nP, const int32_t* pair_a, const int32_t* pair_b,
+                               double* cov_aa_out, double* cov_ab_out, double* cov_bb_out, const cgmr_factor_types* types,
+                               const cgmr_robust* rk);
+int cgmr_observation_covariance(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                                const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt,
+                                const double* info_upper, int nP, const int32_t* pair_a, const int32_t* pair_b,
+                                const uint8_t* obs_kind, double* z_out, double* cov_out, const double* hyp_meas_xyt,
+                                const double* hyp_info_upper, double* d2_out, const cgmr_factor_types* types,
+                                const cgmr_robust* rk);
 
 /* ------------------------------------------------------------------------------------------
  * Generic correlative search (loop-closure / hierarchical / global matching).

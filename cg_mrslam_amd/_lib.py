@@ -46,6 +46,7 @@ _SYMBOLS = [
     "cgmr_global_matching_polished_batch", "cgmr_global_matching_polished",
     "cgmr_marginals_joint", "cgmr_marginals_pairs", "cgmr_relative_covariance",
     "cgmr_marginals_joint_typed", "cgmr_marginals_pairs_typed", "cgmr_observation_covariance",
+    "cgmr_gnc_params_default", "cgmr_gnc_optimize", "cgmr_gnc_optimize_dev", "cgmr_gnc_last_stats",
 ]
 
 JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)
@@ -132,6 +133,45 @@ def dl_params_checked(kw) -> DlParams:
     if not (fin and p.max_trials >= 1 and p.initial_delta > 0 and p.initial_lambda > 0 and p.lambda_factor > 1):
         raise ValueError("dogleg parameters: max_trials >= 1, initial_delta / initial_lambda > 0, lambda_factor > 1, all finite")
     return p
+
+
+class GncParams(C.Structure):
+    """cgmr_gnc_params (include/cgmr.h): graduated non-convexity."""
+    _fields_ = [("loss", C.c_int32), ("mu_factor", C.c_double), ("max_outer", C.c_int32), ("inner_iters", C.c_int32),
+                ("outer_per_wait", C.c_int32), ("barc_sq", C.c_void_p), ("default_barc_sq", C.c_double),
+                ("known_inlier", C.c_void_p), ("weight_out", C.c_void_p), ("edge_chi2_out", C.c_void_p)]
+
+
+GNC_TLS, GNC_GM = 0, 1                            # include/cgmr.h: CGMR_GNC_*
+GNC_LOSSES = {"tls": GNC_TLS, "gm": GNC_GM}
+GNC_DEFAULTS = dict(mu_factor=1.4, inner_iters=1, outer_per_wait=8)
+
+
+def gnc_loss_code(loss) -> int:
+    """CGMR_GNC_* of a loss given by name ("tls", "gm", any case) or by code; an unknown code passes (the library refuses it)."""
+    if isinstance(loss, str):
+        if loss.lower() not in GNC_LOSSES:
+            raise ValueError(f"unknown GNC loss {loss!r}; one of {sorted(GNC_LOSSES)}")
+        return GNC_LOSSES[loss.lower()]
+    return int(loss)
+
+
+def gnc_known_mask(known_inliers, n):
+    """uint8 [n] from an index list or a mask of length n (None: no known inlier)."""
+    mask = np.zeros(n, dtype=np.uint8)
+    if known_inliers is None:
+        return mask
+    k = np.asarray(known_inliers)
+    if k.dtype == np.bool_ or (k.dtype == np.uint8 and k.shape == (n,)):
+        if k.shape != (n,):
+            raise ValueError(f"known-inlier mask: {k.shape} given for {n} edges")
+        mask[:] = k != 0
+    elif k.size:
+        k = k.astype(np.int64).reshape(-1)
+        if k.min() < 0 or k.max() >= n:
+            raise ValueError("known-inlier index out of range")
+        mask[k] = 1
+    return mask
 
 
 class Robust(C.Structure):
@@ -387,6 +427,64 @@ class Context:
         out = self._optimize("cgmr_dl_optimize_dev", ((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), iters, prm, 2,
                              rk=rk, allow_fail=not raise_on_fail)
         return out + (e2, w) if robust else out
+
+    # ------------------------------------------------------------------ graduated non-convexity
+    def _gnc(self, entry, problem, max_outer, loss, barc_sq, known_inliers, vertex_kind, edge_kind, raise_on_cholesky, params):
+        bad = set(params) - set(GNC_DEFAULTS)
+        if bad:
+            raise TypeError(f"unknown GNC parameter(s): {sorted(bad)}")
+        v = dict(GNC_DEFAULTS, **params)
+        nV, p, (poses, fixed, nE, ef, et, meas, info), _keep = self._problem(*problem)
+        n = nE.value
+        typed = vertex_kind is not None or edge_kind is not None
+        ft, _keep_ft = factor_types(vertex_kind, edge_kind, nV, n) if typed else (None, None)
+        c_arr, c0 = None, 0.0
+        if barc_sq is not None and np.ndim(barc_sq) == 0:
+            c0 = float(barc_sq)
+            if not c0 > 0 or not math.isfinite(c0):            # (<= 0 would select the default in the C struct)
+                raise CgmrError(-1, "gnc_optimize: barc_sq must be finite and > 0")
+        elif barc_sq is not None:
+            c_arr = np.ascontiguousarray(barc_sq, dtype=np.float64).reshape(-1)
+            if c_arr.shape != (n,):
+                raise ValueError(f"barc_sq: {c_arr.shape[0]} given for {n} edges")
+        known = gnc_known_mask(known_inliers, n) if known_inliers is not None else None
+        w, e2 = np.zeros(n), np.zeros(n)
+        mo = max(int(max_outer), 1)
+        mu, cost, partial, done = np.zeros(mo), np.zeros(mo + 1), np.zeros(mo, dtype=np.int32), C.c_int32(0)
+        prm = GncParams(gnc_loss_code(loss), float(v["mu_factor"]), int(max_outer), int(v["inner_iters"]), int(v["outer_per_wait"]),
+                        c_arr.ctypes.data if c_arr is not None and n else None, c0,
+                        known.ctypes.data if known is not None and n else None, w.ctypes.data if n else None,
+                        e2.ctypes.data if n else None)
+        rc = getattr(self.lib, entry)(self.h, C.c_int(nV), poses, fixed, nE, ef, et, meas, info,
+                                      C.byref(ft) if ft is not None else C.c_void_p(0), C.byref(prm), _ptr(mu), _ptr(cost),
+                                      _ptr(partial), C.byref(done))
+        self._check(rc, allow_cholesky=not raise_on_cholesky)
+        out = dict(status=rc, mu=mu, cost=cost, partial=partial, outer_done=int(done.value), weights=w, edge_chi2=e2)
+        if p is not None:
+            out["poses"] = p
+        return out
+
+    def gnc_optimize(self, poses, fixed, ef, et, meas, info, max_outer=100, loss="tls", barc_sq=None, known_inliers=None,
+                     vertex_kind=None, edge_kind=None, raise_on_cholesky=True, **params):
+        """Graduated non-convexity (cgmr_gnc_optimize): ``loss`` "tls" or "gm"; ``barc_sq`` a scalar, a per-edge array or None
+        (the chi2 0.99 quantile of each factor's dimension); ``known_inliers`` an index list or mask; ``vertex_kind`` /
+        ``edge_kind`` as the typed calls; ``params``: mu_factor, inner_iters, outer_per_wait.  Host arrays in and out.  Returns a
+        dict: status, poses, mu [max_outer], cost [max_outer + 1], partial [max_outer], outer_done, weights [nE], edge_chi2 [nE]."""
+        return self._gnc("cgmr_gnc_optimize", (poses, fixed, ef, et, meas, info), max_outer, loss, barc_sq, known_inliers,
+                         vertex_kind, edge_kind, raise_on_cholesky, params)
+
+    def gnc_optimize_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, max_outer=100, loss="tls", barc_sq=None,
+                         known_inliers=None, vertex_kind=None, edge_kind=None, raise_on_cholesky=True, **params):
+        """gnc_optimize on device pointers for poses / meas / info (everything per edge stays host memory): the same dict
+        without the poses."""
+        return self._gnc("cgmr_gnc_optimize_dev", ((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), max_outer, loss,
+                         barc_sq, known_inliers, vertex_kind, edge_kind, raise_on_cholesky, params)
+
+    def gnc_last_stats(self):
+        """The last gnc_optimize* call: dict(host_waits, inner_iterations)."""
+        out = np.zeros(2, dtype=np.int64)
+        self._check(self.lib.cgmr_gnc_last_stats(self.h, _ptr(out)))
+        return dict(host_waits=int(out[0]), inner_iterations=int(out[1]))
 
     def dl_last_stats(self):
         """The last dl_optimize* call: dict(host_waits, trials, factorisations)."""

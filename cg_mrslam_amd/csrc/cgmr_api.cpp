@@ -2,6 +2,7 @@
 // Compiled with hipcc; contains no kernels (those live in gn_kernels.hip / matcher_kernels.hip).
 #include "cgmr_ctx.h"
 #include "dl_device.h"
+#include "gnc_device.h"
 #include "gn_host.h"
 #include "lm_device.h"
 #include "tr_device.h"
@@ -735,7 +736,8 @@ int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
 //   queue_round():  the launches of one round, from the host's copy of the state;
 //   also_read():    what a round's wait reads back beside state + records;
 //   empty_system(): the closed-form answer when nothing can move, into the host's copy of state + records;
-//   finish():       records and statistics out, the call's return code.
+//   finish():       records and statistics out, the call's return code;
+//   kRunsEmpty:     its rounds also serve a system with nothing to move (else: empty_system()).
 // The driver owns the rest: upload, the saved poses, the rounds with their one wait each, a timed-out round's repeat
 // (LevelwiseScope), the final pass of the robust statistics.
 template <typename P>
@@ -759,7 +761,7 @@ static int tr_run(cgmr_ctx* ctx, P& pol, int nV, double* d_poses, const uint8_t*
   rc = call.begin();
   if (rc) return rc;
   int64_t waits = 0;
-  if (D.nf == 0 || iters == 0) {
+  if ((D.nf == 0 || iters == 0) && !P::kRunsEmpty) {
     // nothing to move (or nothing asked): chi2 at x, and what g2o makes of an empty system
     GnPassOpts chi_pass;
     chi_pass.chi_only = true;
@@ -819,6 +821,7 @@ static cgmr_lm_params lm_defaults() {
 struct LmPolicy {
   using State = LmState;
   static constexpr const char* kName = "Levenberg-Marquardt";
+  static constexpr bool kRunsEmpty = false;
   cgmr_lm_params P;
   double *chi2_out, *lambda_out;
   int32_t *trials_out, *iters_done;
@@ -916,6 +919,7 @@ bool dl_params_ok(const cgmr_dl_params* p) { return !p || dl_params_valid(*p); }
 struct DlPolicy {
   using State = DlState;
   static constexpr const char* kName = "dogleg";
+  static constexpr bool kRunsEmpty = false;
   cgmr_dl_params P;
   double *chi2_out, *delta_out;
   int32_t *trials_out, *step_out, *iters_done;
@@ -1720,6 +1724,158 @@ static int dl_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t*
                          });
 }
 
+
+// ------------------------------------------------------------------------------------------------ graduated non-convexity
+static cgmr_gnc_params gnc_defaults() {
+  cgmr_gnc_params p;
+  p.loss = CGMR_GNC_TLS; p.mu_factor = 1.4; p.max_outer = 100; p.inner_iters = 1; p.outer_per_wait = 8;
+  p.barc_sq = nullptr; p.default_barc_sq = 0.0; p.known_inlier = nullptr; p.weight_out = nullptr; p.edge_chi2_out = nullptr;
+  return p;
+}
+
+// gnc arena: state | mu, cost [max_outer + 1] | partial [max_outer + 1] || saved poses [3 nV] | weight, barc^2, r [nE] | the
+// start's per-workgroup values | known mask [nE]
+struct GncLayout {
+  size_t o_mu, o_cost, o_part, rec_bytes, o_saved, o_w, o_c, o_r, o_wg, o_known, bytes;
+  GncLayout(int max_outer, int nV, int nE) {
+    BlobLayout B;
+    B.add<GncState>(1);
+    const size_t n = (size_t)max_outer + 1, e = (size_t)std::max(nE, 1);
+    o_mu = B.add<double>(n); o_cost = B.add<double>(n); o_part = B.add<int32_t>(n);
+    rec_bytes = B.off;
+    o_saved = B.add<double>(3 * (size_t)std::max(nV, 1));
+    o_w = B.add<double>(e); o_c = B.add<double>(e); o_r = B.add<double>(e); o_wg = B.add<double>((e + 255) / 256);
+    o_known = B.add<uint8_t>(e);
+    bytes = B.off + 256;
+  }
+};
+
+// The third policy of tr_run.  A round: [the start: one chi-only pass for r, mu0;] up to outer_per_wait outer iterations.
+struct GncPolicy {
+  using State = GncState;
+  static constexpr const char* kName = "graduated non-convexity";
+  static constexpr bool kRunsEmpty = true;
+  cgmr_gnc_params P;
+  double *mu_out, *cost_out;
+  int32_t *partial_out, *outer_done;
+  GncDev L;
+  GncLayout lay;
+  int ran = 0;                                               // outer iterations run (finish())
+
+  // (gnc_run has reserved the arena -- the per-edge arrays went up before the driver started -- and bound L)
+  int reserve(cgmr_ctx*, int, int, int, int, size_t* rec_bytes) { *rec_bytes = lay.rec_bytes; return 0; }
+  GncState start(int) const {
+    GncState hs;
+    hs.factor = P.mu_factor; hs.loss = P.loss; hs.max_outer = P.max_outer; hs.inner_iters = P.inner_iters;
+    return hs;
+  }
+  GnEdges edges(const GnEdges& Ed, int mode, double* r_out) const {
+    GnEdges E = Ed;
+    E.gnc = true; E.gnc_mode = mode; E.gnc_weight = L.weight; E.gnc_c = L.barc_sq; E.gnc_known = L.known; E.gnc_state = L.S;
+    E.gnc_r = r_out;
+    return E;
+  }
+  static void outer_records(hipStream_t st, const GnDevice& D, void* self) { launch_gnc_outer(st, D, ((GncPolicy*)self)->L); }
+  // One outer iteration, the same launches whatever happens (gnc_kernels.hip).  With nothing to move a pass is its
+  // linearisation alone.
+  void outer(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, int nV, double* d_poses, const GnEdges& Ed) {
+    for (int i = 0; i < P.inner_iters; i++) {
+      const GnEdges E = edges(Ed, i == 0 ? kGncCompute : kGncReuse, nullptr);
+      if (D.nf > 0) {
+        GnPassOpts o;
+        if (i == 0) { o.after_assemble = outer_records; o.after_assemble_arg = this; }
+        gn_pass_on(ctx, D, st, d_poses, E, o);
+      } else if (i == 0) {
+        launch_linearize(st, D, d_poses, E, 1);
+        launch_gnc_outer(st, D, L);
+      }
+      launch_gnc_step(st, D, L, i + 1 == P.inner_iters);
+    }
+    launch_tr_commit(st, nV, d_poses, L.saved, &L.S->accept);
+  }
+  void queue_round(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, int nV, double* d_poses, const GnEdges& Ed, const GncState& hs, int) {
+    if (hs.need_init) {
+      launch_linearize(st, D, d_poses, edges(Ed, kGncPlain, L.r), 1);
+      launch_gnc_start(st, D, L);
+    }
+    const int n = std::min(P.outer_per_wait, P.max_outer - hs.iter);
+    for (int t = 0; t < n; t++) outer(ctx, D, st, nV, d_poses, Ed);
+  }
+  GnCall::Readback also_read(const GnDevice&) { return {nullptr, nullptr, 0}; }
+  void empty_system(GncState&, char*, double, int) const {}
+  int finish(cgmr_ctx* ctx, const GncState& hs, const char* h, int ran_, int iters, int64_t waits) {
+    ran = ran_;
+    records_out(mu_out, (const double*)(h + lay.o_mu), ran, iters);
+    records_out(partial_out, (const int32_t*)(h + lay.o_part), ran, iters);
+    if (cost_out) for (int k = 0; k < ran; k++) cost_out[k] = ((const double*)(h + lay.o_cost))[k];   // (the rest: gnc_optimize_impl)
+    if (outer_done) *outer_done = ran;
+    ctx->gnc_stats[0] = waits;
+    ctx->gnc_stats[1] = hs.inner_total;
+    if (hs.failed)
+      return set_err(ctx, CGMR_E_CHOLESKY_BASE - (hs.failed - 1),
+                     "graduated non-convexity: Cholesky failed (non-positive pivot) in inner iteration %d; poses left at the last good update",
+                     hs.failed - 1);
+    return CGMR_OK;
+  }
+};
+
+// dimension of an edge kind's factor (include/cgmr.h: CGMR_EDGE_*)
+static int factor_dim(int kind) { return kind == 2 ? 1 : (kind == 1 || kind == 4) ? 2 : 3; }
+
+static int gnc_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                             const int32_t* to_idx, const double* meas, const double* info, const cgmr_factor_types* ft,
+                             const cgmr_gnc_params* params, double* mu_out, double* cost_out, int32_t* partial_out,
+                             int32_t* outer_done, bool dev) {
+  const char* who = dev ? "cgmr_gnc_optimize_dev" : "cgmr_gnc_optimize";
+  int rc = optimize_args_check(ctx, who, nV, poses, fixed, nE, from_idx, to_idx, meas, info, 0);
+  if (rc) return rc;
+  const cgmr_gnc_params P = params ? *params : gnc_defaults();
+  if ((P.loss != CGMR_GNC_TLS && P.loss != CGMR_GNC_GM) || !std::isfinite(P.mu_factor) || !(P.mu_factor > 1) || P.max_outer < 1 ||
+      P.inner_iters < 1 || P.outer_per_wait < 1 || !std::isfinite(P.default_barc_sq))
+    return set_err(ctx, CGMR_E_INVALID, "%s: loss must be CGMR_GNC_TLS or CGMR_GNC_GM, mu_factor finite and > 1, max_outer / inner_iters / outer_per_wait >= 1, default_barc_sq finite", who);
+  TypedHost typed;
+  rc = typed_check(ctx, who, ft, nV, nE, from_idx, to_idx, typed);
+  if (rc) return rc;
+  const double quantile[4] = {0.0, 6.634896601021213, 9.21034037197618, 11.344866730144373};   // chi2 0.99, by dimension
+  std::vector<double> hc((size_t)nE);
+  std::vector<uint8_t> hk((size_t)nE, 0);
+  for (int k = 0; k < nE; k++) {
+    hc[k] = P.barc_sq ? P.barc_sq[k] : P.default_barc_sq > 0 ? P.default_barc_sq : quantile[factor_dim(typed.any ? typed.ek[k] : 0)];
+    if (!std::isfinite(hc[k]) || !(hc[k] > 0)) return set_err(ctx, CGMR_E_INVALID, "%s: barc_sq of edge %d must be finite and > 0", who, k);
+    if (P.known_inlier) hk[k] = P.known_inlier[k] ? 1 : 0;
+  }
+  rc = optimize_staged(ctx, who, dev, true, nV, poses, nE, meas, info, nullptr, &typed, [&](double* d_poses, const GnEdges& Ed) {
+    hipStream_t st = ctx->stream;
+    GncPolicy pol{P, mu_out, cost_out, partial_out, outer_done, GncDev(), GncLayout(P.max_outer, nV, nE)};
+    int r = arena_reserve(ctx, ctx->gnc_arena, pol.lay.bytes);
+    if (r) return r;
+    char* d = ctx->gnc_arena.ptr;
+    GncDev& L = pol.L;
+    L.S = (GncState*)d; L.rec_mu = (double*)(d + pol.lay.o_mu); L.rec_cost = (double*)(d + pol.lay.o_cost);
+    L.rec_partial = (int32_t*)(d + pol.lay.o_part); L.saved = (double*)(d + pol.lay.o_saved); L.weight = (double*)(d + pol.lay.o_w);
+    L.barc_sq = (double*)(d + pol.lay.o_c); L.r = (double*)(d + pol.lay.o_r); L.part = (double*)(d + pol.lay.o_wg);
+    L.known = (uint8_t*)(d + pol.lay.o_known);
+    if (nE > 0) {   // (pageable host memory: the copies have left the vectors when they return)
+      HIP_TRY(ctx, hipMemcpyAsync(L.barc_sq, hc.data(), 8 * (size_t)nE, hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, hipMemcpyAsync(L.known, hk.data(), (size_t)nE, hipMemcpyHostToDevice, st));
+    }
+    r = tr_run(ctx, pol, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, P.max_outer, nullptr, 0);
+    if (r != CGMR_OK && r > CGMR_E_CHOLESKY_BASE) return r;
+    // the final statistics, at the poses the call returns and with the weights of its last outer iteration
+    GnDevice& D = ctx->gn;
+    double cost_end = 0.0;
+    launch_linearize(st, D, d_poses, pol.edges(Ed, kGncReuse, L.r), 1);
+    launch_chi2(st, D, D.chi2);
+    HIP_TRY(ctx, hipMemcpyAsync(&cost_end, D.chi2, sizeof(double), hipMemcpyDeviceToHost, st));
+    if (nE > 0 && P.weight_out) HIP_TRY(ctx, hipMemcpyAsync(P.weight_out, L.weight, 8 * (size_t)nE, hipMemcpyDeviceToHost, st));
+    if (nE > 0 && P.edge_chi2_out) HIP_TRY(ctx, hipMemcpyAsync(P.edge_chi2_out, L.r, 8 * (size_t)nE, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (cost_out) for (int k = pol.ran; k <= P.max_outer; k++) cost_out[k] = cost_end;
+    return r;
+  });
+  return rc;
+}
+
 }  // namespace cgmr
 
 using namespace cgmr;
@@ -1771,6 +1927,7 @@ void cgmr_ctx_destroy(cgmr_ctx* ctx) {
   if (ctx->si_arena.ptr) (void)hipFree(ctx->si_arena.ptr);
   if (ctx->lm_arena.ptr) (void)hipFree(ctx->lm_arena.ptr);
   if (ctx->dl_arena.ptr) (void)hipFree(ctx->dl_arena.ptr);
+  if (ctx->gnc_arena.ptr) (void)hipFree(ctx->gnc_arena.ptr);
   if (ctx->rk_arena.ptr) (void)hipFree(ctx->rk_arena.ptr);
   if (ctx->ty_arena.ptr) (void)hipFree(ctx->ty_arena.ptr);
   if (ctx->st_arena.ptr) (void)hipFree(ctx->st_arena.ptr);
@@ -1930,6 +2087,30 @@ int cgmr_marginals_all_typed(cgmr_ctx* ctx, int nV, const double* poses, const u
                              const cgmr_factor_types* types, const cgmr_robust* rk) {
   if (!ctx) return CGMR_E_INVALID;
   return marginals_all_driver(ctx, nV, poses, fixed, nE, ef, et, meas, info, cov_out, cross_out, rk, types);
+}
+
+cgmr_gnc_params cgmr_gnc_params_default(void) { return gnc_defaults(); }
+
+int cgmr_gnc_optimize(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                      const int32_t* to_idx, const double* meas, const double* info, const cgmr_factor_types* types,
+                      const cgmr_gnc_params* params, double* mu_out, double* cost_out, int32_t* partial_out, int32_t* outer_done) {
+  return gnc_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, types, params, mu_out, cost_out, partial_out,
+                           outer_done, false);
+}
+
+int cgmr_gnc_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                          const int32_t* to_idx, const double* d_meas, const double* d_info, const cgmr_factor_types* types,
+                          const cgmr_gnc_params* params, double* mu_out, double* cost_out, int32_t* partial_out,
+                          int32_t* outer_done) {
+  return gnc_optimize_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, types, params, mu_out, cost_out,
+                           partial_out, outer_done, true);
+}
+
+int cgmr_gnc_last_stats(const cgmr_ctx* ctx, int64_t out[2]) {
+  if (!ctx || !out) return CGMR_E_INVALID;
+  out[0] = ctx->gnc_stats[0];
+  out[1] = ctx->gnc_stats[1];
+  return CGMR_OK;
 }
 
 int cgmr_dl_last_stats(const cgmr_ctx* ctx, int64_t out[3]) {

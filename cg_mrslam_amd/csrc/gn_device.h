@@ -10,6 +10,8 @@
 
 namespace cgmr {
 
+struct GncState;                         // gnc_device.h
+
 struct GnDevice {
   int nV = 0, nE = 0, nf = 0, nb = 0, nlevels = 0, nfronts = 0;
   // structure (uploaded once per analyse)
@@ -73,6 +75,17 @@ struct GnEdges {
   const uint8_t* edge_kind = nullptr;
   int n_unary = 0;
   const int32_t *uv_vertex = nullptr, *uv_ptr = nullptr, *uv_edge = nullptr;
+  // graduated non-convexity (include/cgmr.h: cgmr_gnc_params; gn_kernels.hip: GncArgs): every edge's terms are scaled by its
+  // GNC weight -- computed from gnc_state->mu and stored in gnc_weight (gnc_mode kGncCompute), read from there (kGncReuse), or
+  // 1 (kGncPlain); gnc_c [nE] barc^2, gnc_known [nE] the known-inlier mask, gnc_r (nullable) receives e^T Omega e of every edge
+  // (device memory).  One job, never with `robust`.
+  bool gnc = false;
+  int gnc_mode = 0;
+  double* gnc_weight = nullptr;
+  const double* gnc_c = nullptr;
+  const uint8_t* gnc_known = nullptr;
+  const GncState* gnc_state = nullptr;
+  double* gnc_r = nullptr;
 };
 // gn_structure.hip: the assembly lists (asm_ptr: nf + nb + 1, asm_src: one entry per (edge, key)) from the permutation, the
 // edge list and the off-diagonal blocks (offbase: nf + 1 column starts into off_row); work space: ekey nE, cnt nf + nb + 3,

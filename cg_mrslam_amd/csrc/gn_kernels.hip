@@ -25,6 +25,7 @@
 
 #include "gn_symbolic.h"
 #include "gn_device.h"
+#include "gnc_device.h"
 #include "panel_cholesky.h"
 
 namespace cgmr {
@@ -177,6 +178,22 @@ __device__ __forceinline__ double robustify(int kind, double delta, double e2, d
 struct TypedArgs {
   const uint8_t* edge_kind;   // [nA]; edges [nA, nE) are kind 0
 };
+// GNC (graduated non-convexity, include/cgmr.h: cgmr_gnc_params; gnc_kernels.hip): a fourth kind of trailing argument, in
+// instances of its own with and without TypedArgs -- the eight others keep their names and their code.  r = e^T O e is formed
+// as the robust instances form e2 (the factor's own dimension); the weight w of a free edge comes from r and the device
+// state's mu (gnc_device.h: gnc_weight), a known inlier's is 1.  w r goes into the chi2 partial sum and the finished 33 terms
+// are scaled by w, the point's dummy pivot with them: the dummy stays the copy of the scaled Hjj(0,0), so summed over a
+// point's edges it is still the block's H_xx and the argument above holds; with w = 0 on all of a point's (or a pose's) edges
+// the block is zero, the pivot is not positive, and the call ends with a Cholesky code.  mode: kGncCompute stores w (unless the
+// call is over: a queued launch behind the end changes nothing), kGncReuse reads the stored one, kGncPlain takes 1.
+struct GncArgs {
+  double* weight;          // [nE]
+  const double* barc_sq;   // [nE]
+  const uint8_t* known;    // [nE]: 1 = known inlier, weight 1
+  const GncState* S;
+  double* r_out;           // [nE] or null: r of every edge
+  int mode;
+};
 template <typename T> __device__ __forceinline__ T pick_arg(T a) { return a; }
 template <typename T, typename U> __device__ __forceinline__ T pick_arg(T a, U) { return a; }
 template <typename T, typename U> __device__ __forceinline__ T pick_arg(U, T b) { return b; }
@@ -190,7 +207,9 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
                                                    double* __restrict__ term, int chi_only, long long js, long long ps,
                                                    Rk... rk_pack) {
   constexpr bool TYPED = pack_has<TypedArgs, Rk...>::value;
-  static_assert(sizeof...(Rk) == (ROBUST ? 1 : 0) + (TYPED ? 1 : 0), "k_linearize: one RobustArgs in the robust instances, one TypedArgs in the typed ones");
+  constexpr bool GNC = pack_has<GncArgs, Rk...>::value;
+  static_assert(sizeof...(Rk) == (ROBUST ? 1 : 0) + (TYPED ? 1 : 0) + (GNC ? 1 : 0) && !(ROBUST && GNC) && !(BATCH && GNC),
+                "k_linearize: one RobustArgs in the robust instances, one TypedArgs in the typed ones, one GncArgs in the GNC ones");
   CGMR_JOB(poses, ps); CGMR_JOB(term, js);
   __shared__ double s_chi[4];
   const int k0 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -239,6 +258,19 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
       ch = live ? rho0 : 0.0;
       if constexpr (!BATCH)                                              // (a batch: no statistics, the host passes none)
         if (rk.stats && k0 < nE) { rk.stats[k] = e2; rk.stats[E + k] = rho1; }
+    }
+    if constexpr (GNC) {
+      const GncArgs ga = pick_arg<GncArgs>(rk_pack...);
+      const double r = e[0] * Oe[0] + e[1] * Oe[1] + e[2] * Oe[2];
+      if (ga.mode == kGncReuse) {
+        rho1 = ga.weight[k];
+      } else if (ga.mode == kGncCompute) {
+        const GncState* S = ga.S;
+        if (!ga.known[k] && !S->nothing) rho1 = gnc_weight(S->loss, S->mu, ga.barc_sq[k], r);
+        if (k0 < nE && !S->done) ga.weight[k] = rho1;
+      }
+      if (ga.r_out && k0 < nE) ga.r_out[k] = r;
+      ch = live ? rho1 * r : 0.0;
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) ch += __shfl_xor(ch, m, 64);
@@ -317,7 +349,7 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
     if (fk == 1) mine[26] = mine[18] > 0.0 ? mine[18] : 1.0;   // the point's dummy pivot
     if (fk == 2) mine[26] = mine[18];                          // ... a bearing's: the copy alone (see above)
   }
-  if constexpr (ROBUST) {
+  if constexpr (ROBUST || GNC) {
 #pragma unroll
     for (int q = 0; q < 33; q++) mine[q] *= rho1;
   }
@@ -1636,6 +1668,21 @@ void launch_linearize(hipStream_t st, const GnDevice& D, const double* poses, co
   gn_init_kernels();
   const dim3 grid((D.nE + 255) / 256, 1, D.njobs);
   const size_t lds = chi_only ? 0 : 256 * 33 * sizeof(double);
+  if (Ed.gnc) {                       // (never a batch, never robust: cgmr_gnc_optimize runs one job)
+    GncArgs ga;
+    ga.weight = Ed.gnc_weight; ga.barc_sq = Ed.gnc_c; ga.known = Ed.gnc_known; ga.S = Ed.gnc_state; ga.r_out = Ed.gnc_r;
+    ga.mode = Ed.gnc_mode;
+    if (Ed.typed) {
+      TypedArgs ty;
+      ty.edge_kind = Ed.edge_kind;
+      hipLaunchKernelGGL((k_linearize<false, false, TypedArgs, GncArgs>), grid, dim3(256), lds, st, D.nE, Ed.nA, Ed.n_active, poses, D.ef,
+                         D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride, D.pose_stride, ty, ga);
+      return;
+    }
+    hipLaunchKernelGGL((k_linearize<false, false, GncArgs>), grid, dim3(256), lds, st, D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et,
+                       Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride, D.pose_stride, ga);
+    return;
+  }
   if (Ed.typed) {                     // (never a batch: the typed entry points run one job)
     TypedArgs ty;
     ty.edge_kind = Ed.edge_kind;
@@ -1699,7 +1746,9 @@ void gn_init_kernels() {
                           reinterpret_cast<const void*>(k_linearize<true, true, RobustArgs>),
                           reinterpret_cast<const void*>(k_linearize<false, false, TypedArgs>), reinterpret_cast<const void*>(k_linearize<true, false, TypedArgs>),
                           reinterpret_cast<const void*>(k_linearize<false, true, RobustArgs, TypedArgs>),
-                          reinterpret_cast<const void*>(k_linearize<true, true, RobustArgs, TypedArgs>)})
+                          reinterpret_cast<const void*>(k_linearize<true, true, RobustArgs, TypedArgs>),
+                          reinterpret_cast<const void*>(k_linearize<false, false, GncArgs>),
+                          reinterpret_cast<const void*>(k_linearize<false, false, TypedArgs, GncArgs>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 33 * (int)sizeof(double));
     for (const void* f : {reinterpret_cast<const void*>(k_top_block<false>), reinterpret_cast<const void*>(k_top_block<true>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, top_smem_bytes(kTopMaxCols));

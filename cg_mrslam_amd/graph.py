@@ -296,6 +296,8 @@ class GraphSLAM:
         self._rk_delta = None
         self.last_edge_chi2 = None
         self.last_weights = None
+        self.last_mu = None
+        self._gnc_rejected = None
 
     def optimize(self, nrunnings: int) -> None:
         """``nrunnings`` iterations on the level-0 edges; estimates updated in place.  Returns nothing and never raises on
@@ -352,6 +354,38 @@ class GraphSLAM:
         g.poses[:] = poses
         self.last_chi2 = chi2
         self.last_status = rc
+
+    # ---------------------------------------------------------------- graduated non-convexity
+    def optimizeGNC(self, max_outer: int = 100, loss: str = "tls", barc_sq=None, known_inliers=None, **params) -> None:     # noqa: N802
+        """Outlier rejection by graduated non-convexity (Context.gnc_optimize) on the level-0 edges, from the estimates as they
+        stand; estimates updated in place.  ``loss``: "tls" or "gm"; ``barc_sq``: a scalar, an array over the graph's edges or
+        None (the chi2 0.99 quantile of each factor's dimension); ``known_inliers``: indices of the graph's edges or a mask
+        over them, None for none; ``params``: mu_factor, inner_iters, outer_per_wait.  A typed graph goes through its kinds;
+        robust kernels set with setRobustKernel play no part.  Leaves ``last_weights`` and ``last_edge_chi2`` (over the
+        level-0 edges), ``last_mu``, ``last_chi2`` (the cost record, [outer iterations run + 1]), ``last_iterations`` (outer
+        iterations run) and ``last_status``; never raises on a Cholesky failure."""
+        from ._lib import gnc_known_mask
+        g = self.graph
+        m = g.edge_level == 0
+        ef, et, meas, info = g.level0()
+        ty = self._typed_level0()
+        kw = {} if ty is None else dict(vertex_kind=ty[0], edge_kind=ty[1])
+        c = barc_sq if barc_sq is None or np.ndim(barc_sq) == 0 else np.asarray(barc_sq, dtype=np.float64).reshape(-1)[m]
+        known = None if known_inliers is None else gnc_known_mask(known_inliers, g.n_edges)[m]
+        out = self.ctx.gnc_optimize(g.poses, g.fixed, ef, et, meas, info, int(max_outer), loss, c, known, raise_on_cholesky=False,
+                                    **kw, **params)
+        done = out["outer_done"]
+        g.poses[:] = out["poses"]
+        self.last_weights, self.last_edge_chi2 = out["weights"], out["edge_chi2"]
+        self.last_mu, self.last_chi2 = out["mu"][:done], out["cost"][:done + 1]
+        self.last_iterations, self.last_status = done, out["status"]
+        self._gnc_rejected = np.flatnonzero(m)[out["weights"] == 0.0] if str(loss).lower() in ("tls", "0") else np.zeros(0, np.int64)
+
+    def rejectedEdges(self):     # noqa: N802
+        """Indices (into the graph's edges) of the edges the last optimizeGNC call with the TLS loss gave weight 0."""
+        if self._gnc_rejected is None:
+            raise RuntimeError("rejectedEdges: call optimizeGNC first")
+        return self._gnc_rejected.copy()
 
     # ---------------------------------------------------------------- landmarks and priors (g2o's slam2d types)
     def _typed_level0(self):

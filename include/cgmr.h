@@ -309,6 +309,65 @@ int cgmr_dl_optimize_typed_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const
                                const double* d_info_upper, int iters, const cgmr_dl_params* params, double* chi2_out,
                                double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
                                const cgmr_factor_types* types, const cgmr_robust* rk);
+/* Graduated non-convexity (same ABI version: callers find the entry points by their symbols): outlier rejection by the
+ * method of Yang, Antonante, Tzoumas and Carlone (RA-L 2020) as GTSAM's GncOptimizer runs it [recalled: from memory, not read
+ * from the paper's or GTSAM's text; the contract is tests/ref_gnc.py].  A truncated-least-squares (TLS) or Geman-McClure (GM)
+ * cost is reached from a convex surrogate by stepping a parameter mu; every outer iteration re-weights the edges from their
+ * residuals and runs inner_iters Gauss-Newton iterations on the weighted system.  The result is an estimate and a weight per
+ * edge (TLS: 0 = rejected).
+ *   r_k = e_k^T Omega_k e_k, in the factor's own dimension for a typed edge; c_k = barc_sq[k]; F = the edges not marked
+ *   known_inlier (those always have weight 1).
+ *   Start, r at the poses passed in:  TLS  mu0 = min over k in F with 2 r_k - c_k > 0 of c_k / (2 r_k - c_k)
+ *                                     GM   mu0 = max over k in F of 2 r_k / c_k
+ *   Nothing to reject (TLS: no such k; GM: mu0 <= 1; F empty): every weight is 1, one outer iteration runs, mu_out[0] = 0,
+ *   *outer_done = 1, and the poses are bit-identical to cgmr_gn_optimize (cgmr_gn_optimize_typed) with iters = inner_iters.
+ *   Outer iteration t, at poses x_t with mu_t: weights from r(x_t) --
+ *     TLS  up = (mu + 1) / mu c, lo = mu / (mu + 1) c:  w = 0 if r >= up, 1 if r <= lo, else sqrt(c mu (mu + 1) / r) - mu
+ *     GM   w = (mu c / (r + mu c))^2
+ *   then inner_iters Gauss-Newton iterations with Omega_k replaced by w_k Omega_k, the weights frozen.
+ *     mu_out[t] = mu_t; cost_out[t] = sum w_k r_k at x_t; partial_out[t] = number of k in F with 0 < w_k < 1.
+ *   Last iteration: TLS the first t with partial_out[t] == 0, GM the t that ran with mu = 1, t = max_outer - 1 at the latest;
+ *   *outer_done = t + 1.  Otherwise mu_(t+1) = mu_t mu_factor (TLS), max(1, mu_t / mu_factor) (GM).
+ *   End: weight_out = the weights of the last outer iteration (not recomputed), edge_chi2_out = r at the returned poses,
+ *   cost_out[outer_done] = sum w r there; mu_out / partial_out behind outer_done are zero, cost_out repeats its last value.
+ * A non-positive pivot in inner iteration i, counted over the whole call, returns CGMR_E_CHOLESKY_BASE - i with the poses at
+ * the last good update (TLS weights of 0 on every edge of a free vertex do that); the iteration it happened in counts in
+ * *outer_done, and weight_out / edge_chi2_out are still written.  CGMR_E_INVALID, before the device is touched: an unknown
+ * loss, mu_factor <= 1 or not finite, max_outer / inner_iters / outer_per_wait < 1, a barc_sq that is not finite and > 0, bad
+ * kinds (as the typed entry points).  CGMR_E_TIMEOUT as cgmr_lm_optimize.  With one Gauss-Newton step per mu the estimate lags
+ * behind mu: at the chi2 0.99 quantile a few true inliers of a graph with many gross outliers are rejected too; a larger
+ * barc_sq or more inner iterations avoid that.  The device keeps mu, the weights and the stop test; the host queues
+ * outer_per_wait outer iterations per wait, and the result does not depend on that number.  Not combined with cgmr_robust;
+ * CGMR_GRAPH capture does not apply to this path. */
+#define CGMR_GNC_TLS 0
+#define CGMR_GNC_GM 1
+typedef struct cgmr_gnc_params {
+  int32_t loss;                 /* CGMR_GNC_TLS or CGMR_GNC_GM */
+  double mu_factor;             /* > 1; default 1.4 */
+  int32_t max_outer;            /* >= 1; default 100 */
+  int32_t inner_iters;          /* >= 1; default 1 */
+  int32_t outer_per_wait;       /* >= 1; default 8 */
+  const double* barc_sq;        /* [nE] host, nullable: default_barc_sq for every edge */
+  double default_barc_sq;       /* <= 0: the chi2 0.99 quantile of the factor's dimension (11.344866730144373, 9.21034037197618, 6.634896601021213 for 3, 2, 1) */
+  const uint8_t* known_inlier;  /* [nE] host, nullable: none */
+  double* weight_out;           /* [nE] host, nullable */
+  double* edge_chi2_out;        /* [nE] host, nullable */
+} cgmr_gnc_params;
+/* TLS, 1.4, 100, 1, 8, no arrays, default_barc_sq 0 (by dimension) */
+cgmr_gnc_params cgmr_gnc_params_default(void);
+/*   params   nullable: the defaults;  types  nullable: every vertex a pose, every edge an EDGE_SE2
+ *   mu_out [max_outer], cost_out [max_outer + 1], partial_out [max_outer], outer_done: nullable */
+int cgmr_gnc_optimize(cgmr_ctx* ctx, int nV, double* poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                      const int32_t* to_idx, const double* meas_xyt, const double* info_upper, const cgmr_factor_types* types,
+                      const cgmr_gnc_params* params, double* mu_out, double* cost_out, int32_t* partial_out, int32_t* outer_done);
+/* Device-resident variant (d_poses / d_meas / d_info on the context's device; the per-edge parameter arrays stay host memory):
+ * bit-identical to the host variant. */
+int cgmr_gnc_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                          const int32_t* to_idx, const double* d_meas_xyt, const double* d_info_upper,
+                          const cgmr_factor_types* types, const cgmr_gnc_params* params, double* mu_out, double* cost_out,
+                          int32_t* partial_out, int32_t* outer_done);
+/* The last cgmr_gnc_optimize* call on this context: out[0] = host waits for the device, out[1] = inner iterations run. */
+int cgmr_gnc_last_stats(const cgmr_ctx* ctx, int64_t out[2]);
 int cgmr_marginals_typed(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
                          const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt, const double* info_upper,
                          int nK, const int32_t* query_idx, double* cov_out, const cgmr_factor_types* types,

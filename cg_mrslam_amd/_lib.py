@@ -47,6 +47,8 @@ _SYMBOLS = [
     "cgmr_marginals_joint", "cgmr_marginals_pairs", "cgmr_relative_covariance",
     "cgmr_marginals_joint_typed", "cgmr_marginals_pairs_typed", "cgmr_observation_covariance",
     "cgmr_gnc_params_default", "cgmr_gnc_optimize", "cgmr_gnc_optimize_dev", "cgmr_gnc_last_stats",
+    "cgmr_graph_set_edge_gnc", "cgmr_graph_set_received_gnc", "cgmr_graph_optimize_gnc", "cgmr_graph_gnc_weights",
+    "cgmr_graph_keep_gnc_weights", "cgmr_graph_set_condensed_gnc",
 ]
 
 JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)

@@ -185,6 +185,66 @@ class RobotGraph:
         self._check(self.lib.cgmr_graph_edge_stats(self.h, C.c_int(n), _p(e2), _p(w)))
         return e2, w
 
+    # ------------------------------------------------------------------ graduated non-convexity
+    def set_edge_gnc(self, barc_sq=None, known_inliers=None, first: int = 0, n: int | None = None):
+        """GNC parameters of own edges [first, first + n) by insertion index (n None: to the last one, or the length of an
+        array given): ``barc_sq`` a scalar, an array or None (the default: the chi2 0.99 quantile, or the call's
+        ``default_barc_sq``); ``known_inliers`` a mask of length n, a list of indices into the range, or None (all free).
+        Edges added later are default and free."""
+        from ._lib import gnc_known_mask
+        if n is None:
+            if barc_sq is not None and np.ndim(barc_sq) == 1:
+                n = len(barc_sq)
+            elif known_inliers is not None and np.asarray(known_inliers).dtype in (np.bool_, np.uint8):
+                n = len(known_inliers)
+            else:
+                n = self.counts()["own_edges"] - first
+        c = None if barc_sq is None else np.ascontiguousarray(np.broadcast_to(np.asarray(barc_sq, dtype=np.float64), (n,)))
+        k = None if known_inliers is None else gnc_known_mask(known_inliers, n)
+        self._check(self.lib.cgmr_graph_set_edge_gnc(self.h, C.c_int(first), C.c_int(n), _p(c) if c is not None else C.c_void_p(0),
+                                                     _p(k) if k is not None else C.c_void_p(0)))
+
+    def set_received_gnc(self, barc_sq: float = 0.0, known_inlier: bool = False):
+        """One GNC class for every edge received from the peers: ``barc_sq`` (0: the default), known inlier or free."""
+        self._check(self.lib.cgmr_graph_set_received_gnc(self.h, C.c_double(float(barc_sq)), C.c_int(1 if known_inlier else 0)))
+
+    def optimize_gnc(self, loss="tls", max_outer: int = 100, default_barc_sq: float = 0.0, raise_on_cholesky: bool = True, **params):
+        """Graduated non-convexity on the system ``optimize`` would solve now (cgmr_graph_optimize_gnc): ``loss`` "tls" or "gm";
+        ``params``: mu_factor, inner_iters, outer_per_wait.  Returns a dict shaped like ``Context.gnc_optimize``'s: status, mu
+        [max_outer], cost [max_outer + 1], partial [max_outer], outer_done, weights and edge_chi2 of every edge (own edges, then
+        the received ones).  The own edges' weights stay with the graph (``gnc_weights``)."""
+        from ._lib import GNC_DEFAULTS, GncParams, gnc_loss_code
+        bad = set(params) - set(GNC_DEFAULTS)
+        if bad:
+            raise TypeError(f"unknown GNC parameter(s): {sorted(bad)}")
+        v = dict(GNC_DEFAULTS, **params)
+        mo = max(int(max_outer), 1)
+        mu, cost, partial, done = np.zeros(mo), np.zeros(mo + 1), np.zeros(mo, dtype=np.int32), C.c_int32(0)
+        prm = GncParams(gnc_loss_code(loss), float(v["mu_factor"]), int(max_outer), int(v["inner_iters"]), int(v["outer_per_wait"]),
+                        None, float(default_barc_sq), None, None, None)
+        rc = self.lib.cgmr_graph_optimize_gnc(self.h, C.byref(prm), _p(mu), _p(cost), _p(partial), C.byref(done))
+        self._check(rc, allow_cholesky=not raise_on_cholesky)
+        st = self.edge_stats()
+        e2, w = st if st is not None else (np.zeros(0), np.zeros(0))
+        return dict(status=rc, mu=mu, cost=cost, partial=partial, outer_done=int(done.value), weights=w, edge_chi2=e2)
+
+    def gnc_weights(self):
+        """The stored GNC weight of every own edge: 1 before any ``optimize_gnc`` and for edges added since the last one."""
+        n = self._check(self.lib.cgmr_graph_gnc_weights(self.h, C.c_int(0), C.c_void_p(0)))
+        w = np.zeros(n)
+        if n:
+            self._check(self.lib.cgmr_graph_gnc_weights(self.h, C.c_int(n), _p(w)))
+        return w
+
+    def keep_gnc_weights(self, on: bool):
+        """``optimize`` (Gauss-Newton) scales every own edge by its stored GNC weight (cgmr_graph_keep_gnc_weights; default off)."""
+        self._check(self.lib.cgmr_graph_keep_gnc_weights(self.h, C.c_int(1 if on else 0)))
+
+    def set_condensed_gnc(self, on: bool, drop_below: float = 0.0):
+        """Build every condensed graph without the own edges of stored weight 0 or below ``drop_below``, the others scaled by
+        their weight (cgmr_graph_set_condensed_gnc; default off: the plain condensed graphs, byte for byte)."""
+        self._check(self.lib.cgmr_graph_set_condensed_gnc(self.h, C.c_int(1 if on else 0), C.c_double(float(drop_below))))
+
     def lm_last(self):
         """Records of the last Levenberg-Marquardt solve: (lambdas, trials), one entry per iteration run."""
         n = self._check(self.lib.cgmr_graph_lm_last(self.h, C.c_int(0), C.c_void_p(0), C.c_void_p(0)))

@@ -1819,6 +1819,53 @@ struct GncPolicy {
   }
 };
 
+bool gnc_params_ok(const cgmr_gnc_params* params) {
+  if (!params) return true;
+  const cgmr_gnc_params& P = *params;
+  return (P.loss == CGMR_GNC_TLS || P.loss == CGMR_GNC_GM) && std::isfinite(P.mu_factor) && P.mu_factor > 1 && P.max_outer >= 1 &&
+         P.inner_iters >= 1 && P.outer_per_wait >= 1 && std::isfinite(P.default_barc_sq);
+}
+cgmr_gnc_params gnc_params_default() { return gnc_defaults(); }
+double gnc_default_barc_sq(int dim) {
+  const double quantile[4] = {0.0, 6.634896601021213, 9.21034037197618, 11.344866730144373};   // chi2 0.99, by dimension
+  return quantile[dim < 1 ? 1 : dim > 3 ? 3 : dim];
+}
+
+// The driver of cgmr_gnc_optimize* and cgmr_graph_optimize_gnc: the arena, the per-edge arrays up, tr_run with GncPolicy, then
+// the final statistics at the poses the call returns, with the weights of its last outer iteration.
+int gnc_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
+            const GnEdges& Ed, const cgmr_gnc_params& P, const double* barc_sq, const uint8_t* known, double* mu_out,
+            double* cost_out, int32_t* partial_out, int32_t* outer_done, double* weight_out, double* edge_chi2_out,
+            const int32_t* hub_vertices, int n_hub_vertices) {
+  hipStream_t st = ctx->stream;
+  GncPolicy pol{P, mu_out, cost_out, partial_out, outer_done, GncDev(), GncLayout(P.max_outer, nV, nE)};
+  int r = arena_reserve(ctx, ctx->gnc_arena, pol.lay.bytes);
+  if (r) return r;
+  char* d = ctx->gnc_arena.ptr;
+  GncDev& L = pol.L;
+  L.S = (GncState*)d; L.rec_mu = (double*)(d + pol.lay.o_mu); L.rec_cost = (double*)(d + pol.lay.o_cost);
+  L.rec_partial = (int32_t*)(d + pol.lay.o_part); L.saved = (double*)(d + pol.lay.o_saved); L.weight = (double*)(d + pol.lay.o_w);
+  L.barc_sq = (double*)(d + pol.lay.o_c); L.r = (double*)(d + pol.lay.o_r); L.part = (double*)(d + pol.lay.o_wg);
+  L.known = (uint8_t*)(d + pol.lay.o_known);
+  if (nE > 0) {   // (pageable host memory: the copies have left the arrays when they return)
+    HIP_TRY(ctx, hipMemcpyAsync(L.barc_sq, barc_sq, 8 * (size_t)nE, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(L.known, known, (size_t)nE, hipMemcpyHostToDevice, st));
+  }
+  r = tr_run(ctx, pol, nV, d_poses, fixed, nE, ef, et, Ed, P.max_outer, hub_vertices, n_hub_vertices);
+  if (r != CGMR_OK && r > CGMR_E_CHOLESKY_BASE) return r;
+  // the final statistics, at the poses the call returns and with the weights of its last outer iteration
+  GnDevice& D = ctx->gn;
+  double cost_end = 0.0;
+  launch_linearize(st, D, d_poses, pol.edges(Ed, kGncReuse, L.r), 1);
+  launch_chi2(st, D, D.chi2);
+  HIP_TRY(ctx, hipMemcpyAsync(&cost_end, D.chi2, sizeof(double), hipMemcpyDeviceToHost, st));
+  if (nE > 0 && weight_out) HIP_TRY(ctx, hipMemcpyAsync(weight_out, L.weight, 8 * (size_t)nE, hipMemcpyDeviceToHost, st));
+  if (nE > 0 && edge_chi2_out) HIP_TRY(ctx, hipMemcpyAsync(edge_chi2_out, L.r, 8 * (size_t)nE, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (cost_out) for (int k = pol.ran; k <= P.max_outer; k++) cost_out[k] = cost_end;
+  return r;
+}
+
 // dimension of an edge kind's factor (include/cgmr.h: CGMR_EDGE_*)
 static int factor_dim(int kind) { return kind == 2 ? 1 : (kind == 1 || kind == 4) ? 2 : 3; }
 
@@ -1845,33 +1892,8 @@ static int gnc_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t
     if (P.known_inlier) hk[k] = P.known_inlier[k] ? 1 : 0;
   }
   rc = optimize_staged(ctx, who, dev, true, nV, poses, nE, meas, info, nullptr, &typed, [&](double* d_poses, const GnEdges& Ed) {
-    hipStream_t st = ctx->stream;
-    GncPolicy pol{P, mu_out, cost_out, partial_out, outer_done, GncDev(), GncLayout(P.max_outer, nV, nE)};
-    int r = arena_reserve(ctx, ctx->gnc_arena, pol.lay.bytes);
-    if (r) return r;
-    char* d = ctx->gnc_arena.ptr;
-    GncDev& L = pol.L;
-    L.S = (GncState*)d; L.rec_mu = (double*)(d + pol.lay.o_mu); L.rec_cost = (double*)(d + pol.lay.o_cost);
-    L.rec_partial = (int32_t*)(d + pol.lay.o_part); L.saved = (double*)(d + pol.lay.o_saved); L.weight = (double*)(d + pol.lay.o_w);
-    L.barc_sq = (double*)(d + pol.lay.o_c); L.r = (double*)(d + pol.lay.o_r); L.part = (double*)(d + pol.lay.o_wg);
-    L.known = (uint8_t*)(d + pol.lay.o_known);
-    if (nE > 0) {   // (pageable host memory: the copies have left the vectors when they return)
-      HIP_TRY(ctx, hipMemcpyAsync(L.barc_sq, hc.data(), 8 * (size_t)nE, hipMemcpyHostToDevice, st));
-      HIP_TRY(ctx, hipMemcpyAsync(L.known, hk.data(), (size_t)nE, hipMemcpyHostToDevice, st));
-    }
-    r = tr_run(ctx, pol, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, P.max_outer, nullptr, 0);
-    if (r != CGMR_OK && r > CGMR_E_CHOLESKY_BASE) return r;
-    // the final statistics, at the poses the call returns and with the weights of its last outer iteration
-    GnDevice& D = ctx->gn;
-    double cost_end = 0.0;
-    launch_linearize(st, D, d_poses, pol.edges(Ed, kGncReuse, L.r), 1);
-    launch_chi2(st, D, D.chi2);
-    HIP_TRY(ctx, hipMemcpyAsync(&cost_end, D.chi2, sizeof(double), hipMemcpyDeviceToHost, st));
-    if (nE > 0 && P.weight_out) HIP_TRY(ctx, hipMemcpyAsync(P.weight_out, L.weight, 8 * (size_t)nE, hipMemcpyDeviceToHost, st));
-    if (nE > 0 && P.edge_chi2_out) HIP_TRY(ctx, hipMemcpyAsync(P.edge_chi2_out, L.r, 8 * (size_t)nE, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (cost_out) for (int k = pol.ran; k <= P.max_outer; k++) cost_out[k] = cost_end;
-    return r;
+    return gnc_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, P, hc.data(), hk.data(), mu_out, cost_out, partial_out, outer_done,
+                   P.weight_out, P.edge_chi2_out);
   });
   return rc;
 }
@@ -1882,7 +1904,7 @@ using namespace cgmr;
 
 extern "C" {
 
-int cgmr_version(void) { return 105; }   // 105: cgmr_*_optimize_robust*, cgmr_graph_set_edge_robust / _set_received_robust / _edge_stats added, later (same number: callers find them by their symbols) cgmr_marginals_robust, cgmr_marginals_all_robust, cgmr_covariance_estimate_robust, cgmr_condense_robust, cgmr_graph_set_condensed_robust, cgmr_dl_optimize*, cgmr_dl_last_stats, cgmr_graph_set_dogleg_params, cgmr_graph_dl_last (CGMR_ALG_DOGLEG), cgmr_marginals_joint, cgmr_marginals_pairs, cgmr_relative_covariance, cgmr_*_optimize_typed*, cgmr_marginals_typed, cgmr_marginals_all_typed, cgmr_marginals_joint_typed, cgmr_marginals_pairs_typed, cgmr_observation_covariance (and edge kind 2, CGMR_EDGE_BEARING_SE2_XY); 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
+int cgmr_version(void) { return 105; }   // 105: cgmr_*_optimize_robust*, cgmr_graph_set_edge_robust / _set_received_robust / _edge_stats added, later (same number: callers find them by their symbols) cgmr_marginals_robust, cgmr_marginals_all_robust, cgmr_covariance_estimate_robust, cgmr_condense_robust, cgmr_graph_set_condensed_robust, cgmr_dl_optimize*, cgmr_dl_last_stats, cgmr_graph_set_dogleg_params, cgmr_graph_dl_last (CGMR_ALG_DOGLEG), cgmr_marginals_joint, cgmr_marginals_pairs, cgmr_relative_covariance, cgmr_*_optimize_typed*, cgmr_marginals_typed, cgmr_marginals_all_typed, cgmr_marginals_joint_typed, cgmr_marginals_pairs_typed, cgmr_observation_covariance (and edge kind 2, CGMR_EDGE_BEARING_SE2_XY), cgmr_gnc_optimize*, cgmr_gnc_last_stats, cgmr_graph_set_edge_gnc / _set_received_gnc / _optimize_gnc / _gnc_weights / _keep_gnc_weights / _set_condensed_gnc; 104: cgmr_lm_optimize*, cgmr_lm_last_stats, cgmr_graph_set_algorithm / _lm_last added; 103: cgmr_marginals_all added; 102 (round 5): cgmr_match_last_redo_pairs / _path_counts, cgmr_graph_failed_batches, cgmr_comm_info added; nothing changed or removed
 
 int cgmr_ctx_create(int device, void* hip_stream, cgmr_ctx** out) {
   if (!out) return CGMR_E_INVALID;

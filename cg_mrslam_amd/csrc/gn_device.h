@@ -79,7 +79,10 @@ struct GnEdges {
   // GNC weight -- computed from gnc_state->mu and stored in gnc_weight (gnc_mode kGncCompute), read from there (kGncReuse), or
   // 1 (kGncPlain); gnc_c [nE] barc^2, gnc_known [nE] the known-inlier mask, gnc_r (nullable) receives e^T Omega e of every edge
   // (device memory).  One job, never with `robust`.
+  // gnc_own_only: the robot graph's condensed batches under stored weights -- kGncReuse, gnc_weight [nA] shared by every job
+  // of the view (the batched instance, whatever the job count), edges [nA, nE) weight 1; nothing else of the description is read.
   bool gnc = false;
+  bool gnc_own_only = false;
   int gnc_mode = 0;
   double* gnc_weight = nullptr;
   const double* gnc_c = nullptr;

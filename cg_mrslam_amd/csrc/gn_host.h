@@ -108,6 +108,20 @@ int dl_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
            int32_t* step_out, int32_t* iters_done, const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0);
 // null, or parameters dl_run accepts
 bool dl_params_ok(const cgmr_dl_params* params);
+// Graduated non-convexity with Gauss-Newton inside (include/cgmr.h: cgmr_gnc_optimize), on the same structure preparation:
+// P checked by the caller (its per-edge pointers are not read), barc_sq / known host arrays [nE] (every entry set), Ed without a
+// robust description.  Outputs mu_out [max_outer], cost_out [max_outer + 1], partial_out [max_outer], *outer_done, and -- host
+// memory, written when the call ends well or with a Cholesky code, behind the call's own final wait -- weight_out /
+// edge_chi2_out [nE] (all nullable).  CGMR_E_CHOLESKY_BASE - i: the poses are those of the last good update.
+int gnc_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
+            const GnEdges& Ed, const cgmr_gnc_params& P, const double* barc_sq, const uint8_t* known, double* mu_out,
+            double* cost_out, int32_t* partial_out, int32_t* outer_done, double* weight_out, double* edge_chi2_out,
+            const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0);
+// null, or parameters gnc_run accepts (the per-edge pointers aside); the defaults
+bool gnc_params_ok(const cgmr_gnc_params* params);
+cgmr_gnc_params gnc_params_default();
+// the chi2 0.99 quantile of a factor of dimension 1..3: the default barc^2
+double gnc_default_barc_sq(int dim);
 // SparseOptimizer::computeInitialGuess from the fixed vertices over the given edges [g2o-recalled]
 void initial_guess_host(int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
                         const double* meas);

@@ -186,8 +186,11 @@ struct TypedArgs {
 // point's edges it is still the block's H_xx and the argument above holds; with w = 0 on all of a point's (or a pose's) edges
 // the block is zero, the pivot is not positive, and the call ends with a Cholesky code.  mode: kGncCompute stores w (unless the
 // call is over: a queued launch behind the end changes nothing), kGncReuse reads the stored one, kGncPlain takes 1.
+// BATCH and GNC together (the robot graph's condensed graphs without the rejected edges, cgmr_graph_set_condensed_gnc): stored
+// weights only -- weight [nA], a snapshot that went up with the batch's staging block and that every job reads where it lies;
+// edges [nA, nE) are switched off in those passes and take 1.  A weight of 0 leaves exact zeros, a weight of 1 the plain terms.
 struct GncArgs {
-  double* weight;          // [nE]
+  double* weight;          // [nE] (a batch: [nA])
   const double* barc_sq;   // [nE]
   const uint8_t* known;    // [nE]: 1 = known inlier, weight 1
   const GncState* S;
@@ -208,7 +211,7 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
                                                    Rk... rk_pack) {
   constexpr bool TYPED = pack_has<TypedArgs, Rk...>::value;
   constexpr bool GNC = pack_has<GncArgs, Rk...>::value;
-  static_assert(sizeof...(Rk) == (ROBUST ? 1 : 0) + (TYPED ? 1 : 0) + (GNC ? 1 : 0) && !(ROBUST && GNC) && !(BATCH && GNC),
+  static_assert(sizeof...(Rk) == (ROBUST ? 1 : 0) + (TYPED ? 1 : 0) + (GNC ? 1 : 0) && !(ROBUST && GNC) && !(BATCH && GNC && TYPED),
                 "k_linearize: one RobustArgs in the robust instances, one TypedArgs in the typed ones, one GncArgs in the GNC ones");
   CGMR_JOB(poses, ps); CGMR_JOB(term, js);
   __shared__ double s_chi[4];
@@ -262,14 +265,20 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
     if constexpr (GNC) {
       const GncArgs ga = pick_arg<GncArgs>(rk_pack...);
       const double r = e[0] * Oe[0] + e[1] * Oe[1] + e[2] * Oe[2];
-      if (ga.mode == kGncReuse) {
-        rho1 = ga.weight[k];
-      } else if (ga.mode == kGncCompute) {
-        const GncState* S = ga.S;
-        if (!ga.known[k] && !S->nothing) rho1 = gnc_weight(S->loss, S->mu, ga.barc_sq[k], r);
-        if (k0 < nE && !S->done) ga.weight[k] = rho1;
+      if constexpr (BATCH) {
+        // the robot graph's condensed graphs under stored GNC weights (cgmr_graph_set_condensed_gnc): kGncReuse only, one
+        // weight per own edge, shared by the jobs (not moved by the job stride); S, barc_sq, known and r_out are null
+        rho1 = k < nA ? ga.weight[k] : 1.0;
+      } else {
+        if (ga.mode == kGncReuse) {
+          rho1 = ga.weight[k];
+        } else if (ga.mode == kGncCompute) {
+          const GncState* S = ga.S;
+          if (!ga.known[k] && !S->nothing) rho1 = gnc_weight(S->loss, S->mu, ga.barc_sq[k], r);
+          if (k0 < nE && !S->done) ga.weight[k] = rho1;
+        }
+        if (ga.r_out && k0 < nE) ga.r_out[k] = r;
       }
-      if (ga.r_out && k0 < nE) ga.r_out[k] = r;
       ch = live ? rho1 * r : 0.0;
     }
 #pragma unroll
@@ -1668,10 +1677,16 @@ void launch_linearize(hipStream_t st, const GnDevice& D, const double* poses, co
   gn_init_kernels();
   const dim3 grid((D.nE + 255) / 256, 1, D.njobs);
   const size_t lds = chi_only ? 0 : 256 * 33 * sizeof(double);
-  if (Ed.gnc) {                       // (never a batch, never robust: cgmr_gnc_optimize runs one job)
+  if (Ed.gnc) {                       // (never robust; a batch: the stored weights of the own edges, never typed)
     GncArgs ga;
     ga.weight = Ed.gnc_weight; ga.barc_sq = Ed.gnc_c; ga.known = Ed.gnc_known; ga.S = Ed.gnc_state; ga.r_out = Ed.gnc_r;
     ga.mode = Ed.gnc_mode;
+    if (Ed.gnc_own_only) {            // (also a batch of one: the weight array ends with the own edges)
+      ga.barc_sq = nullptr; ga.known = nullptr; ga.S = nullptr; ga.r_out = nullptr; ga.mode = kGncReuse;
+      hipLaunchKernelGGL((k_linearize<true, false, GncArgs>), grid, dim3(256), lds, st, D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et,
+                         Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride, D.pose_stride, ga);
+      return;
+    }
     if (Ed.typed) {
       TypedArgs ty;
       ty.edge_kind = Ed.edge_kind;
@@ -1748,7 +1763,8 @@ void gn_init_kernels() {
                           reinterpret_cast<const void*>(k_linearize<false, true, RobustArgs, TypedArgs>),
                           reinterpret_cast<const void*>(k_linearize<true, true, RobustArgs, TypedArgs>),
                           reinterpret_cast<const void*>(k_linearize<false, false, GncArgs>),
-                          reinterpret_cast<const void*>(k_linearize<false, false, TypedArgs, GncArgs>)})
+                          reinterpret_cast<const void*>(k_linearize<false, false, TypedArgs, GncArgs>),
+                          reinterpret_cast<const void*>(k_linearize<true, false, GncArgs>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 33 * (int)sizeof(double));
     for (const void* f : {reinterpret_cast<const void*>(k_top_block<false>), reinterpret_cast<const void*>(k_top_block<true>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, top_smem_bytes(kTopMaxCols));

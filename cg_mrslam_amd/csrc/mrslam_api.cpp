@@ -21,6 +21,7 @@
 
 #include "cgmr_ctx.h"
 #include "gn_host.h"
+#include "gnc_device.h"
 #include "mrslam_device.h"
 
 using namespace cgmr;
@@ -119,6 +120,17 @@ struct cgmr_graph {
   double rk_recv_delta = 1.0;
   std::vector<double> rk_stats;
   bool cond_robust = false;           // cgmr_graph_set_condensed_robust: the condensed graphs take the own edges' kernels
+  // graduated non-convexity (cgmr_graph_optimize_gnc): per own edge barc^2 (0: the call's default), the known-inlier flag and
+  // the stored weight (1 until a GNC solve ends well; the last outer iteration's then); the received edges' class.  The weights
+  // live on the host: cgmr_graph_optimize (keep_gnc_weights) and every condensed batch (cond_gnc) send up a copy of their own
+  std::vector<double> gnc_c, gnc_w, gnc_w_up;
+  std::vector<uint8_t> gnc_known;
+  double gnc_recv_c = 0.0;
+  bool gnc_recv_known = false;
+  bool gnc_keep = false;              // cgmr_graph_keep_gnc_weights
+  bool cond_gnc = false;              // cgmr_graph_set_condensed_gnc: the condensed graphs leave the rejected own edges out
+  double cond_drop_below = 0.0;
+  DevBuf d_gnc_w;                     // the weights of a keep_gnc_weights solve: own edges, then ones for the received
   std::vector<double> lm_lambda;      // records of the last Levenberg solve (cgmr_graph_lm_last)
   std::vector<int32_t> lm_trials;
   std::vector<double> dl_delta;       // records of the last dogleg solve (cgmr_graph_dl_last)
@@ -173,6 +185,40 @@ int dev_grow(cgmr_graph* g, DevBuf& B, size_t used_bytes, size_t need_bytes) {
 }
 
 size_t round256(size_t v) { return (v + 255) & ~size_t(255); }
+
+// the gauge vertices of the stars received from the peers (every received edge starts at one), in order of first appearance
+std::vector<int32_t> received_hubs(const cgmr_graph* g) {
+  std::vector<int32_t> hubs;
+  for (int p = 0; p < g->n_robots; p++)
+    for (int32_t v : g->in[p].from_idx) if (std::find(hubs.begin(), hubs.end(), v) == hubs.end()) hubs.push_back(v);
+  return hubs;
+}
+
+// the page-locked landing zone of a solve's pose read-back, for nV poses
+int pinned_poses_reserve(cgmr_graph* g, int nV) {
+  if ((size_t)nV <= g->pinned_poses_cap) return 0;
+  cgmr_ctx* ctx = g->ctx;
+  if (g->pinned_poses) (void)hipHostFree(g->pinned_poses);
+  g->pinned_poses = nullptr;
+  g->pinned_poses_cap = (size_t)nV + (size_t)nV / 2 + 1024;
+  HIP_TRY(ctx, hipHostMalloc((void**)&g->pinned_poses, 24 * g->pinned_poses_cap, hipHostMallocDefault));
+  return 0;
+}
+
+// some own edge, or the received class, carries a robust kernel other than none
+bool any_robust_kernel(const cgmr_graph* g) {
+  if (g->rk_recv_kind != CGMR_RK_NONE) return true;
+  for (uint8_t k : g->rk_kind) if (k != CGMR_RK_NONE) return true;
+  return false;
+}
+
+// The stored GNC weights as a condensed pass takes them (cgmr_graph_set_condensed_gnc): below drop_below, or zero, the edge is
+// removed (0); the others keep their weight.
+std::vector<double> cond_gnc_weights(const cgmr_graph* g) {
+  std::vector<double> w(g->gnc_w);
+  for (double& x : w) if (x < g->cond_drop_below || x == 0.0) x = 0.0;
+  return w;
+}
 
 // the robust kinds / deltas of own edges [first, first + n) to the device arrays (grown to every own edge)
 int rk_upload(cgmr_graph* g, int first, int n) {
@@ -241,8 +287,10 @@ int alloc_fixed(cgmr_graph* g) {
 // the ONE Gauss-Newton iteration that follows starts far from the optimum and amplifies any rounding difference of its
 // linearisation point by cond(H): the condensed measurements of the two forms agree to ~1e-8 m (libm again every eighth
 // tree level did not change that: it is not drift), well inside the 1e-6 parity bar against the oracle.
+// wt (nullable): per own edge its weight in the pass that follows -- an edge of weight 0 is not in that pass's graph and is
+// not walked (a rejected closure would carry half the tree to a wrong place); a vertex the tree then misses keeps its estimate.
 void initial_guess_own_edges(const cgmr_graph* g, int root, double* poses, std::vector<int32_t>& queue, std::vector<double>& cs,
-                             std::vector<uint8_t>& seen) {
+                             std::vector<uint8_t>& seen, const double* wt = nullptr) {
   const int nV = (int)g->ids.size();
   const double pi = 3.14159265358979323846;
   seen.assign(nV, 0);
@@ -259,6 +307,7 @@ void initial_guess_own_edges(const cgmr_graph* g, int root, double* poses, std::
     const double cu = cs[2 * (size_t)u], su = cs[2 * (size_t)u + 1];
     for (int32_t it = g->adj_head[u]; it >= 0; it = g->adj_next[it]) {
       const int k = it >> 1;
+      if (wt && wt[k] == 0.0) continue;
       const int w = (g->ef[k] == u) ? g->et[k] : g->ef[k];
       if (seen[w]) continue;
       seen[w] = 1;
@@ -413,7 +462,7 @@ void cgmr_graph_destroy(cgmr_graph* g) {
     (void)hipSetDevice(g->ctx->device);
     (void)hipStreamSynchronize(g->ctx->stream);
     (void)side_join_host(g->ctx);
-    for (DevBuf* b : {&g->d_poses, &g->d_meas_a, &g->d_info_a, &g->d_vids, &g->d_rk_kind, &g->d_rk_delta})
+    for (DevBuf* b : {&g->d_poses, &g->d_meas_a, &g->d_info_a, &g->d_vids, &g->d_rk_kind, &g->d_rk_delta, &g->d_gnc_w})
       if (b->ptr) (void)hipFree(b->ptr);
     // the blocks this graph's arrays have outgrown (nothing of it is in flight any more: both streams were waited for above)
     auto& gy = g->ctx->graveyard;
@@ -496,6 +545,9 @@ int cgmr_graph_add_edges(cgmr_graph* g, int n, const int32_t* from_ids, const in
   }
   g->rk_kind.resize(g->ef.size(), CGMR_RK_NONE);
   g->rk_delta.resize(g->ef.size(), 1.0);
+  g->gnc_c.resize(g->ef.size(), 0.0);
+  g->gnc_known.resize(g->ef.size(), 0);
+  g->gnc_w.resize(g->ef.size(), 1.0);
   if (g->rk_dev && n > 0) {
     int rc = rk_upload(g, (int)e0, n);
     if (rc) return rc;
@@ -545,19 +597,31 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out) {
       Ed.rk_stats = (double*)ctx->rk_arena.ptr;
     }
   }
+  if (g->gnc_keep) {                  // cgmr_graph_keep_gnc_weights: every own edge scaled by its stored weight (kGncReuse)
+    if (g->algorithm != CGMR_ALG_GAUSS_NEWTON)
+      return gerr(g, CGMR_E_INVALID, "cgmr_graph_optimize: the stored GNC weights (cgmr_graph_keep_gnc_weights) go with Gauss-Newton only");
+    if (any_robust_kernel(g))
+      return gerr(g, CGMR_E_INVALID, "cgmr_graph_optimize: the stored GNC weights (cgmr_graph_keep_gnc_weights) are not combined with robust kernels");
+    Ed.robust = false;
+    Ed.rk_kind = nullptr; Ed.rk_delta = nullptr; Ed.rk_stats = nullptr;
+    if (nE > 0) {
+      int rc = dev_grow(g, g->d_gnc_w, 0, 8 * (size_t)nE);
+      if (rc) return rc;
+      g->gnc_w_up = g->gnc_w;         // (a member: it outlives the copy, and the solve's final wait comes before the next one)
+      g->gnc_w_up.resize((size_t)nE, 1.0);
+      HIP_TRY(ctx, hipMemcpyAsync(g->d_gnc_w.ptr, g->gnc_w_up.data(), 8 * (size_t)nE, hipMemcpyHostToDevice, ctx->stream));
+      Ed.gnc = true; Ed.gnc_mode = kGncReuse; Ed.gnc_weight = (double*)g->d_gnc_w.ptr;
+    }
+  }
   const double t0 = wall_s();
   // the gauge vertices of the stars received from the peers (every received edge starts at one): hubs of the ordering
-  std::vector<int32_t> hubs;
-  for (int p = 0; p < g->n_robots; p++)
-    for (int32_t v : g->in[p].from_idx) if (std::find(hubs.begin(), hubs.end(), v) == hubs.end()) hubs.push_back(v);
+  const std::vector<int32_t> hubs = received_hubs(g);
   // the host copy of the estimates comes back in the solve's own final wait: the condensed graphs that follow pick their
   // gauges from it, the caller's next key frame dead-reckons from it (cgmr_graph_get_poses: no device round trip then)
   const bool asked = true;
-  if ((size_t)nV > g->pinned_poses_cap) {
-    if (g->pinned_poses) (void)hipHostFree(g->pinned_poses);
-    g->pinned_poses = nullptr;
-    g->pinned_poses_cap = (size_t)nV + (size_t)nV / 2 + 1024;
-    HIP_TRY(ctx, hipHostMalloc((void**)&g->pinned_poses, 24 * g->pinned_poses_cap, hipHostMallocDefault));
+  {
+    int rc = pinned_poses_reserve(g, nV);
+    if (rc) return rc;
   }
   ctx->poses_out_host = g->pinned_poses;
   int rc;
@@ -647,8 +711,111 @@ int cgmr_graph_set_received_robust(cgmr_graph* g, int kind, double delta) {
 
 int cgmr_graph_set_condensed_robust(cgmr_graph* g, int on) {
   if (!g) return CGMR_E_INVALID;
+  if (on && g->cond_gnc)
+    return gerr(g, CGMR_E_INVALID, "cgmr_graph_set_condensed_robust: refused while cgmr_graph_set_condensed_gnc is on (the GNC instances take no robust kernel)");
   g->cond_robust = on != 0;
   return CGMR_OK;
+}
+
+int cgmr_graph_set_edge_gnc(cgmr_graph* g, int first, int n, const double* barc_sq, const uint8_t* known_inlier) {
+  if (!g || first < 0 || n < 0 || (size_t)first + (size_t)n > g->ef.size()) return CGMR_E_INVALID;
+  for (int k = 0; barc_sq && k < n; k++)
+    if (!std::isfinite(barc_sq[k]) || !(barc_sq[k] > 0))
+      return gerr(g, CGMR_E_INVALID, "cgmr_graph_set_edge_gnc: barc_sq must be finite and > 0");
+  for (int k = 0; k < n; k++) {
+    g->gnc_c[first + k] = barc_sq ? barc_sq[k] : 0.0;
+    g->gnc_known[first + k] = known_inlier && known_inlier[k] ? 1 : 0;
+  }
+  return CGMR_OK;
+}
+
+int cgmr_graph_set_received_gnc(cgmr_graph* g, double barc_sq, int known_inlier) {
+  if (!g) return CGMR_E_INVALID;
+  if (!std::isfinite(barc_sq) || barc_sq < 0)
+    return gerr(g, CGMR_E_INVALID, "cgmr_graph_set_received_gnc: barc_sq must be finite and > 0, or 0 for the default");
+  g->gnc_recv_c = barc_sq;
+  g->gnc_recv_known = known_inlier != 0;
+  return CGMR_OK;
+}
+
+int cgmr_graph_gnc_weights(const cgmr_graph* g, int cap, double* weight_out) {
+  if (!g || cap < 0 || (cap > 0 && !weight_out)) return CGMR_E_INVALID;
+  const int n = (int)g->gnc_w.size();
+  for (int k = 0; k < std::min(n, cap); k++) weight_out[k] = g->gnc_w[k];
+  return n;
+}
+
+int cgmr_graph_keep_gnc_weights(cgmr_graph* g, int on) {
+  if (!g) return CGMR_E_INVALID;
+  g->gnc_keep = on != 0;
+  return CGMR_OK;
+}
+
+int cgmr_graph_set_condensed_gnc(cgmr_graph* g, int on, double drop_below) {
+  if (!g) return CGMR_E_INVALID;
+  if (on && g->cond_robust)
+    return gerr(g, CGMR_E_INVALID, "cgmr_graph_set_condensed_gnc: refused while cgmr_graph_set_condensed_robust is on (the GNC instances take no robust kernel)");
+  if (on && (!std::isfinite(drop_below) || drop_below < 0 || drop_below > 1))
+    return gerr(g, CGMR_E_INVALID, "cgmr_graph_set_condensed_gnc: drop_below must lie in [0, 1]");
+  g->cond_gnc = on != 0;
+  g->cond_drop_below = on ? drop_below : 0.0;
+  return CGMR_OK;
+}
+
+// cgmr_gnc_optimize (include/cgmr.h; the contract: tests/ref_gnc.py) on the system cgmr_graph_optimize would solve now: own
+// edges, then the received ones; Gauss-Newton inside; the received stars' gauge vertices are hubs of the ordering.
+int cgmr_graph_optimize_gnc(cgmr_graph* g, const cgmr_gnc_params* params, double* mu_out, double* cost_out, int32_t* partial_out,
+                            int32_t* outer_done) {
+  if (!g) return CGMR_E_INVALID;
+  if (!g->ctx) return gerr(g, CGMR_E_NO_DEVICE, "cgmr_graph_optimize_gnc: the graph was created without a device context");
+  cgmr_ctx* ctx = g->ctx;
+  const cgmr_gnc_params P = params ? *params : gnc_params_default();
+  if (!gnc_params_ok(&P))
+    return gerr(g, CGMR_E_INVALID, "cgmr_graph_optimize_gnc: loss must be CGMR_GNC_TLS or CGMR_GNC_GM, mu_factor finite and > 1, max_outer / inner_iters / outer_per_wait >= 1, default_barc_sq finite");
+  if (P.barc_sq || P.known_inlier || P.weight_out || P.edge_chi2_out)
+    return gerr(g, CGMR_E_INVALID, "cgmr_graph_optimize_gnc: the per-edge pointers of the parameters must be null (the graph holds them: cgmr_graph_set_edge_gnc, cgmr_graph_edge_stats, cgmr_graph_gnc_weights)");
+  if (any_robust_kernel(g))
+    return gerr(g, CGMR_E_INVALID, "cgmr_graph_optimize_gnc: not combined with robust kernels (cgmr_graph_set_edge_robust / _set_received_robust)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int nV = (int)g->ids.size(), nE = (int)g->all_ef.size(), nA = (int)g->ef.size();
+  if (outer_done) *outer_done = 0;
+  for (int k = 0; k < P.max_outer; k++) { if (mu_out) mu_out[k] = 0.0; if (partial_out) partial_out[k] = 0; }
+  for (int k = 0; cost_out && k <= P.max_outer; k++) cost_out[k] = 0.0;
+  if (nV == 0) return CGMR_OK;
+  GnEdges Ed;
+  Ed.meas_a = (const double*)g->d_meas_a.ptr; Ed.info_a = (const double*)g->d_info_a.ptr;
+  Ed.meas_b = g->d_meas_b; Ed.info_b = g->d_info_b;
+  Ed.nA = nA; Ed.n_active = nE;
+  g->rk_stats.clear();
+  const double c0 = P.default_barc_sq > 0 ? P.default_barc_sq : gnc_default_barc_sq(3);
+  std::vector<double> hc((size_t)nE), hw((size_t)nE, 1.0), hr((size_t)nE, 0.0);
+  std::vector<uint8_t> hk((size_t)nE);
+  for (int k = 0; k < nE; k++) {
+    const double c = k < nA ? g->gnc_c[k] : g->gnc_recv_c;
+    hc[k] = c > 0 ? c : c0;
+    hk[k] = k < nA ? g->gnc_known[k] : (g->gnc_recv_known ? 1 : 0);
+  }
+  const double t0 = wall_s();
+  const std::vector<int32_t> hubs = received_hubs(g);
+  int rc = pinned_poses_reserve(g, nV);
+  if (rc) return rc;
+  ctx->poses_out_host = g->pinned_poses;                         // (the estimates ride in every wait of the driver: the last one counts)
+  g->lm_lambda.clear(); g->lm_trials.clear(); g->dl_delta.clear(); g->dl_trials.clear(); g->dl_step.clear();
+  rc = gnc_run(ctx, nV, (double*)g->d_poses.ptr, g->fixed.data(), nE, g->all_ef.data(), g->all_et.data(), Ed, P, hc.data(), hk.data(),
+               mu_out, cost_out, partial_out, outer_done, hw.data(), hr.data(), hubs.data(), (int)hubs.size());
+  ctx->poses_out_host = nullptr;
+  const bool ended = rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE;
+  g->h_poses_fresh = ended;
+  if (ended) {
+    memcpy(g->h_poses.data(), g->pinned_poses, 24 * (size_t)nV);
+    g->rk_stats.assign(hr.begin(), hr.end());                     // cgmr_graph_edge_stats: r of every edge, then its weight
+    g->rk_stats.insert(g->rk_stats.end(), hw.begin(), hw.end());
+  }
+  if (rc == CGMR_OK) std::copy(hw.begin(), hw.begin() + nA, g->gnc_w.begin());   // (a Cholesky code leaves the stored weights alone)
+  g->last_optimize_seconds = wall_s() - t0;
+  g->solved_ef = g->all_ef; g->solved_et = g->all_et;
+  g->solved_nV = nV; g->solved_nA = nA;
+  return rc;
 }
 
 int cgmr_graph_edge_stats(const cgmr_graph* g, int cap, double* edge_chi2_out, double* weight_out) {
@@ -741,16 +908,17 @@ struct CondJob {
   std::vector<int32_t> q;             // the other requested vertices (vertex indices, id order)
 };
 
-// The staging block of a batch of nj jobs: masks | initial guesses | query columns | query vertices | job descriptors go up in
-// one copy from pinned memory (the first s_st bytes); the status words (4 per job) come back behind them.
+// The staging block of a batch of nj jobs: masks | initial guesses | query columns | query vertices | job descriptors | the
+// snapshot of the own edges' GNC weights (nw of them; cgmr_graph_set_condensed_gnc, else none) go up in one copy from pinned
+// memory (the first s_st bytes); the status words (4 per job) come back behind them.
 struct CondStage {
-  size_t s_work = 0, s_qc = 0, s_qv = 0, s_jd = 0, s_st = 0, s_end = 0;
+  size_t s_work = 0, s_qc = 0, s_qv = 0, s_jd = 0, s_w = 0, s_st = 0, s_end = 0;
   CondStage() = default;
-  CondStage(int nj, int nf, int nV, int maxq) {
+  CondStage(int nj, int nf, int nV, int maxq, size_t nw) {
     Layout256 L;
     L.add((size_t)nf * nj);                                      // (the masks: offset 0)
     s_work = L.add((size_t)24 * nV * nj); s_qc = L.add((size_t)4 * maxq * nj); s_qv = L.add((size_t)4 * maxq * nj);
-    s_jd = L.add(sizeof(CondJobDev) * (size_t)nj); s_st = L.add(16 * (size_t)nj);
+    s_jd = L.add(sizeof(CondJobDev) * (size_t)nj); s_w = L.add(8 * nw); s_st = L.add(16 * (size_t)nj);
     s_end = L.off;
   }
 };
@@ -766,6 +934,10 @@ struct CondBatch {
   hipStream_t st = nullptr;           // the context's stream, or its side stream for a batch that is not waited for
   GnDevice DB;                        // the batch's view: job 0's, job j moved by j * DB.job_stride
   GnEdges Ed;
+  // cgmr_graph_set_condensed_gnc: the stored weights as they are when the batch is queued, thresholded (cond_gnc_weights) -- the
+  // snapshot the guesses walk and the passes read from the staging block, whatever a later cgmr_graph_optimize_gnc stores
+  bool use_w = false;
+  std::vector<double> wt;
   MargLayout M;                       // one job's marginals work space; job j: moved by j * per_job
   size_t per_job = 0;
   CondStage S;
@@ -809,7 +981,9 @@ int cond_setup(CondBatch& B) {
   for (CondJob& J : B.jobs) B.maxq = std::max(B.maxq, (int)J.q.size());
   B.M = MargLayout(B.maxq, B.nf, ctx->sym.rows.size(), ctx->gn.nfronts, 0, /*flags_first=*/true);
   B.per_job = round256(B.M.end);
-  B.S = CondStage(B.nj, B.nf, B.nV, B.maxq);
+  B.use_w = g->cond_gnc;
+  if (B.use_w) B.wt = cond_gnc_weights(g);
+  B.S = CondStage(B.nj, B.nf, B.nV, B.maxq, B.wt.size());
   rc = arena_reserve(ctx, ctx->mg_arena, B.per_job * (size_t)B.nj + B.S.s_end + 256);
   if (rc) return rc;
   B.d0 = ctx->mg_arena.ptr;
@@ -827,6 +1001,10 @@ int cond_setup(CondBatch& B) {
     Ed.robust = true;
     Ed.rk_kind = (const uint8_t*)g->d_rk_kind.ptr; Ed.rk_delta = (const double*)g->d_rk_delta.ptr;
     Ed.rk_kind0 = CGMR_RK_NONE; Ed.rk_delta0 = 1.0;
+  }
+  if (B.use_w) {                      // the own edges' stored weights (cond_queue binds the staged snapshot)
+    Ed.robust = false;
+    Ed.gnc = true; Ed.gnc_own_only = true; Ed.gnc_mode = kGncReuse;
   }
   return 0;
 }
@@ -867,6 +1045,15 @@ void cond_fill_stage(CondBatch& B) {
   char* h = B.hstage;
   const double tg0 = wall_s();
   static const bool cached_walk = !(getenv("CGMR_GUESS_CACHED") && atoi(getenv("CGMR_GUESS_CACHED")) == 0);
+  // (the general form walks an edge list: the kept own edges, in their order)
+  std::vector<int32_t> kept_ef, kept_et;
+  std::vector<double> kept_meas;
+  if (B.use_w && !cached_walk)
+    for (int k = 0; k < nA; k++)
+      if (B.wt[k] != 0.0) {
+        kept_ef.push_back(g->ef[k]); kept_et.push_back(g->et[k]);
+        kept_meas.insert(kept_meas.end(), g->h_meas.begin() + 3 * (size_t)k, g->h_meas.begin() + 3 * (size_t)k + 3);
+      }
   host_run_tasks(B.nj, [&](int i) {
     double* w = (double*)(h + B.S.s_work + (size_t)24 * nV * i);
     memcpy(w, g->h_poses.data(), (size_t)24 * nV);
@@ -874,13 +1061,15 @@ void cond_fill_stage(CondBatch& B) {
       thread_local std::vector<int32_t> queue;
       thread_local std::vector<double> cs;
       thread_local std::vector<uint8_t> seen;
-      initial_guess_own_edges(g, B.jobs[i].gauge, w, queue, cs, seen);
+      initial_guess_own_edges(g, B.jobs[i].gauge, w, queue, cs, seen, B.use_w ? B.wt.data() : nullptr);
     } else {
       std::vector<uint8_t> fx(nV, 0);
       fx[B.jobs[i].gauge] = 1;
-      initial_guess_host(nV, w, fx.data(), nA, g->ef.data(), g->et.data(), g->h_meas.data());
+      if (B.use_w) initial_guess_host(nV, w, fx.data(), (int)kept_ef.size(), kept_ef.data(), kept_et.data(), kept_meas.data());
+      else initial_guess_host(nV, w, fx.data(), nA, g->ef.data(), g->et.data(), g->h_meas.data());
     }
   });
+  if (B.use_w && nA > 0) memcpy(h + B.S.s_w, B.wt.data(), 8 * (size_t)nA);
   const double tm0 = wall_s();
   B.t_guess = tm0 - tg0;
   // the column masks: a vertex without an own edge is out of every job's system (the received edges are switched off);
@@ -940,6 +1129,7 @@ int cond_queue(CondBatch& B) {
   const double tp0 = wall_s();
   GnPassOpts pass;
   pass.write_l11c = true;
+  if (B.use_w) B.Ed.gnc_weight = (double*)(ds + S.s_w);          // (went up with the staging block above)
   gn_pass_on(ctx, DB, st, d_work0, B.Ed, pass);
   const double tp1 = wall_s();
   B.t_gn = tp1 - tp0;

@@ -1098,6 +1098,45 @@ int cgmr_graph_set_edge_robust(cgmr_graph* g, int first, int n, const uint8_t* k
 int cgmr_graph_set_received_robust(cgmr_graph* g, int kind, double delta);
 int cgmr_graph_edge_stats(const cgmr_graph* g, int cap, double* edge_chi2_out, double* weight_out);
 int cgmr_graph_set_condensed_robust(cgmr_graph* g, int on);
+/* Graduated non-convexity on the robot graph (same ABI version: found by symbol).  cgmr_graph_optimize_gnc is cgmr_gnc_optimize
+ * above -- the same contract, tests/ref_gnc.py -- on the system cgmr_graph_optimize would solve now: own edges, then the received
+ * ones (the order of cgmr_graph_debug_edges), Gauss-Newton inside, the received stars' gauge vertices as hubs of the ordering.
+ *   cgmr_graph_set_edge_gnc      barc_sq / known_inlier of own edges [first, first + n) by insertion index (host arrays).  A null
+ *                                pointer: the default for the range -- the chi2 0.99 quantile of dimension 3, or the call's
+ *                                default_barc_sq; free.  Edges never named, and edges added later, are default.  A value that is
+ *                                not finite and > 0, a range beyond the own edges: CGMR_E_INVALID.
+ *   cgmr_graph_set_received_gnc  one class for every received edge; barc_sq == 0: the default.
+ *   cgmr_graph_optimize_gnc      params nullable (the defaults); its per-edge pointers (barc_sq, known_inlier, weight_out,
+ *                                edge_chi2_out) must be null -- the graph holds those -- else CGMR_E_INVALID; also refused while an
+ *                                own edge or the received class carries a robust kernel other than CGMR_RK_NONE.  mu_out
+ *                                [max_outer], cost_out [max_outer + 1], partial_out [max_outer], outer_done: nullable.  Like
+ *                                cgmr_graph_optimize it brings the host copy of the estimates along in its final wait;
+ *                                cgmr_graph_edge_stats then returns r and w of every edge of this solve.  On a Cholesky code the
+ *                                poses are those of the last good update and the stored weights stay what they were.
+ *   cgmr_graph_gnc_weights       the stored weight of every own edge (returns their count; weight_out [cap]): 1 before any GNC
+ *                                solve and for edges added since the last one, else the last outer iteration's weights of the
+ *                                last cgmr_graph_optimize_gnc that returned CGMR_OK.  Received edges keep no weight between
+ *                                calls: their set is replaced every round.
+ *   cgmr_graph_keep_gnc_weights  on: cgmr_graph_optimize with Gauss-Newton scales every own edge's information by its stored
+ *                                weight (received edges: 1) -- a key-frame loop's solves between two GNC calls.  With Levenberg
+ *                                or dogleg selected, or a robust kernel set, that call returns CGMR_E_INVALID.  With every weight
+ *                                1 its result is the plain call's bit for bit.  Default off: nothing changes.
+ *   cgmr_graph_set_condensed_gnc on: every condensed graph the robot builds is that of its own-edge graph without the edges of
+ *                                stored weight w < drop_below or w == 0, the others' information scaled by w: the spanning-tree
+ *                                guess does not walk a removed edge (a vertex it no longer reaches keeps its estimate) and the
+ *                                pass gets exact zeros from it.  drop_below in [0, 1]; Geman-McClure never gives an exact zero, so
+ *                                drop_below is what removes its outliers.  A batch works from the weights as they are when it is
+ *                                queued (cgmr_graph_compute_condensed_async: a later cgmr_graph_optimize_gnc does not reach it).  A
+ *                                vertex left with no kept edge fails its pass with the Cholesky code, handled like any failed pass.
+ *                                Refused while cgmr_graph_set_condensed_robust is on, and that one while this is on.  Default off.
+ * A graph without a context takes the setters and answers cgmr_graph_optimize_gnc with CGMR_E_NO_DEVICE. */
+int cgmr_graph_set_edge_gnc(cgmr_graph* g, int first, int n, const double* barc_sq, const uint8_t* known_inlier);
+int cgmr_graph_set_received_gnc(cgmr_graph* g, double barc_sq, int known_inlier);
+int cgmr_graph_optimize_gnc(cgmr_graph* g, const cgmr_gnc_params* params, double* mu_out, double* cost_out, int32_t* partial_out,
+                            int32_t* outer_done);
+int cgmr_graph_gnc_weights(const cgmr_graph* g, int cap, double* weight_out);
+int cgmr_graph_keep_gnc_weights(cgmr_graph* g, int on);
+int cgmr_graph_set_condensed_gnc(cgmr_graph* g, int on, double drop_below);
 int cgmr_graph_lm_last(const cgmr_graph* g, int cap, double* lambda_out, int32_t* trials_out);
 /* estimates of vertices first .. first+n-1 in insertion order */
 int cgmr_graph_get_poses(cgmr_graph* g, int first, int n, double* poses_out);

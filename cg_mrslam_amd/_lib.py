@@ -49,6 +49,8 @@ _SYMBOLS = [
     "cgmr_gnc_params_default", "cgmr_gnc_optimize", "cgmr_gnc_optimize_dev", "cgmr_gnc_last_stats",
     "cgmr_graph_set_edge_gnc", "cgmr_graph_set_received_gnc", "cgmr_graph_optimize_gnc", "cgmr_graph_gnc_weights",
     "cgmr_graph_keep_gnc_weights", "cgmr_graph_set_condensed_gnc",
+    "cgmr_chordal_initialize", "cgmr_chordal_initialize_dev", "cgmr_chordal_initialize_typed",
+    "cgmr_chordal_initialize_typed_dev", "cgmr_initial_guess",
 ]
 
 JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)
@@ -202,6 +204,17 @@ def factor_types(vertex_kind, edge_kind, nV, nE):
         raise ValueError(f"edge kinds: {ek.shape[0]} given for {nE} edges")
     ft = FactorTypes(vk.ctypes.data if vk is not None and nV else None, ek.ctypes.data if ek is not None and nE else None)
     return ft, (vk, ek)
+
+
+def chordal_stages(stages) -> int:
+    """The ``stages`` argument of cgmr_chordal_initialize from 1 / 2 / 3 or "r" / "t" / "rt" (include/cgmr.h: CGMR_CHORDAL_*)."""
+    if isinstance(stages, str):
+        if not stages or set(stages) - set("rt"):
+            raise ValueError(f"chordal stages {stages!r}: some of 'r' (rotation) and 't' (translation)")
+        return (1 if "r" in stages else 0) | (2 if "t" in stages else 0)
+    if isinstance(stages, (bool, np.bool_)) or not isinstance(stages, (int, np.integer)) or not 1 <= int(stages) <= 3:
+        raise ValueError(f"chordal stages must be 1, 2 or 3, got {stages!r}")
+    return int(stages)
 
 
 # g2o's robust kernels by their C codes (include/cgmr.h: CGMR_RK_*)
@@ -487,6 +500,49 @@ class Context:
         out = np.zeros(2, dtype=np.int64)
         self._check(self.lib.cgmr_gnc_last_stats(self.h, _ptr(out)))
         return dict(host_waits=int(out[0]), inner_iterations=int(out[1]))
+
+    # ------------------------------------------------------------------ starting points
+    def _chordal(self, problem, stages, vertex_kind, edge_kind, raise_on_cholesky):
+        nV, p, (poses, fixed, nE, ef, et, meas, info), _keep = self._problem(*problem)
+        typed = vertex_kind is not None or edge_kind is not None
+        ft, _keep_ft = factor_types(vertex_kind, edge_kind, nV, nE.value) if typed else (None, None)
+        entry = "cgmr_chordal_initialize" + ("_typed" if typed else "") + ("_dev" if p is None else "")
+        chi2, counts = np.zeros(2), np.zeros(3, dtype=np.int32)
+        args = [self.h, C.c_int(nV), poses, fixed, nE, ef, et, meas, info, C.c_int(chordal_stages(stages)), _ptr(chi2), _ptr(counts)]
+        if typed:
+            args.append(C.byref(ft))
+        rc = getattr(self.lib, entry)(*args)
+        self._check(rc, allow_cholesky=not raise_on_cholesky)
+        out = dict(status=rc, chi2=chi2, counts=counts)
+        if p is not None:
+            out["poses"] = p
+        return out
+
+    def chordal_initialize(self, poses, fixed, ef, et, meas, info, stages=3, vertex_kind=None, edge_kind=None,
+                           raise_on_cholesky=True):
+        """Chordal initialisation (cgmr_chordal_initialize[_typed]): a starting point from two linear problems, whatever the
+        estimates passed in.  ``stages``: 1 / "r" the headings, 2 / "t" the positions with the headings held, 3 / "rt" both;
+        ``vertex_kind`` / ``edge_kind`` as the typed calls.  Host arrays in and out.  Returns a dict: status, poses, chi2 [2] (the
+        SE(2) chi2 at the start and at the result), counts [3] (vertices solved in the rotation stage, in the translation
+        stage, degenerate headings)."""
+        return self._chordal((poses, fixed, ef, et, meas, info), stages, vertex_kind, edge_kind, raise_on_cholesky)
+
+    def chordal_initialize_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, stages=3, vertex_kind=None,
+                               edge_kind=None, raise_on_cholesky=True):
+        """chordal_initialize on device pointers for poses / meas / info: the same dict without the poses."""
+        return self._chordal(((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), stages, vertex_kind, edge_kind,
+                             raise_on_cholesky)
+
+    def initial_guess(self, poses, fixed, ef, et, meas):
+        """g2o's spanning-tree guess (cgmr_initial_guess): breadth-first from the fixed vertices over the edges.  Host arrays
+        in, the new poses out; a vertex that is not reached keeps its estimate.  No device work."""
+        p = np.ascontiguousarray(poses, dtype=np.float64).copy()
+        fx, f, t = (np.ascontiguousarray(a, dtype=d) for a, d in ((fixed, np.uint8), (ef, np.int32), (et, np.int32)))
+        m = np.ascontiguousarray(meas, dtype=np.float64)
+        rc = self.lib.cgmr_initial_guess(C.c_int(p.shape[0]), _ptr(p), _ptr(fx), C.c_int(len(f)), _ptr(f), _ptr(t), _ptr(m))
+        if rc != 0:
+            raise CgmrError(rc, "cgmr_initial_guess: a null or negative argument, or an edge index out of range")
+        return p
 
     def dl_last_stats(self):
         """The last dl_optimize* call: dict(host_waits, trials, factorisations)."""

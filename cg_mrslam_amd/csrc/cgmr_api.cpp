@@ -4,6 +4,7 @@
 #include "dl_device.h"
 #include "gnc_device.h"
 #include "gn_host.h"
+#include "init_device.h"
 #include "lm_device.h"
 #include "tr_device.h"
 
@@ -586,7 +587,8 @@ void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, con
   // (the forward solve L y = b rides through k_front_factor as an extra row of every front)
   if (D.bwd_chain_level < D.nlevels) T.run(6, 1, [&] { launch_bwd_chain(st, D); });
   for (int l = D.bwd_chain_level - 1; l >= 0; l--) T.run(6, 1, [&] { launch_bwd_level(st, D, l); });
-  if (o.update_poses) T.run(7, 1, [&] { launch_update(st, D, d_poses); });
+  if (o.update_poses)
+    T.run(7, 1, [&] { if (Ed.chordal_stage == kChordalRotation) launch_apply_rotation(st, D, d_poses); else launch_update(st, D, d_poses); });
 }
 
 int LevelwiseScope::arm(hipStream_t st, int it0) {
@@ -726,6 +728,102 @@ int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
     return set_err(ctx, CGMR_E_CHOLESKY_BASE - (status - 1),
                    "Cholesky failed (non-positive pivot) in GN iteration %d; poses left at the last good update",
                    status - 1);
+  return CGMR_OK;
+}
+
+// Chordal initialisation (include/cgmr.h: cgmr_chordal_initialize; init_kernels.hip): one structure, then one pass per
+// requested stage -- the stage's mask, gn_pass with the stage in GnEdges -- between two chi-only passes of the ordinary
+// linearisation, and one wait.  in_rot / in_tr [nV]: the vertices some term of the stage touches; the others are left out of it
+// through its mask like the fixed ones.  The chi2 slots: pass p's own cost in slot p (k_assemble, from status[1]), the SE(2)
+// chi2 at the start and at the result in slots 4 and 5.  A non-positive pivot in pass p: status[0] = p + 1, that pass and the
+// later ones change nothing (k_apply_rotation and k_update_poses skip), the call returns GN's code for iteration p.
+int chordal_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
+                const GnEdges& Ed, int stages, const uint8_t* in_rot, const uint8_t* in_tr, double* chi2_out, int32_t* counts_out) {
+  constexpr int kSlotStart = 4, kSlotEnd = 5, kSlots = 6;
+  GnCall call(ctx, nV, d_poses);
+  int rc = prepare_structure(ctx, nV, nE, ef, et, kSlots);
+  if (rc) return rc;
+  call.t1 = wall_s();
+  const Symbolic& S = ctx->sym;
+  GnDevice& D = ctx->gn;
+  hipStream_t st = ctx->stream;
+  int seq[2], npass = 0;
+  if (stages & kChordalRotation) seq[npass++] = kChordalRotation;
+  if (stages & kChordalTranslation) seq[npass++] = kChordalTranslation;
+  // the passes' column masks, side by side in pinned memory: they stay as they are until the call's last wait
+  rc = pinned_mask_reserve(ctx, (size_t)2 * S.nf + 1);
+  if (rc) return rc;
+  int solved[2] = {0, 0};
+  for (int p = 0; p < npass; p++) {
+    const uint8_t* in = seq[p] == kChordalRotation ? in_rot : in_tr;
+    ctx->vmask.assign(S.nV, 0);
+    for (int v = 0; v < S.nV; v++) ctx->vmask[v] = (fixed[v] || !in[v]) ? 1 : 0;
+    char* pm = ctx->pinned_mask + (size_t)p * S.nf;
+    for (int c = 0; c < S.nf; c++) {
+      pm[c] = (char)ctx->vmask[S.perm[c]];
+      solved[p] += pm[c] ? 0 : 1;
+    }
+  }
+  HIP_TRY(ctx, hipMemsetAsync(D.status, 0, 16, st));
+  call.t2 = wall_s();
+  bool queue_failed = false;
+  // the passes p0 .. npass - 1, then the chi-only pass at the estimate they leave
+  auto queue_from = [&](int p0) {
+    GnPassOpts o;
+    for (int p = p0; p < npass; p++) {
+      if (S.nf > 0 && hipMemcpyAsync(D.cmask, ctx->pinned_mask + (size_t)p * S.nf, (size_t)S.nf, hipMemcpyHostToDevice, st) != hipSuccess) queue_failed = true;
+      GnEdges Es = Ed;
+      Es.chordal_stage = seq[p];
+      o.chi_slot = p;
+      gn_pass(ctx, d_poses, Es, o);
+    }
+    o.chi_only = true;
+    o.chi_slot = kSlotEnd;
+    gn_pass(ctx, d_poses, Ed, o);
+  };
+  rc = call.begin();
+  if (rc) return rc;
+  {
+    GnPassOpts o;
+    o.chi_only = true;
+    o.chi_slot = kSlotStart;
+    gn_pass(ctx, d_poses, Ed, o);
+  }
+  queue_from(0);
+  HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
+  double chi[kSlots] = {0, 0, 0, 0, 0, 0};
+  int status4[4] = {0, 0, 0, 0};
+  const std::initializer_list<GnCall::Readback> results = {{chi, D.chi2, sizeof chi}, {status4, D.status, sizeof status4}};
+  rc = call.wait(results);
+  if (rc) return rc;
+  int degenerate_kept = 0;
+  if (status4[2] != 0 && status4[0] > 0) {
+    // A bounded wait of the chained backward solve ran out in pass status[0] - 1: that pass and the later ones were not applied
+    // and are repeated level-wise (gn_run).  The fresh status words drop the count of an earlier rotation pass: kept here.
+    const int p0 = std::min(status4[0] - 1, npass - 1);
+    if (p0 > 0) degenerate_kept = status4[kChordalDegenerateWord];
+    LevelwiseScope levelwise(ctx, D);
+    rc = levelwise.arm(st, p0);
+    if (rc) return rc;
+    queue_from(p0);
+    rc = call.wait(results);
+    if (rc) return rc;
+    if (status4[2] != 0) return set_err(ctx, CGMR_E_TIMEOUT, "backward solve: a bounded device-side wait ran out twice");
+  }
+  if (queue_failed) return set_err(ctx, CGMR_E_HIP, "cgmr_chordal_initialize: a stage's mask could not be queued");
+  const int status = status4[0];
+  call.finish();
+  if (chi2_out) { chi2_out[0] = chi[kSlotStart]; chi2_out[1] = chi[kSlotEnd]; }
+  if (counts_out) {
+    counts_out[0] = counts_out[1] = 0;
+    for (int p = 0; p < npass; p++)
+      if (status == 0 || p < status - 1) counts_out[seq[p] == kChordalRotation ? 0 : 1] = solved[p];
+    counts_out[2] = status4[kChordalDegenerateWord] + degenerate_kept;
+  }
+  if (status != 0)
+    return set_err(ctx, CGMR_E_CHOLESKY_BASE - (status - 1),
+                   "Cholesky failed (non-positive pivot) in the %s stage of the chordal initialisation; poses left as they were before it",
+                   seq[std::min(status - 1, npass - 1)] == kChordalRotation ? "rotation" : "translation");
   return CGMR_OK;
 }
 
@@ -1898,6 +1996,43 @@ static int gnc_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t
   return rc;
 }
 
+// cgmr_chordal_initialize*: the arguments checked, then which vertices each stage's terms touch -- a term whose information
+// entries for the stage are all zero touches nothing -- from the host's copy of the information (a _dev call reads it back once)
+static int chordal_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                        const int32_t* to_idx, const double* meas, const double* info, const cgmr_factor_types* ft, int stages,
+                        double* chi2_out, int32_t* counts_out, bool dev) {
+  const char* who = ft ? (dev ? "cgmr_chordal_initialize_typed_dev" : "cgmr_chordal_initialize_typed")
+                       : (dev ? "cgmr_chordal_initialize_dev" : "cgmr_chordal_initialize");
+  int rc = optimize_args_check(ctx, who, nV, poses, fixed, nE, from_idx, to_idx, meas, info, 0);
+  if (rc) return rc;
+  if (stages < 1 || stages > 3) return set_err(ctx, CGMR_E_INVALID, "%s: stages must be 1 (rotation), 2 (translation) or 3 (both)", who);
+  TypedHost typed;
+  rc = typed_check(ctx, who, ft, nV, nE, from_idx, to_idx, typed);
+  if (rc) return rc;
+  for (int k = 0; k < nE; k++)
+    if (from_idx[k] < 0 || from_idx[k] >= nV || to_idx[k] < 0 || to_idx[k] >= nV)
+      return set_err(ctx, CGMR_E_INVALID, "%s: edge %d has a vertex index out of range", who, k);
+  std::vector<double> hinfo;
+  const double* hi = info;
+  if (dev && nE > 0) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hinfo.resize(6 * (size_t)nE);
+    HIP_TRY(ctx, hipMemcpyAsync(hinfo.data(), info, 48 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    hi = hinfo.data();
+  }
+  std::vector<uint8_t> in_rot((size_t)nV, 0), in_tr((size_t)nV, 0);
+  for (int k = 0; k < nE; k++) {
+    const int kind = typed.any ? typed.ek[k] : 0;
+    const double* u = hi + 6 * (size_t)k;
+    if ((kind == 0 || kind == 3) && u[5] != 0.0) in_rot[from_idx[k]] = in_rot[to_idx[k]] = 1;
+    if (kind != 2 && (u[0] != 0.0 || u[1] != 0.0 || u[3] != 0.0)) in_tr[from_idx[k]] = in_tr[to_idx[k]] = 1;
+  }
+  return optimize_staged(ctx, who, dev, true, nV, poses, nE, meas, info, nullptr, &typed, [&](double* d_poses, const GnEdges& Ed) {
+    return chordal_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, stages, in_rot.data(), in_tr.data(), chi2_out, counts_out);
+  });
+}
+
 }  // namespace cgmr
 
 using namespace cgmr;
@@ -2126,6 +2261,39 @@ int cgmr_gnc_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t*
                           int32_t* outer_done) {
   return gnc_optimize_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, types, params, mu_out, cost_out,
                            partial_out, outer_done, true);
+}
+
+int cgmr_chordal_initialize(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                            const int32_t* to_idx, const double* meas, const double* info, int stages, double* chi2_out,
+                            int32_t* counts_out) {
+  return chordal_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, nullptr, stages, chi2_out, counts_out, false);
+}
+
+int cgmr_chordal_initialize_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                                const int32_t* to_idx, const double* d_meas, const double* d_info, int stages, double* chi2_out,
+                                int32_t* counts_out) {
+  return chordal_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, nullptr, stages, chi2_out, counts_out, true);
+}
+
+int cgmr_chordal_initialize_typed(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                                  const int32_t* to_idx, const double* meas, const double* info, int stages, double* chi2_out,
+                                  int32_t* counts_out, const cgmr_factor_types* types) {
+  return chordal_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, types, stages, chi2_out, counts_out, false);
+}
+
+int cgmr_chordal_initialize_typed_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
+                                      const int32_t* from_idx, const int32_t* to_idx, const double* d_meas, const double* d_info,
+                                      int stages, double* chi2_out, int32_t* counts_out, const cgmr_factor_types* types) {
+  return chordal_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, types, stages, chi2_out, counts_out, true);
+}
+
+int cgmr_initial_guess(int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx, const int32_t* to_idx,
+                       const double* meas) {
+  if (nV < 0 || nE < 0 || (nV > 0 && (!poses || !fixed)) || (nE > 0 && (!from_idx || !to_idx || !meas))) return CGMR_E_INVALID;
+  for (int k = 0; k < nE; k++)
+    if (from_idx[k] < 0 || from_idx[k] >= nV || to_idx[k] < 0 || to_idx[k] >= nV) return CGMR_E_INVALID;
+  initial_guess_host(nV, poses, fixed, nE, from_idx, to_idx, meas);
+  return CGMR_OK;
 }
 
 int cgmr_gnc_last_stats(const cgmr_ctx* ctx, int64_t out[2]) {

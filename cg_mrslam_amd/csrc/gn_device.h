@@ -89,6 +89,10 @@ struct GnEdges {
   const uint8_t* gnc_known = nullptr;
   const GncState* gnc_state = nullptr;
   double* gnc_r = nullptr;
+  // chordal initialisation (include/cgmr.h: cgmr_chordal_initialize; init_kernels.hip): 0 the Gauss-Newton linearisation, else
+  // the linear stage whose records the pass solves -- init_device.h: kChordalRotation / kChordalTranslation.  One job, never
+  // with `robust` or `gnc`; a rotation pass ends with k_apply_rotation in the place of k_update_poses.
+  int chordal_stage = 0;
 };
 // gn_structure.hip: the assembly lists (asm_ptr: nf + nb + 1, asm_src: one entry per (edge, key)) from the permutation, the
 // edge list and the off-diagonal blocks (offbase: nf + 1 column starts into off_row); work space: ekey nE, cnt nf + nb + 3,

@@ -96,6 +96,10 @@ struct LevelwiseScope {
 };
 int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
            const GnEdges& Ed, int iters, double* chi2_out, const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0);
+// Chordal initialisation on the same structure preparation and factorisation (include/cgmr.h: cgmr_chordal_initialize): one pass
+// per stage of `stages`; in_rot / in_tr [nV] host: the vertices some term of the stage touches; chi2_out [2], counts_out [3] nullable
+int chordal_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
+                const GnEdges& Ed, int stages, const uint8_t* in_rot, const uint8_t* in_tr, double* chi2_out, int32_t* counts_out);
 // Levenberg-Marquardt on the same structure preparation and factorisation (g2o's OptimizationAlgorithmLevenberg): outputs
 // chi2_out [iters + 1], lambda_out / trials_out [iters] (all nullable), *iters_done; never a Cholesky status
 int lm_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,

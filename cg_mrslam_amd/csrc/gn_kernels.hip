@@ -26,6 +26,7 @@
 #include "gn_symbolic.h"
 #include "gn_device.h"
 #include "gnc_device.h"
+#include "init_device.h"
 #include "panel_cholesky.h"
 
 namespace cgmr {
@@ -1674,6 +1675,7 @@ __global__ __launch_bounds__(256) void k_update_poses(int nV, const int32_t* __r
 
 void launch_linearize(hipStream_t st, const GnDevice& D, const double* poses, const GnEdges& Ed, int chi_only) {
   if (D.nE == 0) return;
+  if (Ed.chordal_stage) { launch_linearize_chordal(st, D, poses, Ed); return; }   // (init_kernels.hip; never chi-only)
   gn_init_kernels();
   const dim3 grid((D.nE + 255) / 256, 1, D.njobs);
   const size_t lds = chi_only ? 0 : 256 * 33 * sizeof(double);

@@ -298,6 +298,7 @@ class GraphSLAM:
         self.last_weights = None
         self.last_mu = None
         self._gnc_rejected = None
+        self.last_init_counts = None
 
     def optimize(self, nrunnings: int) -> None:
         """``nrunnings`` iterations on the level-0 edges; estimates updated in place.  Returns nothing and never raises on
@@ -354,6 +355,30 @@ class GraphSLAM:
         g.poses[:] = poses
         self.last_chi2 = chi2
         self.last_status = rc
+
+    # ---------------------------------------------------------------- starting points
+    def initializeChordal(self, stages="rt") -> None:     # noqa: N802
+        """A starting point by chordal relaxation (Context.chordal_initialize) on the level-0 edges, whatever the estimates
+        are: ``stages`` "r" the headings, "t" the positions with the headings held, "rt" both.  A typed graph goes through its
+        kinds; robust kernels play no part (the method is not robust to wrong closures).  Estimates updated in place.  Leaves
+        ``last_chi2`` (the SE(2) chi2 at the start and at the result), ``last_status`` and ``last_init_counts`` (vertices solved
+        in the rotation stage, in the translation stage, degenerate headings); never raises on a Cholesky failure."""
+        g = self.graph
+        ef, et, meas, info = g.level0()
+        ty = self._typed_level0()
+        kw = {} if ty is None else dict(vertex_kind=ty[0], edge_kind=ty[1])
+        out = self.ctx.chordal_initialize(g.poses, g.fixed, ef, et, meas, info, stages, raise_on_cholesky=False, **kw)
+        g.poses[:] = out["poses"]
+        self.last_chi2, self.last_status, self.last_init_counts = out["chi2"], out["status"], out["counts"]
+
+    def computeInitialGuess(self) -> None:     # noqa: N802
+        """g2o's spanning-tree guess (Context.initial_guess) over the level-0 edges of a pose graph, from the fixed vertices;
+        estimates updated in place."""
+        g = self.graph
+        if g.typed:
+            raise ValueError("computeInitialGuess: pose graphs only (a landmark observation is no SE(2) transform)")
+        ef, et, meas, _ = g.level0()
+        g.poses[:] = self.ctx.initial_guess(g.poses, g.fixed, ef, et, meas)
 
     # ---------------------------------------------------------------- graduated non-convexity
     def optimizeGNC(self, max_outer: int = 100, loss: str = "tls", barc_sq=None, known_inliers=None, **params) -> None:     # noqa: N802

@@ -368,6 +368,58 @@ int cgmr_gnc_optimize_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint
                           int32_t* partial_out, int32_t* outer_done);
 /* The last cgmr_gnc_optimize* call on this context: out[0] = host waits for the device, out[1] = inner iterations run. */
 int cgmr_gnc_last_stats(const cgmr_ctx* ctx, int64_t out[2]);
+/* Chordal initialisation (same ABI version: callers find the entry points by their symbols): a starting point from two linear
+ * least-squares problems, as GTSAM's InitializePose and LAGO do [recalled: from memory, not read from either source; the
+ * contract is tests/ref_chordal.py].  Linear problems have no basin of attraction: the result does not depend on the estimates
+ * passed in, up to rounding.  All information is read from the edge's own 3x3 Omega; the cross terms between translation and
+ * heading are ignored by design.
+ *   stages bit 0, the rotation stage: unknown r_i = (c_i, s_i) per free pose, omega = Omega(2,2) --
+ *     CGMR_EDGE_SE2 (i, j)   omega || r_j - R(z_theta) r_i ||^2
+ *     CGMR_EDGE_PRIOR_SE2    omega || r_i - (cos z_theta, sin z_theta) ||^2
+ *     every other kind       nothing
+ *   A fixed pose is the constant (cos theta, sin theta).  Then theta_i = atan2(s_i, c_i); c_i^2 + s_i^2 = 1 is not imposed.  A
+ *   solved (c_i, s_i) of length exactly zero, or not finite, leaves the pose its heading and counts as degenerate.
+ *   stages bit 1, the translation stage: unknown t_i per free pose and l per free point, the headings held at their current
+ *   values (the rotation stage's when both bits are set), weight Omega[0:2, 0:2] --
+ *     CGMR_EDGE_SE2          e = R(z_theta)^T (R_i^T (t_j - t_i) - z_t)
+ *     CGMR_EDGE_SE2_XY       e = R_i^T (l - t_i) - z
+ *     CGMR_EDGE_PRIOR_SE2    e = R(z_theta)^T (t_i - z_t)
+ *     CGMR_EDGE_PRIOR_SE2_XY e = t_i - z
+ *     CGMR_EDGE_BEARING_SE2_XY  nothing
+ * A vertex that no term of a stage touches -- a point in the rotation stage, a point seen by bearings only, a vertex all of
+ * whose information entries for the stage are zero, an isolated vertex -- is left out of that stage and keeps its estimate.
+ *   stages       1, 2 or 3; anything else is CGMR_E_INVALID
+ *   chi2_out     [2], nullable: the SE(2) chi2 (cgmr_gn_optimize's, cgmr_gn_optimize_typed's) at the estimates passed in and at the result
+ *   counts_out   [3], nullable: vertices solved in the rotation stage, in the translation stage, degenerate headings
+ * A stage without a gauge -- no fixed pose and no prior reaches some connected component -- is singular: the call returns
+ * CGMR_E_CHOLESKY_BASE - p, p the stage's place among the requested ones (0 or 1), and the estimates are those from before
+ * that stage; its count and the later stage's are 0.  Chordal relaxation is not robust to wrong loop closures: it is no start
+ * for cgmr_gnc_optimize on a graph with outliers.  One host wait; the _dev variants read d_info_upper back once before it (which
+ * terms are all zero is decided on the host) and are otherwise bit-identical to the host variants.  CGMR_E_TIMEOUT as
+ * cgmr_gn_optimize.  Not offered for the robot graph, condensed graphs or batches. */
+#define CGMR_CHORDAL_ROTATION 1
+#define CGMR_CHORDAL_TRANSLATION 2
+int cgmr_chordal_initialize(cgmr_ctx* ctx, int nV, double* poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                            const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int stages,
+                            double* chi2_out, int32_t* counts_out);
+int cgmr_chordal_initialize_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8_t* fixed, int nE,
+                                const int32_t* from_idx, const int32_t* to_idx, const double* d_meas_xyt,
+                                const double* d_info_upper, int stages, double* chi2_out, int32_t* counts_out);
+/* types nullable (or all zero): the plain call */
+int cgmr_chordal_initialize_typed(cgmr_ctx* ctx, int nV, double* poses_xyt, const uint8_t* fixed, int nE,
+                                  const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt,
+                                  const double* info_upper, int stages, double* chi2_out, int32_t* counts_out,
+                                  const cgmr_factor_types* types);
+int cgmr_chordal_initialize_typed_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8_t* fixed, int nE,
+                                      const int32_t* from_idx, const int32_t* to_idx, const double* d_meas_xyt,
+                                      const double* d_info_upper, int stages, double* chi2_out, int32_t* counts_out,
+                                      const cgmr_factor_types* types);
+/* g2o's SparseOptimizer::computeInitialGuess with unit edge cost [g2o-recalled]: breadth-first from the fixed vertices that
+ * have an edge, over the edges in their order, x_to = x_from * z or x_from = x_to * z^-1; a vertex it does not reach keeps its
+ * estimate.  Host arrays in and out (poses_xyt in place), no device work, no context.  CGMR_E_INVALID: a null or negative
+ * argument, an edge index out of range. */
+int cgmr_initial_guess(int nV, double* poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx, const int32_t* to_idx,
+                       const double* meas_xyt);
 int cgmr_marginals_typed(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
                          const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt, const double* info_upper,
                          int nK, const int32_t* query_idx, double* cov_out, const cgmr_factor_types* types,

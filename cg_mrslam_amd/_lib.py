@@ -51,6 +51,8 @@ _SYMBOLS = [
     "cgmr_graph_keep_gnc_weights", "cgmr_graph_set_condensed_gnc",
     "cgmr_chordal_initialize", "cgmr_chordal_initialize_dev", "cgmr_chordal_initialize_typed",
     "cgmr_chordal_initialize_typed_dev", "cgmr_initial_guess",
+    "cgmr_gn_optimize_mixture", "cgmr_gn_optimize_mixture_dev", "cgmr_lm_optimize_mixture", "cgmr_lm_optimize_mixture_dev",
+    "cgmr_dl_optimize_mixture", "cgmr_dl_optimize_mixture_dev", "cgmr_mixture_select",
 ]
 
 JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)
@@ -187,6 +189,33 @@ class Robust(C.Structure):
 class FactorTypes(C.Structure):
     """cgmr_factor_types (include/cgmr.h): the vertex and edge kinds of one typed call."""
     _fields_ = [("vertex_kind", C.c_void_p), ("edge_kind", C.c_void_p)]
+
+
+class Mixture(C.Structure):
+    """cgmr_mixture (include/cgmr.h): the components of the edges of one mixture call."""
+    _fields_ = [("comp_ptr", C.c_void_p), ("comp_meas", C.c_void_p), ("comp_info", C.c_void_p), ("comp_weight", C.c_void_p),
+                ("selected_out", C.c_void_p)]
+
+
+def mixture_arrays(mixture, nE):
+    """(Mixture or None, selected int32 [nE], the arrays it points into) from ``mixture`` = (comp_ptr [nE + 1], comp_meas [nC, 3],
+    comp_info [nC, 6], comp_weight [nC]) or None.  Shapes are checked here; the values by the library."""
+    sel = np.zeros(nE, dtype=np.int32)
+    if mixture is None:
+        return None, sel, None
+    cp, cm, ci, cw = mixture
+    cp = np.ascontiguousarray(cp, dtype=np.int32).reshape(-1)
+    if cp.shape != (nE + 1,):
+        raise ValueError(f"mixture: comp_ptr has {cp.shape[0]} entries for {nE} edges (nE + 1 expected)")
+    nC = max(int(cp.max()), 0) if cp.size else 0
+    cm = np.ascontiguousarray(cm, dtype=np.float64).reshape(-1, 3)
+    ci = np.ascontiguousarray(ci, dtype=np.float64).reshape(-1, 6)
+    cw = np.ascontiguousarray(cw, dtype=np.float64).reshape(-1)
+    if cm.shape[0] < nC or ci.shape[0] < nC or cw.shape[0] < nC:
+        raise ValueError(f"mixture: comp_ptr names {nC} components, comp_meas / comp_info / comp_weight hold "
+                         f"{cm.shape[0]} / {ci.shape[0]} / {cw.shape[0]}")
+    keep = (cp, cm, ci, cw, sel)
+    return Mixture(*(a.ctypes.data if a.size else None for a in keep)), sel, keep
 
 
 # include/cgmr.h: CGMR_VERTEX_* / CGMR_EDGE_*
@@ -598,6 +627,65 @@ class Context:
         """dl_optimize_typed on device pointers: (status, chi2, deltas, trials, steps, iters_done)."""
         return self._typed("cgmr_dl_optimize_typed_dev", ((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), iters,
                            vertex_kind, edge_kind, kind, delta, dl_params(**params), 2, allow_fail=not raise_on_fail)
+
+    # ------------------------------------------------------------------ max-mixture edges
+    # include/cgmr.h: cgmr_mixture.  ``mixture`` = (comp_ptr [nE + 1], comp_meas [nC, 3], comp_info [nC, 6], comp_weight [nC]), host
+    # arrays in the _dev variants too, None = the typed / plain call; ``meas`` / ``info`` hold every edge's first component.
+    # ``vertex_kind`` / ``edge_kind`` as the typed calls.  Each returns what its typed call does with ``selected`` int32 [nE]
+    # appended: every edge's selected component at the returned poses.
+    def _mixture(self, entry, problem, iters, mixture, vertex_kind, edge_kind, prm=None, n_int=None, allow_fail=False):
+        nE = len(problem[2])
+        nV = problem[0][1] if isinstance(problem[0], tuple) else len(problem[0])
+        ft, _keep_ft = factor_types(vertex_kind, edge_kind, nV, nE)
+        mix, sel, _keep = mixture_arrays(mixture, nE)
+        out = self._optimize(entry, problem, iters, prm, n_int, rk=mix, allow_fail=allow_fail, ft=ft)
+        return out + (sel,)
+
+    def gn_optimize_mixture(self, poses, fixed, ef, et, meas, info, iters, mixture=None, vertex_kind=None, edge_kind=None,
+                            raise_on_cholesky=True):
+        """Gauss-Newton on max-mixture edges: (status, poses, chi2[iters+1], selected)."""
+        return self._mixture("cgmr_gn_optimize_mixture", (poses, fixed, ef, et, meas, info), iters, mixture, vertex_kind, edge_kind,
+                             allow_fail=not raise_on_cholesky)
+
+    def gn_optimize_mixture_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters, mixture=None, vertex_kind=None,
+                                edge_kind=None, raise_on_cholesky=True):
+        """gn_optimize_mixture on device pointers (the mixture stays host arrays): (status, chi2[iters+1], selected)."""
+        return self._mixture("cgmr_gn_optimize_mixture_dev", ((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), iters,
+                             mixture, vertex_kind, edge_kind, allow_fail=not raise_on_cholesky)
+
+    def lm_optimize_mixture(self, poses, fixed, ef, et, meas, info, iters, mixture=None, vertex_kind=None, edge_kind=None, **params):
+        """Levenberg-Marquardt on max-mixture edges: (status, poses, chi2, lambdas, trials, iters_done, selected)."""
+        return self._mixture("cgmr_lm_optimize_mixture", (poses, fixed, ef, et, meas, info), iters, mixture, vertex_kind, edge_kind,
+                             lm_params(**params), 1)
+
+    def lm_optimize_mixture_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters, mixture=None, vertex_kind=None,
+                                edge_kind=None, **params):
+        """lm_optimize_mixture on device pointers: (status, chi2, lambdas, trials, iters_done, selected)."""
+        return self._mixture("cgmr_lm_optimize_mixture_dev", ((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), iters,
+                             mixture, vertex_kind, edge_kind, lm_params(**params), 1)
+
+    def dl_optimize_mixture(self, poses, fixed, ef, et, meas, info, iters, mixture=None, vertex_kind=None, edge_kind=None,
+                            raise_on_fail=True, **params):
+        """Dogleg on max-mixture edges: (status, poses, chi2, deltas, trials, steps, iters_done, selected)."""
+        return self._mixture("cgmr_dl_optimize_mixture", (poses, fixed, ef, et, meas, info), iters, mixture, vertex_kind, edge_kind,
+                             dl_params(**params), 2, allow_fail=not raise_on_fail)
+
+    def dl_optimize_mixture_dev(self, d_poses_ptr, nV, fixed, ef, et, d_meas_ptr, d_info_ptr, iters, mixture=None, vertex_kind=None,
+                                edge_kind=None, raise_on_fail=True, **params):
+        """dl_optimize_mixture on device pointers: (status, chi2, deltas, trials, steps, iters_done, selected)."""
+        return self._mixture("cgmr_dl_optimize_mixture_dev", ((d_poses_ptr, nV), fixed, ef, et, d_meas_ptr, d_info_ptr), iters,
+                             mixture, vertex_kind, edge_kind, dl_params(**params), 2, allow_fail=not raise_on_fail)
+
+    def mixture_select(self, poses, fixed, ef, et, meas, info, mixture=None, vertex_kind=None, edge_kind=None):
+        """The mixture cost and the selection at ``poses`` (cgmr_mixture_select, one chi-only pass): (chi2, selected)."""
+        nV, p, (pp, fx, nE, f, t, m, i), _keep = self._problem(poses, fixed, ef, et, meas, info)
+        ft, _keep_ft = factor_types(vertex_kind, edge_kind, nV, nE.value)
+        mix, sel, _keep_mix = mixture_arrays(mixture, nE.value)
+        chi = np.zeros(1)
+        rc = self.lib.cgmr_mixture_select(self.h, C.c_int(nV), pp, fx, nE, f, t, m, i, C.byref(ft),
+                                          C.byref(mix) if mix is not None else C.c_void_p(0), _ptr(chi))
+        self._check(rc)
+        return float(chi[0]), sel
 
     def marginals_typed(self, poses, fixed, ef, et, meas, info, query, vertex_kind=None, edge_kind=None, kind=None, delta=1.0):
         """marginals on the typed H: cov [nK, 3, 3] (a point's third row and column are zero); (cov, e2, weights) with ``kind``."""

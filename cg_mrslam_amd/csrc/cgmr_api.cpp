@@ -665,6 +665,7 @@ int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
   // (robust statistics: written by the final chi-only pass, at the estimate the call returns)
   GnEdges Ei = Ed;
   Ei.rk_stats = nullptr;
+  Ei.mix_sel = nullptr;                 // (a mixture's selection: written by the same pass)
   // iterations it0 .. iters - 1, then the chi-only pass at the estimate they leave
   auto queue_from = [&](int it0) {
     GnPassOpts o;
@@ -680,7 +681,7 @@ int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
   static const bool trace_launches = getenv("CGMR_TRACE_LAUNCHES") != nullptr;
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
-  if (graph_mode && !ctx->profiling && !trace_launches && iters >= 2 && st != nullptr && D.nf > 0) {
+  if (graph_mode && !ctx->profiling && !trace_launches && iters >= 2 && st != nullptr && D.nf > 0 && !Ed.mix) {
     gn_init_kernels();
     HIP_TRY(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     gn_pass(ctx, d_poses, Ei, GnPassOpts());
@@ -874,6 +875,7 @@ static int tr_run(cgmr_ctx* ctx, P& pol, int nV, double* d_poses, const uint8_t*
     LevelwiseScope levelwise(ctx, D);
     GnEdges Ei = Ed;                                         // (robust statistics: one chi-only pass on the final poses below)
     Ei.rk_stats = nullptr;
+    Ei.mix_sel = nullptr;                                    // (a mixture's selection: the same pass)
     for (;;) {
       pol.queue_round(ctx, D, st, nV, d_poses, Ei, hs, iters);
       HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
@@ -894,7 +896,7 @@ static int tr_run(cgmr_ctx* ctx, P& pol, int nV, double* d_poses, const uint8_t*
       }
       if (hs.done) break;
     }
-    if (Ed.rk_stats) launch_linearize(st, D, d_poses, Ed, 1);   // (read back by the caller, behind the stream)
+    if (Ed.rk_stats || Ed.mix_sel) launch_linearize(st, D, d_poses, Ed, 1);   // (read back by the caller, behind the stream)
   }
   call.finish();
   return pol.finish(ctx, hs, h.data(), std::min(hs.iter, iters), iters, waits);
@@ -1726,6 +1728,87 @@ int joint_driver(cgmr_ctx* ctx, const char* who, int mode, int nV, const double*
   return rc;
 }
 
+// The mixture of a mixture entry point (include/cgmr.h: cgmr_mixture), checked on the host before the device is touched.  `any`:
+// some edge has more than one component (none: the call is the typed / plain one on meas / info, bit for bit).  off: per
+// component c = max_j a_j - a, a = 2 ln w + ln det Omega over the factor's own dimension, in double on the host; 0 on an edge
+// of one component, whose weight and Omega are not looked at.
+struct MixHost {
+  bool any = false;
+  const cgmr_mixture* mix = nullptr;
+  size_t nC = 0;
+  std::vector<double> off;
+};
+static int mix_check(cgmr_ctx* ctx, const char* who, const cgmr_mixture* mix, int nE, const TypedHost& typed, MixHost& M) {
+  if (!mix || !mix->comp_ptr) return 0;
+  const int32_t* cp = mix->comp_ptr;
+  if (cp[0] != 0) return set_err(ctx, CGMR_E_INVALID, "%s: comp_ptr[0] must be 0 (edge 0)", who);
+  for (int k = 0; k < nE; k++) {
+    if (cp[k + 1] <= cp[k])
+      return set_err(ctx, CGMR_E_INVALID, "%s: edge %d has no component (comp_ptr must increase from 0)", who, k);
+    if (cp[k + 1] - cp[k] > 1) M.any = true;
+  }
+  if (!M.any) return 0;
+  if (!mix->comp_meas || !mix->comp_info || !mix->comp_weight)
+    return set_err(ctx, CGMR_E_INVALID, "%s: a mixture needs comp_meas, comp_info and comp_weight", who);
+  M.mix = mix;
+  M.nC = (size_t)cp[nE];
+  M.off.assign(M.nC, 0.0);
+  for (int k = 0; k < nE; k++) {
+    const int p0 = cp[k], p1 = cp[k + 1];
+    if (p1 - p0 < 2) continue;
+    const int kind = typed.any ? typed.ek[k] : 0;
+    double amax = 0;
+    for (int p = p0; p < p1; p++) {
+      const double w = mix->comp_weight[p];
+      const double* u = mix->comp_info + 6 * (size_t)p;
+      const double det = kind == 2 ? u[0]
+                         : (kind == 1 || kind == 4)
+                             ? u[0] * u[3] - u[1] * u[1]
+                             : u[0] * (u[3] * u[5] - u[4] * u[4]) - u[1] * (u[1] * u[5] - u[4] * u[2]) + u[2] * (u[1] * u[4] - u[3] * u[2]);
+      if (!(std::isfinite(w) && w > 0))
+        return set_err(ctx, CGMR_E_INVALID, "%s: edge %d, component %d: the weight must be finite and > 0", who, k, p - p0);
+      if (!(std::isfinite(det) && det > 0))
+        return set_err(ctx, CGMR_E_INVALID, "%s: edge %d, component %d: det Omega (the factor's own dimension) must be finite and > 0", who, k, p - p0);
+      const double a = 2 * std::log(w) + std::log(det);
+      M.off[p] = a;
+      if (p == p0 || a > amax) amax = a;
+    }
+    for (int p = p0; p < p1; p++) M.off[p] = amax - M.off[p];
+  }
+  return 0;
+}
+// ... staged through mix_arena into Ed (nothing without a multi-component edge); the selection lands behind the lists
+static int mix_upload(cgmr_ctx* ctx, const MixHost* M, int nE, GnEdges& Ed) {
+  if (!M || !M->any) return 0;
+  Layout256 L;
+  const size_t nC = M->nC, n = (size_t)nE;
+  const size_t o_ptr = L.add(4 * (n + 1)), o_meas = L.add(24 * nC), o_info = L.add(48 * nC), o_off = L.add(8 * nC), o_sel = L.add(4 * n);
+  int rc = arena_reserve(ctx, ctx->mix_arena, L.off + 256);
+  if (rc) return rc;
+  char* d = ctx->mix_arena.ptr;
+  hipStream_t st = ctx->stream;
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_ptr, M->mix->comp_ptr, 4 * (n + 1), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_meas, M->mix->comp_meas, 24 * nC, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_info, M->mix->comp_info, 48 * nC, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_off, M->off.data(), 8 * nC, hipMemcpyHostToDevice, st));
+  Ed.mix = true;
+  Ed.mix_ptr = (const int32_t*)(d + o_ptr);
+  Ed.mix_meas = (const double*)(d + o_meas); Ed.mix_info = (const double*)(d + o_info); Ed.mix_off = (const double*)(d + o_off);
+  Ed.mix_sel = M->mix->selected_out ? (int32_t*)(d + o_sel) : nullptr;
+  return 0;
+}
+// every edge's first component: what a call routed to the typed / plain path, or one that fails, leaves in selected_out
+static void mix_selection_zero(const cgmr_mixture* mix, int nE) {
+  if (mix && mix->selected_out) for (int k = 0; k < nE; k++) mix->selected_out[k] = 0;
+}
+// the selection of the call's final pass to the caller's host array
+static int mix_selection_out(cgmr_ctx* ctx, const MixHost* M, int nE, const GnEdges& Ed) {
+  if (!M || !Ed.mix_sel || nE <= 0) return 0;
+  HIP_TRY(ctx, hipMemcpyAsync(M->mix->selected_out, Ed.mix_sel, 4 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 // The arguments every *_optimize* entry point takes, checked alike; `name`: the entry point family in the error text
 static int optimize_args_check(cgmr_ctx* ctx, const char* name, int nV, const double* poses, const uint8_t* fixed, int nE,
                                const int32_t* from_idx, const int32_t* to_idx, const double* meas, const double* info, int iters) {
@@ -1740,12 +1823,15 @@ static int optimize_args_check(cgmr_ctx* ctx, const char* name, int nV, const do
 // the robust statistics are returned when the call ended well, and with cholesky_too also on a Cholesky status.
 template <typename Run>
 static int optimize_staged(cgmr_ctx* ctx, const char* who, bool dev, bool cholesky_too, int nV, double* poses, int nE,
-                           const double* meas, const double* info, const cgmr_robust* rk, const TypedHost* typed, Run&& run) {
+                           const double* meas, const double* info, const cgmr_robust* rk, const TypedHost* typed, Run&& run,
+                           const MixHost* mix = nullptr) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   GnEdges Ed;
   int rc = robust_setup(ctx, rk, nE, dev, Ed, who);
   if (rc) return rc;
   rc = typed_upload(ctx, typed, Ed);
+  if (rc) return rc;
+  rc = mix_upload(ctx, mix, nE, Ed);
   if (rc) return rc;
   double* d_poses = poses;
   const size_t bp = sizeof(double) * 3 * (size_t)nV;
@@ -1758,9 +1844,13 @@ static int optimize_staged(cgmr_ctx* ctx, const char* who, bool dev, bool choles
     if (rc) return rc;
     char* d = ctx->io_arena.ptr;
     HIP_TRY(ctx, hipMemcpyAsync(d, poses, bp, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d + om, meas, bm, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d + oi, info, bi, hipMemcpyHostToDevice, ctx->stream));
-    Ed.meas_a = (const double*)(d + om); Ed.info_a = (const double*)(d + oi);
+    if (Ed.mix) {                        // (a mixture pass reads the component lists alone: the first components stay on the host)
+      Ed.meas_a = Ed.mix_meas; Ed.info_a = Ed.mix_info;
+    } else {
+      HIP_TRY(ctx, hipMemcpyAsync(d + om, meas, bm, hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(d + oi, info, bi, hipMemcpyHostToDevice, ctx->stream));
+      Ed.meas_a = (const double*)(d + om); Ed.info_a = (const double*)(d + oi);
+    }
     d_poses = (double*)d;
   }
   Ed.nA = nE; Ed.n_active = nE;
@@ -1773,53 +1863,69 @@ static int optimize_staged(cgmr_ctx* ctx, const char* who, bool dev, bool choles
     }
     const int rs = robust_stats_out(ctx, rk, nE, Ed);
     if (rs) return rs;
+    const int ms = mix_selection_out(ctx, mix, nE, Ed);
+    if (ms) return ms;
   }
   return rc;
 }
 
 static int gn_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                             const int32_t* to_idx, const double* meas, const double* info, int iters, double* chi2_out,
-                            const cgmr_robust* rk, bool dev, const cgmr_factor_types* ft = nullptr) {
+                            const cgmr_robust* rk, bool dev, const cgmr_factor_types* ft = nullptr,
+                            const cgmr_mixture* mix = nullptr) {
   int rc = optimize_args_check(ctx, "cgmr_gn_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
   if (rc) return rc;
   TypedHost typed;
-  rc = typed_check(ctx, dev ? "cgmr_gn_optimize_typed_dev" : "cgmr_gn_optimize_typed", ft, nV, nE, from_idx, to_idx, typed);
+  rc = typed_check(ctx, mix ? "cgmr_gn_optimize_mixture" : dev ? "cgmr_gn_optimize_typed_dev" : "cgmr_gn_optimize_typed", ft, nV, nE, from_idx, to_idx, typed);
   if (rc) return rc;
+  MixHost mh;
+  rc = mix_check(ctx, "cgmr_gn_optimize_mixture", mix, nE, typed, mh);
+  if (rc) return rc;
+  mix_selection_zero(mix, nE);
   return optimize_staged(ctx, ft ? "cgmr_gn_optimize_typed" : dev ? "cgmr_gn_optimize_robust_dev" : "cgmr_gn_optimize_robust", dev, true, nV, poses, nE, meas, info, rk, &typed,
-                         [&](double* d_poses, const GnEdges& Ed) { return gn_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, chi2_out); });
+                         [&](double* d_poses, const GnEdges& Ed) { return gn_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, chi2_out); }, &mh);
 }
 
 static int lm_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                             const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_lm_params* params,
                             double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done, const cgmr_robust* rk,
-                            bool dev, const cgmr_factor_types* ft = nullptr) {
+                            bool dev, const cgmr_factor_types* ft = nullptr, const cgmr_mixture* mix = nullptr) {
   int rc = optimize_args_check(ctx, "cgmr_lm_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
   if (rc) return rc;
   TypedHost typed;
-  rc = typed_check(ctx, dev ? "cgmr_lm_optimize_typed_dev" : "cgmr_lm_optimize_typed", ft, nV, nE, from_idx, to_idx, typed);
+  rc = typed_check(ctx, mix ? "cgmr_lm_optimize_mixture" : dev ? "cgmr_lm_optimize_typed_dev" : "cgmr_lm_optimize_typed", ft, nV, nE, from_idx, to_idx, typed);
   if (rc) return rc;
+  MixHost mh;
+  rc = mix_check(ctx, "cgmr_lm_optimize_mixture", mix, nE, typed, mh);
+  if (rc) return rc;
+  mix_selection_zero(mix, nE);
   return optimize_staged(ctx, ft ? "cgmr_lm_optimize_typed" : dev ? "cgmr_lm_optimize_robust_dev" : "cgmr_lm_optimize_robust", dev, false, nV, poses, nE, meas, info, rk, &typed,
                          [&](double* d_poses, const GnEdges& Ed) {
                            return lm_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, lambda_out, trials_out, iters_done);
-                         });
+                         }, &mh);
 }
 
 static int dl_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                             const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_dl_params* params,
                             double* chi2_out, double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
-                            const cgmr_robust* rk, bool dev, const cgmr_factor_types* ft = nullptr) {
+                            const cgmr_robust* rk, bool dev, const cgmr_factor_types* ft = nullptr,
+                            const cgmr_mixture* mix = nullptr) {
   int rc = optimize_args_check(ctx, "cgmr_dl_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
   if (rc) return rc;
   TypedHost typed;
-  rc = typed_check(ctx, dev ? "cgmr_dl_optimize_typed_dev" : "cgmr_dl_optimize_typed", ft, nV, nE, from_idx, to_idx, typed);
+  rc = typed_check(ctx, mix ? "cgmr_dl_optimize_mixture" : dev ? "cgmr_dl_optimize_typed_dev" : "cgmr_dl_optimize_typed", ft, nV, nE, from_idx, to_idx, typed);
   if (rc) return rc;
+  MixHost mh;
+  rc = mix_check(ctx, "cgmr_dl_optimize_mixture", mix, nE, typed, mh);
+  if (rc) return rc;
+  mix_selection_zero(mix, nE);
   if (!dl_params_ok(params))
     return set_err(ctx, CGMR_E_INVALID,
                    "cgmr_dl_optimize: max_trials must be >= 1, initial_delta / initial_lambda > 0, lambda_factor > 1, all finite");
   return optimize_staged(ctx, ft ? "cgmr_dl_optimize_typed" : dev ? "cgmr_dl_optimize_dev" : "cgmr_dl_optimize", dev, true, nV, poses, nE, meas, info, rk, &typed,
                          [&](double* d_poses, const GnEdges& Ed) {
                            return dl_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, delta_out, trials_out, step_out, iters_done);
-                         });
+                         }, &mh);
 }
 
 
@@ -2087,6 +2193,7 @@ void cgmr_ctx_destroy(cgmr_ctx* ctx) {
   if (ctx->gnc_arena.ptr) (void)hipFree(ctx->gnc_arena.ptr);
   if (ctx->rk_arena.ptr) (void)hipFree(ctx->rk_arena.ptr);
   if (ctx->ty_arena.ptr) (void)hipFree(ctx->ty_arena.ptr);
+  if (ctx->mix_arena.ptr) (void)hipFree(ctx->mix_arena.ptr);
   if (ctx->st_arena.ptr) (void)hipFree(ctx->st_arena.ptr);
   if (ctx->pinned_st) (void)hipHostFree(ctx->pinned_st);
   if (ctx->ev_st_copied) (void)hipEventDestroy(ctx->ev_st_copied);
@@ -2244,6 +2351,55 @@ int cgmr_marginals_all_typed(cgmr_ctx* ctx, int nV, const double* poses, const u
                              const cgmr_factor_types* types, const cgmr_robust* rk) {
   if (!ctx) return CGMR_E_INVALID;
   return marginals_all_driver(ctx, nV, poses, fixed, nE, ef, et, meas, info, cov_out, cross_out, rk, types);
+}
+
+/* max-mixture edges (include/cgmr.h: cgmr_mixture): the typed entry points without a robust kernel, plus the mixture */
+int cgmr_gn_optimize_mixture(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                             const int32_t* to_idx, const double* meas, const double* info, int iters, double* chi2_out,
+                             const cgmr_factor_types* ft, const cgmr_mixture* mix) {
+  return gn_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, chi2_out, nullptr, false, ft, mix);
+}
+int cgmr_gn_optimize_mixture_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                                 const int32_t* to_idx, const double* d_meas, const double* d_info, int iters, double* chi2_out,
+                                 const cgmr_factor_types* ft, const cgmr_mixture* mix) {
+  return gn_optimize_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, chi2_out, nullptr, true, ft, mix);
+}
+int cgmr_lm_optimize_mixture(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                             const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_lm_params* params,
+                             double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done,
+                             const cgmr_factor_types* ft, const cgmr_mixture* mix) {
+  return lm_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, params, chi2_out, lambda_out, trials_out,
+                          iters_done, nullptr, false, ft, mix);
+}
+int cgmr_lm_optimize_mixture_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                                 const int32_t* to_idx, const double* d_meas, const double* d_info, int iters,
+                                 const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
+                                 int32_t* iters_done, const cgmr_factor_types* ft, const cgmr_mixture* mix) {
+  return lm_optimize_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, params, chi2_out, lambda_out,
+                          trials_out, iters_done, nullptr, true, ft, mix);
+}
+int cgmr_dl_optimize_mixture(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                             const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_dl_params* params,
+                             double* chi2_out, double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
+                             const cgmr_factor_types* ft, const cgmr_mixture* mix) {
+  return dl_optimize_impl(ctx, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, params, chi2_out, delta_out, trials_out,
+                          step_out, iters_done, nullptr, false, ft, mix);
+}
+int cgmr_dl_optimize_mixture_dev(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                                 const int32_t* to_idx, const double* d_meas, const double* d_info, int iters,
+                                 const cgmr_dl_params* params, double* chi2_out, double* delta_out, int32_t* trials_out,
+                                 int32_t* step_out, int32_t* iters_done, const cgmr_factor_types* ft, const cgmr_mixture* mix) {
+  return dl_optimize_impl(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, d_meas, d_info, iters, params, chi2_out, delta_out,
+                          trials_out, step_out, iters_done, nullptr, true, ft, mix);
+}
+/* chi2 and selection at the given poses: Gauss-Newton with no iteration, which is its one chi-only pass */
+int cgmr_mixture_select(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                        const int32_t* to_idx, const double* meas, const double* info, const cgmr_factor_types* ft,
+                        const cgmr_mixture* mix, double* chi2_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  if (nV < 0 || (nV > 0 && !poses)) return set_err(ctx, CGMR_E_INVALID, "cgmr_mixture_select: null or negative argument");
+  std::vector<double> x(poses, poses + 3 * (size_t)nV);
+  return gn_optimize_impl(ctx, nV, x.data(), fixed, nE, from_idx, to_idx, meas, info, 0, chi2_out, nullptr, false, ft, mix);
 }
 
 cgmr_gnc_params cgmr_gnc_params_default(void) { return gnc_defaults(); }

@@ -39,6 +39,7 @@ struct cgmr_ctx {
   cgmr::Arena lm_arena;     // cgmr_lm_optimize*: the Levenberg-Marquardt state, its records and the saved poses (lm_kernels.hip)
   cgmr::Arena rk_arena;     // robust entry points: staged per-edge kinds / deltas, the per-edge statistics (cgmr_robust)
   cgmr::Arena ty_arena;     // typed entry points: staged edge kinds and the priors' per-vertex lists (cgmr_factor_types)
+  cgmr::Arena mix_arena;    // mixture entry points: staged component lists, offsets and the selection (cgmr_mixture)
   int64_t lm_stats[2] = {0, 0};   // last Levenberg-Marquardt call: host waits, trials
   cgmr::Arena dl_arena;     // cgmr_dl_optimize*: the dogleg state, its records, the saved poses, hgn / hsd (dl_kernels.hip)
   int64_t dl_stats[3] = {0, 0, 0};   // last dogleg call: host waits, trials, factorisations

@@ -93,6 +93,14 @@ struct GnEdges {
   // the linear stage whose records the pass solves -- init_device.h: kChordalRotation / kChordalTranslation.  One job, never
   // with `robust` or `gnc`; a rotation pass ends with k_apply_rotation in the place of k_update_poses.
   int chordal_stage = 0;
+  // max-mixture edges (include/cgmr.h: cgmr_mixture; gn_kernels.hip: MixArgs): edge k owns the components [mix_ptr[k],
+  // mix_ptr[k + 1]) of (mix_meas, mix_info), each with its offset mix_off; the linearisation keeps the cheapest one and
+  // writes its index within the edge to mix_sel (nullable) -- device memory.  meas_a / info_a are not read.  One job, nA ==
+  // nE, never with `robust`, `gnc` or a chordal stage.
+  bool mix = false;
+  const int32_t* mix_ptr = nullptr;
+  const double *mix_meas = nullptr, *mix_info = nullptr, *mix_off = nullptr;
+  int32_t* mix_sel = nullptr;
 };
 // gn_structure.hip: the assembly lists (asm_ptr: nf + nb + 1, asm_src: one entry per (edge, key)) from the permutation, the
 // edge list and the off-diagonal blocks (offbase: nf + 1 column starts into off_row); work space: ekey nE, cnt nf + nb + 3,

@@ -198,6 +198,40 @@ struct GncArgs {
   double* r_out;           // [nE] or null: r of every edge
   int mode;
 };
+// MIX (max-mixture edges, include/cgmr.h: cgmr_mixture): a fifth kind of trailing argument, in two instances of its own with
+// and without TypedArgs, one job, never with RobustArgs or GncArgs -- the twelve others keep their names and their code.  Edge
+// k owns the components [cptr[k], cptr[k + 1]) of (cmeas, cinfo); meas / info are not read.  The thread forms r_p = e(z_p)^T O_p
+// e(z_p) of every component of its edge in the factor's own dimension (mix_r below: the error lines of the kernel), keeps the
+// first argmin of r_p + coff[p] (ascending, strict <) and falls into the code below with that component's z and O; the chi2
+// partial sum takes r + coff of it.  An edge with one component skips the scan: K components cost K + 1 error evaluations,
+// one none.  sel_out [nE] (nullable) receives the component's index within its edge.  Every linearisation selects afresh at
+// the poses it is given, a chi-only one too.
+struct MixArgs {
+  const int32_t* cptr;     // [nE + 1]
+  const double* cmeas;     // [3 nC]
+  const double* cinfo;     // [6 nC]
+  const double* coff;      // [nC]: max_j a_j - a_p >= 0, a = 2 ln w + ln det O (own dimension); 0 for an edge of one component
+  int32_t* sel_out;        // [nE] or null
+};
+// e^T O e of factor kind fk with measurement z and information u (upper triangle), from what the linearisation has of the two
+// vertices: (rx, ry, rth) = x_i^-1 x_j, x_i itself for the priors
+__device__ __forceinline__ double mix_r(int fk, double rx, double ry, double rth, double xi0, double xi1, double xi2,
+                                        const double* __restrict__ z, const double* __restrict__ u) {
+  const double z0 = z[0], z1 = z[1], z2 = z[2];
+  const double cz = cos(z2), sz = sin(z2);
+  const double tx = rx - z0, ty = ry - z1;
+  double e0 = cz * tx + sz * ty, e1 = -sz * tx + cz * ty, e2 = d_normalize_theta(rth - z2);
+  if (fk == 1) { e0 = tx; e1 = ty; }
+  else if (fk == 2) {
+    const double b = d_normalize_theta((rx * rx + ry * ry > 0.0 ? atan2(ry, rx) : 0.0) - z0);
+    return b * (u[0] * b);
+  } else if (fk == 3) {
+    const double px = xi0 - z0, py = xi1 - z1;
+    e0 = cz * px + sz * py; e1 = -sz * px + cz * py; e2 = d_normalize_theta(xi2 - z2);
+  } else if (fk == 4) { e0 = xi0 - z0; e1 = xi1 - z1; }
+  if (fk == 1 || fk == 4) return e0 * (u[0] * e0 + u[1] * e1) + e1 * (u[1] * e0 + u[3] * e1);
+  return e0 * (u[0] * e0 + u[1] * e1 + u[2] * e2) + e1 * (u[1] * e0 + u[3] * e1 + u[4] * e2) + e2 * (u[2] * e0 + u[4] * e1 + u[5] * e2);
+}
 template <typename T> __device__ __forceinline__ T pick_arg(T a) { return a; }
 template <typename T, typename U> __device__ __forceinline__ T pick_arg(T a, U) { return a; }
 template <typename T, typename U> __device__ __forceinline__ T pick_arg(U, T b) { return b; }
@@ -212,8 +246,11 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
                                                    Rk... rk_pack) {
   constexpr bool TYPED = pack_has<TypedArgs, Rk...>::value;
   constexpr bool GNC = pack_has<GncArgs, Rk...>::value;
-  static_assert(sizeof...(Rk) == (ROBUST ? 1 : 0) + (TYPED ? 1 : 0) + (GNC ? 1 : 0) && !(ROBUST && GNC) && !(BATCH && GNC && TYPED),
-                "k_linearize: one RobustArgs in the robust instances, one TypedArgs in the typed ones, one GncArgs in the GNC ones");
+  constexpr bool MIX = pack_has<MixArgs, Rk...>::value;
+  static_assert(sizeof...(Rk) == (ROBUST ? 1 : 0) + (TYPED ? 1 : 0) + (GNC ? 1 : 0) + (MIX ? 1 : 0) && !(ROBUST && GNC) &&
+                    !(BATCH && GNC && TYPED) && !(MIX && (ROBUST || GNC || BATCH)),
+                "k_linearize: one RobustArgs in the robust instances, one TypedArgs in the typed ones, one GncArgs in the GNC ones, "
+                "one MixArgs in the mixture ones (never robust, GNC or a batch)");
   CGMR_JOB(poses, ps); CGMR_JOB(term, js);
   __shared__ double s_chi[4];
   const int k0 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -228,10 +265,29 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
   double dx = xj0 - xi0, dy = xj1 - xi1;
   double rx = c * dx + s * dy, ry = -s * dx + c * dy;
   double rth = d_normalize_theta(xj2 - xi2);
+  [[maybe_unused]] int mix_best = 0;
+  if constexpr (MIX) {
+    const MixArgs mx = pick_arg<MixArgs>(rk_pack...);
+    const int p0 = mx.cptr[k], p1 = mx.cptr[k + 1];
+    mix_best = p0;
+    if (p1 - p0 > 1) {
+      int mfk = 0;
+      if constexpr (TYPED) mfk = (int)pick_arg<TypedArgs>(rk_pack...).edge_kind[k];
+      double best = mix_r(mfk, rx, ry, rth, xi0, xi1, xi2, mx.cmeas + 3 * (size_t)p0, mx.cinfo + 6 * (size_t)p0) + mx.coff[p0];
+      for (int p = p0 + 1; p < p1; p++) {
+        const double cost = mix_r(mfk, rx, ry, rth, xi0, xi1, xi2, mx.cmeas + 3 * (size_t)p, mx.cinfo + 6 * (size_t)p) + mx.coff[p];
+        if (cost < best) { best = cost; mix_best = p; }
+      }
+    }
+    if (mx.sel_out && k0 < nE) mx.sel_out[k] = mix_best - p0;
+    const double* zs = mx.cmeas + 3 * (size_t)mix_best;
+    z0 = zs[0]; z1 = zs[1]; z2 = zs[2];
+  }
   double cz = cos(z2), sz = sin(z2);
   double tx = rx - z0, ty = ry - z1;
   double e[3] = {cz * tx + sz * ty, -sz * tx + cz * ty, d_normalize_theta(rth - z2)};
   const double* u = k < nA ? info + 6 * (size_t)k : info_b + 6 * (size_t)(k - nA);
+  if constexpr (MIX) u = pick_arg<MixArgs>(rk_pack...).cinfo + 6 * (size_t)mix_best;
   double O[9] = {u[0], u[1], u[2], u[1], u[3], u[4], u[2], u[4], u[5]};
   [[maybe_unused]] int fk = 0;
   if constexpr (TYPED) {
@@ -282,6 +338,7 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
       }
       ch = live ? rho1 * r : 0.0;
     }
+    if constexpr (MIX) ch = live ? ch + pick_arg<MixArgs>(rk_pack...).coff[mix_best] : 0.0;
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) ch += __shfl_xor(ch, m, 64);
     if ((threadIdx.x & 63) == 0) s_chi[threadIdx.x >> 6] = ch;
@@ -1700,6 +1757,20 @@ void launch_linearize(hipStream_t st, const GnDevice& D, const double* poses, co
                        Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride, D.pose_stride, ga);
     return;
   }
+  if (Ed.mix) {                       // (one job, never robust: the mixture entry points take no kernel)
+    MixArgs mx;
+    mx.cptr = Ed.mix_ptr; mx.cmeas = Ed.mix_meas; mx.cinfo = Ed.mix_info; mx.coff = Ed.mix_off; mx.sel_out = Ed.mix_sel;
+    if (Ed.typed) {
+      TypedArgs ty;
+      ty.edge_kind = Ed.edge_kind;
+      hipLaunchKernelGGL((k_linearize<false, false, TypedArgs, MixArgs>), grid, dim3(256), lds, st, D.nE, Ed.nA, Ed.n_active, poses, D.ef,
+                         D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride, D.pose_stride, ty, mx);
+      return;
+    }
+    hipLaunchKernelGGL((k_linearize<false, false, MixArgs>), grid, dim3(256), lds, st, D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et,
+                       Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride, D.pose_stride, mx);
+    return;
+  }
   if (Ed.typed) {                     // (never a batch: the typed entry points run one job)
     TypedArgs ty;
     ty.edge_kind = Ed.edge_kind;
@@ -1766,7 +1837,9 @@ void gn_init_kernels() {
                           reinterpret_cast<const void*>(k_linearize<true, true, RobustArgs, TypedArgs>),
                           reinterpret_cast<const void*>(k_linearize<false, false, GncArgs>),
                           reinterpret_cast<const void*>(k_linearize<false, false, TypedArgs, GncArgs>),
-                          reinterpret_cast<const void*>(k_linearize<true, false, GncArgs>)})
+                          reinterpret_cast<const void*>(k_linearize<true, false, GncArgs>),
+                          reinterpret_cast<const void*>(k_linearize<false, false, MixArgs>),
+                          reinterpret_cast<const void*>(k_linearize<false, false, TypedArgs, MixArgs>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 33 * (int)sizeof(double));
     for (const void* f : {reinterpret_cast<const void*>(k_top_block<false>), reinterpret_cast<const void*>(k_top_block<true>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, top_smem_bytes(kTopMaxCols));

@@ -87,6 +87,71 @@ class PoseGraph:
         # (z, 0, 0) and (I, 0, 0, 0, 0, 0).  None: a pure pose graph, as ever.
         self.vertex_kind = None if vertex_kind is None else np.ascontiguousarray(vertex_kind, dtype=np.uint8).copy()
         self.edge_kind = None if edge_kind is None else np.ascontiguousarray(edge_kind, dtype=np.uint8).copy()
+        # max-mixture edges (include/cgmr.h: cgmr_mixture): edge index -> (meas [K, 3], info [K, 6], weight [K]), K >= 2, in the
+        # padded layout of meas / info; row 0 is the edge's own (meas, info), which every other call goes on reading.  Empty: a
+        # graph without mixtures, as ever.
+        self.mixtures = {}
+
+    @property
+    def has_mixtures(self):
+        """True when some edge has more than one component (the solver then takes the mixture entry points)."""
+        return bool(self.mixtures)
+
+    def set_edge_mixture(self, edge, components):
+        """Make edge ``edge`` a mixture of ``components`` = [(weight, meas, info), ...] in add_edge's value counts; component 0
+        becomes the edge's own (meas, info).  One component: a plain edge again."""
+        k = int(edge)
+        if not 0 <= k < self.n_edges:
+            raise ValueError(f"edge index out of range 0..{self.n_edges - 1}")
+        comps = list(components)
+        if not comps:
+            raise ValueError("a mixture edge needs at least one component")
+        kind = int(self.kinds()[1][k])
+        zs, us, ws = np.zeros((len(comps), 3)), np.zeros((len(comps), 6)), np.zeros(len(comps))
+        for c, (w, meas, info) in enumerate(comps):
+            zs[c], us[c] = self._pad_factor(kind, meas, info)
+            ws[c] = float(w)
+        self.meas[k], self.info[k] = zs[0], us[0]
+        if len(comps) > 1:
+            self.mixtures[k] = (zs, us, ws)
+        else:
+            self.mixtures.pop(k, None)
+
+    def mixture_arrays(self, level0=True):
+        """(comp_ptr [n + 1], comp_meas [nC, 3], comp_info [nC, 6], comp_weight [nC]) over the level-0 edges in level0() order
+        (``level0=False``: over all edges), or None for a graph without mixtures."""
+        if not self.mixtures:
+            return None
+        idx = np.flatnonzero(self.edge_level == 0) if level0 else np.arange(self.n_edges)
+        ptr, zs, us, ws = [0], [], [], []
+        for k in idx:
+            mz, mu, mw = self.mixtures.get(int(k), (self.meas[k][None, :], self.info[k][None, :], np.ones(1)))
+            if int(k) in self.mixtures:
+                mz = mz.copy()
+                mu = mu.copy()
+                mz[0], mu[0] = self.meas[k], self.info[k]          # (component 0 is the edge's own, wherever it was changed)
+            zs.append(mz)
+            us.append(mu)
+            ws.append(mw)
+            ptr.append(ptr[-1] + len(mw))
+        if ptr[-1] == len(idx):
+            return None                                            # (the mixtures are on edges of other levels)
+        return (np.asarray(ptr, dtype=np.int32), np.concatenate(zs).reshape(-1, 3), np.concatenate(us).reshape(-1, 6),
+                np.concatenate(ws))
+
+    @staticmethod
+    def _pad_factor(kind, meas, info):
+        """(meas [3], info [6]) of a factor of ``kind`` from add_edge's value counts."""
+        m, u = np.zeros(3), np.zeros(6)
+        mv, uv = np.asarray(meas, dtype=np.float64).reshape(-1), np.asarray(info, dtype=np.float64).reshape(-1)
+        if kind in (1, 4):
+            m[:2] = mv[:2]
+            u[[0, 1, 3]] = uv[:3] if uv.size == 3 else uv[[0, 1, 3]]
+        elif kind == 2:
+            m[0], u[0] = mv[0], uv[0]
+        else:
+            m[:], u[:] = mv[:3], uv[:6]
+        return m, u
 
     @property
     def typed(self):
@@ -154,7 +219,9 @@ class PoseGraph:
     # ---------------------------------------------------------------- .g2o text format
     def save_g2o(self, path, precision=None):
         """VERTEX_SE2 (+ ROBOTLASER1 data) / FIX / EDGE_SE2 lines, and for a typed graph VERTEX_XY, EDGE_SE2_XY,
-        EDGE_BEARING_SE2_XY, EDGE_PRIOR_SE2 and EDGE_PRIOR_SE2_XY.  ``precision=None`` reproduces g2o's default ostream precision (6 significant
+        EDGE_BEARING_SE2_XY, EDGE_PRIOR_SE2 and EDGE_PRIOR_SE2_XY; a mixture edge as ``EDGE_SE2_MIXTURE from to K`` followed by K groups
+        ``w x y th I11 I12 I13 I22 I23 I33`` (an edge of another kind: its own line, then ``MIXTURE_COMPONENTS K`` and the
+        groups; the project's own tags).  ``precision=None`` reproduces g2o's default ostream precision (6 significant
         digits, lossy -- SURVEY.md section 5); pass 17 for round trips."""
         fmt = "%g" if precision is None else f"%.{precision}g"
         vk, ek = self.kinds()
@@ -174,20 +241,34 @@ class PoseGraph:
                     continue                      # only level-0 edges are saved by default
                 m = self.meas[k]
                 i = self.info[k]
+                if k in self.mixtures:
+                    # the project's own tags (no claim of compatibility with vertigo's): K groups of weight, the three
+                    # measurement values and the six information values of the padded layout.  An EDGE_SE2 becomes one
+                    # EDGE_SE2_MIXTURE line; an edge of another kind keeps its line (component 0) and a MIXTURE_COMPONENTS
+                    # line follows it
+                    mz, mu, mw = self.mixtures[k]
+                    groups = " ".join(fmt % v for c in range(len(mw)) for v in (mw[c], *(m if c == 0 else mz[c]), *(i if c == 0 else mu[c])))
+                    if ek[k] == 0:
+                        f.write("EDGE_SE2_MIXTURE %d %d %d " % (self.ids[self.edge_from[k]], self.ids[self.edge_to[k]], len(mw))
+                                + groups + "\n")
+                        continue
+                    tail = "MIXTURE_COMPONENTS %d " % len(mw) + groups + "\n"
+                else:
+                    tail = ""
                 if ek[k] == 1:
                     f.write("EDGE_SE2_XY %d %d " % (self.ids[self.edge_from[k]], self.ids[self.edge_to[k]])
-                            + " ".join(fmt % v for v in (*m[:2], i[0], i[1], i[3])) + "\n")
+                            + " ".join(fmt % v for v in (*m[:2], i[0], i[1], i[3])) + "\n" + tail)
                     continue
                 if ek[k] == 2:
                     f.write("EDGE_BEARING_SE2_XY %d %d " % (self.ids[self.edge_from[k]], self.ids[self.edge_to[k]])
-                            + " ".join(fmt % v for v in (m[0], i[0])) + "\n")
+                            + " ".join(fmt % v for v in (m[0], i[0])) + "\n" + tail)
                     continue
                 if ek[k] == 3:
-                    f.write("EDGE_PRIOR_SE2 %d " % self.ids[self.edge_from[k]] + " ".join(fmt % v for v in (*m, *i)) + "\n")
+                    f.write("EDGE_PRIOR_SE2 %d " % self.ids[self.edge_from[k]] + " ".join(fmt % v for v in (*m, *i)) + "\n" + tail)
                     continue
                 if ek[k] == 4:
                     f.write("EDGE_PRIOR_SE2_XY %d " % self.ids[self.edge_from[k]]
-                            + " ".join(fmt % v for v in (*m[:2], i[0], i[1], i[3])) + "\n")
+                            + " ".join(fmt % v for v in (*m[:2], i[0], i[1], i[3])) + "\n" + tail)
                     continue
                 f.write("EDGE_SE2 %d %d " % (self.ids[self.edge_from[k]], self.ids[self.edge_to[k]])
                         + " ".join(fmt % v for v in (*m, *i)) + "\n")
@@ -197,6 +278,7 @@ class PoseGraph:
         ids, poses, fixed_ids, ef, et, meas, info = [], [], set(), [], [], [], []
         vkind, ekind = [], []     # typed graphs: VERTEX_XY, EDGE_SE2_XY, EDGE_BEARING_SE2_XY, EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY
         lasers = {}               # vertex id -> RobotLaser
+        mixtures = {}             # edge index -> (meas [K, 3], info [K, 6], weight [K]): EDGE_SE2_MIXTURE / MIXTURE_COMPONENTS
 
         def info2(t):             # I11 I12 I22 in the 3x3 upper-triangle layout
             a, b, c = (float(v) for v in t)
@@ -246,6 +328,21 @@ class PoseGraph:
                     meas.append([float(tok[2]), float(tok[3]), 0.0])
                     info.append(info2(tok[4:7]))
                     ekind.append(4)
+                elif tok[0] == "EDGE_SE2_MIXTURE":
+                    K = int(tok[3])
+                    v = np.array([float(x) for x in tok[4:4 + 10 * K]]).reshape(K, 10)
+                    ef.append(int(tok[1]))
+                    et.append(int(tok[2]))
+                    meas.append(list(v[0, 1:4]))
+                    info.append(list(v[0, 4:10]))
+                    ekind.append(0)
+                    if K > 1:
+                        mixtures[len(ef) - 1] = (v[:, 1:4].copy(), v[:, 4:10].copy(), v[:, 0].copy())
+                elif tok[0] == "MIXTURE_COMPONENTS" and ef:
+                    K = int(tok[1])
+                    v = np.array([float(x) for x in tok[2:2 + 10 * K]]).reshape(K, 10)
+                    if K > 1:
+                        mixtures[len(ef) - 1] = (v[:, 1:4].copy(), v[:, 4:10].copy(), v[:, 0].copy())
                 elif tok[0] == "ROBOTLASER1" and ids:
                     lasers[ids[-1]] = RobotLaser.read(tok)     # data lines belong to the preceding vertex
         ids = np.asarray(ids, dtype=np.int64)
@@ -261,6 +358,7 @@ class PoseGraph:
             g.vertex_kind = np.asarray(vkind, dtype=np.uint8)[order]
             g.edge_kind = np.asarray(ekind, dtype=np.uint8)
         g.lasers = {index[v]: l for v, l in lasers.items()}
+        g.mixtures = mixtures
         return g
 
 
@@ -299,6 +397,7 @@ class GraphSLAM:
         self.last_mu = None
         self._gnc_rejected = None
         self.last_init_counts = None
+        self.last_selected = None
 
     def optimize(self, nrunnings: int) -> None:
         """``nrunnings`` iterations on the level-0 edges; estimates updated in place.  Returns nothing and never raises on
@@ -309,7 +408,25 @@ class GraphSLAM:
         rk = self._robust_level0()
         self.last_edge_chi2 = self.last_weights = None
         ty = self._typed_level0()
-        if ty is not None:
+        mix = g.mixture_arrays()
+        if mix is not None:
+            # max-mixture edges: the mixture entry points, under every algorithm; no robust kernel beside them
+            if rk is not None:
+                raise ValueError("optimize: a graph with mixture edges takes no robust kernel (clearRobustKernels, or collapseMixtures)")
+            a = (g.poses, g.fixed, ef, et, meas, info, int(nrunnings), mix)
+            kw = {} if ty is None else dict(vertex_kind=ty[0], edge_kind=ty[1])
+            if self.algorithm == "levenberg":
+                rc, poses, chi2, lam, tri, done, sel = self.ctx.lm_optimize_mixture(*a, **kw, **self.lm_params)
+                self.last_lambdas, self.last_trials, self.last_iterations = lam[:done], tri[:done], done
+            elif self.algorithm == "dl":
+                rc, poses, chi2, dlt, tri, stp, done, sel = self.ctx.dl_optimize_mixture(*a, **kw, raise_on_fail=False, **self.dl_params)
+                self.last_deltas, self.last_trials, self.last_steps = dlt[:done], tri[:done], stp[:done]
+                self.last_iterations = done if rc == 0 else 0
+            else:
+                rc, poses, chi2, sel = self.ctx.gn_optimize_mixture(*a, **kw, raise_on_cholesky=False)
+                self.last_iterations = int(nrunnings) if rc == 0 else CGMR_E_CHOLESKY_BASE - rc
+            self.last_selected = sel
+        elif ty is not None:
             # landmarks / priors: the typed entry points (the same records; e2 and weights behind them with a kernel set)
             a = (g.poses, g.fixed, ef, et, meas, info, int(nrunnings))
             kw = dict(vertex_kind=ty[0], edge_kind=ty[1], **({} if rk is None else dict(kind=rk[0], delta=rk[1])))
@@ -391,6 +508,8 @@ class GraphSLAM:
         iterations run) and ``last_status``; never raises on a Cholesky failure."""
         from ._lib import gnc_known_mask
         g = self.graph
+        if g.mixture_arrays() is not None:
+            raise ValueError("optimizeGNC: not offered on a graph with mixture edges (collapseMixtures first)")
         m = g.edge_level == 0
         ef, et, meas, info = g.level0()
         ty = self._typed_level0()
@@ -411,6 +530,66 @@ class GraphSLAM:
         if self._gnc_rejected is None:
             raise RuntimeError("rejectedEdges: call optimizeGNC first")
         return self._gnc_rejected.copy()
+
+    # ---------------------------------------------------------------- max-mixture edges
+    def addMixtureEdge(self, i, j, components, kind: int = 0) -> int:     # noqa: N802
+        """An edge between the vertex indices ``i`` and ``j`` that is one of ``components`` = [(weight, meas, info), ...]; every
+        linearisation keeps the most likely one at the current estimate (include/cgmr.h: cgmr_mixture).  Component 0 is what
+        every call outside the mixture path sees of the edge.  Returns the edge index."""
+        comps = list(components)
+        if not comps:
+            raise ValueError("addMixtureEdge: at least one component")
+        k = self.graph.add_edge(i, j, comps[0][1], comps[0][2], kind=kind)
+        self.graph.set_edge_mixture(k, comps)
+        return k
+
+    def setEdgeMixture(self, edge, components) -> None:     # noqa: N802
+        """Replace edge ``edge``'s measurement by the mixture ``components`` = [(weight, meas, info), ...] (one: a plain edge)."""
+        self.graph.set_edge_mixture(edge, components)
+
+    def addNullHypothesis(self, edges, weight: float = 1.0, scale: float = 1e-2) -> None:     # noqa: N802
+        """Give each of the graph's edges ``edges`` a second component with the same measurement and ``scale`` times its
+        information, weights (1, ``weight``): outlier rejection without a schedule.  An edge that is a mixture already gains
+        the component behind its own."""
+        if not (np.isfinite(weight) and weight > 0 and np.isfinite(scale) and scale > 0):
+            raise ValueError("addNullHypothesis: weight and scale must be finite and > 0")
+        g = self.graph
+        for k in np.asarray(edges, dtype=np.int64).reshape(-1):
+            k = int(k)
+            if not 0 <= k < g.n_edges:
+                raise ValueError(f"edge index out of range 0..{g.n_edges - 1}")
+            mz, mu, mw = g.mixtures.get(k, (g.meas[k][None, :], g.info[k][None, :], np.ones(1)))
+            g.mixtures[k] = (np.vstack([mz, g.meas[k][None, :]]), np.vstack([mu, scale * g.info[k][None, :]]),
+                             np.append(mw, float(weight)))
+
+    def _mixture_select(self):
+        g = self.graph
+        ty = self._typed_level0()
+        kw = {} if ty is None else dict(vertex_kind=ty[0], edge_kind=ty[1])
+        return self.ctx.mixture_select(g.poses, g.fixed, *g.level0(), g.mixture_arrays(), **kw)
+
+    def selectedComponents(self):     # noqa: N802
+        """The selected component of every level-0 edge (level0() order) at the current estimates; zeros without mixtures."""
+        return self._mixture_select()[1]
+
+    def mixtureChi2(self) -> float:     # noqa: N802
+        """The mixture cost at the current estimates: the sum over the level-0 edges of min_k (r_k + c_k); chi2() without
+        mixtures.  chi2() itself stays the plain chi2 of every edge's component 0."""
+        return self._mixture_select()[0]
+
+    def collapseMixtures(self) -> PoseGraph:     # noqa: N802
+        """A new PoseGraph without mixtures: every level-0 mixture edge takes its selected (z, Omega) at the current estimates,
+        every other mixture edge its component 0.  The supported route to marginals and condensed graphs."""
+        g = self.graph
+        sel = self.selectedComponents()
+        out = PoseGraph(g.ids, g.poses, g.fixed, g.edge_from, g.edge_to, g.meas.copy(), g.info.copy(), g.edge_level.copy(),
+                        g.vertex_kind, g.edge_kind)
+        out.lasers = dict(g.lasers)
+        for pos, k in enumerate(np.flatnonzero(g.edge_level == 0)):
+            if int(k) in g.mixtures and sel[pos] > 0:
+                mz, mu, _ = g.mixtures[int(k)]
+                out.meas[k], out.info[k] = mz[sel[pos]], mu[sel[pos]]
+        return out
 
     # ---------------------------------------------------------------- landmarks and priors (g2o's slam2d types)
     def _typed_level0(self):

@@ -309,6 +309,71 @@ int cgmr_dl_optimize_typed_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const
                                const double* d_info_upper, int iters, const cgmr_dl_params* params, double* chi2_out,
                                double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
                                const cgmr_factor_types* types, const cgmr_robust* rk);
+/* Max-mixture edges (same ABI version: callers find the entry points by their symbols): an edge is one of K Gaussian
+ * alternatives (z_k, Omega_k, w_k) and every linearisation keeps the most likely one at the estimate it linearises at, after
+ * Olson and Agarwal's max-mixtures [recalled: from memory, not read from the paper's or vertigo's text; the contract is
+ * tests/ref_mixture.py].  For an edge with components k = 1..K:
+ *   r_k = e(z_k)^T Omega_k e(z_k), in the factor's own dimension (as the typed entry points form it)
+ *   a_k = 2 ln w_k + ln det Omega_k, the determinant over the factor's own dimension: 3x3 for kinds 0 and 3, the leading 2x2
+ *         (I11 I12 I22) for kinds 1 and 4, info[0] for a bearing
+ *   c_k = max_j a_j - a_k >= 0
+ *   the edge contributes min_k (r_k + c_k); the selected component is the argmin, ties to the lowest index.
+ * The cost is continuous and non-negative, and for K = 1 it is the plain chi2 (c = 0; Omega may be singular, nothing of it is
+ * checked).  H, b and the chi2 of a linearisation are those of the selected (z, Omega), the chi2 with c added; a chi-only pass
+ * (a Levenberg-Marquardt or dogleg trial point) selects afresh, so the gain ratios compare this cost between points.
+ * Worked example: z equal, Omega_1 = I, Omega_2 = 0.01 I, w = (1/2, 1/2) gives c = (0, 6 ln 10); the second component (a null
+ * hypothesis: same z, inflated covariance) wins exactly when r_1 > 6 ln 10 / 0.99.
+ *   comp_ptr     [nE + 1]: edge k owns the components [comp_ptr[k], comp_ptr[k + 1]); nC = comp_ptr[nE]
+ *   comp_meas    [3 nC], comp_info [6 nC] (upper triangle), comp_weight [nC]
+ *   selected_out [nE], nullable: every edge's selected component (its index within the edge), from the call's final chi-only
+ *                pass at the returned poses
+ * All five are host memory, in the _dev variants too.  meas_xyt / info_upper hold every edge's first component: a null
+ * mixture, a null comp_ptr, or one component on every edge is the typed / plain call on them, bit for bit (the same
+ * launches; selected_out is all zero); on the mixture path they are not read.  The arguments are those of the typed entry
+ * points without rk: a mixture is not combined with cgmr_robust, nor offered for GNC, chordal initialisation, the robot
+ * graph, condensed graphs or batches; every component of an edge has the edge's vertices and kind.  CGMR_E_INVALID, with a
+ * message that names the edge and before the device is touched: a comp_ptr that does not increase from 0 (an edge without a
+ * component); on an edge with K > 1, a weight that is not finite and > 0, or an own-dimension det Omega that is not finite and
+ * > 0.  One launch per linearisation as before: K components cost the edge's thread K + 1 error evaluations.  CGMR_GRAPH
+ * capture is not supported on this path (as for the typed one).
+ * cgmr_mixture_select: the chi2 (chi2_out [1]) and the selection at the given poses -- one chi-only pass, poses untouched; bit
+ * for bit the first (last) chi2 of an optimise call that starts (ends) there. */
+typedef struct cgmr_mixture {
+  const int32_t* comp_ptr;      /* [nE + 1] host */
+  const double* comp_meas;      /* [3 nC] host */
+  const double* comp_info;      /* [6 nC] host */
+  const double* comp_weight;    /* [nC] host */
+  int32_t* selected_out;        /* [nE] host, nullable */
+} cgmr_mixture;
+int cgmr_gn_optimize_mixture(cgmr_ctx* ctx, int nV, double* poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                             const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int iters,
+                             double* chi2_out, const cgmr_factor_types* types, const cgmr_mixture* mixture);
+int cgmr_gn_optimize_mixture_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8_t* fixed, int nE,
+                                 const int32_t* from_idx, const int32_t* to_idx, const double* d_meas_xyt,
+                                 const double* d_info_upper, int iters, double* chi2_out, const cgmr_factor_types* types,
+                                 const cgmr_mixture* mixture);
+int cgmr_lm_optimize_mixture(cgmr_ctx* ctx, int nV, double* poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                             const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int iters,
+                             const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
+                             int32_t* iters_done, const cgmr_factor_types* types, const cgmr_mixture* mixture);
+int cgmr_lm_optimize_mixture_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8_t* fixed, int nE,
+                                 const int32_t* from_idx, const int32_t* to_idx, const double* d_meas_xyt,
+                                 const double* d_info_upper, int iters, const cgmr_lm_params* params, double* chi2_out,
+                                 double* lambda_out, int32_t* trials_out, int32_t* iters_done,
+                                 const cgmr_factor_types* types, const cgmr_mixture* mixture);
+int cgmr_dl_optimize_mixture(cgmr_ctx* ctx, int nV, double* poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                             const int32_t* to_idx, const double* meas_xyt, const double* info_upper, int iters,
+                             const cgmr_dl_params* params, double* chi2_out, double* delta_out, int32_t* trials_out,
+                             int32_t* step_out, int32_t* iters_done, const cgmr_factor_types* types,
+                             const cgmr_mixture* mixture);
+int cgmr_dl_optimize_mixture_dev(cgmr_ctx* ctx, int nV, double* d_poses_xyt, const uint8_t* fixed, int nE,
+                                 const int32_t* from_idx, const int32_t* to_idx, const double* d_meas_xyt,
+                                 const double* d_info_upper, int iters, const cgmr_dl_params* params, double* chi2_out,
+                                 double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
+                                 const cgmr_factor_types* types, const cgmr_mixture* mixture);
+int cgmr_mixture_select(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE, const int32_t* from_idx,
+                        const int32_t* to_idx, const double* meas_xyt, const double* info_upper,
+                        const cgmr_factor_types* types, const cgmr_mixture* mixture, double* chi2_out);
 /* Graduated non-convexity (same ABI version: callers find the entry points by their symbols): outlier rejection by the
  * method of Yang, Antonante, Tzoumas and Carlone (RA-L 2020) as GTSAM's GncOptimizer runs it [recalled: from memory, not read
  * from the paper's or GTSAM's text; the contract is tests/ref_gnc.py].  A truncated-least-squares (TLS) or Geman-McClure (GM)

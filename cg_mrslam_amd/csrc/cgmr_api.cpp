@@ -2,6 +2,7 @@
 // Compiled with hipcc; contains no kernels (those live in gn_kernels.hip / matcher_kernels.hip).
 #include "cgmr_ctx.h"
 #include "dl_device.h"
+#include "factor_model.h"
 #include "gnc_device.h"
 #include "gn_host.h"
 #include "init_device.h"
@@ -544,7 +545,7 @@ void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, con
   }
   D.pan_clean = false;
   T.run(1, 1, [&] { launch_assemble(st, D); });                // + the chi2 sum of this iteration (slot = iterations done)
-  if (Ed.typed && Ed.n_unary > 0) T.run(1, 1, [&] { launch_add_unary(st, D, Ed); });   // the priors: self edges, no assembly key
+  if (Ed.typed && Ed.unary.n > 0) T.run(1, 1, [&] { launch_add_unary(st, D, Ed); });   // the priors: self edges, no assembly key
   if (o.after_assemble) o.after_assemble(st, D, o.after_assemble_arg);
   static const bool trace = getenv("CGMR_TRACE_LAUNCHES") != nullptr;
   if (trace)
@@ -664,8 +665,8 @@ int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
   hipStream_t st = ctx->stream;
   // (robust statistics: written by the final chi-only pass, at the estimate the call returns)
   GnEdges Ei = Ed;
-  Ei.rk_stats = nullptr;
-  Ei.mix_sel = nullptr;                 // (a mixture's selection: written by the same pass)
+  Ei.rk.stats = nullptr;
+  Ei.mx.sel_out = nullptr;                 // (a mixture's selection: written by the same pass)
   // iterations it0 .. iters - 1, then the chi-only pass at the estimate they leave
   auto queue_from = [&](int it0) {
     GnPassOpts o;
@@ -874,8 +875,8 @@ static int tr_run(cgmr_ctx* ctx, P& pol, int nV, double* d_poses, const uint8_t*
   } else {
     LevelwiseScope levelwise(ctx, D);
     GnEdges Ei = Ed;                                         // (robust statistics: one chi-only pass on the final poses below)
-    Ei.rk_stats = nullptr;
-    Ei.mix_sel = nullptr;                                    // (a mixture's selection: the same pass)
+    Ei.rk.stats = nullptr;
+    Ei.mx.sel_out = nullptr;                                    // (a mixture's selection: the same pass)
     for (;;) {
       pol.queue_round(ctx, D, st, nV, d_poses, Ei, hs, iters);
       HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
@@ -896,7 +897,7 @@ static int tr_run(cgmr_ctx* ctx, P& pol, int nV, double* d_poses, const uint8_t*
       }
       if (hs.done) break;
     }
-    if (Ed.rk_stats || Ed.mix_sel) launch_linearize(st, D, d_poses, Ed, 1);   // (read back by the caller, behind the stream)
+    if (Ed.rk.stats || Ed.mx.sel_out) launch_linearize(st, D, d_poses, Ed, 1);   // (read back by the caller, behind the stream)
   }
   call.finish();
   return pol.finish(ctx, hs, h.data(), std::min(hs.iter, iters), iters, waits);
@@ -1201,24 +1202,21 @@ static int robust_setup(cgmr_ctx* ctx, const cgmr_robust* rk, int nE, bool dev, 
   }
   char* d = ctx->rk_arena.ptr;
   Ed.robust = true;
-  Ed.rk_kind0 = rk->default_kind;
-  Ed.rk_delta0 = rk->default_delta;
-  if (dev) {
-    Ed.rk_kind = rk->kind;
-    Ed.rk_delta = rk->delta;
-  } else {
-    if (rk->kind && n > 0) { HIP_TRY(ctx, hipMemcpyAsync(d + ok_, rk->kind, n, hipMemcpyHostToDevice, ctx->stream)); Ed.rk_kind = (const uint8_t*)(d + ok_); }
-    if (rk->delta && n > 0) { HIP_TRY(ctx, hipMemcpyAsync(d + od, rk->delta, 8 * n, hipMemcpyHostToDevice, ctx->stream)); Ed.rk_delta = (const double*)(d + od); }
+  Ed.rk.kind0 = rk->default_kind; Ed.rk.delta0 = rk->default_delta;
+  if (dev) { Ed.rk.kind = rk->kind; Ed.rk.delta = rk->delta; }
+  else {
+    if (rk->kind && n > 0) { HIP_TRY(ctx, hipMemcpyAsync(d + ok_, rk->kind, n, hipMemcpyHostToDevice, ctx->stream)); Ed.rk.kind = (const uint8_t*)(d + ok_); }
+    if (rk->delta && n > 0) { HIP_TRY(ctx, hipMemcpyAsync(d + od, rk->delta, 8 * n, hipMemcpyHostToDevice, ctx->stream)); Ed.rk.delta = (const double*)(d + od); }
   }
-  Ed.rk_stats = stats ? (double*)(d + os) : nullptr;
+  Ed.rk.stats = stats ? (double*)(d + os) : nullptr;
   return 0;
 }
 
 // the statistics of the call's final pass to the caller's host arrays
 static int robust_stats_out(cgmr_ctx* ctx, const cgmr_robust* rk, int nE, const GnEdges& Ed) {
-  if (!rk || !Ed.rk_stats) return 0;
-  if (rk->edge_chi2_out) HIP_TRY(ctx, hipMemcpyAsync(rk->edge_chi2_out, Ed.rk_stats, 8 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
-  if (rk->weight_out) HIP_TRY(ctx, hipMemcpyAsync(rk->weight_out, Ed.rk_stats + nE, 8 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
+  if (!rk || !Ed.rk.stats) return 0;
+  if (rk->edge_chi2_out) HIP_TRY(ctx, hipMemcpyAsync(rk->edge_chi2_out, Ed.rk.stats, 8 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
+  if (rk->weight_out) HIP_TRY(ctx, hipMemcpyAsync(rk->weight_out, Ed.rk.stats + nE, 8 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
@@ -1246,14 +1244,14 @@ static int typed_check(cgmr_ctx* ctx, const char* who, const cgmr_factor_types* 
   for (int k = 0; k < nE; k++) {
     const int kind = T.ek[k], a = ef[k], b = et[k];
     if (a < 0 || a >= nV || b < 0 || b >= nV) return set_err(ctx, CGMR_E_INVALID, "%s: edge %d has a vertex index out of range", who, k);
-    if (kind > 4) return set_err(ctx, CGMR_E_INVALID, "%s: edge %d has unknown kind %d", who, k, kind);
-    if (kind == 1 || kind == 2) {
+    if (kind > CGMR_EDGE_PRIOR_SE2_XY) return set_err(ctx, CGMR_E_INVALID, "%s: edge %d has unknown kind %d", who, k, kind);
+    if (kind == CGMR_EDGE_SE2_XY || kind == CGMR_EDGE_BEARING_SE2_XY) {
       if (T.vk[a] != 0 || T.vk[b] != 1)
-        return set_err(ctx, CGMR_E_INVALID, "%s: edge %d (%s) must go from a pose to a point", who, k, kind == 1 ? "EDGE_SE2_XY" : "EDGE_BEARING_SE2_XY");
+        return set_err(ctx, CGMR_E_INVALID, "%s: edge %d (%s) must go from a pose to a point", who, k, kind == CGMR_EDGE_SE2_XY ? "EDGE_SE2_XY" : "EDGE_BEARING_SE2_XY");
     } else {
       if (T.vk[a] != 0 || T.vk[b] != 0)
         return set_err(ctx, CGMR_E_INVALID, "%s: edge %d (kind %d) touches a point; only EDGE_SE2_XY and EDGE_BEARING_SE2_XY may", who, k, kind);
-      if (kind >= 3) {
+      if (factor_is_prior(kind)) {
         if (a != b) return set_err(ctx, CGMR_E_INVALID, "%s: edge %d is a prior (kind %d) and must have from == to", who, k, kind);
         cnt[a + 1]++;
         n_prior++;
@@ -1270,7 +1268,7 @@ static int typed_check(cgmr_ctx* ctx, const char* who, const cgmr_factor_types* 
   for (size_t u = 0; u < T.uv_vertex.size(); u++) T.uv_ptr[u + 1] = T.uv_ptr[u] + cnt[T.uv_vertex[u] + 1];
   T.uv_edge.assign((size_t)n_prior, 0);
   std::vector<int32_t> cur(T.uv_ptr.begin(), T.uv_ptr.end());
-  for (int k = 0; k < nE; k++) if (T.ek[k] >= 3) T.uv_edge[cur[slot[ef[k]]]++] = k;
+  for (int k = 0; k < nE; k++) if (factor_is_prior(T.ek[k])) T.uv_edge[cur[slot[ef[k]]]++] = k;
   return 0;
 }
 // ... staged through ty_arena into Ed (nothing when every kind is zero)
@@ -1292,9 +1290,8 @@ static int typed_upload(cgmr_ctx* ctx, const TypedHost* T, GnEdges& Ed) {
     HIP_TRY(ctx, hipMemcpyAsync(d + o_ue, T->uv_edge.data(), 4 * T->uv_edge.size(), hipMemcpyHostToDevice, st));
   }
   Ed.typed = true;
-  Ed.edge_kind = (const uint8_t*)(d + o_ek);
-  Ed.n_unary = (int)nU;
-  Ed.uv_vertex = (const int32_t*)(d + o_uv); Ed.uv_ptr = (const int32_t*)(d + o_up); Ed.uv_edge = (const int32_t*)(d + o_ue);
+  Ed.ty.edge_kind = (const uint8_t*)(d + o_ek);
+  Ed.unary = {(int)nU, (const int32_t*)(d + o_uv), (const int32_t*)(d + o_up), (const int32_t*)(d + o_ue)};
   return 0;
 }
 // a point's dummy unknown out of a 3x3 block of H^-1: third row (the block's row vertex is a point) / third column (its column vertex is)
@@ -1579,10 +1576,10 @@ int joint_driver(cgmr_ctx* ctx, const char* who, int mode, int nV, const double*
     for (int k = 0; k < nQ; k++) {
       const int kind = obs_kind ? obs_kind[k] : 0;
       const bool a_pt = ft && !typed.vk.empty() && typed.vk[va[k]], b_pt = ft && !typed.vk.empty() && typed.vk[vb[k]];
-      if (kind > 2) return set_err(ctx, CGMR_E_INVALID, "%s: pair %d has observation kind %d (0, 1 or 2)", who, k, kind);
+      if (kind > CGMR_EDGE_BEARING_SE2_XY) return set_err(ctx, CGMR_E_INVALID, "%s: pair %d has observation kind %d (0, 1 or 2)", who, k, kind);
       if (a_pt) return set_err(ctx, CGMR_E_INVALID, "%s: pair %d is observed from vertex %d, a point", who, k, va[k]);
-      if (kind == 0 && b_pt) return set_err(ctx, CGMR_E_INVALID, "%s: pair %d of kind 0 (EDGE_SE2) ends at vertex %d, a point", who, k, vb[k]);
-      if (kind != 0 && !b_pt) return set_err(ctx, CGMR_E_INVALID, "%s: pair %d of kind %d ends at vertex %d, a pose", who, k, kind, vb[k]);
+      if (kind == CGMR_EDGE_SE2 && b_pt) return set_err(ctx, CGMR_E_INVALID, "%s: pair %d of kind 0 (EDGE_SE2) ends at vertex %d, a point", who, k, vb[k]);
+      if (kind != CGMR_EDGE_SE2 && !b_pt) return set_err(ctx, CGMR_E_INVALID, "%s: pair %d of kind %d ends at vertex %d, a pose", who, k, kind, vb[k]);
       if (kind) obs_typed = true; else obs_pose = true;
     }
   if (nQ == 0) return CGMR_OK;
@@ -1756,13 +1753,13 @@ static int mix_check(cgmr_ctx* ctx, const char* who, const cgmr_mixture* mix, in
   for (int k = 0; k < nE; k++) {
     const int p0 = cp[k], p1 = cp[k + 1];
     if (p1 - p0 < 2) continue;
-    const int kind = typed.any ? typed.ek[k] : 0;
+    const int dim = factor_dim(typed.any ? typed.ek[k] : CGMR_EDGE_SE2);
     double amax = 0;
     for (int p = p0; p < p1; p++) {
       const double w = mix->comp_weight[p];
       const double* u = mix->comp_info + 6 * (size_t)p;
-      const double det = kind == 2 ? u[0]
-                         : (kind == 1 || kind == 4)
+      const double det = dim == 1 ? u[0]
+                         : dim == 2
                              ? u[0] * u[3] - u[1] * u[1]
                              : u[0] * (u[3] * u[5] - u[4] * u[4]) - u[1] * (u[1] * u[5] - u[4] * u[2]) + u[2] * (u[1] * u[4] - u[3] * u[2]);
       if (!(std::isfinite(w) && w > 0))
@@ -1792,9 +1789,9 @@ static int mix_upload(cgmr_ctx* ctx, const MixHost* M, int nE, GnEdges& Ed) {
   HIP_TRY(ctx, hipMemcpyAsync(d + o_info, M->mix->comp_info, 48 * nC, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d + o_off, M->off.data(), 8 * nC, hipMemcpyHostToDevice, st));
   Ed.mix = true;
-  Ed.mix_ptr = (const int32_t*)(d + o_ptr);
-  Ed.mix_meas = (const double*)(d + o_meas); Ed.mix_info = (const double*)(d + o_info); Ed.mix_off = (const double*)(d + o_off);
-  Ed.mix_sel = M->mix->selected_out ? (int32_t*)(d + o_sel) : nullptr;
+  Ed.mx.cptr = (const int32_t*)(d + o_ptr);
+  Ed.mx.cmeas = (const double*)(d + o_meas); Ed.mx.cinfo = (const double*)(d + o_info); Ed.mx.coff = (const double*)(d + o_off);
+  Ed.mx.sel_out = M->mix->selected_out ? (int32_t*)(d + o_sel) : nullptr;
   return 0;
 }
 // every edge's first component: what a call routed to the typed / plain path, or one that fails, leaves in selected_out
@@ -1803,8 +1800,8 @@ static void mix_selection_zero(const cgmr_mixture* mix, int nE) {
 }
 // the selection of the call's final pass to the caller's host array
 static int mix_selection_out(cgmr_ctx* ctx, const MixHost* M, int nE, const GnEdges& Ed) {
-  if (!M || !Ed.mix_sel || nE <= 0) return 0;
-  HIP_TRY(ctx, hipMemcpyAsync(M->mix->selected_out, Ed.mix_sel, 4 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
+  if (!M || !Ed.mx.sel_out || nE <= 0) return 0;
+  HIP_TRY(ctx, hipMemcpyAsync(M->mix->selected_out, Ed.mx.sel_out, 4 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
@@ -1845,7 +1842,7 @@ static int optimize_staged(cgmr_ctx* ctx, const char* who, bool dev, bool choles
     char* d = ctx->io_arena.ptr;
     HIP_TRY(ctx, hipMemcpyAsync(d, poses, bp, hipMemcpyHostToDevice, ctx->stream));
     if (Ed.mix) {                        // (a mixture pass reads the component lists alone: the first components stay on the host)
-      Ed.meas_a = Ed.mix_meas; Ed.info_a = Ed.mix_info;
+      Ed.meas_a = Ed.mx.cmeas; Ed.info_a = Ed.mx.cinfo;
     } else {
       HIP_TRY(ctx, hipMemcpyAsync(d + om, meas, bm, hipMemcpyHostToDevice, ctx->stream));
       HIP_TRY(ctx, hipMemcpyAsync(d + oi, info, bi, hipMemcpyHostToDevice, ctx->stream));
@@ -1869,40 +1866,50 @@ static int optimize_staged(cgmr_ctx* ctx, const char* who, bool dev, bool choles
   return rc;
 }
 
+// What gn / lm / dl_optimize_impl do before they run, for `family` = "cgmr_gn_optimize", ...: the arguments, the factor types
+// (F.typed), the mixture (F.mix; selected_out zeroed), and F.who, the name optimize_staged's own errors carry -- family +
+// "_typed" for a typed call, else + plain / plain_dev.  The names are the ones these texts have always had.
+struct OptimizeFront { TypedHost typed; MixHost mix; char who[64]; };
+static int optimize_front(cgmr_ctx* ctx, const char* family, const char* plain, const char* plain_dev, int nV, const double* poses,
+                          const uint8_t* fixed, int nE, const int32_t* from_idx, const int32_t* to_idx, const double* meas,
+                          const double* info, int iters, bool dev, const cgmr_factor_types* ft, const cgmr_mixture* mix,
+                          OptimizeFront& F) {
+  int rc = optimize_args_check(ctx, family, nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
+  if (rc) return rc;
+  char name[64];
+  snprintf(name, sizeof name, "%s%s", family, mix ? "_mixture" : dev ? "_typed_dev" : "_typed");
+  rc = typed_check(ctx, name, ft, nV, nE, from_idx, to_idx, F.typed);
+  if (rc) return rc;
+  snprintf(name, sizeof name, "%s_mixture", family);
+  rc = mix_check(ctx, name, mix, nE, F.typed, F.mix);
+  if (rc) return rc;
+  mix_selection_zero(mix, nE);
+  snprintf(F.who, sizeof F.who, "%s%s", family, ft ? "_typed" : dev ? plain_dev : plain);
+  return 0;
+}
+
 static int gn_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                             const int32_t* to_idx, const double* meas, const double* info, int iters, double* chi2_out,
                             const cgmr_robust* rk, bool dev, const cgmr_factor_types* ft = nullptr,
                             const cgmr_mixture* mix = nullptr) {
-  int rc = optimize_args_check(ctx, "cgmr_gn_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
+  OptimizeFront F;
+  int rc = optimize_front(ctx, "cgmr_gn_optimize", "_robust", "_robust_dev", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, dev, ft, mix, F);
   if (rc) return rc;
-  TypedHost typed;
-  rc = typed_check(ctx, mix ? "cgmr_gn_optimize_mixture" : dev ? "cgmr_gn_optimize_typed_dev" : "cgmr_gn_optimize_typed", ft, nV, nE, from_idx, to_idx, typed);
-  if (rc) return rc;
-  MixHost mh;
-  rc = mix_check(ctx, "cgmr_gn_optimize_mixture", mix, nE, typed, mh);
-  if (rc) return rc;
-  mix_selection_zero(mix, nE);
-  return optimize_staged(ctx, ft ? "cgmr_gn_optimize_typed" : dev ? "cgmr_gn_optimize_robust_dev" : "cgmr_gn_optimize_robust", dev, true, nV, poses, nE, meas, info, rk, &typed,
-                         [&](double* d_poses, const GnEdges& Ed) { return gn_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, chi2_out); }, &mh);
+  return optimize_staged(ctx, F.who, dev, true, nV, poses, nE, meas, info, rk, &F.typed,
+                         [&](double* d_poses, const GnEdges& Ed) { return gn_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, chi2_out); }, &F.mix);
 }
 
 static int lm_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                             const int32_t* to_idx, const double* meas, const double* info, int iters, const cgmr_lm_params* params,
                             double* chi2_out, double* lambda_out, int32_t* trials_out, int32_t* iters_done, const cgmr_robust* rk,
                             bool dev, const cgmr_factor_types* ft = nullptr, const cgmr_mixture* mix = nullptr) {
-  int rc = optimize_args_check(ctx, "cgmr_lm_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
+  OptimizeFront F;
+  int rc = optimize_front(ctx, "cgmr_lm_optimize", "_robust", "_robust_dev", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, dev, ft, mix, F);
   if (rc) return rc;
-  TypedHost typed;
-  rc = typed_check(ctx, mix ? "cgmr_lm_optimize_mixture" : dev ? "cgmr_lm_optimize_typed_dev" : "cgmr_lm_optimize_typed", ft, nV, nE, from_idx, to_idx, typed);
-  if (rc) return rc;
-  MixHost mh;
-  rc = mix_check(ctx, "cgmr_lm_optimize_mixture", mix, nE, typed, mh);
-  if (rc) return rc;
-  mix_selection_zero(mix, nE);
-  return optimize_staged(ctx, ft ? "cgmr_lm_optimize_typed" : dev ? "cgmr_lm_optimize_robust_dev" : "cgmr_lm_optimize_robust", dev, false, nV, poses, nE, meas, info, rk, &typed,
+  return optimize_staged(ctx, F.who, dev, false, nV, poses, nE, meas, info, rk, &F.typed,
                          [&](double* d_poses, const GnEdges& Ed) {
                            return lm_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, lambda_out, trials_out, iters_done);
-                         }, &mh);
+                         }, &F.mix);
 }
 
 static int dl_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
@@ -1910,22 +1917,16 @@ static int dl_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t*
                             double* chi2_out, double* delta_out, int32_t* trials_out, int32_t* step_out, int32_t* iters_done,
                             const cgmr_robust* rk, bool dev, const cgmr_factor_types* ft = nullptr,
                             const cgmr_mixture* mix = nullptr) {
-  int rc = optimize_args_check(ctx, "cgmr_dl_optimize", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters);
+  OptimizeFront F;
+  int rc = optimize_front(ctx, "cgmr_dl_optimize", "", "_dev", nV, poses, fixed, nE, from_idx, to_idx, meas, info, iters, dev, ft, mix, F);
   if (rc) return rc;
-  TypedHost typed;
-  rc = typed_check(ctx, mix ? "cgmr_dl_optimize_mixture" : dev ? "cgmr_dl_optimize_typed_dev" : "cgmr_dl_optimize_typed", ft, nV, nE, from_idx, to_idx, typed);
-  if (rc) return rc;
-  MixHost mh;
-  rc = mix_check(ctx, "cgmr_dl_optimize_mixture", mix, nE, typed, mh);
-  if (rc) return rc;
-  mix_selection_zero(mix, nE);
   if (!dl_params_ok(params))
     return set_err(ctx, CGMR_E_INVALID,
                    "cgmr_dl_optimize: max_trials must be >= 1, initial_delta / initial_lambda > 0, lambda_factor > 1, all finite");
-  return optimize_staged(ctx, ft ? "cgmr_dl_optimize_typed" : dev ? "cgmr_dl_optimize_dev" : "cgmr_dl_optimize", dev, true, nV, poses, nE, meas, info, rk, &typed,
+  return optimize_staged(ctx, F.who, dev, true, nV, poses, nE, meas, info, rk, &F.typed,
                          [&](double* d_poses, const GnEdges& Ed) {
                            return dl_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, iters, params, chi2_out, delta_out, trials_out, step_out, iters_done);
-                         }, &mh);
+                         }, &F.mix);
 }
 
 
@@ -1975,8 +1976,7 @@ struct GncPolicy {
   }
   GnEdges edges(const GnEdges& Ed, int mode, double* r_out) const {
     GnEdges E = Ed;
-    E.gnc = true; E.gnc_mode = mode; E.gnc_weight = L.weight; E.gnc_c = L.barc_sq; E.gnc_known = L.known; E.gnc_state = L.S;
-    E.gnc_r = r_out;
+    E.gnc = true; E.ga = {L.weight, L.barc_sq, L.known, L.S, r_out, mode};
     return E;
   }
   static void outer_records(hipStream_t st, const GnDevice& D, void* self) { launch_gnc_outer(st, D, ((GncPolicy*)self)->L); }
@@ -2070,9 +2070,6 @@ int gnc_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE
   return r;
 }
 
-// dimension of an edge kind's factor (include/cgmr.h: CGMR_EDGE_*)
-static int factor_dim(int kind) { return kind == 2 ? 1 : (kind == 1 || kind == 4) ? 2 : 3; }
-
 static int gnc_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* from_idx,
                              const int32_t* to_idx, const double* meas, const double* info, const cgmr_factor_types* ft,
                              const cgmr_gnc_params* params, double* mu_out, double* cost_out, int32_t* partial_out,
@@ -2081,25 +2078,22 @@ static int gnc_optimize_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t
   int rc = optimize_args_check(ctx, who, nV, poses, fixed, nE, from_idx, to_idx, meas, info, 0);
   if (rc) return rc;
   const cgmr_gnc_params P = params ? *params : gnc_defaults();
-  if ((P.loss != CGMR_GNC_TLS && P.loss != CGMR_GNC_GM) || !std::isfinite(P.mu_factor) || !(P.mu_factor > 1) || P.max_outer < 1 ||
-      P.inner_iters < 1 || P.outer_per_wait < 1 || !std::isfinite(P.default_barc_sq))
+  if (!gnc_params_ok(&P))
     return set_err(ctx, CGMR_E_INVALID, "%s: loss must be CGMR_GNC_TLS or CGMR_GNC_GM, mu_factor finite and > 1, max_outer / inner_iters / outer_per_wait >= 1, default_barc_sq finite", who);
   TypedHost typed;
   rc = typed_check(ctx, who, ft, nV, nE, from_idx, to_idx, typed);
   if (rc) return rc;
-  const double quantile[4] = {0.0, 6.634896601021213, 9.21034037197618, 11.344866730144373};   // chi2 0.99, by dimension
   std::vector<double> hc((size_t)nE);
   std::vector<uint8_t> hk((size_t)nE, 0);
   for (int k = 0; k < nE; k++) {
-    hc[k] = P.barc_sq ? P.barc_sq[k] : P.default_barc_sq > 0 ? P.default_barc_sq : quantile[factor_dim(typed.any ? typed.ek[k] : 0)];
+    hc[k] = P.barc_sq ? P.barc_sq[k] : P.default_barc_sq > 0 ? P.default_barc_sq : gnc_default_barc_sq(factor_dim(typed.any ? typed.ek[k] : CGMR_EDGE_SE2));
     if (!std::isfinite(hc[k]) || !(hc[k] > 0)) return set_err(ctx, CGMR_E_INVALID, "%s: barc_sq of edge %d must be finite and > 0", who, k);
     if (P.known_inlier) hk[k] = P.known_inlier[k] ? 1 : 0;
   }
-  rc = optimize_staged(ctx, who, dev, true, nV, poses, nE, meas, info, nullptr, &typed, [&](double* d_poses, const GnEdges& Ed) {
+  return optimize_staged(ctx, who, dev, true, nV, poses, nE, meas, info, nullptr, &typed, [&](double* d_poses, const GnEdges& Ed) {
     return gnc_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, P, hc.data(), hk.data(), mu_out, cost_out, partial_out, outer_done,
                    P.weight_out, P.edge_chi2_out);
   });
-  return rc;
 }
 
 // cgmr_chordal_initialize*: the arguments checked, then which vertices each stage's terms touch -- a term whose information
@@ -2129,10 +2123,10 @@ static int chordal_impl(cgmr_ctx* ctx, int nV, double* poses, const uint8_t* fix
   }
   std::vector<uint8_t> in_rot((size_t)nV, 0), in_tr((size_t)nV, 0);
   for (int k = 0; k < nE; k++) {
-    const int kind = typed.any ? typed.ek[k] : 0;
+    const int dim = factor_dim(typed.any ? typed.ek[k] : CGMR_EDGE_SE2);      // 3: a heading term; 2 and 3: a position term
     const double* u = hi + 6 * (size_t)k;
-    if ((kind == 0 || kind == 3) && u[5] != 0.0) in_rot[from_idx[k]] = in_rot[to_idx[k]] = 1;
-    if (kind != 2 && (u[0] != 0.0 || u[1] != 0.0 || u[3] != 0.0)) in_tr[from_idx[k]] = in_tr[to_idx[k]] = 1;
+    if (dim == 3 && u[5] != 0.0) in_rot[from_idx[k]] = in_rot[to_idx[k]] = 1;
+    if (dim >= 2 && (u[0] != 0.0 || u[1] != 0.0 || u[3] != 0.0)) in_tr[from_idx[k]] = in_tr[to_idx[k]] = 1;
   }
   return optimize_staged(ctx, who, dev, true, nV, poses, nE, meas, info, nullptr, &typed, [&](double* d_poses, const GnEdges& Ed) {
     return chordal_run(ctx, nV, d_poses, fixed, nE, from_idx, to_idx, Ed, stages, in_rot.data(), in_tr.data(), chi2_out, counts_out);

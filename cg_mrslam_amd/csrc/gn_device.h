@@ -53,54 +53,59 @@ struct GnDevice {
   std::vector<int32_t> h_level_chrows;   // per level: rows of the factor kernel's F21 staging area (max chunk rows + rhs row)
 };
 
+// The trailing arguments of k_linearize's instances (gn_kernels.hip; the comments there say what each does to the pass).  Plain
+// structs, passed by value: their names, namespace and field order are the kernels' ABI.  All pointers are device memory.
+struct RobustArgs {
+  const uint8_t* kind = nullptr;   // [nA] or null: edges [0, nA) take kind[k]; every other edge takes kind0
+  const double* delta = nullptr;   // [nA] or null: edges [0, nA) take delta[k]; every other edge takes delta0
+  double* stats = nullptr;         // [2 nE] or null: e2 of every edge, then rho1 of every edge (a batch writes none)
+  double delta0 = 1.0;
+  int kind0 = 0;
+};
+struct TypedArgs {
+  const uint8_t* edge_kind = nullptr;   // [nA]; edges [nA, nE) are CGMR_EDGE_SE2
+};
+struct GncArgs {
+  double* weight = nullptr;          // [nE] (a batch: [nA])
+  const double* barc_sq = nullptr;   // [nE]
+  const uint8_t* known = nullptr;    // [nE]: 1 = known inlier, weight 1
+  const GncState* S = nullptr;
+  double* r_out = nullptr;           // [nE] or null: r of every edge
+  int mode = 0;                      // gnc_device.h: kGncCompute / kGncReuse / kGncPlain
+};
+struct MixArgs {
+  const int32_t* cptr = nullptr;     // [nE + 1]
+  const double* cmeas = nullptr;     // [3 nC]
+  const double* cinfo = nullptr;     // [6 nC]
+  const double* coff = nullptr;      // [nC]: max_j a_j - a_p >= 0, a = 2 ln w + ln det O (own dimension); 0 for an edge of one component
+  int32_t* sel_out = nullptr;        // [nE] or null
+};
+// The priors of a typed pass, grouped by vertex for k_add_unary: vertex[u] owns the edges edge[ptr[u] .. ptr[u + 1]), ascending.
+struct UnaryLists {
+  int n = 0;
+  const int32_t *vertex = nullptr, *ptr = nullptr, *edge = nullptr;
+};
+
 // Numeric edge data of one pass: edges [0, nA) from (meas_a, info_a), [nA, nE) from (meas_b, info_b); edges
-// [n_active, nE) are switched off.
-// robust: every edge's information is scaled by rho1 of its robust kernel (gn_kernels.hip: robustify; include/cgmr.h:
-// cgmr_robust): edge k < nA takes kind rk_kind[k] (or rk_kind0 with rk_kind null) and delta rk_delta[k] (or rk_delta0), device
-// memory; edges [nA, nE) take rk_kind0 / rk_delta0.  rk_stats (device, nullable) receives e2 of every edge, then rho1 of
-// every edge.  Not robust: the plain launch, exactly as before.
+// [n_active, nE) are switched off.  Each variant of the linearisation is its argument struct and a flag that says it is
+// there; launch_linearize picks the instance from the flags (the table in gn_kernels.hip) and passes the structs as they are.
+// Which go together is k_linearize's static_assert: GNC never with robust; a mixture never with robust or GNC, nA == nE, its
+// meas_a / info_a not read; typed, a mixture and a chordal stage run one job.  A batch (GnDevice::njobs > 1, the robot graph's
+// condensed graphs) is plain, robust without statistics, or gnc_own_only: stored weights ga.weight [nA] shared by every job
+// (that instance whatever the job count), edges [nA, nE) weight 1, nothing else of ga read.
 struct GnEdges {
   const double *meas_a = nullptr, *info_a = nullptr, *meas_b = nullptr, *info_b = nullptr;
   int nA = 0, n_active = 0;
-  bool robust = false;
-  const uint8_t* rk_kind = nullptr;
-  const double* rk_delta = nullptr;
-  int rk_kind0 = 0;
-  double rk_delta0 = 1.0;
-  double* rk_stats = nullptr;
-  // typed (include/cgmr.h: cgmr_factor_types; gn_kernels.hip: TypedArgs): edge k < nA is of kind edge_kind[k] (device memory).
-  // The priors among them, grouped by vertex for k_add_unary: vertex uv_vertex[u] owns the edges uv_edge[uv_ptr[u] ..
-  // uv_ptr[u + 1]), ascending (device memory).  One job only.  Not typed: the launches as before.
-  bool typed = false;
-  const uint8_t* edge_kind = nullptr;
-  int n_unary = 0;
-  const int32_t *uv_vertex = nullptr, *uv_ptr = nullptr, *uv_edge = nullptr;
-  // graduated non-convexity (include/cgmr.h: cgmr_gnc_params; gn_kernels.hip: GncArgs): every edge's terms are scaled by its
-  // GNC weight -- computed from gnc_state->mu and stored in gnc_weight (gnc_mode kGncCompute), read from there (kGncReuse), or
-  // 1 (kGncPlain); gnc_c [nE] barc^2, gnc_known [nE] the known-inlier mask, gnc_r (nullable) receives e^T Omega e of every edge
-  // (device memory).  One job, never with `robust`.
-  // gnc_own_only: the robot graph's condensed batches under stored weights -- kGncReuse, gnc_weight [nA] shared by every job
-  // of the view (the batched instance, whatever the job count), edges [nA, nE) weight 1; nothing else of the description is read.
-  bool gnc = false;
-  bool gnc_own_only = false;
-  int gnc_mode = 0;
-  double* gnc_weight = nullptr;
-  const double* gnc_c = nullptr;
-  const uint8_t* gnc_known = nullptr;
-  const GncState* gnc_state = nullptr;
-  double* gnc_r = nullptr;
+  bool robust = false, typed = false, gnc = false, gnc_own_only = false, mix = false;
+  RobustArgs rk;
+  TypedArgs ty;
+  UnaryLists unary;
+  GncArgs ga;
+  MixArgs mx;
   // chordal initialisation (include/cgmr.h: cgmr_chordal_initialize; init_kernels.hip): 0 the Gauss-Newton linearisation, else
   // the linear stage whose records the pass solves -- init_device.h: kChordalRotation / kChordalTranslation.  One job, never
-  // with `robust` or `gnc`; a rotation pass ends with k_apply_rotation in the place of k_update_poses.
+  // with `robust`, `gnc` or `mix`; a rotation pass ends with k_apply_rotation in the place of k_update_poses.
   int chordal_stage = 0;
-  // max-mixture edges (include/cgmr.h: cgmr_mixture; gn_kernels.hip: MixArgs): edge k owns the components [mix_ptr[k],
-  // mix_ptr[k + 1]) of (mix_meas, mix_info), each with its offset mix_off; the linearisation keeps the cheapest one and
-  // writes its index within the edge to mix_sel (nullable) -- device memory.  meas_a / info_a are not read.  One job, nA ==
-  // nE, never with `robust`, `gnc` or a chordal stage.
-  bool mix = false;
-  const int32_t* mix_ptr = nullptr;
-  const double *mix_meas = nullptr, *mix_info = nullptr, *mix_off = nullptr;
-  int32_t* mix_sel = nullptr;
 };
 // gn_structure.hip: the assembly lists (asm_ptr: nf + nb + 1, asm_src: one entry per (edge, key)) from the permutation, the
 // edge list and the off-diagonal blocks (offbase: nf + 1 column starts into off_row); work space: ekey nE, cnt nf + nb + 3,

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "gn_symbolic.h"
+#include "factor_model.h"
 #include "gn_device.h"
 #include "gnc_device.h"
 #include "init_device.h"
@@ -61,13 +62,6 @@ static_assert(kFrontW != 48 || 2 * factor_smem_bytes(kLeafChunkRows + 1) <= 160 
 static_assert(kFrontW != 48 || 2 * factor_smem_bytes(kMidChunkRows + 1) <= 160 * 1024, "above the leaves: two workgroups per CU");
 static_assert(kFrontW + kChunkRows + 1 <= 208, "panel_cholesky: at most 4 x 48 rows below a diagonal block");
 
-__device__ __forceinline__ double d_normalize_theta(double t) {
-  const double pi = 3.14159265358979323846;
-  if (t >= -pi && t < pi) return t;
-  double m = floor((t + pi) / (2 * pi));
-  return t - 2 * pi * m;
-}
-
 }  // namespace
 
 // Passes batched over a job dimension (blockIdx.z): the condensed graphs a robot builds for its peers are the same
@@ -103,13 +97,6 @@ __device__ __forceinline__ double d_normalize_theta(double t) {
 // BATCH and ROBUST together (the robot graph's robust condensed graphs, cgmr_graph_set_condensed_robust): every job takes its
 // rho1 from its own poses (moved by the pose stride); kind / delta are the jobs' shared edge list's and are not moved; the
 // statistics are never written (the host rejects a batch with stats).
-struct RobustArgs {
-  const uint8_t* kind;   // [nA] or null: edges [0, nA) take kind[k]; every other edge takes kind0
-  const double* delta;   // [nA] or null: edges [0, nA) take delta[k]; every other edge takes delta0
-  double* stats;         // [2 nE] or null: e2 of every edge, then rho1 of every edge
-  double delta0;
-  int kind0;
-};
 
 // rho0 (returned) and rho1 of g2o's robust kernels (robust_kernel_impl.cpp [g2o-recalled]; the table in include/cgmr.h),
 // in double; kind 0 (or a code the host has not let through): the plain e2, weight 1
@@ -157,30 +144,21 @@ __device__ __forceinline__ double robustify(int kind, double delta, double e2, d
   }
 }
 
-// TYPED (g2o's slam2d factor types, include/cgmr.h: cgmr_factor_types): edge k < nA is of kind edge_kind[k] --
-//   0  EDGE_SE2           as above
-//   1  EDGE_SE2_XY        pose i sees point l:  e = R(th_i)^T (l - t_i) - z (2)
-//   2  EDGE_BEARING_SE2_XY  pose i sees point l: e = normalize(atan2(ry, rx) - z0) (1), (rx, ry) = R(th_i)^T (l - t_i)
-//   3  EDGE_PRIOR_SE2     unary (i == j):       e = (R(z_th)^T (t_i - z_t), normalize(th_i - z_th))
-//   4  EDGE_PRIOR_SE2_XY  unary (i == j):       e = t_i - z (2)
+// TYPED (g2o's slam2d factor types, include/cgmr.h: cgmr_factor_types): edge k < nA is of kind edge_kind[k]; the kinds, their
+// errors and their dimensions are factor_model.h's.
 // A 2-dimensional factor takes z0, z1 and the entries (0,0) (0,1) (1,1) of its information; its third error component and the
 // third row / column of O are zero, so e^T O e -- and with it the robust weight -- is that of the factor's own dimension.  The
-// record keeps its layout.  A point owns a 3x3 block column like a pose: a kind-1 edge leaves the third row / column of Hjj
+// record keeps its layout.  A point owns a 3x3 block column like a pose: an EDGE_SE2_XY leaves the third row / column of Hjj
 // and the third column of Hij zero except for Hjj(2,2), a copy of Hjj(0,0) (1.0 when that is not positive): the dummy unknown
 // decouples with a positive pivot and a zero right-hand side, its dx is exactly zero, and its diagonal never exceeds a real one
 // of the same block (k_lm_init's max |H_jj| is the true-dimension system's).  A bearing reads z0 and the entry (0,0) of its
-// information; its Jacobians are the row (-ry / q) J1[0] + (rx / q) J1[1] of the kind-1 Jacobians J1, q = rx^2 + ry^2 (the heading's
-// entry is -1), zero with the point on the pose.  Its Hjj(2,2) is the copy of Hjj(0,0) with no fall-back to 1.0: a bearing along
+// information; its Jacobians are the row (-ry / q) J1[0] + (rx / q) J1[1] of the EDGE_SE2_XY Jacobians J1, q = rx^2 + ry^2 (the
+// heading's entry is -1), zero with the point on the pose.  Its Hjj(2,2) is the copy of Hjj(0,0) with no fall-back to 1.0: a bearing along
 // the world's x axis has Hjj(0,0) = 0 exactly, and a 1.0 there would exceed the point's real diagonal entries and raise
 // Levenberg's tau * max |H_jj|; summed over the point's edges the dummy is the block's H_xx, positive whenever the point's 2x2
 // block is positive definite.  A prior's record holds Hii and bi; the structure
-// gives a self edge no assembly key, k_add_unary adds the record behind k_assemble.  The kinds are a third kind of trailing
-// argument: the plain and the robust instances keep their names and their code.
-struct TypedArgs {
-  const uint8_t* edge_kind;   // [nA]; edges [nA, nE) are kind 0
-};
-// GNC (graduated non-convexity, include/cgmr.h: cgmr_gnc_params; gnc_kernels.hip): a fourth kind of trailing argument, in
-// instances of its own with and without TypedArgs -- the eight others keep their names and their code.  r = e^T O e is formed
+// gives a self edge no assembly key, k_add_unary adds the record behind k_assemble.
+// GNC (graduated non-convexity, include/cgmr.h: cgmr_gnc_params; gnc_kernels.hip): r = e^T O e is formed
 // as the robust instances form e2 (the factor's own dimension); the weight w of a free edge comes from r and the device
 // state's mu (gnc_device.h: gnc_weight), a known inlier's is 1.  w r goes into the chi2 partial sum and the finished 33 terms
 // are scaled by w, the point's dummy pivot with them: the dummy stays the copy of the scaled Hjj(0,0), so summed over a
@@ -190,46 +168,27 @@ struct TypedArgs {
 // BATCH and GNC together (the robot graph's condensed graphs without the rejected edges, cgmr_graph_set_condensed_gnc): stored
 // weights only -- weight [nA], a snapshot that went up with the batch's staging block and that every job reads where it lies;
 // edges [nA, nE) are switched off in those passes and take 1.  A weight of 0 leaves exact zeros, a weight of 1 the plain terms.
-struct GncArgs {
-  double* weight;          // [nE] (a batch: [nA])
-  const double* barc_sq;   // [nE]
-  const uint8_t* known;    // [nE]: 1 = known inlier, weight 1
-  const GncState* S;
-  double* r_out;           // [nE] or null: r of every edge
-  int mode;
-};
-// MIX (max-mixture edges, include/cgmr.h: cgmr_mixture): a fifth kind of trailing argument, in two instances of its own with
-// and without TypedArgs, one job, never with RobustArgs or GncArgs -- the twelve others keep their names and their code.  Edge
+// MIX (max-mixture edges, include/cgmr.h: cgmr_mixture): one job, never with RobustArgs or GncArgs.  Edge
 // k owns the components [cptr[k], cptr[k + 1]) of (cmeas, cinfo); meas / info are not read.  The thread forms r_p = e(z_p)^T O_p
-// e(z_p) of every component of its edge in the factor's own dimension (mix_r below: the error lines of the kernel), keeps the
+// e(z_p) of every component of its edge in the factor's own dimension (mix_r below), keeps the
 // first argmin of r_p + coff[p] (ascending, strict <) and falls into the code below with that component's z and O; the chi2
 // partial sum takes r + coff of it.  An edge with one component skips the scan: K components cost K + 1 error evaluations,
 // one none.  sel_out [nE] (nullable) receives the component's index within its edge.  Every linearisation selects afresh at
 // the poses it is given, a chi-only one too.
-struct MixArgs {
-  const int32_t* cptr;     // [nE + 1]
-  const double* cmeas;     // [3 nC]
-  const double* cinfo;     // [6 nC]
-  const double* coff;      // [nC]: max_j a_j - a_p >= 0, a = 2 ln w + ln det O (own dimension); 0 for an edge of one component
-  int32_t* sel_out;        // [nE] or null
-};
-// e^T O e of factor kind fk with measurement z and information u (upper triangle), from what the linearisation has of the two
-// vertices: (rx, ry, rth) = x_i^-1 x_j, x_i itself for the priors
+// Every variant is a trailing argument of its own type (gn_device.h), absent from the instances without it: an instance's code
+// is that of its own variants alone (an argument of an empty type would still take 8 bytes of the argument segment and move
+// the implicit arguments behind it).  The live instances are the rows of CGMR_LINEARIZE_TABLE below.
+
+// e^T O e of factor kind fk with measurement z and information u (upper triangle), in the factor's own dimension.  (The three
+// forms stay written out: through the kernel's masked 3x3 O the mixture instance lost its schedule and the typed one registers.)
 __device__ __forceinline__ double mix_r(int fk, double rx, double ry, double rth, double xi0, double xi1, double xi2,
                                         const double* __restrict__ z, const double* __restrict__ u) {
   const double z0 = z[0], z1 = z[1], z2 = z[2];
-  const double cz = cos(z2), sz = sin(z2);
-  const double tx = rx - z0, ty = ry - z1;
-  double e0 = cz * tx + sz * ty, e1 = -sz * tx + cz * ty, e2 = d_normalize_theta(rth - z2);
-  if (fk == 1) { e0 = tx; e1 = ty; }
-  else if (fk == 2) {
-    const double b = d_normalize_theta((rx * rx + ry * ry > 0.0 ? atan2(ry, rx) : 0.0) - z0);
-    return b * (u[0] * b);
-  } else if (fk == 3) {
-    const double px = xi0 - z0, py = xi1 - z1;
-    e0 = cz * px + sz * py; e1 = -sz * px + cz * py; e2 = d_normalize_theta(xi2 - z2);
-  } else if (fk == 4) { e0 = xi0 - z0; e1 = xi1 - z1; }
-  if (fk == 1 || fk == 4) return e0 * (u[0] * e0 + u[1] * e1) + e1 * (u[1] * e0 + u[3] * e1);
+  double e[3];
+  factor_error(fk, rx, ry, rth, xi0, xi1, xi2, z0, z1, z2, cos(z2), sin(z2), e);
+  const double e0 = e[0], e1 = e[1], e2 = e[2];
+  if (factor_dim(fk) == 1) return e0 * (u[0] * e0);
+  if (factor_dim(fk) == 2) return e0 * (u[0] * e0 + u[1] * e1) + e1 * (u[1] * e0 + u[3] * e1);
   return e0 * (u[0] * e0 + u[1] * e1 + u[2] * e2) + e1 * (u[1] * e0 + u[3] * e1 + u[4] * e2) + e2 * (u[2] * e0 + u[4] * e1 + u[5] * e2);
 }
 template <typename T> __device__ __forceinline__ T pick_arg(T a) { return a; }
@@ -247,6 +206,7 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
   constexpr bool TYPED = pack_has<TypedArgs, Rk...>::value;
   constexpr bool GNC = pack_has<GncArgs, Rk...>::value;
   constexpr bool MIX = pack_has<MixArgs, Rk...>::value;
+  // which variants go together (GnEdges, gn_device.h): GNC never with robust, typed GNC never a batch, a mixture alone or typed
   static_assert(sizeof...(Rk) == (ROBUST ? 1 : 0) + (TYPED ? 1 : 0) + (GNC ? 1 : 0) + (MIX ? 1 : 0) && !(ROBUST && GNC) &&
                     !(BATCH && GNC && TYPED) && !(MIX && (ROBUST || GNC || BATCH)),
                 "k_linearize: one RobustArgs in the robust instances, one TypedArgs in the typed ones, one GncArgs in the GNC ones, "
@@ -256,23 +216,23 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
   const int k0 = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = k0 < n_active;
   const int k = k0 < nE ? k0 : nE - 1;                   // idle lanes of the last workgroup shadow the last edge
-  int i = ef[k], j = et[k];
-  double xi0 = poses[3 * i], xi1 = poses[3 * i + 1], xi2 = poses[3 * i + 2];
-  double xj0 = poses[3 * j], xj1 = poses[3 * j + 1], xj2 = poses[3 * j + 2];
-  const double* zp = k < nA ? meas + 3 * (size_t)k : meas_b + 3 * (size_t)(k - nA);
-  double z0 = zp[0], z1 = zp[1], z2 = zp[2];
+  const EdgeEnds L = edge_prologue(k, nA, poses, ef, et, meas, meas_b);
+  const double xi0 = L.xi0, xi1 = L.xi1, xi2 = L.xi2;
+  double z0 = L.z0, z1 = L.z1, z2 = L.z2;
   double c = cos(xi2), s = sin(xi2);
-  double dx = xj0 - xi0, dy = xj1 - xi1;
+  double dx = L.xj0 - xi0, dy = L.xj1 - xi1;
   double rx = c * dx + s * dy, ry = -s * dx + c * dy;
-  double rth = d_normalize_theta(xj2 - xi2);
+  double rth = d_normalize_theta(L.xj2 - xi2);
+  [[maybe_unused]] int fk = CGMR_EDGE_SE2;
+  if constexpr (TYPED) fk = k < nA ? (int)pick_arg<TypedArgs>(rk_pack...).edge_kind[k] : CGMR_EDGE_SE2;
   [[maybe_unused]] int mix_best = 0;
   if constexpr (MIX) {
     const MixArgs mx = pick_arg<MixArgs>(rk_pack...);
     const int p0 = mx.cptr[k], p1 = mx.cptr[k + 1];
     mix_best = p0;
     if (p1 - p0 > 1) {
-      int mfk = 0;
-      if constexpr (TYPED) mfk = (int)pick_arg<TypedArgs>(rk_pack...).edge_kind[k];
+      int mfk = CGMR_EDGE_SE2;
+      if constexpr (TYPED) mfk = (int)pick_arg<TypedArgs>(rk_pack...).edge_kind[k];      // (a mixture: nA == nE)
       double best = mix_r(mfk, rx, ry, rth, xi0, xi1, xi2, mx.cmeas + 3 * (size_t)p0, mx.cinfo + 6 * (size_t)p0) + mx.coff[p0];
       for (int p = p0 + 1; p < p1; p++) {
         const double cost = mix_r(mfk, rx, ry, rth, xi0, xi1, xi2, mx.cmeas + 3 * (size_t)p, mx.cinfo + 6 * (size_t)p) + mx.coff[p];
@@ -284,23 +244,16 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
     z0 = zs[0]; z1 = zs[1]; z2 = zs[2];
   }
   double cz = cos(z2), sz = sin(z2);
-  double tx = rx - z0, ty = ry - z1;
-  double e[3] = {cz * tx + sz * ty, -sz * tx + cz * ty, d_normalize_theta(rth - z2)};
-  const double* u = k < nA ? info + 6 * (size_t)k : info_b + 6 * (size_t)(k - nA);
+  double e[3];
+  factor_error(fk, rx, ry, rth, xi0, xi1, xi2, z0, z1, z2, cz, sz, e);
+  const double* u = k < nA ? info + 6 * (size_t)k : info_b + 6 * (size_t)(k - nA);   // (edge_split, by hand: see factor_model.h)
   if constexpr (MIX) u = pick_arg<MixArgs>(rk_pack...).cinfo + 6 * (size_t)mix_best;
+  // O cut down to the factor's own dimension (factor_dim; by kind, which keeps the typed instances' registers): the rows and
+  // columns beyond it are exact zeros, so e^T O e, J^T O J and the robust weight are the true-dimension factor's
   double O[9] = {u[0], u[1], u[2], u[1], u[3], u[4], u[2], u[4], u[5]};
-  [[maybe_unused]] int fk = 0;
   if constexpr (TYPED) {
-    fk = k < nA ? (int)pick_arg<TypedArgs>(rk_pack...).edge_kind[k] : 0;
-    if (fk == 1) { e[0] = tx; e[1] = ty; e[2] = 0.0; }
-    else if (fk == 2) {
-      e[0] = d_normalize_theta((rx * rx + ry * ry > 0.0 ? atan2(ry, rx) : 0.0) - z0); e[1] = 0.0; e[2] = 0.0;
-    } else if (fk == 3) {
-      const double px = xi0 - z0, py = xi1 - z1;
-      e[0] = cz * px + sz * py; e[1] = -sz * px + cz * py; e[2] = d_normalize_theta(xi2 - z2);
-    } else if (fk == 4) { e[0] = xi0 - z0; e[1] = xi1 - z1; e[2] = 0.0; }
-    if (fk == 1 || fk == 4) { O[2] = O[5] = O[6] = O[7] = O[8] = 0.0; }
-    if (fk == 2) { O[1] = O[2] = O[3] = O[4] = O[5] = O[6] = O[7] = O[8] = 0.0; }
+    if (fk == CGMR_EDGE_SE2_XY || fk == CGMR_EDGE_PRIOR_SE2_XY) { O[2] = O[5] = O[6] = O[7] = O[8] = 0.0; }
+    if (fk == CGMR_EDGE_BEARING_SE2_XY) { O[1] = O[2] = O[3] = O[4] = O[5] = O[6] = O[7] = O[8] = 0.0; }
   }
   double Oe[3];
 #pragma unroll
@@ -324,7 +277,7 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
       const double r = e[0] * Oe[0] + e[1] * Oe[1] + e[2] * Oe[2];
       if constexpr (BATCH) {
         // the robot graph's condensed graphs under stored GNC weights (cgmr_graph_set_condensed_gnc): kGncReuse only, one
-        // weight per own edge, shared by the jobs (not moved by the job stride); S, barc_sq, known and r_out are null
+        // weight per own edge, shared by the jobs (not moved by the job stride); S, barc_sq, known and r_out are not read
         rho1 = k < nA ? ga.weight[k] : 1.0;
       } else {
         if (ga.mode == kGncReuse) {
@@ -339,15 +292,10 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
       ch = live ? rho1 * r : 0.0;
     }
     if constexpr (MIX) ch = live ? ch + pick_arg<MixArgs>(rk_pack...).coff[mix_best] : 0.0;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) ch += __shfl_xor(ch, m, 64);
-    if ((threadIdx.x & 63) == 0) s_chi[threadIdx.x >> 6] = ch;
-    __syncthreads();
-    if (threadIdx.x == 0) term[33 * E + blockIdx.x] = (s_chi[0] + s_chi[1]) + (s_chi[2] + s_chi[3]);
+    block_chi2_partial(ch, s_chi, term, E);
   }
   if (chi_only) return;
   // the 33 doubles of an edge go through LDS so that the workgroup writes its 256 records as one contiguous stream
-  // (a thread writing its own 264-byte record produced 1.5x the bytes at the memory side in partial lines)
   extern __shared__ __attribute__((aligned(16))) double s_t[];        // [256][33]
   double* mine = s_t + threadIdx.x * 33;
   const bool compute = live && k0 < nE;
@@ -369,13 +317,13 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
     Jj[6 + q] = B[6 + q];
   }
   if constexpr (TYPED) {
-    if (fk != 0) {
+    if (fk != CGMR_EDGE_SE2) {
 #pragma unroll
       for (int q = 0; q < 9; q++) { Ji[q] = 0.0; Jj[q] = 0.0; }
-      if (fk == 1) {
+      if (fk == CGMR_EDGE_SE2_XY) {
 #pragma unroll
         for (int q = 0; q < 6; q++) { Ji[q] = A[q]; Jj[q] = B[q]; }
-      } else if (fk == 2) {
+      } else if (fk == CGMR_EDGE_BEARING_SE2_XY) {
         const double qq = rx * rx + ry * ry;
         if (qq > 0.0) {
           const double ua = -ry / qq, ub = rx / qq;
@@ -383,7 +331,7 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
           for (int q = 0; q < 3; q++) { Ji[q] = ua * A[q] + ub * A[3 + q]; Jj[q] = ua * B[q] + ub * B[3 + q]; }
           Ji[2] = -1.0;                                    // (ua ry - ub rx = -1)
         }
-      } else if (fk == 3) {
+      } else if (fk == CGMR_EDGE_PRIOR_SE2) {
         Ji[0] = cz; Ji[1] = sz; Ji[3] = -sz; Ji[4] = cz; Ji[8] = 1.0;
       } else {
         Ji[0] = 1.0; Ji[4] = 1.0;
@@ -413,18 +361,15 @@ __global__ __launch_bounds__(256) void k_linearize(int nE, int nA, int n_active,
     mine[30 + r] = -(JjO[3 * r] * e[0] + JjO[3 * r + 1] * e[1] + JjO[3 * r + 2] * e[2]);
   }
   if constexpr (TYPED) {
-    if (fk == 1) mine[26] = mine[18] > 0.0 ? mine[18] : 1.0;   // the point's dummy pivot
-    if (fk == 2) mine[26] = mine[18];                          // ... a bearing's: the copy alone (see above)
+    if (fk == CGMR_EDGE_SE2_XY) mine[26] = mine[18] > 0.0 ? mine[18] : 1.0;   // the point's dummy pivot
+    if (fk == CGMR_EDGE_BEARING_SE2_XY) mine[26] = mine[18];                  // ... a bearing's: the copy alone (see above)
   }
   if constexpr (ROBUST || GNC) {
 #pragma unroll
     for (int q = 0; q < 33; q++) mine[q] *= rho1;
   }
   }
-  __syncthreads();
-  const int e0 = blockIdx.x * 256, ne = min(256, nE - e0);
-  double* out = term + (size_t)e0 * 33;
-  for (int q = threadIdx.x; q < ne * 33; q += 256) out[q] = s_t[q];
+  CGMR_RECORDS_STREAM_OUT(s_t, term, nE)
 }
 
 // --------------------------------------------------------------------------------- assemble
@@ -527,7 +472,7 @@ __global__ __launch_bounds__(256) void k_chi2_reduce(int nP, const double* __res
 }
 
 // ------------------------------------------------------------------------------ unary terms
-// Priors (edge kinds 3 and 4) are edges from a vertex to itself, which the structure gives no assembly key: their records are
+// Priors (EDGE_PRIOR_SE2, EDGE_PRIOR_SE2_XY) are edges from a vertex to itself, which the structure gives no assembly key: their records are
 // added here, behind k_assemble and in front of whatever reads the assembled system (the damping, the factorisation).  One
 // thread per (vertex with priors, scalar of its diagonal block or of its right-hand side): it walks the vertex's priors in edge
 // order (uv_ptr / uv_edge: a CSR the host builds from the edge kinds) and adds the sum of term[edge * 33 + 0..8] to the block
@@ -1730,76 +1675,50 @@ __global__ __launch_bounds__(256) void k_update_poses(int nV, const int32_t* __r
 // the instance of a kernel for a plain pass or a batch
 #define CGMR_KERN(D, name) ((D).njobs > 1 ? name<true> : name<false>)
 
+// The live instances of k_linearize, written once: X(when, BATCH, ROBUST, trailing argument types...).  launch_linearize takes the
+// first row whose `when` holds for the pass (Ed, and batch = D.njobs > 1), gn_init_kernels raises the LDS limit of every row: an
+// instance is live exactly when it has a row.  The order is the variants' precedence, GNC before mixture before typed / robust;
+// the rows of one variant go from the most arguments to the fewest.  What the entry points cannot produce (GnEdges: a typed
+// batch, GNC with robust, ...) has no row and no handling of its own.
+#define CGMR_LINEARIZE_TABLE(X)                                  \
+  X(Ed.gnc && Ed.gnc_own_only, true, false, GncArgs)             \
+  X(Ed.gnc && Ed.typed, false, false, TypedArgs, GncArgs)        \
+  X(Ed.gnc, false, false, GncArgs)                               \
+  X(Ed.mix && Ed.typed, false, false, TypedArgs, MixArgs)        \
+  X(Ed.mix, false, false, MixArgs)                               \
+  X(Ed.typed && Ed.robust, false, true, RobustArgs, TypedArgs)   \
+  X(Ed.typed, false, false, TypedArgs)                           \
+  X(Ed.robust && batch, true, true, RobustArgs)                  \
+  X(Ed.robust, false, true, RobustArgs)                          \
+  X(batch, true, false)                                          \
+  X(true, false, false)
+
+namespace {
+
+template <typename T> const T& edge_arg(const GnEdges& Ed) {
+  if constexpr (std::is_same<T, RobustArgs>::value) return Ed.rk;
+  else if constexpr (std::is_same<T, TypedArgs>::value) return Ed.ty;
+  else if constexpr (std::is_same<T, GncArgs>::value) return Ed.ga;
+  else return Ed.mx;
+}
+
+template <bool BATCH, bool ROBUST, typename... Args>
+void launch_linearize_as(hipStream_t st, const GnDevice& D, const double* poses, const GnEdges& Ed, int chi_only) {
+  hipLaunchKernelGGL((k_linearize<BATCH, ROBUST, Args...>), dim3((D.nE + 255) / 256, 1, D.njobs), dim3(256), chi_only ? 0 : kRecordLds, st,
+                     D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only,
+                     D.job_stride, D.pose_stride, edge_arg<Args>(Ed)...);
+}
+
+}  // namespace
+
 void launch_linearize(hipStream_t st, const GnDevice& D, const double* poses, const GnEdges& Ed, int chi_only) {
   if (D.nE == 0) return;
   if (Ed.chordal_stage) { launch_linearize_chordal(st, D, poses, Ed); return; }   // (init_kernels.hip; never chi-only)
   gn_init_kernels();
-  const dim3 grid((D.nE + 255) / 256, 1, D.njobs);
-  const size_t lds = chi_only ? 0 : 256 * 33 * sizeof(double);
-  if (Ed.gnc) {                       // (never robust; a batch: the stored weights of the own edges, never typed)
-    GncArgs ga;
-    ga.weight = Ed.gnc_weight; ga.barc_sq = Ed.gnc_c; ga.known = Ed.gnc_known; ga.S = Ed.gnc_state; ga.r_out = Ed.gnc_r;
-    ga.mode = Ed.gnc_mode;
-    if (Ed.gnc_own_only) {            // (also a batch of one: the weight array ends with the own edges)
-      ga.barc_sq = nullptr; ga.known = nullptr; ga.S = nullptr; ga.r_out = nullptr; ga.mode = kGncReuse;
-      hipLaunchKernelGGL((k_linearize<true, false, GncArgs>), grid, dim3(256), lds, st, D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et,
-                         Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride, D.pose_stride, ga);
-      return;
-    }
-    if (Ed.typed) {
-      TypedArgs ty;
-      ty.edge_kind = Ed.edge_kind;
-      hipLaunchKernelGGL((k_linearize<false, false, TypedArgs, GncArgs>), grid, dim3(256), lds, st, D.nE, Ed.nA, Ed.n_active, poses, D.ef,
-                         D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride, D.pose_stride, ty, ga);
-      return;
-    }
-    hipLaunchKernelGGL((k_linearize<false, false, GncArgs>), grid, dim3(256), lds, st, D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et,
-                       Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride, D.pose_stride, ga);
-    return;
-  }
-  if (Ed.mix) {                       // (one job, never robust: the mixture entry points take no kernel)
-    MixArgs mx;
-    mx.cptr = Ed.mix_ptr; mx.cmeas = Ed.mix_meas; mx.cinfo = Ed.mix_info; mx.coff = Ed.mix_off; mx.sel_out = Ed.mix_sel;
-    if (Ed.typed) {
-      TypedArgs ty;
-      ty.edge_kind = Ed.edge_kind;
-      hipLaunchKernelGGL((k_linearize<false, false, TypedArgs, MixArgs>), grid, dim3(256), lds, st, D.nE, Ed.nA, Ed.n_active, poses, D.ef,
-                         D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride, D.pose_stride, ty, mx);
-      return;
-    }
-    hipLaunchKernelGGL((k_linearize<false, false, MixArgs>), grid, dim3(256), lds, st, D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et,
-                       Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride, D.pose_stride, mx);
-    return;
-  }
-  if (Ed.typed) {                     // (never a batch: the typed entry points run one job)
-    TypedArgs ty;
-    ty.edge_kind = Ed.edge_kind;
-    if (Ed.robust) {
-      RobustArgs rk;
-      rk.kind = Ed.rk_kind; rk.delta = Ed.rk_delta; rk.stats = D.njobs > 1 ? nullptr : Ed.rk_stats; rk.delta0 = Ed.rk_delta0;
-      rk.kind0 = Ed.rk_kind0;
-      hipLaunchKernelGGL((D.njobs > 1 ? k_linearize<true, true, RobustArgs, TypedArgs> : k_linearize<false, true, RobustArgs, TypedArgs>), grid,
-                         dim3(256), lds, st, D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term,
-                         chi_only, D.job_stride, D.pose_stride, rk, ty);
-      return;
-    }
-    hipLaunchKernelGGL((D.njobs > 1 ? k_linearize<true, false, TypedArgs> : k_linearize<false, false, TypedArgs>), grid, dim3(256), lds, st,
-                       D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only,
-                       D.job_stride, D.pose_stride, ty);
-    return;
-  }
-  if (Ed.robust) {                    // (a batch takes no statistics: run_cond_jobs never asks for them, the batched instance writes none)
-    RobustArgs rk;
-    rk.kind = Ed.rk_kind; rk.delta = Ed.rk_delta; rk.stats = D.njobs > 1 ? nullptr : Ed.rk_stats; rk.delta0 = Ed.rk_delta0;
-    rk.kind0 = Ed.rk_kind0;
-    hipLaunchKernelGGL((D.njobs > 1 ? k_linearize<true, true, RobustArgs> : k_linearize<false, true, RobustArgs>), grid, dim3(256), lds,
-                       st, D.nE, Ed.nA, Ed.n_active, poses, D.ef, D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only,
-                       D.job_stride, D.pose_stride, rk);
-    return;
-  }
-  hipLaunchKernelGGL((D.njobs > 1 ? k_linearize<true, false> : k_linearize<false, false>), grid, dim3(256), lds, st, D.nE, Ed.nA,
-                     Ed.n_active, poses, D.ef, D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, D.term, chi_only, D.job_stride,
-                     D.pose_stride);
+  const bool batch = D.njobs > 1;
+#define CGMR_X(when, ...) if (when) return launch_linearize_as<__VA_ARGS__>(st, D, poses, Ed, chi_only);
+  CGMR_LINEARIZE_TABLE(CGMR_X)
+#undef CGMR_X
 }
 
 void launch_chi2(hipStream_t st, const GnDevice& D, double* out) {
@@ -1813,8 +1732,9 @@ void launch_assemble(hipStream_t st, const GnDevice& D) {
 }
 
 void launch_add_unary(hipStream_t st, const GnDevice& D, const GnEdges& Ed) {
-  if (!Ed.typed || Ed.n_unary <= 0 || D.nf == 0) return;
-  hipLaunchKernelGGL(k_add_unary, dim3((Ed.n_unary * 12 + 255) / 256), dim3(256), 0, st, Ed.n_unary, Ed.uv_vertex, Ed.uv_ptr, Ed.uv_edge,
+  const UnaryLists& U = Ed.unary;
+  if (!Ed.typed || U.n <= 0 || D.nf == 0) return;
+  hipLaunchKernelGGL(k_add_unary, dim3((U.n * 12 + 255) / 256), dim3(256), 0, st, U.n, U.vertex, U.ptr, U.edge,
                      D.vperm, D.cmask, D.blk_dst, D.b_dst, D.term, D.Ablk, D.Pan, D.bvec);
 }
 
@@ -1829,18 +1749,10 @@ void gn_init_kernels() {
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, factor_smem_bytes(kChunkRows + 1));
     for (const void* f : {reinterpret_cast<const void*>(k_front_level<false>), reinterpret_cast<const void*>(k_front_level<true>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(factor_smem_bytes(kChunkRows + 1), 2 * (int)sizeof(UpdTileLds<kFrontW>)));
-    for (const void* f : {reinterpret_cast<const void*>(k_linearize<false, false>), reinterpret_cast<const void*>(k_linearize<true, false>),
-                          reinterpret_cast<const void*>(k_linearize<false, true, RobustArgs>),
-                          reinterpret_cast<const void*>(k_linearize<true, true, RobustArgs>),
-                          reinterpret_cast<const void*>(k_linearize<false, false, TypedArgs>), reinterpret_cast<const void*>(k_linearize<true, false, TypedArgs>),
-                          reinterpret_cast<const void*>(k_linearize<false, true, RobustArgs, TypedArgs>),
-                          reinterpret_cast<const void*>(k_linearize<true, true, RobustArgs, TypedArgs>),
-                          reinterpret_cast<const void*>(k_linearize<false, false, GncArgs>),
-                          reinterpret_cast<const void*>(k_linearize<false, false, TypedArgs, GncArgs>),
-                          reinterpret_cast<const void*>(k_linearize<true, false, GncArgs>),
-                          reinterpret_cast<const void*>(k_linearize<false, false, MixArgs>),
-                          reinterpret_cast<const void*>(k_linearize<false, false, TypedArgs, MixArgs>)})
-      (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 33 * (int)sizeof(double));
+#define CGMR_X(when, ...) reinterpret_cast<const void*>(k_linearize<__VA_ARGS__>),
+    for (const void* f : {CGMR_LINEARIZE_TABLE(CGMR_X)})
+#undef CGMR_X
+      (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kRecordLds);
     for (const void* f : {reinterpret_cast<const void*>(k_top_block<false>), reinterpret_cast<const void*>(k_top_block<true>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, top_smem_bytes(kTopMaxCols));
   });

@@ -18,13 +18,14 @@
 
 #include <mutex>
 
+#include "factor_model.h"
 #include "gn_device.h"
 #include "init_device.h"
 
 namespace cgmr {
 
-// One thread per edge, 256 per workgroup; the record layout, the (meas, info) / (meas_b, info_b) split, the n_active
-// convention, the LDS staging and the per-workgroup cost at term[33 nE + blockIdx.x] are k_linearize's (gn_kernels.hip).
+// The edge prologue, the per-workgroup cost at term[33 nE + blockIdx.x] and the record stream-out are k_linearize's
+// (factor_model.h), the record layout is its own (gn_kernels.hip).
 // A factor with a term in the stage gives the 2x2 Jacobians Ji, Jj of its 2-vector e, and the 2x2 information (o00, o01, o11):
 //   rotation     EDGE_SE2 (i, j)    e = r_j - R(z_th) r_i                         Ji = -R(z_th)          Jj = I      omega I
 //                EDGE_PRIOR_SE2     e = r_i - (cos z_th, sin z_th)                Ji = I                             omega I
@@ -44,25 +45,23 @@ __global__ __launch_bounds__(256) void k_linearize_chordal(int nE, int nA, int n
   const int k0 = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = k0 < n_active;
   const int k = k0 < nE ? k0 : nE - 1;                   // idle lanes of the last workgroup shadow the last edge
-  const int i = ef[k], j = et[k];
-  const double xi0 = poses[3 * i], xi1 = poses[3 * i + 1], xi2 = poses[3 * i + 2];
-  const double xj0 = poses[3 * j], xj1 = poses[3 * j + 1], xj2 = poses[3 * j + 2];
-  const double* zp = k < nA ? meas + 3 * (size_t)k : meas_b + 3 * (size_t)(k - nA);
-  const double z0 = zp[0], z1 = zp[1], z2 = zp[2];
-  const double* u = k < nA ? info + 6 * (size_t)k : info_b + 6 * (size_t)(k - nA);
-  int fk = 0;
-  if constexpr (TYPED) fk = k < nA ? (int)edge_kind[k] : 0;
+  const EdgeEnds L = edge_prologue(k, nA, poses, ef, et, meas, meas_b);
+  const double xi0 = L.xi0, xi1 = L.xi1, xi2 = L.xi2, xj0 = L.xj0, xj1 = L.xj1, xj2 = L.xj2;
+  const double z0 = L.z0, z1 = L.z1, z2 = L.z2;
+  const double* u = edge_split(k, nA, info, info_b, 6);
+  int fk = CGMR_EDGE_SE2;
+  if constexpr (TYPED) fk = k < nA ? (int)edge_kind[k] : CGMR_EDGE_SE2;
   const double c = cos(xi2), s = sin(xi2);
   const double cz = cos(z2), sz = sin(z2);
   double Ji[4] = {0, 0, 0, 0}, Jj[4] = {0, 0, 0, 0}, e[2] = {0, 0}, o00 = 0, o01 = 0, o11 = 0;
   if constexpr (STAGE == kChordalRotation) {
-    if (fk == 0) {
+    if (fk == CGMR_EDGE_SE2) {
       e[0] = cos(xj2) - (cz * c - sz * s);
       e[1] = sin(xj2) - (sz * c + cz * s);
       Ji[0] = -cz; Ji[1] = sz; Ji[2] = -sz; Ji[3] = -cz;
       Jj[0] = 1.0; Jj[3] = 1.0;
       o00 = o11 = u[5];
-    } else if (fk == 3) {
+    } else if (fk == CGMR_EDGE_PRIOR_SE2) {
       e[0] = c - cz;
       e[1] = s - sz;
       Ji[0] = 1.0; Ji[3] = 1.0;
@@ -71,41 +70,33 @@ __global__ __launch_bounds__(256) void k_linearize_chordal(int nE, int nA, int n
   } else {
     const double dx = xj0 - xi0, dy = xj1 - xi1;
     const double tx = (c * dx + s * dy) - z0, ty = (-s * dx + c * dy) - z1;
-    if (fk == 0) {
+    if (fk == CGMR_EDGE_SE2) {
       e[0] = cz * tx + sz * ty;
       e[1] = -sz * tx + cz * ty;
       Jj[0] = cz * c - sz * s; Jj[1] = cz * s + sz * c;           // R(z_th)^T R_i^T
       Jj[2] = -sz * c - cz * s; Jj[3] = -sz * s + cz * c;
 #pragma unroll
       for (int q = 0; q < 4; q++) Ji[q] = -Jj[q];
-    } else if (fk == 1) {
+    } else if (fk == CGMR_EDGE_SE2_XY) {
       e[0] = tx;
       e[1] = ty;
       Jj[0] = c; Jj[1] = s; Jj[2] = -s; Jj[3] = c;
 #pragma unroll
       for (int q = 0; q < 4; q++) Ji[q] = -Jj[q];
-    } else if (fk == 3) {
+    } else if (fk == CGMR_EDGE_PRIOR_SE2) {
       const double px = xi0 - z0, py = xi1 - z1;
       e[0] = cz * px + sz * py;
       e[1] = -sz * px + cz * py;
       Ji[0] = cz; Ji[1] = sz; Ji[2] = -sz; Ji[3] = cz;
-    } else if (fk == 4) {
+    } else if (fk == CGMR_EDGE_PRIOR_SE2_XY) {
       e[0] = xi0 - z0;
       e[1] = xi1 - z1;
       Ji[0] = 1.0; Ji[3] = 1.0;
     }
-    if (fk != 2) { o00 = u[0]; o01 = u[1]; o11 = u[3]; }
+    if (fk != CGMR_EDGE_BEARING_SE2_XY) { o00 = u[0]; o01 = u[1]; o11 = u[3]; }
   }
   const double Oe0 = o00 * e[0] + o01 * e[1], Oe1 = o01 * e[0] + o11 * e[1];
-  const size_t E = (size_t)nE;
-  {
-    double ch = live ? e[0] * Oe0 + e[1] * Oe1 : 0.0;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) ch += __shfl_xor(ch, m, 64);
-    if ((threadIdx.x & 63) == 0) s_chi[threadIdx.x >> 6] = ch;
-    __syncthreads();
-    if (threadIdx.x == 0) term[33 * E + blockIdx.x] = (s_chi[0] + s_chi[1]) + (s_chi[2] + s_chi[3]);
-  }
+  block_chi2_partial(live ? e[0] * Oe0 + e[1] * Oe1 : 0.0, s_chi, term, nE);
   double* mine = s_t + threadIdx.x * 33;
 #pragma unroll
   for (int q = 0; q < 33; q++) mine[q] = 0.0;            // a switched-off edge, the third row / column, a factor without a term
@@ -133,10 +124,7 @@ __global__ __launch_bounds__(256) void k_linearize_chordal(int nE, int nA, int n
     mine[8] = mine[0];                                    // the dummy unknowns' pivots: the copies of H(0,0)
     mine[26] = mine[18];
   }
-  __syncthreads();
-  const int e0 = blockIdx.x * 256, ne = min(256, nE - e0);
-  double* out = term + (size_t)e0 * 33;
-  for (int q = threadIdx.x; q < ne * 33; q += 256) out[q] = s_t[q];
+  CGMR_RECORDS_STREAM_OUT(s_t, term, nE)
 }
 
 // The rotation stage's pass end, behind the backward solve: theta_v = atan2(sin theta_v + ds, cos theta_v + dc) with (dc, ds)
@@ -162,39 +150,39 @@ __global__ __launch_bounds__(256) void k_apply_rotation(int nV, const int32_t* _
   poses[3 * v + 2] = atan2(ns, nc);
 }
 
-namespace {
-
-constexpr int kRecordLds = 256 * 33 * (int)sizeof(double);
-
-template <int STAGE, bool TYPED>
-void launch_stage(hipStream_t st, const GnDevice& D, const double* poses, const GnEdges& Ed) {
-  hipLaunchKernelGGL((k_linearize_chordal<STAGE, TYPED>), dim3((D.nE + 255) / 256), dim3(256), kRecordLds, st, D.nE, Ed.nA, Ed.n_active,
-                     poses, D.ef, D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, Ed.edge_kind, D.term);
-}
+// The instances of k_linearize_chordal, written once: X(when, STAGE, TYPED), the first row whose `when` holds is the pass's
+// (launch_linearize_chordal), and every row gets the LDS limit (init_chordal_kernels) -- as CGMR_LINEARIZE_TABLE, gn_kernels.hip.
+#define CGMR_CHORDAL_TABLE(X)                      \
+  X(rot && Ed.typed, kChordalRotation, true)       \
+  X(rot, kChordalRotation, false)                  \
+  X(Ed.typed, kChordalTranslation, true)           \
+  X(true, kChordalTranslation, false)
 
 // dynamic LDS above 64 KB: once per HIP device of the process, never inside a stream capture (gn_init_kernels)
-void init_chordal_kernels() {
+static void init_chordal_kernels() {
   static std::once_flag once[64];
   int dev = 0;
   (void)hipGetDevice(&dev);
   std::call_once(once[dev & 63], [] {
-    for (const void* f : {reinterpret_cast<const void*>(k_linearize_chordal<kChordalRotation, false>),
-                          reinterpret_cast<const void*>(k_linearize_chordal<kChordalRotation, true>),
-                          reinterpret_cast<const void*>(k_linearize_chordal<kChordalTranslation, false>),
-                          reinterpret_cast<const void*>(k_linearize_chordal<kChordalTranslation, true>)})
+#define CGMR_X(when, ...) reinterpret_cast<const void*>(k_linearize_chordal<__VA_ARGS__>),
+    for (const void* f : {CGMR_CHORDAL_TABLE(CGMR_X)})
+#undef CGMR_X
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kRecordLds);
   });
 }
-
-}  // namespace
 
 void launch_linearize_chordal(hipStream_t st, const GnDevice& D, const double* poses, const GnEdges& Ed) {
   if (D.nE == 0) return;
   init_chordal_kernels();
   const bool rot = Ed.chordal_stage == kChordalRotation;
-  if (Ed.typed) { if (rot) launch_stage<kChordalRotation, true>(st, D, poses, Ed); else launch_stage<kChordalTranslation, true>(st, D, poses, Ed); }
-  else if (rot) launch_stage<kChordalRotation, false>(st, D, poses, Ed);
-  else launch_stage<kChordalTranslation, false>(st, D, poses, Ed);
+#define CGMR_X(when, ...)                                                                                                        \
+  if (when) {                                                                                                                    \
+    hipLaunchKernelGGL((k_linearize_chordal<__VA_ARGS__>), dim3((D.nE + 255) / 256), dim3(256), kRecordLds, st, D.nE, Ed.nA,      \
+                       Ed.n_active, poses, D.ef, D.et, Ed.meas_a, Ed.info_a, Ed.meas_b, Ed.info_b, Ed.ty.edge_kind, D.term);       \
+    return;                                                                                                                      \
+  }
+  CGMR_CHORDAL_TABLE(CGMR_X)
+#undef CGMR_X
 }
 
 void launch_apply_rotation(hipStream_t st, const GnDevice& D, double* poses) {

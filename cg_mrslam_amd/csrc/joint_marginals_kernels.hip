@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "factor_model.h"
 #include "gn_device.h"
 
 namespace cgmr {
@@ -270,7 +271,7 @@ __global__ void k_observation_cov(int nP, const int32_t* __restrict__ pa, const 
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= nP) return;
   const int fk = kind[p];
-  if (fk == 0) return;
+  if (fk == CGMR_EDGE_SE2) return;
   const double* xa = poses + 3 * (size_t)pa[p];
   const double* xl = poses + 3 * (size_t)pb[p];
   const double c = cos(xa[2]), s = sin(xa[2]);
@@ -287,10 +288,10 @@ __global__ void k_observation_cov(int nP, const int32_t* __restrict__ pa, const 
   for (int i = 0; i < 2; i++)
     for (int j = 0; j < 2; j++) Sg[5 * (3 + i) + 3 + j] = Sbb[3 * i + j];
   double J[10] = {-c, -s, ry, c, s, s, -c, -rx, -s, c};
-  const int dim = fk == 1 ? 2 : 1;
+  const int dim = fk == CGMR_EDGE_SE2_XY ? 2 : 1;
   double z[3] = {rx, ry, 0.0};
   bool on_pose = false;
-  if (fk == 2) {
+  if (fk == CGMR_EDGE_BEARING_SE2_XY) {
     const double q = rx * rx + ry * ry;
     on_pose = !(q > 0.0);
     z[0] = on_pose ? 0.0 : atan2(ry, rx);

@@ -589,12 +589,11 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out) {
   g->rk_stats.clear();
   if (g->rk_dev) {                    // (set once any kernel is: own edges from the device arrays, received ones from the class)
     Ed.robust = true;
-    Ed.rk_kind = (const uint8_t*)g->d_rk_kind.ptr; Ed.rk_delta = (const double*)g->d_rk_delta.ptr;
-    Ed.rk_kind0 = g->rk_recv_kind; Ed.rk_delta0 = g->rk_recv_delta;
+    Ed.rk = {(const uint8_t*)g->d_rk_kind.ptr, (const double*)g->d_rk_delta.ptr, nullptr, g->rk_recv_delta, g->rk_recv_kind};
     if (nE > 0) {
       int rc = arena_reserve(ctx, ctx->rk_arena, 16 * (size_t)nE + 256);
       if (rc) return rc;
-      Ed.rk_stats = (double*)ctx->rk_arena.ptr;
+      Ed.rk.stats = (double*)ctx->rk_arena.ptr;
     }
   }
   if (g->gnc_keep) {                  // cgmr_graph_keep_gnc_weights: every own edge scaled by its stored weight (kGncReuse)
@@ -603,14 +602,14 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out) {
     if (any_robust_kernel(g))
       return gerr(g, CGMR_E_INVALID, "cgmr_graph_optimize: the stored GNC weights (cgmr_graph_keep_gnc_weights) are not combined with robust kernels");
     Ed.robust = false;
-    Ed.rk_kind = nullptr; Ed.rk_delta = nullptr; Ed.rk_stats = nullptr;
+    Ed.rk = RobustArgs();
     if (nE > 0) {
       int rc = dev_grow(g, g->d_gnc_w, 0, 8 * (size_t)nE);
       if (rc) return rc;
       g->gnc_w_up = g->gnc_w;         // (a member: it outlives the copy, and the solve's final wait comes before the next one)
       g->gnc_w_up.resize((size_t)nE, 1.0);
       HIP_TRY(ctx, hipMemcpyAsync(g->d_gnc_w.ptr, g->gnc_w_up.data(), 8 * (size_t)nE, hipMemcpyHostToDevice, ctx->stream));
-      Ed.gnc = true; Ed.gnc_mode = kGncReuse; Ed.gnc_weight = (double*)g->d_gnc_w.ptr;
+      Ed.gnc = true; Ed.ga.mode = kGncReuse; Ed.ga.weight = (double*)g->d_gnc_w.ptr;
     }
   }
   const double t0 = wall_s();
@@ -655,9 +654,9 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out) {
   }
   ctx->poses_out_host = nullptr;
   g->h_poses_fresh = asked && (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE);
-  if (Ed.rk_stats && (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE)) {
+  if (Ed.rk.stats && (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE)) {
     g->rk_stats.resize(2 * (size_t)nE);
-    HIP_TRY(ctx, hipMemcpyAsync(g->rk_stats.data(), Ed.rk_stats, 16 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(g->rk_stats.data(), Ed.rk.stats, 16 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   if (g->h_poses_fresh) memcpy(g->h_poses.data(), g->pinned_poses, 24 * (size_t)nV);
@@ -999,12 +998,11 @@ int cond_setup(CondBatch& B) {
   Ed.nA = B.nA; Ed.n_active = B.nA;                              // getMyEdges: the received edges are switched off
   if (g->cond_robust && g->rk_dev) {  // the own edges' kernels (the received ones are switched off: their class never enters)
     Ed.robust = true;
-    Ed.rk_kind = (const uint8_t*)g->d_rk_kind.ptr; Ed.rk_delta = (const double*)g->d_rk_delta.ptr;
-    Ed.rk_kind0 = CGMR_RK_NONE; Ed.rk_delta0 = 1.0;
+    Ed.rk = {(const uint8_t*)g->d_rk_kind.ptr, (const double*)g->d_rk_delta.ptr, nullptr, 1.0, CGMR_RK_NONE};
   }
   if (B.use_w) {                      // the own edges' stored weights (cond_queue binds the staged snapshot)
     Ed.robust = false;
-    Ed.gnc = true; Ed.gnc_own_only = true; Ed.gnc_mode = kGncReuse;
+    Ed.gnc = true; Ed.gnc_own_only = true; Ed.ga.mode = kGncReuse;
   }
   return 0;
 }
@@ -1129,7 +1127,7 @@ int cond_queue(CondBatch& B) {
   const double tp0 = wall_s();
   GnPassOpts pass;
   pass.write_l11c = true;
-  if (B.use_w) B.Ed.gnc_weight = (double*)(ds + S.s_w);          // (went up with the staging block above)
+  if (B.use_w) B.Ed.ga.weight = (double*)(ds + S.s_w);          // (went up with the staging block above)
   gn_pass_on(ctx, DB, st, d_work0, B.Ed, pass);
   const double tp1 = wall_s();
   B.t_gn = tp1 - tp0;

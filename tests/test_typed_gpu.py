@@ -194,6 +194,48 @@ def test_robust_cauchy_on_corrupted_landmark_observations(ctx):
     assert T.step_backward_error(g["poses"], p1, *a[1:], vk, ek, kind, delta) <= TC.OMEGA_MAX
 
 
+def test_typed_robust_call_then_batched_robust_condensed_graphs(ctx):
+    """The two robust linearisations side by side in one process: a typed Cauchy call on mixed257 (robust + typed, one job), then
+    a robot graph's robust condensed graphs for two peers in one batch (robust, batched -- a robot graph is never typed).  The
+    batch is held to the single calls on the same edges, gauge and query, at tests/test_robust_marginals_gpu.py's bars."""
+    from cg_mrslam_amd import synth
+    from cg_mrslam_amd.condensed import RobotGraph
+    from ref_condensed import select_gauge_centroid
+    from reference_cases import EST_ATOL, INFO_RTOL
+    g = TC.case("mixed257")
+    rc, _, chi, e2, w = ctx.gn_optimize_typed(*_a(g), 2, **_kw(g), kind="cauchy", delta=3.0)
+    assert rc == 0 and np.all(np.isfinite(chi)) and np.all(np.isfinite(e2)) and np.all((w > 0) & (w <= 1))
+    V = 300
+    h = synth.make_pose_graph(V, 900, seed=23, id_base=0)
+    ids = h["ids"].astype(np.int64)
+    e = (h["edge_from"], h["edge_to"], h["meas"], h["info"])
+    rg = RobotGraph(ctx, 0, 3)
+    try:
+        rg.add_vertices(ids, h["poses"], h["fixed"])
+        rg.add_edges(ids[e[0]], ids[e[1]], e[2], e[3])
+        rg.set_edge_robust("cauchy", 1.0)
+        assert rg.optimize(4)[0] == 0
+        want = {p: np.sort(np.random.default_rng(5 + p).choice(V, 6 + 2 * p, replace=False)).astype(np.int32) for p in (1, 2)}
+        for p, idx in want.items():
+            rg.insertOutClosure(p, ids[idx])
+        rg.set_condensed_robust(True)
+        assert rg.computeCondensedGraph(-1) == 2
+        poses = rg.poses()
+        for p, idx in want.items():
+            gid, to, est, iu = rg.condensed(p)
+            gauge = int(idx[select_gauge_centroid(poses[idx, :2])])
+            assert gid == ids[gauge]
+            to1, est1, iu1, _, _, _ = ctx.condense_robust(poses, *e, gauge, idx, "cauchy", 1.0)
+            assert np.array_equal(to, ids[to1])
+            d = est - est1
+            d[:, 2] = synth.normalize_theta(d[:, 2])
+            assert np.abs(d).max() <= EST_ATOL
+            for k in range(len(to)):
+                assert np.linalg.norm(iu[k] - iu1[k]) <= INFO_RTOL * np.linalg.norm(iu1[k]), (p, int(to[k]))
+    finally:
+        rg.close()
+
+
 @pytest.mark.parametrize("name", ["mixed257", "leaf_and_hub"])
 def test_marginals_against_reference(ctx, name):
     g = TC.case(name)

@@ -53,9 +53,11 @@ _SYMBOLS = [
     "cgmr_chordal_initialize_typed_dev", "cgmr_initial_guess",
     "cgmr_gn_optimize_mixture", "cgmr_gn_optimize_mixture_dev", "cgmr_lm_optimize_mixture", "cgmr_lm_optimize_mixture_dev",
     "cgmr_dl_optimize_mixture", "cgmr_dl_optimize_mixture_dev", "cgmr_mixture_select",
+    "cgmr_closure_consistency", "cgmr_max_clique_greedy",
 ]
 
 JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)
+PCM_MAX_CLOSURES = 1024       # include/cgmr.h: CGMR_PCM_MAX_CLOSURES (candidates of a consistency call, vertices of a clique call)
 
 
 def declared_symbols():
@@ -929,6 +931,57 @@ class Context:
                               vertex_kind, edge_kind, typed=True)
         return (z, cz, d2) + st
 
+    # pairwise consistency maximisation of closure candidates (include/cgmr.h: cgmr_closure_consistency, cgmr_max_clique_greedy)
+    @staticmethod
+    def _adj_bool(words, n):
+        """[n, n] bool from rows of 64-bit words: bit (l & 63) of word (k, l >> 6)."""
+        if n == 0:
+            return np.zeros((0, 0), dtype=bool)
+        bits = (words[:, :, None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)
+        return bits.reshape(n, -1)[:, :n].astype(bool)
+
+    @staticmethod
+    def _adj_words(adj):
+        adj = np.asarray(adj)
+        if adj.dtype == np.uint64:                                  # rows of words already ([n, W])
+            return np.ascontiguousarray(adj.reshape(adj.shape[0], -1)), adj.shape[0]
+        n = adj.shape[0]
+        if adj.shape != (n, n):
+            raise ValueError(f"adjacency: a square matrix, not {adj.shape}")
+        W = (n + 63) // 64
+        bits = np.zeros((n, 64 * W), dtype=np.uint64)
+        bits[:, :n] = adj.astype(bool)
+        words = (bits.reshape(n, W, 64) << np.arange(64, dtype=np.uint64)).sum(axis=2, dtype=np.uint64)
+        return np.ascontiguousarray(words), n
+
+    def closure_consistency(self, poses, fixed, ef, et, meas, info, cl_a, cl_b, cl_meas, cl_info, gamma, kind=None, delta=1.0):
+        """Pairwise consistency of N closure candidates (a, b, meas [N, 3], info_upper [N, 6]) that are not edges of the graph:
+        ``(d2 [N, N], adj [N, N] bool, clique, seed)`` -- d2 the squared Mahalanobis distance of the loop every pair closes
+        under the joint covariance of its four poses (NaN where not positive definite, 0 on the diagonal), adj = d2 < gamma off
+        the diagonal, clique the indices (ascending) of the greedy maximum clique of adj and the seed it grew from.  A greedy
+        heuristic, not an exact solver.  At most PCM_MAX_CLOSURES candidates.  ``kind`` / ``delta``: robust kernels on the
+        graph's edges, (e2, weights) appended."""
+        a, b = self._pair_arrays(cl_a, cl_b)
+        n = len(a)
+        cm = np.ascontiguousarray(cl_meas, dtype=np.float64).reshape(n, 3)
+        ci = np.ascontiguousarray(cl_info, dtype=np.float64).reshape(n, 6)
+        W = (n + 63) // 64
+        d2, words = np.zeros((n, n)), np.zeros((n, W), dtype=np.uint64)
+        clique, size, seed = np.full(n, -1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.full(1, -1, dtype=np.int32)
+        st = self._joint_call("cgmr_closure_consistency", poses, fixed, ef, et, meas, info,
+                              (C.c_int(n), _ptr(a), _ptr(b), _ptr(cm), _ptr(ci), C.c_double(float(gamma)), _ptr(d2), _ptr(words),
+                               _ptr(clique), _ptr(size), _ptr(seed)), kind, delta)
+        return (d2, self._adj_bool(words, n), clique[:int(size[0])].copy(), int(seed[0])) + st
+
+    def max_clique_greedy(self, adj):
+        """``(clique, seed)`` of a symmetric adjacency with a clear diagonal -- [n, n] bool, or rows of 64-bit words [n, W]
+        uint64 --: the greedy clique of closure_consistency (from every seed, the candidate with most neighbours left joins;
+        the largest over the seeds, ties to the lowest).  At most PCM_MAX_CLOSURES vertices."""
+        words, n = self._adj_words(adj)
+        clique, size, seed = np.full(n, -1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.full(1, -1, dtype=np.int32)
+        self._check(self.lib.cgmr_max_clique_greedy(self.h, C.c_int(n), _ptr(words), _ptr(clique), _ptr(size), _ptr(seed)))
+        return clique[:int(size[0])].copy(), int(seed[0])
+
     def set_symbolic_cache(self, on: bool):
         """Reuse of the ordering / symbolic analysis / structure upload across calls on the same edge list (default on)."""
         self._check(self.lib.cgmr_set_symbolic_cache(self.h, C.c_int(1 if on else 0)))
@@ -964,6 +1017,15 @@ class Context:
         self._check(self.lib.cgmr_gn_kernel_times_ex(self.h, _ptr(sec), _ptr(n)))
         names = ["linearize", "assemble", "chi2", "front_factor", "front_update", "top_block", "solve_bwd", "update", "front_level"]
         return {k: (float(s), int(c)) for k, s, c in zip(names, sec, n)}
+
+    def pcm_kernel_times(self):
+        """Profiling mode, classes 9..11 of cgmr_gn_kernel_times_ex: what closure_consistency spent in the forward solve and the
+        Gram tiles, in k_closure_consistency, and in the bit words and the clique (max_clique_greedy: the clique alone);
+        (seconds, launches) each, added up since set_profiling(True)."""
+        sec = np.zeros(12)
+        n = np.zeros(12, dtype=np.int64)
+        self._check(self.lib.cgmr_gn_kernel_times_ex(self.h, _ptr(sec), _ptr(n)))
+        return {k: (float(sec[i]), int(n[i])) for i, k in zip((9, 10, 11), ("gram", "consistency", "bits_clique"))}
 
 
 _SYM_KEYS = ["free_poses", "offdiag_blocks", "fronts", "levels", "L_doubles", "U_doubles", "max_border",

@@ -7,6 +7,7 @@
 #include "gn_host.h"
 #include "init_device.h"
 #include "lm_device.h"
+#include "pcm_device.h"
 #include "tr_device.h"
 
 #include <algorithm>
@@ -1725,6 +1726,165 @@ int joint_driver(cgmr_ctx* ctx, const char* who, int mode, int nV, const double*
   return rc;
 }
 
+// What the clique kernels of pcm_kernels.hip work in, behind whatever the caller has put into L: the seeds' member bits and
+// sizes and the result (size, seed, members).
+struct CliqueLayout {
+  size_t o_sb, o_ss, o_out;
+  CliqueLayout(Layout256& L, int n) : o_sb(L.add(8 * (size_t)n * ((n + 63) / 64))), o_ss(L.add(4 * (size_t)n)), o_out(L.add(4 * ((size_t)n + 2))) {}
+};
+// ... and where its result goes on the host once the stream has been waited for (res: n + 2 ints)
+static void clique_result_out(const std::vector<int32_t>& res, int n, int32_t* clique_out, int32_t* size_out, int32_t* seed_out) {
+  *size_out = res[0];
+  *seed_out = res[1];
+  memcpy(clique_out, res.data() + 2, 4 * (size_t)n);
+}
+
+// cgmr_closure_consistency: the pass and the solve half of joint_driver's mode 0 over the unique endpoints of the candidates,
+// every lower Gram tile (the macro-tile path), then the kernels of pcm_kernels.hip on the tiles where they lie: d2 of every
+// pair, its rows as bit words, the greedy clique of every seed and the best of them.  In profiling mode the launch classes
+// 9 (solve + Gram), 10 (k_closure_consistency) and 11 (bits and clique) of cgmr_gn_kernel_times_ex are timed and collected.
+int pcm_driver(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
+               const double* meas, const double* info, int nC, const int32_t* ca, const int32_t* cb, const double* cmeas,
+               const double* cinfo, double gamma, double* d2_out, uint64_t* adj_out, int32_t* clique_out, int32_t* size_out,
+               int32_t* seed_out, const cgmr_robust* rk) {
+  const char* who = "cgmr_closure_consistency";
+  if (nV <= 0 || nE < 0 || nC < 0 || !poses || !fixed || (nE > 0 && (!ef || !et || !meas || !info)) || (nC > 0 && (!ca || !cb || !cmeas || !cinfo)))
+    return set_err(ctx, CGMR_E_INVALID, "%s: null or negative argument", who);
+  const bool want_clique = clique_out || size_out || seed_out;
+  if (want_clique && !(clique_out && size_out && seed_out))
+    return set_err(ctx, CGMR_E_INVALID, "%s: clique_out, clique_size_out and seed_out are given together or not at all", who);
+  if (nC > CGMR_PCM_MAX_CLOSURES)
+    return set_err(ctx, CGMR_E_INVALID, "%s: %d closures, at most CGMR_PCM_MAX_CLOSURES = %d", who, nC, CGMR_PCM_MAX_CLOSURES);
+  for (int k = 0; k < nC; k++)
+    if (ca[k] < 0 || ca[k] >= nV || cb[k] < 0 || cb[k] >= nV)
+      return set_err(ctx, CGMR_E_INVALID, "%s: closure %d (%d -> %d) has an endpoint outside [0, %d)", who, k, ca[k], cb[k], nV);
+  if (!(std::isfinite(gamma) && gamma > 0)) return set_err(ctx, CGMR_E_INVALID, "%s: gamma must be finite and > 0", who);
+  if (nC == 0) { if (size_out) *size_out = 0; return CGMR_OK; }
+  // the unique endpoints, in order of first appearance: 4 columns of Y each (at most 2 nC <= CGMR_JOINT_MAX_QUERIES)
+  std::vector<int32_t> slot_of(nV, -1), uq;
+  auto slot = [&](int v) { if (slot_of[v] < 0) { slot_of[v] = (int32_t)uq.size(); uq.push_back(v); } return slot_of[v]; };
+  for (int k = 0; k < nC; k++) { slot(ca[k]); slot(cb[k]); }
+  const int nU = (int)uq.size();
+  MargCall call(ctx, nV, poses, nE, rk);
+  int rc = call.open(who);
+  if (rc) return rc;
+  rc = call.structure(fixed, ef, et);
+  if (rc) return rc;
+  Symbolic& S = ctx->sym;
+  GnDevice& D = ctx->gn;
+  hipStream_t st = ctx->stream;
+  call.factor = D.nf > 0;                                          // no free vertex: Sigma = 0, the measurement terms alone
+  const MargLayout M(nU, D.nf, S.rows.size(), D.nfronts, 0);
+  const int T = M.m / 16, W = (nC + 63) / 64;
+  const size_t n = (size_t)nC;
+  std::vector<int32_t> qcol(nU), sl(2 * n);
+  for (int k = 0; k < nU; k++) qcol[k] = ctx->vmask[uq[k]] ? -1 : S.vperm[uq[k]];      // fixed / inactive: zero columns
+  for (int k = 0; k < nC; k++) {
+    const int sa = slot_of[ca[k]], sb = slot_of[cb[k]];
+    sl[2 * k] = qcol[sa] < 0 ? -1 : sa; sl[2 * k + 1] = qcol[sb] < 0 ? -1 : sb;
+  }
+  JointGram JG;
+  JG.ntile = (long long)T * (T + 1) / 2;
+  joint_gram_split(M.n, (long long)((T + 3) / 4) * ((T + 3) / 4 + 1) / 2, &JG.rows, &JG.nsplit);
+  // staging: poses | meas | info | query columns, Y, border vectors, live flags (MargLayout) | partial tiles | tiles | the
+  // candidates | d2 | bit words | the clique's work space
+  Layout256& L = call.L;
+  const MargLayout ML(nU, D.nf, S.rows.size(), D.nfronts, L.off);
+  L.off = ML.end;
+  const size_t o_part = L.add(JG.nsplit > 1 ? 2048 * (size_t)JG.nsplit * (size_t)JG.ntile : 0), o_G = L.add(2048 * (size_t)JG.ntile),
+               o_sl = L.add(8 * n), o_ca = L.add(4 * n), o_cb = L.add(4 * n), o_cm = L.add(24 * n), o_ci = L.add(48 * n),
+               o_d2 = L.add(8 * n * n), o_adj = L.add(8 * n * W);
+  const CliqueLayout CL(L, nC);
+  rc = call.stage(meas, info);
+  if (rc) return rc;
+  char* d = call.d;
+  HIP_TRY(ctx, hipMemcpyAsync(d + ML.o_qc, qcol.data(), 4 * (size_t)nU, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_sl, sl.data(), 8 * n, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_ca, ca, 4 * n, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_cb, cb, 4 * n, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_cm, cmeas, 24 * n, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_ci, cinfo, 48 * n, hipMemcpyHostToDevice, st));
+  JG.part = (double*)(d + o_part);
+  JG.G = (double*)(d + o_G);
+  PcmClosures C;
+  C.n = nC;
+  C.a = (const int32_t*)(d + o_ca); C.b = (const int32_t*)(d + o_cb); C.slot = (const int32_t*)(d + o_sl);
+  C.meas = (const double*)(d + o_cm); C.info = (const double*)(d + o_ci);
+  std::vector<int32_t> res(n + 2, 0);
+  GnPassOpts pass;
+  pass.solve = pass.update_poses = false;
+  rc = call.run(pass, [&]() -> int {
+    KTimer KT{ctx, st};
+    if (call.factor)
+      KT.run(9, 2, [&] {
+        launch_marginals_solve(st, D, nU, (const int32_t*)(d + ML.o_qc), ML.m, (double*)(d + ML.o_Y), (double*)(d + ML.o_U),
+                               (uint8_t*)(d + ML.o_live));
+        launch_joint_gram(st, ML.n, ML.m, (const double*)(d + ML.o_Y), JG);
+      });
+    KT.run(10, 1, [&] { launch_closure_consistency(st, C, call.dp, JG.G, (double*)(d + o_d2)); });
+    if (adj_out || want_clique)
+      KT.run(11, want_clique ? 3 : 1, [&] {
+        launch_consistency_bits(st, nC, (const double*)(d + o_d2), gamma, (unsigned long long*)(d + o_adj));
+        if (want_clique)
+          launch_clique_greedy(st, nC, (const unsigned long long*)(d + o_adj), (unsigned long long*)(d + CL.o_sb), (int32_t*)(d + CL.o_ss),
+                               (int32_t*)(d + CL.o_out));
+      });
+    if (d2_out) HIP_TRY(ctx, hipMemcpyAsync(d2_out, d + o_d2, 8 * n * n, hipMemcpyDeviceToHost, st));
+    if (adj_out) HIP_TRY(ctx, hipMemcpyAsync(adj_out, d + o_adj, 8 * n * W, hipMemcpyDeviceToHost, st));
+    if (want_clique) HIP_TRY(ctx, hipMemcpyAsync(res.data(), d + CL.o_out, 4 * (n + 2), hipMemcpyDeviceToHost, st));
+    return 0;
+  });
+  if (ctx->profiling) profile_collect(ctx);
+  if (rc) return rc;
+  rc = call.close();
+  if (rc == CGMR_E_CHOLESKY_BASE) {
+    if (d2_out) memset(d2_out, 0, 8 * n * n);
+    if (adj_out) memset(adj_out, 0, 8 * n * W);
+    std::fill(res.begin(), res.end(), 0);
+  }
+  if (want_clique && (rc == CGMR_OK || rc == CGMR_E_CHOLESKY_BASE)) clique_result_out(res, nC, clique_out, size_out, seed_out);
+  return rc;
+}
+
+// cgmr_max_clique_greedy: the clique kernels alone on a caller's adjacency words, checked on the host first
+int clique_driver(cgmr_ctx* ctx, int n, const uint64_t* adj, int32_t* clique_out, int32_t* size_out, int32_t* seed_out) {
+  const char* who = "cgmr_max_clique_greedy";
+  if (n < 0 || !size_out || (n > 0 && (!adj || !clique_out || !seed_out))) return set_err(ctx, CGMR_E_INVALID, "%s: null or negative argument", who);
+  if (n > CGMR_PCM_MAX_CLOSURES) return set_err(ctx, CGMR_E_INVALID, "%s: %d vertices, at most CGMR_PCM_MAX_CLOSURES = %d", who, n, CGMR_PCM_MAX_CLOSURES);
+  if (n == 0) { *size_out = 0; return CGMR_OK; }
+  const int W = (n + 63) / 64;
+  auto bit = [&](int k, int l) { return (int)((adj[(size_t)k * W + (l >> 6)] >> (l & 63)) & 1u); };
+  for (int k = 0; k < n; k++) {
+    if (bit(k, k)) return set_err(ctx, CGMR_E_INVALID, "%s: word %d: vertex %d is adjacent to itself", who, k * W + (k >> 6), k);
+    if ((n & 63) && (adj[(size_t)k * W + W - 1] >> (n & 63)))
+      return set_err(ctx, CGMR_E_INVALID, "%s: word %d: a padding bit (column >= %d) of row %d is set", who, k * W + W - 1, n, k);
+    for (int l = 0; l < k; l++)
+      if (bit(k, l) != bit(l, k))
+        return set_err(ctx, CGMR_E_INVALID, "%s: word %d: bit (%d, %d) differs from bit (%d, %d)", who, k * W + (l >> 6), k, l, l, k);
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  Layout256 L;
+  const size_t o_adj = L.add(8 * (size_t)n * W);
+  const CliqueLayout CL(L, n);
+  int rc = arena_reserve(ctx, ctx->io_arena, L.off + 256);
+  if (rc) return rc;
+  char* d = ctx->io_arena.ptr;
+  hipStream_t st = ctx->stream;
+  std::vector<int32_t> res((size_t)n + 2, 0);
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_adj, adj, 8 * (size_t)n * W, hipMemcpyHostToDevice, st));
+  KTimer KT{ctx, st};
+  KT.run(11, 2, [&] {
+    launch_clique_greedy(st, n, (const unsigned long long*)(d + o_adj), (unsigned long long*)(d + CL.o_sb), (int32_t*)(d + CL.o_ss),
+                         (int32_t*)(d + CL.o_out));
+  });
+  HIP_TRY(ctx, hipMemcpyAsync(res.data(), d + CL.o_out, 4 * ((size_t)n + 2), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  HIP_TRY(ctx, hipGetLastError());
+  if (ctx->profiling) profile_collect(ctx);
+  clique_result_out(res, n, clique_out, size_out, seed_out);
+  return CGMR_OK;
+}
+
 // The mixture of a mixture entry point (include/cgmr.h: cgmr_mixture), checked on the host before the device is touched.  `any`:
 // some edge has more than one component (none: the call is the typed / plain one on meas / info, bit for bit).  off: per
 // component c = max_j a_j - a, a = 2 ln w + ln det Omega over the factor's own dimension, in double on the host; 0 on an edge
@@ -2611,6 +2771,22 @@ int cgmr_observation_covariance(cgmr_ctx* ctx, int nV, const double* poses, cons
                       d2_out, hyp_meas, hyp_info, rk, types, true, obs_kind);
 }
 
+int cgmr_closure_consistency(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                             const int32_t* et, const double* meas, const double* info, int nC, const int32_t* cl_a,
+                             const int32_t* cl_b, const double* cl_meas, const double* cl_info, double gamma, double* d2_out,
+                             uint64_t* adj_out, int32_t* clique_out, int32_t* clique_size_out, int32_t* seed_out,
+                             const cgmr_robust* rk) {
+  if (!ctx) return CGMR_E_INVALID;
+  return pcm_driver(ctx, nV, poses, fixed, nE, ef, et, meas, info, nC, cl_a, cl_b, cl_meas, cl_info, gamma, d2_out, adj_out, clique_out,
+                    clique_size_out, seed_out, rk);
+}
+
+int cgmr_max_clique_greedy(cgmr_ctx* ctx, int n, const uint64_t* adj_bits, int32_t* clique_out, int32_t* clique_size_out,
+                           int32_t* seed_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  return clique_driver(ctx, n, adj_bits, clique_out, clique_size_out, seed_out);
+}
+
 int cgmr_set_symbolic_cache(cgmr_ctx* ctx, int on) {
   if (!ctx) return CGMR_E_INVALID;
   ctx->sym_cache_on = on != 0;
@@ -2677,7 +2853,7 @@ int cgmr_gn_kernel_times(const cgmr_ctx* ctx, double seconds_out[8], int64_t lau
 }
 
 // the same with the classes beyond the first eight: 8 = front_level (k_front_level: a tree level's factorisation and its update
-// tiles in one launch); classes 9..11 are reserved (zero)
+// tiles in one launch); classes 9..11 are pcm_driver's / clique_driver's
 extern "C" int cgmr_gn_kernel_times_ex(const cgmr_ctx* ctx, double seconds_out[12], int64_t launches_out[12]) {
   if (!ctx || !seconds_out || !launches_out) return CGMR_E_INVALID;
   memcpy(seconds_out, ctx->ksec, sizeof(double) * 12);

@@ -90,7 +90,8 @@ struct cgmr_ctx {
   int64_t match_shape[4] = {0, 0, 0, 0};           // ... what the host chose for it: distance transform, 32-bit sort keys, lean instance, split
   int64_t match_redo_pairs = 0;                    // ... pairs the lean kernel instance handed to the general one
   bool profiling = false;
-  double ksec[12] = {0};        // classes 0..7 as cgmr_gn_kernel_times, 8 = front_level (a level's factorisation + update tiles in one launch)
+  double ksec[12] = {0};        // classes 0..7 as cgmr_gn_kernel_times, 8 = front_level (a level's factorisation + update tiles in one launch),
+                                // 9..11 = cgmr_closure_consistency's solve + Gram / pair kernel / bits + clique
   int64_t klaunch[12] = {0};
   // profiling mode: one event pair per launch, recorded without synchronising (the stream stays busy, so a pair
   // brackets the kernel and not an idle-to-busy launch latency); read back by profile_collect() after the final sync

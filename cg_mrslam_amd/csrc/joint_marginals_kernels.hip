@@ -18,6 +18,7 @@
 
 #include "factor_model.h"
 #include "gn_device.h"
+#include "pcm_device.h"
 
 namespace cgmr {
 
@@ -31,21 +32,7 @@ __device__ __forceinline__ double j_norm_theta(double t) {
   return t - 2 * pi * floor((t + pi) / (2 * pi));
 }
 
-// Element (ca, cb) of Y^T Y (columns of Y) out of the lower tiles: tile (I, J), J <= I, at position pos.  The element of a
-// diagonal tile is read from its lower half, so that (ca, cb) and (cb, ca) are the same double whatever the tile.
-__device__ __forceinline__ double gram_at(const double* __restrict__ G, long long pos, int ca, int cb) {
-  int r = ca & 15, c = cb & 15;
-  if ((ca >> 4) < (cb >> 4) || ((ca >> 4) == (cb >> 4) && r < c)) { const int t = r; r = c; c = t; }
-  return G[(size_t)pos * 256 + r * 16 + c];
-}
-
-__device__ __forceinline__ long long dense_pos(int ca, int cb) {
-  int I = ca >> 4, J = cb >> 4;
-  if (I < J) { const int t = I; I = J; J = t; }
-  return (long long)I * (I + 1) / 2 + J;
-}
-
-}  // namespace
+}  // namespace   (gram_at, dense_pos: pcm_device.h, shared with pcm_kernels.hip)
 
 // Partial tiles of the list: workgroup (tile t, row range s); each of the 4 wavefronts accumulates the tile over its quarter of
 // the range, then the four are summed in a fixed order.  rows: rows per range, a multiple of 16.

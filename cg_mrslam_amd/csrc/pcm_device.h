@@ -1,0 +1,46 @@
+// Device side of the pairwise consistency maximisation of closure candidates (pcm_kernels.hip; include/cgmr.h:
+// cgmr_closure_consistency, cgmr_max_clique_greedy), and the readers of the Gram tiles that it shares with
+// joint_marginals_kernels.hip.
+//
+// The clique search is the greedy heuristic PCM implementations use (seed, then repeatedly the candidate with most neighbours
+// left, over every seed): it returns a maximal clique, NOT a maximum one -- it is not an exact solver.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace cgmr {
+
+// Element (ca, cb) of Y^T Y (columns of Y) out of the lower tiles: tile (I, J), J <= I, at position pos.  The element of a
+// diagonal tile is read from its lower half, so that (ca, cb) and (cb, ca) are the same double whatever the tile.
+__device__ __forceinline__ double gram_at(const double* __restrict__ G, long long pos, int ca, int cb) {
+  int r = ca & 15, c = cb & 15;
+  if ((ca >> 4) < (cb >> 4) || ((ca >> 4) == (cb >> 4) && r < c)) { const int t = r; r = c; c = t; }
+  return G[(size_t)pos * 256 + r * 16 + c];
+}
+
+// position of the tile that holds (ca, cb) in the dense layout: every lower tile, (I, J) at I (I + 1) / 2 + J
+__device__ __forceinline__ long long dense_pos(int ca, int cb) {
+  int I = ca >> 4, J = cb >> 4;
+  if (I < J) { const int t = I; I = J; J = t; }
+  return (long long)I * (I + 1) / 2 + J;
+}
+
+// The candidates of a consistency call on the device: closure k goes from vertex a[k] to b[k] and measures x_a^-1 x_b as
+// meas[3 k ..] with information info[6 k ..] (upper triangle); slot[2 k], slot[2 k + 1]: the 4-column group of Y of a[k] and
+// b[k] among the unique endpoints, or -1 (fixed / inactive: zero rows of Sigma).
+struct PcmClosures {
+  int n = 0;
+  const int32_t *a = nullptr, *b = nullptr, *slot = nullptr;
+  const double *meas = nullptr, *info = nullptr;
+};
+
+// d2 [n * n], symmetric with an exact zero diagonal, from the dense tile set G (joint_marginals_kernels.hip) at `poses`
+void launch_closure_consistency(hipStream_t st, const PcmClosures& C, const double* poses, const double* G, double* d2);
+// adj [n * W], W = (n + 63) / 64: bit (l & 63) of word k * W + (l >> 6) = (k != l && d2[k][l] < gamma); padding bits zero
+void launch_consistency_bits(hipStream_t st, int n, const double* d2, double gamma, unsigned long long* adj);
+// The greedy clique of every seed (seed_bits [n * W]: its members, seed_size [n]), then the best of them: out[0] its size,
+// out[1] its seed, out[2 ..] its members ascending, -1 behind them (out: n + 2 ints).  n >= 1; adj symmetric, zero diagonal.
+void launch_clique_greedy(hipStream_t st, int n, const unsigned long long* adj, unsigned long long* seed_bits, int32_t* seed_size,
+                          int32_t* out);
+
+}  // namespace cgmr

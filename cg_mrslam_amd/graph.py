@@ -764,6 +764,27 @@ class GraphSLAM:
             z, cz, d2 = self.ctx.relative_covariance(*a, pairs[:, 0], pairs[:, 1], hm, hi, **kw)[:3]
         return (z, cz) if hypotheses is None else (z, cz, d2)
 
+    def closureConsistency(self, closures, gamma, robust: bool = False):     # noqa: N802
+        """Pairwise consistency maximisation over closure candidates that are not (yet) edges: ``closures`` a list of
+        ``(i, j, meas, info_upper)`` on vertex indices.  Returns ``(d2 [N, N], adj [N, N] bool, clique, seed)`` as
+        Context.closure_consistency does, on the level-0 edges at the current estimates (as relativeCovariance).  The clique is
+        the greedy heuristic's, not an exact maximum.  A typed graph raises ValueError: pose graphs only."""
+        a, kw, _ = self._joint_args(robust)
+        if "vertex_kind" in kw:
+            raise ValueError("closureConsistency: pose graphs only (the graph has landmarks or priors)")
+        cl = list(closures)
+        ca = np.array([c[0] for c in cl], dtype=np.int32)
+        cb = np.array([c[1] for c in cl], dtype=np.int32)
+        cm = np.array([c[2] for c in cl], dtype=np.float64).reshape(len(cl), 3)
+        ci = np.array([c[3] for c in cl], dtype=np.float64).reshape(len(cl), 6)
+        return self.ctx.closure_consistency(*a, ca, cb, cm, ci, gamma, **kw)[:4]
+
+    # the default gamma: the 0.99 quantile of chi2 with 3 degrees of freedom (scipy.stats.chi2.ppf(0.99, 3)) -- two candidates
+    # that both agree with the graph fail the test together once in a hundred
+    def consistentClosures(self, closures, gamma: float = 11.344866730144373, robust: bool = False):     # noqa: N802
+        """The indices (ascending) of the largest set of pairwise consistent candidates closureConsistency finds."""
+        return self.closureConsistency(closures, gamma, robust)[2]
+
     def observationCovariance(self, pairs, kinds, hypotheses=None, robust: bool = False):     # noqa: N802
         """Data association: for the vertex index pairs ``(pose, b)`` predicted as factors of ``kinds`` (per pair 0 EDGE_SE2,
         1 EDGE_SE2_XY, 2 EDGE_BEARING_SE2_XY): ``(z [n, 3], S [n, 3, 3])``, the predicted observation and its covariance

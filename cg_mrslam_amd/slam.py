@@ -213,7 +213,8 @@ class GraphSLAMDriver(GraphSLAM):
     ``covariance_estimate``."""
 
     def __init__(self, ctx, close_matcher, lc_matcher, idRobot=0, baseId=10000, windowLoopClosure=10, maxScore=0.15,   # noqa: N803
-                 inlierThreshold=2.0, minInliers=7, sm_information="fixed", sm_refine=None, lc_polish=None):   # noqa: N803
+                 inlierThreshold=2.0, minInliers=7, sm_information="fixed", sm_refine=None, lc_polish=None,   # noqa: N803
+                 closure_check="voting"):
         g = PoseGraph(np.zeros(0, dtype=np.int32), np.zeros((0, 3)), np.zeros(0, dtype=np.uint8),
                       np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros((0, 3)), np.zeros((0, 6)))
         super().__init__(g, ctx=ctx)
@@ -251,6 +252,13 @@ class GraphSLAMDriver(GraphSLAM):
         if lc_polish is not None and not (hasattr(lc_polish, "pod") and hasattr(lc_polish, "window")):
             raise ValueError("lc_polish is None or a matcher.PolishParams")
         self.lc_polish = lc_polish
+        # which buffered candidates become edges: "voting" = LoopClosureChecker (the reference: each candidate made exact in turn,
+        # the others' chi2 under a constant information); ("pcm", gamma) = the largest set of pairwise consistent candidates under
+        # the graph's own covariances (GraphSLAM.consistentClosures), gamma the chi2 threshold of a pair's loop
+        if closure_check != "voting" and not (isinstance(closure_check, tuple) and len(closure_check) == 2 and
+                                              closure_check[0] == "pcm" and float(closure_check[1]) > 0):
+            raise ValueError('closure_check is "voting" or ("pcm", gamma) with gamma > 0')
+        self.closure_check = closure_check
 
     # ------------------------------------------------------------------ graph bookkeeping
     def _index_of_id(self, vid):
@@ -458,6 +466,18 @@ class GraphSLAMDriver(GraphSLAM):
 
     def checkClosures(self):   # noqa: N802  (graph_slam.cpp:493-533)
         if not self._closures.checkList(self.windowLoopClosure):
+            return
+        if self.closure_check != "voting":
+            edges = self._closures.edges
+            clique = self.consistentClosures([(e["from"], e["to"], e["meas"], e.get("info", SM_INFO)) for e in edges],
+                                             float(self.closure_check[1]))
+            self.log.append(("pcm", len(clique), len(edges)))
+            if len(clique) >= self.minInliers:
+                for k in clique:
+                    e = edges[int(k)]
+                    if not e["added"]:                                     # HyperGraph::addEdge refuses an edge twice
+                        e["added"] = True
+                        self._add_edge(e["from"], e["to"], e["meas"], e.get("edge_info", SM_INFO), "lc", e["id"])
             return
         self.lcc.init(self.g.poses, self._closures.vertex_ids(), self._closures.edges, self.inlierThreshold)
         self.lcc.check()

@@ -561,7 +561,9 @@ int cgmr_gn_last_timing(const cgmr_ctx* ctx, double out[5]);
 int cgmr_set_profiling(cgmr_ctx* ctx, int on);
 int cgmr_gn_kernel_times(const cgmr_ctx* ctx, double seconds_out[8], int64_t launches_out[8]);
 /* ... with the classes added since: 8 front_level = a tree level's factorisation AND its update tiles in one launch
- * (k_front_level, round 6: the levels whose launch is certainly resident at once); 9..11 reserved.                    */
+ * (k_front_level, round 6: the levels whose launch is certainly resident at once); 9..11 cgmr_closure_consistency's:
+ * 9 the forward solve and the Gram tiles, 10 k_closure_consistency, 11 the bit words and the clique (cgmr_max_clique_greedy:
+ * the clique alone) -- zero in a library that does not export those symbols.                                          */
 int cgmr_gn_kernel_times_ex(const cgmr_ctx* ctx, double seconds_out[12], int64_t launches_out[12]);
 
 /* ------------------------------------------------------------------------------------------
@@ -809,6 +811,52 @@ int cgmr_observation_covariance(cgmr_ctx* ctx, int nV, const double* poses_xyt, 
                                 const uint8_t* obs_kind, double* z_out, double* cov_out, const double* hyp_meas_xyt,
                                 const double* hyp_info_upper, double* d2_out, const cgmr_factor_types* types,
                                 const cgmr_robust* rk);
+
+/* Pairwise consistency maximisation (PCM) of closure candidates (present in C ABI version 105 libraries that export these
+ * symbols).  Where cgmr_relative_covariance gates one hypothesis at a time, these ask whether two candidates agree with EACH
+ * OTHER, given what the graph knows about the poses between them, and keep the largest set whose members all agree pairwise:
+ * what LoopClosureChecker::check (src/slam/closure_checker.cpp) decides by making each candidate exact in turn and counting
+ * the others' chi2 under a constant information.  Pose graphs only.
+ *
+ * Candidate k = (cl_a[k], cl_b[k], z_k = cl_meas_xyt[3 k ..], Omega_k = cl_info_upper[6 k ..]) measures x_a^-1 x_b; the
+ * candidates are not edges of the graph.  With (+) the SE(2) composition on (x, y, theta), theta normalised to (-pi, pi], the
+ * loop residual of the pair l < k is
+ *   eps_kl = z_k (+) (x_bk^-1 (+) x_bl) (+) z_l^-1 (+) (x_al^-1 (+) x_ak)            (the identity when both agree with the graph)
+ * with the first-order covariance
+ *   S_kl = J_x Sigma J_x^T + J_zk Omega_k^-1 J_zk^T + J_zl Omega_l^-1 J_zl^T
+ * Sigma the 12x12 joint covariance of (x_ak, x_bk, x_al, x_bl) at poses_xyt with the given fixed flags, exactly as
+ * cgmr_marginals_joint returns it (cross-covariances included; shared, repeated, fixed and inactive vertices as there), the
+ * Jacobians for additive (x, y, theta) updates.  d2_out [nC * nC], row-major: d2[k][l] = d2[l][k] = eps_kl^T S_kl^-1 eps_kl,
+ * computed once per unordered pair; NaN where S_kl is not finite or not positive definite; exactly 0 on the diagonal.
+ * Adjacency: k ~ l iff k != l and d2[k][l] < gamma (NaN is not adjacent).  adj_out [nC * W], W = (nC + 63) / 64: bit (l & 63)
+ * of word k * W + (l >> 6); padding bits are zero.
+ *
+ * The clique (deterministic): from a seed s, C = {s} and P = A[s]; while P is not empty, the u in P with the largest
+ * |A[u] & P| (ties: the lowest index) joins C and P &= A[u].  The result is the C of largest size over all seeds (ties: the
+ * lowest seed): clique_out [nC] its members ascending, -1 behind them, clique_size_out [1], seed_out [1].  A graph without
+ * an edge gives size 1 from seed 0.  This is the greedy heuristic that PCM implementations use: the set is a maximal clique,
+ * NOT necessarily a maximum one -- it is not an exact solver.
+ *
+ * cgmr_closure_consistency: the nine graph arguments of cgmr_marginals, then the candidates (all four arrays required),
+ *   gamma (a chi2 quantile with 3 degrees of freedom: 11.344866730144373 for 0.99), the outputs -- d2_out and adj_out nullable,
+ *   the clique's three nullable together -- and rk (nullable, last) as for cgmr_marginals_joint.  The work is that call's over
+ *   the unique endpoints (at most 2 nC <= CGMR_JOINT_MAX_QUERIES; its device memory: Y and every lower Gram tile, which stay
+ *   on the device), one thread per pair on the tiles, one workgroup per seed; plus 8 nC^2 bytes of d2.  Analysis cache,
+ *   bounded-wait fall-back, return codes and their order as for cgmr_marginals_joint (CGMR_E_CHOLESKY_BASE: outputs zeroed,
+ *   size 0).  The caller's poses are not modified; two calls give identical bytes.
+ * cgmr_max_clique_greedy: the clique alone on a caller's adjacency words adj_bits (host, [n * W], the layout above).
+ * Both return CGMR_E_INVALID, naming the closure or the word in cgmr_last_error and before anything is queued, for: a null
+ * context or a null required pointer, a negative count, nC or n above CGMR_PCM_MAX_CLOSURES, an endpoint outside [0, nV), a
+ * gamma that is not finite or <= 0; for cgmr_max_clique_greedy a set diagonal bit, an asymmetric bit or a set padding bit.
+ * nC == 0 / n == 0: CGMR_OK, clique_size_out = 0 (where given) and nothing else written. */
+#define CGMR_PCM_MAX_CLOSURES 1024   /* 2 nC unique endpoints <= CGMR_JOINT_MAX_QUERIES */
+int cgmr_closure_consistency(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                             const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt, const double* info_upper,
+                             int nC, const int32_t* cl_a, const int32_t* cl_b, const double* cl_meas_xyt,
+                             const double* cl_info_upper, double gamma, double* d2_out, uint64_t* adj_out,
+                             int32_t* clique_out, int32_t* clique_size_out, int32_t* seed_out, const cgmr_robust* rk);
+int cgmr_max_clique_greedy(cgmr_ctx* ctx, int n, const uint64_t* adj_bits, int32_t* clique_out, int32_t* clique_size_out,
+                           int32_t* seed_out);
 
 /* ------------------------------------------------------------------------------------------
  * Generic correlative search (loop-closure / hierarchical / global matching).

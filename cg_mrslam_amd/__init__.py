@@ -6,6 +6,6 @@ Only what the path needs: ``csrc/`` (HIP kernels + the C ABI of include/cgmr.h, 
 workload generators (``synth``).  There is no CPU fallback: compute entry points raise
 ``CgmrError`` when libcgmr.so or a gfx950 device is missing.
 """
-from ._lib import CgmrError, Context, load_library, library_path  # noqa: F401
+from ._lib import CgmrError, Context, load_library, library_path, switch_table  # noqa: F401
 
-__all__ = ["CgmrError", "Context", "load_library", "library_path"]
+__all__ = ["CgmrError", "Context", "load_library", "library_path", "switch_table"]

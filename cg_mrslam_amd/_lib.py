@@ -53,7 +53,7 @@ _SYMBOLS = [
     "cgmr_chordal_initialize_typed_dev", "cgmr_initial_guess",
     "cgmr_gn_optimize_mixture", "cgmr_gn_optimize_mixture_dev", "cgmr_lm_optimize_mixture", "cgmr_lm_optimize_mixture_dev",
     "cgmr_dl_optimize_mixture", "cgmr_dl_optimize_mixture_dev", "cgmr_mixture_select",
-    "cgmr_closure_consistency", "cgmr_max_clique_greedy",
+    "cgmr_closure_consistency", "cgmr_max_clique_greedy", "cgmr_switches",
 ]
 
 JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)
@@ -1003,6 +1003,11 @@ class Context:
         self.lib.cgmr_gn_timeouts.restype = C.c_int64
         return int(self.lib.cgmr_gn_timeouts(self.h))
 
+    def switches(self):
+        """The environment switches this context holds (cgmr_switches): {name: value}, read when the context was created
+        (the process-scoped ones: when the process first needed them).  Flags and numbers are ints, a path is a string."""
+        return {r["name"]: r["value"] for r in _switch_rows(self.lib, self.h)}
+
     def gn_last_timing(self):
         out = np.zeros(5)
         self._check(self.lib.cgmr_gn_last_timing(self.h, _ptr(out)))
@@ -1026,6 +1031,25 @@ class Context:
         n = np.zeros(12, dtype=np.int64)
         self._check(self.lib.cgmr_gn_kernel_times_ex(self.h, _ptr(sec), _ptr(n)))
         return {k: (float(sec[i]), int(n[i])) for i, k in zip((9, 10, 11), ("gram", "consistency", "bits_clique"))}
+
+
+def _switch_rows(lib, h):
+    need = lib.cgmr_switches(h, None, C.c_int(0))
+    if need <= 0:
+        raise CgmrError(need, "cgmr_switches failed")
+    buf = C.create_string_buffer(need)
+    lib.cgmr_switches(h, buf, C.c_int(need))
+    rows = []
+    for line in buf.value.decode().splitlines():
+        name, scope, value, effect = line.split("\t")
+        rows.append(dict(name=name, scope=scope, value=int(value) if value.lstrip("-").isdigit() else value, effect=effect))
+    return rows
+
+
+def switch_table():
+    """Every environment switch of the library (csrc/switches.h), no device needed: a list of dict(name, scope, value, effect)
+    with ``value`` the default."""
+    return _switch_rows(load_library(), None)
 
 
 _SYM_KEYS = ["free_poses", "offdiag_blocks", "fronts", "levels", "L_doubles", "U_doubles", "max_border",

@@ -201,8 +201,7 @@ int gn_upload(cgmr_ctx* ctx, const Symbolic& S, int iters) {
   D.nlevels_full = (int)S.level_ptr.size() - 1;
   D.h_flevel_ptr = S.level_ptr;
   const std::vector<int32_t>& LF = S.gn_level_fronts;
-  static const int mid_chunk = getenv("CGMR_CHUNK") ? std::min(kChunkRows, std::max(16, atoi(getenv("CGMR_CHUNK")))) : kMidChunkRows;
-  static const int leaf_chunk = getenv("CGMR_LEAF_CHUNK") ? atoi(getenv("CGMR_LEAF_CHUNK")) : kLeafChunkRows;
+  const Switches& sw = ctx->sw;
   // sizing pass: work records (one per front and row chunk) and update tiles per level fix the blob layout
   D.h_tile_ptr.assign(D.nlevels + 1, 0);
   D.h_work_ptr.assign(D.nlevels + 1, 0);
@@ -224,12 +223,10 @@ int gn_upload(cgmr_ctx* ctx, const Symbolic& S, int iters) {
     for (int q = S.gn_level_ptr[l]; q < S.gn_level_ptr[l + 1]; q++)
       if (S.fronts[LF[q]].nchild > 0) D.h_level_leaf[l] = 0;
     // a level of leaves has its own chunk length (kLeafChunkRows)
-    int chunk_rows = (D.h_level_leaf[l] ? std::min(kChunkRows, std::max(16, leaf_chunk)) : mid_chunk);
+    int chunk_rows = D.h_level_leaf[l] ? sw.leaf_chunk : sw.mid_chunk;
     // the few fronts of an upper level (an idle chip): shorter chunks = more workgroups per front, each with less of the
     // panel to pull in on its own (a lone workgroup fetches cold data at 10-25 bytes per clock) -- and few extra records
-    static const int top_chunk = getenv("CGMR_TOP_CHUNK") ? std::min(kChunkRows, std::max(16, atoi(getenv("CGMR_TOP_CHUNK")))) : kTopChunkRows;
-    static const int top_fronts = getenv("CGMR_TOP_CHUNK_FRONTS") ? atoi(getenv("CGMR_TOP_CHUNK_FRONTS")) : kTopChunkFronts;
-    if (!D.h_level_leaf[l] && S.gn_level_ptr[l + 1] - S.gn_level_ptr[l] <= top_fronts) chunk_rows = std::min(chunk_rows, top_chunk);
+    if (!D.h_level_leaf[l] && S.gn_level_ptr[l + 1] - S.gn_level_ptr[l] <= sw.top_chunk_fronts) chunk_rows = std::min(chunk_rows, sw.top_chunk);
     D.h_level_chunk[l] = chunk_rows;
     int nwork = 0;
     for (int q = S.gn_level_ptr[l]; q < S.gn_level_ptr[l + 1]; q++) {
@@ -407,7 +404,7 @@ int gn_replicas(cgmr_ctx* ctx, int n, GnDevice& D, size_t* stride_out) {
 
 // The analysis of (nV, ef, et) into `sym`, which holds the analysis of (prev_nV, pef, pet) when have_prev: extended from it
 // where the two lists allow that, from scratch otherwise (shared by prepare_structure and the host-only test hook).
-int analyze_next(Symbolic& sym, bool have_prev, int prev_nV, const std::vector<int32_t>& pef, const std::vector<int32_t>& pet, int nV,
+int analyze_next(Symbolic& sym, const Switches& sw, bool have_prev, int prev_nV, const std::vector<int32_t>& pef, const std::vector<int32_t>& pet, int nV,
                  int nE, const int32_t* ef, const int32_t* et, const int32_t* hub_vertices, int n_hub_vertices, const AnalyzeHooks* hooks = nullptr) {
   int n_common = 0;
   if (have_prev && nV >= prev_nV && !pef.empty()) {
@@ -418,9 +415,9 @@ int analyze_next(Symbolic& sym, bool have_prev, int prev_nV, const std::vector<i
   const bool grown = n_common > 0 && (n_common == old_nE || (n_hub_vertices > 0 && 2 * n_common >= old_nE));
   if (grown) {
     Symbolic old = std::move(sym);
-    return analyze(nV, nullptr, nE, ef, et, sym, &old, n_common == old_nE && nE >= old_nE ? -1 : n_common, hub_vertices, n_hub_vertices, hooks);
+    return analyze(nV, nullptr, nE, ef, et, sym, sw, &old, n_common == old_nE && nE >= old_nE ? -1 : n_common, hub_vertices, n_hub_vertices, hooks);
   }
-  return analyze(nV, nullptr, nE, ef, et, sym, nullptr, -1, hub_vertices, n_hub_vertices, hooks);
+  return analyze(nV, nullptr, nE, ef, et, sym, sw, nullptr, -1, hub_vertices, n_hub_vertices, hooks);
 }
 
 // Ordering + symbolic analysis + structure upload for the edge list (ef, et), or nothing at all when the context
@@ -450,7 +447,7 @@ int prepare_structure(cgmr_ctx* ctx, int nV, int nE, const int32_t* ef, const in
   AnalyzeHooks hooks;
   int hook_rc = 0;
   hooks.blocks_ready = [&](const Symbolic& S, const int32_t* offbase) { hook_rc = gn_upload_early(ctx, S, ef, et, offbase); return hook_rc ? -100 : 0; };
-  int rc = analyze_next(ctx->sym, have_prev, ctx->sym_nV, ctx->sym_ef, ctx->sym_et, nV, nE, ef, et, hub_vertices, n_hub_vertices, &hooks);
+  int rc = analyze_next(ctx->sym, ctx->sw, have_prev, ctx->sym_nV, ctx->sym_ef, ctx->sym_et, nV, nE, ef, et, hub_vertices, n_hub_vertices, &hooks);
   if (rc == -100) return hook_rc;                                   // (the device pass of the analysis failed: its error is set)
   if (rc == 0 && ctx->sym.extended) ctx->sym_extended++; else ctx->sym_misses++;
   if (rc) return set_err(ctx, CGMR_E_INVALID, "graph structure rejected (edge index out of range)");
@@ -506,8 +503,7 @@ struct KTimer {   // optional per-launch-class timing (profiling mode only)
   hipStream_t st;
   template <typename Fn>
   void run(int cls, int nlaunch, Fn&& fn) {
-    static const bool trace = getenv("CGMR_TRACE_LAUNCHES") != nullptr;      // debugging aid: name every launch, sync after it
-    if (trace) {
+    if (ctx->sw.trace_launches) {                                 // debugging aid: name every launch, sync after it
       fprintf(stderr, "[cgmr] launch class %d (0 lin 1 asm 2 chi2 3 factor 4 update 5 top 6 bwd 7 poses 8 factor+update)\n", cls);
       fn();
       hipError_t e = hipStreamSynchronize(st);
@@ -548,7 +544,7 @@ void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, con
   T.run(1, 1, [&] { launch_assemble(st, D); });                // + the chi2 sum of this iteration (slot = iterations done)
   if (Ed.typed && Ed.unary.n > 0) T.run(1, 1, [&] { launch_add_unary(st, D, Ed); });   // the priors: self edges, no assembly key
   if (o.after_assemble) o.after_assemble(st, D, o.after_assemble_arg);
-  static const bool trace = getenv("CGMR_TRACE_LAUNCHES") != nullptr;
+  const bool trace = ctx->sw.trace_launches;
   if (trace)
     fprintf(stderr, "[cgmr] arena %p .. %p; work %p rel %p Pan %p Ablk %p bvec %p yvec %p uvec %p Lbuf %p Ubuf %p chi2 %p\n",
             (void*)ctx->gn_arena.ptr, (void*)(ctx->gn_arena.ptr + ctx->gn_arena.cap), (void*)D.work, (void*)D.rel, (void*)D.Pan,
@@ -576,7 +572,7 @@ void gn_pass_on(cgmr_ctx* ctx, GnDevice& D, hipStream_t st, double* d_poses, con
     if (D.h_tile_ptr[l + 1] > D.h_tile_ptr[l]) T.run(4, 1, [&] { launch_update_level(st, D, l); });
   }
   // the top of the tree in one launch: assembly, factorisation, forward and backward solve of the block's columns
-  static const bool clear_in_top = !(getenv("CGMR_CLEAR_IN_TOP") && atoi(getenv("CGMR_CLEAR_IN_TOP")) == 0);
+  const bool clear_in_top = ctx->sw.clear_in_top;
   // (the chained backward solve works with L11^-1 of every front: made by the idle workgroups of the top-block launch)
   const bool chain = o.solve && D.bwd_chain_level < D.nlevels;
   if (D.top_nfronts > 0) {
@@ -679,8 +675,7 @@ int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
   if (rc) return rc;
   // Every launch of a GN iteration is the same whatever the iteration's number (status[1] on the device supplies the
   // chi2 slot and the failure tag): CGMR_GRAPH=1 captures one iteration into a hipGraph and replays it.
-  static const bool graph_mode = getenv("CGMR_GRAPH") && atoi(getenv("CGMR_GRAPH")) != 0;
-  static const bool trace_launches = getenv("CGMR_TRACE_LAUNCHES") != nullptr;
+  const bool graph_mode = ctx->sw.graph, trace_launches = ctx->sw.trace_launches;
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   if (graph_mode && !ctx->profiling && !trace_launches && iters >= 2 && st != nullptr && D.nf > 0 && !Ed.mix) {
@@ -703,8 +698,7 @@ int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE,
   if (rc) return rc;
   {
     // CGMR_GN_TRACE: where a solve's wall time goes beside the analysis -- queueing the launches, waiting for the stream
-    static const bool gn_trace = getenv("CGMR_GN_TRACE") != nullptr;
-    if (gn_trace) {
+    if (ctx->sw.gn_trace) {
       const double t4 = wall_s();
       ctx->trace_n++; ctx->trace_sum[0] += call.t1 - call.t0; ctx->trace_sum[1] += call.t2 - call.t1; ctx->trace_sum[2] += t3 - call.t2; ctx->trace_sum[3] += t4 - t3;
     }
@@ -2309,7 +2303,9 @@ int cgmr_ctx_create(int device, void* hip_stream, cgmr_ctx** out) {
   if (hipSetDevice(device) != hipSuccess) return CGMR_E_NO_DEVICE;
   cgmr_ctx* ctx = new cgmr_ctx();
   ctx->device = device;
-  ctx->fwd_merge_any = !(getenv("CGMR_FWD_MERGE_ANY") && atoi(getenv("CGMR_FWD_MERGE_ANY")) == 0);
+  ctx->sw = read_switches();
+  ctx->gn.sw = &ctx->sw;
+  ctx->fwd_merge_any = ctx->sw.fwd_merge_any;
   if (hip_stream) { ctx->stream = (hipStream_t)hip_stream; ctx->own_stream = false; }
   else {
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return CGMR_E_HIP; }
@@ -2638,7 +2634,7 @@ int cgmr_gn_symbolic_info(int nV, const uint8_t* fixed, int nE, const int32_t* f
   if (nV < 0 || nE < 0 || !out) return CGMR_E_INVALID;
   Symbolic S;
   (void)fixed;          // the solver applies the fixed flags numerically: they are not part of the analysis
-  int rc = analyze(nV, nullptr, nE, from_idx, to_idx, S);
+  int rc = analyze(nV, nullptr, nE, from_idx, to_idx, S, read_switches());
   if (rc) return CGMR_E_INVALID;
   symbolic_info_out(S, nV, out, perm_out);
   return CGMR_OK;
@@ -2649,12 +2645,13 @@ int cgmr_gn_symbolic_info_grown(int nV0, int nE0, int n_steps, const int32_t* nV
                                 int32_t* n_extended_out) {
   if (nV0 < 0 || nE0 < 0 || n_steps < 0 || !out || (n_steps > 0 && (!nV_step || !nE_step))) return CGMR_E_INVALID;
   Symbolic S;
-  if (analyze(nV0, nullptr, nE0, from_idx, to_idx, S)) return CGMR_E_INVALID;
+  const Switches sw = read_switches();
+  if (analyze(nV0, nullptr, nE0, from_idx, to_idx, S, sw)) return CGMR_E_INVALID;
   int nV = nV0, next = 0;
   for (int k = 0; k < n_steps; k++) {
     if (nV_step[k] < nV || nE_step[k] < S.nE) return CGMR_E_INVALID;
     Symbolic old = std::move(S);
-    if (analyze(nV_step[k], nullptr, nE_step[k], from_idx, to_idx, S, &old)) return CGMR_E_INVALID;
+    if (analyze(nV_step[k], nullptr, nE_step[k], from_idx, to_idx, S, sw, &old)) return CGMR_E_INVALID;
     nV = nV_step[k];
     next += S.extended ? 1 : 0;
   }
@@ -2824,6 +2821,12 @@ int cgmr_symbolic_cache_stats3(const cgmr_ctx* ctx, int64_t out[3]) {
 
 int64_t cgmr_gn_timeouts(const cgmr_ctx* ctx) { return ctx ? ctx->gn_timeouts : -1; }
 
+int cgmr_switches(const cgmr_ctx* ctx, char* buf, int cap) {
+  if (cap < 0 || (cap > 0 && !buf)) return CGMR_E_INVALID;
+  const Switches defaults;
+  return list_switches(ctx ? ctx->sw : defaults, ctx ? process_switches() : defaults, buf, cap);
+}
+
 int cgmr_gn_last_timing(const cgmr_ctx* ctx, double out[5]) {
   if (!ctx || !out) return CGMR_E_INVALID;
   memcpy(out, ctx->timing, sizeof(double) * 5);
@@ -2867,7 +2870,7 @@ extern "C" int cgmr_gn_kernel_times_ex(const cgmr_ctx* ctx, double seconds_out[1
 extern "C" int cgmr_debug_fronts(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et, int cap, int32_t* out) {
   Symbolic S;
   (void)fixed;
-  if (analyze(nV, nullptr, nE, ef, et, S)) return -1;
+  if (analyze(nV, nullptr, nE, ef, et, S, read_switches())) return -1;
   int n = (int)S.fronts.size();
   for (int f = 0; f < n && f < cap; f++) {
     const FrontDesc& F = S.fronts[f];
@@ -2881,7 +2884,7 @@ extern "C" int cgmr_debug_fronts(int nV, const uint8_t* fixed, int nE, const int
 // parent's panel (0: root, or child of the top block)
 extern "C" int cgmr_debug_schedule(int nV, int nE, const int32_t* ef, const int32_t* et, int cap, int32_t* out) {
   Symbolic S;
-  if (analyze(nV, nullptr, nE, ef, et, S)) return -1;
+  if (analyze(nV, nullptr, nE, ef, et, S, read_switches())) return -1;
   int n = (int)S.fronts.size();
   for (int f = 0; f < n && f < cap; f++) {
     const FrontDesc& F = S.fronts[f];
@@ -2917,12 +2920,13 @@ extern "C" int cgmr_debug_symbolic_steps(int n_steps, const int32_t* nV, const i
                                          int32_t* n_extended_out, int fcap, int32_t* fronts_out, int64_t* per_step_out) {
   if (n_steps < 1 || !nV || !e_ptr || !out) return -1;
   Symbolic S;
+  const Switches sw = read_switches();
   std::vector<int32_t> pef, pet;
   int prev_nV = 0, next = 0;
   for (int k = 0; k < n_steps; k++) {
     const int nE = e_ptr[k + 1] - e_ptr[k];
     const int nh = h_ptr ? h_ptr[k + 1] - h_ptr[k] : 0;
-    if (analyze_next(S, k > 0, prev_nV, pef, pet, nV[k], nE, ef + e_ptr[k], et + e_ptr[k], nh ? hubs + h_ptr[k] : nullptr, nh)) return -1;
+    if (analyze_next(S, sw, k > 0, prev_nV, pef, pet, nV[k], nE, ef + e_ptr[k], et + e_ptr[k], nh ? hubs + h_ptr[k] : nullptr, nh)) return -1;
     if (k > 0 && S.extended) next++;
     if (per_step_out) {                                     // per step: levels, extended, ordering us, structure us, factor flops
       int64_t* o = per_step_out + 5 * (size_t)k;
@@ -2952,7 +2956,7 @@ extern "C" int cgmr_debug_asm_lists(cgmr_ctx* ctx, int nV, int nE, const int32_t
   if (!ctx) {
     Symbolic S;
     StructureRef R;
-    if (analyze(nV, nullptr, nE, ef, et, S) || structure_reference(S, nE, ef, et, R)) return -1;
+    if (analyze(nV, nullptr, nE, ef, et, S, read_switches()) || structure_reference(S, nE, ef, et, R)) return -1;
     const int nk = S.nf + S.nb;
     if (nk + 1 > cap_ptr || (int)R.asm_src.size() > cap_src) return -1;
     if (R.asm_ptr.empty()) { *n_src_out = 0; return nk; }
@@ -2980,7 +2984,7 @@ extern "C" int cgmr_debug_maps(cgmr_ctx* ctx, int nV, int nE, const int32_t* ef,
   if (!ctx) {
     Symbolic S;
     StructureRef R;
-    if (analyze(nV, nullptr, nE, ef, et, S) || structure_reference(S, nE, ef, et, R)) return -1;
+    if (analyze(nV, nullptr, nE, ef, et, S, read_switches()) || structure_reference(S, nE, ef, et, R)) return -1;
     const size_t n = R.rel.size() + R.inv.size() + R.blk_dst.size() + R.b_dst.size();
     if (n > (size_t)cap) return -1;
     int32_t* o = out;

@@ -10,6 +10,7 @@
 #include "../../include/cgmr.h"
 #include "gn_device.h"
 #include "gn_symbolic.h"
+#include "switches.h"
 
 namespace cgmr {
 struct Arena {
@@ -19,6 +20,7 @@ struct Arena {
 }  // namespace cgmr
 
 struct cgmr_ctx {
+  cgmr::Switches sw;             // the environment switches as they were when the context was created (switches.h)
   int device = 0;
   int n_cus = 0;                 // compute units of the device (queried once)
   hipStream_t stream = nullptr;
@@ -74,7 +76,7 @@ struct cgmr_ctx {
   std::vector<int32_t> sym_ef, sym_et;
   int64_t gn_timeouts = 0;       // bounded device-side waits that ran out (cgmr_gn_timeouts)
   bool fwd_merge_any = true;     // merged level launches also where the launch is not certainly resident at once (choose_fwd_merge);
-                                 // cleared by the first time-out on this context, CGMR_FWD_MERGE_ANY=0: never
+                                 // starts as sw.fwd_merge_any, cleared by the first time-out on this context
   int64_t sym_hits = 0, sym_misses = 0, sym_extended = 0;   // calls served from the cache / analysed from scratch / analysed by extending the cached ordering
   std::vector<uint8_t> vmask;    // per vertex: masked in the current pass
   cgmr::Symbolic sym;

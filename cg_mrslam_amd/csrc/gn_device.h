@@ -11,8 +11,10 @@
 namespace cgmr {
 
 struct GncState;                         // gnc_device.h
+struct Switches;                         // switches.h
 
 struct GnDevice {
+  const Switches* sw = nullptr;          // the owning context's switches (set by cgmr_ctx_create; copies of the view keep it)
   int nV = 0, nE = 0, nf = 0, nb = 0, nlevels = 0, nfronts = 0;
   // structure (uploaded once per analyse)
   FrontDesc* fronts = nullptr;

@@ -29,6 +29,7 @@
 #include "gnc_device.h"
 #include "init_device.h"
 #include "panel_cholesky.h"
+#include "switches.h"
 
 namespace cgmr {
 
@@ -1779,8 +1780,7 @@ void launch_front_level(hipStream_t st, const GnDevice& D, int l, bool write_l11
   gn_init_kernels();
   const int nw = D.h_work_ptr[l + 1] - D.h_work_ptr[l], nt = D.h_tile_ptr[l + 1] - D.h_tile_ptr[l];
   const int nw_pad = (nw + 7) / 8 * 8, ntw = ((nt + 1) / 2 + 7) / 8 * 8;
-  const char* sl = getenv("CGMR_BWD_SPIN_LIMIT");               // (the tests' switch for the chained backward solve bounds these waits as well)
-  const unsigned spin_limit = sl ? (unsigned)std::max(1, atoi(sl)) : (1u << 22);
+  const unsigned spin_limit = (unsigned)D.sw->bwd_spin_limit;   // (the tests' switch for the chained backward solve bounds these waits as well)
   hipLaunchKernelGGL(CGMR_KERN(D, k_front_level), dim3(nw_pad + ntw, 1, D.njobs), dim3(kFT), level_merge_smem(D, l), st, D.work, D.h_work_ptr[l], nw, nw_pad,
                      D.Pan, D.Lbuf, D.yvec, D.uvec, D.status, l, write_l11c ? 1 : 0, D.h_level_chunk[l], D.tiles, D.h_tile_ptr[l], nt, ntw,
                      D.fronts, D.children, D.inv, D.rel, D.Ubuf, D.Pan, D.ready, spin_limit, D.job_stride);
@@ -1799,7 +1799,6 @@ int level_merge_wgs(const GnDevice& D, int l) {
 // asking for it on a context that has seen a time-out.  C2's levels 0 and 1 (1656 and 1020 workgroups): 30.3 -> 26.0 and
 // 25.3 -> 23.3 us, 3.76 -> 3.68 ms device per optimize(10).
 void choose_fwd_merge(GnDevice& D, int slots_div, bool off, bool any_size) {
-  static const bool env_on = !(getenv("CGMR_FWD_MERGE") && atoi(getenv("CGMR_FWD_MERGE")) == 0);
   static int per_cu[64][4];                                   // resident workgroups per CU by LDS class (<= 40, 53, 80, 160 KB)
   static std::once_flag once[64];
   int dev = 0;
@@ -1817,7 +1816,7 @@ void choose_fwd_merge(GnDevice& D, int slots_div, bool off, bool any_size) {
   int ncu = 0;
   if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) ncu = 0;
   D.h_level_merge.assign(D.nlevels, 0);
-  if (!env_on || off || kFrontW != 48) return;
+  if (!D.sw->fwd_merge || off || kFrontW != 48) return;
   for (int l = 0; l < D.nlevels; l++) {
     const int wgs = level_merge_wgs(D, l), sm = level_merge_smem(D, l);
     const int cls = sm <= 40 * 1024 ? 0 : sm <= 53 * 1024 ? 1 : sm <= 80 * 1024 ? 2 : 3;
@@ -1863,8 +1862,7 @@ void launch_bwd_chain(hipStream_t st, const GnDevice& D) {
   const int first = D.h_level_ptr[D.bwd_chain_level], last = D.h_level_ptr[D.nlevels];
   if (last <= first) return;
   // CGMR_BWD_SPIN_LIMIT: polls a wait may take (tests force the time-out path with a tiny value)
-  const char* sl = getenv("CGMR_BWD_SPIN_LIMIT");               // (read per launch: a test switches it inside one process)
-  const unsigned spin_limit = sl ? (unsigned)std::max(1, atoi(sl)) : (1u << 22);
+  const unsigned spin_limit = (unsigned)D.sw->bwd_spin_limit;
   auto kern = D.bwd_chain_wgs == 2 ? (D.njobs > 1 ? k_solve_bwd<kFrontW, 2, true> : k_solve_bwd<kFrontW, 2, false>)
                                    : (D.njobs > 1 ? k_solve_bwd<kFrontW, 4, true> : k_solve_bwd<kFrontW, 4, false>);
   hipLaunchKernelGGL(kern, dim3(last - first, 1, D.njobs), dim3(256), bwd_smem_bytes(kFrontW, true), st, D.fronts_lv, last - 1, D.rows,
@@ -1876,8 +1874,7 @@ void launch_bwd_chain(hipStream_t st, const GnDevice& D) {
 // one launch each.  `slots_div`: the resident workgroups are shared (a side stream's batches, the jobs of a batch).
 // CGMR_BWD_CHAIN = n: at most n workgroups in the chained launch (0: one launch per level); CGMR_BWD_CHAIN_WGS = 2 / 4: that instance.
 void choose_bwd_chain(GnDevice& D, int slots_div, bool levelwise) {
-  static const int chain_env = getenv("CGMR_BWD_CHAIN") ? atoi(getenv("CGMR_BWD_CHAIN")) : -1;
-  static const int wgs_env = getenv("CGMR_BWD_CHAIN_WGS") ? atoi(getenv("CGMR_BWD_CHAIN_WGS")) : 0;
+  const int chain_env = D.sw->bwd_chain, wgs_env = D.sw->bwd_chain_wgs;
   slots_div = std::max(1, slots_div);
   const int total = D.h_level_ptr[D.nlevels] - D.h_level_ptr[0];
   int cap2 = bwd_chain_capacity(2) / slots_div, cap4 = bwd_chain_capacity(4) / slots_div;

@@ -1,6 +1,7 @@
 // Host-side symbolic analysis (see gn_symbolic.h).  Plain C++17, no GPU calls, so it is
 // unit-testable on a CPU-only machine through cgmr_gn_symbolic_info().
 #include "gn_symbolic.h"
+#include "switches.h"
 
 #include <algorithm>
 #include <atomic>
@@ -66,7 +67,7 @@ class HelperPool {
   // socket (the caller's home with it).  Called by analyze() once the caller is back on its own affinity mask.
   void rebalance() {
     // opt-in (CGMR_HOST_MOVE=1): a library inside somebody else's process does not move threads around on its own account
-    static const bool on = getenv("CGMR_HOST_MOVE") && atoi(getenv("CGMR_HOST_MOVE")) != 0;
+    const bool on = process_switches().host_move;
     const long long w = wall_ns_.exchange(0, std::memory_order_relaxed), c = cpu_ns_.exchange(0, std::memory_order_relaxed);
     if (!on || getpid() != owner_) return;
     std::lock_guard<std::mutex> lk(state_mu_);                    // (several caller threads analyse: a context per robot, a thread each)
@@ -107,7 +108,7 @@ class HelperPool {
   // robot's long job would hold this caller up behind work it never asked for.)
   static void wait(Job& job);
   void help_until(Job& job) {
-    static const bool steal = !(getenv("CGMR_HOST_STEAL") && atoi(getenv("CGMR_HOST_STEAL")) == 0);
+    const bool steal = process_switches().host_steal;
     while (!job.done.load(std::memory_order_acquire)) {
       Job* other = nullptr;
       if (steal && pending_.load(std::memory_order_acquire) > 0 && getpid() == owner_) {
@@ -154,7 +155,7 @@ class HelperPool {
     return !out.empty();
   }
   void pin_near_caller() {
-    static const bool off = getenv("CGMR_HOST_PIN") && atoi(getenv("CGMR_HOST_PIN")) == 0;
+    const bool off = process_switches().host_pin == 0;
     if (off || threads_.empty() || getpid() != owner_) return;
     int me = sched_getcpu();
     if (me < 0) return;
@@ -231,7 +232,7 @@ class HelperPool {
     }
     if ((int)picks.size() < (int)threads_.size()) return false;   // fewer cores behind this cache than helpers: leave the scheduler alone
     bool all = true;
-    static const int pin_mode = getenv("CGMR_HOST_PIN") ? atoi(getenv("CGMR_HOST_PIN")) : 1;
+    const int pin_mode = process_switches().host_pin;
     cpu_set_t whole;                                               // CGMR_HOST_PIN=2: every helper anywhere in the group but on the caller's core
     CPU_ZERO(&whole);
     for (int c : l3) {
@@ -260,7 +261,7 @@ class HelperPool {
     explicit CallerAtHome(HelperPool& p) {
       // opt-in (CGMR_HOST_PIN_CALLER=1): by default the library never touches the affinity of a thread it does not own -- a
       // ROS node that links it has its own ideas about where its threads run
-      static const bool on = getenv("CGMR_HOST_PIN_CALLER") && atoi(getenv("CGMR_HOST_PIN_CALLER")) != 0;
+      const bool on = process_switches().host_pin_caller;
       if (!on) return;
       // one caller at a time: a second thread of the process that analyses meanwhile (a context per robot, a thread each)
       // stays where it is instead of queueing up for the same core
@@ -307,7 +308,7 @@ class HelperPool {
       // long as it takes to come back with the next analysis (the bench sets 10 ms: a helper that sleeps through the 5 ms of
       // device work between two analyses pays a futex wake-up each time, and on a shared host its core has been given to
       // somebody else in the meantime) -- not the default, because 8 ranks x 7 helpers would then never sleep.
-      static const long long spin_ns = 1000LL * (getenv("CGMR_HOST_SPIN_US") ? std::max(0, atoi(getenv("CGMR_HOST_SPIN_US"))) : 200);
+      const long long spin_ns = 1000LL * process_switches().host_spin_us;
       const long long spin_until = clock_ns(CLOCK_MONOTONIC) + spin_ns;
       for (unsigned spin = 0; !job; spin++) {
         if (pending_.load(std::memory_order_acquire) > 0) {
@@ -372,6 +373,7 @@ struct NDCtx {
   const std::vector<int32_t>& ai;
   std::vector<int32_t>& order;        // in/out working permutation
   std::vector<uint8_t>& pstart;       // pstart[pos] = 1 if a front begins at position pos
+  const Switches& sw;
   std::mutex range_mu;
   std::vector<std::pair<int, int>> subtree_ranges;   // position ranges of the halves of the nodes at depth kRangeDepth:
                                                      // complete subtrees, independent of each other
@@ -441,7 +443,7 @@ int bfs(NDCtx& C, int32_t* q, int root, int id, int visited_id, int32_t* lvl = n
 // `start`: a vertex of the range known to lie at one end of it (the parent's sweep began or ended there), or -1.
 NDRange nd(NDCtx& C, int begin, int end, int depth, int start = -1, int* node_out = nullptr) {
   int n = end - begin;
-  static const bool nd_trace = getenv("CGMR_SYM_TRACE") != nullptr;
+  const bool nd_trace = C.sw.sym_trace;
   const double t_in = nd_trace ? now_s() : 0;
   int node_sink = -1;
   int& node = node_out ? *node_out : node_sink;
@@ -455,8 +457,7 @@ NDRange nd(NDCtx& C, int begin, int end, int depth, int start = -1, int* node_ou
   // first sweep: connectivity + a far vertex; skipped when the parent's sweep already left one (then the second
   // sweep doubles as the connectivity check)
   int vis1 = id + 1, vis2 = id + 2;
-  static const bool reuse_start = !(getenv("CGMR_ND_REUSE_START") && atoi(getenv("CGMR_ND_REUSE_START")) == 0);
-  const bool have_start = reuse_start && start >= 0;
+  const bool have_start = C.sw.nd_reuse_start && start >= 0;
   const double t_l0 = nd_trace ? now_s() : 0;
   // The root (round 6): instead of a sweep for a far vertex and a second one from there -- two whole-graph sweeps one behind
   // the other on one thread, 0.38 ms at C2's size, while the others idle --, K = 4 structuring sweeps side by side from the
@@ -467,7 +468,7 @@ NDRange nd(NDCtx& C, int begin, int end, int depth, int start = -1, int* node_ou
   // on average -- the height of a dissection tree moves by chance with the root's cut, no start rule predicts it (DESIGN.md
   // 2.1); the benchmark graph happens to come out a level shorter (17 / 15 launched instead of 18 / 16).  The result does not
   // depend on the number of threads (the same four candidates whatever runs them).  CGMR_ND_ROOT_STARTS=0: the double sweep.
-  static const int root_starts = getenv("CGMR_ND_ROOT_STARTS") ? atoi(getenv("CGMR_ND_ROOT_STARTS")) : 4;
+  const int root_starts = C.sw.nd_root_starts;
   bool multi_done = false;
   int reached = 0;
   if (depth == 0 && !have_start && root_starts > 1 && n >= 2048) {
@@ -558,7 +559,7 @@ NDRange nd(NDCtx& C, int begin, int end, int depth, int start = -1, int* node_ou
       X.push_back(v);
       xptr.push_back((int)xadj.size());
     }
-    static const bool min_cover = !(getenv("CGMR_ND_MIN_COVER") && atoi(getenv("CGMR_ND_MIN_COVER")) == 0);
+    const bool min_cover = C.sw.nd_min_cover;
     const int nx = (int)X.size(), ny = (int)Y.size();
     if (min_cover && nx > 1 && ny > 0) {
       std::vector<int32_t> mx(nx, -1), my(ny, -1), seen(ny, -1), stack;
@@ -757,8 +758,7 @@ double cgroup_cpu_quota() {
 
 int host_threads() {
   static int n = [] {
-    const char* e = getenv("CGMR_HOST_THREADS");
-    int v = e ? atoi(e) : 0;
+    int v = process_switches().host_threads;
     if (v <= 0) {
       unsigned hc = std::thread::hardware_concurrency();
       v = hc >= 32 ? 8 : (hc >= 8 ? 4 : (hc >= 4 ? 2 : 1));
@@ -841,7 +841,7 @@ void materialize_nd_tree(Symbolic& S) {
 bool extend_order(Symbolic& prev, int nf, const std::vector<int32_t>& ap, const std::vector<int32_t>& ai,
                   std::vector<int32_t>& order, std::vector<uint8_t>& pstart, std::vector<std::pair<int, int>>& pos_ranges,
                   Symbolic& S, int n_new_edges, const int32_t* new_ef, const int32_t* new_et, const std::vector<int32_t>& hidx,
-                  const std::vector<int32_t>& forced_hubs) {
+                  const std::vector<int32_t>& forced_hubs, const Switches& sw) {
   typedef Symbolic::NDNode Node;
   materialize_nd_tree(prev);
   std::vector<Node> T = std::move(prev.nd_nodes);            // (the caller's previous analysis is discarded afterwards either way)
@@ -921,7 +921,7 @@ bool extend_order(Symbolic& prev, int nf, const std::vector<int32_t>& ap, const 
   // from a peer): their nodes must lie on one root path, or the two subtrees are not independent any more -- the parallel
   // border computation below hands "independent" subtrees to different threads and produced a wrong structure for such a
   // graph (found with the C5 rounds of two robots with a context each: Cholesky failure in round 40).  Then: full analysis.
-  static const bool check_new_edges = !(getenv("CGMR_SYM_EXTEND_CHECK") && atoi(getenv("CGMR_SYM_EXTEND_CHECK")) == 0);   // (0: the round-3 bug, for its test)
+  const bool check_new_edges = sw.sym_extend_check;   // (0: the round-3 bug, for its test)
   for (int k = 0; check_new_edges && k < n_new_edges; k++) {
     const int a = hidx[new_ef[k]], b = hidx[new_et[k]];
     if (a < 0 || b < 0 || a == b) continue;
@@ -937,7 +937,7 @@ bool extend_order(Symbolic& prev, int nf, const std::vector<int32_t>& ap, const 
       const int n = (int)T[leaf].verts.size();
       lorder = T[leaf].verts;
       lpstart.assign(n, 0);
-      NDCtx C{ap, ai, lorder, lpstart};
+      NDCtx C{ap, ai, lorder, lpstart, sw};
       C.vs.assign(nf, NDCtx::VState{0, 0});
       C.queue.assign(n, 0);
       C.tmp.assign(n, 0);
@@ -1029,7 +1029,7 @@ bool extend_order(Symbolic& prev, int nf, const std::vector<int32_t>& ap, const 
   // extension saves ~0.35 ms of ordering: a tree that has grown more than a few panels taller than the last from-scratch
   // ordering's is not worth keeping (CGMR_SYM_EXTEND_SLACK panels, default 2; the simulated C5 rounds of eight robots: mean
   // tree height 13.5 levels extended without the bound, 11.2 from scratch every round).
-  static const int slack = getenv("CGMR_SYM_EXTEND_SLACK") ? atoi(getenv("CGMR_SYM_EXTEND_SLACK")) : 2;
+  const int slack = sw.sym_extend_slack;
   if (slack >= 0 && prev.nd_height_full > 0 && whole.height > prev.nd_height_full + slack) return false;
   S.nd_height_full = prev.nd_height_full;
   order.swap(order2);
@@ -1044,10 +1044,10 @@ bool extend_order(Symbolic& prev, int nf, const std::vector<int32_t>& ap, const 
 
 }  // namespace
 
-int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et, Symbolic& S, Symbolic* prev,
-            int n_common, const int32_t* hub_vertices, int n_hub_vertices, const AnalyzeHooks* hooks) {
+int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et, Symbolic& S, const Switches& sw,
+            Symbolic* prev, int n_common, const int32_t* hub_vertices, int n_hub_vertices, const AnalyzeHooks* hooks) {
   double t0 = now_s();
-  static const bool trace = getenv("CGMR_SYM_TRACE") != nullptr;
+  const bool trace = sw.sym_trace;
   struct Rebalance {                                             // (destroyed after at_home: the caller's own mask is back)
     long long w0 = HelperPool::now_ns(CLOCK_MONOTONIC), c0 = HelperPool::now_ns(CLOCK_THREAD_CPUTIME_ID);
     ~Rebalance() {
@@ -1106,8 +1106,7 @@ int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32
   // over the vertices turns the columns into row starts and per-thread write positions, every thread files its share -- the
   // rows hold their entries in edge order, exactly as the one-thread pass leaves them, and the edge list is read once per
   // pass instead of once per thread and pass (CGMR_ADJ_SLICES=0: every thread walks the whole list and keeps its vertex range).
-  static const bool adj_slices = !(getenv("CGMR_ADJ_SLICES") && atoi(getenv("CGMR_ADJ_SLICES")) == 0);
-  if (adj_slices && NTA > 1) {
+  if (sw.adj_slices && NTA > 1) {
     std::vector<int32_t> cnt((size_t)NTA * nf, 0);
     auto in_slices = [&](auto&& body) {
       std::vector<HelperPool::Job> jobs(NTA - 1);
@@ -1205,7 +1204,7 @@ int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32
     // the old vertices must keep their block indices: every old vertex that has an edge now had one before
     bool same = true;
     for (int v = 0; v < prev->nV && same; v++) same = (S.hidx[v] == prev->hidx[v]);
-    static const bool extend_on = !(getenv("CGMR_SYM_EXTEND") && atoi(getenv("CGMR_SYM_EXTEND")) == 0);
+    const bool extend_on = sw.sym_extend;
     const int n_new = nf - prev->nf;
     // edges [0, n_common) are the previous list's first n_common (default: all of it -- a grown list); the others are checked
     // against the tree one by one; edges the previous list had beyond that and this one has not are simply gone (a tree
@@ -1217,17 +1216,17 @@ int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32
         const int v = hub_vertices[k];
         if (v >= 0 && v < nV && S.hidx[v] >= 0 && std::find(fh.begin(), fh.end(), S.hidx[v]) == fh.end()) fh.push_back(S.hidx[v]);
       }
-      extended = extend_order(*prev, nf, ap, ai, order, pstart, pos_ranges, S, nE - nc, ef + nc, et + nc, S.hidx, fh);
+      extended = extend_order(*prev, nf, ap, ai, order, pstart, pos_ranges, S, nE - nc, ef + nc, et + nc, S.hidx, fh, sw);
     }
   }
   if (!extended) {
-    NDCtx C{ap, ai, order, pstart};
+    NDCtx C{ap, ai, order, pstart, sw};
     C.vs.assign(nf, NDCtx::VState{0, 0});
     C.queue.assign(nf, 0);
     C.tmp.assign(nf, 0);
     C.recs.assign(2 * (size_t)nf + 4, NDCtx::Rec());
     C.max_par_depth = NT >= 8 ? 3 : (NT >= 4 ? 2 : (NT >= 2 ? 1 : 0));
-    { static const int pd = getenv("CGMR_ND_PAR_DEPTH") ? atoi(getenv("CGMR_ND_PAR_DEPTH")) : -1; if (pd >= 0 && NT >= 2) C.max_par_depth = pd; }
+    if (sw.nd_par_depth >= 0 && NT >= 2) C.max_par_depth = sw.nd_par_depth;
     // Hubs -- vertices with far more neighbours than a pose has, i.e. the gauge vertices of the condensed stars received from
     // the peers (30-60 edges each) -- are kept out of the dissection and eliminated last, as one more piece of the root's
     // separator: left inside, a star ties the subtrees its ends lie in together, level by level (robot 0 of the eight-robot
@@ -1235,7 +1234,7 @@ int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32
     // sweeps never enter a vertex outside the range being ordered, so leaving the hubs out of the range is all it takes.
     std::vector<int32_t> hubs;
     {
-      static const int hub_min = getenv("CGMR_HUB_DEGREE") ? atoi(getenv("CGMR_HUB_DEGREE")) : 32;
+      const int hub_min = sw.hub_degree;
       const int thr = std::max(hub_min, (int)(4 * (ai.size() / (size_t)std::max(nf, 1))));
       if (hub_min > 0)
         for (int v = 0; v < nf; v++) if (ap[v + 1] - ap[v] > thr) hubs.push_back(v);
@@ -1352,7 +1351,7 @@ int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32
   std::vector<std::vector<int32_t>> kids(nfr);
   S.rows.clear();
   std::vector<uint8_t> dead(nfr, 0);
-  static const bool amalgamate = !(getenv("CGMR_AMALGAMATE") && atoi(getenv("CGMR_AMALGAMATE")) == 0);
+  const bool amalgamate = sw.amalgamate;
   struct BorderCtx {
     std::vector<int32_t> stamp, list;
     std::vector<int32_t>* rows = nullptr;    // row lists of the fronts handled in this context
@@ -1598,8 +1597,7 @@ int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32
   // ---- top block: walk down the root's chain while the columns stay consecutive and fit
   S.gn_level_ptr = S.level_ptr;
   S.gn_level_fronts = S.level_fronts;
-  static const bool top_on = !(getenv("CGMR_TOP_BLOCK") && atoi(getenv("CGMR_TOP_BLOCK")) == 0);
-  if (top_on && nfr > 0) {
+  if (sw.top_block && nfr > 0) {
     int root = nfr - 1;                                    // the last front of the elimination order
     const FrontDesc& Rt = S.fronts[root];
     if (Rt.parent < 0 && Rt.ns == 0 && Rt.level == nlev - 1 && S.level_ptr[nlev] - S.level_ptr[nlev - 1] == 1 &&

@@ -16,6 +16,8 @@
 
 namespace cgmr {
 
+struct Switches;                                           // switches.h
+
 #ifndef CGMR_PANEL_POSES
 #define CGMR_PANEL_POSES 16
 #endif
@@ -164,6 +166,7 @@ void host_run_tasks(int n, const std::function<void(int)>& task);
 // hub_vertices (nullable): vertices to keep out of the dissection and eliminate last whatever their degree (the gauge
 // vertices of the condensed stars received from the peers: every received edge has one of them at an end).
 // hooks (nullable): see AnalyzeHooks.
+// sw: the analysis switches (switches.h) -- the context's, or read_switches() where there is no context.
 struct AnalyzeHooks {
   // Called on the analysing thread once the permutation and the off-diagonal block lists are final -- S.vperm, S.off_row,
   // S.off_col, S.nf, S.nb; offbase[c] = index of column c's first block, nf + 1 entries -- i.e. before the borders, the
@@ -172,7 +175,7 @@ struct AnalyzeHooks {
   // analysis with that value.
   std::function<int(const Symbolic&, const int32_t* offbase)> blocks_ready;
 };
-int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et, Symbolic& S, Symbolic* prev = nullptr,
+int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et, Symbolic& S, const Switches& sw, Symbolic* prev = nullptr,
             int n_common = -1, const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0, const AnalyzeHooks* hooks = nullptr);
 
 // The structure arrays that only the device reads, which the device builds for itself (gn_structure.hip: k_asm_*, k_build_maps),

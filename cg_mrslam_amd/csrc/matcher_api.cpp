@@ -85,7 +85,7 @@ int setup_geometry(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, MatchParams& P
   // initializeKernel's table (scan_matcher.cpp:38-61) is K1 * sqrt(i^2 + j^2) truncated and capped: it qualifies, but the
   // property is checked on the table itself.
   {
-    static const bool edt_on = !(getenv("CGMR_MATCH_EDT") && atoi(getenv("CGMR_MATCH_EDT")) == 0);
+    const bool edt_on = ctx->sw.match_edt;
     const int dim = P.kdim, c = (dim - 1) / 2;
     bool ok = edt_on && c <= 8 && c >= 1;
     std::vector<int> by_d2(2 * c * c + 1, -1);
@@ -169,12 +169,10 @@ int match_run(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_pairs, int n_
   }
   // A handful of pairs (the reference's call shape: one closeScanMatching per key frame) leave the chip idle at one
   // workgroup per pair: up to 16 workgroups then share a pair's search angles (every split-th batch of 8 angles each)
-  static const int split_max = getenv("CGMR_MATCH_SPLIT") ? std::max(1, atoi(getenv("CGMR_MATCH_SPLIT"))) : 16;
-  P.split = std::max(1, std::min(split_max, ctx->n_cus / std::max(n_pairs, 1)));
+  P.split = std::max(1, std::min(ctx->sw.match_split, ctx->n_cus / std::max(n_pairs, 1)));
   // A caller that does not ask for the number of populated result bins (the reference only prints it,
   // scan_matcher.cpp:155-157) gets the pruned search: same winner, candidates that cannot win dropped early
-  static const bool prune_on = !(getenv("CGMR_MATCH_PRUNE") && atoi(getenv("CGMR_MATCH_PRUNE")) == 0);
-  P.prune = (prune_on && !d_nres) ? 1 : 0;
+  P.prune = (ctx->sw.match_prune && !d_nres) ? 1 : 0;
   P.sort32 = (P.n_beams < 2048 && P.sub_res > 0 && P.max_range / P.sub_res < 500.0) ? 1 : 0;
   const int n_items = n_pairs * P.split;
   int nblocks = std::min(n_items, ctx->n_cus);                    // one 160 KB-LDS workgroup per CU
@@ -207,8 +205,7 @@ int match_run(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_pairs, int n_
   const size_t merge_bytes = P.split > 1 ? (size_t)n_pairs * (match_close_max_bins() * 8 + 8) : 0;
   // the lean instances of the kernel (matcher_kernels.hip: k_match_close_batch<1 / 2>) take the shape the batch is normally run in;
   // pairs they cannot take come back on a list and go through the general kernel behind them
-  static const bool lean_on = !(getenv("CGMR_MATCH_LEAN") && atoi(getenv("CGMR_MATCH_LEAN")) == 0);
-  const bool lean = lean_on && match_close_lean_ok(P);
+  const bool lean = ctx->sw.match_lean && match_close_lean_ok(P);
   // (pairs a lean instance found slow to search are spread over kSlowSplit workgroups each, kSlowChunk pairs per launch)
   constexpr int kSlowSplit = 16, kSlowChunk = 256;
   const size_t slow_merge_bytes = lean ? (size_t)kSlowChunk * (match_close_max_bins() * 8 + 8) : 0;
@@ -244,7 +241,7 @@ int match_run(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_pairs, int n_
   // the slow pairs (the back of the list), kSlowSplit workgroups each: the single call's way of sharing a pair
   MatchParams Ps = P;
   Ps.split = kSlowSplit;
-  static const bool no_redo = getenv("CGMR_MATCH_NOREDO") && atoi(getenv("CGMR_MATCH_NOREDO")) != 0;   // (profiling the lean instance alone)
+  const bool no_redo = ctx->sw.match_noredo;                        // (profiling the lean instance alone)
   if (lean) {
     // Pairs left over (err[3]; their indices in the redo list) and pairs that are slow to search (err[8]; the back of the list): the
     // general kernel behind the lean one takes them.  Both launches are ALWAYS queued and find their list lengths on the device
@@ -565,12 +562,6 @@ int cgmr_subsample(int n, const double* pts, double res, double* out) {
 
 namespace {
 
-// CGMR_MATCH_TRACE: the generic searches print one line per stage on stderr (tools/README.md)
-bool match_trace() {
-  static const bool on = getenv("CGMR_MATCH_TRACE") != nullptr;
-  return on;
-}
-
 using Clock = std::chrono::steady_clock;
 double us_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); }
 double us_since(Clock::time_point a) { return us_between(a, Clock::now()); }
@@ -578,9 +569,10 @@ double us_since(Clock::time_point a) { return us_between(a, Clock::now()); }
 // The host's view of one search: tables made and staged, launches up to the call's one synchronisation, results decoded.
 struct StageTrace {
   Clock::time_point begin = Clock::now(), staged, back;
+  // CGMR_MATCH_TRACE: the generic searches print one line per stage on stderr (tools/README.md)
   // "<head>: stage .. us, device+sync .. us (<kernels> ..), decode .. us" -- kernels: the device time between the call's events
   void print(const cgmr_ctx* ctx, const char* kernels, const char* head_fmt, ...) const {
-    if (!match_trace()) return;
+    if (!ctx->sw.match_trace) return;
     char head[256];
     va_list ap;
     va_start(ap, head_fmt);
@@ -1228,7 +1220,7 @@ struct SetPoints {
 // 376-381).  Tasks for the helper threads: the scans of a reference set in runs of a few scans (a 21-scan set is 150 us of
 // host work in one piece), every current set with its subsample; then the runs of a set are joined in scan order and
 // thinned out (a robot that stays in the same rooms hits the same cells again and again: 13k points -> 600).
-void prepare_scan_sets(const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets, const cgmr_scan_set* cur_sets,
+void prepare_scan_sets(const cgmr_ctx* ctx, const cgmr_matcher_config* cfg, int n_jobs, const cgmr_scan_set* ref_sets, const cgmr_scan_set* cur_sets,
                        SetPoints& pts) {
   pts.ref.assign(n_jobs, {}); pts.qry.assign(n_jobs, {}); pts.ref_alias.assign(n_jobs, 0);
   for (int j = 0; j < n_jobs; j++) {
@@ -1268,7 +1260,7 @@ void prepare_scan_sets(const cgmr_matcher_config* cfg, int n_jobs, const cgmr_sc
     for (const Run& r : runs) if (r.job == j) pts.ref[j].insert(pts.ref[j].end(), r.pts.begin(), r.pts.end());
     keep_first_point_per_cell(cfg, pts.ref[j], ref_sets[j].n_scans > kRun ? 0 : 2048);
   });
-  if (match_trace())
+  if (ctx->sw.match_trace)
     fprintf(stderr, "[sets] %d runs + %d current sets %.0f us, join + thin out %.0f us\n", n_runs, n_jobs, us_runs, us_since(ta) - us_runs);
 }
 
@@ -1416,7 +1408,7 @@ int hierarchical_batch_dev(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const 
   trace.back = Clock::now();
   if (rc) return rc;
   if (reinterpret_cast<const int*>(h + h_back)[8] != 0) {     // a job outgrew its slices: level by level instead
-    if (match_trace()) fprintf(stderr, "[hier] %d jobs, %d levels: table slices too small, level by level\n", nj, n_levels);
+    if (ctx->sw.match_trace) fprintf(stderr, "[hier] %d jobs, %d levels: table slices too small, level by level\n", nj, n_levels);
     return CGMR_OK;
   }
   const int* counts = reinterpret_cast<const int*>(h + h_back + 256);
@@ -1440,8 +1432,7 @@ int hierarchical_batch_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, const
                             double max_score, double dx, double dy, double dth, int n_levels,
                             std::vector<std::vector<cgmr_match_result>>& out) {
   const int nj = (int)jobs0.size();
-  static const bool host_loop = getenv("CGMR_HIER_HOST") && atoi(getenv("CGMR_HIER_HOST")) != 0;
-  if (!host_loop) {                                          // the levels chained on the device
+  if (!ctx->sw.hier_host) {                                          // the levels chained on the device
     bool done = false;
     int rc = hierarchical_batch_dev(ctx, cfg, jobs0, theta_res, max_score, dx, dy, dth, n_levels, out, done);
     if (rc || done) return rc;
@@ -1898,7 +1889,7 @@ static int scan_matching_lc_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, 
   struct Key { int a, b, c; bool operator<(const Key& o) const { return a != o.a ? a < o.a : (b != o.b ? b < o.b : c < o.c); } };
   SetPoints pts;
   std::vector<std::vector<float>> regions(n_jobs), regionspi(n_jobs);
-  prepare_scan_sets(cfg, n_jobs, ref_sets, cur_sets, pts);
+  prepare_scan_sets(ctx, cfg, n_jobs, ref_sets, cur_sets, pts);
   for (int j = 0; j < n_jobs; j++) {
     const cgmr_scan_set* S = ref_sets + j;
     const Se2 refp = se2_of(S->poses_xyt + 3 * (size_t)S->ref_index);
@@ -2017,7 +2008,7 @@ static int global_matching_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, i
   const float region[6] = {-10.f, -5.f, -pi_f, 10.f, 5.f, pi_f};                   // scan_matcher.cpp:383-391
   const auto t_begin = Clock::now();
   SetPoints pts;
-  prepare_scan_sets(cfg, n_jobs, ref_sets, cur_sets, pts);
+  prepare_scan_sets(ctx, cfg, n_jobs, ref_sets, cur_sets, pts);
   const double us_sets = us_since(t_begin);
   std::vector<SearchJob> jobs(n_jobs);
   for (int j = 0; j < n_jobs; j++) jobs[j] = pts.job(j, region, 1);
@@ -2025,7 +2016,7 @@ static int global_matching_core(cgmr_ctx* ctx, const cgmr_matcher_config* cfg, i
   const auto t_hier = Clock::now();
   rc = hierarchical_batch_core(ctx, cfg, jobs, 0.025, max_score, 0.5, 0.5, 0.2, 4, res);
   if (rc) return rc;
-  if (match_trace())
+  if (ctx->sw.match_trace)
     fprintf(stderr, "[global] %d jobs: points + subsample (helper threads) %.0f us, hierarchy %.0f us, total %.0f us\n", n_jobs, us_sets,
             us_since(t_hier), us_since(t_begin));
   write_best(res, trel_out, found_out);
@@ -2086,7 +2077,7 @@ int cgmr_scan_matching_lc_hierarchical_batch(cgmr_ctx* ctx, const cgmr_matcher_c
   int rc = check_set_batch(ctx, "cgmr_scan_matching_lc_hierarchical", cfg, n_jobs, ref_sets, cur_sets, trel_out, found_out);
   if (rc) return rc;
   SetPoints pts;
-  prepare_scan_sets(cfg, n_jobs, ref_sets, cur_sets, pts);
+  prepare_scan_sets(ctx, cfg, n_jobs, ref_sets, cur_sets, pts);
   std::vector<std::vector<float>> regions(n_jobs);
   std::vector<SearchJob> jobs(n_jobs);
   for (int j = 0; j < n_jobs; j++) {

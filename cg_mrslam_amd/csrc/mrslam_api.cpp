@@ -1042,7 +1042,7 @@ void cond_fill_stage(CondBatch& B) {
   const int nV = B.nV, nA = B.nA, nf = B.nf, maxq = B.maxq;
   char* h = B.hstage;
   const double tg0 = wall_s();
-  static const bool cached_walk = !(getenv("CGMR_GUESS_CACHED") && atoi(getenv("CGMR_GUESS_CACHED")) == 0);
+  const bool cached_walk = B.ctx->sw.guess_cached;
   // (the general form walks an edge list: the kept own edges, in their order)
   std::vector<int32_t> kept_ef, kept_et;
   std::vector<double> kept_meas;
@@ -1211,8 +1211,7 @@ int run_cond_jobs(cgmr_graph* g, std::vector<CondJob>& jobs, bool to_wire, std::
   if (async_out) *async_out = false;
   if (jobs.empty()) return 0;
   CondBatch B(g, jobs, to_wire);
-  static const bool trace = getenv("CGMR_COND_TRACE") != nullptr;
-  B.trace = trace;
+  B.trace = ctx->sw.cond_trace;
   B.t0 = wall_s();
   int rc = cond_setup(B);
   if (rc) return rc;

@@ -47,7 +47,7 @@ Rccl& rccl() {
     // 1. a copy that is already in the process (PyTorch's), 2. the library path the caller names, 3. the system one
     const char* names[] = {"librccl.so", "librccl.so.1"};
     for (const char* n : names) if (!r.handle) r.handle = dlopen(n, RTLD_NOW | RTLD_NOLOAD | RTLD_GLOBAL);
-    if (!r.handle && getenv("CGMR_RCCL_LIB")) r.handle = dlopen(getenv("CGMR_RCCL_LIB"), RTLD_NOW | RTLD_GLOBAL);
+    if (!r.handle && cgmr::process_switches().rccl_lib) r.handle = dlopen(cgmr::process_switches().rccl_lib, RTLD_NOW | RTLD_GLOBAL);
     for (const char* n : names) if (!r.handle) r.handle = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
     if (!r.handle) r.handle = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
     if (!r.handle) return r;

@@ -516,6 +516,14 @@ int cgmr_symbolic_cache_stats3(const cgmr_ctx* ctx, int64_t out[3]);
  * with one backward launch per tree level (no in-kernel waits) and returns CGMR_OK; the batched condensed-graph /
  * marginals paths return CGMR_E_TIMEOUT.  cgmr_gn_timeouts: how often that has happened on this context.           */
 int64_t cgmr_gn_timeouts(const cgmr_ctx* ctx);
+/* The environment switches (same ABI version: callers find the entry point by its symbol).  A context reads every
+ * context-scoped CGMR_* variable once, when it is created, and works by those values for its whole life; the process-scoped
+ * ones (the host threads, the RCCL library) are read once per process.  cgmr_switches writes one line per switch into buf,
+ * "name<TAB>scope<TAB>value<TAB>effect\n", scope = context or process, a flag's value 0 or 1, a path that is not set empty:
+ * with a context the values it holds (and the process' own for the process-scoped ones), with a null context the defaults.
+ * Returns the bytes the whole listing needs, the terminating zero included; buf (cap bytes, may be null with cap 0) holds as
+ * much of it as fits, terminated.  tools/README.md has the table.                                                       */
+int cgmr_switches(const cgmr_ctx* ctx_or_null, char* buf, int cap);
 
 /* The host threads behind the symbolic analysis (no reference counterpart: g2o's analysis is one thread).
  * out[0] = threads an analysis uses, the caller included (CGMR_HOST_THREADS, default by core count); out[1] = 1 if the

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "gn_symbolic.h"
+#include "switches.h"
 
 using cgmr::FrontDesc;
 using cgmr::Symbolic;
@@ -123,7 +124,7 @@ void check(const std::string& name, const Symbolic& S, int nV, int nE, const int
 
 void run(const std::string& name, const Graph& g, const std::vector<int32_t>& hubs = {}) {
   Symbolic S;
-  const int rc = cgmr::analyze(g.nV, nullptr, (int)g.ef.size(), g.ef.data(), g.et.data(), S, nullptr, -1, hubs.empty() ? nullptr : hubs.data(), (int)hubs.size());
+  const int rc = cgmr::analyze(g.nV, nullptr, (int)g.ef.size(), g.ef.data(), g.et.data(), S, cgmr::read_switches(), nullptr, -1, hubs.empty() ? nullptr : hubs.data(), (int)hubs.size());
   if (rc) { fprintf(stderr, "FAIL %s: analyze returned %d\n", name.c_str(), rc); n_fail++; return; }
   check(name, S, g.nV, (int)g.ef.size(), g.ef.data(), g.et.data());
 }
@@ -132,12 +133,12 @@ void run(const std::string& name, const Graph& g, const std::vector<int32_t>& hu
 void run_grown(const std::string& name, const Graph& g, int nV0, int step) {
   Symbolic S;
   int nV = nV0, n_ext = 0;
-  if (cgmr::analyze(nV, nullptr, g.edges_at[nV], g.ef.data(), g.et.data(), S)) { fprintf(stderr, "FAIL %s: first analysis\n", name.c_str()); n_fail++; return; }
+  if (cgmr::analyze(nV, nullptr, g.edges_at[nV], g.ef.data(), g.et.data(), S, cgmr::read_switches())) { fprintf(stderr, "FAIL %s: first analysis\n", name.c_str()); n_fail++; return; }
   check(name + " @" + std::to_string(nV), S, nV, g.edges_at[nV], g.ef.data(), g.et.data());
   while (nV < g.nV) {
     nV = std::min(g.nV, nV + step);
     Symbolic old = std::move(S);
-    if (cgmr::analyze(nV, nullptr, g.edges_at[nV], g.ef.data(), g.et.data(), S, &old)) { fprintf(stderr, "FAIL %s: analysis at %d\n", name.c_str(), nV); n_fail++; return; }
+    if (cgmr::analyze(nV, nullptr, g.edges_at[nV], g.ef.data(), g.et.data(), S, cgmr::read_switches(), &old)) { fprintf(stderr, "FAIL %s: analysis at %d\n", name.c_str(), nV); n_fail++; return; }
     n_ext += S.extended ? 1 : 0;
     check(name + " @" + std::to_string(nV), S, nV, g.edges_at[nV], g.ef.data(), g.et.data());
   }
@@ -196,8 +197,7 @@ Graph pose_graph(int V, int closures_per_100, uint64_t seed) {
 }  // namespace
 
 int main() {
-  const char* nt = getenv("CGMR_HOST_THREADS");
-  printf("symbolic_sweep: CGMR_HOST_THREADS=%s\n", nt ? nt : "(unset)");
+  printf("symbolic_sweep: CGMR_HOST_THREADS=%d\n", cgmr::process_switches().host_threads);
   for (int n = 2; n <= 71; n++) run("clique_" + std::to_string(n), clique(n));
   for (int b = 1; b <= 54; b++) run("blobs_" + std::to_string(b), blobs(b, 16, 4));
   for (int k : {2, 9}) for (int n = 17; n <= 64; n++) run("forest" + std::to_string(k) + "_" + std::to_string(n), forest(k, n));

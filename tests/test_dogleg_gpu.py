@@ -1,9 +1,5 @@
 """Dogleg on the device (cgmr_dl_optimize, Context.dl_optimize, GraphSLAM(algorithm="dl"), RobotGraph.set_algorithm("dl"))
 against the float64 reference of the contract, tests/ref_dogleg.py."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
@@ -11,6 +7,7 @@ import ref_dogleg
 import ref_numpy as R
 import ref_robust as RR
 import reference_cases as C
+from switch_contexts import assert_launch_shape, context_under
 from test_dogleg_cpu import FIXED, EF, ET, INFO, MEAS
 from test_lm_cpu import EXTRA_CASES
 from test_lm_gpu import rounding_floor
@@ -276,34 +273,18 @@ def test_robust_dogleg_matches_reference(ctx, name):
     assert np.allclose(s.graph.poses, p, rtol=0, atol=1e-9) and np.allclose(s.edgeWeights(), w, rtol=1e-9, atol=1e-300)
 
 
-_CHILD = r"""
-import sys, numpy as np
-sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
-import reference_cases as C
-from test_lm_cpu import EXTRA_CASES
-from cg_mrslam_amd import Context
-ctx = Context(0)
-out = {{}}
-for name, kw in {runs!r}:
-    g = EXTRA_CASES[name][0]() if name in EXTRA_CASES else C.CASES[name][0]()
-    rc, poses, chi, dlt, tri, stp, done = ctx.dl_optimize(*C.args(g), {iters}, **kw)
-    out[name + "_chi"] = chi; out[name + "_dlt"] = dlt; out[name + "_tri"] = tri; out[name + "_stp"] = stp
-    out[name + "_done"] = np.array([done, rc])
-ctx.close()
-np.savez({path!r}, **out)
-"""
+LEVELWISE = {"CGMR_FWD_MERGE": "0", "CGMR_BWD_CHAIN": "0"}
 
 
-def test_one_launch_per_level_gives_the_same_trace(ctx, tmp_path):
+def test_one_launch_per_level_gives_the_same_trace(ctx):
     runs = [("pg2500", dict(initial_delta=1.0)), ("pg9000", {}), ("lat80", dict(initial_delta=1.0)), ("hub100", {}),
             ("bad_start", {})]
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    path = str(tmp_path / "levelwise.npz")
-    code = _CHILD.format(root=root, tests=os.path.join(root, "tests"), runs=runs, iters=ITERS, path=path)
-    env = dict(os.environ, CGMR_FWD_MERGE="0", CGMR_BWD_CHAIN="0")
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    z = np.load(path)
+    z = {}
+    with context_under(LEVELWISE) as c:
+        assert_launch_shape(c, LEVELWISE, C.args(graph(runs[0][0])))
+        for name, kw in runs:
+            rc, _, chi, dlt, tri, stp, done = c.dl_optimize(*C.args(graph(name)), ITERS, **kw)
+            z.update({name + "_chi": chi, name + "_dlt": dlt, name + "_tri": tri, name + "_stp": stp, name + "_done": np.array([done, rc])})
     for name, kw in runs:
         g = graph(name)
         rc, _, chi, dlt, tri, stp, done = ctx.dl_optimize(*C.args(g), ITERS, **kw)
@@ -319,23 +300,23 @@ def test_one_launch_per_level_gives_the_same_trace(ctx, tmp_path):
 def test_a_timed_out_head_is_repeated_one_launch_per_level():
     """A bounded device-side wait that runs out in a head (forced: CGMR_BWD_SPIN_LIMIT=1, one poll per wait) is no verdict:
     the call goes on with one launch per kernel and level and gives the plain call's trace; the context counts the event
-    and the next call runs the merged and chained launches again.  bad_start: trials are rejected and the plain call takes
-    several rounds, so the repeated call passes through every part of the round loop."""
+    and the next call runs the merged and chained launches again (on this context their waits run out again, and that call
+    recovers the same way).  The switch belongs to the context: the plain call has a context of its own.  bad_start: trials
+    are rejected and the plain call takes several rounds, so the repeated call passes through every part of the round loop."""
     from cg_mrslam_amd import Context
     name = "bad_start"
     g, iters = graph(name), CASES[name][1]
     ref = ref_dogleg.dl_optimize(*C.args(g), iters)
-    c = Context(0)
+    c0 = Context(0)
     try:
-        first = c.dl_optimize(*C.args(g), iters)
-        plain = c.dl_last_stats()
-        assert first[0] == 0 and c.gn_timeouts() == 0
-        assert plain["host_waits"] > 1 and any(t > 1 for t in first[4]), (name, plain, "the case rejects nothing")
-        os.environ["CGMR_BWD_SPIN_LIMIT"] = "1"
-        try:
-            rc, _, chi, dlt, tri, stp, done = c.dl_optimize(*C.args(g), iters)
-        finally:
-            del os.environ["CGMR_BWD_SPIN_LIMIT"]
+        first = c0.dl_optimize(*C.args(g), iters)
+        plain = c0.dl_last_stats()
+        assert first[0] == 0 and c0.gn_timeouts() == 0
+    finally:
+        c0.close()
+    assert plain["host_waits"] > 1 and any(t > 1 for t in first[4]), (name, plain, "the case rejects nothing")
+    with context_under({"CGMR_BWD_SPIN_LIMIT": "1"}) as c:
+        rc, _, chi, dlt, tri, stp, done = c.dl_optimize(*C.args(g), iters)
         print(name, "plain", plain, "forced", c.dl_last_stats(), "timeouts", c.gn_timeouts(), "trials", tri, first[4], "steps", stp, first[5])
         print(name, "chi", np.abs(chi - first[2]) / np.abs(first[2]), "delta", np.abs(dlt - first[3]) / np.maximum(first[3], 1e-300))
         assert rc == 0
@@ -346,11 +327,12 @@ def test_a_timed_out_head_is_repeated_one_launch_per_level():
         assert np.allclose(dlt[:k], first[3][:k], rtol=VARIANT_RTOL, atol=0)
         assert np.allclose(chi[:k + 1], first[2][:k + 1], rtol=VARIANT_RTOL, atol=1e3 * U * chi[0])
         assert check_trace(name, ref, chi, dlt, tri, stp, done, rounding_floor(g)) >= 1
-        again = c.dl_optimize(*C.args(g), iters)
-        for u, v in zip(first, again):
-            assert np.array_equal(np.asarray(u), np.asarray(v))
-    finally:
-        c.close()
+        t1 = c.gn_timeouts()
+        rc, _, chi, dlt, tri, stp, done = c.dl_optimize(*C.args(g), iters)
+        assert rc == 0 and c.gn_timeouts() > t1
+        assert done == first[6] and np.array_equal(tri, first[4]) and np.array_equal(stp, first[5]), (tri, first[4], stp, first[5])
+        assert np.allclose(dlt[:k], first[3][:k], rtol=VARIANT_RTOL, atol=0)
+        assert np.allclose(chi[:k + 1], first[2][:k + 1], rtol=VARIANT_RTOL, atol=1e3 * U * chi[0])
 
 
 def test_robot_graph_dogleg_matches_reference():

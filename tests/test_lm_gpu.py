@@ -1,9 +1,5 @@
 """Levenberg-Marquardt on the device (cgmr_lm_optimize, Context.lm_optimize, GraphSLAM(algorithm="levenberg"),
 RobotGraph.set_algorithm) against the float64 reference of the contract, tests/ref_lm.py."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -11,6 +7,7 @@ import scipy.sparse as sp
 import ref_lm
 import ref_numpy as R
 import reference_cases as C
+from switch_contexts import assert_launch_shape, context_under
 from test_lm_cpu import EXTRA_CASES
 
 pytestmark = pytest.mark.gpu
@@ -200,60 +197,44 @@ def test_graph_slam_levenberg(ctx):
     assert np.allclose(s.last_chi2, ref["chi2"], rtol=RTOL, atol=0)
 
 
-_CHILD = r"""
-import sys, numpy as np
-sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
-import reference_cases as C
-from test_lm_cpu import EXTRA_CASES
-from cg_mrslam_amd import Context
-ctx = Context(0)
-out = {{}}
-for name in {names!r}:
-    g = EXTRA_CASES[name][0]() if name in EXTRA_CASES else C.CASES[name][0]()
-    iters = EXTRA_CASES[name][1] if name in EXTRA_CASES else {iters}
-    rc, poses, chi, lam, tri, done = ctx.lm_optimize(*C.args(g), iters)
-    out[name + "_chi"] = chi; out[name + "_lam"] = lam; out[name + "_tri"] = tri; out[name + "_done"] = np.array([done, rc])
-ctx.close()
-np.savez({path!r}, **out)
-"""
+LEVELWISE = {"CGMR_FWD_MERGE": "0", "CGMR_BWD_CHAIN": "0"}
 
 
-def test_one_launch_per_level_gives_the_same_trace(ctx, tmp_path):
+def test_one_launch_per_level_gives_the_same_trace(ctx):
     names = ["pg2500", "pg9000", "lat80", "hub100", "bad_start"]
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    path = str(tmp_path / "levelwise.npz")
-    code = _CHILD.format(root=root, tests=os.path.join(root, "tests"), names=names, iters=ITERS, path=path)
-    env = dict(os.environ, CGMR_FWD_MERGE="0", CGMR_BWD_CHAIN="0")
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    z = np.load(path)
+    z = {}
+    with context_under(LEVELWISE) as c:
+        assert_launch_shape(c, LEVELWISE, C.args(graph(names[0])))
+        for name in names:
+            z[name] = c.lm_optimize(*C.args(graph(name)), CASES[name][1])
     for name in names:
         g, iters = graph(name), CASES[name][1]
         rc, _, chi, lam, tri, done = ctx.lm_optimize(*C.args(g), iters)
-        assert z[name + "_done"].tolist() == [done, rc] and np.array_equal(z[name + "_tri"], tri), name
-        assert np.allclose(z[name + "_lam"], lam, rtol=RTOL, atol=0) and np.allclose(z[name + "_chi"], chi, rtol=RTOL, atol=0), name
+        z_rc, _, z_chi, z_lam, z_tri, z_done = z[name]
+        assert [z_done, z_rc] == [done, rc] and np.array_equal(z_tri, tri), name
+        assert np.allclose(z_lam, lam, rtol=RTOL, atol=0) and np.allclose(z_chi, chi, rtol=RTOL, atol=0), name
 
 
 def test_a_timed_out_trial_is_repeated_one_launch_per_level():
     """A bounded device-side wait that runs out in a trial (forced: CGMR_BWD_SPIN_LIMIT=1, one poll per wait) is no verdict:
     the call goes on with one launch per kernel and level and gives the plain call's trace; the context counts the event
-    and the next call runs the merged and chained launches again.  bad_start: trials are rejected and the plain call takes
-    several rounds, so the repeated call passes through every part of the round loop."""
+    and the next call runs the merged and chained launches again (on this context their waits run out again, and that call
+    recovers the same way).  The switch belongs to the context: the plain call has a context of its own.  bad_start: trials
+    are rejected and the plain call takes several rounds, so the repeated call passes through every part of the round loop."""
     from cg_mrslam_amd import Context
     name = "bad_start"
     g, iters = graph(name), CASES[name][1]
     ref = ref_lm.lm_optimize(*C.args(g), iters)
-    c = Context(0)
+    c0 = Context(0)
     try:
-        first = c.lm_optimize(*C.args(g), iters)
-        plain = c.lm_last_stats()
-        assert first[0] == 0 and c.gn_timeouts() == 0
-        assert plain["host_waits"] > 1 and any(t > 1 for t in first[4]), (name, plain, "the case rejects nothing")
-        os.environ["CGMR_BWD_SPIN_LIMIT"] = "1"
-        try:
-            rc, _, chi, lam, tri, done = c.lm_optimize(*C.args(g), iters)
-        finally:
-            del os.environ["CGMR_BWD_SPIN_LIMIT"]
+        first = c0.lm_optimize(*C.args(g), iters)
+        plain = c0.lm_last_stats()
+        assert first[0] == 0 and c0.gn_timeouts() == 0
+    finally:
+        c0.close()
+    assert plain["host_waits"] > 1 and any(t > 1 for t in first[4]), (name, plain, "the case rejects nothing")
+    with context_under({"CGMR_BWD_SPIN_LIMIT": "1"}) as c:
+        rc, _, chi, lam, tri, done = c.lm_optimize(*C.args(g), iters)
         print(name, "plain", plain, "forced", c.lm_last_stats(), "timeouts", c.gn_timeouts(), "trials", tri, first[4])
         print(name, "chi", np.abs(chi - first[2]) / np.abs(first[2]), "lambda", np.abs(lam - first[3]) / np.maximum(first[3], 1e-300))
         assert rc == 0
@@ -261,11 +242,11 @@ def test_a_timed_out_trial_is_repeated_one_launch_per_level():
         assert done == first[5] and np.array_equal(tri, first[4]), (tri, first[4])
         assert np.allclose(lam, first[3], rtol=RTOL, atol=0) and np.allclose(chi, first[2], rtol=RTOL, atol=0)
         assert check_trace(name, ref, chi, lam, tri, done, rounding_floor(g)) >= 1
-        again = c.lm_optimize(*C.args(g), iters)
-        for u, v in zip(first, again):
-            assert np.array_equal(np.asarray(u), np.asarray(v))
-    finally:
-        c.close()
+        t1 = c.gn_timeouts()
+        rc, _, chi, lam, tri, done = c.lm_optimize(*C.args(g), iters)
+        assert rc == 0 and c.gn_timeouts() > t1
+        assert done == first[5] and np.array_equal(tri, first[4]), (tri, first[4])
+        assert np.allclose(lam, first[3], rtol=RTOL, atol=0) and np.allclose(chi, first[2], rtol=RTOL, atol=0)
 
 
 def test_robot_graph_levenberg_matches_reference():

@@ -220,21 +220,14 @@ def test_pruned_search_returns_the_exhaustive_winner(ctx, oracle):
 def test_fallback_rasteriser_and_exhaustive_search_match_the_golden_fixture():
     """The library read with CGMR_MATCH_EDT=0 CGMR_MATCH_PRUNE=0 (compare-and-swap stamping instead of the distance
     transform, every candidate evaluated): the paths grids with overflow tiles, unusual kernels and bin counts fall back
-    to must stay bit-identical too.  The switches are read once per process, hence the child."""
-    import subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = (
-        "import os, numpy as np\n"
-        "from cg_mrslam_amd import Context\n"
-        "from cg_mrslam_amd.matcher import ScanMatcher\n"
-        "d = np.load(os.path.join('tests', 'golden', 'match_close12.npz'))\n"
-        "m = ScanMatcher(Context(0), d['ranges_ref'].shape[1], float(d['angle_min']), float(d['angle_inc']), float(d['max_range']))\n"
-        "f, x, s = m.closeScanMatching(d['ranges_ref'], d['ranges_qry'], d['guess'])\n"
-        "assert np.array_equal(f, d['found'].astype(bool)) and np.array_equal(x, d['xyt']) and np.array_equal(s, d['score'])\n"
-        "print('fallback ok')\n")
-    env = dict(os.environ, CGMR_MATCH_EDT="0", CGMR_MATCH_PRUNE="0", PYTHONPATH=root)
-    r = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "fallback ok" in r.stdout, r.stderr[-2000:]
+    to must stay bit-identical too.  A context reads the switches when it is created, hence a context of its own."""
+    from cg_mrslam_amd.matcher import ScanMatcher
+    from switch_contexts import context_under
+    d = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "match_close12.npz"))
+    with context_under({"CGMR_MATCH_EDT": "0", "CGMR_MATCH_PRUNE": "0"}) as c:
+        m = ScanMatcher(c, d["ranges_ref"].shape[1], float(d["angle_min"]), float(d["angle_inc"]), float(d["max_range"]))
+        f, x, s = m.closeScanMatching(d["ranges_ref"], d["ranges_qry"], d["guess"])
+    assert np.array_equal(f, d["found"].astype(bool)) and np.array_equal(x, d["xyt"]) and np.array_equal(s, d["score"])
 
 
 def test_rejects_bad_configuration(ctx):
@@ -319,8 +312,9 @@ def test_hierarchical_and_global_matching(ctx, oracle):
 def test_level_loop_on_the_device_and_level_by_level(ctx, oracle):
     """hierarchicalSearch's levels run back to back on the device (k_hier_next makes a level's regions from the results of the
     one before); a search with more than 256 results on a level outgrows the device tables and is served level by level with
-    the tables made on the host.  Both against the oracle, and the device loop against the host loop of another process."""
-    import subprocess, sys, os, json
+    the tables made on the host.  Both against the oracle, and the device loop against the host loop of a context created
+    under CGMR_HIER_HOST=1."""
+    from switch_contexts import context_under
     sp = synth.make_scan_pairs(2, seed=77)
     m = _lc(ctx, sp)
     ref = m.cartesian(sp["ranges_ref"][0])
@@ -333,16 +327,10 @@ def test_level_loop_on_the_device_and_level_by_level(ctx, oracle):
         assert len(got) == n and np.array_equal(got, want), (levels, max_score, len(got), n)
         counts[(levels, max_score)] = n
     assert 256 < counts[(3, 0.45)] <= 4096                        # (cannot have stayed in the device tables; the oracle wrapper holds 4096 rows)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import numpy as np, json\nfrom cg_mrslam_amd import Context, synth\nfrom tests.test_matcher_gpu import _lc\n"
-            "ctx = Context(0)\nsp = synth.make_scan_pairs(2, seed=77)\nm = _lc(ctx, sp)\n"
-            "ref = m.cartesian(sp['ranges_ref'][0]); q = m.subsample(m.cartesian(sp['ranges_qry'][0]))\n"
-            "region = np.array([[-6, -4, np.float32(-np.pi), 6, 4, np.float32(np.pi)]], dtype=np.float32)\n"
-            "print(json.dumps(np.asarray(m.hierarchicalSearch(ref, q, region, 0.025, 0.25, 0.5, 0.5, 0.2, 4)).tolist()))\n")
-    r = subprocess.run([sys.executable, "-c", code], cwd=root, env=dict(os.environ, PYTHONPATH=root, CGMR_HIER_HOST="1"),
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-1500:]
-    host = np.array(json.loads(r.stdout.strip().splitlines()[-1]))
+    with context_under({"CGMR_HIER_HOST": "1"}) as c:
+        mh = _lc(c, sp)
+        host = np.asarray(mh.hierarchicalSearch(mh.cartesian(sp["ranges_ref"][0]), mh.subsample(mh.cartesian(sp["ranges_qry"][0])),
+                                                region, 0.025, 0.25, 0.5, 0.5, 0.2, 4))
     dev = np.asarray(m.hierarchicalSearch(ref, q, region, 0.025, 0.25, 0.5, 0.5, 0.2, 4))
     assert host.shape == dev.shape and np.array_equal(host.reshape(dev.shape), dev)
 
@@ -362,8 +350,8 @@ def test_level_by_level_batch_with_a_job_that_dies(ctx, oracle):
       * at least one job has none: job 2's current scan is all at max range, so it dies at the first level while the others
         go on -- the level-by-level loop's alive / who[q] -> j bookkeeping with a batch.
     Both conditions are asserted from the oracle's counts.  Per job the batch equals the single globalMatching call and the
-    first row of the oracle's hierarchical_search bit for bit, and the same batch in a process with CGMR_HIER_HOST=1."""
-    import subprocess, sys, os, json
+    first row of the oracle's hierarchical_search bit for bit, and the same batch on a context created under CGMR_HIER_HOST=1."""
+    from switch_contexts import context_under
     seed, max_score = 77, 0.4
     sp = synth.make_scan_pairs(3, seed=seed)
     m = _lc(ctx, sp)
@@ -386,20 +374,13 @@ def test_level_by_level_batch_with_a_job_that_dies(ctx, oracle):
         assert found == ok1 == (counts[j] > 0), (j, found, ok1, counts[j])
         if found:
             assert np.array_equal(trel, trel1) and np.array_equal(trel, first[j]), (j, trel, trel1, first[j])
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import json\nfrom cg_mrslam_amd import Context, synth\nfrom tests.test_matcher_gpu import _lc, _global_batch_jobs\n"
-            f"ctx = Context(0)\nsp = synth.make_scan_pairs(3, seed={seed})\nm = _lc(ctx, sp)\n"
-            f"res = m.globalMatchingBatch(_global_batch_jobs(sp), {max_score})\n"
-            "print(json.dumps([[bool(f), None if t is None else [float(v).hex() for v in t]] for f, t in res]))\n")
-    r = subprocess.run([sys.executable, "-c", code], cwd=root, env=dict(os.environ, PYTHONPATH=root, CGMR_HIER_HOST="1"),
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-1500:]
-    host = json.loads(r.stdout.strip().splitlines()[-1])
+    with context_under({"CGMR_HIER_HOST": "1"}) as c:
+        host = _lc(c, sp).globalMatchingBatch(_global_batch_jobs(sp), max_score)
     assert len(host) == 3
     for (found, trel), (hf, ht) in zip(batch, host):
         assert found == hf
         if found:
-            assert np.array_equal(trel, np.array([float.fromhex(v) for v in ht]))
+            assert np.array_equal(trel, ht)
 
 
 def test_scan_matching_lc_multi_scan_reference_set(ctx, oracle):

@@ -4,9 +4,6 @@ they discriminate): every Gauss-Newton step's componentwise backward error again
 launch variants; marginal blocks against refined columns of H^-1 (ref_numpy.marginal_blocks_ref), each by its own norm; the
 condensed graph against the numpy unscented labelling; and the marginal path's recovery from a bounded wait that ran out."""
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,6 +14,8 @@ from reference_cases import EST_ATOL, EST_OWN_ATOL_BATCH, INFO_RTOL, OMEGA_MAX, 
 from reference_cases import check_labels_on_own_step as _check_labels_on_own_step
 from cg_mrslam_amd import synth
 from cg_mrslam_amd._lib import gn_symbolic_info
+from switch_contexts import assert_launch_shape, context_under
+from switch_contexts import launch_counts as _launches
 
 pytestmark = pytest.mark.gpu
 
@@ -30,25 +29,8 @@ TOP_MAX_COLS = 128     # kTopMaxCols (gn_symbolic.h): scalar columns of the top 
 @pytest.fixture(scope="module")
 def ctx_resident_only():
     """A context that merges only the level launches that are certainly resident (CGMR_FWD_MERGE_ANY=0, read at creation)."""
-    from cg_mrslam_amd import Context
-    os.environ["CGMR_FWD_MERGE_ANY"] = "0"
-    try:
-        c = Context(0)
-    finally:
-        del os.environ["CGMR_FWD_MERGE_ANY"]
-    return c
-
-
-def _launches(c, a):
-    """Launches of one Gauss-Newton pass by class (profiling mode counts them)."""
-    c.set_profiling(True)
-    try:
-        rc, _, _ = c.gn_optimize(*a, 1)
-        assert rc == 0
-        t = c.gn_kernel_times()
-    finally:
-        c.set_profiling(False)
-    return {k: v[1] for k, v in t.items()}
+    with context_under({"CGMR_FWD_MERGE_ANY": "0"}) as c:
+        yield c
 
 
 def _branch(name, g, ctx, ctx_resident_only):
@@ -143,49 +125,27 @@ VARIANTS = (("default", {}), ("separate_launches", {"CGMR_FWD_MERGE": "0"}), ("c
             ("bwd_levelwise", {"CGMR_BWD_CHAIN": "0"}), ("no_amalgamation", {"CGMR_AMALGAMATE": "0"}))
 VARIANT_CASES = (("pg2500", 3), ("pg9000", 6), ("lat80", 3), ("hub100", 3))
 
-_CHILD = """import sys; sys.path[:0] = [{root!r}, {tests!r}]
-import numpy as np
-import reference_cases as C
-from cg_mrslam_amd import Context
-c = Context(0)
-out = {{}}
-for name, iters in {cases!r}:
-    g = C.CASES[name][0]()
-    a = C.args(g)
-    p = g["poses"]
-    ps = [p]
-    for it in range(iters):
-        rc, p, _ = c.gn_optimize(p, *a[1:], 1)
-        assert rc == 0, (name, it, rc)
-        ps.append(p)
-    out[name] = np.stack(ps)
-out["timeouts"] = np.array(c.gn_timeouts())
-np.savez({path!r}, **out)
-print("DONE")
-"""
-
-
-def test_launch_variants_backward_error(tmp_path):
-    """Every switch that changes the factorisation's shape, one child process at a time (they are read once per process):
+def test_launch_variants_backward_error():
+    """Every switch that changes the factorisation's shape, one context at a time (a context reads them when it is created):
     each step's backward error, on graphs whose tree fits the resident workgroups and on ones that do not, a lattice with
-    wide borders and a hub with > 64 children.  (CGMR_GRAPH is left out: it replays a captured graph.)"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    tests = os.path.join(root, "tests")
+    wide borders and a hub with > 64 children.  Each variant's context holds its switches, and its launches show them.
+    (CGMR_GRAPH is left out: it replays a captured graph.)"""
     graphs = {name: C.CASES[name][0]() for name, _ in VARIANT_CASES}
     report = {}
     for vname, env in VARIANTS:
-        path = str(tmp_path / f"{vname}.npz")
-        code = _CHILD.format(root=root, tests=tests, cases=VARIANT_CASES, path=path)
-        r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0 and "DONE" in r.stdout, (vname, r.stderr[-2000:])
-        d = np.load(path)
-        assert int(d["timeouts"]) == 0, vname
-        for name, iters in VARIANT_CASES:
-            g = graphs[name]
-            ps = d[name]
-            ws = [R.step_backward_error(ps[i], ps[i + 1], *C.args(g)[1:]) for i in range(iters)]
-            report[(vname, name)] = [round(w / R.U, 1) for w in ws]
-            assert max(ws) <= OMEGA_MAX, (vname, name, report[(vname, name)])
+        with context_under(env) as c:
+            assert_launch_shape(c, env, C.args(graphs[VARIANT_CASES[0][0]]))
+            for name, iters in VARIANT_CASES:
+                a = C.args(graphs[name])
+                ps = [a[0]]
+                for it in range(iters):
+                    rc, p, _ = c.gn_optimize(ps[-1], *a[1:], 1)
+                    assert rc == 0, (vname, name, it, rc)
+                    ps.append(p)
+                ws = [R.step_backward_error(ps[i], ps[i + 1], *a[1:]) for i in range(iters)]
+                report[(vname, name)] = [round(w / R.U, 1) for w in ws]
+                assert max(ws) <= OMEGA_MAX, (vname, name, report[(vname, name)])
+            assert c.gn_timeouts() == 0, vname
     print("omega / u per iteration:", json.dumps({f"{v}/{n}": w for (v, n), w in report.items()}))
 
 
@@ -286,13 +246,15 @@ def test_condense_and_covariance_estimate_against_reference(ctx, oracle, wrap):
 def test_marginal_path_recovers_from_a_bounded_wait_that_ran_out(oracle):
     """CGMR_BWD_SPIN_LIMIT=1 (one poll per wait) makes the merged level launches' hand-offs run out: marginals, the covariance
     estimate and the condensed graph must still return OK with blocks that meet the reference (the pass is repeated with one
-    launch per kernel and level), the context counts the event, and the next call -- no switch -- returns exactly the bits of
-    a context that only ever merged what is certainly resident."""
+    launch per kernel and level), the context counts the event, and its cached structure merges from then on exactly the
+    levels a context merges that only ever merged what is certainly resident.  The switch belongs to the context (read when
+    it is created): the estimate the blocks are taken at comes from a second, plain context."""
     from cg_mrslam_amd import Context
     g = synth.make_pose_graph(2500, 9000, seed=5)
     a = C.args(g)
-    c = Context(0)
-    rc, p, _ = c.gn_optimize(*a, 8)
+    plain = Context(0)
+    rc, p, _ = plain.gn_optimize(*a, 8)
+    plain.close()
     assert rc == 0
     query = np.linspace(0, 2499, 20).astype(np.int32)
     gauge = 2499
@@ -300,15 +262,17 @@ def test_marginal_path_recovers_from_a_bounded_wait_that_ran_out(oracle):
     H, _, hidx = R.build_system(p, fx, *a[2:])
     want, _ = R.marginal_blocks_ref(H, hidx, query)
     ref = _condense_case(oracle, g, gauge, query, p)
-    t0 = c.gn_timeouts()
-    os.environ["CGMR_BWD_SPIN_LIMIT"] = "1"
-    try:
+    with context_under({"CGMR_BWD_SPIN_LIMIT": "1"}) as c, context_under({"CGMR_FWD_MERGE_ANY": "0"}) as c2:
+        t0 = c.gn_timeouts()
         cov = c.marginals(p, g["fixed"], *a[2:], query)
         t1 = c.gn_timeouts()
         cov_e = c.covariance_estimate(p, *a[2:], gauge, query)
         to, est, iu, _ = c.condense(p, *a[2:], gauge, query)
-    finally:
-        del os.environ["CGMR_BWD_SPIN_LIMIT"]
+        # the cached structure after the time-out against a context that never asked for merges beyond the resident ones
+        # (a pass of the spin-limited context that runs out again is repeated with separate launches: no merged one more)
+        n_b, n_c = _launches(c, a), _launches(c2, a)
+        assert n_b["front_level"] == n_c["front_level"] > 0, (n_b, n_c)
+        assert c2.gn_timeouts() == 0
     assert t1 >= t0 + 1, "the forced time-out did not happen: the test checks nothing"
     assert query[0] == 0 and hidx[0] < 0 and np.all(cov[0] == 0)         # the fixed vertex: exact zeros
     for k in range(1, len(query)):
@@ -319,20 +283,6 @@ def test_marginal_path_recovers_from_a_bounded_wait_that_ran_out(oracle):
     np.testing.assert_allclose(est, ref["est"], rtol=0, atol=EST_ATOL)
     for k in range(len(to)):
         assert np.linalg.norm(iu[k] - ref["iu"][k]) <= INFO_RTOL * np.linalg.norm(ref["iu"][k])
-    # the cached structure, without the switch, against a context that never asked for merges beyond the resident ones
-    cov_b = c.marginals(p, g["fixed"], *a[2:], query)
-    to_b, est_b, iu_b, _ = c.condense(p, *a[2:], gauge, query)
-    os.environ["CGMR_FWD_MERGE_ANY"] = "0"
-    try:
-        c2 = Context(0)
-    finally:
-        del os.environ["CGMR_FWD_MERGE_ANY"]
-    rc, _, _ = c2.gn_optimize(*a, 1)
-    assert rc == 0
-    cov_c = c2.marginals(p, g["fixed"], *a[2:], query)
-    to_c, est_c, iu_c, _ = c2.condense(p, *a[2:], gauge, query)
-    assert np.array_equal(cov_b, cov_c) and np.array_equal(est_b, est_c) and np.array_equal(iu_b, iu_c)
-    assert c2.gn_timeouts() == 0
 
 
 def test_batched_condensed_graphs_against_reference(oracle):

@@ -6,9 +6,8 @@ ref_numpy.step_backward_error <= OMEGA_MAX; a check that resolves one received e
 1 + 1e-9.  Condensed graphs of later rounds, built with the received edges switched off, are checked against
 ref_numpy.condense_ref on the own edges, and the optimal gauge against the reference's uncertainties.  Also checked: the
 asynchronous batch with the device exchange, and the launch variants that change the factorisation's shape."""
+import contextlib
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,6 +17,7 @@ from cg_mrslam_amd import synth
 from cg_mrslam_amd._lib import CgmrError
 from reference_cases import EST_ATOL, EST_OWN_ATOL_BATCH, INFO_RTOL, OMEGA_MAX, REF_ERR_MAX, check_labels_on_own_step
 from ref_condensed import select_gauge_centroid
+from switch_contexts import assert_launch_shape, context_under
 from robot_sequences import checked_rounds, make_robot_rounds, run_steps
 
 pytestmark = pytest.mark.gpu
@@ -236,41 +236,25 @@ VARIANTS = (("default", {}), ("no_top_block", {"CGMR_TOP_BLOCK": "0"}), ("separa
             ("no_amalgamation", {"CGMR_AMALGAMATE": "0"}))
 VARIANT_CASE = (2, 1200, 4000, 44, 120, 10)
 
-_CHILD = """import sys; sys.path[:0] = [{root!r}, {tests!r}]
-import numpy as np
-from cg_mrslam_amd import Context
-from robot_sequences import checked_rounds, make_robot_rounds
-nr, nv, ne, seed, chunk, n_rounds = {case!r}
-ctxs = [Context(0) for _ in range(nr)]
-rounds = make_robot_rounds(ctxs, nv, ne, seed, chunk)
-try:
-    steps, _, _ = checked_rounds(rounds, n_rounds)
-    out = dict(n=np.array(len(steps)), timeouts=np.array([c.gn_timeouts() for c in ctxs]))
-finally:
-    for rr in rounds:
-        rr.g.close()
-    for c in ctxs:
-        c.close()
-for i, s in enumerate(steps):
-    for k in ("t", "robot", "start", "n_own", "p0", "p1", "fixed", "ef", "et", "meas", "info"):
-        out["%d_%s" % (i, k)] = np.asarray(s[k])
-np.savez({path!r}, **out)
-print("DONE")
-"""
 
-
-def test_launch_variants_robot_graph_steps(tmp_path):
+def test_launch_variants_robot_graph_steps():
     """E: A's step check under the switches that change the factorisation's shape -- CGMR_TOP_BLOCK=0 makes the hubs'
-    separator ordinary fronts -- one child process at a time (they are read once per process)."""
+    separator ordinary fronts -- one set of contexts at a time (a context reads them when it is created)."""
+    nr, nv, ne, seed, chunk, n_rounds = VARIANT_CASE
     report = {}
     for vname, env in VARIANTS:
-        path = str(tmp_path / f"{vname}.npz")
-        code = _CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests"), case=VARIANT_CASE, path=path)
-        r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0 and "DONE" in r.stdout, (vname, r.returncode, r.stderr[-2000:])
-        d = np.load(path)
-        assert d["timeouts"].tolist() == [0] * VARIANT_CASE[0], (vname, d["timeouts"])
-        steps = [{k: d[f"{i}_{k}"] for k in ("t", "robot", "start", "n_own", "p0", "p1") + SYSTEM_KEYS} for i in range(int(d["n"]))]
+        with contextlib.ExitStack() as stack:
+            ctxs = [stack.enter_context(context_under(env)) for _ in range(nr)]
+            rounds = make_robot_rounds(ctxs, nv, ne, seed, chunk)
+            try:
+                steps, _, _ = checked_rounds(rounds, n_rounds)
+                timeouts = [c.gn_timeouts() for c in ctxs]
+            finally:
+                for rr in rounds:
+                    rr.g.close()
+            s = steps[-1]
+            assert_launch_shape(ctxs[0], env, (s["p0"],) + tuple(s[k] for k in SYSTEM_KEYS))
+        assert timeouts == [0] * nr, (vname, timeouts)
         ws, n_recv = _check_steps(vname, steps)
         assert n_recv > len(steps) // 2, (vname, n_recv, len(steps))
         report[vname] = round(max(ws) / R.U, 1)

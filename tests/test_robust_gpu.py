@@ -1,14 +1,11 @@
 """Robust kernels on the device (include/cgmr.h: cgmr_robust) against the float64 contract of tests/ref_robust.py."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import ref_numpy as R
 import ref_robust as RR
 import reference_cases as C
+from switch_contexts import assert_launch_shape, context_under
 from test_reference_gpu import VARIANTS
 
 pytestmark = pytest.mark.gpu
@@ -330,38 +327,19 @@ def test_robot_graph_robust_round():
 
 
 # ------------------------------------------------------------------------------------------------------------------- 8
-_CHILD = """import sys; sys.path[:0] = [{root!r}, {tests!r}]
-import numpy as np
-import ref_robust as RR
-import reference_cases as C
-from cg_mrslam_amd import Context
-c = Context(0)
-g, bad, _ = RR.outlier_graph()
-a = C.args(g)
-p = g["poses"]
-ps = [p]
-for it in range(3):
-    rc, p, _, _, _ = c.gn_optimize_robust(p, *a[1:], 1, kind="huber", delta=1.0)
-    assert rc == 0, (it, rc)
-    ps.append(p)
-np.savez({path!r}, ps=np.stack(ps), timeouts=np.array(c.gn_timeouts()))
-print("DONE")
-"""
-
-
-def test_launch_variants_backward_error(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    tests = os.path.join(root, "tests")
+def test_launch_variants_backward_error():
     g = outlier()["g"]
-    ef, et, meas, info = C.args(g)[2:6]
+    a = C.args(g)
+    ef, et, meas, info = a[2:6]
     for vname, env in VARIANTS:
-        path = str(tmp_path / f"{vname}.npz")
-        code = _CHILD.format(root=root, tests=tests, path=path)
-        r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0 and "DONE" in r.stdout, (vname, r.stderr[-2000:])
-        d = np.load(path)
-        assert int(d["timeouts"]) == 0, vname
-        ps = d["ps"]
+        with context_under(env) as c:
+            assert_launch_shape(c, env, a)
+            ps = [g["poses"]]
+            for it in range(3):
+                rc, p, _, _, _ = c.gn_optimize_robust(ps[-1], *a[1:], 1, kind="huber", delta=1.0)
+                assert rc == 0, (vname, it, rc)
+                ps.append(p)
+            assert c.gn_timeouts() == 0, vname
         for i in range(len(ps) - 1):
             ws = RR.scaled_info(ps[i], ef, et, meas, info, 1, 1.0)
             om = R.step_backward_error(ps[i], ps[i + 1], g["fixed"], ef, et, meas, ws)

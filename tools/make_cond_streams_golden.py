@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Record tests/golden/cond_streams_r4x6.npz: what the per-stream condensed-graph passes computed, on an MI355X.
+"""How tests/golden/cond_streams_r4x6.npz was once recorded: what the per-stream condensed-graph passes computed, on an MI355X.
+A record of provenance, not a tool that runs on this tree: the switch it sets, CGMR_COND_BATCH, went with the retired path and
+is not in the library's switch table (cg_mrslam_amd/csrc/switches.h), so no library built from this tree is accepted.
 
     CGMR_LIB=/abs/path/to/parent/libcgmr.so python tools/make_cond_streams_golden.py [--out tests/golden/cond_streams_r4x6.npz]
 

@@ -1,5 +1,5 @@
 """Latency of ONE closeScanMatching call (the reference's call shape: once per key frame): wall per call and kernel time,
-for the workgroups-per-pair settings given (CGMR_MATCH_SPLIT is read once per process: one subprocess each)."""
+for the workgroups-per-pair settings given (CGMR_MATCH_SPLIT is read when a context is created: one subprocess each)."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CODE = r'''

@@ -1,5 +1,5 @@
 """Tree levels / launched levels / factorisation flops of the ordering over a set of graphs (host only), for one setting of the
-environment (the switches are read once per process): python tools/nd_root_eval.py  -> one line per graph and the sums."""
+environment (the call reads the switches as the environment stands): python tools/nd_root_eval.py  -> one line per graph and the sums."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cg_mrslam_amd import synth

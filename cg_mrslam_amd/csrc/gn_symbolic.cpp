@@ -382,6 +382,7 @@ struct NDCtx {
   std::vector<int32_t> queue;         // BFS order, indexed by *position*: a call only touches [begin, end)
   std::vector<int32_t> tmp;           // partition scratch, indexed by position
   std::atomic<int> next_label{1};
+  std::atomic<int> inherited_near{0}, inherited_first{0};   // nodes that took their sweep from the caller (CGMR_ND_INHERIT; the trace)
   int max_par_depth = 0;              // recursion levels that fork a thread for one half
   // the dissection tree, recorded for the incremental analysis of a graph that grows (sizes only: positions follow from
   // the root's, children may trade places after they were recorded)
@@ -439,9 +440,23 @@ int bfs(NDCtx& C, int32_t* q, int root, int id, int visited_id, int32_t* lvl = n
   return qt;
 }
 
+// What the caller's sweep already holds of the sweep a range would run first (CGMR_ND_INHERIT).
+//   js >= 0: the range is the near half of the caller's level structure and `start` the root of that sweep.  Every vertex of
+//     the half was discovered from a vertex of a lower level, and all of those are in the half: its earliest-queued neighbour
+//     is the same in the half as in the caller's range, so the half is connected and a sweep from `start` visits it in the
+//     order the caller queued it -- the order it already stands in.  Depths are the caller's, js for the level-js vertices
+//     the cover moved to the near side (positions >= s_js; the cover left js-1 there), and the caller has written the level
+//     counts -- its own below js, then the number of moved vertices -- into the range's slice of C.tmp.  No sweep.
+//   far >= 0: the range is the first component of a disconnected range, in the caller's queue order.  The sweep for a far
+//     vertex would start at the same vertex over the same vertices: the same BFS, and `far` is the vertex it ends at.
+struct NDGiven {
+  int js = -1, s_js = 0;
+  int far = -1;
+};
+
 // Orders [begin, end) and marks its panels.
 // `start`: a vertex of the range known to lie at one end of it (the parent's sweep began or ended there), or -1.
-NDRange nd(NDCtx& C, int begin, int end, int depth, int start = -1, int* node_out = nullptr) {
+NDRange nd(NDCtx& C, int begin, int end, int depth, int start = -1, int* node_out = nullptr, NDGiven given = NDGiven()) {
   int n = end - begin;
   const bool nd_trace = C.sw.sym_trace;
   const double t_in = nd_trace ? now_s() : 0;
@@ -452,13 +467,11 @@ NDRange nd(NDCtx& C, int begin, int end, int depth, int start = -1, int* node_ou
   if (n <= kPanelW) { node = C.new_rec(-1, -1, n, n); return emit_panels(C, begin, end); }
   int32_t* Q = C.queue.data() + begin;                  // this call's slice of the BFS queue
   int id = C.next_label.fetch_add(3);
-  for (int p = begin; p < end; p++) C.vs[C.order[p]].label = id;
   int32_t* LV = C.tmp.data() + begin;                   // level counts of the structuring sweep (the slice is free until the partition)
   // first sweep: connectivity + a far vertex; skipped when the parent's sweep already left one (then the second
   // sweep doubles as the connectivity check)
   int vis1 = id + 1, vis2 = id + 2;
   const bool have_start = C.sw.nd_reuse_start && start >= 0;
-  const double t_l0 = nd_trace ? now_s() : 0;
   // The root (round 6): instead of a sweep for a far vertex and a second one from there -- two whole-graph sweeps one behind
   // the other on one thread, 0.38 ms at C2's size, while the others idle --, K = 4 structuring sweeps side by side from the
   // vertices at 0, 1/3, 2/3 and the end of the range (the first and the last pose among them), the deepest level structure
@@ -469,9 +482,23 @@ NDRange nd(NDCtx& C, int begin, int end, int depth, int start = -1, int* node_ou
   // 2.1); the benchmark graph happens to come out a level shorter (17 / 15 launched instead of 18 / 16).  The result does not
   // depend on the number of threads (the same four candidates whatever runs them).  CGMR_ND_ROOT_STARTS=0: the double sweep.
   const int root_starts = C.sw.nd_root_starts;
+  const bool multi = depth == 0 && !have_start && root_starts > 1 && n >= 2048;
+  const bool near_given = have_start && given.js >= 0;
+  const bool far_given = !have_start && !multi && given.far >= 0;   // (the root's side-by-side sweeps keep theirs)
+  if (near_given) {
+    for (int q = 0; q < n; q++) { const int v = C.order[begin + q]; Q[q] = v; C.vs[v].label = vis2; }
+    for (int q = given.s_js; q < n; q++) C.vs[Q[q]].dist = given.js;
+    C.inherited_near.fetch_add(1, std::memory_order_relaxed);
+  } else if (far_given) {
+    for (int p = begin; p < end; p++) C.vs[C.order[p]].label = vis1;
+    C.inherited_first.fetch_add(1, std::memory_order_relaxed);
+  } else {
+    for (int p = begin; p < end; p++) C.vs[C.order[p]].label = id;
+  }
+  const double t_l0 = nd_trace ? now_s() : 0;
   bool multi_done = false;
   int reached = 0;
-  if (depth == 0 && !have_start && root_starts > 1 && n >= 2048) {
+  if (multi) {
     const int K = std::min(root_starts, 16);
     struct Cand { std::vector<NDCtx::VState> vs; std::vector<int32_t> q, lv; int reached = 0, nlev = 0; };
     static thread_local std::vector<Cand> cand;
@@ -499,7 +526,8 @@ NDRange nd(NDCtx& C, int begin, int end, int depth, int start = -1, int* node_ou
       multi_done = true;
     }
   }
-  if (!multi_done) reached = have_start ? bfs(C, Q, start, id, vis2, LV) : bfs(C, Q, C.order[begin], id, vis1);
+  if (near_given || far_given) reached = n;
+  else if (!multi_done) reached = have_start ? bfs(C, Q, start, id, vis2, LV) : bfs(C, Q, C.order[begin], id, vis1);
   const double t_l1 = nd_trace ? now_s() : 0;
   if (reached < n) {
     // disconnected: component first, then the rest (independent subtrees, no separator)
@@ -508,14 +536,18 @@ NDRange nd(NDCtx& C, int begin, int end, int depth, int start = -1, int* node_ou
     for (int p = begin; p < end; p++) if (C.vs[C.order[p]].label == id) C.tmp[k++] = C.order[p];
     std::copy(C.tmp.begin() + begin, C.tmp.begin() + end, C.order.begin() + begin);
     int n1 = -1, n2 = -1;
-    NDRange r1 = nd(C, begin, begin + reached, depth, -1, &n1);   // (passing the parent's end vertex on instead of a fresh double sweep: 466 instead of 448 tree levels over 24 graphs -- round 6)
+    // The component still gets its double sweep (seeding it with this range's end vertex instead: 466 instead of 448 tree levels
+    // over 24 graphs -- round 6), but the first of the two is the sweep just done: only the vertex it ended at is passed on.
+    NDGiven first;
+    if (C.sw.nd_inherit) first.far = Q[reached - 1];
+    NDRange r1 = nd(C, begin, begin + reached, depth, -1, &n1, first);
     NDRange r2 = nd(C, begin + reached, end, depth, -1, &n2);
     r2.height = std::max(r1.height, r2.height);
     node = C.new_rec(n1, n2, n, 0);                       // independent components: two halves, no separator
     return r2;
   }
   if (!have_start && !multi_done) {
-    int far = Q[reached - 1];
+    int far = far_given ? given.far : Q[reached - 1];
     // second sweep from the far vertex gives the level structure
     bfs(C, Q, far, vis1, vis2, LV);
   }
@@ -545,7 +577,10 @@ NDRange nd(NDCtx& C, int begin, int end, int depth, int start = -1, int* node_ou
     for (int j = 0; j < js; j++) s_js += lvl_cnt[j];
     thread_local std::vector<int32_t> ylocal;             // vertex -> index in Y, -1 outside this block
     if ((int)ylocal.size() < (int)C.vs.size()) ylocal.assign(C.vs.size(), -1);
-    std::vector<int32_t> X, Y, xptr(1, 0), xadj;
+    struct CoverScratch { std::vector<int32_t> X, Y, xptr, xadj, mx, my, seen, stack; std::vector<uint8_t> zx, zy; };
+    thread_local CoverScratch cs;
+    std::vector<int32_t>&X = cs.X, &Y = cs.Y, &xptr = cs.xptr, &xadj = cs.xadj;
+    X.clear(); Y.clear(); xptr.assign(1, 0); xadj.clear();
     for (int q = s_js; q < s_js + lvl_cnt[js]; q++) {
       int v = Q[q];
       const size_t before = xadj.size();
@@ -562,20 +597,25 @@ NDRange nd(NDCtx& C, int begin, int end, int depth, int start = -1, int* node_ou
     const bool min_cover = C.sw.nd_min_cover;
     const int nx = (int)X.size(), ny = (int)Y.size();
     if (min_cover && nx > 1 && ny > 0) {
-      std::vector<int32_t> mx(nx, -1), my(ny, -1), seen(ny, -1), stack;
+      std::vector<int32_t>&mx = cs.mx, &my = cs.my, &seen = cs.seen, &stack = cs.stack;
+      mx.assign(nx, -1); my.assign(ny, -1); seen.assign(ny, -1); stack.clear();
       // maximum matching by augmenting paths (the blocks are small: tens of vertices)
-      std::function<bool(int, int)> augment = [&](int x, int stamp) {
-        for (int p = xptr[x]; p < xptr[x + 1]; p++) {
-          int y = xadj[p];
-          if (seen[y] == stamp) continue;
-          seen[y] = stamp;
-          if (my[y] < 0 || augment(my[y], stamp)) { mx[x] = y; my[y] = x; return true; }
+      struct Augment {
+        const int32_t *xptr, *xadj; int32_t *mx, *my, *seen;
+        bool operator()(int x, int stamp) const {
+          for (int p = xptr[x]; p < xptr[x + 1]; p++) {
+            int y = xadj[p];
+            if (seen[y] == stamp) continue;
+            seen[y] = stamp;
+            if (my[y] < 0 || (*this)(my[y], stamp)) { mx[x] = y; my[y] = x; return true; }
+          }
+          return false;
         }
-        return false;
-      };
+      } augment{xptr.data(), xadj.data(), mx.data(), my.data(), seen.data()};
       for (int x = 0; x < nx; x++) augment(x, x);
       // Koenig: Z = reachable from the unmatched X by alternating paths; cover = (X \ Z) + (Y in Z)
-      std::vector<uint8_t> zx(nx, 0), zy(ny, 0);
+      std::vector<uint8_t>&zx = cs.zx, &zy = cs.zy;
+      zx.assign(nx, 0); zy.assign(ny, 0);
       for (int x = 0; x < nx; x++) if (mx[x] < 0) { zx[x] = 1; stack.push_back(x); }
       while (!stack.empty()) {
         int x = stack.back(); stack.pop_back();
@@ -613,18 +653,32 @@ NDRange nd(NDCtx& C, int begin, int end, int depth, int start = -1, int* node_ou
   for (int q = e_js; q < e_js1; q++) { const int v = Q[q]; if (C.vs[v].dist > js) C.tmp[pb++] = v; else C.tmp[ps++] = v; }
   for (int q = e_js1; q < n; q++) C.tmp[pb++] = Q[q];
   std::copy(C.tmp.begin() + begin, C.tmp.begin() + end, C.order.begin() + begin);
-  if (nd_trace && depth <= 3) fprintf(stderr, "    nd depth %d n %5d own work %.1f us (labels %.1f, sweep 1 %.1f, sweep 2 %.1f, level choice + cover %.1f, partition %.1f; levels %d, separator level %d of size %d)\n", depth, n, 1e6 * (now_s() - t_in), 1e6 * (t_l0 - t_in), 1e6 * (t_l1 - t_l0), 1e6 * (t_l2 - t_l1), 1e6 * (t_l3 - t_l2), 1e6 * (now_s() - t_l3), nlev, js, lvl_cnt[js]);
+  // the near half's level structure is a part of this one: its level counts into its slice of the partition scratch (free
+  // from here on, and the half's own LV; js <= s_js <= na entries, one more only where a moved vertex follows them)
+  NDGiven near;
+  if (C.sw.nd_inherit && C.sw.nd_reuse_start) {
+    near.js = js; near.s_js = s_js;
+    std::copy(lvl_cnt.begin(), lvl_cnt.begin() + js, C.tmp.begin() + begin);
+    if (na > s_js) C.tmp[begin + js] = na - s_js;
+  }
+  char swept[96];
+  if (nd_trace && depth <= 3) {
+    if (near_given) snprintf(swept, sizeof swept, "sweep inherited from the parent's");
+    else if (far_given) snprintf(swept, sizeof swept, "sweep 1 inherited from the caller's, sweep 2 %.1f", 1e6 * (t_l2 - t_l1));
+    else snprintf(swept, sizeof swept, "sweep 1 %.1f, sweep 2 %.1f", 1e6 * (t_l1 - t_l0), 1e6 * (t_l2 - t_l1));
+  }
+  if (nd_trace && depth <= 3) fprintf(stderr, "    nd depth %d n %5d own work %.1f us (labels %.1f, %s, level choice + cover %.1f, partition %.1f; levels %d, separator level %d of size %d)\n", depth, n, 1e6 * (now_s() - t_in), 1e6 * (t_l0 - t_in), swept, 1e6 * (t_l3 - t_l2), 1e6 * (now_s() - t_l3), nlev, js, lvl_cnt[js]);
   // the two halves touch disjoint vertices and disjoint position ranges: fork one of them near the top
   NDRange r1, r2;
   int n1 = -1, n2 = -1;
   if (depth < C.max_par_depth && na > 512 && nb > 512) {
     HelperPool::Job job;
-    job.fn = [&C, &r1, &n1, begin, na, depth, start_a] { r1 = nd(C, begin, begin + na, depth + 1, start_a, &n1); };
+    job.fn = [&C, &r1, &n1, begin, na, depth, start_a, near] { r1 = nd(C, begin, begin + na, depth + 1, start_a, &n1, near); };
     pool().run(job);
     r2 = nd(C, begin + na, begin + na + nb, depth + 1, start_b, &n2);
     HelperPool::wait(job);
   } else {
-    r1 = nd(C, begin, begin + na, depth + 1, start_a, &n1);
+    r1 = nd(C, begin, begin + na, depth + 1, start_a, &n1, near);
     r2 = nd(C, begin + na, begin + na + nb, depth + 1, start_b, &n2);
   }
   // Only the half right in front of the separator can share a panel with it (see the amalgamation in analyze()):
@@ -1271,6 +1325,7 @@ int analyze(int nV, const uint8_t* fixed, int nE, const int32_t* ef, const int32
     // for 0.24 ms per level and optimize(10)), nor a choice after three levels of both (517 levels).  DESIGN.md 2.1.
     const NDRange whole = nd(C, 0, n_nd, 0, -1, &root_rec);
     CK("  nd: dissection");
+    if (trace) fprintf(stderr, "  sym   nd: sweeps inherited     %d near halves, %d first components\n", C.inherited_near.load(), C.inherited_first.load());
     S.nd_height_full = whole.height + (nf - n_nd + kPanelW - 1) / kPanelW;
     for (int p = n_nd; p < nf; p += kPanelW) pstart[p] = 1;
     pos_ranges.swap(C.subtree_ranges);

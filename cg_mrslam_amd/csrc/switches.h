@@ -43,6 +43,7 @@ namespace cgmr {
   X("CGMR_AMALGAMATE", amalgamate, flag, true, context, "merge a front into its parent where that is free; 0: one front per panel")  \
   X("CGMR_ND_REUSE_START", nd_reuse_start, flag, true, context, "a dissection node starts its sweep where the parent's ended; 0: its own far-vertex sweep") \
   X("CGMR_ND_ROOT_STARTS", nd_root_starts, num, 4, context, "structuring sweeps the root runs side by side (at most 16); 0 / 1: the double sweep") \
+  X("CGMR_ND_INHERIT", nd_inherit, flag, true, context, "a dissection node takes the sweep its caller already holds (near half, first component); 0: it sweeps anew") \
   X("CGMR_ND_MIN_COVER", nd_min_cover, flag, true, context, "separator = minimum vertex cover between two levels; 0: the whole level") \
   X("CGMR_ND_PAR_DEPTH", nd_par_depth, num, -1, context, "dissection levels that fork a helper thread; -1: by the number of host threads") \
   X("CGMR_HUB_DEGREE", hub_degree, num, 32, context, "vertices of more neighbours are eliminated last (hubs); 0: no hubs, named ones included") \

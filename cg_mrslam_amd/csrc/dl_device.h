@@ -8,7 +8,7 @@
 
 namespace cgmr {
 
-// One per call, in device memory, set up by the host before the first head (cgmr_api.cpp: tr_run) and read back once per round.
+// One per call, in device memory, set up by the host before the first head (optimize_host.cpp: tr_run) and read back once per round.
 struct DlState {
   double delta = 1e4;                        // trust-region radius
   double lambda = 1e-7;                      // currentLambda: the damping once H has not been positive definite

@@ -7,7 +7,7 @@
 //   the GN / SD / DL choice                               -> k_dl_step
 //   rho, the trust region, push / pop                     -> k_dl_decide, k_tr_commit (tr_kernels.hip)
 //
-// An iteration is a head and one or more tails (cgmr_api.cpp: DlPolicy).  Head: linearise, assemble, [damp,] factor, solve
+// An iteration is a head and one or more tails (optimize_host.cpp: DlPolicy).  Head: linearise, assemble, [damp,] factor, solve
 // (no pose update), k_dl_quad(b), k_dl_begin.  Tail: k_dl_step, k_dl_quad(h), update, chi-only linearise, k_dl_decide,
 // k_tr_commit.  A rejected trial changes delta only, so the next tail mixes the same saved hgn and hsd again: no
 // factorisation.  The term records k_linearize left at x stay valid through the tails (the chi-only linearisation returns

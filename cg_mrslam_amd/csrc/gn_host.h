@@ -1,8 +1,17 @@
-// Host-side drivers of the Gauss-Newton path shared by the C-ABI translation units (cgmr_api.cpp, mrslam_api.cpp).
+// Host-side drivers of the Gauss-Newton path shared by the solver's translation units (gn_host.cpp, optimize_host.cpp,
+// marginals_host.cpp, cgmr_api.cpp, cgmr_debug.cpp) and mrslam_api.cpp.
 #pragma once
 #include <cmath>
+#include <cstdio>
+#include <initializer_list>
 
 #include "cgmr_ctx.h"
+
+#define HIP_TRY(ctx, call)                                                                      \
+  do {                                                                                          \
+    hipError_t e_ = (call);                                                                     \
+    if (e_ != hipSuccess) return set_err(ctx, CGMR_E_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
+  } while (0)
 
 namespace cgmr {
 
@@ -94,33 +103,39 @@ struct LevelwiseScope {
     D.h_level_merge.swap(merge_was);
   }
 };
-int gn_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
-           const GnEdges& Ed, int iters, double* chi2_out, const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0);
+// What a driver solves, on the device: the vertices with their estimates and fixed flags (host), the edge list (host), and the
+// vertices the ordering keeps out of the dissection and eliminates last (nullable; gn_symbolic.h: analyze).
+struct GnSystem {
+  int nV; double* d_poses; const uint8_t* fixed; int nE; const int32_t *ef, *et;
+  const int32_t* hub_vertices = nullptr; int n_hub_vertices = 0;
+};
+inline int prepare_structure(cgmr_ctx* ctx, const GnSystem& S, int iters) {
+  return prepare_structure(ctx, S.nV, S.nE, S.ef, S.et, iters, S.hub_vertices, S.n_hub_vertices);
+}
+// the caller's arrays every *_run fills (all nullable): chi2 [iters + 1], the per-iteration records [iters], *iters_done
+struct LmOut { double *chi2, *lambda; int32_t *trials, *iters_done; };
+struct DlOut { double *chi2, *delta; int32_t *trials, *step, *iters_done; };
+// mu [max_outer], cost [max_outer + 1], partial [max_outer], *outer_done, and -- host memory, written when the call ends well
+// or with a Cholesky code, behind the call's own final wait -- weight / edge_chi2 [nE]
+struct GncOut { double *mu, *cost; int32_t *partial, *outer_done; double *weight, *edge_chi2; };
+int gn_run(cgmr_ctx* ctx, const GnSystem& S, const GnEdges& Ed, int iters, double* chi2_out);
 // Chordal initialisation on the same structure preparation and factorisation (include/cgmr.h: cgmr_chordal_initialize): one pass
 // per stage of `stages`; in_rot / in_tr [nV] host: the vertices some term of the stage touches; chi2_out [2], counts_out [3] nullable
-int chordal_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
-                const GnEdges& Ed, int stages, const uint8_t* in_rot, const uint8_t* in_tr, double* chi2_out, int32_t* counts_out);
-// Levenberg-Marquardt on the same structure preparation and factorisation (g2o's OptimizationAlgorithmLevenberg): outputs
-// chi2_out [iters + 1], lambda_out / trials_out [iters] (all nullable), *iters_done; never a Cholesky status
-int lm_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
-           const GnEdges& Ed, int iters, const cgmr_lm_params* params, double* chi2_out, double* lambda_out, int32_t* trials_out,
-           int32_t* iters_done, const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0);
-// Dogleg on the same structure preparation and factorisation (g2o's OptimizationAlgorithmDogleg): outputs chi2_out
-// [iters + 1], delta_out / trials_out / step_out [iters] (all nullable), *iters_done; CGMR_E_CHOLESKY_BASE - i on g2o's Fail
-int dl_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
-           const GnEdges& Ed, int iters, const cgmr_dl_params* params, double* chi2_out, double* delta_out, int32_t* trials_out,
-           int32_t* step_out, int32_t* iters_done, const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0);
+int chordal_run(cgmr_ctx* ctx, const GnSystem& S, const GnEdges& Ed, int stages, const uint8_t* in_rot, const uint8_t* in_tr,
+                double* chi2_out, int32_t* counts_out);
+// Levenberg-Marquardt on the same structure preparation and factorisation (g2o's OptimizationAlgorithmLevenberg); never a
+// Cholesky status
+int lm_run(cgmr_ctx* ctx, const GnSystem& S, const GnEdges& Ed, int iters, const cgmr_lm_params* params, const LmOut& out);
+// Dogleg on the same structure preparation and factorisation (g2o's OptimizationAlgorithmDogleg); CGMR_E_CHOLESKY_BASE - i on
+// g2o's Fail
+int dl_run(cgmr_ctx* ctx, const GnSystem& S, const GnEdges& Ed, int iters, const cgmr_dl_params* params, const DlOut& out);
 // null, or parameters dl_run accepts
 bool dl_params_ok(const cgmr_dl_params* params);
 // Graduated non-convexity with Gauss-Newton inside (include/cgmr.h: cgmr_gnc_optimize), on the same structure preparation:
 // P checked by the caller (its per-edge pointers are not read), barc_sq / known host arrays [nE] (every entry set), Ed without a
-// robust description.  Outputs mu_out [max_outer], cost_out [max_outer + 1], partial_out [max_outer], *outer_done, and -- host
-// memory, written when the call ends well or with a Cholesky code, behind the call's own final wait -- weight_out /
-// edge_chi2_out [nE] (all nullable).  CGMR_E_CHOLESKY_BASE - i: the poses are those of the last good update.
-int gnc_run(cgmr_ctx* ctx, int nV, double* d_poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
-            const GnEdges& Ed, const cgmr_gnc_params& P, const double* barc_sq, const uint8_t* known, double* mu_out,
-            double* cost_out, int32_t* partial_out, int32_t* outer_done, double* weight_out, double* edge_chi2_out,
-            const int32_t* hub_vertices = nullptr, int n_hub_vertices = 0);
+// robust description.  CGMR_E_CHOLESKY_BASE - i: the poses are those of the last good update.
+int gnc_run(cgmr_ctx* ctx, const GnSystem& S, const GnEdges& Ed, const cgmr_gnc_params& P, const double* barc_sq,
+            const uint8_t* known, const GncOut& out);
 // null, or parameters gnc_run accepts (the per-edge pointers aside); the defaults
 bool gnc_params_ok(const cgmr_gnc_params* params);
 cgmr_gnc_params gnc_params_default();
@@ -129,5 +144,99 @@ double gnc_default_barc_sq(int dim);
 // SparseOptimizer::computeInitialGuess from the fixed vertices over the given edges [g2o-recalled]
 void initial_guess_host(int nV, double* poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
                         const double* meas);
+// The analysis of the system's edge list (N: its nV, nE, ef, et and hubs) into `sym`, which holds the analysis of (prev_nV, pef,
+// pet) when have_prev: extended from it where the two lists allow that, from scratch otherwise
+int analyze_next(Symbolic& sym, const Switches& sw, bool have_prev, int prev_nV, const std::vector<int32_t>& pef, const std::vector<int32_t>& pet,
+                 const GnSystem& N, const AnalyzeHooks* hooks = nullptr);
+// the 16 figures of cgmr_gn_symbolic_info for an analysis, and its vertex permutation (nullable)
+void symbolic_info_out(const Symbolic& S, int nV, int64_t out[16], int32_t* perm_out);
+// gn_symbolic.cpp: the helper pool as it runs -- threads an analysis uses (caller included), 1 if the helpers are pinned around
+// a last-level cache, the caller's home CPU while it analyses (-1: not pinned), CPUs the process may use, moves of the pool
+void host_pool_info(int out[5]);
+// profiling mode: add up the event pairs of the launches since the last collection (call after a stream sync)
+void profile_collect(cgmr_ctx* ctx);
+
+struct BlobLayout {
+  size_t off = 0;
+  template <typename T>
+  size_t add(size_t count) {
+    off = (off + 15) & ~size_t(15);
+    size_t o = off;
+    off += count * sizeof(T);
+    return o;
+  }
+};
+
+struct KTimer {   // optional per-launch-class timing (profiling mode only)
+  cgmr_ctx* ctx;
+  hipStream_t st;
+  template <typename Fn>
+  void run(int cls, int nlaunch, Fn&& fn) {
+    if (ctx->sw.trace_launches) {                                 // debugging aid: name every launch, sync after it
+      fprintf(stderr, "[cgmr] launch class %d (0 lin 1 asm 2 chi2 3 factor 4 update 5 top 6 bwd 7 poses 8 factor+update)\n", cls);
+      fn();
+      hipError_t e = hipStreamSynchronize(st);
+      fprintf(stderr, "[cgmr]   done: %s\n", hipGetErrorString(e));
+      return;
+    }
+    if (!ctx->profiling || st != ctx->stream || 2 * (ctx->ev_cls.size() + 1) > ctx->ev_pool.size()) { fn(); return; }
+    const size_t k = ctx->ev_cls.size();
+    (void)hipEventRecord(ctx->ev_pool[2 * k], ctx->stream);
+    fn();
+    (void)hipEventRecord(ctx->ev_pool[2 * k + 1], ctx->stream);
+    ctx->ev_cls.push_back(cls);
+    ctx->klaunch[cls] += nlaunch;
+  }
+};
+
+// What an optimisation call does around its device work, whatever the algorithm: the structure and the masks with their
+// wall-clock marks, the timing events, the caller's host copy of the estimates, the wait, cgmr_gn_timing's five entries.
+struct GnCall {
+  cgmr_ctx* ctx;
+  const GnSystem& sys;
+  double t0, t1 = 0, t2 = 0;
+  double* poses_host = nullptr;
+  struct Readback { void* dst; const void* src; size_t bytes; };
+
+  GnCall(cgmr_ctx* c, const GnSystem& s) : ctx(c), sys(s), t0(wall_s()) {}
+  // chi_slots: iterations whose chi2 slot the structure's work space must hold
+  int prepare(int n_active, int chi_slots) {
+    int rc = prepare_structure(ctx, sys, chi_slots);
+    if (rc) return rc;
+    t1 = wall_s();
+    rc = prepare_pass(ctx, sys.fixed, sys.nE, sys.ef, sys.et, n_active);
+    t2 = wall_s();
+    return rc;
+  }
+  // the device work starts here (ev0; its end: the last hipEventRecord of ev1 before a wait)
+  int begin() {
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    // the caller's host copy of the estimates rides in every wait (a robot graph whose peers have asked for condensed graphs
+    // picks their gauges from it right after the solve)
+    poses_host = ctx->poses_out_host;
+    ctx->poses_out_host = nullptr;
+    return 0;
+  }
+  int wait(std::initializer_list<Readback> what) {
+    hipStream_t st = ctx->stream;
+    for (const Readback& r : what)
+      if (r.bytes) HIP_TRY(ctx, hipMemcpyAsync(r.dst, r.src, r.bytes, hipMemcpyDeviceToHost, st));
+    if (poses_host && sys.nV > 0) HIP_TRY(ctx, hipMemcpyAsync(poses_host, sys.d_poses, 24 * (size_t)sys.nV, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+  }
+  void finish() {
+    const Symbolic& S = ctx->sym;
+    if (ctx->profiling) profile_collect(ctx);
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+    ctx->timing[0] = S.t_order;
+    ctx->timing[1] = S.t_struct;
+    ctx->timing[2] = (t2 - t1) + S.t_upload;     // structure blob (host staging + H2D enqueue) + per-pass masks
+    ctx->timing[3] = 1e-3 * ms;
+    ctx->timing[4] = wall_s() - t0;
+  }
+};
 
 }  // namespace cgmr

@@ -68,7 +68,7 @@ static_assert(kFrontW + kChunkRows + 1 <= 208, "panel_cholesky: at most 4 x 48 r
 // Passes batched over a job dimension (blockIdx.z): the condensed graphs a robot builds for its peers are the same
 // structure with another gauge -- one launch per step serves all of them instead of one stream of launches each (the
 // device dispatches ~7 us per kernel when several short chains run side by side: 455 launches for 7 peers).  The numeric
-// work space of job j is the first job's moved by j * js bytes (cgmr_api.cpp: gn_replicas), its poses by j * ps bytes;
+// work space of job j is the first job's moved by j * js bytes (gn_host.cpp: gn_replicas), its poses by j * ps bytes;
 // the structure is shared.
 // (Moving a kernel argument pointer costs the loads through it their no-alias / invariant standing -- 3 % of a whole solve
 // when tried unconditionally -- so the batch is a template parameter and a plain solve runs the code it always ran.)

@@ -15,7 +15,7 @@ constexpr int kGncCompute = 0;   // from mu and r at these poses, stored (unless
 constexpr int kGncReuse = 1;     // the stored ones (later inner iterations, the final statistics)
 constexpr int kGncPlain = 2;     // all 1, nothing read or stored (the start's chi-only pass)
 
-// One per call, in device memory, set up by the host (cgmr_api.cpp: GncPolicy) and read back once per round.
+// One per call, in device memory, set up by the host (optimize_host.cpp: GncPolicy) and read back once per round.
 struct GncState {
   double mu = 0, factor = 1.4;
   int32_t loss = kGncTls, max_outer = 100, inner_iters = 1;

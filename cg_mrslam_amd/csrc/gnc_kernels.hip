@@ -7,7 +7,7 @@
 //   cost / partial records, "is this the last one"      -> k_gnc_outer
 //   failure, the inner count, the step of mu, done      -> k_gnc_step, k_tr_commit (tr_kernels.hip)
 //
-// One outer iteration is a fixed launch sequence whatever its outcome (cgmr_api.cpp: GncPolicy::outer): linearise with fresh
+// One outer iteration is a fixed launch sequence whatever its outcome (optimize_host.cpp: GncPolicy::outer): linearise with fresh
 // weights, assemble, k_gnc_outer, factor, solve, update, k_gnc_step; for every further inner iteration the same with the stored
 // weights and without k_gnc_outer; then the commit.  The state (mu, counters, records) lives on the device: the host queues
 // outer iterations without reading anything back in between.  Once the call is over, every later launch of a queued iteration

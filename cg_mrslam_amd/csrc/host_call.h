@@ -1,0 +1,57 @@
+// What a solver entry point was given, and what cgmr_api.cpp and marginals_host.cpp share to check and stage it.
+#pragma once
+#include "gn_host.h"
+
+namespace cgmr {
+
+// The problem arguments of an entry point as the caller passed them -- host pointers, or with `dev` device pointers for poses,
+// meas and info -- and the optional descriptions that go with them.  The marginals family never writes through `poses`.
+struct HostCall {
+  int nV;
+  double* poses;
+  const uint8_t* fixed;
+  int nE;
+  const int32_t *ef, *et;
+  const double *meas, *info;
+  bool dev;
+  const cgmr_robust* rk;
+  const cgmr_factor_types* ft;
+  const cgmr_mixture* mix;
+};
+struct HostCallHow { bool dev = false; const cgmr_robust* rk = nullptr; const cgmr_factor_types* ft = nullptr; const cgmr_mixture* mix = nullptr; };
+inline HostCall host_call(int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef, const int32_t* et,
+                          const double* meas, const double* info, const HostCallHow& how = HostCallHow()) {
+  return {nV, const_cast<double*>(poses), fixed, nE, ef, et, meas, info, how.dev, how.rk, how.ft, how.mix};
+}
+
+// The factor types of a typed entry point (include/cgmr.h: cgmr_factor_types), checked on the host before the device is
+// touched: every vertex kind 0 or 1, every edge kind with the vertex kinds and the arity its factor needs.  `any`: some kind
+// is not zero (all zero: the call is the plain one, bit for bit -- the plain launches).  The priors grouped by vertex, in edge
+// order, for k_add_unary.
+struct TypedHost {
+  bool any = false;
+  std::vector<uint8_t> vk, ek;
+  std::vector<int32_t> uv_vertex, uv_ptr, uv_edge;
+};
+int typed_check(cgmr_ctx* ctx, const char* who, const HostCall& c, TypedHost& T);
+// ... staged through ty_arena into Ed (nothing when every kind is zero)
+int typed_upload(cgmr_ctx* ctx, const TypedHost* T, GnEdges& Ed);
+// The robust description of an entry point (include/cgmr.h: cgmr_robust) into Ed, checked before anything is queued; the
+// statistics of the call's final pass to the caller's host arrays (cgmr_api.cpp)
+int robust_setup(cgmr_ctx* ctx, const cgmr_robust* rk, int nE, bool dev, GnEdges& Ed, const char* who);
+int robust_stats_out(cgmr_ctx* ctx, const cgmr_robust* rk, int nE, const GnEdges& Ed);
+
+// The marginals family (marginals_host.cpp).  marginal_driver: mode 0 marginals at c.poses with c.fixed; 1 covariance estimate
+// (gauge); 2 condense (gauge).  joint_driver: mode 0 joint, 1 pairs, 2 relative / observation covariance.
+int marginal_driver(cgmr_ctx* ctx, int mode, const HostCall& c, int gauge, int nK, const int32_t* query, int32_t* to_out,
+                    double* est_out, double* info_out, double* cov_out);
+int marginals_all_driver(cgmr_ctx* ctx, const HostCall& c, double* cov_out, double* cross_out);
+int joint_driver(cgmr_ctx* ctx, const char* who, int mode, const HostCall& c, int nQ, const int32_t* va, const int32_t* vb,
+                 double* out_a, double* out_b, double* out_c, const double* hyp_meas, const double* hyp_info, bool obs = false,
+                 const uint8_t* obs_kind = nullptr);
+int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, const int32_t* cb, const double* cmeas,
+               const double* cinfo, double gamma, double* d2_out, uint64_t* adj_out, int32_t* clique_out, int32_t* size_out,
+               int32_t* seed_out);
+int clique_driver(cgmr_ctx* ctx, int n, const uint64_t* adj, int32_t* clique_out, int32_t* size_out, int32_t* seed_out);
+
+}  // namespace cgmr

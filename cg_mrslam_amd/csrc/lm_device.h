@@ -8,7 +8,7 @@
 
 namespace cgmr {
 
-// One per call, in device memory, set up by the host before the first trial (cgmr_api.cpp: tr_run) and read back once per round.
+// One per call, in device memory, set up by the host before the first trial (optimize_host.cpp: tr_run) and read back once per round.
 struct LmState {
   double lambda = 0, nu = 2;                 // current damping and its growth factor on a reject
   double tau = 1e-5, initial_lambda = -1;    // g2o's properties (initial_lambda <= 0: tau * max |H_jj|)

@@ -5,7 +5,7 @@
 //   BlockSolver::setLambda (H + lambda I)               -> k_lm_damp
 //   computeScale, the rho test, lambda / nu, push / pop -> k_lm_decide, k_tr_commit (tr_kernels.hip)
 //
-// One trial is a fixed launch sequence whatever its outcome (cgmr_api.cpp: LmPolicy::trial): linearise, assemble, [init,] damp,
+// One trial is a fixed launch sequence whatever its outcome (optimize_host.cpp: LmPolicy::trial): linearise, assemble, [init,] damp,
 // factor, solve, update, chi-only linearise, decide, commit.  Re-linearising at unchanged poses yields the same terms bit for
 // bit, so a rejected trial needs nothing but the restored poses.  The state (lambda, nu, counters, records) lives on the
 // device: the host queues trials without reading anything back in between.  Once the call has terminated, every later

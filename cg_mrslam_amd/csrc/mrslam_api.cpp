@@ -26,12 +26,6 @@
 
 using namespace cgmr;
 
-#define HIP_TRY(ctx, call)                                                                      \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess) return set_err(ctx, CGMR_E_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
-  } while (0)
-
 namespace {
 
 struct DevBuf {                       // growable device array; contents survive growth
@@ -204,6 +198,48 @@ int pinned_poses_reserve(cgmr_graph* g, int nV) {
   HIP_TRY(ctx, hipHostMalloc((void**)&g->pinned_poses, 24 * g->pinned_poses_cap, hipHostMallocDefault));
   return 0;
 }
+
+// What cgmr_graph_optimize and cgmr_graph_optimize_gnc share around their *_run.  The system the graph solves now: the level-0
+// edges from its device arrays (own edges, then the received ones), the received stars' gauge vertices as hubs of the ordering.
+// begin(): the clock, the hubs, the landing zone of the estimates -- they come back in the solve's own final wait: the
+// condensed graphs that follow pick their gauges from the host copy, the caller's next key frame dead-reckons from it
+// (cgmr_graph_get_poses: no device round trip then) --, the LM / dogleg records cleared.  end(): the host copy and what was solved.
+struct GraphSolve {
+  cgmr_graph* g;
+  const int nV, nE, nA;
+  GnEdges Ed;
+  std::vector<int32_t> hubs;
+  GnSystem sys;
+  double t0 = 0;
+  explicit GraphSolve(cgmr_graph* graph)
+      : g(graph), nV((int)g->ids.size()), nE((int)g->all_ef.size()), nA((int)g->ef.size()),
+        sys{nV, (double*)g->d_poses.ptr, g->fixed.data(), nE, g->all_ef.data(), g->all_et.data()} {
+    Ed.meas_a = (const double*)g->d_meas_a.ptr; Ed.info_a = (const double*)g->d_info_a.ptr;
+    Ed.meas_b = g->d_meas_b; Ed.info_b = g->d_info_b;
+    Ed.nA = nA; Ed.n_active = nE;
+    g->rk_stats.clear();
+  }
+  int begin() {
+    t0 = wall_s();
+    hubs = received_hubs(g);
+    sys.hub_vertices = hubs.data(); sys.n_hub_vertices = (int)hubs.size();
+    const int rc = pinned_poses_reserve(g, nV);
+    if (rc) return rc;
+    g->ctx->poses_out_host = g->pinned_poses;                    // (the estimates ride in every wait of the driver: the last one counts)
+    g->lm_lambda.clear(); g->lm_trials.clear(); g->dl_delta.clear(); g->dl_trials.clear(); g->dl_step.clear();
+    return 0;
+  }
+  static bool ended(int rc) { return rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE; }
+  int end(int rc) {
+    g->ctx->poses_out_host = nullptr;
+    g->h_poses_fresh = ended(rc);
+    if (g->h_poses_fresh) memcpy(g->h_poses.data(), g->pinned_poses, 24 * (size_t)nV);
+    g->last_optimize_seconds = wall_s() - t0;
+    g->solved_ef = g->all_ef; g->solved_et = g->all_et;
+    g->solved_nV = nV; g->solved_nA = nA;
+    return rc;
+  }
+};
 
 // some own edge, or the received class, carries a robust kernel other than none
 bool any_robust_kernel(const cgmr_graph* g) {
@@ -580,13 +616,10 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out) {
   if (!g->ctx) return gerr(g, CGMR_E_NO_DEVICE, "cgmr_graph_optimize: the graph was created without a device context");
   cgmr_ctx* ctx = g->ctx;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int nV = (int)g->ids.size(), nE = (int)g->all_ef.size();
-  if (nV == 0) return CGMR_OK;
-  GnEdges Ed;
-  Ed.meas_a = (const double*)g->d_meas_a.ptr; Ed.info_a = (const double*)g->d_info_a.ptr;
-  Ed.meas_b = g->d_meas_b; Ed.info_b = g->d_info_b;
-  Ed.nA = (int)g->ef.size(); Ed.n_active = nE;
-  g->rk_stats.clear();
+  if (g->ids.empty()) return CGMR_OK;
+  GraphSolve S(g);
+  GnEdges& Ed = S.Ed;
+  const int nE = S.nE;
   if (g->rk_dev) {                    // (set once any kernel is: own edges from the device arrays, received ones from the class)
     Ed.robust = true;
     Ed.rk = {(const uint8_t*)g->d_rk_kind.ptr, (const double*)g->d_rk_delta.ptr, nullptr, g->rk_recv_delta, g->rk_recv_kind};
@@ -612,58 +645,34 @@ int cgmr_graph_optimize(cgmr_graph* g, int iters, double* chi2_out) {
       Ed.gnc = true; Ed.ga.mode = kGncReuse; Ed.ga.weight = (double*)g->d_gnc_w.ptr;
     }
   }
-  const double t0 = wall_s();
-  // the gauge vertices of the stars received from the peers (every received edge starts at one): hubs of the ordering
-  const std::vector<int32_t> hubs = received_hubs(g);
-  // the host copy of the estimates comes back in the solve's own final wait: the condensed graphs that follow pick their
-  // gauges from it, the caller's next key frame dead-reckons from it (cgmr_graph_get_poses: no device round trip then)
-  const bool asked = true;
-  {
-    int rc = pinned_poses_reserve(g, nV);
-    if (rc) return rc;
-  }
-  ctx->poses_out_host = g->pinned_poses;
-  int rc;
-  g->lm_lambda.clear();
-  g->lm_trials.clear();
-  g->dl_delta.clear();
-  g->dl_trials.clear();
-  g->dl_step.clear();
+  int rc = S.begin();
+  if (rc) return rc;
   if (g->algorithm == CGMR_ALG_LEVENBERG) {
     std::vector<double> lam(iters);
     std::vector<int32_t> tri(iters);
     int32_t done = 0;
-    rc = lm_run(ctx, nV, (double*)g->d_poses.ptr, g->fixed.data(), nE, g->all_ef.data(), g->all_et.data(), Ed, iters,
-                g->lm_params_set ? &g->lm_params : nullptr, chi2_out, lam.data(), tri.data(), &done, hubs.data(), (int)hubs.size());
+    rc = lm_run(ctx, S.sys, Ed, iters, g->lm_params_set ? &g->lm_params : nullptr, {chi2_out, lam.data(), tri.data(), &done});
     if (rc == CGMR_OK) { g->lm_lambda.assign(lam.begin(), lam.begin() + done); g->lm_trials.assign(tri.begin(), tri.begin() + done); }
   } else if (g->algorithm == CGMR_ALG_DOGLEG) {
     std::vector<double> del(iters);
     std::vector<int32_t> tri(iters), stp(iters);
     int32_t done = 0;
-    rc = dl_run(ctx, nV, (double*)g->d_poses.ptr, g->fixed.data(), nE, g->all_ef.data(), g->all_et.data(), Ed, iters,
-                g->dl_params_set ? &g->dl_params : nullptr, chi2_out, del.data(), tri.data(), stp.data(), &done, hubs.data(),
-                (int)hubs.size());
-    if (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE) {
+    rc = dl_run(ctx, S.sys, Ed, iters, g->dl_params_set ? &g->dl_params : nullptr, {chi2_out, del.data(), tri.data(), stp.data(), &done});
+    if (S.ended(rc)) {
       g->dl_delta.assign(del.begin(), del.begin() + done);
       g->dl_trials.assign(tri.begin(), tri.begin() + done);
       g->dl_step.assign(stp.begin(), stp.begin() + done);
     }
   } else {
-    rc = gn_run(ctx, nV, (double*)g->d_poses.ptr, g->fixed.data(), nE, g->all_ef.data(), g->all_et.data(), Ed, iters, chi2_out,
-                hubs.data(), (int)hubs.size());
+    rc = gn_run(ctx, S.sys, Ed, iters, chi2_out);
   }
-  ctx->poses_out_host = nullptr;
-  g->h_poses_fresh = asked && (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE);
-  if (Ed.rk.stats && (rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE)) {
+  if (Ed.rk.stats && S.ended(rc)) {
+    ctx->poses_out_host = nullptr; g->h_poses_fresh = true;   // (what end() does first: a failed read-back leaves the graph as it always has)
     g->rk_stats.resize(2 * (size_t)nE);
     HIP_TRY(ctx, hipMemcpyAsync(g->rk_stats.data(), Ed.rk.stats, 16 * (size_t)nE, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
-  if (g->h_poses_fresh) memcpy(g->h_poses.data(), g->pinned_poses, 24 * (size_t)nV);
-  g->last_optimize_seconds = wall_s() - t0;
-  g->solved_ef = g->all_ef; g->solved_et = g->all_et;
-  g->solved_nV = nV; g->solved_nA = (int)g->ef.size();
-  return rc;
+  return S.end(rc);
 }
 
 int cgmr_graph_set_algorithm(cgmr_graph* g, int algorithm, const cgmr_lm_params* params) {
@@ -776,16 +785,12 @@ int cgmr_graph_optimize_gnc(cgmr_graph* g, const cgmr_gnc_params* params, double
   if (any_robust_kernel(g))
     return gerr(g, CGMR_E_INVALID, "cgmr_graph_optimize_gnc: not combined with robust kernels (cgmr_graph_set_edge_robust / _set_received_robust)");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int nV = (int)g->ids.size(), nE = (int)g->all_ef.size(), nA = (int)g->ef.size();
   if (outer_done) *outer_done = 0;
   for (int k = 0; k < P.max_outer; k++) { if (mu_out) mu_out[k] = 0.0; if (partial_out) partial_out[k] = 0; }
   for (int k = 0; cost_out && k <= P.max_outer; k++) cost_out[k] = 0.0;
-  if (nV == 0) return CGMR_OK;
-  GnEdges Ed;
-  Ed.meas_a = (const double*)g->d_meas_a.ptr; Ed.info_a = (const double*)g->d_info_a.ptr;
-  Ed.meas_b = g->d_meas_b; Ed.info_b = g->d_info_b;
-  Ed.nA = nA; Ed.n_active = nE;
-  g->rk_stats.clear();
+  if (g->ids.empty()) return CGMR_OK;
+  GraphSolve S(g);
+  const int nE = S.nE, nA = S.nA;
   const double c0 = P.default_barc_sq > 0 ? P.default_barc_sq : gnc_default_barc_sq(3);
   std::vector<double> hc((size_t)nE), hw((size_t)nE, 1.0), hr((size_t)nE, 0.0);
   std::vector<uint8_t> hk((size_t)nE);
@@ -794,27 +799,15 @@ int cgmr_graph_optimize_gnc(cgmr_graph* g, const cgmr_gnc_params* params, double
     hc[k] = c > 0 ? c : c0;
     hk[k] = k < nA ? g->gnc_known[k] : (g->gnc_recv_known ? 1 : 0);
   }
-  const double t0 = wall_s();
-  const std::vector<int32_t> hubs = received_hubs(g);
-  int rc = pinned_poses_reserve(g, nV);
+  int rc = S.begin();
   if (rc) return rc;
-  ctx->poses_out_host = g->pinned_poses;                         // (the estimates ride in every wait of the driver: the last one counts)
-  g->lm_lambda.clear(); g->lm_trials.clear(); g->dl_delta.clear(); g->dl_trials.clear(); g->dl_step.clear();
-  rc = gnc_run(ctx, nV, (double*)g->d_poses.ptr, g->fixed.data(), nE, g->all_ef.data(), g->all_et.data(), Ed, P, hc.data(), hk.data(),
-               mu_out, cost_out, partial_out, outer_done, hw.data(), hr.data(), hubs.data(), (int)hubs.size());
-  ctx->poses_out_host = nullptr;
-  const bool ended = rc == CGMR_OK || rc <= CGMR_E_CHOLESKY_BASE;
-  g->h_poses_fresh = ended;
-  if (ended) {
-    memcpy(g->h_poses.data(), g->pinned_poses, 24 * (size_t)nV);
+  rc = gnc_run(ctx, S.sys, S.Ed, P, hc.data(), hk.data(), {mu_out, cost_out, partial_out, outer_done, hw.data(), hr.data()});
+  if (S.ended(rc)) {
     g->rk_stats.assign(hr.begin(), hr.end());                     // cgmr_graph_edge_stats: r of every edge, then its weight
     g->rk_stats.insert(g->rk_stats.end(), hw.begin(), hw.end());
   }
   if (rc == CGMR_OK) std::copy(hw.begin(), hw.begin() + nA, g->gnc_w.begin());   // (a Cholesky code leaves the stored weights alone)
-  g->last_optimize_seconds = wall_s() - t0;
-  g->solved_ef = g->all_ef; g->solved_et = g->all_et;
-  g->solved_nV = nV; g->solved_nA = nA;
-  return rc;
+  return S.end(rc);
 }
 
 int cgmr_graph_edge_stats(const cgmr_graph* g, int cap, double* edge_chi2_out, double* weight_out) {

@@ -146,7 +146,7 @@ def graph(name):
 
 
 def level_chunks(t, top, n_levels):
-    """Border rows per work item of every launch level, by the rule of gn_upload (cgmr_api.cpp): kLeafChunkRows on a level of
+    """Border rows per work item of every launch level, by the rule of gn_upload (gn_host.cpp): kLeafChunkRows on a level of
     leaves, else kMidChunkRows, kTopChunkRows where the level has at most kTopChunkFronts fronts (the top block's left out)."""
     out = []
     for l in range(n_levels):

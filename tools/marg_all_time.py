@@ -71,7 +71,7 @@ line("marginals, 1000 queries, warm", w, d)
 nz = np.abs(cq).sum(axis=(1, 2)) > 0
 rel = np.linalg.norm(cov[q1000] - cq, axis=(1, 2))[nz] / np.linalg.norm(cq, axis=(1, 2))[nz]
 print(f"  largest difference marginals_all / marginals on those 1000: {rel.max():.2e}")
-# cgmr_marginals' work space for nK queries (cgmr_api.cpp marginal_driver): Y (3 nf x m), the border vectors
+# cgmr_marginals' work space for nK queries (marginals_host.cpp marginal_driver): Y (3 nf x m), the border vectors
 # ((3 * border rows + 3) x m), the Gram partials (nchunk x 16 x m), m = 4 nK padded to 16
 nf = V - int(g["fixed"].sum())
 m = (4 * V + 15) // 16 * 16

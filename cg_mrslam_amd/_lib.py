@@ -54,10 +54,13 @@ _SYMBOLS = [
     "cgmr_gn_optimize_mixture", "cgmr_gn_optimize_mixture_dev", "cgmr_lm_optimize_mixture", "cgmr_lm_optimize_mixture_dev",
     "cgmr_dl_optimize_mixture", "cgmr_dl_optimize_mixture_dev", "cgmr_mixture_select",
     "cgmr_closure_consistency", "cgmr_max_clique_greedy", "cgmr_switches",
+    "cgmr_closure_consistency_exact", "cgmr_max_clique_exact",
 ]
 
 JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)
 PCM_MAX_CLOSURES = 1024       # include/cgmr.h: CGMR_PCM_MAX_CLOSURES (candidates of a consistency call, vertices of a clique call)
+EXACT_DEFAULT_NODE_LIMIT = 512    # include/cgmr.h: CGMR_EXACT_DEFAULT_NODE_LIMIT (nodes per root and round of the exact clique search)
+EXACT_ROUNDS = 2              # csrc/pcm_device.h: CGMR_EXACT_ROUNDS (a call expands at most n * EXACT_ROUNDS * node_limit nodes)
 
 
 def declared_symbols():
@@ -981,6 +984,36 @@ class Context:
         clique, size, seed = np.full(n, -1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.full(1, -1, dtype=np.int32)
         self._check(self.lib.cgmr_max_clique_greedy(self.h, C.c_int(n), _ptr(words), _ptr(clique), _ptr(size), _ptr(seed)))
         return clique[:int(size[0])].copy(), int(seed[0])
+
+    def closure_consistency_exact(self, poses, fixed, ef, et, meas, info, cl_a, cl_b, cl_meas, cl_info, gamma,
+                                  node_limit=EXACT_DEFAULT_NODE_LIMIT, kind=None, delta=1.0):
+        """closure_consistency with the exact maximum clique of adj (cgmr_closure_consistency_exact): ``(d2, adj, clique,
+        proven)``, d2 and adj the plain call's.  ``node_limit``: as for max_clique_exact; when ``proven`` is False the clique is
+        the best found, never smaller than the greedy one.  ``kind`` / ``delta``: robust kernels, (e2, weights) appended."""
+        a, b = self._pair_arrays(cl_a, cl_b)
+        n = len(a)
+        cm = np.ascontiguousarray(cl_meas, dtype=np.float64).reshape(n, 3)
+        ci = np.ascontiguousarray(cl_info, dtype=np.float64).reshape(n, 6)
+        W = (n + 63) // 64
+        d2, words = np.zeros((n, n)), np.zeros((n, W), dtype=np.uint64)
+        clique, size, proven = np.full(n, -1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+        st = self._joint_call("cgmr_closure_consistency_exact", poses, fixed, ef, et, meas, info,
+                              (C.c_int(n), _ptr(a), _ptr(b), _ptr(cm), _ptr(ci), C.c_double(float(gamma)), _ptr(d2), _ptr(words),
+                               C.c_int64(int(node_limit)), _ptr(clique), _ptr(size), _ptr(proven)), kind, delta)
+        return (d2, self._adj_bool(words, n), clique[:int(size[0])].copy(), bool(proven[0])) + st
+
+    def max_clique_exact(self, adj, node_limit=EXACT_DEFAULT_NODE_LIMIT):
+        """``(clique, proven, nodes)`` of a symmetric adjacency with a clear diagonal, given as for max_clique_greedy: a maximum
+        clique (members ascending) by branch and bound behind the greedy one (cgmr_max_clique_exact).  Every root's search
+        stops after ``node_limit`` nodes in each of its EXACT_ROUNDS rounds; ``proven`` is True when none was stopped in its
+        last round -- then the size is the clique number --, otherwise the clique is the best found, never smaller than the
+        greedy one.  ``nodes``: the nodes expanded, at most n * EXACT_ROUNDS * node_limit.  Deterministic."""
+        words, n = self._adj_words(adj)
+        clique, size, proven = np.full(n, -1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+        nodes = np.zeros(1, dtype=np.int64)
+        self._check(self.lib.cgmr_max_clique_exact(self.h, C.c_int(n), _ptr(words), C.c_int64(int(node_limit)), _ptr(clique),
+                                                   _ptr(size), _ptr(proven), _ptr(nodes)))
+        return clique[:int(size[0])].copy(), bool(proven[0]), int(nodes[0])
 
     def set_symbolic_cache(self, on: bool):
         """Reuse of the ordering / symbolic analysis / structure upload across calls on the same edge list (default on)."""

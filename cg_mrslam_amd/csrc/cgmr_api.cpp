@@ -797,6 +797,23 @@ int cgmr_max_clique_greedy(cgmr_ctx* ctx, int n, const uint64_t* adj_bits, int32
   return clique_driver(ctx, n, adj_bits, clique_out, clique_size_out, seed_out);
 }
 
+int cgmr_closure_consistency_exact(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                                   const int32_t* et, const double* meas, const double* info, int nC, const int32_t* cl_a,
+                                   const int32_t* cl_b, const double* cl_meas, const double* cl_info, double gamma, double* d2_out,
+                                   uint64_t* adj_out, int64_t node_limit, int32_t* clique_out, int32_t* clique_size_out,
+                                   int32_t* proven_out, const cgmr_robust* rk) {
+  const CliqueExact ex{node_limit, proven_out, nullptr};
+  return pcm_driver(ctx, host_call(nV, poses, fixed, nE, ef, et, meas, info, {false, rk}), nC, cl_a, cl_b, cl_meas, cl_info, gamma, d2_out, adj_out, clique_out,
+      clique_size_out, nullptr, &ex);
+}
+
+int cgmr_max_clique_exact(cgmr_ctx* ctx, int n, const uint64_t* adj_bits, int64_t node_limit, int32_t* clique_out,
+                          int32_t* clique_size_out, int32_t* proven_out, int64_t* nodes_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  const CliqueExact ex{node_limit, proven_out, nodes_out};
+  return clique_driver(ctx, n, adj_bits, clique_out, clique_size_out, nullptr, &ex);
+}
+
 int cgmr_set_symbolic_cache(cgmr_ctx* ctx, int on) {
   if (!ctx) return CGMR_E_INVALID;
   ctx->sym_cache_on = on != 0;

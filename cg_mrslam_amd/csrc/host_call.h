@@ -49,9 +49,13 @@ int marginals_all_driver(cgmr_ctx* ctx, const HostCall& c, double* cov_out, doub
 int joint_driver(cgmr_ctx* ctx, const char* who, int mode, const HostCall& c, int nQ, const int32_t* va, const int32_t* vb,
                  double* out_a, double* out_b, double* out_c, const double* hyp_meas, const double* hyp_info, bool obs = false,
                  const uint8_t* obs_kind = nullptr);
+// pcm_driver / clique_driver with `ex`: the exact solver behind the greedy clique (cgmr_closure_consistency_exact,
+// cgmr_max_clique_exact); proven_out takes seed_out's place among the outputs, seed_out is not read.  Without: the greedy pair.
+struct CliqueExact { int64_t node_limit; int32_t* proven_out; int64_t* nodes_out; };
 int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, const int32_t* cb, const double* cmeas,
                const double* cinfo, double gamma, double* d2_out, uint64_t* adj_out, int32_t* clique_out, int32_t* size_out,
-               int32_t* seed_out);
-int clique_driver(cgmr_ctx* ctx, int n, const uint64_t* adj, int32_t* clique_out, int32_t* size_out, int32_t* seed_out);
+               int32_t* seed_out, const CliqueExact* ex = nullptr);
+int clique_driver(cgmr_ctx* ctx, int n, const uint64_t* adj, int32_t* clique_out, int32_t* size_out, int32_t* seed_out,
+                  const CliqueExact* ex = nullptr);
 
 }  // namespace cgmr

@@ -445,14 +445,46 @@ int joint_driver(cgmr_ctx* ctx, const char* who, int mode, const HostCall& c, in
 
 // What the clique kernels of pcm_kernels.hip work in, behind whatever the caller has put into L: the seeds' member bits and
 // sizes and the result (size, seed, members).
+// With `exact`, behind them what the exact solver of clique_exact_kernels.hip works in (pcm_device.h: ExactWork), its result
+// (size, proven, members) and its node count: the order, the adjacency in bit positions, per round and root the clique found,
+// its size, the stopped flag and the nodes, and the search stack -- one P of W words per root and depth, n levels deep, so
+// 8 n^2 W bytes (128 MiB at n = 1024), sized here from n and W.
 struct CliqueLayout {
   size_t o_sb, o_ss, o_out;
-  CliqueLayout(Layout256& L, int n) : o_sb(L.add(8 * (size_t)n * ((n + 63) / 64))), o_ss(L.add(4 * (size_t)n)), o_out(L.add(4 * ((size_t)n + 2))) {}
+  size_t o_xvp = 0, o_xpv = 0, o_xB = 0, o_xbits = 0, o_xsize = 0, o_xstop = 0, o_xnodes = 0, o_xstack = 0, o_xout = 0, o_xtotal = 0;
+  CliqueLayout(Layout256& L, int n, bool exact = false)
+      : o_sb(L.add(8 * (size_t)n * ((n + 63) / 64))), o_ss(L.add(4 * (size_t)n)), o_out(L.add(4 * ((size_t)n + 2))) {
+    if (!exact) return;
+    const size_t N = (size_t)n, W = (N + 63) / 64, R = CGMR_EXACT_ROUNDS;
+    o_xvp = L.add(4 * N); o_xpv = L.add(4 * N); o_xB = L.add(8 * N * W); o_xbits = L.add(8 * R * N * W);
+    o_xsize = L.add(4 * R * N); o_xstop = L.add(4 * R * N); o_xnodes = L.add(8 * R * N); o_xstack = L.add(8 * N * N * W);
+    o_xout = L.add(4 * (N + 2)); o_xtotal = L.add(8);
+  }
+  ExactWork work(char* d) const {
+    ExactWork X;
+    X.vtx_of_pos = (int32_t*)(d + o_xvp); X.pos_of_vtx = (int32_t*)(d + o_xpv);
+    X.B = (unsigned long long*)(d + o_xB); X.bits = (unsigned long long*)(d + o_xbits);
+    X.size = (int32_t*)(d + o_xsize); X.out_of_nodes = (int32_t*)(d + o_xstop);
+    X.nodes = (long long*)(d + o_xnodes); X.stack = (unsigned long long*)(d + o_xstack);
+    return X;
+  }
+  // the greedy launches, then with `ex` the exact ones; where the result (n + 2 ints) lies afterwards
+  size_t launch(hipStream_t st, char* d, int n, size_t o_adj, const CliqueExact* ex) const {
+    launch_clique_greedy(st, n, (const unsigned long long*)(d + o_adj), (unsigned long long*)(d + o_sb), (int32_t*)(d + o_ss),
+                         (int32_t*)(d + o_out));
+    if (!ex) return o_out;
+    launch_clique_exact(st, n, (const unsigned long long*)(d + o_adj), ex->node_limit, (const int32_t*)(d + o_out), work(d),
+                        (int32_t*)(d + o_xout), (long long*)(d + o_xtotal));
+    return o_xout;
+  }
 };
-// ... and where its result goes on the host once the stream has been waited for (res: n + 2 ints)
-static void clique_result_out(const std::vector<int32_t>& res, int n, int32_t* clique_out, int32_t* size_out, int32_t* seed_out) {
+// ... and where its result goes on the host once the stream has been waited for (res: n + 2 ints; res[1] the seed, or with `ex`
+// proven, and the node count `total`)
+static void clique_result_out(const std::vector<int32_t>& res, int n, int32_t* clique_out, int32_t* size_out, int32_t* seed_out,
+                              const CliqueExact* ex = nullptr, int64_t total = 0) {
   *size_out = res[0];
-  *seed_out = res[1];
+  if (ex) { *ex->proven_out = res[1]; if (ex->nodes_out) *ex->nodes_out = total; }
+  else *seed_out = res[1];
   memcpy(clique_out, res.data() + 2, 4 * (size_t)n);
 }
 
@@ -460,22 +492,26 @@ static void clique_result_out(const std::vector<int32_t>& res, int n, int32_t* c
 // every lower Gram tile (the macro-tile path), then the kernels of pcm_kernels.hip on the tiles where they lie: d2 of every
 // pair, its rows as bit words, the greedy clique of every seed and the best of them.  In profiling mode the launch classes
 // 9 (solve + Gram), 10 (k_closure_consistency) and 11 (bits and clique) of cgmr_gn_kernel_times_ex are timed and collected.
+// With `ex` (cgmr_closure_consistency_exact): the exact solver's launches behind the greedy ones, in class 11 as well.
 int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, const int32_t* cb, const double* cmeas,
                const double* cinfo, double gamma, double* d2_out, uint64_t* adj_out, int32_t* clique_out, int32_t* size_out,
-               int32_t* seed_out) {
-  const char* who = "cgmr_closure_consistency";
+               int32_t* seed_out, const CliqueExact* ex) {
+  const char* who = ex ? "cgmr_closure_consistency_exact" : "cgmr_closure_consistency";
+  if (ex) seed_out = ex->proven_out;                               // (the third of the clique's outputs, for the checks below)
   MargCall call(ctx, c);
   int rc = call.args(nC < 0 || !c.fixed || (nC > 0 && (!ca || !cb || !cmeas || !cinfo)), who);
   if (rc) return rc;
   const bool want_clique = clique_out || size_out || seed_out;
   if (want_clique && !(clique_out && size_out && seed_out))
-    return set_err(ctx, CGMR_E_INVALID, "%s: clique_out, clique_size_out and seed_out are given together or not at all", who);
+    return set_err(ctx, CGMR_E_INVALID, "%s: clique_out, clique_size_out and %s are given together or not at all", who,
+                   ex ? "proven_out" : "seed_out");
   if (nC > CGMR_PCM_MAX_CLOSURES)
     return set_err(ctx, CGMR_E_INVALID, "%s: %d closures, at most CGMR_PCM_MAX_CLOSURES = %d", who, nC, CGMR_PCM_MAX_CLOSURES);
   for (int k = 0; k < nC; k++)
     if (ca[k] < 0 || ca[k] >= c.nV || cb[k] < 0 || cb[k] >= c.nV)
       return set_err(ctx, CGMR_E_INVALID, "%s: closure %d (%d -> %d) has an endpoint outside [0, %d)", who, k, ca[k], cb[k], c.nV);
   if (!(std::isfinite(gamma) && gamma > 0)) return set_err(ctx, CGMR_E_INVALID, "%s: gamma must be finite and > 0", who);
+  if (ex && ex->node_limit <= 0) return set_err(ctx, CGMR_E_INVALID, "%s: node_limit must be > 0", who);
   if (nC == 0) { if (size_out) *size_out = 0; return CGMR_OK; }
   // the unique endpoints, in order of first appearance: 4 columns of Y each (at most 2 nC <= CGMR_JOINT_MAX_QUERIES)
   std::vector<int32_t> slot_of(c.nV, -1), uq;
@@ -510,7 +546,7 @@ int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, cons
   const size_t o_part = L.add(JG.nsplit > 1 ? 2048 * (size_t)JG.nsplit * (size_t)JG.ntile : 0), o_G = L.add(2048 * (size_t)JG.ntile),
                o_sl = L.add(8 * n), o_ca = L.add(4 * n), o_cb = L.add(4 * n), o_cm = L.add(24 * n), o_ci = L.add(48 * n),
                o_d2 = L.add(8 * n * n), o_adj = L.add(8 * n * W);
-  const CliqueLayout CL(L, nC);
+  const CliqueLayout CL(L, nC, ex && want_clique);
   rc = call.stage();
   if (rc) return rc;
   char* d = call.d;
@@ -527,6 +563,7 @@ int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, cons
   C.a = (const int32_t*)(d + o_ca); C.b = (const int32_t*)(d + o_cb); C.slot = (const int32_t*)(d + o_sl);
   C.meas = (const double*)(d + o_cm); C.info = (const double*)(d + o_ci);
   std::vector<int32_t> res(n + 2, 0);
+  int64_t total = 0;
   GnPassOpts pass;
   pass.solve = pass.update_poses = false;
   rc = call.run(pass, [&]() -> int {
@@ -538,16 +575,16 @@ int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, cons
         launch_joint_gram(st, ML.n, ML.m, (const double*)(d + ML.o_Y), JG);
       });
     KT.run(10, 1, [&] { launch_closure_consistency(st, C, call.dp, JG.G, (double*)(d + o_d2)); });
+    size_t o_res = CL.o_out;
     if (adj_out || want_clique)
-      KT.run(11, want_clique ? 3 : 1, [&] {
+      KT.run(11, want_clique ? (ex ? 6 + CGMR_EXACT_ROUNDS : 3) : 1, [&] {
         launch_consistency_bits(st, nC, (const double*)(d + o_d2), gamma, (unsigned long long*)(d + o_adj));
-        if (want_clique)
-          launch_clique_greedy(st, nC, (const unsigned long long*)(d + o_adj), (unsigned long long*)(d + CL.o_sb), (int32_t*)(d + CL.o_ss),
-                               (int32_t*)(d + CL.o_out));
+        if (want_clique) o_res = CL.launch(st, d, nC, o_adj, ex);
       });
     if (d2_out) HIP_TRY(ctx, hipMemcpyAsync(d2_out, d + o_d2, 8 * n * n, hipMemcpyDeviceToHost, st));
     if (adj_out) HIP_TRY(ctx, hipMemcpyAsync(adj_out, d + o_adj, 8 * n * W, hipMemcpyDeviceToHost, st));
-    if (want_clique) HIP_TRY(ctx, hipMemcpyAsync(res.data(), d + CL.o_out, 4 * (n + 2), hipMemcpyDeviceToHost, st));
+    if (want_clique) HIP_TRY(ctx, hipMemcpyAsync(res.data(), d + o_res, 4 * (n + 2), hipMemcpyDeviceToHost, st));
+    if (want_clique && ex) HIP_TRY(ctx, hipMemcpyAsync(&total, d + CL.o_xtotal, 8, hipMemcpyDeviceToHost, st));
     return 0;
   });
   if (ctx->profiling) profile_collect(ctx);
@@ -557,16 +594,21 @@ int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, cons
     if (d2_out) memset(d2_out, 0, 8 * n * n);
     if (adj_out) memset(adj_out, 0, 8 * n * W);
     std::fill(res.begin(), res.end(), 0);
+    total = 0;
   }
-  if (want_clique && (rc == CGMR_OK || rc == CGMR_E_CHOLESKY_BASE)) clique_result_out(res, nC, clique_out, size_out, seed_out);
+  if (want_clique && (rc == CGMR_OK || rc == CGMR_E_CHOLESKY_BASE)) clique_result_out(res, nC, clique_out, size_out, seed_out, ex, total);
   return rc;
 }
 
-// cgmr_max_clique_greedy: the clique kernels alone on a caller's adjacency words, checked on the host first
-int clique_driver(cgmr_ctx* ctx, int n, const uint64_t* adj, int32_t* clique_out, int32_t* size_out, int32_t* seed_out) {
-  const char* who = "cgmr_max_clique_greedy";
+// cgmr_max_clique_greedy: the clique kernels alone on a caller's adjacency words, checked on the host first.  With `ex`
+// (cgmr_max_clique_exact): the exact solver's launches behind them.
+int clique_driver(cgmr_ctx* ctx, int n, const uint64_t* adj, int32_t* clique_out, int32_t* size_out, int32_t* seed_out,
+                  const CliqueExact* ex) {
+  const char* who = ex ? "cgmr_max_clique_exact" : "cgmr_max_clique_greedy";
+  if (ex) seed_out = ex->proven_out;
   if (n < 0 || !size_out || (n > 0 && (!adj || !clique_out || !seed_out))) return set_err(ctx, CGMR_E_INVALID, "%s: null or negative argument", who);
   if (n > CGMR_PCM_MAX_CLOSURES) return set_err(ctx, CGMR_E_INVALID, "%s: %d vertices, at most CGMR_PCM_MAX_CLOSURES = %d", who, n, CGMR_PCM_MAX_CLOSURES);
+  if (ex && ex->node_limit <= 0) return set_err(ctx, CGMR_E_INVALID, "%s: node_limit must be > 0", who);
   if (n == 0) { *size_out = 0; return CGMR_OK; }
   const int W = (n + 63) / 64;
   auto bit = [&](int k, int l) { return (int)((adj[(size_t)k * W + (l >> 6)] >> (l & 63)) & 1u); };
@@ -581,7 +623,7 @@ int clique_driver(cgmr_ctx* ctx, int n, const uint64_t* adj, int32_t* clique_out
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   Layout256 L;
   const size_t o_adj = L.add(8 * (size_t)n * W);
-  const CliqueLayout CL(L, n);
+  const CliqueLayout CL(L, n, ex != nullptr);
   int rc = arena_reserve(ctx, ctx->io_arena, L.off + 256);
   if (rc) return rc;
   char* d = ctx->io_arena.ptr;
@@ -589,15 +631,15 @@ int clique_driver(cgmr_ctx* ctx, int n, const uint64_t* adj, int32_t* clique_out
   std::vector<int32_t> res((size_t)n + 2, 0);
   HIP_TRY(ctx, hipMemcpyAsync(d + o_adj, adj, 8 * (size_t)n * W, hipMemcpyHostToDevice, st));
   KTimer KT{ctx, st};
-  KT.run(11, 2, [&] {
-    launch_clique_greedy(st, n, (const unsigned long long*)(d + o_adj), (unsigned long long*)(d + CL.o_sb), (int32_t*)(d + CL.o_ss),
-                         (int32_t*)(d + CL.o_out));
-  });
-  HIP_TRY(ctx, hipMemcpyAsync(res.data(), d + CL.o_out, 4 * ((size_t)n + 2), hipMemcpyDeviceToHost, st));
+  size_t o_res = CL.o_out;
+  int64_t total = 0;
+  KT.run(11, ex ? 5 + CGMR_EXACT_ROUNDS : 2, [&] { o_res = CL.launch(st, d, n, o_adj, ex); });
+  HIP_TRY(ctx, hipMemcpyAsync(res.data(), d + o_res, 4 * ((size_t)n + 2), hipMemcpyDeviceToHost, st));
+  if (ex) HIP_TRY(ctx, hipMemcpyAsync(&total, d + CL.o_xtotal, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   HIP_TRY(ctx, hipGetLastError());
   if (ctx->profiling) profile_collect(ctx);
-  clique_result_out(res, n, clique_out, size_out, seed_out);
+  clique_result_out(res, n, clique_out, size_out, seed_out, ex, total);
   return CGMR_OK;
 }
 

@@ -3,7 +3,8 @@
 // joint_marginals_kernels.hip.
 //
 // The clique search is the greedy heuristic PCM implementations use (seed, then repeatedly the candidate with most neighbours
-// left, over every seed): it returns a maximal clique, NOT a maximum one -- it is not an exact solver.
+// left, over every seed): it returns a maximal clique, NOT a maximum one.  The exact solver (clique_exact_kernels.hip;
+// cgmr_max_clique_exact, cgmr_closure_consistency_exact) starts from that clique's size and returns a maximum one.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,5 +43,22 @@ void launch_consistency_bits(hipStream_t st, int n, const double* d2, double gam
 // out[1] its seed, out[2 ..] its members ascending, -1 behind them (out: n + 2 ints).  n >= 1; adj symmetric, zero diagonal.
 void launch_clique_greedy(hipStream_t st, int n, const unsigned long long* adj, unsigned long long* seed_bits, int32_t* seed_size,
                           int32_t* out);
+
+// What the exact solver works in (clique_exact_kernels.hip), W = (n + 63) / 64.  [2][n]: one entry per round and root.
+#define CGMR_EXACT_ROUNDS 2
+struct ExactWork {
+  int32_t *vtx_of_pos = nullptr, *pos_of_vtx = nullptr;          // [n] each: the fixed order as bit positions
+  unsigned long long* B = nullptr;                                // [n * W] the adjacency in bit positions
+  unsigned long long* bits = nullptr;                             // [2][n][W] the clique a root found, in bit positions
+  int32_t *size = nullptr, *out_of_nodes = nullptr;               // [2][n] its size (0: none above the bound); stopped early
+  long long* nodes = nullptr;                                     // [2][n] nodes expanded
+  unsigned long long* stack = nullptr;                            // [n][n][W] one P per root and depth
+};
+// The exact maximum clique behind launch_clique_greedy's result greedy_out (device, n + 2 ints) on the same stream: out[0] its
+// size, out[1] proven (no root stopped at node_limit), out[2 ..] its members ascending, -1 behind them (n + 2 ints);
+// nodes_out[0] the nodes expanded over all roots and rounds, at most n * CGMR_EXACT_ROUNDS * node_limit.  n >= 1,
+// node_limit >= 1.  Five launches more than the greedy two.
+void launch_clique_exact(hipStream_t st, int n, const unsigned long long* adj, long long node_limit, const int32_t* greedy_out,
+                         const ExactWork& X, int32_t* out, long long* nodes_out);
 
 }  // namespace cgmr

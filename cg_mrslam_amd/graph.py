@@ -764,11 +764,14 @@ class GraphSLAM:
             z, cz, d2 = self.ctx.relative_covariance(*a, pairs[:, 0], pairs[:, 1], hm, hi, **kw)[:3]
         return (z, cz) if hypotheses is None else (z, cz, d2)
 
-    def closureConsistency(self, closures, gamma, robust: bool = False):     # noqa: N802
+    def closureConsistency(self, closures, gamma, robust: bool = False, exact: bool = False, node_limit=None):     # noqa: N802
         """Pairwise consistency maximisation over closure candidates that are not (yet) edges: ``closures`` a list of
         ``(i, j, meas, info_upper)`` on vertex indices.  Returns ``(d2 [N, N], adj [N, N] bool, clique, seed)`` as
         Context.closure_consistency does, on the level-0 edges at the current estimates (as relativeCovariance).  The clique is
-        the greedy heuristic's, not an exact maximum.  A typed graph raises ValueError: pose graphs only."""
+        the greedy heuristic's, not an exact maximum.  ``exact``: ``(d2, adj, clique, proven)`` as
+        Context.closure_consistency_exact does, the clique a maximum one when ``proven`` (every root's search stays within
+        ``node_limit`` nodes; None: the binding's default), else the best found and no smaller than the greedy one.  A typed
+        graph raises ValueError: pose graphs only."""
         a, kw, _ = self._joint_args(robust)
         if "vertex_kind" in kw:
             raise ValueError("closureConsistency: pose graphs only (the graph has landmarks or priors)")
@@ -777,13 +780,18 @@ class GraphSLAM:
         cb = np.array([c[1] for c in cl], dtype=np.int32)
         cm = np.array([c[2] for c in cl], dtype=np.float64).reshape(len(cl), 3)
         ci = np.array([c[3] for c in cl], dtype=np.float64).reshape(len(cl), 6)
+        if exact:
+            if node_limit is not None:
+                kw = dict(kw, node_limit=node_limit)
+            return self.ctx.closure_consistency_exact(*a, ca, cb, cm, ci, gamma, **kw)[:4]
         return self.ctx.closure_consistency(*a, ca, cb, cm, ci, gamma, **kw)[:4]
 
     # the default gamma: the 0.99 quantile of chi2 with 3 degrees of freedom (scipy.stats.chi2.ppf(0.99, 3)) -- two candidates
     # that both agree with the graph fail the test together once in a hundred
-    def consistentClosures(self, closures, gamma: float = 11.344866730144373, robust: bool = False):     # noqa: N802
-        """The indices (ascending) of the largest set of pairwise consistent candidates closureConsistency finds."""
-        return self.closureConsistency(closures, gamma, robust)[2]
+    def consistentClosures(self, closures, gamma: float = 11.344866730144373, robust: bool = False, exact: bool = False):     # noqa: N802
+        """The indices (ascending) of the largest set of pairwise consistent candidates closureConsistency finds (``exact``: by
+        the exact search, at its default node limit)."""
+        return self.closureConsistency(closures, gamma, robust, exact)[2]
 
     def observationCovariance(self, pairs, kinds, hypotheses=None, robust: bool = False):     # noqa: N802
         """Data association: for the vertex index pairs ``(pose, b)`` predicted as factors of ``kinds`` (per pair 0 EDGE_SE2,

@@ -254,10 +254,12 @@ class GraphSLAMDriver(GraphSLAM):
         self.lc_polish = lc_polish
         # which buffered candidates become edges: "voting" = LoopClosureChecker (the reference: each candidate made exact in turn,
         # the others' chi2 under a constant information); ("pcm", gamma) = the largest set of pairwise consistent candidates under
-        # the graph's own covariances (GraphSLAM.consistentClosures), gamma the chi2 threshold of a pair's loop
+        # the graph's own covariances (GraphSLAM.consistentClosures), gamma the chi2 threshold of a pair's loop, the set found by
+        # the greedy clique; ("pcm-exact", gamma) = the same with the exact maximum clique (closureConsistency(exact=True)) --
+        # where the search is not proven within its node limit, the clique it returns is used: it is no smaller than the greedy one
         if closure_check != "voting" and not (isinstance(closure_check, tuple) and len(closure_check) == 2 and
-                                              closure_check[0] == "pcm" and float(closure_check[1]) > 0):
-            raise ValueError('closure_check is "voting" or ("pcm", gamma) with gamma > 0')
+                                              closure_check[0] in ("pcm", "pcm-exact") and float(closure_check[1]) > 0):
+            raise ValueError('closure_check is "voting", ("pcm", gamma) or ("pcm-exact", gamma) with gamma > 0')
         self.closure_check = closure_check
 
     # ------------------------------------------------------------------ graph bookkeeping
@@ -469,9 +471,13 @@ class GraphSLAMDriver(GraphSLAM):
             return
         if self.closure_check != "voting":
             edges = self._closures.edges
-            clique = self.consistentClosures([(e["from"], e["to"], e["meas"], e.get("info", SM_INFO)) for e in edges],
-                                             float(self.closure_check[1]))
-            self.log.append(("pcm", len(clique), len(edges)))
+            cands = [(e["from"], e["to"], e["meas"], e.get("info", SM_INFO)) for e in edges]
+            if self.closure_check[0] == "pcm-exact":
+                clique, proven = self.closureConsistency(cands, float(self.closure_check[1]), exact=True)[2:4]
+                self.log.append(("pcm-exact", len(clique), len(edges), bool(proven)))
+            else:
+                clique = self.consistentClosures(cands, float(self.closure_check[1]))
+                self.log.append(("pcm", len(clique), len(edges)))
             if len(clique) >= self.minInliers:
                 for k in clique:
                     e = edges[int(k)]

@@ -571,7 +571,8 @@ int cgmr_gn_kernel_times(const cgmr_ctx* ctx, double seconds_out[8], int64_t lau
 /* ... with the classes added since: 8 front_level = a tree level's factorisation AND its update tiles in one launch
  * (k_front_level, round 6: the levels whose launch is certainly resident at once); 9..11 cgmr_closure_consistency's:
  * 9 the forward solve and the Gram tiles, 10 k_closure_consistency, 11 the bit words and the clique (cgmr_max_clique_greedy:
- * the clique alone) -- zero in a library that does not export those symbols.                                          */
+ * the clique alone; the exact calls: the exact solver's launches with it) -- zero in a library that does not export
+ * those symbols.                                                                                                       */
 int cgmr_gn_kernel_times_ex(const cgmr_ctx* ctx, double seconds_out[12], int64_t launches_out[12]);
 
 /* ------------------------------------------------------------------------------------------
@@ -865,6 +866,46 @@ int cgmr_closure_consistency(cgmr_ctx* ctx, int nV, const double* poses_xyt, con
                              int32_t* clique_out, int32_t* clique_size_out, int32_t* seed_out, const cgmr_robust* rk);
 int cgmr_max_clique_greedy(cgmr_ctx* ctx, int n, const uint64_t* adj_bits, int32_t* clique_out, int32_t* clique_size_out,
                            int32_t* seed_out);
+
+/* The exact maximum clique, as published PCM keeps it (present in C ABI version 105 libraries that export these symbols).
+ * cgmr_max_clique_exact is cgmr_max_clique_greedy, and cgmr_closure_consistency_exact is cgmr_closure_consistency, with a
+ * branch and bound behind the greedy clique; arguments, checks, error texts and their order are the greedy pair's, with
+ * proven_out in seed_out's place and node_limit <= 0 refused as CGMR_E_INVALID as well.  The result is never smaller than the
+ * greedy call's.
+ *
+ * The search (deterministic; csrc/clique_exact_kernels.hip).  The greedy clique G of the call above is the lower bound.  The
+ * vertices are ordered by ascending degree, ties by ascending index.  One sub-problem per root vertex r: C = {r}, P = the
+ * neighbours of r later in the order.  A node (C, P) is expanded as follows.  P empty: C is kept if larger than the best
+ * known to this root (at first |G|, or the round's bound below).  Otherwise P is coloured greedily -- the uncoloured vertices
+ * are taken from the last in the order to the first; a vertex joins the current class unless adjacent to one already in it;
+ * when none is left to try, the next class opens -- and the node is left if |C| + classes <= best.  Else the last vertex
+ * coloured, v, joins: the child (C + v, P & A[v]) is expanded, and then the node itself again with P - v.  Every root stops
+ * after node_limit nodes, its own root node counted; a stopped root keeps the best clique it has found.  Two rounds: in the
+ * first every root runs with the bound |G|; in the second the roots that were stopped run again from their root node, with
+ * the largest size of the first round as the bound.  Bounds pass between rounds only, never between the roots of a round.
+ * The result: the largest clique over roots, ties to the root first in the order; of one root the second round's, and in a
+ * round the first of its final size that the search met; G itself when no root found a larger one.  This need not be the
+ * lexicographically smallest maximum clique.
+ *   clique_out [n] the members ascending, -1 behind them; clique_size_out [1];
+ *   proven_out [1]: 1 when no root was stopped in its last round -- the size is the clique number --, else 0: the set is
+ *     still a clique and still at least as large as the greedy one;
+ *   nodes_out [1] (nullable): the nodes expanded over all roots and rounds, at most 2 n node_limit.
+ * Work: one wavefront per root, at most 2 n node_limit nodes per call; device memory 8 n^2 W bytes of search stack (one set
+ * per root and depth; 128 MiB at n = 1024) beside the greedy call's.  Two calls give identical bytes in every output.
+ * CGMR_EXACT_DEFAULT_NODE_LIMIT is what the Python binding passes: the largest power of two for which a call in which every
+ * one of 1024 roots is stopped in both rounds stays under 0.5 s on an MI355X.  Measured: a node costs one
+ * colouring of its candidate set, so the rate falls with the graph's density -- 4.1e7 nodes/s over a call on G(1024, 0.5),
+ * 1.0e6 on G(1024, 0.995), where the slowest workgroup expands 3.9e3 nodes/s and spends its whole budget: 265 ms of device
+ * time at node_limit 512, 524 ms at 1024.  The closure sets of DESIGN.md 2.14 are proven at the root nodes (N nodes). */
+#define CGMR_EXACT_DEFAULT_NODE_LIMIT 512
+int cgmr_closure_consistency_exact(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                                   const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt,
+                                   const double* info_upper, int nC, const int32_t* cl_a, const int32_t* cl_b,
+                                   const double* cl_meas_xyt, const double* cl_info_upper, double gamma, double* d2_out,
+                                   uint64_t* adj_out, int64_t node_limit, int32_t* clique_out, int32_t* clique_size_out,
+                                   int32_t* proven_out, const cgmr_robust* rk);
+int cgmr_max_clique_exact(cgmr_ctx* ctx, int n, const uint64_t* adj_bits, int64_t node_limit, int32_t* clique_out,
+                          int32_t* clique_size_out, int32_t* proven_out, int64_t* nodes_out);
 
 /* ------------------------------------------------------------------------------------------
  * Generic correlative search (loop-closure / hierarchical / global matching).

@@ -55,6 +55,7 @@ _SYMBOLS = [
     "cgmr_dl_optimize_mixture", "cgmr_dl_optimize_mixture_dev", "cgmr_mixture_select",
     "cgmr_closure_consistency", "cgmr_max_clique_greedy", "cgmr_switches",
     "cgmr_closure_consistency_exact", "cgmr_max_clique_exact",
+    "cgmr_closure_consistency_inter", "cgmr_closure_consistency_inter_exact",
 ]
 
 JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)
@@ -1014,6 +1015,53 @@ class Context:
         self._check(self.lib.cgmr_max_clique_exact(self.h, C.c_int(n), _ptr(words), C.c_int64(int(node_limit)), _ptr(clique),
                                                    _ptr(size), _ptr(proven), _ptr(nodes)))
         return clique[:int(size[0])].copy(), bool(proven[0]), int(nodes[0])
+
+    # inter-robot PCM: candidates that end at a peer's vertex (include/cgmr.h: cgmr_closure_consistency_inter)
+    @staticmethod
+    def _inter_arrays(cl_a, peer_pose, peer_cov, cl_meas, cl_info):
+        a = np.ascontiguousarray(cl_a, dtype=np.int32).reshape(-1)
+        n = len(a)
+        pp = np.ascontiguousarray(peer_pose, dtype=np.float64).reshape(n, 3)
+        pc = None
+        if peer_cov is not None:
+            pc = np.ascontiguousarray(peer_cov, dtype=np.float64)
+            if pc.shape != (3 * n, 3 * n):
+                raise ValueError(f"peer_cov: [{3 * n}, {3 * n}] for {n} candidates, not {pc.shape}")
+        cm = np.ascontiguousarray(cl_meas, dtype=np.float64).reshape(n, 3)
+        ci = np.ascontiguousarray(cl_info, dtype=np.float64).reshape(n, 6)
+        return a, pp, pc, cm, ci
+
+    def closure_consistency_inter(self, poses, fixed, ef, et, meas, info, cl_a, peer_pose, cl_meas, cl_info, gamma, peer_cov=None,
+                                  kind=None, delta=1.0):
+        """closure_consistency for N candidates between this graph and a peer robot's: candidate k goes from the own vertex
+        ``cl_a[k]`` to a peer vertex that is in no graph, known by the pose ``peer_pose[k]`` the peer sent (its frame does not
+        matter: only p_k^-1 p_l enters).  ``peer_cov`` [3 N, 3 N]: the joint covariance of the peer poses, indexed by candidate
+        (only its lower triangle is read); None: the peer's poses are taken as exact, which under-states the loop's covariance
+        -- the gate is then stricter than the data justify.  Returns ``(d2, adj, clique, seed)`` as closure_consistency;
+        ``kind`` / ``delta``: robust kernels on the graph's edges, (e2, weights) appended."""
+        a, pp, pc, cm, ci = self._inter_arrays(cl_a, peer_pose, peer_cov, cl_meas, cl_info)
+        n = len(a)
+        W = (n + 63) // 64
+        d2, words = np.zeros((n, n)), np.zeros((n, W), dtype=np.uint64)
+        clique, size, seed = np.full(n, -1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.full(1, -1, dtype=np.int32)
+        st = self._joint_call("cgmr_closure_consistency_inter", poses, fixed, ef, et, meas, info,
+                              (C.c_int(n), _ptr(a), _ptr(pp), _ptr(pc), _ptr(cm), _ptr(ci), C.c_double(float(gamma)), _ptr(d2),
+                               _ptr(words), _ptr(clique), _ptr(size), _ptr(seed)), kind, delta)
+        return (d2, self._adj_bool(words, n), clique[:int(size[0])].copy(), int(seed[0])) + st
+
+    def closure_consistency_inter_exact(self, poses, fixed, ef, et, meas, info, cl_a, peer_pose, cl_meas, cl_info, gamma,
+                                        peer_cov=None, node_limit=EXACT_DEFAULT_NODE_LIMIT, kind=None, delta=1.0):
+        """closure_consistency_inter with the exact maximum clique of adj (cgmr_closure_consistency_inter_exact): ``(d2, adj,
+        clique, proven)``, as closure_consistency_exact."""
+        a, pp, pc, cm, ci = self._inter_arrays(cl_a, peer_pose, peer_cov, cl_meas, cl_info)
+        n = len(a)
+        W = (n + 63) // 64
+        d2, words = np.zeros((n, n)), np.zeros((n, W), dtype=np.uint64)
+        clique, size, proven = np.full(n, -1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+        st = self._joint_call("cgmr_closure_consistency_inter_exact", poses, fixed, ef, et, meas, info,
+                              (C.c_int(n), _ptr(a), _ptr(pp), _ptr(pc), _ptr(cm), _ptr(ci), C.c_double(float(gamma)), _ptr(d2),
+                               _ptr(words), C.c_int64(int(node_limit)), _ptr(clique), _ptr(size), _ptr(proven)), kind, delta)
+        return (d2, self._adj_bool(words, n), clique[:int(size[0])].copy(), bool(proven[0])) + st
 
     def set_symbolic_cache(self, on: bool):
         """Reuse of the ordering / symbolic analysis / structure upload across calls on the same edge list (default on)."""

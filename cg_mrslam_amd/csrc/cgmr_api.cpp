@@ -807,6 +807,27 @@ int cgmr_closure_consistency_exact(cgmr_ctx* ctx, int nV, const double* poses, c
       clique_size_out, nullptr, &ex);
 }
 
+int cgmr_closure_consistency_inter(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                                   const int32_t* et, const double* meas, const double* info, int nC, const int32_t* cl_a,
+                                   const double* peer_pose, const double* peer_cov, const double* cl_meas, const double* cl_info,
+                                   double gamma, double* d2_out, uint64_t* adj_out, int32_t* clique_out, int32_t* clique_size_out,
+                                   int32_t* seed_out, const cgmr_robust* rk) {
+  const PcmInter inter{peer_pose, peer_cov};
+  return pcm_driver(ctx, host_call(nV, poses, fixed, nE, ef, et, meas, info, {false, rk}), nC, cl_a, nullptr, cl_meas, cl_info, gamma, d2_out, adj_out,
+      clique_out, clique_size_out, seed_out, nullptr, &inter);
+}
+
+int cgmr_closure_consistency_inter_exact(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                                         const int32_t* et, const double* meas, const double* info, int nC, const int32_t* cl_a,
+                                         const double* peer_pose, const double* peer_cov, const double* cl_meas,
+                                         const double* cl_info, double gamma, double* d2_out, uint64_t* adj_out, int64_t node_limit,
+                                         int32_t* clique_out, int32_t* clique_size_out, int32_t* proven_out, const cgmr_robust* rk) {
+  const CliqueExact ex{node_limit, proven_out, nullptr};
+  const PcmInter inter{peer_pose, peer_cov};
+  return pcm_driver(ctx, host_call(nV, poses, fixed, nE, ef, et, meas, info, {false, rk}), nC, cl_a, nullptr, cl_meas, cl_info, gamma, d2_out, adj_out,
+      clique_out, clique_size_out, nullptr, &ex, &inter);
+}
+
 int cgmr_max_clique_exact(cgmr_ctx* ctx, int n, const uint64_t* adj_bits, int64_t node_limit, int32_t* clique_out,
                           int32_t* clique_size_out, int32_t* proven_out, int64_t* nodes_out) {
   if (!ctx) return CGMR_E_INVALID;

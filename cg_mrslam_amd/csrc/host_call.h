@@ -52,9 +52,12 @@ int joint_driver(cgmr_ctx* ctx, const char* who, int mode, const HostCall& c, in
 // pcm_driver / clique_driver with `ex`: the exact solver behind the greedy clique (cgmr_closure_consistency_exact,
 // cgmr_max_clique_exact); proven_out takes seed_out's place among the outputs, seed_out is not read.  Without: the greedy pair.
 struct CliqueExact { int64_t node_limit; int32_t* proven_out; int64_t* nodes_out; };
+// pcm_driver with `inter`: the two-graph form (cgmr_closure_consistency_inter[_exact]) -- candidate k ends at a peer's vertex
+// known by peer_pose[3 k ..], cb is not read; peer_cov [3 nC * 3 nC] or null (pcm_device.h: PcmInterClosures).
+struct PcmInter { const double* peer_pose; const double* peer_cov; };
 int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, const int32_t* cb, const double* cmeas,
                const double* cinfo, double gamma, double* d2_out, uint64_t* adj_out, int32_t* clique_out, int32_t* size_out,
-               int32_t* seed_out, const CliqueExact* ex = nullptr);
+               int32_t* seed_out, const CliqueExact* ex = nullptr, const PcmInter* inter = nullptr);
 int clique_driver(cgmr_ctx* ctx, int n, const uint64_t* adj, int32_t* clique_out, int32_t* size_out, int32_t* seed_out,
                   const CliqueExact* ex = nullptr);
 

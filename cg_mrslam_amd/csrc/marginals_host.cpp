@@ -493,13 +493,18 @@ static void clique_result_out(const std::vector<int32_t>& res, int n, int32_t* c
 // pair, its rows as bit words, the greedy clique of every seed and the best of them.  In profiling mode the launch classes
 // 9 (solve + Gram), 10 (k_closure_consistency) and 11 (bits and clique) of cgmr_gn_kernel_times_ex are timed and collected.
 // With `ex` (cgmr_closure_consistency_exact): the exact solver's launches behind the greedy ones, in class 11 as well.
+// With `inter` (cgmr_closure_consistency_inter[_exact]): the unique endpoints are those of ca alone (at most nC), the peer's
+// poses and, where given, their covariance go up beside the candidates, and class 10 is k_closure_consistency_inter; every
+// step before and after is the same statement.
 int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, const int32_t* cb, const double* cmeas,
                const double* cinfo, double gamma, double* d2_out, uint64_t* adj_out, int32_t* clique_out, int32_t* size_out,
-               int32_t* seed_out, const CliqueExact* ex) {
-  const char* who = ex ? "cgmr_closure_consistency_exact" : "cgmr_closure_consistency";
+               int32_t* seed_out, const CliqueExact* ex, const PcmInter* inter) {
+  const char* who = inter ? (ex ? "cgmr_closure_consistency_inter_exact" : "cgmr_closure_consistency_inter")
+                          : (ex ? "cgmr_closure_consistency_exact" : "cgmr_closure_consistency");
   if (ex) seed_out = ex->proven_out;                               // (the third of the clique's outputs, for the checks below)
   MargCall call(ctx, c);
-  int rc = call.args(nC < 0 || !c.fixed || (nC > 0 && (!ca || !cb || !cmeas || !cinfo)), who);
+  const bool no_ends = inter ? !inter->peer_pose : !cb;             // (where the candidates end: the peer's poses, or b)
+  int rc = call.args(nC < 0 || !c.fixed || (nC > 0 && (!ca || no_ends || !cmeas || !cinfo)), who);
   if (rc) return rc;
   const bool want_clique = clique_out || size_out || seed_out;
   if (want_clique && !(clique_out && size_out && seed_out))
@@ -507,16 +512,33 @@ int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, cons
                    ex ? "proven_out" : "seed_out");
   if (nC > CGMR_PCM_MAX_CLOSURES)
     return set_err(ctx, CGMR_E_INVALID, "%s: %d closures, at most CGMR_PCM_MAX_CLOSURES = %d", who, nC, CGMR_PCM_MAX_CLOSURES);
-  for (int k = 0; k < nC; k++)
+  for (int k = 0; k < nC && !inter; k++)
     if (ca[k] < 0 || ca[k] >= c.nV || cb[k] < 0 || cb[k] >= c.nV)
       return set_err(ctx, CGMR_E_INVALID, "%s: closure %d (%d -> %d) has an endpoint outside [0, %d)", who, k, ca[k], cb[k], c.nV);
+  for (int k = 0; k < nC && inter; k++) {
+    if (ca[k] < 0 || ca[k] >= c.nV)
+      return set_err(ctx, CGMR_E_INVALID, "%s: closure %d starts at vertex %d, outside [0, %d)", who, k, ca[k], c.nV);
+    const double* pp = inter->peer_pose + 3 * (size_t)k;
+    if (!(std::isfinite(pp[0]) && std::isfinite(pp[1]) && std::isfinite(pp[2])))
+      return set_err(ctx, CGMR_E_INVALID, "%s: closure %d has a peer pose that is not finite", who, k);
+  }
+  if (inter && inter->peer_cov)                                    // the lower triangle is all that is read
+    for (size_t r = 0, N3 = 3 * (size_t)nC; r < N3; r++) {
+      const double* row = inter->peer_cov + r * N3;
+      for (size_t q = 0; q <= r; q++)
+        if (!std::isfinite(row[q]))
+          return set_err(ctx, CGMR_E_INVALID, "%s: peer_cov (%zu, %zu), closures %zu and %zu, is not finite", who, r, q, r / 3, q / 3);
+      if (row[r] < 0)
+        return set_err(ctx, CGMR_E_INVALID, "%s: peer_cov (%zu, %zu), closure %zu, is a negative variance", who, r, r, r / 3);
+    }
   if (!(std::isfinite(gamma) && gamma > 0)) return set_err(ctx, CGMR_E_INVALID, "%s: gamma must be finite and > 0", who);
   if (ex && ex->node_limit <= 0) return set_err(ctx, CGMR_E_INVALID, "%s: node_limit must be > 0", who);
   if (nC == 0) { if (size_out) *size_out = 0; return CGMR_OK; }
-  // the unique endpoints, in order of first appearance: 4 columns of Y each (at most 2 nC <= CGMR_JOINT_MAX_QUERIES)
+  // the unique endpoints, in order of first appearance: 4 columns of Y each (at most 2 nC <= CGMR_JOINT_MAX_QUERIES; with
+  // `inter` the own ones alone, at most nC)
   std::vector<int32_t> slot_of(c.nV, -1), uq;
   auto slot = [&](int v) { if (slot_of[v] < 0) { slot_of[v] = (int32_t)uq.size(); uq.push_back(v); } return slot_of[v]; };
-  for (int k = 0; k < nC; k++) { slot(ca[k]); slot(cb[k]); }
+  for (int k = 0; k < nC; k++) { slot(ca[k]); if (!inter) slot(cb[k]); }
   const int nU = (int)uq.size();
   rc = call.open(who);
   if (rc) return rc;
@@ -529,22 +551,24 @@ int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, cons
   const MargLayout M(nU, D.nf, S.rows.size(), D.nfronts, 0);
   const int T = M.m / 16, W = (nC + 63) / 64;
   const size_t n = (size_t)nC;
-  std::vector<int32_t> qcol(nU), sl(2 * n);
+  std::vector<int32_t> qcol(nU), sl(2 * n);                         // (with `inter`: one slot per candidate, the front half)
   for (int k = 0; k < nU; k++) qcol[k] = ctx->vmask[uq[k]] ? -1 : S.vperm[uq[k]];      // fixed / inactive: zero columns
-  for (int k = 0; k < nC; k++) {
+  for (int k = 0; k < nC && !inter; k++) {
     const int sa = slot_of[ca[k]], sb = slot_of[cb[k]];
     sl[2 * k] = qcol[sa] < 0 ? -1 : sa; sl[2 * k + 1] = qcol[sb] < 0 ? -1 : sb;
   }
+  for (int k = 0; k < nC && inter; k++) { const int sa = slot_of[ca[k]]; sl[k] = qcol[sa] < 0 ? -1 : sa; }
   JointGram JG;
   JG.ntile = (long long)T * (T + 1) / 2;
   joint_gram_split(M.n, (long long)((T + 3) / 4) * ((T + 3) / 4 + 1) / 2, &JG.rows, &JG.nsplit);
   // staging: poses | meas | info | query columns, Y, border vectors, live flags (MargLayout) | partial tiles | tiles | the
-  // candidates | d2 | bit words | the clique's work space
+  // candidates (b, or with `inter` the peer's poses [| their covariance]) | d2 | bit words | the clique's work space
   Layout256& L = call.L;
   const MargLayout ML(nU, D.nf, S.rows.size(), D.nfronts, L.off);
   L.off = ML.end;
   const size_t o_part = L.add(JG.nsplit > 1 ? 2048 * (size_t)JG.nsplit * (size_t)JG.ntile : 0), o_G = L.add(2048 * (size_t)JG.ntile),
-               o_sl = L.add(8 * n), o_ca = L.add(4 * n), o_cb = L.add(4 * n), o_cm = L.add(24 * n), o_ci = L.add(48 * n),
+               o_sl = L.add(8 * n), o_ca = L.add(4 * n), o_cb = L.add(inter ? 24 * n : 4 * n),
+               o_pc = L.add(inter && inter->peer_cov ? 72 * n * n : 0), o_cm = L.add(24 * n), o_ci = L.add(48 * n),
                o_d2 = L.add(8 * n * n), o_adj = L.add(8 * n * W);
   const CliqueLayout CL(L, nC, ex && want_clique);
   rc = call.stage();
@@ -553,7 +577,9 @@ int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, cons
   HIP_TRY(ctx, hipMemcpyAsync(d + ML.o_qc, qcol.data(), 4 * (size_t)nU, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d + o_sl, sl.data(), 8 * n, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d + o_ca, ca, 4 * n, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d + o_cb, cb, 4 * n, hipMemcpyHostToDevice, st));
+  if (!inter) HIP_TRY(ctx, hipMemcpyAsync(d + o_cb, cb, 4 * n, hipMemcpyHostToDevice, st));
+  if (inter) HIP_TRY(ctx, hipMemcpyAsync(d + o_cb, inter->peer_pose, 24 * n, hipMemcpyHostToDevice, st));
+  if (inter && inter->peer_cov) HIP_TRY(ctx, hipMemcpyAsync(d + o_pc, inter->peer_cov, 72 * n * n, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d + o_cm, cmeas, 24 * n, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d + o_ci, cinfo, 48 * n, hipMemcpyHostToDevice, st));
   JG.part = (double*)(d + o_part);
@@ -562,6 +588,11 @@ int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, cons
   C.n = nC;
   C.a = (const int32_t*)(d + o_ca); C.b = (const int32_t*)(d + o_cb); C.slot = (const int32_t*)(d + o_sl);
   C.meas = (const double*)(d + o_cm); C.info = (const double*)(d + o_ci);
+  PcmInterClosures CI;
+  CI.n = nC;
+  CI.a = C.a; CI.slot = C.slot; CI.meas = C.meas; CI.info = C.info;
+  CI.peer = (const double*)(d + o_cb);
+  CI.peer_cov = inter && inter->peer_cov ? (const double*)(d + o_pc) : nullptr;
   std::vector<int32_t> res(n + 2, 0);
   int64_t total = 0;
   GnPassOpts pass;
@@ -574,7 +605,10 @@ int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, cons
                                (uint8_t*)(d + ML.o_live));
         launch_joint_gram(st, ML.n, ML.m, (const double*)(d + ML.o_Y), JG);
       });
-    KT.run(10, 1, [&] { launch_closure_consistency(st, C, call.dp, JG.G, (double*)(d + o_d2)); });
+    KT.run(10, 1, [&] {
+      if (inter) launch_closure_consistency_inter(st, CI, call.dp, JG.G, (double*)(d + o_d2));
+      else launch_closure_consistency(st, C, call.dp, JG.G, (double*)(d + o_d2));
+    });
     size_t o_res = CL.o_out;
     if (adj_out || want_clique)
       KT.run(11, want_clique ? (ex ? 6 + CGMR_EXACT_ROUNDS : 3) : 1, [&] {

@@ -37,6 +37,19 @@ struct PcmClosures {
 
 // d2 [n * n], symmetric with an exact zero diagonal, from the dense tile set G (joint_marginals_kernels.hip) at `poses`
 void launch_closure_consistency(hipStream_t st, const PcmClosures& C, const double* poses, const double* G, double* d2);
+// The candidates of an inter-robot consistency call (cgmr_closure_consistency_inter): closure k goes from the own vertex a[k]
+// to a peer's vertex with the pose peer[3 k ..] (in the peer's frame; only p_k^-1 p_l enters) and measures x_a^-1 x_p;
+// slot[k]: the 4-column group of Y of a[k] among the unique own endpoints, or -1.  peer_cov [3 n * 3 n], row-major, indexed by
+// candidate: the joint covariance of the peer poses, of which only the lower triangle is read; null: Sigma_p = 0, the peer's
+// poses are taken as exact (as LoopClosureChecker takes them).  That under-states S, so the gate d2 < gamma is stricter than
+// the data justify: consistent candidates may be refused, inconsistent ones are not let in.
+struct PcmInterClosures {
+  int n = 0;
+  const int32_t *a = nullptr, *slot = nullptr;
+  const double *peer = nullptr, *peer_cov = nullptr, *meas = nullptr, *info = nullptr;
+};
+// d2 [n * n] as launch_closure_consistency writes it, for the two-graph form
+void launch_closure_consistency_inter(hipStream_t st, const PcmInterClosures& C, const double* poses, const double* G, double* d2);
 // adj [n * W], W = (n + 63) / 64: bit (l & 63) of word k * W + (l >> 6) = (k != l && d2[k][l] < gamma); padding bits zero
 void launch_consistency_bits(hipStream_t st, int n, const double* d2, double gamma, unsigned long long* adj);
 // The greedy clique of every seed (seed_bits [n * W]: its members, seed_size [n]), then the best of them: out[0] its size,

@@ -8,6 +8,8 @@
 //
 //   k_closure_consistency   one thread per pair l < k, behind the dense Gram tiles of the unique endpoints
 //                           (joint_marginals_kernels.hip: k_gram_macro_partial; the tiles stay on the device)
+//   k_closure_consistency_inter   the same for candidates that end at a peer robot's vertex, known only by the pose (and,
+//                           where the caller has one, the covariance) the peer sent (cgmr_closure_consistency_inter)
 //   k_consistency_bits      rows of d2 -> rows of 64-bit words, one __ballot per word
 //   k_clique_greedy         one workgroup per seed: P in LDS, candidates strided over the threads, __popcll counts
 //   k_clique_best           the seeds' results reduced by (size, lowest seed), the winner's members written ascending
@@ -201,6 +203,134 @@ __global__ __launch_bounds__(64) void k_closure_consistency(PcmClosures C, const
   d2[(size_t)l * n + k] = r;
 }
 
+// The two-graph form (cgmr_closure_consistency_inter): candidate k goes from the own vertex a[k] to a peer vertex that is in no
+// graph, known by the pose peer[3 k ..] the peer sent.  Pair (k, l), l < k: pair_d2's residual with x_b replaced by p,
+//   eps = z_k (+) (p_k^-1 p_l) (+) z_l^-1 (+) (x_al^-1 x_ak),
+// the same chain of Jacobians, and S = J_a Sigma_a J_a^T + J_p Sigma_p J_p^T + J_zk Omega_k^-1 J_zk^T + J_zl Omega_l^-1 J_zl^T:
+// Sigma_a the 6x6 joint covariance of (x_ak, x_al) out of the Gram tiles (3 blocks), Sigma_p the 6x6 sub-matrix at candidates
+// (k, l) of the caller's peer_cov, read from its lower triangle (3 blocks; none when peer_cov is null: the peer's poses taken as
+// exact).  The two graphs share no factor, so there is no cross term.  Symmetrisation, factorisation of S and the rejection
+// test are pair_d2's, statement for statement.
+__device__ __forceinline__ double pair_d2_inter(const PcmInterClosures& C, const double* __restrict__ poses,
+                                                const double* __restrict__ G, int k, int l) {
+  const double* zk = C.meas + 3 * (size_t)k;
+  const double* zl = C.meas + 3 * (size_t)l;
+  const double* xak = poses + 3 * (size_t)C.a[k];
+  const double* xbk = C.peer + 3 * (size_t)k;
+  const double* xal = poses + 3 * (size_t)C.a[l];
+  const double* xbl = C.peer + 3 * (size_t)l;
+  double T2[3], T3[3], T4[3], P2[3], P3[3], eps[3];
+  double J2a[9], J2b[9], J4a[9], J4b[9], L1[9], L2[9], L3[9], R[9], U[9], V[9];
+  double Ja[2][9], Jp[2][9], Jzk[9], Jzl[9];                      // Ja: for x_ak, x_al; Jp: for p_k, p_l
+  relative(xbk, xbl, T2, J2a, J2b);
+  relative(xal, xak, T4, J4a, J4b);
+  // T3 = z_l^-1 and its Jacobian
+  const double cl = cos(zl[2]), sl = sin(zl[2]);
+  T3[0] = -cl * zl[0] - sl * zl[1]; T3[1] = sl * zl[0] - cl * zl[1]; T3[2] = -zl[2];
+  const double Ji[9] = {-cl, -sl, T3[1], sl, -cl, -T3[0], 0, 0, -1};
+  compose(zk, T2, P2, L1);
+  compose(P2, T3, P3, L2);
+  compose(P3, T4, eps, L3);
+  eps[2] = p_norm_theta(eps[2]);
+  rot3(P3[2], R);                                                 // d eps / d T4
+  mul3(R, J4a, Ja[1]);
+  mul3(R, J4b, Ja[0]);
+  rot3(P2[2], R);
+  mul3(L3, R, U);                                                 // d eps / d T3
+  mul3(U, Ji, Jzl);
+  mul3(L3, L2, U);
+  rot3(zk[2], R);
+  mul3(U, R, V);                                                  // d eps / d T2
+  mul3(V, J2a, Jp[0]);
+  mul3(V, J2b, Jp[1]);
+  mul3(U, L1, Jzk);                                               // d eps / d T1
+  const int32_t sl2[2] = {C.slot[k], C.slot[l]};
+  double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int j = i; j < 2; j++) {
+      if (sl2[i] < 0 || sl2[j] < 0) continue;                     // fixed / inactive: zero rows of Sigma_a
+      const int ca = 4 * sl2[i], cb = 4 * sl2[j];
+      const long long pos = dense_pos(ca, cb);
+      double B[9];
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) B[3 * r + c] = gram_at(G, pos, ca + r, cb + c);
+      add_jbjt(Ja[i], B, Ja[j], j != i, S);
+    }
+  if (C.peer_cov) {
+    const size_t N3 = 3 * (size_t)C.n;
+    const int kl[2] = {k, l};
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+      for (int j = i; j < 2; j++) {
+        double B[9];                                              // block (kl[i], kl[j]), rows kl[i], out of the lower triangle
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+          for (int c = 0; c < 3; c++) {
+            const size_t row = 3 * (size_t)kl[i] + r, col = 3 * (size_t)kl[j] + c;
+            B[3 * r + c] = row >= col ? C.peer_cov[row * N3 + col] : C.peer_cov[col * N3 + row];
+          }
+        add_jbjt(Jp[i], B, Jp[j], j != i, S);
+      }
+  }
+  double W[9];
+  info_inverse(C.info + 6 * (size_t)k, W);
+  add_jbjt(Jzk, W, Jzk, false, S);
+  info_inverse(C.info + 6 * (size_t)l, W);
+  add_jbjt(Jzl, W, Jzl, false, S);
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < i; j++) { const double u = 0.5 * (S[3 * i + j] + S[3 * j + i]); S[3 * i + j] = u; S[3 * j + i] = u; }
+  // S = L L^T; d2 = |L^-1 eps|^2
+  double L[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    double d = S[3 * j + j];
+    for (int p = 0; p < j; p++) d -= L[3 * j + p] * L[3 * j + p];
+    if (!(d > 0) || !(d < INFINITY)) ok = false;
+    L[3 * j + j] = sqrt(d);
+    for (int i = j + 1; i < 3; i++) {
+      double u = S[3 * i + j];
+      for (int p = 0; p < j; p++) u -= L[3 * i + p] * L[3 * j + p];
+      L[3 * i + j] = u / L[3 * j + j];
+    }
+  }
+  double r = NAN;
+  if (ok) {
+    const double y0 = eps[0] / L[0];
+    const double y1 = (eps[1] - L[3] * y0) / L[4];
+    const double y2 = (eps[2] - L[6] * y0 - L[7] * y1) / L[8];
+    r = y0 * y0 + y1 * y1 + y2 * y2;
+    if (!(r < INFINITY)) r = NAN;                                 // (an entry of S that is not finite)
+  }
+  return r;
+}
+
+// One thread per pair l < k, k_closure_consistency's mapping: its d2 written to (k, l) and (l, k); threads q < n also write
+// the zero diagonal.
+__global__ __launch_bounds__(64) void k_closure_consistency_inter(PcmInterClosures C, const double* __restrict__ poses,
+                                                                  const double* __restrict__ G, double* __restrict__ d2) {
+  const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int n = C.n;
+  if (q < n) d2[(size_t)q * n + q] = 0.0;
+  if (q >= (long long)n * (n - 1) / 2) return;
+  // q = k (k - 1) / 2 + l
+  int k = (int)((1.0 + sqrt(1.0 + 8.0 * (double)q)) * 0.5);
+  while ((long long)k * (k + 1) / 2 <= q) k++;
+  while ((long long)k * (k - 1) / 2 > q) k--;
+  const int l = (int)(q - (long long)k * (k - 1) / 2);
+  const double r = pair_d2_inter(C, poses, G, k, l);
+  d2[(size_t)k * n + l] = r;
+  d2[(size_t)l * n + k] = r;
+}
+
 // Word (k, w): lane t tests column 64 w + t of row k; NaN is not adjacent, the diagonal and the padding bits are zero.
 __global__ __launch_bounds__(64) void k_consistency_bits(int n, int W, const double* __restrict__ d2, double gamma,
                                                          u64* __restrict__ adj) {
@@ -293,6 +423,11 @@ __global__ __launch_bounds__(256) void k_clique_best(int n, int W, const u64* __
 void launch_closure_consistency(hipStream_t st, const PcmClosures& C, const double* poses, const double* G, double* d2) {
   const long long np = (long long)C.n * (C.n - 1) / 2, nt = np > C.n ? np : C.n;
   hipLaunchKernelGGL(k_closure_consistency, dim3((unsigned)((nt + 63) / 64)), dim3(64), 0, st, C, poses, G, d2);
+}
+
+void launch_closure_consistency_inter(hipStream_t st, const PcmInterClosures& C, const double* poses, const double* G, double* d2) {
+  const long long np = (long long)C.n * (C.n - 1) / 2, nt = np > C.n ? np : C.n;
+  hipLaunchKernelGGL(k_closure_consistency_inter, dim3((unsigned)((nt + 63) / 64)), dim3(64), 0, st, C, poses, G, d2);
 }
 
 void launch_consistency_bits(hipStream_t st, int n, const double* d2, double gamma, unsigned long long* adj) {

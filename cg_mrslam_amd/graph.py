@@ -788,10 +788,33 @@ class GraphSLAM:
 
     # the default gamma: the 0.99 quantile of chi2 with 3 degrees of freedom (scipy.stats.chi2.ppf(0.99, 3)) -- two candidates
     # that both agree with the graph fail the test together once in a hundred
-    def consistentClosures(self, closures, gamma: float = 11.344866730144373, robust: bool = False, exact: bool = False):     # noqa: N802
+    GAMMA_99 = 11.344866730144373
+
+    def consistentClosures(self, closures, gamma: float = GAMMA_99, robust: bool = False, exact: bool = False):     # noqa: N802
         """The indices (ascending) of the largest set of pairwise consistent candidates closureConsistency finds (``exact``: by
         the exact search, at its default node limit)."""
         return self.closureConsistency(closures, gamma, robust, exact)[2]
+
+    def interRobotConsistency(self, cands, gamma: float = GAMMA_99, peer_cov=None, exact: bool = False,     # noqa: N802
+                              robust: bool = False, node_limit=None):
+        """closureConsistency for candidates between this graph and a peer robot's: ``cands`` a list of ``(i, peer_pose, meas,
+        info_upper)``, i an own vertex index, peer_pose the pose of the peer's vertex as the peer sent it (in no graph yet).
+        ``peer_cov`` [3 N, 3 N]: the joint covariance of the peer poses, indexed by candidate; None: they are taken as exact (as
+        LoopClosureChecker takes them), and the gate is stricter than the data justify.  Returns ``(d2, adj, clique, seed)``,
+        with ``exact`` ``(d2, adj, clique, proven)``, as closureConsistency; a typed graph raises ValueError."""
+        a, kw, _ = self._joint_args(robust)
+        if "vertex_kind" in kw:
+            raise ValueError("interRobotConsistency: pose graphs only (the graph has landmarks or priors)")
+        cl = list(cands)
+        ca = np.array([c[0] for c in cl], dtype=np.int32)
+        pp = np.array([c[1] for c in cl], dtype=np.float64).reshape(len(cl), 3)
+        cm = np.array([c[2] for c in cl], dtype=np.float64).reshape(len(cl), 3)
+        ci = np.array([c[3] for c in cl], dtype=np.float64).reshape(len(cl), 6)
+        if exact:
+            if node_limit is not None:
+                kw = dict(kw, node_limit=node_limit)
+            return self.ctx.closure_consistency_inter_exact(*a, ca, pp, cm, ci, gamma, peer_cov=peer_cov, **kw)[:4]
+        return self.ctx.closure_consistency_inter(*a, ca, pp, cm, ci, gamma, peer_cov=peer_cov, **kw)[:4]
 
     def observationCovariance(self, pairs, kinds, hypotheses=None, robust: bool = False):     # noqa: N802
         """Data association: for the vertex index pairs ``(pose, b)`` predicted as factors of ``kinds`` (per pair 0 EDGE_SE2,

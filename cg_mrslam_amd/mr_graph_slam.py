@@ -89,12 +89,25 @@ class MRGraphSLAMDriver(GraphSLAMDriver):
     ``robot_graph``: a ``condensed.RobotGraph`` (or an object with its interface) created for (idRobot, nRobots); it holds
     the optimiser's copy of the graph, so ``optimize`` runs there and the estimates are read back."""
 
-    def __init__(self, ctx, close_matcher, lc_matcher, robot_graph, idRobot, nRobots, mr_polish=None, **kw):   # noqa: N803
+    def __init__(self, ctx, close_matcher, lc_matcher, robot_graph, idRobot, nRobots, mr_polish=None, mr_closure_check="voting",   # noqa: N803
+                 mr_peer_covariance=None, **kw):
         # inter-robot edges: None = globalMatching's result with the constant information (the reference); a matcher.PolishParams =
         # the result polished behind the search, as GraphSLAMDriver's lc_polish does for loop closures
         if mr_polish is not None and not (hasattr(mr_polish, "pod") and hasattr(mr_polish, "window")):
             raise ValueError("mr_polish is None or a matcher.PolishParams")
         self.mr_polish = mr_polish
+        # which buffered inter-robot candidates become edges: "voting" = LoopClosureChecker (the reference); ("pcm", gamma) /
+        # ("pcm-exact", gamma) = the largest set of pairwise consistent candidates (GraphSLAM.interRobotConsistency: the own side of
+        # a pair's loop under this graph's covariances, the peer side from the poses the peer sent), as closure_check does for
+        # the robot's own closures.  mr_peer_covariance: None = the peer's poses are taken as exact (all the wire format carries:
+        # the gate is stricter than the data justify); or a callable (robot id, [peer vertex id per candidate]) -> the
+        # [3 n, 3 n] joint covariance of those vertices, or None (team_peer_covariance, for robots in one process)
+        if mr_closure_check != "voting" and not (isinstance(mr_closure_check, tuple) and len(mr_closure_check) == 2 and
+                                                 mr_closure_check[0] in ("pcm", "pcm-exact") and float(mr_closure_check[1]) > 0):
+            raise ValueError('mr_closure_check is "voting", ("pcm", gamma) or ("pcm-exact", gamma) with gamma > 0')
+        if mr_peer_covariance is not None and not callable(mr_peer_covariance):
+            raise ValueError("mr_peer_covariance is None or a callable (robot id, peer vertex ids) -> covariance")
+        self.mr_closure_check, self.mr_peer_covariance = mr_closure_check, mr_peer_covariance
         self.rg = robot_graph
         self.nRobots = nRobots   # noqa: N815
         self._n_recv = 0                       # received condensed edges at the tail of the host edge arrays
@@ -230,6 +243,9 @@ class MRGraphSLAMDriver(GraphSLAMDriver):
             cb = self.interRobotClosures.mrClosures[robot_id]
             if not cb.checkList(self.windowMRLoopClosure):
                 continue
+            if self.mr_closure_check != "voting":
+                self._check_inter_robot_pcm(robot_id, cb)
+                continue
             local = sorted(set(cb.vertex_ids()))
             poses = {vid: self._peer_pose(vid) for vid in local}
             for e in cb.edges:
@@ -258,6 +274,42 @@ class MRGraphSLAMDriver(GraphSLAMDriver):
                 in_closures.append(vto)
             if in_closures:
                 self.rg.insertInClosure(robot_id, np.asarray(sorted(set(in_closures))))
+
+    def _check_inter_robot_pcm(self, robot_id, cb):
+        """A peer's buffered candidates by pairwise consistency (mr_closure_check): one call on the host arrays -- the received
+        condensed edges at their tail, as the own-closure PCM sees them --, then exactly the clique's candidates through the
+        lines the voting path adds its inliers with."""
+        edges = cb.edges
+        cands = [(self._index_of_id(e["from"]), self._peer_pose(e["to"]), e["meas"], e.get("edge_info", INTER_ROBOT_INFO)) for e in edges]
+        peer_cov = None
+        if self.mr_peer_covariance is not None:
+            peer_cov = self.mr_peer_covariance(robot_id, [int(e["to"]) for e in edges])
+        how, gamma = self.mr_closure_check[0], float(self.mr_closure_check[1])
+        if how == "pcm-exact":
+            clique, proven = self.interRobotConsistency(cands, gamma, peer_cov=peer_cov, exact=True)[2:4]
+            self.log.append(("mr_pcm-exact", robot_id, len(clique), len(edges), bool(proven)))
+        else:
+            clique = self.interRobotConsistency(cands, gamma, peer_cov=peer_cov)[2]
+            self.log.append(("mr_pcm", robot_id, len(clique), len(edges)))
+        if len(clique) < self.minInliersMR:
+            return
+        in_closures = []
+        for k in clique:
+            e = edges[int(k)]
+            self._running_edge_id += 1
+            vto = e["to"]
+            idx = self._index_of_id(vto)
+            if idx is None:
+                idx = self._add_vertex(vto, self.peer[vto]["pose"], False, self.peer[vto]["ranges"])
+            elif idx not in self.lasers and vto in self.peer:
+                self.lasers[idx] = self.peer[vto]["ranges"]
+            if not e["added"]:                                   # HyperGraph::addEdge refuses an edge twice
+                e["added"] = True
+                self._add_edge(self._index_of_id(e["from"]), idx, e["meas"], e.get("edge_info", INTER_ROBOT_INFO), "mr",
+                               self._running_edge_id + self.baseId)
+            in_closures.append(vto)
+        if in_closures:
+            self.rg.insertInClosure(robot_id, np.asarray(sorted(set(in_closures))))
 
     def updateInterRobotClosures(self):   # noqa: N802
         self.interRobotClosures.update(self.windowMRLoopClosure)
@@ -478,6 +530,26 @@ class GraphCommSim:
         self.delivered += sum(run(process, list(zip(self.slams, queues))))
 
 
+def team_peer_covariance(slams):
+    """For robots that run in one process (GraphCommSim): a callable for ``MRGraphSLAMDriver(mr_peer_covariance=...)`` that asks
+    the sending robot's driver for the joint covariance of the requested vertices (GraphSLAM.jointMarginal on its graph at its
+    current estimates) and expands it per candidate -- a vertex that several candidates end at repeats its rows and columns.
+    None when the sender does not hold one of the vertices.  ``slams``: the drivers, a list indexed by robot id or a dict; it is
+    read at call time, so it may be filled after the drivers are built.  GraphCommRanks has no such source: the wire format is
+    pinned to the reference's, which carries no covariance -- leave mr_peer_covariance None there."""
+    def cov(robot_id, vertex_ids):
+        s = slams[robot_id]
+        uq = sorted(set(int(v) for v in vertex_ids))
+        idx = [s._index_of_id(v) for v in uq]
+        if not uq or any(i is None for i in idx):
+            return None
+        joint = np.asarray(s.jointMarginal(idx))
+        where = {v: k for k, v in enumerate(uq)}
+        rows = np.concatenate([np.arange(3 * where[int(v)], 3 * where[int(v)] + 3) for v in vertex_ids])
+        return np.ascontiguousarray(joint[np.ix_(rows, rows)])
+    return cov
+
+
 def pack_outbox(out, cap_bytes):
     """(dest, bytes) list -> one fixed-size uint8 record: int32 count, then per message {int32 dest, int32 len, payload}."""
     buf = np.zeros(cap_bytes, dtype=np.uint8)
@@ -587,4 +659,4 @@ def run_cg_mrslam_rank(slam, trajectories, comm=None, linearUpdate=0.25, angular
 
 
 __all__ = ["MRClosureBuffer", "MRGraphSLAMDriver", "RobotLoop", "GraphCommSim", "GraphCommRanks", "run_cg_mrslam",
-           "run_cg_mrslam_rank", "pack_outbox", "unpack_outbox", "SIM_COMM_RANGE", "INTER_ROBOT_INFO"]
+           "run_cg_mrslam_rank", "team_peer_covariance", "pack_outbox", "unpack_outbox", "SIM_COMM_RANGE", "INTER_ROBOT_INFO"]

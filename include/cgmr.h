@@ -570,7 +570,7 @@ int cgmr_set_profiling(cgmr_ctx* ctx, int on);
 int cgmr_gn_kernel_times(const cgmr_ctx* ctx, double seconds_out[8], int64_t launches_out[8]);
 /* ... with the classes added since: 8 front_level = a tree level's factorisation AND its update tiles in one launch
  * (k_front_level, round 6: the levels whose launch is certainly resident at once); 9..11 cgmr_closure_consistency's:
- * 9 the forward solve and the Gram tiles, 10 k_closure_consistency, 11 the bit words and the clique (cgmr_max_clique_greedy:
+ * 9 the forward solve and the Gram tiles, 10 k_closure_consistency[_inter], 11 the bit words and the clique (cgmr_max_clique_greedy:
  * the clique alone; the exact calls: the exact solver's launches with it) -- zero in a library that does not export
  * those symbols.                                                                                                       */
 int cgmr_gn_kernel_times_ex(const cgmr_ctx* ctx, double seconds_out[12], int64_t launches_out[12]);
@@ -906,6 +906,47 @@ int cgmr_closure_consistency_exact(cgmr_ctx* ctx, int nV, const double* poses_xy
                                    int32_t* proven_out, const cgmr_robust* rk);
 int cgmr_max_clique_exact(cgmr_ctx* ctx, int n, const uint64_t* adj_bits, int64_t node_limit, int32_t* clique_out,
                           int32_t* clique_size_out, int32_t* proven_out, int64_t* nodes_out);
+
+/* Inter-robot PCM: the two-graph form of the test, as published PCM states it (present in C ABI version 105 libraries that
+ * export these symbols).  A candidate between this robot and a peer ends at a vertex that is in no graph until it is accepted,
+ * so cgmr_closure_consistency cannot take it.  Here candidate k = (cl_a[k], p_k = peer_pose_xyt[3 k ..], z_k, Omega_k): cl_a[k]
+ * an own vertex (an index into the graph), p_k the peer vertex's pose as the peer sent it, in the peer's frame, z_k a
+ * measurement of x_a^-1 x_p.  The loop residual of the pair l < k is
+ *   eps_kl = z_k (+) (p_k^-1 (+) p_l) (+) z_l^-1 (+) (x_al^-1 (+) x_ak)
+ * -- cgmr_closure_consistency's with x_b replaced by p; only the peer's relative pose enters, so its frame does not matter --
+ * with the first-order covariance
+ *   S_kl = J_a Sigma_a J_a^T + J_p Sigma_p J_p^T + J_zk Omega_k^-1 J_zk^T + J_zl Omega_l^-1 J_zl^T
+ * Sigma_a the 6x6 joint covariance of (x_ak, x_al) exactly as cgmr_marginals_joint returns it (shared, repeated, fixed and
+ * inactive vertices as there), Sigma_p the 6x6 sub-matrix at candidates (k, l) of peer_cov [3 nC * 3 nC] (host, row-major,
+ * indexed by candidate: rows 3 k .. 3 k + 2 are p_k's; two candidates at one peer vertex repeat its rows).  Only the lower
+ * triangle of peer_cov is read, so (i, j) and (j, i) are the same double.  The two graphs share no factor: no cross term
+ * between Sigma_a and Sigma_p; correlations between the own graph and peer vertices already accepted into it are ignored.
+ * peer_cov == NULL: Sigma_p = 0, the peer's poses are taken as exact -- how LoopClosureChecker treats them, and all that the
+ * reference's wire format allows (a peer's vertices arrive as bare poses).  This UNDER-states S, so the gate d2 < gamma is
+ * stricter than the data justify: consistent candidates may be refused; inconsistent ones are not let in by it.  A null
+ * peer_cov and an all-zero one give identical bytes.
+ * d2_out, the adjacency, the clique (greedy; _exact: the branch and bound behind it), output nullability, nC == 0, the limit
+ * CGMR_PCM_MAX_CLOSURES, analysis cache, bounded-wait fall-back, return codes and their order, the zeroed outputs on
+ * CGMR_E_CHOLESKY_BASE and the launch classes 9..11 are those of cgmr_closure_consistency[_exact]; class 10 is
+ * k_closure_consistency_inter.  Device memory: cgmr_marginals_joint's at the unique own endpoints (at most nC, where the
+ * single-graph call has up to 2 nC), plus 8 nC^2 bytes of d2, plus 72 nC^2 bytes when peer_cov is given.
+ * CGMR_E_INVALID, before anything is queued and with the candidate named in cgmr_last_error, for every reason
+ * cgmr_closure_consistency[_exact] refuses a call (cl_a[k] outside [0, nV) among them), a null peer_pose_xyt with nC > 0, a
+ * peer pose that is not finite, a peer_cov with an entry in its lower triangle that is not finite, or with a negative
+ * diagonal entry. */
+int cgmr_closure_consistency_inter(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                                   const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt,
+                                   const double* info_upper, int nC, const int32_t* cl_a, const double* peer_pose_xyt,
+                                   const double* peer_cov, const double* cl_meas_xyt, const double* cl_info_upper, double gamma,
+                                   double* d2_out, uint64_t* adj_out, int32_t* clique_out, int32_t* clique_size_out,
+                                   int32_t* seed_out, const cgmr_robust* rk);
+int cgmr_closure_consistency_inter_exact(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                                         const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt,
+                                         const double* info_upper, int nC, const int32_t* cl_a, const double* peer_pose_xyt,
+                                         const double* peer_cov, const double* cl_meas_xyt, const double* cl_info_upper,
+                                         double gamma, double* d2_out, uint64_t* adj_out, int64_t node_limit,
+                                         int32_t* clique_out, int32_t* clique_size_out, int32_t* proven_out,
+                                         const cgmr_robust* rk);
 
 /* ------------------------------------------------------------------------------------------
  * Generic correlative search (loop-closure / hierarchical / global matching).

@@ -56,6 +56,7 @@ _SYMBOLS = [
     "cgmr_closure_consistency", "cgmr_max_clique_greedy", "cgmr_switches",
     "cgmr_closure_consistency_exact", "cgmr_max_clique_exact",
     "cgmr_closure_consistency_inter", "cgmr_closure_consistency_inter_exact",
+    "cgmr_match_close_vset_batch_dev", "cgmr_scan_transforms",
 ]
 
 JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)

@@ -650,6 +650,29 @@ class ScanMatcher(_GenericSearch, _BatchedSearch):
                                                      C.c_void_p(d_score), C.c_void_p(d_found), C.c_void_p(d_nres))
         self.ctx._check(rc)
 
+    def scan_transforms(self, rel_xyt):
+        """``cgmr_scan_transforms`` (host, libm, no GPU): ``rel_xyt`` (..., 3) = origin^-1 * v_k of reference scans ->
+        (n, 4) = (cos, sin, tx, ty) of (origin^-1 * v_k) * laserPose, what ``closeScanMatchingVSet_dev`` takes."""
+        rel = np.ascontiguousarray(rel_xyt, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros((len(rel), 4))
+        rc = self.ctx.lib.cgmr_scan_transforms(C.byref(self.cfg), C.c_int(len(rel)), C.c_void_p(rel.ctypes.data),
+                                               C.c_void_p(out.ctypes.data))
+        if rc != 0:
+            raise CgmrError(rc, "cgmr_scan_transforms: bad argument")
+        return out
+
+    def closeScanMatchingVSet_dev(self, d_ranges_ref, d_ref_xform, d_ranges_cur, d_guess, n_pairs, n_ref_scans, d_xyt,   # noqa: N802
+                                  d_score, d_found, maxScore=0.15, d_nres=0):   # noqa: N803
+        """Device-pointer variant of ``closeScanMatchingVSetBatch`` (ints from ``tensor.data_ptr()``): ``d_ranges_ref``
+        (P, S, n_beams) float32, ``d_ref_xform`` (P, S, 4) float64 from ``scan_transforms`` -- not the relative poses the
+        host call takes --, ``d_ranges_cur`` (P, n_beams), ``d_guess`` (P, 3)."""
+        rc = self.ctx.lib.cgmr_match_close_vset_batch_dev(self.ctx.h, C.byref(self.cfg), C.c_int(n_pairs), C.c_int(n_ref_scans),
+                                                          C.c_void_p(d_ranges_ref), C.c_void_p(d_ref_xform),
+                                                          C.c_void_p(d_ranges_cur), C.c_void_p(d_guess), C.c_double(maxScore),
+                                                          C.c_void_p(d_xyt), C.c_void_p(d_score), C.c_void_p(d_found),
+                                                          C.c_void_p(d_nres))
+        self.ctx._check(rc)
+
     def last_kernel_seconds(self) -> float:
         s = C.c_double()
         self.ctx._check(self.ctx.lib.cgmr_match_last_kernel_seconds(self.ctx.h, C.byref(s)))

@@ -7,7 +7,7 @@ Thin host-side mirror of the reference's
   * the wire structs of ``msg_factory.h`` (44 bytes per edge, float32 on the wire, src/mrslam/msg_factory.h:78-112,200-218);
   * ``GraphComm``'s pairwise UDP send / receive (src/mrslam/graph_comm.cpp:103-208), replaced by ONE all-gather per round
     of a fixed-capacity buffer per rank over RCCL / xGMI
-over the C ABI (include/cgmr.h "robot graph" and "exchange"; csrc/mrslam_api.cpp, mrslam_kernels.hip, rccl_comm.cpp).
+over the C ABI (include/cgmr.h "robot graph" and "exchange"; csrc/robot_graph.cpp, condensed_host.cpp, exchange_host.cpp, mrslam_kernels.hip, rccl_comm.cpp).
 Everything here is a ctypes call; there is no numeric or bookkeeping logic in Python and no CPU fallback for the numeric
 entry points (a graph created without a context only keeps the books, for CPU tests of the protocol).
 """

@@ -1,5 +1,7 @@
-// The cgmr_debug_* entry points of libcgmr.so: test hooks and debugging aids.
+// The cgmr_debug_* entry points of libcgmr.so: test hooks and debugging aids; behind them the robot graph's (cgmr_graph_debug_*)
+// and the wire kernels' (cgmr_wire_narrow_edges*).
 #include "gn_host.h"
+#include "robot_graph.h"
 
 #include <algorithm>
 #include <cstring>
@@ -182,3 +184,123 @@ extern "C" int cgmr_debug_work_records(cgmr_ctx* ctx, int cap, void* dev_out, vo
   }
   return n_work;
 }
+
+// ---- the robot graph and the wire (robot_graph.h, mrslam_device.h)
+
+extern "C" {
+
+// Debugging aid: the level-0 edge list (vertex indices) the solver sees: own edges first, then the received ones.
+int cgmr_graph_debug_edges(const cgmr_graph* g, int cap, int32_t* from_out, int32_t* to_out, int32_t* n_own_out) {
+  if (!g || cap < 0) return CGMR_E_INVALID;
+  const int n = (int)g->all_ef.size();
+  for (int k = 0; k < n && k < cap; k++) { from_out[k] = g->all_ef[k]; to_out[k] = g->all_et[k]; }
+  if (n_own_out) *n_own_out = (int32_t)g->ef.size();
+  return n;
+}
+
+// Test support: the compact second edge segment as the solver reads it (what k_accept_gather_edges / k_gather_edges wrote),
+// peer order -- the order of cgmr_graph_debug_edges behind the own edges.  cgmr_graph_received_edges reads the staging.
+int cgmr_graph_debug_received_segment(cgmr_graph* g, int cap, double* meas_out, double* info_upper_out) {
+  if (!g || cap < 0) return CGMR_E_INVALID;
+  if (!g->ctx) return gerr(g, CGMR_E_NO_DEVICE, "cgmr_graph_debug_received_segment: no device context");
+  cgmr_ctx* ctx = g->ctx;
+  const int n = std::min(g->nB, cap);
+  if (n > 0 && (meas_out || info_upper_out)) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (meas_out) HIP_TRY(ctx, hipMemcpyAsync(meas_out, g->d_meas_b, 24 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (info_upper_out) HIP_TRY(ctx, hipMemcpyAsync(info_upper_out, g->d_info_b, 48 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return g->nB;
+}
+
+namespace {
+struct ScratchDev {                   // device scratch of one test-support call
+  std::vector<void*> blocks;
+  ~ScratchDev() { for (void* p : blocks) (void)hipFree(p); }
+  void* alloc(size_t bytes) {
+    void* p = nullptr;
+    if (hipMalloc(&p, std::max(bytes, (size_t)16)) != hipSuccess) return nullptr;
+    blocks.push_back(p);
+    return p;
+  }
+  // a copy of `bytes` host bytes on the device
+  void* up(cgmr_ctx* ctx, const void* host, size_t bytes) {
+    void* p = alloc(bytes);
+    if (p && bytes && hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return nullptr;
+    return p;
+  }
+};
+}  // namespace
+
+// Test support: k_wire_write_edges on host data.  The kernel only ever sees solver output; this is the way in for values
+// the solver never produces (float32 subnormals, ties, overflow).  Every index is checked here: the kernel checks none.
+int cgmr_wire_narrow_edges(cgmr_ctx* ctx, int n, int32_t from_id, const int32_t* to_vertex, int n_vertices, const int32_t* vertex_ids,
+                           const double* est, const double* info_upper, void* edges44_out) {
+  if (!ctx || n < 0 || n_vertices < 0 || (n > 0 && (!to_vertex || !vertex_ids || !est || !info_upper || !edges44_out)))
+    return CGMR_E_INVALID;
+  for (int k = 0; k < n; k++)
+    if (to_vertex[k] < 0 || to_vertex[k] >= n_vertices) return set_err(ctx, CGMR_E_INVALID, "cgmr_wire_narrow_edges: vertex index out of range");
+  if (n == 0) return CGMR_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ScratchDev S;
+  void* d_to = S.up(ctx, to_vertex, 4 * (size_t)n);
+  void* d_ids = S.up(ctx, vertex_ids, 4 * (size_t)n_vertices);
+  void* d_est = S.up(ctx, est, 24 * (size_t)n);
+  void* d_info = S.up(ctx, info_upper, 48 * (size_t)n);
+  void* d_out = S.alloc(sizeof(WireEdge) * (size_t)n);
+  if (!d_to || !d_ids || !d_est || !d_info || !d_out) return set_err(ctx, CGMR_E_ALLOC, "cgmr_wire_narrow_edges: device scratch");
+  launch_wire_write_edges(ctx->stream, n, from_id, (const int32_t*)d_to, (const int32_t*)d_ids, (const double*)d_est, (const double*)d_info,
+                          (WireEdge*)d_out);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(edges44_out, d_out, sizeof(WireEdge) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return CGMR_OK;
+}
+
+// The batched form, as a batch of condensed-graph passes launches it: job j reads its vertex indices at to_vertex + j * marg_stride
+// bytes, and -- by its OUTPUT SLOT -- est / info at out_slot[j] * est_stride / info_stride bytes, and writes nq[j] records at
+// wire_inout + out_slot[j] * wire_stride bytes.  to_vertex holds njobs * marg_stride bytes, est / info / wire_inout n_slots strides
+// each; wire_inout goes to the device as it is and comes back whole (what the kernel must not touch keeps the caller's bytes).
+int cgmr_wire_narrow_edges_batched(cgmr_ctx* ctx, int njobs, const int32_t* nq, const int32_t* gauge_id, const int32_t* out_slot, int n_slots,
+                                   long long marg_stride, long long est_stride, long long info_stride, long long wire_stride,
+                                   const void* to_vertex, int n_vertices, const int32_t* vertex_ids, const void* est, const void* info_upper,
+                                   void* wire_inout) {
+  if (!ctx || njobs < 1 || n_slots < 1 || n_vertices < 0 || !nq || !gauge_id || !out_slot || !to_vertex || !vertex_ids || !est ||
+      !info_upper || !wire_inout || marg_stride < 4 || est_stride < 8 || info_stride < 8 || wire_stride < 4 || marg_stride % 4 ||
+      est_stride % 8 || info_stride % 8 || wire_stride % 4)
+    return CGMR_E_INVALID;
+  int nmax = 0;
+  std::vector<CondJobDev> jobs(njobs);
+  for (int j = 0; j < njobs; j++) {
+    const long long q = nq[j];
+    if (q < 0 || out_slot[j] < 0 || out_slot[j] >= n_slots || 4 * q > marg_stride || 24 * q > est_stride || 48 * q > info_stride ||
+        (long long)sizeof(WireEdge) * q > wire_stride)
+      return set_err(ctx, CGMR_E_INVALID, "cgmr_wire_narrow_edges_batched: job %d does not fit its strides", j);
+    const int32_t* tv = (const int32_t*)((const char*)to_vertex + (long long)j * marg_stride);
+    for (int k = 0; k < q; k++)
+      if (tv[k] < 0 || tv[k] >= n_vertices) return set_err(ctx, CGMR_E_INVALID, "cgmr_wire_narrow_edges_batched: vertex index out of range");
+    jobs[j] = CondJobDev{nq[j], 0, gauge_id[j], out_slot[j]};
+    nmax = std::max(nmax, nq[j]);
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ScratchDev S;
+  void* d_jobs = S.up(ctx, jobs.data(), sizeof(CondJobDev) * (size_t)njobs);
+  void* d_to = S.up(ctx, to_vertex, (size_t)njobs * (size_t)marg_stride);
+  void* d_ids = S.up(ctx, vertex_ids, 4 * (size_t)n_vertices);
+  void* d_est = S.up(ctx, est, (size_t)n_slots * (size_t)est_stride);
+  void* d_info = S.up(ctx, info_upper, (size_t)n_slots * (size_t)info_stride);
+  void* d_out = S.up(ctx, wire_inout, (size_t)n_slots * (size_t)wire_stride);
+  if (!d_jobs || !d_to || !d_ids || !d_est || !d_info || !d_out) return set_err(ctx, CGMR_E_ALLOC, "cgmr_wire_narrow_edges_batched: device scratch");
+  MargBatch mb;
+  mb.jobs = (const CondJobDev*)d_jobs;
+  mb.marg_stride = marg_stride; mb.est_stride = est_stride; mb.info_stride = info_stride; mb.wire_stride = wire_stride;
+  launch_wire_write_edges(ctx->stream, nmax, 0, (const int32_t*)d_to, (const int32_t*)d_ids, (const double*)d_est, (const double*)d_info,
+                          (WireEdge*)d_out, njobs, &mb);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(wire_inout, d_out, (size_t)n_slots * (size_t)wire_stride, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return CGMR_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // Host-side drivers of the Gauss-Newton path shared by the solver's translation units (gn_host.cpp, optimize_host.cpp,
-// marginals_host.cpp, cgmr_api.cpp, cgmr_debug.cpp) and mrslam_api.cpp.
+// marginals_host.cpp, cgmr_api.cpp, cgmr_debug.cpp) and the robot graph's (robot_graph.h).
 #pragma once
 #include <cmath>
 #include <cstdio>

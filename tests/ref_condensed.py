@@ -2,7 +2,7 @@
 (src/mrslam/condensed_graph/condensed_graph_buffer.{h,cpp}; src/mrslam/msg_factory.h:78-112,200-218;
 src/mrslam/mr_graph_slam.cpp:331-395), with the numeric step (``CondensedGraphCreator::compute``) delegated to whatever
 ``ctx.condense`` it is given -- the CPU oracle in the tests.  The product implements the same protocol in C++ / HIP
-behind the C ABI (csrc/mrslam_api.cpp, ``cg_mrslam_amd.condensed.RobotGraph``); the GPU tests run both through the same
+behind the C ABI (csrc/robot_graph.cpp, condensed_host.cpp, exchange_host.cpp, ``cg_mrslam_amd.condensed.RobotGraph``); the GPU tests run both through the same
 multi-robot rounds and compare edge by edge.  ``RefRobotGraph`` below gives this restatement the product's interface.
 Nothing under ``cg_mrslam_amd/`` imports this file.
 """

@@ -163,6 +163,56 @@ def test_capacity_overflow_skips_the_message_like_the_reference():
     assert g.message_from(big) == 0 and g.skipped_messages() == 2
 
 
+def test_ingests_and_one_peer_messages_in_sequence_equal_the_restatement():
+    """A round buffer, a one-peer message with fewer edges, a one-peer message with only unknown end points (the set is kept), a
+    round buffer again (tests/message_sequence.py): after every step a host-only graph holds exactly what the restatement
+    holds -- the edges of every peer, the counts, the out-closures, the skipped messages.  The one-peer path writes only the
+    slots of its message into the host staging; the round path the whole range of a sender."""
+    import message_sequence as MS
+    a, ra = RobotGraph(None, MS.ME, MS.R, cap_edges=MS.CAP), RefRobotGraph(None, MS.ME, MS.R, cap_edges=MS.CAP)
+    MS.fill(a); MS.fill(ra)
+    for kind, what, accepted in MS.steps():
+        if kind == "round":
+            n, n_ref = a.ingest_host(what), ra.ingest_host(what)
+            assert list(n) == list(n_ref) == accepted
+        else:
+            n, n_ref = a.message_from(what), ra.buf.ingest_from(what.robotId, what.edges, what.closures)
+            assert n == n_ref == accepted
+        MS.assert_same_state(MS.state(a), MS.state(ra))
+        assert a.counts() == ra.counts() and a.skipped_messages() == getattr(ra.buf, "skipped", 0) == 0     # (the restatement counts from its first pack on)
+    assert a.counts()["received_edges"] == 6 and list(a.closures(1, "out")) == [1, 2, 3] and list(a.closures(2, "out")) == [4]
+
+
+def test_error_texts_of_a_graph_without_a_device():
+    """The texts a robot graph reports where it has no device, byte for byte as they have always read."""
+    import ctypes as C
+    from cg_mrslam_amd import library_path
+    from cg_mrslam_amd._lib import CgmrError
+    g = RobotGraph(None, 0, 2, cap_edges=4)
+    g.add_vertices([0, 1], np.zeros((2, 3)), [1, 0])
+    g.add_edges([0], [1], [[1.0, 0, 0]], [[100, 0, 0, 100, 0, 1000]])
+    g.insertInClosure(1, [10000, 10001])
+
+    def last():
+        return g.lib.cgmr_graph_last_error(g.h).decode()
+
+    for call, text in ((lambda: g.pack(), "cgmr_graph_pack: no device context (use cgmr_graph_pack_host)"),
+                       (lambda: g.ingest(), "cgmr_graph_ingest: no device context (use cgmr_graph_ingest_host)"),
+                       (lambda: g.optimize(1), "cgmr_graph_optimize: the graph was created without a device context"),
+                       (lambda: g.optimize_gnc(), "cgmr_graph_optimize_gnc: the graph was created without a device context"),
+                       (lambda: g.computeCondensedGraph(-1), "cgmr_graph_compute_condensed: the graph was created without a device context"),
+                       (lambda: g.debug_received_segment(), "cgmr_graph_debug_received_segment: no device context")):
+        with pytest.raises(CgmrError) as ei:
+            call()
+        assert last() == text and text in str(ei.value)
+    ne, nc = C.c_int32(-1), C.c_int32(-1)                        # two requests for robot 1, room for none
+    rc = g.lib.cgmr_graph_message_for(g.h, C.c_int(1), C.c_int(0), None, C.byref(ne), C.c_int(0), None, C.byref(nc))
+    assert rc < 0 and last() == "cgmr_graph_message_for: output capacity too small"
+    # no call reaches this one without a device (a condensed graph set from the host is on the host): the library holds it
+    with open(library_path(), "rb") as f:
+        assert b"\0condensed graph not available on the host\0" in f.read()
+
+
 def test_select_gauge_centroid():
     xy = np.array([[0.0, 0], [10, 0], [4, 1], [5, 5]])
     assert select_gauge_centroid(xy) == 2

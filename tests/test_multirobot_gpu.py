@@ -165,7 +165,7 @@ COND_STREAMS_GOLDEN = os.path.join(ROOT, "tests", "golden", "cond_streams_r4x6.n
 
 
 def test_condensed_graphs_as_one_batch_equal_the_recorded_passes_on_streams(tmp_path):
-    """The condensed graphs of a round run as ONE batch of launches with a job dimension (mrslam_api.cpp run_cond_jobs).  Until
+    """The condensed graphs of a round run as ONE batch of launches with a job dimension (condensed_host.cpp run_cond_jobs).  Until
     they were retired every pass could also get its own stream of launches, as in round 2; what those passes computed for four
     robots x 6 rounds is on record (COND_STREAMS_GOLDEN, written from the last library that had them).  The batch, in a child process as the record was made: same world, same graphs built, same requested vertices,
     condensed edges and poses equal to rounding (the batch splits the backward solve's chained launch at another level: other

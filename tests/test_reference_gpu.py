@@ -286,7 +286,7 @@ def test_marginal_path_recovers_from_a_bounded_wait_that_ran_out(oracle):
 
 
 def test_batched_condensed_graphs_against_reference(oracle):
-    """The batched condensed path (k_solve_fwd_multi and k_label_edges with a job dimension, mrslam_api.cpp run_cond_jobs)
+    """The batched condensed path (k_solve_fwd_multi and k_label_edges with a job dimension, condensed_host.cpp run_cond_jobs)
     through RobotGraph.computeCondensedGraph: the first round of three robots with their own edges only, so the graph each
     condensed graph is built on is known exactly.  Gauge and query as RefRobotGraph takes them (selectGaugeCentroid over the
     requested vertices); every condensed(peer) meets condense_ref at the bars of the single-graph path."""

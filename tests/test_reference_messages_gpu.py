@@ -133,6 +133,35 @@ def test_read_side_equals_the_reference_decoder(ctx, fx):
     g.close()
 
 
+@pytest.mark.timeout(120)
+def test_ingests_and_one_peer_messages_in_sequence_on_the_device(ctx):
+    """The four steps of tests/message_sequence.py on a device graph -- a round buffer through k_wire_read and
+    k_accept_gather_edges, two one-peer messages through the host widening and k_gather_edges (one accepted, one that keeps the
+    set), a round buffer again: the host mirror of the staging goes stale, fresh, fresh, stale, and both users of the slot list
+    run.  After every step the staging (received_edges) and the solver's compact segment hold, bit for bit, what the restatement
+    holds -- which test_condensed_cpu.py shows a host-only graph of this library to hold as well."""
+    import torch
+    import message_sequence as MS
+    from ref_condensed import RefRobotGraph
+    g, ref = RobotGraph(ctx, MS.ME, MS.R, cap_edges=MS.CAP), RefRobotGraph(None, MS.ME, MS.R, cap_edges=MS.CAP)
+    MS.fill(g); MS.fill(ref)
+    for kind, what, accepted in MS.steps():
+        if kind == "round":
+            t = torch.from_numpy(what).cuda()
+            torch.cuda.synchronize()
+            assert list(g.ingest(t.data_ptr())) == list(ref.ingest_host(what)) == accepted
+        else:
+            assert g.message_from(what) == ref.buf.ingest_from(what.robotId, what.edges, what.closures) == accepted
+        ctx.synchronize()
+        want = MS.state(ref)
+        MS.assert_same_state(MS.state(g), want)
+        m, i = g.debug_received_segment()
+        assert np.array_equal(_bits(m), _bits(np.concatenate([want[0][p][2] for p in range(MS.R)])))
+        assert np.array_equal(_bits(i), _bits(np.concatenate([want[0][p][3] for p in range(MS.R)])))
+        assert g.counts() == ref.counts() and g.skipped_messages() == 0
+    g.close()
+
+
 def _index_map(to_ids, seed):
     """A shuffled id table and, per edge, the index of its far end in it: a permutation, nowhere the identity by luck alone."""
     ids = np.random.default_rng(seed).permutation(np.unique(to_ids)).astype(np.int32)

@@ -6,8 +6,9 @@ range's scratch slice holds -- four bytes past a vector of nf ints, from 2048 po
     cgmr_debug_asm_lists), several rounds in one process: the library once aborted in glibc ("double free or corruption") on
     such a sequence.  No sanitizer: what this pins is that the results are consistent and repeat.
   * tests/host/symbolic_sweep.cpp, the stand-alone harness, built with the host AddressSanitizer and
-    UndefinedBehaviorSanitizer and run as its own process with one and with four analysis threads.  Host code only: skipped
-    where a GPU is visible, or where the compiler or its sanitizer runtime is missing."""
+    UndefinedBehaviorSanitizer and run as its own process with one and with four analysis threads; beside it, built and run the
+    same way, tests/host/wire_sweep.cpp: the host's writer and reader of the inter-robot wire format (wire_format.h) on hostile
+    slices.  Host code only: skipped where a GPU is visible, or where the compiler or its sanitizer runtime is missing."""
 import os
 import shutil
 import subprocess
@@ -84,3 +85,6 @@ def test_sanitized_host_harness(tmp_path):
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-6000:])
     done = [l for l in r.stdout.splitlines() if l.startswith("symbolic_sweep:") and "analyses checked" in l]
     assert len(done) == 2 and all(l.endswith(" 0 failed") for l in done), done
+    # the second program of `make check`: the wire format's writer and reader (tests/host/wire_sweep.cpp)
+    wire = [l for l in r.stdout.splitlines() if l.startswith("wire_sweep:") and l.endswith(" cases checked")]
+    assert len(wire) == 1 and int(wire[0].split()[1]) > 1000, wire

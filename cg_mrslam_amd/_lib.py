@@ -57,12 +57,34 @@ _SYMBOLS = [
     "cgmr_closure_consistency_exact", "cgmr_max_clique_exact",
     "cgmr_closure_consistency_inter", "cgmr_closure_consistency_inter_exact",
     "cgmr_match_close_vset_batch_dev", "cgmr_scan_transforms",
+    "cgmr_jcbb_dense", "cgmr_joint_compatibility",
 ]
 
 JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)
 PCM_MAX_CLOSURES = 1024       # include/cgmr.h: CGMR_PCM_MAX_CLOSURES (candidates of a consistency call, vertices of a clique call)
 EXACT_DEFAULT_NODE_LIMIT = 512    # include/cgmr.h: CGMR_EXACT_DEFAULT_NODE_LIMIT (nodes per root and round of the exact clique search)
 EXACT_ROUNDS = 2              # csrc/pcm_device.h: CGMR_EXACT_ROUNDS (a call expands at most n * EXACT_ROUNDS * node_limit nodes)
+JC_MAX_OBS = 32               # include/cgmr.h: CGMR_JC_MAX_OBS (observations of a joint-compatibility call)
+JC_MAX_LANDMARKS = 256        # include/cgmr.h: CGMR_JC_MAX_LANDMARKS (its candidate landmarks)
+JC_ROUNDS = 2                 # csrc/jcbb_device.h: CGMR_JC_ROUNDS (a call makes at most roots * JC_ROUNDS * node_limit joint tests)
+JC_DEFAULT_NODE_LIMIT = 2048  # include/cgmr.h: CGMR_JC_DEFAULT_NODE_LIMIT (joint tests per root and round)
+# scipy.stats.chi2.ppf(0.99, k) for k = 1 .. 64 at index k (index 0 unused): the thresholds of a joint-compatibility call at the
+# 0.99 level, by degrees of freedom; entry 3 is GraphSLAM.GAMMA_99
+JC_GAMMA_99 = (
+    0.0, 6.6348966010212145, 9.21034037197618, 11.344866730144373, 13.276704135987622,
+    15.08627246938899, 16.811893829770927, 18.475306906582357, 20.090235029663233, 21.665994333461924,
+    23.209251158954356, 24.724970311318277, 26.216967305535853, 27.68824961045705, 29.141237740672796,
+    30.57791416689249, 31.999926908815176, 33.40866360500461, 34.805305734705065, 36.19086912927004,
+    37.56623478662507, 38.93217268351607, 40.289360437593864, 41.638398118858476, 42.97982013935165,
+    44.31410489621915, 45.64168266628317, 46.962942124751436, 48.27823577031548, 49.58788447289881,
+    50.89218131151707, 52.19139483319193, 53.48577183623535, 54.77553976011035, 56.06090874778906,
+    57.3420734338592, 58.61921450168706, 59.89250004508689, 61.1620867636897, 62.4281210161849,
+    63.690739751564465, 64.9500713352112, 66.20623628399322, 67.45934792232582, 68.7095129693454,
+    69.95683206583814, 71.20140024831149, 72.44330737654823, 73.68263852010573, 74.91947430847816,
+    76.1538912490127, 77.38596201613736, 78.6157557150025, 79.84333812225145, 81.0687719062971,
+    82.29211682919967, 83.51342993198946, 84.73276570506393, 85.95017624510335, 87.16571139978757,
+    88.37941890144937, 89.59134449068712, 90.80153203083871, 92.01002361413214, 93.21685966023843,
+)
 
 
 def declared_symbols():
@@ -1063,6 +1085,70 @@ class Context:
                               (C.c_int(n), _ptr(a), _ptr(pp), _ptr(pc), _ptr(cm), _ptr(ci), C.c_double(float(gamma)), _ptr(d2),
                                _ptr(words), C.c_int64(int(node_limit)), _ptr(clique), _ptr(size), _ptr(proven)), kind, delta)
         return (d2, self._adj_bool(words, n), clique[:int(size[0])].copy(), bool(proven[0])) + st
+
+    # joint-compatibility data association of landmark observations (include/cgmr.h: cgmr_jcbb_dense, cgmr_joint_compatibility)
+    @staticmethod
+    def _jc_outputs(nM, nL):
+        return (np.zeros((nM, nL)), np.full(nM, -1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.zeros(1),
+                np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int64))
+
+    @staticmethod
+    def _jc_gamma(gamma_by_dof, nM):
+        g = np.ascontiguousarray(JC_GAMMA_99 if gamma_by_dof is None else gamma_by_dof, dtype=np.float64).reshape(-1)
+        if len(g) < 2 * nM + 1:
+            raise ValueError(f"gamma_by_dof: {len(g)} entries, {2 * nM + 1} needed (index = degrees of freedom, 0 unused)")
+        return np.ascontiguousarray(g[:2 * nM + 1])
+
+    def jcbb_dense(self, obs_pose_slot, obs_dim, sigma, e, J, R_upper, gamma_by_dof=None, node_limit=JC_DEFAULT_NODE_LIMIT):
+        """Joint compatibility branch and bound on a caller's covariance (cgmr_jcbb_dense): M observations, observation i made
+        from pose ``obs_pose_slot[i]`` in dimension ``obs_dim[i]`` (2 xy, 1 bearing), against L landmarks.  ``sigma``
+        [3 nA + 2 L, 3 nA + 2 L]: the poses first, then the landmarks (the lower triangle is read); ``e`` [M, L, 2], ``J``
+        [M, L, 2, 5] the innovation and Jacobian of every pair, ``R_upper`` [M, 3] = (R00, R01, R11).  ``gamma_by_dof``: the
+        thresholds by degrees of freedom (None: JC_GAMMA_99).  Returns ``(assign [M] landmark positions or -1, count, d2, dof,
+        proven, ic [M, L], nodes)``: the admissible hypothesis with the most pairings, among those the smallest joint d2;
+        ``proven`` False: some root's search stopped at ``node_limit``, the result is the best found.  Deterministic."""
+        slot = np.ascontiguousarray(obs_pose_slot, dtype=np.int32).reshape(-1)
+        dim = np.ascontiguousarray(obs_dim, dtype=np.int32).reshape(-1)
+        nM = len(slot)
+        sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+        e = np.ascontiguousarray(e, dtype=np.float64).reshape(nM, -1, 2) if nM else np.zeros((0, 0, 2))
+        nL = e.shape[1]
+        nA = (sigma.shape[0] - 2 * nL) // 3
+        if dim.shape != (nM,) or sigma.shape != (3 * nA + 2 * nL, 3 * nA + 2 * nL) or nA < 0:
+            raise ValueError(f"jcbb_dense: {nM} observations, {nL} landmarks, sigma {sigma.shape}")
+        J = np.ascontiguousarray(J, dtype=np.float64).reshape(nM, nL, 2, 5)
+        R = np.ascontiguousarray(R_upper, dtype=np.float64).reshape(nM, 3)
+        g = self._jc_gamma(gamma_by_dof, nM)
+        ic, assign, count, d2, dof, proven, nodes = self._jc_outputs(nM, nL)
+        self._check(self.lib.cgmr_jcbb_dense(self.h, C.c_int(nM), C.c_int(nL), C.c_int(nA), _ptr(slot), _ptr(dim), _ptr(sigma), _ptr(e),
+                                             _ptr(J), _ptr(R), _ptr(g), C.c_int64(int(node_limit)), _ptr(ic), _ptr(assign),
+                                             _ptr(count), _ptr(d2), _ptr(dof), _ptr(proven), _ptr(nodes)))
+        return assign, int(count[0]), float(d2[0]), int(dof[0]), bool(proven[0]), ic, int(nodes[0])
+
+    def joint_compatibility(self, poses, fixed, ef, et, meas, info, obs_pose, obs_kind, obs_meas, obs_info, landmarks,
+                            gamma_by_dof=None, node_limit=JC_DEFAULT_NODE_LIMIT, vertex_kind=None, edge_kind=None, kind=None,
+                            delta=1.0):
+        """jcbb_dense on the graph's own covariance (cgmr_joint_compatibility): observation i made from pose vertex
+        ``obs_pose[i]`` as a factor of ``obs_kind[i]`` (1 EDGE_SE2_XY, 2 EDGE_BEARING_SE2_XY) with ``obs_meas`` [M, 3] /
+        ``obs_info`` [M, 6] (or None: no measurement noise) read as observation_covariance reads a hypothesis; ``landmarks``:
+        the candidate point vertices.  Returns jcbb_dense's tuple with ``assign`` in vertex indices; ``kind`` / ``delta``:
+        robust kernels, (e2, weights) appended."""
+        op = np.ascontiguousarray(obs_pose, dtype=np.int32).reshape(-1)
+        nM = len(op)
+        ok = np.ascontiguousarray(obs_kind, dtype=np.uint8).reshape(-1)
+        if ok.shape != (nM,):
+            raise ValueError(f"observation kinds: {ok.shape[0]} given for {nM} observations")
+        om = np.ascontiguousarray(obs_meas, dtype=np.float64).reshape(nM, 3)
+        oi = None if obs_info is None else np.ascontiguousarray(obs_info, dtype=np.float64).reshape(nM, 6)
+        lm = np.ascontiguousarray(landmarks, dtype=np.int32).reshape(-1)
+        nL = len(lm)
+        g = self._jc_gamma(gamma_by_dof, nM)
+        ic, assign, count, d2, dof, proven, nodes = self._jc_outputs(nM, nL)
+        st = self._joint_call("cgmr_joint_compatibility", poses, fixed, ef, et, meas, info,
+                              (C.c_int(nM), _ptr(op), _ptr(ok), _ptr(om), _ptr(oi), C.c_int(nL), _ptr(lm), _ptr(g),
+                               C.c_int64(int(node_limit)), _ptr(ic), _ptr(assign), _ptr(count), _ptr(d2), _ptr(dof), _ptr(proven),
+                               _ptr(nodes)), kind, delta, vertex_kind, edge_kind, typed=True)
+        return (assign, int(count[0]), float(d2[0]), int(dof[0]), bool(proven[0]), ic, int(nodes[0])) + st
 
     def set_symbolic_cache(self, on: bool):
         """Reuse of the ordering / symbolic analysis / structure upload across calls on the same edge list (default on)."""

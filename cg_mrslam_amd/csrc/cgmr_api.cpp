@@ -835,6 +835,25 @@ int cgmr_max_clique_exact(cgmr_ctx* ctx, int n, const uint64_t* adj_bits, int64_
   return clique_driver(ctx, n, adj_bits, clique_out, clique_size_out, nullptr, &ex);
 }
 
+int cgmr_jcbb_dense(cgmr_ctx* ctx, int nM, int nL, int nA, const int32_t* obs_pose_slot, const int32_t* obs_dim,
+                    const double* sigma, const double* e, const double* J, const double* R_upper, const double* gamma_by_dof,
+                    int64_t node_limit, double* ic_d2_out, int32_t* assign_out, int32_t* count_out, double* d2_out,
+                    int32_t* dof_out, int32_t* proven_out, int64_t* nodes_out) {
+  const JcOut out{ic_d2_out, assign_out, count_out, d2_out, dof_out, proven_out, nodes_out};
+  return jc_dense_driver(ctx, nM, nL, nA, obs_pose_slot, obs_dim, sigma, e, J, R_upper, gamma_by_dof, node_limit, out);
+}
+
+int cgmr_joint_compatibility(cgmr_ctx* ctx, int nV, const double* poses, const uint8_t* fixed, int nE, const int32_t* ef,
+                             const int32_t* et, const double* meas, const double* info, int nM, const int32_t* obs_pose,
+                             const uint8_t* obs_kind, const double* obs_meas, const double* obs_info, int nL,
+                             const int32_t* landmark_idx, const double* gamma_by_dof, int64_t node_limit, double* ic_d2_out,
+                             int32_t* assign_out, int32_t* count_out, double* d2_out, int32_t* dof_out, int32_t* proven_out,
+                             int64_t* nodes_out, const cgmr_factor_types* types, const cgmr_robust* rk) {
+  const JcOut out{ic_d2_out, assign_out, count_out, d2_out, dof_out, proven_out, nodes_out};
+  return jc_driver(ctx, host_call(nV, poses, fixed, nE, ef, et, meas, info, {false, rk, types}), nM, obs_pose, obs_kind, obs_meas,
+                   obs_info, nL, landmark_idx, gamma_by_dof, node_limit, out);
+}
+
 int cgmr_set_symbolic_cache(cgmr_ctx* ctx, int on) {
   if (!ctx) return CGMR_E_INVALID;
   ctx->sym_cache_on = on != 0;

@@ -60,5 +60,14 @@ int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, cons
                int32_t* seed_out, const CliqueExact* ex = nullptr, const PcmInter* inter = nullptr);
 int clique_driver(cgmr_ctx* ctx, int n, const uint64_t* adj, int32_t* clique_out, int32_t* size_out, int32_t* seed_out,
                   const CliqueExact* ex = nullptr);
+// Joint-compatibility data association (jcbb_host.cpp; include/cgmr.h: cgmr_jcbb_dense, cgmr_joint_compatibility).  The
+// outputs of both: ic [nM * nL] and nodes nullable, the others required; assign holds positions among the candidates
+// (jc_dense_driver) or their vertex indices (jc_driver).
+struct JcOut { double* ic; int32_t *assign, *count; double* d2; int32_t *dof, *proven; int64_t* nodes; };
+int jc_dense_driver(cgmr_ctx* ctx, int nM, int nL, int nA, const int32_t* slot, const int32_t* dim, const double* sigma,
+                    const double* e, const double* J, const double* R, const double* gamma, int64_t node_limit, const JcOut& out);
+// the pass and the solve half of joint_driver's mode 0 over the observing poses and the candidates, every lower Gram tile
+int jc_driver(cgmr_ctx* ctx, const HostCall& c, int nM, const int32_t* obs_pose, const uint8_t* obs_kind, const double* obs_meas,
+              const double* obs_info, int nL, const int32_t* lm, const double* gamma, int64_t node_limit, const JcOut& out);
 
 }  // namespace cgmr

@@ -849,6 +849,55 @@ class GraphSLAM:
                                         robust)[2]
         return d2.reshape(M, L)
 
+    def associateObservations(self, pose_idx, landmark_idxs, z, info, kind=1, gamma_by_dof=None, node_limit=None,     # noqa: N802
+                              robust: bool = False):
+        """Joint-compatibility data association (JCBB) of M measurements taken from pose ``pose_idx`` against L known
+        landmarks: where gateObservations leaves the assignment to the caller, this returns it.  ``z`` / ``info`` as for
+        gateObservations; ``kind`` 1, 2, or one kind per measurement (then ``z`` [M, 2] and ``info`` [M, 3], a bearing in
+        column 0).  ``gamma_by_dof``: the thresholds by degrees of freedom (None: the 0.99 quantiles, _lib.JC_GAMMA_99);
+        ``node_limit``: joint tests per root and round (None: the binding's default).  Returns ``(assign [M] of vertex indices or
+        -1, d2, dof, proven)``: the hypothesis with the most pairings whose every pairing passes its own gate and whose every
+        prefix passes the joint one, among those the smallest joint d2; ``proven`` False: the best found within the limit."""
+        lm = np.asarray(landmark_idxs, dtype=np.int32).reshape(-1)
+        kinds = np.asarray(kind, dtype=np.uint8).reshape(-1)
+        mixed = kinds.size > 1
+        zz = np.asarray(z, dtype=np.float64)
+        zz = zz.reshape(-1, 2) if mixed or int(kinds[0]) == 1 else zz.reshape(-1, 1)
+        M = len(zz)
+        kinds = kinds if mixed else np.full(M, int(kinds[0]), dtype=np.uint8)
+        if kinds.shape != (M,) or not np.all((kinds == 1) | (kinds == 2)):
+            raise ValueError("associateObservations: kind must be 1 (EDGE_SE2_XY) or 2 (EDGE_BEARING_SE2_XY), one or one per measurement")
+        uu = np.asarray(info, dtype=np.float64).reshape(M, -1)
+        hm, hi = np.zeros((M, 3)), np.zeros((M, 6))
+        xy = kinds == 1
+        if xy.any():
+            hm[xy, :2] = zz[xy, :2]
+            hi[np.ix_(xy, [0, 1, 3])] = uu[xy][:, :3] if uu.shape[1] == 3 else uu[xy][:, [0, 1, 3]]
+        hm[~xy, 0], hi[~xy, 0] = zz[~xy, 0], uu[~xy, 0]
+        a, kw, _ = self._joint_args(robust)
+        if node_limit is not None:
+            kw = dict(kw, node_limit=node_limit)
+        assign, _count, d2, dof, proven = self.ctx.joint_compatibility(*a, np.full(M, int(pose_idx), dtype=np.int32), kinds, hm, hi, lm,
+                                                                       gamma_by_dof, **kw)[:5]
+        return assign, d2, dof, proven
+
+    def addAssociatedObservations(self, pose_idx, landmark_idxs, z, info, kind=1, gamma_by_dof=None, node_limit=None,     # noqa: N802
+                                  robust: bool = False):
+        """associateObservations, then an addObservation / addBearing edge for every paired measurement (in measurement
+        order).  Returns the new edges' indices; an unpaired measurement adds nothing."""
+        assign = self.associateObservations(pose_idx, landmark_idxs, z, info, kind, gamma_by_dof, node_limit, robust)[0]
+        M = len(assign)
+        kinds = np.broadcast_to(np.asarray(kind, dtype=np.uint8).reshape(-1), (M,))
+        zz = np.asarray(z, dtype=np.float64).reshape(M, -1)
+        uu = np.asarray(info, dtype=np.float64).reshape(M, -1)
+        edges = []
+        for m in np.flatnonzero(assign >= 0):
+            if kinds[m] == 1:
+                edges.append(self.addObservation(int(pose_idx), int(assign[m]), zz[m, :2], uu[m, :3] if uu.shape[1] == 3 else uu[m, [0, 1, 3]]))
+            else:
+                edges.append(self.addBearing(int(pose_idx), int(assign[m]), zz[m, 0], uu[m, 0]))
+        return edges
+
     def chi2(self) -> float:
         g = self.graph
         ef, et, meas, info = g.level0()

@@ -948,6 +948,82 @@ int cgmr_closure_consistency_inter_exact(cgmr_ctx* ctx, int nV, const double* po
                                          int32_t* clique_out, int32_t* clique_size_out, int32_t* proven_out,
                                          const cgmr_robust* rk);
 
+/* Joint-compatibility data association of landmark observations: Neira and Tardos' joint compatibility branch and bound, JCBB
+ * (present in C ABI version 105 libraries that export these symbols).  cgmr_observation_covariance gates every (measurement,
+ * landmark) pair on its own; the innovations of one scan share the pose error, so two pairings that each pass can fail
+ * together.  These return the assignment.
+ *
+ * Observation i = 0 .. nM - 1 is made from a pose a_i in dimension d_i (2: EDGE_SE2_XY, 1: EDGE_BEARING_SE2_XY) with the
+ * measurement zh_i and the noise covariance R_i; the candidates j = 0 .. nL - 1 are distinct point landmarks.  Pair (i, j) has
+ * the innovation e_ij = z(a_i, l_j) - zh_i (a bearing's normalised), the Jacobian J_ij (d_i x 5) with respect to (x_ai, l_j)
+ * exactly as in cgmr_observation_covariance, and the individual distance ic_ij = e^T (J Sigma J^T + R_i)^-1 e.  A hypothesis
+ * h[i] in {-1} or [0, nL) is injective on its pairings.  Its joint distance d2_H = e_H^T C_H^-1 e_H: e_H stacks the paired
+ * innovations in observation order (dof D = the sum of their d_i); C_H has for paired i, k the block
+ * J_i Sigma_{(ai, h[i]), (ak, h[k])} J_k^T from the four cross blocks of Sigma, plus R_i on the diagonal blocks.  A test passes
+ * iff the distance is finite and < gamma_by_dof[dof] (host, [2 nM + 1], entry 0 unused; the caller owns the confidence
+ * level); NaN or a pivot of the Cholesky factorisation of C_H that is not positive and finite fails.  A hypothesis is
+ * ADMISSIBLE iff every pairing passes on its own (ic_ij < gamma[d_i]) and, for every i, its restriction to the observations
+ * 0 .. i passes jointly -- JCBB's prefix rule: the admissible set does not depend on the traversal, and it is smaller than
+ * "every jointly compatible subset".  The result is an admissible hypothesis with the most pairings, among those one with the
+ * smallest d2_H.
+ *
+ * The search (deterministic; csrc/jcbb_kernels.hip).  The candidates of observation i are its individually compatible
+ * landmarks in ascending (ic, j).  The greedy hypothesis is the lower bound: observations in order, each takes its first
+ * candidate that is unused and keeps the hypothesis jointly compatible, else none.  One sub-problem per root, an individually
+ * compatible pair (i0, j): the observations before i0 unpaired, i0 with j, depth-first over i0 + 1 .. nM - 1, candidates in list
+ * order, "unpaired" last.  A hypothesis is kept as soon as its last pairing passes when it has more pairings than the bound,
+ * or as many and a smaller d2; a subtree is left when the pairings it can still reach (one per observation left that has a
+ * candidate) are fewer than the bound's, or as many with d2 -- which never decreases along a branch -- not below the bound's.
+ * A node is one joint test, the root's own included; a root stops in front of test node_limit + 1 and keeps its best.  Two
+ * rounds: every root with the greedy hypothesis as the bound, then the stopped roots again with the best of the first round.
+ * Ties (equal count and bit-equal d2): within a root the hypothesis met first stays; over roots the lowest root i0 * nL + j,
+ * then the earlier round; the greedy hypothesis unless strictly beaten.
+ *   ic_d2_out [nM * nL] (nullable): ic_ij, NaN where not positive definite
+ *   assign_out [nM]: h (cgmr_jcbb_dense: the landmark's position j; cgmr_joint_compatibility: its vertex index), or -1
+ *   count_out, d2_out, dof_out [1]: the pairings, d2_H and D of the result
+ *   proven_out [1]: 1 when no root was stopped in its last round -- the result is the optimum --, else 0: the hypothesis is
+ *     still admissible and no worse than the greedy one
+ *   nodes_out [1] (nullable): the tests made over all roots and rounds, at most roots * CGMR_JC_ROUNDS (2) * node_limit
+ *
+ * cgmr_jcbb_dense: the caller's own Sigma and predictions.  obs_pose_slot [nM] in [0, nA), obs_dim [nM] 1 or 2; sigma
+ *   [(3 nA + 2 nL)^2] row-major, the nA poses first (3 each), then the nL landmarks (2 each), only the lower triangle is read;
+ *   e [nM * nL * 2], J [nM * nL * 2 * 5] (a bearing: e[0] and row 0 alone are read), R_upper [nM * 3] = (R00, R01, R11).
+ * cgmr_joint_compatibility: the nine graph arguments of cgmr_observation_covariance, then the observations -- obs_pose [nM]
+ *   vertex indices (poses), obs_kind [nM] 1 or 2, obs_meas_xyt [nM * 3] and obs_info_upper [nM * 6] read as that call reads a
+ *   hypothesis (nullable: R = 0) -- and the candidates landmark_idx [nL] (distinct points); types and rk last.  Sigma is that
+ *   of cgmr_marginals_joint_typed over the unique observing poses and the candidates (at most CGMR_JOINT_MAX_QUERIES), kept
+ *   on the device; analysis cache, bounded-wait fall-back, Cholesky / timeout / HIP / allocation codes as there
+ *   (CGMR_E_CHOLESKY_BASE: outputs zeroed, count 0).  The caller's poses are not modified; the other entry points' bytes do
+ *   not change.
+ * nM == 0 or nL == 0: CGMR_OK, count 0, proven 1, every assign_out -1.  CGMR_E_INVALID, before anything is queued and naming
+ * the observation or the landmark in cgmr_last_error: a null context or required pointer, a negative count, nM above
+ * CGMR_JC_MAX_OBS, nL above CGMR_JC_MAX_LANDMARKS, node_limit <= 0, a kind or dimension outside {1, 2}, a pose slot outside
+ * [0, nA), an observing vertex that is a point or out of range, a candidate that is a pose or out of range, a repeated
+ * candidate, a gamma_by_dof[1 .. 2 nM] that is not finite or not increasing, an entry of sigma's lower triangle or of R_upper that is not finite (a non-finite e or J only makes its pair
+ * incompatible).
+ * Work: one wavefront per root, the Cholesky factor of C_H (at most 64 x 64 doubles, 32 KiB) in LDS, four roots per workgroup;
+ * two calls give identical bytes in every output.  CGMR_JC_DEFAULT_NODE_LIMIT is what the Python binding passes: the largest
+ * power of two for which the slowest call found at the cap shape (32 x 256) stays at or under 0.27 s on an MI355X, the figure
+ * CGMR_EXACT_DEFAULT_NODE_LIMIT was chosen against.  Measured (tools/gpu_jcbb_time.py): a row of landmarks
+ * 0.5 m apart with a pose variance of 1e4 along it and a decoy that leaves the greedy hypothesis one pairing, so that all 8192
+ * roots search in the first round and half of the two rounds' budget is spent: 75 ms of device time at node_limit 512, 128 ms
+ * at 1024, 229 ms at 2048, 417 ms at 4096.  Tests per second over a call: 6e7 there (every root busy, mostly shallow tests),
+ * 7.5e5 .. 1.2e6 where only the few hundred roots of observation 0 search and descend to D = 64. */
+#define CGMR_JC_MAX_OBS 32
+#define CGMR_JC_MAX_LANDMARKS 256
+#define CGMR_JC_DEFAULT_NODE_LIMIT 2048
+int cgmr_jcbb_dense(cgmr_ctx* ctx, int nM, int nL, int nA, const int32_t* obs_pose_slot, const int32_t* obs_dim,
+                    const double* sigma, const double* e, const double* J, const double* R_upper, const double* gamma_by_dof,
+                    int64_t node_limit, double* ic_d2_out, int32_t* assign_out, int32_t* count_out, double* d2_out,
+                    int32_t* dof_out, int32_t* proven_out, int64_t* nodes_out);
+int cgmr_joint_compatibility(cgmr_ctx* ctx, int nV, const double* poses_xyt, const uint8_t* fixed, int nE,
+                             const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt, const double* info_upper,
+                             int nM, const int32_t* obs_pose, const uint8_t* obs_kind, const double* obs_meas_xyt,
+                             const double* obs_info_upper, int nL, const int32_t* landmark_idx, const double* gamma_by_dof,
+                             int64_t node_limit, double* ic_d2_out, int32_t* assign_out, int32_t* count_out, double* d2_out,
+                             int32_t* dof_out, int32_t* proven_out, int64_t* nodes_out, const cgmr_factor_types* types,
+                             const cgmr_robust* rk);
+
 /* ------------------------------------------------------------------------------------------
  * Generic correlative search (loop-closure / hierarchical / global matching).
  *

@@ -58,9 +58,11 @@ _SYMBOLS = [
     "cgmr_closure_consistency_inter", "cgmr_closure_consistency_inter_exact",
     "cgmr_match_close_vset_batch_dev", "cgmr_scan_transforms",
     "cgmr_jcbb_dense", "cgmr_joint_compatibility",
+    "cgmr_condense_tree", "cgmr_min_spanning_tree",
 ]
 
 JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)
+TREE_MAX_NODES = 1025         # include/cgmr.h: CGMR_TREE_MAX_NODES (the gauge and the unique requested vertices of a condense_tree call)
 PCM_MAX_CLOSURES = 1024       # include/cgmr.h: CGMR_PCM_MAX_CLOSURES (candidates of a consistency call, vertices of a clique call)
 EXACT_DEFAULT_NODE_LIMIT = 512    # include/cgmr.h: CGMR_EXACT_DEFAULT_NODE_LIMIT (nodes per root and round of the exact clique search)
 EXACT_ROUNDS = 2              # csrc/pcm_device.h: CGMR_EXACT_ROUNDS (a call expands at most n * EXACT_ROUNDS * node_limit nodes)
@@ -866,6 +868,40 @@ class Context:
             self._check(rc)
         return to[:rc].copy(), est[:rc].copy(), iu[:rc].copy(), cov[:rc].copy(), e2, w
 
+    # the condensed graph as a spanning tree of relative poses (include/cgmr.h: cgmr_condense_tree, cgmr_min_spanning_tree)
+    def condense_tree(self, poses, ef, et, meas, info, gauge, query, kind=None, delta=1.0):
+        """The condensed graph over ``query`` as the minimum spanning tree of log det Sigma_z over the gauge and the unique
+        requested vertices, rooted at the gauge: ``(from [n], to [n], est [n, 3], info_upper [n, 6], weight [n], flags [n])``,
+        one edge per requested vertex other than the gauge in order of first appearance, from = its parent in the tree.
+        flags: 0, 1 (unlabelled: identity information), 2 (no finite weight: hung on the gauge).  At most TREE_MAX_NODES nodes.
+        ``kind`` / ``delta``: robust kernels as condense_robust takes them, (e2, weights) appended."""
+        poses, ef, et, meas, info = self._graph_args(poses, ef, et, meas, info)
+        query = np.ascontiguousarray(query, dtype=np.int32).reshape(-1)
+        rk, e2, w, _keep = self._robust(kind, delta, len(ef)) if kind is not None else (None, None, None, None)
+        n = max(len(query), 1)
+        fr, to, fl = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        est, iu, wt = np.zeros((n, 3)), np.zeros((n, 6)), np.zeros(n)
+        rc = self.lib.cgmr_condense_tree(self.h, C.c_int(poses.shape[0]), _ptr(poses), C.c_int(len(ef)), _ptr(ef), _ptr(et),
+                                         _ptr(meas), _ptr(info), C.c_int(int(gauge)), C.c_int(len(query)), _ptr(query), _ptr(fr),
+                                         _ptr(to), _ptr(est), _ptr(iu), _ptr(wt), _ptr(fl),
+                                         C.byref(rk) if rk is not None else C.c_void_p(0))
+        if rc < 0:
+            self._check(rc)
+        out = tuple(a[:rc].copy() for a in (fr, to, est, iu, wt, fl))
+        return out if kind is None else out + (e2, w)
+
+    def min_spanning_tree(self, weights, root=0):
+        """``parent [n]`` (int32, parent[root] = -1) of the minimum spanning tree of the dense symmetric ``weights`` [n, n] under
+        the total order (w, max(a, b), min(a, b)), rooted at ``root``: the combinatorial half of condense_tree.  Only the lower
+        triangle is read; a NaN counts as +inf.  1 <= n <= TREE_MAX_NODES.  Deterministic."""
+        W = np.ascontiguousarray(weights, dtype=np.float64)
+        n = W.shape[0]
+        if W.shape != (n, n):
+            raise ValueError(f"weights: a square matrix, not {W.shape}")
+        parent = np.full(n, -1, dtype=np.int32)
+        self._check(self.lib.cgmr_min_spanning_tree(self.h, C.c_int(n), _ptr(W), C.c_int(int(root)), _ptr(parent)))
+        return parent
+
     # joint and pairwise blocks of H^-1, relative-pose uncertainty (include/cgmr.h: cgmr_marginals_joint ...).  ``kind`` None: the
     # plain call; otherwise robust kernels as marginals_robust takes them, and (e2 [nE], weights [nE]) are appended.
     # ``vertex_kind`` / ``edge_kind`` (either given): the typed entry point (cgmr_marginals_joint_typed ...), kinds as for
@@ -1193,7 +1229,8 @@ class Context:
 
     def pcm_kernel_times(self):
         """Profiling mode, classes 9..11 of cgmr_gn_kernel_times_ex: what closure_consistency spent in the forward solve and the
-        Gram tiles, in k_closure_consistency, and in the bit words and the clique (max_clique_greedy: the clique alone);
+        Gram tiles, in k_closure_consistency, and in the bit words and the clique (max_clique_greedy: the clique alone;
+        min_spanning_tree and condense_tree count their spanning-tree launch into the same class);
         (seconds, launches) each, added up since set_profiling(True)."""
         sec = np.zeros(12)
         n = np.zeros(12, dtype=np.int64)

@@ -854,6 +854,18 @@ int cgmr_joint_compatibility(cgmr_ctx* ctx, int nV, const double* poses, const u
                    obs_info, nL, landmark_idx, gamma_by_dof, node_limit, out);
 }
 
+int cgmr_condense_tree(cgmr_ctx* ctx, int nV, const double* poses, int nE, const int32_t* ef, const int32_t* et, const double* meas,
+                       const double* info, int gauge, int nK, const int32_t* query, int32_t* from_out, int32_t* to_out,
+                       double* est_out, double* info_out, double* weight_out, int32_t* flags_out, const cgmr_robust* rk) {
+  return condense_tree_driver(ctx, host_call(nV, poses, nullptr, nE, ef, et, meas, info, {false, rk}), gauge, nK, query, from_out, to_out,
+                              est_out, info_out, weight_out, flags_out);
+}
+
+int cgmr_min_spanning_tree(cgmr_ctx* ctx, int n, const double* weights, int root, int32_t* parent_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  return mst_driver(ctx, n, weights, root, parent_out);
+}
+
 int cgmr_set_symbolic_cache(cgmr_ctx* ctx, int on) {
   if (!ctx) return CGMR_E_INVALID;
   ctx->sym_cache_on = on != 0;

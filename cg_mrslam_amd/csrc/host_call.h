@@ -60,6 +60,11 @@ int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, cons
                int32_t* seed_out, const CliqueExact* ex = nullptr, const PcmInter* inter = nullptr);
 int clique_driver(cgmr_ctx* ctx, int n, const uint64_t* adj, int32_t* clique_out, int32_t* size_out, int32_t* seed_out,
                   const CliqueExact* ex = nullptr);
+// The condensed graph as a spanning tree of relative poses (include/cgmr.h: cgmr_condense_tree; c.fixed is not read: the gauge
+// alone is fixed), and the spanning tree alone on a caller's weights (cgmr_min_spanning_tree)
+int condense_tree_driver(cgmr_ctx* ctx, const HostCall& c, int gauge, int nK, const int32_t* query, int32_t* from_out,
+                         int32_t* to_out, double* est_out, double* info_out, double* weight_out, int32_t* flags_out);
+int mst_driver(cgmr_ctx* ctx, int n, const double* weights, int root, int32_t* parent_out);
 // Joint-compatibility data association (jcbb_host.cpp; include/cgmr.h: cgmr_jcbb_dense, cgmr_joint_compatibility).  The
 // outputs of both: ic [nM * nL] and nodes nullable, the others required; assign holds positions among the candidates
 // (jc_dense_driver) or their vertex indices (jc_driver).

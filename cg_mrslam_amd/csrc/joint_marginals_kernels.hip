@@ -19,20 +19,14 @@
 #include "factor_model.h"
 #include "gn_device.h"
 #include "pcm_device.h"
+#include "relative_cov_device.h"
 
 namespace cgmr {
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
-namespace {
-
-__device__ __forceinline__ double j_norm_theta(double t) {
-  const double pi = 3.14159265358979323846;
-  if (t >= -pi && t < pi) return t;
-  return t - 2 * pi * floor((t + pi) / (2 * pi));
-}
-
-}  // namespace   (gram_at, dense_pos: pcm_device.h, shared with pcm_kernels.hip)
+// (gram_at, dense_pos: pcm_device.h, shared with pcm_kernels.hip; j_norm_theta, relative_pose_cov: relative_cov_device.h, shared
+// with condense_tree_kernels.hip)
 
 // Partial tiles of the list: workgroup (tile t, row range s); each of the 4 wavefronts accumulates the tile over its quarter of
 // the range, then the four are summed in a fixed order.  rows: rows per range, a multiple of 16.
@@ -145,9 +139,8 @@ __global__ void k_pairs_extract(int nP, const int32_t* __restrict__ pr, const do
   ab[q] = (sa >= 0 && sb >= 0) ? gram_at(G, P[3], ca, cb) : 0.0;
 }
 
-// z = x_a^-1 x_b and its covariance by first-order propagation of the joint covariance of (x_a, x_b); one thread per pair.
-// J_a, J_b: the Jacobians of z for the additive (x, y, theta) update -- A and B of k_linearize (gn_kernels.hip) with a zero
-// measurement.  With a hypothesis (zh, Omega): e = zh^-1 z (EdgeSE2::computeError), J_e = R(zh.theta)^T (+) 1, and
+// z = x_a^-1 x_b and its covariance by first-order propagation of the joint covariance of (x_a, x_b) (relative_pose_cov); one
+// thread per pair.  With a hypothesis (zh, Omega): e = zh^-1 z (EdgeSE2::computeError), J_e = R(zh.theta)^T (+) 1, and
 // d2 = e^T (J_e Sigma_z J_e^T + Omega^-1)^-1 e (no Omega term with hyp_info null); NaN when that matrix is not positive definite.
 __global__ void k_relative_cov(int nP, const int32_t* __restrict__ pa, const int32_t* __restrict__ pb,
                                const double* __restrict__ poses, const double* __restrict__ aa, const double* __restrict__ ab,
@@ -158,34 +151,8 @@ __global__ void k_relative_cov(int nP, const int32_t* __restrict__ pa, const int
   if (p >= nP) return;
   const double* xa = poses + 3 * (size_t)pa[p];
   const double* xb = poses + 3 * (size_t)pb[p];
-  const double c = cos(xa[2]), s = sin(xa[2]);
-  const double dx = xb[0] - xa[0], dy = xb[1] - xa[1];
-  const double z[3] = {c * dx + s * dy, -s * dx + c * dy, j_norm_theta(xb[2] - xa[2])};
-  const double Ja[9] = {-c, -s, -s * dx + c * dy, s, -c, -c * dx - s * dy, 0, 0, -1};
-  const double Jb[9] = {c, s, 0, -s, c, 0, 0, 0, 1};
-  const double* Saa = aa + 9 * (size_t)p;
-  const double* Sab = ab + 9 * (size_t)p;
-  const double* Sbb = bb + 9 * (size_t)p;
-  // M_a = J_a Saa + J_b Sab^T, M_b = J_a Sab + J_b Sbb;  Sigma_z = M_a J_a^T + M_b J_b^T
-  double Ma[9], Mb[9], Sz[9];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) {
-      double u = 0, v = 0;
-      for (int k = 0; k < 3; k++) {
-        u += Ja[3 * i + k] * Saa[3 * k + j] + Jb[3 * i + k] * Sab[3 * j + k];
-        v += Ja[3 * i + k] * Sab[3 * k + j] + Jb[3 * i + k] * Sbb[3 * k + j];
-      }
-      Ma[3 * i + j] = u; Mb[3 * i + j] = v;
-    }
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) {
-      double u = 0;
-      for (int k = 0; k < 3; k++) u += Ma[3 * i + k] * Ja[3 * j + k] + Mb[3 * i + k] * Jb[3 * j + k];
-      Sz[3 * i + j] = u;
-    }
-  // (the two cross terms are each other's transposes: the sum is symmetric to rounding; returned symmetrised)
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < i; j++) { const double u = 0.5 * (Sz[3 * i + j] + Sz[3 * j + i]); Sz[3 * i + j] = u; Sz[3 * j + i] = u; }
+  double z[3], Sz[9];
+  relative_pose_cov(xa, xb, aa + 9 * (size_t)p, ab + 9 * (size_t)p, bb + 9 * (size_t)p, z, Sz);
   if (rel) for (int i = 0; i < 3; i++) rel[3 * (size_t)p + i] = z[i];
   if (rel_cov) for (int i = 0; i < 9; i++) rel_cov[9 * (size_t)p + i] = Sz[i];
   if (!d2) return;

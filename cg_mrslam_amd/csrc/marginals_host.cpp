@@ -1,5 +1,6 @@
-// The marginals family (host_call.h): the drivers of the marginals, joint, PCM and clique entry points.
+// The marginals family (host_call.h): the drivers of the marginals, joint, PCM, clique and condensed-tree entry points.
 // Compiled with hipcc; contains no kernels.
+#include "condense_tree_device.h"
 #include "marg_call.h"
 #include "pcm_device.h"
 
@@ -12,6 +13,36 @@ namespace cgmr {
 static void zero_point_dims(double* blk, bool row_point, bool col_point) {
   if (row_point) blk[6] = blk[7] = blk[8] = 0.0;
   if (col_point) blk[2] = blk[5] = blk[8] = 0.0;
+}
+
+// fixGauge and the spanning-tree guess from it: the linearisation point of marginal_driver's modes 1 and 2 and of
+// condense_tree_driver (call.work: the private copy of the poses)
+static void gauge_guess(MargCall& call, int gauge, std::vector<uint8_t>& fixed) {
+  const HostCall& c = call.c;
+  fixed[gauge] = 1;                                                   // fixGauge: every other vertex is freed
+  initial_guess_host(c.nV, call.work.data(), fixed.data(), c.nE, c.ef, c.et, c.meas);
+}
+
+// the permuted column of every vertex of `verts`, or -1 (fixed / inactive: zeros)
+static std::vector<int32_t> query_columns(const cgmr_ctx* ctx, const std::vector<int32_t>& verts) {
+  std::vector<int32_t> qcol(verts.size());
+  for (size_t k = 0; k < verts.size(); k++) qcol[k] = ctx->vmask[verts[k]] ? -1 : ctx->sym.vperm[verts[k]];
+  return qcol;
+}
+
+// The dense Gram half of a joint call -- every lower tile of Y^T Y, in 64x64 macro-tiles -- as joint_driver's mode 0,
+// pcm_driver and condense_tree_driver use it: the tile count and the row split for the layout M of the unique vertices ...
+static void dense_gram_plan(const MargLayout& M, JointGram& JG) {
+  const int T = M.m / 16;
+  JG.tiles = nullptr;
+  JG.ntile = (long long)T * (T + 1) / 2;
+  joint_gram_split(M.n, (long long)((T + 3) / 4) * ((T + 3) / 4 + 1) / 2, &JG.rows, &JG.nsplit);
+}
+// ... and, behind the pass, the solve half (Y = L^-1 E for the nU vertices' columns) with the tiles after it
+static void queue_solve_and_gram(hipStream_t st, const GnDevice& D, int nU, char* d, const MargLayout& ML, const JointGram& JG) {
+  launch_marginals_solve(st, D, nU, (const int32_t*)(d + ML.o_qc), ML.m, (double*)(d + ML.o_Y), (double*)(d + ML.o_U),
+                         (uint8_t*)(d + ML.o_live));
+  launch_joint_gram(st, ML.n, ML.m, (const double*)(d + ML.o_Y), JG);
 }
 
 // Shared driver of cgmr_marginals / cgmr_covariance_estimate / cgmr_condense (host pointers).
@@ -31,10 +62,7 @@ int marginal_driver(cgmr_ctx* ctx, int mode, const HostCall& c, int gauge, int n
   const TypedHost& typed = call.typed;
   std::vector<uint8_t> fixed(c.nV, 0);
   if (mode == 0) { if (!c.fixed) return set_err(ctx, CGMR_E_INVALID, "fixed flags missing"); fixed.assign(c.fixed, c.fixed + c.nV); }
-  else {
-    fixed[gauge] = 1;                                                   // fixGauge: every other vertex is freed
-    initial_guess_host(c.nV, call.work.data(), fixed.data(), c.nE, c.ef, c.et, c.meas);
-  }
+  else gauge_guess(call, gauge, fixed);
   // query list (condense: everything but the gauge)
   std::vector<int32_t> q;
   for (int k = 0; k < nK; k++) if (mode != 2 || query[k] != gauge) q.push_back(query[k]);
@@ -52,8 +80,7 @@ int marginal_driver(cgmr_ctx* ctx, int mode, const HostCall& c, int gauge, int n
   rc = call.stage();
   if (rc) return rc;
   char* d = call.d;
-  std::vector<int32_t> qcol(nq);
-  for (int k = 0; k < nq; k++) qcol[k] = ctx->vmask[q[k]] ? -1 : S.vperm[q[k]];     // fixed / inactive: zeros
+  const std::vector<int32_t> qcol = query_columns(ctx, q);
   HIP_TRY(ctx, hipMemcpyAsync(d + M.o_qc, qcol.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d + M.o_qv, q.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, st));
   // the Hessian of this iteration (linearised at the initial guess) is what computeMarginals sees [g2o-recalled];
@@ -229,11 +256,11 @@ int joint_driver(cgmr_ctx* ctx, const char* who, int mode, const HostCall& c, in
   // the tiles: every lower one (joint), or those of the pairs' blocks, sorted, each once
   const MargLayout M(nU, D.nf, S.rows.size(), D.nfronts, 0);
   const int T = M.m / 16;
-  std::vector<int32_t> qcol(nU), tl, pr;
-  for (int k = 0; k < nU; k++) qcol[k] = ctx->vmask[uq[k]] ? -1 : S.vperm[uq[k]];      // fixed / inactive: zero columns
+  const std::vector<int32_t> qcol = query_columns(ctx, uq);
+  std::vector<int32_t> tl, pr;
   JointGram JG;
   if (mode == 0) {
-    JG.ntile = (long long)T * (T + 1) / 2;
+    dense_gram_plan(M, JG);
     pr.resize(nQ);
     for (int k = 0; k < nQ; k++) pr[k] = qcol[slot_of[va[k]]] < 0 ? -1 : slot_of[va[k]];
   } else {
@@ -258,8 +285,7 @@ int joint_driver(cgmr_ctx* ctx, const char* who, int mode, const HostCall& c, in
       P[2] = pos(sa, sa); P[3] = pos(sa, sb); P[4] = pos(sb, sb);
     }
   }
-  const long long nwg = mode == 0 ? (long long)((T + 3) / 4) * ((T + 3) / 4 + 1) / 2 : JG.ntile;
-  joint_gram_split(M.n, nwg, &JG.rows, &JG.nsplit);
+  if (mode != 0) joint_gram_split(M.n, JG.ntile, &JG.rows, &JG.nsplit);
   // staging: poses | meas | info | query columns, Y, border vectors, live flags (MargLayout) | tile list | pairs / slots |
   // partial tiles | tiles | outputs | the pair vertices and the hypotheses
   Layout256& L = call.L;
@@ -284,7 +310,7 @@ int joint_driver(cgmr_ctx* ctx, const char* who, int mode, const HostCall& c, in
     if (hyp_info) HIP_TRY(ctx, hipMemcpyAsync(d + o_hi, hyp_info, 48 * nq, hipMemcpyHostToDevice, st));
     if (obs_typed) HIP_TRY(ctx, hipMemcpyAsync(d + o_ok, obs_kind, nq, hipMemcpyHostToDevice, st));
   }
-  JG.tiles = mode == 0 ? nullptr : (const int32_t*)(d + o_tl);
+  if (mode != 0) JG.tiles = (const int32_t*)(d + o_tl);
   JG.part = (double*)(d + o_part);
   JG.G = (double*)(d + o_G);
   GnPassOpts pass;
@@ -292,9 +318,7 @@ int joint_driver(cgmr_ctx* ctx, const char* who, int mode, const HostCall& c, in
   const bool want_d2 = mode == 2 && out_c;
   rc = call.run(pass, [&]() -> int {
     if (call.factor) {
-      launch_marginals_solve(st, D, nU, (const int32_t*)(d + ML.o_qc), ML.m, (double*)(d + ML.o_Y), (double*)(d + ML.o_U),
-                             (uint8_t*)(d + ML.o_live));
-      launch_joint_gram(st, ML.n, ML.m, (const double*)(d + ML.o_Y), JG);
+      queue_solve_and_gram(st, D, nU, d, ML, JG);
       if (mode == 0) launch_joint_extract(st, nQ, (const int32_t*)(d + o_pr), JG.G, (double*)(d + o_a));
       else launch_pairs_extract(st, nQ, (const int32_t*)(d + o_pr), JG.G, (double*)(d + o_a), (double*)(d + o_b), (double*)(d + o_c));
     } else {                                                           // (mode 2 without a free vertex: zero blocks)
@@ -450,18 +474,17 @@ int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, cons
   hipStream_t st = ctx->stream;
   call.factor = D.nf > 0;                                          // no free vertex: Sigma = 0, the measurement terms alone
   const MargLayout M(nU, D.nf, S.rows.size(), D.nfronts, 0);
-  const int T = M.m / 16, W = (nC + 63) / 64;
+  const int W = (nC + 63) / 64;
   const size_t n = (size_t)nC;
-  std::vector<int32_t> qcol(nU), sl(2 * n);                         // (with `inter`: one slot per candidate, the front half)
-  for (int k = 0; k < nU; k++) qcol[k] = ctx->vmask[uq[k]] ? -1 : S.vperm[uq[k]];      // fixed / inactive: zero columns
+  const std::vector<int32_t> qcol = query_columns(ctx, uq);
+  std::vector<int32_t> sl(2 * n);                                   // (with `inter`: one slot per candidate, the front half)
   for (int k = 0; k < nC && !inter; k++) {
     const int sa = slot_of[ca[k]], sb = slot_of[cb[k]];
     sl[2 * k] = qcol[sa] < 0 ? -1 : sa; sl[2 * k + 1] = qcol[sb] < 0 ? -1 : sb;
   }
   for (int k = 0; k < nC && inter; k++) { const int sa = slot_of[ca[k]]; sl[k] = qcol[sa] < 0 ? -1 : sa; }
   JointGram JG;
-  JG.ntile = (long long)T * (T + 1) / 2;
-  joint_gram_split(M.n, (long long)((T + 3) / 4) * ((T + 3) / 4 + 1) / 2, &JG.rows, &JG.nsplit);
+  dense_gram_plan(M, JG);
   // staging: poses | meas | info | query columns, Y, border vectors, live flags (MargLayout) | partial tiles | tiles | the
   // candidates (b, or with `inter` the peer's poses [| their covariance]) | d2 | bit words | the clique's work space
   Layout256& L = call.L;
@@ -501,11 +524,7 @@ int pcm_driver(cgmr_ctx* ctx, const HostCall& c, int nC, const int32_t* ca, cons
   rc = call.run(pass, [&]() -> int {
     KTimer KT{ctx, st};
     if (call.factor)
-      KT.run(9, 2, [&] {
-        launch_marginals_solve(st, D, nU, (const int32_t*)(d + ML.o_qc), ML.m, (double*)(d + ML.o_Y), (double*)(d + ML.o_U),
-                               (uint8_t*)(d + ML.o_live));
-        launch_joint_gram(st, ML.n, ML.m, (const double*)(d + ML.o_Y), JG);
-      });
+      KT.run(9, 2, [&] { queue_solve_and_gram(st, D, nU, d, ML, JG); });
     KT.run(10, 1, [&] {
       if (inter) launch_closure_consistency_inter(st, CI, call.dp, JG.G, (double*)(d + o_d2));
       else launch_closure_consistency(st, C, call.dp, JG.G, (double*)(d + o_d2));
@@ -575,6 +594,131 @@ int clique_driver(cgmr_ctx* ctx, int n, const uint64_t* adj, int32_t* clique_out
   HIP_TRY(ctx, hipGetLastError());
   if (ctx->profiling) profile_collect(ctx);
   clique_result_out(res, n, clique_out, size_out, seed_out, ex, total);
+  return CGMR_OK;
+}
+
+// cgmr_condense_tree: the front half of marginal_driver's mode 2 (the gauge fixed, the spanning-tree guess, one pass with the
+// step solved and applied), the solve half and the dense Gram half of joint_driver's mode 0 over the nq unique requested
+// vertices, then the kernels of condense_tree_kernels.hip on the tiles where they lie: the weight of every pair of nodes, the
+// minimum spanning tree from the gauge (in profiling mode in class 11, as cgmr_min_spanning_tree's) and the label of every
+// tree edge at the poses after the step.
+int condense_tree_driver(cgmr_ctx* ctx, const HostCall& c, int gauge, int nK, const int32_t* query, int32_t* from_out,
+                         int32_t* to_out, double* est_out, double* info_out, double* weight_out, int32_t* flags_out) {
+  const char* who = "cgmr_condense_tree";
+  MargCall call(ctx, c);
+  int rc = call.args(nK < 0 || (nK > 0 && (!query || !from_out || !to_out || !est_out || !info_out)), who);
+  if (rc) return rc;
+  if (gauge < 0 || gauge >= c.nV) return set_err(ctx, CGMR_E_INVALID, "%s: gauge index out of range", who);
+  for (int k = 0; k < nK; k++)
+    if (query[k] < 0 || query[k] >= c.nV) return set_err(ctx, CGMR_E_INVALID, "%s: query index out of range", who);
+  // the nodes: the gauge, then the unique requested vertices other than it, in order of first appearance
+  std::vector<int32_t> vert(1, gauge);
+  {
+    std::vector<uint8_t> seen(c.nV, 0);
+    seen[gauge] = 1;
+    for (int k = 0; k < nK; k++)
+      if (!seen[query[k]]) { seen[query[k]] = 1; vert.push_back(query[k]); }
+  }
+  const int n = (int)vert.size(), nq = n - 1;
+  if (n > CGMR_TREE_MAX_NODES)
+    return set_err(ctx, CGMR_E_INVALID, "%s: %d nodes (the gauge and %d requested vertices), at most CGMR_TREE_MAX_NODES = %d", who, n, nq,
+                   CGMR_TREE_MAX_NODES);
+  rc = call.open(who);
+  if (rc) return rc;
+  std::vector<uint8_t> fixed(c.nV, 0);
+  gauge_guess(call, gauge, fixed);
+  rc = call.structure(fixed.data());
+  if (rc) return rc;
+  Symbolic& S = ctx->sym;
+  GnDevice& D = ctx->gn;
+  hipStream_t st = ctx->stream;
+  if (D.nf == 0 || nq == 0) { HIP_TRY(ctx, hipStreamSynchronize(st)); return 0; }
+  const std::vector<int32_t> q(vert.begin() + 1, vert.end());
+  const std::vector<int32_t> qcol = query_columns(ctx, q);
+  std::vector<int32_t> slot(n, -1);                                // (node 0, the gauge: zero rows of Sigma)
+  for (int k = 0; k < nq; k++) slot[k + 1] = qcol[k] < 0 ? -1 : k;
+  // staging: poses | meas | info | query columns, Y, border vectors, the edges' estimates, information and flags, live flags
+  // (MargLayout) | partial tiles | tiles | node vertices | node slots | weights | parents | chosen weights
+  Layout256& L = call.L;
+  const MargLayout ML(nq, D.nf, S.rows.size(), D.nfronts, L.off);
+  L.off = ML.end;
+  JointGram JG;
+  dense_gram_plan(ML, JG);
+  const size_t o_part = L.add(JG.nsplit > 1 ? 2048 * (size_t)JG.nsplit * (size_t)JG.ntile : 0), o_G = L.add(2048 * (size_t)JG.ntile),
+               o_nv = L.add(4 * (size_t)n), o_ns = L.add(4 * (size_t)n), o_W = L.add(8 * (size_t)n * n), o_par = L.add(4 * (size_t)n),
+               o_ws = L.add(8 * (size_t)n);
+  rc = call.stage();
+  if (rc) return rc;
+  char* d = call.d;
+  HIP_TRY(ctx, hipMemcpyAsync(d + ML.o_qc, qcol.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_nv, vert.data(), 4 * (size_t)n, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_ns, slot.data(), 4 * (size_t)n, hipMemcpyHostToDevice, st));
+  JG.part = (double*)(d + o_part);
+  JG.G = (double*)(d + o_G);
+  TreeNodes N;
+  N.n = n;
+  N.vert = (const int32_t*)(d + o_nv); N.slot = (const int32_t*)(d + o_ns);
+  std::vector<int32_t> parent(n), flags(nq);
+  std::vector<double> wsel(n);
+  GnPassOpts pass;
+  pass.solve = pass.update_poses = true;
+  rc = call.run(pass, [&]() -> int {
+    KTimer KT{ctx, st};
+    queue_solve_and_gram(st, D, nq, d, ML, JG);
+    launch_tree_weights(st, N, call.dp, JG.G, (double*)(d + o_W));
+    KT.run(11, 1, [&] { launch_min_spanning_tree(st, n, (const double*)(d + o_W), 0, (int32_t*)(d + o_par), (double*)(d + o_ws)); });
+    launch_tree_labels(st, N, (const int32_t*)(d + o_par), (const double*)(d + o_ws), call.dp, JG.G, (double*)(d + ML.o_est),
+                       (double*)(d + ML.o_info), (int32_t*)(d + ML.o_fl));
+    HIP_TRY(ctx, hipMemcpyAsync(parent.data(), d + o_par, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(wsel.data(), d + o_ws, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(flags.data(), d + ML.o_fl, 4 * (size_t)nq, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(est_out, d + ML.o_est, 24 * (size_t)nq, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(info_out, d + ML.o_info, 48 * (size_t)nq, hipMemcpyDeviceToHost, st));
+    return 0;
+  });
+  if (ctx->profiling) profile_collect(ctx);
+  if (rc) return rc;
+  rc = call.close();
+  if (rc) return rc;
+  for (int k = 0; k < nq; k++) {
+    from_out[k] = vert[parent[k + 1]];
+    to_out[k] = vert[k + 1];
+    if (weight_out) weight_out[k] = wsel[k + 1];
+    if (flags_out) flags_out[k] = flags[k];
+  }
+  return nq;
+}
+
+// cgmr_min_spanning_tree: k_min_spanning_tree alone on a caller's matrix.  The kernel walks whole rows: the lower triangle is
+// mirrored into the upper on the way up (a NaN as +inf), so that only the lower one is ever read.
+int mst_driver(cgmr_ctx* ctx, int n, const double* weights, int root, int32_t* parent_out) {
+  const char* who = "cgmr_min_spanning_tree";
+  if (n < 1 || !weights || !parent_out) return set_err(ctx, CGMR_E_INVALID, "%s: null or non-positive argument", who);
+  if (n > CGMR_TREE_MAX_NODES) return set_err(ctx, CGMR_E_INVALID, "%s: %d nodes, at most CGMR_TREE_MAX_NODES = %d", who, n, CGMR_TREE_MAX_NODES);
+  if (root < 0 || root >= n) return set_err(ctx, CGMR_E_INVALID, "%s: root %d outside [0, %d)", who, root, n);
+  const size_t N = (size_t)n;
+  std::vector<double> W(N * N);
+  for (size_t a = 0; a < N; a++) {
+    W[a * N + a] = INFINITY;
+    for (size_t b = 0; b < a; b++) {
+      const double w = weights[a * N + b];
+      W[a * N + b] = W[b * N + a] = w == w ? w : INFINITY;
+    }
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  Layout256 L;
+  const size_t o_W = L.add(8 * N * N), o_par = L.add(4 * N), o_ws = L.add(8 * N);
+  int rc = arena_reserve(ctx, ctx->io_arena, L.off + 256);
+  if (rc) return rc;
+  char* d = ctx->io_arena.ptr;
+  hipStream_t st = ctx->stream;
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_W, W.data(), 8 * N * N, hipMemcpyHostToDevice, st));
+  KTimer KT{ctx, st};
+  KT.run(11, 1, [&] { launch_min_spanning_tree(st, n, (const double*)(d + o_W), root, (int32_t*)(d + o_par), (double*)(d + o_ws)); });
+  HIP_TRY(ctx, hipMemcpyAsync(parent_out, d + o_par, 4 * N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  HIP_TRY(ctx, hipGetLastError());
+  if (ctx->profiling) profile_collect(ctx);
   return CGMR_OK;
 }
 

@@ -19,6 +19,7 @@
 
 #include "gn_device.h"
 #include "gn_symbolic.h"
+#include "label_device.h"
 
 namespace cgmr {
 
@@ -26,12 +27,6 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 
 namespace {
 constexpr int MB = 16;            // right-hand sides per workgroup in the multi-RHS forward solve
-
-__device__ __forceinline__ double d_norm_theta(double t) {
-  const double pi = 3.14159265358979323846;
-  if (t >= -pi && t < pi) return t;
-  return t - 2 * pi * floor((t + pi) / (2 * pi));
-}
 }  // namespace
 
 // job dimension (blockIdx.z) of a batch of passes: gn_device.h MargBatch, gn_kernels.hip CGMR_JOB
@@ -234,7 +229,7 @@ __global__ void k_marg_extract(int nK, const double* __restrict__ G, double* __r
   cov[q] = G[(size_t)(k >> 2) * 256 + (o + e / 3) * 16 + o + e % 3];
 }
 
-// EdgeLabeler::labelEdge for star edges gauge -> v (SURVEY.md Appendix A [g2o-recalled]); one thread per edge.
+// EdgeLabeler::labelEdge for star edges gauge -> v (label_device.h: label_star_edge); one thread per edge.
 __global__ void k_label_edges(int nK, const int32_t* __restrict__ qvert, int gauge, const double* __restrict__ poses,
                               const double* __restrict__ cov, double* __restrict__ est, double* __restrict__ info,
                               int* __restrict__ flags, const CondJobDev* __restrict__ jobs, long long ms, long long ps,
@@ -249,72 +244,7 @@ __global__ void k_label_edges(int nK, const int32_t* __restrict__ qvert, int gau
   if (k >= nK) return;
   const double* xg = poses + 3 * (size_t)gauge;
   const double* xv = poses + 3 * (size_t)qvert[k];
-  const double* S = cov + 9 * (size_t)k;
-  const double alpha = 1e-3, beta = 2.0;
-  const int dim = 3;
-  const double lambda = alpha * alpha * dim;
-  const double wi = 1.0 / (2.0 * (dim + lambda));
-  const double wm0 = lambda / (dim + lambda);
-  const double wc0 = wm0 + (1.0 - alpha * alpha + beta);
-  // measurement := xg^-1 * xv (setMeasurementFromState)
-  double cg = cos(xg[2]), sg = sin(xg[2]);
-  double dx = xv[0] - xg[0], dy = xv[1] - xg[1];
-  double z0 = cg * dx + sg * dy, z1 = -sg * dx + cg * dy, z2 = d_norm_theta(xv[2] - xg[2]);
-  est[3 * k] = z0; est[3 * k + 1] = z1; est[3 * k + 2] = z2;
-  // LLT of (dim + lambda) * Sigma
-  double A[9], L[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int q = 0; q < 9; q++) A[q] = S[q] * (dim + lambda);
-  bool ok = true;
-  for (int j = 0; j < 3 && ok; j++) {
-    double d = A[3 * j + j];
-    for (int q = 0; q < j; q++) d -= L[3 * j + q] * L[3 * j + q];
-    if (!(d > 0)) { ok = false; break; }
-    L[3 * j + j] = sqrt(d);
-    for (int i = j + 1; i < 3; i++) {
-      double s = A[3 * i + j];
-      for (int q = 0; q < j; q++) s -= L[3 * i + q] * L[3 * j + q];
-      L[3 * i + j] = s / L[3 * j + j];
-    }
-  }
-  double* iu = info + 6 * (size_t)k;
-  if (!ok) {   // g2o leaves the edge unlabeled: identity information
-    iu[0] = 1; iu[1] = 0; iu[2] = 0; iu[3] = 1; iu[4] = 0; iu[5] = 1;
-    flags[k] = 1;
-    return;
-  }
-  double err[7][3], wm[7], wc[7];
-  const double czz = cos(z2), szz = sin(z2);
-  for (int q = 0; q < 7; q++) {
-    double px = 0, py = 0, pt = 0;
-    if (q > 0) {
-      int i = (q - 1) >> 1;
-      double sgn = ((q - 1) & 1) ? -1.0 : 1.0;
-      px = sgn * L[0 + i]; py = sgn * L[3 + i]; pt = sgn * L[6 + i];
-    }
-    wm[q] = q ? wi : wm0;
-    wc[q] = q ? wi : wc0;
-    double sx = xv[0] + px, sy = xv[1] + py, st = d_norm_theta(xv[2] + pt);
-    double ddx = sx - xg[0], ddy = sy - xg[1];
-    double rx = cg * ddx + sg * ddy, ry = -sg * ddx + cg * ddy, rth = d_norm_theta(st - xg[2]);
-    double tx = rx - z0, ty = ry - z1;
-    err[q][0] = czz * tx + szz * ty;
-    err[q][1] = -szz * tx + czz * ty;
-    err[q][2] = d_norm_theta(rth - z2);
-  }
-  double mean[3] = {0, 0, 0}, C[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int q = 0; q < 7; q++)
-    for (int a = 0; a < 3; a++) mean[a] += wm[q] * err[q][a];
-  for (int q = 0; q < 7; q++) {
-    double d[3] = {err[q][0] - mean[0], err[q][1] - mean[1], err[q][2] - mean[2]};
-    for (int a = 0; a < 3; a++)
-      for (int b = 0; b < 3; b++) C[3 * a + b] += wc[q] * d[a] * d[b];
-  }
-  double a = C[0], b = C[1], c = C[2], d = C[3], e = C[4], f = C[5], g = C[6], h = C[7], i = C[8];
-  double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
-  double id = 1.0 / det;
-  iu[0] = (e * i - f * h) * id; iu[1] = (c * h - b * i) * id; iu[2] = (b * f - c * e) * id;
-  iu[3] = (a * i - c * g) * id; iu[4] = (c * d - a * f) * id; iu[5] = (a * e - b * d) * id;
-  flags[k] = 0;
+  flags[k] = label_star_edge(xg, xv, cov + 9 * (size_t)k, est + 3 * k, info + 6 * (size_t)k);
 }
 
 // ----------------------------------------------------------------------------------- launchers

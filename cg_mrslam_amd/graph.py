@@ -751,6 +751,18 @@ class GraphSLAM:
         out = self.ctx.marginals_joint(*a, vertices, **kw)
         return out[0] if stats else out
 
+    def condensedTree(self, vertices, gauge, robust: bool = False):     # noqa: N802 (g2o spelling)
+        """The condensed graph over the given vertex indices as a spanning tree of relative poses rooted at ``gauge``
+        (Context.condense_tree on the level-0 edges at the current estimates): ``(from_ids, to_ids, est [n, 3], info_upper
+        [n, 6], weight [n], flags [n])``, the edges by vertex id -- what a peer receives as ordinary EdgeSE2.  ``robust`` as for
+        computeMarginals.  A typed graph raises ValueError: condensed graphs are pose-only."""
+        a, kw, _ = self._joint_args(robust)
+        if "vertex_kind" in kw:
+            raise ValueError("condensedTree: pose graphs only (the graph has landmarks or priors)")
+        fr, to, est, iu, w, fl = self.ctx.condense_tree(a[0], *a[2:], int(gauge), vertices, **kw)[:6]
+        ids = np.asarray(self.graph.ids)
+        return ids[fr], ids[to], est, iu, w, fl
+
     def relativeCovariance(self, pairs, hypotheses=None, robust: bool = False):     # noqa: N802 (g2o spelling)
         """For the vertex index pairs ``(a, b)``: ``(z [n, 3], Sigma_z [n, 3, 3])``, z = x_a^-1 x_b and its covariance, without
         re-gauging the graph per pair.  ``hypotheses`` = ``(meas [n, 3], info_upper [n, 6] or None)``: a candidate measurement

@@ -1024,6 +1024,48 @@ int cgmr_joint_compatibility(cgmr_ctx* ctx, int nV, const double* poses_xyt, con
                              int32_t* dof_out, int32_t* proven_out, int64_t* nodes_out, const cgmr_factor_types* types,
                              const cgmr_robust* rk);
 
+/* Condensed graphs as spanning trees of relative poses (present in C ABI version 105 libraries that export these symbols).
+ *
+ * cgmr_condense labels a star gauge -> v from Sigma_vv alone, as CondensedGraphCreator::compute does, and drops every
+ * cross-covariance between the requested vertices.  cgmr_condense_tree keeps the edge count, the edge type and the wire record
+ * and chooses which pairs the edges join: the nodes are the gauge (node 0) and the unique requested vertices other than the
+ * gauge (nodes 1 .. nq, in order of first appearance), every unordered pair (a, b) is a candidate edge of weight
+ *     w(a, b) = log det Sigma_z(a, b),
+ * Sigma_z the first-order covariance of z = x_a^-1 x_b, a < b, under the joint covariance of the two vertices
+ * (cgmr_relative_covariance's formula; Sigma_aa = Sigma_ab = 0 for the gauge), at the estimates after the completed iteration,
+ * the determinant from a 3x3 Cholesky factor; a pivot that is not positive and finite, or a NaN, gives +inf, and so does every
+ * pair of a requested vertex that no edge touches (it has no covariance: it is not known exactly, it is not known).  The condensed
+ * graph is the minimum spanning tree under the total order (w, max(a, b), min(a, b)), compared lexicographically -- unique
+ * whichever algorithm finds it -- rooted at the gauge: one edge per node 1 .. nq, in node order, from = the node's parent, to =
+ * the node.  On a chain of odometry edges the tree is the chain and its labels are the odometry's, whichever vertex is the gauge.
+ *
+ *   the pass: cgmr_condense's (the gauge alone fixed, the spanning-tree guess, one iteration solved and applied), then the
+ *   forward solve and every lower Gram tile of cgmr_marginals_joint over the nq vertices (their device memory: as there).
+ *   est_out [3 nq]: x_parent^-1 x_child at the estimates after the iteration.  info_upper_out [6 nq]: g2o's EdgeLabeler -- a
+ *   parent that is the gauge: cgmr_condense's labelling (7 sigma points of Sigma_cc); otherwise sampleUnscented at dimension 6
+ *   (alpha 1e-3, beta 2, lambda = alpha^2 6): 13 sigma points of [Sigma_pp Sigma_pc; Sigma_cp Sigma_cc], each applied to both
+ *   vertices by the additive (x, y, theta) update, the edge error in the measurement's frame, weighted mean and covariance, 3x3
+ *   inverse.
+ *   from_out / to_out [nq]: vertex indices.  weight_out [nq] (nullable): the chosen edge's w.  flags_out [nq] (nullable): 0, 1
+ *   (no Cholesky factor: identity information, as cgmr_condense leaves it), 2 (every weight of the node was +inf: it hangs on
+ *   the gauge, identity information).
+ *   rk: as cgmr_condense_robust (null: the plain call).
+ * Returns the edge count nq (0 with no requested vertex besides the gauge, or no free vertex), or a negative code:
+ * CGMR_E_INVALID before anything is queued for a null required pointer, an index out of range, or more than
+ * CGMR_TREE_MAX_NODES nodes (the weight matrix: 8 n^2 bytes, 8.4 MB at the limit); otherwise as cgmr_condense.
+ * Pose graphs only.  Deterministic: no atomics, two calls give identical bytes.
+ *
+ * cgmr_min_spanning_tree: the combinatorial half on a caller's dense symmetric matrix weights [n * n] (host, row-major; only
+ * the lower triangle is read, a NaN counts as +inf): parent_out [n] of the tree of the same total order rooted at `root`,
+ * parent_out[root] = -1.  CGMR_E_INVALID for n < 1, n > CGMR_TREE_MAX_NODES or a root outside [0, n).  In profiling mode its
+ * one launch is counted in class 11 of cgmr_gn_kernel_times_ex. */
+#define CGMR_TREE_MAX_NODES 1025
+int cgmr_condense_tree(cgmr_ctx* ctx, int nV, const double* poses_xyt, int nE, const int32_t* from_idx, const int32_t* to_idx,
+                       const double* meas_xyt, const double* info_upper, int gauge_idx, int nK, const int32_t* query_idx,
+                       int32_t* from_out, int32_t* to_out, double* est_out, double* info_upper_out, double* weight_out,
+                       int32_t* flags_out, const cgmr_robust* rk);
+int cgmr_min_spanning_tree(cgmr_ctx* ctx, int n, const double* weights, int root, int32_t* parent_out);
+
 /* ------------------------------------------------------------------------------------------
  * Generic correlative search (loop-closure / hierarchical / global matching).
  *

@@ -59,9 +59,11 @@ _SYMBOLS = [
     "cgmr_match_close_vset_batch_dev", "cgmr_scan_transforms",
     "cgmr_jcbb_dense", "cgmr_joint_compatibility",
     "cgmr_condense_tree", "cgmr_min_spanning_tree",
+    "cgmr_remove_nodes",
 ]
 
 JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)
+REMOVE_MAX_DEGREE = 16        # include/cgmr.h: CGMR_REMOVE_MAX_DEGREE (distinct neighbours of a vertex remove_nodes takes out)
 TREE_MAX_NODES = 1025         # include/cgmr.h: CGMR_TREE_MAX_NODES (the gauge and the unique requested vertices of a condense_tree call)
 PCM_MAX_CLOSURES = 1024       # include/cgmr.h: CGMR_PCM_MAX_CLOSURES (candidates of a consistency call, vertices of a clique call)
 EXACT_DEFAULT_NODE_LIMIT = 512    # include/cgmr.h: CGMR_EXACT_DEFAULT_NODE_LIMIT (nodes per root and round of the exact clique search)
@@ -901,6 +903,38 @@ class Context:
         parent = np.full(n, -1, dtype=np.int32)
         self._check(self.lib.cgmr_min_spanning_tree(self.h, C.c_int(n), _ptr(W), C.c_int(int(root)), _ptr(parent)))
         return parent
+
+    # vertex removal (include/cgmr.h: cgmr_remove_nodes)
+    def remove_nodes(self, ef, et, meas, info, remove, num_vertices=None):
+        """What replaces the edges of each vertex of ``remove`` (an independent set of a pose-only graph) once it is gone: the
+        vertex marginalised out of the star of its incident edges, and a minimum spanning tree of log det Sigma_z over its
+        neighbours, rooted at the lowest, with first-order labels.  Estimates are not an input.  Returns ``(off [nR + 1],
+        from [n], to [n], meas [n, 3], info_upper [n, 6], weight [n], flags [nR])``: the edges of ``remove[r]`` are
+        off[r] .. off[r + 1] - 1; flags 0 removed, 1 no Cholesky factor, 2 more than REMOVE_MAX_DEGREE neighbours, 3 a tree
+        edge without a finite weight -- a vertex flagged 1, 2 or 3 stays and gets no edges.  ``num_vertices``: default, the
+        largest index used + 1.  Deterministic."""
+        ef, et = np.ascontiguousarray(ef, dtype=np.int32).reshape(-1), np.ascontiguousarray(et, dtype=np.int32).reshape(-1)
+        meas, info = np.ascontiguousarray(meas, dtype=np.float64), np.ascontiguousarray(info, dtype=np.float64)
+        remove = np.ascontiguousarray(remove, dtype=np.int32).reshape(-1)
+        nE, nR = len(ef), len(remove)
+        if len(et) != nE or meas.size != 3 * nE or info.size != 6 * nE:
+            raise ValueError("remove_nodes: ef, et [nE], meas [nE, 3], info [nE, 6]")
+        if num_vertices is None:
+            num_vertices = 1 + max([0] + [int(a.max()) for a in (ef, et, remove) if len(a)])
+        # every removed vertex' degree is at most its count of incident edges
+        cnt = np.bincount(np.concatenate([ef, et]).clip(0), minlength=1)
+        ok = remove[(remove >= 0) & (remove < len(cnt))]
+        cap = int(np.maximum(np.minimum(cnt[ok], REMOVE_MAX_DEGREE) - 1, 0).sum())
+        n = max(cap, 1)
+        off, fl = np.zeros(nR + 1, dtype=np.int32), np.zeros(max(nR, 1), dtype=np.int32)
+        fr, to = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        z, iu, wt = np.zeros((n, 3)), np.zeros((n, 6)), np.zeros(n)
+        rc = self.lib.cgmr_remove_nodes(self.h, C.c_int(int(num_vertices)), C.c_int(nE), _ptr(ef), _ptr(et), _ptr(meas), _ptr(info),
+                                        C.c_int(nR), _ptr(remove), C.c_int(cap), _ptr(off), _ptr(fr), _ptr(to), _ptr(z), _ptr(iu),
+                                        _ptr(wt), _ptr(fl))
+        if rc < 0:
+            self._check(rc)
+        return (off,) + tuple(a[:rc].copy() for a in (fr, to, z, iu, wt)) + (fl[:nR].copy(),)
 
     # joint and pairwise blocks of H^-1, relative-pose uncertainty (include/cgmr.h: cgmr_marginals_joint ...).  ``kind`` None: the
     # plain call; otherwise robust kernels as marginals_robust takes them, and (e2 [nE], weights [nE]) are appended.

@@ -866,6 +866,14 @@ int cgmr_min_spanning_tree(cgmr_ctx* ctx, int n, const double* weights, int root
   return mst_driver(ctx, n, weights, root, parent_out);
 }
 
+int cgmr_remove_nodes(cgmr_ctx* ctx, int nV, int nE, const int32_t* ef, const int32_t* et, const double* meas, const double* info, int nR,
+                      const int32_t* remove, int cap_out, int32_t* off_out, int32_t* from_out, int32_t* to_out, double* meas_out,
+                      double* info_out, double* weight_out, int32_t* flags_out) {
+  if (!ctx) return CGMR_E_INVALID;
+  return remove_nodes_driver(ctx, nV, nE, ef, et, meas, info, nR, remove, cap_out, off_out, from_out, to_out, meas_out, info_out,
+                             weight_out, flags_out);
+}
+
 int cgmr_set_symbolic_cache(cgmr_ctx* ctx, int on) {
   if (!ctx) return CGMR_E_INVALID;
   ctx->sym_cache_on = on != 0;

@@ -65,6 +65,11 @@ int clique_driver(cgmr_ctx* ctx, int n, const uint64_t* adj, int32_t* clique_out
 int condense_tree_driver(cgmr_ctx* ctx, const HostCall& c, int gauge, int nK, const int32_t* query, int32_t* from_out,
                          int32_t* to_out, double* est_out, double* info_out, double* weight_out, int32_t* flags_out);
 int mst_driver(cgmr_ctx* ctx, int n, const double* weights, int root, int32_t* parent_out);
+// Vertex removal (remove_nodes_host.cpp; include/cgmr.h: cgmr_remove_nodes): every check, the CSR of incident edges, one launch on
+// the context's stream (in profiling mode in class 11, with the other spanning-tree launches), the packed result
+int remove_nodes_driver(cgmr_ctx* ctx, int nV, int nE, const int32_t* ef, const int32_t* et, const double* meas, const double* info,
+                        int nR, const int32_t* remove, int cap_out, int32_t* off_out, int32_t* from_out, int32_t* to_out,
+                        double* meas_out, double* info_out, double* weight_out, int32_t* flags_out);
 // Joint-compatibility data association (jcbb_host.cpp; include/cgmr.h: cgmr_jcbb_dense, cgmr_joint_compatibility).  The
 // outputs of both: ic [nM * nL] and nodes nullable, the others required; assign holds positions among the candidates
 // (jc_dense_driver) or their vertex indices (jc_driver).

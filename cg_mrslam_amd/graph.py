@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import CGMR_E_CHOLESKY_BASE, DL_DEFAULTS, Context, dl_params_checked, robust_arrays, robust_code
+from ._lib import CGMR_E_CHOLESKY_BASE, DL_DEFAULTS, REMOVE_MAX_DEGREE, Context, dl_params_checked, robust_arrays, robust_code
 
 ODOM_INFO = (100.0, 100.0, 1000.0)      # _odominf, src/slam/graph_slam.cpp:72-73
 SM_INFO = (1000.0, 1000.0, 10000.0)     # _SMinf,   src/slam/graph_slam.cpp:75-76
@@ -762,6 +762,91 @@ class GraphSLAM:
         fr, to, est, iu, w, fl = self.ctx.condense_tree(a[0], *a[2:], int(gauge), vertices, **kw)[:6]
         ids = np.asarray(self.graph.ids)
         return ids[fr], ids[to], est, iu, w, fl
+
+    def removeVertices(self, indices, max_degree: int = REMOVE_MAX_DEGREE):     # noqa: N802
+        """Take the vertices ``indices`` out of the graph: each is marginalised out of the star of its level-0 edges and the
+        star replaced by a spanning tree of relative-pose edges over its neighbours (Context.remove_nodes; the estimates are
+        not an input).  The vertices and their edges are deleted, the new edges appended at level 0 without a robust kernel,
+        and ``ids``, ``poses``, ``fixed``, ``lasers`` and the robust-kernel arrays compacted.
+
+        One device call removes an independent set.  A request that is not one is worked off in rounds: each round takes, in
+        index order, the requested vertices not adjacent in the *current* graph to one already taken this round, and its new
+        edges join the graph before the next round -- so the result depends on this order.  A vertex with more than
+        ``max_degree`` (at most 16) distinct neighbours when its round comes, or whose local system has no Cholesky factor,
+        stays in the graph with its edges.
+
+        Returns ``(index_map [old nV], new_edges, skipped)``: the new index of every old vertex (-1: removed), the indices of
+        the new edges in the rewritten graph, and ``[(old vertex index, flag), ...]`` of the vertices left in place (flags as
+        Context.remove_nodes).  Raises ValueError for an index out of range, a fixed vertex, a typed graph, a graph with
+        mixtures, a vertex touched by an edge of another level, or a ``max_degree`` outside 1..16."""
+        g = self.graph
+        if g.typed:
+            raise ValueError("removeVertices: pose graphs only (the graph has landmarks or priors)")
+        if g.has_mixtures:
+            raise ValueError("removeVertices: a graph with mixture edges (collapseMixtures first)")
+        if not 1 <= int(max_degree) <= REMOVE_MAX_DEGREE:
+            raise ValueError(f"removeVertices: max_degree must be 1..{REMOVE_MAX_DEGREE}")
+        nV = g.n_vertices
+        left = sorted(set(int(v) for v in np.asarray(indices, dtype=np.int64).reshape(-1)))
+        if left and (left[0] < 0 or left[-1] >= nV):
+            raise ValueError(f"removeVertices: vertex index out of range 0..{nV - 1}")
+        if g.fixed[left].any():
+            raise ValueError("removeVertices: a fixed vertex cannot be removed")
+        other = g.edge_level != 0
+        if np.isin(g.edge_from[other], left).any() or np.isin(g.edge_to[other], left).any():
+            raise ValueError("removeVertices: a vertex is touched by an edge of another level")
+        orig = np.flatnonzero(~other)                              # the level-0 edges at work: their old index, -1 for a new one
+        ef, et, meas, info = (a.copy() for a in g.level0())
+        skipped, removed = [], []
+        while left:
+            adj = {}
+            for a, b in zip(ef.tolist(), et.tolist()):
+                adj.setdefault(a, set()).add(b)
+                adj.setdefault(b, set()).add(a)
+            take, blocked = [], set()
+            for v in left:
+                if v not in blocked:
+                    take.append(v)
+                    blocked |= adj.get(v, set())
+            call = [v for v in take if len(adj.get(v, ())) <= int(max_degree)]
+            skipped += [(v, 2) for v in take if len(adj.get(v, ())) > int(max_degree)]
+            _, fr, to, z, iu, _, fl = self.ctx.remove_nodes(ef, et, meas, info, call, num_vertices=nV)
+            gone = [v for v, f in zip(call, fl) if f == 0]
+            removed += gone
+            skipped += [(v, int(f)) for v, f in zip(call, fl) if f != 0]
+            keep = ~(np.isin(ef, gone) | np.isin(et, gone))
+            ef, et = np.concatenate([ef[keep], fr]), np.concatenate([et[keep], to])
+            meas, info = np.vstack([meas[keep], z]), np.vstack([info[keep], iu])
+            orig = np.concatenate([orig[keep], np.full(len(fr), -1, dtype=orig.dtype)])
+            taken = set(take)
+            left = [v for v in left if v not in taken]
+        # the rewritten graph: the old edges that stay, in their order, then the new ones; the vertices compacted
+        stay_v = np.ones(nV, dtype=bool)
+        stay_v[removed] = False
+        index_map = np.full(nV, -1, dtype=np.int64)
+        index_map[stay_v] = np.arange(int(stay_v.sum()))
+        stay_e = other.copy()
+        stay_e[orig[orig >= 0]] = True
+        new = orig < 0
+        n_new = int(new.sum())
+        if self._rk_kind is not None:
+            self._grow_robust()
+            self._rk_kind = np.concatenate([self._rk_kind[stay_e], np.zeros(n_new, dtype=np.uint8)])
+            self._rk_delta = np.concatenate([self._rk_delta[stay_e], np.ones(n_new)])
+        if g.edge_kind is not None:
+            g.edge_kind = np.concatenate([g.edge_kind[stay_e], np.zeros(n_new, dtype=np.uint8)])
+        if g.vertex_kind is not None:
+            g.vertex_kind = g.vertex_kind[stay_v]
+        g.edge_from = np.concatenate([index_map[g.edge_from[stay_e]], index_map[ef[new]]]).astype(np.int32)
+        g.edge_to = np.concatenate([index_map[g.edge_to[stay_e]], index_map[et[new]]]).astype(np.int32)
+        g.meas = np.vstack([g.meas[stay_e], meas[new]])
+        g.info = np.vstack([g.info[stay_e], info[new]])
+        g.edge_level = np.concatenate([g.edge_level[stay_e], np.zeros(n_new, dtype=np.int32)])
+        g.ids, g.poses, g.fixed = g.ids[stay_v], g.poses[stay_v].copy(), g.fixed[stay_v]
+        g.lasers = {int(index_map[v]): l for v, l in g.lasers.items() if index_map[v] >= 0}
+        # what the last optimize() left per edge no longer fits the edge list
+        self.last_edge_chi2 = self.last_weights = self.last_selected = self._gnc_rejected = None
+        return index_map, np.arange(g.n_edges - n_new, g.n_edges), skipped
 
     def relativeCovariance(self, pairs, hypotheses=None, robust: bool = False):     # noqa: N802 (g2o spelling)
         """For the vertex index pairs ``(a, b)``: ``(z [n, 3], Sigma_z [n, 3, 3])``, z = x_a^-1 x_b and its covariance, without

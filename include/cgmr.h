@@ -1066,6 +1066,40 @@ int cgmr_condense_tree(cgmr_ctx* ctx, int nV, const double* poses_xyt, int nE, c
                        int32_t* flags_out, const cgmr_robust* rk);
 int cgmr_min_spanning_tree(cgmr_ctx* ctx, int n, const double* weights, int root, int32_t* parent_out);
 
+/* Vertex removal: marginalise vertices out of a pose graph into spanning trees of relative-pose edges (present in C ABI version
+ * 105 libraries that export this symbol).
+ *
+ * Every other entry point makes the graph grow or reads it.  cgmr_remove_nodes computes what replaces the edges of each vertex
+ * of remove_idx once the vertex is gone -- generic-linear-constraint node removal with a Chow-Liu-style tree -- from the edges
+ * incident to that vertex alone; estimates are not an input.  Pose graphs only (every edge an EdgeSE2 between two different
+ * poses).  For a removed vertex v with the distinct neighbours n_1 < .. < n_m (by vertex index; the nodes 1 .. m):
+ *   1. the local configuration: v at the identity, n at z_vn of the lowest-index edge between v and n, inverted where that edge
+ *      is stored n -> v: the exact optimum of the star of those edges.
+ *   2. H = sum J^T Omega J over all incident edges at that configuration, EdgeSE2's Jacobians with each measurement's own
+ *      rotation.  A parallel edge adds its term there; its residual against the first edge is dropped.
+ *   3. n_1 is fixed; the rest is factored by Cholesky, v first, and the trailing 3 (m - 1) block inverted: the covariance of
+ *      n_2 .. n_m with v marginalised out, zero blocks for n_1.
+ *   4. w(a, b) = log det Sigma_z(a, b) for every pair of nodes as in cgmr_condense_tree (a 3x3 Cholesky factor; a pivot that is
+ *      not positive and finite gives +inf).  Sigma_z does not depend on which neighbour is fixed.
+ *   5. the minimum spanning tree under cgmr_condense_tree's total order (w, max, min), rooted at n_1.
+ *   6. each tree edge parent -> child: meas = x_p^-1 x_c at the local configuration (= z_vp^-1 (+) z_vc), information =
+ *      (R(meas.theta)^T Sigma_z R(meas.theta))^-1, first order.  With two neighbours this is exactly the composed edge.
+ *   7. m - 1 new edges in order of the child's node; m = 0 or 1: none.
+ * flags_out [nR]: 0 removed; 1 H has no Cholesky factor; 2 more than CGMR_REMOVE_MAX_DEGREE distinct neighbours; 3 a tree
+ * edge's Sigma_z has no factor (its weight is +inf).  A vertex flagged 1, 2 or 3 is to be left in place and gets no edges.
+ * off_out [nR + 1]: the edges of remove_idx[r] are off_out[r] .. off_out[r + 1] - 1 of from_out / to_out (vertex indices),
+ * meas_out [3 per edge], info_upper_out [6 per edge] and weight_out (nullable: the edge's w).
+ * Returns the number of new edges (0 for nR == 0), or CGMR_E_INVALID, before anything is queued and with the reason in
+ * cgmr_last_error, for: a null required pointer (the edge outputs are required with cap_out > 0) or a negative count, an
+ * index out of range, a repeated remove_idx, a self edge on a removed vertex, two removed vertices joined by an edge (one call
+ * removes an independent set), cap_out smaller than the sum of max(m_v - 1, 0) over the vertices within the degree limit;
+ * CGMR_E_HIP / _ALLOC.  One launch on the context's stream, one 64-lane workgroup per vertex (in profiling mode counted in class
+ * 11 of cgmr_gn_kernel_times_ex).  Deterministic: no atomics, two calls give identical bytes. */
+#define CGMR_REMOVE_MAX_DEGREE 16
+int cgmr_remove_nodes(cgmr_ctx* ctx, int nV, int nE, const int32_t* from_idx, const int32_t* to_idx, const double* meas_xyt,
+                      const double* info_upper, int nR, const int32_t* remove_idx, int cap_out, int32_t* off_out, int32_t* from_out,
+                      int32_t* to_out, double* meas_out, double* info_upper_out, double* weight_out, int32_t* flags_out);
+
 /* ------------------------------------------------------------------------------------------
  * Generic correlative search (loop-closure / hierarchical / global matching).
  *

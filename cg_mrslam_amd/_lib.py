@@ -60,10 +60,12 @@ _SYMBOLS = [
     "cgmr_jcbb_dense", "cgmr_joint_compatibility",
     "cgmr_condense_tree", "cgmr_min_spanning_tree",
     "cgmr_remove_nodes",
+    "cgmr_scan_information", "cgmr_scan_prune", "cgmr_scan_info_last_stats",
 ]
 
 JOINT_MAX_QUERIES = 2048      # include/cgmr.h: CGMR_JOINT_MAX_QUERIES (unique query vertices of a joint / pairs call)
 REMOVE_MAX_DEGREE = 16        # include/cgmr.h: CGMR_REMOVE_MAX_DEGREE (distinct neighbours of a vertex remove_nodes takes out)
+SCAN_INFO_DEFAULT_SCRATCH = 1 << 30   # include/cgmr.h: CGMR_SCAN_INFO_DEFAULT_SCRATCH (bytes of scan windows alive at one time)
 TREE_MAX_NODES = 1025         # include/cgmr.h: CGMR_TREE_MAX_NODES (the gauge and the unique requested vertices of a condense_tree call)
 PCM_MAX_CLOSURES = 1024       # include/cgmr.h: CGMR_PCM_MAX_CLOSURES (candidates of a consistency call, vertices of a clique call)
 EXACT_DEFAULT_NODE_LIMIT = 512    # include/cgmr.h: CGMR_EXACT_DEFAULT_NODE_LIMIT (nodes per root and round of the exact clique search)
@@ -935,6 +937,64 @@ class Context:
         if rc < 0:
             self._check(rc)
         return (off,) + tuple(a[:rc].copy() for a in (fr, to, z, iu, wt)) + (fl[:nR].copy(),)
+
+    # scan ranking and greedy pruning (include/cgmr.h: cgmr_scan_information, cgmr_scan_prune)
+    @staticmethod
+    def _scan_args(cfg, ranges, robot_poses):
+        ranges = np.ascontiguousarray(ranges, dtype=np.float32)
+        poses = np.ascontiguousarray(robot_poses, dtype=np.float64).reshape(-1, 3)
+        if ranges.ndim != 2 or ranges.shape[0] != poses.shape[0]:
+            raise ValueError("ranges [n_scans, n_beams], robot_poses [n_scans, 3]")
+        return ranges, poses, (int(cfg.rows), int(cfg.cols))
+
+    def scan_information(self, cfg, ranges, robot_poses, scratch_bytes_limit=0):
+        """What every scan tells the occupancy map of all of them (``cfg``: an occupancy.OccupancyConfig as cgmr_occupancy_map
+        takes it).  Returns a dict: ``delta`` [n] the entropy, in nats, the map gains if the scan is dropped; ``cells`` [n] the
+        cells the scan touches; ``hit_sum`` / ``miss_sum`` [n] int64; ``hits`` / ``misses`` [rows, cols] the totals;
+        ``map_entropy``; ``kernel_seconds``.  ``scratch_bytes_limit``: the bytes of scan windows alive at one time (0: the
+        library's default); the result does not depend on it."""
+        ranges, poses, shape = self._scan_args(cfg, ranges, robot_poses)
+        n = ranges.shape[0]
+        out = dict(delta=np.zeros(n), cells=np.zeros(n, dtype=np.int32), hit_sum=np.zeros(n, dtype=np.int64),
+                   miss_sum=np.zeros(n, dtype=np.int64), hits=np.zeros(shape, dtype=np.int32), misses=np.zeros(shape, dtype=np.int32))
+        ent, ks = C.c_double(), C.c_double()
+        rc = self.lib.cgmr_scan_information(self.h, C.byref(cfg), C.c_int(n), C.c_int(ranges.shape[1]), _ptr(ranges), _ptr(poses),
+                                            C.c_int64(int(scratch_bytes_limit)), _ptr(out["delta"]), _ptr(out["cells"]),
+                                            _ptr(out["hit_sum"]), _ptr(out["miss_sum"]), _ptr(out["hits"]), _ptr(out["misses"]),
+                                            C.byref(ent), C.byref(ks))
+        self._check(rc)
+        out.update(map_entropy=ent.value, kernel_seconds=ks.value)
+        return out
+
+    def scan_prune(self, cfg, ranges, robot_poses, max_remove, max_entropy_increase=-1.0, protected=None, scratch_bytes_limit=0):
+        """Greedy pruning: scans are taken one at a time, each time the unprotected one whose loss raises the map's entropy
+        least (ties: the lower index), until ``max_remove`` are gone, none is left, or -- ``max_entropy_increase`` >= 0 -- the
+        sum of the taken deltas would exceed it.  Returns a dict: ``order`` [k] the scans in the order taken, ``delta`` [k];
+        ``entropy_before`` / ``entropy_after``; ``hits`` / ``misses`` the totals of the kept scans; ``kernel_seconds``."""
+        ranges, poses, shape = self._scan_args(cfg, ranges, robot_poses)
+        n = ranges.shape[0]
+        prot = None
+        if protected is not None:
+            prot = np.ascontiguousarray(np.asarray(protected).astype(bool), dtype=np.uint8).reshape(-1)
+            if len(prot) != n:
+                raise ValueError("protected: one flag per scan")
+        cap = max(min(int(max_remove), n), 1)
+        order, delta = np.zeros(cap, dtype=np.int32), np.zeros(cap)
+        hits, misses = np.zeros(shape, dtype=np.int32), np.zeros(shape, dtype=np.int32)
+        k, before, after, ks = C.c_int32(), C.c_double(), C.c_double(), C.c_double()
+        rc = self.lib.cgmr_scan_prune(self.h, C.byref(cfg), C.c_int(n), C.c_int(ranges.shape[1]), _ptr(ranges), _ptr(poses), _ptr(prot),
+                                      C.c_int(int(max_remove)), C.c_double(float(max_entropy_increase)),
+                                      C.c_int64(int(scratch_bytes_limit)), _ptr(order), _ptr(delta), C.byref(k), C.byref(before),
+                                      C.byref(after), _ptr(hits), _ptr(misses), C.byref(ks))
+        self._check(rc)
+        return dict(order=order[:k.value].copy(), delta=delta[:k.value].copy(), entropy_before=before.value, entropy_after=after.value,
+                    hits=hits, misses=misses, kernel_seconds=ks.value)
+
+    def scan_info_last_stats(self):
+        """(bytes of all scan windows, chunks, largest window in bytes, greedy rounds queued) of the last ranking / pruning call."""
+        out = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.cgmr_scan_info_last_stats(self.h, _ptr(out)))
+        return tuple(int(v) for v in out)
 
     # joint and pairwise blocks of H^-1, relative-pose uncertainty (include/cgmr.h: cgmr_marginals_joint ...).  ``kind`` None: the
     # plain call; otherwise robust kernels as marginals_robust takes them, and (e2 [nE], weights [nE]) are appended.

@@ -47,6 +47,7 @@ struct cgmr_ctx {
   int64_t dl_stats[3] = {0, 0, 0};   // last dogleg call: host waits, trials, factorisations
   cgmr::Arena gnc_arena;    // cgmr_gnc_optimize*: the GNC state, its records, the saved poses, the per-edge arrays (gnc_kernels.hip)
   int64_t gnc_stats[2] = {0, 0};     // last GNC call: host waits, inner iterations run
+  int64_t si_stats[4] = {0, 0, 0, 0};   // last scan ranking / pruning call: window bytes, chunks, largest window, rounds queued
   // What the device needs of the analysis BEFORE the borders / maps are done (vperm, the edge list, the off-diagonal blocks'
   // rows / columns / column starts) and what it makes of it underneath the rest of the analysis: the assembly lists
   // (gn_structure.hip).  Own arena and own pinned staging block: the structure blob's are sized at the END of the analysis.

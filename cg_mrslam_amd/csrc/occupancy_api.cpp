@@ -5,6 +5,7 @@
 
 #include "cgmr_ctx.h"
 #include "occupancy_device.h"
+#include "occupancy_host.h"
 
 using namespace cgmr;
 
@@ -19,32 +20,16 @@ struct Layout {
   size_t off = 0;
   size_t add(size_t bytes) { off = (off + 255) & ~size_t(255); size_t o = off; off += bytes; return o; }
 };
-double normalize_theta(double t) {            // g2o::normalize_theta [g2o-recalled], as everywhere in this library
-  const double pi = 3.14159265358979323846;
-  if (t >= -pi && t < pi) return t;
-  double m = std::floor((t + pi) / (2 * pi));
-  return t - 2 * pi * m;
-}
 }  // namespace
 
 extern "C" int cgmr_occupancy_map(cgmr_ctx* ctx, const cgmr_occupancy_config* cfg, int n_scans, int n_beams,
                                   const float* ranges, const double* robot_poses_xyt, int32_t* hits_out,
                                   int32_t* misses_out, uint8_t* image_out, double* kernel_seconds_out) {
   if (!ctx) return CGMR_E_INVALID;
-  // n_beams >= 1: the beam threads of a scan also carry its fillRobotPose cells (a scan without beams is not a scan)
-  if (!cfg || n_scans < 0 || n_beams < 1 || cfg->rows <= 0 || cfg->cols <= 0 || !(cfg->resolution > 0) ||
-      (n_scans > 0 && n_beams > 0 && (!ranges || !robot_poses_xyt)) || cfg->square_size < 0)
+  if (!occ_args_ok(cfg, n_scans, n_beams, ranges, robot_poses_xyt))
     return set_err(ctx, CGMR_E_INVALID, "cgmr_occupancy_map: bad argument");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  OccParams P;
-  memset(&P, 0, sizeof P);
-  P.rows = cfg->rows; P.cols = cfg->cols;
-  P.resolution = cfg->resolution; P.off_x = cfg->offset_x; P.off_y = cfg->offset_y;
-  P.max_range = cfg->max_range < 0 ? (float)cfg->laser_max_range : cfg->max_range;        // frequency_map.cpp:29-30
-  P.usable_range = cfg->usable_range < 0 ? P.max_range : cfg->usable_range;
-  P.infinity_filling_range = cfg->infinity_filling_range;
-  P.gain = cfg->gain; P.square_size = cfg->square_size;
-  P.n_scans = n_scans; P.n_beams = n_beams;
+  const OccParams P = occ_params(cfg, n_scans, n_beams);
   const size_t ncells = (size_t)P.rows * P.cols;
   Layout L;
   size_t o_scans = L.add(sizeof(OccScan) * (size_t)std::max(n_scans, 1)), o_cs = L.add(sizeof(float2) * (size_t)std::max(n_beams, 1));
@@ -55,23 +40,8 @@ extern "C" int cgmr_occupancy_map(cgmr_ctx* ctx, const cgmr_occupancy_config* cf
   if (rc) return rc;
   rc = pinned_reserve(ctx, hbytes);
   if (rc) return rc;
-  // per scan: laserCenter = robotPose * laserPose (frequency_map.cpp:32), its rotation as cos / sin (Eigen Rotation2D)
-  OccScan* hs = reinterpret_cast<OccScan*>(ctx->pinned + o_scans);
-  for (int s = 0; s < n_scans; s++) {
-    const double* rp = robot_poses_xyt + 3 * (size_t)s;
-    const double cr = std::cos(rp[2]), sr = std::sin(rp[2]);
-    hs[s].lx = (cr * cfg->laser_pose[0] - sr * cfg->laser_pose[1]) + rp[0];
-    hs[s].ly = (sr * cfg->laser_pose[0] + cr * cfg->laser_pose[1]) + rp[1];
-    const double lt = normalize_theta(rp[2] + cfg->laser_pose[2]);
-    hs[s].cl = std::cos(lt); hs[s].sl = std::sin(lt);
-    hs[s].rx = rp[0]; hs[s].ry = rp[1];
-  }
-  // beam table: cosf / sinf of the float beam angle (frequency_map.cpp:50-51), host libm like the reference
-  float2* hb = reinterpret_cast<float2*>(ctx->pinned + o_cs);
-  for (int i = 0; i < n_beams; i++) {
-    const float a = (float)(cfg->first_beam_angle + i * cfg->angular_step);
-    hb[i] = make_float2(cosf(a), sinf(a));
-  }
+  occ_fill_scans(cfg, n_scans, robot_poses_xyt, reinterpret_cast<OccScan*>(ctx->pinned + o_scans));
+  occ_fill_beams(cfg, n_beams, reinterpret_cast<float2*>(ctx->pinned + o_cs));
   char* d = ctx->mt_arena.ptr;
   hipStream_t st = ctx->stream;
   HIP_TRY(ctx, hipMemcpyAsync(d, ctx->pinned, hbytes, hipMemcpyHostToDevice, st));

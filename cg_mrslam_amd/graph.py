@@ -848,6 +848,56 @@ class GraphSLAM:
         self.last_edge_chi2 = self.last_weights = self.last_selected = self._gnc_rejected = None
         return index_map, np.arange(g.n_edges - n_new, g.n_edges), skipped
 
+    def _laser_map(self, who, **map_kw):
+        """(vertex indices that carry a laser, in id order; the Graph2occupancy over them at the current estimates).  The scans
+        must share one laser: beam count, first beam angle, angular step, maximum range, mounting pose."""
+        from .occupancy import Graph2occupancy
+        g = self.graph
+        idx = np.array(sorted(g.lasers, key=lambda v: int(g.ids[v])), dtype=np.int64)
+        if len(idx) == 0:
+            raise ValueError(f"{who}: no vertex carries a laser scan")
+        first = g.lasers[int(idx[0])]
+        for v in idx[1:]:
+            l = g.lasers[int(v)]
+            if (len(l.ranges) != len(first.ranges) or (l.first_beam_angle, l.angular_step, l.max_range) !=
+                    (first.first_beam_angle, first.angular_step, first.max_range) or not np.array_equal(l.laser_pose, first.laser_pose)):
+                raise ValueError(f"{who}: the scans of vertices {int(idx[0])} and {int(v)} come from different lasers")
+        scans = np.stack([g.lasers[int(v)].ranges for v in idx])
+        occ = Graph2occupancy(self.ctx, g.poses[idx], scans, first.first_beam_angle, first.angular_step, first.max_range,
+                              laser_pose=first.laser_pose, fixed=g.fixed[idx], **map_kw)
+        return idx, occ
+
+    def scanInformation(self, **map_kw):     # noqa: N802
+        """``(vertex indices with a laser, dH [n])``: for every key frame the entropy, in nats, the occupancy map of all of them
+        gains if its scan is dropped (Graph2occupancy.scanInformation at the current estimates; ``map_kw``: Graph2occupancy's
+        keywords -- resolution, usableRange, ...).  The higher, the more the map owes to the scan."""
+        idx, occ = self._laser_map("scanInformation", **map_kw)
+        return idx, occ.scanInformation()["delta"]
+
+    def pruneScans(self, max_remove, max_entropy_increase: float = -1.0, keep=(), **map_kw):     # noqa: N802
+        """Choose up to ``max_remove`` key frames by what their scans tell the occupancy map and take them out of the graph.
+        The greedy selection (Graph2occupancy.pruneScans at the current estimates) drops, one at a time, the scan whose loss
+        raises the map's entropy least, while the sum of the increases stays within ``max_entropy_increase`` (negative: no
+        budget).  Fixed vertices and ``keep`` are never chosen; a vertex without a laser is not a candidate.  The chosen
+        vertices go to ``removeVertices``.
+
+        Returns ``(index_map, new_edges, skipped, order, delta)``: ``removeVertices``' result -- ``skipped`` lists the chosen
+        vertices it left in place, with their flags -- then the chosen vertices as old indices in the order chosen, and the
+        entropy increase of each.  Raises as ``removeVertices`` does (typed graphs, mixtures), before anything is selected."""
+        g = self.graph
+        if g.typed:
+            raise ValueError("pruneScans: pose graphs only (the graph has landmarks or priors)")
+        if g.has_mixtures:
+            raise ValueError("pruneScans: a graph with mixture edges (collapseMixtures first)")
+        idx, occ = self._laser_map("pruneScans", **map_kw)
+        keep = np.asarray(keep, dtype=np.int64).reshape(-1)
+        if len(keep) and (keep.min() < 0 or keep.max() >= g.n_vertices):
+            raise ValueError(f"pruneScans: keep: vertex index out of range 0..{g.n_vertices - 1}")
+        protected = np.asarray(g.fixed[idx]).astype(bool) | np.isin(idx, keep)
+        res = occ.pruneScans(max_remove, max_entropy_increase, protected)
+        order = idx[res["order"]]
+        return self.removeVertices(order) + (order, res["delta"])
+
     def relativeCovariance(self, pairs, hypotheses=None, robust: bool = False):     # noqa: N802 (g2o spelling)
         """For the vertex index pairs ``(a, b)``: ``(z [n, 3], Sigma_z [n, 3, 3])``, z = x_a^-1 x_b and its covariance, without
         re-gauging the graph per pair.  ``hypotheses`` = ``(meas [n, 3], info_upper [n, 6] or None)``: a candidate measurement

@@ -74,12 +74,8 @@ class Graph2occupancy:
         offset = (np.float32(xmin), np.float32(ymin))
         return tposes, size, offset
 
-    def computeMap(self):   # noqa: N802
-        if len(self.poses) == 0:
-            return False                                      # "No laser scans found ... quitting!"
-        tposes, size, offset = self.geometry()
-        if size[0] == 0 or size[1] == 0:
-            return False                                      # "Zero map size ... quitting!"
+    def config(self, size, offset):
+        """The cgmr_occupancy_config of this map for the result of ``geometry()``."""
         cfg = OccupancyConfig()
         cfg.resolution, cfg.offset_x, cfg.offset_y = float(self.resolution), float(offset[0]), float(offset[1])
         cfg.rows, cfg.cols = size
@@ -90,6 +86,36 @@ class Graph2occupancy:
         for k in range(3):
             cfg.laser_pose[k] = self.laser_pose[k]
         cfg.threshold, cfg.free_threshold = float(self.threshold), float(self.free_threshold)
+        return cfg
+
+    def _ranking_inputs(self, who):
+        if len(self.poses) == 0:
+            raise ValueError(f"{who}: no laser scans")
+        tposes, size, offset = self.geometry()
+        if size[0] == 0 or size[1] == 0:
+            raise ValueError(f"{who}: zero map size")
+        return self.config(size, offset), np.ascontiguousarray(tposes)
+
+    def scanInformation(self, scratch_bytes_limit=0):   # noqa: N802
+        """What every scan tells the map, on the same ``geometry()`` as ``computeMap`` (same poses, offset and size):
+        Context.scan_information's dict -- ``delta`` [K], the entropy in nats the map gains if the scan is dropped, the counts
+        and the totals."""
+        cfg, tposes = self._ranking_inputs("scanInformation")
+        return self.ctx.scan_information(cfg, self.scans, tposes, scratch_bytes_limit)
+
+    def pruneScans(self, max_remove, max_entropy_increase=-1.0, protected=None, scratch_bytes_limit=0):   # noqa: N802
+        """Greedy selection of the scans to drop (Context.scan_prune's dict), on the same ``geometry()`` as ``computeMap`` with
+        all scans: the map keeps its size and offset.  ``protected``: a flag per scan; a protected scan is never taken."""
+        cfg, tposes = self._ranking_inputs("pruneScans")
+        return self.ctx.scan_prune(cfg, self.scans, tposes, max_remove, max_entropy_increase, protected, scratch_bytes_limit)
+
+    def computeMap(self):   # noqa: N802
+        if len(self.poses) == 0:
+            return False                                      # "No laser scans found ... quitting!"
+        tposes, size, offset = self.geometry()
+        if size[0] == 0 or size[1] == 0:
+            return False                                      # "Zero map size ... quitting!"
+        cfg = self.config(size, offset)
         K, B = self.scans.shape
         hits = np.zeros(size, dtype=np.int32)
         misses = np.zeros(size, dtype=np.int32)

@@ -1691,6 +1691,60 @@ int cgmr_occupancy_map(cgmr_ctx* ctx, const cgmr_occupancy_config* cfg, int n_sc
                        const double* robot_poses_xyt, int32_t* hits_out, int32_t* misses_out, uint8_t* image_out,
                        double* kernel_seconds_out);
 
+/* ------------------------------------------------------------------ scan ranking and greedy pruning
+ * Which key frames is the map worth keeping for?  After Kretzschmar and Stachniss, "Information-theoretic compression of pose
+ * graphs for laser-based SLAM": a scan is worth what it tells the occupancy map, and scans are discarded greedily, each time
+ * the one whose loss raises the map's entropy least.  Everything is over the FrequencyMap counters exactly as
+ * cgmr_occupancy_map produces them (same cfg, same arguments, the same ray walk on the device).
+ *
+ *   cell entropy      f(h, m) = -p ln p - (1 - p) ln(1 - p), p = (h + 1) / (h + m + 2), in nats and in double: the Bernoulli
+ *                     entropy of the posterior mean under a uniform prior; f(0, 0) = ln 2
+ *   map entropy       H(T) = sum over all rows * cols cells of f(H_c, M_c), T the totals of all scans
+ *   a scan's counts   (h_s,c, m_s,c): what integrateScan + fillRobotPose of scan s alone adds to cell c
+ *   information       dH_s(T) = sum over the cells with h_s,c + m_s,c > 0 of f(H_c - h_s,c, M_c - m_s,c) - f(H_c, M_c): the
+ *                     entropy the map gains if s is dropped; negative for a scan that contradicts the others
+ *   greedy pruning    all scans alive, T their sum; each round takes, among the alive scans with protected[s] == 0, the
+ *                     minimum of dH_s(T) under the total order (dH, s) -- unless max_remove scans are gone, there is no
+ *                     candidate, or max_entropy_increase >= 0 and the sum of the taken deltas plus this one exceeds it: then
+ *                     the loop stops before taking it.  Taking: order[k] = s, delta[k] = dH_s, T loses the scan's counts.
+ *
+ * cgmr_scan_information: for every scan dH_s against the totals of all (delta_out [n_scans]), the cells it touches (cells_out
+ * [n_scans] int32), the sums of its hits and misses (hit_sum_out, miss_sum_out [n_scans] int64), the totals (hits_out,
+ * misses_out [rows * cols], equal to cgmr_occupancy_map's) and H(T) (map_entropy_out).  Every output is nullable.
+ * n_scans == 0: CGMR_OK, zero totals, map_entropy = rows * cols * ln 2.
+ *
+ * cgmr_scan_prune: the greedy loop, resident on the device (per round: the dH pass, one workgroup that picks and applies the
+ * stop rules, the subtraction; all rounds queued at once, one wait).  protected_or_null [n_scans] uint8; order_out, delta_out
+ * [min(max_remove, n_scans)], the first *n_removed_out written; entropy_before_out = H(all scans), entropy_after_out = H of the
+ * final totals, recomputed from them; hits_out / misses_out the final totals: bit for bit cgmr_occupancy_map over the kept
+ * scans.  n_removed_out is required, order_out and delta_out when min(max_remove, n_scans) > 0; the rest is nullable.
+ *
+ * Scratch.  Every scan counts into a window of its own: the bounding box of the map cells its walk visits, 8 bytes a cell.  A
+ * pre-pass finds the boxes (one read-back).  scratch_bytes_limit bounds the windows that exist at one time; 0 means
+ * CGMR_SCAN_INFO_DEFAULT_SCRATCH.  cgmr_scan_information works through the scans in chunks of consecutive scans (each chunk
+ * filled, in scan order, until the next window would not fit); the result does not depend on the chunks.  cgmr_scan_prune needs
+ * all windows at once and returns CGMR_E_ALLOC, with the bytes needed in cgmr_last_error, when they do not fit -- after the
+ * pre-pass, before anything of the selection is queued and with every output untouched.  So does either call when one window
+ * alone exceeds the limit.  cgmr_scan_info_last_stats: out[0] the bytes of all windows of the last successful call on this
+ * context, out[1] its chunks, out[2] its largest window in bytes, out[3] the greedy rounds it queued.
+ *
+ * CGMR_E_INVALID, before anything is queued and with the outputs untouched: what cgmr_occupancy_map refuses, gain < 0,
+ * scratch_bytes_limit < 0, max_remove < 0, a NaN max_entropy_increase, a required pointer that is null.  Deterministic: the
+ * counts are integer sums, every floating-point sum has a fixed order that depends on a cell's place in its window only, and
+ * there are no floating-point atomics -- two calls give identical bytes, two identical scans identical dH (the lower index is
+ * taken first).  kernel_seconds_out: HIP-event time of the pre-pass plus everything queued after it. */
+#define CGMR_SCAN_INFO_DEFAULT_SCRATCH ((int64_t)1 << 30)
+int cgmr_scan_information(cgmr_ctx* ctx, const cgmr_occupancy_config* cfg, int n_scans, int n_beams, const float* ranges,
+                          const double* robot_poses_xyt, int64_t scratch_bytes_limit, double* delta_out, int32_t* cells_out,
+                          int64_t* hit_sum_out, int64_t* miss_sum_out, int32_t* hits_out, int32_t* misses_out,
+                          double* map_entropy_out, double* kernel_seconds_out);
+int cgmr_scan_prune(cgmr_ctx* ctx, const cgmr_occupancy_config* cfg, int n_scans, int n_beams, const float* ranges,
+                    const double* robot_poses_xyt, const uint8_t* protected_or_null, int max_remove, double max_entropy_increase,
+                    int64_t scratch_bytes_limit, int32_t* order_out, double* delta_out, int32_t* n_removed_out,
+                    double* entropy_before_out, double* entropy_after_out, int32_t* hits_out, int32_t* misses_out,
+                    double* kernel_seconds_out);
+int cgmr_scan_info_last_stats(const cgmr_ctx* ctx, int64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

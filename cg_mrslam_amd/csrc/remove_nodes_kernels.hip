@@ -244,14 +244,18 @@ __global__ __launch_bounds__(64) void k_remove_nodes(RemoveNodes P) {
         for (int k = 0; k < 3; k++) u += T[3 * a + k] * Je[3 * b + k];
         C[3 * a + b] = u;
       }
-    // the inverse of the symmetrised C by its adjugate
+    // the inverse of the symmetrised C from its Cholesky factor, C = L L^T, Z = L^-1, C^-1 = Z^T Z: no cancelling cofactors
+    // (DESIGN.md 2.17).  C is a rotation of Sz, whose Cholesky factor the chosen weight has already taken.
     const double a = C[0], b = 0.5 * (C[1] + C[3]), cc = 0.5 * (C[2] + C[6]), e = C[4], f = 0.5 * (C[5] + C[7]), i = C[8];
-    const double det = a * (e * i - f * f) - b * (b * i - f * cc) + cc * (b * f - e * cc);
-    const double id = 1.0 / det;
+    const double l00 = sqrt(a), l10 = b / l00, l20 = cc / l00;
+    const double l11 = sqrt(e - l10 * l10), l21 = (f - l20 * l10) / l11;
+    const double l22 = sqrt(i - l20 * l20 - l21 * l21);
+    const double z00 = 1.0 / l00, z11 = 1.0 / l11, z22 = 1.0 / l22;
+    const double z10 = -l10 * z00 * z11, z21 = -l21 * z11 * z22, z20 = -(l20 * z00 + l21 * z10) * z22;
     const size_t o = (size_t)P.out_off[r] + (size_t)(lane - 1);
     double* iu = P.info_out + 6 * o;
-    iu[0] = (e * i - f * f) * id; iu[1] = (cc * f - b * i) * id; iu[2] = (b * f - cc * e) * id;
-    iu[3] = (a * i - cc * cc) * id; iu[4] = (cc * b - a * f) * id; iu[5] = (a * e - b * b) * id;
+    iu[0] = z00 * z00 + z10 * z10 + z20 * z20; iu[1] = z10 * z11 + z20 * z21; iu[2] = z20 * z22;
+    iu[3] = z11 * z11 + z21 * z21; iu[4] = z21 * z22; iu[5] = z22 * z22;
     P.est[3 * o] = z[0]; P.est[3 * o + 1] = z[1]; P.est[3 * o + 2] = z[2];
     P.parent[o] = par;
     P.weight[o] = key;
